@@ -2,7 +2,7 @@
 """bench.py -- headline benchmark: fused Winograd 3x3 conv + BN + ReLU, 256->256, 14x14, N=128.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--layer NAME] [--batch B]
-                    [--scaling weak|strong] [--preheat-ms MS] [--no-cpu-baseline]
+                    [--scaling weak|strong] [--preheat-ms MS] [--no-cpu-baseline] [--dump-outputs DIR]
 
 One "step" = one pass of the hot path (ONE launch of the fused HIP kernel through the
 C-ABI) over one batch of synthetic input that is already resident in HBM.  With N GPUs the
@@ -25,13 +25,19 @@ synchronise (wino_diag_last_clock) -- same binary, same burst, no probe launch. 
 clock_ghz = "cycles_per_launch", the number to compare across boxes.  The reference's protocol is
 the same idea: discard the first calls, average the rest (Test.c:14,45-53).
 
-Prints ONE JSON line (rank 0).  The K-step timed region is repeated --trials times; `value` (and
-ms_per_step, roofline.*) come from the MEDIAN trial, "trials_us" lists them all, with their mean and
-best.  `value` = algorithmic FLOPs of all ranks / wall time, where algorithmic FLOPs are the direct-
+Prints ONE JSON line (rank 0).  The timed region is exactly K = --steps steps, and `ms_per_step` is
+the milliseconds one of them took.  --trials T (default 1) repeats the K-step region T times; `value`
+(and ms_per_step, roofline.*) then come from the MEDIAN trial, "trials_us" lists them all, with their
+mean and best.  `value` = algorithmic FLOPs of all ranks / wall time, where algorithmic FLOPs are the direct-
 convolution FLOPs 2*N*P*Q*K*C*R*S, so it may exceed the fp32 MFMA peak:
 F(2x2,3x3) executes 2.25x fewer multiplies.  `roofline.frac` is therefore the EXECUTED-MFMA fraction
 (FLOPs the matrix pipes really execute / kernel time / peak: a physical utilisation, <= 1);
 `roofline.effective_frac` is the algorithmic one.
+
+--dump-outputs DIR writes what the last timed step computed -- the output tensor the caller of the timed
+path receives -- as DIR/<name>.npy (float32, rank 0).  The inputs come from a fixed seed, so two builds run
+with the same arguments can be compared output for output; an output above the size cap is written as a
+seeded sample of its leading index (images, or GEMM rows), which is the same sample in every run.
 """
 from __future__ import annotations
 
@@ -231,6 +237,30 @@ def pmc_traffic(layer: str):
         return None, None
 
 
+DUMP_BYTES = 60 * 10 ** 6   # --dump-outputs writes at most this many array bytes in all (64 MB with the .npy headers)
+
+
+def dump_outputs(directory: str, outputs: dict) -> dict:
+    """Write every tensor of `outputs` as <directory>/<name>.npy in float32.  One larger than its share of
+    DUMP_BYTES keeps a seeded, sorted sample of its leading index, so every run writes the same elements.
+    Returns name -> {shape written, shape computed, how it was sampled or None}."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // len(outputs)
+    written = {}
+    for name, t in outputs.items():
+        a = t.detach().float().cpu().numpy()
+        full_shape, rows = list(a.shape), None
+        if a.nbytes > share:
+            keep = share // (a.nbytes // a.shape[0])
+            rows = np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))
+            a = a[rows]
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(a))
+        written[name] = {"shape": list(a.shape), "full_shape": full_shape,
+                         "sample": None if rows is None else f"{len(rows)} of {full_shape[0]} along axis 0, seed 0"}
+    return written
+
+
 # ------------------------------------------------------------------ main
 def main():
     ap = argparse.ArgumentParser()
@@ -240,13 +270,18 @@ def main():
     ap.add_argument("--layer", default="conv3x3_256", choices=sorted(LAYERS))
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-images", type=int, default=BATCH)
-    ap.add_argument("--trials", type=int, default=3)
+    ap.add_argument("--trials", type=int, default=1,
+                    help="repeat the K-step timed region this many times and report the median (default 1)")
     ap.add_argument("--batch", type=int, default=BATCH,
                     help="images per GPU (weak scaling) or in the whole job (strong scaling)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak")
     ap.add_argument("--preheat-ms", type=float, default=400.0,
                     help="untimed clock-ramp phase before the warm-up steps (disclosed in the JSON line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output of the last timed step as DIR/<name>.npy (float32, rank 0)")
     args = ap.parse_args()
+    if args.steps < 1 or args.trials < 1 or args.warmup < 0:
+        ap.error("--steps and --trials must be >= 1, --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # convenience: relaunch under torch.distributed.run as a CHILD (never exec after GPU init)
@@ -376,6 +411,8 @@ def main():
             except pkg.WinoError:
                 clk = None
         trials.append({"elapsed": t, "kernel_ms": ev0.elapsed_time(ev1) / args.steps, "clock": clk})
+    # every step writes `out` in full from the same inputs; after the closing synchronise it holds the last timed step's
+    dumped = dump_outputs(args.dump_outputs, {"out": out}) if args.dump_outputs and rank == 0 else None
     order = sorted(range(len(trials)), key=lambda i: trials[i]["elapsed"])
     med = trials[order[(len(order) - 1) // 2]]   # (lower median for an even count)
     elapsed, kernel_ms = med["elapsed"], med["kernel_ms"]
@@ -430,6 +467,8 @@ def main():
                              "effective_* = algorithmic (direct-conv) FLOPs / the same time (Winograd executes 2.25x "
                              "fewer); peak = 157.3 TFLOP/s at 2.4 GHz, frac_of_peak_at_clock scales it to clock_ghz"},
     }
+    if dumped is not None:
+        line["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     if rank == 0 and world == 1 and not args.no_cpu_baseline and kind in ("3x3", "1x1") and H == 14:
         line["cpu_baseline"] = cpu_baseline(kind, C, K, relu, min(args.cpu_images, BATCH))
     if world > 1:
