@@ -66,6 +66,15 @@ static inline bool bad_1x1_dims(int Cin, int Kout) {
          (unsigned long long)Cin * (unsigned long long)Kout * sizeof(float) >= (1ull << 32);
 }
 static inline bool four_waves(int Cin, int Kout) { return Kout <= 128 || Cin <= 128 || (Kout % 128) != 0; }
+// The shape check of the 1x1 entry points; `row_tiles`: also the tiled kernel's limit of 2^24 row tiles.
+static int check_1x1(long M, int Cin, int Kout, bool row_tiles = true) {
+  if (M < 1 || bad_1x1_dims(Cin, Kout)) {
+    set_error("unsupported 1x1 shape M=%ld Cin=%d Kout=%d (need Cin %% 32 == 0, Kout %% 64 == 0)", M, Cin, Kout);
+    return WINO_E_SHAPE;
+  }
+  if (row_tiles && (M + BM - 1) / BM > (1L << 24)) { set_error("M too large"); return WINO_E_SHAPE; }
+  return WINO_OK;
+}
 
 // Stream-K grid for `tiles` output tiles of nk k-steps on `cus` CUs, or 0 for the plain
 // one-tile-per-workgroup launch.  A launch lasts as long as its busiest CU (conv1x1_kernel.h): the
@@ -97,8 +106,7 @@ constexpr long long SK1_MAX_GRID = 16384;   // 2 * G slabs of <= 56 KB must stay
 struct Sk1Model { double a_plain, t_plain, e_tile, a_sk1, t_sk1, a_sk2, t_sk2; };
 constexpr Sk1Model SK1_MODEL_8W = {2.7, 1.555, 1.75, 12.0, 1.60, 13.0, 1.558};
 constexpr Sk1Model SK1_MODEL_4W = {3.8, 0.778, 0.7, 9.5, 0.89, 11.0, 0.816};
-static int sk1_grid(long long tiles, int nk, int cus, int nblk, bool four_wave_form, double* t_pred = nullptr) {
-  const Knobs kn = knobs();
+static int sk1_grid(long long tiles, int nk, int cus, int nblk, bool four_wave_form, const Knobs& kn, double* t_pred) {
   const int force = kn.sk_1x1;
   {   // the plain form's predicted time: what stands when no stream-K / split-K grid is taken
     const Sk1Model& m0 = four_wave_form ? SK1_MODEL_4W : SK1_MODEL_8W;
@@ -198,11 +206,9 @@ static double small1_time(long M, int Cin, int Kout, int cus, int ks, int rt, in
   const long long deep = (*wgs + cus - 1) / cus;
   return 2.16 + (double)deep * (0.0281 * a_kb + (ct == 4 ? 0.0171 : 0.0141) * b_kb + 0.098 * c_kb + 0.43);
 }
-static Small1Plan small1_plan(long M, int Cin, int Kout, int flags, int batch, int cus) {
+// t_tiled: the tiled kernel's launch model (sk1_grid)
+static Small1Plan small1_plan(long M, int Cin, int Kout, int cus, double t_tiled, const Knobs& kn) {
   Small1Plan pl = {false, 1, 1, 1, 0, 0.0, 0.0};
-  if (batch != 1 || M < 1) return pl;   // (every flag of the tiled kernel travels; batched launches do not)
-  (void)flags;
-  const Knobs kn = knobs();
   double best = 1e30;
   for (int rt = 1; rt <= 2; rt++)
     for (int ct = 1; ct <= 4; ct *= 2)
@@ -219,93 +225,103 @@ static Small1Plan small1_plan(long M, int Cin, int Kout, int flags, int batch, i
         if (t < best) { best = t; pl.ks = ks; pl.rt = rt; pl.ct = ct; pl.wgs = wgs; pl.t_us = t; }
       }
   if (best > 1e29) return pl;
-  {
-    double t_big = 0.0;
-    const bool four = four_waves(Cin, Kout);
-    const int bn = four ? 64 : 128;
-    (void)sk1_grid(((M + BM - 1) / BM) * (long long)(Kout / bn), Cin / 32, cus, Kout / bn, four, &t_big);
-    pl.t_big_us = t_big;
-    pl.use = best < (pl.wgs > cus ? 0.8 : 0.93) * t_big;   // (1024->256 at 40 images: modelled 38.5 / 41.0 us, measured 48.5 / 44.4)
-  }
+  pl.t_big_us = t_tiled;
+  pl.use = best < (pl.wgs > cus ? 0.8 : 0.93) * t_tiled;   // (1024->256 at 40 images: modelled 38.5 / 41.0 us, measured 48.5 / 44.4)
   if (kn.sk_1x1 != -1 || kn.sk_1x1_grid != 0) pl.use = false;   // a developer is forcing a form of the tiled kernel
   if (kn.algo_1x1 == 1) pl.use = false;
   if (kn.algo_1x1 == 2) pl.use = true;
   return pl;
 }
-template <int RT, int CT>
-static void launch_1x1_small_ks(int ks, dim3 grid, hipStream_t s, const float* A, const float* B, const float* bnBias,
-                                const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags, PadGeo pg) {
-  const dim3 block(256);
-  if (ks == 4) hipLaunchKernelGGL((conv1x1_small_kernel<4, RT, CT>), grid, block, 0, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else if (ks == 2) hipLaunchKernelGGL((conv1x1_small_kernel<2, RT, CT>), grid, block, 0, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else hipLaunchKernelGGL((conv1x1_small_kernel<1, RT, CT>), grid, block, 0, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
+
+// The plan of one launch, read by every consumer -- conv1x1_ex, gemm_batched, prepare, the wino_conv1x1_*plan* queries
+// and wino_debug_conv1x1_models: the tiled kernel's form (its stream-K grid and launch model from one sk1_grid call)
+// and the latency form priced against that model.  Every flag of the tiled kernel travels to the latency form;
+// batched launches (batch > 1: gemm_batched) take neither it nor stream-K.
+struct Plan1x1 {
+  bool four;            // 4-wave workgroups (64 columns), else 8 (128)
+  int nblk, nk;         // column blocks, k-steps
+  long long nMB;        // row tiles
+  int sk;               // stream-K / split-K grid, 0: the plain form
+  int grid;             // the tiled launch's grid (per batch)
+  Small1Plan small;
+};
+static Plan1x1 plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn) {
+  Plan1x1 p{};
+  p.four = four_waves(Cin, Kout);
+  p.nblk = Kout / (p.four ? 64 : 128);
+  p.nk = Cin / 32;
+  p.nMB = (M + BM - 1) / BM;
+  p.small = {false, 1, 1, 1, 0, 0.0, 0.0};
+  if (batch == 1) {
+    double t_tiled = 0.0;
+    p.sk = sk1_grid(p.nMB * p.nblk, p.nk, cus, p.nblk, p.four, kn, &t_tiled);
+    p.small = small1_plan(M, Cin, Kout, cus, t_tiled, kn);
+  }
+  p.grid = p.sk ? p.sk : (int)(8ll * p.nblk * ((p.nMB + 7) / 8));
+  return p;
 }
+// the plan of a launch on the current device; *dev receives the device
+static int plan_1x1_here(long M, int Cin, int Kout, int batch, int* dev, Plan1x1* p) {
+  int cus = 0;
+  WINO_HIP(hipGetDevice(dev));
+  if (int rc = device_cus(*dev, &cus)) return rc;
+  *p = plan_1x1(M, Cin, Kout, batch, cus, knobs());
+  return WINO_OK;
+}
+// the tiled kernel's stream-K scratch: 2 slabs of NW x RB KB per range, a ticket counter per tile
+static int tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs) {
+  return sk_scratch(dev, s, (size_t)2 * p.sk * (p.four ? 4 : 8) * RB * 1024, (size_t)(p.nMB * p.nblk), bufs);
+}
+
+// the latency kernel's instantiations by [KS / 2][RT - 1][CT / 2]
+#define WINO_SMALL1_CT(KS, RT) {conv1x1_small_kernel<KS, RT, 1>, conv1x1_small_kernel<KS, RT, 2>, conv1x1_small_kernel<KS, RT, 4>}
+static decltype(&conv1x1_small_kernel<1>) const SMALL1_KERNELS[3][2][3] = {
+    {WINO_SMALL1_CT(1, 1), WINO_SMALL1_CT(1, 2)},
+    {WINO_SMALL1_CT(2, 1), WINO_SMALL1_CT(2, 2)},
+    {WINO_SMALL1_CT(4, 1), WINO_SMALL1_CT(4, 2)}};
+#undef WINO_SMALL1_CT
+
 static int launch_1x1_small(const Small1Plan& pl, const float* A, const float* B, const float* bnBias,
                             const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags, PadGeo pg,
                             hipStream_t s) {
   // x = column group, y = row block: see the kernel
   const dim3 grid((unsigned)(Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((M + 16 * pl.rt - 1) / (16 * pl.rt)));
-  if (pl.rt == 2 && pl.ct == 4) launch_1x1_small_ks<2, 4>(pl.ks, grid, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else if (pl.ct == 4) launch_1x1_small_ks<1, 4>(pl.ks, grid, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else if (pl.rt == 2 && pl.ct == 2) launch_1x1_small_ks<2, 2>(pl.ks, grid, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else if (pl.rt == 2) launch_1x1_small_ks<2, 1>(pl.ks, grid, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else if (pl.ct == 2) launch_1x1_small_ks<1, 2>(pl.ks, grid, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
-  else launch_1x1_small_ks<1, 1>(pl.ks, grid, s, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, pg);
+  hipLaunchKernelGGL(SMALL1_KERNELS[pl.ks >> 1][pl.rt - 1][pl.ct >> 1], grid, dim3(256), 0, s, A, B, bnBias, bnScale, R, C,
+                     M, Cin, Kout, flags, pg);
   return launch_status("conv1x1_small_kernel");
 }
 
-template <int BK, int NW, bool RES = false>
-static int launch_1x1_res(const float* A, const float* B, const float* bnBias, const float* bnScale,
-                          const float* R, float* C, long M, int Cin, int Kout, int flags, int nMB,
-                          hipStream_t s, int batch, long batchA, long batchB, long batchC,
-                          bool prepare_only, PadGeo pg);
-
-template <int BK, int NW>
-static int launch_1x1(const float* A, const float* B, const float* bnBias, const float* bnScale,
-                      const float* R, float* C, long M, int Cin, int Kout, int flags, int nMB,
-                      hipStream_t s, int batch = 1, long batchA = 0, long batchB = 0, long batchC = 0,
-                      bool prepare_only = false, PadGeo pg = make_padgeo(WINO_PQ, WINO_PQ)) {
-  if (flags & WINO_ADD_RESIDUAL)
-    return launch_1x1_res<BK, NW, true>(A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, nMB, s, batch, batchA, batchB, batchC, prepare_only, pg);
-  return launch_1x1_res<BK, NW, false>(A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, nMB, s, batch, batchA, batchB, batchC, prepare_only, pg);
-}
-
-template <int BK, int NW, bool RES>
-static int launch_1x1_res(const float* A, const float* B, const float* bnBias, const float* bnScale,
-                          const float* R, float* C, long M, int Cin, int Kout, int flags, int nMB,
-                          hipStream_t s, int batch, long batchA, long batchB, long batchC,
-                          bool prepare_only, PadGeo pg) {
-  using G = Cfg<BK, NW>;
-  static std::atomic<unsigned long long> attr_done{0};
-  int dev = 0;
-  WINO_HIP(hipGetDevice(&dev));
-  if (!((attr_done.load() >> (dev & 63)) & 1ull)) {
-    WINO_HIP(hipFuncSetAttribute((const void*)(conv1x1_bn_kernel<BK, NW, 0, false, RES>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-    WINO_HIP(hipFuncSetAttribute((const void*)(conv1x1_bn_kernel<BK, NW, 0, true, RES>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  int cus = 0;
-  if (int rc = device_cus(dev, &cus)) return rc;
-  const long long tiles = (long long)nMB * (Kout / G::BN);
-  const int Gsk = batch == 1 ? sk1_grid(tiles, Cin / BK, cus, Kout / G::BN, NW == 4) : 0;
-  if (Gsk) {
+// BK = 32 keeps a workgroup at 60 KB of LDS, so two workgroups share a CU (4 waves per SIMD)
+// and one's prologue / barrier bubbles / store tail hide under the other's MFMAs; measured
+// 3-14 % faster than BK = 64 (120 KB, one workgroup per CU) on the four reference shapes.
+template <int NW, bool RES>
+static int launch_1x1_tiled(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
+                            const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags,
+                            hipStream_t s, int batch, long batchA, long batchB, long batchC, PadGeo pg) {
+  using G = Cfg<32, NW>;
+  if (int rc = lds_cap_once<conv1x1_bn_kernel<32, NW, 0, false, RES>, conv1x1_bn_kernel<32, NW, 0, true, RES>>(dev, G::LDS_BYTES))
+    return rc;
+  const int nMB = (int)p.nMB;
+  if (p.sk) {
     SkBufs bufs;
-    if (int rc = sk_scratch(dev, s, (size_t)2 * Gsk * NW * RB * 1024, (size_t)tiles, &bufs)) return rc;
-    if (prepare_only) return WINO_OK;
+    if (int rc = tiled_scratch(dev, s, p, &bufs)) return rc;
     const SkArgs sk{bufs.slabs, bufs.tickets, nullptr, bufs.err};
-    hipLaunchKernelGGL((conv1x1_bn_kernel<BK, NW, 0, true, RES>), dim3(Gsk), dim3(G::NT), G::LDS_BYTES, s, A, B,
+    hipLaunchKernelGGL((conv1x1_bn_kernel<32, NW, 0, true, RES>), dim3(p.sk), dim3(G::NT), G::LDS_BYTES, s, A, B,
                        bnBias, bnScale, R, C, M, Cin, Kout, flags, nMB, 0L, 0L, 0L, sk, pg);
     const int rc = launch_status("conv1x1_bn_kernel (stream-K)");
     if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
     return rc;
   }
-  if (prepare_only) return WINO_OK;
-  const int grid = 8 * (Kout / G::BN) * ((nMB + 7) / 8);
-  hipLaunchKernelGGL((conv1x1_bn_kernel<BK, NW, 0, false, RES>), dim3(grid, batch), dim3(G::NT), G::LDS_BYTES, s, A, B,
+  hipLaunchKernelGGL((conv1x1_bn_kernel<32, NW, 0, false, RES>), dim3(p.grid, batch), dim3(G::NT), G::LDS_BYTES, s, A, B,
                      bnBias, bnScale, R, C, M, Cin, Kout, flags, nMB, batchA, batchB, batchC, SkArgs{nullptr, nullptr, nullptr, nullptr}, pg);
   return launch_status("conv1x1_bn_kernel");
+}
+static int launch_1x1_tiled(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
+                            const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags,
+                            hipStream_t s, int batch, long batchA, long batchB, long batchC, PadGeo pg) {
+  auto* launch = (flags & WINO_ADD_RESIDUAL) ? (p.four ? launch_1x1_tiled<4, true> : launch_1x1_tiled<8, true>)
+                                             : (p.four ? launch_1x1_tiled<4, false> : launch_1x1_tiled<8, false>);
+  return launch(p, dev, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, s, batch, batchA, batchB, batchC, pg);
 }
 
 namespace wino {
@@ -313,19 +329,17 @@ int last_clock_1x1(unsigned long long* stamps) {
   WINO_HIP(hipMemcpyFromSymbol(stamps, HIP_SYMBOL(wino::gemm1x1::wino_clk_slot_1x1), 4 * sizeof(unsigned long long)));
   return WINO_OK;
 }
-// Batched plain GEMM C_b = A_b . B_b (no BN) on the 1x1 kernel: used by the F(4x4) compatibility path.
 int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int Kout, int batch,
                  long batchA, long batchB, long batchC, hipStream_t s) {
   if (bad_1x1_dims(Cin, Kout) || M < 1 || batch < 1 || batch > 65535) {
     set_error("unsupported batched GEMM shape");
     return WINO_E_SHAPE;
   }
-  const int nMB = (int)((M + BM - 1) / BM);
-  if (four_waves(Cin, Kout))
-    return launch_1x1<32, 4>(A, B, nullptr, nullptr, nullptr, C, M, Cin, Kout, gemm1x1::WINO_INTERNAL_NO_BN, nMB, s,
-                             batch, batchA, batchB, batchC);
-  return launch_1x1<32, 8>(A, B, nullptr, nullptr, nullptr, C, M, Cin, Kout, gemm1x1::WINO_INTERNAL_NO_BN, nMB, s,
-                           batch, batchA, batchB, batchC);
+  int dev = 0;
+  Plan1x1 p;
+  if (int rc = plan_1x1_here(M, Cin, Kout, batch, &dev, &p)) return rc;
+  return launch_1x1_tiled(p, dev, A, B, nullptr, nullptr, nullptr, C, M, Cin, Kout, gemm1x1::WINO_INTERNAL_NO_BN, s,
+                          batch, batchA, batchB, batchC, make_padgeo(WINO_PQ, WINO_PQ));
 }
 }  // namespace wino
 
@@ -337,14 +351,7 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
   if ((flags & WINO_ADD_RESIDUAL) && !residual) { set_error("WINO_ADD_RESIDUAL without residual"); return WINO_E_ARG; }
   if (misaligned16(A, B, C, residual)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
   if (flags & ~(WINO_RELU | WINO_A_PADDED | WINO_C_PADDED | WINO_ADD_RESIDUAL)) { set_error("unknown flag bits 0x%x", flags); return WINO_E_ARG; }
-  if (M < 1 || bad_1x1_dims(Cin, Kout)) {
-    set_error("unsupported 1x1 shape M=%ld Cin=%d Kout=%d (need Cin %% 32 == 0, Kout %% 64 == 0)",
-              M, Cin, Kout);
-    return WINO_E_SHAPE;
-  }
-  const long nMBl = (M + BM - 1) / BM;
-  if (nMBl > (1L << 24)) { set_error("M too large"); return WINO_E_SHAPE; }
-  const int nMB = (int)nMBl;
+  if (int rc = check_1x1(M, Cin, Kout)) return rc;
   PadGeo pg = make_padgeo(WINO_PQ, WINO_PQ);
   if (flags & (WINO_A_PADDED | WINO_C_PADDED)) {
     if (H < 1 || W < 1 || H > 4094 || W > 4094) { set_error("unsupported feature map %dx%d", H, W); return WINO_E_SHAPE; }
@@ -357,19 +364,11 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
     if (ring_units >= (1ull << 32)) { set_error("padded output too large for one launch"); return WINO_E_SHAPE; }
     pg = make_padgeo(H, W);
   }
-  {
-    int dev = 0, cus = 0;
-    WINO_HIP(hipGetDevice(&dev));
-    if (int rc = device_cus(dev, &cus)) return rc;
-    const Small1Plan sp = small1_plan(M, Cin, Kout, flags, 1, cus);
-    if (sp.use) return launch_1x1_small(sp, A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg, (hipStream_t)s);
-  }
-  // BK = 32 keeps a workgroup at 60 KB of LDS, so two workgroups share a CU (4 waves per SIMD)
-  // and one's prologue / barrier bubbles / store tail hide under the other's MFMAs; measured
-  // 3-14 % faster than BK = 64 (120 KB, one workgroup per CU) on the four reference shapes.
-  if (four_waves(Cin, Kout))
-    return launch_1x1<32, 4>(A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, nMB, (hipStream_t)s, 1, 0, 0, 0, false, pg);
-  return launch_1x1<32, 8>(A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, nMB, (hipStream_t)s, 1, 0, 0, 0, false, pg);
+  int dev = 0;
+  Plan1x1 p;
+  if (int rc = plan_1x1_here(M, Cin, Kout, 1, &dev, &p)) return rc;
+  if (p.small.use) return launch_1x1_small(p.small, A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg, (hipStream_t)s);
+  return launch_1x1_tiled(p, dev, A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, (hipStream_t)s, 1, 0, 0, 0, pg);
 }
 
 extern "C" {
@@ -391,26 +390,19 @@ int wino_conv1x1_bn_ex_hw(const float* A, const float* B, const float* bnBias, c
 int wino_conv1x1_plan(long M, int Cin, int Kout, int cus, int* grid, int* row_tiles, int* col_blocks,
                       int* k_steps, int* stream_k) {
   if (!grid || !row_tiles || !col_blocks || !k_steps || !stream_k || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
-  if (M < 1 || bad_1x1_dims(Cin, Kout)) {
-    set_error("unsupported 1x1 shape M=%ld Cin=%d Kout=%d (need Cin %% 32 == 0, Kout %% 64 == 0)",
-              M, Cin, Kout);
-    return WINO_E_SHAPE;
-  }
-  const long nMBl = (M + BM - 1) / BM;
-  if (nMBl > (1L << 24)) { set_error("M too large"); return WINO_E_SHAPE; }
-  const int bn = four_waves(Cin, Kout) ? 64 : 128;   // as wino_conv1x1_bn_ex
-  const int nblk = Kout / bn;
-  const int G = sk1_grid((long long)nMBl * nblk, Cin / 32, cus, nblk, four_waves(Cin, Kout));
-  *row_tiles = (int)nMBl;
-  *col_blocks = nblk;
-  *k_steps = Cin / 32;
-  *stream_k = G != 0;
-  *grid = G ? G : 8 * nblk * (int)((nMBl + 7) / 8);
+  if (int rc = check_1x1(M, Cin, Kout)) return rc;
+  const Plan1x1 p = plan_1x1(M, Cin, Kout, 1, cus, knobs());
+  *row_tiles = (int)p.nMB;
+  *col_blocks = p.nblk;
+  *k_steps = p.nk;
+  *stream_k = p.sk != 0;
+  *grid = p.grid;
   return WINO_OK;
 }
 
-// Host-side only: does a PLAIN layer of this shape take the latency form (conv1x1_small_kernel.h) on a device
-// with `cus` CUs: *use, the K-split inside a workgroup and the number of workgroups.
+// Host-side only: does a layer of this shape take the latency form (conv1x1_small_kernel.h) on a device with `cus`
+// CUs -- plain or chained alike -- and in which form: *use, the K-split inside a workgroup, the block's row and column
+// tiles, and the number of workgroups.
 int wino_conv1x1_small_plan(long M, int Cin, int Kout, int cus, int* use, int* k_split, int* workgroups) {
   int rt = 0, ct = 0;
   return wino_conv1x1_small_plan2(M, Cin, Kout, cus, use, k_split, &rt, &ct, workgroups);
@@ -419,48 +411,36 @@ int wino_conv1x1_small_plan(long M, int Cin, int Kout, int cus, int* use, int* k
 int wino_conv1x1_small_plan2(long M, int Cin, int Kout, int cus, int* use, int* k_split, int* row_tiles, int* col_tiles,
                              int* workgroups) {
   if (!use || !k_split || !row_tiles || !col_tiles || !workgroups || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
-  if (M < 1 || bad_1x1_dims(Cin, Kout)) {
-    set_error("unsupported 1x1 shape M=%ld Cin=%d Kout=%d (need Cin %% 32 == 0, Kout %% 64 == 0)", M, Cin, Kout);
-    return WINO_E_SHAPE;
-  }
-  const Small1Plan pl = small1_plan(M, Cin, Kout, 0, 1, cus);
-  *use = pl.use;
-  *k_split = pl.ks;
-  *row_tiles = pl.rt;
-  *col_tiles = pl.ct;
-  *workgroups = pl.use ? (int)pl.wgs : 0;
+  if (int rc = check_1x1(M, Cin, Kout, false)) return rc;   // (the latency form has no row-tile limit of its own)
+  const Plan1x1 p = plan_1x1(M, Cin, Kout, 1, cus, knobs());
+  *use = p.small.use;
+  *k_split = p.small.ks;
+  *row_tiles = p.small.rt;
+  *col_tiles = p.small.ct;
+  *workgroups = p.small.use ? (int)p.small.wgs : 0;
   return WINO_OK;
 }
 
 int wino_debug_conv1x1_models(long M, int Cin, int Kout, int cus, double* t_latency_us, double* t_tiled_us) {
   if (!t_latency_us || !t_tiled_us || cus < 1 || M < 1 || bad_1x1_dims(Cin, Kout)) { set_error("bad argument"); return WINO_E_ARG; }
-  const Small1Plan pl = small1_plan(M, Cin, Kout, 0, 1, cus);
-  *t_latency_us = pl.t_us;
-  *t_tiled_us = pl.t_big_us;
+  const Plan1x1 p = plan_1x1(M, Cin, Kout, 1, cus, knobs());
+  *t_latency_us = p.small.t_us;
+  *t_tiled_us = p.small.t_big_us;
   return WINO_OK;
 }
 
 // Allocates the stream-K scratch this shape's launches on stream `s` will use (nothing for shapes
 // that take the plain form): call it before capturing wino_conv1x1_bn(_ex) into a HIP graph.
+// (A layer small enough for the latency form uses no scratch; the tiled kernel's is allocated all the same: a
+// developer knob may still send the launch there.)
 int wino_conv1x1_prepare(long M, int Cin, int Kout, wino_stream_t s) {
-  if (M < 1 || bad_1x1_dims(Cin, Kout)) {
-    set_error("unsupported 1x1 shape M=%ld Cin=%d Kout=%d (need Cin %% 32 == 0, Kout %% 64 == 0)",
-              M, Cin, Kout);
-    return WINO_E_SHAPE;
-  }
-  const long nMBl = (M + BM - 1) / BM;
-  if (nMBl > (1L << 24)) { set_error("M too large"); return WINO_E_SHAPE; }
-  const int nMB = (int)nMBl;
-  {   // (a layer small enough for the latency form uses no scratch; the tiled kernel's is allocated below all the same:
-      //  a developer knob may still send the launch there)
-    int dev = 0, cus = 0;
-    WINO_HIP(hipGetDevice(&dev));
-    if (int rc = device_cus(dev, &cus)) return rc;
-    (void)cus;
-  }
-  if (four_waves(Cin, Kout))
-    return launch_1x1<32, 4>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, M, Cin, Kout, 0, nMB, (hipStream_t)s, 1, 0, 0, 0, true);
-  return launch_1x1<32, 8>(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, M, Cin, Kout, 0, nMB, (hipStream_t)s, 1, 0, 0, 0, true);
+  if (int rc = check_1x1(M, Cin, Kout)) return rc;
+  int dev = 0;
+  Plan1x1 p;
+  if (int rc = plan_1x1_here(M, Cin, Kout, 1, &dev, &p)) return rc;
+  if (!p.sk) return WINO_OK;
+  SkBufs bufs;
+  return tiled_scratch(dev, (hipStream_t)s, p, &bufs);
 }
 
 int wino_conv1x1_bn(const float* A, const float* B, const float* bnBias, const float* bnScale,

@@ -5,8 +5,10 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdio>
+#include <initializer_list>
 
 #include "winograd_mi355x.h"
 
@@ -53,8 +55,6 @@ struct Knobs {
   int algo_3x3;       // WINO_3X3_ALGO: 0 automatic, 1 "big" (throughput kernel), 2 "small" (latency kernel)
   int sk_1x1;         // WINO_1X1_SK: -1 automatic, 0 plain form, 1 stream-K whenever a legal grid exists
   int sk_1x1_grid;    // WINO_1X1_SK_GRID: number of ranges (0 = model)
-  int sk_kp;          // WINO_SK_KP: 1 (default) the 3x3 stream-K tail per k-block, ranges placed in phase order; 0 round 2's
-                      // item-major list in launch order; 2 / 3 only the groups / only the phase order (A/B measurements)
   int small_split;    // WINO_SMALL_SPLIT: C-split S of the 3x3 latency kernel (0 = policy)
   int small3_ct;      // WINO_SMALL_CT: MFMA tiles per wave (block width / 16) of the 3x3 latency kernel, 1 / 2 / 4 (0 = policy)
   int algo_1x1;       // WINO_1X1_ALGO: 0 automatic, 1 "big" (LDS-staged kernel), 2 "small" (latency kernel)
@@ -74,6 +74,23 @@ static inline int launch_status(const char* what) {
   if (e != hipSuccess) return hip_fail(e, what);
   return WINO_OK;
 }
+
+// Raises the dynamic-LDS cap of the given kernels to `bytes` once per device (one bit per device).
+template <auto... KERNELS>
+int lds_cap_once(int dev, int bytes) {
+  static std::atomic<unsigned long long> done{0};
+  if ((done.load() >> (dev & 63)) & 1ull) return WINO_OK;
+  for (const void* k : {(const void*)KERNELS...})
+    WINO_HIP(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+  done.fetch_or(1ull << (dev & 63));
+  return WINO_OK;
+}
+
+// Defined in conv1x1.hip: the 1x1 kernels' clock stamps (wino_diag_last_clock), and the batched plain GEMM
+// C_b = A_b . B_b (no BN) on the tiled 1x1 kernel that the F(4x4) compatibility path runs.
+int last_clock_1x1(unsigned long long* stamps);
+int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int Kout, int batch,
+                 long batchA, long batchB, long batchC, hipStream_t s);
 
 // 16-byte global -> LDS DMA (global_load_lds_dwordx4): each lane fetches 16 B from its
 // own `src`; the wave's 64 pieces land at `lds_wave_base + lane*16` (wave-uniform base).

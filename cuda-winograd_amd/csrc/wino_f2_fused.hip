@@ -131,7 +131,6 @@ __global__ void filter_import_f4_kernel(const float* __restrict__ u36, float* __
 }  // namespace wino
 
 using namespace wino;
-namespace wino { int last_clock_1x1(unsigned long long* stamps); }   // conv1x1.hip
 
 extern "C" {
 
@@ -177,8 +176,6 @@ int wino_filter_import_f4(const float* u36, float* U, int C, int K, wino_stream_
 // Stream-K scratch of this kernel: 2 slabs of SLAB_BYTES per logical workgroup, one ticket counter
 // per (item, wave); the per-(device, stream) set lives in wino_runtime.hip (sk_scratch).
 // ---------------------------------------------------------------------------------
-static int sk_cus(int dev, int* cus) { return device_cus(dev, cus); }
-
 static int sk_workspace(int dev, hipStream_t s, int G, size_t items, SkBufs* bufs) {
   const size_t wgs = G < 256 ? 256 : (size_t)G;
   return sk_scratch(dev, s, 2 * wgs * SLAB_BYTES, items * 8, bufs);
@@ -226,8 +223,7 @@ static double sk_cost(long long items, int nchunks, long long G) {
   }
   return c;
 }
-static int sk_grid_for(int cus, long long items, int nchunks, int* G) {
-  const Knobs kn = knobs();   // developer overrides (cached; tests sweep the decomposition through them)
+static int sk_grid_for(int cus, long long items, int nchunks, const Knobs& kn) {
   const int min_iters = kn.sk_min_iters > 0 ? kn.sk_min_iters : SK_MIN_ITERS;
   const long long T = items * nchunks;
   long long g = cus;
@@ -255,35 +251,7 @@ static int sk_grid_for(int cus, long long items, int nchunks, int* G) {
   }
   if (kn.sk_grid >= 1) g = kn.sk_grid;
   if (g > 16384) g = 16384;   // 2 * G slabs of 64 KB must stay below the 4 GiB a buffer descriptor spans
-  *G = (int)g;
-  return WINO_OK;
-}
-
-// k-groups of the stream-K tail (wino_f2_fused_kernel.h): K/64 when the grid is a multiple of it -- the items are
-// K/64 per tile block, so the tail's item count is then a multiple too -- else 1 (one item-major list, round 2's
-// scheme).  WINO_SK_KP=0 forces round 2's scheme altogether (A/B measurements).
-static int tail_groups(int G, int K) {
-  const int kblk = K / KB;
-  if (knobs().sk_kp == 0 || knobs().sk_kp == 3 || kblk <= 1 || (G % kblk) != 0) return 1;
-  return kblk;
-}
-
-// Phase order of a k-group's tail ranges (tail_range_of, wino_f2_fused_kernel.h): for Gp equal ranges of q iterations
-// the period P = nchunks / gcd(q, nchunks) of their channel phases, the inverse of q / gcd modulo P, and Gp / P.
-struct PhaseOrder { int P, inv, copies; };
-static PhaseOrder phase_order(long long q, long long rem, int nchunks, long long Gp) {
-  PhaseOrder id = {1, 0, (int)Gp};
-  if (rem != 0 || q <= 0 || knobs().sk_kp == 0 || knobs().sk_kp == 2) return id;   // (WINO_SK_KP=0: round 2's scheme; 2: k-groups without the phase order; 3: phase order without the groups -- A/B)
-  long long a = q % nchunks, b = nchunks;
-  while (a) { const long long t = b % a; b = a; a = t; }
-  const long long g = b, P = nchunks / g;
-  if (P <= 1 || Gp % P != 0) return id;
-  const long long qq = (q / g) % P;
-  long long inv = 0;
-  for (long long x = 1; x < P; x++)
-    if ((qq * x) % P == 1) { inv = x; break; }
-  if (!inv) return id;
-  return PhaseOrder{(int)P, (int)inv, (int)(Gp / P)};
+  return (int)g;
 }
 
 // The largest batch one launch takes: the kernels address the tensors with 32-bit byte offsets
@@ -370,13 +338,12 @@ static bool small_form(int N, int tiles, int C, int K, int cus, int ct, SmallPla
   pl->t_us = SMALL_T0 + (double)((ntask + waves - 1) / waves) * (SMALL_ROUND + (SMALL_FLT + SMALL_FLT_FILL * fill) * ct) + split_us;
   return true;
 }
-static SmallPlan small_plan(int N, int H, int W, int C, int K, int cus) {
+static SmallPlan small_plan(int N, int H, int W, int C, int K, int cus, const Knobs& kn) {
   SmallPlan pl = {false, 1, 0, 0, 1, 0.0};
   if ((C % 16) != 0 || H < 1 || W < 1) return pl;
   const long long tiles_ll = (long long)((H + 1) / 2) * ((W + 1) / 2);
   if (tiles_ll * N > (1ll << 30)) return pl;
   const int tiles = (int)tiles_ll;
-  const Knobs kn = knobs();
   if (kn.small3_ct == 1 || kn.small3_ct == 2 || kn.small3_ct == 4) {
     pl.use = small_form(N, tiles, C, K, cus, kn.small3_ct, &pl);
   } else {
@@ -402,6 +369,39 @@ static int small_scratch(int dev, hipStream_t s, const SmallPlan& pl, SkBufs* bu
   return sk_scratch(dev, s, pl.blocks * pl.split * pl.ct * SMALL_SLAB_BYTES, pl.blocks, bufs);
 }
 
+// The plan of one launch, read by every consumer -- the launch, prepare, the clock probe and the wino_conv3x3_*plan*
+// queries: the latency kernel's form and, when that kernel does not run or `throughput` asks for it all the same, the
+// throughput kernel's grid and work layout.
+struct Plan3x3 {
+  SmallPlan small;
+  Geo geo;
+  int G;            // logical workgroups of the throughput kernel
+  long long items;
+  FusedParams fp;   // its shape and work layout; the tensor and scratch pointers are filled in at launch
+};
+static Plan3x3 plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs& kn, bool throughput) {
+  Plan3x3 p{};
+  const unsigned tiles_x = (unsigned)((W + 1) / 2), tiles = (unsigned)((H + 1) / 2) * tiles_x;
+  p.geo = {H + 2, W + 2, tiles, tiles_x, make_fastdiv(tiles), make_fastdiv(tiles_x)};
+  p.small = small_plan(N, H, W, C, K, cus, kn);
+  if (p.small.use && !throughput) return p;
+  const int nTB = (int)(((long long)N * tiles + TB - 1) / TB);
+  p.items = (long long)nTB * (K / KB);
+  p.G = sk_grid_for(cus, p.items, C / BC, kn);
+  p.fp.N = N, p.fp.C = C, p.fp.K = K, p.fp.nTB = nTB, p.fp.geo = p.geo;
+  fused_work_layout(p.fp, p.items, p.G);
+  return p;
+}
+
+// the plan of a launch on the current device; *dev receives the device
+static int plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p) {
+  int cus = 0;   // one device query per launch; the CU count is cached per device
+  WINO_HIP(hipGetDevice(dev));
+  if (int rc = device_cus(*dev, &cus)) return rc;
+  *p = plan_3x3(N, H, W, C, K, cus, knobs(), throughput);
+  return WINO_OK;
+}
+
 static int conv3x3_prepare(int N, int H, int W, int C, int K, hipStream_t s) {
   if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
   if (N < 1) { set_error("bad batch N=%d", N); return WINO_E_SHAPE; }
@@ -410,28 +410,23 @@ static int conv3x3_prepare(int N, int H, int W, int C, int K, hipStream_t s) {
     if (N > step) N = (int)(step > 64 ? step - step % 64 : step);
   }
   if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
-  int dev = 0, cus = 0;
-  WINO_HIP(hipGetDevice(&dev));
-  if (int rc = sk_cus(dev, &cus)) return rc;
+  int dev = 0;
+  Plan3x3 p;
+  if (int rc = plan_3x3_here(N, H, W, C, K, false, &dev, &p)) return rc;
   SkBufs bufs;
-  const SmallPlan sp = small_plan(N, H, W, C, K, cus);
-  if (sp.use) return small_scratch(dev, s, sp, &bufs);
-  const int nTB = (int)(((long long)N * ((H + 1) / 2) * ((W + 1) / 2) + TB - 1) / TB);
-  const size_t items = (size_t)nTB * (K / KB);
-  int G = 0;
-  if (int rc = sk_grid_for(cus, (long long)items, C / BC, &G)) return rc;
-  return sk_workspace(dev, s, G, items, &bufs);
+  if (p.small.use) return small_scratch(dev, s, p.small, &bufs);
+  return sk_workspace(dev, s, p.G, (size_t)p.items, &bufs);
 }
+
+// the latency kernel's instantiations by [GEN][CT / 2]
+static void (*const SMALL_KERNELS[2][3])(SmallParams) = {
+    {wino_f2_small_kernel<1, false>, wino_f2_small_kernel<2, false>, wino_f2_small_kernel<4, false>},
+    {wino_f2_small_kernel<1, true>, wino_f2_small_kernel<2, true>, wino_f2_small_kernel<4, true>}};
 
 template <bool GEN, bool TAIL>
 static int launch_fused(const FusedParams& prm, int G, int dev, hipStream_t s) {
-  // raise the dynamic-LDS cap (all 160 KB of the CU) once per device
-  static std::atomic<unsigned long long> attr_done{0};
-  if (!((attr_done.load() >> (dev & 63)) & 1ull)) {
-    WINO_HIP(hipFuncSetAttribute((const void*)(wino_f2_fused_kernel<0, GEN, TAIL>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
+  // all 160 KB of the CU's LDS
+  if (int rc = lds_cap_once<wino_f2_fused_kernel<0, GEN, TAIL>>(dev, LDS_BYTES)) return rc;
   hipLaunchKernelGGL((wino_f2_fused_kernel<0, GEN, TAIL>), dim3(G), dim3(NTHREADS), LDS_BYTES, s, prm);
   const int rc = launch_status("wino_f2_fused_kernel");
   if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
@@ -439,7 +434,32 @@ static int launch_fused(const FusedParams& prm, int G, int dev, hipStream_t s) {
 }
 
 static int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, const float* bnScale,
-                              float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s);
+                              float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
+  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
+  const bool fixed14 = H == WINO_PQ && W == WINO_PQ;
+  int dev = 0;
+  Plan3x3 p;
+  if (int rc = plan_3x3_here(N, H, W, C, K, false, &dev, &p)) return rc;
+  if (p.small.use) {
+    const SmallPlan& sp = p.small;
+    SkBufs bufs;
+    if (int rc = small_scratch(dev, s, sp, &bufs)) return rc;
+    const SmallParams prm = {in, U, bnBias, bnScale, out, N, C, K, relu, bufs.slabs, bufs.tickets, bufs.err, nullptr, p.geo};
+    const dim3 grid(K / (16 * sp.ct), sp.nT16, sp.split), block(64 * SMALL_WAVES);   // x = out-channel block: see the kernel
+    hipLaunchKernelGGL(SMALL_KERNELS[!fixed14][sp.ct >> 1], grid, block, 0, s, prm);
+    const int rc = launch_status("wino_f2_small_kernel");
+    if (rc && sp.split > 1) sk_mark_failed(dev, s);
+    return rc;
+  }
+  SkBufs bufs;
+  if (int rc = sk_workspace(dev, s, p.G, (size_t)p.items, &bufs)) return rc;
+  FusedParams prm = p.fp;
+  prm.in = in, prm.Uq = U, prm.relu = relu, prm.bnBias = bnBias, prm.bnScale = bnScale, prm.out = out;
+  prm.slabs = bufs.slabs, prm.tickets = bufs.tickets, prm.err = bufs.err;
+  // whole items only (no stream-K tail): the kernel variant without the hand-off in its epilogue
+  if (p.items % p.G == 0) return fixed14 ? launch_fused<false, false>(prm, p.G, dev, s) : launch_fused<true, false>(prm, p.G, dev, s);
+  return fixed14 ? launch_fused<false, true>(prm, p.G, dev, s) : launch_fused<true, true>(prm, p.G, dev, s);
+}
 
 // Any batch: batches whose tensors would reach 4 GiB go out as several launches of whole images
 // (a multiple of 64 images each, so that every launch but the last fills its 64-tile blocks).
@@ -461,53 +481,6 @@ static int conv3x3_launch(const float* in, const float* U, const float* bnBias, 
   return WINO_OK;
 }
 
-static int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, const float* bnScale,
-                              float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
-  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
-  const bool fixed14 = H == WINO_PQ && W == WINO_PQ;
-  int dev = 0, cus = 0;   // one device query per launch; the CU count is cached per device
-  WINO_HIP(hipGetDevice(&dev));
-  if (int rc = sk_cus(dev, &cus)) return rc;
-  const SmallPlan sp = small_plan(N, H, W, C, K, cus);
-  if (sp.use) {
-    SkBufs bufs;
-    if (int rc = small_scratch(dev, s, sp, &bufs)) return rc;
-    const unsigned stx = (unsigned)((W + 1) / 2), st = (unsigned)((H + 1) / 2) * stx;
-    const Geo sgeo = {H + 2, W + 2, st, stx, make_fastdiv(st), make_fastdiv(stx)};
-    const SmallParams prm = {in, U, bnBias, bnScale, out, N, C, K, relu, bufs.slabs, bufs.tickets, bufs.err, nullptr, sgeo};
-    const dim3 grid(K / (16 * sp.ct), sp.nT16, sp.split), block(64 * SMALL_WAVES);   // x = out-channel block: see the kernel
-    if (fixed14) {
-      if (sp.ct == 4) hipLaunchKernelGGL((wino_f2_small_kernel<4, false>), grid, block, 0, s, prm);
-      else if (sp.ct == 2) hipLaunchKernelGGL((wino_f2_small_kernel<2, false>), grid, block, 0, s, prm);
-      else hipLaunchKernelGGL((wino_f2_small_kernel<1, false>), grid, block, 0, s, prm);
-    } else {
-      if (sp.ct == 4) hipLaunchKernelGGL((wino_f2_small_kernel<4, true>), grid, block, 0, s, prm);
-      else if (sp.ct == 2) hipLaunchKernelGGL((wino_f2_small_kernel<2, true>), grid, block, 0, s, prm);
-      else hipLaunchKernelGGL((wino_f2_small_kernel<1, true>), grid, block, 0, s, prm);
-    }
-    const int rc = launch_status("wino_f2_small_kernel");
-    if (rc && sp.split > 1) sk_mark_failed(dev, s);
-    return rc;
-  }
-  const unsigned tiles_x = (unsigned)((W + 1) / 2), tiles = (unsigned)((H + 1) / 2) * tiles_x;
-  const int nTB = (int)(((long long)N * tiles + TB - 1) / TB);
-  const size_t items = (size_t)nTB * (K / KB);
-  int G = 0;
-  if (int rc = sk_grid_for(cus, (long long)items, C / BC, &G)) return rc;
-  SkBufs bufs;
-  if (int rc = sk_workspace(dev, s, G, items, &bufs)) return rc;
-  const long long Tt = (long long)(items % (size_t)G) * (C / BC);   // the stream-K tail's iterations
-  const int kp = tail_groups(G, K);                                   // ... cut per k-block when the grid allows it
-  const long long Tg = Tt / kp, Gp = G / kp;
-  const Geo geo = {H + 2, W + 2, tiles, tiles_x, make_fastdiv(tiles), make_fastdiv(tiles_x)};
-  const PhaseOrder po = phase_order(Tg / Gp, Tg % Gp, C / BC, Gp);
-  const FusedParams prm = {in, U, N, C, K, relu, nTB, (int)(items / (size_t)G), (unsigned)(Tg / Gp), (unsigned)(Tg % Gp), kp, (int)Gp,
-                           po.P, po.inv, po.copies, make_fastdiv((unsigned)kp), make_fastdiv((unsigned)po.P), make_fastdiv((unsigned)po.copies), geo, bnBias, bnScale, out, bufs.slabs, bufs.tickets, bufs.err, nullptr};
-  // whole items only (no stream-K tail): the kernel variant without the hand-off in its epilogue
-  if (Tt == 0) return fixed14 ? launch_fused<false, false>(prm, G, dev, s) : launch_fused<true, false>(prm, G, dev, s);
-  return fixed14 ? launch_fused<false, true>(prm, G, dev, s) : launch_fused<true, true>(prm, G, dev, s);
-}
-
 // Diagnostic: the throughput kernel's stamped build (ABLATE = 16: s_memtime / s_memrealtime at the start
 // and at the end of every workgroup's main loop, each pair stored at once; the outputs are the product kernel's).  bench.py runs it right
 // after its timed region to report the clock the chip holds inside THIS kernel under sustained load.
@@ -516,32 +489,26 @@ static int conv3x3_clock_probe(const float* in, const float* U, const float* bnB
                                hipStream_t s) {
   if (!in || !U || !bnBias || !bnScale || !out || !stamps || !workgroups) { set_error("NULL pointer"); return WINO_E_ARG; }
   if (int rc = check_conv3x3(N, WINO_PQ, WINO_PQ, C, K)) return rc;
-  int dev = 0, cus = 0;
-  WINO_HIP(hipGetDevice(&dev));
-  if (int rc = sk_cus(dev, &cus)) return rc;
-  const int nTB = (int)(((long long)N * WINO_TILES + TB - 1) / TB);
-  const size_t items = (size_t)nTB * (K / KB);
-  int G = 0;
-  if (int rc = sk_grid_for(cus, (long long)items, C / BC, &G)) return rc;
-  if (G > 2048) { set_error("clock probe: grid %d exceeds the stamp buffer", G); return WINO_E_SHAPE; }
+  int dev = 0;
+  Plan3x3 p;
+  if (int rc = plan_3x3_here(N, WINO_PQ, WINO_PQ, C, K, true, &dev, &p)) return rc;
+  if (p.G > 2048) { set_error("clock probe: grid %d exceeds the stamp buffer", p.G); return WINO_E_SHAPE; }
   SkBufs bufs;
-  if (int rc = sk_workspace(dev, s, G, items, &bufs)) return rc;
-  const long long Tt = (long long)(items % (size_t)G) * (C / BC);
-  const int kp = tail_groups(G, K);
-  const long long Tg = Tt / kp, Gp = G / kp;
-  const Geo geo = {WINO_HW, WINO_HW, WINO_TILES, 7, make_fastdiv(WINO_TILES), make_fastdiv(7)};
-  const PhaseOrder po = phase_order(Tg / Gp, Tg % Gp, C / BC, Gp);
-  const FusedParams prm = {in, U, N, C, K, 1, nTB, (int)(items / (size_t)G), (unsigned)(Tg / Gp), (unsigned)(Tg % Gp), kp, (int)Gp,
-                           po.P, po.inv, po.copies, make_fastdiv((unsigned)kp), make_fastdiv((unsigned)po.P), make_fastdiv((unsigned)po.copies), geo, bnBias, bnScale, out, bufs.slabs, bufs.tickets, bufs.err, stamps};
-  static std::atomic<unsigned long long> attr_done{0};
-  if (!((attr_done.load() >> (dev & 63)) & 1ull)) {
-    WINO_HIP(hipFuncSetAttribute((const void*)(wino_f2_fused_kernel<16, false>),
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
-    attr_done.fetch_or(1ull << (dev & 63));
-  }
-  hipLaunchKernelGGL((wino_f2_fused_kernel<16, false>), dim3(G), dim3(NTHREADS), LDS_BYTES, s, prm);
-  *workgroups = G;
+  if (int rc = sk_workspace(dev, s, p.G, (size_t)p.items, &bufs)) return rc;
+  FusedParams prm = p.fp;
+  prm.in = in, prm.Uq = U, prm.relu = 1, prm.bnBias = bnBias, prm.bnScale = bnScale, prm.out = out;
+  prm.slabs = bufs.slabs, prm.tickets = bufs.tickets, prm.err = bufs.err, prm.dbg = stamps;
+  if (int rc = lds_cap_once<wino_f2_fused_kernel<16, false>>(dev, LDS_BYTES)) return rc;
+  hipLaunchKernelGGL((wino_f2_fused_kernel<16, false>), dim3(p.G), dim3(NTHREADS), LDS_BYTES, s, prm);
+  *workgroups = p.G;
   return launch_status("wino_f2_fused_kernel (stamped)");
+}
+
+// the plan of a wino_conv3x3_*plan* query
+static int plan_query(int N, int H, int W, int C, int K, int cus, Plan3x3* p) {
+  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
+  *p = plan_3x3(N, H, W, C, K, cus, knobs(), true);
+  return WINO_OK;
 }
 
 extern "C" {
@@ -555,37 +522,33 @@ int wino_diag_conv3x3_clock(const float* in, const float* U, const float* bnBias
 int wino_conv3x3_plan(int N, int H, int W, int C, int K, int cus, int* grid, int* rounds, long* tail_iters,
                       int* iters_per_item) {
   if (!grid || !rounds || !tail_iters || !iters_per_item || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
-  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
-  const long long nTB = ((long long)N * ((H + 1) / 2) * ((W + 1) / 2) + TB - 1) / TB;
-  const long long items = nTB * (K / KB);
-  int G = 0;
-  if (int rc = sk_grid_for(cus, items, C / BC, &G)) return rc;
-  *grid = G;
-  *rounds = (int)(items / G);
-  *tail_iters = (long)((items % G) * (C / BC));
+  Plan3x3 p;
+  if (int rc = plan_query(N, H, W, C, K, cus, &p)) return rc;
+  *grid = p.G;
+  *rounds = p.fp.ndp;
+  *tail_iters = (long)((p.items % p.G) * (C / BC));
   *iters_per_item = C / BC;
   return WINO_OK;
 }
 
 // Host-side only: does this shape take the latency kernel on a device with `cus` CUs, and in which form.
-int wino_conv3x3_small_plan(int N, int H, int W, int C, int K, int cus, int* use, int* point_rows, int* split,
-                            int* workgroups) {
-  if (!use || !point_rows || !split || !workgroups || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
-  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
-  const SmallPlan pl = small_plan(N, H, W, C, K, cus);
-  *use = pl.use;
+int wino_conv3x3_small_plan2(int N, int H, int W, int C, int K, int cus, int* use, int* point_rows, int* split,
+                             int* col_tiles, int* workgroups) {
+  if (!use || !point_rows || !split || !col_tiles || !workgroups || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
+  Plan3x3 p;
+  if (int rc = plan_query(N, H, W, C, K, cus, &p)) return rc;
+  *use = p.small.use;
   *point_rows = 2;
-  *split = pl.split;
-  *workgroups = pl.use ? (int)(pl.blocks * pl.split) : 0;
+  *split = p.small.split;
+  *col_tiles = p.small.ct;
+  *workgroups = p.small.use ? (int)(p.small.blocks * p.small.split) : 0;
   return WINO_OK;
 }
 
-int wino_conv3x3_small_plan2(int N, int H, int W, int C, int K, int cus, int* use, int* point_rows, int* split,
-                             int* col_tiles, int* workgroups) {
-  if (!col_tiles) { set_error("bad argument"); return WINO_E_ARG; }
-  if (int rc = wino_conv3x3_small_plan(N, H, W, C, K, cus, use, point_rows, split, workgroups)) return rc;
-  *col_tiles = small_plan(N, H, W, C, K, cus).ct;
-  return WINO_OK;
+int wino_conv3x3_small_plan(int N, int H, int W, int C, int K, int cus, int* use, int* point_rows, int* split,
+                            int* workgroups) {
+  int ct = 0;
+  return wino_conv3x3_small_plan2(N, H, W, C, K, cus, use, point_rows, split, &ct, workgroups);
 }
 
 int wino_diag_last_clock(int kernel, wino_stream_t s, unsigned long long stamps[4]) {
@@ -604,18 +567,12 @@ int wino_diag_last_clock(int kernel, wino_stream_t s, unsigned long long stamps[
 int wino_conv3x3_plan_groups(int N, int H, int W, int C, int K, int cus, int* groups, int* phase_period, int* phase_inv,
                              int* phase_copies) {
   if (!groups || !phase_period || !phase_inv || !phase_copies || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
-  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
-  const long long nTB = ((long long)N * ((H + 1) / 2) * ((W + 1) / 2) + TB - 1) / TB;
-  const long long items = nTB * (K / KB);
-  int G = 0;
-  if (int rc = sk_grid_for(cus, items, C / BC, &G)) return rc;
-  const int kp = tail_groups(G, K);
-  const long long Tg = (items % G) * (C / BC) / kp, Gp = G / kp;
-  const PhaseOrder po = phase_order(Tg / Gp, Tg % Gp, C / BC, Gp);
-  *groups = kp;
-  *phase_period = po.P;
-  *phase_inv = po.inv;
-  *phase_copies = po.copies;
+  Plan3x3 p;
+  if (int rc = plan_query(N, H, W, C, K, cus, &p)) return rc;
+  *groups = p.fp.kp;
+  *phase_period = p.fp.ph_P;
+  *phase_inv = p.fp.ph_inv;
+  *phase_copies = p.fp.ph_copies;
   return WINO_OK;
 }
 

@@ -188,6 +188,37 @@ struct FusedParams {
   unsigned long long* dbg;     // diagnostic builds only (ABLATE & (16 | 2048)): where the stamps go
 };
 
+// Host side: the work layout fields above (ndp ... d_copies) of `items` items of p.C / BC chunk iterations on a grid
+// of G logical workgroups: items / G whole-item rounds, the rest a stream-K tail.
+// k-groups of the tail: K/64 when the grid is a multiple of it -- the items are K/64 per tile block, so the tail's
+// item count is then a multiple too -- else 1 (one item-major list).
+// Phase order of a k-group's tail ranges (tail_range_of): for Gp equal ranges of q iterations the period P = nchunks /
+// gcd(q, nchunks) of their channel phases, the inverse of q / gcd modulo P, and Gp / P; the identity otherwise.
+inline void fused_work_layout(FusedParams& p, long long items, int G) {
+  const int nchunks = p.C / BC, kblk = p.K / KB;
+  const int kp = kblk <= 1 || (G % kblk) != 0 ? 1 : kblk;
+  const long long Tg = (items % G) * nchunks / kp, Gp = G / kp, q = Tg / Gp, rem = Tg % Gp;
+  p.ndp = (int)(items / G);
+  p.sk_q = (unsigned)q;
+  p.sk_rem = (unsigned)rem;
+  p.kp = kp;
+  p.Gp = (int)Gp;
+  p.ph_P = 1, p.ph_inv = 0, p.ph_copies = (int)Gp;
+  if (rem == 0 && q > 0) {
+    long long a = q % nchunks, b = nchunks;
+    while (a) { const long long t = b % a; b = a; a = t; }
+    const long long g = b, P = nchunks / g;
+    if (P > 1 && Gp % P == 0) {
+      const long long qq = (q / g) % P;
+      for (long long x = 1; x < P; x++)
+        if ((qq * x) % P == 1) { p.ph_P = (int)P; p.ph_inv = (int)x; p.ph_copies = (int)(Gp / P); break; }
+    }
+  }
+  p.d_kp = make_fastdiv((unsigned)kp);
+  p.d_P = make_fastdiv((unsigned)p.ph_P);
+  p.d_copies = make_fastdiv((unsigned)p.ph_copies);
+}
+
 // The clock the chip holds inside the product kernel: workgroup 0 of every launch stores {s_memtime,
 // s_memrealtime} here at its entry and at its exit (four 8-byte stores per launch from one lane; nothing
 // reads them on the device).  wino_diag_last_clock() copies them out: bench.py takes the clock OF its timed

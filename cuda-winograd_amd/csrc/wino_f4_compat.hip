@@ -15,9 +15,6 @@
 #include "wino_common.h"
 
 namespace wino {
-int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int Kout, int batch,
-                 long batchA, long batchB, long batchC, hipStream_t s);   // conv1x1.hip
-
 namespace {
 
 // B^T of F(4x4,3x3) applied to six values (rows of BT_F4 in oracle/oracle.py; Kernel128_winograd.cu:42-73)

@@ -151,7 +151,7 @@ int wino_conv3x3_prepare(int N, int C, int K, wino_stream_t s);
  * 14x14): H x W outputs (odd sizes such as the 7x7 stage included: the last tile row / column is
  * clipped), in [N][H+2][W+2][C], out [N][H+2][W+2][K] with the result at [1..H][1..W] and the ring
  * written as 0.  Same kernel, same packed filters; H = W = 14 is exactly
- * wino_conv3x3_bn_relu.  The latency kernel for tiny batches exists for 14x14 only. */
+ * wino_conv3x3_bn_relu.  Small batches take the latency kernel at every feature map, as at 14x14. */
 int wino_conv3x3_bn_relu_hw(const float* in, const float* U, const float* bnBias,
                             const float* bnScale, float* out, int N, int H, int W, int C, int K,
                             int relu, wino_stream_t s);
@@ -173,15 +173,15 @@ int wino_conv3x3_plan(int N, int H, int W, int C, int K, int cus, int* grid, int
  * and channel chunks in step and share the patches in the XCD's L2; neighbours in phase share the filter chunks. */
 int wino_conv3x3_plan_groups(int N, int H, int W, int C, int K, int cus, int* groups, int* phase_period, int* phase_inv,
                              int* phase_copies);
-/* Host-side only: whether this shape takes the latency kernel instead (small batches of the 14x14 stage: the
- * reference's own N = 1), and in which form: *point_rows (4, 2 or 1 rows of the 4x4 point grid per wave task)
+/* Host-side only: whether this shape takes the latency kernel instead (small batches of any feature map: the
+ * reference's own N = 1), and in which form: *point_rows (always 2 rows of the 4x4 point grid per wave task)
  * and *split (workgroups that share one 16-tile x 16-out-channel block's contraction, meeting through
  * library-owned slabs + tickets when > 1); *workgroups = blocks x split. */
 int wino_conv3x3_small_plan(int N, int H, int W, int C, int K, int cus, int* use, int* point_rows, int* split,
                             int* workgroups);
 /* The same with the block width: a wave holds *col_tiles MFMA tiles side by side (a block = 16 tiles x
  * 16 col_tiles out-channels; 1 at the reference's N = 1, 2 or 4 for the batches between that and the
- * throughput kernel's range, two point rows per task then). */
+ * throughput kernel's range). */
 int wino_conv3x3_small_plan2(int N, int H, int W, int C, int K, int cus, int* use, int* point_rows, int* split,
                              int* col_tiles, int* workgroups);
 
@@ -254,13 +254,14 @@ int wino_conv1x1_prepare(long M, int Cin, int Kout, wino_stream_t s);
  * and logical workgroup r*col_blocks + nb runs range r for column block nb. */
 int wino_conv1x1_plan(long M, int Cin, int Kout, int cus, int* grid, int* row_tiles, int* col_blocks,
                       int* k_steps, int* stream_k);
-/* Host-side only: plain layers (wino_conv1x1_bn; no padded operand, no residual) with few pixel rows -- the
- * reference's own M = 196 -- take a latency form instead of the tiled kernel wino_conv1x1_plan describes:
- * 16 x 16 output blocks, 4 waves per workgroup, a block's K loop split over *k_split of them (4, 2 or 1).
- * *use = 0: the tiled kernel runs. */
+/* Host-side only: layers with few pixel rows -- the reference's own M = 196 -- take a latency form instead of the
+ * tiled kernel wino_conv1x1_plan describes, plain ones (wino_conv1x1_bn) and chained ones (wino_conv1x1_bn_ex /
+ * _ex_hw: padded input, padded output with its ring pass, residual) alike: blocks of 16 row_tiles x 16 col_tiles
+ * outputs (row_tiles 1 or 2, col_tiles 1, 2 or 4: wino_conv1x1_small_plan2), 4 waves per workgroup, a block's K
+ * loop split over *k_split of them (4, 2 or 1).  *use = 0: the tiled kernel runs. */
 int wino_conv1x1_small_plan(long M, int Cin, int Kout, int cus, int* use, int* k_split, int* workgroups);
 /* The same with the block shape: a wave holds *row_tiles x *col_tiles MFMA tiles (16 x 16 each; 1 x 1 at M = 196,
- * 2 x 2 -- half the operand bytes per FLOP -- from a few images on). */
+ * larger blocks up to 2 x 4 -- fewer operand bytes per FLOP -- from a few images on). */
 int wino_conv1x1_small_plan2(long M, int Cin, int Kout, int cus, int* use, int* k_split, int* row_tiles, int* col_tiles,
                              int* workgroups);
 /* Host-side only (developer aid): the two launch models' times for this shape, the latency form's best candidate and the
