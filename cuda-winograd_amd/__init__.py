@@ -43,6 +43,8 @@ ABI_SYMBOLS = [
     "wino_debug_tickets_in_use", "wino_stream_check", "wino_stream_reset_scratch", "wino_debug_poison_ticket",
     "wino_diag_last_clock", "wino_conv3x3_small_plan", "wino_conv1x1_small_plan", "wino_conv3x3_plan_groups", "wino_conv1x1_small_plan2",
     "wino_conv3x3_small_plan2", "wino_debug_conv1x1_models",
+    "wino_proj_tail_elems", "wino_proj_tail_pack", "wino_proj_block_workspace_bytes_hw", "wino_proj_block_prepare_hw",
+    "wino_proj_block_hw", "wino_proj_tail_plan",
     # reference entry points + helpers (Kernel*.h, util.h)
     "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
     "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
@@ -134,6 +136,14 @@ def lib() -> ctypes.CDLL:
     L.wino_conv1x1_small_plan.argtypes = [c_long, c_int, c_int, c_int] + [POINTER(c_int)] * 3
     L.wino_conv1x1_small_plan2.argtypes = [c_long, c_int, c_int, c_int] + [POINTER(c_int)] * 5
     L.wino_conv3x3_plan_groups.argtypes = [c_int] * 6 + [POINTER(c_int)] * 4
+    L.wino_proj_tail_elems.restype = c_size_t
+    L.wino_proj_tail_elems.argtypes = [c_int] * 3
+    L.wino_proj_tail_pack.argtypes = [fp] * 7 + [c_int] * 3 + [c_void_p]
+    L.wino_proj_block_workspace_bytes_hw.restype = c_size_t
+    L.wino_proj_block_workspace_bytes_hw.argtypes = [c_int] * 4
+    L.wino_proj_block_prepare_hw.argtypes = [c_int] * 7 + [c_void_p]
+    L.wino_proj_block_hw.argtypes = [fp] * 9 + [c_int] * 7 + [fp, c_size_t, c_void_p]
+    L.wino_proj_tail_plan.argtypes = [c_int] * 8 + [POINTER(c_int)] * 2
     for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
                  "kernel_256_1_in", "kernel_256_1_out"):
         getattr(L, name).restype = c_int
@@ -479,6 +489,84 @@ def residual_block(x, w1, bn1, U2, bn2, w3, bn3, out=None, workspace=None) -> to
     else:
         _check(lib().wino_residual_block_hw(*args, N, H, W, C4, Cm, workspace.data_ptr(),
                                             workspace.numel() * 4, _stream()), "wino_residual_block_hw")
+    return out
+
+
+FORM_TILED, FORM_STREAM_K, FORM_LATENCY = 0, 1, 2   # WINO_1X1_FORM_*
+
+
+def proj_tail_pack(w3, bn3, wp, bnp) -> torch.Tensor:
+    """The projection block's fused last layer: w3 [Cm][C4], wp [Cin][C4] and their folded BNs (bias, scale) packed
+    into one opaque buffer (wino_proj_tail_pack) -- the analogue of filter_transform_f2 for U2."""
+    w3, wp = _dev(w3, "w3"), _dev(wp, "wp")
+    vecs = [_dev(v, "bn") for pair in (bn3, bnp) for v in pair]
+    Cm, C4, Cin = int(w3.shape[0]), int(w3.shape[1]), int(wp.shape[0])
+    if w3.dim() != 2 or wp.dim() != 2 or int(wp.shape[1]) != C4 or any(v.numel() != C4 for v in vecs):
+        raise WinoError("w3 must be [Cm][C4], wp [Cin][C4], the BN vectors [C4]")
+    n = lib().wino_proj_tail_elems(Cm, Cin, C4)
+    if n == 0:
+        raise WinoError(f"bad projection tail shape Cm={Cm} Cin={Cin} C4={C4}")
+    packed = torch.empty(n, dtype=torch.float32, device=w3.device)
+    _on_current_device(w3, wp, packed, *vecs)
+    _check(lib().wino_proj_tail_pack(w3.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), wp.data_ptr(),
+                                     vecs[2].data_ptr(), vecs[3].data_ptr(), packed.data_ptr(), Cm, Cin, C4, _stream()),
+           "wino_proj_tail_pack")
+    return packed
+
+
+def _proj_out_hw(Hin: int, Win: int, stride: int):
+    return (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+
+
+def proj_block_prepare(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int, stride: int) -> None:
+    """Allocate the scratch of proj_block's three launches for the current stream (before graph capture)."""
+    _check(lib().wino_proj_block_prepare_hw(int(N), int(Hin), int(Win), int(Cin), int(Cm), int(C4), int(stride),
+                                            _stream()), "wino_proj_block_prepare_hw")
+
+
+def proj_tail_plan(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int, stride: int, cus: int = 256):
+    """(first, tail): the FORM_* each of the projection block's two 1x1 launches takes (host-side)."""
+    v = [c_int(0), c_int(0)]
+    _check(lib().wino_proj_tail_plan(N, Hin, Win, Cin, Cm, C4, stride, cus, *[ctypes.byref(x) for x in v]),
+           "wino_proj_tail_plan")
+    return int(v[0].value), int(v[1].value)
+
+
+def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None) -> torch.Tensor:
+    """ResNet projection bottleneck (a stage's first block, v1 placement): x [N][Hin][Win][Cin] ->
+    [N][H][W][C4], H = (Hin-1)//stride + 1.  bnX = (bias, scale) folded BN vectors; w1 [Cin][Cm]; U2 from
+    filter_transform_f2 (Cm -> Cm); tail from proj_tail_pack (w3, bn3, wp, bnp)."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise WinoError("x must be [N][Hin][Win][Cin]")
+    N, Hin, Win, Cin = (int(v) for v in x.shape)
+    w1, U2, tail = _dev(w1, "w1"), _dev(U2, "U2"), _dev(tail, "tail")
+    if w1.dim() != 2 or int(w1.shape[0]) != Cin:
+        raise WinoError("w1 must be [Cin][Cm]")
+    Cm = int(w1.shape[1])
+    if tail.numel() % (Cm + Cin + 2):
+        raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
+    C4 = tail.numel() // (Cm + Cin + 2)
+    if int(stride) not in (1, 2):
+        raise WinoError(f"stride must be 1 or 2, got {stride}")
+    H, W = _proj_out_hw(Hin, Win, int(stride))
+    vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
+    need = lib().wino_proj_block_workspace_bytes_hw(N, H, W, Cm)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    else:
+        _out(workspace, None, "workspace")
+        if workspace.numel() * 4 < need:
+            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
+    if out is None:
+        out = torch.empty((N, H, W, C4), dtype=torch.float32, device=x.device)
+    else:
+        _out(out, (N, H, W, C4), "out")
+    _on_current_device(x, w1, U2, tail, out, workspace, *vecs)
+    _check(lib().wino_proj_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), U2.data_ptr(),
+                                    vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(), out.data_ptr(), N, Hin, Win,
+                                    Cin, Cm, C4, int(stride), workspace.data_ptr(), workspace.numel() * 4, _stream()),
+           "wino_proj_block_hw")
     return out
 
 

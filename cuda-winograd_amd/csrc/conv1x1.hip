@@ -23,6 +23,7 @@
 // counted lgkmcnt waits, and the LDS-DMA pieces are issued one per step: see the notes in
 // wino_f2_fused_kernel.h, the same three hipcc behaviours apply here.
 #include "conv1x1_kernel.h"
+#include "conv1x1_plan.h"
 #include "conv1x1_small_kernel.h"
 
 #include <atomic>
@@ -187,12 +188,6 @@ static int sk1_grid(long long tiles, int nk, int cus, int nblk, bool four_wave_f
 // M = 196: 1024->256 5.4 us against the tiled kernel's 19.3, 512->128 3.8 / 10.5, 128->512 3.4 / 6.7, 256->1024 4.7 / 14.4;
 // 8 images: 14.6 / 22.1, 6.7 / 12.6, 7.4 / 8.6, 14.7 / 19.1 (32 x 64 blocks with 16-byte filter loads).
 // WINO_1X1_ALGO=big|small and WINO_1X1_SMALL_KS / _RT / _CT override.
-struct Small1Plan {
-  bool use;
-  int ks, rt, ct;
-  long long wgs;
-  double t_us, t_big_us;   // the two launch models' times
-};
 static bool small1_legal(int Cin, int Kout, int ks, int rt, int ct) {
   (void)rt;
   return Cin % (16 * ks) == 0 && Kout % ((4 / ks) * ct * 16) == 0;
@@ -237,15 +232,8 @@ static Small1Plan small1_plan(long M, int Cin, int Kout, int cus, double t_tiled
 // and wino_debug_conv1x1_models: the tiled kernel's form (its stream-K grid and launch model from one sk1_grid call)
 // and the latency form priced against that model.  Every flag of the tiled kernel travels to the latency form;
 // batched launches (batch > 1: gemm_batched) take neither it nor stream-K.
-struct Plan1x1 {
-  bool four;            // 4-wave workgroups (64 columns), else 8 (128)
-  int nblk, nk;         // column blocks, k-steps
-  long long nMB;        // row tiles
-  int sk;               // stream-K / split-K grid, 0: the plain form
-  int grid;             // the tiled launch's grid (per batch)
-  Small1Plan small;
-};
-static Plan1x1 plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn) {
+// (Plan1x1 and Small1Plan: conv1x1_plan.h, shared with the projection block's launches in proj_block.hip)
+Plan1x1 wino::plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn) {
   Plan1x1 p{};
   p.four = four_waves(Cin, Kout);
   p.nblk = Kout / (p.four ? 64 : 128);
@@ -269,7 +257,7 @@ static int plan_1x1_here(long M, int Cin, int Kout, int batch, int* dev, Plan1x1
   return WINO_OK;
 }
 // the tiled kernel's stream-K scratch: 2 slabs of NW x RB KB per range, a ticket counter per tile
-static int tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs) {
+int wino::tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs) {
   return sk_scratch(dev, s, (size_t)2 * p.sk * (p.four ? 4 : 8) * RB * 1024, (size_t)(p.nMB * p.nblk), bufs);
 }
 

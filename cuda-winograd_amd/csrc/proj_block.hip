@@ -1,0 +1,238 @@
+// The projection (downsampling) bottleneck block: the first block of every ResNet stage, ResNet v1 placement (the
+// stride sits on the first 1x1 and on the projection, the 3x3 runs at stride 1 on the output grid):
+//   xs  = x[:, ::s, ::s, :]                                   (never materialised)
+//   t1  = relu(bn1(xs . w1))              padded [N][H+2][W+2][Cm]   (workspace)
+//   t2  = relu(bn2(conv3x3(t1, U2)))      padded [N][H+2][W+2][Cm]   (workspace)
+//   out = relu(bn3(t2 . w3) + bnp(xs . wp))     [N][H][W][C4]
+// Three launches: the strided 1x1 (s = 1: the plain 1x1 entry point), the Winograd 3x3, and the FUSED TAIL -- one
+// GEMM of K = Cm + Cin whose k-steps read t2 first and the strided x after it (conv1x1_kernel.h, A_TWO), against
+// the stacked, scale-folded [bn3Scale . w3 ; bnpScale . wp] with the summed bias: the shortcut is accumulated in
+// the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernels of conv1x1.hip in
+// their A_STRIDED / A_TWO operand forms, instantiated here so that conv1x1.hip's own stay exactly what they were.
+#include "conv1x1_kernel.h"
+#include "conv1x1_plan.h"
+#include "conv1x1_small_kernel.h"
+
+namespace wino {
+namespace {
+
+using namespace gemm1x1;
+
+// packed = [bn3Scale . w3 ; bnpScale . wp] ([Cm + Cin][C4], row-major), then bn3Bias + bnpBias, then C4 ones (the
+// tail's BN scale: the scales are folded into the matrix).  One thread per element.
+__global__ void proj_tail_pack_kernel(const float* __restrict__ w3, const float* __restrict__ b3,
+                                      const float* __restrict__ s3, const float* __restrict__ wp,
+                                      const float* __restrict__ bp, const float* __restrict__ sp,
+                                      float* __restrict__ packed, int Cm, int Cin, int C4) {
+  const long total = (long)(Cm + Cin + 2) * C4;
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const long r = i / C4;
+  const int k = (int)(i - r * C4);
+  float v;
+  if (r < Cm) v = s3[k] * w3[i];
+  else if (r < Cm + Cin) v = sp[k] * wp[i - (long)Cm * C4];
+  else if (r == Cm + Cin) v = b3[k] + bp[k];
+  else v = 1.f;
+  packed[i] = v;
+}
+
+// The latency kernel's projection forms by [AF - 1][KS / 2][RT - 1][CT / 2].
+#define WINO_SMALLP_CT(KS, RT, AF) \
+  {conv1x1_small_proj_kernel<KS, RT, 1, AF>, conv1x1_small_proj_kernel<KS, RT, 2, AF>, conv1x1_small_proj_kernel<KS, RT, 4, AF>}
+#define WINO_SMALLP_AF(AF) \
+  {{WINO_SMALLP_CT(1, 1, AF), WINO_SMALLP_CT(1, 2, AF)}, {WINO_SMALLP_CT(2, 1, AF), WINO_SMALLP_CT(2, 2, AF)}, \
+   {WINO_SMALLP_CT(4, 1, AF), WINO_SMALLP_CT(4, 2, AF)}}
+static decltype(&conv1x1_small_proj_kernel<1, 1, 1, A_STRIDED>) const SMALLP_KERNELS[2][3][2][3] = {
+    WINO_SMALLP_AF(A_STRIDED), WINO_SMALLP_AF(A_TWO)};
+#undef WINO_SMALLP_AF
+#undef WINO_SMALLP_CT
+
+// The block's geometry, checked once.  Every 32-bit quantity the strided / two-source addressing creates is bounded
+// here: the pixel row index (M < 2^31, one input image < 2^31 pixels), the buffer-descriptor windows of a 112-row tile
+// over the strided x and over the padded t2, the ring pass's 16-byte units, and B's descriptor.
+struct ProjGeom {
+  int N, Hin, Win, Cin, Cm, C4, s, H, W;
+  long M;
+};
+constexpr unsigned long long FOUR_GIB = 1ull << 32;
+static int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, ProjGeom* g) {
+  if (stride != 1 && stride != 2) { set_error("projection block: stride %d (need 1 or 2)", stride); return WINO_E_ARG; }
+  if (N < 1 || Hin < 1 || Win < 1) { set_error("projection block: bad N=%d Hin=%d Win=%d", N, Hin, Win); return WINO_E_SHAPE; }
+  if (Cin <= 0 || Cm <= 0 || C4 <= 0 || Cin % 32 || Cm % 64 || C4 % 64) {
+    set_error("projection block: unsupported channels Cin=%d Cm=%d C4=%d (need Cin %% 32 == 0, Cm %% 64 == 0, C4 %% 64 == 0)",
+              Cin, Cm, C4);
+    return WINO_E_SHAPE;
+  }
+  const int H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
+  if (H > 4094 || W > 4094) { set_error("projection block: unsupported feature map %dx%d", H, W); return WINO_E_SHAPE; }
+  const unsigned long long M = (unsigned long long)N * H * W;
+  if (M >= (1ull << 31)) { set_error("projection block: N*H*W = %llu pixel rows (need < 2^31)", M); return WINO_E_SHAPE; }
+  if ((unsigned long long)Hin * Win >= (1ull << 31)) { set_error("projection block: input image too large"); return WINO_E_SHAPE; }
+  // a tile's window over the strided x: consecutive pixel rows are at most s*Win input pixels apart
+  const unsigned long long x_win = ((unsigned long long)(BM - 1) * stride * Win + 1) * Cin * sizeof(float);
+  // ... and over the padded t2: at most 2(W+2)+3 padded pixels apart (the step to the next image)
+  const unsigned long long t_win = ((unsigned long long)(BM - 1) * (2ull * (W + 2) + 3) + 1) * Cm * sizeof(float);
+  // the first launch's ring pass (t1's zero ring) counts 16-byte units in 32 bits
+  const unsigned long long ring = (unsigned long long)N * (2ull * (W + 2) + 2ull * H) * (Cm / 4);
+  const unsigned long long b_tail = (unsigned long long)(Cm + Cin) * C4 * sizeof(float);
+  const unsigned long long b_first = (unsigned long long)Cin * Cm * sizeof(float);
+  if (x_win >= FOUR_GIB || t_win >= FOUR_GIB || ring >= FOUR_GIB || b_tail >= FOUR_GIB || b_first >= FOUR_GIB) {
+    set_error("projection block: a tile's window or a filter matrix reaches 4 GiB (Win=%d Cin=%d Cm=%d C4=%d)", Win, Cin, Cm, C4);
+    return WINO_E_SHAPE;
+  }
+  if ((M + BM - 1) / BM > (1ull << 24)) { set_error("projection block: M too large"); return WINO_E_SHAPE; }
+  *g = ProjGeom{N, Hin, Win, Cin, Cm, C4, stride, H, W, (long)M};
+  return WINO_OK;
+}
+static ProjGeo proj_geo(const ProjGeom& g, const float* x) {
+  return ProjGeo{x, (unsigned)g.Hin * (unsigned)g.Win, (unsigned)(g.s * g.Win), (unsigned)g.s, g.Cin, g.Cm};
+}
+
+// The plans of the two 1x1 launches: the planner and the launch models see each as one GEMM, the tail with
+// K = Cm + Cin.  The latency form's K split must cut both of the tail's sources into 16-channel chunks; a split the
+// planner finds legal for K is legal for both, since Cm % 64 == 0 makes K % (16 KS) == Cin % (16 KS) for KS <= 4.
+static Plan1x1 plan_first(const ProjGeom& g, int cus, const Knobs& kn) { return plan_1x1(g.M, g.Cin, g.Cm, 1, cus, kn); }
+static Plan1x1 plan_tail(const ProjGeom& g, int cus, const Knobs& kn) { return plan_1x1(g.M, g.Cm + g.Cin, g.C4, 1, cus, kn); }
+static int form_of(const Plan1x1& p) { return p.small.use ? WINO_1X1_FORM_LATENCY : p.sk ? WINO_1X1_FORM_STREAM_K : WINO_1X1_FORM_TILED; }
+
+template <int NW, int AF>
+static int launch_tiled(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
+                        const float* bnScale, float* C, long M, int K, int Kout, int flags, PadGeo pg, ProjGeo xg,
+                        hipStream_t s) {
+  using G = Cfg<32, NW>;
+  if (int rc = lds_cap_once<conv1x1_proj_kernel<NW, false, AF>, conv1x1_proj_kernel<NW, true, AF>>(dev, G::LDS_BYTES))
+    return rc;
+  if (p.sk) {
+    SkBufs bufs;
+    if (int rc = tiled_scratch(dev, s, p, &bufs)) return rc;
+    const SkArgs sk{bufs.slabs, bufs.tickets, nullptr, bufs.err};
+    hipLaunchKernelGGL((conv1x1_proj_kernel<NW, true, AF>), dim3(p.sk), dim3(G::NT), G::LDS_BYTES, s, A, B, bnBias,
+                       bnScale, C, M, K, Kout, flags, (int)p.nMB, sk, pg, xg);
+    const int rc = launch_status("conv1x1_proj_kernel (stream-K)");
+    if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
+    return rc;
+  }
+  hipLaunchKernelGGL((conv1x1_proj_kernel<NW, false, AF>), dim3(p.grid), dim3(G::NT), G::LDS_BYTES, s, A, B, bnBias,
+                     bnScale, C, M, K, Kout, flags, (int)p.nMB, SkArgs{nullptr, nullptr, nullptr, nullptr}, pg, xg);
+  return launch_status("conv1x1_proj_kernel");
+}
+template <int AF>
+static int launch_proj_1x1(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
+                           const float* bnScale, float* C, long M, int K, int Kout, int flags, PadGeo pg, ProjGeo xg,
+                           hipStream_t s) {
+  if (p.small.use) {
+    const Small1Plan& pl = p.small;
+    const dim3 grid((unsigned)(Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((M + 16 * pl.rt - 1) / (16 * pl.rt)));
+    hipLaunchKernelGGL(SMALLP_KERNELS[AF - 1][pl.ks >> 1][pl.rt - 1][pl.ct >> 1], grid, dim3(256), 0, s, A, B, bnBias,
+                       bnScale, C, M, K, Kout, flags, pg, xg);
+    return launch_status("conv1x1_small_proj_kernel");
+  }
+  auto* launch = p.four ? launch_tiled<4, AF> : launch_tiled<8, AF>;
+  return launch(p, dev, A, B, bnBias, bnScale, C, M, K, Kout, flags, pg, xg, s);
+}
+
+static int current_cus(int* dev, int* cus) {
+  WINO_HIP(hipGetDevice(dev));
+  return device_cus(*dev, cus);
+}
+
+}  // namespace
+}  // namespace wino
+
+using namespace wino;
+
+extern "C" {
+
+size_t wino_proj_tail_elems(int Cm, int Cin, int C4) {
+  if (Cm <= 0 || Cin <= 0 || C4 <= 0) return 0;
+  return (size_t)(Cm + Cin + 2) * (size_t)C4;
+}
+
+int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3Scale, const float* wp,
+                        const float* bnpBias, const float* bnpScale, float* packed, int Cm, int Cin, int C4, wino_stream_t s) {
+  if (!w3 || !bn3Bias || !bn3Scale || !wp || !bnpBias || !bnpScale || !packed) { set_error("NULL pointer"); return WINO_E_ARG; }
+  if (misaligned16(packed)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (Cm <= 0 || Cin <= 0 || C4 <= 0 || Cin % 32 || Cm % 64 || C4 % 64 ||
+      (unsigned long long)(Cm + Cin) * C4 * sizeof(float) >= FOUR_GIB) {
+    set_error("projection tail: unsupported shape Cm=%d Cin=%d C4=%d (need Cin %% 32 == 0, Cm %% 64 == 0, C4 %% 64 == 0)",
+              Cm, Cin, C4);
+    return WINO_E_SHAPE;
+  }
+  const long total = (long)(Cm + Cin + 2) * C4;
+  hipLaunchKernelGGL(proj_tail_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s, w3,
+                     bn3Bias, bn3Scale, wp, bnpBias, bnpScale, packed, Cm, Cin, C4);
+  return launch_status("proj_tail_pack_kernel");
+}
+
+size_t wino_proj_block_workspace_bytes_hw(int N, int H, int W, int Cm) {
+  if (N < 1 || H < 1 || W < 1 || Cm < 1) return 0;
+  return (size_t)2 * N * (H + 2) * (W + 2) * Cm * sizeof(float);
+}
+
+int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, int cus, int* first_form,
+                        int* tail_form) {
+  if (!first_form || !tail_form || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
+  ProjGeom g;
+  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
+  const Knobs kn = knobs();
+  *first_form = form_of(plan_first(g, cus, kn));   // (stride 1 runs the plain 1x1 entry point: the same plan)
+  *tail_form = form_of(plan_tail(g, cus, kn));
+  return WINO_OK;
+}
+
+int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, wino_stream_t s) {
+  ProjGeom g;
+  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
+  int dev = 0, cus = 0;
+  if (int rc = current_cus(&dev, &cus)) return rc;
+  const Knobs kn = knobs();
+  SkBufs bufs;
+  const Plan1x1 p1 = plan_first(g, cus, kn), pt = plan_tail(g, cus, kn);
+  if (p1.sk)
+    if (int rc = tiled_scratch(dev, (hipStream_t)s, p1, &bufs)) return rc;
+  if (int rc = wino_conv3x3_prepare_hw(N, g.H, g.W, Cm, Cm, s)) return rc;
+  if (pt.sk)
+    if (int rc = tiled_scratch(dev, (hipStream_t)s, pt, &bufs)) return rc;
+  return WINO_OK;
+}
+
+int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale, const float* U2,
+                       const float* bn2Bias, const float* bn2Scale, const float* tail_packed, float* out, int N, int Hin,
+                       int Win, int Cin, int Cm, int C4, int stride, void* workspace, size_t workspace_bytes,
+                       wino_stream_t s) {
+  if (!x || !w1 || !bn1Bias || !bn1Scale || !U2 || !bn2Bias || !bn2Scale || !tail_packed || !out) {
+    set_error("NULL pointer");
+    return WINO_E_ARG;
+  }
+  if (misaligned16(x, w1, U2, out) || misaligned16(tail_packed, workspace)) {
+    set_error("tensor pointers must be 16-byte aligned");
+    return WINO_E_ARG;
+  }
+  ProjGeom g;
+  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
+  const size_t need = wino_proj_block_workspace_bytes_hw(N, g.H, g.W, Cm);
+  if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  int dev = 0, cus = 0;
+  if (int rc = current_cus(&dev, &cus)) return rc;
+  const Knobs kn = knobs();
+  float* t1 = (float*)workspace;
+  float* t2 = t1 + (size_t)N * (g.H + 2) * (g.W + 2) * Cm;
+  const PadGeo pg = make_padgeo(g.H, g.W);
+  const ProjGeo xg = proj_geo(g, x);
+  const hipStream_t hs = (hipStream_t)s;
+  int rc;
+  if (stride == 1)   // xs = x: the plain 1x1 layer, exactly as the identity block's first launch
+    rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, g.H, g.W, Cin, Cm, WINO_RELU | WINO_C_PADDED, s);
+  else
+    rc = launch_proj_1x1<A_STRIDED>(plan_first(g, cus, kn), dev, x, w1, bn1Bias, bn1Scale, t1, g.M, Cin, Cm,
+                                    WINO_RELU | WINO_C_PADDED, pg, xg, hs);
+  if (rc) return rc;
+  rc = wino_conv3x3_bn_relu_hw(t1, U2, bn2Bias, bn2Scale, t2, N, g.H, g.W, Cm, Cm, 1, s);
+  if (rc) return rc;
+  const float* bias = tail_packed + (size_t)(Cm + Cin) * C4;
+  return launch_proj_1x1<A_TWO>(plan_tail(g, cus, kn), dev, t2, tail_packed, bias, bias + C4, out, g.M, Cm + Cin, C4,
+                                WINO_RELU | WINO_A_PADDED, pg, xg, hs);
+}
+
+}  // extern "C"

@@ -50,7 +50,8 @@ extern "C" {
  * wino_diag_conv3x3_clock, wino_debug_tickets_in_use, wino_stream_check, wino_stream_reset_scratch,
  * wino_debug_poison_ticket, wino_diag_last_clock, wino_conv3x3_small_plan, wino_conv1x1_small_plan,
  * wino_conv3x3_plan_groups, wino_conv1x1_small_plan2, wino_conv3x3_small_plan2, wino_debug_conv1x1_models,
- * WINO_E_STATE.  The library-owned stream-K scratch is never freed or moved while its
+ * WINO_E_STATE, wino_proj_tail_elems, wino_proj_tail_pack, wino_proj_block_workspace_bytes_hw,
+ * wino_proj_block_prepare_hw, wino_proj_block_hw, wino_proj_tail_plan, WINO_1X1_FORM_*.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived). */
 #define WINO_ABI_VERSION 1
 
@@ -292,6 +293,38 @@ int wino_residual_block_hw(const float* x, const float* w1, const float* bn1Bias
  * graph capture (the block's analogue of wino_conv3x3_prepare / wino_conv1x1_prepare). */
 int wino_residual_block_prepare(int N, int C4, int Cm, wino_stream_t s);
 int wino_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, wino_stream_t s);
+
+/* ---- ResNet projection (downsampling) bottleneck block: the first block of every stage ----------------
+ * ResNet v1 placement: the stride s sits on the first 1x1 and on the projection shortcut, the 3x3 runs at
+ * stride 1 on the output grid (the Winograd kernel above).  With H = (Hin-1)/s + 1, W = (Win-1)/s + 1 and
+ * xs = x[:, ::s, ::s, :] (never materialised):
+ *   out = relu( bn3(conv1x1(relu(bn2(conv3x3(relu(bn1(conv1x1(xs, w1))), U2))), w3)) + bnp(conv1x1(xs, wp)) )
+ * x [N][Hin][Win][Cin], out [N][H][W][C4] (unpadded); w1 [Cin][Cm]; U2 = packed F(2x2,3x3) filters Cm -> Cm.
+ * The last 1x1 and the projection run as ONE GEMM of K = Cm + Cin (the shortcut never reaches memory) against
+ * `tail_packed`: w3 [Cm][C4], wp [Cin][C4] and the two folded BNs packed by wino_proj_tail_pack
+ * (wino_proj_tail_elems floats; the layout is private to the library, like U's).
+ * Constraints: stride 1 or 2, Cin % 32 == 0, Cm % 64 == 0, C4 % 64 == 0; shapes whose 32-bit tile windows,
+ * pixel rows or ring pass would overflow are rejected (WINO_E_SHAPE).  Three launches on `s`; the padded
+ * intermediates live in `workspace` (wino_proj_block_workspace_bytes_hw(N, H, W, Cm), H x W the OUTPUT grid).
+ * v1.5 placement (stride on the 3x3, torchvision) is not supported: F(2x2,3x3) has no stride-2 form. */
+size_t wino_proj_tail_elems(int Cm, int Cin, int C4);
+int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3Scale, const float* wp,
+                        const float* bnpBias, const float* bnpScale, float* tail_packed, int Cm, int Cin, int C4,
+                        wino_stream_t s);
+size_t wino_proj_block_workspace_bytes_hw(int N, int H, int W, int Cm);
+int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                       const float* U2, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
+                       float* out, int N, int Hin, int Win, int Cin, int Cm, int C4, int stride,
+                       void* workspace, size_t workspace_bytes, wino_stream_t s);
+/* Allocates the library-owned scratch of the block's three launches on `s`, ahead of a graph capture. */
+int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, wino_stream_t s);
+/* Host-side only: the form each of the block's two 1x1 launches takes on a device with `cus` CUs -- the strided
+ * first 1x1 (Cin -> Cm) and the fused tail (K = Cm + Cin -> C4): one of WINO_1X1_FORM_*. */
+#define WINO_1X1_FORM_TILED 0      /* the tiled kernel, one whole tile per workgroup */
+#define WINO_1X1_FORM_STREAM_K 1   /* the tiled kernel in stream-K / split-K form */
+#define WINO_1X1_FORM_LATENCY 2    /* the latency kernel (wino_conv1x1_small_plan2) */
+int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, int cus, int* first_form,
+                        int* tail_form);
 
 /* Independent comparator for the 1x1 layers: one thread per output, fp32 FMA loop. */
 int wino_conv1x1_direct(const float* A, const float* B, const float* bnBias,

@@ -1,0 +1,232 @@
+"""GPU tests of the projection (downsampling) bottleneck block, wino_proj_block_hw: the first block of every ResNet
+stage, v1 placement (stride on the first 1x1 and on the projection).  Three launches -- strided 1x1, Winograd 3x3,
+and the fused tail (last 1x1 + projection shortcut in one GEMM of K = Cm + Cin) -- against the fp64 composition of
+the layer oracles, the comparator kernels, and the four-launch composition the library allowed before."""
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+TIGHT = 2e-5
+
+# ResNet-50's four stage-entry blocks: (Hin, Cin, Cm, C4, stride)
+STAGES = {
+    "conv2": (56, 64, 64, 256, 1),
+    "conv3": (56, 256, 128, 512, 2),
+    "conv4": (28, 512, 256, 1024, 2),
+    "conv5": (14, 1024, 512, 2048, 2),
+}
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch, torch.device("cuda:0")
+
+
+def _weights(rng, Cin, Cm, C4):
+    w1 = ((rng.rand(Cin, Cm) - 0.5) / np.sqrt(Cin) * 4).astype(np.float32)
+    w2 = ((rng.rand(Cm, Cm, 3, 3) - 0.5) / np.sqrt(9 * Cm) * 4).astype(np.float32)
+    w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
+    wp = ((rng.rand(Cin, C4) - 0.5) / np.sqrt(Cin) * 2).astype(np.float32)
+    bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4, C4)]
+    return w1, w2, w3, wp, bn
+
+
+def _oracle(O, x, s, w1, w2, w3, wp, bn):
+    """fp64 composition of the layer oracles: xs = x[:, ::s, ::s], 1x1 + BN + ReLU, 3x3 (pad 1) + BN + ReLU,
+    1x1 + BN, + BN(xs . wp), ReLU."""
+    xs = np.asarray(x, np.float64)[:, ::s, ::s, :]
+    N, H, W, Cin = xs.shape
+    Cm = w1.shape[1]
+    t1 = O.conv1x1_bn(xs.reshape(-1, Cin), w1, bn[0][0], bn[0][1], True).reshape(N, H, W, Cm)
+    t1p = np.zeros((N, H + 2, W + 2, Cm))
+    t1p[:, 1:-1, 1:-1, :] = t1
+    t2 = O.conv3x3_bn_relu_direct(t1p, w2, bn[1][1], bn[1][0], True)[:, 1:-1, 1:-1, :]
+    t3 = O.conv1x1_bn(t2.reshape(-1, Cm), w3, bn[2][0], bn[2][1], False)
+    sc = O.conv1x1_bn(xs.reshape(-1, Cin), wp, bn[3][0], bn[3][1], False)
+    return np.maximum(t3 + sc, 0).reshape(N, H, W, -1)
+
+
+class _Block:
+    """One block's tensors on the GPU, and the library's three ways to run it."""
+
+    def __init__(self, pkg, torch_dev, N, Hin, Win, Cin, Cm, C4, s, seed):
+        self.torch, self.dev = torch_dev
+        self.pkg, self.s = pkg, s
+        rng = np.random.RandomState(seed)
+        self.x = (rng.rand(N, Hin, Win, Cin) - 0.5).astype(np.float32)
+        self.w1, self.w2, self.w3, self.wp, self.bn = _weights(rng, Cin, Cm, C4)
+        t = lambda a: self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
+        self.xt, self.w1t, self.w2t, self.w3t, self.wpt = t(self.x), t(self.w1), t(self.w2), t(self.w3), t(self.wp)
+        self.bnt = [(t(b), t(sc)) for b, sc in self.bn]
+        self.U2 = pkg.filter_transform_f2(self.w2t)
+        self.tail = pkg.proj_tail_pack(self.w3t, self.bnt[2], self.wpt, self.bnt[3])
+        self.H, self.W = (Hin - 1) // s + 1, (Win - 1) // s + 1
+        self.N, self.Cin, self.Cm, self.C4 = N, Cin, Cm, C4
+
+    def run(self, out=None, workspace=None):
+        """The fused block, into NaN-filled output and workspace unless given."""
+        torch = self.torch
+        if out is None:
+            out = torch.full((self.N, self.H, self.W, self.C4), float("nan"), device=self.dev)
+        if workspace is None:
+            need = self.pkg.lib().wino_proj_block_workspace_bytes_hw(self.N, self.H, self.W, self.Cm)
+            workspace = torch.full((need // 4,), float("nan"), device=self.dev)
+        return self.pkg.proj_block(self.xt, self.w1t, self.bnt[0], self.U2, self.bnt[1], self.tail, self.s,
+                                   out=out, workspace=workspace)
+
+    def composed(self):
+        """What the library allowed before: a torch strided copy of x, the projection 1x1 written to memory, then
+        the identity block's three launches with the shortcut added as a residual."""
+        pkg, torch = self.pkg, self.torch
+        xs = self.xt[:, ::self.s, ::self.s, :].contiguous()
+        short = pkg.conv1x1_bn_ex(xs, self.wpt, self.bnt[3][0], self.bnt[3][1], 0)
+        t1p = pkg.conv1x1_bn_ex(xs, self.w1t, self.bnt[0][0], self.bnt[0][1], pkg.RELU | pkg.C_PADDED)
+        t2p = pkg.conv3x3_bn_relu(t1p, self.U2, self.bnt[1][0], self.bnt[1][1])
+        out = pkg.conv1x1_bn_ex(t2p, self.w3t, self.bnt[2][0], self.bnt[2][1],
+                                pkg.RELU | pkg.A_PADDED | pkg.ADD_RESIDUAL, residual=short)
+        return out.reshape(self.N, self.H, self.W, self.C4)
+
+    def oracle(self, O, idx=None):
+        x = self.x if idx is None else self.x[idx]
+        return _oracle(O, x, self.s, self.w1, self.w2, self.w3, self.wp, self.bn)
+
+
+def _check_block(blk, O, got, idx=None):
+    got = got.cpu().numpy()
+    assert np.isfinite(got).all()
+    want = blk.oracle(O, idx)
+    g = got if idx is None else got[idx]
+    assert g.shape == want.shape
+    assert O.rel_error(g, want) < TIGHT
+    assert (want > 0).mean() > 0.2   # both sides of the final ReLU
+    assert blk.pkg.tickets_in_use() == 0
+
+
+@pytest.mark.parametrize("N", [1, 3])
+@pytest.mark.parametrize("stage", sorted(STAGES))
+def test_stage_entry_blocks(stage, N, pkg, O, torch_dev):
+    """ResNet-50's four stage-entry blocks at one image (the latency forms) and a few."""
+    Hin, Cin, Cm, C4, s = STAGES[stage]
+    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=Hin + N)
+    _check_block(blk, O, blk.run())
+
+
+@pytest.mark.parametrize("N,Cin,Cm,C4", [(1, 64, 64, 128), (4, 96, 128, 256)])
+def test_odd_input_stride_two(N, Cin, Cm, C4, pkg, O, torch_dev):
+    """Hin = 15, Win = 13 at stride 2: the (Hin-1)/2 + 1 edge (8 x 7 outputs); Cin = 96 is not a multiple of 64."""
+    blk = _Block(pkg, torch_dev, N, 15, 13, Cin, Cm, C4, 2, seed=1513 + N)
+    assert (blk.H, blk.W) == (8, 7)
+    _check_block(blk, O, blk.run())
+
+
+def test_conv4_block_at_128_images(pkg, O, torch_dev):
+    """The conv4_x entry block at N = 128: sampled images against the fp64 oracle, every element against a chain of
+    the comparator kernels (direct 1x1 on a strided copy, direct 3x3, direct 1x1 for the tail and the projection)."""
+    torch, dev = torch_dev
+    Hin, Cin, Cm, C4, s = STAGES["conv4"]
+    N = 128
+    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=4128)
+    got = blk.run()
+    _check_block(blk, O, got, idx=[0, 77, 127])
+    H, W = blk.H, blk.W
+    xs = blk.xt[:, ::s, ::s, :].contiguous().reshape(-1, Cin)
+    t1 = pkg.conv1x1_direct(xs, blk.w1t, blk.bnt[0][0], blk.bnt[0][1], True)
+    t1p = torch.zeros((N, H + 2, W + 2, Cm), device=dev)
+    t1p[:, 1:-1, 1:-1, :] = t1.reshape(N, H, W, Cm)
+    t2 = pkg.conv3x3_direct(t1p, blk.w2t, blk.bnt[1][0], blk.bnt[1][1], True)[:, 1:-1, 1:-1, :].reshape(-1, Cm)
+    t3 = pkg.conv1x1_direct(t2, blk.w3t, blk.bnt[2][0], blk.bnt[2][1], False)
+    sc = pkg.conv1x1_direct(xs, blk.wpt, blk.bnt[3][0], blk.bnt[3][1], False)
+    chain = torch.relu(t3 + sc).reshape(N, H, W, C4)
+    assert O.rel_error(got.cpu().numpy(), chain.cpu().numpy()) < TIGHT
+
+
+# (knob settings) -> the forms both 1x1 launches are forced into
+FORMS = {
+    "latency": {"WINO_1X1_ALGO": "small"},
+    "latency_ks2": {"WINO_1X1_ALGO": "small", "WINO_1X1_SMALL_KS": 2},
+    "latency_ks4": {"WINO_1X1_ALGO": "small", "WINO_1X1_SMALL_KS": 4},
+    "tiled": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 0},
+    "stream_k": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1},
+    # ranges that do not line up with the tail's phase boundary (Cm/32 = 4 k-steps of t2, then 8 of x)
+    "split_24": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 24},
+    "split_40": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 40},
+    "split_104": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 104},
+}
+
+
+@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("N,Hin,Cin,Cm,C4,s", [(2, 28, 256, 128, 512, 2), (2, 14, 96, 64, 128, 1)])
+def test_forced_forms(form, N, Hin, Cin, Cm, C4, s, pkg, O, torch_dev, knobs):
+    """Every form of both kernel families, including stream-K / split-K segments that start, end or straddle the
+    fused tail's phase boundary; each against the oracle, and all forms against each other to tolerance."""
+    for k, v in FORMS[form].items():
+        knobs.set(k, v)
+    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=N * Hin + Cin)
+    _check_block(blk, O, blk.run())
+
+
+def test_plan_query_names_the_forced_forms(pkg, knobs):
+    """The forms the forced-form test relies on are the ones the plan query reports."""
+    shape = (2, 28, 28, 256, 128, 512, 2)
+    knobs.set("WINO_1X1_ALGO", "small")
+    assert pkg.proj_tail_plan(*shape) == (pkg.FORM_LATENCY, pkg.FORM_LATENCY)
+    knobs.set("WINO_1X1_ALGO", "big")
+    knobs.set("WINO_1X1_SK", 0)
+    assert pkg.proj_tail_plan(*shape) == (pkg.FORM_TILED, pkg.FORM_TILED)
+    knobs.set("WINO_1X1_SK", 1)
+    assert pkg.proj_tail_plan(*shape) == (pkg.FORM_STREAM_K, pkg.FORM_STREAM_K)
+
+
+@pytest.mark.parametrize("stage,N", [("conv3", 1), ("conv4", 8), ("conv5", 32), ("conv2", 2)])
+def test_reproducible_and_equal_to_the_composition(stage, N, pkg, O, torch_dev):
+    """Two calls give bitwise-equal outputs; the result agrees with the four-launch composition of the existing
+    entry points (strided copy, projection 1x1, three launches with the shortcut as residual) to tolerance."""
+    torch, _ = torch_dev
+    Hin, Cin, Cm, C4, s = STAGES[stage]
+    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=77 + N)
+    a = blk.run().clone()
+    b = blk.run()
+    assert torch.equal(a, b)
+    comp = blk.composed()
+    assert O.rel_error(a.cpu().numpy(), comp.cpu().numpy()) < TIGHT
+    assert pkg.tickets_in_use() == 0
+
+
+@pytest.mark.parametrize("stage,N", [("conv4", 20), ("conv3", 1)])
+def test_block_in_a_graph(stage, N, pkg, O, torch_dev):
+    """The three launches captured into one HIP graph after proj_block_prepare: the replay equals eager bit for bit."""
+    torch, dev = torch_dev
+    Hin, Cin, Cm, C4, s = STAGES[stage]
+    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=808 + N)
+    eager = blk.run().clone()
+    out = torch.zeros_like(eager)
+    ws = torch.empty(pkg.lib().wino_proj_block_workspace_bytes_hw(N, blk.H, blk.W, Cm) // 4, device=dev)
+    sg = torch.cuda.Stream()
+    with torch.cuda.stream(sg):
+        pkg.proj_block_prepare(N, Hin, Hin, Cin, Cm, C4, s)
+    sg.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=sg):
+        blk.run(out=out, workspace=ws)
+    for _ in range(2):
+        out.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, eager)
+    with torch.cuda.stream(sg):
+        assert pkg.tickets_in_use() == 0
+    assert pkg.tickets_in_use() == 0
+    _check_block(blk, O, eager, idx=[0])
+
+
+def test_bad_arguments_raise(pkg, torch_dev):
+    torch, dev = torch_dev
+    blk = _Block(pkg, torch_dev, 1, 14, 14, 64, 64, 128, 2, seed=5)
+    with pytest.raises(pkg.WinoError):
+        pkg.proj_block(blk.xt, blk.w1t, blk.bnt[0], blk.U2, blk.bnt[1], blk.tail, 3)
+    ws = torch.empty(16, device=dev)
+    with pytest.raises(pkg.WinoError):
+        blk.run(workspace=ws)

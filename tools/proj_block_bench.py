@@ -1,0 +1,111 @@
+"""Developer tool (GPU box): the projection bottleneck block, fused (wino_proj_block_hw: strided 1x1, 3x3, fused tail)
+against the best composition the library allowed before it (a torch strided copy of x, the projection 1x1 written
+to memory, then the identity block's three launches with the shortcut added as WINO_ADD_RESIDUAL), interleaved.
+usage: python tools/proj_block_bench.py [out.json] [--ns 1,16,128] [--trials 5] [--reps 50]
+Per (stage, N): 0.4 s of preheat, then `trials` rounds; in every round each variant runs `reps` blocks between two
+events.  Reported: the median round per variant (us per block), the ratio, and the chip clock the last 3x3 launch
+of each variant ran at (wino_diag_last_clock)."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import __graft_entry__ as ge  # noqa: E402
+
+STAGES = {   # ResNet-50's stage-entry blocks: (Hin, Cin, Cm, C4, stride)
+    "conv2": (56, 64, 64, 256, 1),
+    "conv3": (56, 256, 128, 512, 2),
+    "conv4": (28, 512, 256, 1024, 2),
+    "conv5": (14, 1024, 512, 2048, 2),
+}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("out", nargs="?", default=None)
+    ap.add_argument("--ns", default="1,16,128")
+    ap.add_argument("--trials", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=50)
+    a = ap.parse_args()
+    pkg = ge.load_package()
+    dev = torch.device("cuda:0")
+    rows = []
+    for stage, (Hin, Cin, Cm, C4, s) in STAGES.items():
+        for N in (int(v) for v in a.ns.split(",")):
+            g = torch.Generator(device="cpu").manual_seed(N)
+            r = lambda *shape, sc=1.0: ((torch.rand(*shape, generator=g) - 0.5) * sc).to(dev)
+            x = r(N, Hin, Hin, Cin)
+            w1, wp = r(Cin, Cm, sc=4 / Cin ** 0.5), r(Cin, C4, sc=2 / Cin ** 0.5)
+            w2, w3 = r(Cm, Cm, 3, 3, sc=4 / (9 * Cm) ** 0.5), r(Cm, C4, sc=4 / Cm ** 0.5)
+            bn = [(r(c), r(c) + 1.0) for c in (Cm, Cm, C4, C4)]
+            U2 = pkg.filter_transform_f2(w2)
+            tail = pkg.proj_tail_pack(w3, bn[2], wp, bn[3])
+            H = (Hin - 1) // s + 1
+            out = torch.empty(N, H, H, C4, device=dev)
+            ws = torch.empty(pkg.lib().wino_proj_block_workspace_bytes_hw(N, H, H, Cm) // 4, device=dev)
+            short = torch.empty(N * H * H, C4, device=dev)
+            t1p = torch.empty(N, H + 2, H + 2, Cm, device=dev)
+            t2p = torch.empty_like(t1p)
+            out2 = torch.empty(N * H * H, C4, device=dev)
+
+            def fused():
+                pkg.proj_block(x, w1, bn[0], U2, bn[1], tail, s, out=out, workspace=ws)
+
+            def composed():
+                xs = x[:, ::s, ::s, :].contiguous() if s > 1 else x
+                pkg.conv1x1_bn_ex(xs, wp, bn[3][0], bn[3][1], 0, out=short)
+                pkg.conv1x1_bn_ex(xs, w1, bn[0][0], bn[0][1], pkg.RELU | pkg.C_PADDED, out=t1p)
+                pkg.conv3x3_bn_relu(t1p, U2, bn[1][0], bn[1][1], out=t2p)
+                pkg.conv1x1_bn_ex(t2p, w3, bn[2][0], bn[2][1], pkg.RELU | pkg.A_PADDED | pkg.ADD_RESIDUAL,
+                                  residual=short, out=out2)
+
+            fns = {"fused": fused, "composed": composed}
+            fused(); composed(); torch.cuda.synchronize()
+            rel = float((out.reshape(-1, C4) - out2).abs().max() / out2.abs().max().clamp_min(1e-30))
+            t0 = time.time()
+            while time.time() - t0 < 0.4:
+                for f in fns.values():
+                    for _ in range(5):
+                        f()
+                torch.cuda.synchronize()
+            times = {k: [] for k in fns}
+            clocks = {k: [] for k in fns}
+            for _ in range(a.trials):
+                for k, f in fns.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    for _ in range(a.reps):
+                        f()
+                    e1.record()
+                    e1.synchronize()
+                    times[k].append(e0.elapsed_time(e1) * 1e3 / a.reps)
+                    c = pkg.last_clock_ghz(0)
+                    clocks[k].append(c[0] if c else None)
+            row = {"stage": stage, "N": N, "Hin": Hin, "Cin": Cin, "Cm": Cm, "C4": C4, "stride": s,
+                   "forms_first_tail": pkg.proj_tail_plan(N, Hin, Hin, Cin, Cm, C4, s),
+                   "fused_us": statistics.median(times["fused"]), "composed_us": statistics.median(times["composed"]),
+                   "fused_trials_us": times["fused"], "composed_trials_us": times["composed"],
+                   "clock_ghz_fused": statistics.median([c for c in clocks["fused"] if c] or [0.0]),
+                   "clock_ghz_composed": statistics.median([c for c in clocks["composed"] if c] or [0.0]),
+                   "rel_diff_fused_vs_composed": rel}
+            row["speedup"] = row["composed_us"] / row["fused_us"]
+            rows.append(row)
+            print(f"{stage} N={N:4d}  fused {row['fused_us']:9.1f} us  composed {row['composed_us']:9.1f} us  "
+                  f"x{row['speedup']:.3f}  clk {row['clock_ghz_fused']:.2f}/{row['clock_ghz_composed']:.2f} GHz  "
+                  f"forms {row['forms_first_tail']}  rel {rel:.1e}", flush=True)
+            del x, out, ws, short, t1p, t2p, out2
+            torch.cuda.empty_cache()
+    res = {"tool": "tools/proj_block_bench.py", "device": torch.cuda.get_device_name(0), "trials": a.trials,
+           "reps": a.reps, "rows": rows}
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()
