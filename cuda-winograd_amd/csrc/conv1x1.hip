@@ -22,9 +22,7 @@
 // The point loop is pinned (sched_barrier) with LDS requests two steps ahead of their use and
 // counted lgkmcnt waits, and the LDS-DMA pieces are issued one per step: see the notes in
 // wino_f2_fused_kernel.h, the same three hipcc behaviours apply here.
-#include "conv1x1_kernel.h"
-#include "conv1x1_plan.h"
-#include "conv1x1_small_kernel.h"
+#include "conv1x1_launch.h"
 
 #include <atomic>
 
@@ -232,7 +230,7 @@ static Small1Plan small1_plan(long M, int Cin, int Kout, int cus, double t_tiled
 // and wino_debug_conv1x1_models: the tiled kernel's form (its stream-K grid and launch model from one sk1_grid call)
 // and the latency form priced against that model.  Every flag of the tiled kernel travels to the latency form;
 // batched launches (batch > 1: gemm_batched) take neither it nor stream-K.
-// (Plan1x1 and Small1Plan: conv1x1_plan.h, shared with the projection block's launches in proj_block.hip)
+// (Plan1x1 and Small1Plan: conv1x1_launch.h, shared with the projection block's launches in proj_block.hip)
 Plan1x1 wino::plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn) {
   Plan1x1 p{};
   p.four = four_waves(Cin, Kout);
@@ -251,65 +249,13 @@ Plan1x1 wino::plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knob
 // the plan of a launch on the current device; *dev receives the device
 static int plan_1x1_here(long M, int Cin, int Kout, int batch, int* dev, Plan1x1* p) {
   int cus = 0;
-  WINO_HIP(hipGetDevice(dev));
-  if (int rc = device_cus(*dev, &cus)) return rc;
+  if (int rc = current_device(dev, &cus)) return rc;
   *p = plan_1x1(M, Cin, Kout, batch, cus, knobs());
   return WINO_OK;
 }
 // the tiled kernel's stream-K scratch: 2 slabs of NW x RB KB per range, a ticket counter per tile
 int wino::tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs) {
   return sk_scratch(dev, s, (size_t)2 * p.sk * (p.four ? 4 : 8) * RB * 1024, (size_t)(p.nMB * p.nblk), bufs);
-}
-
-// the latency kernel's instantiations by [KS / 2][RT - 1][CT / 2]
-#define WINO_SMALL1_CT(KS, RT) {conv1x1_small_kernel<KS, RT, 1>, conv1x1_small_kernel<KS, RT, 2>, conv1x1_small_kernel<KS, RT, 4>}
-static decltype(&conv1x1_small_kernel<1>) const SMALL1_KERNELS[3][2][3] = {
-    {WINO_SMALL1_CT(1, 1), WINO_SMALL1_CT(1, 2)},
-    {WINO_SMALL1_CT(2, 1), WINO_SMALL1_CT(2, 2)},
-    {WINO_SMALL1_CT(4, 1), WINO_SMALL1_CT(4, 2)}};
-#undef WINO_SMALL1_CT
-
-static int launch_1x1_small(const Small1Plan& pl, const float* A, const float* B, const float* bnBias,
-                            const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags, PadGeo pg,
-                            hipStream_t s) {
-  // x = column group, y = row block: see the kernel
-  const dim3 grid((unsigned)(Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((M + 16 * pl.rt - 1) / (16 * pl.rt)));
-  hipLaunchKernelGGL(SMALL1_KERNELS[pl.ks >> 1][pl.rt - 1][pl.ct >> 1], grid, dim3(256), 0, s, A, B, bnBias, bnScale, R, C,
-                     M, Cin, Kout, flags, pg);
-  return launch_status("conv1x1_small_kernel");
-}
-
-// BK = 32 keeps a workgroup at 60 KB of LDS, so two workgroups share a CU (4 waves per SIMD)
-// and one's prologue / barrier bubbles / store tail hide under the other's MFMAs; measured
-// 3-14 % faster than BK = 64 (120 KB, one workgroup per CU) on the four reference shapes.
-template <int NW, bool RES>
-static int launch_1x1_tiled(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
-                            const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags,
-                            hipStream_t s, int batch, long batchA, long batchB, long batchC, PadGeo pg) {
-  using G = Cfg<32, NW>;
-  if (int rc = lds_cap_once<conv1x1_bn_kernel<32, NW, 0, false, RES>, conv1x1_bn_kernel<32, NW, 0, true, RES>>(dev, G::LDS_BYTES))
-    return rc;
-  const int nMB = (int)p.nMB;
-  if (p.sk) {
-    SkBufs bufs;
-    if (int rc = tiled_scratch(dev, s, p, &bufs)) return rc;
-    const SkArgs sk{bufs.slabs, bufs.tickets, nullptr, bufs.err};
-    hipLaunchKernelGGL((conv1x1_bn_kernel<32, NW, 0, true, RES>), dim3(p.sk), dim3(G::NT), G::LDS_BYTES, s, A, B,
-                       bnBias, bnScale, R, C, M, Cin, Kout, flags, nMB, 0L, 0L, 0L, sk, pg);
-    const int rc = launch_status("conv1x1_bn_kernel (stream-K)");
-    if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
-    return rc;
-  }
-  hipLaunchKernelGGL((conv1x1_bn_kernel<32, NW, 0, false, RES>), dim3(p.grid, batch), dim3(G::NT), G::LDS_BYTES, s, A, B,
-                     bnBias, bnScale, R, C, M, Cin, Kout, flags, nMB, batchA, batchB, batchC, SkArgs{nullptr, nullptr, nullptr, nullptr}, pg);
-  return launch_status("conv1x1_bn_kernel");
-}
-static int launch_1x1_tiled(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
-                            const float* bnScale, const float* R, float* C, long M, int Cin, int Kout, int flags,
-                            hipStream_t s, int batch, long batchA, long batchB, long batchC, PadGeo pg) {
-  auto* launch = (flags & WINO_ADD_RESIDUAL) ? (p.four ? launch_1x1_tiled<4, true> : launch_1x1_tiled<8, true>)
-                                             : (p.four ? launch_1x1_tiled<4, false> : launch_1x1_tiled<8, false>);
-  return launch(p, dev, A, B, bnBias, bnScale, R, C, M, Cin, Kout, flags, s, batch, batchA, batchB, batchC, pg);
 }
 
 namespace wino {
@@ -319,15 +265,16 @@ int last_clock_1x1(unsigned long long* stamps) {
 }
 int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int Kout, int batch,
                  long batchA, long batchB, long batchC, hipStream_t s) {
-  if (bad_1x1_dims(Cin, Kout) || M < 1 || batch < 1 || batch > 65535) {
+  if (bad_1x1_dims(Cin, Kout) || M < 1 || batch < 2 || batch > 65535) {
     set_error("unsupported batched GEMM shape");
     return WINO_E_SHAPE;
   }
   int dev = 0;
   Plan1x1 p;
   if (int rc = plan_1x1_here(M, Cin, Kout, batch, &dev, &p)) return rc;
-  return launch_1x1_tiled(p, dev, A, B, nullptr, nullptr, nullptr, C, M, Cin, Kout, gemm1x1::WINO_INTERNAL_NO_BN, s,
-                          batch, batchA, batchB, batchC, make_padgeo(WINO_PQ, WINO_PQ));
+  const Operands1x1 o{A, B, nullptr, nullptr, nullptr, C, M, Cin, Kout, WINO_INTERNAL_NO_BN, make_padgeo(WINO_PQ, WINO_PQ),
+                      {}, batch, batchA, batchB, batchC};
+  return launch_1x1<A_PLAIN>(p, dev, o, s);
 }
 }  // namespace wino
 
@@ -355,8 +302,7 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
   int dev = 0;
   Plan1x1 p;
   if (int rc = plan_1x1_here(M, Cin, Kout, 1, &dev, &p)) return rc;
-  if (p.small.use) return launch_1x1_small(p.small, A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg, (hipStream_t)s);
-  return launch_1x1_tiled(p, dev, A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, (hipStream_t)s, 1, 0, 0, 0, pg);
+  return launch_1x1<A_PLAIN>(p, dev, {A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg}, (hipStream_t)s);
 }
 
 extern "C" {

@@ -1,0 +1,123 @@
+// The 1x1 kernels' launch plan and launcher, shared by the translation units that launch them: conv1x1.hip (the plain
+// operand form, A_PLAIN) and proj_block.hip (the projection block's A_STRIDED / A_TWO forms, conv1x1_kernel.h).
+// A template is instantiated where it is used, so each file compiles the kernels of its own forms and no others.
+#pragma once
+#include "conv1x1_kernel.h"
+#include "conv1x1_small_kernel.h"
+
+namespace wino {
+
+// The latency form's choice (conv1x1_small_kernel.h): use it or not, its K split and MFMA tiles per wave.
+struct Small1Plan {
+  bool use;
+  int ks, rt, ct;
+  long long wgs;
+  double t_us, t_big_us;   // the two launch models' times
+};
+// The plan of one launch, read by every consumer -- see plan_1x1 in conv1x1.hip.
+struct Plan1x1 {
+  bool four;            // 4-wave workgroups (64 columns), else 8 (128)
+  int nblk, nk;         // column blocks, k-steps
+  long long nMB;        // row tiles
+  int sk;               // stream-K / split-K grid, 0: the plain form
+  int grid;             // the tiled launch's grid (per batch)
+  Small1Plan small;
+};
+Plan1x1 plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn);
+// the tiled kernel's stream-K scratch of stream `s` for this plan (sk_scratch)
+int tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs);
+
+// One launch's operands.  R: the residual (A_PLAIN, WINO_ADD_RESIDUAL); xg: the strided / second source (A_STRIDED,
+// A_TWO); batch and the per-batch strides: the batched plain GEMM (gemm_batched; its plans have no stream-K form).
+struct Operands1x1 {
+  const float *A, *B, *bnBias, *bnScale, *R;
+  float* C;
+  long M;
+  int Cin, Kout, flags;
+  gemm1x1::PadGeo pg;
+  gemm1x1::ProjGeo xg = {};
+  int batch = 1;
+  long batchA = 0, batchB = 0, batchC = 0;
+};
+
+// The kernels of operand form AF: the tiled kernel (RES: the plain form's residual epilogue) and the latency kernel.
+template <int NW, bool SK, int AF, bool RES>
+constexpr auto tiled_1x1_kernel() {
+  if constexpr (AF == gemm1x1::A_PLAIN) return gemm1x1::conv1x1_bn_kernel<32, NW, 0, SK, RES>;
+  else return gemm1x1::conv1x1_proj_kernel<NW, SK, AF>;
+}
+template <int AF, int KS, int RT, int CT>
+constexpr auto small_1x1_kernel() {
+  if constexpr (AF == gemm1x1::A_PLAIN) return gemm1x1::conv1x1_small_kernel<KS, RT, CT>;
+  else return gemm1x1::conv1x1_small_proj_kernel<KS, RT, CT, AF>;
+}
+// the latency kernel's instantiations by [KS / 2][RT - 1][CT / 2]
+template <int AF>
+constexpr decltype(small_1x1_kernel<AF, 1, 1, 1>()) SMALL_1X1_KERNELS[3][2][3] = {
+    {{small_1x1_kernel<AF, 1, 1, 1>(), small_1x1_kernel<AF, 1, 1, 2>(), small_1x1_kernel<AF, 1, 1, 4>()},
+     {small_1x1_kernel<AF, 1, 2, 1>(), small_1x1_kernel<AF, 1, 2, 2>(), small_1x1_kernel<AF, 1, 2, 4>()}},
+    {{small_1x1_kernel<AF, 2, 1, 1>(), small_1x1_kernel<AF, 2, 1, 2>(), small_1x1_kernel<AF, 2, 1, 4>()},
+     {small_1x1_kernel<AF, 2, 2, 1>(), small_1x1_kernel<AF, 2, 2, 2>(), small_1x1_kernel<AF, 2, 2, 4>()}},
+    {{small_1x1_kernel<AF, 4, 1, 1>(), small_1x1_kernel<AF, 4, 1, 2>(), small_1x1_kernel<AF, 4, 1, 4>()},
+     {small_1x1_kernel<AF, 4, 2, 1>(), small_1x1_kernel<AF, 4, 2, 2>(), small_1x1_kernel<AF, 4, 2, 4>()}}};
+
+template <int NW, bool SK, int AF, bool RES>
+int launch_tiled_1x1_kernel(dim3 grid, int nMB, const Operands1x1& o, gemm1x1::SkArgs sk, hipStream_t s) {
+  using G = gemm1x1::Cfg<32, NW>;
+  if constexpr (AF == gemm1x1::A_PLAIN) {
+    hipLaunchKernelGGL((gemm1x1::conv1x1_bn_kernel<32, NW, 0, SK, RES>), grid, dim3(G::NT), G::LDS_BYTES, s, o.A, o.B,
+                       o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout, o.flags, nMB, o.batchA, o.batchB, o.batchC, sk,
+                       o.pg);
+    return launch_status(SK ? "conv1x1_bn_kernel (stream-K)" : "conv1x1_bn_kernel");
+  } else {
+    hipLaunchKernelGGL((gemm1x1::conv1x1_proj_kernel<NW, SK, AF>), grid, dim3(G::NT), G::LDS_BYTES, s, o.A, o.B,
+                       o.bnBias, o.bnScale, o.C, o.M, o.Cin, o.Kout, o.flags, nMB, sk, o.pg, o.xg);
+    return launch_status(SK ? "conv1x1_proj_kernel (stream-K)" : "conv1x1_proj_kernel");
+  }
+}
+
+// BK = 32 keeps a workgroup at 60 KB of LDS, so two workgroups share a CU (4 waves per SIMD)
+// and one's prologue / barrier bubbles / store tail hide under the other's MFMAs; measured
+// 3-14 % faster than BK = 64 (120 KB, one workgroup per CU) on the four reference shapes.
+template <int NW, int AF, bool RES>
+int launch_tiled_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
+  constexpr int LDS_BYTES = gemm1x1::Cfg<32, NW>::LDS_BYTES;
+  if (int rc = lds_cap_once<tiled_1x1_kernel<NW, false, AF, RES>(), tiled_1x1_kernel<NW, true, AF, RES>()>(dev, LDS_BYTES))
+    return rc;
+  if (!p.sk)
+    return launch_tiled_1x1_kernel<NW, false, AF, RES>(dim3(p.grid, o.batch), (int)p.nMB, o,
+                                                       gemm1x1::SkArgs{nullptr, nullptr, nullptr, nullptr}, s);
+  SkBufs bufs;
+  if (int rc = tiled_scratch(dev, s, p, &bufs)) return rc;
+  const int rc = launch_tiled_1x1_kernel<NW, true, AF, RES>(dim3(p.sk), (int)p.nMB, o,
+                                                            gemm1x1::SkArgs{bufs.slabs, bufs.tickets, nullptr, bufs.err}, s);
+  if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
+  return rc;
+}
+
+// One launch of the 1x1 GEMM in operand form AF as planned: the latency form, or the tiled kernel with 4 or 8 waves,
+// plain or stream-K.
+template <int AF>
+int launch_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
+  if (p.small.use) {
+    const Small1Plan& pl = p.small;
+    const auto kernel = SMALL_1X1_KERNELS<AF>[pl.ks >> 1][pl.rt - 1][pl.ct >> 1];
+    // x = column group, y = row block: see the kernel
+    const dim3 grid((unsigned)(o.Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((o.M + 16 * pl.rt - 1) / (16 * pl.rt)));
+    if constexpr (AF == gemm1x1::A_PLAIN) {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.A, o.B, o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout,
+                         o.flags, o.pg);
+      return launch_status("conv1x1_small_kernel");
+    } else {
+      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.A, o.B, o.bnBias, o.bnScale, o.C, o.M, o.Cin, o.Kout, o.flags,
+                         o.pg, o.xg);
+      return launch_status("conv1x1_small_proj_kernel");
+    }
+  }
+  auto* launch = p.four ? launch_tiled_1x1<4, AF, false> : launch_tiled_1x1<8, AF, false>;
+  if constexpr (AF == gemm1x1::A_PLAIN)   // the residual epilogue is a compile-time property (conv1x1_kernel.h)
+    if (o.flags & WINO_ADD_RESIDUAL) launch = p.four ? launch_tiled_1x1<4, AF, true> : launch_tiled_1x1<8, AF, true>;
+  return launch(p, dev, o, s);
+}
+
+}  // namespace wino

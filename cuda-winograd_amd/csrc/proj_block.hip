@@ -7,11 +7,10 @@
 // Three launches: the strided 1x1 (s = 1: the plain 1x1 entry point), the Winograd 3x3, and the FUSED TAIL -- one
 // GEMM of K = Cm + Cin whose k-steps read t2 first and the strided x after it (conv1x1_kernel.h, A_TWO), against
 // the stacked, scale-folded [bn3Scale . w3 ; bnpScale . wp] with the summed bias: the shortcut is accumulated in
-// the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernels of conv1x1.hip in
-// their A_STRIDED / A_TWO operand forms, instantiated here so that conv1x1.hip's own stay exactly what they were.
-#include "conv1x1_kernel.h"
-#include "conv1x1_plan.h"
-#include "conv1x1_small_kernel.h"
+// the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernels in their A_STRIDED /
+// A_TWO operand forms, launched by the same launch_1x1 as conv1x1.hip's (conv1x1_launch.h).  This file's calls
+// instantiate them here, so that conv1x1.hip compiles exactly the kernels it did before these forms existed.
+#include "conv1x1_launch.h"
 
 namespace wino {
 namespace {
@@ -36,17 +35,6 @@ __global__ void proj_tail_pack_kernel(const float* __restrict__ w3, const float*
   else v = 1.f;
   packed[i] = v;
 }
-
-// The latency kernel's projection forms by [AF - 1][KS / 2][RT - 1][CT / 2].
-#define WINO_SMALLP_CT(KS, RT, AF) \
-  {conv1x1_small_proj_kernel<KS, RT, 1, AF>, conv1x1_small_proj_kernel<KS, RT, 2, AF>, conv1x1_small_proj_kernel<KS, RT, 4, AF>}
-#define WINO_SMALLP_AF(AF) \
-  {{WINO_SMALLP_CT(1, 1, AF), WINO_SMALLP_CT(1, 2, AF)}, {WINO_SMALLP_CT(2, 1, AF), WINO_SMALLP_CT(2, 2, AF)}, \
-   {WINO_SMALLP_CT(4, 1, AF), WINO_SMALLP_CT(4, 2, AF)}}
-static decltype(&conv1x1_small_proj_kernel<1, 1, 1, A_STRIDED>) const SMALLP_KERNELS[2][3][2][3] = {
-    WINO_SMALLP_AF(A_STRIDED), WINO_SMALLP_AF(A_TWO)};
-#undef WINO_SMALLP_AF
-#undef WINO_SMALLP_CT
 
 // The block's geometry, checked once.  Every 32-bit quantity the strided / two-source addressing creates is bounded
 // here: the pixel row index (M < 2^31, one input image < 2^31 pixels), the buffer-descriptor windows of a 112-row tile
@@ -96,47 +84,6 @@ static Plan1x1 plan_first(const ProjGeom& g, int cus, const Knobs& kn) { return 
 static Plan1x1 plan_tail(const ProjGeom& g, int cus, const Knobs& kn) { return plan_1x1(g.M, g.Cm + g.Cin, g.C4, 1, cus, kn); }
 static int form_of(const Plan1x1& p) { return p.small.use ? WINO_1X1_FORM_LATENCY : p.sk ? WINO_1X1_FORM_STREAM_K : WINO_1X1_FORM_TILED; }
 
-template <int NW, int AF>
-static int launch_tiled(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
-                        const float* bnScale, float* C, long M, int K, int Kout, int flags, PadGeo pg, ProjGeo xg,
-                        hipStream_t s) {
-  using G = Cfg<32, NW>;
-  if (int rc = lds_cap_once<conv1x1_proj_kernel<NW, false, AF>, conv1x1_proj_kernel<NW, true, AF>>(dev, G::LDS_BYTES))
-    return rc;
-  if (p.sk) {
-    SkBufs bufs;
-    if (int rc = tiled_scratch(dev, s, p, &bufs)) return rc;
-    const SkArgs sk{bufs.slabs, bufs.tickets, nullptr, bufs.err};
-    hipLaunchKernelGGL((conv1x1_proj_kernel<NW, true, AF>), dim3(p.sk), dim3(G::NT), G::LDS_BYTES, s, A, B, bnBias,
-                       bnScale, C, M, K, Kout, flags, (int)p.nMB, sk, pg, xg);
-    const int rc = launch_status("conv1x1_proj_kernel (stream-K)");
-    if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
-    return rc;
-  }
-  hipLaunchKernelGGL((conv1x1_proj_kernel<NW, false, AF>), dim3(p.grid), dim3(G::NT), G::LDS_BYTES, s, A, B, bnBias,
-                     bnScale, C, M, K, Kout, flags, (int)p.nMB, SkArgs{nullptr, nullptr, nullptr, nullptr}, pg, xg);
-  return launch_status("conv1x1_proj_kernel");
-}
-template <int AF>
-static int launch_proj_1x1(const Plan1x1& p, int dev, const float* A, const float* B, const float* bnBias,
-                           const float* bnScale, float* C, long M, int K, int Kout, int flags, PadGeo pg, ProjGeo xg,
-                           hipStream_t s) {
-  if (p.small.use) {
-    const Small1Plan& pl = p.small;
-    const dim3 grid((unsigned)(Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((M + 16 * pl.rt - 1) / (16 * pl.rt)));
-    hipLaunchKernelGGL(SMALLP_KERNELS[AF - 1][pl.ks >> 1][pl.rt - 1][pl.ct >> 1], grid, dim3(256), 0, s, A, B, bnBias,
-                       bnScale, C, M, K, Kout, flags, pg, xg);
-    return launch_status("conv1x1_small_proj_kernel");
-  }
-  auto* launch = p.four ? launch_tiled<4, AF> : launch_tiled<8, AF>;
-  return launch(p, dev, A, B, bnBias, bnScale, C, M, K, Kout, flags, pg, xg, s);
-}
-
-static int current_cus(int* dev, int* cus) {
-  WINO_HIP(hipGetDevice(dev));
-  return device_cus(*dev, cus);
-}
-
 }  // namespace
 }  // namespace wino
 
@@ -185,7 +132,7 @@ int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4,
   ProjGeom g;
   if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
   int dev = 0, cus = 0;
-  if (int rc = current_cus(&dev, &cus)) return rc;
+  if (int rc = current_device(&dev, &cus)) return rc;
   const Knobs kn = knobs();
   SkBufs bufs;
   const Plan1x1 p1 = plan_first(g, cus, kn), pt = plan_tail(g, cus, kn);
@@ -214,7 +161,7 @@ int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, co
   const size_t need = wino_proj_block_workspace_bytes_hw(N, g.H, g.W, Cm);
   if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
   int dev = 0, cus = 0;
-  if (int rc = current_cus(&dev, &cus)) return rc;
+  if (int rc = current_device(&dev, &cus)) return rc;
   const Knobs kn = knobs();
   float* t1 = (float*)workspace;
   float* t2 = t1 + (size_t)N * (g.H + 2) * (g.W + 2) * Cm;
@@ -225,14 +172,15 @@ int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, co
   if (stride == 1)   // xs = x: the plain 1x1 layer, exactly as the identity block's first launch
     rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, g.H, g.W, Cin, Cm, WINO_RELU | WINO_C_PADDED, s);
   else
-    rc = launch_proj_1x1<A_STRIDED>(plan_first(g, cus, kn), dev, x, w1, bn1Bias, bn1Scale, t1, g.M, Cin, Cm,
-                                    WINO_RELU | WINO_C_PADDED, pg, xg, hs);
+    rc = launch_1x1<A_STRIDED>(plan_first(g, cus, kn), dev,
+                               {x, w1, bn1Bias, bn1Scale, nullptr, t1, g.M, Cin, Cm, WINO_RELU | WINO_C_PADDED, pg, xg}, hs);
   if (rc) return rc;
   rc = wino_conv3x3_bn_relu_hw(t1, U2, bn2Bias, bn2Scale, t2, N, g.H, g.W, Cm, Cm, 1, s);
   if (rc) return rc;
   const float* bias = tail_packed + (size_t)(Cm + Cin) * C4;
-  return launch_proj_1x1<A_TWO>(plan_tail(g, cus, kn), dev, t2, tail_packed, bias, bias + C4, out, g.M, Cm + Cin, C4,
-                                WINO_RELU | WINO_A_PADDED, pg, xg, hs);
+  return launch_1x1<A_TWO>(plan_tail(g, cus, kn), dev,
+                           {t2, tail_packed, bias, bias + C4, nullptr, out, g.M, Cm + Cin, C4, WINO_RELU | WINO_A_PADDED, pg, xg},
+                           hs);
 }
 
 }  // extern "C"

@@ -46,7 +46,9 @@ int sk_scratch(int dev, hipStream_t s, size_t slab_bytes, size_t n_tickets, SkBu
 int sk_scratch_release(hipStream_t s);   // wino_stream_destroy: the stream's scratch, on every device
 // A launch that had been handed the scratch failed: the stream's counters can no longer be trusted.
 void sk_mark_failed(int dev, hipStream_t s);
-int device_cus(int dev, int* cus);
+int device_cus(int dev, int* cus);   // cached per device
+// The calling thread's current device and its CU count: the device query of every launch.
+int current_device(int* dev, int* cus);
 // Developer knobs (WINO_* environment variables), read once per process at first use and cached;
 // wino_debug_reload_knobs() re-reads them (tests sweep the launch decompositions that way).
 struct Knobs {
@@ -87,7 +89,8 @@ int lds_cap_once(int dev, int bytes) {
 }
 
 // Defined in conv1x1.hip: the 1x1 kernels' clock stamps (wino_diag_last_clock), and the batched plain GEMM
-// C_b = A_b . B_b (no BN) on the tiled 1x1 kernel that the F(4x4) compatibility path runs.
+// C_b = A_b . B_b (no BN, batch >= 2: the planner gives such launches the tiled kernel, the only one that can skip
+// the BN) that the F(4x4) compatibility path runs.
 int last_clock_1x1(unsigned long long* stamps);
 int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int Kout, int batch,
                  long batchA, long batchB, long batchC, hipStream_t s);

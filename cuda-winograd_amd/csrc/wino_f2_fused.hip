@@ -395,9 +395,8 @@ static Plan3x3 plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs&
 
 // the plan of a launch on the current device; *dev receives the device
 static int plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p) {
-  int cus = 0;   // one device query per launch; the CU count is cached per device
-  WINO_HIP(hipGetDevice(dev));
-  if (int rc = device_cus(*dev, &cus)) return rc;
+  int cus = 0;
+  if (int rc = current_device(dev, &cus)) return rc;
   *p = plan_3x3(N, H, W, C, K, cus, knobs(), throughput);
   return WINO_OK;
 }

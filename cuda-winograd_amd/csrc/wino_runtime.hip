@@ -178,6 +178,11 @@ int device_cus(int dev, int* cus) {
   return WINO_OK;
 }
 
+int current_device(int* dev, int* cus) {
+  WINO_HIP(hipGetDevice(dev));
+  return device_cus(*dev, cus);
+}
+
 }  // namespace wino
 
 using namespace wino;
