@@ -23,7 +23,7 @@ all: $(LIB) Test
 $(BUILD):
 	mkdir -p $(BUILD)
 
-$(BUILD)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) $(wildcard $(CSRC)/*.inc) include/winograd_mi355x.h | $(BUILD)
+$(BUILD)/%.o: $(CSRC)/%.hip $(wildcard $(CSRC)/*.h) include/winograd_mi355x.h | $(BUILD)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 $(BUILD)/cpu_baseline.o: CFLAGS := -O3 -march=x86-64-v3 -fPIC -std=gnu11 -Iinclude -I$(HOST) -Wall

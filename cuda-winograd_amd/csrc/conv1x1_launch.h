@@ -40,40 +40,29 @@ struct Operands1x1 {
   long batchA = 0, batchB = 0, batchC = 0;
 };
 
-// The kernels of operand form AF: the tiled kernel (RES: the plain form's residual epilogue) and the latency kernel.
-template <int NW, bool SK, int AF, bool RES>
-constexpr auto tiled_1x1_kernel() {
-  if constexpr (AF == gemm1x1::A_PLAIN) return gemm1x1::conv1x1_bn_kernel<32, NW, 0, SK, RES>;
-  else return gemm1x1::conv1x1_proj_kernel<NW, SK, AF>;
-}
-template <int AF, int KS, int RT, int CT>
-constexpr auto small_1x1_kernel() {
-  if constexpr (AF == gemm1x1::A_PLAIN) return gemm1x1::conv1x1_small_kernel<KS, RT, CT>;
-  else return gemm1x1::conv1x1_small_proj_kernel<KS, RT, CT, AF>;
-}
 // the latency kernel's instantiations by [KS / 2][RT - 1][CT / 2]
 template <int AF>
-constexpr decltype(small_1x1_kernel<AF, 1, 1, 1>()) SMALL_1X1_KERNELS[3][2][3] = {
-    {{small_1x1_kernel<AF, 1, 1, 1>(), small_1x1_kernel<AF, 1, 1, 2>(), small_1x1_kernel<AF, 1, 1, 4>()},
-     {small_1x1_kernel<AF, 1, 2, 1>(), small_1x1_kernel<AF, 1, 2, 2>(), small_1x1_kernel<AF, 1, 2, 4>()}},
-    {{small_1x1_kernel<AF, 2, 1, 1>(), small_1x1_kernel<AF, 2, 1, 2>(), small_1x1_kernel<AF, 2, 1, 4>()},
-     {small_1x1_kernel<AF, 2, 2, 1>(), small_1x1_kernel<AF, 2, 2, 2>(), small_1x1_kernel<AF, 2, 2, 4>()}},
-    {{small_1x1_kernel<AF, 4, 1, 1>(), small_1x1_kernel<AF, 4, 1, 2>(), small_1x1_kernel<AF, 4, 1, 4>()},
-     {small_1x1_kernel<AF, 4, 2, 1>(), small_1x1_kernel<AF, 4, 2, 2>(), small_1x1_kernel<AF, 4, 2, 4>()}}};
+constexpr decltype(&gemm1x1::conv1x1_small_kernel<1, 1, 1, AF>) SMALL_1X1_KERNELS[3][2][3] = {
+    {{gemm1x1::conv1x1_small_kernel<1, 1, 1, AF>, gemm1x1::conv1x1_small_kernel<1, 1, 2, AF>,
+      gemm1x1::conv1x1_small_kernel<1, 1, 4, AF>},
+     {gemm1x1::conv1x1_small_kernel<1, 2, 1, AF>, gemm1x1::conv1x1_small_kernel<1, 2, 2, AF>,
+      gemm1x1::conv1x1_small_kernel<1, 2, 4, AF>}},
+    {{gemm1x1::conv1x1_small_kernel<2, 1, 1, AF>, gemm1x1::conv1x1_small_kernel<2, 1, 2, AF>,
+      gemm1x1::conv1x1_small_kernel<2, 1, 4, AF>},
+     {gemm1x1::conv1x1_small_kernel<2, 2, 1, AF>, gemm1x1::conv1x1_small_kernel<2, 2, 2, AF>,
+      gemm1x1::conv1x1_small_kernel<2, 2, 4, AF>}},
+    {{gemm1x1::conv1x1_small_kernel<4, 1, 1, AF>, gemm1x1::conv1x1_small_kernel<4, 1, 2, AF>,
+      gemm1x1::conv1x1_small_kernel<4, 1, 4, AF>},
+     {gemm1x1::conv1x1_small_kernel<4, 2, 1, AF>, gemm1x1::conv1x1_small_kernel<4, 2, 2, AF>,
+      gemm1x1::conv1x1_small_kernel<4, 2, 4, AF>}}};
 
 template <int NW, bool SK, int AF, bool RES>
 int launch_tiled_1x1_kernel(dim3 grid, int nMB, const Operands1x1& o, gemm1x1::SkArgs sk, hipStream_t s) {
   using G = gemm1x1::Cfg<32, NW>;
-  if constexpr (AF == gemm1x1::A_PLAIN) {
-    hipLaunchKernelGGL((gemm1x1::conv1x1_bn_kernel<32, NW, 0, SK, RES>), grid, dim3(G::NT), G::LDS_BYTES, s, o.A, o.B,
-                       o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout, o.flags, nMB, o.batchA, o.batchB, o.batchC, sk,
-                       o.pg);
-    return launch_status(SK ? "conv1x1_bn_kernel (stream-K)" : "conv1x1_bn_kernel");
-  } else {
-    hipLaunchKernelGGL((gemm1x1::conv1x1_proj_kernel<NW, SK, AF>), grid, dim3(G::NT), G::LDS_BYTES, s, o.A, o.B,
-                       o.bnBias, o.bnScale, o.C, o.M, o.Cin, o.Kout, o.flags, nMB, sk, o.pg, o.xg);
-    return launch_status(SK ? "conv1x1_proj_kernel (stream-K)" : "conv1x1_proj_kernel");
-  }
+  hipLaunchKernelGGL((gemm1x1::conv1x1_bn_kernel<32, NW, 0, SK, RES, AF>), grid, dim3(G::NT), G::LDS_BYTES, s, o.A,
+                     o.B, o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout, o.flags, nMB, o.batchA, o.batchB, o.batchC, sk,
+                     o.pg, o.xg);
+  return launch_status(SK ? "conv1x1_bn_kernel (stream-K)" : "conv1x1_bn_kernel");
 }
 
 // BK = 32 keeps a workgroup at 60 KB of LDS, so two workgroups share a CU (4 waves per SIMD)
@@ -82,7 +71,8 @@ int launch_tiled_1x1_kernel(dim3 grid, int nMB, const Operands1x1& o, gemm1x1::S
 template <int NW, int AF, bool RES>
 int launch_tiled_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
   constexpr int LDS_BYTES = gemm1x1::Cfg<32, NW>::LDS_BYTES;
-  if (int rc = lds_cap_once<tiled_1x1_kernel<NW, false, AF, RES>(), tiled_1x1_kernel<NW, true, AF, RES>()>(dev, LDS_BYTES))
+  if (int rc = lds_cap_once<gemm1x1::conv1x1_bn_kernel<32, NW, 0, false, RES, AF>,
+                            gemm1x1::conv1x1_bn_kernel<32, NW, 0, true, RES, AF>>(dev, LDS_BYTES))
     return rc;
   if (!p.sk)
     return launch_tiled_1x1_kernel<NW, false, AF, RES>(dim3(p.grid, o.batch), (int)p.nMB, o,
@@ -104,15 +94,9 @@ int launch_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
     const auto kernel = SMALL_1X1_KERNELS<AF>[pl.ks >> 1][pl.rt - 1][pl.ct >> 1];
     // x = column group, y = row block: see the kernel
     const dim3 grid((unsigned)(o.Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((o.M + 16 * pl.rt - 1) / (16 * pl.rt)));
-    if constexpr (AF == gemm1x1::A_PLAIN) {
-      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.A, o.B, o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout,
-                         o.flags, o.pg);
-      return launch_status("conv1x1_small_kernel");
-    } else {
-      hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.A, o.B, o.bnBias, o.bnScale, o.C, o.M, o.Cin, o.Kout, o.flags,
-                         o.pg, o.xg);
-      return launch_status("conv1x1_small_proj_kernel");
-    }
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.A, o.B, o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout,
+                       o.flags, o.pg, o.xg);
+    return launch_status("conv1x1_small_kernel");
   }
   auto* launch = p.four ? launch_tiled_1x1<4, AF, false> : launch_tiled_1x1<8, AF, false>;
   if constexpr (AF == gemm1x1::A_PLAIN)   // the residual epilogue is a compile-time property (conv1x1_kernel.h)

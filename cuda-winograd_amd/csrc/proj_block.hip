@@ -7,9 +7,9 @@
 // Three launches: the strided 1x1 (s = 1: the plain 1x1 entry point), the Winograd 3x3, and the FUSED TAIL -- one
 // GEMM of K = Cm + Cin whose k-steps read t2 first and the strided x after it (conv1x1_kernel.h, A_TWO), against
 // the stacked, scale-folded [bn3Scale . w3 ; bnpScale . wp] with the summed bias: the shortcut is accumulated in
-// the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernels in their A_STRIDED /
-// A_TWO operand forms, launched by the same launch_1x1 as conv1x1.hip's (conv1x1_launch.h).  This file's calls
-// instantiate them here, so that conv1x1.hip compiles exactly the kernels it did before these forms existed.
+// the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernel templates with the
+// operand form as a template argument (AF = A_STRIDED / A_TWO), launched by the same launch_1x1 as conv1x1.hip's
+// (conv1x1_launch.h).  This file's calls instantiate those forms here; conv1x1.hip instantiates only A_PLAIN.
 #include "conv1x1_launch.h"
 
 namespace wino {

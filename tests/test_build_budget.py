@@ -65,8 +65,20 @@ def _compile_report(src, tmp_path):
     return kernels
 
 
+def _template_args(name, family):
+    """The template arguments (bools as 0 / 1) of `name` if it is a mangled instantiation of the kernel template
+    `family`, else None.  The 1x1 kernels' last argument is their operand form AF (conv1x1_kernel.h)."""
+    m = re.search(family + r"I((?:L[ib]\d+E)+)E", name)
+    return [int(x) for x in re.findall(r"L[ib](\d+)E", m.group(1))] if m else None
+
+
+def _plain_1x1(kernels, family):
+    """The instantiations of the 1x1 kernel template `family` in the plain operand form (AF = A_PLAIN = 0)."""
+    return {n: v for n, v in kernels.items() if (_template_args(n, family) or [None])[-1] == 0}
+
+
 def test_gemm_kernel_keeps_four_waves_per_simd(tmp_path):
-    k = {n: v for n, v in _compile_report("conv1x1.hip", tmp_path).items() if "conv1x1_bn_kernel" in n}
+    k = _plain_1x1(_compile_report("conv1x1.hip", tmp_path), "conv1x1_bn_kernel")
     assert len(k) == 8, sorted(k)          # {4, 8 waves} x {plain, stream-K} x {no residual, residual}
     for name, v in k.items():
         # 8-wave form: 60 KB of LDS -> two workgroups per CU -> 4 waves per SIMD -> 128 VGPRs.
@@ -106,7 +118,7 @@ def test_latency_kernels_spill_nothing(tmp_path):
         assert v["mfma"] >= 32, (name, v)
     sub = tmp_path / "one"
     sub.mkdir()
-    k1 = {n: v for n, v in _compile_report("conv1x1.hip", sub).items() if "conv1x1_small_kernel" in n}
+    k1 = _plain_1x1(_compile_report("conv1x1.hip", sub), "conv1x1_small_kernel")
     assert len(k1) == 18, sorted(k1)               # KS {1, 2, 4} x RT {1, 2} x CT {1, 2, 4}
     for name, v in k1.items():
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)

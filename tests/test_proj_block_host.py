@@ -8,7 +8,7 @@ import os
 import pytest
 
 from conftest import ROOT
-from test_build_budget import _compile_report
+from test_build_budget import _compile_report, _template_args
 
 STAGES = {   # (Hin, Cin, Cm, C4, stride): ResNet-50's stage-entry blocks
     "conv2": (56, 64, 64, 256, 1),
@@ -115,29 +115,38 @@ def test_plan_routing_at_the_stage_shapes(pkg, knobs):
     assert _plan(pkg, 2, 28, 28, 256, 128, 512, 2)[1] == (pkg.FORM_TILED,) * 2
 
 
-def test_proj_block_build_budget(tmp_path):
-    """The new forms keep the budgets of the forms they come from (tests/test_build_budget.py): the tiled kernel
+def test_proj_form_kernels_build_budget(tmp_path):
+    """proj_block.hip instantiates the 1x1 kernel templates in the projection forms only (the form is the templates'
+    last argument, AF), and those keep the budgets of the plain forms (tests/test_build_budget.py): the tiled kernel
     128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), a few spills outside the loops at most; the latency kernel no
     spill at all; neither any spill code beside MFMAs."""
     k = _compile_report("proj_block.hip", tmp_path)
-    tiled = {n: v for n, v in k.items() if "conv1x1_proj_kernel" in n}
-    small = {n: v for n, v in k.items() if "conv1x1_small_proj_kernel" in n}
+    tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
+    small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     assert len(tiled) == 8, sorted(tiled)     # {4, 8 waves} x {plain, stream-K} x {strided, two sources}
     assert len(small) == 36, sorted(small)    # KS {1, 2, 4} x RT {1, 2} x CT {1, 2, 4} x {strided, two sources}
+    # half in each projection form (AF = A_STRIDED 1 / A_TWO 2), none in the plain form
+    forms = [_template_args(n, "conv1x1_bn_kernel")[-1] for n in tiled]
+    assert sorted(forms) == [1] * 4 + [2] * 4, sorted(tiled)
+    forms = [_template_args(n, "conv1x1_small_kernel")[-1] for n in small]
+    assert sorted(forms) == [1] * 18 + [2] * 18, sorted(small)
     for name, v in tiled.items():
-        eight = "ILi8E" in name
-        assert eight or "ILi4E" in name, name
+        eight = "ILi32ELi8E" in name
+        assert eight or "ILi32ELi4E" in name, name
         budget, waves = (128, 4) if eight else (168, 3)
         assert v["vgprs"] <= budget and v["occupancy"] >= waves and v["spill"] <= 8, (name, v)
         assert v["mfma"] >= 56 and v["spill_code_in_mfma_blocks"] == 0 and v["sgpr_spill"] <= 40, (name, v)
     for name, v in small.items():
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)
-    assert not [n for n in k if "conv1x1_bn_kernel" in n or "conv1x1_small_kernel" in n]
 
 
 def test_conv1x1_kernel_set_unchanged(tmp_path):
-    """conv1x1.hip instantiates exactly the kernels it did before the projection forms existed, none of the new ones."""
+    """conv1x1.hip instantiates exactly the kernels it did before the projection forms existed: all in the plain
+    operand form (AF = A_PLAIN = 0), none in the new ones."""
     k = _compile_report("conv1x1.hip", tmp_path)
-    assert sum("conv1x1_bn_kernel" in n for n in k) == 8
-    assert sum("conv1x1_small_kernel" in n for n in k) == 18
+    tiled = [n for n in k if "conv1x1_bn_kernel" in n]
+    small = [n for n in k if "conv1x1_small_kernel" in n]
+    assert len(tiled) == 8 and len(small) == 18, sorted(k)
+    assert all(_template_args(n, "conv1x1_bn_kernel")[-1] == 0 for n in tiled), tiled
+    assert all(_template_args(n, "conv1x1_small_kernel")[-1] == 0 for n in small), small
     assert not [n for n in k if "proj" in n]

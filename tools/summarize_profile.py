@@ -24,20 +24,28 @@ HOT = ("wino_f2_fused_kernel", "wino_f2_small_kernel", "conv1x1_bn_kernel", "con
        "f4_input_transform_kernel", "f4_output_transform_kernel", "f4_ring_kernel")
 
 
+def af_label(af):
+    """The 1x1 kernels' A operand form (conv1x1_kernel.h): the plain form keeps its old label, the projection block's
+    forms get their own, so that their times never merge with the plain form's."""
+    return {"0": "", "1": ",strided", "2": ",two-source"}.get(af, ",AF" + af)
+
+
 def short(name):
     for h in HOT:
         if h in name:
-            if h == "conv1x1_bn_kernel":      # keep the variant: <BK, NW, ABLATE, SK>
+            if h == "conv1x1_bn_kernel":      # keep the variant: <BK, NW, ABLATE, SK, RES, AF>
                 m = re.search(r"conv1x1_bn_kernel<([^>]*)>", name)
                 if m:
                     a = [x.strip() for x in m.group(1).split(",")]
-                    return "conv1x1_bn_kernel<%sw%s>" % (a[1] if len(a) > 1 else "?", ",streamK" if len(a) > 3 and a[3] in ("true", "1") else "")
+                    return "conv1x1_bn_kernel<%sw%s%s>" % (a[1] if len(a) > 1 else "?",
+                                                          ",streamK" if len(a) > 3 and a[3] in ("true", "1") else "",
+                                                          af_label(a[5] if len(a) > 5 else "0"))
             if h == "wino_f2_small_kernel":   # keep the form: <CT>
                 m = re.search(h + r"<\s*(\d+)", name)
                 return h + ("<%s>" % m.group(1) if m else "")
-            if h == "conv1x1_small_kernel":   # <KS, RT, CT>
-                m = re.search(h + r"<\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)", name)
-                return h + ("<%s,%s,%s>" % m.groups() if m else "")
+            if h == "conv1x1_small_kernel":   # <KS, RT, CT, AF>
+                m = re.search(h + r"<\s*(\d+)\s*,\s*(\d+)\s*,\s*(\d+)(?:\s*,\s*(\d+))?", name)
+                return h + ("<%s,%s,%s%s>" % (m.groups()[:3] + (af_label(m.group(4) or "0"),)) if m else "")
             if h == "wino_f2_fused_kernel" and re.search(r"wino_f2_fused_kernel<\s*16\s*,", name):
                 return "wino_f2_fused_kernel<stamped diagnostic build: bench.py's clock probe>"
             return h
