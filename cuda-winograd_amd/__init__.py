@@ -45,6 +45,8 @@ ABI_SYMBOLS = [
     "wino_conv3x3_small_plan2", "wino_debug_conv1x1_models",
     "wino_proj_tail_elems", "wino_proj_tail_pack", "wino_proj_block_workspace_bytes_hw", "wino_proj_block_prepare_hw",
     "wino_proj_block_hw", "wino_proj_tail_plan",
+    "wino_conv3x3_s2_bn_relu_hw", "wino_conv3x3_s2_prepare_hw", "wino_conv3x3_s2_plan",
+    "wino_proj_block_v15_workspace_bytes_hw", "wino_proj_block_v15_hw", "wino_proj_block_v15_prepare_hw",
     # reference entry points + helpers (Kernel*.h, util.h)
     "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
     "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
@@ -144,6 +146,13 @@ def lib() -> ctypes.CDLL:
     L.wino_proj_block_prepare_hw.argtypes = [c_int] * 7 + [c_void_p]
     L.wino_proj_block_hw.argtypes = [fp] * 9 + [c_int] * 7 + [fp, c_size_t, c_void_p]
     L.wino_proj_tail_plan.argtypes = [c_int] * 8 + [POINTER(c_int)] * 2
+    L.wino_conv3x3_s2_bn_relu_hw.argtypes = [fp] * 5 + [c_int] * 6 + [c_void_p]
+    L.wino_conv3x3_s2_prepare_hw.argtypes = [c_int] * 5 + [c_void_p]
+    L.wino_conv3x3_s2_plan.argtypes = [c_int] * 6 + [POINTER(c_int)]
+    L.wino_proj_block_v15_workspace_bytes_hw.restype = c_size_t
+    L.wino_proj_block_v15_workspace_bytes_hw.argtypes = [c_int] * 4
+    L.wino_proj_block_v15_hw.argtypes = [fp] * 9 + [c_int] * 6 + [fp, c_size_t, c_void_p]
+    L.wino_proj_block_v15_prepare_hw.argtypes = [c_int] * 6 + [c_void_p]
     for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
                  "kernel_256_1_in", "kernel_256_1_out"):
         getattr(L, name).restype = c_int
@@ -567,6 +576,104 @@ def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None)
                                     vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(), out.data_ptr(), N, Hin, Win,
                                     Cin, Cm, C4, int(stride), workspace.data_ptr(), workspace.numel() * 4, _stream()),
            "wino_proj_block_hw")
+    return out
+
+
+def filter_pack_s2(w_kcrs: torch.Tensor) -> torch.Tensor:
+    """[K][C][3][3] taps -> the stride-2 3x3 layer's [3][3][C][K] filter (w.permute(2, 3, 1, 0)), the analogue of
+    filter_transform_f2 for conv3x3_s2_bn_relu."""
+    w = _dev(w_kcrs, "w_kcrs")
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
+        raise WinoError("w_kcrs must be [K][C][3][3]")
+    return w.permute(2, 3, 1, 0).contiguous()
+
+
+def _s2_out_hw(Hin: int, Win: int):
+    return (Hin - 1) // 2 + 1, (Win - 1) // 2 + 1
+
+
+def conv3x3_s2_bn_relu(inp: torch.Tensor, w_taps: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
+                       relu: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Stride-2, pad-1 3x3 conv + folded BN (+ReLU): inp [N][Hin+2][Win+2][C] (zero ring) -> out [N][H+2][W+2][K]
+    (interior H x W = (Hin-1)//2 + 1 x (Win-1)//2 + 1, zero ring).  w_taps [3][3][C][K] from filter_pack_s2.  One launch."""
+    x, w = _dev(inp, "inp"), _dev(w_taps, "w_taps")
+    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("inp must be [N][Hin+2][Win+2][C]")
+    N, Hin, Win, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    if w.dim() != 4 or tuple(w.shape[:3]) != (3, 3, C):
+        raise WinoError(f"w_taps must be [3][3][{C}][K]: pack it with filter_pack_s2")
+    K = int(w.shape[3])
+    if b.numel() != K or s.numel() != K:
+        raise WinoError("bn vectors do not match K")
+    H, W = _s2_out_hw(Hin, Win)
+    if out is None:
+        out = torch.empty((N, H + 2, W + 2, K), dtype=torch.float32, device=x.device)
+    else:
+        _out(out, (N, H + 2, W + 2, K), "out")
+    _on_current_device(x, w, b, s, out)
+    _check(lib().wino_conv3x3_s2_bn_relu_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
+                                            N, Hin, Win, C, K, int(relu), _stream()), "wino_conv3x3_s2_bn_relu_hw")
+    return out
+
+
+def conv3x3_s2_prepare(N: int, Hin: int, Win: int, C: int, K: int) -> None:
+    """Allocate the stride-2 3x3 layer's stream-K scratch for the current stream (before graph capture)."""
+    _check(lib().wino_conv3x3_s2_prepare_hw(int(N), int(Hin), int(Win), int(C), int(K), _stream()),
+           "wino_conv3x3_s2_prepare_hw")
+
+
+def conv3x3_s2_plan(N: int, Hin: int, Win: int, C: int, K: int, cus: int = 256) -> int:
+    """The FORM_* the stride-2 3x3 layer takes on a device with `cus` CUs (host-side)."""
+    f = c_int(-1)
+    _check(lib().wino_conv3x3_s2_plan(int(N), int(Hin), int(Win), int(C), int(K), int(cus), ctypes.byref(f)),
+           "wino_conv3x3_s2_plan")
+    return int(f.value)
+
+
+def proj_block_v15_prepare(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int) -> None:
+    """Allocate the scratch of proj_block_v15's three launches for the current stream (before graph capture)."""
+    _check(lib().wino_proj_block_v15_prepare_hw(int(N), int(Hin), int(Win), int(Cin), int(Cm), int(C4), _stream()),
+           "wino_proj_block_v15_prepare_hw")
+
+
+def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> torch.Tensor:
+    """ResNet projection bottleneck, v1.5 placement (torchvision's: the stride 2 on the 3x3): x [N][Hin][Win][Cin] ->
+    [N][H][W][C4], H = (Hin-1)//2 + 1.  bnX = (bias, scale) folded BN vectors; w1 [Cin][Cm]; w2_taps [3][3][Cm][Cm]
+    from filter_pack_s2; tail from proj_tail_pack (w3, bn3, wp, bnp)."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise WinoError("x must be [N][Hin][Win][Cin]")
+    N, Hin, Win, Cin = (int(v) for v in x.shape)
+    w1, w2, tail = _dev(w1, "w1"), _dev(w2_taps, "w2_taps"), _dev(tail, "tail")
+    if w1.dim() != 2 or int(w1.shape[0]) != Cin:
+        raise WinoError("w1 must be [Cin][Cm]")
+    Cm = int(w1.shape[1])
+    if w2.dim() != 4 or tuple(w2.shape) != (3, 3, Cm, Cm):
+        raise WinoError(f"w2_taps must be [3][3][{Cm}][{Cm}]: pack it with filter_pack_s2")
+    if tail.numel() % (Cm + Cin + 2):
+        raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
+    C4 = tail.numel() // (Cm + Cin + 2)
+    H, W = _s2_out_hw(Hin, Win)
+    vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
+    if any(v.numel() != Cm for v in vecs):
+        raise WinoError("bn1 / bn2 vectors must have Cm values")
+    need = lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    else:
+        _out(workspace, None, "workspace")
+        if workspace.numel() * 4 < need:
+            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
+    if out is None:
+        out = torch.empty((N, H, W, C4), dtype=torch.float32, device=x.device)
+    else:
+        _out(out, (N, H, W, C4), "out")
+    _on_current_device(x, w1, w2, tail, out, workspace, *vecs)
+    _check(lib().wino_proj_block_v15_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
+                                        w2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
+                                        out.data_ptr(), N, Hin, Win, Cin, Cm, C4, workspace.data_ptr(),
+                                        workspace.numel() * 4, _stream()), "wino_proj_block_v15_hw")
     return out
 
 

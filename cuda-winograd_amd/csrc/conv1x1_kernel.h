@@ -84,12 +84,24 @@ __device__ __forceinline__ long padded_row(long m, const PadGeo& g) {
 //   A_TWO      two A sources along K: k-steps [0, cm/BK) read A (the padded t2 tensor, row length cm), the rest
 //              read the strided x (row length cx) -- the block's last 1x1 and its projection shortcut in one
 //              set of accumulators; B is the stacked [cm + cx][Kout] matrix
-enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2 };
+//   A_TAPS     a stride-2, pad-1 3x3 convolution as one GEMM of K = 9 C (conv3x3_s2.hip): A is the padded
+//              [N][Hin+2][Win+2][C] input (row length C = cx), row m's window starts at padded pixel
+//              n*(Hin+2)*(Win+2) + 2y*(Win+2) + 2x (strided_row with img = (Hin+2)*(Win+2), row = 2*(Win+2), s = 2),
+//              and tap (dy, dx) adds the same pixel offset dy*(Win+2) + dx (Win+2 = cm) to every row; B is
+//              [3][3][C][Kout], its row (3 dy + dx) C + c tap (dy, dx) of channel c.  C % 32 == 0: no k-step and no
+//              16-channel chunk crosses a tap.
+enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3 };
 struct ProjGeo {
   const float* X;         // A_TWO: the block input x
   unsigned img, row, s;   // x's pixels per image (Hin*Win), pixels per strided row step (s*Win), the stride
-  int cx, cm;             // A_TWO: channels of x, of the first source (the phase boundary is k = cm)
+  int cx, cm;             // A_TWO: channels of x, of the first source (the phase boundary is k = cm); A_TAPS: C, Win+2
 };
+// A_TAPS: the element offset of GEMM column k (any k inside the tap row dy = k / 3C) from its row's window start.
+// k = (3 dy + dx) C + c lies at (dy (Win+2) + dx) C + c = k + dy (Win+2-3) C: a scalar select and multiply-add.
+__device__ __forceinline__ unsigned tap_offset(unsigned k, const ProjGeo& x) {
+  const unsigned c3 = 3u * (unsigned)x.cx;
+  return k + ((k >= c3) + (k >= 2 * c3)) * (unsigned)(x.cm - 3) * (unsigned)x.cx;
+}
 // logical pixel row m of the H x W grid -> row of the strided input (same FastDiv work as padded_row)
 __device__ __forceinline__ long strided_row(long m, const PadGeo& g, const ProjGeo& x) {
   const unsigned mu = (unsigned)m;   // M < 2^31 (checked on the host)
@@ -158,7 +170,8 @@ __device__ unsigned long long wino_clk_slot_1x1[4];
 // their presence -- register allocation and code layout of the rest.
 // AF = the A operand form.  The projection block's forms (proj_block.hip) run with BK = 32, no residual and no batch:
 // A_STRIDED: A = x, Cin = x's channels; A_TWO: A = t2 (padded, flags WINO_A_PADDED), Cin = cm + cx, B = the stacked
-// tail matrix.  xg is last, so that the plain form's other arguments keep their offsets.
+// tail matrix.  The stride-2 3x3 layer (conv3x3_s2.hip) runs A_TAPS the same way: A = the padded input, Cin = 9 C.
+// xg is last, so that the plain form's other arguments keep their offsets.
 template <int BK, int NW, int ABLATE = 0, bool SK = false, bool RES = false, int AF = A_PLAIN>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3)
 conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -302,14 +315,17 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   //   B: one descriptor over all of B (< 4 GiB, checked on the host); piece q covers
   //      B_ROWS_PER_PIECE k rows; lane -> (k, unit'), source unit = unit' ^ 4*bit2(k).
   //   A_STRIDED / A_TWO past kb: rows map into the strided x, a window about s^2 times as long (host-checked < 4 GiB).
-  const bool a_str = AF == A_STRIDED || (AF == A_TWO && k0 >= kb);
+  //   A_TAPS: rows map into the padded input the same way, and the window grows by the taps' reach, 2 (Win+2) + 2
+  //      pixels past the last row (host-checked < 4 GiB); the k offset of a k-step is tap_offset(k BK) * 4 bytes.
+  const bool a_str = AF == A_STRIDED || AF == A_TAPS || (AF == A_TWO && k0 >= kb);
   const float* const Aseg = AF == A_TWO && a_str ? xg.X : A;
-  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : Cin;   // A row length of this segment
+  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : AF == A_TAPS ? xg.cx : Cin;   // A row length of this segment
   const int ka = AF == A_TWO && a_str ? k0 - kb : k0;        // its first k-step inside that source
   const long a_row0 = a_str ? strided_row(m0 < M ? m0 : M - 1, pg, xg)
                             : a_padded ? padded_row(m0 < M ? m0 : M - 1, pg) : (m0 < M ? m0 : M - 1);
   const long m_last = m0 + BM - 1 < M ? m0 + BM - 1 : M - 1;
-  const long a_rows = (a_str ? strided_row(m_last, pg, xg) : a_padded ? padded_row(m_last, pg) : m_last) - a_row0 + 1;
+  long a_rows = (a_str ? strided_row(m_last, pg, xg) : a_padded ? padded_row(m_last, pg) : m_last) - a_row0 + 1;
+  if constexpr (AF == A_TAPS) a_rows += 2 * (long)xg.cm + 2;
   const auto rsrc_a = make_rsrc(Aseg + a_row0 * ca, (unsigned)(a_rows * ca * (long)sizeof(float)));
   const auto rsrc_b = make_rsrc(B, (unsigned)((size_t)Cin * Kout * sizeof(float)));
   unsigned a_voff[G::A_PER_WAVE];
@@ -336,6 +352,17 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     b_voff[j] = (unsigned)(k * Kout + n0 + unit * 4) * (unsigned)sizeof(float);
   }
   const unsigned a_kstep = (unsigned)(BK * sizeof(float)), b_kstep = (unsigned)(BK * sizeof(float)) * (unsigned)Kout;
+  // A_TAPS: k-step k's A offset in bytes, tap_offset(k BK) * 4 -- a stream-K segment that starts mid-tap computes the
+  // same.  One scalar per k-step: k a_kstep plus one tap-row step for each tap row that k-step has passed.  The tap-row
+  // geometry -- k-steps per tap row, 3 C / BK, and the bytes from one tap row to the next past a window's width,
+  // (Win+2-3) C 4 -- is made wave-uniform per segment: read through xg, the compiler takes it for per-lane data,
+  // computes the offset on the VALU and wraps every A piece in a readfirstlane loop inside the MFMA loop.  (Per
+  // segment rather than per launch: not live across the stream-K hand-off, where the SGPRs are short.)
+  const int taps_k3 = AF == A_TAPS ? __builtin_amdgcn_readfirstlane(3 * (xg.cx / BK)) : 0;
+  const unsigned taps_row = AF == A_TAPS ? (unsigned)__builtin_amdgcn_readfirstlane((xg.cm - 3) * xg.cx * (int)sizeof(float)) : 0u;
+  auto taps_soff = [&](int k) {
+    return (unsigned)k * a_kstep + (k >= taps_k3 ? taps_row : 0u) + (k >= 2 * taps_k3 ? taps_row : 0u);
+  };
   auto issue_piece = [&](int stage, unsigned a_soff, unsigned b_soff, int p) {  // p = 0 .. A_PER_WAVE + B_PER_WAVE - 1
     char* sb = smem + stage * G::STAGE;
     if (p < G::A_PER_WAVE) {
@@ -369,7 +396,8 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   }
 
 #pragma unroll
-  for (int p = 0; p < PIECES; p++) issue_piece(0, (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
+  for (int p = 0; p < PIECES; p++)
+    issue_piece(0, AF == A_TAPS ? taps_soff(k0) : (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
   __builtin_amdgcn_s_setprio(0);
 
   // `more` (is there a k-step after this one to fetch) is a compile-time property of the body: the
@@ -383,6 +411,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     }
     unsigned a_soff;   // `it` counts from the segment's first k-step k0 (A_TWO: from ka inside its source)
     if constexpr (AF == A_TWO) a_soff = (unsigned)(ka + it + 1) * a_kstep;
+    else if constexpr (AF == A_TAPS) a_soff = taps_soff(k0 + it + 1);
     else a_soff = (unsigned)(k0 + it + 1) * a_kstep;
     const unsigned b_soff = (unsigned)(k0 + it + 1) * b_kstep;
     const char* st = smem + PAR * G::STAGE;

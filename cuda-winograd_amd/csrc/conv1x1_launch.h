@@ -1,5 +1,6 @@
 // The 1x1 kernels' launch plan and launcher, shared by the translation units that launch them: conv1x1.hip (the plain
-// operand form, A_PLAIN) and proj_block.hip (the projection block's A_STRIDED / A_TWO forms, conv1x1_kernel.h).
+// operand form, A_PLAIN), proj_block.hip (the projection block's A_STRIDED / A_TWO forms) and conv3x3_s2.hip (the
+// stride-2 3x3's A_TAPS form); the forms: conv1x1_kernel.h.
 // A template is instantiated where it is used, so each file compiles the kernels of its own forms and no others.
 #pragma once
 #include "conv1x1_kernel.h"
@@ -28,7 +29,7 @@ Plan1x1 plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn)
 int tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs);
 
 // One launch's operands.  R: the residual (A_PLAIN, WINO_ADD_RESIDUAL); xg: the strided / second source (A_STRIDED,
-// A_TWO); batch and the per-batch strides: the batched plain GEMM (gemm_batched; its plans have no stream-K form).
+// A_TWO) or the padded input's tap geometry (A_TAPS); batch and the per-batch strides: the batched plain GEMM (gemm_batched; its plans have no stream-K form).
 struct Operands1x1 {
   const float *A, *B, *bnBias, *bnScale, *R;
   float* C;

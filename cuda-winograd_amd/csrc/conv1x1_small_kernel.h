@@ -36,7 +36,9 @@ namespace gemm1x1 {
 // AF = the A operand form (conv1x1_kernel.h).  The projection block's forms (proj_block.hip) have no residual:
 // A_STRIDED: A = x, Cin = x's channels.  A_TWO: A = t2 (padded, flags WINO_A_PADDED), Cin = cm + cx, B = the stacked
 // tail matrix; each wave contracts its share of both sources (cm / KS channels of t2, then cx / KS of x), so the K
-// split stays in k order.  xg is last, so that the plain form's other arguments keep their offsets.
+// split stays in k order.  A_TAPS (conv3x3_s2.hip): A = the padded input, Cin = 9 C; a 16-channel chunk never crosses
+// a tap, so its address is the row pointer plus tap_offset of the chunk's first k.  xg is last, so that the plain
+// form's other arguments keep their offsets.
 template <int KS, int RT = 1, int CT = 1, int AF = A_PLAIN>
 __global__ void __launch_bounds__(256)
 conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -104,9 +106,10 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
   for (int r = 0; r < RT; r++) {
     long m = m0 + 16 * r + r16;
     m = m < M ? m : M - 1;                 // rows past the end read a valid row (never stored)
-    if (AF == A_STRIDED) m = strided_row(m, pg, xg);
+    if (AF == A_STRIDED || AF == A_TAPS) m = strided_row(m, pg, xg);
     else if (a_padded) m = padded_row(m, pg);
-    ap[r] = A + m * (AF == A_TWO ? xg.cm : Cin) + kq * kspan + 4 * h;
+    if constexpr (AF == A_TAPS) ap[r] = A + m * xg.cx + 4 * h;   // the wave's k range starts inside tap_offset below
+    else ap[r] = A + m * (AF == A_TWO ? xg.cm : Cin) + kq * kspan + 4 * h;
   }
   const float* bp = B + (size_t)(kq * kspan + 4 * h) * Kout + n0 + (WIDE ? 4 * r16 : r16);
 
@@ -115,8 +118,14 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
     for (int i = 0; i < GS; i++) {
       int s = g * GS + i;
       s = s < nsc ? s : nsc - 1;           // past the end: re-read the last one (never multiplied)
+      if constexpr (AF == A_TAPS) {
+        const unsigned off = tap_offset((unsigned)(kq * kspan + s * 16), xg);
 #pragma unroll
-      for (int r = 0; r < RT; r++) a[i][r] = *(const f32x4*)(ap[r] + s * 16);
+        for (int r = 0; r < RT; r++) a[i][r] = *(const f32x4*)(ap[r] + off);
+      } else {
+#pragma unroll
+        for (int r = 0; r < RT; r++) a[i][r] = *(const f32x4*)(ap[r] + s * 16);
+      }
       if constexpr (WIDE) {
 #pragma unroll
         for (int jj = 0; jj < 4; jj++) {

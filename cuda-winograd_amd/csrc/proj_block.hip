@@ -10,6 +10,12 @@
 // the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernel templates with the
 // operand form as a template argument (AF = A_STRIDED / A_TWO), launched by the same launch_1x1 as conv1x1.hip's
 // (conv1x1_launch.h).  This file's calls instantiate those forms here; conv1x1.hip instantiates only A_PLAIN.
+//
+// The v1.5 placement (torchvision's ResNet-50: the stride on the 3x3) is host code over the same kernels:
+//   t1  = relu(bn1(x . w1))                      padded [N][Hin+2][Win+2][Cm]   (workspace; the plain 1x1 entry point)
+//   t2  = relu(bn2(conv3x3_s2(t1, w2_taps)))     padded [N][H+2][W+2][Cm]       (workspace; conv3x3_s2.hip)
+//   out = the same fused tail as v1 at stride 2
+// so this file instantiates no kernel for it.
 #include "conv1x1_launch.h"
 
 namespace wino {
@@ -144,6 +150,20 @@ int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4,
   return WINO_OK;
 }
 
+// The v1.5 block's shape check, before anything is launched: the v1 block's at stride 2 (the tail and the strided
+// shortcut are the same), the first 1x1 at full input resolution, and the stride-2 3x3's own limits.
+static int check_v15(int N, int Hin, int Win, int Cin, int Cm, int C4, ProjGeom* g) {
+  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, 2, g)) return rc;
+  const unsigned long long M1 = (unsigned long long)N * Hin * Win;
+  const unsigned long long ring1 = (unsigned long long)N * (2ull * (Win + 2) + 2ull * Hin) * (Cm / 4);
+  if (Hin > 4094 || Win > 4094 || M1 >= (1ull << 31) || (M1 + BM - 1) / BM > (1ull << 24) || ring1 >= FOUR_GIB) {
+    set_error("v1.5 projection block: the first 1x1 at %dx%d x %d images is too large for one launch", Hin, Win, N);
+    return WINO_E_SHAPE;
+  }
+  int form = 0;
+  return wino_conv3x3_s2_plan(N, Hin, Win, Cm, Cm, 1, &form);   // (host-side: the 3x3's shape check)
+}
+
 int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale, const float* U2,
                        const float* bn2Bias, const float* bn2Scale, const float* tail_packed, float* out, int N, int Hin,
                        int Win, int Cin, int Cm, int C4, int stride, void* workspace, size_t workspace_bytes,
@@ -181,6 +201,55 @@ int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, co
   return launch_1x1<A_TWO>(plan_tail(g, cus, kn), dev,
                            {t2, tail_packed, bias, bias + C4, nullptr, out, g.M, Cm + Cin, C4, WINO_RELU | WINO_A_PADDED, pg, xg},
                            hs);
+}
+
+size_t wino_proj_block_v15_workspace_bytes_hw(int N, int Hin, int Win, int Cm) {
+  if (N < 1 || Hin < 1 || Win < 1 || Cm < 1) return 0;
+  const size_t H = (size_t)(Hin - 1) / 2 + 1, W = (size_t)(Win - 1) / 2 + 1;
+  return (size_t)N * ((size_t)(Hin + 2) * (Win + 2) + (H + 2) * (W + 2)) * Cm * sizeof(float);
+}
+
+int wino_proj_block_v15_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, wino_stream_t s) {
+  ProjGeom g;
+  if (int rc = check_v15(N, Hin, Win, Cin, Cm, C4, &g)) return rc;
+  int dev = 0, cus = 0;
+  if (int rc = current_device(&dev, &cus)) return rc;
+  if (int rc = wino_conv1x1_prepare((long)N * Hin * Win, Cin, Cm, s)) return rc;
+  if (int rc = wino_conv3x3_s2_prepare_hw(N, Hin, Win, Cm, Cm, s)) return rc;
+  const Plan1x1 pt = plan_tail(g, cus, knobs());
+  SkBufs bufs;
+  return pt.sk ? tiled_scratch(dev, (hipStream_t)s, pt, &bufs) : WINO_OK;
+}
+
+int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                           const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
+                           float* out, int N, int Hin, int Win, int Cin, int Cm, int C4, void* workspace,
+                           size_t workspace_bytes, wino_stream_t s) {
+  if (!x || !w1 || !bn1Bias || !bn1Scale || !w2_taps || !bn2Bias || !bn2Scale || !tail_packed || !out) {
+    set_error("NULL pointer");
+    return WINO_E_ARG;
+  }
+  if (misaligned16(x, w1, w2_taps, out) || misaligned16(tail_packed, workspace)) {
+    set_error("tensor pointers must be 16-byte aligned");
+    return WINO_E_ARG;
+  }
+  ProjGeom g;
+  if (int rc = check_v15(N, Hin, Win, Cin, Cm, C4, &g)) return rc;
+  const size_t need = wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm);
+  if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  int dev = 0, cus = 0;
+  if (int rc = current_device(&dev, &cus)) return rc;
+  float* t1 = (float*)workspace;
+  float* t2 = t1 + (size_t)N * (Hin + 2) * (Win + 2) * Cm;
+  int rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, Hin, Win, Cin, Cm, WINO_RELU | WINO_C_PADDED, s);
+  if (rc) return rc;
+  rc = wino_conv3x3_s2_bn_relu_hw(t1, w2_taps, bn2Bias, bn2Scale, t2, N, Hin, Win, Cm, Cm, 1, s);
+  if (rc) return rc;
+  const float* bias = tail_packed + (size_t)(Cm + Cin) * C4;
+  return launch_1x1<A_TWO>(plan_tail(g, cus, knobs()), dev,
+                           {t2, tail_packed, bias, bias + C4, nullptr, out, g.M, Cm + Cin, C4, WINO_RELU | WINO_A_PADDED,
+                            make_padgeo(g.H, g.W), proj_geo(g, x)},
+                           (hipStream_t)s);
 }
 
 }  // extern "C"

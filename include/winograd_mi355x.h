@@ -51,7 +51,9 @@ extern "C" {
  * wino_debug_poison_ticket, wino_diag_last_clock, wino_conv3x3_small_plan, wino_conv1x1_small_plan,
  * wino_conv3x3_plan_groups, wino_conv1x1_small_plan2, wino_conv3x3_small_plan2, wino_debug_conv1x1_models,
  * WINO_E_STATE, wino_proj_tail_elems, wino_proj_tail_pack, wino_proj_block_workspace_bytes_hw,
- * wino_proj_block_prepare_hw, wino_proj_block_hw, wino_proj_tail_plan, WINO_1X1_FORM_*.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_proj_block_prepare_hw, wino_proj_block_hw, wino_proj_tail_plan, WINO_1X1_FORM_*,
+ * wino_conv3x3_s2_bn_relu_hw, wino_conv3x3_s2_prepare_hw, wino_conv3x3_s2_plan, wino_proj_block_v15_hw,
+ * wino_proj_block_v15_workspace_bytes_hw, wino_proj_block_v15_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived). */
 #define WINO_ABI_VERSION 1
 
@@ -306,7 +308,7 @@ int wino_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, wino_str
  * Constraints: stride 1 or 2, Cin % 32 == 0, Cm % 64 == 0, C4 % 64 == 0; shapes whose 32-bit tile windows,
  * pixel rows or ring pass would overflow are rejected (WINO_E_SHAPE).  Three launches on `s`; the padded
  * intermediates live in `workspace` (wino_proj_block_workspace_bytes_hw(N, H, W, Cm), H x W the OUTPUT grid).
- * v1.5 placement (stride on the 3x3, torchvision) is not supported: F(2x2,3x3) has no stride-2 form. */
+ * v1.5 placement (stride on the 3x3, torchvision): wino_proj_block_v15_hw below. */
 size_t wino_proj_tail_elems(int Cm, int Cin, int C4);
 int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3Scale, const float* wp,
                         const float* bnpBias, const float* bnpScale, float* tail_packed, int Cm, int Cin, int C4,
@@ -325,6 +327,38 @@ int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4,
 #define WINO_1X1_FORM_LATENCY 2    /* the latency kernel (wino_conv1x1_small_plan2) */
 int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, int cus, int* first_form,
                         int* tail_form);
+
+/* ---- stride-2 3x3 convolution + BN (+ReLU): the 3x3 of the v1.5 projection block ----------------------
+ * A stride-2, pad-1 3x3 as an implicit GEMM of M = N*H*W, K = 9*C (the 1x1 GEMM kernels reading the input
+ * through the nine taps; F(2x2,3x3) has no stride-2 form).  H = (Hin-1)/2 + 1, W = (Win-1)/2 + 1.
+ *   in      [N][Hin+2][Win+2][C] with a zero ring (what WINO_C_PADDED layers write)
+ *   w_taps  [3][3][C][K]: tap (dy, dx) of input channel c to output channel k -- torch's w.permute(2, 3, 1, 0)
+ *   out     [N][H+2][W+2][K], the result at [1..H][1..W] and the ring written as 0 (wino_conv3x3_bn_relu_hw's layout)
+ * Constraints: C % 32 == 0, K % 64 == 0.  Shapes whose pixel rows (N*H*W < 2^31), tile windows over `in`, filter
+ * matrix or ring pass would overflow 32 bits are rejected (WINO_E_SHAPE).  One launch on `s`; it takes the latency,
+ * tiled or stream-K form the 1x1 planner picks for the GEMM (N*H*W, 9*C, K) (WINO_1X1_* knobs apply). */
+int wino_conv3x3_s2_bn_relu_hw(const float* in, const float* w_taps, const float* bnBias, const float* bnScale,
+                               float* out, int N, int Hin, int Win, int C, int K, int relu, wino_stream_t s);
+/* Allocates the layer's stream-K scratch on `s` ahead of a graph capture. */
+int wino_conv3x3_s2_prepare_hw(int N, int Hin, int Win, int C, int K, wino_stream_t s);
+/* Host-side only: the form the layer takes on a device with `cus` CUs, one of WINO_1X1_FORM_*. */
+int wino_conv3x3_s2_plan(int N, int Hin, int Win, int C, int K, int cus, int* form);
+
+/* ---- ResNet v1.5 projection block (torchvision's placement): the stride on the 3x3 ----------------------
+ *   out = relu( bn3(conv1x1(relu(bn2(conv3x3_s2(relu(bn1(conv1x1(x, w1))), w2_taps))), w3)) + bnp(conv1x1(xs, wp)) )
+ * with xs = x[:, ::2, ::2, :].  x [N][Hin][Win][Cin], out [N][H][W][C4] (H, W as for the stride-2 3x3); w1 [Cin][Cm];
+ * w2_taps [3][3][Cm][Cm] (wino_conv3x3_s2_bn_relu_hw); tail_packed from wino_proj_tail_pack, as for the v1 block.
+ * Three launches on `s`: the 1x1 at full input resolution, the stride-2 3x3, and the v1 block's fused tail at stride 2.
+ * The stride is always 2: at stride 1 the two placements are the same network (wino_proj_block_hw).  Constraints:
+ * those of wino_proj_block_hw at stride 2 and of the two layers.  The padded intermediates -- t1 [N][Hin+2][Win+2][Cm],
+ * then t2 [N][H+2][W+2][Cm] -- live in `workspace` (wino_proj_block_v15_workspace_bytes_hw). */
+size_t wino_proj_block_v15_workspace_bytes_hw(int N, int Hin, int Win, int Cm);
+int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                           const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
+                           float* out, int N, int Hin, int Win, int Cin, int Cm, int C4, void* workspace,
+                           size_t workspace_bytes, wino_stream_t s);
+/* Allocates the library-owned scratch of the block's three launches on `s`, ahead of a graph capture. */
+int wino_proj_block_v15_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, wino_stream_t s);
 
 /* Independent comparator for the 1x1 layers: one thread per output, fp32 FMA loop. */
 int wino_conv1x1_direct(const float* A, const float* B, const float* bnBias,

@@ -4,7 +4,11 @@ to memory, then the identity block's three launches with the shortcut added as W
 usage: python tools/proj_block_bench.py [out.json] [--ns 1,16,128] [--trials 5] [--reps 50]
 Per (stage, N): 0.4 s of preheat, then `trials` rounds; in every round each variant runs `reps` blocks between two
 events.  Reported: the median round per variant (us per block), the ratio, and the chip clock the last 3x3 launch
-of each variant ran at (wino_diag_last_clock)."""
+of each variant ran at (wino_diag_last_clock).
+--v15: the v1.5 block (wino_proj_block_v15_hw: 1x1, stride-2 3x3, fused tail) at conv3/4/5 against the same block with
+the stride-2 3x3 done by torch -- F.conv2d(stride=2, padding=1) on channels-last tensors, BN and ReLU in torch -- and
+the tail as the library's shortcut 1x1 + last 1x1 with WINO_ADD_RESIDUAL (the fused tail has no entry point of its
+own); in the same rounds the stride-2 3x3 alone, library against torch."""
 import argparse
 import json
 import os
@@ -31,8 +35,11 @@ def main():
     ap.add_argument("--ns", default="1,16,128")
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--v15", action="store_true")
     a = ap.parse_args()
     pkg = ge.load_package()
+    if a.v15:
+        return main_v15(a, pkg)
     dev = torch.device("cuda:0")
     rows = []
     for stage, (Hin, Cin, Cm, C4, s) in STAGES.items():
@@ -101,6 +108,95 @@ def main():
             del x, out, ws, short, t1p, t2p, out2
             torch.cuda.empty_cache()
     res = {"tool": "tools/proj_block_bench.py", "device": torch.cuda.get_device_name(0), "trials": a.trials,
+           "reps": a.reps, "rows": rows}
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
+def _interleaved(fns, trials, reps):
+    """0.4 s of preheat, then `trials` rounds of every variant: the median us per call of each."""
+    t0 = time.time()
+    while time.time() - t0 < 0.4:
+        for f in fns.values():
+            for _ in range(5):
+                f()
+        torch.cuda.synchronize()
+    times = {k: [] for k in fns}
+    for _ in range(trials):
+        for k, f in fns.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(reps):
+                f()
+            e1.record()
+            e1.synchronize()
+            times[k].append(e0.elapsed_time(e1) * 1e3 / reps)
+    return {k: statistics.median(v) for k, v in times.items()}, times
+
+
+def main_v15(a, pkg):
+    F = torch.nn.functional
+    dev = torch.device("cuda:0")
+    rows = []
+    for stage in ("conv3", "conv4", "conv5"):
+        Hin, Cin, Cm, C4, _ = STAGES[stage]
+        H = (Hin - 1) // 2 + 1
+        for N in (int(v) for v in a.ns.split(",")):
+            g = torch.Generator(device="cpu").manual_seed(N)
+            r = lambda *shape, sc=1.0: ((torch.rand(*shape, generator=g) - 0.5) * sc).to(dev)
+            x = r(N, Hin, Hin, Cin)
+            w1, wp = r(Cin, Cm, sc=4 / Cin ** 0.5), r(Cin, C4, sc=2 / Cin ** 0.5)
+            w2, w3 = r(Cm, Cm, 3, 3, sc=4 / (9 * Cm) ** 0.5), r(Cm, C4, sc=4 / Cm ** 0.5)
+            bn = [(r(c), r(c) + 1.0) for c in (Cm, Cm, C4, C4)]
+            taps = pkg.filter_pack_s2(w2)
+            w2_cl = w2.contiguous(memory_format=torch.channels_last)
+            tail = pkg.proj_tail_pack(w3, bn[2], wp, bn[3])
+            out = torch.empty(N, H, H, C4, device=dev)
+            ws = torch.empty(pkg.lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Hin, Cm) // 4, device=dev)
+            t1p = torch.zeros(N, Hin + 2, Hin + 2, Cm, device=dev)
+            t2p = torch.zeros(N, H + 2, H + 2, Cm, device=dev)
+            t2l = torch.empty_like(t2p)
+            short = torch.empty(N * H * H, C4, device=dev)
+            out2 = torch.empty(N * H * H, C4, device=dev)
+            sc2, bi2 = bn[1][1][None, :, None, None], bn[1][0][None, :, None, None]
+
+            def torch_s2():   # channels-last NCHW views of the padded NHWC tensors
+                y = F.conv2d(t1p[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2), w2_cl, stride=2, padding=1)
+                t2p[:, 1:-1, 1:-1, :] = torch.relu(y * sc2 + bi2).permute(0, 2, 3, 1)
+
+            def fused():
+                pkg.proj_block_v15(x, w1, bn[0], taps, bn[1], tail, out=out, workspace=ws)
+
+            def composed():
+                pkg.conv1x1_bn_ex(x, w1, bn[0][0], bn[0][1], pkg.RELU | pkg.C_PADDED, out=t1p)
+                torch_s2()
+                pkg.conv1x1_bn_ex(x[:, ::2, ::2, :].contiguous(), wp, bn[3][0], bn[3][1], 0, out=short)
+                pkg.conv1x1_bn_ex(t2p, w3, bn[2][0], bn[2][1], pkg.RELU | pkg.A_PADDED | pkg.ADD_RESIDUAL,
+                                  residual=short, out=out2)
+
+            def layer():
+                pkg.conv3x3_s2_bn_relu(t1p, taps, bn[1][0], bn[1][1], out=t2l)
+
+            fns = {"fused": fused, "composed": composed, "layer": layer, "torch_layer": torch_s2}
+            fused(); composed(); layer(); torch.cuda.synchronize()
+            rel = float((out.reshape(-1, C4) - out2).abs().max() / out2.abs().max().clamp_min(1e-30))
+            rel_layer = float((t2l - t2p).abs().max() / t2p.abs().max().clamp_min(1e-30))
+            med, trials = _interleaved(fns, a.trials, a.reps)
+            row = {"stage": stage, "N": N, "Hin": Hin, "Cin": Cin, "Cm": Cm, "C4": C4,
+                   "form_3x3": pkg.conv3x3_s2_plan(N, Hin, Hin, Cm, Cm),
+                   "fused_us": med["fused"], "composed_torch_3x3_us": med["composed"],
+                   "s2_layer_us": med["layer"], "torch_s2_layer_us": med["torch_layer"],
+                   "trials_us": trials, "rel_diff_fused_vs_composed": rel, "rel_diff_layer_vs_torch": rel_layer}
+            row["speedup_block"] = row["composed_torch_3x3_us"] / row["fused_us"]
+            row["speedup_layer"] = row["torch_s2_layer_us"] / row["s2_layer_us"]
+            rows.append(row)
+            print(f"{stage} N={N:4d}  v1.5 block {med['fused']:9.1f} us  with torch 3x3 {med['composed']:9.1f} us  "
+                  f"x{row['speedup_block']:.3f}   3x3 s2 {med['layer']:8.1f} us  torch {med['torch_layer']:8.1f} us  "
+                  f"x{row['speedup_layer']:.3f}  form {row['form_3x3']}  rel {rel:.1e} / {rel_layer:.1e}", flush=True)
+            del x, out, ws, t1p, t2p, t2l, short, out2
+            torch.cuda.empty_cache()
+    res = {"tool": "tools/proj_block_bench.py --v15", "device": torch.cuda.get_device_name(0), "trials": a.trials,
            "reps": a.reps, "rows": rows}
     if a.out:
         with open(a.out, "w") as f:

@@ -1,4 +1,5 @@
-"""Developer tool (GPU box): soak of the stream-K hand-offs of both kernels.  For several shapes and forced
+"""Developer tool (GPU box): soak of the stream-K hand-offs of both kernels (the 1x1 kernel in its plain form and in
+the stride-2 3x3 layer's tap form).  For several shapes and forced
 grids, launches the layer back to back and compares every result bitwise with the first of its
 configuration (stream-K sums are added in segment order, so they must not move); under uneven load
 (a second stream runs another layer concurrently).  usage: python tools/soak.py [seconds]"""
@@ -29,6 +30,15 @@ for (N, Cin, Kout, grid) in [(128, 1024, 256, 0), (128, 1024, 256, 512), (100, 5
     Bm = torch.rand(Cin, Kout, device=dev) - 0.5
     b, s = torch.rand(Kout, device=dev) - 0.5, torch.rand(Kout, device=dev) - 0.5
     cfg1.append([N, Cin, Kout, grid, A, Bm, b, s, None])
+# the stride-2 3x3 layer (the 1x1 kernel in tap form): stream-K / split-K segments that start and end inside taps
+cfg_s2 = []
+for (N, Hin, C, K, grid) in [(128, 28, 256, 256, 0), (128, 14, 512, 512, 0), (16, 56, 128, 128, 0), (8, 28, 256, 256, 104),
+                             (3, 15, 96, 128, 40)]:
+    x = torch.zeros(N, Hin + 2, Hin + 2, C, device=dev)
+    x[:, 1:-1, 1:-1, :] = torch.rand(N, Hin, Hin, C, device=dev) - 0.5
+    taps = pkg.filter_pack_s2((torch.rand(K, C, 3, 3, device=dev) - 0.5) / (9 * C) ** 0.5)
+    b, s = torch.rand(K, device=dev) - 0.5, torch.rand(K, device=dev) - 0.5
+    cfg_s2.append([N, Hin, C, K, grid, x, taps, b, s, None])
 # 3x3 latency kernel: blocks shared by S workgroups through slabs + one ticket per workgroup (round 3); forms forced
 cfgs_small = []
 for (N, C, K, sp, ct) in [(1, 256, 256, 4, 1), (1, 128, 128, 4, 1), (2, 256, 256, 2, 1), (1, 256, 256, 8, 2), (3, 128, 128, 3, 1),
@@ -108,6 +118,31 @@ while time.time() - t0 < budget:
                 st = stats.setdefault(("1x1", N, Cin, Kout, grid), [0, 0.0, 0, 0])
                 d = (o - ref).abs()
                 st[0] += 1; st[1] = max(st[1], float(d.max())); st[2] = max(st[2], int((d > 0).sum())); st[3] = max(st[3], int(torch.isnan(o).sum()))
+    os.environ["WINO_1X1_SK"] = "1"
+    for c in cfg_s2:
+        N, Hin, C, K, grid, x, taps, b, s, ref = c
+        if grid: os.environ["WINO_1X1_SK_GRID"] = str(grid)
+        else: os.environ.pop("WINO_1X1_SK_GRID", None)
+        L.wino_debug_reload_knobs()
+        if use_side:
+            with torch.cuda.stream(side):
+                for _ in range(3): pkg.conv3x3_bn_relu(xs, Us, vs, vs)
+        outs = [pkg.conv3x3_s2_bn_relu(x, taps, b, s) for _ in range(10)]
+        launches += 10
+        if ref is None:
+            c[9] = outs[0].clone(); ref = c[9]
+            w = taps.double().permute(3, 2, 0, 1)   # [3][3][C][K] -> [K][C][3][3]
+            y = torch.nn.functional.conv2d(x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double(), w, stride=2, padding=1)
+            want = torch.relu(y * s.double()[None, :, None, None] + b.double()[None, :, None, None]).permute(0, 2, 3, 1)
+            err = float((ref[:, 1:-1, 1:-1, :].double() - want).abs().max() / want.abs().max())
+            assert err < 2e-5, ("stride-2 3x3 first result wrong", N, Hin, C, K, grid, err)
+        for o in outs:
+            if not torch.equal(o, ref):
+                bad += 1
+                st = stats.setdefault(("s2", N, Hin, C, K, grid), [0, 0.0, 0, 0])
+                d = (o - ref).abs()
+                st[0] += 1; st[1] = max(st[1], float(d.max())); st[2] = max(st[2], int((d > 0).sum())); st[3] = max(st[3], int(torch.isnan(o).sum()))
+    os.environ.pop("WINO_1X1_SK", None)
     os.environ.pop("WINO_1X1_SK_GRID", None)
     torch.cuda.synchronize()
 for k, v in stats.items(): print("  differs", k, "times", v[0], "max |diff|", v[1], "max elements", v[2], "nan", v[3])
