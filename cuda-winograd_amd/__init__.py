@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "wino_proj_block_hw", "wino_proj_tail_plan",
     "wino_conv3x3_s2_bn_relu_hw", "wino_conv3x3_s2_prepare_hw", "wino_conv3x3_s2_plan",
     "wino_proj_block_v15_workspace_bytes_hw", "wino_proj_block_v15_hw", "wino_proj_block_v15_prepare_hw",
+    "wino_conv3x3_bn_add_relu_hw", "wino_basic_block_workspace_bytes_hw", "wino_basic_block_hw",
+    "wino_basic_block_prepare_hw",
     # reference entry points + helpers (Kernel*.h, util.h)
     "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
     "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
@@ -153,6 +155,11 @@ def lib() -> ctypes.CDLL:
     L.wino_proj_block_v15_workspace_bytes_hw.argtypes = [c_int] * 4
     L.wino_proj_block_v15_hw.argtypes = [fp] * 9 + [c_int] * 6 + [fp, c_size_t, c_void_p]
     L.wino_proj_block_v15_prepare_hw.argtypes = [c_int] * 6 + [c_void_p]
+    L.wino_conv3x3_bn_add_relu_hw.argtypes = [fp] * 6 + [c_int] * 6 + [c_void_p]
+    L.wino_basic_block_workspace_bytes_hw.restype = c_size_t
+    L.wino_basic_block_workspace_bytes_hw.argtypes = [c_int] * 4
+    L.wino_basic_block_hw.argtypes = [fp] * 8 + [c_int] * 4 + [fp, c_size_t, c_void_p]
+    L.wino_basic_block_prepare_hw.argtypes = [c_int] * 4 + [c_void_p]
     for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
                  "kernel_256_1_in", "kernel_256_1_out"):
         getattr(L, name).restype = c_int
@@ -674,6 +681,71 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
                                         w2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
                                         out.data_ptr(), N, Hin, Win, Cin, Cm, C4, workspace.data_ptr(),
                                         workspace.numel() * 4, _stream()), "wino_proj_block_v15_hw")
+    return out
+
+
+def conv3x3_bn_add_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
+                        residual: torch.Tensor, relu: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+    """out = act(bn_scale * conv3x3(inp, U) + bn_bias + residual): the second 3x3 of a ResNet basic block, one HIP
+    launch.  inp [N][H+2][W+2][C]; residual and out [N][H+2][W+2][K] (out's ring written 0, residual's ring not read).
+    out may be residual itself (in place); the ReLU follows the add."""
+    x = _dev(inp, "inp")
+    U = _dev(U, "U")
+    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("inp must be [N][H+2][W+2][C]")
+    N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(b.numel())
+    if U.numel() != 16 * C * K or s.numel() != K:
+        raise WinoError("U / bn vectors do not match C, K")
+    r = _out(residual, (N, Hp, Wp, K), "residual")
+    if out is None:
+        out = torch.empty((N, Hp, Wp, K), dtype=torch.float32, device=x.device)
+    else:
+        _out(out, (N, Hp, Wp, K), "out")
+    _on_current_device(x, U, b, s, r, out)
+    _check(lib().wino_conv3x3_bn_add_relu_hw(x.data_ptr(), U.data_ptr(), b.data_ptr(), s.data_ptr(), r.data_ptr(),
+                                             out.data_ptr(), N, Hp - 2, Wp - 2, C, K, int(relu), _stream()),
+           "wino_conv3x3_bn_add_relu_hw")
+    return out
+
+
+def basic_block_prepare(N: int, H: int, W: int, C: int) -> None:
+    """Allocate the scratch of basic_block's two launches for the current stream (before graph capture)."""
+    _check(lib().wino_basic_block_prepare_hw(int(N), int(H), int(W), int(C), _stream()), "wino_basic_block_prepare_hw")
+
+
+def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
+    """ResNet basic block (ResNet-18 / -34), identity shortcut: out = relu(bn2(conv3x3(relu(bn1(conv3x3(x, U1))), U2))
+    + x).  x [N][H+2][W+2][C] with a zero ring -> out, the same layout (its ring written 0: the next block's x).
+    U1, U2 from filter_transform_f2 (C -> C); bnX = (bias, scale) folded BN vectors.  Two HIP launches; out may be x
+    (in place)."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("x must be [N][H+2][W+2][C]")
+    N, Hp, Wp, C = (int(v) for v in x.shape)
+    for name, u in (("U1", U1), ("U2", U2)):   # (shape first: a C -> K filter is refused before any device check)
+        if not isinstance(u, torch.Tensor) or u.numel() != 16 * C * C:
+            raise WinoError(f"{name} must be a {C} -> {C} filter from filter_transform_f2 (16*C*C values): "
+                            "the basic block keeps its channel count")
+    x, U1, U2 = _dev(x, "x"), _dev(U1, "U1"), _dev(U2, "U2")
+    vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
+    if any(v.numel() != C for v in vecs):
+        raise WinoError("bn1 / bn2 vectors must have C values")
+    need = lib().wino_basic_block_workspace_bytes_hw(N, Hp - 2, Wp - 2, C)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    else:
+        _out(workspace, None, "workspace")
+        if workspace.numel() * 4 < need:
+            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
+    if out is None:
+        out = torch.empty((N, Hp, Wp, C), dtype=torch.float32, device=x.device)
+    else:
+        _out(out, (N, Hp, Wp, C), "out")
+    _on_current_device(x, U1, U2, out, workspace, *vecs)
+    _check(lib().wino_basic_block_hw(x.data_ptr(), U1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
+                                     U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), out.data_ptr(),
+                                     N, Hp - 2, Wp - 2, C, workspace.data_ptr(), workspace.numel() * 4, _stream()),
+           "wino_basic_block_hw")
     return out
 
 

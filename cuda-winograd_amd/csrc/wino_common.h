@@ -133,6 +133,10 @@ __device__ __forceinline__ void buf_store16_nt(f32x4 v, buffer_rsrc_t rsrc, unsi
 __device__ __forceinline__ f32x4 slab_load16(buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
   return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 16));
 }
+// plain 16-byte load through a buffer descriptor (out of range: zeros)
+__device__ __forceinline__ f32x4 buf_load16(buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
+  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
+}
 #else  // host pass: the kernels are only parsed, these builtins do not exist there
 typedef int buffer_rsrc_t;
 __device__ inline buffer_rsrc_t make_rsrc(const void*, unsigned) { return 0; }
@@ -141,6 +145,7 @@ __device__ inline void slab_store16(f32x4, buffer_rsrc_t, unsigned, unsigned) {}
 __device__ inline void buf_store16(f32x4, buffer_rsrc_t, unsigned, unsigned) {}
 __device__ inline void buf_store16_nt(f32x4, buffer_rsrc_t, unsigned, unsigned) {}
 __device__ inline f32x4 slab_load16(buffer_rsrc_t, unsigned, unsigned) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
+__device__ inline f32x4 buf_load16(buffer_rsrc_t, unsigned, unsigned) { return f32x4{0.f, 0.f, 0.f, 0.f}; }
 #endif
 
 // Division of a 32-bit unsigned by a launch-invariant divisor (Granlund-Montgomery): the

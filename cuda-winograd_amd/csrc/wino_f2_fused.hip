@@ -34,7 +34,7 @@
 // LDS bank-conflict avoidance is done by XOR-permuting 16-byte units, applied on the DMA
 // *source* address for the raw patches (the LDS destination of an LDS-DMA is lane-linear)
 // and baked into the packed filter layout for U.
-#include "wino_f2_small_kernel.h"
+#include "wino_f2_launch.h"
 
 #include <atomic>
 #include <mutex>
@@ -142,14 +142,6 @@ long wino_filter_f2_index(int C, int K, int e, int c, int k) {
   return (long)u_index(C, K, e, c, k);
 }
 
-static int check_ck(int C, int K) {
-  if (C <= 0 || K <= 0 || (C % 8) != 0 || (K % 64) != 0) {
-    set_error("unsupported channels C=%d K=%d (need C %% 8 == 0, K %% 64 == 0)", C, K);
-    return WINO_E_SHAPE;
-  }
-  return WINO_OK;
-}
-
 int wino_filter_transform_f2(const float* w_kcrs, float* U, int C, int K, wino_stream_t s) {
   if (!w_kcrs || !U) { set_error("NULL pointer"); return WINO_E_ARG; }
   if (misaligned16(U)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
@@ -172,14 +164,6 @@ int wino_filter_import_f4(const float* u36, float* U, int C, int K, wino_stream_
 
 }  // extern "C"
 
-// ---------------------------------------------------------------------------------
-// Stream-K scratch of this kernel: 2 slabs of SLAB_BYTES per logical workgroup, one ticket counter
-// per (item, wave); the per-(device, stream) set lives in wino_runtime.hip (sk_scratch).
-// ---------------------------------------------------------------------------------
-static int sk_workspace(int dev, hipStream_t s, int G, size_t items, SkBufs* bufs) {
-  const size_t wgs = G < 256 ? 256 : (size_t)G;
-  return sk_scratch(dev, s, 2 * wgs * SLAB_BYTES, items * 8, bufs);
-}
 
 // Launch geometry of the throughput kernel (see the header of wino_f2_fused_kernel.h): G logical
 // workgroups run items / G whole-item rounds and share the remaining items % G items as a
@@ -254,44 +238,7 @@ static int sk_grid_for(int cus, long long items, int nchunks, const Knobs& kn) {
   return (int)g;
 }
 
-// The largest batch one launch takes: the kernels address the tensors with 32-bit byte offsets
-// (both tensors must stay below 4 GiB) and the stream-K bookkeeping counts chunk iterations in
-// 32 bits.  Larger batches are split by the launcher (images are independent).
-static long long conv3x3_batch_limit(int H, int W, int C, int K) {
-  const unsigned long long per_image = (unsigned long long)(H + 2) * (W + 2) * (unsigned long long)(C > K ? C : K) * sizeof(float);
-  long long n = (long long)(((1ull << 32) - 1) / per_image);
-  const long long tiles = (long long)((H + 1) / 2) * ((W + 1) / 2);
-  const long long per_tb = (long long)(K / KB) * (C / BC);               // chunk iterations per 64-tile block
-  const long long max_tb = ((1ll << 31) - 1) / per_tb - 1;
-  const long long n_iter = max_tb * TB / tiles;
-  if (n > n_iter) n = n_iter;
-  if (n > (1ll << 30)) n = 1ll << 30;
-  return n;
-}
 
-static int check_conv3x3_dims(int H, int W, int C, int K) {
-  if (int rc = check_ck(C, K)) return rc;
-  if (H < 1 || W < 1 || H > 4094 || W > 4094) {
-    set_error("unsupported feature map %dx%d", H, W);
-    return WINO_E_SHAPE;
-  }
-  if (conv3x3_batch_limit(H, W, C, K) < 1) {
-    set_error("%dx%d C=%d K=%d: one image does not fit a launch (tensors must stay below 4 GiB)", H, W, C, K);
-    return WINO_E_SHAPE;
-  }
-  return WINO_OK;
-}
-
-// one launch
-static int check_conv3x3(int N, int H, int W, int C, int K) {
-  if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
-  if (N < 1 || N > conv3x3_batch_limit(H, W, C, K)) {
-    set_error("bad batch N=%d (one launch takes 1..%lld images of this shape: input/output below 4 GiB)", N,
-              conv3x3_batch_limit(H, W, C, K));
-    return WINO_E_SHAPE;
-  }
-  return WINO_OK;
-}
 
 // Two kernels, same arithmetic: the throughput kernel (64-tile x 64-out-channel items, 8-wave
 // workgroups, whole-item rounds + stream-K tail) and the one-wave-per-SIMD latency kernel (blocks of 16 tiles
@@ -306,13 +253,6 @@ static int check_conv3x3(int N, int H, int W, int C, int K) {
 // channels, within 3 us): the latency kernel's price per task grows with C, and from 384 channels on a full round of
 // its blocks is the slower launch.
 // WINO_3X3_ALGO=big|small, WINO_SMALL_SPLIT, WINO_SMALL_CT override.
-struct SmallPlan {
-  bool use;
-  int split, nT16;       // nT16: blocks of 16 tiles
-  size_t blocks;
-  int ct;                // MFMA tiles per wave, side by side
-  double t_us;           // the model's time
-};
 // T = 5.70 us + rounds x (0.487 + (0.509 + 0.229 fill) CT) us + split cost: a round is 8 whole-line pixel loads per wave
 // (the workgroup's 32, shared through LDS) and 8 CT filter-fragment loads; fill = workgroups / CUs; the split cost (slab
 // round trip, growing with the block) 0.4 / 1.2 / 4.5 us at CT = 1 / 2 / 4.  148 measured forms, rms 0.85 us.
@@ -363,23 +303,8 @@ static SmallPlan small_plan(int N, int H, int W, int C, int K, int cus, const Kn
   if (kn.small_split >= 1 && kn.small_split <= SMALL_MAX_SPLIT) pl.split = kn.small_split;
   return pl;
 }
-static int small_scratch(int dev, hipStream_t s, const SmallPlan& pl, SkBufs* bufs) {
-  bufs->slabs = nullptr; bufs->tickets = nullptr; bufs->err = nullptr;
-  if (pl.split <= 1) return WINO_OK;
-  return sk_scratch(dev, s, pl.blocks * pl.split * pl.ct * SMALL_SLAB_BYTES, pl.blocks, bufs);
-}
 
-// The plan of one launch, read by every consumer -- the launch, prepare, the clock probe and the wino_conv3x3_*plan*
-// queries: the latency kernel's form and, when that kernel does not run or `throughput` asks for it all the same, the
-// throughput kernel's grid and work layout.
-struct Plan3x3 {
-  SmallPlan small;
-  Geo geo;
-  int G;            // logical workgroups of the throughput kernel
-  long long items;
-  FusedParams fp;   // its shape and work layout; the tensor and scratch pointers are filled in at launch
-};
-static Plan3x3 plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs& kn, bool throughput) {
+Plan3x3 wino::plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs& kn, bool throughput) {
   Plan3x3 p{};
   const unsigned tiles_x = (unsigned)((W + 1) / 2), tiles = (unsigned)((H + 1) / 2) * tiles_x;
   p.geo = {H + 2, W + 2, tiles, tiles_x, make_fastdiv(tiles), make_fastdiv(tiles_x)};
@@ -393,8 +318,7 @@ static Plan3x3 plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs&
   return p;
 }
 
-// the plan of a launch on the current device; *dev receives the device
-static int plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p) {
+int wino::plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p) {
   int cus = 0;
   if (int rc = current_device(dev, &cus)) return rc;
   *p = plan_3x3(N, H, W, C, K, cus, knobs(), throughput);
@@ -417,68 +341,7 @@ static int conv3x3_prepare(int N, int H, int W, int C, int K, hipStream_t s) {
   return sk_workspace(dev, s, p.G, (size_t)p.items, &bufs);
 }
 
-// the latency kernel's instantiations by [GEN][CT / 2]
-static void (*const SMALL_KERNELS[2][3])(SmallParams) = {
-    {wino_f2_small_kernel<1, false>, wino_f2_small_kernel<2, false>, wino_f2_small_kernel<4, false>},
-    {wino_f2_small_kernel<1, true>, wino_f2_small_kernel<2, true>, wino_f2_small_kernel<4, true>}};
 
-template <bool GEN, bool TAIL>
-static int launch_fused(const FusedParams& prm, int G, int dev, hipStream_t s) {
-  // all 160 KB of the CU's LDS
-  if (int rc = lds_cap_once<wino_f2_fused_kernel<0, GEN, TAIL>>(dev, LDS_BYTES)) return rc;
-  hipLaunchKernelGGL((wino_f2_fused_kernel<0, GEN, TAIL>), dim3(G), dim3(NTHREADS), LDS_BYTES, s, prm);
-  const int rc = launch_status("wino_f2_fused_kernel");
-  if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
-  return rc;
-}
-
-static int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, const float* bnScale,
-                              float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
-  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
-  const bool fixed14 = H == WINO_PQ && W == WINO_PQ;
-  int dev = 0;
-  Plan3x3 p;
-  if (int rc = plan_3x3_here(N, H, W, C, K, false, &dev, &p)) return rc;
-  if (p.small.use) {
-    const SmallPlan& sp = p.small;
-    SkBufs bufs;
-    if (int rc = small_scratch(dev, s, sp, &bufs)) return rc;
-    const SmallParams prm = {in, U, bnBias, bnScale, out, N, C, K, relu, bufs.slabs, bufs.tickets, bufs.err, nullptr, p.geo};
-    const dim3 grid(K / (16 * sp.ct), sp.nT16, sp.split), block(64 * SMALL_WAVES);   // x = out-channel block: see the kernel
-    hipLaunchKernelGGL(SMALL_KERNELS[!fixed14][sp.ct >> 1], grid, block, 0, s, prm);
-    const int rc = launch_status("wino_f2_small_kernel");
-    if (rc && sp.split > 1) sk_mark_failed(dev, s);
-    return rc;
-  }
-  SkBufs bufs;
-  if (int rc = sk_workspace(dev, s, p.G, (size_t)p.items, &bufs)) return rc;
-  FusedParams prm = p.fp;
-  prm.in = in, prm.Uq = U, prm.relu = relu, prm.bnBias = bnBias, prm.bnScale = bnScale, prm.out = out;
-  prm.slabs = bufs.slabs, prm.tickets = bufs.tickets, prm.err = bufs.err;
-  // whole items only (no stream-K tail): the kernel variant without the hand-off in its epilogue
-  if (p.items % p.G == 0) return fixed14 ? launch_fused<false, false>(prm, p.G, dev, s) : launch_fused<true, false>(prm, p.G, dev, s);
-  return fixed14 ? launch_fused<false, true>(prm, p.G, dev, s) : launch_fused<true, true>(prm, p.G, dev, s);
-}
-
-// Any batch: batches whose tensors would reach 4 GiB go out as several launches of whole images
-// (a multiple of 64 images each, so that every launch but the last fills its 64-tile blocks).
-static int conv3x3_launch(const float* in, const float* U, const float* bnBias, const float* bnScale,
-                          float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
-  if (!in || !U || !bnBias || !bnScale || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(in, U, out)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
-  if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
-  if (N < 1) { set_error("bad batch N=%d", N); return WINO_E_SHAPE; }
-  long long step = conv3x3_batch_limit(H, W, C, K);
-  if (N <= step) return conv3x3_launch_one(in, U, bnBias, bnScale, out, N, H, W, C, K, relu, s);
-  if (step > 64) step -= step % 64;
-  const size_t in_img = (size_t)(H + 2) * (W + 2) * C, out_img = (size_t)(H + 2) * (W + 2) * K;
-  for (long long n0 = 0; n0 < N; n0 += step) {
-    const int n = (int)(N - n0 < step ? N - n0 : step);
-    if (int rc = conv3x3_launch_one(in + (size_t)n0 * in_img, U, bnBias, bnScale, out + (size_t)n0 * out_img,
-                                    n, H, W, C, K, relu, s)) return rc;
-  }
-  return WINO_OK;
-}
 
 // Diagnostic: the throughput kernel's stamped build (ABLATE = 16: s_memtime / s_memrealtime at the start
 // and at the end of every workgroup's main loop, each pair stored at once; the outputs are the product kernel's).  bench.py runs it right
@@ -586,13 +449,15 @@ int wino_conv3x3_prepare_hw(int N, int H, int W, int C, int K, wino_stream_t s) 
 int wino_conv3x3_bn_relu(const float* in, const float* U, const float* bnBias,
                          const float* bnScale, float* out, int N, int C, int K, int relu,
                          wino_stream_t s) {
-  return conv3x3_launch(in, U, bnBias, bnScale, out, N, WINO_PQ, WINO_PQ, C, K, relu, (hipStream_t)s);
+  return wino_conv3x3_bn_relu_hw(in, U, bnBias, bnScale, out, N, WINO_PQ, WINO_PQ, C, K, relu, s);
 }
 
 int wino_conv3x3_bn_relu_hw(const float* in, const float* U, const float* bnBias,
                             const float* bnScale, float* out, int N, int H, int W, int C, int K,
                             int relu, wino_stream_t s) {
-  return conv3x3_launch(in, U, bnBias, bnScale, out, N, H, W, C, K, relu, (hipStream_t)s);
+  if (!in || !U || !bnBias || !bnScale || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
+  if (misaligned16(in, U, out)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  return conv3x3_launch<false>(in, U, bnBias, bnScale, nullptr, out, N, H, W, C, K, relu, (hipStream_t)s);
 }
 
 }  // extern "C"

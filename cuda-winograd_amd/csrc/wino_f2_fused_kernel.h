@@ -187,6 +187,15 @@ struct FusedParams {
   unsigned* err;               // host-visible word, set when a ticket is drawn on a counter that was not zero at launch
   unsigned long long* dbg;     // diagnostic builds only (ABLATE & (16 | 2048)): where the stamps go
 };
+// The arguments of the RES = true kernels: the plain ones, then the residual (padded like `out`; its ring is not read).
+// The residual goes behind every existing field in a struct of its own rather than into FusedParams, so that the plain
+// kernels' argument segment -- and the offsets of the implicit arguments the runtime places behind it -- stay as they
+// were: their code is byte-identical with or without this form.
+struct FusedResParams : FusedParams {
+  const float* res;
+};
+template <bool RES>
+using FusedArgs = std::conditional_t<RES, FusedResParams, FusedParams>;
 
 // Host side: the work layout fields above (ndp ... d_copies) of `items` items of p.C / BC chunk iterations on a grid
 // of G logical workgroups: items / G whole-item rounds, the rest a stream-K tail.
@@ -230,9 +239,14 @@ __device__ unsigned long long wino_clk_slot_3x3[4];
 // 40.1 -> 39.6 us, 256 channels N = 64 71.7 -> 71.0.  (Tried for the launches WITH a tail in the same step: the
 // gather with two slabs in flight and the accumulators re-zeroed at the end of the epilogue to make room -- no
 // gain at small batches, where an item has up to 8 segments, +0.8..1.2 % at 256 channels N = 96 / 256.)
-template <int ABLATE, bool GEN = false, bool TAIL = true>
+//
+// RES = the residual epilogue (the second 3x3 of a ResNet basic block): out = act(scale*conv + bias + res), res padded
+// like out.  BN is applied before the LDS transpose as in the plain form; the ReLU waits until the residual's 16 bytes,
+// loaded at the store's own offset, have been added.  Each residual element is read only by the lane that stores that
+// offset, before its store, so out may be res (in place).  RES = false compiles exactly the plain kernel.
+template <int ABLATE, bool GEN = false, bool TAIL = true, bool RES = false>
 __global__ void __launch_bounds__(NTHREADS, 2)
-wino_f2_fused_kernel(const FusedParams prm) {
+wino_f2_fused_kernel(const FusedArgs<RES> prm) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const float* in = prm.in;
   const float* Uq = prm.Uq;
@@ -976,6 +990,26 @@ wino_f2_fused_kernel(const FusedParams prm) {
       // XORed with (tile>>2)&3 = the MFMA row group h, which makes the ds_write_b32 of the 4 row
       // groups and the ds_read_b128 of every 16 lanes hit 64 distinct banks.
       const int tb = item / KBLK, kb = item - tb * KBLK;
+      // RES: the eight residual runs this lane stores are requested before the transpose, so that their latency hides
+      // under it; each only where its store is kept (the residual's ring is never read)
+      f32x4 rv[RES ? 8 : 1];
+      if constexpr (RES) {
+        typedef const __attribute__((address_space(4))) FusedResParams* ResKernargPtr;
+        const auto rsrc_res = make_rsrc(((ResKernargPtr)kp)->res, (unsigned)((size_t)N * Hp * Wp * K * sizeof(float)));
+        const int px = (ln >> 3) & 3, pa = px >> 1, pb = px & 1;
+        const unsigned kbyte = (unsigned)((kb * KB + e_wk * 32 + (ln & 7) * 4) * sizeof(float));
+#pragma unroll
+        for (int i = 0; i < 8; i++) {   // (the addressing of the store loop below)
+          const int g = tb * TB + e_wt * 16 + 2 * i + (ln >> 5);
+          const bool live = g < totalTiles;
+          const TileCoord tc = decode_tile_g<GEN>(live ? g : 0, geo);
+          const int py = 1 + 2 * tc.ty + pa, pxx = 1 + 2 * tc.tx + pb;
+          const unsigned img = (unsigned)(tc.n * Hp * Wp);
+          rv[i] = (f32x4){0.f, 0.f, 0.f, 0.f};
+          if (live && (!GEN || (py <= Hp - 2 && pxx <= Wp - 2)))
+            rv[i] = buf_load16(rsrc_res, (unsigned)((img + py * Wp + pxx) * K * sizeof(float)) + kbyte, 0);
+        }
+      }
       int ep_wbase[4], ep_rbase[4];
 #pragma unroll
       for (int jj = 0; jj < 4; jj++) {
@@ -990,7 +1024,7 @@ wino_f2_fused_kernel(const FusedParams prm) {
 #pragma unroll
           for (int pp = 0; pp < 4; pp++) {
             float v1 = sc2[cb] * y[r][cb][pp] + bi2[cb];
-            if (relu) v1 = fmaxf(v1, 0.f);
+            if (!RES && relu) v1 = fmaxf(v1, 0.f);   // (RES: after the residual's add, below)
             const int g = pp * 2 + cb;
             *(float*)(wreg + ep_wbase[g & 3] + r * 512 + (g >> 2) * 256) = v1;
           }
@@ -1002,7 +1036,14 @@ wino_f2_fused_kernel(const FusedParams prm) {
       const unsigned kbyte = (unsigned)((kb * KB + e_wk * 32 + (ln & 7) * 4) * sizeof(float));
 #pragma unroll
       for (int i = 0; i < 8; i++) {
-        const f32x4 val = *(const f32x4*)(wreg + ep_rbase[i >> 1] + i * 1024);
+        f32x4 val = *(const f32x4*)(wreg + ep_rbase[i >> 1] + i * 1024);
+        if constexpr (RES) {
+          val += rv[i];
+          if (relu) {
+#pragma unroll
+            for (int q = 0; q < 4; q++) val[q] = fmaxf(val[q], 0.f);
+          }
+        }
         const int g = tb * TB + e_wt * 16 + 2 * i + (ln >> 5);
         const bool live = g < totalTiles;
         const TileCoord tc = decode_tile_g<GEN>(live ? g : 0, geo);

@@ -1,0 +1,184 @@
+// The 3x3 F(2x2,3x3) layers' launch plan and launcher, shared by the translation units that launch them:
+// wino_f2_fused.hip (the plain epilogue, RES = false) and conv3x3_res.hip (the residual epilogue, RES = true: the second
+// 3x3 of a ResNet basic block).  A template is instantiated where it is used, so each file compiles the kernels of its
+// own epilogue and no others.  The planner (plan_3x3, plan_3x3_here) is defined once, in wino_f2_fused.hip: a residual
+// launch takes exactly the plan of the plain layer of the same shape.
+#pragma once
+#include "wino_f2_small_kernel.h"
+
+namespace wino {
+using namespace fused;
+
+inline int check_ck(int C, int K) {
+  if (C <= 0 || K <= 0 || (C % 8) != 0 || (K % 64) != 0) {
+    set_error("unsupported channels C=%d K=%d (need C %% 8 == 0, K %% 64 == 0)", C, K);
+    return WINO_E_SHAPE;
+  }
+  return WINO_OK;
+}
+
+// ---------------------------------------------------------------------------------
+// Stream-K scratch of this kernel: 2 slabs of SLAB_BYTES per logical workgroup, one ticket counter
+// per (item, wave); the per-(device, stream) set lives in wino_runtime.hip (sk_scratch).
+// ---------------------------------------------------------------------------------
+inline int sk_workspace(int dev, hipStream_t s, int G, size_t items, SkBufs* bufs) {
+  const size_t wgs = G < 256 ? 256 : (size_t)G;
+  return sk_scratch(dev, s, 2 * wgs * SLAB_BYTES, items * 8, bufs);
+}
+
+// The largest batch one launch takes: the kernels address the tensors with 32-bit byte offsets
+// (both tensors must stay below 4 GiB) and the stream-K bookkeeping counts chunk iterations in
+// 32 bits.  Larger batches are split by the launcher (images are independent).
+inline long long conv3x3_batch_limit(int H, int W, int C, int K) {
+  const unsigned long long per_image = (unsigned long long)(H + 2) * (W + 2) * (unsigned long long)(C > K ? C : K) * sizeof(float);
+  long long n = (long long)(((1ull << 32) - 1) / per_image);
+  const long long tiles = (long long)((H + 1) / 2) * ((W + 1) / 2);
+  const long long per_tb = (long long)(K / KB) * (C / BC);               // chunk iterations per 64-tile block
+  const long long max_tb = ((1ll << 31) - 1) / per_tb - 1;
+  const long long n_iter = max_tb * TB / tiles;
+  if (n > n_iter) n = n_iter;
+  if (n > (1ll << 30)) n = 1ll << 30;
+  return n;
+}
+
+inline int check_conv3x3_dims(int H, int W, int C, int K) {
+  if (int rc = check_ck(C, K)) return rc;
+  if (H < 1 || W < 1 || H > 4094 || W > 4094) {
+    set_error("unsupported feature map %dx%d", H, W);
+    return WINO_E_SHAPE;
+  }
+  if (conv3x3_batch_limit(H, W, C, K) < 1) {
+    set_error("%dx%d C=%d K=%d: one image does not fit a launch (tensors must stay below 4 GiB)", H, W, C, K);
+    return WINO_E_SHAPE;
+  }
+  return WINO_OK;
+}
+
+// one launch
+inline int check_conv3x3(int N, int H, int W, int C, int K) {
+  if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
+  if (N < 1 || N > conv3x3_batch_limit(H, W, C, K)) {
+    set_error("bad batch N=%d (one launch takes 1..%lld images of this shape: input/output below 4 GiB)", N,
+              conv3x3_batch_limit(H, W, C, K));
+    return WINO_E_SHAPE;
+  }
+  return WINO_OK;
+}
+
+// Two kernels, same arithmetic: the throughput kernel (64-tile x 64-out-channel items, 8-wave
+// workgroups, whole-item rounds + stream-K tail) and the one-wave-per-SIMD latency kernel (blocks of 16 tiles
+// x 16 CT out-channels, CT = 1, 2 or 4; any feature map; wino_f2_small_kernel.h), which wins while its blocks fit
+// ONE round of the CUs (a second round of blocks doubles the latency kernel's time at once).
+// While the blocks leave CUs idle the latency kernel also splits a block's contraction over S workgroups
+// (C-split): S as large as the idle CUs allow (at most 8, and every wave of the S workgroups gets a task in the
+// first round: 4 S <= 2 C / 16).
+// Among the block widths that fit, the one with the shortest modelled time (small_form below; least squares over the
+// forms measured by tools/latency_cases.py explore3, profiles/r3/), and only while that beats the throughput kernel's
+// fitted time in this regime, 18.8 us + 0.0174 us x C + 1.94 us x (chunk iterations per CU) (54 points at 64 ... 512
+// channels, within 3 us): the latency kernel's price per task grows with C, and from 384 channels on a full round of
+// its blocks is the slower launch.
+// WINO_3X3_ALGO=big|small, WINO_SMALL_SPLIT, WINO_SMALL_CT override.
+struct SmallPlan {
+  bool use;
+  int split, nT16;       // nT16: blocks of 16 tiles
+  size_t blocks;
+  int ct;                // MFMA tiles per wave, side by side
+  double t_us;           // the model's time
+};
+
+inline int small_scratch(int dev, hipStream_t s, const SmallPlan& pl, SkBufs* bufs) {
+  bufs->slabs = nullptr; bufs->tickets = nullptr; bufs->err = nullptr;
+  if (pl.split <= 1) return WINO_OK;
+  return sk_scratch(dev, s, pl.blocks * pl.split * pl.ct * SMALL_SLAB_BYTES, pl.blocks, bufs);
+}
+
+// The plan of one launch, read by every consumer -- the launch, prepare, the clock probe and the wino_conv3x3_*plan*
+// queries: the latency kernel's form and, when that kernel does not run or `throughput` asks for it all the same, the
+// throughput kernel's grid and work layout.
+struct Plan3x3 {
+  SmallPlan small;
+  Geo geo;
+  int G;            // logical workgroups of the throughput kernel
+  long long items;
+  FusedParams fp;   // its shape and work layout; the tensor and scratch pointers are filled in at launch
+};
+Plan3x3 plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs& kn, bool throughput);
+// the plan of a launch on the current device; *dev receives the device
+int plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p);
+
+// the latency kernel's instantiations by [GEN][CT / 2]
+template <bool RES>
+constexpr decltype(&wino_f2_small_kernel<1, false, false, RES>) SMALL_3X3_KERNELS[2][3] = {
+    {wino_f2_small_kernel<1, false, false, RES>, wino_f2_small_kernel<2, false, false, RES>,
+     wino_f2_small_kernel<4, false, false, RES>},
+    {wino_f2_small_kernel<1, true, false, RES>, wino_f2_small_kernel<2, true, false, RES>,
+     wino_f2_small_kernel<4, true, false, RES>}};
+
+template <bool GEN, bool TAIL, bool RES>
+int launch_fused(const FusedArgs<RES>& prm, int G, int dev, hipStream_t s) {
+  // all 160 KB of the CU's LDS
+  if (int rc = lds_cap_once<wino_f2_fused_kernel<0, GEN, TAIL, RES>>(dev, LDS_BYTES)) return rc;
+  hipLaunchKernelGGL((wino_f2_fused_kernel<0, GEN, TAIL, RES>), dim3(G), dim3(NTHREADS), LDS_BYTES, s, prm);
+  const int rc = launch_status("wino_f2_fused_kernel");
+  if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
+  return rc;
+}
+
+// One launch of `plan_3x3_here`'s plan.  RES: out = act(bnScale*conv + bnBias + res), res padded like out; the plan is
+// the plain layer's (res is not read by RES = false).
+template <bool RES>
+int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, const float* bnScale, const float* res,
+                       float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
+  if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
+  const bool fixed14 = H == WINO_PQ && W == WINO_PQ;
+  int dev = 0;
+  Plan3x3 p;
+  if (int rc = plan_3x3_here(N, H, W, C, K, false, &dev, &p)) return rc;
+  if (p.small.use) {
+    const SmallPlan& sp = p.small;
+    SkBufs bufs;
+    if (int rc = small_scratch(dev, s, sp, &bufs)) return rc;
+    SmallArgs<RES> prm;
+    static_cast<SmallParams&>(prm) = {in, U, bnBias, bnScale, out, N, C, K, relu, bufs.slabs, bufs.tickets, bufs.err, nullptr, p.geo};
+    if constexpr (RES) prm.res = res;
+    const dim3 grid(K / (16 * sp.ct), sp.nT16, sp.split), block(64 * SMALL_WAVES);   // x = out-channel block: see the kernel
+    hipLaunchKernelGGL(SMALL_3X3_KERNELS<RES>[!fixed14][sp.ct >> 1], grid, block, 0, s, prm);
+    const int rc = launch_status("wino_f2_small_kernel");
+    if (rc && sp.split > 1) sk_mark_failed(dev, s);
+    return rc;
+  }
+  SkBufs bufs;
+  if (int rc = sk_workspace(dev, s, p.G, (size_t)p.items, &bufs)) return rc;
+  FusedArgs<RES> prm;
+  static_cast<FusedParams&>(prm) = p.fp;
+  prm.in = in, prm.Uq = U, prm.relu = relu, prm.bnBias = bnBias, prm.bnScale = bnScale, prm.out = out;
+  prm.slabs = bufs.slabs, prm.tickets = bufs.tickets, prm.err = bufs.err;
+  if constexpr (RES) prm.res = res;
+  // whole items only (no stream-K tail): the kernel variant without the hand-off in its epilogue
+  if (p.items % p.G == 0)
+    return fixed14 ? launch_fused<false, false, RES>(prm, p.G, dev, s) : launch_fused<true, false, RES>(prm, p.G, dev, s);
+  return fixed14 ? launch_fused<false, true, RES>(prm, p.G, dev, s) : launch_fused<true, true, RES>(prm, p.G, dev, s);
+}
+
+// Any batch: batches whose tensors would reach 4 GiB go out as several launches of whole images
+// (a multiple of 64 images each, so that every launch but the last fills its 64-tile blocks).  The residual has
+// K channels, like out: it advances with out, and the per-image limit already covers it.
+// The caller has checked the pointers.
+template <bool RES>
+int conv3x3_launch(const float* in, const float* U, const float* bnBias, const float* bnScale, const float* res,
+                   float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
+  if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
+  if (N < 1) { set_error("bad batch N=%d", N); return WINO_E_SHAPE; }
+  long long step = conv3x3_batch_limit(H, W, C, K);
+  if (N <= step) return conv3x3_launch_one<RES>(in, U, bnBias, bnScale, res, out, N, H, W, C, K, relu, s);
+  if (step > 64) step -= step % 64;
+  const size_t in_img = (size_t)(H + 2) * (W + 2) * C, out_img = (size_t)(H + 2) * (W + 2) * K;
+  for (long long n0 = 0; n0 < N; n0 += step) {
+    const int n = (int)(N - n0 < step ? N - n0 : step);
+    if (int rc = conv3x3_launch_one<RES>(in + (size_t)n0 * in_img, U, bnBias, bnScale, RES ? res + (size_t)n0 * out_img : nullptr,
+                                         out + (size_t)n0 * out_img, n, H, W, C, K, relu, s)) return rc;
+  }
+  return WINO_OK;
+}
+
+}  // namespace wino

@@ -77,13 +77,22 @@ struct SmallParams {
   unsigned long long* dbg;   // timeline build only (DIAG, tools/small_timeline): 8 stamps per workgroup
   Geo geo;                   // GEN = true only: the feature map (other than the reference's 14 x 14)
 };
+// RES = true: the plain arguments, then the residual, padded like `out` (its ring is not read); a struct of its own, as
+// FusedResParams, so that the plain kernels' argument segment is unchanged
+struct SmallResParams : SmallParams {
+  const float* res;
+};
+template <bool RES>
+using SmallArgs = std::conditional_t<RES, SmallResParams, SmallParams>;
 
 // DIAG = true is the timeline build (tools/small_timeline.hip): wave 0 of every workgroup stores s_memrealtime
 // (100 MHz, chip-wide) at entry, first stage in LDS, MFMAs done, LDS level done, slab drained, ticket drawn, gather
 // landed, exit.  The product kernel is DIAG = false.
-template <int CT, bool GEN = false, bool DIAG = false>
+// RES = the residual epilogue: out = act(scale*conv + bias + res), res padded like out, read by the finishing lane at
+// its store's own offset just before the store (so out may be res); the ReLU follows the add.
+template <int CT, bool GEN = false, bool DIAG = false, bool RES = false>
 __global__ void __launch_bounds__(64 * SMALL_WAVES)
-wino_f2_small_kernel(const SmallParams prm) {
+wino_f2_small_kernel(const SmallArgs<RES> prm) {
   static_assert(CT == 1 || CT == 2 || CT == 4, "MFMA tiles per wave");
   constexpr int STAGE = 16 * 16 * 128;                   // one round's patches: 16 tiles x 16 px x 32 channels
   static_assert(2 * STAGE >= (SMALL_WAVES - 1) * CT * 4 * 64 * 16, "the reduction image reuses the stages");
@@ -394,6 +403,11 @@ wino_f2_small_kernel(const SmallParams prm) {
     for (int pp = 0; pp < 4; pp++) {
       f32x4 val = {y[c][0][pp], y[c][1][pp], y[c][2][pp], y[c][3][pp]};
       val = sc4[c] * val + bi4[c];
+      if constexpr (RES) {   // the residual at this store's offset, where the store is kept (its ring is not read)
+        if (!GEN || (oy + (pp >> 1) <= Hp - 2 && ox + (pp & 1) <= Wp - 2))
+          val += *(const f32x4*)(prm.res + (size_t)tc.n * Hp * Wp * K + (kqq * CT + c) * 16 + 4 * h +
+                                 (size_t)((oy + (pp >> 1)) * Wp + ox + (pp & 1)) * K);
+      }
       if (relu) {
 #pragma unroll
         for (int r = 0; r < 4; r++) val[r] = fmaxf(val[r], 0.f);

@@ -53,7 +53,8 @@ extern "C" {
  * WINO_E_STATE, wino_proj_tail_elems, wino_proj_tail_pack, wino_proj_block_workspace_bytes_hw,
  * wino_proj_block_prepare_hw, wino_proj_block_hw, wino_proj_tail_plan, WINO_1X1_FORM_*,
  * wino_conv3x3_s2_bn_relu_hw, wino_conv3x3_s2_prepare_hw, wino_conv3x3_s2_plan, wino_proj_block_v15_hw,
- * wino_proj_block_v15_workspace_bytes_hw, wino_proj_block_v15_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_proj_block_v15_workspace_bytes_hw, wino_proj_block_v15_prepare_hw, wino_conv3x3_bn_add_relu_hw,
+ * wino_basic_block_workspace_bytes_hw, wino_basic_block_hw, wino_basic_block_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived). */
 #define WINO_ABI_VERSION 1
 
@@ -418,6 +419,32 @@ typedef struct {
   double max_rel_diff;   /* ... / max |CPU| */
 } wino_cpu_baseline_result;
 int wino_driver_cpu_baseline(wino_cpu_baseline_result* r);
+
+/* ---- ResNet basic block (ResNet-18 / -34) -----------------------------------------------------
+ * out = act(bnScale*conv3x3(in, U) + bnBias + residual): the second 3x3 of a ResNet basic block.
+ * in [N][H+2][W+2][C]; residual, out [N][H+2][W+2][K] (result at [1..H][1..W], out's ring written 0,
+ * residual's ring not read).  Constraints of wino_conv3x3_bn_relu_hw.  out may BE residual (in place);
+ * any other overlap among in, residual and out is WINO_E_ARG.
+ * In place is safe: each residual element is read only by the lane that stores the output at the same offset,
+ * just before that store, and the ring pass writes zeros onto a ring that is not read.  The launch takes exactly the
+ * plan of wino_conv3x3_bn_relu_hw at the same shape (wino_conv3x3_plan / wino_conv3x3_small_plan2 describe it, and
+ * wino_conv3x3_prepare_hw prepares it); the ReLU (relu != 0) is applied after the add. */
+int wino_conv3x3_bn_add_relu_hw(const float* in, const float* U, const float* bnBias, const float* bnScale,
+                                const float* residual, float* out, int N, int H, int W, int C, int K,
+                                int relu, wino_stream_t s);
+
+/* Identity basic block: out = relu(bn2(conv3x3(relu(bn1(conv3x3(x, U1))), U2)) + x).
+ * x, out [N][H+2][W+2][C] with a zero ring (out's ring written 0: out is the next block's x); U1, U2 from
+ * wino_filter_transform_f2 (C -> C).  Two launches; t1 [N][H+2][W+2][C] lives in workspace.
+ * out may be x (in place: a chain of blocks then needs one activation tensor and one workspace); workspace must
+ * not overlap x or out; any other overlap of x and out is WINO_E_ARG.  Constraints of wino_conv3x3_bn_relu_hw with
+ * K = C (C % 64 == 0).  wino_basic_block_prepare_hw reserves the stream's scratch for both launches (before a
+ * graph capture). */
+size_t wino_basic_block_workspace_bytes_hw(int N, int H, int W, int C);
+int wino_basic_block_hw(const float* x, const float* U1, const float* bn1Bias, const float* bn1Scale,
+                        const float* U2, const float* bn2Bias, const float* bn2Scale, float* out,
+                        int N, int H, int W, int C, void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_basic_block_prepare_hw(int N, int H, int W, int C, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */

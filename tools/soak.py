@@ -1,5 +1,5 @@
 """Developer tool (GPU box): soak of the stream-K hand-offs of both kernels (the 1x1 kernel in its plain form and in
-the stride-2 3x3 layer's tap form).  For several shapes and forced
+the stride-2 3x3 layer's tap form; the 3x3 kernels also in their residual form).  For several shapes and forced
 grids, launches the layer back to back and compares every result bitwise with the first of its
 configuration (stream-K sums are added in segment order, so they must not move); under uneven load
 (a second stream runs another layer concurrently).  usage: python tools/soak.py [seconds]"""
@@ -48,6 +48,17 @@ for (N, C, K, sp, ct) in [(1, 256, 256, 4, 1), (1, 128, 128, 4, 1), (2, 256, 256
     U = pkg.filter_transform_f2(torch.rand(K, C, 3, 3, device=dev) - 0.5)
     b, s = torch.rand(K, device=dev) - 0.5, torch.rand(K, device=dev) - 0.5
     cfgs_small.append([N, C, K, (sp, ct), x, U, b, s, None])
+# the residual 3x3 layer (RES kernels): the throughput kernel with a stream-K tail, the latency kernel with S > 1
+cfg_res = []
+for (N, H, C, grid, sp, ct) in [(128, 14, 256, 333, 0, 0), (96, 28, 128, 0, 0, 0), (8, 7, 512, 13, 0, 0), (1, 14, 256, 0, 4, 1),
+                                (2, 28, 128, 0, 2, 2), (2, 7, 512, 0, 4, 4)]:
+    x = torch.zeros(N, H + 2, H + 2, C, device=dev)
+    x[:, 1:-1, 1:-1, :] = torch.rand(N, H, H, C, device=dev) - 0.5
+    r = torch.zeros_like(x)
+    r[:, 1:-1, 1:-1, :] = torch.rand(N, H, H, C, device=dev) - 0.5
+    w = (torch.rand(C, C, 3, 3, device=dev) - 0.5) / (9 * C) ** 0.5
+    b, s = torch.rand(C, device=dev) - 0.5, torch.rand(C, device=dev) + 0.5
+    cfg_res.append([N, H, C, grid, (sp, ct), x, r, w, pkg.filter_transform_f2(w), b, s, None])
 side = torch.cuda.Stream()
 xs = torch.rand(64, 16, 16, 128, device=dev); Us = pkg.filter_transform_f2(torch.rand(128, 128, 3, 3, device=dev)); vs = torch.rand(128, device=dev)
 use_side = os.environ.get("SOAK_SIDE", "1") != "0"
@@ -144,6 +155,33 @@ while time.time() - t0 < budget:
                 st[0] += 1; st[1] = max(st[1], float(d.max())); st[2] = max(st[2], int((d > 0).sum())); st[3] = max(st[3], int(torch.isnan(o).sum()))
     os.environ.pop("WINO_1X1_SK", None)
     os.environ.pop("WINO_1X1_SK_GRID", None)
+    for c in cfg_res:
+        N, H, C, grid, (sp, ct), x, r, w, U, b, s, ref = c
+        for k in ("WINO_SK_GRID", "WINO_SMALL_SPLIT", "WINO_SMALL_CT"): os.environ.pop(k, None)
+        if sp: os.environ.update(WINO_3X3_ALGO="small", WINO_SMALL_SPLIT=str(sp), WINO_SMALL_CT=str(ct))
+        else: os.environ["WINO_3X3_ALGO"] = "big"
+        if grid: os.environ["WINO_SK_GRID"] = str(grid)
+        L.wino_debug_reload_knobs()
+        if use_side:
+            with torch.cuda.stream(side):
+                for _ in range(3): pkg.conv3x3_bn_relu(xs, Us, vs, vs)
+        outs = [pkg.conv3x3_bn_add_relu(x, U, b, s, r) for _ in range(10)]
+        launches += 10
+        if ref is None:
+            c[11] = outs[0].clone(); ref = c[11]
+            y = torch.nn.functional.conv2d(x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double(), w.double(), padding=1)
+            y = y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
+            want = torch.relu(y + r[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()).permute(0, 2, 3, 1)
+            err = float((ref[:, 1:-1, 1:-1, :].double() - want).abs().max() / want.abs().max())
+            assert err < 2e-5, ("residual 3x3 first result wrong", N, H, C, grid, sp, ct, err)
+        for o in outs:
+            if not torch.equal(o, ref):
+                bad += 1
+                st = stats.setdefault(("res", N, H, C, grid, sp, ct), [0, 0.0, 0, 0])
+                d = (o - ref).abs()
+                st[0] += 1; st[1] = max(st[1], float(d.max())); st[2] = max(st[2], int((d > 0).sum())); st[3] = max(st[3], int(torch.isnan(o).sum()))
+    for k in ("WINO_SK_GRID", "WINO_SMALL_SPLIT", "WINO_SMALL_CT"): os.environ.pop(k, None)
+    os.environ["WINO_3X3_ALGO"] = "big"
     torch.cuda.synchronize()
 for k, v in stats.items(): print("  differs", k, "times", v[0], "max |diff|", v[1], "max elements", v[2], "nan", v[3])
 print("ticket counters in use at the end:", pkg.tickets_in_use())
