@@ -49,6 +49,8 @@ ABI_SYMBOLS = [
     "wino_proj_block_v15_workspace_bytes_hw", "wino_proj_block_v15_hw", "wino_proj_block_v15_prepare_hw",
     "wino_conv3x3_bn_add_relu_hw", "wino_basic_block_workspace_bytes_hw", "wino_basic_block_hw",
     "wino_basic_block_prepare_hw",
+    "wino_s2_proj_elems", "wino_s2_proj_pack", "wino_conv3x3_s2_proj_bn_relu_hw", "wino_basic_block_s2_workspace_bytes_hw",
+    "wino_basic_block_s2_hw", "wino_basic_block_s2_prepare_hw",
     # reference entry points + helpers (Kernel*.h, util.h)
     "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
     "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
@@ -160,6 +162,14 @@ def lib() -> ctypes.CDLL:
     L.wino_basic_block_workspace_bytes_hw.argtypes = [c_int] * 4
     L.wino_basic_block_hw.argtypes = [fp] * 8 + [c_int] * 4 + [fp, c_size_t, c_void_p]
     L.wino_basic_block_prepare_hw.argtypes = [c_int] * 4 + [c_void_p]
+    L.wino_s2_proj_elems.restype = c_size_t
+    L.wino_s2_proj_elems.argtypes = [c_int] * 2
+    L.wino_s2_proj_pack.argtypes = [fp] * 7 + [c_int] * 2 + [c_void_p]
+    L.wino_conv3x3_s2_proj_bn_relu_hw.argtypes = [fp] * 4 + [c_int] * 5 + [c_void_p]
+    L.wino_basic_block_s2_workspace_bytes_hw.restype = c_size_t
+    L.wino_basic_block_s2_workspace_bytes_hw.argtypes = [c_int] * 4
+    L.wino_basic_block_s2_hw.argtypes = [fp] * 6 + [c_int] * 5 + [fp, c_size_t, c_void_p]
+    L.wino_basic_block_s2_prepare_hw.argtypes = [c_int] * 5 + [c_void_p]
     for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
                  "kernel_256_1_in", "kernel_256_1_out"):
         getattr(L, name).restype = c_int
@@ -746,6 +756,95 @@ def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
                                      U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), out.data_ptr(),
                                      N, Hp - 2, Wp - 2, C, workspace.data_ptr(), workspace.numel() * 4, _stream()),
            "wino_basic_block_hw")
+    return out
+
+
+def s2_proj_pack(w_taps, bn1, wd, bnd) -> torch.Tensor:
+    """The downsampling basic block's first layer: w_taps [3][3][C][K] (filter_pack_s2), its BN bn1 = (bias, scale),
+    the shortcut wd [C][K] (torch's [K][C][1][1] weight as w.view(K, C).t()) and its BN bnd = (bias, scale), packed
+    into one opaque buffer (wino_s2_proj_pack).  The scales are not folded into the filters."""
+    w, wd = _dev(w_taps, "w_taps"), _dev(wd, "wd")
+    if w.dim() != 4 or tuple(w.shape[:2]) != (3, 3):
+        raise WinoError("w_taps must be [3][3][C][K]: pack it with filter_pack_s2")
+    C, K = int(w.shape[2]), int(w.shape[3])
+    if wd.dim() != 2 or tuple(wd.shape) != (C, K):
+        raise WinoError(f"wd must be [{C}][{K}]")
+    vecs = [_dev(v, "bn") for pair in (bn1, bnd) for v in pair]
+    if any(v.numel() != K for v in vecs):
+        raise WinoError("bn1 / bnd vectors must have K values")
+    n = lib().wino_s2_proj_elems(C, K)
+    if n == 0:
+        raise WinoError(f"bad shape C={C} K={K}")
+    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    _on_current_device(w, wd, packed, *vecs)
+    _check(lib().wino_s2_proj_pack(w.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), wd.data_ptr(),
+                                   vecs[2].data_ptr(), vecs[3].data_ptr(), packed.data_ptr(), C, K, _stream()),
+           "wino_s2_proj_pack")
+    return packed
+
+
+def _s2_proj_ck(x: torch.Tensor, packed: torch.Tensor):
+    """(N, Hin, Win, C, K) of a padded x [N][Hin+2][Win+2][C] and a buffer from s2_proj_pack."""
+    if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("x must be [N][Hin+2][Win+2][C]")
+    N, Hin, Win, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    if not isinstance(packed, torch.Tensor) or packed.dim() != 1 or packed.numel() % (10 * C + 4):
+        raise WinoError(f"packed does not match C={C}: pack it with s2_proj_pack")
+    return N, Hin, Win, C, packed.numel() // (10 * C + 4)
+
+
+def conv3x3_s2_proj(x, packed, t1=None, sc=None):
+    """The downsampling basic block's first layer, one HIP launch: t1 = relu(bn1(conv3x3_s2(x))) and the shortcut
+    sc = bnd(conv1x1_s2(x, wd)).  x [N][Hin+2][Win+2][C] with a zero ring; t1 and sc [N][H+2][W+2][K],
+    H = (Hin-1)//2 + 1: t1 exactly as conv3x3_s2_bn_relu writes it (ring 0), sc's interior written and its ring not
+    touched.  packed from s2_proj_pack.  Returns (t1, sc)."""
+    N, Hin, Win, C, K = _s2_proj_ck(x, packed)
+    x, packed = _dev(x, "x"), _dev(packed, "packed")
+    H, W = _s2_out_hw(Hin, Win)
+    shape = (N, H + 2, W + 2, K)
+    t1 = torch.empty(shape, dtype=torch.float32, device=x.device) if t1 is None else _out(t1, shape, "t1")
+    sc = torch.empty(shape, dtype=torch.float32, device=x.device) if sc is None else _out(sc, shape, "sc")
+    _on_current_device(x, packed, t1, sc)
+    _check(lib().wino_conv3x3_s2_proj_bn_relu_hw(x.data_ptr(), packed.data_ptr(), t1.data_ptr(), sc.data_ptr(), N, Hin,
+                                                 Win, C, K, _stream()), "wino_conv3x3_s2_proj_bn_relu_hw")
+    return t1, sc
+
+
+def basic_block_s2_prepare(N: int, Hin: int, Win: int, C: int, K: int) -> None:
+    """Allocate the scratch of basic_block_s2's two launches for the current stream (before graph capture)."""
+    _check(lib().wino_basic_block_s2_prepare_hw(int(N), int(Hin), int(Win), int(C), int(K), _stream()),
+           "wino_basic_block_s2_prepare_hw")
+
+
+def basic_block_s2(x, packed, U2, bn2, out=None, workspace=None) -> torch.Tensor:
+    """ResNet-18 / -34 downsampling basic block (torchvision's BasicBlock with `downsample`): out =
+    relu(bn2(conv3x3(relu(bn1(conv3x3_s2(x))), U2)) + bnd(conv1x1_s2(x, wd))).  x [N][Hin+2][Win+2][C] with a zero
+    ring -> out [N][H+2][W+2][K], H = (Hin-1)//2 + 1, its ring written 0 (the next identity basic_block's x).
+    packed from s2_proj_pack (w_taps, bn1, wd, bnd); U2 from filter_transform_f2 (K -> K); bn2 = (bias, scale).
+    Two HIP launches."""
+    N, Hin, Win, C, K = _s2_proj_ck(x, packed)
+    if not isinstance(U2, torch.Tensor) or U2.numel() != 16 * K * K:
+        raise WinoError(f"U2 must be a {K} -> {K} filter from filter_transform_f2 (16*K*K values)")
+    x, packed, U2 = _dev(x, "x"), _dev(packed, "packed"), _dev(U2, "U2")
+    vecs = [_dev(v, "bn") for v in bn2]
+    if len(vecs) != 2 or any(v.numel() != K for v in vecs):
+        raise WinoError("bn2 must be (bias, scale) with K values each")
+    H, W = _s2_out_hw(Hin, Win)
+    need = lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Win, K)
+    if workspace is None:
+        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
+    else:
+        _out(workspace, None, "workspace")
+        if workspace.numel() * 4 < need:
+            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
+    if out is None:
+        out = torch.empty((N, H + 2, W + 2, K), dtype=torch.float32, device=x.device)
+    else:
+        _out(out, (N, H + 2, W + 2, K), "out")
+    _on_current_device(x, packed, U2, out, workspace, *vecs)
+    _check(lib().wino_basic_block_s2_hw(x.data_ptr(), packed.data_ptr(), U2.data_ptr(), vecs[0].data_ptr(),
+                                        vecs[1].data_ptr(), out.data_ptr(), N, Hin, Win, C, K, workspace.data_ptr(),
+                                        workspace.numel() * 4, _stream()), "wino_basic_block_s2_hw")
     return out
 
 

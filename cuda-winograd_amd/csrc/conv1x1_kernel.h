@@ -90,7 +90,16 @@ __device__ __forceinline__ long padded_row(long m, const PadGeo& g) {
 //              and tap (dy, dx) adds the same pixel offset dy*(Win+2) + dx (Win+2 = cm) to every row; B is
 //              [3][3][C][Kout], its row (3 dy + dx) C + c tap (dy, dx) of channel c.  C % 32 == 0: no k-step and no
 //              16-channel chunk crosses a tap.
-enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3 };
+//   A_TAPS_PROJ  A_TAPS plus the downsampling basic block's 1x1 stride-2 shortcut in the same launch
+//              (basic_block_s2.hip).  The shortcut reads pixel (2y, 2x) of the unpadded input, which is the centre
+//              tap (1, 1) of the window: GEMM columns [4C, 5C) with A_TAPS's addressing.  B is [10 C][Kout], the
+//              taps' rows then the shortcut's C rows; the BN vectors are bn1Bias, bn1Scale, bndBias, bndScale, each
+//              Kout long, at bnBias, bnScale = bnBias + Kout, bnBias + 2 Kout, bnBias + 3 Kout; R carries the
+//              shortcut's output, padded like Cout.  Workgroups past the 3x3's own grid are the shortcut's whole
+//              tiles over k-steps [4C / BK, 5C / BK): B is advanced by 5 C rows (GEMM row 4C + j is packed row
+//              9C + j), the second BN, no ReLU, the stores go to R (the latency kernel appends row blocks instead:
+//              conv1x1_small_kernel.h).  The 3x3's workgroups run exactly as A_TAPS.
+enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3, A_TAPS_PROJ = 4 };
 struct ProjGeo {
   const float* X;         // A_TWO: the block input x
   unsigned img, row, s;   // x's pixels per image (Hin*Win), pixels per strided row step (s*Win), the stride
@@ -171,6 +180,9 @@ __device__ unsigned long long wino_clk_slot_1x1[4];
 // AF = the A operand form.  The projection block's forms (proj_block.hip) run with BK = 32, no residual and no batch:
 // A_STRIDED: A = x, Cin = x's channels; A_TWO: A = t2 (padded, flags WINO_A_PADDED), Cin = cm + cx, B = the stacked
 // tail matrix.  The stride-2 3x3 layer (conv3x3_s2.hip) runs A_TAPS the same way: A = the padded input, Cin = 9 C.
+// A_TAPS_PROJ (basic_block_s2.hip) is A_TAPS with the shortcut's whole tiles appended to the grid: batchA, unused by
+// the tap forms, is the 3x3's own grid -- the stream-K ranges and the ring pass are cut over that, never over the
+// appended tiles.
 // xg is last, so that the plain form's other arguments keep their offsets.
 template <int BK, int NW, int ABLATE = 0, bool SK = false, bool RES = false, int AF = A_PLAIN>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3)
@@ -179,6 +191,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
                   const float* __restrict__ R, float* __restrict__ Cout, long M, int Cin, int Kout,
                   int flags, int nMB, long batchA, long batchB, long batchC, SkArgs sk, PadGeo pg, ProjGeo xg) {
   static_assert(AF == A_PLAIN || !RES, "the residual epilogue is the plain form's");
+  constexpr bool TAPS = AF == A_TAPS || AF == A_TAPS_PROJ;
   using G = Cfg<BK, NW>;
   // batched GEMMs (the 36 Winograd points of the F(4x4) compatibility path): blockIdx.y selects
   // the problem, the three operands advance by their batch strides (in floats)
@@ -188,6 +201,19 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     Cout += (size_t)blockIdx.y * batchC;
   }
   constexpr int BN = G::BN;
+  // A_TAPS_PROJ: the 3x3's own grid (Gmain) and whether this workgroup is one of the shortcut's tiles behind it.
+  // (gridDim.x is read where the other forms read it, so that their code stays as it was.)
+  const unsigned Gmain = AF == A_TAPS_PROJ ? (unsigned)batchA : 0u;
+  const bool proj_sc = AF == A_TAPS_PROJ && blockIdx.x >= Gmain;
+  if constexpr (AF == A_TAPS_PROJ) {
+    if (proj_sc) {
+      B += (size_t)5 * xg.cx * Kout;
+      bnBias += 2 * Kout;
+      bnScale += 2 * Kout;
+      Cout = const_cast<float*>(R);
+      flags &= ~WINO_RELU;
+    }
+  }
   const bool relu = flags & WINO_RELU, a_padded = flags & WINO_A_PADDED;
   const bool c_padded = flags & WINO_C_PADDED;
   constexpr bool add_res = RES;   // (the host picks the instantiation from flags & WINO_ADD_RESIDUAL)
@@ -201,7 +227,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   const bool stream_out = !c_padded && Cin >= 4 * BK;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int NBLK = Kout / BN;
-  const int bid = blockIdx.x;
+  const int bid = proj_sc ? (int)(blockIdx.x - Gmain) : blockIdx.x;   // (A_TAPS_PROJ's shortcut: counted from Gmain)
   const int nk = Cin / BK;
   // A new workgroup's waves are the youngest on their SIMDs, and the arbiter serves the oldest first: beside two
   // resident workgroups in their MFMA loops, the address set-up below took 2.5 us (median; 6.7 us at the 90th
@@ -222,14 +248,15 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
       sk.dbg[(size_t)blockIdx.x * 8 + 4] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11));
     }
   }
-  if (c_padded && !(ABLATE & 512)) {
+  if (c_padded && !proj_sc && !(ABLATE & 512)) {   // (A_TAPS_PROJ: t1's ring; the shortcut's is never read)
     // ring pass: the padded output's zero ring (the 3x3 layer's padding) as a flat list of
     // 16-byte units -- images x ring pixels x Kout/4 units -- split over the grid
     const unsigned upp = (unsigned)Kout >> 2;
     const unsigned rpx = 2 * pg.Wp + 2 * (pg.Hp - 2);   // ring pixels per image
     const unsigned imgs = fastdiv((unsigned)M, pg.d_hw);
     const unsigned long long U = (unsigned long long)imgs * rpx * upp;
-    const unsigned u_begin = (unsigned)(U * bid / gridDim.x), u_end = (unsigned)(U * (bid + 1ull) / gridDim.x);
+    const unsigned u_begin = (unsigned)(U * bid / (AF == A_TAPS_PROJ ? Gmain : gridDim.x)),
+                   u_end = (unsigned)(U * (bid + 1ull) / (AF == A_TAPS_PROJ ? Gmain : gridDim.x));
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     for (unsigned u = u_begin + threadIdx.x; u < u_end; u += 64 * NW) {
       const unsigned pid = u / upp, unit = u - pid * upp;
@@ -249,13 +276,15 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   //               neighbours on one XCD and read the same A k-slices at the same time (cutting
   //               tile * nk + k instead let them drift 4 steps apart: L2 hit rate 0.71 -> 0.49,
   //               HBM fetch 115 -> 214 MB on the 1024->256 layer).  G is a multiple of 8 and of NBLK.
-  const int Gsk = (int)gridDim.x;
+  //   A_TAPS_PROJ's shortcut tiles: the plain form's mapping over the workgroups past Gmain, k-steps
+  //               [4C / BK, 5C / BK) of the tile (the centre tap), never cut in either form.
+  const int Gsk = AF == A_TAPS_PROJ ? (int)Gmain : (int)gridDim.x;
   const int Gr = SK ? Gsk / NBLK : 1;
   const long long Usk = (long long)nMB * nk;
   auto sk_u0 = [&](int r) -> long long { return Usk * r / Gr; };
   int lg = 0, rg = 0, nb_sk = 0;
   long long u, uend;
-  if (SK) {
+  if (SK && !proj_sc) {
     lg = (bid & 7) * (Gsk >> 3) + (bid >> 3);
     rg = lg / NBLK;
     nb_sk = lg - rg * NBLK;
@@ -268,6 +297,13 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     nb_sk = slot % NBLK;
     u = (long long)mb_plain * nk;
     uend = u + nk;
+    if constexpr (AF == A_TAPS_PROJ) {
+      if (proj_sc) {
+        const int kc = xg.cx / BK;   // k-steps per tap
+        u += 4 * kc;
+        uend = u + kc;
+      }
+    }
   }
   const int r16 = lane & 15, h = lane >> 4;
   bool first_seg = true;
@@ -317,15 +353,15 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   //   A_STRIDED / A_TWO past kb: rows map into the strided x, a window about s^2 times as long (host-checked < 4 GiB).
   //   A_TAPS: rows map into the padded input the same way, and the window grows by the taps' reach, 2 (Win+2) + 2
   //      pixels past the last row (host-checked < 4 GiB); the k offset of a k-step is tap_offset(k BK) * 4 bytes.
-  const bool a_str = AF == A_STRIDED || AF == A_TAPS || (AF == A_TWO && k0 >= kb);
+  const bool a_str = AF == A_STRIDED || TAPS || (AF == A_TWO && k0 >= kb);
   const float* const Aseg = AF == A_TWO && a_str ? xg.X : A;
-  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : AF == A_TAPS ? xg.cx : Cin;   // A row length of this segment
+  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : TAPS ? xg.cx : Cin;   // A row length of this segment
   const int ka = AF == A_TWO && a_str ? k0 - kb : k0;        // its first k-step inside that source
   const long a_row0 = a_str ? strided_row(m0 < M ? m0 : M - 1, pg, xg)
                             : a_padded ? padded_row(m0 < M ? m0 : M - 1, pg) : (m0 < M ? m0 : M - 1);
   const long m_last = m0 + BM - 1 < M ? m0 + BM - 1 : M - 1;
   long a_rows = (a_str ? strided_row(m_last, pg, xg) : a_padded ? padded_row(m_last, pg) : m_last) - a_row0 + 1;
-  if constexpr (AF == A_TAPS) a_rows += 2 * (long)xg.cm + 2;
+  if constexpr (TAPS) a_rows += 2 * (long)xg.cm + 2;
   const auto rsrc_a = make_rsrc(Aseg + a_row0 * ca, (unsigned)(a_rows * ca * (long)sizeof(float)));
   const auto rsrc_b = make_rsrc(B, (unsigned)((size_t)Cin * Kout * sizeof(float)));
   unsigned a_voff[G::A_PER_WAVE];
@@ -358,8 +394,8 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   // (Win+2-3) C 4 -- is made wave-uniform per segment: read through xg, the compiler takes it for per-lane data,
   // computes the offset on the VALU and wraps every A piece in a readfirstlane loop inside the MFMA loop.  (Per
   // segment rather than per launch: not live across the stream-K hand-off, where the SGPRs are short.)
-  const int taps_k3 = AF == A_TAPS ? __builtin_amdgcn_readfirstlane(3 * (xg.cx / BK)) : 0;
-  const unsigned taps_row = AF == A_TAPS ? (unsigned)__builtin_amdgcn_readfirstlane((xg.cm - 3) * xg.cx * (int)sizeof(float)) : 0u;
+  const int taps_k3 = TAPS ? __builtin_amdgcn_readfirstlane(3 * (xg.cx / BK)) : 0;
+  const unsigned taps_row = TAPS ? (unsigned)__builtin_amdgcn_readfirstlane((xg.cm - 3) * xg.cx * (int)sizeof(float)) : 0u;
   auto taps_soff = [&](int k) {
     return (unsigned)k * a_kstep + (k >= taps_k3 ? taps_row : 0u) + (k >= 2 * taps_k3 ? taps_row : 0u);
   };
@@ -397,7 +433,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
 
 #pragma unroll
   for (int p = 0; p < PIECES; p++)
-    issue_piece(0, AF == A_TAPS ? taps_soff(k0) : (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
+    issue_piece(0, TAPS ? taps_soff(k0) : (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
   __builtin_amdgcn_s_setprio(0);
 
   // `more` (is there a k-step after this one to fetch) is a compile-time property of the body: the
@@ -411,7 +447,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     }
     unsigned a_soff;   // `it` counts from the segment's first k-step k0 (A_TWO: from ka inside its source)
     if constexpr (AF == A_TWO) a_soff = (unsigned)(ka + it + 1) * a_kstep;
-    else if constexpr (AF == A_TAPS) a_soff = taps_soff(k0 + it + 1);
+    else if constexpr (TAPS) a_soff = taps_soff(k0 + it + 1);
     else a_soff = (unsigned)(k0 + it + 1) * a_kstep;
     const unsigned b_soff = (unsigned)(k0 + it + 1) * b_kstep;
     const char* st = smem + PAR * G::STAGE;
@@ -503,7 +539,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   const int r16_e = lane_e & 15, h_e = lane_e >> 4;
   if (!direct_epi || SK)
   __syncthreads();   // every wave is done with the pipeline stages; no LDS-DMA is in flight
-  if (SK && !(AF == A_TWO ? kt0 == 0 && k0 + len == nk : k0 == 0 && len == nk)) {
+  if (SK && !proj_sc && !(AF == A_TWO ? kt0 == 0 && k0 + len == nk : k0 == 0 && len == nk)) {
     // Partial segment.  The tile is finished by whoever learns that all of its other segments
     // have been published: a range's last segment first looks at the tile's counter -- its
     // neighbours started their share of the tile long ago, so it usually finds them all there and

@@ -1,6 +1,7 @@
 // The 1x1 kernels' launch plan and launcher, shared by the translation units that launch them: conv1x1.hip (the plain
-// operand form, A_PLAIN), proj_block.hip (the projection block's A_STRIDED / A_TWO forms) and conv3x3_s2.hip (the
-// stride-2 3x3's A_TAPS form); the forms: conv1x1_kernel.h.
+// operand form, A_PLAIN), proj_block.hip (the projection block's A_STRIDED / A_TWO forms), conv3x3_s2.hip (the
+// stride-2 3x3's A_TAPS form) and basic_block_s2.hip (A_TAPS_PROJ, the stride-2 3x3 with its 1x1 shortcut); the forms:
+// conv1x1_kernel.h.
 // A template is instantiated where it is used, so each file compiles the kernels of its own forms and no others.
 #pragma once
 #include "conv1x1_kernel.h"
@@ -28,7 +29,7 @@ Plan1x1 plan_1x1(long M, int Cin, int Kout, int batch, int cus, const Knobs& kn)
 // the tiled kernel's stream-K scratch of stream `s` for this plan (sk_scratch)
 int tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs);
 
-// One launch's operands.  R: the residual (A_PLAIN, WINO_ADD_RESIDUAL); xg: the strided / second source (A_STRIDED,
+// One launch's operands.  R: the residual (A_PLAIN, WINO_ADD_RESIDUAL) or the shortcut's output (A_TAPS_PROJ); xg: the strided / second source (A_STRIDED,
 // A_TWO) or the padded input's tap geometry (A_TAPS); batch and the per-batch strides: the batched plain GEMM (gemm_batched; its plans have no stream-K form).
 struct Operands1x1 {
   const float *A, *B, *bnBias, *bnScale, *R;
@@ -75,12 +76,19 @@ int launch_tiled_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_
   if (int rc = lds_cap_once<gemm1x1::conv1x1_bn_kernel<32, NW, 0, false, RES, AF>,
                             gemm1x1::conv1x1_bn_kernel<32, NW, 0, true, RES, AF>>(dev, LDS_BYTES))
     return rc;
+  // A_TAPS_PROJ: the shortcut's whole tiles (a plain tiled grid) go behind the planned grid, whose size batchA carries
+  unsigned extra = 0;
+  Operands1x1 op = o;
+  if constexpr (AF == gemm1x1::A_TAPS_PROJ) {
+    extra = (unsigned)(8ll * p.nblk * ((p.nMB + 7) / 8));
+    op.batchA = p.sk ? p.sk : p.grid;
+  }
   if (!p.sk)
-    return launch_tiled_1x1_kernel<NW, false, AF, RES>(dim3(p.grid, o.batch), (int)p.nMB, o,
+    return launch_tiled_1x1_kernel<NW, false, AF, RES>(dim3(p.grid + extra, o.batch), (int)p.nMB, op,
                                                        gemm1x1::SkArgs{nullptr, nullptr, nullptr, nullptr}, s);
   SkBufs bufs;
   if (int rc = tiled_scratch(dev, s, p, &bufs)) return rc;
-  const int rc = launch_tiled_1x1_kernel<NW, true, AF, RES>(dim3(p.sk), (int)p.nMB, o,
+  const int rc = launch_tiled_1x1_kernel<NW, true, AF, RES>(dim3(p.sk + extra), (int)p.nMB, op,
                                                             gemm1x1::SkArgs{bufs.slabs, bufs.tickets, nullptr, bufs.err}, s);
   if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
   return rc;
@@ -93,8 +101,10 @@ int launch_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
   if (p.small.use) {
     const Small1Plan& pl = p.small;
     const auto kernel = SMALL_1X1_KERNELS<AF>[pl.ks >> 1][pl.rt - 1][pl.ct >> 1];
-    // x = column group, y = row block: see the kernel
-    const dim3 grid((unsigned)(o.Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)((o.M + 16 * pl.rt - 1) / (16 * pl.rt)));
+    // x = column group, y = row block: see the kernel.  A_TAPS_PROJ: the shortcut's row blocks behind the 3x3's
+    const long long rows = (o.M + 16 * pl.rt - 1) / (16 * pl.rt) * (AF == gemm1x1::A_TAPS_PROJ ? 2 : 1);
+    if (rows > 65535) { set_error("latency form: %lld row blocks (gridDim.y)", rows); return WINO_E_SHAPE; }
+    const dim3 grid((unsigned)(o.Kout / ((4 / pl.ks) * pl.ct * 16)), (unsigned)rows);
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, o.A, o.B, o.bnBias, o.bnScale, o.R, o.C, o.M, o.Cin, o.Kout,
                        o.flags, o.pg, o.xg);
     return launch_status("conv1x1_small_kernel");

@@ -37,8 +37,14 @@ namespace gemm1x1 {
 // A_STRIDED: A = x, Cin = x's channels.  A_TWO: A = t2 (padded, flags WINO_A_PADDED), Cin = cm + cx, B = the stacked
 // tail matrix; each wave contracts its share of both sources (cm / KS channels of t2, then cx / KS of x), so the K
 // split stays in k order.  A_TAPS (conv3x3_s2.hip): A = the padded input, Cin = 9 C; a 16-channel chunk never crosses
-// a tap, so its address is the row pointer plus tap_offset of the chunk's first k.  xg is last, so that the plain
-// form's other arguments keep their offsets.
+// a tap, so its address is the row pointer plus tap_offset of the chunk's first k.  A_TAPS_PROJ (basic_block_s2.hip):
+// A_TAPS with the shortcut's column groups appended behind the grid -- the second half of the grid's y (the same row
+// blocks again) contracts C / KS channels per wave from GEMM column 4C (the centre tap) against B advanced by 5 C
+// rows, with the second BN, no ReLU, into R (conv1x1_kernel.h).  Behind, not beside along x: workgroups are dispatched
+// in linear order, so every 3x3 workgroup is placed before any shortcut one and none has to share its CU with
+// another 3x3 workgroup because shortcut ones took CUs first (interleaved along x, conv4 at 8 images took 2.5x the
+// plain layer's time).  C / KS is a multiple of 16 whenever 9 C / KS is (gcd(9, 16) = 1).  xg is last, so that
+// the plain form's other arguments keep their offsets.
 template <int KS, int RT = 1, int CT = 1, int AF = A_PLAIN>
 __global__ void __launch_bounds__(256)
 conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
@@ -51,6 +57,7 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
   constexpr int CB = 4 / KS;               // blocks per workgroup, side by side
   constexpr int GS = RT * CT == 1 ? 8 : RT * CT >= 8 ? 2 : 4;   // super-chunks per register buffer; two buffers in flight
   constexpr int NT = RT * CT;
+  constexpr bool TAPS = AF == A_TAPS || AF == A_TAPS_PROJ;
   __shared__ f32x4 red[4][NT][64];
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -61,17 +68,30 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
     wino_clk_slot_1x1[0] = __builtin_amdgcn_s_memtime();
     wino_clk_slot_1x1[1] = __builtin_amdgcn_s_memrealtime();
   }
+  // A_TAPS_PROJ: the 3x3's own row blocks (gy) and whether this workgroup is one of the shortcut's behind them.
+  // (gridDim.y is read where the other forms read it, so that their code stays as it was.)
+  const unsigned gy = AF == A_TAPS_PROJ ? gridDim.y >> 1 : 0u;
+  const bool proj_sc = AF == A_TAPS_PROJ && blockIdx.y >= gy;
+  if constexpr (AF == A_TAPS_PROJ) {
+    if (proj_sc) {
+      B += (size_t)5 * xg.cx * Kout;
+      bnBias += 2 * Kout;
+      bnScale += 2 * Kout;
+      Cout = const_cast<float*>(Res);
+      flags &= ~WINO_RELU;
+    }
+  }
   const int r16 = lane & 15, h = lane >> 4;
   const bool relu = flags & WINO_RELU, a_padded = flags & WINO_A_PADDED, c_padded = flags & WINO_C_PADDED;
   const bool add_res = flags & WINO_ADD_RESIDUAL;
-  if (c_padded) {
+  if (c_padded && !proj_sc) {
     // ring pass: the padded output's zero ring (the 3x3 layer's padding) as a flat list of 16-byte units --
     // images x ring pixels x Kout/4 units -- split over the grid (as in the tiled kernel)
     const unsigned upp = (unsigned)Kout >> 2;
     const unsigned rpx = 2 * pg.Wp + 2 * (pg.Hp - 2);   // ring pixels per image
     const unsigned imgs = fastdiv((unsigned)M, pg.d_hw);
     const unsigned long long U = (unsigned long long)imgs * rpx * upp;
-    const unsigned long long nblk = (unsigned long long)gridDim.x * gridDim.y, bid = (unsigned long long)blockIdx.y * gridDim.x + blockIdx.x;
+    const unsigned long long nblk = (unsigned long long)gridDim.x * (AF == A_TAPS_PROJ ? gy : gridDim.y), bid = (unsigned long long)blockIdx.y * gridDim.x + blockIdx.x;
     const unsigned u_begin = (unsigned)(U * bid / nblk), u_end = (unsigned)(U * (bid + 1ull) / nblk);
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     for (unsigned u = u_begin + threadIdx.x; u < u_end; u += 256) {
@@ -85,10 +105,12 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
   // blockIdx.x = column group: workgroups are dealt to the XCDs round-robin in x-fastest order, so the row blocks
   // that read one column slice of B share an XCD and its L2 (the column groups are a multiple of 8 for every
   // Kout % 128 == 0): B is then fetched once per launch instead of once per XCD
-  const long m0 = (long)blockIdx.y * (16 * RT);
+  const long m0 = (long)(proj_sc ? blockIdx.y - gy : blockIdx.y) * (16 * RT);
   const int n0 = ((int)blockIdx.x * CB + cb) * (16 * CT);
-  // channels this wave contracts (a multiple of 16: checked on the host); A_TWO: of the first source, t2
-  const int kspan = (AF == A_TWO ? xg.cm : Cin) / KS;
+  // channels this wave contracts (a multiple of 16: checked on the host); A_TWO: of the first source, t2;
+  // A_TAPS_PROJ's shortcut: C channels from k_sc = 4C
+  const int kspan = (AF == A_TWO ? xg.cm : proj_sc ? xg.cx : Cin) / KS;
+  const int k_sc = proj_sc ? 4 * xg.cx : 0;
   int nsc = kspan >> 4;
   // folded BN of this lane's out-channels: requested now, used at the very end
   // (WIDE: sc[r] = the scales of columns n0 + 16 h + 4 r .. + 3, the four tiles' components r)
@@ -106,20 +128,20 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
   for (int r = 0; r < RT; r++) {
     long m = m0 + 16 * r + r16;
     m = m < M ? m : M - 1;                 // rows past the end read a valid row (never stored)
-    if (AF == A_STRIDED || AF == A_TAPS) m = strided_row(m, pg, xg);
+    if (AF == A_STRIDED || TAPS) m = strided_row(m, pg, xg);
     else if (a_padded) m = padded_row(m, pg);
-    if constexpr (AF == A_TAPS) ap[r] = A + m * xg.cx + 4 * h;   // the wave's k range starts inside tap_offset below
+    if constexpr (TAPS) ap[r] = A + m * xg.cx + 4 * h;   // the wave's k range starts inside tap_offset below
     else ap[r] = A + m * (AF == A_TWO ? xg.cm : Cin) + kq * kspan + 4 * h;
   }
-  const float* bp = B + (size_t)(kq * kspan + 4 * h) * Kout + n0 + (WIDE ? 4 * r16 : r16);
+  const float* bp = B + (size_t)(k_sc + kq * kspan + 4 * h) * Kout + n0 + (WIDE ? 4 * r16 : r16);
 
   auto load_group = [&](int g, f32x4 (*a)[RT], float (*b)[CT][4]) {
 #pragma unroll
     for (int i = 0; i < GS; i++) {
       int s = g * GS + i;
       s = s < nsc ? s : nsc - 1;           // past the end: re-read the last one (never multiplied)
-      if constexpr (AF == A_TAPS) {
-        const unsigned off = tap_offset((unsigned)(kq * kspan + s * 16), xg);
+      if constexpr (TAPS) {
+        const unsigned off = tap_offset((unsigned)(k_sc + kq * kspan + s * 16), xg);
 #pragma unroll
         for (int r = 0; r < RT; r++) a[i][r] = *(const f32x4*)(ap[r] + off);
       } else {

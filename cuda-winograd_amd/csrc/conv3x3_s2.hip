@@ -7,18 +7,16 @@
 // operand form A_TAPS (conv1x1_kernel.h): the same LDS-DMA pipeline and MFMA loop with one scalar A offset per k-step,
 // the same latency / tiled / stream-K forms, the same planner (plan_1x1 on the GEMM's shape, its latency-or-tiled
 // choice re-priced for the tap form: plan_s2) and launcher (launch_1x1, conv1x1_launch.h).  This file instantiates that form and no other.
-#include "conv1x1_launch.h"
+// check_s2 and plan_s2 are shared with basic_block_s2.hip (conv3x3_s2.h).
+#include "conv3x3_s2.h"
 
 namespace wino {
-namespace {
 
 using namespace gemm1x1;
 
-struct S2Geom {
-  int N, Hin, Win, C, K, H, W;
-  long M;
-};
+namespace {
 constexpr unsigned long long FOUR_GIB = 1ull << 32;
+}  // namespace
 // The layer's geometry, checked once.  Every 32-bit quantity of the tap addressing is bounded here: the pixel row
 // index (M < 2^31, one padded input image < 2^31 pixels), a 112-row tile's buffer-descriptor window over the padded
 // input, B's descriptor and the ring pass's 16-byte units.
@@ -67,7 +65,6 @@ Plan1x1 plan_s2(const S2Geom& g, int cus, const Knobs& kn) {
   return p;
 }
 
-}  // namespace
 }  // namespace wino
 
 using namespace wino;

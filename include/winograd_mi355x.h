@@ -54,7 +54,9 @@ extern "C" {
  * wino_proj_block_prepare_hw, wino_proj_block_hw, wino_proj_tail_plan, WINO_1X1_FORM_*,
  * wino_conv3x3_s2_bn_relu_hw, wino_conv3x3_s2_prepare_hw, wino_conv3x3_s2_plan, wino_proj_block_v15_hw,
  * wino_proj_block_v15_workspace_bytes_hw, wino_proj_block_v15_prepare_hw, wino_conv3x3_bn_add_relu_hw,
- * wino_basic_block_workspace_bytes_hw, wino_basic_block_hw, wino_basic_block_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_basic_block_workspace_bytes_hw, wino_basic_block_hw, wino_basic_block_prepare_hw, wino_s2_proj_elems,
+ * wino_s2_proj_pack, wino_conv3x3_s2_proj_bn_relu_hw, wino_basic_block_s2_workspace_bytes_hw, wino_basic_block_s2_hw,
+ * wino_basic_block_s2_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived). */
 #define WINO_ABI_VERSION 1
 
@@ -445,6 +447,38 @@ int wino_basic_block_hw(const float* x, const float* U1, const float* bn1Bias, c
                         const float* U2, const float* bn2Bias, const float* bn2Scale, float* out,
                         int N, int H, int W, int C, void* workspace, size_t workspace_bytes, wino_stream_t s);
 int wino_basic_block_prepare_hw(int N, int H, int W, int C, wino_stream_t s);
+
+/* Downsampling basic block (the first block of ResNet-18 / -34's conv3, conv4, conv5; torchvision's BasicBlock with
+ * `downsample`), H = (Hin-1)/2 + 1, W = (Win-1)/2 + 1:
+ *   t1  = relu(bn1(conv3x3_s2(x, w_taps)))      C -> K, stride 2, pad 1
+ *   sc  = bnd(conv1x1_s2(x, wd))                C -> K, stride 2, no padding, no ReLU
+ *   out = relu(bn2(conv3x3(t1, U2)) + sc)       K -> K
+ * The shortcut reads the pixel the stride-2 3x3's centre tap reads, so it runs inside the stride-2 3x3's launch as
+ * extra workgroups over that tap's k-range.  `packed` holds w_taps [3][3][C][K] (wino_conv3x3_s2_bn_relu_hw's
+ * format), wd [C][K] and the four BN vectors (bias, scale: not folded into the filters), as wino_s2_proj_pack writes
+ * it (wino_s2_proj_elems floats; the layout is private to the library).
+ * wino_conv3x3_s2_proj_bn_relu_hw is the fused layer on its own, one launch: in [N][Hin+2][Win+2][C] with a zero
+ * ring; t1 [N][H+2][W+2][K] exactly as wino_conv3x3_s2_bn_relu_hw(relu = 1) writes it (bitwise; ring written 0);
+ * sc [N][H+2][W+2][K], the interior written, the ring not touched.  It takes the stride-2 layer's plan unchanged
+ * (wino_conv3x3_s2_plan describes it, wino_conv3x3_s2_prepare_hw prepares it).
+ * wino_basic_block_s2_hw is the block, two launches: the fused layer writes t1 into `workspace`
+ * (wino_basic_block_s2_workspace_bytes_hw(N, Hin, Win, K) bytes) and sc into out's interior, then
+ * wino_conv3x3_bn_add_relu_hw(t1, U2, bn2, residual = out, out = out) runs in place.  x [N][Hin+2][Win+2][C] with a
+ * zero ring (what wino_basic_block_hw takes and writes); out [N][H+2][W+2][K] with its ring written 0: the next
+ * identity block's x as it stands.  U2 from wino_filter_transform_f2 (K -> K).  Constraints: C % 32 == 0,
+ * K % 64 == 0, those of the stride-2 layer and of the K -> K 3x3 on the H x W grid; x, out, workspace and packed must
+ * not overlap (WINO_E_ARG).  wino_basic_block_s2_prepare_hw reserves the stream's scratch of both launches (before a
+ * graph capture). */
+size_t wino_s2_proj_elems(int C, int K);
+int wino_s2_proj_pack(const float* w_taps, const float* bn1Bias, const float* bn1Scale, const float* wd,
+                      const float* bndBias, const float* bndScale, float* packed, int C, int K, wino_stream_t s);
+int wino_conv3x3_s2_proj_bn_relu_hw(const float* in, const float* packed, float* t1, float* sc, int N, int Hin,
+                                    int Win, int C, int K, wino_stream_t s);
+size_t wino_basic_block_s2_workspace_bytes_hw(int N, int Hin, int Win, int K);
+int wino_basic_block_s2_hw(const float* x, const float* packed, const float* U2, const float* bn2Bias,
+                           const float* bn2Scale, float* out, int N, int Hin, int Win, int C, int K,
+                           void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_basic_block_s2_prepare_hw(int N, int Hin, int Win, int C, int K, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
