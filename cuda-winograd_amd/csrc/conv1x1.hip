@@ -305,6 +305,15 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
   return launch_1x1<A_PLAIN>(p, dev, {A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg}, (hipStream_t)s);
 }
 
+// The bottleneck block's checks before its first launch: batch and feature map, and the 3x3's shape limits (its filter
+// matrix among them), so that a shape the middle layer refuses launches nothing (host-side only)
+static int check_residual_block(int N, int H, int W, int Cm) {
+  if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
+  int grid = 0, rounds = 0, ipi = 0;
+  long tail = 0;
+  return wino_conv3x3_plan(1, H, W, Cm, Cm, 1, &grid, &rounds, &tail, &ipi);
+}
+
 extern "C" {
 
 int wino_conv1x1_bn_ex(const float* A, const float* B, const float* bnBias, const float* bnScale,
@@ -390,7 +399,7 @@ int wino_residual_block_hw(const float* x, const float* w1, const float* bn1Bias
                            const float* w3, const float* bn3Bias, const float* bn3Scale, float* out,
                            int N, int H, int W, int C4, int Cm, void* workspace, size_t workspace_bytes,
                            wino_stream_t s) {
-  if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
+  if (int rc = check_residual_block(N, H, W, Cm)) return rc;
   if (!workspace || workspace_bytes < wino_residual_block_workspace_bytes_hw(N, H, W, Cm)) {
     set_error("workspace too small: need %zu bytes", wino_residual_block_workspace_bytes_hw(N, H, W, Cm));
     return WINO_E_ARG;
@@ -406,7 +415,7 @@ int wino_residual_block_hw(const float* x, const float* w1, const float* bn1Bias
 }
 
 int wino_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, wino_stream_t s) {
-  if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
+  if (int rc = check_residual_block(N, H, W, Cm)) return rc;
   const long M = (long)N * H * W;
   if (int rc = wino_conv1x1_prepare(M, C4, Cm, s)) return rc;
   if (int rc = wino_conv3x3_prepare_hw(N, H, W, Cm, Cm, s)) return rc;

@@ -79,6 +79,13 @@ static int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stri
   *g = ProjGeom{N, Hin, Win, Cin, Cm, C4, stride, H, W, (long)M};
   return WINO_OK;
 }
+// the v1 block's middle layer is the Winograd 3x3 (Cm -> Cm at H x W): its shape limits, the filter matrix's among
+// them, before anything is launched (host-side only)
+static int check_proj_3x3(const ProjGeom& g) {
+  int grid = 0, rounds = 0, ipi = 0;
+  long tail = 0;
+  return wino_conv3x3_plan(1, g.H, g.W, g.Cm, g.Cm, 1, &grid, &rounds, &tail, &ipi);
+}
 static ProjGeo proj_geo(const ProjGeom& g, const float* x) {
   return ProjGeo{x, (unsigned)g.Hin * (unsigned)g.Win, (unsigned)(g.s * g.Win), (unsigned)g.s, g.Cin, g.Cm};
 }
@@ -137,6 +144,7 @@ int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int st
 int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, wino_stream_t s) {
   ProjGeom g;
   if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
+  if (int rc = check_proj_3x3(g)) return rc;
   int dev = 0, cus = 0;
   if (int rc = current_device(&dev, &cus)) return rc;
   const Knobs kn = knobs();
@@ -178,6 +186,7 @@ int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, co
   }
   ProjGeom g;
   if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
+  if (int rc = check_proj_3x3(g)) return rc;
   const size_t need = wino_proj_block_workspace_bytes_hw(N, g.H, g.W, Cm);
   if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
   int dev = 0, cus = 0;

@@ -47,6 +47,14 @@ inline int check_conv3x3_dims(int H, int W, int C, int K) {
     set_error("unsupported feature map %dx%d", H, W);
     return WINO_E_SHAPE;
   }
+  // U [16][C][K] goes through one buffer descriptor in the throughput kernel (32-bit size and offsets); the latency
+  // kernel could address more, but both take the same shapes (one plan per shape)
+  const unsigned long long u_bytes = (unsigned long long)16 * C * K * sizeof(float);
+  if (u_bytes >= (1ull << 32)) {
+    set_error("C=%d K=%d: the filter matrix U (16 x C x K floats, %llu bytes) must stay below 4 GiB (C * K < 2^26)", C,
+              K, u_bytes);
+    return WINO_E_SHAPE;
+  }
   if (conv3x3_batch_limit(H, W, C, K) < 1) {
     set_error("%dx%d C=%d K=%d: one image does not fit a launch (tensors must stay below 4 GiB)", H, W, C, K);
     return WINO_E_SHAPE;

@@ -137,7 +137,10 @@ int wino_filter_import_f4(const float* u36, float* U, int C, int K, wino_stream_
  *                       (= the next 3x3 layer's padded input, Kernel128_winograd.cu:163)
  * out = relu(bnScale[k] * conv + bnBias[k]);  argument order (in, bias, scale, out)
  * follows kernel_*_winograd_AtIA (Kernel128_winograd.cu:123).
- * Constraints: C % 8 == 0, K % 64 == 0, N >= 1.  One launch.  The throughput kernel splits the
+ * Constraints: C % 8 == 0, K % 64 == 0, N >= 1, and C * K < 2^26: the filter matrix U (16 C K floats, read through
+ * one 32-bit buffer descriptor) stays below 4 GiB -- C = K = 8192 is refused (WINO_E_SHAPE), C = 8192 with K = 8128
+ * runs.  Every entry point built on this layer (the residual 3x3, the basic blocks, the bottleneck and v1 projection
+ * blocks) refuses such a shape before its first launch.  One launch.  The throughput kernel splits the
  * work evenly over the CUs (stream-K) and hands partial sums between workgroups through a small
  * scratch buffer the LIBRARY owns, one per (device, stream), allocated at the first call that needs
  * it (a synchronous hipMalloc).  Launches on one stream serialise, so they share it safely; two

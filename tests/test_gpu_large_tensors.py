@@ -1,0 +1,538 @@
+"""Every layer and block past 2 GiB and 4 GiB tensors (run with `-m gpu` on an MI355X).
+
+The kernels address their tensors through buffer descriptors: 32-bit sizes and 32-bit byte offsets.  The library
+re-bases them (the 1x1 kernels at every tile's first row, the 3x3 launcher by cutting a batch into launches whose
+tensors stay below 4 GiB), so each entry point takes tensors of any size.  Here every operand form and block runs at a
+batch whose tensors cross 2^31 and 2^32 bytes, into NaN-filled outputs and workspaces:
+
+* on the GPU, the whole output is finite and its padded ring exactly zero;
+* the images around each boundary (n = 2^31 // P and 2^32 // P, with n - 1 and n + 1, for every tensor of P bytes per
+  image that crosses it), both sides of every batch cut, the first and the last image match an fp64 reference on the
+  CPU (the suite's own: the oracle module and the reference methods of the other GPU test files) at TIGHT;
+* a second launch gives the same bits on those images, and no stream-K ticket is left held.
+
+Inputs are built on the device from a seeded generator; a case skips when the card has less free memory than it needs
+(at most about 20 GiB)."""
+import types
+
+import numpy as np
+import pytest
+
+from test_gpu_basic_block import _Block as _BasicBlock
+from test_gpu_basic_block import _Layer as _ResLayer
+from test_gpu_basic_block_s2 import _Block as _S2Block
+from test_gpu_conv3x3_s2 import _Layer as _S2Layer
+from test_gpu_proj_block import _oracle as _proj_oracle
+from test_gpu_proj_block import _weights as _proj_weights
+from test_gpu_proj_block_v15 import _Block as _V15Block
+
+pytestmark = pytest.mark.gpu
+
+TIGHT = 2e-5
+GIB = 1 << 30
+NAN = float("nan")
+
+FORMS_1X1 = {
+    "default": {},
+    "tiled": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 0},
+    "stream_k": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1},
+}
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch, torch.device("cuda:0")
+
+
+@pytest.fixture
+def free_after(torch_dev):
+    torch, _ = torch_dev
+    yield
+    torch.cuda.synchronize()
+    torch.cuda.empty_cache()
+
+
+def _need(torch, nbytes):
+    free, _ = torch.cuda.mem_get_info()
+    if free < nbytes + GIB:
+        pytest.skip(f"needs {(nbytes + GIB) / GIB:.1f} GiB of free device memory, {free / GIB:.1f} free")
+
+
+def _set(knobs, form):
+    for k, v in form.items():
+        knobs.set(k, v)
+
+
+def _images(N, per_image_bytes, cuts=()):
+    """The images to check: both sides of 2^31 and 2^32 bytes for every tensor of P bytes per image that crosses them,
+    both sides of every batch cut, the first and the last."""
+    s = {0, N - 1}
+    for P in per_image_bytes:
+        for b in (1 << 31, 1 << 32):
+            if N * P > b:
+                n = b // P
+                s |= {n - 1, n, n + 1}
+    for c in cuts:
+        s |= {c - 1, c}
+    return sorted(i for i in s if 0 <= i < N)
+
+
+def _rand(torch, dev, shape, seed, out=None):
+    """Uniform in [-0.5, 0.5) from a seeded generator on the device (into `out` when given: the same values again)."""
+    g = torch.Generator(device=dev).manual_seed(seed)
+    if out is not None:
+        return torch.rand(out.shape, device=dev, generator=g, out=out).sub_(0.5)
+    return torch.rand(*shape, device=dev, generator=g).sub_(0.5)
+
+
+def _zero_ring(x):
+    x[:, 0].zero_()
+    x[:, -1].zero_()
+    x[:, :, 0].zero_()
+    x[:, :, -1].zero_()
+    return x
+
+
+def _padded_rand(torch, dev, N, H, W, C, seed, out=None):
+    """[N][H+2][W+2][C], interior uniform in [-0.5, 0.5), zero ring; built in place (no interior-sized temporary)."""
+    return _zero_ring(_rand(torch, dev, (N, H + 2, W + 2, C), seed, out=out))
+
+
+def _finite(torch, t):
+    """Every element finite, on the GPU, a slab of images at a time."""
+    step = max(1, (1 << 28) // max(1, t[0].numel()))
+    return all(bool(torch.isfinite(t[i:i + step]).all()) for i in range(0, t.shape[0], step))
+
+
+def _ring_zero(t):
+    return all(bool((r == 0).all()) for r in (t[:, 0], t[:, -1], t[:, :, 0], t[:, :, -1]))
+
+
+def _pick(torch, t, idx):
+    return t[torch.as_tensor(idx, device=t.device)].cpu()
+
+
+def _check_padded(O, torch, out, idx, want, name=""):
+    """out [N][H+2][W+2][K] on the GPU: finite, zero ring, the images idx against want [n][H][W][K]."""
+    assert _finite(torch, out), name
+    assert _ring_zero(out), name
+    got = _pick(torch, out, idx)
+    assert O.rel_error(got[:, 1:-1, 1:-1, :].numpy(), want) < TIGHT, name
+    return got
+
+
+# ------------------------------------------------------------------ the residual 3x3 (a batch cut into two launches)
+N_3X3, H_3X3, C_3X3 = 5100, 56, 64
+CUT_3X3 = 4928   # the first launch: the largest multiple of 64 images whose tensors stay below 4 GiB
+
+
+@pytest.mark.parametrize("form", ["default", "stream_k_tail"])
+@pytest.mark.parametrize("in_place", [False, True])
+def test_residual_3x3_beyond_4gib(form, in_place, pkg, O, torch_dev, knobs, free_after):
+    """conv3x3_bn_add_relu, 5100 images of 56x56x64: in, res and out are 4.4 GB each; the launcher cuts the batch
+    at 4928 and advances in, res and out together.  Out of place and in place (res is out); the planner's form, and
+    the throughput kernel forced with a grid that leaves a stream-K tail in both launches."""
+    torch, dev = torch_dev
+    N, H, C = N_3X3, H_3X3, C_3X3
+    P = (H + 2) * (H + 2) * C * 4
+    _need(torch, (2 if in_place else 3) * N * P)
+    if form == "stream_k_tail":
+        knobs.set("WINO_3X3_ALGO", "big")
+        knobs.set("WINO_SK_GRID", 1000)   # 60368 and 2107 items: tails of 368 and 107
+    idx = _images(N, [P], cuts=[CUT_3X3])
+    g = torch.Generator(device="cpu").manual_seed(71)
+    w = (torch.rand(C, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
+    bias, scale = torch.rand(C, generator=g) - 0.5, torch.rand(C, generator=g) + 0.5
+    U, bt, st = pkg.filter_transform_f2(w.to(dev)), bias.to(dev), scale.to(dev)
+    x = _padded_rand(torch, dev, N, H, H, C, 72)
+    res = _padded_rand(torch, dev, N, H, H, C, 73)
+    ref = types.SimpleNamespace(torch=torch, x=_pick(torch, x, idx), res=_pick(torch, res, idx), w=w, bias=bias,
+                                scale=scale)
+    want = _ResLayer.reference(ref, relu=True)
+    out = res if in_place else torch.empty_like(x)
+    first = None
+    for rep in range(2):
+        if in_place and rep:   # the first launch overwrote the residual: the same values again
+            _padded_rand(torch, dev, N, H, H, C, 73, out=res)
+        if not in_place:
+            out.fill_(NAN)
+        got = pkg.conv3x3_bn_add_relu(x, U, bt, st, res, out=out)
+        assert got.data_ptr() == out.data_ptr()
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert 0.2 < (want > 0).mean() < 0.8
+    del x, res, out, got
+
+
+def test_basic_block_beyond_4gib(pkg, O, torch_dev, free_after):
+    """basic_block, 5100 images of 56x56x64: x, out and the workspace (t1) are 4.4 GB each; both convolutions are
+    cut at 4928 images, the second reading x as its residual."""
+    torch, dev = torch_dev
+    N, H, C = N_3X3, H_3X3, C_3X3
+    P = (H + 2) * (H + 2) * C * 4
+    _need(torch, 3 * N * P)
+    idx = _images(N, [P], cuts=[CUT_3X3])
+    g = torch.Generator(device="cpu").manual_seed(81)
+    ws_ = [(torch.rand(C, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4 for _ in range(2)]
+    bn = [(torch.rand(C, generator=g) - 0.5, torch.rand(C, generator=g) + 0.5) for _ in range(2)]
+    U = [pkg.filter_transform_f2(w.to(dev)) for w in ws_]
+    bnt = [(b.to(dev), s.to(dev)) for b, s in bn]
+    x = _padded_rand(torch, dev, N, H, H, C, 82)
+    x_idx = _pick(torch, x, idx)
+    want = _BasicBlock.reference(types.SimpleNamespace(torch=torch, w=ws_, bn=bn), x_idx)
+    need = pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, H, C)
+    assert need == N * P
+    out = torch.empty_like(x)
+    ws = torch.empty(need // 4, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        ws.fill_(NAN)
+        pkg.basic_block(x, U[0], bnt[0], U[1], bnt[1], out=out, workspace=ws)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
+        assert _finite(torch, ws.view(N, H + 2, H + 2, C)) and _ring_zero(ws.view(N, H + 2, H + 2, C))
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert (want > 0).mean() > 0.2
+    del x, out, ws
+
+
+# ------------------------------------------------------------------ the chained 1x1 (A_PADDED, C_PADDED, ADD_RESIDUAL)
+@pytest.mark.parametrize("form", sorted(FORMS_1X1))
+def test_conv1x1_chaining_forms_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
+    """conv1x1_bn_ex at 56x56, 256 -> 256, 1400 images: A unpadded 4.5 GB or padded 4.8 GB, the residual 4.5 GB, out
+    4.5 GB or (C_PADDED) 4.8 GB.  Every combination of A_PADDED, C_PADDED and ADD_RESIDUAL (with the ReLU), in the
+    planner's form, tiled and stream-K."""
+    torch, dev = torch_dev
+    N, H, C, K = 1400, 56, 256, 256
+    M = N * H * H
+    Pu, Pp = H * H * C * 4, (H + 2) * (H + 2) * C * 4
+    _need(torch, N * (Pu + Pp) + N * H * H * K * 4 + N * (H + 2) * (H + 2) * K * 4)
+    _set(knobs, FORMS_1X1[form])
+    idx = _images(N, [Pu, Pp])
+    rng = np.random.RandomState(91)
+    B = ((rng.rand(C, K) - 0.5) / np.sqrt(C) * 4).astype(np.float32)
+    s = (rng.rand(K) + 0.5).astype(np.float32)
+    b = (rng.rand(K) - 0.5).astype(np.float32)
+    Bt, st, bt = (torch.from_numpy(a).to(dev) for a in (B, s, b))
+    Ap = _rand(torch, dev, (N, H + 2, H + 2, C), 92)
+    Ap[:, 0].fill_(NAN)                     # A_PADDED does not read the ring
+    Ap[:, :, -1].fill_(1e6)
+    Au = _rand(torch, dev, (N, H, H, C), 93)
+    R = _rand(torch, dev, (M, K), 94)
+    out_buf = torch.empty(N * (H + 2) * (H + 2) * K, device=dev)
+    # the fp64 reference of the checked images: BN(A . B), then the residual and the ReLU per combination
+    pick = lambda t: _pick(torch, t, idx).double().numpy()
+    yp = O.conv1x1_bn(pick(Ap)[:, 1:-1, 1:-1, :].reshape(-1, C), B, b, s, False).reshape(len(idx), H, H, K)
+    yu = O.conv1x1_bn(pick(Au).reshape(-1, C), B, b, s, False).reshape(len(idx), H, H, K)
+    r_idx = pick(R.view(N, H, H, K))
+    for flags in range(1, 8):
+        a_pad, c_pad, add = bool(flags & 1), bool(flags & 2), bool(flags & 4)
+        f = pkg.RELU | (pkg.A_PADDED if a_pad else 0) | (pkg.C_PADDED if c_pad else 0) | (pkg.ADD_RESIDUAL if add else 0)
+        want = (yp if a_pad else yu) + (r_idx if add else 0)
+        want = np.maximum(want, 0)
+        out = out_buf.view(N, H + 2, H + 2, K) if c_pad else out_buf[:M * K].view(M, K)
+        first = None
+        for rep in range(2):
+            out_buf.fill_(NAN)
+            got = pkg.conv1x1_bn_ex(Ap if a_pad else Au, Bt, bt, st, f, residual=R if add else None, out=out)
+            assert got.data_ptr() == out_buf.data_ptr()
+            torch.cuda.synchronize()
+            assert pkg.tickets_in_use() == 0, flags
+            if c_pad:
+                g_idx = _check_padded(O, torch, out, idx, want, f"flags {flags}")
+            else:
+                o4 = out.view(N, H, H, K)
+                assert _finite(torch, o4), flags
+                g_idx = _pick(torch, o4, idx)
+                assert O.rel_error(g_idx.numpy(), want) < TIGHT, flags
+            if first is None:
+                first = g_idx
+            assert torch.equal(g_idx, first), flags
+        assert 0.2 < (want > 0).mean() < 0.8, flags
+    del Ap, Au, R, out_buf, out, got
+
+
+# ------------------------------------------------------------------ the stride-2 3x3 (A_TAPS) and its fused form
+@pytest.mark.parametrize("form", sorted(FORMS_1X1))
+def test_conv3x3_s2_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
+    """conv3x3_s2_bn_relu at conv3 (56 -> 28), 128 -> 128, 5200 images: the input is 9.0 GB (past 2^31, 2^32, 3 x 2^31
+    and 2^33), the output 2.4 GB (past 2^31)."""
+    torch, dev = torch_dev
+    N, Hin, C, K = 5200, 56, 128, 128
+    H = (Hin - 1) // 2 + 1
+    Pin, Pout = (Hin + 2) * (Hin + 2) * C * 4, (H + 2) * (H + 2) * K * 4
+    _need(torch, N * (Pin + Pout))
+    _set(knobs, FORMS_1X1[form])
+    idx = _images(N, [Pin, Pout])
+    g = torch.Generator(device="cpu").manual_seed(101)
+    w = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
+    bias, scale = torch.rand(K, generator=g) - 0.5, torch.rand(K, generator=g) + 0.5
+    taps, bt, st = pkg.filter_pack_s2(w.to(dev)), bias.to(dev), scale.to(dev)
+    x = _padded_rand(torch, dev, N, Hin, Hin, C, 102)
+    ref = types.SimpleNamespace(torch=torch, x=_pick(torch, x, idx), w=w, bias=bias, scale=scale)
+    want = _S2Layer.reference(ref)
+    out = torch.empty(N, H + 2, H + 2, K, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        pkg.conv3x3_s2_bn_relu(x, taps, bt, st, relu=True, out=out)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert (want > 0).mean() > 0.2
+    del x, out
+
+
+@pytest.mark.parametrize("form", sorted(FORMS_1X1))
+def test_downsampling_block_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
+    """conv3x3_s2_proj (A_TAPS_PROJ) and basic_block_s2 at the conv3 entry, 64 -> 128, 5100 images: x is 4.4 GB,
+    t1, sc, out and the workspace 2.35 GB each (past 2^31)."""
+    torch, dev = torch_dev
+    N, Hin, C, K = 5100, 56, 64, 128
+    H = (Hin - 1) // 2 + 1
+    Pin, Pout = (Hin + 2) * (Hin + 2) * C * 4, (H + 2) * (H + 2) * K * 4
+    _need(torch, N * (Pin + 2 * Pout))
+    _set(knobs, FORMS_1X1[form])
+    idx = _images(N, [Pin, Pout])
+    g = torch.Generator(device="cpu").manual_seed(111)
+    ref = types.SimpleNamespace(torch=torch)
+    ref.w1 = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
+    ref.wd = (torch.rand(K, C, 1, 1, generator=g) - 0.5) / np.sqrt(C) * 4
+    ref.w2 = (torch.rand(K, K, 3, 3, generator=g) - 0.5) / np.sqrt(9 * K) * 4
+    vec = lambda lo: torch.rand(K, generator=g) + lo
+    ref.b1, ref.s1, ref.bd, ref.sd, ref.b2, ref.s2 = vec(-0.5), vec(0.5), vec(-0.5), vec(0.5), vec(-0.5), vec(0.5)
+    t = lambda a: a.contiguous().to(dev)
+    packed = pkg.s2_proj_pack(pkg.filter_pack_s2(t(ref.w1)), (t(ref.b1), t(ref.s1)), t(ref.wd.view(K, C).t()),
+                              (t(ref.bd), t(ref.sd)))
+    U2, bn2 = pkg.filter_transform_f2(t(ref.w2)), (t(ref.b2), t(ref.s2))
+    x = _padded_rand(torch, dev, N, Hin, Hin, C, 112)
+    ref.x = _pick(torch, x, idx)
+    want_t1, want_sc, want = _S2Block.reference(ref)
+    # the fused layer alone: t1 as the plain stride-2 layer writes it, sc's interior (its ring is not touched)
+    t1 = torch.empty(N, H + 2, H + 2, K, device=dev)
+    sc = torch.empty_like(t1)
+    first = None
+    for rep in range(2):
+        t1.fill_(NAN)
+        sc.fill_(NAN)
+        pkg.conv3x3_s2_proj(x, packed, t1=t1, sc=sc)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        a = _check_padded(O, torch, t1, idx, want_t1, f"t1 rep {rep}")
+        assert _finite(torch, sc[:, 1:-1, 1:-1, :])
+        assert bool(torch.isnan(sc[:, 0]).all()) and bool(torch.isnan(sc[:, :, -1]).all()), "sc's ring was written"
+        b = _pick(torch, sc, idx)[:, 1:-1, 1:-1, :]   # (the ring stays NaN)
+        assert O.rel_error(b.numpy(), want_sc) < TIGHT
+        if first is None:
+            first = (a, b)
+        assert torch.equal(a, first[0]) and torch.equal(b, first[1])
+    del t1, sc
+    torch.cuda.empty_cache()
+    # the block: out and the workspace (t1)
+    need = pkg.lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Hin, K)
+    assert need == N * Pout
+    out = torch.empty(N, H + 2, H + 2, K, device=dev)
+    ws = torch.empty(need // 4, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        ws.fill_(NAN)
+        pkg.basic_block_s2(x, packed, U2, bn2, out=out, workspace=ws)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        g_idx = _check_padded(O, torch, out, idx, want, f"block rep {rep}")
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert (want > 0).mean() > 0.2 and (want_sc < 0).mean() > 0.2
+    del x, out, ws
+
+
+# ------------------------------------------------------------------ the bottleneck blocks
+N_BLK, H_BLK = 1400, 56
+
+
+@pytest.mark.parametrize("form", ["default", "stream_k"])
+@pytest.mark.parametrize("stride", [2, 1])
+def test_proj_block_beyond_4gib(stride, form, pkg, O, torch_dev, knobs, free_after):
+    """proj_block (A_STRIDED at stride 2, the plain 1x1 at stride 1, A_TWO in the tail) at the conv3 entry, 256 -> 128
+    -> 512, 1400 images: x is 4.5 GB; out 2.2 GB (stride 2) or 9.0 GB (stride 1); the workspace 1.3 or 4.8 GB."""
+    torch, dev = torch_dev
+    N, Hin, Cin, Cm, C4 = N_BLK, H_BLK, 256, 128, 512
+    H = (Hin - 1) // stride + 1
+    Px, Pout, Pt = Hin * Hin * Cin * 4, H * H * C4 * 4, (H + 2) * (H + 2) * Cm * 4
+    need = pkg.lib().wino_proj_block_workspace_bytes_hw(N, H, H, Cm)
+    assert need == 2 * N * Pt
+    _need(torch, N * (Px + Pout) + need)
+    _set(knobs, FORMS_1X1[form])
+    idx = _images(N, [Px, Pout, Pt])
+    rng = np.random.RandomState(121 + stride)
+    w1, w2, w3, wp, bn = _proj_weights(rng, Cin, Cm, C4)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    bnt = [(t(b), t(s)) for b, s in bn]
+    U2 = pkg.filter_transform_f2(t(w2))
+    tail = pkg.proj_tail_pack(t(w3), bnt[2], t(wp), bnt[3])
+    x = _rand(torch, dev, (N, Hin, Hin, Cin), 122)
+    want = _proj_oracle(O, _pick(torch, x, idx).numpy(), stride, w1, w2, w3, wp, bn)
+    out = torch.empty(N, H, H, C4, device=dev)
+    ws = torch.empty(need // 4, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        ws.fill_(NAN)
+        pkg.proj_block(x, t(w1), bnt[0], U2, bnt[1], tail, stride, out=out, workspace=ws)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        assert _finite(torch, out)
+        t12 = ws.view(2 * N, H + 2, H + 2, Cm)
+        assert _finite(torch, t12) and _ring_zero(t12)
+        g_idx = _pick(torch, out, idx)
+        assert O.rel_error(g_idx.numpy(), want) < TIGHT, rep
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert (want > 0).mean() > 0.2
+    del x, out, ws
+
+
+def test_proj_block_v15_beyond_4gib(pkg, O, torch_dev, free_after):
+    """proj_block_v15 at the conv3 entry, 256 -> 128 -> 512, 1400 images: x is 4.5 GB, t1 (at the input's 56x56)
+    2.4 GB, out 2.2 GB."""
+    torch, dev = torch_dev
+    N, Hin, Cin, Cm, C4 = N_BLK, H_BLK, 256, 128, 512
+    H = (Hin - 1) // 2 + 1
+    Px, Pout, Pt1 = Hin * Hin * Cin * 4, H * H * C4 * 4, (Hin + 2) * (Hin + 2) * Cm * 4
+    need = pkg.lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Hin, Cm)
+    _need(torch, N * (Px + Pout) + need)
+    idx = _images(N, [Px, Pout, Pt1])
+    g = torch.Generator(device="cpu").manual_seed(131)
+    r = lambda *s: torch.rand(*s, generator=g) - 0.5
+    ref = types.SimpleNamespace(torch=torch)
+    ref.w1 = r(Cin, Cm) / np.sqrt(Cin) * 4
+    ref.w2 = r(Cm, Cm, 3, 3) / np.sqrt(9 * Cm) * 4
+    ref.w3 = r(Cm, C4) / np.sqrt(Cm) * 4
+    ref.wp = r(Cin, C4) / np.sqrt(Cin) * 2
+    ref.bn = [(r(c), r(c) + 1.0) for c in (Cm, Cm, C4, C4)]
+    t = lambda a: a.contiguous().to(dev)
+    bnt = [(t(b), t(s)) for b, s in ref.bn]
+    taps = pkg.filter_pack_s2(t(ref.w2))
+    tail = pkg.proj_tail_pack(t(ref.w3), bnt[2], t(ref.wp), bnt[3])
+    x = _rand(torch, dev, (N, Hin, Hin, Cin), 132)
+    ref.x = _pick(torch, x, idx)
+    want = _V15Block.reference(ref)
+    out = torch.empty(N, H, H, C4, device=dev)
+    ws = torch.empty(need // 4, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        ws.fill_(NAN)
+        pkg.proj_block_v15(x, t(ref.w1), bnt[0], taps, bnt[1], tail, out=out, workspace=ws)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        assert _finite(torch, out)
+        g_idx = _pick(torch, out, idx)
+        assert O.rel_error(g_idx.numpy(), want) < TIGHT, rep
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert (want > 0).mean() > 0.2
+    del x, out, ws
+
+
+def test_residual_block_beyond_4gib(pkg, O, torch_dev, free_after):
+    """residual_block (wino_residual_block_hw) at 56x56, 256 -> 64 -> 256, 1400 images: x and out are 4.5 GB each,
+    the workspace (two padded intermediates) 2.4 GB."""
+    torch, dev = torch_dev
+    N, H, C4, Cm = N_BLK, H_BLK, 256, 64
+    P, Pt = H * H * C4 * 4, (H + 2) * (H + 2) * Cm * 4
+    need = pkg.lib().wino_residual_block_workspace_bytes_hw(N, H, H, Cm)
+    assert need == 2 * N * Pt
+    _need(torch, 2 * N * P + need)
+    idx = _images(N, [P, Pt])
+    rng = np.random.RandomState(141)
+    w1 = ((rng.rand(C4, Cm) - 0.5) / np.sqrt(C4) * 4).astype(np.float32)
+    w2 = ((rng.rand(Cm, Cm, 3, 3) - 0.5) / np.sqrt(9 * Cm) * 4).astype(np.float32)
+    w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
+    bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4)]
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    bnt = [(t(b), t(s)) for b, s in bn]
+    U2 = pkg.filter_transform_f2(t(w2))
+    x = _rand(torch, dev, (N, H, H, C4), 142)
+    want = O.residual_block(_pick(torch, x, idx).numpy(), w1, bn[0], w2, bn[1], w3, bn[2])
+    out = torch.empty_like(x)
+    ws = torch.empty(need // 4, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        ws.fill_(NAN)
+        pkg.residual_block(x, t(w1), bnt[0], U2, bnt[1], t(w3), bnt[2], out=out, workspace=ws)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        assert _finite(torch, out)
+        t12 = ws.view(2 * N, H + 2, H + 2, Cm)
+        assert _finite(torch, t12) and _ring_zero(t12)
+        g_idx = _pick(torch, out, idx)
+        assert O.rel_error(g_idx.numpy(), want) < TIGHT, rep
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert (want > 0).mean() > 0.2
+    del x, out, ws
+
+
+# ------------------------------------------------------------------ the largest filter matrix the 3x3 accepts
+def test_3x3_largest_accepted_filter(pkg, O, torch_dev, knobs, free_after):
+    """C = 8192, K = 8128: U is 3.97 GiB (the throughput kernel reads it through one descriptor, so its high offsets
+    are those of the last channel chunks and out-channel blocks), w 2.2 GiB.  One 4x4 image keeps the fp64 reference
+    cheap; all K output channels are checked, in both kernels."""
+    torch, dev = torch_dev
+    N, H, C, K = 1, 4, 8192, 8128
+    assert 16 * C * K * 4 < (1 << 32) <= 16 * C * (K + 64) * 4
+    _need(torch, (9 + 16) * C * K * 4)
+    g = torch.Generator(device=dev).manual_seed(151)
+    w = (torch.rand(K, C, 3, 3, device=dev, generator=g) - 0.5) / np.sqrt(9 * C) * 4
+    bias = torch.rand(K, device=dev, generator=g) - 0.5
+    scale = torch.rand(K, device=dev, generator=g) + 0.5
+    x = _padded_rand(torch, dev, N, H, H, C, 152)
+    U = pkg.filter_transform_f2(w)
+    torch.cuda.synchronize()
+    w_cpu = w.cpu().numpy()
+    del w
+    torch.cuda.empty_cache()
+    want = O.conv3x3_bn_relu_direct(x.cpu().numpy(), w_cpu, scale.cpu().numpy(), bias.cpu().numpy())
+    del w_cpu
+    out = torch.empty(N, H + 2, H + 2, K, device=dev)
+    for algo in ("big", "small"):
+        knobs.set("WINO_3X3_ALGO", algo)
+        assert pkg.small_plan_3x3(N, C, K, H=H, W=H)[0] == (algo == "small")
+        first = None
+        for rep in range(2):
+            out.fill_(NAN)
+            pkg.conv3x3_bn_relu(x, U, bias, scale, relu=True, out=out)
+            torch.cuda.synchronize()
+            assert pkg.tickets_in_use() == 0
+            got = out.cpu()
+            assert np.isfinite(got.numpy()).all(), algo
+            assert (got[:, 0] == 0).all() and (got[:, -1] == 0).all() and (got[:, :, 0] == 0).all() \
+                and (got[:, :, -1] == 0).all(), algo
+            assert O.rel_error(got.numpy(), want) < TIGHT, algo
+            # the last out-channel block alone: its filters sit at U's highest offsets
+            assert O.rel_error(got.numpy()[..., -64:], want[..., -64:]) < TIGHT, algo
+            if first is None:
+                first = got
+            assert torch.equal(got, first), algo
+    assert 0.2 < (want[:, 1:-1, 1:-1, :] > 0).mean() < 0.8
+    del x, U, out
