@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "wino_basic_block_prepare_hw",
     "wino_s2_proj_elems", "wino_s2_proj_pack", "wino_conv3x3_s2_proj_bn_relu_hw", "wino_basic_block_s2_workspace_bytes_hw",
     "wino_basic_block_s2_hw", "wino_basic_block_s2_prepare_hw",
+    "wino_stem_filter_elems", "wino_stem_filter_pack", "wino_stem_hw", "wino_stem_plan", "wino_head_elems",
+    "wino_head_pack", "wino_head_workspace_bytes", "wino_head_prepare", "wino_avgpool_fc_hw",
     # reference entry points + helpers (Kernel*.h, util.h)
     "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
     "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
@@ -170,6 +172,18 @@ def lib() -> ctypes.CDLL:
     L.wino_basic_block_s2_workspace_bytes_hw.argtypes = [c_int] * 4
     L.wino_basic_block_s2_hw.argtypes = [fp] * 6 + [c_int] * 5 + [fp, c_size_t, c_void_p]
     L.wino_basic_block_s2_prepare_hw.argtypes = [c_int] * 5 + [c_void_p]
+    L.wino_stem_filter_elems.restype = c_size_t
+    L.wino_stem_filter_elems.argtypes = [c_int]
+    L.wino_stem_filter_pack.argtypes = [fp] * 4 + [c_int, c_void_p]
+    L.wino_stem_hw.argtypes = [fp] * 3 + [c_int] * 5 + [c_void_p]
+    L.wino_stem_plan.argtypes = [c_int] * 5 + [POINTER(c_int)]
+    L.wino_head_elems.restype = c_size_t
+    L.wino_head_elems.argtypes = [c_int] * 2
+    L.wino_head_pack.argtypes = [fp] * 3 + [c_int] * 2 + [c_void_p]
+    L.wino_head_workspace_bytes.restype = c_size_t
+    L.wino_head_workspace_bytes.argtypes = [c_int] * 3
+    L.wino_head_prepare.argtypes = [c_int] * 3 + [c_void_p]
+    L.wino_avgpool_fc_hw.argtypes = [fp] * 3 + [c_int] * 6 + [fp, c_size_t, c_void_p]
     for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
                  "kernel_256_1_in", "kernel_256_1_out"):
         getattr(L, name).restype = c_int
@@ -848,6 +862,113 @@ def basic_block_s2(x, packed, U2, bn2, out=None, workspace=None) -> torch.Tensor
     return out
 
 
+STEM_FORM_BIG, STEM_FORM_SMALL = 1, 2   # WINO_STEM_FORM_*
+
+
+def stem_out_hw(H: int, W: int):
+    """The stem's pooled grid: conv 7x7 stride 2 pad 3, then max-pool 3x3 stride 2 pad 1 (224 -> 112 -> 56)."""
+    Hc, Wc = (int(H) - 1) // 2 + 1, (int(W) - 1) // 2 + 1
+    return (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+
+
+def stem_filter_pack(w, bn) -> torch.Tensor:
+    """The stem's conv filter, torch's w [K][3][7][7], and its BN bn = (bias, scale) packed into one opaque buffer
+    (wino_stem_filter_pack).  The scale is not folded into the filter."""
+    w = _dev(w, "w")
+    if w.dim() != 4 or tuple(w.shape[1:]) != (3, 7, 7):
+        raise WinoError("w must be [K][3][7][7]")
+    K = int(w.shape[0])
+    vecs = [_dev(v, "bn") for v in bn]
+    if len(vecs) != 2 or any(v.numel() != K for v in vecs):
+        raise WinoError("bn must be (bias, scale) with K values each")
+    n = lib().wino_stem_filter_elems(K)
+    if n == 0:
+        raise WinoError(f"stem: unsupported K={K} (need K % 64 == 0)")
+    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    _on_current_device(w, packed, *vecs)
+    _check(lib().wino_stem_filter_pack(w.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), packed.data_ptr(), K,
+                                       _stream()), "wino_stem_filter_pack")
+    return packed
+
+
+def stem_plan(N: int, H: int, W: int, K: int = 64, cus: int = 256) -> int:
+    """The STEM_FORM_* the stem takes for this shape on a device with `cus` CUs (host-side)."""
+    f = c_int(0)
+    _check(lib().wino_stem_plan(int(N), int(H), int(W), int(K), int(cus), ctypes.byref(f)), "wino_stem_plan")
+    return int(f.value)
+
+
+def stem(x, packed, out_padded: bool = False, out=None) -> torch.Tensor:
+    """ResNet stem, one HIP launch: maxpool3x3_s2_p1(relu(bn(conv7x7_s2_p3(x)))).  x [N][3][H][W] (NCHW) ->
+    out [N][Hp][Wp][K] (channels-last; proj_block's and residual_block's x) or, out_padded, [N][Hp+2][Wp+2][K] with a
+    zero ring (basic_block's x).  packed from stem_filter_pack."""
+    x, packed = _dev(x, "x"), _dev(packed, "packed")
+    if x.dim() != 4 or int(x.shape[1]) != 3:
+        raise WinoError("x must be [N][3][H][W]")
+    N, H, W = int(x.shape[0]), int(x.shape[2]), int(x.shape[3])
+    if packed.dim() != 1 or packed.numel() % 150:
+        raise WinoError("packed does not hold a stem filter: pack it with stem_filter_pack")
+    K = packed.numel() // 150
+    Hp, Wp = stem_out_hw(H, W)
+    p = 2 if out_padded else 0
+    shape = (N, Hp + p, Wp + p, K)
+    out = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else _out(out, shape, "out")
+    _on_current_device(x, packed, out)
+    _check(lib().wino_stem_hw(x.data_ptr(), packed.data_ptr(), out.data_ptr(), N, H, W, K, int(bool(out_padded)),
+                              _stream()), "wino_stem_hw")
+    return out
+
+
+def head_pack(wfc, bfc) -> torch.Tensor:
+    """The classifier head's FC layer, torch's weight [classes][C] and bias [classes], packed into one opaque buffer
+    (wino_head_pack; the class count padded to a multiple of 64 inside)."""
+    w, b = _dev(wfc, "wfc"), _dev(bfc, "bfc")
+    if w.dim() != 2 or b.dim() != 1 or int(b.shape[0]) != int(w.shape[0]):
+        raise WinoError("wfc must be [classes][C], bfc [classes]")
+    classes, C = int(w.shape[0]), int(w.shape[1])
+    n = lib().wino_head_elems(C, classes)
+    if n == 0:
+        raise WinoError(f"head: unsupported C={C} classes={classes} (need C % 32 == 0)")
+    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    _on_current_device(w, b, packed)
+    _check(lib().wino_head_pack(w.data_ptr(), b.data_ptr(), packed.data_ptr(), C, classes, _stream()), "wino_head_pack")
+    return packed
+
+
+def head_prepare(N: int, C: int, classes: int) -> None:
+    """Allocate the head GEMM's stream-K scratch for the current stream (before graph capture)."""
+    _check(lib().wino_head_prepare(int(N), int(C), int(classes), _stream()), "wino_head_prepare")
+
+
+def avgpool_fc(feat, packed, classes: int, in_padded: bool = False, out=None, workspace=None) -> torch.Tensor:
+    """Classifier head: logits [N][classes] = mean_hw(feat) . Wfc^T + b.  feat [N][H][W][C] or, in_padded,
+    [N][H+2][W+2][C] (the ring is not read); packed from head_pack(Wfc, b) with the same `classes`."""
+    f, packed = _dev(feat, "feat"), _dev(packed, "packed")
+    if f.dim() != 4:
+        raise WinoError("feat must be [N][H][W][C]")
+    p = 2 if in_padded else 0
+    N, H, W, C = int(f.shape[0]), int(f.shape[1]) - p, int(f.shape[2]) - p, int(f.shape[3])
+    if H < 1 or W < 1:
+        raise WinoError("feat has no interior")
+    classes = int(classes)
+    n = lib().wino_head_elems(C, classes)
+    if n == 0 or packed.numel() != n:
+        raise WinoError(f"packed does not match C={C} classes={classes}: pack it with head_pack")
+    need = lib().wino_head_workspace_bytes(N, C, classes)
+    if workspace is None:
+        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=f.device)
+    else:
+        _out(workspace, None, "workspace")
+        if workspace.numel() * 4 < need:
+            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
+    out = torch.empty((N, classes), dtype=torch.float32, device=f.device) if out is None else _out(out, (N, classes), "out")
+    _on_current_device(f, packed, out, workspace)
+    _check(lib().wino_avgpool_fc_hw(f.data_ptr(), packed.data_ptr(), out.data_ptr(), N, H, W, C, classes,
+                                    int(bool(in_padded)), workspace.data_ptr(), workspace.numel() * 4, _stream()),
+           "wino_avgpool_fc_hw")
+    return out
+
+
 def conv1x1_direct(A, B, bn_bias, bn_scale, relu: bool) -> torch.Tensor:
     a, bm = _dev(A, "A"), _dev(B, "B")
     b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
@@ -867,3 +988,6 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
     if world < 1 or not (0 <= rank < world):
         raise ValueError("bad rank/world")
     return (N * rank) // world, (N * (rank + 1)) // world
+
+
+from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)

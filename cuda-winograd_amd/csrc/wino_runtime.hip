@@ -150,6 +150,7 @@ void read_knobs() {
   k.small_ks = env_num("WINO_1X1_SMALL_KS", 0);
   k.small_rt = env_num("WINO_1X1_SMALL_RT", 0);
   k.small_ct = env_num("WINO_1X1_SMALL_CT", 0);
+  k.stem_form = env_num("WINO_STEM_FORM", 0);
   g_knobs = k;
 }
 }  // namespace

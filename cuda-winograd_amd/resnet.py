@@ -1,0 +1,306 @@
+"""Whole torchvision ResNets (18, 34, 50, 101, 152) on the library's kernels.
+
+``ResNet.from_state_dict(sd, arch)`` takes a torchvision state dict (its key names), folds every BN and packs every
+filter once; ``model(x_nchw)`` returns the logits.  The forward is a straight chain of launches on the current
+stream: the stem, the blocks, the head.
+
+- ResNet-18 / -34 (basic blocks) keep the padded layout [N][H+2][W+2][C] from the stem on: the stem writes its
+  zero ring, ``basic_block_s2`` opens conv3..conv5, ``basic_block`` runs in place on its stage's tensor, and the head
+  reads the padded map without its ring.
+- ResNet-50 / -101 / -152 (bottlenecks, torchvision's v1.5 placement) use the unpadded layout [N][H][W][C]:
+  ``proj_block`` at stride 1 opens conv2, ``proj_block_v15`` opens conv3..conv5, and ``residual_block`` ping-pongs
+  between the stage's two tensors.
+
+``prepare(N, H, W)`` allocates the activations and one shared workspace for an input shape and reserves every
+launch's stream scratch, so that a whole forward can then be captured in one ``torch.cuda.graph``.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import (WinoError, avgpool_fc, basic_block, basic_block_prepare, basic_block_s2, basic_block_s2_prepare,
+               filter_pack_s2, filter_transform_f2, head_pack, head_prepare, lib, proj_block, proj_block_prepare,
+               proj_block_v15, proj_block_v15_prepare, proj_tail_pack, residual_block, residual_block_prepare,
+               s2_proj_pack, stem, stem_filter_pack, stem_out_hw)
+
+# arch -> (bottleneck?, blocks per stage)
+ARCHS = {
+    "resnet18": (False, (2, 2, 2, 2)),
+    "resnet34": (False, (3, 4, 6, 3)),
+    "resnet50": (True, (3, 4, 6, 3)),
+    "resnet101": (True, (3, 4, 23, 3)),
+    "resnet152": (True, (3, 8, 36, 3)),
+}
+PLANES = (64, 128, 256, 512)
+BN_KEYS = ("weight", "bias", "running_mean", "running_var")
+
+
+def _s2(h: int) -> int:
+    return (h - 1) // 2 + 1
+
+
+def stage_shapes(arch: str, H: int, W: int):
+    """[(name, C, h, w)] of the stem's output and of the four stages' outputs for an H x W input."""
+    if arch not in ARCHS:
+        raise WinoError(f"unknown arch {arch!r}: one of {sorted(ARCHS)}")
+    bottleneck, _ = ARCHS[arch]
+    h, w = stem_out_hw(H, W)
+    shapes = [("stem", 64, h, w)]
+    for i, planes in enumerate(PLANES):
+        if i:
+            h, w = _s2(h), _s2(w)
+        shapes.append((f"layer{i + 1}", planes * (4 if bottleneck else 1), h, w))
+    return shapes
+
+
+def expected_keys(arch: str, classes: int):
+    """{key: shape} of a torchvision state dict of `arch` (num_batches_tracked aside)."""
+    if arch not in ARCHS:
+        raise WinoError(f"unknown arch {arch!r}: one of {sorted(ARCHS)}")
+    bottleneck, blocks = ARCHS[arch]
+    exp = {}
+
+    def bn(prefix, c):
+        for k in BN_KEYS:
+            exp[f"{prefix}.{k}"] = (c,)
+
+    exp["conv1.weight"] = (64, 3, 7, 7)
+    bn("bn1", 64)
+    cin = 64
+    for L, (planes, nb) in enumerate(zip(PLANES, blocks), 1):
+        for b in range(nb):
+            p = f"layer{L}.{b}"
+            stride = 2 if (b == 0 and L > 1) else 1
+            if bottleneck:
+                cout = planes * 4
+                exp[f"{p}.conv1.weight"] = (planes, cin, 1, 1)
+                exp[f"{p}.conv2.weight"] = (planes, planes, 3, 3)
+                exp[f"{p}.conv3.weight"] = (cout, planes, 1, 1)
+                bn(f"{p}.bn1", planes), bn(f"{p}.bn2", planes), bn(f"{p}.bn3", cout)
+            else:
+                cout = planes
+                exp[f"{p}.conv1.weight"] = (planes, cin, 3, 3)
+                exp[f"{p}.conv2.weight"] = (planes, planes, 3, 3)
+                bn(f"{p}.bn1", planes), bn(f"{p}.bn2", planes)
+            if stride != 1 or cin != cout:
+                exp[f"{p}.downsample.0.weight"] = (cout, cin, 1, 1)
+                bn(f"{p}.downsample.1", cout)
+            cin = cout
+    exp["fc.weight"] = (classes, cin)
+    exp["fc.bias"] = (classes,)
+    return exp
+
+
+def validate_state_dict(sd, arch: str) -> int:
+    """Checks every key and shape of `sd` against `arch` on the host; returns the class count.  Raises WinoError
+    naming the first missing, unexpected or wrongly shaped key."""
+    if "fc.weight" not in sd:
+        raise WinoError("state dict: missing key 'fc.weight'")
+    classes = int(sd["fc.weight"].shape[0])
+    exp = expected_keys(arch, classes)
+    for k in exp:
+        if k not in sd:
+            raise WinoError(f"state dict: missing key {k!r} for {arch}")
+    for k, v in sd.items():
+        if k.endswith(".num_batches_tracked") and k[: -len("num_batches_tracked")] + "weight" in exp:
+            continue
+        if k not in exp:
+            raise WinoError(f"state dict: unexpected key {k!r} for {arch}")
+        if tuple(v.shape) != exp[k]:
+            raise WinoError(f"state dict: key {k!r} has shape {tuple(v.shape)}, {arch} needs {exp[k]}")
+    return classes
+
+
+class ResNet:
+    """A torchvision ResNet on the library's kernels, inference only (BN folded at load)."""
+
+    def __init__(self, arch: str, classes: int, device):
+        self.arch, self.classes, self.device = arch, classes, torch.device(device)
+        self.bottleneck, self.blocks = ARCHS[arch]
+        self._shape = None
+
+    # ------------------------------------------------------------------ loading
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, eps: float = 1e-5, device=None) -> "ResNet":
+        """Validate `sd` (torchvision key names) for `arch`, fold every BN (scale = gamma / sqrt(var + eps),
+        bias = beta - mean * scale) and pack every filter on `device` (default: the current CUDA device)."""
+        classes = validate_state_dict(sd, arch)
+        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if dev.type != "cuda":
+            raise WinoError("ResNet runs on a CUDA(HIP) device only -- there is no CPU path")
+        m = cls(arch, classes, dev)
+        with torch.cuda.device(dev):
+            m._pack(sd, eps)
+        return m
+
+    def _t(self, v):
+        return v.detach().to(device=self.device, dtype=torch.float32).contiguous()
+
+    def _bn(self, sd, prefix, eps):
+        g, b = sd[f"{prefix}.weight"].double(), sd[f"{prefix}.bias"].double()
+        mean, var = sd[f"{prefix}.running_mean"].double(), sd[f"{prefix}.running_var"].double()
+        scale = g / torch.sqrt(var + eps)
+        return self._t(b - mean * scale), self._t(scale)   # (bias, scale), the library's order
+
+    def _pack(self, sd, eps):
+        def w1x1(key):   # torch's [K][C][1][1] -> the library's [C][K]
+            w = sd[key]
+            return self._t(w.reshape(w.shape[0], w.shape[1]).t())
+
+        self.stem_packed = stem_filter_pack(self._t(sd["conv1.weight"]), self._bn(sd, "bn1", eps))
+        self.layers = []
+        cin = 64
+        for L, (planes, nb) in enumerate(zip(PLANES, self.blocks), 1):
+            blocks = []
+            for b in range(nb):
+                p = f"layer{L}.{b}"
+                first = b == 0
+                bn1, bn2 = self._bn(sd, f"{p}.bn1", eps), self._bn(sd, f"{p}.bn2", eps)
+                if self.bottleneck:
+                    cout = planes * 4
+                    w1, bn3 = w1x1(f"{p}.conv1.weight"), self._bn(sd, f"{p}.bn3", eps)
+                    if first:
+                        tail = proj_tail_pack(w1x1(f"{p}.conv3.weight"), bn3, w1x1(f"{p}.downsample.0.weight"),
+                                              self._bn(sd, f"{p}.downsample.1", eps))
+                        if L == 1:   # stride 1: the v1 and v1.5 placements are the same block
+                            w2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
+                            blocks.append(("proj", cin, planes, cout, (w1, bn1, w2, bn2, tail)))
+                        else:
+                            w2 = filter_pack_s2(self._t(sd[f"{p}.conv2.weight"]))
+                            blocks.append(("proj_v15", cin, planes, cout, (w1, bn1, w2, bn2, tail)))
+                    else:
+                        U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
+                        blocks.append(("residual", cin, planes, cout,
+                                       (w1, bn1, U2, bn2, w1x1(f"{p}.conv3.weight"), bn3)))
+                else:
+                    cout = planes
+                    if first and L > 1:
+                        packed = s2_proj_pack(filter_pack_s2(self._t(sd[f"{p}.conv1.weight"])), bn1,
+                                              w1x1(f"{p}.downsample.0.weight"), self._bn(sd, f"{p}.downsample.1", eps))
+                        U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
+                        blocks.append(("basic_s2", cin, planes, cout, (packed, U2, bn2)))
+                    else:
+                        U1 = filter_transform_f2(self._t(sd[f"{p}.conv1.weight"]))
+                        U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
+                        blocks.append(("basic", cin, planes, cout, (U1, bn1, U2, bn2)))
+                cin = cout
+            self.layers.append(blocks)
+        self.feat_c = cin
+        self.head_packed = head_pack(self._t(sd["fc.weight"]), self._t(sd["fc.bias"]))
+        torch.cuda.current_stream().synchronize()
+
+    # ------------------------------------------------------------------ per input shape
+    def prepare(self, N: int, H: int, W: int) -> None:
+        """Allocate the activations and the shared workspace for [N][3][H][W] inputs and reserve the stream scratch of
+        every launch on the current stream.  Call it before capturing a forward into a graph."""
+        N, H, W = int(N), int(H), int(W)
+        if N < 1 or H < 1 or W < 1:
+            raise WinoError(f"bad input shape N={N} H={H} W={W}")
+        dev, f32 = self.device, torch.float32
+        shapes = stage_shapes(self.arch, H, W)
+        pad = 0 if self.bottleneck else 2
+        L = lib()
+        with torch.cuda.device(dev):
+            _, c0, h0, w0 = shapes[0]
+            self._stem_out = torch.zeros((N, h0 + pad, w0 + pad, c0), dtype=f32, device=dev)
+            self._stages = []   # per stage: the tensors its blocks write (two for the bottleneck ping-pong)
+            ws = 0
+            h, w = h0, w0
+            for (name, c, ho, wo), blocks in zip(shapes[1:], self.layers):
+                bufs = [torch.zeros((N, ho + pad, wo + pad, c), dtype=f32, device=dev)
+                        for _ in range(2 if self.bottleneck else 1)]
+                self._stages.append(bufs)
+                for kind, cin, cm, cout, _ in blocks:
+                    if kind == "basic":
+                        ws = max(ws, L.wino_basic_block_workspace_bytes_hw(N, ho, wo, cout))
+                        basic_block_prepare(N, ho, wo, cout)
+                    elif kind == "basic_s2":
+                        ws = max(ws, L.wino_basic_block_s2_workspace_bytes_hw(N, h, w, cout))
+                        basic_block_s2_prepare(N, h, w, cin, cout)
+                    elif kind == "proj":
+                        ws = max(ws, L.wino_proj_block_workspace_bytes_hw(N, ho, wo, cm))
+                        proj_block_prepare(N, h, w, cin, cm, cout, 1)
+                    elif kind == "proj_v15":
+                        ws = max(ws, L.wino_proj_block_v15_workspace_bytes_hw(N, h, w, cm))
+                        proj_block_v15_prepare(N, h, w, cin, cm, cout)
+                    else:
+                        ws = max(ws, L.wino_residual_block_workspace_bytes_hw(N, ho, wo, cm))
+                        residual_block_prepare(N, cout, cm, ho, wo)
+                h, w = ho, wo
+            ws = max(ws, L.wino_head_workspace_bytes(N, self.feat_c, self.classes))
+            head_prepare(N, self.feat_c, self.classes)
+            self._ws = torch.empty((ws + 3) // 4, dtype=f32, device=dev)
+            self._logits = torch.empty((N, self.classes), dtype=f32, device=dev)
+        self._shape = (N, H, W)
+
+    def _run_stages(self, x):
+        ws = self._ws
+        stem(x, self.stem_packed, out_padded=not self.bottleneck, out=self._stem_out)
+        cur = self._stem_out
+        outs = []
+        for bufs, blocks in zip(self._stages, self.layers):
+            for i, (kind, _, _, _, p) in enumerate(blocks):
+                if kind == "basic":   # in place on the stage's tensor after its first block
+                    basic_block(cur, p[0], p[1], p[2], p[3], out=bufs[0], workspace=ws)
+                    nxt = bufs[0]
+                elif kind == "basic_s2":
+                    nxt = basic_block_s2(cur, p[0], p[1], p[2], out=bufs[0], workspace=ws)
+                else:
+                    nxt = bufs[i % 2]
+                    if kind == "proj":
+                        proj_block(cur, p[0], p[1], p[2], p[3], p[4], 1, out=nxt, workspace=ws)
+                    elif kind == "proj_v15":
+                        proj_block_v15(cur, p[0], p[1], p[2], p[3], p[4], out=nxt, workspace=ws)
+                    else:
+                        residual_block(cur, p[0], p[1], p[2], p[3], p[4], p[5], out=nxt, workspace=ws)
+                cur = nxt
+            outs.append(cur)
+        avgpool_fc(cur, self.head_packed, self.classes, in_padded=not self.bottleneck, out=self._logits, workspace=ws)
+        return outs
+
+    def _interior(self, t):
+        return t if self.bottleneck else t[:, 1:-1, 1:-1, :]
+
+    def forward(self, x: torch.Tensor, return_stages: bool = False):
+        """x [N][3][H][W] float32 on the model's device -> logits [N][classes] (the model's own output tensor,
+        rewritten by the next forward).  With return_stages, also {"stem", "layer1".."layer4"}: views of the
+        activations (NHWC interiors), valid until the next forward.  A new input shape re-runs prepare()."""
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[1]) != 3:
+            raise WinoError("x must be [N][3][H][W]")
+        if x.device != self.device or x.dtype != torch.float32:
+            raise WinoError(f"x must be float32 on {self.device}")
+        shape = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3]))
+        if shape != self._shape:
+            self.prepare(*shape)
+        with torch.cuda.device(self.device):
+            outs = self._run_stages(x.contiguous())
+        if not return_stages:
+            return self._logits
+        names = ["layer1", "layer2", "layer3", "layer4"]
+        stages = {"stem": self._interior(self._stem_out)}
+        stages.update({n: self._interior(t) for n, t in zip(names, outs)})
+        return self._logits, stages
+
+    __call__ = forward
+
+    def flops(self, H: int = 224, W: int = 224) -> float:
+        """Algorithmic multiply-add FLOPs of one image (2 per MAC; convolutions and FC)."""
+        shapes = stage_shapes(self.arch, H, W)
+        Hc, Wc = _s2(H), _s2(W)
+        f = 2.0 * Hc * Wc * 64 * 147
+        for (_, _, ho, wo), blocks in zip(shapes[1:], self.layers):
+            for kind, cin, cm, cout, _ in blocks:
+                px = ho * wo
+                if self.bottleneck:
+                    hin = px * 4 if kind == "proj_v15" else px
+                    f += 2.0 * (hin * cin * cm + px * 9 * cm * cm + px * cm * cout)
+                    if kind in ("proj", "proj_v15"):
+                        f += 2.0 * px * cin * cout
+                else:
+                    f += 2.0 * px * 9 * (cin * cout + cout * cout)
+                    if kind == "basic_s2":
+                        f += 2.0 * px * cin * cout
+        return f + 2.0 * self.feat_c * self.classes
+
+
+__all__ = ["ARCHS", "ResNet", "stage_shapes", "expected_keys", "validate_state_dict"]

@@ -56,7 +56,8 @@ extern "C" {
  * wino_proj_block_v15_workspace_bytes_hw, wino_proj_block_v15_prepare_hw, wino_conv3x3_bn_add_relu_hw,
  * wino_basic_block_workspace_bytes_hw, wino_basic_block_hw, wino_basic_block_prepare_hw, wino_s2_proj_elems,
  * wino_s2_proj_pack, wino_conv3x3_s2_proj_bn_relu_hw, wino_basic_block_s2_workspace_bytes_hw, wino_basic_block_s2_hw,
- * wino_basic_block_s2_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_basic_block_s2_prepare_hw, wino_stem_filter_elems, wino_stem_filter_pack, wino_stem_hw, wino_stem_plan,
+ * wino_head_elems, wino_head_pack, wino_head_workspace_bytes, wino_head_prepare, wino_avgpool_fc_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived). */
 #define WINO_ABI_VERSION 1
 
@@ -482,6 +483,44 @@ int wino_basic_block_s2_hw(const float* x, const float* packed, const float* U2,
                            const float* bn2Scale, float* out, int N, int Hin, int Win, int C, int K,
                            void* workspace, size_t workspace_bytes, wino_stream_t s);
 int wino_basic_block_s2_prepare_hw(int N, int Hin, int Win, int C, int K, wino_stream_t s);
+
+/* ---- ResNet stem: conv 7x7 stride 2 pad 3 (3 -> K) + BN + ReLU + max-pool 3x3 stride 2 pad 1, one launch ----------
+ *   x    [N][3][H][W], NCHW as images come from torch; any H, W >= 1 (rows need no alignment, the base pointer does)
+ *   out  [N][Hp][Wp][K] (out_padded = 0: what wino_proj_block_hw / wino_residual_block_hw take) or
+ *        [N][Hp+2][Wp+2][K] with its ring written 0 (out_padded = 1: what wino_basic_block_hw takes),
+ *        Hc = (H-1)/2 + 1, Hp = (Hc-1)/2 + 1, the same for W (224 -> 112 -> 56)
+ * `packed` holds torch's w [K][3][7][7] and the BN vectors (bias, scale; not folded into the filter, the scale may be
+ * negative: BN and ReLU come before the max) as wino_stem_filter_pack writes them (wino_stem_filter_elems(K) floats;
+ * the layout is private to the library).  Constraints: K % 64 == 0; one image's input and output each below 2^31
+ * elements (any batch: every image is addressed from its own 64-bit base).  x, packed and out must not overlap.
+ * The contraction runs on the f32 MFMA (exact f32); the conv output never reaches memory.  No stream scratch.
+ * wino_stem_plan (host-side only): the form this shape takes on a device with `cus` CUs -- WINO_STEM_FORM_BIG
+ * (8x8 pooled outputs x 64 channels per workgroup) or WINO_STEM_FORM_SMALL (4x4 x 16, small batches); the
+ * WINO_STEM_FORM developer knob (1 / 2) forces one. */
+#define WINO_STEM_FORM_BIG 1
+#define WINO_STEM_FORM_SMALL 2
+size_t wino_stem_filter_elems(int K);
+int wino_stem_filter_pack(const float* w, const float* bnBias, const float* bnScale, float* packed, int K,
+                          wino_stream_t s);
+int wino_stem_hw(const float* x, const float* packed, float* out, int N, int H, int W, int K, int out_padded,
+                 wino_stream_t s);
+int wino_stem_plan(int N, int H, int W, int K, int cus, int* form);
+
+/* ---- ResNet classifier head: global average pool + fully connected layer ------------------------------------
+ *   logits [N][classes] = mean_hw(feat) . Wfc^T + b
+ * feat [N][H][W][C], or [N][H+2][W+2][C] with in_padded = 1 (the ring is not read).  `packed` holds torch's
+ * Wfc [classes][C] and b [classes] as wino_head_pack writes them (wino_head_elems floats; the class count is
+ * padded to a multiple of 64 inside).  An average-pool launch writes the pooled [N][C] into `workspace`
+ * (wino_head_workspace_bytes), the 1x1 GEMM (wino_conv1x1_bn with BN scale 1 and the FC bias as BN bias)
+ * multiplies it, and a trim launch copies the first `classes` columns to out (when classes % 64 != 0).
+ * Constraints: C % 32 == 0, classes >= 1.  feat, packed, out and workspace must not overlap.  The GEMM may take
+ * its stream-K form: wino_head_prepare reserves the stream's scratch ahead of a graph capture. */
+size_t wino_head_elems(int C, int classes);
+int wino_head_pack(const float* wfc, const float* bfc, float* packed, int C, int classes, wino_stream_t s);
+size_t wino_head_workspace_bytes(int N, int C, int classes);
+int wino_head_prepare(int N, int C, int classes, wino_stream_t s);
+int wino_avgpool_fc_hw(const float* feat, const float* packed, float* out, int N, int H, int W, int C, int classes,
+                       int in_padded, void* workspace, size_t workspace_bytes, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
