@@ -294,6 +294,23 @@ def _out(t: torch.Tensor, shape, name: str) -> torch.Tensor:
     return t
 
 
+def _output(t, shape, device, name: str = "out") -> torch.Tensor:
+    """The caller's output checked by _out, or a new one of `shape` on `device`."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    return _out(t, shape, name)
+
+
+def _workspace(t, need: int, device) -> torch.Tensor:
+    """The caller's workspace, checked by _out and against `need` bytes, or a new one of `need` bytes."""
+    if t is None:
+        return torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+    _out(t, None, "workspace")
+    if t.numel() * 4 < need:
+        raise WinoError(f"workspace too small: {t.numel() * 4} bytes, need {need}")
+    return t
+
+
 # --------------------------------------------------------------------------- operators
 def filter_transform_f2(w_kcrs: torch.Tensor) -> torch.Tensor:
     """[K][C][3][3] taps -> packed F(2x2,3x3) filter buffer (opaque layout, 16*C*K floats)."""
@@ -333,10 +350,7 @@ def conv3x3_bn_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor,
     N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(b.numel())
     if U.numel() != 16 * C * K or s.numel() != K:
         raise WinoError("U / bn vectors do not match C, K")
-    if out is None:
-        out = torch.empty((N, Hp, Wp, K), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, Hp, Wp, K), "out")
+    out = _output(out, (N, Hp, Wp, K), x.device)
     _on_current_device(x, U, b, s, out)
     if Hp == 16 and Wp == 16:
         _check(lib().wino_conv3x3_bn_relu(x.data_ptr(), U.data_ptr(), b.data_ptr(), s.data_ptr(),
@@ -398,10 +412,7 @@ def conv1x1_bn(A: torch.Tensor, B: torch.Tensor, bn_bias: torch.Tensor, bn_scale
     M, Cin, Kout = int(a.shape[0]), int(a.shape[1]), int(bm.shape[1])
     if b.numel() != Kout or s.numel() != Kout:
         raise WinoError("bn vectors do not match Kout")
-    if out is None:
-        out = torch.empty((M, Kout), dtype=torch.float32, device=a.device)
-    else:
-        _out(out, (M, Kout), "out")
+    out = _output(out, (M, Kout), a.device)
     _on_current_device(a, bm, b, s, out)
     _check(lib().wino_conv1x1_bn(a.data_ptr(), bm.data_ptr(), b.data_ptr(), s.data_ptr(),
                                  out.data_ptr(), M, Cin, Kout, int(relu), _stream()),
@@ -508,17 +519,8 @@ def residual_block(x, w1, bn1, U2, bn2, w3, bn3, out=None, workspace=None) -> to
     w1, w3, U2 = _dev(w1, "w1"), _dev(w3, "w3"), _dev(U2, "U2")
     Cm = int(w1.shape[1])
     vecs = [_dev(v, "bn") for pair in (bn1, bn2, bn3) for v in pair]
-    need = lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    else:
-        _out(workspace, None, "workspace")
-        if workspace.numel() * 4 < need:
-            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _out(out, x.shape, "out")
+    workspace = _workspace(workspace, lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm), x.device)
+    out = _output(out, x.shape, x.device)
     _on_current_device(x, w1, w3, U2, out, workspace, *vecs)
     args = (x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
             U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(),
@@ -591,17 +593,8 @@ def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None)
         raise WinoError(f"stride must be 1 or 2, got {stride}")
     H, W = _proj_out_hw(Hin, Win, int(stride))
     vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
-    need = lib().wino_proj_block_workspace_bytes_hw(N, H, W, Cm)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    else:
-        _out(workspace, None, "workspace")
-        if workspace.numel() * 4 < need:
-            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
-    if out is None:
-        out = torch.empty((N, H, W, C4), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, H, W, C4), "out")
+    workspace = _workspace(workspace, lib().wino_proj_block_workspace_bytes_hw(N, H, W, Cm), x.device)
+    out = _output(out, (N, H, W, C4), x.device)
     _on_current_device(x, w1, U2, tail, out, workspace, *vecs)
     _check(lib().wino_proj_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), U2.data_ptr(),
                                     vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(), out.data_ptr(), N, Hin, Win,
@@ -638,10 +631,7 @@ def conv3x3_s2_bn_relu(inp: torch.Tensor, w_taps: torch.Tensor, bn_bias: torch.T
     if b.numel() != K or s.numel() != K:
         raise WinoError("bn vectors do not match K")
     H, W = _s2_out_hw(Hin, Win)
-    if out is None:
-        out = torch.empty((N, H + 2, W + 2, K), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, H + 2, W + 2, K), "out")
+    out = _output(out, (N, H + 2, W + 2, K), x.device)
     _on_current_device(x, w, b, s, out)
     _check(lib().wino_conv3x3_s2_bn_relu_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
                                             N, Hin, Win, C, K, int(relu), _stream()), "wino_conv3x3_s2_bn_relu_hw")
@@ -689,17 +679,8 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
     vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
     if any(v.numel() != Cm for v in vecs):
         raise WinoError("bn1 / bn2 vectors must have Cm values")
-    need = lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    else:
-        _out(workspace, None, "workspace")
-        if workspace.numel() * 4 < need:
-            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
-    if out is None:
-        out = torch.empty((N, H, W, C4), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, H, W, C4), "out")
+    workspace = _workspace(workspace, lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm), x.device)
+    out = _output(out, (N, H, W, C4), x.device)
     _on_current_device(x, w1, w2, tail, out, workspace, *vecs)
     _check(lib().wino_proj_block_v15_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
                                         w2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
@@ -722,10 +703,7 @@ def conv3x3_bn_add_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tenso
     if U.numel() != 16 * C * K or s.numel() != K:
         raise WinoError("U / bn vectors do not match C, K")
     r = _out(residual, (N, Hp, Wp, K), "residual")
-    if out is None:
-        out = torch.empty((N, Hp, Wp, K), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, Hp, Wp, K), "out")
+    out = _output(out, (N, Hp, Wp, K), x.device)
     _on_current_device(x, U, b, s, r, out)
     _check(lib().wino_conv3x3_bn_add_relu_hw(x.data_ptr(), U.data_ptr(), b.data_ptr(), s.data_ptr(), r.data_ptr(),
                                              out.data_ptr(), N, Hp - 2, Wp - 2, C, K, int(relu), _stream()),
@@ -754,17 +732,8 @@ def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
     vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
     if any(v.numel() != C for v in vecs):
         raise WinoError("bn1 / bn2 vectors must have C values")
-    need = lib().wino_basic_block_workspace_bytes_hw(N, Hp - 2, Wp - 2, C)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    else:
-        _out(workspace, None, "workspace")
-        if workspace.numel() * 4 < need:
-            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
-    if out is None:
-        out = torch.empty((N, Hp, Wp, C), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, Hp, Wp, C), "out")
+    workspace = _workspace(workspace, lib().wino_basic_block_workspace_bytes_hw(N, Hp - 2, Wp - 2, C), x.device)
+    out = _output(out, (N, Hp, Wp, C), x.device)
     _on_current_device(x, U1, U2, out, workspace, *vecs)
     _check(lib().wino_basic_block_hw(x.data_ptr(), U1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
                                      U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), out.data_ptr(),
@@ -816,8 +785,8 @@ def conv3x3_s2_proj(x, packed, t1=None, sc=None):
     x, packed = _dev(x, "x"), _dev(packed, "packed")
     H, W = _s2_out_hw(Hin, Win)
     shape = (N, H + 2, W + 2, K)
-    t1 = torch.empty(shape, dtype=torch.float32, device=x.device) if t1 is None else _out(t1, shape, "t1")
-    sc = torch.empty(shape, dtype=torch.float32, device=x.device) if sc is None else _out(sc, shape, "sc")
+    t1 = _output(t1, shape, x.device, "t1")
+    sc = _output(sc, shape, x.device, "sc")
     _on_current_device(x, packed, t1, sc)
     _check(lib().wino_conv3x3_s2_proj_bn_relu_hw(x.data_ptr(), packed.data_ptr(), t1.data_ptr(), sc.data_ptr(), N, Hin,
                                                  Win, C, K, _stream()), "wino_conv3x3_s2_proj_bn_relu_hw")
@@ -844,17 +813,8 @@ def basic_block_s2(x, packed, U2, bn2, out=None, workspace=None) -> torch.Tensor
     if len(vecs) != 2 or any(v.numel() != K for v in vecs):
         raise WinoError("bn2 must be (bias, scale) with K values each")
     H, W = _s2_out_hw(Hin, Win)
-    need = lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Win, K)
-    if workspace is None:
-        workspace = torch.empty(need // 4, dtype=torch.float32, device=x.device)
-    else:
-        _out(workspace, None, "workspace")
-        if workspace.numel() * 4 < need:
-            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
-    if out is None:
-        out = torch.empty((N, H + 2, W + 2, K), dtype=torch.float32, device=x.device)
-    else:
-        _out(out, (N, H + 2, W + 2, K), "out")
+    workspace = _workspace(workspace, lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Win, K), x.device)
+    out = _output(out, (N, H + 2, W + 2, K), x.device)
     _on_current_device(x, packed, U2, out, workspace, *vecs)
     _check(lib().wino_basic_block_s2_hw(x.data_ptr(), packed.data_ptr(), U2.data_ptr(), vecs[0].data_ptr(),
                                         vecs[1].data_ptr(), out.data_ptr(), N, Hin, Win, C, K, workspace.data_ptr(),
@@ -912,7 +872,7 @@ def stem(x, packed, out_padded: bool = False, out=None) -> torch.Tensor:
     Hp, Wp = stem_out_hw(H, W)
     p = 2 if out_padded else 0
     shape = (N, Hp + p, Wp + p, K)
-    out = torch.empty(shape, dtype=torch.float32, device=x.device) if out is None else _out(out, shape, "out")
+    out = _output(out, shape, x.device)
     _on_current_device(x, packed, out)
     _check(lib().wino_stem_hw(x.data_ptr(), packed.data_ptr(), out.data_ptr(), N, H, W, K, int(bool(out_padded)),
                               _stream()), "wino_stem_hw")
@@ -954,14 +914,8 @@ def avgpool_fc(feat, packed, classes: int, in_padded: bool = False, out=None, wo
     n = lib().wino_head_elems(C, classes)
     if n == 0 or packed.numel() != n:
         raise WinoError(f"packed does not match C={C} classes={classes}: pack it with head_pack")
-    need = lib().wino_head_workspace_bytes(N, C, classes)
-    if workspace is None:
-        workspace = torch.empty((need + 3) // 4, dtype=torch.float32, device=f.device)
-    else:
-        _out(workspace, None, "workspace")
-        if workspace.numel() * 4 < need:
-            raise WinoError(f"workspace too small: {workspace.numel() * 4} bytes, need {need}")
-    out = torch.empty((N, classes), dtype=torch.float32, device=f.device) if out is None else _out(out, (N, classes), "out")
+    workspace = _workspace(workspace, lib().wino_head_workspace_bytes(N, C, classes), f.device)
+    out = _output(out, (N, classes), f.device)
     _on_current_device(f, packed, out, workspace)
     _check(lib().wino_avgpool_fc_hw(f.data_ptr(), packed.data_ptr(), out.data_ptr(), N, H, W, C, classes,
                                     int(bool(in_padded)), workspace.data_ptr(), workspace.numel() * 4, _stream()),

@@ -38,22 +38,7 @@ __global__ void s2_proj_pack_kernel(const float* __restrict__ w_taps, const floa
   packed[i] = v;
 }
 
-// [p, p + bytes) and [q, q + bytes_q) share a byte
-bool overlaps(const void* p, size_t bytes, const void* q, size_t bytes_q) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + bytes_q && b < a + bytes;
-}
-
-size_t padded_bytes(int N, int H, int W, int C) { return (size_t)N * (H + 2) * (W + 2) * C * sizeof(float); }
 size_t packed_bytes(int C, int K) { return (size_t)(10 * (size_t)C + 4) * K * sizeof(float); }
-
-// any two of the n regions share a byte
-bool any_overlap(std::initializer_list<std::pair<const void*, size_t>> r) {
-  for (auto i = r.begin(); i != r.end(); ++i)
-    for (auto j = i + 1; j != r.end(); ++j)
-      if (overlaps(i->first, i->second, j->first, j->second)) return true;
-  return false;
-}
 
 // The fused layer's launch: the plain stride-2 layer's plan and operands, plus the shortcut's output in R
 int launch_s2_proj(const float* in, const float* packed, float* t1, float* sc, const S2Geom& g, hipStream_t s) {
@@ -65,14 +50,6 @@ int launch_s2_proj(const float* in, const float* packed, float* t1, float* sc, c
                                  {in, packed, bn, bn + g.K, sc, t1, g.M, 9 * g.C, g.K, WINO_RELU | WINO_C_PADDED,
                                   make_padgeo(g.H, g.W), xg},
                                  s);
-}
-
-// the block's second conv, K -> K on the H x W grid: the residual 3x3's shape limits (host-side only; any batch goes,
-// the 3x3 launcher splits one that one launch cannot address)
-int check_second_conv(const S2Geom& g) {
-  int grid = 0, rounds = 0, ipi = 0;
-  long tail = 0;
-  return wino_conv3x3_plan(1, g.H, g.W, g.K, g.K, 1, &grid, &rounds, &tail, &ipi);
 }
 
 }  // namespace
@@ -89,8 +66,8 @@ size_t wino_s2_proj_elems(int C, int K) {
 
 int wino_s2_proj_pack(const float* w_taps, const float* bn1Bias, const float* bn1Scale, const float* wd,
                       const float* bndBias, const float* bndScale, float* packed, int C, int K, wino_stream_t s) {
-  if (!w_taps || !bn1Bias || !bn1Scale || !wd || !bndBias || !bndScale || !packed) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(packed)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(w_taps, bn1Bias, bn1Scale, wd, bndBias, bndScale, packed)) return rc;
+  if (int rc = check_aligned16(packed)) return rc;
   if (C <= 0 || K <= 0 || C % 32 || K % 64) {
     set_error("stride-2 projection pack: unsupported channels C=%d K=%d (need C %% 32 == 0, K %% 64 == 0)", C, K);
     return WINO_E_SHAPE;
@@ -103,8 +80,8 @@ int wino_s2_proj_pack(const float* w_taps, const float* bn1Bias, const float* bn
 
 int wino_conv3x3_s2_proj_bn_relu_hw(const float* in, const float* packed, float* t1, float* sc, int N, int Hin, int Win,
                                     int C, int K, wino_stream_t s) {
-  if (!in || !packed || !t1 || !sc) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(in, packed, t1, sc)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, packed, t1, sc)) return rc;
+  if (int rc = check_aligned16(in, packed, t1, sc)) return rc;
   S2Geom g;
   if (int rc = check_s2(N, Hin, Win, C, K, &g)) return rc;
   const size_t in_b = padded_bytes(N, Hin, Win, C), out_b = padded_bytes(N, g.H, g.W, K);
@@ -123,7 +100,7 @@ size_t wino_basic_block_s2_workspace_bytes_hw(int N, int Hin, int Win, int K) {
 int wino_basic_block_s2_prepare_hw(int N, int Hin, int Win, int C, int K, wino_stream_t s) {
   S2Geom g;
   if (int rc = check_s2(N, Hin, Win, C, K, &g)) return rc;
-  if (int rc = check_second_conv(g)) return rc;
+  if (int rc = check_conv3x3_dims(g.H, g.W, K, K)) return rc;   // the second conv, K -> K on the H x W grid
   // the fused layer's scratch is the plain stride-2 layer's (same plan), the second launch's the plain K -> K 3x3's
   if (int rc = wino_conv3x3_s2_prepare_hw(N, Hin, Win, C, K, s)) return rc;
   return wino_conv3x3_prepare_hw(N, g.H, g.W, K, K, s);
@@ -132,16 +109,13 @@ int wino_basic_block_s2_prepare_hw(int N, int Hin, int Win, int C, int K, wino_s
 int wino_basic_block_s2_hw(const float* x, const float* packed, const float* U2, const float* bn2Bias,
                            const float* bn2Scale, float* out, int N, int Hin, int Win, int C, int K, void* workspace,
                            size_t workspace_bytes, wino_stream_t s) {
-  if (!x || !packed || !U2 || !bn2Bias || !bn2Scale || !out || !workspace) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(x, packed, U2, out) || misaligned16(workspace)) {
-    set_error("tensor pointers must be 16-byte aligned");
-    return WINO_E_ARG;
-  }
+  if (int rc = check_nonnull(x, packed, U2, bn2Bias, bn2Scale, out, workspace)) return rc;
+  if (int rc = check_aligned16(x, packed, U2, out, workspace)) return rc;
   S2Geom g;
   if (int rc = check_s2(N, Hin, Win, C, K, &g)) return rc;
-  if (int rc = check_second_conv(g)) return rc;
+  if (int rc = check_conv3x3_dims(g.H, g.W, K, K)) return rc;   // the second conv
   const size_t need = wino_basic_block_s2_workspace_bytes_hw(N, Hin, Win, K);
-  if (workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   if (any_overlap({{x, padded_bytes(N, Hin, Win, C)}, {packed, packed_bytes(C, K)}, {out, need}, {workspace, need}})) {
     set_error("x, packed, out and the workspace must not overlap");
     return WINO_E_ARG;

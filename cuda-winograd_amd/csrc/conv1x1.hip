@@ -62,7 +62,7 @@ using namespace wino;
 // descriptor (32-bit byte offsets)
 static inline bool bad_1x1_dims(int Cin, int Kout) {
   return Cin <= 0 || Kout <= 0 || (Cin % 32) != 0 || (Kout % 64) != 0 ||
-         (unsigned long long)Cin * (unsigned long long)Kout * sizeof(float) >= (1ull << 32);
+         (unsigned long long)Cin * (unsigned long long)Kout * sizeof(float) >= FOUR_GIB;
 }
 static inline bool four_waves(int Cin, int Kout) { return Kout <= 128 || Cin <= 128 || (Kout % 128) != 0; }
 // The shape check of the 1x1 entry points; `row_tiles`: also the tiled kernel's limit of 2^24 row tiles.
@@ -72,6 +72,18 @@ static int check_1x1(long M, int Cin, int Kout, bool row_tiles = true) {
     return WINO_E_SHAPE;
   }
   if (row_tiles && (M + BM - 1) / BM > (1L << 24)) { set_error("M too large"); return WINO_E_SHAPE; }
+  return WINO_OK;
+}
+// The padded layouts' limits (WINO_A_PADDED / WINO_C_PADDED): the feature map, M = N*H*W, and the ring pass, which
+// counts 16-byte units of the output in 32 bits.
+static int check_1x1_padded(long M, int H, int W, int Kout) {
+  if (H < 1 || W < 1 || H > 4094 || W > 4094) { set_error("unsupported feature map %dx%d", H, W); return WINO_E_SHAPE; }
+  if ((M % ((long)H * W)) != 0) {
+    set_error("padded layouts need M = N*%d*%d, got M=%ld", H, W, M);
+    return WINO_E_SHAPE;
+  }
+  const unsigned long long ring_units = (unsigned long long)(M / ((long)H * W)) * (2ull * (W + 2) + 2ull * H) * (Kout / 4);
+  if (ring_units >= FOUR_GIB) { set_error("padded output too large for one launch"); return WINO_E_SHAPE; }
   return WINO_OK;
 }
 
@@ -282,21 +294,14 @@ int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int 
 static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const float* bnScale,
                       const float* residual, float* C, long M, int H, int W, int Cin, int Kout, int flags,
                       wino_stream_t s) {
-  if (!A || !B || !bnBias || !bnScale || !C) { set_error("NULL pointer"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(A, B, bnBias, bnScale, C)) return rc;
   if ((flags & WINO_ADD_RESIDUAL) && !residual) { set_error("WINO_ADD_RESIDUAL without residual"); return WINO_E_ARG; }
-  if (misaligned16(A, B, C, residual)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_aligned16(A, B, C, residual)) return rc;
   if (flags & ~(WINO_RELU | WINO_A_PADDED | WINO_C_PADDED | WINO_ADD_RESIDUAL)) { set_error("unknown flag bits 0x%x", flags); return WINO_E_ARG; }
   if (int rc = check_1x1(M, Cin, Kout)) return rc;
   PadGeo pg = make_padgeo(WINO_PQ, WINO_PQ);
   if (flags & (WINO_A_PADDED | WINO_C_PADDED)) {
-    if (H < 1 || W < 1 || H > 4094 || W > 4094) { set_error("unsupported feature map %dx%d", H, W); return WINO_E_SHAPE; }
-    if ((M % ((long)H * W)) != 0) {
-      set_error("padded layouts need M = N*%d*%d, got M=%ld", H, W, M);
-      return WINO_E_SHAPE;
-    }
-    // the ring pass counts 16-byte units in 32 bits
-    const unsigned long long ring_units = (unsigned long long)(M / ((long)H * W)) * (2ull * (W + 2) + 2ull * H) * (Kout / 4);
-    if (ring_units >= (1ull << 32)) { set_error("padded output too large for one launch"); return WINO_E_SHAPE; }
+    if (int rc = check_1x1_padded(M, H, W, Kout)) return rc;
     pg = make_padgeo(H, W);
   }
   int dev = 0;
@@ -305,13 +310,17 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
   return launch_1x1<A_PLAIN>(p, dev, {A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg}, (hipStream_t)s);
 }
 
-// The bottleneck block's checks before its first launch: batch and feature map, and the 3x3's shape limits (its filter
-// matrix among them), so that a shape the middle layer refuses launches nothing (host-side only)
-static int check_residual_block(int N, int H, int W, int Cm) {
+// The bottleneck block's shape checks before its first launch: batch and feature map, both 1x1 layers (C4 -> Cm
+// writing padded t1, Cm -> C4 reading padded t2) and the 3x3's limits (its filter matrix among them), so that a shape
+// any of its layers refuses launches nothing
+static int check_residual_block(int N, int H, int W, int C4, int Cm) {
   if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
-  int grid = 0, rounds = 0, ipi = 0;
-  long tail = 0;
-  return wino_conv3x3_plan(1, H, W, Cm, Cm, 1, &grid, &rounds, &tail, &ipi);
+  const long M = (long)N * H * W;
+  if (int rc = check_1x1(M, C4, Cm)) return rc;
+  if (int rc = check_1x1_padded(M, H, W, Cm)) return rc;
+  if (int rc = check_1x1(M, Cm, C4)) return rc;
+  if (int rc = check_1x1_padded(M, H, W, C4)) return rc;
+  return check_conv3x3_dims(H, W, Cm, Cm);
 }
 
 extern "C" {
@@ -399,13 +408,19 @@ int wino_residual_block_hw(const float* x, const float* w1, const float* bn1Bias
                            const float* w3, const float* bn3Bias, const float* bn3Scale, float* out,
                            int N, int H, int W, int C4, int Cm, void* workspace, size_t workspace_bytes,
                            wino_stream_t s) {
-  if (int rc = check_residual_block(N, H, W, Cm)) return rc;
-  if (!workspace || workspace_bytes < wino_residual_block_workspace_bytes_hw(N, H, W, Cm)) {
-    set_error("workspace too small: need %zu bytes", wino_residual_block_workspace_bytes_hw(N, H, W, Cm));
+  if (int rc = check_nonnull(x, w1, bn1Bias, bn1Scale, U2, bn2Bias, bn2Scale, w3, bn3Bias, bn3Scale, out)) return rc;
+  if (int rc = check_aligned16(x, w1, U2, w3, out, workspace)) return rc;
+  if (int rc = check_residual_block(N, H, W, C4, Cm)) return rc;
+  const size_t need = wino_residual_block_workspace_bytes_hw(N, H, W, Cm);
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
+  // x is read again as the residual by the third launch, after the first two have written the workspace
+  const size_t act_b = (size_t)N * H * W * C4 * sizeof(float);
+  if (overlaps(workspace, need, x, act_b) || overlaps(workspace, need, out, act_b)) {
+    set_error("the workspace overlaps x or out");
     return WINO_E_ARG;
   }
   float* t1 = (float*)workspace;
-  float* t2 = t1 + (size_t)N * (H + 2) * (W + 2) * Cm;
+  float* t2 = (float*)((char*)workspace + padded_bytes(N, H, W, Cm));
   int rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, H, W, C4, Cm, WINO_RELU | WINO_C_PADDED, s);
   if (rc) return rc;
   rc = wino_conv3x3_bn_relu_hw(t1, U2, bn2Bias, bn2Scale, t2, N, H, W, Cm, Cm, 1, s);
@@ -415,7 +430,7 @@ int wino_residual_block_hw(const float* x, const float* w1, const float* bn1Bias
 }
 
 int wino_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, wino_stream_t s) {
-  if (int rc = check_residual_block(N, H, W, Cm)) return rc;
+  if (int rc = check_residual_block(N, H, W, C4, Cm)) return rc;
   const long M = (long)N * H * W;
   if (int rc = wino_conv1x1_prepare(M, C4, Cm, s)) return rc;
   if (int rc = wino_conv3x3_prepare_hw(N, H, W, Cm, Cm, s)) return rc;
@@ -427,7 +442,7 @@ int wino_residual_block_prepare(int N, int C4, int Cm, wino_stream_t s) {
 }
 
 size_t wino_residual_block_workspace_bytes_hw(int N, int H, int W, int Cm) {
-  return (size_t)2 * N * (H + 2) * (W + 2) * Cm * sizeof(float);
+  return 2 * padded_bytes(N, H, W, Cm);
 }
 
 int wino_residual_block(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
@@ -446,7 +461,7 @@ size_t wino_residual_block_workspace_bytes(int N, int Cm) {
 int wino_conv1x1_direct(const float* A, const float* B, const float* bnBias,
                         const float* bnScale, float* C, long M, int Cin, int Kout, int relu,
                         wino_stream_t s) {
-  if (!A || !B || !bnBias || !bnScale || !C) { set_error("NULL pointer"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(A, B, bnBias, bnScale, C)) return rc;
   if (M < 1 || Cin <= 0 || Kout <= 0) { set_error("bad 1x1 shape"); return WINO_E_SHAPE; }
   const long total = M * Kout;
   hipLaunchKernelGGL(conv1x1_direct_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,

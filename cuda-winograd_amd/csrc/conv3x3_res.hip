@@ -13,19 +13,11 @@ using namespace wino;
 
 namespace {
 
-// [p, p + bytes) and [q, q + bytes_q) share a byte
-bool overlaps(const void* p, size_t bytes, const void* q, size_t bytes_q) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + bytes_q && b < a + bytes;
-}
-
-size_t padded_bytes(int N, int H, int W, int C) { return (size_t)N * (H + 2) * (W + 2) * C * sizeof(float); }
-
 // the residual layer's checks, all before any device query: pointers, shape, overlap (out == residual is allowed)
 int check_res(const float* in, const float* U, const float* bnBias, const float* bnScale, const float* residual,
               const float* out, int N, int H, int W, int C, int K) {
-  if (!in || !U || !bnBias || !bnScale || !residual || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(in, U, residual, out)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, U, bnBias, bnScale, residual, out)) return rc;
+  if (int rc = check_aligned16(in, U, residual, out)) return rc;
   if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
   if (N < 1) { set_error("bad batch N=%d", N); return WINO_E_SHAPE; }
   const size_t in_b = padded_bytes(N, H, W, C), out_b = padded_bytes(N, H, W, K);
@@ -64,18 +56,12 @@ int wino_basic_block_prepare_hw(int N, int H, int W, int C, wino_stream_t s) {
 int wino_basic_block_hw(const float* x, const float* U1, const float* bn1Bias, const float* bn1Scale,
                         const float* U2, const float* bn2Bias, const float* bn2Scale, float* out,
                         int N, int H, int W, int C, void* workspace, size_t workspace_bytes, wino_stream_t s) {
-  if (!x || !U1 || !bn1Bias || !bn1Scale || !U2 || !bn2Bias || !bn2Scale || !out || !workspace) {
-    set_error("NULL pointer");
-    return WINO_E_ARG;
-  }
-  if (misaligned16(x, U1, U2, out) || misaligned16(workspace)) {
-    set_error("tensor pointers must be 16-byte aligned");
-    return WINO_E_ARG;
-  }
+  if (int rc = check_nonnull(x, U1, bn1Bias, bn1Scale, U2, bn2Bias, bn2Scale, out, workspace)) return rc;
+  if (int rc = check_aligned16(x, U1, U2, out, workspace)) return rc;
   if (int rc = check_conv3x3_dims(H, W, C, C)) return rc;
   if (N < 1) { set_error("bad batch N=%d", N); return WINO_E_SHAPE; }
   const size_t need = wino_basic_block_workspace_bytes_hw(N, H, W, C);
-  if (workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   if (overlaps(workspace, need, x, need) || overlaps(workspace, need, out, need)) {
     set_error("the workspace overlaps x or out");
     return WINO_E_ARG;

@@ -7,16 +7,13 @@
 // operand form A_TAPS (conv1x1_kernel.h): the same LDS-DMA pipeline and MFMA loop with one scalar A offset per k-step,
 // the same latency / tiled / stream-K forms, the same planner (plan_1x1 on the GEMM's shape, its latency-or-tiled
 // choice re-priced for the tap form: plan_s2) and launcher (launch_1x1, conv1x1_launch.h).  This file instantiates that form and no other.
-// check_s2 and plan_s2 are shared with basic_block_s2.hip (conv3x3_s2.h).
+// check_s2 and plan_s2 are shared with basic_block_s2.hip, check_s2 also with proj_block.hip (conv3x3_s2.h).
 #include "conv3x3_s2.h"
 
 namespace wino {
 
 using namespace gemm1x1;
 
-namespace {
-constexpr unsigned long long FOUR_GIB = 1ull << 32;
-}  // namespace
 // The layer's geometry, checked once.  Every 32-bit quantity of the tap addressing is bounded here: the pixel row
 // index (M < 2^31, one padded input image < 2^31 pixels), a 112-row tile's buffer-descriptor window over the padded
 // input, B's descriptor and the ring pass's 16-byte units.
@@ -73,8 +70,8 @@ extern "C" {
 
 int wino_conv3x3_s2_bn_relu_hw(const float* in, const float* w_taps, const float* bnBias, const float* bnScale,
                                float* out, int N, int Hin, int Win, int C, int K, int relu, wino_stream_t s) {
-  if (!in || !w_taps || !bnBias || !bnScale || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(in, w_taps, out)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, w_taps, bnBias, bnScale, out)) return rc;
+  if (int rc = check_aligned16(in, w_taps, out)) return rc;
   S2Geom g;
   if (int rc = check_s2(N, Hin, Win, C, K, &g)) return rc;
   int dev = 0, cus = 0;

@@ -48,7 +48,7 @@ using namespace wino;
 
 static int direct_launch(const float* in, const float* w_kcrs, const float* bnBias, const float* bnScale,
                          float* out, int N, int H, int W, int C, int K, int relu, wino_stream_t s) {
-  if (!in || !w_kcrs || !bnBias || !bnScale || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, w_kcrs, bnBias, bnScale, out)) return rc;
   if (N < 1 || C < 1 || K < 1 || H < 1 || W < 1) { set_error("bad shape"); return WINO_E_SHAPE; }
   const long total = (long)N * (H + 2) * (W + 2) * K;
   if ((total + 255) / 256 > 0x7fffffffL) { set_error("too large"); return WINO_E_SHAPE; }

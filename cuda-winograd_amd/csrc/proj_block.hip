@@ -16,7 +16,7 @@
 //   t2  = relu(bn2(conv3x3_s2(t1, w2_taps)))     padded [N][H+2][W+2][Cm]       (workspace; conv3x3_s2.hip)
 //   out = the same fused tail as v1 at stride 2
 // so this file instantiates no kernel for it.
-#include "conv1x1_launch.h"
+#include "conv3x3_s2.h"
 
 namespace wino {
 namespace {
@@ -49,7 +49,6 @@ struct ProjGeom {
   int N, Hin, Win, Cin, Cm, C4, s, H, W;
   long M;
 };
-constexpr unsigned long long FOUR_GIB = 1ull << 32;
 static int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, ProjGeom* g) {
   if (stride != 1 && stride != 2) { set_error("projection block: stride %d (need 1 or 2)", stride); return WINO_E_ARG; }
   if (N < 1 || Hin < 1 || Win < 1) { set_error("projection block: bad N=%d Hin=%d Win=%d", N, Hin, Win); return WINO_E_SHAPE; }
@@ -80,11 +79,16 @@ static int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stri
   return WINO_OK;
 }
 // the v1 block's middle layer is the Winograd 3x3 (Cm -> Cm at H x W): its shape limits, the filter matrix's among
-// them, before anything is launched (host-side only)
-static int check_proj_3x3(const ProjGeom& g) {
-  int grid = 0, rounds = 0, ipi = 0;
-  long tail = 0;
-  return wino_conv3x3_plan(1, g.H, g.W, g.Cm, g.Cm, 1, &grid, &rounds, &tail, &ipi);
+// them, before anything is launched
+static int check_proj_3x3(const ProjGeom& g) { return check_conv3x3_dims(g.H, g.W, g.Cm, g.Cm); }
+// the workspace holds t1 and t2, written before the tail reads x (its shortcut) and writes out: it must overlap neither
+static int check_ws_overlap(const ProjGeom& g, const void* x, const void* out, const void* workspace, size_t need) {
+  const size_t x_b = (size_t)g.N * g.Hin * g.Win * g.Cin * sizeof(float), out_b = (size_t)g.M * g.C4 * sizeof(float);
+  if (overlaps(workspace, need, x, x_b) || overlaps(workspace, need, out, out_b)) {
+    set_error("the workspace overlaps x or out");
+    return WINO_E_ARG;
+  }
+  return WINO_OK;
 }
 static ProjGeo proj_geo(const ProjGeom& g, const float* x) {
   return ProjGeo{x, (unsigned)g.Hin * (unsigned)g.Win, (unsigned)(g.s * g.Win), (unsigned)g.s, g.Cin, g.Cm};
@@ -111,8 +115,8 @@ size_t wino_proj_tail_elems(int Cm, int Cin, int C4) {
 
 int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3Scale, const float* wp,
                         const float* bnpBias, const float* bnpScale, float* packed, int Cm, int Cin, int C4, wino_stream_t s) {
-  if (!w3 || !bn3Bias || !bn3Scale || !wp || !bnpBias || !bnpScale || !packed) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(packed)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(w3, bn3Bias, bn3Scale, wp, bnpBias, bnpScale, packed)) return rc;
+  if (int rc = check_aligned16(packed)) return rc;
   if (Cm <= 0 || Cin <= 0 || C4 <= 0 || Cin % 32 || Cm % 64 || C4 % 64 ||
       (unsigned long long)(Cm + Cin) * C4 * sizeof(float) >= FOUR_GIB) {
     set_error("projection tail: unsupported shape Cm=%d Cin=%d C4=%d (need Cin %% 32 == 0, Cm %% 64 == 0, C4 %% 64 == 0)",
@@ -127,7 +131,7 @@ int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3S
 
 size_t wino_proj_block_workspace_bytes_hw(int N, int H, int W, int Cm) {
   if (N < 1 || H < 1 || W < 1 || Cm < 1) return 0;
-  return (size_t)2 * N * (H + 2) * (W + 2) * Cm * sizeof(float);
+  return 2 * padded_bytes(N, H, W, Cm);
 }
 
 int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, int cus, int* first_form,
@@ -168,32 +172,27 @@ static int check_v15(int N, int Hin, int Win, int Cin, int Cm, int C4, ProjGeom*
     set_error("v1.5 projection block: the first 1x1 at %dx%d x %d images is too large for one launch", Hin, Win, N);
     return WINO_E_SHAPE;
   }
-  int form = 0;
-  return wino_conv3x3_s2_plan(N, Hin, Win, Cm, Cm, 1, &form);   // (host-side: the 3x3's shape check)
+  S2Geom g2;
+  return check_s2(N, Hin, Win, Cm, Cm, &g2);
 }
 
 int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale, const float* U2,
                        const float* bn2Bias, const float* bn2Scale, const float* tail_packed, float* out, int N, int Hin,
                        int Win, int Cin, int Cm, int C4, int stride, void* workspace, size_t workspace_bytes,
                        wino_stream_t s) {
-  if (!x || !w1 || !bn1Bias || !bn1Scale || !U2 || !bn2Bias || !bn2Scale || !tail_packed || !out) {
-    set_error("NULL pointer");
-    return WINO_E_ARG;
-  }
-  if (misaligned16(x, w1, U2, out) || misaligned16(tail_packed, workspace)) {
-    set_error("tensor pointers must be 16-byte aligned");
-    return WINO_E_ARG;
-  }
+  if (int rc = check_nonnull(x, w1, bn1Bias, bn1Scale, U2, bn2Bias, bn2Scale, tail_packed, out)) return rc;
+  if (int rc = check_aligned16(x, w1, U2, tail_packed, out, workspace)) return rc;
   ProjGeom g;
   if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
   if (int rc = check_proj_3x3(g)) return rc;
   const size_t need = wino_proj_block_workspace_bytes_hw(N, g.H, g.W, Cm);
-  if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
+  if (int rc = check_ws_overlap(g, x, out, workspace, need)) return rc;
   int dev = 0, cus = 0;
   if (int rc = current_device(&dev, &cus)) return rc;
   const Knobs kn = knobs();
   float* t1 = (float*)workspace;
-  float* t2 = t1 + (size_t)N * (g.H + 2) * (g.W + 2) * Cm;
+  float* t2 = (float*)((char*)workspace + padded_bytes(N, g.H, g.W, Cm));
   const PadGeo pg = make_padgeo(g.H, g.W);
   const ProjGeo xg = proj_geo(g, x);
   const hipStream_t hs = (hipStream_t)s;
@@ -214,8 +213,7 @@ int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, co
 
 size_t wino_proj_block_v15_workspace_bytes_hw(int N, int Hin, int Win, int Cm) {
   if (N < 1 || Hin < 1 || Win < 1 || Cm < 1) return 0;
-  const size_t H = (size_t)(Hin - 1) / 2 + 1, W = (size_t)(Win - 1) / 2 + 1;
-  return (size_t)N * ((size_t)(Hin + 2) * (Win + 2) + (H + 2) * (W + 2)) * Cm * sizeof(float);
+  return padded_bytes(N, Hin, Win, Cm) + padded_bytes(N, (Hin - 1) / 2 + 1, (Win - 1) / 2 + 1, Cm);
 }
 
 int wino_proj_block_v15_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, wino_stream_t s) {
@@ -234,22 +232,17 @@ int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias
                            const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
                            float* out, int N, int Hin, int Win, int Cin, int Cm, int C4, void* workspace,
                            size_t workspace_bytes, wino_stream_t s) {
-  if (!x || !w1 || !bn1Bias || !bn1Scale || !w2_taps || !bn2Bias || !bn2Scale || !tail_packed || !out) {
-    set_error("NULL pointer");
-    return WINO_E_ARG;
-  }
-  if (misaligned16(x, w1, w2_taps, out) || misaligned16(tail_packed, workspace)) {
-    set_error("tensor pointers must be 16-byte aligned");
-    return WINO_E_ARG;
-  }
+  if (int rc = check_nonnull(x, w1, bn1Bias, bn1Scale, w2_taps, bn2Bias, bn2Scale, tail_packed, out)) return rc;
+  if (int rc = check_aligned16(x, w1, w2_taps, tail_packed, out, workspace)) return rc;
   ProjGeom g;
   if (int rc = check_v15(N, Hin, Win, Cin, Cm, C4, &g)) return rc;
   const size_t need = wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm);
-  if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
+  if (int rc = check_ws_overlap(g, x, out, workspace, need)) return rc;
   int dev = 0, cus = 0;
   if (int rc = current_device(&dev, &cus)) return rc;
   float* t1 = (float*)workspace;
-  float* t2 = t1 + (size_t)N * (Hin + 2) * (Win + 2) * Cm;
+  float* t2 = (float*)((char*)workspace + padded_bytes(N, Hin, Win, Cm));
   int rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, Hin, Win, Cin, Cm, WINO_RELU | WINO_C_PADDED, s);
   if (rc) return rc;
   rc = wino_conv3x3_s2_bn_relu_hw(t1, w2_taps, bn2Bias, bn2Scale, t2, N, Hin, Win, Cm, Cm, 1, s);

@@ -250,19 +250,6 @@ int launch_stem(const float* x, const float* packed, float* out, int N, StemGeo 
   return launch_status("stem_kernel");
 }
 
-// [p, p + bytes) and [q, q + bytes_q) share a byte
-bool overlaps(const void* p, size_t bytes, const void* q, size_t bytes_q) {
-  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
-  return a < b + bytes_q && b < a + bytes;
-}
-
-bool any_overlap(std::initializer_list<std::pair<const void*, size_t>> r) {
-  for (auto i = r.begin(); i != r.end(); ++i)
-    for (auto j = i + 1; j != r.end(); ++j)
-      if (overlaps(i->first, i->second, j->first, j->second)) return true;
-  return false;
-}
-
 // ---- head ----
 int head_cols(int classes) { return (classes + 63) / 64 * 64; }
 size_t pooled_bytes(int N, int C) { return ((size_t)N * C * sizeof(float) + 255) / 256 * 256; }
@@ -337,8 +324,8 @@ size_t wino_stem_filter_elems(int K) {
 
 int wino_stem_filter_pack(const float* w, const float* bnBias, const float* bnScale, float* packed, int K,
                           wino_stream_t s) {
-  if (!w || !bnBias || !bnScale || !packed) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(packed)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(w, bnBias, bnScale, packed)) return rc;
+  if (int rc = check_aligned16(packed)) return rc;
   if (K < 64 || K % 64 || K > (1 << 20)) { set_error("stem pack: unsupported K=%d (need K %% 64 == 0)", K); return WINO_E_SHAPE; }
   const int total = (int)stem_elems(K);
   hipLaunchKernelGGL(stem_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)s, w, bnBias,
@@ -356,8 +343,8 @@ int wino_stem_plan(int N, int H, int W, int K, int cus, int* form) {
 
 int wino_stem_hw(const float* x, const float* packed, float* out, int N, int H, int W, int K, int out_padded,
                  wino_stream_t s) {
-  if (!x || !packed || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(x, packed, out)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(x, packed, out)) return rc;
+  if (int rc = check_aligned16(x, packed, out)) return rc;
   StemGeo g;
   if (int rc = check_stem(N, H, W, K, out_padded, &g)) return rc;
   const size_t in_b = (size_t)N * 3 * H * W * sizeof(float);
@@ -379,8 +366,8 @@ size_t wino_head_elems(int C, int classes) {
 }
 
 int wino_head_pack(const float* wfc, const float* bfc, float* packed, int C, int classes, wino_stream_t s) {
-  if (!wfc || !bfc || !packed) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(packed)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(wfc, bfc, packed)) return rc;
+  if (int rc = check_aligned16(packed)) return rc;
   if (!wino_head_elems(C, classes) || wino_head_elems(C, classes) >= (1ul << 31)) {
     set_error("head pack: unsupported C=%d classes=%d (need C %% 32 == 0, classes >= 1)", C, classes);
     return WINO_E_SHAPE;
@@ -403,11 +390,11 @@ int wino_head_prepare(int N, int C, int classes, wino_stream_t s) {
 
 int wino_avgpool_fc_hw(const float* feat, const float* packed, float* out, int N, int H, int W, int C, int classes,
                        int in_padded, void* workspace, size_t workspace_bytes, wino_stream_t s) {
-  if (!feat || !packed || !out || !workspace) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(feat, packed, out, workspace)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(feat, packed, out, workspace)) return rc;
+  if (int rc = check_aligned16(feat, packed, out, workspace)) return rc;
   if (int rc = check_head(N, H, W, C, classes, in_padded)) return rc;
   const size_t need = wino_head_workspace_bytes(N, C, classes);
-  if (workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
   const int Kp = head_cols(classes);
   const size_t feat_b = (size_t)N * (H + 2 * in_padded) * (W + 2 * in_padded) * C * sizeof(float);
   if (any_overlap({{feat, feat_b}, {packed, wino_head_elems(C, classes) * sizeof(float)},

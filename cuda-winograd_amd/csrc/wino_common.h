@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <initializer_list>
+#include <utility>
 
 #include "winograd_mi355x.h"
 
@@ -19,12 +20,44 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // Thread-local last-error text behind wino_last_error_string().
 void set_error(const char* fmt, ...);
-// Every tensor pointer of the C-ABI must be 16-byte aligned (the kernels move 16 bytes per lane; hipMalloc gives 256):
-// true if any of the given pointers is not.  BN vectors are read four bytes at a time and need no more than that.
-inline bool misaligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c) |
-           reinterpret_cast<uintptr_t>(d)) & 15u) != 0;
+
+// ---- the C-ABI's argument checks (host only), shared by every entry point: each returns WINO_OK or sets the error
+// text and returns WINO_E_ARG.  Multi-launch entry points run all of them before their first device query.
+constexpr unsigned long long FOUR_GIB = 1ull << 32;
+// bytes of a padded activation [N][H+2][W+2][C]
+inline size_t padded_bytes(int N, int H, int W, int C) { return (size_t)N * (H + 2) * (W + 2) * C * sizeof(float); }
+// [p, p + bytes) and [q, q + bytes_q) share a byte
+inline bool overlaps(const void* p, size_t bytes, const void* q, size_t bytes_q) {
+  const uintptr_t a = reinterpret_cast<uintptr_t>(p), b = reinterpret_cast<uintptr_t>(q);
+  return a < b + bytes_q && b < a + bytes;
 }
+// any two of the regions share a byte
+inline bool any_overlap(std::initializer_list<std::pair<const void*, size_t>> r) {
+  for (auto i = r.begin(); i != r.end(); ++i)
+    for (auto j = i + 1; j != r.end(); ++j)
+      if (overlaps(i->first, i->second, j->first, j->second)) return true;
+  return false;
+}
+template <class... T>
+int check_nonnull(const T*... p) {
+  if (((p == nullptr) || ...)) { set_error("NULL pointer"); return WINO_E_ARG; }
+  return WINO_OK;
+}
+// Every tensor pointer of the C-ABI must be 16-byte aligned (the kernels move 16 bytes per lane; hipMalloc gives 256).
+// BN vectors are read four bytes at a time and need no more than that: they are not passed here.
+template <class... T>
+int check_aligned16(const T*... p) {
+  if ((reinterpret_cast<uintptr_t>(p) | ... | 0u) & 15u) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  return WINO_OK;
+}
+inline int check_workspace(const void* workspace, size_t workspace_bytes, size_t need) {
+  if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
+  return WINO_OK;
+}
+// The Winograd 3x3's shape limits at any batch (WINO_E_SHAPE otherwise; wino_f2_fused.hip): channels, feature map,
+// the filter matrix below 4 GiB and one image per launch.  Blocks call it for their 3x3 before anything is launched.
+int check_conv3x3_dims(int H, int W, int C, int K);
+
 int hip_fail(hipError_t e, const char* what);
 // Stream-K scratch (wino_runtime.hip): write-through slabs for partial segments and ticket
 // counters, owned by the library, one set per (device, stream) so that launches on different

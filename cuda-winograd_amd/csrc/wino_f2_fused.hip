@@ -143,8 +143,8 @@ long wino_filter_f2_index(int C, int K, int e, int c, int k) {
 }
 
 int wino_filter_transform_f2(const float* w_kcrs, float* U, int C, int K, wino_stream_t s) {
-  if (!w_kcrs || !U) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(U)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(w_kcrs, U)) return rc;
+  if (int rc = check_aligned16(U)) return rc;
   if (int rc = check_ck(C, K)) return rc;
   const int n = C * K;
   hipLaunchKernelGGL(filter_transform_f2_kernel, dim3((n + 255) / 256), dim3(256), 0,
@@ -153,8 +153,8 @@ int wino_filter_transform_f2(const float* w_kcrs, float* U, int C, int K, wino_s
 }
 
 int wino_filter_import_f4(const float* u36, float* U, int C, int K, wino_stream_t s) {
-  if (!u36 || !U) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(U)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(u36, U)) return rc;
+  if (int rc = check_aligned16(U)) return rc;
   if (int rc = check_ck(C, K)) return rc;
   const int n = C * K;
   hipLaunchKernelGGL(filter_import_f4_kernel, dim3((n + 255) / 256), dim3(256), 0,
@@ -318,6 +318,27 @@ Plan3x3 wino::plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs& 
   return p;
 }
 
+int wino::check_conv3x3_dims(int H, int W, int C, int K) {
+  if (int rc = check_ck(C, K)) return rc;
+  if (H < 1 || W < 1 || H > 4094 || W > 4094) {
+    set_error("unsupported feature map %dx%d", H, W);
+    return WINO_E_SHAPE;
+  }
+  // U [16][C][K] goes through one buffer descriptor in the throughput kernel (32-bit size and offsets); the latency
+  // kernel could address more, but both take the same shapes (one plan per shape)
+  const unsigned long long u_bytes = (unsigned long long)16 * C * K * sizeof(float);
+  if (u_bytes >= FOUR_GIB) {
+    set_error("C=%d K=%d: the filter matrix U (16 x C x K floats, %llu bytes) must stay below 4 GiB (C * K < 2^26)", C,
+              K, u_bytes);
+    return WINO_E_SHAPE;
+  }
+  if (conv3x3_batch_limit(H, W, C, K) < 1) {
+    set_error("%dx%d C=%d K=%d: one image does not fit a launch (tensors must stay below 4 GiB)", H, W, C, K);
+    return WINO_E_SHAPE;
+  }
+  return WINO_OK;
+}
+
 int wino::plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p) {
   int cus = 0;
   if (int rc = current_device(dev, &cus)) return rc;
@@ -349,7 +370,7 @@ static int conv3x3_prepare(int N, int H, int W, int C, int K, hipStream_t s) {
 static int conv3x3_clock_probe(const float* in, const float* U, const float* bnBias, const float* bnScale,
                                float* out, int N, int C, int K, unsigned long long* stamps, int* workgroups,
                                hipStream_t s) {
-  if (!in || !U || !bnBias || !bnScale || !out || !stamps || !workgroups) { set_error("NULL pointer"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, U, bnBias, bnScale, out, stamps, workgroups)) return rc;
   if (int rc = check_conv3x3(N, WINO_PQ, WINO_PQ, C, K)) return rc;
   int dev = 0;
   Plan3x3 p;
@@ -455,8 +476,8 @@ int wino_conv3x3_bn_relu(const float* in, const float* U, const float* bnBias,
 int wino_conv3x3_bn_relu_hw(const float* in, const float* U, const float* bnBias,
                             const float* bnScale, float* out, int N, int H, int W, int C, int K,
                             int relu, wino_stream_t s) {
-  if (!in || !U || !bnBias || !bnScale || !out) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(in, U, out)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, U, bnBias, bnScale, out)) return rc;
+  if (int rc = check_aligned16(in, U, out)) return rc;
   return conv3x3_launch<false>(in, U, bnBias, bnScale, nullptr, out, N, H, W, C, K, relu, (hipStream_t)s);
 }
 

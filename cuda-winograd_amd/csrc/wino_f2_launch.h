@@ -31,7 +31,7 @@ inline int sk_workspace(int dev, hipStream_t s, int G, size_t items, SkBufs* buf
 // 32 bits.  Larger batches are split by the launcher (images are independent).
 inline long long conv3x3_batch_limit(int H, int W, int C, int K) {
   const unsigned long long per_image = (unsigned long long)(H + 2) * (W + 2) * (unsigned long long)(C > K ? C : K) * sizeof(float);
-  long long n = (long long)(((1ull << 32) - 1) / per_image);
+  long long n = (long long)((FOUR_GIB - 1) / per_image);
   const long long tiles = (long long)((H + 1) / 2) * ((W + 1) / 2);
   const long long per_tb = (long long)(K / KB) * (C / BC);               // chunk iterations per 64-tile block
   const long long max_tb = ((1ll << 31) - 1) / per_tb - 1;
@@ -39,27 +39,6 @@ inline long long conv3x3_batch_limit(int H, int W, int C, int K) {
   if (n > n_iter) n = n_iter;
   if (n > (1ll << 30)) n = 1ll << 30;
   return n;
-}
-
-inline int check_conv3x3_dims(int H, int W, int C, int K) {
-  if (int rc = check_ck(C, K)) return rc;
-  if (H < 1 || W < 1 || H > 4094 || W > 4094) {
-    set_error("unsupported feature map %dx%d", H, W);
-    return WINO_E_SHAPE;
-  }
-  // U [16][C][K] goes through one buffer descriptor in the throughput kernel (32-bit size and offsets); the latency
-  // kernel could address more, but both take the same shapes (one plan per shape)
-  const unsigned long long u_bytes = (unsigned long long)16 * C * K * sizeof(float);
-  if (u_bytes >= (1ull << 32)) {
-    set_error("C=%d K=%d: the filter matrix U (16 x C x K floats, %llu bytes) must stay below 4 GiB (C * K < 2^26)", C,
-              K, u_bytes);
-    return WINO_E_SHAPE;
-  }
-  if (conv3x3_batch_limit(H, W, C, K) < 1) {
-    set_error("%dx%d C=%d K=%d: one image does not fit a launch (tensors must stay below 4 GiB)", H, W, C, K);
-    return WINO_E_SHAPE;
-  }
-  return WINO_OK;
 }
 
 // one launch

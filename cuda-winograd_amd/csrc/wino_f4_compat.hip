@@ -132,16 +132,13 @@ size_t wino_conv3x3_f4_workspace_bytes(int N, int C, int K) {
 int wino_conv3x3_f4_bn_relu(const float* in, const float* u36, const float* bnBias, const float* bnScale,
                             float* out, int N, int C, int K, int relu, void* workspace,
                             size_t workspace_bytes, wino_stream_t s) {
-  if (!in || !u36 || !bnBias || !bnScale || !out || !workspace) { set_error("NULL pointer"); return WINO_E_ARG; }
-  if (misaligned16(in, u36, out, workspace)) { set_error("tensor pointers must be 16-byte aligned"); return WINO_E_ARG; }
+  if (int rc = check_nonnull(in, u36, bnBias, bnScale, out, workspace)) return rc;
+  if (int rc = check_aligned16(in, u36, out, workspace)) return rc;
   if (N < 1 || C <= 0 || K <= 0 || (C % 32) != 0 || (K % 64) != 0) {
     set_error("unsupported F(4x4) shape N=%d C=%d K=%d (need C %% 32 == 0, K %% 64 == 0)", N, C, K);
     return WINO_E_SHAPE;
   }
-  if (workspace_bytes < wino_conv3x3_f4_workspace_bytes(N, C, K)) {
-    set_error("workspace too small: need %zu bytes", wino_conv3x3_f4_workspace_bytes(N, C, K));
-    return WINO_E_ARG;
-  }
+  if (int rc = check_workspace(workspace, workspace_bytes, wino_conv3x3_f4_workspace_bytes(N, C, K))) return rc;
   const long T = (long)N * 16;
   float* V = (float*)workspace;
   float* M = V + (size_t)36 * T * C;

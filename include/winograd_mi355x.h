@@ -58,7 +58,10 @@ extern "C" {
  * wino_s2_proj_pack, wino_conv3x3_s2_proj_bn_relu_hw, wino_basic_block_s2_workspace_bytes_hw, wino_basic_block_s2_hw,
  * wino_basic_block_s2_prepare_hw, wino_stem_filter_elems, wino_stem_filter_pack, wino_stem_hw, wino_stem_plan,
  * wino_head_elems, wino_head_pack, wino_head_workspace_bytes, wino_head_prepare, wino_avgpool_fc_hw.  The library-owned stream-K scratch is never freed or moved while its
- * stream lives (it used to be reallocated when a larger shape arrived). */
+ * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
+ * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
+ * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
+ * with a corrupted result. */
 #define WINO_ABI_VERSION 1
 
 enum {
@@ -282,7 +285,8 @@ int wino_debug_conv1x1_models(long M, int Cin, int Kout, int cus, double* t_late
  * out = relu( bn3(conv1x1(relu(bn2(conv3x3(relu(bn1(conv1x1(x, w1))), U2))), w3)) + x )
  * x, out [N][14][14][C4] (unpadded, = [N*196][C4]); w1 [C4][Cm], w3 [Cm][C4] (the reference's
  * [Cin][Kout] 1x1 layout); U2 = packed F(2x2,3x3) filters of the Cm->Cm 3x3 layer; all BN folded.
- * Three launches on `s`, intermediates in `workspace` (wino_residual_block_workspace_bytes). */
+ * Three launches on `s`, intermediates in `workspace` (wino_residual_block_workspace_bytes), which must not overlap x
+ * or out (x is read again as the residual by the last launch). */
 size_t wino_residual_block_workspace_bytes(int N, int Cm);
 int wino_residual_block(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
                         const float* U2, const float* bn2Bias, const float* bn2Scale,
@@ -314,7 +318,8 @@ int wino_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, wino_str
  * (wino_proj_tail_elems floats; the layout is private to the library, like U's).
  * Constraints: stride 1 or 2, Cin % 32 == 0, Cm % 64 == 0, C4 % 64 == 0; shapes whose 32-bit tile windows,
  * pixel rows or ring pass would overflow are rejected (WINO_E_SHAPE).  Three launches on `s`; the padded
- * intermediates live in `workspace` (wino_proj_block_workspace_bytes_hw(N, H, W, Cm), H x W the OUTPUT grid).
+ * intermediates live in `workspace` (wino_proj_block_workspace_bytes_hw(N, H, W, Cm), H x W the OUTPUT grid), which
+ * must not overlap x (read again by the last launch for the shortcut) or out.
  * v1.5 placement (stride on the 3x3, torchvision): wino_proj_block_v15_hw below. */
 size_t wino_proj_tail_elems(int Cm, int Cin, int C4);
 int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3Scale, const float* wp,
@@ -358,7 +363,8 @@ int wino_conv3x3_s2_plan(int N, int Hin, int Win, int C, int K, int cus, int* fo
  * Three launches on `s`: the 1x1 at full input resolution, the stride-2 3x3, and the v1 block's fused tail at stride 2.
  * The stride is always 2: at stride 1 the two placements are the same network (wino_proj_block_hw).  Constraints:
  * those of wino_proj_block_hw at stride 2 and of the two layers.  The padded intermediates -- t1 [N][Hin+2][Win+2][Cm],
- * then t2 [N][H+2][W+2][Cm] -- live in `workspace` (wino_proj_block_v15_workspace_bytes_hw). */
+ * then t2 [N][H+2][W+2][Cm] -- live in `workspace` (wino_proj_block_v15_workspace_bytes_hw), which must not overlap x
+ * or out. */
 size_t wino_proj_block_v15_workspace_bytes_hw(int N, int Hin, int Win, int Cm);
 int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
                            const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
