@@ -312,25 +312,25 @@ def _workspace(t, need: int, device) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------- operators
-def filter_transform_f2(w_kcrs: torch.Tensor) -> torch.Tensor:
-    """[K][C][3][3] taps -> packed F(2x2,3x3) filter buffer (opaque layout, 16*C*K floats)."""
+def filter_transform_f2(w_kcrs: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
+    """[K][C][3][3] taps -> packed F(2x2,3x3) filter buffer (opaque layout, 16*C*K floats; `out`: the caller's)."""
     w = _dev(w_kcrs, "w_kcrs")
     K, C = int(w.shape[0]), int(w.shape[1])
     if tuple(w.shape[2:]) != (3, 3):
         raise WinoError("w_kcrs must be [K][C][3][3]")
-    U = torch.empty(lib().wino_filter_f2_elems(C, K), dtype=torch.float32, device=w.device)
+    U = _output(out, (lib().wino_filter_f2_elems(C, K),), w.device)
     _check(lib().wino_filter_transform_f2(w.data_ptr(), U.data_ptr(), C, K, _stream()),
            "wino_filter_transform_f2")
     return U
 
 
-def filter_import_f4(u36: torch.Tensor) -> torch.Tensor:
+def filter_import_f4(u36: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """The reference's weight_winograd_C_K.bin tensor [36][C][K] -> packed F(2x2) buffer."""
     u = _dev(u36, "u36")
     if u.dim() != 3 or u.shape[0] != 36:
         raise WinoError("u36 must be [36][C][K]")
     C, K = int(u.shape[1]), int(u.shape[2])
-    U = torch.empty(lib().wino_filter_f2_elems(C, K), dtype=torch.float32, device=u.device)
+    U = _output(out, (lib().wino_filter_f2_elems(C, K),), u.device)
     _check(lib().wino_filter_import_f4(u.data_ptr(), U.data_ptr(), C, K, _stream()),
            "wino_filter_import_f4")
     return U
@@ -364,7 +364,7 @@ def conv3x3_bn_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor,
 
 
 def conv3x3_f4_bn_relu(inp: torch.Tensor, u36: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
-                       relu: bool = True) -> torch.Tensor:
+                       relu: bool = True, out: torch.Tensor | None = None, workspace=None) -> torch.Tensor:
     """F(4x4,3x3) compatibility path: the reference's three stages on its own weight_winograd tensor
     u36 [36][C][K], consumed as is.  inp [N][16][16][C] -> out [N][16][16][K]."""
     x, u = _dev(inp, "inp"), _dev(u36, "u36")
@@ -374,11 +374,11 @@ def conv3x3_f4_bn_relu(inp: torch.Tensor, u36: torch.Tensor, bn_bias: torch.Tens
     N, C, K = int(x.shape[0]), int(x.shape[3]), int(u.shape[2])
     if int(u.shape[1]) != C or b.numel() != K or s.numel() != K:
         raise WinoError("u36 / bn vectors do not match C, K")
-    out = torch.empty((N, 16, 16, K), dtype=torch.float32, device=x.device)
-    nbytes = lib().wino_conv3x3_f4_workspace_bytes(N, C, K)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)
+    out = _output(out, (N, 16, 16, K), x.device)
+    ws = _workspace(workspace, lib().wino_conv3x3_f4_workspace_bytes(N, C, K), x.device)
+    _on_current_device(x, u, b, s, out, ws)
     _check(lib().wino_conv3x3_f4_bn_relu(x.data_ptr(), u.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
-                                         N, C, K, int(relu), ws.data_ptr(), nbytes, _stream()),
+                                         N, C, K, int(relu), ws.data_ptr(), ws.numel() * 4, _stream()),
            "wino_conv3x3_f4_bn_relu")
     return out
 
@@ -390,12 +390,12 @@ def conv3x3_prepare(N: int, C: int, K: int, H: int = 14, W: int = 14) -> None:
            "wino_conv3x3_prepare_hw")
 
 
-def conv3x3_direct(inp, w_kcrs, bn_bias, bn_scale, relu: bool = True) -> torch.Tensor:
+def conv3x3_direct(inp, w_kcrs, bn_bias, bn_scale, relu: bool = True, out=None) -> torch.Tensor:
     """Comparator: direct 3x3 conv + BN + ReLU on the GPU (not the product path); any H, W."""
     x, w = _dev(inp, "inp"), _dev(w_kcrs, "w_kcrs")
     b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
     N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(w.shape[0])
-    out = torch.empty((N, Hp, Wp, K), dtype=torch.float32, device=x.device)
+    out = _output(out, (N, Hp, Wp, K), x.device)
     _check(lib().wino_conv3x3_direct_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(),
                                         out.data_ptr(), N, Hp - 2, Wp - 2, C, K, int(relu), _stream()),
            "wino_conv3x3_direct_hw")
@@ -537,7 +537,7 @@ def residual_block(x, w1, bn1, U2, bn2, w3, bn3, out=None, workspace=None) -> to
 FORM_TILED, FORM_STREAM_K, FORM_LATENCY = 0, 1, 2   # WINO_1X1_FORM_*
 
 
-def proj_tail_pack(w3, bn3, wp, bnp) -> torch.Tensor:
+def proj_tail_pack(w3, bn3, wp, bnp, out=None) -> torch.Tensor:
     """The projection block's fused last layer: w3 [Cm][C4], wp [Cin][C4] and their folded BNs (bias, scale) packed
     into one opaque buffer (wino_proj_tail_pack) -- the analogue of filter_transform_f2 for U2."""
     w3, wp = _dev(w3, "w3"), _dev(wp, "wp")
@@ -548,7 +548,7 @@ def proj_tail_pack(w3, bn3, wp, bnp) -> torch.Tensor:
     n = lib().wino_proj_tail_elems(Cm, Cin, C4)
     if n == 0:
         raise WinoError(f"bad projection tail shape Cm={Cm} Cin={Cin} C4={C4}")
-    packed = torch.empty(n, dtype=torch.float32, device=w3.device)
+    packed = _output(out, (n,), w3.device)
     _on_current_device(w3, wp, packed, *vecs)
     _check(lib().wino_proj_tail_pack(w3.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), wp.data_ptr(),
                                      vecs[2].data_ptr(), vecs[3].data_ptr(), packed.data_ptr(), Cm, Cin, C4, _stream()),
@@ -603,13 +603,16 @@ def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None)
     return out
 
 
-def filter_pack_s2(w_kcrs: torch.Tensor) -> torch.Tensor:
+def filter_pack_s2(w_kcrs: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """[K][C][3][3] taps -> the stride-2 3x3 layer's [3][3][C][K] filter (w.permute(2, 3, 1, 0)), the analogue of
     filter_transform_f2 for conv3x3_s2_bn_relu."""
     w = _dev(w_kcrs, "w_kcrs")
     if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3):
         raise WinoError("w_kcrs must be [K][C][3][3]")
-    return w.permute(2, 3, 1, 0).contiguous()
+    taps = w.permute(2, 3, 1, 0)
+    if out is None:
+        return taps.contiguous()
+    return _out(out, taps.shape, "out").copy_(taps)
 
 
 def _s2_out_hw(Hin: int, Win: int):
@@ -742,7 +745,7 @@ def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
     return out
 
 
-def s2_proj_pack(w_taps, bn1, wd, bnd) -> torch.Tensor:
+def s2_proj_pack(w_taps, bn1, wd, bnd, out=None) -> torch.Tensor:
     """The downsampling basic block's first layer: w_taps [3][3][C][K] (filter_pack_s2), its BN bn1 = (bias, scale),
     the shortcut wd [C][K] (torch's [K][C][1][1] weight as w.view(K, C).t()) and its BN bnd = (bias, scale), packed
     into one opaque buffer (wino_s2_proj_pack).  The scales are not folded into the filters."""
@@ -758,7 +761,7 @@ def s2_proj_pack(w_taps, bn1, wd, bnd) -> torch.Tensor:
     n = lib().wino_s2_proj_elems(C, K)
     if n == 0:
         raise WinoError(f"bad shape C={C} K={K}")
-    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    packed = _output(out, (n,), w.device)
     _on_current_device(w, wd, packed, *vecs)
     _check(lib().wino_s2_proj_pack(w.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), wd.data_ptr(),
                                    vecs[2].data_ptr(), vecs[3].data_ptr(), packed.data_ptr(), C, K, _stream()),
@@ -831,7 +834,7 @@ def stem_out_hw(H: int, W: int):
     return (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
 
 
-def stem_filter_pack(w, bn) -> torch.Tensor:
+def stem_filter_pack(w, bn, out=None) -> torch.Tensor:
     """The stem's conv filter, torch's w [K][3][7][7], and its BN bn = (bias, scale) packed into one opaque buffer
     (wino_stem_filter_pack).  The scale is not folded into the filter."""
     w = _dev(w, "w")
@@ -844,7 +847,7 @@ def stem_filter_pack(w, bn) -> torch.Tensor:
     n = lib().wino_stem_filter_elems(K)
     if n == 0:
         raise WinoError(f"stem: unsupported K={K} (need K % 64 == 0)")
-    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    packed = _output(out, (n,), w.device)
     _on_current_device(w, packed, *vecs)
     _check(lib().wino_stem_filter_pack(w.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), packed.data_ptr(), K,
                                        _stream()), "wino_stem_filter_pack")
@@ -879,7 +882,7 @@ def stem(x, packed, out_padded: bool = False, out=None) -> torch.Tensor:
     return out
 
 
-def head_pack(wfc, bfc) -> torch.Tensor:
+def head_pack(wfc, bfc, out=None) -> torch.Tensor:
     """The classifier head's FC layer, torch's weight [classes][C] and bias [classes], packed into one opaque buffer
     (wino_head_pack; the class count padded to a multiple of 64 inside)."""
     w, b = _dev(wfc, "wfc"), _dev(bfc, "bfc")
@@ -889,7 +892,7 @@ def head_pack(wfc, bfc) -> torch.Tensor:
     n = lib().wino_head_elems(C, classes)
     if n == 0:
         raise WinoError(f"head: unsupported C={C} classes={classes} (need C % 32 == 0)")
-    packed = torch.empty(n, dtype=torch.float32, device=w.device)
+    packed = _output(out, (n,), w.device)
     _on_current_device(w, b, packed)
     _check(lib().wino_head_pack(w.data_ptr(), b.data_ptr(), packed.data_ptr(), C, classes, _stream()), "wino_head_pack")
     return packed
@@ -923,11 +926,11 @@ def avgpool_fc(feat, packed, classes: int, in_padded: bool = False, out=None, wo
     return out
 
 
-def conv1x1_direct(A, B, bn_bias, bn_scale, relu: bool) -> torch.Tensor:
+def conv1x1_direct(A, B, bn_bias, bn_scale, relu: bool, out=None) -> torch.Tensor:
     a, bm = _dev(A, "A"), _dev(B, "B")
     b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
     M, Cin, Kout = int(a.shape[0]), int(a.shape[1]), int(bm.shape[1])
-    out = torch.empty((M, Kout), dtype=torch.float32, device=a.device)
+    out = _output(out, (M, Kout), a.device)
     _check(lib().wino_conv1x1_direct(a.data_ptr(), bm.data_ptr(), b.data_ptr(), s.data_ptr(),
                                      out.data_ptr(), M, Cin, Kout, int(relu), _stream()),
            "wino_conv1x1_direct")

@@ -69,7 +69,9 @@ enum {
   WINO_E_HIP = -1,       /* a HIP runtime call failed (no device, OOM, launch error) */
   WINO_E_SHAPE = -2,     /* unsupported / inconsistent shape argument */
   WINO_E_ARG = -3,       /* NULL pointer, bad enum, workspace too small, a tensor pointer that is not 16-byte aligned
-                            (the kernels move 16 bytes per lane; wino_malloc / hipMalloc give 256; BN vectors need 4) */
+                            (the kernels move 16 bytes per lane; wino_malloc / hipMalloc give 256; BN vectors need 4).
+                            Pass a 256-byte-aligned workspace (what wino_malloc gives): the blocks carve their
+                            intermediates from it.  16 is the checked minimum */
   WINO_E_STATE = -4,     /* the stream's library-owned scratch cannot be trusted (an earlier launch on it
                             failed or was aborted): wino_stream_reset_scratch() recovers */
 };

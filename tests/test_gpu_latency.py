@@ -5,6 +5,8 @@ the CPU oracle is only the checker."""
 import numpy as np
 import pytest
 
+import guarded as G
+
 pytestmark = pytest.mark.gpu
 
 TIGHT = 2e-5
@@ -275,7 +277,8 @@ def test_latency_kernels_random_shapes(pkg, torch_dev, knobs):
     """Seeded sweep of the two latency kernels with their forms FORCED (the automatic choice would send most of these
     shapes to the throughput kernels): random legal shapes -- 3x3: any N, H, W, C % 16, K % 64 (wider blocks where K
     allows), a random split; 1x1: any M, Cin % 32, Kout % 64, random (K-split, row tiles, column tiles), random
-    chaining flags -- against the direct GPU comparators (no Winograd, no MFMA) on NaN-filled outputs."""
+    chaining flags -- against the direct GPU comparators (no Winograd, no MFMA) on NaN-filled outputs.  The launches'
+    tensors lie on the guarded arena (tests/guarded.py), each case at both placements; no guard may be touched."""
     torch, dev = torch_dev
     rng = np.random.RandomState(4242)
     mk = lambda *s: torch.from_numpy(((rng.rand(*s) - 0.5) * 2).astype(np.float32)).to(dev)
@@ -291,16 +294,19 @@ def test_latency_kernels_random_shapes(pkg, torch_dev, knobs):
         x, w, s, b = mk(N, H + 2, W + 2, C), mk(K, C, 3, 3), mk(K), mk(K)
         U = pkg.filter_transform_f2(w)
         assert pkg.small_plan_3x3_full(N, C, K, H=H, W=W)[:4] == (1, 2, sp, ct), (N, H, W, C, K, ct, sp)
-        out = torch.full((N, H + 2, W + 2, K), float("nan"), device=dev)
-        pkg.conv3x3_bn_relu(x, U, b, s, relu=bool(i & 1), out=out)
         want = pkg.conv3x3_direct(x, w, b, s, relu=bool(i & 1))
-        assert not bool(torch.isnan(out).any()), (N, H, W, C, K, ct, sp)
         inner = (slice(None), slice(1, H + 1), slice(1, W + 1), slice(None))
-        assert float((out[inner] - want[inner]).abs().max()) < TIGHT * float(want[inner].abs().max() + 1e-6), (N, H, W, C, K, ct, sp)
         ring = torch.ones(H + 2, W + 2, dtype=torch.bool, device=dev)
         ring[1:-1, 1:-1] = False
-        assert bool((out[:, ring, :] == 0).all()), (N, H, W, C, K, ct, sp)
-        assert pkg.tickets_in_use() == 0
+        for align in G.ALIGNS:
+            arena = G.Arena(torch, dev, align=align)
+            out = arena.output(N, H + 2, W + 2, K)
+            pkg.conv3x3_bn_relu(*(arena.input(v) for v in (x, U, b, s)), relu=bool(i & 1), out=out)
+            assert not bool(torch.isnan(out).any()), (N, H, W, C, K, ct, sp, align)
+            assert float((out[inner] - want[inner]).abs().max()) < TIGHT * float(want[inner].abs().max() + 1e-6), (N, H, W, C, K, ct, sp, align)
+            assert bool((out[:, ring, :] == 0).all()), (N, H, W, C, K, ct, sp, align)
+            assert pkg.tickets_in_use() == 0
+            arena.check(f"conv3x3_bn_relu latency N={N} H={H} W={W} C={C} K={K} ct={ct} split={sp} align={align}")
     for k in ("WINO_3X3_ALGO", "WINO_SMALL_CT", "WINO_SMALL_SPLIT"):
         knobs.unset(k)
     knobs.set("WINO_1X1_ALGO", "small")
@@ -324,19 +330,23 @@ def test_latency_kernels_random_shapes(pkg, torch_dev, knobs):
             lin = lin + R
         want = torch.relu(lin) if flags & pkg.RELU else lin
         shape = (N, H + 2, W + 2, Kout) if flags & pkg.C_PADDED else (M, Kout)
-        out = torch.full(shape, float("nan"), device=dev)
-        pkg.conv1x1_bn_ex(Ap if flags & pkg.A_PADDED else A, Bm, b, s, flags, residual=R if flags & pkg.ADD_RESIDUAL else None,
-                          out=out, hw=(H, W))
-        tag = (M, Cin, Kout, ks, rt, ct, flags)
-        if flags & pkg.C_PADDED:
-            ring = torch.ones(H + 2, W + 2, dtype=torch.bool, device=dev)
-            ring[1:-1, 1:-1] = False
-            assert bool((out[:, ring, :] == 0).all()), tag
-            got = out[:, 1:-1, 1:-1, :].reshape(M, Kout)
-        else:
-            got = out
-        assert not bool(torch.isnan(got).any()), tag
-        assert float((got - want).abs().max()) < TIGHT * float(want.abs().max() + 1e-6), tag
+        for align in G.ALIGNS:
+            arena = G.Arena(torch, dev, align=align)
+            out = arena.output(*shape)
+            pkg.conv1x1_bn_ex(arena.input(Ap if flags & pkg.A_PADDED else A), arena.input(Bm), arena.input(b),
+                              arena.input(s), flags, residual=arena.input(R) if flags & pkg.ADD_RESIDUAL else None,
+                              out=out, hw=(H, W))
+            tag = (M, Cin, Kout, ks, rt, ct, flags, align)
+            if flags & pkg.C_PADDED:
+                ring = torch.ones(H + 2, W + 2, dtype=torch.bool, device=dev)
+                ring[1:-1, 1:-1] = False
+                assert bool((out[:, ring, :] == 0).all()), tag
+                got = out[:, 1:-1, 1:-1, :].reshape(M, Kout)
+            else:
+                got = out
+            assert not bool(torch.isnan(got).any()), tag
+            assert float((got - want).abs().max()) < TIGHT * float(want.abs().max() + 1e-6), tag
+            arena.check(f"conv1x1_bn_ex latency {tag}")
         done += 1
     assert done >= 20
     for k in ("WINO_1X1_ALGO", "WINO_1X1_SMALL_KS", "WINO_1X1_SMALL_RT", "WINO_1X1_SMALL_CT"):

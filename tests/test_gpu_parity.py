@@ -12,6 +12,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import guarded as G
 from conftest import ROOT, load_bin
 
 pytestmark = pytest.mark.gpu
@@ -761,7 +762,8 @@ def test_conv3x3_batch_beyond_one_launch(pkg, O, torch_dev):
     """One launch addresses its tensors with 32-bit byte offsets (< 4 GiB each); the entry point takes
     any batch and cuts larger ones into launches of whole images.  5100 images of 56x56x64 are 4.4 GB
     in and 4.4 GB out: 4928 + 172.  The first and last image and the two on either side of the cut
-    against the fp64 oracle, zero ring, every output finite."""
+    against the fp64 oracle, zero ring, every output finite.  `out` lies between guards (tests/guarded.py; one image
+    each): the second launch starts at out + cut images and ends right at the back guard."""
     torch, dev = torch_dev
     N, H, W, C, K = 5100, 56, 56, 64, 64
     free, _ = torch.cuda.mem_get_info()
@@ -778,7 +780,8 @@ def test_conv3x3_batch_beyond_one_launch(pkg, O, torch_dev):
     s = (rng.rand(K) - 0.5).astype(np.float32)
     b = (rng.rand(K) - 0.5).astype(np.float32)
     U = pkg.filter_transform_f2(_t(torch_dev, w))
-    out = torch.full((N, H + 2, W + 2, K), float("nan"), device=dev)
+    arena = G.Arena(torch, dev)
+    out = arena.output(N, H + 2, W + 2, K, name="out")
     pkg.conv3x3_bn_relu(x, U, _t(torch_dev, b), _t(torch_dev, s), relu=True, out=out)
     assert bool(torch.isfinite(out).all())
     ring = np.ones((H + 2, W + 2), bool)
@@ -788,7 +791,8 @@ def test_conv3x3_batch_beyond_one_launch(pkg, O, torch_dev):
         want = O.conv3x3_bn_relu_direct(x[n:n + 1].cpu().numpy(), w, s, b, relu=True)
         assert O.rel_error(got, want) < TIGHT, n
         assert (got[:, ring, :] == 0).all(), n
-    del x, out
+    arena.check(f"conv3x3_bn_relu N={N} cut at {cut}")
+    del x, out, arena
     torch.cuda.empty_cache()
 
 
@@ -881,10 +885,10 @@ def test_random_legal_shapes(pkg, O, torch_dev, knobs):
     N, H, W, C % 8, K % 64), each against the fp64 oracle on an output pre-filled with NaN: the
     corners between the hand-picked cases (a column count that is a multiple of 64 but not of
     128 went uncomputed until a sweep like this one).  Stream-K forms are forced on every other
-    1x1 case so that both launch forms see odd shapes."""
+    1x1 case so that both launch forms see odd shapes.  Every tensor lies on the guarded arena
+    (tests/guarded.py), each case at both placements; no guard may be touched, no operand written."""
     torch, dev = torch_dev
     rng = np.random.RandomState(2024)
-    t = lambda a: _t(torch_dev, a)
     for i in range(24):
         M = int(rng.randint(1, 2600)); Cin = 32 * int(rng.randint(1, 20)); Kout = 64 * int(rng.randint(1, 11))
         A = ((rng.rand(M, Cin) - 0.5) * 4).astype(np.float32)
@@ -895,15 +899,20 @@ def test_random_legal_shapes(pkg, O, torch_dev, knobs):
         if i % 2:
             knobs.set("WINO_1X1_SK", "1")
             knobs.set("WINO_1X1_SK_GRID", str(8 * int(rng.randint(1, 64))))
+        want = O.conv1x1_bn(A, B, b, s, relu)
         try:
-            out = torch.full((M, Kout), float("nan"), device=dev)
-            pkg.conv1x1_bn(t(A), t(B), t(b), t(s), relu, out=out)
-            got = out.cpu().numpy()
+            for align in G.ALIGNS:
+                arena = G.Arena(torch, dev, align=align)
+                t = lambda a: arena.input(torch.from_numpy(a))
+                out = arena.output(M, Kout)
+                pkg.conv1x1_bn(t(A), t(B), t(b), t(s), relu, out=out)
+                got = out.cpu().numpy()
+                assert np.isfinite(got).all(), (M, Cin, Kout, align)
+                assert O.rel_error(got, want) < TIGHT, (M, Cin, Kout, align)
+                arena.check(f"conv1x1_bn M={M} Cin={Cin} Kout={Kout} sk={i % 2} align={align}")
         finally:
             knobs.unset("WINO_1X1_SK")
             knobs.unset("WINO_1X1_SK_GRID")
-        assert np.isfinite(got).all(), (M, Cin, Kout)
-        assert O.rel_error(got, O.conv1x1_bn(A, B, b, s, relu)) < TIGHT, (M, Cin, Kout)
     for i in range(16):
         N = int(rng.randint(1, 6)); H = int(rng.randint(1, 21)); W = int(rng.randint(1, 21))
         C = 8 * int(rng.randint(1, 20)); K = 64 * int(rng.randint(1, 4))
@@ -912,22 +921,27 @@ def test_random_legal_shapes(pkg, O, torch_dev, knobs):
         s = (rng.rand(K) - 0.5).astype(np.float32)
         b = (rng.rand(K) - 0.5).astype(np.float32)
         relu = bool(i & 1)
-        U = pkg.filter_transform_f2(t(w))
-        out = torch.full((N, H + 2, W + 2, K), float("nan"), device=dev)
-        pkg.conv3x3_bn_relu(t(x), U, t(b), t(s), relu=relu, out=out)
-        got = out.cpu().numpy()
-        assert np.isfinite(got).all(), (N, H, W, C, K)
         want = O.conv3x3_bn_relu_direct(x, w, s, b, relu=relu)
-        assert O.rel_error(got, want) < TIGHT, (N, H, W, C, K)
         ring = np.ones((H + 2, W + 2), bool); ring[1:-1, 1:-1] = False
-        assert (got[:, ring, :] == 0).all(), (N, H, W, C, K)
+        for align in G.ALIGNS:
+            arena = G.Arena(torch, dev, align=align)
+            t = lambda a: arena.input(torch.from_numpy(a))
+            U = arena.input(pkg.filter_transform_f2(t(w)))
+            out = arena.output(N, H + 2, W + 2, K)
+            pkg.conv3x3_bn_relu(t(x), U, t(b), t(s), relu=relu, out=out)
+            got = out.cpu().numpy()
+            assert np.isfinite(got).all(), (N, H, W, C, K, align)
+            assert O.rel_error(got, want) < TIGHT, (N, H, W, C, K, align)
+            assert (got[:, ring, :] == 0).all(), (N, H, W, C, K, align)
+            arena.check(f"conv3x3_bn_relu N={N} H={H} W={W} C={C} K={K} align={align}")
 
 
 def test_random_forced_grids_3x3(pkg, torch_dev, knobs):
     """Seeded sweep of the 3x3 throughput kernel's hand-off over random shapes AND random forced grids (1 ... 700
     logical workgroups: fewer than items, more than CUs, whole-item rounds with short and long tails, items cut
     into many segments), at the reference's 14x14 and at other feature maps: NaN-filled outputs against the direct
-    comparator kernel, every launch twice (bitwise equal), ticket counters at zero after every launch."""
+    comparator kernel, every launch twice (bitwise equal), ticket counters at zero after every launch.  The launches'
+    tensors lie on the guarded arena (tests/guarded.py), each case at both placements."""
     torch, dev = torch_dev
     knobs.set("WINO_3X3_ALGO", "big")
     rng = np.random.RandomState(777)
@@ -944,17 +958,21 @@ def test_random_forced_grids_3x3(pkg, torch_dev, knobs):
         U = pkg.filter_transform_f2(w)
         want = pkg.conv3x3_direct(x, w, bi, sc)
         scale = float(want.abs().max())
-        knobs.set("WINO_SK_GRID", str(grid))
-        outs = []
-        for rep in range(2):
-            out = torch.full((N, H + 2, W + 2, K), float("nan"), device=dev)
-            pkg.conv3x3_bn_relu(x, U, bi, sc, out=out)
-            assert pkg.tickets_in_use() == 0, (i, N, H, W, C, K, grid)
-            outs.append(out)
-        knobs.unset("WINO_SK_GRID")
-        assert not bool(torch.isnan(outs[0]).any()), (i, N, H, W, C, K, grid)
-        assert torch.equal(outs[0], outs[1]), (i, N, H, W, C, K, grid)
-        assert float((outs[0] - want).abs().max()) < TIGHT * scale, (i, N, H, W, C, K, grid)
+        for align in G.ALIGNS:
+            arena = G.Arena(torch, dev, align=align)
+            xa, Ua, bia, sca = (arena.input(v) for v in (x, U, bi, sc))
+            knobs.set("WINO_SK_GRID", str(grid))
+            outs = []
+            for rep in range(2):
+                out = arena.output(N, H + 2, W + 2, K)
+                pkg.conv3x3_bn_relu(xa, Ua, bia, sca, out=out)
+                assert pkg.tickets_in_use() == 0, (i, N, H, W, C, K, grid, align)
+                outs.append(out)
+            knobs.unset("WINO_SK_GRID")
+            assert not bool(torch.isnan(outs[0]).any()), (i, N, H, W, C, K, grid, align)
+            assert torch.equal(outs[0], outs[1]), (i, N, H, W, C, K, grid, align)
+            assert float((outs[0] - want).abs().max()) < TIGHT * scale, (i, N, H, W, C, K, grid, align)
+            arena.check(f"conv3x3_bn_relu #{i} N={N} H={H} W={W} C={C} K={K} grid={grid} align={align}")
 
 
 def test_residual_block_in_a_graph(pkg, O, torch_dev):
