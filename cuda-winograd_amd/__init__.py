@@ -53,6 +53,7 @@ ABI_SYMBOLS = [
     "wino_basic_block_s2_hw", "wino_basic_block_s2_prepare_hw",
     "wino_stem_filter_elems", "wino_stem_filter_pack", "wino_stem_hw", "wino_stem_plan", "wino_head_elems",
     "wino_head_pack", "wino_head_workspace_bytes", "wino_head_prepare", "wino_avgpool_fc_hw",
+    "wino_conv3x3_bn_relu_pool_hw", "wino_image_pack_hw", "wino_avgpool7_flatten_hw",
     # reference entry points + helpers (Kernel*.h, util.h)
     "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
     "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
@@ -184,6 +185,9 @@ def lib() -> ctypes.CDLL:
     L.wino_head_workspace_bytes.argtypes = [c_int] * 3
     L.wino_head_prepare.argtypes = [c_int] * 3 + [c_void_p]
     L.wino_avgpool_fc_hw.argtypes = [fp] * 3 + [c_int] * 6 + [fp, c_size_t, c_void_p]
+    L.wino_conv3x3_bn_relu_pool_hw.argtypes = [fp] * 5 + [c_int] * 6 + [c_void_p]
+    L.wino_image_pack_hw.argtypes = [fp] * 2 + [c_int] * 5 + [c_void_p]
+    L.wino_avgpool7_flatten_hw.argtypes = [fp] * 2 + [c_int] * 5 + [c_void_p]
     for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
                  "kernel_256_1_in", "kernel_256_1_out"):
         getattr(L, name).restype = c_int
@@ -926,6 +930,58 @@ def avgpool_fc(feat, packed, classes: int, in_padded: bool = False, out=None, wo
     return out
 
 
+def conv3x3_bn_relu_pool(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
+                         relu: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+    """The 3x3 layer with MaxPool2d(2, 2) fused into its epilogue, one HIP launch: inp [N][H+2][W+2][C] ->
+    out [N][H//2+2][W//2+2][K] = maxpool2x2_s2(act(scale*conv3x3(inp) + bias)) with a zero ring.  The launch takes the
+    plan of conv3x3_bn_relu at the same shape (conv3x3_prepare reserves its scratch).  H, W >= 2."""
+    x = _dev(inp, "inp")
+    U = _dev(U, "U")
+    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
+    if x.dim() != 4 or x.shape[1] < 4 or x.shape[2] < 4:
+        raise WinoError("inp must be [N][H+2][W+2][C] with H, W >= 2")
+    N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(b.numel())
+    if U.numel() != 16 * C * K or s.numel() != K:
+        raise WinoError("U / bn vectors do not match C, K")
+    H, W = Hp - 2, Wp - 2
+    out = _output(out, (N, H // 2 + 2, W // 2 + 2, K), x.device)
+    _on_current_device(x, U, b, s, out)
+    _check(lib().wino_conv3x3_bn_relu_pool_hw(x.data_ptr(), U.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
+                                              N, H, W, C, K, int(relu), _stream()), "wino_conv3x3_bn_relu_pool_hw")
+    return out
+
+
+def image_pack(x, Cpad: int = 16, out=None) -> torch.Tensor:
+    """x [N][Cin][H][W] (NCHW) -> out [N][H+2][W+2][Cpad]: the first 3x3 layer's input, channels Cin .. Cpad-1 and the
+    ring written 0.  1 <= Cin <= Cpad, Cpad % 8 == 0.  One HIP launch."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise WinoError("x must be [N][Cin][H][W]")
+    N, Cin, H, W = (int(v) for v in x.shape)
+    Cpad = int(Cpad)
+    out = _output(out, (N, H + 2, W + 2, Cpad), x.device)
+    _on_current_device(x, out)
+    _check(lib().wino_image_pack_hw(x.data_ptr(), out.data_ptr(), N, Cin, H, W, Cpad, _stream()), "wino_image_pack_hw")
+    return out
+
+
+def avgpool7_flatten(feat, in_padded: bool = False, out=None) -> torch.Tensor:
+    """torch's AdaptiveAvgPool2d((7, 7)) + flatten, channels innermost: feat [N][H][W][C] or, in_padded,
+    [N][H+2][W+2][C] (the ring is not read) -> out [N][49*C] in (h, w, c) order.  C % 4 == 0.  One HIP launch."""
+    f = _dev(feat, "feat")
+    if f.dim() != 4:
+        raise WinoError("feat must be [N][H][W][C]")
+    p = 2 if in_padded else 0
+    N, H, W, C = int(f.shape[0]), int(f.shape[1]) - p, int(f.shape[2]) - p, int(f.shape[3])
+    if H < 1 or W < 1:
+        raise WinoError("feat has no interior")
+    out = _output(out, (N, 49 * C), f.device)
+    _on_current_device(f, out)
+    _check(lib().wino_avgpool7_flatten_hw(f.data_ptr(), out.data_ptr(), N, H, W, C, int(bool(in_padded)), _stream()),
+           "wino_avgpool7_flatten_hw")
+    return out
+
+
 def conv1x1_direct(A, B, bn_bias, bn_scale, relu: bool, out=None) -> torch.Tensor:
     a, bm = _dev(A, "A"), _dev(B, "B")
     b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
@@ -948,3 +1004,4 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
 
 
 from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)
+from .vgg import VGG  # noqa: E402

@@ -196,6 +196,8 @@ struct FusedResParams : FusedParams {
 };
 template <bool RES>
 using FusedArgs = std::conditional_t<RES, FusedResParams, FusedParams>;
+// the epilogue forms of the two 3x3 kernels (their last template argument)
+constexpr int EPI_PLAIN = 0, EPI_RES = 1, EPI_POOL = 2;
 
 // Host side: the work layout fields above (ndp ... d_copies) of `items` items of p.C / BC chunk iterations on a grid
 // of G logical workgroups: items / G whole-item rounds, the rest a stream-K tail.
@@ -244,9 +246,22 @@ __device__ unsigned long long wino_clk_slot_3x3[4];
 // like out.  BN is applied before the LDS transpose as in the plain form; the ReLU waits until the residual's 16 bytes,
 // loaded at the store's own offset, have been added.  Each residual element is read only by the lane that stores that
 // offset, before its store, so out may be res (in place).  RES = false compiles exactly the plain kernel.
-template <int ABLATE, bool GEN = false, bool TAIL = true, bool RES = false>
+//
+// POOL = the pooled epilogue (a VGG layer that is followed by MaxPool2d(2, 2)): out = maxpool2x2_s2(act(scale*conv +
+// bias)), [N][H/2+2][W/2+2][K] with its zero ring.  An F(2x2) tile IS a pooling window: after the gather, BN and the
+// ReLU its four outputs sit in one lane (y[r][cb][0..3]), so the max is taken in-lane and one value per (tile,
+// out-channel) goes through the LDS transpose -- 2 KB per wave and two 16-byte store rounds where the plain form has
+// 8 KB and eight.  Everything up to the finalize, the launch plan included, is the plain layer's; only the ring pass
+// and the store addressing use the pooled geometry.  Tiles of a clipped last tile row / column (odd H or W) are
+// dropped whole: floor, as torch pools.
+//
+// The epilogue is one template argument, EPI = EPI_PLAIN / EPI_RES / EPI_POOL (0 / 1 / 2: `false` and `true` still name
+// the plain and the residual form).  EPI_PLAIN and EPI_RES compile exactly what RES = false / true compiled.
+template <int ABLATE, bool GEN = false, bool TAIL = true, int EPI = EPI_PLAIN>
 __global__ void __launch_bounds__(NTHREADS, 2)
-wino_f2_fused_kernel(const FusedArgs<RES> prm) {
+wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
+  static_assert(EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_POOL, "epilogue form");
+  constexpr bool RES = EPI == EPI_RES, POOL = EPI == EPI_POOL;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const float* in = prm.in;
   const float* Uq = prm.Uq;
@@ -303,7 +318,9 @@ wino_f2_fused_kernel(const FusedArgs<RES> prm) {
   // cost more than the tiles' own stores: sparse predicated stores and their address arithmetic.)
   auto ring_pass = [&]() {
     if (ABLATE & 512) return;
-    const unsigned Hp = GEN ? (unsigned)prm.geo.Hp : (unsigned)WINO_HW, Wp = GEN ? (unsigned)prm.geo.Wp : (unsigned)WINO_HW;
+    // (POOL: the ring of the pooled output, (H/2 + 2) x (W/2 + 2))
+    const unsigned Hi = GEN ? (unsigned)prm.geo.Hp : (unsigned)WINO_HW, Wi = GEN ? (unsigned)prm.geo.Wp : (unsigned)WINO_HW;
+    const unsigned Hp = POOL ? (Hi - 2u) / 2u + 2u : Hi, Wp = POOL ? (Wi - 2u) / 2u + 2u : Wi;
     const unsigned rpx = 2u * Wp + 2u * (Hp - 2u);               // ring pixels per image (60 at 16 x 16)
     const unsigned upp = (unsigned)K >> 2;                       // units per ring pixel
     const unsigned long long U = (unsigned long long)N * rpx * upp;
@@ -801,7 +818,9 @@ wino_f2_fused_kernel(const FusedArgs<RES> prm) {
     const float* bnBias = kp->bnBias;
     const float* bnScale = kp->bnScale;
     unsigned* tickets = kp->tickets;
-    const auto rsrc_out = make_rsrc(kp->out, (unsigned)((size_t)N * Hp * Wp * K * sizeof(float)));
+    // (POOL: the output is the pooled map, Hq x Wq padded)
+    const int Hq = POOL ? (Hp - 2) / 2 + 2 : Hp, Wq = POOL ? (Wp - 2) / 2 + 2 : Wp;
+    const auto rsrc_out = make_rsrc(kp->out, (unsigned)((size_t)N * Hq * Wq * K * sizeof(float)));
     const auto rsrc_slab = make_rsrc(kp->slabs, (unsigned)((size_t)2 * G * SLAB_BYTES));
     const unsigned slab_voff = (unsigned)((wv * 8 * 64 + ln) * 16);
 
@@ -1009,6 +1028,43 @@ wino_f2_fused_kernel(const FusedArgs<RES> prm) {
           if (live && (!GEN || (py <= Hp - 2 && pxx <= Wp - 2)))
             rv[i] = buf_load16(rsrc_res, (unsigned)((img + py * Wp + pxx) * K * sizeof(float)) + kbyte, 0);
         }
+      }
+      if constexpr (POOL) {
+        // Pooled finalize.  Image: [row P = 4 r + h][k 0..31] floats, 2 KB: tile 4 h + r of the wave's 16 sits in row
+        // 4 r + h, and its 16-float group cb is XORed with h >> 1 -- the four row groups h of a ds_write_b32 then
+        // hit the four 16-bank quarters, and the two rows a 16-lane ds_read_b128 group reads are consecutive (the
+        // two 32-bank halves).
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+#pragma unroll
+          for (int cb = 0; cb < 2; cb++) {
+            float m = 0.f;
+#pragma unroll
+            for (int pp = 0; pp < 4; pp++) {
+              float v1 = sc2[cb] * y[r][cb][pp] + bi2[cb];
+              if (relu) v1 = fmaxf(v1, 0.f);
+              m = pp == 0 ? v1 : fmaxf(m, v1);
+            }
+            *(float*)(wreg + (4 * r + e_h) * 128 + ((cb ^ (e_h >> 1)) << 6) + e_t16 * 4) = m;
+          }
+        }
+        // lane -> row P = 8 i + (lane >> 3) = tile 4 (P & 3) + (P >> 2), 16-byte chunk lane & 7: two rounds of eight
+        // whole 128-byte runs
+        const unsigned kbyte = (unsigned)((kb * KB + e_wk * 32 + (ln & 7) * 4) * sizeof(float));
+#pragma unroll
+        for (int i = 0; i < 2; i++) {
+          const int P = 8 * i + (ln >> 3), ph_t = P & 3, tl = 4 * ph_t + (P >> 2);
+          const f32x4 val = *(const f32x4*)(wreg + P * 128 + (((((ln & 7) >> 2) ^ (ph_t >> 1))) << 6) + (ln & 3) * 16);
+          const int g = tb * TB + e_wt * 16 + tl;
+          const bool live = g < totalTiles;
+          const TileCoord tc = decode_tile_g<GEN>(live ? g : 0, geo);
+          const int py = 1 + tc.ty, pxx = 1 + tc.tx;
+          const unsigned img = (unsigned)(tc.n * Hq * Wq);
+          // (odd H or W: the clipped last tile row / column has no pooled output)
+          const bool keep = live && (!GEN || (py <= Hq - 2 && pxx <= Wq - 2));
+          if (keep) buf_store16_nt(val, rsrc_out, (unsigned)((img + py * Wq + pxx) * K * sizeof(float)) + kbyte, 0);
+        }
+        continue;
       }
       int ep_wbase[4], ep_rbase[4];
 #pragma unroll

@@ -1,8 +1,9 @@
 // The 3x3 F(2x2,3x3) layers' launch plan and launcher, shared by the translation units that launch them:
-// wino_f2_fused.hip (the plain epilogue, RES = false) and conv3x3_res.hip (the residual epilogue, RES = true: the second
-// 3x3 of a ResNet basic block).  A template is instantiated where it is used, so each file compiles the kernels of its
+// wino_f2_fused.hip (the plain epilogue, EPI = EPI_PLAIN), conv3x3_res.hip (the residual epilogue, EPI = EPI_RES: the
+// second 3x3 of a ResNet basic block) and conv3x3_pool.hip (the pooled epilogue, EPI = EPI_POOL: a VGG layer followed
+// by MaxPool2d(2, 2)).  A template is instantiated where it is used, so each file compiles the kernels of its
 // own epilogue and no others.  The planner (plan_3x3, plan_3x3_here) is defined once, in wino_f2_fused.hip: a residual
-// launch takes exactly the plan of the plain layer of the same shape.
+// launch and a pooled launch take exactly the plan of the plain layer of the same shape.
 #pragma once
 #include "wino_f2_small_kernel.h"
 
@@ -93,29 +94,34 @@ Plan3x3 plan_3x3(int N, int H, int W, int C, int K, int cus, const Knobs& kn, bo
 // the plan of a launch on the current device; *dev receives the device
 int plan_3x3_here(int N, int H, int W, int C, int K, bool throughput, int* dev, Plan3x3* p);
 
-// the latency kernel's instantiations by [GEN][CT / 2]
-template <bool RES>
-constexpr decltype(&wino_f2_small_kernel<1, false, false, RES>) SMALL_3X3_KERNELS[2][3] = {
-    {wino_f2_small_kernel<1, false, false, RES>, wino_f2_small_kernel<2, false, false, RES>,
-     wino_f2_small_kernel<4, false, false, RES>},
-    {wino_f2_small_kernel<1, true, false, RES>, wino_f2_small_kernel<2, true, false, RES>,
-     wino_f2_small_kernel<4, true, false, RES>}};
+// the latency kernel's instantiations by [CT / 2]: the 14x14 form (GEN = false; it has no pooled epilogue) and the
+// general one
+template <int EPI>
+constexpr decltype(&wino_f2_small_kernel<1, false, false, EPI>) SMALL_3X3_FIXED14[3] = {
+    wino_f2_small_kernel<1, false, false, EPI>, wino_f2_small_kernel<2, false, false, EPI>,
+    wino_f2_small_kernel<4, false, false, EPI>};
+template <int EPI>
+constexpr decltype(&wino_f2_small_kernel<1, true, false, EPI>) SMALL_3X3_GENERAL[3] = {
+    wino_f2_small_kernel<1, true, false, EPI>, wino_f2_small_kernel<2, true, false, EPI>,
+    wino_f2_small_kernel<4, true, false, EPI>};
 
-template <bool GEN, bool TAIL, bool RES>
-int launch_fused(const FusedArgs<RES>& prm, int G, int dev, hipStream_t s) {
+template <bool GEN, bool TAIL, int EPI>
+int launch_fused(const FusedArgs<EPI == EPI_RES>& prm, int G, int dev, hipStream_t s) {
   // all 160 KB of the CU's LDS
-  if (int rc = lds_cap_once<wino_f2_fused_kernel<0, GEN, TAIL, RES>>(dev, LDS_BYTES)) return rc;
-  hipLaunchKernelGGL((wino_f2_fused_kernel<0, GEN, TAIL, RES>), dim3(G), dim3(NTHREADS), LDS_BYTES, s, prm);
+  if (int rc = lds_cap_once<wino_f2_fused_kernel<0, GEN, TAIL, EPI>>(dev, LDS_BYTES)) return rc;
+  hipLaunchKernelGGL((wino_f2_fused_kernel<0, GEN, TAIL, EPI>), dim3(G), dim3(NTHREADS), LDS_BYTES, s, prm);
   const int rc = launch_status("wino_f2_fused_kernel");
   if (rc) sk_mark_failed(dev, s);   // the launch held the stream's scratch
   return rc;
 }
 
-// One launch of `plan_3x3_here`'s plan.  RES: out = act(bnScale*conv + bnBias + res), res padded like out; the plan is
-// the plain layer's (res is not read by RES = false).
-template <bool RES>
+// One launch of `plan_3x3_here`'s plan, with the epilogue EPI.  EPI_RES: out = act(bnScale*conv + bnBias + res), res
+// padded like out (EPI_PLAIN and EPI_POOL do not read res).  EPI_POOL: out = maxpool2x2_s2(act(bnScale*conv + bnBias)),
+// [N][H/2+2][W/2+2][K].  The plan is the plain layer's in every form.
+template <int EPI>
 int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, const float* bnScale, const float* res,
                        float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
+  constexpr bool RES = EPI == EPI_RES;
   if (int rc = check_conv3x3(N, H, W, C, K)) return rc;
   const bool fixed14 = H == WINO_PQ && W == WINO_PQ;
   int dev = 0;
@@ -129,7 +135,11 @@ int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, con
     static_cast<SmallParams&>(prm) = {in, U, bnBias, bnScale, out, N, C, K, relu, bufs.slabs, bufs.tickets, bufs.err, nullptr, p.geo};
     if constexpr (RES) prm.res = res;
     const dim3 grid(K / (16 * sp.ct), sp.nT16, sp.split), block(64 * SMALL_WAVES);   // x = out-channel block: see the kernel
-    hipLaunchKernelGGL(SMALL_3X3_KERNELS<RES>[!fixed14][sp.ct >> 1], grid, block, 0, s, prm);
+    // (a pooled 14x14 launch takes the general form: the 14x14 one writes its ring per tile, for a 16x16 output)
+    if constexpr (EPI == EPI_POOL)
+      hipLaunchKernelGGL((SMALL_3X3_GENERAL<EPI>[sp.ct >> 1]), grid, block, 0, s, prm);
+    else
+      hipLaunchKernelGGL((fixed14 ? SMALL_3X3_FIXED14<EPI>[sp.ct >> 1] : SMALL_3X3_GENERAL<EPI>[sp.ct >> 1]), grid, block, 0, s, prm);
     const int rc = launch_status("wino_f2_small_kernel");
     if (rc && sp.split > 1) sk_mark_failed(dev, s);
     return rc;
@@ -143,26 +153,29 @@ int conv3x3_launch_one(const float* in, const float* U, const float* bnBias, con
   if constexpr (RES) prm.res = res;
   // whole items only (no stream-K tail): the kernel variant without the hand-off in its epilogue
   if (p.items % p.G == 0)
-    return fixed14 ? launch_fused<false, false, RES>(prm, p.G, dev, s) : launch_fused<true, false, RES>(prm, p.G, dev, s);
-  return fixed14 ? launch_fused<false, true, RES>(prm, p.G, dev, s) : launch_fused<true, true, RES>(prm, p.G, dev, s);
+    return fixed14 ? launch_fused<false, false, EPI>(prm, p.G, dev, s) : launch_fused<true, false, EPI>(prm, p.G, dev, s);
+  return fixed14 ? launch_fused<false, true, EPI>(prm, p.G, dev, s) : launch_fused<true, true, EPI>(prm, p.G, dev, s);
 }
 
 // Any batch: batches whose tensors would reach 4 GiB go out as several launches of whole images
 // (a multiple of 64 images each, so that every launch but the last fills its 64-tile blocks).  The residual has
-// K channels, like out: it advances with out, and the per-image limit already covers it.
+// K channels, like out: it advances with out, and the per-image limit already covers it.  POOL: the output image is
+// the pooled one, (H/2+2) x (W/2+2) x K -- smaller than the un-pooled image the limit is taken from.
 // The caller has checked the pointers.
-template <bool RES>
+template <int EPI>
 int conv3x3_launch(const float* in, const float* U, const float* bnBias, const float* bnScale, const float* res,
                    float* out, int N, int H, int W, int C, int K, int relu, hipStream_t s) {
+  constexpr bool RES = EPI == EPI_RES, POOL = EPI == EPI_POOL;
   if (int rc = check_conv3x3_dims(H, W, C, K)) return rc;
   if (N < 1) { set_error("bad batch N=%d", N); return WINO_E_SHAPE; }
   long long step = conv3x3_batch_limit(H, W, C, K);
-  if (N <= step) return conv3x3_launch_one<RES>(in, U, bnBias, bnScale, res, out, N, H, W, C, K, relu, s);
+  if (N <= step) return conv3x3_launch_one<EPI>(in, U, bnBias, bnScale, res, out, N, H, W, C, K, relu, s);
   if (step > 64) step -= step % 64;
-  const size_t in_img = (size_t)(H + 2) * (W + 2) * C, out_img = (size_t)(H + 2) * (W + 2) * K;
+  const size_t in_img = (size_t)(H + 2) * (W + 2) * C;
+  const size_t out_img = POOL ? (size_t)(H / 2 + 2) * (W / 2 + 2) * K : (size_t)(H + 2) * (W + 2) * K;
   for (long long n0 = 0; n0 < N; n0 += step) {
     const int n = (int)(N - n0 < step ? N - n0 : step);
-    if (int rc = conv3x3_launch_one<RES>(in + (size_t)n0 * in_img, U, bnBias, bnScale, RES ? res + (size_t)n0 * out_img : nullptr,
+    if (int rc = conv3x3_launch_one<EPI>(in + (size_t)n0 * in_img, U, bnBias, bnScale, RES ? res + (size_t)n0 * out_img : nullptr,
                                          out + (size_t)n0 * out_img, n, H, W, C, K, relu, s)) return rc;
   }
   return WINO_OK;

@@ -90,9 +90,16 @@ using SmallArgs = std::conditional_t<RES, SmallResParams, SmallParams>;
 // landed, exit.  The product kernel is DIAG = false.
 // RES = the residual epilogue: out = act(scale*conv + bias + res), res padded like out, read by the finishing lane at
 // its store's own offset just before the store (so out may be res); the ReLU follows the add.
-template <int CT, bool GEN = false, bool DIAG = false, bool RES = false>
+// POOL = the pooled epilogue: out = maxpool2x2_s2(act(scale*conv + bias)), [N][H/2+2][W/2+2][K] with its zero ring.  The
+// finishing lane holds the four pixels of its tile (y[c][r][0..3]): the max is taken in-lane behind BN and the ReLU, one
+// 16-byte store per out-channel block instead of four.  GEN = true only (the 14x14 build writes its ring per tile, for a
+// 16x16 output; pooled 14x14 launches take the general form and its flat ring pass).
+// The epilogue is one template argument, EPI = EPI_PLAIN / EPI_RES / EPI_POOL, as in the throughput kernel.
+template <int CT, bool GEN = false, bool DIAG = false, int EPI = EPI_PLAIN>
 __global__ void __launch_bounds__(64 * SMALL_WAVES)
-wino_f2_small_kernel(const SmallArgs<RES> prm) {
+wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
+  constexpr bool RES = EPI == EPI_RES, POOL = EPI == EPI_POOL;
+  static_assert(EPI == EPI_PLAIN || RES || (POOL && GEN), "epilogue form (the pooled one: general form only)");
   static_assert(CT == 1 || CT == 2 || CT == 4, "MFMA tiles per wave");
   constexpr int STAGE = 16 * 16 * 128;                   // one round's patches: 16 tiles x 16 px x 32 channels
   static_assert(2 * STAGE >= (SMALL_WAVES - 1) * CT * 4 * 64 * 16, "the reduction image reuses the stages");
@@ -126,11 +133,12 @@ wino_f2_small_kernel(const SmallArgs<RES> prm) {
   };
   const Geo geo = prm.geo;
   const int Hp = GEN ? geo.Hp : WINO_HW, Wp = GEN ? geo.Wp : WINO_HW;
+  const int Hq = POOL ? (Hp - 2) / 2 + 2 : Hp, Wq = POOL ? (Wp - 2) / 2 + 2 : Wp;   // the output's padded extents
   if constexpr (GEN) {
     // ring pass: the output's zero ring (the next 3x3 layer's padding) as a flat list of 16-byte units -- images x ring
     // pixels x K/4 units -- split over the grid (the 14x14 build writes each tile's share with the tile, below)
     const unsigned upp = (unsigned)K >> 2;
-    const unsigned rpx = 2u * Wp + 2u * (Hp - 2);       // ring pixels per image
+    const unsigned rpx = 2u * Wq + 2u * (Hq - 2);       // ring pixels per image
     const unsigned long long U = (unsigned long long)N * rpx * upp;
     const unsigned long long nblk = (unsigned long long)gridDim.x * gridDim.y * gridDim.z;
     const unsigned long long bid = ((unsigned long long)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
@@ -139,7 +147,7 @@ wino_f2_small_kernel(const SmallArgs<RES> prm) {
     for (unsigned u = u_begin + threadIdx.x; u < u_end; u += 64 * SMALL_WAVES) {
       const unsigned pid = u / upp, unit = u - pid * upp;
       const unsigned n = pid / rpx, qq = pid - n * rpx;
-      const unsigned uW = (unsigned)Wp, uH = (unsigned)Hp;
+      const unsigned uW = (unsigned)Wq, uH = (unsigned)Hq;
       const unsigned y = qq < uW ? 0u : qq < 2 * uW ? uH - 1 : qq < 2 * uW + uH - 2 ? qq - 2 * uW + 1 : qq - 2 * uW - (uH - 2) + 1;
       const unsigned x = qq < uW ? qq : qq < 2 * uW ? qq - uW : qq < 2 * uW + uH - 2 ? 0u : uW - 1;
       *(f32x4*)(prm.out + ((size_t)(n * uH + y) * uW + x) * K + unit * 4) = zero4;
@@ -398,6 +406,23 @@ wino_f2_small_kernel(const SmallArgs<RES> prm) {
   const int oy = 1 + 2 * tc.ty, ox = 1 + 2 * tc.tx;
 #pragma unroll
   for (int c = 0; c < CT; c++) {
+    if constexpr (POOL) {
+      // (odd H or W: the clipped last tile row / column has no pooled output)
+      if (tc.ty >= Hq - 2 || tc.tx >= Wq - 2) break;
+      f32x4 m = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int pp = 0; pp < 4; pp++) {
+        f32x4 val = {y[c][0][pp], y[c][1][pp], y[c][2][pp], y[c][3][pp]};
+        val = sc4[c] * val + bi4[c];
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+          if (relu) val[r] = fmaxf(val[r], 0.f);
+          m[r] = pp == 0 ? val[r] : fmaxf(m[r], val[r]);
+        }
+      }
+      *(f32x4*)(out + ((size_t)(tc.n * Hq + 1 + tc.ty) * Wq + 1 + tc.tx) * K + (kqq * CT + c) * 16 + 4 * h) = m;
+      continue;
+    }
     float* o = out + (size_t)tc.n * Hp * Wp * K + (kqq * CT + c) * 16 + 4 * h;
 #pragma unroll
     for (int pp = 0; pp < 4; pp++) {

@@ -57,7 +57,8 @@ extern "C" {
  * wino_basic_block_workspace_bytes_hw, wino_basic_block_hw, wino_basic_block_prepare_hw, wino_s2_proj_elems,
  * wino_s2_proj_pack, wino_conv3x3_s2_proj_bn_relu_hw, wino_basic_block_s2_workspace_bytes_hw, wino_basic_block_s2_hw,
  * wino_basic_block_s2_prepare_hw, wino_stem_filter_elems, wino_stem_filter_pack, wino_stem_hw, wino_stem_plan,
- * wino_head_elems, wino_head_pack, wino_head_workspace_bytes, wino_head_prepare, wino_avgpool_fc_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_head_elems, wino_head_pack, wino_head_workspace_bytes, wino_head_prepare, wino_avgpool_fc_hw,
+ * wino_conv3x3_bn_relu_pool_hw, wino_image_pack_hw, wino_avgpool7_flatten_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -529,6 +530,35 @@ size_t wino_head_workspace_bytes(int N, int C, int classes);
 int wino_head_prepare(int N, int C, int classes, wino_stream_t s);
 int wino_avgpool_fc_hw(const float* feat, const float* packed, float* out, int N, int H, int W, int C, int classes,
                        int in_padded, void* workspace, size_t workspace_bytes, wino_stream_t s);
+
+/* ---- VGG: the pooled 3x3 layer and the two memory-bound kernels around the convolutions --------------------------
+ * wino_conv3x3_bn_relu_pool_hw, one launch:  out = maxpool2x2_s2(act(bnScale*conv3x3(in, U) + bnBias))
+ *   in   [N][H+2][W+2][C] with a zero ring, U from wino_filter_transform_f2: as for wino_conv3x3_bn_relu_hw
+ *   out  [N][H/2+2][W/2+2][K], the pooled map at [1..H/2][1..W/2], its ring written 0 (what the next 3x3 layer reads)
+ * H/2 and W/2 floor (torch's MaxPool2d(2, 2)): for odd H or W the clipped last tile row / column is dropped.  An
+ * F(2x2) tile is one pooling window, so the max is taken in the epilogue, in the lane that holds the tile, after the
+ * stream-K gather, BN and the ReLU; the un-pooled activation never reaches memory.  The launch takes exactly the plan
+ * of the plain layer of the same (N, H, W, C, K): wino_conv3x3_plan / _small_plan2 describe it, wino_conv3x3_prepare_hw
+ * reserves its scratch.  Constraints: those of wino_conv3x3_bn_relu_hw, and H, W >= 2; in and out must not overlap
+ * (WINO_E_ARG).  Any batch (tensors of 4 GiB and more go out as several launches of whole images).
+ *
+ * wino_image_pack_hw, one launch:  x [N][Cin][H][W] (NCHW, as images come from torch) ->
+ *   out [N][H+2][W+2][Cpad] with channels Cin .. Cpad-1 and the ring written 0 -- the first 3x3 layer's input; its
+ *   filter is zero-padded to [K][Cpad][3][3] before wino_filter_transform_f2.  1 <= Cin <= Cpad, Cpad % 8 == 0,
+ *   H, W >= 1; one image's input and output each below 2^31 elements.  x and out must not overlap.
+ *
+ * wino_avgpool7_flatten_hw, one launch:  torch's AdaptiveAvgPool2d((7, 7)) and flatten
+ *   feat [N][H][W][C], or [N][H+2][W+2][C] with in_padded = 1 (the ring is not read)
+ *   out  [N][49*C] in (h, w, c) order: bin (i, j) is the mean over rows floor(i*H/7) .. ceil((i+1)*H/7) - 1 and the
+ *        same for columns (a 1x1 map is replicated 49 times).  The first FC's weight columns are permuted from torch's
+ *        (c, h, w) to this order once, at pack time.
+ *   H, W >= 1 with H * W < 2^24, C % 4 == 0; one image's input and output each below 2^31 elements (any batch: every
+ *   image is addressed from its own 64-bit base).  feat and out must not overlap. */
+int wino_conv3x3_bn_relu_pool_hw(const float* in, const float* U, const float* bnBias, const float* bnScale,
+                                 float* out, int N, int H, int W, int C, int K, int relu, wino_stream_t s);
+int wino_image_pack_hw(const float* x, float* out, int N, int Cin, int H, int W, int Cpad, wino_stream_t s);
+int wino_avgpool7_flatten_hw(const float* feat, float* out, int N, int H, int W, int C, int in_padded,
+                             wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
