@@ -2,7 +2,7 @@
 
 Python side of the drop-in boundary: a ctypes binding of the C-ABI declared in
 ``include/winograd_mi355x.h`` (the same shared library the C ``./Test`` driver
-links), plus thin operator wrappers that take torch tensors.  PyTorch is only
+links; the binding is ``_abi.py``), plus thin operator wrappers that take torch tensors.  PyTorch is only
 plumbing here (device memory, streams, ``torch.distributed``); every compute
 call goes to the hand-written HIP kernels in ``csrc/``.  There is NO CPU or
 eager fallback: if the library is missing or no GPU is visible, calls raise.
@@ -13,192 +13,12 @@ The directory name contains a hyphen, so import it through
 from __future__ import annotations
 
 import ctypes
-import os
-from ctypes import c_char_p, c_int, c_long, c_size_t, c_void_p, POINTER
+from ctypes import c_int, c_long, c_void_p
 
 import torch  # imported first on purpose: the library then binds to torch's HIP runtime
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.path.join(_HERE, "libwinograd_mi355x.so")
-
-# every symbol include/*.h declares (tests/test_abi.py checks the export table against it)
-ABI_SYMBOLS = [
-    "wino_abi_version", "wino_last_error_string", "wino_device_count", "wino_set_device",
-    "wino_device_name", "wino_malloc", "wino_free", "wino_memset", "wino_memcpy_h2d",
-    "wino_memcpy_d2h", "wino_memcpy_d2d", "wino_device_synchronize", "wino_stream_create",
-    "wino_stream_destroy", "wino_stream_synchronize", "wino_event_create", "wino_event_destroy",
-    "wino_event_record", "wino_event_elapsed_ms", "wino_filter_f2_elems", "wino_filter_f2_index",
-    "wino_filter_transform_f2", "wino_filter_import_f4", "wino_conv3x3_bn_relu", "wino_conv3x3_prepare",
-    "wino_conv3x3_bn_relu_hw", "wino_conv3x3_prepare_hw", "wino_conv3x3_direct_hw", "wino_conv3x3_plan",
-    "wino_conv1x1_prepare", "wino_conv1x1_plan", "wino_conv1x1_bn_ex_hw", "wino_residual_block_hw",
-    "wino_residual_block_workspace_bytes_hw",
-    "wino_conv3x3_f4_bn_relu", "wino_conv3x3_f4_workspace_bytes",
-    "wino_conv3x3_direct", "wino_conv1x1_bn", "wino_conv1x1_bn_ex", "wino_conv1x1_direct",
-    "wino_residual_block", "wino_residual_block_workspace_bytes", "wino_driver_set_batch",
-    "wino_driver_set_gpus", "wino_driver_set_quiet", "wino_driver_get_batch",
-    "wino_driver_get_gpus", "wino_driver_last_result", "wino_driver_last_output", "wino_driver_pack_times",
-    "wino_driver_set_gpu_alias", "wino_driver_set_stdout_compat", "wino_driver_get_stdout_compat",
-    "wino_driver_cpu_baseline", "wino_last_status_name", "wino_debug_reload_knobs",
-    "wino_residual_block_prepare", "wino_residual_block_prepare_hw", "wino_diag_conv3x3_clock",
-    "wino_debug_tickets_in_use", "wino_stream_check", "wino_stream_reset_scratch", "wino_debug_poison_ticket",
-    "wino_diag_last_clock", "wino_conv3x3_small_plan", "wino_conv1x1_small_plan", "wino_conv3x3_plan_groups", "wino_conv1x1_small_plan2",
-    "wino_conv3x3_small_plan2", "wino_debug_conv1x1_models",
-    "wino_proj_tail_elems", "wino_proj_tail_pack", "wino_proj_block_workspace_bytes_hw", "wino_proj_block_prepare_hw",
-    "wino_proj_block_hw", "wino_proj_tail_plan",
-    "wino_conv3x3_s2_bn_relu_hw", "wino_conv3x3_s2_prepare_hw", "wino_conv3x3_s2_plan",
-    "wino_proj_block_v15_workspace_bytes_hw", "wino_proj_block_v15_hw", "wino_proj_block_v15_prepare_hw",
-    "wino_conv3x3_bn_add_relu_hw", "wino_basic_block_workspace_bytes_hw", "wino_basic_block_hw",
-    "wino_basic_block_prepare_hw",
-    "wino_s2_proj_elems", "wino_s2_proj_pack", "wino_conv3x3_s2_proj_bn_relu_hw", "wino_basic_block_s2_workspace_bytes_hw",
-    "wino_basic_block_s2_hw", "wino_basic_block_s2_prepare_hw",
-    "wino_stem_filter_elems", "wino_stem_filter_pack", "wino_stem_hw", "wino_stem_plan", "wino_head_elems",
-    "wino_head_pack", "wino_head_workspace_bytes", "wino_head_prepare", "wino_avgpool_fc_hw",
-    "wino_conv3x3_bn_relu_pool_hw", "wino_image_pack_hw", "wino_avgpool7_flatten_hw",
-    # reference entry points + helpers (Kernel*.h, util.h)
-    "kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in",
-    "kernel_256_1_out", "get_parameter", "transpose", "getTimeMicroseconds64", "output_checker",
-    "output_checker_accumulate",
-]
-
-
-class WinoError(RuntimeError):
-    pass
-
-
-class DriverResult(ctypes.Structure):
-    _fields_ = [("mine_us", ctypes.c_double), ("comparator_us", ctypes.c_double),
-                ("max_abs_err", ctypes.c_double), ("max_rel_err", ctypes.c_double),
-                ("error_cnt", c_long), ("flops", ctypes.c_double), ("N", c_int), ("gpus", c_int),
-                ("steady_us", ctypes.c_double)]
-
-
-class CpuBaselineResult(ctypes.Structure):
-    _fields_ = [("us", ctypes.c_double), ("gflops", ctypes.c_double), ("threads", c_int), ("reps", c_int),
-                ("max_abs_diff", ctypes.c_double), ("max_rel_diff", ctypes.c_double)]
-
-
-_lib = None
-
-
-def lib() -> ctypes.CDLL:
-    """Load libwinograd_mi355x.so (built in-tree by `make` / __graft_entry__.build())."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise WinoError(
-            f"{LIB_PATH} not found: build it with `make` (or __graft_entry__.build()). "
-            "There is no fallback path.")
-    L = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    fp = c_void_p
-    L.wino_last_error_string.restype = c_char_p
-    L.wino_filter_f2_elems.restype = c_size_t
-    L.wino_filter_f2_elems.argtypes = [c_int, c_int]
-    L.wino_filter_f2_index.restype = c_long
-    L.wino_filter_f2_index.argtypes = [c_int] * 5
-    L.wino_filter_transform_f2.argtypes = [fp, fp, c_int, c_int, c_void_p]
-    L.wino_filter_import_f4.argtypes = [fp, fp, c_int, c_int, c_void_p]
-    L.wino_conv3x3_bn_relu.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, c_void_p]
-    L.wino_conv3x3_prepare.argtypes = [c_int, c_int, c_int, c_void_p]
-    L.wino_conv1x1_prepare.argtypes = [c_long, c_int, c_int, c_void_p]
-    L.wino_conv1x1_plan.argtypes = [c_long, c_int, c_int, c_int] + [POINTER(c_int)] * 5
-    L.wino_conv3x3_bn_relu_hw.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    L.wino_conv3x3_prepare_hw.argtypes = [c_int, c_int, c_int, c_int, c_int, c_void_p]
-    L.wino_conv3x3_f4_workspace_bytes.restype = c_size_t
-    L.wino_conv3x3_f4_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.wino_conv3x3_f4_bn_relu.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, fp, c_size_t, c_void_p]
-    L.wino_conv3x3_plan.argtypes = [c_int] * 6 + [POINTER(c_int), POINTER(c_int), POINTER(c_long), POINTER(c_int)]
-    L.wino_conv3x3_direct_hw.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    L.wino_conv3x3_direct.argtypes = [fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, c_void_p]
-    L.wino_conv1x1_bn.argtypes = [fp, fp, fp, fp, fp, c_long, c_int, c_int, c_int, c_void_p]
-    L.wino_conv1x1_direct.argtypes = [fp, fp, fp, fp, fp, c_long, c_int, c_int, c_int, c_void_p]
-    L.wino_conv1x1_bn_ex.argtypes = [fp, fp, fp, fp, fp, fp, c_long, c_int, c_int, c_int, c_void_p]
-    L.wino_residual_block_workspace_bytes.restype = c_size_t
-    L.wino_residual_block_workspace_bytes.argtypes = [c_int, c_int]
-    L.wino_residual_block.argtypes = [fp] * 11 + [c_int, c_int, c_int, fp, c_size_t, c_void_p]
-    L.wino_conv1x1_bn_ex_hw.argtypes = [fp, fp, fp, fp, fp, fp, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]
-    L.wino_residual_block_workspace_bytes_hw.restype = c_size_t
-    L.wino_residual_block_workspace_bytes_hw.argtypes = [c_int, c_int, c_int, c_int]
-    L.wino_residual_block_hw.argtypes = [fp] * 11 + [c_int] * 5 + [fp, c_size_t, c_void_p]
-    L.wino_device_count.argtypes = [POINTER(c_int)]
-    L.wino_driver_last_result.argtypes = [POINTER(DriverResult)]
-    L.wino_driver_set_batch.argtypes = [c_int]
-    L.wino_driver_set_gpus.argtypes = [c_int]
-    L.wino_driver_set_quiet.argtypes = [c_int]
-    L.wino_driver_set_gpu_alias.argtypes = [c_int]
-    L.wino_driver_set_stdout_compat.argtypes = [c_int]
-    L.wino_driver_pack_times.argtypes = [ctypes.c_uint64, ctypes.c_uint64]
-    L.wino_driver_last_output.restype = POINTER(ctypes.c_float)
-    L.wino_driver_last_output.argtypes = [POINTER(c_size_t)]
-    L.wino_driver_cpu_baseline.argtypes = [POINTER(CpuBaselineResult)]
-    L.wino_last_status_name.restype = c_char_p
-    L.wino_residual_block_prepare.argtypes = [c_int, c_int, c_int, c_void_p]
-    L.wino_residual_block_prepare_hw.argtypes = [c_int] * 5 + [c_void_p]
-    L.wino_diag_conv3x3_clock.argtypes = [fp] * 5 + [c_int] * 3 + [fp, POINTER(c_int), c_void_p]
-    L.wino_stream_check.argtypes = [c_void_p]
-    L.wino_stream_reset_scratch.argtypes = [c_void_p]
-    L.wino_debug_poison_ticket.argtypes = [c_void_p, c_long, ctypes.c_uint]
-    L.wino_diag_last_clock.argtypes = [c_int, c_void_p, POINTER(ctypes.c_ulonglong)]
-    L.wino_conv3x3_small_plan.argtypes = [c_int] * 6 + [POINTER(c_int)] * 4
-    L.wino_conv3x3_small_plan2.argtypes = [c_int] * 6 + [POINTER(c_int)] * 5
-    L.wino_debug_conv1x1_models.argtypes = [c_long, c_int, c_int, c_int, POINTER(ctypes.c_double), POINTER(ctypes.c_double)]
-    L.wino_conv1x1_small_plan.argtypes = [c_long, c_int, c_int, c_int] + [POINTER(c_int)] * 3
-    L.wino_conv1x1_small_plan2.argtypes = [c_long, c_int, c_int, c_int] + [POINTER(c_int)] * 5
-    L.wino_conv3x3_plan_groups.argtypes = [c_int] * 6 + [POINTER(c_int)] * 4
-    L.wino_proj_tail_elems.restype = c_size_t
-    L.wino_proj_tail_elems.argtypes = [c_int] * 3
-    L.wino_proj_tail_pack.argtypes = [fp] * 7 + [c_int] * 3 + [c_void_p]
-    L.wino_proj_block_workspace_bytes_hw.restype = c_size_t
-    L.wino_proj_block_workspace_bytes_hw.argtypes = [c_int] * 4
-    L.wino_proj_block_prepare_hw.argtypes = [c_int] * 7 + [c_void_p]
-    L.wino_proj_block_hw.argtypes = [fp] * 9 + [c_int] * 7 + [fp, c_size_t, c_void_p]
-    L.wino_proj_tail_plan.argtypes = [c_int] * 8 + [POINTER(c_int)] * 2
-    L.wino_conv3x3_s2_bn_relu_hw.argtypes = [fp] * 5 + [c_int] * 6 + [c_void_p]
-    L.wino_conv3x3_s2_prepare_hw.argtypes = [c_int] * 5 + [c_void_p]
-    L.wino_conv3x3_s2_plan.argtypes = [c_int] * 6 + [POINTER(c_int)]
-    L.wino_proj_block_v15_workspace_bytes_hw.restype = c_size_t
-    L.wino_proj_block_v15_workspace_bytes_hw.argtypes = [c_int] * 4
-    L.wino_proj_block_v15_hw.argtypes = [fp] * 9 + [c_int] * 6 + [fp, c_size_t, c_void_p]
-    L.wino_proj_block_v15_prepare_hw.argtypes = [c_int] * 6 + [c_void_p]
-    L.wino_conv3x3_bn_add_relu_hw.argtypes = [fp] * 6 + [c_int] * 6 + [c_void_p]
-    L.wino_basic_block_workspace_bytes_hw.restype = c_size_t
-    L.wino_basic_block_workspace_bytes_hw.argtypes = [c_int] * 4
-    L.wino_basic_block_hw.argtypes = [fp] * 8 + [c_int] * 4 + [fp, c_size_t, c_void_p]
-    L.wino_basic_block_prepare_hw.argtypes = [c_int] * 4 + [c_void_p]
-    L.wino_s2_proj_elems.restype = c_size_t
-    L.wino_s2_proj_elems.argtypes = [c_int] * 2
-    L.wino_s2_proj_pack.argtypes = [fp] * 7 + [c_int] * 2 + [c_void_p]
-    L.wino_conv3x3_s2_proj_bn_relu_hw.argtypes = [fp] * 4 + [c_int] * 5 + [c_void_p]
-    L.wino_basic_block_s2_workspace_bytes_hw.restype = c_size_t
-    L.wino_basic_block_s2_workspace_bytes_hw.argtypes = [c_int] * 4
-    L.wino_basic_block_s2_hw.argtypes = [fp] * 6 + [c_int] * 5 + [fp, c_size_t, c_void_p]
-    L.wino_basic_block_s2_prepare_hw.argtypes = [c_int] * 5 + [c_void_p]
-    L.wino_stem_filter_elems.restype = c_size_t
-    L.wino_stem_filter_elems.argtypes = [c_int]
-    L.wino_stem_filter_pack.argtypes = [fp] * 4 + [c_int, c_void_p]
-    L.wino_stem_hw.argtypes = [fp] * 3 + [c_int] * 5 + [c_void_p]
-    L.wino_stem_plan.argtypes = [c_int] * 5 + [POINTER(c_int)]
-    L.wino_head_elems.restype = c_size_t
-    L.wino_head_elems.argtypes = [c_int] * 2
-    L.wino_head_pack.argtypes = [fp] * 3 + [c_int] * 2 + [c_void_p]
-    L.wino_head_workspace_bytes.restype = c_size_t
-    L.wino_head_workspace_bytes.argtypes = [c_int] * 3
-    L.wino_head_prepare.argtypes = [c_int] * 3 + [c_void_p]
-    L.wino_avgpool_fc_hw.argtypes = [fp] * 3 + [c_int] * 6 + [fp, c_size_t, c_void_p]
-    L.wino_conv3x3_bn_relu_pool_hw.argtypes = [fp] * 5 + [c_int] * 6 + [c_void_p]
-    L.wino_image_pack_hw.argtypes = [fp] * 2 + [c_int] * 5 + [c_void_p]
-    L.wino_avgpool7_flatten_hw.argtypes = [fp] * 2 + [c_int] * 5 + [c_void_p]
-    for name in ("kernel_128", "kernel_256", "kernel_128_1_in", "kernel_128_1_out",
-                 "kernel_256_1_in", "kernel_256_1_out"):
-        getattr(L, name).restype = c_int
-        getattr(L, name).argtypes = []
-    _lib = L
-    return L
-
-
-def _check(rc: int, what: str) -> None:
-    if rc != 0:
-        raise WinoError(f"{what} failed (rc={rc}): {lib().wino_last_error_string().decode()}")
+from ._abi import (ABI_SYMBOLS, LIB_PATH, SIGNATURES, CpuBaselineResult, DriverResult, WinoError,  # noqa: F401
+                   _check, lib)
 
 
 def _dev(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -249,32 +69,31 @@ def last_clock_ghz(kernel: int = 0):
     return cyc / ticks * 0.1, int(cyc), ticks / 100.0
 
 
+def _plan_query(name: str, n: int, *args):
+    """A host-side plan query of the library: `args`, then n int out-parameters, returned as a tuple."""
+    v = [c_int(0) for _ in range(n)]
+    _check(getattr(lib(), name)(*args, *[ctypes.byref(x) for x in v]), name)
+    return tuple(int(x.value) for x in v)
+
+
 def small_plan_3x3(N: int, C: int, K: int, cus: int = 256, H: int = 14, W: int = 14):
     """(use, point_rows, split, workgroups) of the 3x3 latency kernel for this shape (host-side)."""
-    v = [c_int(0) for _ in range(4)]
-    _check(lib().wino_conv3x3_small_plan(N, H, W, C, K, cus, *[ctypes.byref(x) for x in v]), "wino_conv3x3_small_plan")
-    return tuple(int(x.value) for x in v)
+    return _plan_query("wino_conv3x3_small_plan", 4, N, H, W, C, K, cus)
 
 
 def small_plan_3x3_full(N: int, C: int, K: int, cus: int = 256, H: int = 14, W: int = 14):
     """(use, point_rows, split, col_tiles, workgroups) of the 3x3 latency kernel (host-side)."""
-    v = [c_int(0) for _ in range(5)]
-    _check(lib().wino_conv3x3_small_plan2(N, H, W, C, K, cus, *[ctypes.byref(x) for x in v]), "wino_conv3x3_small_plan2")
-    return tuple(int(x.value) for x in v)
+    return _plan_query("wino_conv3x3_small_plan2", 5, N, H, W, C, K, cus)
 
 
 def small_plan_1x1(M: int, Cin: int, Kout: int, cus: int = 256):
     """(use, k_split, workgroups) of the 1x1 latency form for a plain layer of this shape (host-side)."""
-    v = [c_int(0) for _ in range(3)]
-    _check(lib().wino_conv1x1_small_plan(M, Cin, Kout, cus, *[ctypes.byref(x) for x in v]), "wino_conv1x1_small_plan")
-    return tuple(int(x.value) for x in v)
+    return _plan_query("wino_conv1x1_small_plan", 3, M, Cin, Kout, cus)
 
 
 def small_plan_1x1_full(M: int, Cin: int, Kout: int, cus: int = 256):
     """(use, k_split, row_tiles, col_tiles, workgroups) of the 1x1 latency form (host-side)."""
-    v = [c_int(0) for _ in range(5)]
-    _check(lib().wino_conv1x1_small_plan2(M, Cin, Kout, cus, *[ctypes.byref(x) for x in v]), "wino_conv1x1_small_plan2")
-    return tuple(int(x.value) for x in v)
+    return _plan_query("wino_conv1x1_small_plan2", 5, M, Cin, Kout, cus)
 
 
 def _on_current_device(*tensors) -> None:
@@ -315,6 +134,41 @@ def _workspace(t, need: int, device) -> torch.Tensor:
     return t
 
 
+def _prepare(name: str, *dims) -> None:
+    """A *_prepare entry point of the library: the shape as ints, then the current stream."""
+    _check(getattr(lib(), name)(*(int(d) for d in dims), _stream()), name)
+
+
+def _ws_args(ws: torch.Tensor):
+    """(pointer, bytes): how every entry point takes a workspace."""
+    return ws.data_ptr(), ws.numel() * 4
+
+
+def _bn_vecs(*pairs):
+    """Folded BN (bias, scale) pairs -> their vectors in the C argument order, each checked by _dev."""
+    return [_dev(v, "bn") for pair in pairs for v in pair]
+
+
+def _out_hw(h: int, w: int, stride: int):
+    """The output grid of a centred (pad = kernel // 2) convolution or pool of this stride."""
+    return (h - 1) // stride + 1, (w - 1) // stride + 1
+
+
+def _operands_3x3(inp, U, bn_bias, bn_scale, min_hp: int = 3, what: str = "inp must be [N][H+2][W+2][C]"):
+    """The opening of the Winograd 3x3 layers: the four operands checked by _dev, the padded input's rank and minimum
+    extent, and U / the BN vectors against C, K.  Returns (x, U, bias, scale, N, Hp, Wp, C, K)."""
+    x = _dev(inp, "inp")
+    U = _dev(U, "U")
+    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
+    shape = x.shape   # (read once: every .shape builds a new torch.Size, and this is the launch path)
+    if len(shape) != 4 or shape[1] < min_hp or shape[2] < min_hp:
+        raise WinoError(what)
+    N, Hp, Wp, C, K = int(shape[0]), int(shape[1]), int(shape[2]), int(shape[3]), int(b.numel())
+    if U.numel() != 16 * C * K or s.numel() != K:
+        raise WinoError("U / bn vectors do not match C, K")
+    return x, U, b, s, N, Hp, Wp, C, K
+
+
 # --------------------------------------------------------------------------- operators
 def filter_transform_f2(w_kcrs: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
     """[K][C][3][3] taps -> packed F(2x2,3x3) filter buffer (opaque layout, 16*C*K floats; `out`: the caller's)."""
@@ -346,14 +200,7 @@ def conv3x3_bn_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor,
     """inp [N][H+2][W+2][C] -> out [N][H+2][W+2][K] (interior H x W, zero ring).  One HIP launch.
     [N][16][16][C] is the reference's 14x14 stage (wino_conv3x3_bn_relu); any other even H, W goes
     through wino_conv3x3_bn_relu_hw."""
-    x = _dev(inp, "inp")
-    U = _dev(U, "U")
-    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
-    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
-        raise WinoError("inp must be [N][H+2][W+2][C]")
-    N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(b.numel())
-    if U.numel() != 16 * C * K or s.numel() != K:
-        raise WinoError("U / bn vectors do not match C, K")
+    x, U, b, s, N, Hp, Wp, C, K = _operands_3x3(inp, U, bn_bias, bn_scale)
     out = _output(out, (N, Hp, Wp, K), x.device)
     _on_current_device(x, U, b, s, out)
     if Hp == 16 and Wp == 16:
@@ -382,7 +229,7 @@ def conv3x3_f4_bn_relu(inp: torch.Tensor, u36: torch.Tensor, bn_bias: torch.Tens
     ws = _workspace(workspace, lib().wino_conv3x3_f4_workspace_bytes(N, C, K), x.device)
     _on_current_device(x, u, b, s, out, ws)
     _check(lib().wino_conv3x3_f4_bn_relu(x.data_ptr(), u.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
-                                         N, C, K, int(relu), ws.data_ptr(), ws.numel() * 4, _stream()),
+                                         N, C, K, int(relu), *_ws_args(ws), _stream()),
            "wino_conv3x3_f4_bn_relu")
     return out
 
@@ -390,8 +237,7 @@ def conv3x3_f4_bn_relu(inp: torch.Tensor, u36: torch.Tensor, bn_bias: torch.Tens
 def conv3x3_prepare(N: int, C: int, K: int, H: int = 14, W: int = 14) -> None:
     """Allocate the library-owned stream-K scratch of conv3x3_bn_relu for this shape on the current
     device and stream ahead of time (needed before capturing the call into a HIP graph)."""
-    _check(lib().wino_conv3x3_prepare_hw(int(N), int(H), int(W), int(C), int(K), _stream()),
-           "wino_conv3x3_prepare_hw")
+    _prepare("wino_conv3x3_prepare_hw", N, H, W, C, K)
 
 
 def conv3x3_direct(inp, w_kcrs, bn_bias, bn_scale, relu: bool = True, out=None) -> torch.Tensor:
@@ -429,8 +275,7 @@ RELU, A_PADDED, C_PADDED, ADD_RESIDUAL = 1, 2, 4, 8  # WINO_* flag bits of wino_
 
 def residual_block_prepare(N: int, C4: int, Cm: int, H: int = 14, W: int = 14) -> None:
     """Allocate the scratch of residual_block's three launches for the current stream (before graph capture)."""
-    _check(lib().wino_residual_block_prepare_hw(int(N), int(H), int(W), int(C4), int(Cm), _stream()),
-           "wino_residual_block_prepare_hw")
+    _prepare("wino_residual_block_prepare_hw", N, H, W, C4, Cm)
 
 
 def conv3x3_clock_ghz(inp, U, bn_bias, bn_scale, out) -> float:
@@ -456,7 +301,7 @@ def conv3x3_clock_ghz(inp, U, bn_bias, bn_scale, out) -> float:
 
 def conv1x1_prepare(M: int, Cin: int, Kout: int) -> None:
     """Allocate the 1x1 layer's stream-K scratch for the current stream (before graph capture)."""
-    _check(lib().wino_conv1x1_prepare(int(M), int(Cin), int(Kout), _stream()), "wino_conv1x1_prepare")
+    _prepare("wino_conv1x1_prepare", M, Cin, Kout)
 
 
 def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, hw=None) -> torch.Tensor:
@@ -500,15 +345,13 @@ def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, 
     else:
         _out(out, None, "out")   # unpadded: any contiguous view of M*Kout values ([M][Kout] or [N][H][W][Kout])
     _on_current_device(a, bm, b, s, r, out)
+    args = (a.data_ptr(), bm.data_ptr(), b.data_ptr(), s.data_ptr(), r.data_ptr() if r is not None else None,
+            out.data_ptr())
     if padded and (H, W) != (14, 14):
-        _check(lib().wino_conv1x1_bn_ex_hw(a.data_ptr(), bm.data_ptr(), b.data_ptr(), s.data_ptr(),
-                                           r.data_ptr() if r is not None else None, out.data_ptr(),
-                                           M // (H * W), H, W, Cin, Kout, int(flags), _stream()),
+        _check(lib().wino_conv1x1_bn_ex_hw(*args, M // (H * W), H, W, Cin, Kout, int(flags), _stream()),
                "wino_conv1x1_bn_ex_hw")
     else:
-        _check(lib().wino_conv1x1_bn_ex(a.data_ptr(), bm.data_ptr(), b.data_ptr(), s.data_ptr(),
-                                        r.data_ptr() if r is not None else None, out.data_ptr(),
-                                        M, Cin, Kout, int(flags), _stream()), "wino_conv1x1_bn_ex")
+        _check(lib().wino_conv1x1_bn_ex(*args, M, Cin, Kout, int(flags), _stream()), "wino_conv1x1_bn_ex")
     return out
 
 
@@ -522,7 +365,7 @@ def residual_block(x, w1, bn1, U2, bn2, w3, bn3, out=None, workspace=None) -> to
     N, H, W, C4 = (int(v) for v in x.shape)
     w1, w3, U2 = _dev(w1, "w1"), _dev(w3, "w3"), _dev(U2, "U2")
     Cm = int(w1.shape[1])
-    vecs = [_dev(v, "bn") for pair in (bn1, bn2, bn3) for v in pair]
+    vecs = _bn_vecs(bn1, bn2, bn3)
     workspace = _workspace(workspace, lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm), x.device)
     out = _output(out, x.shape, x.device)
     _on_current_device(x, w1, w3, U2, out, workspace, *vecs)
@@ -530,11 +373,11 @@ def residual_block(x, w1, bn1, U2, bn2, w3, bn3, out=None, workspace=None) -> to
             U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(),
             w3.data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr(), out.data_ptr())
     if (H, W) == (14, 14):
-        _check(lib().wino_residual_block(*args, N, C4, Cm, workspace.data_ptr(), workspace.numel() * 4, _stream()),
+        _check(lib().wino_residual_block(*args, N, C4, Cm, *_ws_args(workspace), _stream()),
                "wino_residual_block")
     else:
-        _check(lib().wino_residual_block_hw(*args, N, H, W, C4, Cm, workspace.data_ptr(),
-                                            workspace.numel() * 4, _stream()), "wino_residual_block_hw")
+        _check(lib().wino_residual_block_hw(*args, N, H, W, C4, Cm, *_ws_args(workspace), _stream()),
+               "wino_residual_block_hw")
     return out
 
 
@@ -545,7 +388,7 @@ def proj_tail_pack(w3, bn3, wp, bnp, out=None) -> torch.Tensor:
     """The projection block's fused last layer: w3 [Cm][C4], wp [Cin][C4] and their folded BNs (bias, scale) packed
     into one opaque buffer (wino_proj_tail_pack) -- the analogue of filter_transform_f2 for U2."""
     w3, wp = _dev(w3, "w3"), _dev(wp, "wp")
-    vecs = [_dev(v, "bn") for pair in (bn3, bnp) for v in pair]
+    vecs = _bn_vecs(bn3, bnp)
     Cm, C4, Cin = int(w3.shape[0]), int(w3.shape[1]), int(wp.shape[0])
     if w3.dim() != 2 or wp.dim() != 2 or int(wp.shape[1]) != C4 or any(v.numel() != C4 for v in vecs):
         raise WinoError("w3 must be [Cm][C4], wp [Cin][C4], the BN vectors [C4]")
@@ -560,22 +403,14 @@ def proj_tail_pack(w3, bn3, wp, bnp, out=None) -> torch.Tensor:
     return packed
 
 
-def _proj_out_hw(Hin: int, Win: int, stride: int):
-    return (Hin - 1) // stride + 1, (Win - 1) // stride + 1
-
-
 def proj_block_prepare(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int, stride: int) -> None:
     """Allocate the scratch of proj_block's three launches for the current stream (before graph capture)."""
-    _check(lib().wino_proj_block_prepare_hw(int(N), int(Hin), int(Win), int(Cin), int(Cm), int(C4), int(stride),
-                                            _stream()), "wino_proj_block_prepare_hw")
+    _prepare("wino_proj_block_prepare_hw", N, Hin, Win, Cin, Cm, C4, stride)
 
 
 def proj_tail_plan(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int, stride: int, cus: int = 256):
     """(first, tail): the FORM_* each of the projection block's two 1x1 launches takes (host-side)."""
-    v = [c_int(0), c_int(0)]
-    _check(lib().wino_proj_tail_plan(N, Hin, Win, Cin, Cm, C4, stride, cus, *[ctypes.byref(x) for x in v]),
-           "wino_proj_tail_plan")
-    return int(v[0].value), int(v[1].value)
+    return _plan_query("wino_proj_tail_plan", 2, N, Hin, Win, Cin, Cm, C4, stride, cus)
 
 
 def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None) -> torch.Tensor:
@@ -595,14 +430,14 @@ def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None)
     C4 = tail.numel() // (Cm + Cin + 2)
     if int(stride) not in (1, 2):
         raise WinoError(f"stride must be 1 or 2, got {stride}")
-    H, W = _proj_out_hw(Hin, Win, int(stride))
-    vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
+    H, W = _out_hw(Hin, Win, int(stride))
+    vecs = _bn_vecs(bn1, bn2)
     workspace = _workspace(workspace, lib().wino_proj_block_workspace_bytes_hw(N, H, W, Cm), x.device)
     out = _output(out, (N, H, W, C4), x.device)
     _on_current_device(x, w1, U2, tail, out, workspace, *vecs)
     _check(lib().wino_proj_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), U2.data_ptr(),
                                     vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(), out.data_ptr(), N, Hin, Win,
-                                    Cin, Cm, C4, int(stride), workspace.data_ptr(), workspace.numel() * 4, _stream()),
+                                    Cin, Cm, C4, int(stride), *_ws_args(workspace), _stream()),
            "wino_proj_block_hw")
     return out
 
@@ -619,10 +454,6 @@ def filter_pack_s2(w_kcrs: torch.Tensor, out: torch.Tensor | None = None) -> tor
     return _out(out, taps.shape, "out").copy_(taps)
 
 
-def _s2_out_hw(Hin: int, Win: int):
-    return (Hin - 1) // 2 + 1, (Win - 1) // 2 + 1
-
-
 def conv3x3_s2_bn_relu(inp: torch.Tensor, w_taps: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
                        relu: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
     """Stride-2, pad-1 3x3 conv + folded BN (+ReLU): inp [N][Hin+2][Win+2][C] (zero ring) -> out [N][H+2][W+2][K]
@@ -637,7 +468,7 @@ def conv3x3_s2_bn_relu(inp: torch.Tensor, w_taps: torch.Tensor, bn_bias: torch.T
     K = int(w.shape[3])
     if b.numel() != K or s.numel() != K:
         raise WinoError("bn vectors do not match K")
-    H, W = _s2_out_hw(Hin, Win)
+    H, W = _out_hw(Hin, Win, 2)
     out = _output(out, (N, H + 2, W + 2, K), x.device)
     _on_current_device(x, w, b, s, out)
     _check(lib().wino_conv3x3_s2_bn_relu_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
@@ -647,22 +478,17 @@ def conv3x3_s2_bn_relu(inp: torch.Tensor, w_taps: torch.Tensor, bn_bias: torch.T
 
 def conv3x3_s2_prepare(N: int, Hin: int, Win: int, C: int, K: int) -> None:
     """Allocate the stride-2 3x3 layer's stream-K scratch for the current stream (before graph capture)."""
-    _check(lib().wino_conv3x3_s2_prepare_hw(int(N), int(Hin), int(Win), int(C), int(K), _stream()),
-           "wino_conv3x3_s2_prepare_hw")
+    _prepare("wino_conv3x3_s2_prepare_hw", N, Hin, Win, C, K)
 
 
 def conv3x3_s2_plan(N: int, Hin: int, Win: int, C: int, K: int, cus: int = 256) -> int:
     """The FORM_* the stride-2 3x3 layer takes on a device with `cus` CUs (host-side)."""
-    f = c_int(-1)
-    _check(lib().wino_conv3x3_s2_plan(int(N), int(Hin), int(Win), int(C), int(K), int(cus), ctypes.byref(f)),
-           "wino_conv3x3_s2_plan")
-    return int(f.value)
+    return _plan_query("wino_conv3x3_s2_plan", 1, int(N), int(Hin), int(Win), int(C), int(K), int(cus))[0]
 
 
 def proj_block_v15_prepare(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int) -> None:
     """Allocate the scratch of proj_block_v15's three launches for the current stream (before graph capture)."""
-    _check(lib().wino_proj_block_v15_prepare_hw(int(N), int(Hin), int(Win), int(Cin), int(Cm), int(C4), _stream()),
-           "wino_proj_block_v15_prepare_hw")
+    _prepare("wino_proj_block_v15_prepare_hw", N, Hin, Win, Cin, Cm, C4)
 
 
 def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> torch.Tensor:
@@ -682,8 +508,8 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
     if tail.numel() % (Cm + Cin + 2):
         raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
     C4 = tail.numel() // (Cm + Cin + 2)
-    H, W = _s2_out_hw(Hin, Win)
-    vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
+    H, W = _out_hw(Hin, Win, 2)
+    vecs = _bn_vecs(bn1, bn2)
     if any(v.numel() != Cm for v in vecs):
         raise WinoError("bn1 / bn2 vectors must have Cm values")
     workspace = _workspace(workspace, lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm), x.device)
@@ -691,8 +517,8 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
     _on_current_device(x, w1, w2, tail, out, workspace, *vecs)
     _check(lib().wino_proj_block_v15_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
                                         w2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
-                                        out.data_ptr(), N, Hin, Win, Cin, Cm, C4, workspace.data_ptr(),
-                                        workspace.numel() * 4, _stream()), "wino_proj_block_v15_hw")
+                                        out.data_ptr(), N, Hin, Win, Cin, Cm, C4, *_ws_args(workspace), _stream()),
+           "wino_proj_block_v15_hw")
     return out
 
 
@@ -701,14 +527,7 @@ def conv3x3_bn_add_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tenso
     """out = act(bn_scale * conv3x3(inp, U) + bn_bias + residual): the second 3x3 of a ResNet basic block, one HIP
     launch.  inp [N][H+2][W+2][C]; residual and out [N][H+2][W+2][K] (out's ring written 0, residual's ring not read).
     out may be residual itself (in place); the ReLU follows the add."""
-    x = _dev(inp, "inp")
-    U = _dev(U, "U")
-    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
-    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
-        raise WinoError("inp must be [N][H+2][W+2][C]")
-    N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(b.numel())
-    if U.numel() != 16 * C * K or s.numel() != K:
-        raise WinoError("U / bn vectors do not match C, K")
+    x, U, b, s, N, Hp, Wp, C, K = _operands_3x3(inp, U, bn_bias, bn_scale)
     r = _out(residual, (N, Hp, Wp, K), "residual")
     out = _output(out, (N, Hp, Wp, K), x.device)
     _on_current_device(x, U, b, s, r, out)
@@ -720,7 +539,7 @@ def conv3x3_bn_add_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tenso
 
 def basic_block_prepare(N: int, H: int, W: int, C: int) -> None:
     """Allocate the scratch of basic_block's two launches for the current stream (before graph capture)."""
-    _check(lib().wino_basic_block_prepare_hw(int(N), int(H), int(W), int(C), _stream()), "wino_basic_block_prepare_hw")
+    _prepare("wino_basic_block_prepare_hw", N, H, W, C)
 
 
 def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
@@ -736,7 +555,7 @@ def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
             raise WinoError(f"{name} must be a {C} -> {C} filter from filter_transform_f2 (16*C*C values): "
                             "the basic block keeps its channel count")
     x, U1, U2 = _dev(x, "x"), _dev(U1, "U1"), _dev(U2, "U2")
-    vecs = [_dev(v, "bn") for pair in (bn1, bn2) for v in pair]
+    vecs = _bn_vecs(bn1, bn2)
     if any(v.numel() != C for v in vecs):
         raise WinoError("bn1 / bn2 vectors must have C values")
     workspace = _workspace(workspace, lib().wino_basic_block_workspace_bytes_hw(N, Hp - 2, Wp - 2, C), x.device)
@@ -744,7 +563,7 @@ def basic_block(x, U1, bn1, U2, bn2, out=None, workspace=None) -> torch.Tensor:
     _on_current_device(x, U1, U2, out, workspace, *vecs)
     _check(lib().wino_basic_block_hw(x.data_ptr(), U1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
                                      U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), out.data_ptr(),
-                                     N, Hp - 2, Wp - 2, C, workspace.data_ptr(), workspace.numel() * 4, _stream()),
+                                     N, Hp - 2, Wp - 2, C, *_ws_args(workspace), _stream()),
            "wino_basic_block_hw")
     return out
 
@@ -759,7 +578,7 @@ def s2_proj_pack(w_taps, bn1, wd, bnd, out=None) -> torch.Tensor:
     C, K = int(w.shape[2]), int(w.shape[3])
     if wd.dim() != 2 or tuple(wd.shape) != (C, K):
         raise WinoError(f"wd must be [{C}][{K}]")
-    vecs = [_dev(v, "bn") for pair in (bn1, bnd) for v in pair]
+    vecs = _bn_vecs(bn1, bnd)
     if any(v.numel() != K for v in vecs):
         raise WinoError("bn1 / bnd vectors must have K values")
     n = lib().wino_s2_proj_elems(C, K)
@@ -790,7 +609,7 @@ def conv3x3_s2_proj(x, packed, t1=None, sc=None):
     touched.  packed from s2_proj_pack.  Returns (t1, sc)."""
     N, Hin, Win, C, K = _s2_proj_ck(x, packed)
     x, packed = _dev(x, "x"), _dev(packed, "packed")
-    H, W = _s2_out_hw(Hin, Win)
+    H, W = _out_hw(Hin, Win, 2)
     shape = (N, H + 2, W + 2, K)
     t1 = _output(t1, shape, x.device, "t1")
     sc = _output(sc, shape, x.device, "sc")
@@ -802,8 +621,7 @@ def conv3x3_s2_proj(x, packed, t1=None, sc=None):
 
 def basic_block_s2_prepare(N: int, Hin: int, Win: int, C: int, K: int) -> None:
     """Allocate the scratch of basic_block_s2's two launches for the current stream (before graph capture)."""
-    _check(lib().wino_basic_block_s2_prepare_hw(int(N), int(Hin), int(Win), int(C), int(K), _stream()),
-           "wino_basic_block_s2_prepare_hw")
+    _prepare("wino_basic_block_s2_prepare_hw", N, Hin, Win, C, K)
 
 
 def basic_block_s2(x, packed, U2, bn2, out=None, workspace=None) -> torch.Tensor:
@@ -816,16 +634,16 @@ def basic_block_s2(x, packed, U2, bn2, out=None, workspace=None) -> torch.Tensor
     if not isinstance(U2, torch.Tensor) or U2.numel() != 16 * K * K:
         raise WinoError(f"U2 must be a {K} -> {K} filter from filter_transform_f2 (16*K*K values)")
     x, packed, U2 = _dev(x, "x"), _dev(packed, "packed"), _dev(U2, "U2")
-    vecs = [_dev(v, "bn") for v in bn2]
+    vecs = _bn_vecs(bn2)
     if len(vecs) != 2 or any(v.numel() != K for v in vecs):
         raise WinoError("bn2 must be (bias, scale) with K values each")
-    H, W = _s2_out_hw(Hin, Win)
+    H, W = _out_hw(Hin, Win, 2)
     workspace = _workspace(workspace, lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Win, K), x.device)
     out = _output(out, (N, H + 2, W + 2, K), x.device)
     _on_current_device(x, packed, U2, out, workspace, *vecs)
     _check(lib().wino_basic_block_s2_hw(x.data_ptr(), packed.data_ptr(), U2.data_ptr(), vecs[0].data_ptr(),
-                                        vecs[1].data_ptr(), out.data_ptr(), N, Hin, Win, C, K, workspace.data_ptr(),
-                                        workspace.numel() * 4, _stream()), "wino_basic_block_s2_hw")
+                                        vecs[1].data_ptr(), out.data_ptr(), N, Hin, Win, C, K, *_ws_args(workspace),
+                                        _stream()), "wino_basic_block_s2_hw")
     return out
 
 
@@ -834,8 +652,7 @@ STEM_FORM_BIG, STEM_FORM_SMALL = 1, 2   # WINO_STEM_FORM_*
 
 def stem_out_hw(H: int, W: int):
     """The stem's pooled grid: conv 7x7 stride 2 pad 3, then max-pool 3x3 stride 2 pad 1 (224 -> 112 -> 56)."""
-    Hc, Wc = (int(H) - 1) // 2 + 1, (int(W) - 1) // 2 + 1
-    return (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
+    return _out_hw(*_out_hw(int(H), int(W), 2), 2)
 
 
 def stem_filter_pack(w, bn, out=None) -> torch.Tensor:
@@ -845,7 +662,7 @@ def stem_filter_pack(w, bn, out=None) -> torch.Tensor:
     if w.dim() != 4 or tuple(w.shape[1:]) != (3, 7, 7):
         raise WinoError("w must be [K][3][7][7]")
     K = int(w.shape[0])
-    vecs = [_dev(v, "bn") for v in bn]
+    vecs = _bn_vecs(bn)
     if len(vecs) != 2 or any(v.numel() != K for v in vecs):
         raise WinoError("bn must be (bias, scale) with K values each")
     n = lib().wino_stem_filter_elems(K)
@@ -860,9 +677,7 @@ def stem_filter_pack(w, bn, out=None) -> torch.Tensor:
 
 def stem_plan(N: int, H: int, W: int, K: int = 64, cus: int = 256) -> int:
     """The STEM_FORM_* the stem takes for this shape on a device with `cus` CUs (host-side)."""
-    f = c_int(0)
-    _check(lib().wino_stem_plan(int(N), int(H), int(W), int(K), int(cus), ctypes.byref(f)), "wino_stem_plan")
-    return int(f.value)
+    return _plan_query("wino_stem_plan", 1, int(N), int(H), int(W), int(K), int(cus))[0]
 
 
 def stem(x, packed, out_padded: bool = False, out=None) -> torch.Tensor:
@@ -904,7 +719,7 @@ def head_pack(wfc, bfc, out=None) -> torch.Tensor:
 
 def head_prepare(N: int, C: int, classes: int) -> None:
     """Allocate the head GEMM's stream-K scratch for the current stream (before graph capture)."""
-    _check(lib().wino_head_prepare(int(N), int(C), int(classes), _stream()), "wino_head_prepare")
+    _prepare("wino_head_prepare", N, C, classes)
 
 
 def avgpool_fc(feat, packed, classes: int, in_padded: bool = False, out=None, workspace=None) -> torch.Tensor:
@@ -925,7 +740,7 @@ def avgpool_fc(feat, packed, classes: int, in_padded: bool = False, out=None, wo
     out = _output(out, (N, classes), f.device)
     _on_current_device(f, packed, out, workspace)
     _check(lib().wino_avgpool_fc_hw(f.data_ptr(), packed.data_ptr(), out.data_ptr(), N, H, W, C, classes,
-                                    int(bool(in_padded)), workspace.data_ptr(), workspace.numel() * 4, _stream()),
+                                    int(bool(in_padded)), *_ws_args(workspace), _stream()),
            "wino_avgpool_fc_hw")
     return out
 
@@ -935,14 +750,8 @@ def conv3x3_bn_relu_pool(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tens
     """The 3x3 layer with MaxPool2d(2, 2) fused into its epilogue, one HIP launch: inp [N][H+2][W+2][C] ->
     out [N][H//2+2][W//2+2][K] = maxpool2x2_s2(act(scale*conv3x3(inp) + bias)) with a zero ring.  The launch takes the
     plan of conv3x3_bn_relu at the same shape (conv3x3_prepare reserves its scratch).  H, W >= 2."""
-    x = _dev(inp, "inp")
-    U = _dev(U, "U")
-    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
-    if x.dim() != 4 or x.shape[1] < 4 or x.shape[2] < 4:
-        raise WinoError("inp must be [N][H+2][W+2][C] with H, W >= 2")
-    N, Hp, Wp, C, K = int(x.shape[0]), int(x.shape[1]), int(x.shape[2]), int(x.shape[3]), int(b.numel())
-    if U.numel() != 16 * C * K or s.numel() != K:
-        raise WinoError("U / bn vectors do not match C, K")
+    x, U, b, s, N, Hp, Wp, C, K = _operands_3x3(inp, U, bn_bias, bn_scale, 4,
+                                                "inp must be [N][H+2][W+2][C] with H, W >= 2")
     H, W = Hp - 2, Wp - 2
     out = _output(out, (N, H // 2 + 2, W // 2 + 2, K), x.device)
     _on_current_device(x, U, b, s, out)

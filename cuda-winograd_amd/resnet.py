@@ -18,10 +18,11 @@ from __future__ import annotations
 
 import torch
 
-from . import (WinoError, avgpool_fc, basic_block, basic_block_prepare, basic_block_s2, basic_block_s2_prepare,
-               filter_pack_s2, filter_transform_f2, head_pack, head_prepare, lib, proj_block, proj_block_prepare,
-               proj_block_v15, proj_block_v15_prepare, proj_tail_pack, residual_block, residual_block_prepare,
-               s2_proj_pack, stem, stem_filter_pack, stem_out_hw)
+from . import (WinoError, _out_hw, avgpool_fc, basic_block, basic_block_prepare, basic_block_s2,
+               basic_block_s2_prepare, filter_pack_s2, filter_transform_f2, head_pack, head_prepare, lib, proj_block,
+               proj_block_prepare, proj_block_v15, proj_block_v15_prepare, proj_tail_pack, residual_block,
+               residual_block_prepare, s2_proj_pack, stem, stem_filter_pack, stem_out_hw)
+from ._net import BN_KEYS, Net, check_state_dict
 
 # arch -> (bottleneck?, blocks per stage)
 ARCHS = {
@@ -32,11 +33,6 @@ ARCHS = {
     "resnet152": (True, (3, 8, 36, 3)),
 }
 PLANES = (64, 128, 256, 512)
-BN_KEYS = ("weight", "bias", "running_mean", "running_var")
-
-
-def _s2(h: int) -> int:
-    return (h - 1) // 2 + 1
 
 
 def stage_shapes(arch: str, H: int, W: int):
@@ -48,7 +44,7 @@ def stage_shapes(arch: str, H: int, W: int):
     shapes = [("stem", 64, h, w)]
     for i, planes in enumerate(PLANES):
         if i:
-            h, w = _s2(h), _s2(w)
+            h, w = _out_hw(h, w, 2)
         shapes.append((f"layer{i + 1}", planes * (4 if bottleneck else 1), h, w))
     return shapes
 
@@ -97,57 +93,31 @@ def validate_state_dict(sd, arch: str) -> int:
     if "fc.weight" not in sd:
         raise WinoError("state dict: missing key 'fc.weight'")
     classes = int(sd["fc.weight"].shape[0])
-    exp = expected_keys(arch, classes)
-    for k in exp:
-        if k not in sd:
-            raise WinoError(f"state dict: missing key {k!r} for {arch}")
-    for k, v in sd.items():
-        if k.endswith(".num_batches_tracked") and k[: -len("num_batches_tracked")] + "weight" in exp:
-            continue
-        if k not in exp:
-            raise WinoError(f"state dict: unexpected key {k!r} for {arch}")
-        if tuple(v.shape) != exp[k]:
-            raise WinoError(f"state dict: key {k!r} has shape {tuple(v.shape)}, {arch} needs {exp[k]}")
+    check_state_dict(sd, expected_keys(arch, classes), arch, "weight")
     return classes
 
 
-class ResNet:
+class ResNet(Net):
     """A torchvision ResNet on the library's kernels, inference only (BN folded at load)."""
 
     def __init__(self, arch: str, classes: int, device):
-        self.arch, self.classes, self.device = arch, classes, torch.device(device)
+        super().__init__(device)
+        self.arch, self.classes = arch, classes
         self.bottleneck, self.blocks = ARCHS[arch]
-        self._shape = None
 
     # ------------------------------------------------------------------ loading
     @classmethod
     def from_state_dict(cls, sd, arch: str, eps: float = 1e-5, device=None) -> "ResNet":
         """Validate `sd` (torchvision key names) for `arch`, fold every BN (scale = gamma / sqrt(var + eps),
         bias = beta - mean * scale) and pack every filter on `device` (default: the current CUDA device)."""
-        classes = validate_state_dict(sd, arch)
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise WinoError("ResNet runs on a CUDA(HIP) device only -- there is no CPU path")
-        m = cls(arch, classes, dev)
-        with torch.cuda.device(dev):
-            m._pack(sd, eps)
-        return m
-
-    def _t(self, v):
-        return v.detach().to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _bn(self, sd, prefix, eps):
-        g, b = sd[f"{prefix}.weight"].double(), sd[f"{prefix}.bias"].double()
-        mean, var = sd[f"{prefix}.running_mean"].double(), sd[f"{prefix}.running_var"].double()
-        scale = g / torch.sqrt(var + eps)
-        return self._t(b - mean * scale), self._t(scale)   # (bias, scale), the library's order
+        return cls._load(sd, eps, device, arch, validate_state_dict(sd, arch))
 
     def _pack(self, sd, eps):
         def w1x1(key):   # torch's [K][C][1][1] -> the library's [C][K]
             w = sd[key]
             return self._t(w.reshape(w.shape[0], w.shape[1]).t())
 
-        self.stem_packed = stem_filter_pack(self._t(sd["conv1.weight"]), self._bn(sd, "bn1", eps))
+        self.stem_packed = stem_filter_pack(self._t(sd["conv1.weight"]), self._fold_bn(sd, "bn1", eps))
         self.layers = []
         cin = 64
         for L, (planes, nb) in enumerate(zip(PLANES, self.blocks), 1):
@@ -155,13 +125,13 @@ class ResNet:
             for b in range(nb):
                 p = f"layer{L}.{b}"
                 first = b == 0
-                bn1, bn2 = self._bn(sd, f"{p}.bn1", eps), self._bn(sd, f"{p}.bn2", eps)
+                bn1, bn2 = self._fold_bn(sd, f"{p}.bn1", eps), self._fold_bn(sd, f"{p}.bn2", eps)
                 if self.bottleneck:
                     cout = planes * 4
-                    w1, bn3 = w1x1(f"{p}.conv1.weight"), self._bn(sd, f"{p}.bn3", eps)
+                    w1, bn3 = w1x1(f"{p}.conv1.weight"), self._fold_bn(sd, f"{p}.bn3", eps)
                     if first:
                         tail = proj_tail_pack(w1x1(f"{p}.conv3.weight"), bn3, w1x1(f"{p}.downsample.0.weight"),
-                                              self._bn(sd, f"{p}.downsample.1", eps))
+                                              self._fold_bn(sd, f"{p}.downsample.1", eps))
                         if L == 1:   # stride 1: the v1 and v1.5 placements are the same block
                             w2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
                             blocks.append(("proj", cin, planes, cout, (w1, bn1, w2, bn2, tail)))
@@ -176,7 +146,8 @@ class ResNet:
                     cout = planes
                     if first and L > 1:
                         packed = s2_proj_pack(filter_pack_s2(self._t(sd[f"{p}.conv1.weight"])), bn1,
-                                              w1x1(f"{p}.downsample.0.weight"), self._bn(sd, f"{p}.downsample.1", eps))
+                                              w1x1(f"{p}.downsample.0.weight"),
+                                              self._fold_bn(sd, f"{p}.downsample.1", eps))
                         U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
                         blocks.append(("basic_s2", cin, planes, cout, (packed, U2, bn2)))
                     else:
@@ -265,13 +236,7 @@ class ResNet:
         """x [N][3][H][W] float32 on the model's device -> logits [N][classes] (the model's own output tensor,
         rewritten by the next forward).  With return_stages, also {"stem", "layer1".."layer4"}: views of the
         activations (NHWC interiors), valid until the next forward.  A new input shape re-runs prepare()."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[1]) != 3:
-            raise WinoError("x must be [N][3][H][W]")
-        if x.device != self.device or x.dtype != torch.float32:
-            raise WinoError(f"x must be float32 on {self.device}")
-        shape = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3]))
-        if shape != self._shape:
-            self.prepare(*shape)
+        self._begin(x)
         with torch.cuda.device(self.device):
             outs = self._run_stages(x.contiguous())
         if not return_stages:
@@ -281,12 +246,10 @@ class ResNet:
         stages.update({n: self._interior(t) for n, t in zip(names, outs)})
         return self._logits, stages
 
-    __call__ = forward
-
     def flops(self, H: int = 224, W: int = 224) -> float:
         """Algorithmic multiply-add FLOPs of one image (2 per MAC; convolutions and FC)."""
         shapes = stage_shapes(self.arch, H, W)
-        Hc, Wc = _s2(H), _s2(W)
+        Hc, Wc = _out_hw(H, W, 2)
         f = 2.0 * Hc * Wc * 64 * 147
         for (_, _, ho, wo), blocks in zip(shapes[1:], self.layers):
             for kind, cin, cm, cout, _ in blocks:

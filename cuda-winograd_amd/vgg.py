@@ -25,6 +25,7 @@ import torch
 
 from . import (WinoError, avgpool7_flatten, avgpool_fc, conv1x1_bn, conv1x1_prepare, conv3x3_bn_relu,
                conv3x3_bn_relu_pool, conv3x3_prepare, filter_transform_f2, head_pack, head_prepare, image_pack, lib)
+from ._net import BN_KEYS, Net, check_state_dict
 
 # torchvision's configurations A, B, D, E
 _CFGS = {
@@ -38,7 +39,6 @@ ARCHS = {
     "vgg11": ("A", False), "vgg13": ("B", False), "vgg16": ("D", False), "vgg19": ("E", False),
     "vgg11_bn": ("A", True), "vgg13_bn": ("B", True), "vgg16_bn": ("D", True), "vgg19_bn": ("E", True),
 }
-BN_KEYS = ("weight", "bias", "running_mean", "running_var")
 CPAD = 16        # channels of the packed image (see the module docstring)
 MIN_HW = 32      # five floors of H/2 must leave a pixel
 
@@ -96,17 +96,7 @@ def validate_state_dict(sd, arch: str):
     if hidden < 64 or hidden % 64:
         raise WinoError(f"state dict: key 'classifier.0.weight' gives the hidden width {hidden}: it must be a "
                         "multiple of 64")
-    exp = expected_keys(arch, classes, hidden)
-    for k in exp:
-        if k not in sd:
-            raise WinoError(f"state dict: missing key {k!r} for {arch}")
-    for k, v in sd.items():
-        if k.endswith(".num_batches_tracked") and k[: -len("num_batches_tracked")] + "running_mean" in exp:
-            continue
-        if k not in exp:
-            raise WinoError(f"state dict: unexpected key {k!r} for {arch}")
-        if tuple(v.shape) != exp[k]:
-            raise WinoError(f"state dict: key {k!r} has shape {tuple(v.shape)}, {arch} needs {exp[k]}")
+    check_state_dict(sd, expected_keys(arch, classes, hidden), arch, "running_mean")
     return classes, hidden
 
 
@@ -128,13 +118,13 @@ def layer_shapes(arch: str, H: int, W: int):
     return out
 
 
-class VGG:
+class VGG(Net):
     """A torchvision VGG on the library's kernels, inference only (conv bias and BN folded at load)."""
 
     def __init__(self, arch: str, classes: int, hidden: int, device):
-        self.arch, self.classes, self.hidden, self.device = arch, classes, hidden, torch.device(device)
+        super().__init__(device)
+        self.arch, self.classes, self.hidden = arch, classes, hidden
         _, self.bn = _arch(arch)
-        self._shape = None
 
     # ------------------------------------------------------------------ loading
     @classmethod
@@ -142,27 +132,7 @@ class VGG:
         """Validate `sd` (torchvision key names) for `arch`, fold every conv bias and BN (scale = gamma / sqrt(var +
         eps), bias = beta + (b - mean) * scale; without BN scale = 1, bias = b) and pack every filter on `device`
         (default: the current CUDA device)."""
-        classes, hidden = validate_state_dict(sd, arch)
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if dev.type != "cuda":
-            raise WinoError("VGG runs on a CUDA(HIP) device only -- there is no CPU path")
-        m = cls(arch, classes, hidden, dev)
-        with torch.cuda.device(dev):
-            m._pack(sd, eps)
-        return m
-
-    def _t(self, v):
-        return v.detach().to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _fold(self, sd, i, eps):
-        b = sd[f"features.{i}.bias"].double()
-        if not self.bn:
-            return self._t(b), self._t(torch.ones_like(b))
-        p = f"features.{i + 1}"
-        g, beta = sd[f"{p}.weight"].double(), sd[f"{p}.bias"].double()
-        mean, var = sd[f"{p}.running_mean"].double(), sd[f"{p}.running_var"].double()
-        scale = g / torch.sqrt(var + eps)
-        return self._t(beta + (b - mean) * scale), self._t(scale)   # (bias, scale), the library's order
+        return cls._load(sd, eps, device, arch, *validate_state_dict(sd, arch))
 
     def _pack(self, sd, eps):
         self.convs = []   # (Cin as run, Cout, pooled?, U, bias, scale)
@@ -171,7 +141,9 @@ class VGG:
             if cin < CPAD and cin % 8:   # the first layer: zero channels up to the packed image's
                 w = torch.cat([w, w.new_zeros(cout, CPAD - cin, 3, 3)], dim=1)
                 cin = CPAD
-            bias, scale = self._fold(sd, i, eps)
+            b = sd[f"features.{i}.bias"]   # without BN: scale = 1, bias = b
+            bias, scale = (self._fold_bn(sd, f"features.{i + 1}", eps, conv_bias=b) if self.bn
+                           else (self._t(b), self._t(torch.ones_like(b))))
             self.convs.append((cin, cout, pool, filter_transform_f2(self._t(w)), bias, scale))
         self.feat_c = self.convs[-1][1]
         ones = torch.ones(self.hidden, dtype=torch.float32, device=self.device)
@@ -241,21 +213,13 @@ class VGG:
         """x [N][3][H][W] float32 on the model's device -> logits [N][classes] (the model's own output tensor,
         rewritten by the next forward).  With return_stages, also {"pool1".."pool5"}: copies of the five pooled maps
         (NHWC interiors).  A new input shape re-runs prepare()."""
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[1]) != 3:
-            raise WinoError("x must be [N][3][H][W]")
-        if x.device != self.device or x.dtype != torch.float32:
-            raise WinoError(f"x must be float32 on {self.device}")
-        shape = (int(x.shape[0]), int(x.shape[2]), int(x.shape[3]))
-        if shape != self._shape:
-            self.prepare(*shape)
+        self._begin(x)
         stages = {} if return_stages else None
         with torch.cuda.device(self.device):
             self._run(x.contiguous(), stages)
         if not return_stages:
             return self._logits
         return self._logits, stages
-
-    __call__ = forward
 
     def flops(self, H: int = 224, W: int = 224) -> float:
         """Algorithmic multiply-add FLOPs of one image (2 per MAC; convolutions on their true input channels, FCs)."""
