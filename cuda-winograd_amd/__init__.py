@@ -522,6 +522,138 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
     return out
 
 
+def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
+    """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
+    bounds by the kernel)."""
+    groups = int(groups)
+    n = lib().wino_conv3x3_grouped_filter_elems(C, groups)
+    if n == 0:
+        raise WinoError(f"grouped 3x3: unsupported C={C} groups={groups} "
+                        "(need C % 64 == 0 and C / groups in {4, 8, 16, 32, 64})")
+    if packed.dim() != 1 or packed.numel() != n:
+        raise WinoError(f"{name} does not match C={C} groups={groups}: pack it with filter_pack_grouped")
+    return groups
+
+
+def filter_pack_grouped(w: torch.Tensor, groups: int, out: torch.Tensor | None = None) -> torch.Tensor:
+    """torch's grouped 3x3 weight [C][C/groups][3][3] -> the grouped layer's packed filter (opaque layout,
+    wino_conv3x3_grouped_filter_elems floats), the analogue of filter_transform_f2 for conv3x3_grouped_bn_relu."""
+    w = _dev(w, "w")
+    groups = int(groups)
+    if w.dim() != 4 or tuple(w.shape[2:]) != (3, 3) or groups < 1 or int(w.shape[0]) != int(w.shape[1]) * groups:
+        raise WinoError("w must be [C][C/groups][3][3]")
+    C = int(w.shape[0])
+    n = lib().wino_conv3x3_grouped_filter_elems(C, groups)
+    if n == 0:
+        raise WinoError(f"grouped 3x3: unsupported C={C} groups={groups} "
+                        "(need C % 64 == 0 and C / groups in {4, 8, 16, 32, 64})")
+    packed = _output(out, (n,), w.device)
+    _on_current_device(w, packed)
+    _check(lib().wino_conv3x3_grouped_filter_pack(w.data_ptr(), packed.data_ptr(), C, groups, _stream()),
+           "wino_conv3x3_grouped_filter_pack")
+    return packed
+
+
+def conv3x3_grouped_bn_relu(inp: torch.Tensor, packed: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
+                            groups: int, stride: int = 1, relu: bool = True,
+                            out: torch.Tensor | None = None) -> torch.Tensor:
+    """Grouped 3x3 conv (stride 1 or 2, pad 1) + folded BN (+ReLU): inp [N][Hin+2][Win+2][C] (zero ring) ->
+    out [N][H+2][W+2][C] (interior H x W = (Hin-1)//stride + 1 x (Win-1)//stride + 1, zero ring).  packed from
+    filter_pack_grouped(w, groups).  One HIP launch."""
+    x, packed = _dev(inp, "inp"), _dev(packed, "packed")
+    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("inp must be [N][Hin+2][Win+2][C]")
+    N, Hin, Win, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    groups = _groups_of(packed, C, groups, "packed")
+    if b.numel() != C or s.numel() != C:
+        raise WinoError("bn vectors do not match C")
+    if int(stride) not in (1, 2):
+        raise WinoError(f"stride must be 1 or 2, got {stride}")
+    H, W = _out_hw(Hin, Win, int(stride))
+    out = _output(out, (N, H + 2, W + 2, C), x.device)
+    _on_current_device(x, packed, b, s, out)
+    _check(lib().wino_conv3x3_grouped_bn_relu_hw(x.data_ptr(), packed.data_ptr(), b.data_ptr(), s.data_ptr(),
+                                                 out.data_ptr(), N, Hin, Win, C, groups, int(stride), int(relu),
+                                                 _stream()), "wino_conv3x3_grouped_bn_relu_hw")
+    return out
+
+
+def grouped_residual_block_prepare(N: int, H: int, W: int, C4: int, Cm: int, groups: int) -> None:
+    """Allocate the scratch of grouped_residual_block's two 1x1 launches for the current stream (before graph capture)."""
+    _prepare("wino_grouped_residual_block_prepare_hw", N, H, W, C4, Cm, groups)
+
+
+def grouped_residual_block(x, w1, bn1, wg, bn2, w3, bn3, groups: int, out=None, workspace=None) -> torch.Tensor:
+    """ResNeXt identity bottleneck: residual_block with the grouped 3x3 in the middle.  x [N][H][W][C4] -> same shape;
+    w1 [C4][Cm], w3 [Cm][C4]; wg from filter_pack_grouped (Cm channels in `groups` groups); bnX = (bias, scale)."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise WinoError("x must be [N][H][W][C4]")
+    N, H, W, C4 = (int(v) for v in x.shape)
+    w1, w3, wg = _dev(w1, "w1"), _dev(w3, "w3"), _dev(wg, "wg")
+    if w1.dim() != 2 or int(w1.shape[0]) != C4 or w3.dim() != 2 or tuple(w3.shape) != (int(w1.shape[1]), C4):
+        raise WinoError("w1 must be [C4][Cm], w3 [Cm][C4]")
+    Cm = int(w1.shape[1])
+    groups = _groups_of(wg, Cm, groups, "wg")
+    vecs = _bn_vecs(bn1, bn2, bn3)
+    if any(v.numel() != c for v, c in zip(vecs, (Cm, Cm, Cm, Cm, C4, C4))):
+        raise WinoError("bn1 / bn2 vectors must have Cm values, bn3's C4")
+    workspace = _workspace(workspace, lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm), x.device)
+    out = _output(out, x.shape, x.device)
+    _on_current_device(x, w1, w3, wg, out, workspace, *vecs)
+    _check(lib().wino_grouped_residual_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
+                                                wg.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), w3.data_ptr(),
+                                                vecs[4].data_ptr(), vecs[5].data_ptr(), out.data_ptr(), N, H, W, C4, Cm,
+                                                groups, *_ws_args(workspace), _stream()),
+           "wino_grouped_residual_block_hw")
+    return out
+
+
+def grouped_proj_block_workspace_bytes(N: int, Hin: int, Win: int, Cm: int, stride: int) -> int:
+    """The workspace of grouped_proj_block: its intermediates are the dense projection blocks', so are the sizes."""
+    if int(stride) == 1:
+        return lib().wino_proj_block_workspace_bytes_hw(N, Hin, Win, Cm)
+    return lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm)
+
+
+def grouped_proj_block_prepare(N: int, Hin: int, Win: int, Cin: int, Cm: int, C4: int, groups: int, stride: int) -> None:
+    """Allocate the scratch of grouped_proj_block's two 1x1 launches for the current stream (before graph capture)."""
+    _prepare("wino_grouped_proj_block_prepare_hw", N, Hin, Win, Cin, Cm, C4, groups, stride)
+
+
+def grouped_proj_block(x, w1, bn1, wg, bn2, tail, groups: int, stride: int, out=None, workspace=None) -> torch.Tensor:
+    """ResNeXt projection bottleneck (a stage's first block, torchvision's placement): x [N][Hin][Win][Cin] ->
+    [N][H][W][C4], H = (Hin-1)//stride + 1.  The first 1x1 runs at Hin x Win, the grouped 3x3 at `stride`; w1 [Cin][Cm];
+    wg from filter_pack_grouped; tail from proj_tail_pack (w3, bn3, wp, bnp); bnX = (bias, scale)."""
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise WinoError("x must be [N][Hin][Win][Cin]")
+    N, Hin, Win, Cin = (int(v) for v in x.shape)
+    w1, wg, tail = _dev(w1, "w1"), _dev(wg, "wg"), _dev(tail, "tail")
+    if w1.dim() != 2 or int(w1.shape[0]) != Cin:
+        raise WinoError("w1 must be [Cin][Cm]")
+    Cm = int(w1.shape[1])
+    groups = _groups_of(wg, Cm, groups, "wg")
+    if tail.numel() % (Cm + Cin + 2):
+        raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
+    C4 = tail.numel() // (Cm + Cin + 2)
+    if int(stride) not in (1, 2):
+        raise WinoError(f"stride must be 1 or 2, got {stride}")
+    H, W = _out_hw(Hin, Win, int(stride))
+    vecs = _bn_vecs(bn1, bn2)
+    if any(v.numel() != Cm for v in vecs):
+        raise WinoError("bn1 / bn2 vectors must have Cm values")
+    workspace = _workspace(workspace, grouped_proj_block_workspace_bytes(N, Hin, Win, Cm, stride), x.device)
+    out = _output(out, (N, H, W, C4), x.device)
+    _on_current_device(x, w1, wg, tail, out, workspace, *vecs)
+    _check(lib().wino_grouped_proj_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
+                                            wg.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
+                                            out.data_ptr(), N, Hin, Win, Cin, Cm, C4, groups, int(stride),
+                                            *_ws_args(workspace), _stream()), "wino_grouped_proj_block_hw")
+    return out
+
+
 def conv3x3_bn_add_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
                         residual: torch.Tensor, relu: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
     """out = act(bn_scale * conv3x3(inp, U) + bn_bias + residual): the second 3x3 of a ResNet basic block, one HIP

@@ -142,6 +142,14 @@ SIGNATURES = {
     "wino_conv3x3_bn_relu_pool_hw": (i, [vp] * 5 + [i] * 6 + [vp]),
     "wino_image_pack_hw": (i, [vp] * 2 + [i] * 5 + [vp]),
     "wino_avgpool7_flatten_hw": (i, [vp] * 2 + [i] * 5 + [vp]),
+    # ---- grouped 3x3 and the ResNeXt blocks
+    "wino_conv3x3_grouped_filter_elems": (sz, [i] * 2),
+    "wino_conv3x3_grouped_filter_pack": (i, [vp] * 2 + [i] * 2 + [vp]),
+    "wino_conv3x3_grouped_bn_relu_hw": (i, [vp] * 5 + [i] * 7 + [vp]),
+    "wino_grouped_residual_block_hw": (i, [vp] * 11 + [i] * 6 + [vp, sz, vp]),
+    "wino_grouped_residual_block_prepare_hw": (i, [i] * 6 + [vp]),
+    "wino_grouped_proj_block_hw": (i, [vp] * 9 + [i] * 8 + [vp, sz, vp]),
+    "wino_grouped_proj_block_prepare_hw": (i, [i] * 8 + [vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -313,13 +313,19 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
 // The bottleneck block's shape checks before its first launch: batch and feature map, both 1x1 layers (C4 -> Cm
 // writing padded t1, Cm -> C4 reading padded t2) and the 3x3's limits (its filter matrix among them), so that a shape
 // any of its layers refuses launches nothing
-static int check_residual_block(int N, int H, int W, int C4, int Cm) {
+namespace wino {
+// the block's batch, feature map and two 1x1 layers (shared with the grouped bottleneck, grouped_block.hip: proj_block.h)
+int check_bottleneck_1x1s(int N, int H, int W, int C4, int Cm) {
   if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
   const long M = (long)N * H * W;
   if (int rc = check_1x1(M, C4, Cm)) return rc;
   if (int rc = check_1x1_padded(M, H, W, Cm)) return rc;
   if (int rc = check_1x1(M, Cm, C4)) return rc;
-  if (int rc = check_1x1_padded(M, H, W, C4)) return rc;
+  return check_1x1_padded(M, H, W, C4);
+}
+}  // namespace wino
+static int check_residual_block(int N, int H, int W, int C4, int Cm) {
+  if (int rc = check_bottleneck_1x1s(N, H, W, C4, Cm)) return rc;
   return check_conv3x3_dims(H, W, Cm, Cm);
 }
 

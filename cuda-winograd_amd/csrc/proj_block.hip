@@ -16,12 +16,13 @@
 //   t2  = relu(bn2(conv3x3_s2(t1, w2_taps)))     padded [N][H+2][W+2][Cm]       (workspace; conv3x3_s2.hip)
 //   out = the same fused tail as v1 at stride 2
 // so this file instantiates no kernel for it.
-#include "conv3x3_s2.h"
+#include "proj_block.h"
 
 namespace wino {
-namespace {
 
 using namespace gemm1x1;
+
+namespace {
 
 // packed = [bn3Scale . w3 ; bnpScale . wp] ([Cm + Cin][C4], row-major), then bn3Bias + bnpBias, then C4 ones (the
 // tail's BN scale: the scales are folded into the matrix).  One thread per element.
@@ -42,14 +43,12 @@ __global__ void proj_tail_pack_kernel(const float* __restrict__ w3, const float*
   packed[i] = v;
 }
 
+}  // namespace
+
 // The block's geometry, checked once.  Every 32-bit quantity the strided / two-source addressing creates is bounded
 // here: the pixel row index (M < 2^31, one input image < 2^31 pixels), the buffer-descriptor windows of a 112-row tile
 // over the strided x and over the padded t2, the ring pass's 16-byte units, and B's descriptor.
-struct ProjGeom {
-  int N, Hin, Win, Cin, Cm, C4, s, H, W;
-  long M;
-};
-static int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, ProjGeom* g) {
+int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, ProjGeom* g) {
   if (stride != 1 && stride != 2) { set_error("projection block: stride %d (need 1 or 2)", stride); return WINO_E_ARG; }
   if (N < 1 || Hin < 1 || Win < 1) { set_error("projection block: bad N=%d Hin=%d Win=%d", N, Hin, Win); return WINO_E_SHAPE; }
   if (Cin <= 0 || Cm <= 0 || C4 <= 0 || Cin % 32 || Cm % 64 || C4 % 64) {
@@ -78,11 +77,8 @@ static int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stri
   *g = ProjGeom{N, Hin, Win, Cin, Cm, C4, stride, H, W, (long)M};
   return WINO_OK;
 }
-// the v1 block's middle layer is the Winograd 3x3 (Cm -> Cm at H x W): its shape limits, the filter matrix's among
-// them, before anything is launched
-static int check_proj_3x3(const ProjGeom& g) { return check_conv3x3_dims(g.H, g.W, g.Cm, g.Cm); }
 // the workspace holds t1 and t2, written before the tail reads x (its shortcut) and writes out: it must overlap neither
-static int check_ws_overlap(const ProjGeom& g, const void* x, const void* out, const void* workspace, size_t need) {
+int check_ws_overlap(const ProjGeom& g, const void* x, const void* out, const void* workspace, size_t need) {
   const size_t x_b = (size_t)g.N * g.Hin * g.Win * g.Cin * sizeof(float), out_b = (size_t)g.M * g.C4 * sizeof(float);
   if (overlaps(workspace, need, x, x_b) || overlaps(workspace, need, out, out_b)) {
     set_error("the workspace overlaps x or out");
@@ -90,6 +86,12 @@ static int check_ws_overlap(const ProjGeom& g, const void* x, const void* out, c
   }
   return WINO_OK;
 }
+
+namespace {
+
+// the v1 block's middle layer is the Winograd 3x3 (Cm -> Cm at H x W): its shape limits, the filter matrix's among
+// them, before anything is launched
+static int check_proj_3x3(const ProjGeom& g) { return check_conv3x3_dims(g.H, g.W, g.Cm, g.Cm); }
 static ProjGeo proj_geo(const ProjGeom& g, const float* x) {
   return ProjGeo{x, (unsigned)g.Hin * (unsigned)g.Win, (unsigned)(g.s * g.Win), (unsigned)g.s, g.Cin, g.Cm};
 }
@@ -102,6 +104,34 @@ static Plan1x1 plan_tail(const ProjGeom& g, int cus, const Knobs& kn) { return p
 static int form_of(const Plan1x1& p) { return p.small.use ? WINO_1X1_FORM_LATENCY : p.sk ? WINO_1X1_FORM_STREAM_K : WINO_1X1_FORM_TILED; }
 
 }  // namespace
+
+// the first 1x1 at full input resolution (the v1.5 and the grouped placements): its pixel rows, row tiles and ring pass
+int check_first_1x1_full(int N, int Hin, int Win, int Cm) {
+  const unsigned long long M1 = (unsigned long long)N * Hin * Win;
+  const unsigned long long ring1 = (unsigned long long)N * (2ull * (Win + 2) + 2ull * Hin) * (Cm / 4);
+  if (Hin > 4094 || Win > 4094 || M1 >= (1ull << 31) || (M1 + BM - 1) / BM > (1ull << 24) || ring1 >= FOUR_GIB) {
+    set_error("projection block: the first 1x1 at %dx%d x %d images is too large for one launch", Hin, Win, N);
+    return WINO_E_SHAPE;
+  }
+  return WINO_OK;
+}
+
+// the fused tail (A_TWO): out = relu(t2 . [bn3Scale w3] + xs . [bnpScale wp] + bias), t2 padded [N][H+2][W+2][Cm]
+int launch_proj_tail(const ProjGeom& g, const float* t2, const float* tail_packed, const float* x, float* out, int dev,
+                     int cus, const Knobs& kn, hipStream_t s) {
+  const float* bias = tail_packed + (size_t)(g.Cm + g.Cin) * g.C4;
+  return launch_1x1<A_TWO>(plan_tail(g, cus, kn), dev,
+                           {t2, tail_packed, bias, bias + g.C4, nullptr, out, g.M, g.Cm + g.Cin, g.C4,
+                            WINO_RELU | WINO_A_PADDED, make_padgeo(g.H, g.W), proj_geo(g, x)},
+                           s);
+}
+
+int prepare_proj_tail(const ProjGeom& g, int dev, int cus, hipStream_t s) {
+  const Plan1x1 pt = plan_tail(g, cus, knobs());
+  SkBufs bufs;
+  return pt.sk ? tiled_scratch(dev, s, pt, &bufs) : WINO_OK;
+}
+
 }  // namespace wino
 
 using namespace wino;
@@ -166,12 +196,7 @@ int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4,
 // shortcut are the same), the first 1x1 at full input resolution, and the stride-2 3x3's own limits.
 static int check_v15(int N, int Hin, int Win, int Cin, int Cm, int C4, ProjGeom* g) {
   if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, 2, g)) return rc;
-  const unsigned long long M1 = (unsigned long long)N * Hin * Win;
-  const unsigned long long ring1 = (unsigned long long)N * (2ull * (Win + 2) + 2ull * Hin) * (Cm / 4);
-  if (Hin > 4094 || Win > 4094 || M1 >= (1ull << 31) || (M1 + BM - 1) / BM > (1ull << 24) || ring1 >= FOUR_GIB) {
-    set_error("v1.5 projection block: the first 1x1 at %dx%d x %d images is too large for one launch", Hin, Win, N);
-    return WINO_E_SHAPE;
-  }
+  if (int rc = check_first_1x1_full(N, Hin, Win, Cm)) return rc;
   S2Geom g2;
   return check_s2(N, Hin, Win, Cm, Cm, &g2);
 }
@@ -205,10 +230,7 @@ int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, co
   if (rc) return rc;
   rc = wino_conv3x3_bn_relu_hw(t1, U2, bn2Bias, bn2Scale, t2, N, g.H, g.W, Cm, Cm, 1, s);
   if (rc) return rc;
-  const float* bias = tail_packed + (size_t)(Cm + Cin) * C4;
-  return launch_1x1<A_TWO>(plan_tail(g, cus, kn), dev,
-                           {t2, tail_packed, bias, bias + C4, nullptr, out, g.M, Cm + Cin, C4, WINO_RELU | WINO_A_PADDED, pg, xg},
-                           hs);
+  return launch_proj_tail(g, t2, tail_packed, x, out, dev, cus, kn, hs);
 }
 
 size_t wino_proj_block_v15_workspace_bytes_hw(int N, int Hin, int Win, int Cm) {
@@ -223,9 +245,7 @@ int wino_proj_block_v15_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int
   if (int rc = current_device(&dev, &cus)) return rc;
   if (int rc = wino_conv1x1_prepare((long)N * Hin * Win, Cin, Cm, s)) return rc;
   if (int rc = wino_conv3x3_s2_prepare_hw(N, Hin, Win, Cm, Cm, s)) return rc;
-  const Plan1x1 pt = plan_tail(g, cus, knobs());
-  SkBufs bufs;
-  return pt.sk ? tiled_scratch(dev, (hipStream_t)s, pt, &bufs) : WINO_OK;
+  return prepare_proj_tail(g, dev, cus, (hipStream_t)s);
 }
 
 int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
@@ -247,11 +267,7 @@ int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias
   if (rc) return rc;
   rc = wino_conv3x3_s2_bn_relu_hw(t1, w2_taps, bn2Bias, bn2Scale, t2, N, Hin, Win, Cm, Cm, 1, s);
   if (rc) return rc;
-  const float* bias = tail_packed + (size_t)(Cm + Cin) * C4;
-  return launch_1x1<A_TWO>(plan_tail(g, cus, knobs()), dev,
-                           {t2, tail_packed, bias, bias + C4, nullptr, out, g.M, Cm + Cin, C4, WINO_RELU | WINO_A_PADDED,
-                            make_padgeo(g.H, g.W), proj_geo(g, x)},
-                           (hipStream_t)s);
+  return launch_proj_tail(g, t2, tail_packed, x, out, dev, cus, knobs(), (hipStream_t)s);
 }
 
 }  // extern "C"

@@ -1,4 +1,5 @@
-"""Whole torchvision ResNets (18, 34, 50, 101, 152) on the library's kernels.
+"""Whole torchvision ResNets (18, 34, 50, 101, 152), Wide ResNets (50-2, 101-2) and ResNeXts (50 32x4d, 101 32x8d,
+101 64x4d) on the library's kernels.
 
 ``ResNet.from_state_dict(sd, arch)`` takes a torchvision state dict (its key names), folds every BN and packs every
 filter once; ``model(x_nchw)`` returns the logits.  The forward is a straight chain of launches on the current
@@ -9,7 +10,9 @@ stream: the stem, the blocks, the head.
   reads the padded map without its ring.
 - ResNet-50 / -101 / -152 (bottlenecks, torchvision's v1.5 placement) use the unpadded layout [N][H][W][C]:
   ``proj_block`` at stride 1 opens conv2, ``proj_block_v15`` opens conv3..conv5, and ``residual_block`` ping-pongs
-  between the stage's two tensors.
+  between the stage's two tensors.  The Wide ResNets are the same blocks with a middle width of 2 x planes.
+- The ResNeXts use the same layout and ping-pong with the grouped 3x3 in the middle of every block:
+  ``grouped_proj_block`` opens every stage (stride 1 in conv2, 2 after it), ``grouped_residual_block`` follows.
 
 ``prepare(N, H, W)`` allocates the activations and one shared workspace for an input shape and reserves every
 launch's stream scratch, so that a whole forward can then be captured in one ``torch.cuda.graph``.
@@ -19,9 +22,11 @@ from __future__ import annotations
 import torch
 
 from . import (WinoError, _out_hw, avgpool_fc, basic_block, basic_block_prepare, basic_block_s2,
-               basic_block_s2_prepare, filter_pack_s2, filter_transform_f2, head_pack, head_prepare, lib, proj_block,
-               proj_block_prepare, proj_block_v15, proj_block_v15_prepare, proj_tail_pack, residual_block,
-               residual_block_prepare, s2_proj_pack, stem, stem_filter_pack, stem_out_hw)
+               basic_block_s2_prepare, filter_pack_grouped, filter_pack_s2, filter_transform_f2, grouped_proj_block,
+               grouped_proj_block_prepare, grouped_proj_block_workspace_bytes, grouped_residual_block,
+               grouped_residual_block_prepare, head_pack, head_prepare, lib, proj_block, proj_block_prepare,
+               proj_block_v15, proj_block_v15_prepare, proj_tail_pack, residual_block, residual_block_prepare,
+               s2_proj_pack, stem, stem_filter_pack, stem_out_hw)
 from ._net import BN_KEYS, Net, check_state_dict
 
 # arch -> (bottleneck?, blocks per stage)
@@ -31,8 +36,28 @@ ARCHS = {
     "resnet50": (True, (3, 4, 6, 3)),
     "resnet101": (True, (3, 4, 23, 3)),
     "resnet152": (True, (3, 8, 36, 3)),
+    "resnext50_32x4d": (True, (3, 4, 6, 3)),
+    "resnext101_32x8d": (True, (3, 4, 23, 3)),
+    "resnext101_64x4d": (True, (3, 4, 23, 3)),
+    "wide_resnet50_2": (True, (3, 4, 6, 3)),
+    "wide_resnet101_2": (True, (3, 4, 23, 3)),
+}
+# arch -> (groups, width_per_group) of its bottlenecks' 3x3; every other arch: (1, 64)
+WIDTHS = {
+    "resnext50_32x4d": (32, 4),
+    "resnext101_32x8d": (32, 8),
+    "resnext101_64x4d": (64, 4),
+    "wide_resnet50_2": (1, 128),
+    "wide_resnet101_2": (1, 128),
 }
 PLANES = (64, 128, 256, 512)
+
+
+def mid_channels(arch: str, planes: int):
+    """(groups, Cm) of a bottleneck of `arch`: the middle width planes * width_per_group / 64 * groups (torchvision's
+    Bottleneck), in `groups` groups."""
+    groups, wpg = WIDTHS.get(arch, (1, 64))
+    return groups, planes * wpg // 64 * groups
 
 
 def stage_shapes(arch: str, H: int, W: int):
@@ -69,10 +94,11 @@ def expected_keys(arch: str, classes: int):
             stride = 2 if (b == 0 and L > 1) else 1
             if bottleneck:
                 cout = planes * 4
-                exp[f"{p}.conv1.weight"] = (planes, cin, 1, 1)
-                exp[f"{p}.conv2.weight"] = (planes, planes, 3, 3)
-                exp[f"{p}.conv3.weight"] = (cout, planes, 1, 1)
-                bn(f"{p}.bn1", planes), bn(f"{p}.bn2", planes), bn(f"{p}.bn3", cout)
+                groups, cm = mid_channels(arch, planes)
+                exp[f"{p}.conv1.weight"] = (cm, cin, 1, 1)
+                exp[f"{p}.conv2.weight"] = (cm, cm // groups, 3, 3)
+                exp[f"{p}.conv3.weight"] = (cout, cm, 1, 1)
+                bn(f"{p}.bn1", cm), bn(f"{p}.bn2", cm), bn(f"{p}.bn3", cout)
             else:
                 cout = planes
                 exp[f"{p}.conv1.weight"] = (planes, cin, 3, 3)
@@ -104,6 +130,7 @@ class ResNet(Net):
         super().__init__(device)
         self.arch, self.classes = arch, classes
         self.bottleneck, self.blocks = ARCHS[arch]
+        self.groups = WIDTHS.get(arch, (1, 64))[0]
 
     # ------------------------------------------------------------------ loading
     @classmethod
@@ -128,19 +155,30 @@ class ResNet(Net):
                 bn1, bn2 = self._fold_bn(sd, f"{p}.bn1", eps), self._fold_bn(sd, f"{p}.bn2", eps)
                 if self.bottleneck:
                     cout = planes * 4
+                    cm = mid_channels(self.arch, planes)[1]
                     w1, bn3 = w1x1(f"{p}.conv1.weight"), self._fold_bn(sd, f"{p}.bn3", eps)
+                    grouped = self.groups > 1   # ResNeXt: the grouped 3x3 in every block
                     if first:
                         tail = proj_tail_pack(w1x1(f"{p}.conv3.weight"), bn3, w1x1(f"{p}.downsample.0.weight"),
                                               self._fold_bn(sd, f"{p}.downsample.1", eps))
-                        if L == 1:   # stride 1: the v1 and v1.5 placements are the same block
+                        if grouped:
+                            w2 = filter_pack_grouped(self._t(sd[f"{p}.conv2.weight"]), self.groups)
+                            # stride 1 in conv2, 2 (on the 3x3) in conv3..conv5
+                            blocks.append(("grouped_proj" if L == 1 else "grouped_proj_s2", cin, cm, cout,
+                                           (w1, bn1, w2, bn2, tail)))
+                        elif L == 1:   # stride 1: the v1 and v1.5 placements are the same block
                             w2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
-                            blocks.append(("proj", cin, planes, cout, (w1, bn1, w2, bn2, tail)))
+                            blocks.append(("proj", cin, cm, cout, (w1, bn1, w2, bn2, tail)))
                         else:
                             w2 = filter_pack_s2(self._t(sd[f"{p}.conv2.weight"]))
-                            blocks.append(("proj_v15", cin, planes, cout, (w1, bn1, w2, bn2, tail)))
+                            blocks.append(("proj_v15", cin, cm, cout, (w1, bn1, w2, bn2, tail)))
+                    elif grouped:
+                        wg = filter_pack_grouped(self._t(sd[f"{p}.conv2.weight"]), self.groups)
+                        blocks.append(("grouped_residual", cin, cm, cout,
+                                       (w1, bn1, wg, bn2, w1x1(f"{p}.conv3.weight"), bn3)))
                     else:
                         U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
-                        blocks.append(("residual", cin, planes, cout,
+                        blocks.append(("residual", cin, cm, cout,
                                        (w1, bn1, U2, bn2, w1x1(f"{p}.conv3.weight"), bn3)))
                 else:
                     cout = planes
@@ -194,6 +232,13 @@ class ResNet(Net):
                     elif kind == "proj_v15":
                         ws = max(ws, L.wino_proj_block_v15_workspace_bytes_hw(N, h, w, cm))
                         proj_block_v15_prepare(N, h, w, cin, cm, cout)
+                    elif kind in ("grouped_proj", "grouped_proj_s2"):
+                        stride = 2 if kind == "grouped_proj_s2" else 1
+                        ws = max(ws, grouped_proj_block_workspace_bytes(N, h, w, cm, stride))
+                        grouped_proj_block_prepare(N, h, w, cin, cm, cout, self.groups, stride)
+                    elif kind == "grouped_residual":
+                        ws = max(ws, L.wino_residual_block_workspace_bytes_hw(N, ho, wo, cm))
+                        grouped_residual_block_prepare(N, ho, wo, cout, cm, self.groups)
                     else:
                         ws = max(ws, L.wino_residual_block_workspace_bytes_hw(N, ho, wo, cm))
                         residual_block_prepare(N, cout, cm, ho, wo)
@@ -222,6 +267,12 @@ class ResNet(Net):
                         proj_block(cur, p[0], p[1], p[2], p[3], p[4], 1, out=nxt, workspace=ws)
                     elif kind == "proj_v15":
                         proj_block_v15(cur, p[0], p[1], p[2], p[3], p[4], out=nxt, workspace=ws)
+                    elif kind in ("grouped_proj", "grouped_proj_s2"):
+                        grouped_proj_block(cur, p[0], p[1], p[2], p[3], p[4], self.groups,
+                                           2 if kind == "grouped_proj_s2" else 1, out=nxt, workspace=ws)
+                    elif kind == "grouped_residual":
+                        grouped_residual_block(cur, p[0], p[1], p[2], p[3], p[4], p[5], self.groups, out=nxt,
+                                               workspace=ws)
                     else:
                         residual_block(cur, p[0], p[1], p[2], p[3], p[4], p[5], out=nxt, workspace=ws)
                 cur = nxt
@@ -255,9 +306,9 @@ class ResNet(Net):
             for kind, cin, cm, cout, _ in blocks:
                 px = ho * wo
                 if self.bottleneck:
-                    hin = px * 4 if kind == "proj_v15" else px
-                    f += 2.0 * (hin * cin * cm + px * 9 * cm * cm + px * cm * cout)
-                    if kind in ("proj", "proj_v15"):
+                    hin = px * 4 if kind in ("proj_v15", "grouped_proj_s2") else px
+                    f += 2.0 * (hin * cin * cm + px * 9 * cm * (cm // self.groups) + px * cm * cout)
+                    if kind in ("proj", "proj_v15", "grouped_proj", "grouped_proj_s2"):
                         f += 2.0 * px * cin * cout
                 else:
                     f += 2.0 * px * 9 * (cin * cout + cout * cout)
@@ -266,4 +317,4 @@ class ResNet(Net):
         return f + 2.0 * self.feat_c * self.classes
 
 
-__all__ = ["ARCHS", "ResNet", "stage_shapes", "expected_keys", "validate_state_dict"]
+__all__ = ["ARCHS", "WIDTHS", "ResNet", "stage_shapes", "expected_keys", "mid_channels", "validate_state_dict"]

@@ -58,7 +58,9 @@ extern "C" {
  * wino_s2_proj_pack, wino_conv3x3_s2_proj_bn_relu_hw, wino_basic_block_s2_workspace_bytes_hw, wino_basic_block_s2_hw,
  * wino_basic_block_s2_prepare_hw, wino_stem_filter_elems, wino_stem_filter_pack, wino_stem_hw, wino_stem_plan,
  * wino_head_elems, wino_head_pack, wino_head_workspace_bytes, wino_head_prepare, wino_avgpool_fc_hw,
- * wino_conv3x3_bn_relu_pool_hw, wino_image_pack_hw, wino_avgpool7_flatten_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_conv3x3_bn_relu_pool_hw, wino_image_pack_hw, wino_avgpool7_flatten_hw, wino_conv3x3_grouped_filter_elems,
+ * wino_conv3x3_grouped_filter_pack, wino_conv3x3_grouped_bn_relu_hw, wino_grouped_residual_block_hw,
+ * wino_grouped_residual_block_prepare_hw, wino_grouped_proj_block_hw, wino_grouped_proj_block_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -559,6 +561,49 @@ int wino_conv3x3_bn_relu_pool_hw(const float* in, const float* U, const float* b
 int wino_image_pack_hw(const float* x, float* out, int N, int Cin, int H, int W, int Cpad, wino_stream_t s);
 int wino_avgpool7_flatten_hw(const float* feat, float* out, int N, int H, int W, int C, int in_padded,
                              wino_stream_t s);
+
+/* ---- grouped 3x3 convolution + BN (+ReLU) and the ResNeXt bottleneck blocks ---------------------------------------
+ *   out = act(bnScale[k] * conv3x3_grouped(in, w) + bnBias[k]),  stride 1 or 2, pad 1, C -> C channels in `groups`
+ *   groups of Cg = C / groups: output channel k reads input channels (k / Cg) * Cg .. + Cg - 1
+ *   in      [N][Hin+2][Win+2][C] with a zero ring (what WINO_C_PADDED layers write)
+ *   packed  from wino_conv3x3_grouped_filter_pack (wino_conv3x3_grouped_filter_elems(C, groups) floats, 0 for an
+ *           illegal shape; the layout is private to the library), of torch's w [C][Cg][3][3]
+ *   out     [N][H+2][W+2][C], the result at [1..H][1..W], the ring written 0; H = (Hin-1)/stride + 1, the same for W
+ * Constraints: C % 64 == 0 and Cg in {4, 8, 16, 32, 64} -- every 3x3 of resnext50_32x4d, resnext101_32x8d and
+ * resnext101_64x4d -- so that a 64-channel output block reads exactly its own 64 input channels; anything else (a
+ * `groups` that does not divide C, Cg = 2, groups = 1 at C > 64) is WINO_E_SHAPE; a stride other than 1 or 2 is
+ * WINO_E_ARG.  Any N: every image is addressed from its own 64-bit base, and one padded input image must stay below
+ * 2^31 elements (WINO_E_SHAPE).  in and out must not overlap (WINO_E_ARG).  One launch, an implicit GEMM on the f32 MFMA
+ * (exact f32; there is no bf16 path); no stream scratch, so there is no prepare.  BN stays in its two vectors.
+ *
+ * wino_grouped_residual_block_hw: wino_residual_block_hw with this layer in the middle (wg from
+ * wino_conv3x3_grouped_filter_pack(Cm, groups)); x, out [N][H][W][C4].
+ * wino_grouped_proj_block_hw: the projection bottleneck in torchvision's placement -- the first 1x1 at the full
+ * Hin x Win, this layer at `stride` (1 or 2), then the fused tail of wino_proj_block_hw (tail_packed from
+ * wino_proj_tail_pack); x [N][Hin][Win][Cin], out [N][H][W][C4].
+ * Every argument, shape and overlap is checked before the first launch.  The blocks' intermediates are exactly their
+ * dense counterparts', so their workspaces are sized by the dense blocks' queries:
+ *   wino_grouped_residual_block_hw          wino_residual_block_workspace_bytes_hw(N, H, W, Cm)
+ *   wino_grouped_proj_block_hw, stride 1    wino_proj_block_workspace_bytes_hw(N, H, W, Cm)
+ *   wino_grouped_proj_block_hw, stride 2    wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm)
+ * A smaller workspace, or one that overlaps x or out, is WINO_E_ARG.  The *_prepare_hw entry points reserve the stream-K
+ * scratch of the blocks' two 1x1 launches ahead of a graph capture. */
+size_t wino_conv3x3_grouped_filter_elems(int C, int groups);
+int wino_conv3x3_grouped_filter_pack(const float* w, float* packed, int C, int groups, wino_stream_t s);
+int wino_conv3x3_grouped_bn_relu_hw(const float* in, const float* packed, const float* bnBias, const float* bnScale,
+                                    float* out, int N, int Hin, int Win, int C, int groups, int stride, int relu,
+                                    wino_stream_t s);
+int wino_grouped_residual_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                                   const float* wg, const float* bn2Bias, const float* bn2Scale, const float* w3,
+                                   const float* bn3Bias, const float* bn3Scale, float* out, int N, int H, int W, int C4,
+                                   int Cm, int groups, void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_grouped_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, int groups, wino_stream_t s);
+int wino_grouped_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                               const float* wg, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
+                               float* out, int N, int Hin, int Win, int Cin, int Cm, int C4, int groups, int stride,
+                               void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_grouped_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int groups, int stride,
+                                       wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */

@@ -1,0 +1,396 @@
+"""GPU tests of the grouped 3x3 layer (wino_conv3x3_grouped_bn_relu_hw), the two ResNeXt blocks built on it and the
+ResNeXt / Wide-ResNet networks.
+
+The oracle is F.conv2d(..., groups=G) in fp64 on the CPU with BN and the ReLU applied in fp64; an fp32 CPU grouped
+conv sits at 2-4e-7 from it at these shapes, and the bar is the project's layer bar, max |diff| / max |want| < 2e-5.
+Every layer and block tensor lives on a guarded arena (tests/guarded.py) at both placements of guarded.ALIGNS, and
+arena.check runs after every case: no guard word written, every input equal to its master bit for bit."""
+import importlib
+
+import pytest
+
+import guarded
+
+pytestmark = pytest.mark.gpu
+
+TIGHT = 2e-5
+NET_TOL = 1e-3
+CGS = (4, 8, 16, 32, 64)
+MAPS = ((1, 1), (2, 3), (7, 5), (9, 8))       # 9 x 8: stride 2 clips an odd and an even edge
+
+
+@pytest.fixture(scope="module")
+def torch_dev():
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a GPU"
+    return torch, torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def R(pkg):
+    return importlib.import_module("cuda_winograd_amd.resnet")
+
+
+def _rel(torch, got, want):
+    got = got.detach().cpu().double()
+    assert got.shape == want.shape, (got.shape, want.shape)
+    assert not torch.isnan(got).any()
+    return float((got - want).abs().max() / want.abs().max())
+
+
+# ---------------------------------------------------------------------------------------------------- the layer
+def _layer_inputs(torch, N, Hin, Win, C, Cg, seed):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.zeros(N, Hin + 2, Win + 2, C)
+    x[:, 1:-1, 1:-1, :] = torch.rand(N, Hin, Win, C, generator=g) - 0.5
+    w = (torch.rand(C, Cg, 3, 3, generator=g) - 0.5) * (4.0 / (9 * Cg) ** 0.5)
+    bias = torch.rand(C, generator=g) - 0.5
+    sign = (torch.rand(C, generator=g) < 0.5).float() * 2 - 1          # BN scales of both signs
+    scale = (torch.rand(C, generator=g) + 0.5) * sign
+    return x, w, bias, scale
+
+
+def _layer_reference(torch, x, w, bias, scale, groups, stride, relu):
+    """fp64 on the CPU, NHWC interior [N][H][W][C]."""
+    F = torch.nn.functional
+    y = F.conv2d(x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double(), w.double(), stride=stride, padding=1, groups=groups)
+    y = y * scale.double()[None, :, None, None] + bias.double()[None, :, None, None]
+    return (torch.relu(y) if relu else y).permute(0, 2, 3, 1)
+
+
+def _run_layer(pkg, torch_dev, x, w, bias, scale, groups, stride, relu, align, tag):
+    """The layer on a guarded arena: (out interior, on the CPU); the ring is checked to be exactly 0 here."""
+    torch, dev = torch_dev
+    N, Hin, Win, C = x.shape[0], x.shape[1] - 2, x.shape[2] - 2, x.shape[3]
+    H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    packed = pkg.filter_pack_grouped(w.to(dev), groups)
+    assert packed.numel() == pkg.lib().wino_conv3x3_grouped_filter_elems(C, groups)
+    arena = guarded.Arena(torch, dev, align)
+    xin, pk = arena.input(x, name="in"), arena.input(packed, name="packed")
+    b, s = arena.input(bias, name="bias"), arena.input(scale, name="scale")
+    out = arena.output(N, H + 2, W + 2, C, name="out")
+    got = pkg.conv3x3_grouped_bn_relu(xin, pk, b, s, groups, stride=stride, relu=relu, out=out)
+    assert got.data_ptr() == out.data_ptr()
+    arena.check(tag)
+    o = out.cpu()
+    ring = o.clone()
+    ring[:, 1:-1, 1:-1, :] = 0
+    assert torch.equal(ring, torch.zeros_like(ring)), f"{tag}: ring not 0"     # (a NaN left in the ring fails too)
+    return o[:, 1:-1, 1:-1, :]
+
+
+def _layer_case(pkg, torch_dev, N, Hin, Win, C, Cg, stride, relu, align):
+    torch, _ = torch_dev
+    tag = f"grouped N={N} {Hin}x{Win} C={C} Cg={Cg} s={stride} relu={relu} align={align}"
+    x, w, bias, scale = _layer_inputs(torch, N, Hin, Win, C, Cg, seed=1000 * Hin + 10 * Win + Cg + stride)
+    got = _run_layer(pkg, torch_dev, x, w, bias, scale, C // Cg, stride, relu, align, tag)
+    want = _layer_reference(torch, x, w, bias, scale, C // Cg, stride, relu)
+    err = _rel(torch, got, want)
+    assert err < TIGHT, (tag, err)
+    return want
+
+
+@pytest.mark.parametrize("C", [64, 128])      # two channel blocks catch a wrong block base
+@pytest.mark.parametrize("Cg", CGS)
+def test_layer_matches_fp64(Cg, C, pkg, torch_dev):
+    saw_negative = False
+    for align in guarded.ALIGNS:
+        for stride in (1, 2):
+            for Hin, Win in MAPS:
+                for N, relu in ((1, True), (3, False), (1, False), (3, True)):
+                    want = _layer_case(pkg, torch_dev, N, Hin, Win, C, Cg, stride, relu, align)
+                    saw_negative |= bool((want < 0).any())
+    assert saw_negative      # relu off really left negative outputs to compare
+
+
+@pytest.mark.parametrize("stride", [1, 2])
+@pytest.mark.parametrize("Cg", [4, 64])
+def test_layer_past_one_tile_in_every_direction(Cg, stride, pkg, torch_dev):
+    """N = 3, 29 x 23, C = 192: several tiles down and across (clipped last ones), three channel blocks, three images."""
+    for align in guarded.ALIGNS:
+        _layer_case(pkg, torch_dev, 3, 29, 23, 192, Cg, stride, True, align)
+
+
+@pytest.mark.parametrize("Cg", CGS)
+def test_one_hot_weights_do_not_leak_across_groups(Cg, pkg, torch_dev):
+    """One non-zero tap from one input channel of one group: every output channel outside that group is exactly
+    act(bias) -- a filter value packed off the block diagonal, or a column tile contracting over a neighbour's
+    channels, shows here, where random weights would hide it below the tolerance."""
+    torch, _ = torch_dev
+    C, N, Hin, Win = 128, 2, 7, 5
+    groups = C // Cg
+    x, _, bias, scale = _layer_inputs(torch, N, Hin, Win, C, Cg, seed=77 + Cg)
+    for i, (grp, cl, tap) in enumerate(((0, 0, 4), (groups - 1, Cg - 1, 0), (groups // 2, Cg // 2, 8), (1 % groups, 1, 5))):
+        for stride, relu in ((1, False), (2, True)):
+            w = torch.zeros(C, Cg, 3, 3)
+            w[grp * Cg:(grp + 1) * Cg, cl, tap // 3, tap % 3] = torch.arange(1, Cg + 1, dtype=torch.float32) / Cg
+            tag = f"one-hot Cg={Cg} group={grp} channel={cl} tap={tap} s={stride}"
+            got = _run_layer(pkg, torch_dev, x, w, bias, scale, groups, stride, relu, guarded.ALIGNS[i % 2], tag)
+            want = _layer_reference(torch, x, w, bias, scale, groups, stride, relu)
+            inside = torch.zeros(C, dtype=torch.bool)
+            inside[grp * Cg:(grp + 1) * Cg] = True
+            act = torch.relu(bias) if relu else bias
+            assert torch.equal(got[..., ~inside], act[~inside].expand_as(got[..., ~inside])), tag
+            assert _rel(torch, got[..., inside], want[..., inside]) < TIGHT, tag
+            assert float((want[..., inside] - act[inside].double()).abs().max()) > 0.05, tag   # the tap does something
+
+
+def test_bad_arguments_raise(pkg, torch_dev):
+    torch, dev = torch_dev
+    x, w, bias, scale = (t.to(dev) for t in _layer_inputs(torch, 1, 7, 5, 128, 4, seed=3))
+    packed = pkg.filter_pack_grouped(w, 32)
+    # packed for another group count.  (Cg = 4, 8 and 16 all pack to 9 * C * 16 floats -- a column tile is 16 wide --
+    # so the size tells those apart from Cg = 32 and 64 only: the buffer is opaque and carries no group count.)
+    with pytest.raises(pkg.WinoError):
+        pkg.conv3x3_grouped_bn_relu(x, packed, bias, scale, 4)
+    with pytest.raises(pkg.WinoError):
+        pkg.conv3x3_grouped_bn_relu(x, packed[:-4], bias, scale, 32)         # a short buffer
+    with pytest.raises(pkg.WinoError):
+        pkg.conv3x3_grouped_bn_relu(x, packed, bias, scale, 32, stride=3)
+    with pytest.raises(pkg.WinoError):
+        pkg.conv3x3_grouped_bn_relu(x, packed, bias, scale, 32, out=torch.empty(1, 9, 7, 64, device=dev))
+    with pytest.raises(pkg.WinoError):
+        pkg.filter_pack_grouped(torch.zeros(128, 2, 3, 3, device=dev), 64)    # Cg = 2
+    with pytest.raises(pkg.WinoError, match="rc=-3"):
+        pkg.conv3x3_grouped_bn_relu(x, packed, bias, scale, 32, out=x)        # in place
+
+
+# ---------------------------------------------------------------------------------------------------- the blocks
+CIN, CM, C4, GROUPS = 64, 128, 256, 32
+
+
+class _Blocks:
+    """The tensors of one identity and one projection block (folded BN vectors, NHWC activations) and their fp64
+    compositions."""
+
+    def __init__(self, torch, N, Hin, Win, seed):
+        g = torch.Generator().manual_seed(seed)
+        r = lambda *s: torch.rand(*s, generator=g) - 0.5
+        self.torch = torch
+        self.N, self.Hin, self.Win = N, Hin, Win
+        self.x_res = r(N, Hin, Win, C4)
+        self.x_proj = r(N, Hin, Win, CIN)
+        self.w1_res = r(C4, CM) / C4 ** 0.5 * 4
+        self.w1_proj = r(CIN, CM) / CIN ** 0.5 * 4
+        self.wg = r(CM, CM // GROUPS, 3, 3) / (9 * CM // GROUPS) ** 0.5 * 4
+        self.w3 = r(CM, C4) / CM ** 0.5 * 4
+        self.wp = r(CIN, C4) / CIN ** 0.5 * 2
+        self.bn = [(r(c), r(c) + 1.0) for c in (CM, CM, C4, C4)]     # (bias, scale): bn1, bn2, bn3, bnp
+
+    def _bn(self, y, i):
+        b, s = self.bn[i]
+        return y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
+
+    def _middle(self, x, w1, stride):
+        torch = self.torch
+        F = torch.nn.functional
+        one = lambda w: w.double().t()[:, :, None, None]              # [Cin][Cout] -> [Cout][Cin][1][1]
+        t1 = torch.relu(self._bn(F.conv2d(x, one(w1)), 0))
+        t2 = torch.relu(self._bn(F.conv2d(t1, self.wg.double(), stride=stride, padding=1, groups=GROUPS), 1))
+        return self._bn(F.conv2d(t2, one(self.w3)), 2)
+
+    def reference_residual(self):
+        x = self.x_res.permute(0, 3, 1, 2).double()
+        return self.torch.relu(self._middle(x, self.w1_res, 1) + x).permute(0, 2, 3, 1)
+
+    def reference_proj(self, stride):
+        F = self.torch.nn.functional
+        x = self.x_proj.permute(0, 3, 1, 2).double()
+        sc = self._bn(F.conv2d(x, self.wp.double().t()[:, :, None, None], stride=stride), 3)
+        return self.torch.relu(self._middle(x, self.w1_proj, stride) + sc).permute(0, 2, 3, 1)
+
+
+def _run_blocks(pkg, torch_dev, blk, stride, align, tag):
+    """Both blocks on one arena, the workspaces exactly the reported sizes between sentinel guards."""
+    torch, dev = torch_dev
+    L = pkg.lib()
+    N, Hin, Win = blk.N, blk.Hin, blk.Win
+    H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    arena = guarded.Arena(torch, dev, align)
+    a = lambda t, name: arena.input(t, name=name)
+    bn = [(a(b, f"bn{i}b"), a(s, f"bn{i}s")) for i, (b, s) in enumerate(blk.bn)]
+    wg = a(pkg.filter_pack_grouped(blk.wg.to(dev), GROUPS), "wg")
+    out = {}
+    # identity block (always stride 1, at Hin x Win)
+    x, w1, w3 = a(blk.x_res, "x_res"), a(blk.w1_res, "w1_res"), a(blk.w3, "w3")
+    need = L.wino_residual_block_workspace_bytes_hw(N, Hin, Win, CM)
+    ws = arena.workspace(need, name="ws_res")
+    assert ws.numel() * 4 == need
+    o = arena.output(N, Hin, Win, C4, name="out_res")
+    pkg.grouped_residual_block(x, w1, bn[0], wg, bn[1], w3, bn[2], GROUPS, out=o, workspace=ws)
+    out["residual"] = o
+    # projection block
+    xp, w1p = a(blk.x_proj, "x_proj"), a(blk.w1_proj, "w1_proj")
+    tail = a(pkg.proj_tail_pack(w3, bn[2], blk.wp.to(dev), bn[3]), "tail")
+    need = (L.wino_proj_block_workspace_bytes_hw(N, H, W, CM) if stride == 1
+            else L.wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, CM))
+    assert need == pkg.grouped_proj_block_workspace_bytes(N, Hin, Win, CM, stride)
+    wsp = arena.workspace(need, name="ws_proj")
+    assert wsp.numel() * 4 == need
+    op = arena.output(N, H, W, C4, name="out_proj")
+    pkg.grouped_proj_block(xp, w1p, bn[0], wg, bn[1], tail, GROUPS, stride, out=op, workspace=wsp)
+    out["proj"] = op
+    arena.check(tag)
+    assert pkg.tickets_in_use() == 0
+    # a workspace one byte smaller is refused (WINO_E_ARG) before anything is launched
+    for short, call in ((ws, "wino_grouped_residual_block_hw"), (wsp, "wino_grouped_proj_block_hw")):
+        args = ((x, w1, bn[0][0], bn[0][1], wg, bn[1][0], bn[1][1], w3, bn[2][0], bn[2][1], o) if short is ws else
+                (xp, w1p, bn[0][0], bn[0][1], wg, bn[1][0], bn[1][1], tail, op))
+        dims = (N, Hin, Win, C4, CM, GROUPS) if short is ws else (N, Hin, Win, CIN, CM, C4, GROUPS, stride)
+        rc = getattr(L, call)(*[t.data_ptr() for t in args], *dims, short.data_ptr(), short.numel() * 4 - 1,
+                              torch.cuda.current_stream().cuda_stream)
+        assert rc == -3, (call, rc)
+    arena.check(tag + " (short workspace)")
+    return {k: v.cpu() for k, v in out.items()}
+
+
+BLOCK_CASES = [(7, 9, 1), (2, 3, 1), (9, 8, 2), (3, 2, 2)]   # (Hin, Win, the projection block's stride)
+
+
+@pytest.mark.parametrize("forced", [False, True], ids=["planned", "stream_k"])
+@pytest.mark.parametrize("Hin,Win,stride", BLOCK_CASES)
+def test_blocks_match_fp64(Hin, Win, stride, forced, pkg, knobs, torch_dev):
+    """Cin 64 -> Cm 128 -> C4 256, groups 32, N = 2; `forced`: the 1x1 launches in the tiled kernel's stream-K form."""
+    torch, _ = torch_dev
+    if forced:
+        knobs.set("WINO_1X1_ALGO", "big")
+        knobs.set("WINO_1X1_SK", 1)
+    blk = _Blocks(torch, 2, Hin, Win, seed=100 * Hin + Win)
+    want = {"residual": blk.reference_residual(), "proj": blk.reference_proj(stride)}
+    for align in guarded.ALIGNS:
+        got = _run_blocks(pkg, torch_dev, blk, stride, align, f"blocks {Hin}x{Win} s={stride} forced={forced} align={align}")
+        for name in want:
+            err = _rel(torch, got[name], want[name])
+            assert err < TIGHT, (name, Hin, Win, stride, align, err)
+            assert 0.1 < float((want[name] > 0).double().mean()) < 1.0      # both sides of the final ReLU
+    assert pkg.tickets_in_use() == 0
+
+
+# ---------------------------------------------------------------------------------------------------- the networks
+def random_state_dict(torch, R, arch, classes=1000, seed=0):
+    """torchvision-format weights with O(1) activations: He-scaled convs (fan-in of the group), BN near identity, and a
+    small gamma on each block's last BN so that the residual sums stay O(1) over many blocks."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    last = "bn3" if R.ARCHS[arch][0] else "bn2"
+    for k, shape in R.expected_keys(arch, classes).items():
+        if k.endswith(".weight") and len(shape) == 4:
+            sd[k] = torch.randn(shape, generator=g) * (2.0 / (shape[1] * shape[2] * shape[3])) ** 0.5
+        elif k.endswith("running_mean"):
+            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
+        elif k.endswith("running_var"):
+            sd[k] = torch.rand(shape, generator=g) + 0.5
+            sd[k[: -len("running_var")] + "num_batches_tracked"] = torch.tensor(100)
+        elif k.endswith(".weight") and len(shape) == 1:
+            sd[k] = (torch.rand(shape, generator=g) + 0.5) * (0.2 if k.split(".")[-2] == last and k.startswith("layer") else 1.0)
+        elif k == "fc.weight":
+            sd[k] = torch.randn(shape, generator=g) * (1.0 / shape[1]) ** 0.5
+        elif k == "fc.bias":
+            sd[k] = torch.rand(shape, generator=g) - 0.5
+        else:
+            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
+    return sd
+
+
+def reference_forward(torch, sd, x, eps=1e-5):
+    """fp64 CPU forward of a torchvision ResNet / ResNeXt / Wide ResNet in eval mode, read off the state dict alone:
+    a block is a bottleneck when it has a conv3, its groups are conv2's out / in channel ratio, the stride sits on the
+    3x3 (or, in a basic block, on conv1).  Returns (logits, {stage: NHWC})."""
+    F = torch.nn.functional
+    d = {k: v.double() for k, v in sd.items()}
+
+    def bn(t, p):
+        return F.batch_norm(t, d[p + ".running_mean"], d[p + ".running_var"], d[p + ".weight"], d[p + ".bias"],
+                            False, 0.0, eps)
+
+    t = F.max_pool2d(torch.relu(bn(F.conv2d(x.double(), d["conv1.weight"], stride=2, padding=3), "bn1")), 3, 2, 1)
+    stages = {"stem": t.permute(0, 2, 3, 1)}
+    for L in range(1, 5):
+        b = 0
+        while f"layer{L}.{b}.conv1.weight" in d:
+            p = f"layer{L}.{b}"
+            s = 2 if (b == 0 and L > 1) else 1
+            if p + ".conv3.weight" in d:
+                w2 = d[p + ".conv2.weight"]
+                y = torch.relu(bn(F.conv2d(t, d[p + ".conv1.weight"]), p + ".bn1"))
+                y = torch.relu(bn(F.conv2d(y, w2, stride=s, padding=1, groups=w2.shape[0] // w2.shape[1]), p + ".bn2"))
+                y = bn(F.conv2d(y, d[p + ".conv3.weight"]), p + ".bn3")
+            else:
+                y = torch.relu(bn(F.conv2d(t, d[p + ".conv1.weight"], stride=s, padding=1), p + ".bn1"))
+                y = bn(F.conv2d(y, d[p + ".conv2.weight"], padding=1), p + ".bn2")
+            sc = t
+            if p + ".downsample.0.weight" in d:
+                sc = bn(F.conv2d(t, d[p + ".downsample.0.weight"], stride=s), p + ".downsample.1")
+            t = torch.relu(y + sc)
+            b += 1
+        stages[f"layer{L}"] = t.permute(0, 2, 3, 1)
+    return t.mean(dim=(2, 3)) @ d["fc.weight"].t() + d["fc.bias"], stages
+
+
+def _input(torch, dev, N, H, W, seed):
+    return (torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(seed)) * 2 - 1).to(dev)
+
+
+@pytest.mark.parametrize("arch,N,H", [("resnext50_32x4d", 2, 64), ("wide_resnet50_2", 2, 64), ("resnext101_64x4d", 1, 32)])
+def test_network_matches_fp64(arch, N, H, pkg, R, torch_dev):
+    torch, dev = torch_dev
+    sd = random_state_dict(torch, R, arch, seed=len(arch) + N)
+    model = pkg.ResNet.from_state_dict(sd, arch)
+    kinds = {kind for blocks in model.layers for kind, *_ in blocks}
+    if arch.startswith("resnext"):
+        assert kinds == {"grouped_proj", "grouped_proj_s2", "grouped_residual"}, kinds
+    else:
+        assert kinds == {"proj", "proj_v15", "residual"}, kinds
+    x = _input(torch, dev, N, H, H, seed=N + H)
+    logits, stages = model.forward(x, return_stages=True)
+    torch.cuda.synchronize()
+    want_logits, want = reference_forward(torch, sd, x.cpu())
+    errs = {name: _rel(torch, stages[name], want[name]) for name in want}
+    errs["logits"] = _rel(torch, logits, want_logits)
+    print(f"{arch} N={N} {H}x{H}: " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
+    assert not {k: v for k, v in errs.items() if not v < NET_TOL}, errs
+    assert pkg.tickets_in_use() == 0
+
+
+def test_resnext50_graph_replay_is_bitwise_eager(pkg, R, torch_dev):
+    torch, dev = torch_dev
+    arch, N, H, W = "resnext50_32x4d", 2, 64, 48
+    sd = random_state_dict(torch, R, arch, classes=10, seed=50)
+    model = pkg.ResNet.from_state_dict(sd, arch)
+    x = _input(torch, dev, N, H, W, seed=9)
+    sg = torch.cuda.Stream()
+    with torch.cuda.stream(sg):
+        model.prepare(N, H, W)
+        eager = model(x).clone()
+    sg.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=sg):
+        out = model(x)
+    out.fill_(float("nan"))
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(out, eager)
+    with torch.cuda.stream(sg):
+        assert pkg.tickets_in_use() == 0
+    want, _ = reference_forward(torch, sd, x.cpu())
+    assert _rel(torch, eager, want) < NET_TOL
+    del graph
+
+
+@pytest.mark.parametrize("arch", ["resnet18", "resnet34", "resnet50", "resnet101", "resnet152"])
+def test_existing_archs_have_not_moved(arch, pkg, R, torch_dev):
+    """The default (groups, width_per_group) = (1, 64) path: the same block kinds and shapes as before, the logits within
+    NET_TOL of the fp64 forward."""
+    torch, dev = torch_dev
+    sd = random_state_dict(torch, R, arch, seed=len(arch))
+    model = pkg.ResNet.from_state_dict(sd, arch)
+    assert model.groups == 1
+    for planes, blocks in zip(R.PLANES, model.layers):
+        assert all(cm == planes for _, _, cm, _, _ in blocks)
+        assert not any(kind.startswith("grouped") for kind, *_ in blocks)
+    x = _input(torch, dev, 1, 64, 64, seed=64)
+    logits = model(x)
+    torch.cuda.synchronize()
+    want, _ = reference_forward(torch, sd, x.cpu())
+    assert _rel(torch, logits, want) < NET_TOL
+    assert pkg.tickets_in_use() == 0
