@@ -355,30 +355,72 @@ def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, 
     return out
 
 
+def _bottleneck(entry, x, w1, bn1, mid, w2, bn2, last, bn3, out, workspace, stride=1, groups=None):
+    """The one body of the five bottleneck wrappers: operands checked against each other, workspace and output made or
+    checked, then `entry(x, w1, bn1, w2, bn2, last[, bn3], out, N, Hin, Win, Cin, Cm[, C4][, groups][, stride],
+    workspace, stream)`.  `mid` names what w2 is packed for: "U2" (filter_transform_f2: Winograd, a stride sits on the
+    first 1x1), "w2_taps" (filter_pack_s2: the 3x3 at stride 2, which its entry point does not take as an argument) or
+    "wg" (filter_pack_grouped: `stride` on the 3x3).  `last` is w3 with its bn3 (identity shortcut: C4 = Cin) or, bn3
+    None, the packed tail of a projection block."""
+    identity = bn3 is not None
+    x = _dev(x, "x")
+    if x.dim() != 4:
+        raise WinoError("x must be [N][H][W][C4]" if identity else "x must be [N][Hin][Win][Cin]")
+    N, Hin, Win, Cin = (int(v) for v in x.shape)
+    w1, w2, last = _dev(w1, "w1"), _dev(w2, mid), _dev(last, "w3" if identity else "tail")
+    Cm = int(w1.shape[1]) if w1.dim() == 2 else 0
+    if identity:
+        C4 = Cin
+        if w1.dim() != 2 or int(w1.shape[0]) != C4 or last.dim() != 2 or tuple(last.shape) != (Cm, C4):
+            raise WinoError("w1 must be [C4][Cm], w3 [Cm][C4]")
+    elif w1.dim() != 2 or int(w1.shape[0]) != Cin:
+        raise WinoError("w1 must be [Cin][Cm]")
+    if mid == "U2":
+        if w2.numel() != 16 * Cm * Cm:
+            raise WinoError(f"U2 must be a {Cm} -> {Cm} filter from filter_transform_f2 (16*Cm*Cm values)")
+    elif mid == "w2_taps":
+        if w2.dim() != 4 or tuple(w2.shape) != (3, 3, Cm, Cm):
+            raise WinoError(f"w2_taps must be [3][3][{Cm}][{Cm}]: pack it with filter_pack_s2")
+    else:
+        groups = _groups_of(w2, Cm, groups, "wg")
+    if not identity:
+        if last.numel() % (Cm + Cin + 2):
+            raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
+        C4 = last.numel() // (Cm + Cin + 2)
+        if int(stride) not in (1, 2):
+            raise WinoError(f"stride must be 1 or 2, got {stride}")
+    H, W = _out_hw(Hin, Win, int(stride))
+    vecs = _bn_vecs(bn1, bn2, bn3) if identity else _bn_vecs(bn1, bn2)
+    if any(v.numel() != c for v, c in zip(vecs, (Cm, Cm, Cm, Cm, C4, C4))):
+        raise WinoError("bn1 / bn2 vectors must have Cm values" + (", bn3's C4" if identity else ""))
+    if identity:
+        need = lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm)
+    elif mid == "U2" or int(stride) == 1:   # t1 and t2 both on the output grid
+        need = lib().wino_proj_block_workspace_bytes_hw(N, H, W, Cm)
+    else:
+        need = lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm)
+    workspace = _workspace(workspace, need, x.device)
+    out = _output(out, (N, H, W, C4), x.device)
+    _on_current_device(x, w1, w2, last, out, workspace, *vecs)
+    dims = (N, Hin, Win, Cin, Cm) if identity else (N, Hin, Win, Cin, Cm, C4)
+    if mid == "wg":
+        dims += (groups,)
+    if not identity and mid != "w2_taps":
+        dims += (int(stride),)
+    if entry == "wino_residual_block_hw" and (H, W) == (14, 14):   # the reference's stage has an entry point of its own
+        entry, dims = "wino_residual_block", (N, C4, Cm)
+    _check(getattr(lib(), entry)(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), w2.data_ptr(),
+                                 vecs[2].data_ptr(), vecs[3].data_ptr(), last.data_ptr(),
+                                 *(v.data_ptr() for v in vecs[4:]), out.data_ptr(), *dims, *_ws_args(workspace),
+                                 _stream()), entry)
+    return out
+
+
 def residual_block(x, w1, bn1, U2, bn2, w3, bn3, out=None, workspace=None) -> torch.Tensor:
     """ResNet bottleneck: x [N][H][W][C4] -> same shape (the reference's stage is 14 x 14:
     wino_residual_block; other sizes: wino_residual_block_hw).  bnX = (bias, scale) folded BN
     vectors; w1 [C4][Cm], w3 [Cm][C4]; U2 from filter_transform_f2 (Cm -> Cm)."""
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise WinoError("x must be [N][H][W][C4]")
-    N, H, W, C4 = (int(v) for v in x.shape)
-    w1, w3, U2 = _dev(w1, "w1"), _dev(w3, "w3"), _dev(U2, "U2")
-    Cm = int(w1.shape[1])
-    vecs = _bn_vecs(bn1, bn2, bn3)
-    workspace = _workspace(workspace, lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm), x.device)
-    out = _output(out, x.shape, x.device)
-    _on_current_device(x, w1, w3, U2, out, workspace, *vecs)
-    args = (x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
-            U2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(),
-            w3.data_ptr(), vecs[4].data_ptr(), vecs[5].data_ptr(), out.data_ptr())
-    if (H, W) == (14, 14):
-        _check(lib().wino_residual_block(*args, N, C4, Cm, *_ws_args(workspace), _stream()),
-               "wino_residual_block")
-    else:
-        _check(lib().wino_residual_block_hw(*args, N, H, W, C4, Cm, *_ws_args(workspace), _stream()),
-               "wino_residual_block_hw")
-    return out
+    return _bottleneck("wino_residual_block_hw", x, w1, bn1, "U2", U2, bn2, w3, bn3, out, workspace)
 
 
 FORM_TILED, FORM_STREAM_K, FORM_LATENCY = 0, 1, 2   # WINO_1X1_FORM_*
@@ -417,29 +459,7 @@ def proj_block(x, w1, bn1, U2, bn2, tail, stride: int, out=None, workspace=None)
     """ResNet projection bottleneck (a stage's first block, v1 placement): x [N][Hin][Win][Cin] ->
     [N][H][W][C4], H = (Hin-1)//stride + 1.  bnX = (bias, scale) folded BN vectors; w1 [Cin][Cm]; U2 from
     filter_transform_f2 (Cm -> Cm); tail from proj_tail_pack (w3, bn3, wp, bnp)."""
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise WinoError("x must be [N][Hin][Win][Cin]")
-    N, Hin, Win, Cin = (int(v) for v in x.shape)
-    w1, U2, tail = _dev(w1, "w1"), _dev(U2, "U2"), _dev(tail, "tail")
-    if w1.dim() != 2 or int(w1.shape[0]) != Cin:
-        raise WinoError("w1 must be [Cin][Cm]")
-    Cm = int(w1.shape[1])
-    if tail.numel() % (Cm + Cin + 2):
-        raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
-    C4 = tail.numel() // (Cm + Cin + 2)
-    if int(stride) not in (1, 2):
-        raise WinoError(f"stride must be 1 or 2, got {stride}")
-    H, W = _out_hw(Hin, Win, int(stride))
-    vecs = _bn_vecs(bn1, bn2)
-    workspace = _workspace(workspace, lib().wino_proj_block_workspace_bytes_hw(N, H, W, Cm), x.device)
-    out = _output(out, (N, H, W, C4), x.device)
-    _on_current_device(x, w1, U2, tail, out, workspace, *vecs)
-    _check(lib().wino_proj_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), U2.data_ptr(),
-                                    vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(), out.data_ptr(), N, Hin, Win,
-                                    Cin, Cm, C4, int(stride), *_ws_args(workspace), _stream()),
-           "wino_proj_block_hw")
-    return out
+    return _bottleneck("wino_proj_block_hw", x, w1, bn1, "U2", U2, bn2, tail, None, out, workspace, stride)
 
 
 def filter_pack_s2(w_kcrs: torch.Tensor, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -495,31 +515,7 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
     """ResNet projection bottleneck, v1.5 placement (torchvision's: the stride 2 on the 3x3): x [N][Hin][Win][Cin] ->
     [N][H][W][C4], H = (Hin-1)//2 + 1.  bnX = (bias, scale) folded BN vectors; w1 [Cin][Cm]; w2_taps [3][3][Cm][Cm]
     from filter_pack_s2; tail from proj_tail_pack (w3, bn3, wp, bnp)."""
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise WinoError("x must be [N][Hin][Win][Cin]")
-    N, Hin, Win, Cin = (int(v) for v in x.shape)
-    w1, w2, tail = _dev(w1, "w1"), _dev(w2_taps, "w2_taps"), _dev(tail, "tail")
-    if w1.dim() != 2 or int(w1.shape[0]) != Cin:
-        raise WinoError("w1 must be [Cin][Cm]")
-    Cm = int(w1.shape[1])
-    if w2.dim() != 4 or tuple(w2.shape) != (3, 3, Cm, Cm):
-        raise WinoError(f"w2_taps must be [3][3][{Cm}][{Cm}]: pack it with filter_pack_s2")
-    if tail.numel() % (Cm + Cin + 2):
-        raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
-    C4 = tail.numel() // (Cm + Cin + 2)
-    H, W = _out_hw(Hin, Win, 2)
-    vecs = _bn_vecs(bn1, bn2)
-    if any(v.numel() != Cm for v in vecs):
-        raise WinoError("bn1 / bn2 vectors must have Cm values")
-    workspace = _workspace(workspace, lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm), x.device)
-    out = _output(out, (N, H, W, C4), x.device)
-    _on_current_device(x, w1, w2, tail, out, workspace, *vecs)
-    _check(lib().wino_proj_block_v15_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
-                                        w2.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
-                                        out.data_ptr(), N, Hin, Win, Cin, Cm, C4, *_ws_args(workspace), _stream()),
-           "wino_proj_block_v15_hw")
-    return out
+    return _bottleneck("wino_proj_block_v15_hw", x, w1, bn1, "w2_taps", w2_taps, bn2, tail, None, out, workspace, 2)
 
 
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
@@ -587,27 +583,8 @@ def grouped_residual_block_prepare(N: int, H: int, W: int, C4: int, Cm: int, gro
 def grouped_residual_block(x, w1, bn1, wg, bn2, w3, bn3, groups: int, out=None, workspace=None) -> torch.Tensor:
     """ResNeXt identity bottleneck: residual_block with the grouped 3x3 in the middle.  x [N][H][W][C4] -> same shape;
     w1 [C4][Cm], w3 [Cm][C4]; wg from filter_pack_grouped (Cm channels in `groups` groups); bnX = (bias, scale)."""
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise WinoError("x must be [N][H][W][C4]")
-    N, H, W, C4 = (int(v) for v in x.shape)
-    w1, w3, wg = _dev(w1, "w1"), _dev(w3, "w3"), _dev(wg, "wg")
-    if w1.dim() != 2 or int(w1.shape[0]) != C4 or w3.dim() != 2 or tuple(w3.shape) != (int(w1.shape[1]), C4):
-        raise WinoError("w1 must be [C4][Cm], w3 [Cm][C4]")
-    Cm = int(w1.shape[1])
-    groups = _groups_of(wg, Cm, groups, "wg")
-    vecs = _bn_vecs(bn1, bn2, bn3)
-    if any(v.numel() != c for v, c in zip(vecs, (Cm, Cm, Cm, Cm, C4, C4))):
-        raise WinoError("bn1 / bn2 vectors must have Cm values, bn3's C4")
-    workspace = _workspace(workspace, lib().wino_residual_block_workspace_bytes_hw(N, H, W, Cm), x.device)
-    out = _output(out, x.shape, x.device)
-    _on_current_device(x, w1, w3, wg, out, workspace, *vecs)
-    _check(lib().wino_grouped_residual_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
-                                                wg.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), w3.data_ptr(),
-                                                vecs[4].data_ptr(), vecs[5].data_ptr(), out.data_ptr(), N, H, W, C4, Cm,
-                                                groups, *_ws_args(workspace), _stream()),
-           "wino_grouped_residual_block_hw")
-    return out
+    return _bottleneck("wino_grouped_residual_block_hw", x, w1, bn1, "wg", wg, bn2, w3, bn3, out, workspace,
+                       groups=groups)
 
 
 def grouped_proj_block_workspace_bytes(N: int, Hin: int, Win: int, Cm: int, stride: int) -> int:
@@ -626,32 +603,8 @@ def grouped_proj_block(x, w1, bn1, wg, bn2, tail, groups: int, stride: int, out=
     """ResNeXt projection bottleneck (a stage's first block, torchvision's placement): x [N][Hin][Win][Cin] ->
     [N][H][W][C4], H = (Hin-1)//stride + 1.  The first 1x1 runs at Hin x Win, the grouped 3x3 at `stride`; w1 [Cin][Cm];
     wg from filter_pack_grouped; tail from proj_tail_pack (w3, bn3, wp, bnp); bnX = (bias, scale)."""
-    x = _dev(x, "x")
-    if x.dim() != 4:
-        raise WinoError("x must be [N][Hin][Win][Cin]")
-    N, Hin, Win, Cin = (int(v) for v in x.shape)
-    w1, wg, tail = _dev(w1, "w1"), _dev(wg, "wg"), _dev(tail, "tail")
-    if w1.dim() != 2 or int(w1.shape[0]) != Cin:
-        raise WinoError("w1 must be [Cin][Cm]")
-    Cm = int(w1.shape[1])
-    groups = _groups_of(wg, Cm, groups, "wg")
-    if tail.numel() % (Cm + Cin + 2):
-        raise WinoError("tail does not match Cm / Cin: pack it with proj_tail_pack")
-    C4 = tail.numel() // (Cm + Cin + 2)
-    if int(stride) not in (1, 2):
-        raise WinoError(f"stride must be 1 or 2, got {stride}")
-    H, W = _out_hw(Hin, Win, int(stride))
-    vecs = _bn_vecs(bn1, bn2)
-    if any(v.numel() != Cm for v in vecs):
-        raise WinoError("bn1 / bn2 vectors must have Cm values")
-    workspace = _workspace(workspace, grouped_proj_block_workspace_bytes(N, Hin, Win, Cm, stride), x.device)
-    out = _output(out, (N, H, W, C4), x.device)
-    _on_current_device(x, w1, wg, tail, out, workspace, *vecs)
-    _check(lib().wino_grouped_proj_block_hw(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(),
-                                            wg.data_ptr(), vecs[2].data_ptr(), vecs[3].data_ptr(), tail.data_ptr(),
-                                            out.data_ptr(), N, Hin, Win, Cin, Cm, C4, groups, int(stride),
-                                            *_ws_args(workspace), _stream()), "wino_grouped_proj_block_hw")
-    return out
+    return _bottleneck("wino_grouped_proj_block_hw", x, w1, bn1, "wg", wg, bn2, tail, None, out, workspace, stride,
+                       groups)
 
 
 def conv3x3_bn_add_relu(inp: torch.Tensor, U: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,

@@ -310,11 +310,9 @@ static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const
   return launch_1x1<A_PLAIN>(p, dev, {A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg}, (hipStream_t)s);
 }
 
-// The bottleneck block's shape checks before its first launch: batch and feature map, both 1x1 layers (C4 -> Cm
-// writing padded t1, Cm -> C4 reading padded t2) and the 3x3's limits (its filter matrix among them), so that a shape
-// any of its layers refuses launches nothing
+// The identity bottleneck's batch, feature map and two 1x1 layers (C4 -> Cm writing padded t1, Cm -> C4 reading padded
+// t2), for bottleneck.hip's shape check (declared in proj_block.h)
 namespace wino {
-// the block's batch, feature map and two 1x1 layers (shared with the grouped bottleneck, grouped_block.hip: proj_block.h)
 int check_bottleneck_1x1s(int N, int H, int W, int C4, int Cm) {
   if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
   const long M = (long)N * H * W;
@@ -324,10 +322,6 @@ int check_bottleneck_1x1s(int N, int H, int W, int C4, int Cm) {
   return check_1x1_padded(M, H, W, C4);
 }
 }  // namespace wino
-static int check_residual_block(int N, int H, int W, int C4, int Cm) {
-  if (int rc = check_bottleneck_1x1s(N, H, W, C4, Cm)) return rc;
-  return check_conv3x3_dims(H, W, Cm, Cm);
-}
 
 extern "C" {
 
@@ -404,64 +398,6 @@ int wino_conv1x1_prepare(long M, int Cin, int Kout, wino_stream_t s) {
 int wino_conv1x1_bn(const float* A, const float* B, const float* bnBias, const float* bnScale,
                     float* C, long M, int Cin, int Kout, int relu, wino_stream_t s) {
   return wino_conv1x1_bn_ex(A, B, bnBias, bnScale, NULL, C, M, Cin, Kout, relu ? WINO_RELU : 0, s);
-}
-
-// 1x1 (C4 -> Cm) + BN + ReLU  ->  3x3 (Cm -> Cm) + BN + ReLU  ->  1x1 (Cm -> C4) + BN + skip + ReLU.
-// Three launches on one stream; the two intermediates live in `workspace` in the padded
-// [N][16][16][Cm] layout the 3x3 kernel reads and writes, so no repacking pass exists.
-int wino_residual_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
-                           const float* U2, const float* bn2Bias, const float* bn2Scale,
-                           const float* w3, const float* bn3Bias, const float* bn3Scale, float* out,
-                           int N, int H, int W, int C4, int Cm, void* workspace, size_t workspace_bytes,
-                           wino_stream_t s) {
-  if (int rc = check_nonnull(x, w1, bn1Bias, bn1Scale, U2, bn2Bias, bn2Scale, w3, bn3Bias, bn3Scale, out)) return rc;
-  if (int rc = check_aligned16(x, w1, U2, w3, out, workspace)) return rc;
-  if (int rc = check_residual_block(N, H, W, C4, Cm)) return rc;
-  const size_t need = wino_residual_block_workspace_bytes_hw(N, H, W, Cm);
-  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
-  // x is read again as the residual by the third launch, after the first two have written the workspace
-  const size_t act_b = (size_t)N * H * W * C4 * sizeof(float);
-  if (overlaps(workspace, need, x, act_b) || overlaps(workspace, need, out, act_b)) {
-    set_error("the workspace overlaps x or out");
-    return WINO_E_ARG;
-  }
-  float* t1 = (float*)workspace;
-  float* t2 = (float*)((char*)workspace + padded_bytes(N, H, W, Cm));
-  int rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, H, W, C4, Cm, WINO_RELU | WINO_C_PADDED, s);
-  if (rc) return rc;
-  rc = wino_conv3x3_bn_relu_hw(t1, U2, bn2Bias, bn2Scale, t2, N, H, W, Cm, Cm, 1, s);
-  if (rc) return rc;
-  return wino_conv1x1_bn_ex_hw(t2, w3, bn3Bias, bn3Scale, x, out, N, H, W, Cm, C4,
-                               WINO_RELU | WINO_A_PADDED | WINO_ADD_RESIDUAL, s);
-}
-
-int wino_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, wino_stream_t s) {
-  if (int rc = check_residual_block(N, H, W, C4, Cm)) return rc;
-  const long M = (long)N * H * W;
-  if (int rc = wino_conv1x1_prepare(M, C4, Cm, s)) return rc;
-  if (int rc = wino_conv3x3_prepare_hw(N, H, W, Cm, Cm, s)) return rc;
-  return wino_conv1x1_prepare(M, Cm, C4, s);
-}
-
-int wino_residual_block_prepare(int N, int C4, int Cm, wino_stream_t s) {
-  return wino_residual_block_prepare_hw(N, WINO_PQ, WINO_PQ, C4, Cm, s);
-}
-
-size_t wino_residual_block_workspace_bytes_hw(int N, int H, int W, int Cm) {
-  return 2 * padded_bytes(N, H, W, Cm);
-}
-
-int wino_residual_block(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
-                        const float* U2, const float* bn2Bias, const float* bn2Scale,
-                        const float* w3, const float* bn3Bias, const float* bn3Scale, float* out,
-                        int N, int C4, int Cm, void* workspace, size_t workspace_bytes,
-                        wino_stream_t s) {
-  return wino_residual_block_hw(x, w1, bn1Bias, bn1Scale, U2, bn2Bias, bn2Scale, w3, bn3Bias, bn3Scale, out,
-                                N, WINO_PQ, WINO_PQ, C4, Cm, workspace, workspace_bytes, s);
-}
-
-size_t wino_residual_block_workspace_bytes(int N, int Cm) {
-  return wino_residual_block_workspace_bytes_hw(N, WINO_PQ, WINO_PQ, Cm);
 }
 
 int wino_conv1x1_direct(const float* A, const float* B, const float* bnBias,

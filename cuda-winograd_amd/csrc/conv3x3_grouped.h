@@ -1,5 +1,5 @@
-// The grouped 3x3 layer's geometry check (defined in conv3x3_grouped.hip), shared with grouped_block.hip, which runs
-// it for both blocks before their first launch.
+// The grouped 3x3 layer's geometry check (defined in conv3x3_grouped.hip), shared with bottleneck.hip, which runs
+// it for both grouped blocks before their first launch.
 #pragma once
 #include "wino_common.h"
 

@@ -1,6 +1,6 @@
 // The stride-2 3x3 layer's geometry check and launch plan (defined in conv3x3_s2.hip), shared by the translation units
 // that launch the tap forms: conv3x3_s2.hip (A_TAPS) and basic_block_s2.hip (A_TAPS_PROJ, the layer with the
-// downsampling basic block's shortcut), which takes exactly the plain layer's plan.  proj_block.hip runs check_s2 for
+// downsampling basic block's shortcut), which takes exactly the plain layer's plan.  bottleneck.hip runs check_s2 for
 // the v1.5 block's stride-2 3x3 before its first launch.
 #pragma once
 #include "conv1x1_launch.h"

@@ -7,7 +7,7 @@
 // operand form A_TAPS (conv1x1_kernel.h): the same LDS-DMA pipeline and MFMA loop with one scalar A offset per k-step,
 // the same latency / tiled / stream-K forms, the same planner (plan_1x1 on the GEMM's shape, its latency-or-tiled
 // choice re-priced for the tap form: plan_s2) and launcher (launch_1x1, conv1x1_launch.h).  This file instantiates that form and no other.
-// check_s2 and plan_s2 are shared with basic_block_s2.hip, check_s2 also with proj_block.hip (conv3x3_s2.h).
+// check_s2 and plan_s2 are shared with basic_block_s2.hip, check_s2 also with bottleneck.hip (conv3x3_s2.h).
 #include "conv3x3_s2.h"
 
 namespace wino {

@@ -1,21 +1,18 @@
-// The projection (downsampling) bottleneck block: the first block of every ResNet stage, ResNet v1 placement (the
-// stride sits on the first 1x1 and on the projection, the 3x3 runs at stride 1 on the output grid):
+// The projection (downsampling) bottleneck's own pieces: the geometry check, the packed fused tail, and the two 1x1
+// launches in the operand forms only this block uses.  ResNet v1 placement (the stride on the first 1x1 and on the
+// projection, the 3x3 at stride 1 on the output grid):
 //   xs  = x[:, ::s, ::s, :]                                   (never materialised)
 //   t1  = relu(bn1(xs . w1))              padded [N][H+2][W+2][Cm]   (workspace)
 //   t2  = relu(bn2(conv3x3(t1, U2)))      padded [N][H+2][W+2][Cm]   (workspace)
 //   out = relu(bn3(t2 . w3) + bnp(xs . wp))     [N][H][W][C4]
-// Three launches: the strided 1x1 (s = 1: the plain 1x1 entry point), the Winograd 3x3, and the FUSED TAIL -- one
-// GEMM of K = Cm + Cin whose k-steps read t2 first and the strided x after it (conv1x1_kernel.h, A_TWO), against
-// the stacked, scale-folded [bn3Scale . w3 ; bnpScale . wp] with the summed bias: the shortcut is accumulated in
-// the same registers as the last 1x1 and never reaches memory.  The kernels are the 1x1 kernel templates with the
-// operand form as a template argument (AF = A_STRIDED / A_TWO), launched by the same launch_1x1 as conv1x1.hip's
-// (conv1x1_launch.h).  This file's calls instantiate those forms here; conv1x1.hip instantiates only A_PLAIN.
-//
-// The v1.5 placement (torchvision's ResNet-50: the stride on the 3x3) is host code over the same kernels:
-//   t1  = relu(bn1(x . w1))                      padded [N][Hin+2][Win+2][Cm]   (workspace; the plain 1x1 entry point)
-//   t2  = relu(bn2(conv3x3_s2(t1, w2_taps)))     padded [N][H+2][W+2][Cm]       (workspace; conv3x3_s2.hip)
-//   out = the same fused tail as v1 at stride 2
-// so this file instantiates no kernel for it.
+// The strided first 1x1 (A_STRIDED; s = 1 is the plain 1x1 entry point) and the FUSED TAIL -- one GEMM of K = Cm + Cin
+// whose k-steps read t2 first and the strided x after it (conv1x1_kernel.h, A_TWO), against the stacked, scale-folded
+// [bn3Scale . w3 ; bnpScale . wp] with the summed bias: the shortcut is accumulated in the same registers as the last
+// 1x1 and never reaches memory.  The kernels are the 1x1 kernel templates with the operand form as a template
+// argument, launched by the same launch_1x1 as conv1x1.hip's (conv1x1_launch.h).  This file's calls instantiate those
+// forms here; conv1x1.hip instantiates only A_PLAIN.
+// The blocks themselves -- this one, the v1.5 and the grouped placements, which end in the same tail -- are composed in
+// bottleneck.hip.
 #include "proj_block.h"
 
 namespace wino {
@@ -77,21 +74,9 @@ int check_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, Pro
   *g = ProjGeom{N, Hin, Win, Cin, Cm, C4, stride, H, W, (long)M};
   return WINO_OK;
 }
-// the workspace holds t1 and t2, written before the tail reads x (its shortcut) and writes out: it must overlap neither
-int check_ws_overlap(const ProjGeom& g, const void* x, const void* out, const void* workspace, size_t need) {
-  const size_t x_b = (size_t)g.N * g.Hin * g.Win * g.Cin * sizeof(float), out_b = (size_t)g.M * g.C4 * sizeof(float);
-  if (overlaps(workspace, need, x, x_b) || overlaps(workspace, need, out, out_b)) {
-    set_error("the workspace overlaps x or out");
-    return WINO_E_ARG;
-  }
-  return WINO_OK;
-}
 
 namespace {
 
-// the v1 block's middle layer is the Winograd 3x3 (Cm -> Cm at H x W): its shape limits, the filter matrix's among
-// them, before anything is launched
-static int check_proj_3x3(const ProjGeom& g) { return check_conv3x3_dims(g.H, g.W, g.Cm, g.Cm); }
 static ProjGeo proj_geo(const ProjGeom& g, const float* x) {
   return ProjGeo{x, (unsigned)g.Hin * (unsigned)g.Win, (unsigned)(g.s * g.Win), (unsigned)g.s, g.Cin, g.Cm};
 }
@@ -116,17 +101,32 @@ int check_first_1x1_full(int N, int Hin, int Win, int Cm) {
   return WINO_OK;
 }
 
+// the strided first 1x1 (A_STRIDED): t1 = relu(bn1(xs . w1)), padded [N][H+2][W+2][Cm]; the plain layer's plan at M = N*H*W
+int launch_first_strided(const ProjGeom& g, const float* x, const float* w1, const float* bnBias, const float* bnScale,
+                         float* t1, hipStream_t s) {
+  int dev = 0, cus = 0;
+  if (int rc = current_device(&dev, &cus)) return rc;
+  return launch_1x1<A_STRIDED>(plan_first(g, cus, knobs()), dev,
+                               {x, w1, bnBias, bnScale, nullptr, t1, g.M, g.Cin, g.Cm, WINO_RELU | WINO_C_PADDED,
+                                make_padgeo(g.H, g.W), proj_geo(g, x)},
+                               s);
+}
+
 // the fused tail (A_TWO): out = relu(t2 . [bn3Scale w3] + xs . [bnpScale wp] + bias), t2 padded [N][H+2][W+2][Cm]
-int launch_proj_tail(const ProjGeom& g, const float* t2, const float* tail_packed, const float* x, float* out, int dev,
-                     int cus, const Knobs& kn, hipStream_t s) {
+int launch_proj_tail(const ProjGeom& g, const float* t2, const float* tail_packed, const float* x, float* out,
+                     hipStream_t s) {
+  int dev = 0, cus = 0;
+  if (int rc = current_device(&dev, &cus)) return rc;
   const float* bias = tail_packed + (size_t)(g.Cm + g.Cin) * g.C4;
-  return launch_1x1<A_TWO>(plan_tail(g, cus, kn), dev,
+  return launch_1x1<A_TWO>(plan_tail(g, cus, knobs()), dev,
                            {t2, tail_packed, bias, bias + g.C4, nullptr, out, g.M, g.Cm + g.Cin, g.C4,
                             WINO_RELU | WINO_A_PADDED, make_padgeo(g.H, g.W), proj_geo(g, x)},
                            s);
 }
 
-int prepare_proj_tail(const ProjGeom& g, int dev, int cus, hipStream_t s) {
+int prepare_proj_tail(const ProjGeom& g, hipStream_t s) {
+  int dev = 0, cus = 0;
+  if (int rc = current_device(&dev, &cus)) return rc;
   const Plan1x1 pt = plan_tail(g, cus, knobs());
   SkBufs bufs;
   return pt.sk ? tiled_scratch(dev, s, pt, &bufs) : WINO_OK;
@@ -159,11 +159,6 @@ int wino_proj_tail_pack(const float* w3, const float* bn3Bias, const float* bn3S
   return launch_status("proj_tail_pack_kernel");
 }
 
-size_t wino_proj_block_workspace_bytes_hw(int N, int H, int W, int Cm) {
-  if (N < 1 || H < 1 || W < 1 || Cm < 1) return 0;
-  return 2 * padded_bytes(N, H, W, Cm);
-}
-
 int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, int cus, int* first_form,
                         int* tail_form) {
   if (!first_form || !tail_form || cus < 1) { set_error("bad argument"); return WINO_E_ARG; }
@@ -173,101 +168,6 @@ int wino_proj_tail_plan(int N, int Hin, int Win, int Cin, int Cm, int C4, int st
   *first_form = form_of(plan_first(g, cus, kn));   // (stride 1 runs the plain 1x1 entry point: the same plan)
   *tail_form = form_of(plan_tail(g, cus, kn));
   return WINO_OK;
-}
-
-int wino_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int stride, wino_stream_t s) {
-  ProjGeom g;
-  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
-  if (int rc = check_proj_3x3(g)) return rc;
-  int dev = 0, cus = 0;
-  if (int rc = current_device(&dev, &cus)) return rc;
-  const Knobs kn = knobs();
-  SkBufs bufs;
-  const Plan1x1 p1 = plan_first(g, cus, kn), pt = plan_tail(g, cus, kn);
-  if (p1.sk)
-    if (int rc = tiled_scratch(dev, (hipStream_t)s, p1, &bufs)) return rc;
-  if (int rc = wino_conv3x3_prepare_hw(N, g.H, g.W, Cm, Cm, s)) return rc;
-  if (pt.sk)
-    if (int rc = tiled_scratch(dev, (hipStream_t)s, pt, &bufs)) return rc;
-  return WINO_OK;
-}
-
-// The v1.5 block's shape check, before anything is launched: the v1 block's at stride 2 (the tail and the strided
-// shortcut are the same), the first 1x1 at full input resolution, and the stride-2 3x3's own limits.
-static int check_v15(int N, int Hin, int Win, int Cin, int Cm, int C4, ProjGeom* g) {
-  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, 2, g)) return rc;
-  if (int rc = check_first_1x1_full(N, Hin, Win, Cm)) return rc;
-  S2Geom g2;
-  return check_s2(N, Hin, Win, Cm, Cm, &g2);
-}
-
-int wino_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale, const float* U2,
-                       const float* bn2Bias, const float* bn2Scale, const float* tail_packed, float* out, int N, int Hin,
-                       int Win, int Cin, int Cm, int C4, int stride, void* workspace, size_t workspace_bytes,
-                       wino_stream_t s) {
-  if (int rc = check_nonnull(x, w1, bn1Bias, bn1Scale, U2, bn2Bias, bn2Scale, tail_packed, out)) return rc;
-  if (int rc = check_aligned16(x, w1, U2, tail_packed, out, workspace)) return rc;
-  ProjGeom g;
-  if (int rc = check_proj(N, Hin, Win, Cin, Cm, C4, stride, &g)) return rc;
-  if (int rc = check_proj_3x3(g)) return rc;
-  const size_t need = wino_proj_block_workspace_bytes_hw(N, g.H, g.W, Cm);
-  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
-  if (int rc = check_ws_overlap(g, x, out, workspace, need)) return rc;
-  int dev = 0, cus = 0;
-  if (int rc = current_device(&dev, &cus)) return rc;
-  const Knobs kn = knobs();
-  float* t1 = (float*)workspace;
-  float* t2 = (float*)((char*)workspace + padded_bytes(N, g.H, g.W, Cm));
-  const PadGeo pg = make_padgeo(g.H, g.W);
-  const ProjGeo xg = proj_geo(g, x);
-  const hipStream_t hs = (hipStream_t)s;
-  int rc;
-  if (stride == 1)   // xs = x: the plain 1x1 layer, exactly as the identity block's first launch
-    rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, g.H, g.W, Cin, Cm, WINO_RELU | WINO_C_PADDED, s);
-  else
-    rc = launch_1x1<A_STRIDED>(plan_first(g, cus, kn), dev,
-                               {x, w1, bn1Bias, bn1Scale, nullptr, t1, g.M, Cin, Cm, WINO_RELU | WINO_C_PADDED, pg, xg}, hs);
-  if (rc) return rc;
-  rc = wino_conv3x3_bn_relu_hw(t1, U2, bn2Bias, bn2Scale, t2, N, g.H, g.W, Cm, Cm, 1, s);
-  if (rc) return rc;
-  return launch_proj_tail(g, t2, tail_packed, x, out, dev, cus, kn, hs);
-}
-
-size_t wino_proj_block_v15_workspace_bytes_hw(int N, int Hin, int Win, int Cm) {
-  if (N < 1 || Hin < 1 || Win < 1 || Cm < 1) return 0;
-  return padded_bytes(N, Hin, Win, Cm) + padded_bytes(N, (Hin - 1) / 2 + 1, (Win - 1) / 2 + 1, Cm);
-}
-
-int wino_proj_block_v15_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, wino_stream_t s) {
-  ProjGeom g;
-  if (int rc = check_v15(N, Hin, Win, Cin, Cm, C4, &g)) return rc;
-  int dev = 0, cus = 0;
-  if (int rc = current_device(&dev, &cus)) return rc;
-  if (int rc = wino_conv1x1_prepare((long)N * Hin * Win, Cin, Cm, s)) return rc;
-  if (int rc = wino_conv3x3_s2_prepare_hw(N, Hin, Win, Cm, Cm, s)) return rc;
-  return prepare_proj_tail(g, dev, cus, (hipStream_t)s);
-}
-
-int wino_proj_block_v15_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
-                           const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* tail_packed,
-                           float* out, int N, int Hin, int Win, int Cin, int Cm, int C4, void* workspace,
-                           size_t workspace_bytes, wino_stream_t s) {
-  if (int rc = check_nonnull(x, w1, bn1Bias, bn1Scale, w2_taps, bn2Bias, bn2Scale, tail_packed, out)) return rc;
-  if (int rc = check_aligned16(x, w1, w2_taps, tail_packed, out, workspace)) return rc;
-  ProjGeom g;
-  if (int rc = check_v15(N, Hin, Win, Cin, Cm, C4, &g)) return rc;
-  const size_t need = wino_proj_block_v15_workspace_bytes_hw(N, Hin, Win, Cm);
-  if (int rc = check_workspace(workspace, workspace_bytes, need)) return rc;
-  if (int rc = check_ws_overlap(g, x, out, workspace, need)) return rc;
-  int dev = 0, cus = 0;
-  if (int rc = current_device(&dev, &cus)) return rc;
-  float* t1 = (float*)workspace;
-  float* t2 = (float*)((char*)workspace + padded_bytes(N, Hin, Win, Cm));
-  int rc = wino_conv1x1_bn_ex_hw(x, w1, bn1Bias, bn1Scale, NULL, t1, N, Hin, Win, Cin, Cm, WINO_RELU | WINO_C_PADDED, s);
-  if (rc) return rc;
-  rc = wino_conv3x3_s2_bn_relu_hw(t1, w2_taps, bn2Bias, bn2Scale, t2, N, Hin, Win, Cm, Cm, 1, s);
-  if (rc) return rc;
-  return launch_proj_tail(g, t2, tail_packed, x, out, dev, cus, knobs(), (hipStream_t)s);
 }
 
 }  // extern "C"

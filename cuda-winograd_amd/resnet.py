@@ -19,6 +19,9 @@ launch's stream scratch, so that a whole forward can then be captured in one ``t
 """
 from __future__ import annotations
 
+from collections import namedtuple
+from types import SimpleNamespace
+
 import torch
 
 from . import (WinoError, _out_hw, avgpool_fc, basic_block, basic_block_prepare, basic_block_s2,
@@ -58,6 +61,99 @@ def mid_channels(arch: str, planes: int):
     Bottleneck), in `groups` groups."""
     groups, wpg = WIDTHS.get(arch, (1, 64))
     return groups, planes * wpg // 64 * groups
+
+
+# ---------------------------------------------------------------------------------------------------- the block table
+# One row per block kind: everything the model does with a block.  `ld` loads from the state dict (w: a tensor on the
+# device, w1x1: torch's [K][C][1][1] as the library's [C][K], bn: a folded BN); `s` is the block at one input size.
+_Shape = namedtuple("_Shape", "N h w ho wo cin cm cout groups")   # h x w: the block's input map, ho x wo: its output
+_Kind = namedtuple("_Kind", "stride pack workspace prepare run macs")
+# stride:    of the block (a field, so that nothing reads it off a name)
+# pack:      (ld, "layerL.b", groups) -> the block's packed parameters
+# workspace: (s) -> bytes;  prepare: (s) -> None, reserves the launches' stream scratch
+# run:       (x, params, groups, out, workspace) -> the output tensor
+# macs:      (px, cin, cm, cout, groups) -> multiply-adds per image at px output pixels
+
+
+def _bottleneck_kind(stride, mid_pack, workspace, prepare, run, proj):
+    """A bottleneck row: 1x1, the 3x3 packed by mid_pack, then w3 with bn3 (identity) or the packed projection tail."""
+    def pack(ld, p, groups):
+        w1, bn1, bn2, bn3 = ld.w1x1(f"{p}.conv1.weight"), ld.bn(f"{p}.bn1"), ld.bn(f"{p}.bn2"), ld.bn(f"{p}.bn3")
+        w2, w3 = mid_pack(ld.w(f"{p}.conv2.weight"), groups), ld.w1x1(f"{p}.conv3.weight")
+        if not proj:
+            return w1, bn1, w2, bn2, w3, bn3
+        wp, bnp = ld.w1x1(f"{p}.downsample.0.weight"), ld.bn(f"{p}.downsample.1")
+        return w1, bn1, w2, bn2, proj_tail_pack(w3, bn3, wp, bnp)
+
+    def macs(px, cin, cm, cout, groups):   # torchvision's placement: the first 1x1 runs before the stride
+        return px * (stride * stride * cin * cm + 9 * cm * (cm // groups) + cm * cout + (cin * cout if proj else 0))
+
+    return _Kind(stride, pack, workspace, prepare, run, macs)
+
+
+def _pack_basic(ld, p, groups):
+    return (filter_transform_f2(ld.w(f"{p}.conv1.weight")), ld.bn(f"{p}.bn1"),
+            filter_transform_f2(ld.w(f"{p}.conv2.weight")), ld.bn(f"{p}.bn2"))
+
+
+def _pack_basic_s2(ld, p, groups):
+    packed = s2_proj_pack(filter_pack_s2(ld.w(f"{p}.conv1.weight")), ld.bn(f"{p}.bn1"),
+                          ld.w1x1(f"{p}.downsample.0.weight"), ld.bn(f"{p}.downsample.1"))
+    return packed, filter_transform_f2(ld.w(f"{p}.conv2.weight")), ld.bn(f"{p}.bn2")
+
+
+def _grouped_proj_kind(stride):
+    return _bottleneck_kind(
+        stride, filter_pack_grouped, lambda s: grouped_proj_block_workspace_bytes(s.N, s.h, s.w, s.cm, stride),
+        lambda s: grouped_proj_block_prepare(s.N, s.h, s.w, s.cin, s.cm, s.cout, s.groups, stride),
+        lambda x, p, g, out, ws: grouped_proj_block(x, *p, g, stride, out=out, workspace=ws), proj=True)
+
+
+def _residual_workspace(s):
+    return lib().wino_residual_block_workspace_bytes_hw(s.N, s.ho, s.wo, s.cm)
+
+
+_dense = lambda w, groups: filter_transform_f2(w)
+KINDS = {
+    # ResNet-18 / -34: in place on the stage's tensor after its first block
+    "basic": _Kind(1, _pack_basic, lambda s: lib().wino_basic_block_workspace_bytes_hw(s.N, s.ho, s.wo, s.cout),
+                   lambda s: basic_block_prepare(s.N, s.ho, s.wo, s.cout),
+                   lambda x, p, g, out, ws: basic_block(x, *p, out=out, workspace=ws),
+                   lambda px, cin, cm, cout, groups: px * 9 * (cin * cout + cout * cout)),
+    "basic_s2": _Kind(2, _pack_basic_s2, lambda s: lib().wino_basic_block_s2_workspace_bytes_hw(s.N, s.h, s.w, s.cout),
+                      lambda s: basic_block_s2_prepare(s.N, s.h, s.w, s.cin, s.cout),
+                      lambda x, p, g, out, ws: basic_block_s2(x, *p, out=out, workspace=ws),
+                      lambda px, cin, cm, cout, groups: px * (9 * (cin * cout + cout * cout) + cin * cout)),
+    # the bottleneck nets; at stride 1 the v1 and v1.5 placements are the same block
+    "residual": _bottleneck_kind(1, _dense, _residual_workspace,
+                                 lambda s: residual_block_prepare(s.N, s.cout, s.cm, s.ho, s.wo),
+                                 lambda x, p, g, out, ws: residual_block(x, *p, out=out, workspace=ws), proj=False),
+    "proj": _bottleneck_kind(1, _dense, lambda s: lib().wino_proj_block_workspace_bytes_hw(s.N, s.ho, s.wo, s.cm),
+                             lambda s: proj_block_prepare(s.N, s.h, s.w, s.cin, s.cm, s.cout, 1),
+                             lambda x, p, g, out, ws: proj_block(x, *p, 1, out=out, workspace=ws), proj=True),
+    "proj_v15": _bottleneck_kind(2, lambda w, groups: filter_pack_s2(w),
+                                 lambda s: lib().wino_proj_block_v15_workspace_bytes_hw(s.N, s.h, s.w, s.cm),
+                                 lambda s: proj_block_v15_prepare(s.N, s.h, s.w, s.cin, s.cm, s.cout),
+                                 lambda x, p, g, out, ws: proj_block_v15(x, *p, out=out, workspace=ws), proj=True),
+    # the ResNeXts: the grouped 3x3 in every block, the stride on it
+    "grouped_residual": _bottleneck_kind(
+        1, filter_pack_grouped, _residual_workspace,
+        lambda s: grouped_residual_block_prepare(s.N, s.ho, s.wo, s.cout, s.cm, s.groups),
+        lambda x, p, g, out, ws: grouped_residual_block(x, *p, g, out=out, workspace=ws), proj=False),
+    "grouped_proj": _grouped_proj_kind(1),
+    "grouped_proj_s2": _grouped_proj_kind(2),
+}
+
+
+def block_kind(bottleneck: bool, grouped: bool, stage: int, first: bool) -> str:
+    """The KINDS row of a block: `first` of its stage (1..4) or not; conv2 opens at stride 1, conv3..conv5 at 2."""
+    if not bottleneck:
+        return "basic_s2" if first and stage > 1 else "basic"
+    if not first:
+        return "grouped_residual" if grouped else "residual"
+    if grouped:
+        return "grouped_proj" if stage == 1 else "grouped_proj_s2"
+    return "proj" if stage == 1 else "proj_v15"
 
 
 def stage_shapes(arch: str, H: int, W: int):
@@ -144,58 +240,22 @@ class ResNet(Net):
             w = sd[key]
             return self._t(w.reshape(w.shape[0], w.shape[1]).t())
 
-        self.stem_packed = stem_filter_pack(self._t(sd["conv1.weight"]), self._fold_bn(sd, "bn1", eps))
-        self.layers = []
+        ld = SimpleNamespace(w=lambda key: self._t(sd[key]), w1x1=w1x1,
+                             bn=lambda prefix: self._fold_bn(sd, prefix, eps))
+        self.stem_packed = stem_filter_pack(ld.w("conv1.weight"), ld.bn("bn1"))
+        self.layers = []   # per stage: (kind, cin, cm, cout, packed parameters) of its blocks, kind a KINDS row
         cin = 64
         for L, (planes, nb) in enumerate(zip(PLANES, self.blocks), 1):
+            cout = planes * 4 if self.bottleneck else planes
+            cm = mid_channels(self.arch, planes)[1] if self.bottleneck else planes
             blocks = []
             for b in range(nb):
-                p = f"layer{L}.{b}"
-                first = b == 0
-                bn1, bn2 = self._fold_bn(sd, f"{p}.bn1", eps), self._fold_bn(sd, f"{p}.bn2", eps)
-                if self.bottleneck:
-                    cout = planes * 4
-                    cm = mid_channels(self.arch, planes)[1]
-                    w1, bn3 = w1x1(f"{p}.conv1.weight"), self._fold_bn(sd, f"{p}.bn3", eps)
-                    grouped = self.groups > 1   # ResNeXt: the grouped 3x3 in every block
-                    if first:
-                        tail = proj_tail_pack(w1x1(f"{p}.conv3.weight"), bn3, w1x1(f"{p}.downsample.0.weight"),
-                                              self._fold_bn(sd, f"{p}.downsample.1", eps))
-                        if grouped:
-                            w2 = filter_pack_grouped(self._t(sd[f"{p}.conv2.weight"]), self.groups)
-                            # stride 1 in conv2, 2 (on the 3x3) in conv3..conv5
-                            blocks.append(("grouped_proj" if L == 1 else "grouped_proj_s2", cin, cm, cout,
-                                           (w1, bn1, w2, bn2, tail)))
-                        elif L == 1:   # stride 1: the v1 and v1.5 placements are the same block
-                            w2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
-                            blocks.append(("proj", cin, cm, cout, (w1, bn1, w2, bn2, tail)))
-                        else:
-                            w2 = filter_pack_s2(self._t(sd[f"{p}.conv2.weight"]))
-                            blocks.append(("proj_v15", cin, cm, cout, (w1, bn1, w2, bn2, tail)))
-                    elif grouped:
-                        wg = filter_pack_grouped(self._t(sd[f"{p}.conv2.weight"]), self.groups)
-                        blocks.append(("grouped_residual", cin, cm, cout,
-                                       (w1, bn1, wg, bn2, w1x1(f"{p}.conv3.weight"), bn3)))
-                    else:
-                        U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
-                        blocks.append(("residual", cin, cm, cout,
-                                       (w1, bn1, U2, bn2, w1x1(f"{p}.conv3.weight"), bn3)))
-                else:
-                    cout = planes
-                    if first and L > 1:
-                        packed = s2_proj_pack(filter_pack_s2(self._t(sd[f"{p}.conv1.weight"])), bn1,
-                                              w1x1(f"{p}.downsample.0.weight"),
-                                              self._fold_bn(sd, f"{p}.downsample.1", eps))
-                        U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
-                        blocks.append(("basic_s2", cin, planes, cout, (packed, U2, bn2)))
-                    else:
-                        U1 = filter_transform_f2(self._t(sd[f"{p}.conv1.weight"]))
-                        U2 = filter_transform_f2(self._t(sd[f"{p}.conv2.weight"]))
-                        blocks.append(("basic", cin, planes, cout, (U1, bn1, U2, bn2)))
+                kind = block_kind(self.bottleneck, self.groups > 1, L, b == 0)
+                blocks.append((kind, cin, cm, cout, KINDS[kind].pack(ld, f"layer{L}.{b}", self.groups)))
                 cin = cout
             self.layers.append(blocks)
         self.feat_c = cin
-        self.head_packed = head_pack(self._t(sd["fc.weight"]), self._t(sd["fc.bias"]))
+        self.head_packed = head_pack(ld.w("fc.weight"), ld.w("fc.bias"))
         torch.cuda.current_stream().synchronize()
 
     # ------------------------------------------------------------------ per input shape
@@ -208,7 +268,6 @@ class ResNet(Net):
         dev, f32 = self.device, torch.float32
         shapes = stage_shapes(self.arch, H, W)
         pad = 0 if self.bottleneck else 2
-        L = lib()
         with torch.cuda.device(dev):
             _, c0, h0, w0 = shapes[0]
             self._stem_out = torch.zeros((N, h0 + pad, w0 + pad, c0), dtype=f32, device=dev)
@@ -220,30 +279,11 @@ class ResNet(Net):
                         for _ in range(2 if self.bottleneck else 1)]
                 self._stages.append(bufs)
                 for kind, cin, cm, cout, _ in blocks:
-                    if kind == "basic":
-                        ws = max(ws, L.wino_basic_block_workspace_bytes_hw(N, ho, wo, cout))
-                        basic_block_prepare(N, ho, wo, cout)
-                    elif kind == "basic_s2":
-                        ws = max(ws, L.wino_basic_block_s2_workspace_bytes_hw(N, h, w, cout))
-                        basic_block_s2_prepare(N, h, w, cin, cout)
-                    elif kind == "proj":
-                        ws = max(ws, L.wino_proj_block_workspace_bytes_hw(N, ho, wo, cm))
-                        proj_block_prepare(N, h, w, cin, cm, cout, 1)
-                    elif kind == "proj_v15":
-                        ws = max(ws, L.wino_proj_block_v15_workspace_bytes_hw(N, h, w, cm))
-                        proj_block_v15_prepare(N, h, w, cin, cm, cout)
-                    elif kind in ("grouped_proj", "grouped_proj_s2"):
-                        stride = 2 if kind == "grouped_proj_s2" else 1
-                        ws = max(ws, grouped_proj_block_workspace_bytes(N, h, w, cm, stride))
-                        grouped_proj_block_prepare(N, h, w, cin, cm, cout, self.groups, stride)
-                    elif kind == "grouped_residual":
-                        ws = max(ws, L.wino_residual_block_workspace_bytes_hw(N, ho, wo, cm))
-                        grouped_residual_block_prepare(N, ho, wo, cout, cm, self.groups)
-                    else:
-                        ws = max(ws, L.wino_residual_block_workspace_bytes_hw(N, ho, wo, cm))
-                        residual_block_prepare(N, cout, cm, ho, wo)
-                h, w = ho, wo
-            ws = max(ws, L.wino_head_workspace_bytes(N, self.feat_c, self.classes))
+                    shape = _Shape(N, h, w, ho, wo, cin, cm, cout, self.groups)
+                    ws = max(ws, KINDS[kind].workspace(shape))
+                    KINDS[kind].prepare(shape)
+                    h, w = ho, wo
+            ws = max(ws, lib().wino_head_workspace_bytes(N, self.feat_c, self.classes))
             head_prepare(N, self.feat_c, self.classes)
             self._ws = torch.empty((ws + 3) // 4, dtype=f32, device=dev)
             self._logits = torch.empty((N, self.classes), dtype=f32, device=dev)
@@ -255,27 +295,8 @@ class ResNet(Net):
         cur = self._stem_out
         outs = []
         for bufs, blocks in zip(self._stages, self.layers):
-            for i, (kind, _, _, _, p) in enumerate(blocks):
-                if kind == "basic":   # in place on the stage's tensor after its first block
-                    basic_block(cur, p[0], p[1], p[2], p[3], out=bufs[0], workspace=ws)
-                    nxt = bufs[0]
-                elif kind == "basic_s2":
-                    nxt = basic_block_s2(cur, p[0], p[1], p[2], out=bufs[0], workspace=ws)
-                else:
-                    nxt = bufs[i % 2]
-                    if kind == "proj":
-                        proj_block(cur, p[0], p[1], p[2], p[3], p[4], 1, out=nxt, workspace=ws)
-                    elif kind == "proj_v15":
-                        proj_block_v15(cur, p[0], p[1], p[2], p[3], p[4], out=nxt, workspace=ws)
-                    elif kind in ("grouped_proj", "grouped_proj_s2"):
-                        grouped_proj_block(cur, p[0], p[1], p[2], p[3], p[4], self.groups,
-                                           2 if kind == "grouped_proj_s2" else 1, out=nxt, workspace=ws)
-                    elif kind == "grouped_residual":
-                        grouped_residual_block(cur, p[0], p[1], p[2], p[3], p[4], p[5], self.groups, out=nxt,
-                                               workspace=ws)
-                    else:
-                        residual_block(cur, p[0], p[1], p[2], p[3], p[4], p[5], out=nxt, workspace=ws)
-                cur = nxt
+            for i, (kind, _, _, _, p) in enumerate(blocks):   # (bottlenecks ping-pong between the stage's two tensors)
+                cur = KINDS[kind].run(cur, p, self.groups, bufs[i % len(bufs)], ws)
             outs.append(cur)
         avgpool_fc(cur, self.head_packed, self.classes, in_padded=not self.bottleneck, out=self._logits, workspace=ws)
         return outs
@@ -304,16 +325,7 @@ class ResNet(Net):
         f = 2.0 * Hc * Wc * 64 * 147
         for (_, _, ho, wo), blocks in zip(shapes[1:], self.layers):
             for kind, cin, cm, cout, _ in blocks:
-                px = ho * wo
-                if self.bottleneck:
-                    hin = px * 4 if kind in ("proj_v15", "grouped_proj_s2") else px
-                    f += 2.0 * (hin * cin * cm + px * 9 * cm * (cm // self.groups) + px * cm * cout)
-                    if kind in ("proj", "proj_v15", "grouped_proj", "grouped_proj_s2"):
-                        f += 2.0 * px * cin * cout
-                else:
-                    f += 2.0 * px * 9 * (cin * cout + cout * cout)
-                    if kind == "basic_s2":
-                        f += 2.0 * px * cin * cout
+                f += 2.0 * KINDS[kind].macs(ho * wo, cin, cm, cout, self.groups)
         return f + 2.0 * self.feat_c * self.classes
 
 

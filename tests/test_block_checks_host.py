@@ -35,6 +35,9 @@ def _blocks(L):
     Hin, Cin, Ho = 28, 64, 14
     proj = {"x": "t", "w1": "t", "b1": "v", "s1": "v", "U2": "t", "b2": "v", "s2": "v", "tail": "t", "out": "t"}
     x_proj, out_proj = N * Hin * Hin * Cin * F, N * Ho * Ho * C4 * F
+    Cg, groups = 128, 32    # the grouped blocks' middle width
+    gres = {("wg" if k == "U2" else k): v for k, v in res.items()}
+    gproj = {("wg" if k == "U2" else k): v for k, v in proj.items()}
     C, K = 64, 128
     bb = {"x": "t", "U1": "t", "b1": "v", "s1": "v", "U2": "t", "b2": "v", "s2": "v", "out": "t"}
     bb_act = 2 * (H + 2) * (H + 2) * C * F
@@ -48,6 +51,10 @@ def _blocks(L):
                                     L.wino_proj_block_workspace_bytes_hw(N, Ho, Ho, Cm), x_proj, out_proj),
         "wino_proj_block_v15_hw": Block("wino_proj_block_v15_hw", proj, (N, Hin, Hin, Cin, Cm, C4),
                                         L.wino_proj_block_v15_workspace_bytes_hw(N, Hin, Hin, Cm), x_proj, out_proj),
+        "wino_grouped_residual_block_hw": Block("wino_grouped_residual_block_hw", gres, (N, H, H, C4, Cg, groups),
+                                                L.wino_residual_block_workspace_bytes_hw(N, H, H, Cg), act, act),
+        "wino_grouped_proj_block_hw": Block("wino_grouped_proj_block_hw", gproj, (N, Hin, Hin, Cin, Cg, C4, groups, 2),
+                                            L.wino_proj_block_v15_workspace_bytes_hw(N, Hin, Hin, Cg), x_proj, out_proj),
         "wino_basic_block_hw": Block("wino_basic_block_hw", bb, (2, H, H, C),
                                      L.wino_basic_block_workspace_bytes_hw(2, H, H, C), bb_act, bb_act),
         "wino_basic_block_s2_hw": Block("wino_basic_block_s2_hw", s2, (2, Hin, Hin, C, K),
@@ -59,7 +66,8 @@ def _blocks(L):
 
 
 @pytest.mark.parametrize("name", ["wino_residual_block_hw", "wino_residual_block", "wino_proj_block_hw",
-                                  "wino_proj_block_v15_hw", "wino_basic_block_hw", "wino_basic_block_s2_hw",
+                                  "wino_proj_block_v15_hw", "wino_grouped_residual_block_hw",
+                                  "wino_grouped_proj_block_hw", "wino_basic_block_hw", "wino_basic_block_s2_hw",
                                   "wino_avgpool_fc_hw"])
 def test_blocks_refuse_before_their_first_launch(name, pkg):
     L = pkg.lib()

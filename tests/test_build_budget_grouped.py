@@ -1,7 +1,7 @@
 """Register budget of the grouped 3x3 kernel (conv3x3_grouped.hip), with the report of test_build_budget.py: the file
 compiles the pack kernel and the twelve instantiations of the one kernel body -- stride {1, 2} x tile width {8, 16} x
-contraction width {16, 32, 64} -- and none spills a VGPR or an SGPR; grouped_block.hip, host code over existing
-launches, instantiates no kernel at all."""
+contraction width {16, 32, 64} -- and none spills a VGPR or an SGPR; bottleneck.hip, which composes every bottleneck
+block (the grouped ones among them) as host code over existing launches, instantiates no kernel at all."""
 from test_build_budget import _compile_report, _template_args
 
 
@@ -21,4 +21,4 @@ def test_grouped_kernel_spills_nothing(tmp_path):
 
 
 def test_grouped_blocks_instantiate_no_kernel(tmp_path):
-    assert _compile_report("grouped_block.hip", tmp_path) == {}
+    assert _compile_report("bottleneck.hip", tmp_path) == {}

@@ -313,5 +313,11 @@ def test_caller_supplied_buffers_are_validated(pkg, torch_dev):
         pkg.residual_block(x, w1, bn, U2, bn, w3, bn3, workspace=z(1000))    # too small
     with pytest.raises(pkg.WinoError):
         pkg.residual_block(x, w1, bn, U2, bn, w3, bn3, out=z(2, 14, 14, 64))
+    # a short BN vector would be read past its end by the kernel: each of the three pairs is checked against Cm / C4
+    for short in ((bn, bn, (z(128), z(64))), (bn, (z(32), z(64)), bn3), ((z(64), z(63)), bn, bn3)):
+        with pytest.raises(pkg.WinoError, match="bn1 / bn2 vectors must have Cm values, bn3's C4"):
+            pkg.residual_block(x, w1, short[0], U2, short[1], w3, short[2])
+    with pytest.raises(pkg.WinoError, match=r"w1 must be \[C4\]\[Cm\], w3 \[Cm\]\[C4\]"):
+        pkg.residual_block(x, w1, bn, U2, bn, z(64, 64), bn3)
     with pytest.raises(pkg.WinoError):
         pkg.conv3x3_bn_relu(z(1, 16, 16, 64), U2, z(64), z(64), out=z(1, 16, 16, 128))

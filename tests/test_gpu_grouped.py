@@ -153,6 +153,13 @@ def test_bad_arguments_raise(pkg, torch_dev):
         pkg.filter_pack_grouped(torch.zeros(128, 2, 3, 3, device=dev), 64)    # Cg = 2
     with pytest.raises(pkg.WinoError, match="rc=-3"):
         pkg.conv3x3_grouped_bn_relu(x, packed, bias, scale, 32, out=x)        # in place
+    # the blocks: one BN vector of the wrong length each (the kernels would read past its end)
+    z = lambda *s: torch.zeros(*s, device=dev)
+    bn, bn3 = (z(128), z(128)), (z(256), z(256))
+    with pytest.raises(pkg.WinoError, match="bn1 / bn2 vectors must have Cm values, bn3's C4"):
+        pkg.grouped_residual_block(z(1, 7, 5, 256), z(256, 128), bn, packed, bn, z(128, 256), (z(256), z(128)), 32)
+    with pytest.raises(pkg.WinoError, match="bn1 / bn2 vectors must have Cm values"):
+        pkg.grouped_proj_block(z(1, 7, 5, 64), z(64, 128), bn, packed, (z(64), z(128)), z((128 + 64 + 2) * 256), 32, 2)
 
 
 # ---------------------------------------------------------------------------------------------------- the blocks

@@ -230,3 +230,6 @@ def test_bad_arguments_raise(pkg, torch_dev):
     ws = torch.empty(16, device=dev)
     with pytest.raises(pkg.WinoError):
         blk.run(workspace=ws)
+    short = (blk.bnt[1][0], blk.bnt[1][1][:-1])                                            # bn2's scale one value short
+    with pytest.raises(pkg.WinoError, match="bn1 / bn2 vectors must have Cm values"):
+        pkg.proj_block(blk.xt, blk.w1t, blk.bnt[0], blk.U2, short, blk.tail, 2)

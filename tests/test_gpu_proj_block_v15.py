@@ -205,6 +205,9 @@ def test_bad_arguments_raise(pkg, torch_dev):
                            blk.tail)                                                       # [K][C][3][3] taps
     with pytest.raises(pkg.WinoError):
         pkg.proj_block_v15(blk.x, blk.w1t, blk.bnt[0], blk.taps, blk.bnt[1], blk.tail)    # CPU input
+    with pytest.raises(pkg.WinoError, match="bn1 / bn2 vectors must have Cm values"):
+        pkg.proj_block_v15(blk.xt, blk.w1t, (blk.bnt[0][0][:-1], blk.bnt[0][1]), blk.taps, blk.bnt[1],
+                           blk.tail)                                                       # bn1's bias one value short
     x48 = torch.zeros(1, 14, 14, 48, device=dev)
     with pytest.raises(pkg.WinoError, match="rc=-2"):
         pkg.proj_block_v15(x48, torch.zeros(48, 64, device=dev), blk.bnt[0], blk.taps, blk.bnt[1],
