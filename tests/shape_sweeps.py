@@ -14,8 +14,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 # the latency forms the plan queries accept are those of the existing forced-form tests (one table per family)
-from test_gpu_conv3x3_s2 import FORMS as S2_FORMS, _legal as _s2_legal
-from test_gpu_proj_block import FORMS as PROJ_FORMS
+from cases import PROJ_FORMS, S2_FORMS, s2_legal
 
 MAX_MACS = 2e9
 CUS = 256
@@ -185,7 +184,7 @@ def _s2_ok(form):
     def ok(sh):
         if kn is None:
             return True
-        if not _s2_legal(form, (sh["N"], sh["Hin"], sh["Win"], sh["C"], sh["K"])):
+        if not s2_legal(form, (sh["N"], sh["Hin"], sh["Win"], sh["C"], sh["K"])):
             return False
         if kn["WINO_1X1_ALGO"] == "small":
             return (9 * sh["C"]) // kn["WINO_1X1_SMALL_KS"] >= 64   # the planner's shortest K loop per wave

@@ -8,8 +8,8 @@ import os
 
 import pytest
 
+from build_report import compile_report, template_args
 from conftest import ROOT
-from test_build_budget import _compile_report, _template_args
 
 E_SHAPE, E_ARG = -2, -3
 NEW = ["wino_conv3x3_bn_add_relu_hw", "wino_basic_block_workspace_bytes_hw", "wino_basic_block_hw",
@@ -138,11 +138,11 @@ def test_python_block_refuses_a_channel_change(pkg):
 
 
 def _res_kernels(kernels, family):
-    return {n: _template_args(n, family) for n in kernels if _template_args(n, family) is not None}
+    return {n: template_args(n, family) for n in kernels if template_args(n, family) is not None}
 
 
 def test_res_file_compiles_the_res_kernels_only_within_budget(tmp_path):
-    k = _compile_report("conv3x3_res.hip", tmp_path)
+    k = compile_report("conv3x3_res.hip", tmp_path)
     fused = _res_kernels(k, "wino_f2_fused_kernel")
     small = _res_kernels(k, "wino_f2_small_kernel")
     assert len(k) == len(fused) + len(small), sorted(k)        # nothing else
@@ -161,7 +161,7 @@ def test_res_file_compiles_the_res_kernels_only_within_budget(tmp_path):
 
 
 def test_plain_file_has_no_res_instantiation(tmp_path):
-    k = _compile_report("wino_f2_fused.hip", tmp_path)
+    k = compile_report("wino_f2_fused.hip", tmp_path)
     for family in ("wino_f2_fused_kernel", "wino_f2_small_kernel"):
         args = _res_kernels(k, family)
         assert args, family

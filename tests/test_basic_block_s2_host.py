@@ -10,8 +10,8 @@ import subprocess
 
 import pytest
 
+from build_report import CSRC, compile_report, template_args
 from conftest import ROOT
-from test_build_budget import CSRC, _compile_report, _template_args
 
 E_SHAPE, E_ARG = -2, -3
 A_TAPS_PROJ = 4
@@ -167,7 +167,7 @@ def test_proj_file_compiles_the_proj_form_only_within_budget(tmp_path):
     budgets: the tiled kernel 128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), the latency kernels no spill at all, no
     spill code beside MFMAs.  (The stream-K kernels hold a few more SGPRs than A_TAPS's -- the shortcut's flag and
     pointers -- spilled to VGPR lanes outside the MFMA blocks.)"""
-    k = _compile_report("basic_block_s2.hip", tmp_path)
+    k = compile_report("basic_block_s2.hip", tmp_path)
     tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
     small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     pack = {n: v for n, v in k.items() if "s2_proj_pack_kernel" in n}
@@ -175,8 +175,8 @@ def test_proj_file_compiles_the_proj_form_only_within_budget(tmp_path):
     assert len(small) == 18, sorted(small)
     assert len(pack) == 1, sorted(k)
     assert set(k) == set(tiled) | set(small) | set(pack), sorted(k)
-    assert all(_template_args(n, "conv1x1_bn_kernel")[-1] == A_TAPS_PROJ for n in tiled), sorted(tiled)
-    assert all(_template_args(n, "conv1x1_small_kernel")[-1] == A_TAPS_PROJ for n in small), sorted(small)
+    assert all(template_args(n, "conv1x1_bn_kernel")[-1] == A_TAPS_PROJ for n in tiled), sorted(tiled)
+    assert all(template_args(n, "conv1x1_small_kernel")[-1] == A_TAPS_PROJ for n in small), sorted(small)
     for name, v in tiled.items():
         eight = "ILi32ELi8E" in name
         assert eight or "ILi32ELi4E" in name, name

@@ -10,61 +10,7 @@ import subprocess
 
 import pytest
 
-from conftest import ROOT
-
-INC = os.path.join(ROOT, "include")
-LIBDIR = os.path.join(ROOT, "cuda-winograd_amd")
-
-# A caller shaped like the reference's Test.c:13-56 (own text): unprototyped use of the six entry
-# points through the reference-named headers, `res >> 16` / `res & 0xFFFF`, first two calls
-# discarded, integer means over nTest - 2.  The one edit INTEGRATION.md section 1 prescribes is made:
-# cudaSetDevice(0) -> wino_set_device(0).
-REFERENCE_SHAPED_CALLER = r"""
-#include <stdio.h>
-#include <stdlib.h>
-#include "Kernel128_one.h"
-#include "Kernel128_winograd.h"
-#include "Kernel256_one.h"
-#include "Kernel256_winograd.h"
-#include "util.h"
-#include "winograd_mi355x.h"
-
-int main(int argc, char** argv) {
-  int nTest = 5, sum = 0, sum_other = 0, i, mode = 0;
-  wino_set_device(0);
-  if (argc >= 2) mode = atoi(argv[1]);
-  if (argc >= 3) nTest = atoi(argv[2]);
-  for (i = 0; i < nTest; i++) {
-    int res = -1;
-    printf("---- Iter: %d ----\n", i);
-    switch (mode) {
-      case 0: res = kernel_128(); break;
-      case 1: res = kernel_256(); break;
-      case 2: res = kernel_128_1_in(); break;
-      case 3: res = kernel_128_1_out(); break;
-      case 4: res = kernel_256_1_in(); break;
-      case 5: res = kernel_256_1_out(); break;
-    }
-    if (i > 1) { sum += res >> 16; sum_other += res & 0xFFFF; }
-  }
-  printf("Average Total Time: [Mine: %d us], [cuDNN: %d us]\n", sum / (nTest - 2), sum_other / (nTest - 2));
-  return 0;
-}
-"""
-
-
-def build_reference_shaped_caller(workdir):
-    """Compile + link per INTEGRATION.md section 1; returns the executable's path."""
-    src = os.path.join(workdir, "RefShapedTest.c")
-    with open(src, "w") as f:
-        f.write(REFERENCE_SHAPED_CALLER)
-    exe = os.path.join(workdir, "RefShapedTest")
-    obj = os.path.join(workdir, "RefShapedTest.o")
-    subprocess.check_call(["gcc", "-Wall", "-Werror", "-I" + INC, "-c", src, "-o", obj])
-    subprocess.check_call(["gcc", "-o", exe, obj, "-L" + LIBDIR, "-lwinograd_mi355x",
-                           "-Wl,-rpath," + LIBDIR, "-lpthread", "-lm"])
-    return exe
-
+from build_report import INC, build_reference_shaped_caller
 
 @pytest.mark.skipif(shutil.which("gcc") is None, reason="no gcc")
 def test_reference_shaped_caller_builds_against_include_and_so(tmp_path):

@@ -13,72 +13,16 @@ scratch_store -- inside any basic block that holds MFMAs, i.e. the main loops, w
 instruction is paid for (in-order issue).  SGPR spills outside the loops
 (prologue, epilogue, stream-K bookkeeping: 36-57 in the fused kernel, up to 37 in the GEMM's stream-K variants) cost a
 lane move each and are only bounded."""
-import os
-import re
-import shutil
-import subprocess
-
-import pytest
-
-from conftest import ROOT
-
-CSRC = os.path.join(ROOT, "cuda-winograd_amd", "csrc")
-
-
-def _compile_report(src, tmp_path):
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
-                          "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-c", os.path.join(CSRC, src),
-                          "-o", str(tmp_path / "x.o"), "-Rpass-analysis=kernel-resource-usage", "-save-temps"],
-                         capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
-    assert out.returncode == 0, out.stderr[-2000:]
-    kernels, cur = {}, None
-    for line in out.stderr.splitlines():
-        m = re.search(r"Function Name: (\S+)", line)
-        if m:
-            cur = kernels.setdefault(m.group(1), {})
-            continue
-        for key, pat in (("vgprs", r"\bVGPRs: (\d+)"), ("spill", r"VGPRs Spill: (\d+)"),
-                         ("sgpr_spill", r"SGPRs Spill: (\d+)"), ("occupancy", r"Occupancy \[waves/SIMD\]: (\d+)")):
-            m = re.search(pat, line)
-            if m and cur is not None and key not in cur:
-                cur[key] = int(m.group(1))
-    isa = [f for f in os.listdir(tmp_path) if f.endswith(".s") and "gfx950" in f]
-    assert len(isa) == 1, isa
-    text = (tmp_path / isa[0]).read_text()
-    for name, v in kernels.items():
-        i = text.index(name + ":")
-        body = text[i:text.index(".Lfunc_end", i)].splitlines()
-        blocks, blk = [], []
-        for line in body:
-            if re.match(r"^\.LBB\d+_\d+:", line):
-                blocks.append(blk)
-                blk = []
-            blk.append(line)
-        blocks.append(blk)
-        hot = [b for b in blocks if any("v_mfma" in x for x in b)]
-        v["mfma"] = sum("v_mfma" in x for b in hot for x in b)
-        v["spill_code_in_mfma_blocks"] = sum(any(p in x for p in ("v_readlane", "v_writelane", "scratch_load", "scratch_store"))
-                                             for b in hot for x in b)
-    return kernels
-
-
-def _template_args(name, family):
-    """The template arguments (bools as 0 / 1) of `name` if it is a mangled instantiation of the kernel template
-    `family`, else None.  The 1x1 kernels' last argument is their operand form AF (conv1x1_kernel.h)."""
-    m = re.search(family + r"I((?:L[ib]\d+E)+)E", name)
-    return [int(x) for x in re.findall(r"L[ib](\d+)E", m.group(1))] if m else None
+from build_report import compile_report, template_args
 
 
 def _plain_1x1(kernels, family):
     """The instantiations of the 1x1 kernel template `family` in the plain operand form (AF = A_PLAIN = 0)."""
-    return {n: v for n, v in kernels.items() if (_template_args(n, family) or [None])[-1] == 0}
+    return {n: v for n, v in kernels.items() if (template_args(n, family) or [None])[-1] == 0}
 
 
 def test_gemm_kernel_keeps_four_waves_per_simd(tmp_path):
-    k = _plain_1x1(_compile_report("conv1x1.hip", tmp_path), "conv1x1_bn_kernel")
+    k = _plain_1x1(compile_report("conv1x1.hip", tmp_path), "conv1x1_bn_kernel")
     assert len(k) == 8, sorted(k)          # {4, 8 waves} x {plain, stream-K} x {no residual, residual}
     for name, v in k.items():
         # 8-wave form: 60 KB of LDS -> two workgroups per CU -> 4 waves per SIMD -> 128 VGPRs.
@@ -95,7 +39,7 @@ def test_gemm_kernel_keeps_four_waves_per_simd(tmp_path):
 
 
 def test_fused_kernel_keeps_two_waves_per_simd(tmp_path):
-    k = {n: v for n, v in _compile_report("wino_f2_fused.hip", tmp_path).items() if "wino_f2_fused_kernel" in n}
+    k = {n: v for n, v in compile_report("wino_f2_fused.hip", tmp_path).items() if "wino_f2_fused_kernel" in n}
     # the 14x14 specialisation, the general H x W form, and the stamped diagnostic build of the
     # first (ILi16E: wino_diag_conv3x3_clock), which must stay within the same budget to be a
     # faithful probe of the product kernel's clock
@@ -111,14 +55,14 @@ def test_latency_kernels_spill_nothing(tmp_path):
     kernel (128 accumulators + 128 filter-fragment registers + the staging buffer) does -- but a spill there is a
     round trip to memory inside a loop that is bound by memory round trips: the first build of that form spilled 55
     registers (DESIGN_NOTEBOOK section 3).  None may spill, and no spill code may sit beside MFMAs."""
-    k3 = {n: v for n, v in _compile_report("wino_f2_fused.hip", tmp_path).items() if "wino_f2_small_kernel" in n}
+    k3 = {n: v for n, v in compile_report("wino_f2_fused.hip", tmp_path).items() if "wino_f2_small_kernel" in n}
     assert len(k3) == 6, sorted(k3)                # block widths 16 / 32 / 64 x {14x14, any feature map}
     for name, v in k3.items():
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)
         assert v["mfma"] >= 32, (name, v)
     sub = tmp_path / "one"
     sub.mkdir()
-    k1 = _plain_1x1(_compile_report("conv1x1.hip", sub), "conv1x1_small_kernel")
+    k1 = _plain_1x1(compile_report("conv1x1.hip", sub), "conv1x1_small_kernel")
     assert len(k1) == 18, sorted(k1)               # KS {1, 2, 4} x RT {1, 2} x CT {1, 2, 4}
     for name, v in k1.items():
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)

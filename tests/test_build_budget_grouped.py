@@ -1,13 +1,13 @@
-"""Register budget of the grouped 3x3 kernel (conv3x3_grouped.hip), with the report of test_build_budget.py: the file
+"""Register budget of the grouped 3x3 kernel (conv3x3_grouped.hip), with the report of build_report.py: the file
 compiles the pack kernel and the twelve instantiations of the one kernel body -- stride {1, 2} x tile width {8, 16} x
 contraction width {16, 32, 64} -- and none spills a VGPR or an SGPR; bottleneck.hip, which composes every bottleneck
 block (the grouped ones among them) as host code over existing launches, instantiates no kernel at all."""
-from test_build_budget import _compile_report, _template_args
+from build_report import compile_report, template_args
 
 
 def test_grouped_kernel_spills_nothing(tmp_path):
-    k = _compile_report("conv3x3_grouped.hip", tmp_path)
-    conv = {n: tuple(_template_args(n, "conv3x3_grouped_kernel")) for n in k if "conv3x3_grouped_kernel" in n}
+    k = compile_report("conv3x3_grouped.hip", tmp_path)
+    conv = {n: tuple(template_args(n, "conv3x3_grouped_kernel")) for n in k if "conv3x3_grouped_kernel" in n}
     assert sorted(conv.values()) == [(s, tw, kc) for s in (1, 2) for tw in (8, 16) for kc in (16, 32, 64)], conv
     assert len(k) == len(conv) + 1 and any("grouped_pack_kernel" in n for n in k), sorted(k)
     for name, v in k.items():
@@ -21,4 +21,4 @@ def test_grouped_kernel_spills_nothing(tmp_path):
 
 
 def test_grouped_blocks_instantiate_no_kernel(tmp_path):
-    assert _compile_report("bottleneck.hip", tmp_path) == {}
+    assert compile_report("bottleneck.hip", tmp_path) == {}

@@ -1,19 +1,19 @@
-"""Register budgets of the pooled 3x3 kernels (conv3x3_pool.hip), with the report of test_build_budget.py: the file
+"""Register budgets of the pooled 3x3 kernels (conv3x3_pool.hip), with the report of build_report.py: the file
 instantiates the two 3x3 kernel templates with the pooled epilogue only (EPI = 2), every throughput instantiation
 within the plain kernel's budget -- at most 256 VGPRs, two waves per SIMD, no VGPR spill, 128 MFMAs, no spill code in
 a block with MFMAs, at most 80 SGPR spills -- and every latency instantiation without a spill of either kind; and the
 plain file still holds no instantiation of another epilogue."""
-from test_build_budget import _compile_report, _template_args
+from build_report import compile_report, template_args
 
 EPI_POOL = 2
 
 
 def _of(kernels, family):
-    return {n: _template_args(n, family) for n in kernels if _template_args(n, family) is not None}
+    return {n: template_args(n, family) for n in kernels if template_args(n, family) is not None}
 
 
 def test_pool_file_compiles_the_pooled_kernels_only_within_budget(tmp_path):
-    k = _compile_report("conv3x3_pool.hip", tmp_path)
+    k = compile_report("conv3x3_pool.hip", tmp_path)
     fused = _of(k, "wino_f2_fused_kernel")
     small = _of(k, "wino_f2_small_kernel")
     assert len(k) == len(fused) + len(small), sorted(k)        # nothing else
@@ -33,7 +33,7 @@ def test_pool_file_compiles_the_pooled_kernels_only_within_budget(tmp_path):
 
 
 def test_vgg_ops_file_spills_nothing(tmp_path):
-    k = _compile_report("vgg_ops.hip", tmp_path)
+    k = compile_report("vgg_ops.hip", tmp_path)
     assert sorted(n for n in k) and all("image_pack_kernel" in n or "avgpool7_flatten_kernel" in n for n in k), sorted(k)
     assert len(k) == 2, sorted(k)
     for name, v in k.items():

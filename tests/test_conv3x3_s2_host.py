@@ -6,8 +6,8 @@ templates in operand form A_TAPS only."""
 import ctypes
 import os
 
+from build_report import compile_report, template_args
 from conftest import ROOT
-from test_build_budget import _compile_report, _template_args
 
 E_SHAPE, E_ARG = -2, -3
 A_TAPS = 3
@@ -156,14 +156,14 @@ def test_tap_form_kernels_build_budget(tmp_path):
     {plain, stream-K}) and 18 latency kernels (KS x RT x CT) -- within the budgets of the other forms
     (test_proj_block_host.py): the tiled kernel 128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), a few spills outside
     the loops at most; the latency kernels no spill at all; no spill code beside MFMAs."""
-    k = _compile_report("conv3x3_s2.hip", tmp_path)
+    k = compile_report("conv3x3_s2.hip", tmp_path)
     tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
     small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     assert len(tiled) == 4, sorted(tiled)
     assert len(small) == 18, sorted(small)
     assert set(k) == set(tiled) | set(small), sorted(k)
-    assert all(_template_args(n, "conv1x1_bn_kernel")[-1] == A_TAPS for n in tiled), sorted(tiled)
-    assert all(_template_args(n, "conv1x1_small_kernel")[-1] == A_TAPS for n in small), sorted(small)
+    assert all(template_args(n, "conv1x1_bn_kernel")[-1] == A_TAPS for n in tiled), sorted(tiled)
+    assert all(template_args(n, "conv1x1_small_kernel")[-1] == A_TAPS for n in small), sorted(small)
     for name, v in tiled.items():
         eight = "ILi32ELi8E" in name
         assert eight or "ILi32ELi4E" in name, name
@@ -182,7 +182,7 @@ def test_tap_offset_is_scalar_in_the_k_loop(tmp_path):
     import re
     import shutil
     import subprocess
-    from test_build_budget import CSRC
+    from build_report import CSRC
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     asm = tmp_path / "s2.s"
     out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),

@@ -8,83 +8,13 @@ import ctypes
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from cases import TIGHT, BasicBlock, ResLayer
+from gpu_support import dirty_ticket_scenario, graph_replay_scenario, torch_dev  # noqa: F401
 
-TIGHT = 2e-5
+pytestmark = pytest.mark.gpu
 
 # ResNet-18/34's stages: (H, C); every 3x3 of the basic blocks there is C -> C at stride 1
 STAGES = {"conv2": (56, 64), "conv3": (28, 128), "conv4": (14, 256), "conv5": (7, 512)}
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-def _padded(torch, N, H, W, C, g, ring=0.0):
-    """[N][H+2][W+2][C], interior uniform in [-0.5, 0.5), the ring set to `ring`."""
-    x = torch.full((N, H + 2, W + 2, C), ring)
-    x[:, 1:-1, 1:-1, :] = torch.rand(N, H, W, C, generator=g) - 0.5
-    return x
-
-
-class _Layer:
-    """One residual layer's tensors (CPU masters and device copies) and the library's run of it."""
-
-    def __init__(self, pkg, torch_dev, N, H, W, C, K, seed):
-        self.torch, self.dev = torch_dev
-        torch = self.torch
-        self.pkg = pkg
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        self.x = _padded(torch, N, H, W, C, g)
-        # the residual's ring is never read: NaN there would reach any output that read it
-        self.res = _padded(torch, N, H, W, K, g, ring=float("nan"))
-        self.w = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
-        self.bias = torch.rand(K, generator=g) - 0.5
-        self.scale = torch.rand(K, generator=g) + 0.5
-        t = lambda a: a.contiguous().to(self.dev)
-        self.xt, self.rt, self.bt, self.st = t(self.x), t(self.res), t(self.bias), t(self.scale)
-        self.U = pkg.filter_transform_f2(t(self.w))
-        self.N, self.H, self.W, self.C, self.K = N, H, W, C, K
-
-    def run(self, relu=True, res=None, out=None):
-        torch = self.torch
-        if out is None:
-            out = torch.full((self.N, self.H + 2, self.W + 2, self.K), float("nan"), device=self.dev)
-        return self.pkg.conv3x3_bn_add_relu(self.xt, self.U, self.bt, self.st, self.rt if res is None else res,
-                                            relu=relu, out=out)
-
-    def reference(self, relu=True, idx=None):
-        torch = self.torch
-        F = torch.nn.functional
-        pick = (lambda a: a) if idx is None else (lambda a: a[idx])
-        x = pick(self.x)[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        r = pick(self.res)[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        y = F.conv2d(x, self.w.double(), padding=1)
-        y = y * self.scale.double()[None, :, None, None] + self.bias.double()[None, :, None, None] + r
-        if relu:
-            y = torch.relu(y)
-        return y.permute(0, 2, 3, 1).numpy()
-
-    def check(self, O, got, relu=True, idx=None):
-        g = got.cpu().numpy()
-        if idx is not None:
-            g = g[idx]
-        ring = np.ones(g.shape[1:3], bool)
-        ring[1:-1, 1:-1] = False
-        assert (g[:, ring, :] == 0).all(), "out's ring is not zero"
-        inner = g[:, 1:-1, 1:-1, :]
-        assert np.isfinite(inner).all()
-        want = self.reference(relu, idx)
-        assert inner.shape == want.shape
-        assert O.rel_error(inner, want) < TIGHT
-        if relu:
-            assert 0.2 < (want > 0).mean() < 0.8   # both sides of the ReLU
-        else:
-            assert (want < 0).mean() > 0.2
-        assert self.pkg.tickets_in_use() == 0
 
 
 @pytest.mark.parametrize("N", [1, 8, 128])
@@ -92,14 +22,14 @@ class _Layer:
 def test_layer_at_the_stage_shapes(stage, N, pkg, O, torch_dev):
     """14x14 takes the fixed-geometry kernels, the others the general path (7x7: odd)."""
     H, C = STAGES[stage]
-    layer = _Layer(pkg, torch_dev, N, H, H, C, C, seed=H * 1000 + N)
+    layer = ResLayer(pkg, torch_dev, N, H, H, C, C, seed=H * 1000 + N)
     layer.check(O, layer.run(), idx=None if N < 128 else [0, 61, 127])
 
 
 @pytest.mark.parametrize("shape", [(3, 14, 14, 128, 64), (2, 9, 13, 64, 128)])
 def test_layer_without_relu(shape, pkg, O, torch_dev):
     N, H, W, C, K = shape
-    layer = _Layer(pkg, torch_dev, N, H, W, C, K, seed=N + H + W)
+    layer = ResLayer(pkg, torch_dev, N, H, W, C, K, seed=N + H + W)
     layer.check(O, layer.run(relu=False), relu=False)
 
 
@@ -127,7 +57,7 @@ def test_every_throughput_form(shape, pkg, O, torch_dev, knobs):
     result plus the residual (the same plan, the same accumulation order) and the fp64 composition."""
     torch, dev = torch_dev
     N, H, W, C, K = shape
-    layer = _Layer(pkg, torch_dev, N, H, W, C, K, seed=sum(shape))
+    layer = ResLayer(pkg, torch_dev, N, H, W, C, K, seed=sum(shape))
     items = _items(N, H, W, K)
     knobs.set("WINO_3X3_ALGO", "big")
     seen = set()
@@ -148,7 +78,7 @@ def test_every_latency_form(shape, ct, pkg, O, torch_dev, knobs):
     """WINO_3X3_ALGO=small at every block width, without and with the split-C reduction (S > 1)."""
     torch, dev = torch_dev
     N, H, W, C, K = shape
-    layer = _Layer(pkg, torch_dev, N, H, W, C, K, seed=ct * 7 + sum(shape))
+    layer = ResLayer(pkg, torch_dev, N, H, W, C, K, seed=ct * 7 + sum(shape))
     knobs.set("WINO_3X3_ALGO", "small")
     knobs.set("WINO_SMALL_CT", ct)
     for split in (1, 2, 4):
@@ -165,7 +95,7 @@ def test_every_latency_form(shape, ct, pkg, O, torch_dev, knobs):
 def test_zero_residual_is_the_plain_layer_bitwise(shape, algo, pkg, torch_dev, knobs):
     torch, dev = torch_dev
     N, H, W, C, K = shape
-    layer = _Layer(pkg, torch_dev, N, H, W, C, K, seed=3 + N)
+    layer = ResLayer(pkg, torch_dev, N, H, W, C, K, seed=3 + N)
     if algo:
         knobs.set("WINO_3X3_ALGO", algo)
     if algo == "big":
@@ -183,7 +113,7 @@ def test_zero_residual_is_the_plain_layer_bitwise(shape, algo, pkg, torch_dev, k
 def test_in_place_equals_out_of_place(shape, algo, pkg, O, torch_dev, knobs):
     torch, dev = torch_dev
     N, H, W, C, K = shape
-    layer = _Layer(pkg, torch_dev, N, H, W, C, K, seed=11 + N)
+    layer = ResLayer(pkg, torch_dev, N, H, W, C, K, seed=11 + N)
     if algo:
         knobs.set("WINO_3X3_ALGO", algo)
     if algo == "big":
@@ -198,59 +128,11 @@ def test_in_place_equals_out_of_place(shape, algo, pkg, O, torch_dev, knobs):
     layer.check(O, got)
 
 
-class _Block:
-    def __init__(self, pkg, torch_dev, N, H, W, C, seed):
-        self.torch, self.dev = torch_dev
-        torch = self.torch
-        self.pkg = pkg
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        self.x = _padded(torch, N, H, W, C, g)
-        self.w = [(torch.rand(C, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4 for _ in range(2)]
-        self.bn = [(torch.rand(C, generator=g) - 0.5, torch.rand(C, generator=g) + 0.5) for _ in range(2)]
-        t = lambda a: a.contiguous().to(self.dev)
-        self.xt = t(self.x)
-        self.U = [pkg.filter_transform_f2(t(w)) for w in self.w]
-        self.bnt = [(t(b), t(s)) for b, s in self.bn]
-        self.N, self.H, self.W, self.C = N, H, W, C
-
-    def run(self, x=None, out=None, workspace=None):
-        torch = self.torch
-        if out is None:
-            out = torch.full((self.N, self.H + 2, self.W + 2, self.C), float("nan"), device=self.dev)
-        if workspace is None:
-            need = self.pkg.lib().wino_basic_block_workspace_bytes_hw(self.N, self.H, self.W, self.C)
-            workspace = torch.full((need // 4,), float("nan"), device=self.dev)
-        return self.pkg.basic_block(self.xt if x is None else x, self.U[0], self.bnt[0], self.U[1], self.bnt[1],
-                                    out=out, workspace=workspace)
-
-    def reference(self, x_padded, blocks=1):
-        """fp64 on the CPU, `blocks` times in a row."""
-        torch = self.torch
-        F = torch.nn.functional
-        x = x_padded[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        bn = lambda y, i: y * self.bn[i][1].double()[None, :, None, None] + self.bn[i][0].double()[None, :, None, None]
-        for _ in range(blocks):
-            t1 = torch.relu(bn(F.conv2d(x, self.w[0].double(), padding=1), 0))
-            x = torch.relu(bn(F.conv2d(t1, self.w[1].double(), padding=1), 1) + x)
-        return x.permute(0, 2, 3, 1).numpy()
-
-    def check(self, O, got, blocks=1):
-        g = got.cpu().numpy()
-        ring = np.ones(g.shape[1:3], bool)
-        ring[1:-1, 1:-1] = False
-        assert (g[:, ring, :] == 0).all(), "out's ring is not zero"
-        want = self.reference(self.x, blocks)
-        assert np.isfinite(g).all()
-        assert O.rel_error(g[:, 1:-1, 1:-1, :], want) < TIGHT
-        assert (want > 0).mean() > 0.2
-        assert self.pkg.tickets_in_use() == 0
-
-
 @pytest.mark.parametrize("N", [1, 8])
 @pytest.mark.parametrize("stage", sorted(STAGES))
 def test_block_at_the_stage_shapes(stage, N, pkg, O, torch_dev):
     H, C = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, H, H, C, seed=500 + H + N)
+    blk = BasicBlock(pkg, torch_dev, N, H, H, C, seed=500 + H + N)
     blk.check(O, blk.run())
 
 
@@ -313,7 +195,7 @@ def test_two_blocks_chained_in_place(stage, N, pkg, O, torch_dev):
     """out fed forward as the next block's x, in place: one activation tensor and one workspace for the chain."""
     torch, dev = torch_dev
     H, C = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, H, H, C, seed=77 + N)
+    blk = BasicBlock(pkg, torch_dev, N, H, H, C, seed=77 + N)
     x = blk.xt.clone()
     ws = torch.empty(pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, H, C) // 4, device=dev)
     for _ in range(2):
@@ -329,24 +211,9 @@ def test_block_in_a_graph(stage, N, pkg, O, torch_dev):
     """The two launches captured into one graph (one stream) after basic_block_prepare: the replay equals eager."""
     torch, dev = torch_dev
     H, C = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, H, H, C, seed=909 + N)
-    eager = blk.run().clone()
-    out = torch.zeros_like(eager)
-    ws = torch.empty(pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, H, C) // 4, device=dev)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        pkg.basic_block_prepare(N, H, H, C)
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        blk.run(out=out, workspace=ws)
-    for _ in range(2):
-        out.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, eager)
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
+    blk = BasicBlock(pkg, torch_dev, N, H, H, C, seed=909 + N)
+    eager = graph_replay_scenario(pkg, torch_dev, blk.run, lambda: pkg.basic_block_prepare(N, H, H, C),
+                                  pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, H, C))
     if N <= 8:
         blk.check(O, eager)
 
@@ -371,26 +238,8 @@ def test_a_dirty_ticket_counter_is_reported_and_reset_recovers(form, pkg, O, tor
         use, _, sp, ct, wgs = pkg.small_plan_3x3_full(N, C, K, H=H, W=W)
         assert use == 1 and sp == 4
         n_tickets = wgs // sp
-    layer = _Layer(pkg, torch_dev, N, H, W, C, K, seed=99)
-    stream = torch.cuda.Stream()
-    with torch.cuda.stream(stream):
-        ref = layer.run().clone()
-        layer.check(O, ref)
-        pkg.stream_check()
-        for i in range(n_tickets):
-            pkg.poison_ticket(i, 1)
-        layer.run()   # computes with dirty counters: its result is not to be trusted, and it must say so
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            pkg.stream_check()
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            layer.run()
-        pkg.stream_reset_scratch()
-        pkg.stream_check()
-        assert pkg.tickets_in_use() == 0
-        for _ in range(2):
-            assert torch.equal(layer.run(), ref)
-        assert pkg.tickets_in_use() == 0
-    torch.cuda.synchronize()
+    layer = ResLayer(pkg, torch_dev, N, H, W, C, K, seed=99)
+    dirty_ticket_scenario(pkg, torch, layer.run, n_tickets, check=lambda ref: layer.check(O, ref))
 
 
 def test_batch_split_across_two_launches(pkg, O, torch_dev):
@@ -426,13 +275,13 @@ def test_batch_split_across_two_launches(pkg, O, torch_dev):
 
 def test_bad_arguments_raise(pkg, torch_dev):
     torch, dev = torch_dev
-    layer = _Layer(pkg, torch_dev, 1, 14, 14, 64, 128, seed=5)
+    layer = ResLayer(pkg, torch_dev, 1, 14, 14, 64, 128, seed=5)
     with pytest.raises(pkg.WinoError):
         layer.run(res=torch.zeros(1, 16, 16, 64, device=dev))            # residual with C channels, not K
-    square = _Layer(pkg, torch_dev, 1, 14, 14, 128, 128, seed=7)
+    square = ResLayer(pkg, torch_dev, 1, 14, 14, 128, 128, seed=7)
     with pytest.raises(pkg.WinoError, match="rc=-3"):
         square.run(res=square.xt)                                        # the residual is the input
-    blk = _Block(pkg, torch_dev, 1, 14, 14, 64, seed=6)
+    blk = BasicBlock(pkg, torch_dev, 1, 14, 14, 64, seed=6)
     with pytest.raises(pkg.WinoError):
         blk.run(workspace=torch.empty(16, device=dev))                   # workspace too small
     with pytest.raises(pkg.WinoError, match="rc=-3"):

@@ -7,107 +7,13 @@ contract; Python argument errors."""
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from cases import S2_FORM_SHAPES, S2_FORMS, TIGHT, S2Block, ring_mask, s2_legal
+from gpu_support import dirty_ticket_scenario, graph_replay_scenario, torch_dev  # noqa: F401
 
-TIGHT = 2e-5
+pytestmark = pytest.mark.gpu
 
 # the downsampling blocks of ResNet-18 / -34: (Hin, C, K), stride 2 on the first 3x3 and on the 1x1 shortcut
 STAGES = {"conv3": (56, 64, 128), "conv4": (28, 128, 256), "conv5": (14, 256, 512)}
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-def _ring(H, W):
-    ring = np.ones((H + 2, W + 2), bool)
-    ring[1:-1, 1:-1] = False
-    return ring
-
-
-class _Block:
-    """One downsampling block's parameters (CPU masters, device copies, the packed buffer) and its fp64 reference."""
-
-    def __init__(self, pkg, torch_dev, N, Hin, Win, C, K, seed):
-        self.torch, self.dev = torch_dev
-        torch = self.torch
-        self.pkg = pkg
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        x = torch.zeros(N, Hin + 2, Win + 2, C)
-        x[:, 1:-1, 1:-1, :] = torch.rand(N, Hin, Win, C, generator=g) - 0.5
-        self.x = x
-        self.w1 = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
-        self.wd = (torch.rand(K, C, 1, 1, generator=g) - 0.5) / np.sqrt(C) * 4
-        self.w2 = (torch.rand(K, K, 3, 3, generator=g) - 0.5) / np.sqrt(9 * K) * 4
-        vec = lambda lo: torch.rand(K, generator=g) + lo
-        self.b1, self.s1 = vec(-0.5), vec(0.5)
-        self.bd, self.sd = vec(-0.5), vec(0.5)
-        self.b2, self.s2 = vec(-0.5), vec(0.5)
-        t = lambda a: a.contiguous().to(self.dev)
-        self.xt = t(x)
-        self.taps = pkg.filter_pack_s2(t(self.w1))
-        self.packed = pkg.s2_proj_pack(self.taps, (t(self.b1), t(self.s1)), t(self.wd.view(K, C).t()),
-                                       (t(self.bd), t(self.sd)))
-        self.U2 = pkg.filter_transform_f2(t(self.w2))
-        self.bn1 = (t(self.b1), t(self.s1))
-        self.bn2 = (t(self.b2), t(self.s2))
-        self.N, self.Hin, self.Win, self.C, self.K = N, Hin, Win, C, K
-        self.H, self.W = (Hin - 1) // 2 + 1, (Win - 1) // 2 + 1
-
-    def nan(self):
-        return self.torch.full((self.N, self.H + 2, self.W + 2, self.K), float("nan"), device=self.dev)
-
-    def layer(self):
-        return self.pkg.conv3x3_s2_proj(self.xt, self.packed, t1=self.nan(), sc=self.nan())
-
-    def plain(self):
-        return self.pkg.conv3x3_s2_bn_relu(self.xt, self.taps, *self.bn1, relu=True, out=self.nan())
-
-    def block(self, out=None, workspace=None):
-        return self.pkg.basic_block_s2(self.xt, self.packed, self.U2, self.bn2,
-                                       out=self.nan() if out is None else out, workspace=workspace)
-
-    def reference(self, idx=None, block=True):
-        """fp64 on the CPU: (t1, sc, out), each [n][H][W][K] (out None unless `block`)."""
-        torch = self.torch
-        F = torch.nn.functional
-        x = self.x if idx is None else self.x[idx]
-        xin = x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        bn = lambda y, s, b: y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-        t1 = torch.relu(bn(F.conv2d(xin, self.w1.double(), stride=2, padding=1), self.s1, self.b1))
-        sc = bn(F.conv2d(xin, self.wd.double(), stride=2), self.sd, self.bd)
-        nhwc = lambda y: y.permute(0, 2, 3, 1).numpy()
-        if not block:
-            return nhwc(t1), nhwc(sc), None
-        out = torch.relu(bn(F.conv2d(t1, self.w2.double(), padding=1), self.s2, self.b2) + sc)
-        return nhwc(t1), nhwc(sc), nhwc(out)
-
-    def check_layer(self, O, t1, sc, idx=None):
-        a, b = t1.cpu().numpy(), sc.cpu().numpy()
-        if idx is not None:
-            a, b = a[idx], b[idx]
-        ring = _ring(self.H, self.W)
-        assert np.isfinite(a).all()
-        assert (a[:, ring, :] == 0).all(), "t1's ring is not zero"
-        assert np.isfinite(b[:, 1:-1, 1:-1, :]).all(), "sc's interior is not all written"
-        assert np.isnan(b[:, ring, :]).all(), "sc's ring was written"
-        want_t1, want_sc, _ = self.reference(idx, block=False)
-        assert O.rel_error(a[:, 1:-1, 1:-1, :], want_t1) < TIGHT
-        assert O.rel_error(b[:, 1:-1, 1:-1, :], want_sc) < TIGHT
-        assert (want_t1 > 0).mean() > 0.2 and (want_sc < 0).mean() > 0.2   # both sides of t1's ReLU; sc has none
-
-    def check_block(self, O, out, idx=None):
-        g = out.cpu().numpy()
-        if idx is not None:
-            g = g[idx]
-        assert np.isfinite(g).all()
-        assert (g[:, _ring(self.H, self.W), :] == 0).all(), "out's ring is not zero"
-        want = self.reference(idx)[2]
-        assert O.rel_error(g[:, 1:-1, 1:-1, :], want) < TIGHT
-        assert (want > 0).mean() > 0.2
 
 
 LAYER_POINTS = [(s, n) for s in sorted(STAGES) for n in (1, 2, 8, 32)] + [("conv4", 128)]
@@ -118,49 +24,23 @@ def test_fused_layer_at_stage_shapes(stage, N, pkg, O, torch_dev):
     """t1 and sc of the fused layer against fp64, and t1 bitwise the plain stride-2 layer's output."""
     torch, _ = torch_dev
     Hin, C, K = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=Hin * 1000 + N)
+    blk = S2Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=Hin * 1000 + N)
     t1, sc = blk.layer()
     blk.check_layer(O, t1, sc, idx=None if N <= 32 else [0, 77, 127])
     assert torch.equal(t1, blk.plain())
     assert pkg.tickets_in_use() == 0
 
 
-# (knob settings) -> a forced form, as in test_gpu_conv3x3_s2.py
-FORMS = {f"latency_ks{ks}_rt{rt}_ct{ct}": {"WINO_1X1_ALGO": "small", "WINO_1X1_SMALL_KS": ks, "WINO_1X1_SMALL_RT": rt,
-                                          "WINO_1X1_SMALL_CT": ct}
-         for ks in (1, 2, 4) for rt in (1, 2) for ct in (1, 2, 4)}
-FORMS.update({
-    "tiled": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 0},
-    "stream_k": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1},
-    # ranges that start and end inside taps, the centre tap's included
-    "split_24": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 24},
-    "split_40": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 40},
-    "split_104": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 104},
-})
-# (N, Hin, Win, C, K): 8-wave tiles (K = 256) with 2 k-steps per tap, 4-wave tiles (K = 128) with 3 per tap
-FORM_SHAPES = [(2, 28, 28, 64, 256), (3, 15, 13, 96, 128)]
-
-
-def _legal(form, shape):
-    """The latency forms the planner accepts for this shape (K = 9C in 16-channel chunks per wave, the workgroup's
-    columns a divisor of K)."""
-    kn = FORMS[form]
-    if kn["WINO_1X1_ALGO"] != "small":
-        return True
-    C, K, ks, ct = shape[3], shape[4], kn["WINO_1X1_SMALL_KS"], kn["WINO_1X1_SMALL_CT"]
-    return (9 * C) % (16 * ks) == 0 and K % ((4 // ks) * ct * 16) == 0
-
-
-@pytest.mark.parametrize("form,shape", [(f, s) for s in FORM_SHAPES for f in sorted(FORMS) if _legal(f, s)])
+@pytest.mark.parametrize("form,shape", [(f, s) for s in S2_FORM_SHAPES for f in sorted(S2_FORMS) if s2_legal(f, s)])
 def test_forced_forms(form, shape, pkg, O, torch_dev, knobs):
     """In every form: t1 bitwise the plain layer's, sc against fp64, both bitwise from launch to launch."""
     torch, _ = torch_dev
-    for k, v in FORMS[form].items():
+    for k, v in S2_FORMS[form].items():
         knobs.set(k, v)
     N, Hin, Win, C, K = shape
     want = {"latency": pkg.FORM_LATENCY, "tiled": pkg.FORM_TILED}.get(form.split("_")[0], pkg.FORM_STREAM_K)
     assert pkg.conv3x3_s2_plan(N, Hin, Win, C, K) == want
-    blk = _Block(pkg, torch_dev, N, Hin, Win, C, K, seed=N * Hin + C)
+    blk = S2Block(pkg, torch_dev, N, Hin, Win, C, K, seed=N * Hin + C)
     t1, sc = blk.layer()
     blk.check_layer(O, t1, sc)
     assert torch.equal(t1, blk.plain())
@@ -213,7 +93,7 @@ def test_block_against_fp64_and_torch(stage, N, pkg, O, torch_dev):
     BatchNorm with random running statistics, folded) run by torch on the GPU."""
     torch, dev = torch_dev
     Hin, C, K = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=7 * Hin + N)
+    blk = S2Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=7 * Hin + N)
     fwd = _torch_basic_block(torch, blk, dev)
     t = lambda a: a.contiguous().to(dev)
     K_ = blk.K
@@ -236,7 +116,7 @@ def test_block_against_fp64_and_torch(stage, N, pkg, O, torch_dev):
 ])
 def test_odd_and_tiny_maps(N, Hin, Win, C, K, pkg, O, torch_dev):
     torch, _ = torch_dev
-    blk = _Block(pkg, torch_dev, N, Hin, Win, C, K, seed=N + Hin * Win + C)
+    blk = S2Block(pkg, torch_dev, N, Hin, Win, C, K, seed=N + Hin * Win + C)
     t1, sc = blk.layer()
     blk.check_layer(O, t1, sc)
     assert torch.equal(t1, blk.plain())
@@ -249,7 +129,7 @@ def test_resnet18_stage_opening(N, pkg, O, torch_dev):
     out -- the padded layout chains as it stands -- against fp64."""
     torch, dev = torch_dev
     Hin, C, K = STAGES["conv4"]
-    blk = _Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=1804 + N)
+    blk = S2Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=1804 + N)
     g = torch.Generator(device="cpu").manual_seed(N)
     w3 = (torch.rand(K, K, 3, 3, generator=g) - 0.5) / np.sqrt(9 * K) * 4
     w4 = (torch.rand(K, K, 3, 3, generator=g) - 0.5) / np.sqrt(9 * K) * 4
@@ -265,7 +145,7 @@ def test_resnet18_stage_opening(N, pkg, O, torch_dev):
     u = torch.relu(bn(F.conv2d(y0, w3.double(), padding=1), s3, b3))
     want = torch.relu(bn(F.conv2d(u, w4.double(), padding=1), s4, b4) + y0).permute(0, 2, 3, 1).numpy()
     g_ = out.cpu().numpy()
-    assert (g_[:, _ring(blk.H, blk.W), :] == 0).all()
+    assert (g_[:, ring_mask(blk.H, blk.W), :] == 0).all()
     assert O.rel_error(g_[:, 1:-1, 1:-1, :], want) < TIGHT
 
 
@@ -275,24 +155,9 @@ def test_block_in_a_graph(stage, N, pkg, O, torch_dev):
     eager result."""
     torch, dev = torch_dev
     Hin, C, K = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=4242 + N)
-    eager = blk.block().clone()
-    out = torch.zeros_like(eager)
-    ws = torch.empty(pkg.lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Hin, K) // 4, device=dev)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        pkg.basic_block_s2_prepare(N, Hin, Hin, C, K)
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        blk.block(out=out, workspace=ws)
-    for _ in range(2):
-        out.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, eager)
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
+    blk = S2Block(pkg, torch_dev, N, Hin, Hin, C, K, seed=4242 + N)
+    eager = graph_replay_scenario(pkg, torch_dev, blk.block, lambda: pkg.basic_block_s2_prepare(N, Hin, Hin, C, K),
+                                  pkg.lib().wino_basic_block_s2_workspace_bytes_hw(N, Hin, Hin, K))
     blk.check_block(O, eager)
 
 
@@ -303,41 +168,20 @@ def test_a_dirty_ticket_counter_is_reported_and_reset_recovers(pkg, O, torch_dev
     torch, dev = torch_dev
     knobs.set("WINO_1X1_ALGO", "big")
     knobs.set("WINO_1X1_SK", 1)
-    N, Hin, Win, C, K = FORM_SHAPES[0]
-    blk = _Block(pkg, torch_dev, N, Hin, Win, C, K, seed=99)
+    N, Hin, Win, C, K = S2_FORM_SHAPES[0]
+    blk = S2Block(pkg, torch_dev, N, Hin, Win, C, K, seed=99)
     assert pkg.conv3x3_s2_plan(N, Hin, Win, C, K) == pkg.FORM_STREAM_K
     n_tickets = ((N * 14 * 14 + 111) // 112) * (K // 128)   # row tiles x column blocks
-    stream = torch.cuda.Stream()
-    with torch.cuda.stream(stream):
-        t1, sc = blk.layer()
-        t1, sc = t1.clone(), sc.clone()
-        blk.check_layer(O, t1, sc)
-        assert pkg.tickets_in_use() == 0
-        pkg.stream_check()
-        for i in range(n_tickets):
-            pkg.poison_ticket(i, 1)
-        blk.layer()   # computes with dirty counters: its result is not to be trusted, and it must say so
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            pkg.stream_check()
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            blk.layer()
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            blk.block()
-        pkg.stream_reset_scratch()
-        pkg.stream_check()
-        assert pkg.tickets_in_use() == 0
-        for _ in range(2):
-            a, b = blk.layer()
-            assert torch.equal(a, t1)
-            assert torch.equal(b[:, 1:-1, 1:-1, :], sc[:, 1:-1, 1:-1, :])
-        blk.check_block(O, blk.block())
-        assert pkg.tickets_in_use() == 0
-    torch.cuda.synchronize()
+    inner = lambda sc: sc[:, 1:-1, 1:-1, :]   # sc's ring is never written
+    dirty_ticket_scenario(pkg, torch, blk.layer, n_tickets,
+                          same=lambda got, ref: torch.equal(got[0], ref[0]) and torch.equal(inner(got[1]), inner(ref[1])),
+                          check=lambda ref: blk.check_layer(O, *ref), also_refused=[blk.block],
+                          after=lambda: blk.check_block(O, blk.block()))
 
 
 def test_bad_arguments_raise(pkg, torch_dev):
     torch, dev = torch_dev
-    blk = _Block(pkg, torch_dev, 1, 14, 14, 64, 128, seed=3)
+    blk = S2Block(pkg, torch_dev, 1, 14, 14, 64, 128, seed=3)
     with pytest.raises(pkg.WinoError):
         pkg.s2_proj_pack(blk.taps, blk.bn1, blk.taps, blk.bn1)                        # wd not [C][K]
     with pytest.raises(pkg.WinoError):

@@ -12,9 +12,10 @@ import subprocess
 import numpy as np
 import pytest
 
+from build_report import build_reference_shaped_caller
+from cases import TIGHT, rand_layer, ring_mask, to_dev
 from conftest import ROOT, load_bin
-from test_boundary import build_reference_shaped_caller
-from test_gpu_parity import REL, TIGHT, _rand_layer, _ring, _t, torch_dev  # noqa: F401
+from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -27,7 +28,7 @@ def _golden_for(O, golden_outputs, name):
 
 @pytest.mark.parametrize("mode", [0, 5])
 def test_reference_shaped_caller_runs_with_the_reference_stdout(mode, data_dir, tmp_path):
-    """The caller of tests/test_boundary.py (reference-shaped main, built per INTEGRATION.md section 1) on the
+    """The caller of tests/build_report.py (reference-shaped main, built per INTEGRATION.md section 1) on the
     reference data set with WINO_STDOUT_COMPAT=1: exactly the reference's lines, in its order
     (Test.c:23,50-53; Kernel128_winograd.cu:270,275,404,409; util.c:62)."""
     exe = build_reference_shaped_caller(str(tmp_path))
@@ -100,7 +101,7 @@ def test_entry_point_outputs_match_the_oracle(mode, data_dir, pkg, O, golden_out
     if mode < 2:
         K = 128 if mode == 0 else 256
         got = got.reshape(1, 16, 16, K)
-        assert (got[:, _ring(), :] == 0).all()
+        assert (got[:, ring_mask(), :] == 0).all()
         got = got[:, 1:15, 1:15, :]
     assert O.rel_error(got.reshape(want.shape), want) < TIGHT
 
@@ -217,8 +218,8 @@ def test_graph_captured_before_the_scratch_grew_still_replays(pkg, O, torch_dev,
     torch, dev = torch_dev
     rng = np.random.RandomState(91)
     N, C, K = 40, 64, 64
-    x, w, s, b = _rand_layer(rng, N, C, K)
-    xt, wt, st, bt = (_t(torch_dev, a) for a in (x, w, s, b))
+    x, w, s, b = rand_layer(rng, N, C, K)
+    xt, wt, st, bt = (to_dev(torch_dev, a) for a in (x, w, s, b))
     U = pkg.filter_transform_f2(wt)
     knobs.set("WINO_3X3_ALGO", "big")
     knobs.set("WINO_SK_GRID", "56")                  # everything is stream-K tail: the slabs are in use
@@ -236,7 +237,7 @@ def test_graph_captured_before_the_scratch_grew_still_replays(pkg, O, torch_dev,
     N2, C2, K2 = 700, 64, 64
     x2 = (torch.rand(N2, 16, 16, C2, device=dev) - 0.5)
     w2 = (rng.rand(K2, C2, 3, 3) - 0.5).astype(np.float32)
-    U2 = pkg.filter_transform_f2(_t(torch_dev, w2))
+    U2 = pkg.filter_transform_f2(to_dev(torch_dev, w2))
     with torch.cuda.stream(sg):
         big = pkg.conv3x3_bn_relu(x2, U2, bt, st)
     sg.synchronize()
@@ -268,7 +269,7 @@ def test_residual_block_prepare_then_capture(pkg, O, torch_dev):
     w2 = ((rng.rand(Cm, Cm, 3, 3) - 0.5) / np.sqrt(9 * Cm) * 4).astype(np.float32)
     w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
     bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4)]
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     bnt = [(t(a), t(b)) for a, b in bn]
     xt, w1t, w3t, U2 = t(x), t(w1), t(w3), pkg.filter_transform_f2(t(w2))
     sg = torch.cuda.Stream()

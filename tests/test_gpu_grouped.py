@@ -5,37 +5,17 @@ The oracle is F.conv2d(..., groups=G) in fp64 on the CPU with BN and the ReLU ap
 conv sits at 2-4e-7 from it at these shapes, and the bar is the project's layer bar, max |diff| / max |want| < 2e-5.
 Every layer and block tensor lives on a guarded arena (tests/guarded.py) at both placements of guarded.ALIGNS, and
 arena.check runs after every case: no guard word written, every input equal to its master bit for bit."""
-import importlib
-
 import pytest
 
 import guarded
+from gpu_support import R, network_graph_scenario, rel, torch_dev  # noqa: F401
+from reference_nets import NET_TOL, check_net, random_state_dict, reference_forward
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 2e-5
-NET_TOL = 1e-3
 CGS = (4, 8, 16, 32, 64)
 MAPS = ((1, 1), (2, 3), (7, 5), (9, 8))       # 9 x 8: stride 2 clips an odd and an even edge
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def R(pkg):
-    return importlib.import_module("cuda_winograd_amd.resnet")
-
-
-def _rel(torch, got, want):
-    got = got.detach().cpu().double()
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert not torch.isnan(got).any()
-    return float((got - want).abs().max() / want.abs().max())
 
 
 # ---------------------------------------------------------------------------------------------------- the layer
@@ -85,7 +65,7 @@ def _layer_case(pkg, torch_dev, N, Hin, Win, C, Cg, stride, relu, align):
     x, w, bias, scale = _layer_inputs(torch, N, Hin, Win, C, Cg, seed=1000 * Hin + 10 * Win + Cg + stride)
     got = _run_layer(pkg, torch_dev, x, w, bias, scale, C // Cg, stride, relu, align, tag)
     want = _layer_reference(torch, x, w, bias, scale, C // Cg, stride, relu)
-    err = _rel(torch, got, want)
+    err = rel(torch, got, want)
     assert err < TIGHT, (tag, err)
     return want
 
@@ -131,7 +111,7 @@ def test_one_hot_weights_do_not_leak_across_groups(Cg, pkg, torch_dev):
             inside[grp * Cg:(grp + 1) * Cg] = True
             act = torch.relu(bias) if relu else bias
             assert torch.equal(got[..., ~inside], act[~inside].expand_as(got[..., ~inside])), tag
-            assert _rel(torch, got[..., inside], want[..., inside]) < TIGHT, tag
+            assert rel(torch, got[..., inside], want[..., inside]) < TIGHT, tag
             assert float((want[..., inside] - act[inside].double()).abs().max()) > 0.05, tag   # the tap does something
 
 
@@ -267,73 +247,14 @@ def test_blocks_match_fp64(Hin, Win, stride, forced, pkg, knobs, torch_dev):
     for align in guarded.ALIGNS:
         got = _run_blocks(pkg, torch_dev, blk, stride, align, f"blocks {Hin}x{Win} s={stride} forced={forced} align={align}")
         for name in want:
-            err = _rel(torch, got[name], want[name])
+            err = rel(torch, got[name], want[name])
             assert err < TIGHT, (name, Hin, Win, stride, align, err)
             assert 0.1 < float((want[name] > 0).double().mean()) < 1.0      # both sides of the final ReLU
     assert pkg.tickets_in_use() == 0
 
 
+
 # ---------------------------------------------------------------------------------------------------- the networks
-def random_state_dict(torch, R, arch, classes=1000, seed=0):
-    """torchvision-format weights with O(1) activations: He-scaled convs (fan-in of the group), BN near identity, and a
-    small gamma on each block's last BN so that the residual sums stay O(1) over many blocks."""
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    last = "bn3" if R.ARCHS[arch][0] else "bn2"
-    for k, shape in R.expected_keys(arch, classes).items():
-        if k.endswith(".weight") and len(shape) == 4:
-            sd[k] = torch.randn(shape, generator=g) * (2.0 / (shape[1] * shape[2] * shape[3])) ** 0.5
-        elif k.endswith("running_mean"):
-            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
-        elif k.endswith("running_var"):
-            sd[k] = torch.rand(shape, generator=g) + 0.5
-            sd[k[: -len("running_var")] + "num_batches_tracked"] = torch.tensor(100)
-        elif k.endswith(".weight") and len(shape) == 1:
-            sd[k] = (torch.rand(shape, generator=g) + 0.5) * (0.2 if k.split(".")[-2] == last and k.startswith("layer") else 1.0)
-        elif k == "fc.weight":
-            sd[k] = torch.randn(shape, generator=g) * (1.0 / shape[1]) ** 0.5
-        elif k == "fc.bias":
-            sd[k] = torch.rand(shape, generator=g) - 0.5
-        else:
-            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
-    return sd
-
-
-def reference_forward(torch, sd, x, eps=1e-5):
-    """fp64 CPU forward of a torchvision ResNet / ResNeXt / Wide ResNet in eval mode, read off the state dict alone:
-    a block is a bottleneck when it has a conv3, its groups are conv2's out / in channel ratio, the stride sits on the
-    3x3 (or, in a basic block, on conv1).  Returns (logits, {stage: NHWC})."""
-    F = torch.nn.functional
-    d = {k: v.double() for k, v in sd.items()}
-
-    def bn(t, p):
-        return F.batch_norm(t, d[p + ".running_mean"], d[p + ".running_var"], d[p + ".weight"], d[p + ".bias"],
-                            False, 0.0, eps)
-
-    t = F.max_pool2d(torch.relu(bn(F.conv2d(x.double(), d["conv1.weight"], stride=2, padding=3), "bn1")), 3, 2, 1)
-    stages = {"stem": t.permute(0, 2, 3, 1)}
-    for L in range(1, 5):
-        b = 0
-        while f"layer{L}.{b}.conv1.weight" in d:
-            p = f"layer{L}.{b}"
-            s = 2 if (b == 0 and L > 1) else 1
-            if p + ".conv3.weight" in d:
-                w2 = d[p + ".conv2.weight"]
-                y = torch.relu(bn(F.conv2d(t, d[p + ".conv1.weight"]), p + ".bn1"))
-                y = torch.relu(bn(F.conv2d(y, w2, stride=s, padding=1, groups=w2.shape[0] // w2.shape[1]), p + ".bn2"))
-                y = bn(F.conv2d(y, d[p + ".conv3.weight"]), p + ".bn3")
-            else:
-                y = torch.relu(bn(F.conv2d(t, d[p + ".conv1.weight"], stride=s, padding=1), p + ".bn1"))
-                y = bn(F.conv2d(y, d[p + ".conv2.weight"], padding=1), p + ".bn2")
-            sc = t
-            if p + ".downsample.0.weight" in d:
-                sc = bn(F.conv2d(t, d[p + ".downsample.0.weight"], stride=s), p + ".downsample.1")
-            t = torch.relu(y + sc)
-            b += 1
-        stages[f"layer{L}"] = t.permute(0, 2, 3, 1)
-    return t.mean(dim=(2, 3)) @ d["fc.weight"].t() + d["fc.bias"], stages
-
-
 def _input(torch, dev, N, H, W, seed):
     return (torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(seed)) * 2 - 1).to(dev)
 
@@ -349,13 +270,7 @@ def test_network_matches_fp64(arch, N, H, pkg, R, torch_dev):
     else:
         assert kinds == {"proj", "proj_v15", "residual"}, kinds
     x = _input(torch, dev, N, H, H, seed=N + H)
-    logits, stages = model.forward(x, return_stages=True)
-    torch.cuda.synchronize()
-    want_logits, want = reference_forward(torch, sd, x.cpu())
-    errs = {name: _rel(torch, stages[name], want[name]) for name in want}
-    errs["logits"] = _rel(torch, logits, want_logits)
-    print(f"{arch} N={N} {H}x{H}: " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
-    assert not {k: v for k, v in errs.items() if not v < NET_TOL}, errs
+    check_net(torch, model, sd, arch, x)
     assert pkg.tickets_in_use() == 0
 
 
@@ -365,22 +280,9 @@ def test_resnext50_graph_replay_is_bitwise_eager(pkg, R, torch_dev):
     sd = random_state_dict(torch, R, arch, classes=10, seed=50)
     model = pkg.ResNet.from_state_dict(sd, arch)
     x = _input(torch, dev, N, H, W, seed=9)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        model.prepare(N, H, W)
-        eager = model(x).clone()
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        out = model(x)
-    out.fill_(float("nan"))
-    graph.replay()
-    torch.cuda.synchronize()
-    assert torch.equal(out, eager)
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
+    eager, graph = network_graph_scenario(pkg, torch, model, x, rounds=1)
     want, _ = reference_forward(torch, sd, x.cpu())
-    assert _rel(torch, eager, want) < NET_TOL
+    assert rel(torch, eager, want) < NET_TOL
     del graph
 
 
@@ -399,5 +301,5 @@ def test_existing_archs_have_not_moved(arch, pkg, R, torch_dev):
     logits = model(x)
     torch.cuda.synchronize()
     want, _ = reference_forward(torch, sd, x.cpu())
-    assert _rel(torch, logits, want) < NET_TOL
+    assert rel(torch, logits, want) < NET_TOL
     assert pkg.tickets_in_use() == 0

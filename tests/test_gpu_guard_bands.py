@@ -4,7 +4,7 @@ runs at both placements (256-byte aligned, and 16 mod 256: the weakest pointer w
 with its fp64 reference at TIGHT, and ends in arena.check: no guard touched, no read-only operand written.
 
 Covered here: the pack and filter-transform entry points at their smallest legal shape, a ResNet stage shape and
-K = 64 x odd with the smallest C (through their consumers' sweep cases, tests/test_gpu_shape_sweeps.py, where no index
+K = 64 x odd with the smallest C (through their consumers' sweep cases, tests/sweep_cases.py, where no index
 function is exported); conv1x1_bn_ex in every operand form x launch form; residual_block(_hw); the F(4x4) compatibility
 path; the direct comparators; and that every *_workspace_bytes* query is exercised at exactly its size somewhere.
 
@@ -21,18 +21,11 @@ import pytest
 
 import guarded as G
 import shape_sweeps as S
-import test_gpu_shape_sweeps as SW
+import sweep_cases as SC
+from cases import TIGHT
+from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-TIGHT = 2e-5
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
 
 
 @contextlib.contextmanager
@@ -131,37 +124,37 @@ def _case(entry, shape, **flags):
 # exactly *_elems floats between guards, the consumer reads it from a guarded address; fp64 reference at TIGHT)
 PACK_CASES = [
     # filter_pack_s2 + s2_proj_pack_kernel -> conv3x3_s2_proj
-    (SW._s2_proj_case, _case("conv3x3_s2_proj", {"N": 1, "Hin": 2, "Win": 2, "C": 32, "K": 64}, nonneg=False)),
-    (SW._s2_proj_case, _case("conv3x3_s2_proj", {"N": 1, "Hin": 56, "Win": 56, "C": 64, "K": 128}, nonneg=True)),
-    (SW._s2_proj_case, _case("conv3x3_s2_proj", {"N": 2, "Hin": 9, "Win": 7, "C": 32, "K": 192}, nonneg=False)),
+    (SC.s2_proj_case, _case("conv3x3_s2_proj", {"N": 1, "Hin": 2, "Win": 2, "C": 32, "K": 64}, nonneg=False)),
+    (SC.s2_proj_case, _case("conv3x3_s2_proj", {"N": 1, "Hin": 56, "Win": 56, "C": 64, "K": 128}, nonneg=True)),
+    (SC.s2_proj_case, _case("conv3x3_s2_proj", {"N": 2, "Hin": 9, "Win": 7, "C": 32, "K": 192}, nonneg=False)),
     # filter_pack_s2 alone -> conv3x3_s2_bn_relu
-    (SW._s2_case, _case("conv3x3_s2_bn_relu", {"N": 1, "Hin": 1, "Win": 1, "C": 32, "K": 64}, nonneg=False, relu=False)),
-    (SW._s2_case, _case("conv3x3_s2_bn_relu", {"N": 2, "Hin": 28, "Win": 28, "C": 128, "K": 256}, nonneg=True, relu=True)),
-    (SW._s2_case, _case("conv3x3_s2_bn_relu", {"N": 3, "Hin": 5, "Win": 11, "C": 32, "K": 320}, nonneg=False, relu=True)),
+    (SC.s2_case, _case("conv3x3_s2_bn_relu", {"N": 1, "Hin": 1, "Win": 1, "C": 32, "K": 64}, nonneg=False, relu=False)),
+    (SC.s2_case, _case("conv3x3_s2_bn_relu", {"N": 2, "Hin": 28, "Win": 28, "C": 128, "K": 256}, nonneg=True, relu=True)),
+    (SC.s2_case, _case("conv3x3_s2_bn_relu", {"N": 3, "Hin": 5, "Win": 11, "C": 32, "K": 320}, nonneg=False, relu=True)),
     # proj_tail_pack_kernel -> proj_block
-    (SW._proj_case, _case("proj_block", {"N": 1, "Hin": 1, "Win": 1, "Cin": 32, "Cm": 64, "C4": 64, "stride": 1},
+    (SC.proj_case, _case("proj_block", {"N": 1, "Hin": 1, "Win": 1, "Cin": 32, "Cm": 64, "C4": 64, "stride": 1},
                           nonneg=False)),
-    (SW._proj_case, _case("proj_block", {"N": 1, "Hin": 56, "Win": 56, "Cin": 64, "Cm": 64, "C4": 256, "stride": 1},
+    (SC.proj_case, _case("proj_block", {"N": 1, "Hin": 56, "Win": 56, "Cin": 64, "Cm": 64, "C4": 256, "stride": 1},
                           nonneg=True)),
-    (SW._proj_case, _case("proj_block", {"N": 2, "Hin": 5, "Win": 7, "Cin": 32, "Cm": 64, "C4": 192, "stride": 2},
+    (SC.proj_case, _case("proj_block", {"N": 2, "Hin": 5, "Win": 7, "Cin": 32, "Cm": 64, "C4": 192, "stride": 2},
                           nonneg=False)),
     # stem_pack_kernel -> stem
-    (SW._stem_case, _case("stem", {"N": 1, "H": 1, "W": 1, "K": 64}, padded=False)),
-    (SW._stem_case, _case("stem", {"N": 1, "H": 224, "W": 224, "K": 64}, padded=True)),
-    (SW._stem_case, _case("stem", {"N": 2, "H": 9, "W": 11, "K": 192}, padded=False)),
+    (SC.stem_case, _case("stem", {"N": 1, "H": 1, "W": 1, "K": 64}, padded=False)),
+    (SC.stem_case, _case("stem", {"N": 1, "H": 224, "W": 224, "K": 64}, padded=True)),
+    (SC.stem_case, _case("stem", {"N": 2, "H": 9, "W": 11, "K": 192}, padded=False)),
     # head_pack_kernel -> avgpool_fc
-    (SW._head_case, _case("avgpool_fc", {"N": 1, "H": 1, "W": 1, "C": 32, "classes": 1}, padded=False)),
-    (SW._head_case, _case("avgpool_fc", {"N": 2, "H": 7, "W": 7, "C": 512, "classes": 1000}, padded=True)),
-    (SW._head_case, _case("avgpool_fc", {"N": 3, "H": 2, "W": 3, "C": 32, "classes": 192}, padded=False)),
+    (SC.head_case, _case("avgpool_fc", {"N": 1, "H": 1, "W": 1, "C": 32, "classes": 1}, padded=False)),
+    (SC.head_case, _case("avgpool_fc", {"N": 2, "H": 7, "W": 7, "C": 512, "classes": 1000}, padded=True)),
+    (SC.head_case, _case("avgpool_fc", {"N": 3, "H": 2, "W": 3, "C": 32, "classes": 192}, padded=False)),
 ]
 
 
 @pytest.mark.parametrize("run,case", PACK_CASES, ids=[c.tag() for _, c in PACK_CASES])
 def test_pack_kernels_through_their_consumers(run, case, pkg, knobs, torch_dev):
     assert S.macs(case) <= S.MAX_MACS
-    before = SW.CHECKS[case.entry]
+    before = SC.CHECKS[case.entry]
     run(pkg, knobs, torch_dev, case, 4000 + len(case.tag()))
-    assert SW.CHECKS[case.entry] - before == 2, "both placements were checked"
+    assert SC.CHECKS[case.entry] - before == 2, "both placements were checked"
 
 
 def test_filter_pack_s2_layout(pkg, torch_dev):
@@ -410,17 +403,17 @@ def test_every_workspace_query_has_a_guarded_run(pkg, knobs, O, torch_dev):
         "wino_residual_block_workspace_bytes": lambda: test_residual_block_between_guards(1, 14, 14, {}, pkg, knobs, torch_dev),
         "wino_residual_block_workspace_bytes_hw": lambda: test_residual_block_between_guards(1, 7, 9, {}, pkg, knobs, torch_dev),
         "wino_conv3x3_f4_workspace_bytes": lambda: test_f4_compat_path_between_guards(1, pkg, O, torch_dev),
-        "wino_basic_block_workspace_bytes_hw": lambda: SW._basic_block_case(
+        "wino_basic_block_workspace_bytes_hw": lambda: SC.basic_block_case(
             pkg, knobs, torch_dev, _case("basic_block", {"N": 1, "H": 2, "W": 3, "C": 64}, in_place=False, nonneg=False), 1),
-        "wino_basic_block_s2_workspace_bytes_hw": lambda: SW._basic_block_s2_case(
+        "wino_basic_block_s2_workspace_bytes_hw": lambda: SC.basic_block_s2_case(
             pkg, knobs, torch_dev, _case("basic_block_s2", {"N": 1, "Hin": 3, "Win": 4, "C": 32, "K": 64}, nonneg=False), 2),
-        "wino_proj_block_workspace_bytes_hw": lambda: SW._proj_case(
+        "wino_proj_block_workspace_bytes_hw": lambda: SC.proj_case(
             pkg, knobs, torch_dev, _case("proj_block", {"N": 1, "Hin": 2, "Win": 3, "Cin": 32, "Cm": 64, "C4": 64, "stride": 1},
                                          nonneg=False), 3),
-        "wino_proj_block_v15_workspace_bytes_hw": lambda: SW._v15_case(
+        "wino_proj_block_v15_workspace_bytes_hw": lambda: SC.v15_case(
             pkg, knobs, torch_dev, _case("proj_block_v15", {"N": 1, "Hin": 3, "Win": 2, "Cin": 32, "Cm": 64, "C4": 64},
                                          nonneg=False), 4),
-        "wino_head_workspace_bytes": lambda: SW._head_case(
+        "wino_head_workspace_bytes": lambda: SC.head_case(
             pkg, knobs, torch_dev, _case("avgpool_fc", {"N": 2, "H": 1, "W": 2, "C": 32, "classes": 5}, padded=False), 5),
     }
     queries = {s for s in pkg.ABI_SYMBOLS if "workspace_bytes" in s}

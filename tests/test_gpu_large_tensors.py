@@ -18,17 +18,11 @@ import types
 import numpy as np
 import pytest
 
-from test_gpu_basic_block import _Block as _BasicBlock
-from test_gpu_basic_block import _Layer as _ResLayer
-from test_gpu_basic_block_s2 import _Block as _S2Block
-from test_gpu_conv3x3_s2 import _Layer as _S2Layer
-from test_gpu_proj_block import _oracle as _proj_oracle
-from test_gpu_proj_block import _weights as _proj_weights
-from test_gpu_proj_block_v15 import _Block as _V15Block
+from cases import TIGHT, BasicBlock, ResLayer, S2Block, S2Layer, V15Block, proj_oracle, proj_weights, ring_zero
+from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-TIGHT = 2e-5
 GIB = 1 << 30
 NAN = float("nan")
 
@@ -37,13 +31,6 @@ FORMS_1X1 = {
     "tiled": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 0},
     "stream_k": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1},
 }
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
 
 
 @pytest.fixture
@@ -106,10 +93,6 @@ def _finite(torch, t):
     return all(bool(torch.isfinite(t[i:i + step]).all()) for i in range(0, t.shape[0], step))
 
 
-def _ring_zero(t):
-    return all(bool((r == 0).all()) for r in (t[:, 0], t[:, -1], t[:, :, 0], t[:, :, -1]))
-
-
 def _pick(torch, t, idx):
     return t[torch.as_tensor(idx, device=t.device)].cpu()
 
@@ -117,7 +100,7 @@ def _pick(torch, t, idx):
 def _check_padded(O, torch, out, idx, want, name=""):
     """out [N][H+2][W+2][K] on the GPU: finite, zero ring, the images idx against want [n][H][W][K]."""
     assert _finite(torch, out), name
-    assert _ring_zero(out), name
+    assert ring_zero(out), name
     got = _pick(torch, out, idx)
     assert O.rel_error(got[:, 1:-1, 1:-1, :].numpy(), want) < TIGHT, name
     return got
@@ -150,7 +133,7 @@ def test_residual_3x3_beyond_4gib(form, in_place, pkg, O, torch_dev, knobs, free
     res = _padded_rand(torch, dev, N, H, H, C, 73)
     ref = types.SimpleNamespace(torch=torch, x=_pick(torch, x, idx), res=_pick(torch, res, idx), w=w, bias=bias,
                                 scale=scale)
-    want = _ResLayer.reference(ref, relu=True)
+    want = ResLayer.reference(ref, relu=True)
     out = res if in_place else torch.empty_like(x)
     first = None
     for rep in range(2):
@@ -185,7 +168,7 @@ def test_basic_block_beyond_4gib(pkg, O, torch_dev, free_after):
     bnt = [(b.to(dev), s.to(dev)) for b, s in bn]
     x = _padded_rand(torch, dev, N, H, H, C, 82)
     x_idx = _pick(torch, x, idx)
-    want = _BasicBlock.reference(types.SimpleNamespace(torch=torch, w=ws_, bn=bn), x_idx)
+    want = BasicBlock.reference(types.SimpleNamespace(torch=torch, w=ws_, bn=bn), x_idx)
     need = pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, H, C)
     assert need == N * P
     out = torch.empty_like(x)
@@ -198,7 +181,7 @@ def test_basic_block_beyond_4gib(pkg, O, torch_dev, free_after):
         torch.cuda.synchronize()
         assert pkg.tickets_in_use() == 0
         g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
-        assert _finite(torch, ws.view(N, H + 2, H + 2, C)) and _ring_zero(ws.view(N, H + 2, H + 2, C))
+        assert _finite(torch, ws.view(N, H + 2, H + 2, C)) and ring_zero(ws.view(N, H + 2, H + 2, C))
         if first is None:
             first = g_idx
         assert torch.equal(g_idx, first)
@@ -280,7 +263,7 @@ def test_conv3x3_s2_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
     taps, bt, st = pkg.filter_pack_s2(w.to(dev)), bias.to(dev), scale.to(dev)
     x = _padded_rand(torch, dev, N, Hin, Hin, C, 102)
     ref = types.SimpleNamespace(torch=torch, x=_pick(torch, x, idx), w=w, bias=bias, scale=scale)
-    want = _S2Layer.reference(ref)
+    want = S2Layer.reference(ref)
     out = torch.empty(N, H + 2, H + 2, K, device=dev)
     first = None
     for rep in range(2):
@@ -320,7 +303,7 @@ def test_downsampling_block_beyond_4gib(form, pkg, O, torch_dev, knobs, free_aft
     U2, bn2 = pkg.filter_transform_f2(t(ref.w2)), (t(ref.b2), t(ref.s2))
     x = _padded_rand(torch, dev, N, Hin, Hin, C, 112)
     ref.x = _pick(torch, x, idx)
-    want_t1, want_sc, want = _S2Block.reference(ref)
+    want_t1, want_sc, want = S2Block.reference(ref)
     # the fused layer alone: t1 as the plain stride-2 layer writes it, sc's interior (its ring is not touched)
     t1 = torch.empty(N, H + 2, H + 2, K, device=dev)
     sc = torch.empty_like(t1)
@@ -380,13 +363,13 @@ def test_proj_block_beyond_4gib(stride, form, pkg, O, torch_dev, knobs, free_aft
     _set(knobs, FORMS_1X1[form])
     idx = _images(N, [Px, Pout, Pt])
     rng = np.random.RandomState(121 + stride)
-    w1, w2, w3, wp, bn = _proj_weights(rng, Cin, Cm, C4)
+    w1, w2, w3, wp, bn = proj_weights(rng, Cin, Cm, C4)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
     bnt = [(t(b), t(s)) for b, s in bn]
     U2 = pkg.filter_transform_f2(t(w2))
     tail = pkg.proj_tail_pack(t(w3), bnt[2], t(wp), bnt[3])
     x = _rand(torch, dev, (N, Hin, Hin, Cin), 122)
-    want = _proj_oracle(O, _pick(torch, x, idx).numpy(), stride, w1, w2, w3, wp, bn)
+    want = proj_oracle(O, _pick(torch, x, idx).numpy(), stride, w1, w2, w3, wp, bn)
     out = torch.empty(N, H, H, C4, device=dev)
     ws = torch.empty(need // 4, device=dev)
     first = None
@@ -398,7 +381,7 @@ def test_proj_block_beyond_4gib(stride, form, pkg, O, torch_dev, knobs, free_aft
         assert pkg.tickets_in_use() == 0
         assert _finite(torch, out)
         t12 = ws.view(2 * N, H + 2, H + 2, Cm)
-        assert _finite(torch, t12) and _ring_zero(t12)
+        assert _finite(torch, t12) and ring_zero(t12)
         g_idx = _pick(torch, out, idx)
         assert O.rel_error(g_idx.numpy(), want) < TIGHT, rep
         if first is None:
@@ -432,7 +415,7 @@ def test_proj_block_v15_beyond_4gib(pkg, O, torch_dev, free_after):
     tail = pkg.proj_tail_pack(t(ref.w3), bnt[2], t(ref.wp), bnt[3])
     x = _rand(torch, dev, (N, Hin, Hin, Cin), 132)
     ref.x = _pick(torch, x, idx)
-    want = _V15Block.reference(ref)
+    want = V15Block.reference(ref)
     out = torch.empty(N, H, H, C4, device=dev)
     ws = torch.empty(need // 4, device=dev)
     first = None
@@ -483,7 +466,7 @@ def test_residual_block_beyond_4gib(pkg, O, torch_dev, free_after):
         assert pkg.tickets_in_use() == 0
         assert _finite(torch, out)
         t12 = ws.view(2 * N, H + 2, H + 2, Cm)
-        assert _finite(torch, t12) and _ring_zero(t12)
+        assert _finite(torch, t12) and ring_zero(t12)
         g_idx = _pick(torch, out, idx)
         assert O.rel_error(g_idx.numpy(), want) < TIGHT, rep
         if first is None:

@@ -6,24 +6,10 @@ import numpy as np
 import pytest
 
 import guarded as G
+from cases import TIGHT, ring_mask
+from gpu_support import dirty_ticket_scenario, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-TIGHT = 2e-5
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-def _ring():
-    r = np.ones((16, 16), bool)
-    r[1:15, 1:15] = False
-    return r
-
 
 def _layer(torch_dev, seed, N, C, K):
     torch, dev = torch_dev
@@ -69,7 +55,7 @@ def test_conv3x3_latency_forms_agree(N, C, K, pkg, O, torch_dev, knobs):
             got = out.cpu().numpy()
             assert not np.isnan(got).any(), (ct, sp)
             assert O.rel_error(got, want) < TIGHT, (ct, sp, O.rel_error(got, want))
-            assert (got[:, _ring(), :] == 0).all(), (ct, sp)
+            assert (got[:, ring_mask(), :] == 0).all(), (ct, sp)
             for _ in range(3):
                 assert torch.equal(pkg.conv3x3_bn_relu(xt, U, bt, st), out), (ct, sp)
             if ref is None:
@@ -365,42 +351,24 @@ def test_a_dirty_ticket_counter_is_reported_and_reset_recovers(kind, pkg, torch_
     torch, dev = torch_dev
     g = torch.Generator(device="cpu").manual_seed(31)
     mk = lambda *s: (torch.rand(*s, generator=g) - 0.5).to(dev)
-    stream = torch.cuda.Stream()
-    with torch.cuda.stream(stream):
-        if kind == "1x1":
-            knobs.set("WINO_1X1_ALGO", "big")
-            A, Bm, b, s = mk(2 * 196, 1024), mk(1024, 256), mk(256), mk(256)
-            run = lambda: pkg.conv1x1_bn(A, Bm, b, s, True)
-            n_tickets = 8
-        else:
-            N = {"3x3 throughput": 40, "3x3 latency": 1, "3x3 latency wide": 4}[kind]
-            if kind == "3x3 throughput":
-                knobs.set("WINO_3X3_ALGO", "big")
-                knobs.set("WINO_SK_GRID", "256")
-            x, w, s, b = mk(N, 16, 16, 256), mk(256, 256, 3, 3), mk(256), mk(256)
-            U = pkg.filter_transform_f2(w)
-            run = lambda: pkg.conv3x3_bn_relu(x, U, b, s)
-            if kind == "3x3 latency wide":
-                assert pkg.small_plan_3x3_full(N, 256, 256)[1:] == (2, 2, 2, 208)
-            n_tickets = {"3x3 latency": 64, "3x3 latency wide": 104}.get(kind, 8 * 4 * ((N * 49 + 63) // 64))
-        ref = run().clone()
-        assert pkg.tickets_in_use() == 0
-        pkg.stream_check()
-        # every counter the launch draws on is left one too high, as by a launch that never finished
-        for i in range(n_tickets):
-            pkg.poison_ticket(i, 1)
-        run()   # computes with dirty counters: its results are not to be trusted, and it must say so
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            pkg.stream_check()
-        with pytest.raises(pkg.WinoError, match="rc=-4"):
-            run()
-        pkg.stream_reset_scratch()
-        pkg.stream_check()
-        assert pkg.tickets_in_use() == 0
-        for _ in range(3):
-            assert torch.equal(run(), ref)
-        assert pkg.tickets_in_use() == 0
-    torch.cuda.synchronize()
+    if kind == "1x1":
+        knobs.set("WINO_1X1_ALGO", "big")
+        A, Bm, b, s = mk(2 * 196, 1024), mk(1024, 256), mk(256), mk(256)
+        run = lambda: pkg.conv1x1_bn(A, Bm, b, s, True)
+        n_tickets = 8
+    else:
+        N = {"3x3 throughput": 40, "3x3 latency": 1, "3x3 latency wide": 4}[kind]
+        if kind == "3x3 throughput":
+            knobs.set("WINO_3X3_ALGO", "big")
+            knobs.set("WINO_SK_GRID", "256")
+        x, w, s, b = mk(N, 16, 16, 256), mk(256, 256, 3, 3), mk(256), mk(256)
+        U = pkg.filter_transform_f2(w)
+        run = lambda: pkg.conv3x3_bn_relu(x, U, b, s)
+        if kind == "3x3 latency wide":
+            assert pkg.small_plan_3x3_full(N, 256, 256)[1:] == (2, 2, 2, 208)
+        n_tickets = {"3x3 latency": 64, "3x3 latency wide": 104}.get(kind, 8 * 4 * ((N * 49 + 63) // 64))
+    torch.cuda.synchronize()   # the operands were made on the current stream; the scenario runs on one of its own
+    dirty_ticket_scenario(pkg, torch, run, n_tickets, reruns=3)
 
 
 def test_in_kernel_clock_of_the_last_launch(pkg, torch_dev, knobs):

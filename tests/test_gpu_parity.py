@@ -2,8 +2,8 @@
 libwinograd_mi355x.so; the CPU oracle is only the checker.
 
 Tolerance: BASELINE.json's north_star asks for outputs within 1e-3 RELATIVE of the
-reference maths; `REL` below is that bar (max|got-want| / max|want|).  fp32 F(2x2,3x3) lands
-around 1e-6, so a much tighter `TIGHT` is asserted too to catch indexing slips that a loose
+reference maths; `REL` in tests/cases.py is that bar (max|got-want| / max|want|).  fp32 F(2x2,3x3) lands
+around 1e-6, so a much tighter `TIGHT` is what is asserted, to catch indexing slips that a loose
 bound would hide."""
 import ctypes
 import os
@@ -13,38 +13,11 @@ import numpy as np
 import pytest
 
 import guarded as G
+from cases import TIGHT, rand_layer, ring_mask, to_dev
 from conftest import ROOT, load_bin
+from gpu_support import graph_replay_scenario, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-REL = 1e-3
-TIGHT = 2e-5
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-def _t(torch_dev, a):
-    torch, dev = torch_dev
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _ring():
-    r = np.ones((16, 16), bool)
-    r[1:15, 1:15] = False
-    return r
-
-
-def _rand_layer(rng, N, C, K):
-    x = (rng.rand(N, 16, 16, C) - 0.5).astype(np.float32)
-    w = (rng.rand(K, C, 3, 3) - 0.5).astype(np.float32)
-    s = (rng.rand(K) - 0.5).astype(np.float32)
-    b = (rng.rand(K) - 0.5).astype(np.float32)
-    return x, w, s, b
 
 
 # ------------------------------------------------------------------ golden: Test-0 / Test-1
@@ -57,17 +30,17 @@ def test_reference_layers_match_golden(C, weights, data_dir, pkg, O, golden_outp
     b = load_bin(data_dir, f"bnBias_winograd_{C}.bin")
     if weights == "transform_f2":
         w = load_bin(data_dir, f"weight_NCHW_{C}_{C}.bin").reshape(C, C, 3, 3)
-        U = pkg.filter_transform_f2(_t(torch_dev, w))
+        U = pkg.filter_transform_f2(to_dev(torch_dev, w))
     else:  # the file the reference's custom path actually reads (Kernel128_winograd.cu:232)
         u36 = load_bin(data_dir, f"weight_winograd_{C}_{C}.bin").reshape(36, C, C)
-        U = pkg.filter_import_f4(_t(torch_dev, u36))
+        U = pkg.filter_import_f4(to_dev(torch_dev, u36))
     torch, _ = torch_dev
     out = torch.full((1, 16, 16, C), float("nan"), device="cuda:0")
-    pkg.conv3x3_bn_relu(_t(torch_dev, x), U, _t(torch_dev, b), _t(torch_dev, s), out=out)
+    pkg.conv3x3_bn_relu(to_dev(torch_dev, x), U, to_dev(torch_dev, b), to_dev(torch_dev, s), out=out)
     got = out.cpu().numpy()
     g = golden_outputs[f"kernel_{C}"]
     assert O.rel_error(got[0, 1:15, 1:15, :], g) < TIGHT
-    assert (got[0][_ring()] == 0).all(), "ring must be written as zero"
+    assert (got[0][ring_mask()] == 0).all(), "ring must be written as zero"
     max_err, cnt = O.output_checker(got[0], g, 14, C, 1)   # the reference's own check
     assert max_err < 1e-4 and cnt < 0.01 * g.size
 
@@ -83,16 +56,16 @@ def test_f4_compat_path_on_reference_files(C, data_dir, pkg, O, golden_outputs, 
     s = load_bin(data_dir, f"bnScale_winograd_{C}.bin")
     b = load_bin(data_dir, f"bnBias_winograd_{C}.bin")
     u36 = load_bin(data_dir, f"weight_winograd_{C}_{C}.bin").reshape(36, C, C)
-    got = pkg.conv3x3_f4_bn_relu(_t(torch_dev, x), _t(torch_dev, u36), _t(torch_dev, b), _t(torch_dev, s)).cpu().numpy()
+    got = pkg.conv3x3_f4_bn_relu(to_dev(torch_dev, x), to_dev(torch_dev, u36), to_dev(torch_dev, b), to_dev(torch_dev, s)).cpu().numpy()
     staged = O.winograd_f4_reference(x, u36, s, b)
     assert O.rel_error(got, staged) < 2e-5   # two fp32 pipelines, different summation order over C
     g = golden_outputs[f"kernel_{C}"]
     assert O.rel_error(got[0, 1:15, 1:15, :], g) < 1e-4          # F(4x4) in fp32: ~1e-5 (report section 5)
     max_err, cnt = O.output_checker(got[0], g, 14, C, 1)         # the reference's own check
     assert max_err < 1e-3
-    assert (got[0][_ring()] == 0).all()
-    f2 = pkg.conv3x3_bn_relu(_t(torch_dev, x), pkg.filter_import_f4(_t(torch_dev, u36)), _t(torch_dev, b),
-                             _t(torch_dev, s)).cpu().numpy()
+    assert (got[0][ring_mask()] == 0).all()
+    f2 = pkg.conv3x3_bn_relu(to_dev(torch_dev, x), pkg.filter_import_f4(to_dev(torch_dev, u36)), to_dev(torch_dev, b),
+                             to_dev(torch_dev, s)).cpu().numpy()
     assert O.rel_error(got, f2) < 1e-4
 
 
@@ -103,15 +76,15 @@ def test_f4_compat_path_batched(N, C, K, pkg, O, torch_dev):
     way (G g G^T in fp64, stored fp32).  K = 192 with C > 128: a column count that is a multiple of
     64 but not of 128 (the batched GEMM must take its 64-column form)."""
     rng = np.random.RandomState(91)
-    x, w, s, b = _rand_layer(rng, N, C, K)
+    x, w, s, b = rand_layer(rng, N, C, K)
     G = O.G_F4
     u36 = np.einsum('xr,kcrs,ys->xyck', G, w.astype(np.float64), G).reshape(36, C, K).astype(np.float32)
     for relu in (True, False):
-        got = pkg.conv3x3_f4_bn_relu(_t(torch_dev, x), _t(torch_dev, u36), _t(torch_dev, b), _t(torch_dev, s),
+        got = pkg.conv3x3_f4_bn_relu(to_dev(torch_dev, x), to_dev(torch_dev, u36), to_dev(torch_dev, b), to_dev(torch_dev, s),
                                      relu=relu).cpu().numpy()
         want = O.conv3x3_bn_relu_direct(x, w, s, b, relu=relu)
         assert O.rel_error(got, want) < 1e-4
-        assert (got[:, _ring(), :] == 0).all()
+        assert (got[:, ring_mask(), :] == 0).all()
 
 
 def test_filter_transforms_match_oracle(data_dir, pkg, O, torch_dev):
@@ -126,8 +99,8 @@ def test_filter_transforms_match_oracle(data_dir, pkg, O, torch_dev):
     # index of (e, c, k) -- vectorised from three probes per axis would hide bugs: call it for all
     idx = np.fromiter((L.wino_filter_f2_index(C, K, int(a), int(b), int(d))
                        for a, b, d in zip(e.ravel(), c.ravel(), k.ravel())), dtype=np.int64, count=e.size)
-    U1 = pkg.filter_transform_f2(_t(torch_dev, w)).cpu().numpy()
-    U2 = pkg.filter_import_f4(_t(torch_dev, u36)).cpu().numpy()
+    U1 = pkg.filter_transform_f2(to_dev(torch_dev, w)).cpu().numpy()
+    U2 = pkg.filter_import_f4(to_dev(torch_dev, u36)).cpu().numpy()
     assert np.array_equal(U1[idx], want.ravel())
     assert np.abs(U2[idx] - want.ravel()).max() < 2e-6       # taps recovered from fp32 F(4x4) weights
 
@@ -139,14 +112,14 @@ def test_conv3x3_vs_oracle(N, C, K, pkg, O, torch_dev):
     """N*49 tiles never divide the 64-tile workgroup block: partial blocks, blocks that
     straddle image boundaries, several k-blocks, smallest legal C."""
     rng = np.random.RandomState(100 + N)
-    x, w, s, b = _rand_layer(rng, N, C, K)
-    U = pkg.filter_transform_f2(_t(torch_dev, w))
+    x, w, s, b = rand_layer(rng, N, C, K)
+    U = pkg.filter_transform_f2(to_dev(torch_dev, w))
     for relu in (True, False):
-        got = pkg.conv3x3_bn_relu(_t(torch_dev, x), U, _t(torch_dev, b), _t(torch_dev, s), relu=relu)
+        got = pkg.conv3x3_bn_relu(to_dev(torch_dev, x), U, to_dev(torch_dev, b), to_dev(torch_dev, s), relu=relu)
         got = got.cpu().numpy()
         want = O.conv3x3_bn_relu_direct(x, w, s, b, relu=relu)
         assert O.rel_error(got, want) < TIGHT
-        assert (got[:, _ring(), :] == 0).all()
+        assert (got[:, ring_mask(), :] == 0).all()
 
 
 def test_conv3x3_full_size_properties(pkg, O, torch_dev):
@@ -156,8 +129,8 @@ def test_conv3x3_full_size_properties(pkg, O, torch_dev):
     torch, dev = torch_dev
     rng = np.random.RandomState(42)
     N, C, K = 128, 256, 256
-    x, w, s, b = _rand_layer(rng, N, C, K)
-    xt, wt, st, bt = (_t(torch_dev, a) for a in (x, w, s, b))
+    x, w, s, b = rand_layer(rng, N, C, K)
+    xt, wt, st, bt = (to_dev(torch_dev, a) for a in (x, w, s, b))
     U = pkg.filter_transform_f2(wt)
     out = pkg.conv3x3_bn_relu(xt, U, bt, st)
     got = out.cpu().numpy()
@@ -169,7 +142,7 @@ def test_conv3x3_full_size_properties(pkg, O, torch_dev):
     cmp_ = pkg.conv3x3_direct(xt, wt, bt, st).cpu().numpy()
     assert O.rel_error(got, cmp_) < TIGHT
     # (c1) ring
-    assert (got[:, _ring(), :] == 0).all()
+    assert (got[:, ring_mask(), :] == 0).all()
     # (c2) images are independent: a sub-batch gives the same values as the same images inside
     # the full batch (both run the throughput kernel; tile blocks straddle image boundaries
     # differently and the stream-K ranges cut the channel sums at different chunks in the two
@@ -224,8 +197,8 @@ def test_conv3x3_streamk_decompositions_agree(N, C, K, pkg, O, torch_dev, knobs)
     torch, dev = torch_dev
     knobs.set("WINO_3X3_ALGO", "big")
     rng = np.random.RandomState(5 + N)
-    x, w, s, b = _rand_layer(rng, N, C, K)
-    xt, wt, st, bt = (_t(torch_dev, a) for a in (x, w, s, b))
+    x, w, s, b = rand_layer(rng, N, C, K)
+    xt, wt, st, bt = (to_dev(torch_dev, a) for a in (x, w, s, b))
     U = pkg.filter_transform_f2(wt)
     knobs.unset("WINO_SK_GRID")
     ref = pkg.conv3x3_bn_relu(xt, U, bt, st).clone()
@@ -238,7 +211,7 @@ def test_conv3x3_streamk_decompositions_agree(N, C, K, pkg, O, torch_dev, knobs)
         c = pkg.conv3x3_bn_relu(xt, U, bt, st)
         assert torch.equal(a, c), f"grid {grid}: not reproducible"
         assert float((a - ref).abs().max()) < 2e-6 * scale, f"grid {grid}"
-        assert (a.cpu().numpy()[:, _ring(), :] == 0).all()
+        assert (a.cpu().numpy()[:, ring_mask(), :] == 0).all()
 
 
 @pytest.mark.parametrize("N,C,K,grids", [(128, 256, 256, (257, 300, 333, 391, 400)), (128, 64, 256, (300, 391)),
@@ -349,7 +322,7 @@ def test_conv3x3_other_feature_maps(N, H, W, C, K, pkg, O, torch_dev):
     w = (rng.rand(K, C, 3, 3) - 0.5).astype(np.float32)
     s = (rng.rand(K) - 0.5).astype(np.float32)
     b = (rng.rand(K) - 0.5).astype(np.float32)
-    xt, wt, st, bt = (_t(torch_dev, a) for a in (x, w, s, b))
+    xt, wt, st, bt = (to_dev(torch_dev, a) for a in (x, w, s, b))
     U = pkg.filter_transform_f2(wt)
     got_t = pkg.conv3x3_bn_relu(xt, U, bt, st)
     again = pkg.conv3x3_bn_relu(xt, U, bt, st)
@@ -408,8 +381,8 @@ def test_conv3x3_config2_128(pkg, O, torch_dev):
     """BASELINE configs[1]: 128->128, N=128, against the comparator + oracle sample."""
     rng = np.random.RandomState(43)
     N, C, K = 128, 128, 128
-    x, w, s, b = _rand_layer(rng, N, C, K)
-    xt, wt, st, bt = (_t(torch_dev, a) for a in (x, w, s, b))
+    x, w, s, b = rand_layer(rng, N, C, K)
+    xt, wt, st, bt = (to_dev(torch_dev, a) for a in (x, w, s, b))
     got = pkg.conv3x3_bn_relu(xt, pkg.filter_transform_f2(wt), bt, st).cpu().numpy()
     assert O.rel_error(got, pkg.conv3x3_direct(xt, wt, bt, st).cpu().numpy()) < TIGHT
     idx = [0, 31, 127]
@@ -418,8 +391,8 @@ def test_conv3x3_config2_128(pkg, O, torch_dev):
 
 def test_comparator_is_independent_and_correct(pkg, O, torch_dev):
     rng = np.random.RandomState(5)
-    x, w, s, b = _rand_layer(rng, 2, 32, 64)
-    got = pkg.conv3x3_direct(*(_t(torch_dev, a) for a in (x, w, b, s))).cpu().numpy()
+    x, w, s, b = rand_layer(rng, 2, 32, 64)
+    got = pkg.conv3x3_direct(*(to_dev(torch_dev, a) for a in (x, w, b, s))).cpu().numpy()
     assert O.rel_error(got, O.conv3x3_bn_relu_direct(x, w, s, b)) < TIGHT
 
 
@@ -432,10 +405,10 @@ def test_comparator_3x3_matches_golden(C, data_dir, pkg, O, golden_outputs, torc
     w = load_bin(data_dir, f"weight_NCHW_{C}_{C}.bin").reshape(C, C, 3, 3)
     s = load_bin(data_dir, f"bnScale_winograd_{C}.bin")
     b = load_bin(data_dir, f"bnBias_winograd_{C}.bin")
-    got = pkg.conv3x3_direct(*(_t(torch_dev, a) for a in (x, w, b, s))).cpu().numpy()
+    got = pkg.conv3x3_direct(*(to_dev(torch_dev, a) for a in (x, w, b, s))).cpu().numpy()
     want = golden_outputs["kernel_128" if C == 128 else "kernel_256"]
     assert O.rel_error(got[:, 1:15, 1:15, :].reshape(want.shape), want) < TIGHT
-    assert (got[:, _ring(), :] == 0).all()
+    assert (got[:, ring_mask(), :] == 0).all()
 
 
 @pytest.mark.parametrize("name", ["kernel_128_1_in", "kernel_128_1_out", "kernel_256_1_in", "kernel_256_1_out"])
@@ -445,7 +418,7 @@ def test_comparator_1x1_matches_golden(name, data_dir, pkg, O, golden_outputs, t
     B = load_bin(data_dir, "weight_one_1024.bin", Cin * Kout).reshape(Cin, Kout)
     s = load_bin(data_dir, "bnScale_myKernel_one_1024.bin", Kout)
     b = load_bin(data_dir, "bnBias_myKernel_one_1024.bin", Kout)
-    got = pkg.conv1x1_direct(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s), relu)
+    got = pkg.conv1x1_direct(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s), relu)
     assert O.rel_error(got.cpu().numpy(), golden_outputs[name]) < TIGHT
 
 
@@ -457,7 +430,7 @@ def test_one_by_one_golden(name, data_dir, pkg, O, golden_outputs, torch_dev):
     B = load_bin(data_dir, "weight_one_1024.bin", Cin * Kout).reshape(Cin, Kout)
     s = load_bin(data_dir, "bnScale_myKernel_one_1024.bin", Kout)
     b = load_bin(data_dir, "bnBias_myKernel_one_1024.bin", Kout)
-    got = pkg.conv1x1_bn(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s), relu)
+    got = pkg.conv1x1_bn(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s), relu)
     assert O.rel_error(got.cpu().numpy(), golden_outputs[name]) < TIGHT
 
 
@@ -470,7 +443,7 @@ def test_one_by_one_ragged_rows(M, pkg, O, torch_dev):
     s = (rng.rand(Kout) - 0.5).astype(np.float32)
     b = (rng.rand(Kout) - 0.5).astype(np.float32)
     for relu in (True, False):
-        got = pkg.conv1x1_bn(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s), relu)
+        got = pkg.conv1x1_bn(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s), relu)
         assert O.rel_error(got.cpu().numpy(), O.conv1x1_bn(A, B, b, s, relu)) < TIGHT
 
 
@@ -486,7 +459,7 @@ def test_one_by_one_column_counts(M, Cin, Kout, pkg, O, torch_dev):
     s = (rng.rand(Kout) - 0.5).astype(np.float32)
     b = ((rng.rand(Kout) - 0.5) * 4).astype(np.float32)
     out = torch.full((M, Kout), float("nan"), device=dev)
-    pkg.conv1x1_bn(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s), False, out=out)
+    pkg.conv1x1_bn(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s), False, out=out)
     got = out.cpu().numpy()
     assert np.isfinite(got).all()
     assert O.rel_error(got, O.conv1x1_bn(A, B, b, s, False)) < TIGHT
@@ -502,7 +475,7 @@ def test_one_by_one_full_size(name, pkg, O, torch_dev):
     B = ((rng.rand(Cin, Kout) - 0.5) * 40).astype(np.float32)
     s = ((rng.rand(Kout) - 0.5)).astype(np.float32)
     b = ((rng.rand(Kout) - 0.5) * 40).astype(np.float32)
-    At, Bt, bt, st = (_t(torch_dev, a) for a in (A, B, b, s))
+    At, Bt, bt, st = (to_dev(torch_dev, a) for a in (A, B, b, s))
     got = pkg.conv1x1_bn(At, Bt, bt, st, relu).cpu().numpy()
     assert O.rel_error(got, O.conv1x1_bn(A, B, b, s, relu)) < TIGHT
     assert O.rel_error(got, pkg.conv1x1_direct(At, Bt, bt, st, relu).cpu().numpy()) < TIGHT
@@ -522,7 +495,7 @@ def test_one_by_one_streamk_decompositions_agree(M, Cin, Kout, pkg, O, torch_dev
     B = ((rng.rand(Cin, Kout) - 0.5) * 4).astype(np.float32)
     s = (rng.rand(Kout) - 0.5).astype(np.float32)
     b = ((rng.rand(Kout) - 0.5) * 4).astype(np.float32)
-    At, Bt, bt, st = (_t(torch_dev, a) for a in (A, B, b, s))
+    At, Bt, bt, st = (to_dev(torch_dev, a) for a in (A, B, b, s))
     want = O.conv1x1_bn(A, B, b, s, True)
     knobs.set("WINO_1X1_SK", "0")
     knobs.unset("WINO_1X1_SK_GRID")
@@ -562,17 +535,17 @@ def test_one_by_one_streamk_flags_and_graph(pkg, O, torch_dev, knobs):
     for grid in ("24", "200"):
         knobs.set("WINO_1X1_SK_GRID", grid)
         out = torch.full((N, 16, 16, Kout), float("nan"), device=dev)
-        pkg.conv1x1_bn_ex(_t(torch_dev, Ap), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s),
+        pkg.conv1x1_bn_ex(to_dev(torch_dev, Ap), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s),
                           pkg.RELU | pkg.A_PADDED | pkg.C_PADDED, out=out)
         got = out.cpu().numpy()
         assert O.rel_error(got[:, 1:15, 1:15, :].reshape(-1, Kout), want) < TIGHT
-        assert (got[:, _ring(), :] == 0).all()
-        got3 = pkg.conv1x1_bn_ex(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s),
-                                 pkg.RELU | pkg.ADD_RESIDUAL, residual=_t(torch_dev, R)).cpu().numpy()
+        assert (got[:, ring_mask(), :] == 0).all()
+        got3 = pkg.conv1x1_bn_ex(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s),
+                                 pkg.RELU | pkg.ADD_RESIDUAL, residual=to_dev(torch_dev, R)).cpu().numpy()
         assert O.rel_error(got3, want_res) < TIGHT
     # graph capture on a side stream: scratch allocated by prepare, outside the capture
     knobs.set("WINO_1X1_SK_GRID", "200")
-    At, Bt, bt, st = (_t(torch_dev, a) for a in (A.reshape(-1, Cin), B, b, s))
+    At, Bt, bt, st = (to_dev(torch_dev, a) for a in (A.reshape(-1, Cin), B, b, s))
     outg = torch.zeros(N * 196, Kout, device=dev)
     sg = torch.cuda.Stream()
     with torch.cuda.stream(sg):
@@ -605,7 +578,7 @@ def test_one_by_one_activations_beyond_4gib(pkg, O, torch_dev):
     s = (rng.rand(Kout) - 0.5).astype(np.float32)
     b = (rng.rand(Kout) - 0.5).astype(np.float32)
     out = torch.full((M, Kout), float("nan"), device=dev)
-    pkg.conv1x1_bn(A, _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s), False, out=out)
+    pkg.conv1x1_bn(A, to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s), False, out=out)
     assert bool(torch.isfinite(out).all())
     boundary = (1 << 32) // (Cin * 4)
     rows = np.unique(np.concatenate([np.arange(0, 224), np.arange(boundary - 300, boundary + 300),
@@ -630,21 +603,21 @@ def test_conv1x1_padded_in_out_and_residual(pkg, O, torch_dev):
     want = O.conv1x1_bn(A.reshape(-1, Cin), B, b, s, True)
     # C_PADDED: result in the interior of [N][16][16][Kout], ring written as exact zeros
     out = torch.full((N, 16, 16, Kout), float("nan"), device=dev)
-    pkg.conv1x1_bn_ex(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s),
+    pkg.conv1x1_bn_ex(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s),
                       pkg.RELU | pkg.C_PADDED, out=out)
     got = out.cpu().numpy()
     assert O.rel_error(got[:, 1:15, 1:15, :].reshape(-1, Kout), want) < TIGHT
-    assert (got[:, _ring(), :] == 0).all()
+    assert (got[:, ring_mask(), :] == 0).all()
     # A_PADDED: read the interior of a padded tensor whose ring holds garbage that must be ignored
     Ap = rng.rand(N, 16, 16, Cin).astype(np.float32) * 100
     Ap[:, 1:15, 1:15, :] = A
-    got2 = pkg.conv1x1_bn_ex(_t(torch_dev, Ap), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s),
+    got2 = pkg.conv1x1_bn_ex(to_dev(torch_dev, Ap), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s),
                              pkg.RELU | pkg.A_PADDED).cpu().numpy()
     assert O.rel_error(got2, want) < TIGHT
     # ADD_RESIDUAL before the ReLU
     want3 = np.maximum(O.conv1x1_bn(A.reshape(-1, Cin), B, b, s, False) + R, 0)
-    got3 = pkg.conv1x1_bn_ex(_t(torch_dev, A), _t(torch_dev, B), _t(torch_dev, b), _t(torch_dev, s),
-                             pkg.RELU | pkg.ADD_RESIDUAL, residual=_t(torch_dev, R)).cpu().numpy()
+    got3 = pkg.conv1x1_bn_ex(to_dev(torch_dev, A), to_dev(torch_dev, B), to_dev(torch_dev, b), to_dev(torch_dev, s),
+                             pkg.RELU | pkg.ADD_RESIDUAL, residual=to_dev(torch_dev, R)).cpu().numpy()
     assert O.rel_error(got3, want3) < TIGHT
 
 
@@ -660,7 +633,7 @@ def test_conv1x1_padded_other_feature_maps(N, H, W, Cin, Kout, pkg, O, torch_dev
     s = (rng.rand(Kout) - 0.5).astype(np.float32)
     b = (rng.rand(Kout) - 0.5).astype(np.float32)
     R = (rng.rand(N * H * W, Kout) - 0.5).astype(np.float32)
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     want = O.conv1x1_bn(A.reshape(-1, Cin), B, b, s, True)
     out = torch.full((N, H + 2, W + 2, Kout), float("nan"), device=dev)
     pkg.conv1x1_bn_ex(t(A), t(B), t(b), t(s), pkg.RELU | pkg.C_PADDED, out=out)
@@ -693,7 +666,7 @@ def test_residual_block_other_feature_maps(N, H, W, C4, Cm, pkg, O, torch_dev):
     w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
     bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4)]
     want = O.residual_block(x, w1, bn[0], w2, bn[1], w3, bn[2])
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     U2 = pkg.filter_transform_f2(t(w2))
     got = pkg.residual_block(t(x), t(w1), (t(bn[0][0]), t(bn[0][1])), U2, (t(bn[1][0]), t(bn[1][1])),
                              t(w3), (t(bn[2][0]), t(bn[2][1]))).cpu().numpy()
@@ -713,7 +686,7 @@ def test_residual_block(N, C4, Cm, pkg, O, torch_dev):
     w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
     bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4)]
     want = O.residual_block(x, w1, bn[0], w2, bn[1], w3, bn[2])
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     U2 = pkg.filter_transform_f2(t(w2))
     got = pkg.residual_block(t(x), t(w1), (t(bn[0][0]), t(bn[0][1])), U2, (t(bn[1][0]), t(bn[1][1])),
                              t(w3), (t(bn[2][0]), t(bn[2][1]))).cpu().numpy()
@@ -736,7 +709,7 @@ def test_residual_block_config5_per_gpu_share(pkg, O, torch_dev):
     w2 = ((rng.rand(Cm, Cm, 3, 3) - 0.5) / np.sqrt(9 * Cm) * 4).astype(np.float32)
     w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
     bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4)]
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     bnt = [(t(a), t(b)) for a, b in bn]
     xt, w1t, w2t, w3t = t(x), t(w1), t(w2), t(w3)
     out = torch.full((N, 14, 14, C4), float("nan"), device=dev)
@@ -779,10 +752,10 @@ def test_conv3x3_batch_beyond_one_launch(pkg, O, torch_dev):
     w = (rng.rand(K, C, 3, 3) - 0.5).astype(np.float32)
     s = (rng.rand(K) - 0.5).astype(np.float32)
     b = (rng.rand(K) - 0.5).astype(np.float32)
-    U = pkg.filter_transform_f2(_t(torch_dev, w))
+    U = pkg.filter_transform_f2(to_dev(torch_dev, w))
     arena = G.Arena(torch, dev)
     out = arena.output(N, H + 2, W + 2, K, name="out")
-    pkg.conv3x3_bn_relu(x, U, _t(torch_dev, b), _t(torch_dev, s), relu=True, out=out)
+    pkg.conv3x3_bn_relu(x, U, to_dev(torch_dev, b), to_dev(torch_dev, s), relu=True, out=out)
     assert bool(torch.isfinite(out).all())
     ring = np.ones((H + 2, W + 2), bool)
     ring[1:-1, 1:-1] = False
@@ -804,7 +777,7 @@ def test_streamk_scratch_is_never_stale(pkg, O, torch_dev, knobs):
     order, and must be bitwise what the same input gave the time before."""
     torch, dev = torch_dev
     rng = np.random.RandomState(314)
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     # 1x1: many partial tiles per launch
     M, Cin, Kout = 9 * 196, 512, 256
     Bm = t((rng.rand(Cin, Kout) - 0.5).astype(np.float32))
@@ -855,7 +828,7 @@ def test_streams_created_and_destroyed_do_not_leak_scratch(pkg, O, torch_dev, kn
     B = ((rng.rand(Cin, Kout) - 0.5) * 4).astype(np.float32)
     s = (rng.rand(Kout) - 0.5).astype(np.float32)
     b = (rng.rand(Kout) - 0.5).astype(np.float32)
-    At, Bt, bt, st = (_t(torch_dev, a) for a in (A, B, b, s))
+    At, Bt, bt, st = (to_dev(torch_dev, a) for a in (A, B, b, s))
     out = torch.empty(M, Kout, device=dev)
     want = O.conv1x1_bn(A, B, b, s, True)
     knobs.set("WINO_1X1_SK", "1")
@@ -989,28 +962,22 @@ def test_residual_block_in_a_graph(pkg, O, torch_dev):
     w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
     bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4)]
     want = O.residual_block(x, w1, bn[0], w2, bn[1], w3, bn[2])
-    t = lambda a: _t(torch_dev, a)
+    t = lambda a: to_dev(torch_dev, a)
     xt, w1t, w3t = t(x), t(w1), t(w3)
     U2 = pkg.filter_transform_f2(t(w2))
     bnt = [(t(b), t(s)) for b, s in bn]
-    eager = pkg.residual_block(xt, w1t, bnt[0], U2, bnt[1], w3t, bnt[2]).clone()
-    assert O.rel_error(eager.cpu().numpy(), want) < TIGHT
-    out = torch.zeros_like(xt)
-    ws = torch.empty(pkg.lib().wino_residual_block_workspace_bytes(N, Cm) // 4, device=dev)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
+
+    def run(out=None, workspace=None):
+        return pkg.residual_block(xt, w1t, bnt[0], U2, bnt[1], w3t, bnt[2], out=out, workspace=workspace)
+
+    def prepare():
         pkg.conv1x1_prepare(N * 196, C4, Cm)
         pkg.conv3x3_prepare(N, Cm, Cm, 14, 14)
         pkg.conv1x1_prepare(N * 196, Cm, C4)
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        pkg.residual_block(xt, w1t, bnt[0], U2, bnt[1], w3t, bnt[2], out=out, workspace=ws)
-    for _ in range(3):
-        out.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, eager)
+
+    eager = graph_replay_scenario(pkg, torch_dev, run, prepare, pkg.lib().wino_residual_block_workspace_bytes(N, Cm),
+                                  rounds=3)
+    assert O.rel_error(eager.cpu().numpy(), want) < TIGHT
 
 
 # ------------------------------------------------------------------ errors

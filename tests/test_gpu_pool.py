@@ -14,19 +14,14 @@ import pytest
 
 import guarded as G
 import shape_sweeps as S
+from cases import ring_zero
+from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 TIGHT = 2e-5          # the project's asserted layer bar
 MAX_MACS = 3e8        # of one case's fp64 reference
 GIB = 1 << 30
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
 
 
 # form -> the knobs that force it (split / grid are filled in per shape)
@@ -127,10 +122,6 @@ def _rel(got, want):
     return float((got.double() - want).abs().max() / want.abs().max().clamp_min(1e-30))
 
 
-def _ring_zero(t):
-    return all(bool((r == 0).all()) for r in (t[:, 0], t[:, -1], t[:, :, 0], t[:, :, -1]))
-
-
 def run_case(pkg, knobs, torch_dev, form, sh, kn, flags, seed, exact):
     torch, dev = torch_dev
     import torch.nn.functional as F
@@ -157,7 +148,7 @@ def run_case(pkg, knobs, torch_dev, form, sh, kn, flags, seed, exact):
         assert pkg.tickets_in_use() == 0, tag
         o = out.cpu()
         assert not torch.isnan(o).any(), tag
-        assert _ring_zero(o), tag
+        assert ring_zero(o), tag
         err = _rel(o[:, 1:-1, 1:-1, :], want)
         print(f"{tag} rel {err:.2e}")
         worst = max(worst, err)
@@ -197,7 +188,7 @@ def test_pooled_layer_automatic_plan(pkg, knobs, torch_dev):
                                  arena.input(scale), True, out=out)
         arena.check(str(sh))
         assert pkg.tickets_in_use() == 0
-        assert _ring_zero(out) and _rel(out.cpu()[:, 1:-1, 1:-1, :], want) < TIGHT
+        assert ring_zero(out) and _rel(out.cpu()[:, 1:-1, 1:-1, :], want) < TIGHT
 
 
 @pytest.mark.parametrize("form", FORMS)
@@ -238,7 +229,7 @@ def test_pooled_layer_beyond_4gib(pkg, torch_dev):
     pkg.conv3x3_bn_relu_pool(x, pkg.filter_transform_f2(w.to(dev)), bias.to(dev), scale.to(dev), True, out=out)
     torch.cuda.synchronize()
     assert pkg.tickets_in_use() == 0
-    assert bool(torch.isfinite(out).all()) and _ring_zero(out)
+    assert bool(torch.isfinite(out).all()) and ring_zero(out)
     sel = torch.as_tensor(idx, device=dev)
     want = _reference(torch, x[sel].cpu(), w, bias, scale, True)
     assert _rel(out[sel].cpu()[:, 1:-1, 1:-1, :], want) < TIGHT

@@ -5,9 +5,10 @@ the layer oracles, the comparator kernels, and the four-launch composition the l
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from cases import PROJ_FORMS, TIGHT, proj_oracle, proj_weights
+from gpu_support import graph_replay_scenario, torch_dev  # noqa: F401
 
-TIGHT = 2e-5
+pytestmark = pytest.mark.gpu
 
 # ResNet-50's four stage-entry blocks: (Hin, Cin, Cm, C4, stride)
 STAGES = {
@@ -18,37 +19,6 @@ STAGES = {
 }
 
 
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-def _weights(rng, Cin, Cm, C4):
-    w1 = ((rng.rand(Cin, Cm) - 0.5) / np.sqrt(Cin) * 4).astype(np.float32)
-    w2 = ((rng.rand(Cm, Cm, 3, 3) - 0.5) / np.sqrt(9 * Cm) * 4).astype(np.float32)
-    w3 = ((rng.rand(Cm, C4) - 0.5) / np.sqrt(Cm) * 4).astype(np.float32)
-    wp = ((rng.rand(Cin, C4) - 0.5) / np.sqrt(Cin) * 2).astype(np.float32)
-    bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4, C4)]
-    return w1, w2, w3, wp, bn
-
-
-def _oracle(O, x, s, w1, w2, w3, wp, bn):
-    """fp64 composition of the layer oracles: xs = x[:, ::s, ::s], 1x1 + BN + ReLU, 3x3 (pad 1) + BN + ReLU,
-    1x1 + BN, + BN(xs . wp), ReLU."""
-    xs = np.asarray(x, np.float64)[:, ::s, ::s, :]
-    N, H, W, Cin = xs.shape
-    Cm = w1.shape[1]
-    t1 = O.conv1x1_bn(xs.reshape(-1, Cin), w1, bn[0][0], bn[0][1], True).reshape(N, H, W, Cm)
-    t1p = np.zeros((N, H + 2, W + 2, Cm))
-    t1p[:, 1:-1, 1:-1, :] = t1
-    t2 = O.conv3x3_bn_relu_direct(t1p, w2, bn[1][1], bn[1][0], True)[:, 1:-1, 1:-1, :]
-    t3 = O.conv1x1_bn(t2.reshape(-1, Cm), w3, bn[2][0], bn[2][1], False)
-    sc = O.conv1x1_bn(xs.reshape(-1, Cin), wp, bn[3][0], bn[3][1], False)
-    return np.maximum(t3 + sc, 0).reshape(N, H, W, -1)
-
-
 class _Block:
     """One block's tensors on the GPU, and the library's three ways to run it."""
 
@@ -57,7 +27,7 @@ class _Block:
         self.pkg, self.s = pkg, s
         rng = np.random.RandomState(seed)
         self.x = (rng.rand(N, Hin, Win, Cin) - 0.5).astype(np.float32)
-        self.w1, self.w2, self.w3, self.wp, self.bn = _weights(rng, Cin, Cm, C4)
+        self.w1, self.w2, self.w3, self.wp, self.bn = proj_weights(rng, Cin, Cm, C4)
         t = lambda a: self.torch.from_numpy(np.ascontiguousarray(a)).to(self.dev)
         self.xt, self.w1t, self.w2t, self.w3t, self.wpt = t(self.x), t(self.w1), t(self.w2), t(self.w3), t(self.wp)
         self.bnt = [(t(b), t(sc)) for b, sc in self.bn]
@@ -91,7 +61,7 @@ class _Block:
 
     def oracle(self, O, idx=None):
         x = self.x if idx is None else self.x[idx]
-        return _oracle(O, x, self.s, self.w1, self.w2, self.w3, self.wp, self.bn)
+        return proj_oracle(O, x, self.s, self.w1, self.w2, self.w3, self.wp, self.bn)
 
 
 def _check_block(blk, O, got, idx=None):
@@ -143,26 +113,12 @@ def test_conv4_block_at_128_images(pkg, O, torch_dev):
     assert O.rel_error(got.cpu().numpy(), chain.cpu().numpy()) < TIGHT
 
 
-# (knob settings) -> the forms both 1x1 launches are forced into
-FORMS = {
-    "latency": {"WINO_1X1_ALGO": "small"},
-    "latency_ks2": {"WINO_1X1_ALGO": "small", "WINO_1X1_SMALL_KS": 2},
-    "latency_ks4": {"WINO_1X1_ALGO": "small", "WINO_1X1_SMALL_KS": 4},
-    "tiled": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 0},
-    "stream_k": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1},
-    # ranges that do not line up with the tail's phase boundary (Cm/32 = 4 k-steps of t2, then 8 of x)
-    "split_24": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 24},
-    "split_40": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 40},
-    "split_104": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": 104},
-}
-
-
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("form", sorted(PROJ_FORMS))
 @pytest.mark.parametrize("N,Hin,Cin,Cm,C4,s", [(2, 28, 256, 128, 512, 2), (2, 14, 96, 64, 128, 1)])
 def test_forced_forms(form, N, Hin, Cin, Cm, C4, s, pkg, O, torch_dev, knobs):
     """Every form of both kernel families, including stream-K / split-K segments that start, end or straddle the
     fused tail's phase boundary; each against the oracle, and all forms against each other to tolerance."""
-    for k, v in FORMS[form].items():
+    for k, v in PROJ_FORMS[form].items():
         knobs.set(k, v)
     blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=N * Hin + Cin)
     _check_block(blk, O, blk.run())
@@ -201,24 +157,8 @@ def test_block_in_a_graph(stage, N, pkg, O, torch_dev):
     torch, dev = torch_dev
     Hin, Cin, Cm, C4, s = STAGES[stage]
     blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, s, seed=808 + N)
-    eager = blk.run().clone()
-    out = torch.zeros_like(eager)
-    ws = torch.empty(pkg.lib().wino_proj_block_workspace_bytes_hw(N, blk.H, blk.W, Cm) // 4, device=dev)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        pkg.proj_block_prepare(N, Hin, Hin, Cin, Cm, C4, s)
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        blk.run(out=out, workspace=ws)
-    for _ in range(2):
-        out.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, eager)
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
-    assert pkg.tickets_in_use() == 0
+    eager = graph_replay_scenario(pkg, torch_dev, blk.run, lambda: pkg.proj_block_prepare(N, Hin, Hin, Cin, Cm, C4, s),
+                                  pkg.lib().wino_proj_block_workspace_bytes_hw(N, blk.H, blk.W, Cm))
     _check_block(blk, O, eager, idx=[0])
 
 

@@ -2,12 +2,12 @@
 Three launches -- the 1x1 at full input resolution, the stride-2 3x3 (conv3x3_s2.hip), the v1 block's fused tail at
 stride 2 -- against an fp64 composition computed here, against a v1.5 Bottleneck module written in plain torch with
 eval-mode BN, and captured in a graph."""
-import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from cases import TIGHT, V15Block
+from gpu_support import graph_replay_scenario, torch_dev  # noqa: F401
 
-TIGHT = 2e-5
+pytestmark = pytest.mark.gpu
 
 # ResNet-50's v1.5 downsampling blocks: (Hin, Cin, Cm, C4)
 STAGES = {
@@ -17,89 +17,23 @@ STAGES = {
 }
 
 
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-class _Block:
-    """One block's tensors (folded BN vectors, NHWC activations) and the library's run of it."""
-
-    def __init__(self, pkg, torch_dev, N, Hin, Win, Cin, Cm, C4, seed):
-        self.torch, self.dev = torch_dev
-        torch = self.torch
-        self.pkg = pkg
-        g = torch.Generator(device="cpu").manual_seed(seed)
-        r = lambda *s: torch.rand(*s, generator=g) - 0.5
-        self.x = r(N, Hin, Win, Cin)
-        self.w1 = r(Cin, Cm) / np.sqrt(Cin) * 4
-        self.w2 = r(Cm, Cm, 3, 3) / np.sqrt(9 * Cm) * 4        # [K][C][3][3]
-        self.w3 = r(Cm, C4) / np.sqrt(Cm) * 4
-        self.wp = r(Cin, C4) / np.sqrt(Cin) * 2
-        self.bn = [(r(c), r(c) + 1.0) for c in (Cm, Cm, C4, C4)]   # (bias, scale)
-        t = lambda a: a.contiguous().to(self.dev)
-        self.xt, self.w1t, self.w3t, self.wpt = t(self.x), t(self.w1), t(self.w3), t(self.wp)
-        self.bnt = [(t(b), t(s)) for b, s in self.bn]
-        self.taps = pkg.filter_pack_s2(t(self.w2))
-        self.tail = pkg.proj_tail_pack(self.w3t, self.bnt[2], self.wpt, self.bnt[3])
-        self.H, self.W = (Hin - 1) // 2 + 1, (Win - 1) // 2 + 1
-        self.N, self.Hin, self.Win, self.Cin, self.Cm, self.C4 = N, Hin, Win, Cin, Cm, C4
-
-    def run(self, out=None, workspace=None):
-        """The fused block, into NaN-filled output and workspace unless given."""
-        torch = self.torch
-        if out is None:
-            out = torch.full((self.N, self.H, self.W, self.C4), float("nan"), device=self.dev)
-        if workspace is None:
-            need = self.pkg.lib().wino_proj_block_v15_workspace_bytes_hw(self.N, self.Hin, self.Win, self.Cm)
-            workspace = torch.full((need // 4,), float("nan"), device=self.dev)
-        return self.pkg.proj_block_v15(self.xt, self.w1t, self.bnt[0], self.taps, self.bnt[1], self.tail,
-                                       out=out, workspace=workspace)
-
-    def reference(self, idx=None):
-        """fp64 on the CPU: 1x1 at stride 1, 3x3 at stride 2 with pad 1, 1x1, plus the stride-2 projection, ReLU."""
-        torch = self.torch
-        F = torch.nn.functional
-        x = (self.x if idx is None else self.x[idx]).permute(0, 3, 1, 2).double()
-        bn = lambda y, i: y * self.bn[i][1].double()[None, :, None, None] + self.bn[i][0].double()[None, :, None, None]
-        one = lambda w: w.double().t()[:, :, None, None]   # [Cin][Cout] -> [Cout][Cin][1][1]
-        t1 = torch.relu(bn(F.conv2d(x, one(self.w1)), 0))
-        t2 = torch.relu(bn(F.conv2d(t1, self.w2.double(), stride=2, padding=1), 1))
-        t3 = bn(F.conv2d(t2, one(self.w3)), 2)
-        sc = bn(F.conv2d(x, one(self.wp), stride=2), 3)
-        return torch.relu(t3 + sc).permute(0, 2, 3, 1).numpy()
-
-    def check(self, O, got, idx=None):
-        g = got.cpu().numpy()
-        if idx is not None:
-            g = g[idx]
-        assert np.isfinite(g).all()
-        want = self.reference(idx)
-        assert g.shape == want.shape
-        assert O.rel_error(g, want) < TIGHT
-        assert (want > 0).mean() > 0.2   # both sides of the final ReLU
-        assert self.pkg.tickets_in_use() == 0
-
-
 @pytest.mark.parametrize("N", [1, 16])
 @pytest.mark.parametrize("stage", sorted(STAGES))
 def test_stage_blocks(stage, N, pkg, O, torch_dev):
     Hin, Cin, Cm, C4 = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, seed=Hin + N)
+    blk = V15Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, seed=Hin + N)
     blk.check(O, blk.run())
 
 
 def test_conv4_block_at_128_images(pkg, O, torch_dev):
     Hin, Cin, Cm, C4 = STAGES["conv4"]
-    blk = _Block(pkg, torch_dev, 128, Hin, Hin, Cin, Cm, C4, seed=4128)
+    blk = V15Block(pkg, torch_dev, 128, Hin, Hin, Cin, Cm, C4, seed=4128)
     blk.check(O, blk.run(), idx=[0, 77, 127])
 
 
 def test_odd_input(pkg, O, torch_dev):
     """Hin = 15, Win = 13 (8 x 7 outputs), Cin = 96."""
-    blk = _Block(pkg, torch_dev, 3, 15, 13, 96, 128, 256, seed=1513)
+    blk = V15Block(pkg, torch_dev, 3, 15, 13, 96, 128, 256, seed=1513)
     blk.check(O, blk.run())
 
 
@@ -172,30 +106,15 @@ def test_block_in_a_graph(stage, N, pkg, O, torch_dev):
     the replay equals eager bit for bit."""
     torch, dev = torch_dev
     Hin, Cin, Cm, C4 = STAGES[stage]
-    blk = _Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, seed=808 + N)
-    eager = blk.run().clone()
-    out = torch.zeros_like(eager)
-    ws = torch.empty(pkg.lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Hin, Cm) // 4, device=dev)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        pkg.proj_block_v15_prepare(N, Hin, Hin, Cin, Cm, C4)
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        blk.run(out=out, workspace=ws)
-    for _ in range(2):
-        out.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, eager)
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
+    blk = V15Block(pkg, torch_dev, N, Hin, Hin, Cin, Cm, C4, seed=808 + N)
+    eager = graph_replay_scenario(pkg, torch_dev, blk.run, lambda: pkg.proj_block_v15_prepare(N, Hin, Hin, Cin, Cm, C4),
+                                  pkg.lib().wino_proj_block_v15_workspace_bytes_hw(N, Hin, Hin, Cm))
     blk.check(O, eager, idx=[0])
 
 
 def test_bad_arguments_raise(pkg, torch_dev):
     torch, dev = torch_dev
-    blk = _Block(pkg, torch_dev, 1, 14, 14, 64, 64, 128, seed=5)
+    blk = V15Block(pkg, torch_dev, 1, 14, 14, 64, 64, 128, seed=5)
     with pytest.raises(pkg.WinoError):
         blk.run(workspace=torch.empty(16, device=dev))                                     # workspace too small
     with pytest.raises(pkg.WinoError):

@@ -5,104 +5,10 @@ another input shape; inputs whose last stages are 1x1, a batch where the through
 inside the network, and ResNet-152; no stream-K ticket left held."""
 import pytest
 
+from gpu_support import R, network_graph_scenario, rel, torch_dev  # noqa: F401
+from reference_nets import NET_TOL, check_net, random_state_dict, reference_forward
+
 pytestmark = pytest.mark.gpu
-
-NET_TOL = 1e-3
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def R(pkg):
-    import importlib
-    return importlib.import_module("cuda_winograd_amd.resnet")
-
-
-def random_state_dict(torch, R, arch, classes=1000, seed=0):
-    """torchvision-format weights with O(1) activations: He-scaled convs, BN near identity, and a small gamma on each
-    block's last BN so that the residual sums stay O(1) over 100+ blocks."""
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    last_bn = {f"layer{L}.{b}.bn{3 if ARCH_BOTTLENECK[arch] else 2}" for L in range(1, 5) for b in range(64)}
-    for k, shape in R.expected_keys(arch, classes).items():
-        if k.endswith(".weight") and len(shape) == 4:
-            fan_in = shape[1] * shape[2] * shape[3]
-            sd[k] = torch.randn(shape, generator=g) * (2.0 / fan_in) ** 0.5
-        elif k.endswith("running_mean"):
-            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
-        elif k.endswith("running_var"):
-            sd[k] = torch.rand(shape, generator=g) + 0.5
-        elif k.endswith(".weight") and len(shape) == 1:
-            gamma = torch.rand(shape, generator=g) + 0.5
-            sd[k] = gamma * (0.2 if k[: -len(".weight")] in last_bn else 1.0)
-        elif k.endswith(".bias") and not k.startswith("fc"):
-            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
-        elif k == "fc.weight":
-            sd[k] = torch.randn(shape, generator=g) * (1.0 / shape[1]) ** 0.5
-        else:
-            sd[k] = torch.rand(shape, generator=g) - 0.5
-        if k.endswith("running_var"):
-            sd[k[: -len("running_var")] + "num_batches_tracked"] = torch.tensor(100)
-    return sd
-
-
-ARCH_BOTTLENECK = {"resnet18": False, "resnet34": False, "resnet50": True, "resnet101": True, "resnet152": True}
-
-
-def reference_forward(torch, R, sd, arch, x, eps=1e-5):
-    """fp64 CPU forward of torchvision's ResNet (v1.5 placement) in eval mode: (logits, {stage: NHWC})."""
-    import torch.nn.functional as F
-    d = {k: v.double() for k, v in sd.items()}
-
-    def bn(t, p):
-        return F.batch_norm(t, d[p + ".running_mean"], d[p + ".running_var"], d[p + ".weight"], d[p + ".bias"],
-                            False, 0.0, eps)
-
-    bottleneck, blocks = R.ARCHS[arch]
-    t = F.max_pool2d(torch.relu(bn(F.conv2d(x.double(), d["conv1.weight"], stride=2, padding=3), "bn1")), 3, 2, 1)
-    stages = {"stem": t.permute(0, 2, 3, 1)}
-    for L, nb in enumerate(blocks, 1):
-        for b in range(nb):
-            p = f"layer{L}.{b}"
-            s = 2 if (b == 0 and L > 1) else 1
-            if bottleneck:
-                y = torch.relu(bn(F.conv2d(t, d[p + ".conv1.weight"]), p + ".bn1"))
-                y = torch.relu(bn(F.conv2d(y, d[p + ".conv2.weight"], stride=s, padding=1), p + ".bn2"))
-                y = bn(F.conv2d(y, d[p + ".conv3.weight"]), p + ".bn3")
-            else:
-                y = torch.relu(bn(F.conv2d(t, d[p + ".conv1.weight"], stride=s, padding=1), p + ".bn1"))
-                y = bn(F.conv2d(y, d[p + ".conv2.weight"], padding=1), p + ".bn2")
-            sc = t
-            if p + ".downsample.0.weight" in d:
-                sc = bn(F.conv2d(t, d[p + ".downsample.0.weight"], stride=s), p + ".downsample.1")
-            t = torch.relu(y + sc)
-        stages[f"layer{L}"] = t.permute(0, 2, 3, 1)
-    logits = t.mean(dim=(2, 3)) @ d["fc.weight"].t() + d["fc.bias"]
-    return logits, stages
-
-
-def _rel(torch, got, want):
-    got = got.detach().cpu().double()
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert not torch.isnan(got).any()
-    return float((got - want).abs().max() / want.abs().max())
-
-
-def _check_net(torch, R, model, sd, arch, x):
-    logits, stages = model.forward(x, return_stages=True)
-    torch.cuda.synchronize()
-    want_logits, want = reference_forward(torch, R, sd, arch, x.cpu())
-    errs = {name: _rel(torch, stages[name], want[name]) for name in want}
-    errs["logits"] = _rel(torch, logits, want_logits)
-    print(f"{arch} N={x.shape[0]} {x.shape[2]}x{x.shape[3]}: " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
-    bad = {k: v for k, v in errs.items() if not v < NET_TOL}
-    assert not bad, errs
-    return logits.clone()
 
 
 @pytest.mark.parametrize("arch,N,H,W", [("resnet18", 2, 224, 224), ("resnet50", 2, 224, 224),
@@ -112,7 +18,7 @@ def test_network_matches_fp64(arch, N, H, W, pkg, R, torch_dev):
     sd = random_state_dict(torch, R, arch, seed=len(arch) + N)
     model = pkg.ResNet.from_state_dict(sd, arch)
     x = (torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(N + H)) * 2 - 1).to(dev)
-    _check_net(torch, R, model, sd, arch, x)
+    check_net(torch, model, sd, arch, x)
     assert pkg.tickets_in_use() == 0
 
 
@@ -121,29 +27,14 @@ def test_whole_network_graph_replay_and_reprepare(arch, pkg, R, torch_dev):
     torch, dev = torch_dev
     sd = random_state_dict(torch, R, arch, classes=10, seed=77)
     model = pkg.ResNet.from_state_dict(sd, arch)
-    N, H, W = 2, 128, 96
-    x = (torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(5)) * 2 - 1).to(dev)
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        model.prepare(N, H, W)
-        eager = model(x).clone()
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        out = model(x)
-    for _ in range(2):
-        out.fill_(float("nan"))
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(out, eager)
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
-    want, _ = reference_forward(torch, R, sd, arch, x.cpu())
-    assert _rel(torch, eager, want) < NET_TOL
+    x = (torch.rand(2, 3, 128, 96, generator=torch.Generator().manual_seed(5)) * 2 - 1).to(dev)
+    eager, graph = network_graph_scenario(pkg, torch, model, x)
+    want, _ = reference_forward(torch, sd, x.cpu())
+    assert rel(torch, eager, want) < NET_TOL
     # a second prepare at another shape, eager
     x2 = (torch.rand(3, 3, 75, 61, generator=torch.Generator().manual_seed(6)) * 2 - 1).to(dev)
     model.prepare(3, 75, 61)
-    _check_net(torch, R, model, sd, arch, x2)
+    check_net(torch, model, sd, arch, x2)
     assert pkg.tickets_in_use() == 0
     del graph
 
@@ -157,7 +48,7 @@ def test_network_at_small_maps(arch, H, pkg, R, torch_dev):
     sd = random_state_dict(torch, R, arch, seed=H + len(arch))
     model = pkg.ResNet.from_state_dict(sd, arch)
     x = (torch.rand(3, 3, H, H, generator=torch.Generator().manual_seed(H)) * 2 - 1).to(dev)
-    _check_net(torch, R, model, sd, arch, x)
+    check_net(torch, model, sd, arch, x)
     assert pkg.tickets_in_use() == 0
 
 
@@ -203,7 +94,7 @@ def test_network_where_the_throughput_forms_take_over(arch, pkg, R, torch_dev):
     sd = random_state_dict(torch, R, arch, seed=N + len(arch))
     model = pkg.ResNet.from_state_dict(sd, arch)
     x = (torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(N)) * 2 - 1).to(dev)
-    _check_net(torch, R, model, sd, arch, x)
+    check_net(torch, model, sd, arch, x)
     assert pkg.tickets_in_use() == 0
 
 
@@ -212,5 +103,5 @@ def test_resnet152_forward(pkg, R, torch_dev):
     sd = random_state_dict(torch, R, "resnet152", seed=152)
     model = pkg.ResNet.from_state_dict(sd, "resnet152")
     x = (torch.rand(1, 3, 64, 64, generator=torch.Generator().manual_seed(152)) * 2 - 1).to(dev)
-    _check_net(torch, R, model, sd, "resnet152", x)
+    check_net(torch, model, sd, "resnet152", x)
     assert pkg.tickets_in_use() == 0

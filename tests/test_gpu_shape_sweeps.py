@@ -1,6 +1,6 @@
 """Seeded random-shape sweeps of the ResNet entry points (tests/shape_sweeps.py: shapes from the whole legal envelope
 of winograd_mi355x.h, every forced form the planner takes, the automatic ones): each case against an fp64 reference
-computed here on the CPU from the raw torch-layout weights and unfolded BN vectors, into NaN-filled outputs and
+computed on the CPU (tests/sweep_cases.py: the case runners) from the raw torch-layout weights and unfolded BN vectors, into NaN-filled outputs and
 workspaces, with NaN in every ring the contract says is not read, negative BN scales on a third of the channels, and
 post-ReLU-like (non-negative) inputs in part of the cases.  Every launch runs twice and must repeat bit for bit; no
 stream-K ticket may stay held.  tests/test_shape_sweeps_host.py checks on the host that every case is legal and that
@@ -12,468 +12,45 @@ placements, 256-byte aligned and 16 mod 256 (the weakest pointer the header acce
 and ends each in arena.check: no guard touched, no read-only operand written.  No case may be left out: each test
 counts its checks.  The pack entry points write through out= into arena outputs of exactly the queried count, and their
 consumers read the packed tensor from a guarded address."""
-import collections
-import contextlib
-
-import numpy as np
 import pytest
 
-import guarded as G
-import shape_sweeps as S
+import sweep_cases as SC
+from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
-TIGHT = 2e-5
-SENTINEL = 1234.5
-CHECKS = collections.Counter()   # arena.check calls that passed, by entry point
 
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
-
-
-@contextlib.contextmanager
-def _forced(knobs, case):
-    for k, v in (case.knobs or {}).items():
-        knobs.set(k, v)
-    try:
-        yield
-    finally:
-        for k in case.knobs or {}:
-            knobs.unset(k)
-
-
-class _Sweep:
-    """fp32 tensors drawn for one case (CPU masters; `dev` copies), fp64 reference helpers, and the checks."""
-
-    def __init__(self, torch, dev, case, pkg, seed):
-        self.torch, self.dev, self.case, self.pkg = torch, dev, case, pkg
-        self.F = torch.nn.functional
-        self.g = torch.Generator().manual_seed(seed)
-        self.tag = self.base_tag = case.tag()
-        self.arena = None
-
-    def passes(self):
-        """One pass per placement of the tensors, each on an arena of its own and ended by done()."""
-        for align in G.ALIGNS:
-            self.arena = G.Arena(self.torch, self.dev, align=align)
-            self.tag = f"{self.base_tag[:-1]} align={align}]"
-            yield align
-            self.done()
-        self.arena = None
-
-    def rand(self, *shape):
-        return self.torch.rand(*shape, generator=self.g)
-
-    def act(self, *shape):
-        """Activations: uniform in [-0.5, 0.5), or in [0, 1) (non-zero mean, as after a ReLU) for nonneg cases."""
-        r = self.rand(*shape)
-        return r if self.case.flags.get("nonneg") else r - 0.5
-
-    def conv_w(self, K, C, k=3):
-        return (self.rand(K, C, k, k) - 0.5) / np.sqrt(k * k * C) * 4
-
-    def bn(self, K):
-        """(bias, scale) with a negative scale on every third channel."""
-        bias, scale = self.rand(K) - 0.5, self.rand(K) + 0.5
-        scale[::3] *= -1
-        return bias, scale
-
-    def padded(self, inner, ring=0.0):
-        N, H, W, C = inner.shape
-        x = self.torch.full((N, H + 2, W + 2, C), ring)
-        x[:, 1:-1, 1:-1, :] = inner
-        return x
-
-    def nan(self, *shape, name=None):
-        """A NaN-filled output between sentinel guards."""
-        return self.arena.output(*shape, name=name)
-
-    def ws(self, nbytes, query):
-        """A NaN-filled workspace of exactly `nbytes` (whole floats), what size query `query` reported, between sentinel
-        guards."""
-        return self.arena.workspace(nbytes, name="workspace", query=query)
-
-    def d(self, t, name=None):
-        """A read-only operand between NaN guards (a tensor the library packed is re-homed there for its consumer)."""
-        return self.arena.input(t, name=name)
-
-    def packed(self, pack, shape, name, *args):
-        """What a pack entry point makes of `args`: written into a guarded output of exactly `shape` (the size query's
-        count), then re-homed as a read-only operand for its consumer."""
-        shape = (int(shape),) if isinstance(shape, int) else tuple(shape)
-        out = self.nan(*shape, name=name + " (pack out)")
-        got = pack(*args, out=out)
-        assert got.data_ptr() == out.data_ptr(), self.tag
-        return self.d(got, name)
-
-    def U(self, w, name="U"):
-        K, C = w.shape[:2]
-        return self.packed(self.pkg.filter_transform_f2, self.pkg.lib().wino_filter_f2_elems(C, K), name,
-                           self.d(w, name + ".w"))
-
-    def bnd(self, bn, name="bn"):
-        return self.d(bn[0], name + ".bias"), self.d(bn[1], name + ".scale")
-
-    def buf(self, t, name="buf"):
-        """A fresh guarded copy of `t` that the launch writes in place."""
-        return self.arena.input(t, name=name, in_place=True)
-
-    # fp64 reference pieces, NCHW
-    @staticmethod
-    def nchw(x_nhwc):
-        return x_nhwc.permute(0, 3, 1, 2).double()
-
-    def conv(self, x, w, stride=1, pad=1):
-        return self.F.conv2d(x, w.double(), stride=stride, padding=pad)
-
-    def conv1x1(self, x, w_io, stride=1):
-        """w [Cin][Cout] (the library's 1x1 layout)."""
-        return self.F.conv2d(x, w_io.double().t()[:, :, None, None], stride=stride)
-
-    @staticmethod
-    def affine(y, bn):
-        b, s = bn
-        return y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-
-    # checks
-    def close(self, got, want, what="out"):
-        g = got.detach().cpu().double() if hasattr(got, "detach") else got
-        w = want.detach().cpu().double() if hasattr(want, "detach") else want
-        assert tuple(g.shape) == tuple(w.shape), f"{self.tag} {what}: shape {tuple(g.shape)} != {tuple(w.shape)}"
-        assert bool(self.torch.isfinite(g).all()), f"{self.tag} {what}: non-finite values (not all written)"
-        err = float((g - w).abs().max() / w.abs().max())
-        assert err < TIGHT, f"{self.tag} {what}: rel err {err:.3e}"
-
-    def ring_is(self, got, value, what="out"):
-        g = got.detach().cpu()
-        ring = self.torch.ones(g.shape[1:3], dtype=self.torch.bool)
-        ring[1:-1, 1:-1] = False
-        assert bool((g[:, ring, :] == value).all()), f"{self.tag} {what}: ring is not exactly {value}"
-
-    def both_sides(self, pre):
-        pos, neg = int((pre > 0).sum()), int((pre < 0).sum())
-        assert pos > 0 and neg > 0, f"{self.tag}: the ReLU sees one side only ({pos} > 0, {neg} < 0)"
-
-    def same(self, a, b, what="out"):
-        assert self.torch.equal(a, b), f"{self.tag} {what}: two launches differ"
-
-    def done(self):
-        assert self.pkg.tickets_in_use() == 0, f"{self.tag}: a stream-K ticket is still held"
-        self.arena.check(self.tag)
-        CHECKS[self.case.entry] += 1
-
-
-def _start(pkg, knobs, torch_dev, case, seed):
-    """The sweep's tensors, with the plan query asked (under the case's knobs) that the forced form is taken."""
-    torch, dev = torch_dev
-    sw = _Sweep(torch, dev, case, pkg, seed)
-    plan = S.plan_form(pkg, case)
-    bad = S.check_forced(case, plan)
-    assert bad is None, f"{sw.tag}: {bad}"
-    sw.tag = sw.base_tag = f"{sw.tag[:-1]} plan={plan['form']}]"
-    return sw
-
-
-def _sweep(entry, run, pkg, knobs, torch_dev, seed0):
-    """Every case of the entry point's generator, and the count that none was left out at either placement."""
-    cases = S.GENERATORS[entry]()
-    before = CHECKS[entry]
-    for i, case in enumerate(cases):
-        assert case.entry == entry
-        with _forced(knobs, case):
-            run(pkg, knobs, torch_dev, case, seed0 + i)
-    done = CHECKS[entry] - before
-    assert done == 2 * len(cases), f"{entry}: {done} guard checks for {len(cases)} cases at two placements"
-
-
-# ---- the residual 3x3 ------------------------------------------------------------------------------------------------
 def test_residual_3x3_sweep(pkg, knobs, torch_dev):
-    _sweep("conv3x3_bn_add_relu", _residual_case, pkg, knobs, torch_dev, 100)
+    SC.run_sweep("conv3x3_bn_add_relu", SC.residual_case, pkg, knobs, torch_dev, 100)
 
 
-def _residual_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    N, H, W, C, K = case.N, case.H, case.W, case.C, case.K
-    relu, in_place = case.flags["relu"], case.flags["in_place"]
-    x = sw.padded(sw.act(N, H, W, C))
-    res = sw.padded(sw.act(N, H, W, K), ring=float("nan"))   # the residual's ring is not read
-    w, bn = sw.conv_w(K, C), sw.bn(K)
-    pre = sw.affine(sw.conv(sw.nchw(x[:, 1:-1, 1:-1, :]), w), bn) + sw.nchw(res[:, 1:-1, 1:-1, :])
-    want = (sw.torch.relu(pre) if relu else pre).permute(0, 2, 3, 1)
-    if relu:
-        sw.both_sides(pre)
-    for _ in sw.passes():
-        xd, U = sw.d(x, "x"), sw.U(w)
-        bd, sd = sw.bnd(bn)
-        resd = None if in_place else sw.d(res, "residual")
-        outs = []
-        for _ in range(2):
-            if in_place:
-                buf = sw.buf(res)   # a fresh copy before each launch
-                got = pkg.conv3x3_bn_add_relu(xd, U, bd, sd, buf, relu=relu, out=buf)
-                assert got.data_ptr() == buf.data_ptr(), sw.tag
-            else:
-                got = pkg.conv3x3_bn_add_relu(xd, U, bd, sd, resd, relu=relu, out=sw.nan(N, H + 2, W + 2, K))
-            outs.append(got)
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
-
-
-# ---- the identity basic block ------------------------------------------------------------------------------------------
 def test_basic_block_sweep(pkg, knobs, torch_dev):
-    _sweep("basic_block", _basic_block_case, pkg, knobs, torch_dev, 200)
-
-
-def _basic_block_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    N, H, W, C = case.N, case.H, case.W, case.C
-    x = sw.padded(sw.act(N, H, W, C))
-    w1, w2, bn1, bn2 = sw.conv_w(C, C), sw.conv_w(C, C), sw.bn(C), sw.bn(C)
-    xi = sw.nchw(x[:, 1:-1, 1:-1, :])
-    t1 = sw.torch.relu(sw.affine(sw.conv(xi, w1), bn1))
-    pre = sw.affine(sw.conv(t1, w2), bn2) + xi
-    sw.both_sides(pre)
-    want = sw.torch.relu(pre).permute(0, 2, 3, 1)
-    need = pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, W, C)
-    for _ in sw.passes():
-        U1, U2 = sw.U(w1, "U1"), sw.U(w2, "U2")
-        bnd1, bnd2 = sw.bnd(bn1, "bn1"), sw.bnd(bn2, "bn2")
-        xd = None if case.flags["in_place"] else sw.d(x, "x")
-        outs = []
-        for _ in range(2):
-            ws = sw.ws(need, "wino_basic_block_workspace_bytes_hw")
-            if case.flags["in_place"]:
-                buf = sw.buf(x)
-                got = pkg.basic_block(buf, U1, bnd1, U2, bnd2, out=buf, workspace=ws)
-                assert got.data_ptr() == buf.data_ptr(), sw.tag
-            else:
-                got = pkg.basic_block(xd, U1, bnd1, U2, bnd2, out=sw.nan(N, H + 2, W + 2, C), workspace=ws)
-            outs.append(got)
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
-
-
-# ---- the stride-2 3x3, the fused stride-2 3x3 + shortcut, the downsampling basic block ---------------------------
-class _S2:
-    """A stride-2 case's tensors: padded x, the 3x3 and 1x1 shortcut weights, their BNs, and the fp64 t1, sc."""
-
-    def __init__(self, sw, case, with_block=False):
-        N, Hin, Win, C, K = case.N, case.Hin, case.Win, case.C, case.K
-        self.H, self.W = S._s2(Hin), S._s2(Win)
-        self.x = sw.padded(sw.act(N, Hin, Win, C))
-        self.w1, self.wd = sw.conv_w(K, C), sw.conv_w(K, C, k=1)
-        self.bn1, self.bnd = sw.bn(K), sw.bn(K)
-        xi = sw.nchw(self.x[:, 1:-1, 1:-1, :])
-        self.pre1 = sw.affine(sw.conv(xi, self.w1, stride=2), self.bn1)
-        self.sc = sw.affine(sw.F.conv2d(xi, self.wd.double(), stride=2), self.bnd)
-        self.shape = (N, self.H + 2, self.W + 2, K)
-        if with_block:
-            self.w2, self.bn2 = sw.conv_w(K, K), sw.bn(K)
-
-    def place(self, sw):
-        """The device operands of one pass, on sw's arena."""
-        K, C = self.w1.shape[:2]
-        self.xd = sw.d(self.x, "x")
-        self.taps = sw.packed(sw.pkg.filter_pack_s2, (3, 3, C, K), "taps", sw.d(self.w1, "w1"))
-        self.bn1d, self.bndd = sw.bnd(self.bn1, "bn1"), sw.bnd(self.bnd, "bnd")
-
-    def packed(self, sw):
-        K, C = self.w1.shape[:2]
-        return sw.packed(sw.pkg.s2_proj_pack, sw.pkg.lib().wino_s2_proj_elems(C, K), "packed",
-                         self.taps, self.bn1d, sw.d(self.wd.view(K, C).t(), "wd"), self.bndd)
+    SC.run_sweep("basic_block", SC.basic_block_case, pkg, knobs, torch_dev, 200)
 
 
 def test_conv3x3_s2_sweep(pkg, knobs, torch_dev):
-    _sweep("conv3x3_s2_bn_relu", _s2_case, pkg, knobs, torch_dev, 300)
-
-
-def _s2_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    L = _S2(sw, case)
-    relu = case.flags["relu"]
-    if relu:
-        sw.both_sides(L.pre1)
-    want = (sw.torch.relu(L.pre1) if relu else L.pre1).permute(0, 2, 3, 1)
-    for _ in sw.passes():
-        L.place(sw)
-        outs = [pkg.conv3x3_s2_bn_relu(L.xd, L.taps, *L.bn1d, relu=relu, out=sw.nan(*L.shape)) for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+    SC.run_sweep("conv3x3_s2_bn_relu", SC.s2_case, pkg, knobs, torch_dev, 300)
 
 
 def test_conv3x3_s2_proj_sweep(pkg, knobs, torch_dev):
-    _sweep("conv3x3_s2_proj", _s2_proj_case, pkg, knobs, torch_dev, 400)
-
-
-def _s2_proj_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    L = _S2(sw, case)
-    sw.both_sides(L.pre1)
-    for _ in sw.passes():
-        L.place(sw)
-        packed = L.packed(sw)
-        runs = []
-        for _ in range(2):
-            sc = sw.nan(*L.shape, name="sc")
-            sc[:, 0, :, :] = sc[:, -1, :, :] = SENTINEL   # sc's ring is not touched
-            sc[:, :, 0, :] = sc[:, :, -1, :] = SENTINEL
-            runs.append(pkg.conv3x3_s2_proj(L.xd, packed, t1=sw.nan(*L.shape, name="t1"), sc=sc))
-        (t1, sc), (t1b, scb) = runs
-        sw.ring_is(t1, 0.0, "t1")
-        sw.ring_is(sc, SENTINEL, "sc")
-        sw.close(t1[:, 1:-1, 1:-1, :], sw.torch.relu(L.pre1).permute(0, 2, 3, 1), "t1")
-        sw.close(sc[:, 1:-1, 1:-1, :], L.sc.permute(0, 2, 3, 1), "sc")
-        plain = pkg.conv3x3_s2_bn_relu(L.xd, L.taps, *L.bn1d, relu=True, out=sw.nan(*L.shape))
-        sw.same(t1, plain, "t1 against the plain stride-2 layer:")
-        sw.same(t1, t1b, "t1")
-        sw.same(sc, scb, "sc")
+    SC.run_sweep("conv3x3_s2_proj", SC.s2_proj_case, pkg, knobs, torch_dev, 400)
 
 
 def test_basic_block_s2_sweep(pkg, knobs, torch_dev):
-    _sweep("basic_block_s2", _basic_block_s2_case, pkg, knobs, torch_dev, 500)
-
-
-def _basic_block_s2_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    L = _S2(sw, case, with_block=True)
-    t1 = sw.torch.relu(L.pre1)
-    pre = sw.affine(sw.conv(t1, L.w2), L.bn2) + L.sc
-    sw.both_sides(pre)
-    want = sw.torch.relu(pre).permute(0, 2, 3, 1)
-    need = pkg.lib().wino_basic_block_s2_workspace_bytes_hw(case.N, case.Hin, case.Win, case.K)
-    for _ in sw.passes():
-        L.place(sw)
-        packed, U2 = L.packed(sw), sw.U(L.w2, "U2")
-        bn2 = sw.bnd(L.bn2, "bn2")
-        outs = [pkg.basic_block_s2(L.xd, packed, U2, bn2, out=sw.nan(*L.shape),
-                                   workspace=sw.ws(need, "wino_basic_block_s2_workspace_bytes_hw"))
-                for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
-
-
-# ---- the projection bottleneck blocks ------------------------------------------------------------------------------
-class _Proj:
-    def __init__(self, sw, case):
-        N, Hin, Win, Cin, Cm, C4 = case.N, case.Hin, case.Win, case.Cin, case.Cm, case.C4
-        self.x = sw.act(N, Hin, Win, Cin)
-        w11 = lambda i, o, gain: (sw.rand(i, o) - 0.5) / np.sqrt(i) * gain
-        self.w1, self.w2, self.w3, self.wp = w11(Cin, Cm, 4), sw.conv_w(Cm, Cm), w11(Cm, C4, 4), w11(Cin, C4, 2)
-        self.bn = [sw.bn(c) for c in (Cm, Cm, C4, C4)]
-
-    def place(self, sw):
-        """The device operands of one pass, on sw's arena."""
-        self.xd, self.w1d = sw.d(self.x, "x"), sw.d(self.w1, "w1")
-        self.bnd = [sw.bnd(b, f"bn{i}") for i, b in enumerate(self.bn)]
-        Cin, Cm, C4 = self.w1.shape[0], self.w1.shape[1], self.w3.shape[1]
-        self.tail = sw.packed(sw.pkg.proj_tail_pack, sw.pkg.lib().wino_proj_tail_elems(Cm, Cin, C4), "tail",
-                              sw.d(self.w3, "w3"), self.bnd[2], sw.d(self.wp, "wp"), self.bnd[3])
-
-    def reference(self, sw, stride, v15):
-        """(pre-ReLU sum, output) in fp64, NCHW."""
-        x = sw.nchw(self.x)
-        xs = x[:, :, ::stride, ::stride]
-        t1 = sw.torch.relu(sw.affine(sw.conv1x1(x if v15 else xs, self.w1), self.bn[0]))
-        t2 = sw.torch.relu(sw.affine(sw.conv(t1, self.w2, stride=2 if v15 else 1), self.bn[1]))
-        pre = sw.affine(sw.conv1x1(t2, self.w3), self.bn[2]) + sw.affine(sw.conv1x1(xs, self.wp), self.bn[3])
-        return pre, sw.torch.relu(pre)
+    SC.run_sweep("basic_block_s2", SC.basic_block_s2_case, pkg, knobs, torch_dev, 500)
 
 
 def test_proj_block_sweep(pkg, knobs, torch_dev):
-    _sweep("proj_block", _proj_case, pkg, knobs, torch_dev, 600)
-
-
-def _proj_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    B, st = _Proj(sw, case), case.stride
-    pre, want = B.reference(sw, st, v15=False)
-    sw.both_sides(pre)
-    H, W = (case.Hin - 1) // st + 1, (case.Win - 1) // st + 1
-    need = pkg.lib().wino_proj_block_workspace_bytes_hw(case.N, H, W, case.Cm)
-    for _ in sw.passes():
-        B.place(sw)
-        U2 = sw.U(B.w2, "U2")
-        outs = [pkg.proj_block(B.xd, B.w1d, B.bnd[0], U2, B.bnd[1], B.tail, st, out=sw.nan(case.N, H, W, case.C4),
-                               workspace=sw.ws(need, "wino_proj_block_workspace_bytes_hw")) for _ in range(2)]
-        sw.close(outs[0], want.permute(0, 2, 3, 1))
-        sw.same(outs[0], outs[1])
+    SC.run_sweep("proj_block", SC.proj_case, pkg, knobs, torch_dev, 600)
 
 
 def test_proj_block_v15_sweep(pkg, knobs, torch_dev):
-    _sweep("proj_block_v15", _v15_case, pkg, knobs, torch_dev, 700)
+    SC.run_sweep("proj_block_v15", SC.v15_case, pkg, knobs, torch_dev, 700)
 
 
-def _v15_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    B = _Proj(sw, case)
-    pre, want = B.reference(sw, 2, v15=True)
-    sw.both_sides(pre)
-    H, W = S._s2(case.Hin), S._s2(case.Win)
-    need = pkg.lib().wino_proj_block_v15_workspace_bytes_hw(case.N, case.Hin, case.Win, case.Cm)
-    for _ in sw.passes():
-        B.place(sw)
-        taps = sw.packed(pkg.filter_pack_s2, (3, 3, case.Cm, case.Cm), "taps", sw.d(B.w2, "w2"))
-        outs = [pkg.proj_block_v15(B.xd, B.w1d, B.bnd[0], taps, B.bnd[1], B.tail, out=sw.nan(case.N, H, W, case.C4),
-                                   workspace=sw.ws(need, "wino_proj_block_v15_workspace_bytes_hw")) for _ in range(2)]
-        sw.close(outs[0], want.permute(0, 2, 3, 1))
-        sw.same(outs[0], outs[1])
-
-
-# ---- the stem and the head -----------------------------------------------------------------------------------------
 def test_stem_sweep(pkg, knobs, torch_dev):
-    _sweep("stem", _stem_case, pkg, knobs, torch_dev, 800)
-
-
-def _stem_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    N, H, W, K, padded = case.N, case.H, case.W, case.K, case.flags["padded"]
-    x = sw.rand(N, 3, H, W) * 2 - 1
-    w = (sw.rand(K, 3, 7, 7) - 0.5) * 0.3
-    bn = sw.bn(K)
-    pre = sw.affine(sw.conv(x.double(), w, stride=2, pad=3), bn)
-    sw.both_sides(pre)
-    want = sw.F.max_pool2d(sw.torch.relu(pre), 3, 2, 1).permute(0, 2, 3, 1)
-    Hp, Wp = pkg.stem_out_hw(H, W)
-    p = 2 if padded else 0
-    for _ in sw.passes():
-        packed = sw.packed(pkg.stem_filter_pack, pkg.lib().wino_stem_filter_elems(K), "packed", sw.d(w, "w"),
-                           sw.bnd(bn))
-        xd = sw.d(x, "x")
-        outs = [pkg.stem(xd, packed, out_padded=padded, out=sw.nan(N, Hp + p, Wp + p, K)) for _ in range(2)]
-        got = outs[0]
-        if padded:
-            sw.ring_is(got, 0.0)
-            got = got[:, 1:-1, 1:-1, :]
-        sw.close(got, want)
-        sw.same(outs[0], outs[1])
+    SC.run_sweep("stem", SC.stem_case, pkg, knobs, torch_dev, 800)
 
 
 def test_head_sweep(pkg, knobs, torch_dev):
-    _sweep("avgpool_fc", _head_case, pkg, knobs, torch_dev, 900)
-
-
-def _head_case(pkg, knobs, torch_dev, case, seed):
-    sw = _start(pkg, knobs, torch_dev, case, seed)
-    N, H, W, C, classes, padded = case.N, case.H, case.W, case.C, case.classes, case.flags["padded"]
-    feat = sw.rand(N, H, W, C) * 2            # post-ReLU features
-    wfc = (sw.rand(classes, C) - 0.5) / np.sqrt(C) * 2
-    bfc = sw.rand(classes) - 0.5
-    want = feat.double().mean(dim=(1, 2)) @ wfc.double().t() + bfc.double()
-    f = sw.padded(feat, ring=float("nan")) if padded else feat   # the padded input's ring is not read
-    need = pkg.lib().wino_head_workspace_bytes(N, C, classes)
-    for _ in sw.passes():
-        packed = sw.packed(pkg.head_pack, pkg.lib().wino_head_elems(C, classes), "packed",
-                           sw.d(wfc, "wfc"), sw.d(bfc, "bfc"))
-        fd = sw.d(f, "feat")
-        outs = [pkg.avgpool_fc(fd, packed, classes, in_padded=padded, out=sw.nan(N, classes),
-                               workspace=sw.ws(need, "wino_head_workspace_bytes")) for _ in range(2)]
-        sw.close(outs[0], want, "logits")
-        sw.same(outs[0], outs[1], "logits")
+    SC.run_sweep("avgpool_fc", SC.head_case, pkg, knobs, torch_dev, 900)

@@ -5,16 +5,11 @@ whose input and output cross 2^32 bytes."""
 import numpy as np
 import pytest
 
+from gpu_support import torch_dev  # noqa: F401
+
 pytestmark = pytest.mark.gpu
 
 TIGHT = 2e-5
-
-
-@pytest.fixture(scope="module")
-def torch_dev():
-    import torch
-    assert torch.cuda.is_available(), "GPU tests need a GPU"
-    return torch, torch.device("cuda:0")
 
 
 def _stem_params(torch, K, seed, neg=True):

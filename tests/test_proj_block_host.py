@@ -7,8 +7,8 @@ import os
 
 import pytest
 
+from build_report import compile_report, template_args
 from conftest import ROOT
-from test_build_budget import _compile_report, _template_args
 
 STAGES = {   # (Hin, Cin, Cm, C4, stride): ResNet-50's stage-entry blocks
     "conv2": (56, 64, 64, 256, 1),
@@ -120,15 +120,15 @@ def test_proj_form_kernels_build_budget(tmp_path):
     last argument, AF), and those keep the budgets of the plain forms (tests/test_build_budget.py): the tiled kernel
     128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), a few spills outside the loops at most; the latency kernel no
     spill at all; neither any spill code beside MFMAs."""
-    k = _compile_report("proj_block.hip", tmp_path)
+    k = compile_report("proj_block.hip", tmp_path)
     tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
     small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     assert len(tiled) == 8, sorted(tiled)     # {4, 8 waves} x {plain, stream-K} x {strided, two sources}
     assert len(small) == 36, sorted(small)    # KS {1, 2, 4} x RT {1, 2} x CT {1, 2, 4} x {strided, two sources}
     # half in each projection form (AF = A_STRIDED 1 / A_TWO 2), none in the plain form
-    forms = [_template_args(n, "conv1x1_bn_kernel")[-1] for n in tiled]
+    forms = [template_args(n, "conv1x1_bn_kernel")[-1] for n in tiled]
     assert sorted(forms) == [1] * 4 + [2] * 4, sorted(tiled)
-    forms = [_template_args(n, "conv1x1_small_kernel")[-1] for n in small]
+    forms = [template_args(n, "conv1x1_small_kernel")[-1] for n in small]
     assert sorted(forms) == [1] * 18 + [2] * 18, sorted(small)
     for name, v in tiled.items():
         eight = "ILi32ELi8E" in name
@@ -143,10 +143,10 @@ def test_proj_form_kernels_build_budget(tmp_path):
 def test_conv1x1_kernel_set_unchanged(tmp_path):
     """conv1x1.hip instantiates exactly the kernels it did before the projection forms existed: all in the plain
     operand form (AF = A_PLAIN = 0), none in the new ones."""
-    k = _compile_report("conv1x1.hip", tmp_path)
+    k = compile_report("conv1x1.hip", tmp_path)
     tiled = [n for n in k if "conv1x1_bn_kernel" in n]
     small = [n for n in k if "conv1x1_small_kernel" in n]
     assert len(tiled) == 8 and len(small) == 18, sorted(k)
-    assert all(_template_args(n, "conv1x1_bn_kernel")[-1] == 0 for n in tiled), tiled
-    assert all(_template_args(n, "conv1x1_small_kernel")[-1] == 0 for n in small), small
+    assert all(template_args(n, "conv1x1_bn_kernel")[-1] == 0 for n in tiled), tiled
+    assert all(template_args(n, "conv1x1_small_kernel")[-1] == 0 for n in small), small
     assert not [n for n in k if "proj" in n]
