@@ -1,6 +1,6 @@
 // The 1x1-conv GEMM kernel as a header, so that the library (conv1x1.hip) and the ablation tool
-// (tools/ablate_1x1.hip) compile the same source.  ABLATE (0 = product): 1 skip the A LDS-DMA,
-// 2 skip the B LDS-DMA, 4 skip the MFMAs, 8 skip the per-stage wait+barrier, 512 skip the stores.
+// (tools/ablate_1x1.hip) compile the same source.  ABLATE (PROBE_OFF = product): the probe bits and the timeline
+// build's stamp buffer (sk.dbg) are listed in wino_probe.h.
 //
 // SK = true is the stream-K launch form.  A launch lasts as long as its busiest CU: a CU gives its
 // workgroups a fixed throughput (one alone walks 32 k-steps of the 1024->256 layer in 57 us, two
@@ -21,10 +21,8 @@
 namespace wino {
 namespace gemm1x1 {
 
-#ifndef WINO_1X1_DMA0
-#define WINO_1X1_DMA0 4   // first step of a stage (of 14) that issues an LDS-DMA piece of the next one;
+constexpr int DMA0 = 4;   // first step of a stage (of 14) that issues an LDS-DMA piece of the next one;
                           // tools/ablate_1x1: 0 / 2 / 4 / 6 within 1 % on all four reference shapes, 8 up to +9 %
-#endif
 constexpr int BM = 112;
 constexpr int WINO_INTERNAL_NO_BN = 1 << 16;   // not part of the public flag set
 constexpr int RB = BM / 16;  // 7 row blocks
@@ -163,7 +161,7 @@ struct Cfg {
 struct SkArgs {
   float* slabs;
   unsigned* tickets;
-  unsigned long long* dbg;   // timeline build only (ABLATE & 32768, tools/ablate_1x1 t): 8 uint64 per workgroup
+  unsigned long long* dbg;   // timeline build only (PROBE_TIMELINE, tools/ablate_1x1 t): TL_WORDS per workgroup
   unsigned* err;             // host-visible word, set when a ticket is drawn on a counter that was not zero at launch
 };
 
@@ -235,20 +233,20 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   // slot holds LDS and registers and feeds nothing.  High priority until the first stage is requested.
   __builtin_amdgcn_s_setprio(3);
   const int tid = threadIdx.x, lane = tid & 63;
-  if (ABLATE == 0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+  if (ABLATE == PROBE_OFF && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
     wino_clk_slot_1x1[0] = __builtin_amdgcn_s_memtime();
     wino_clk_slot_1x1[1] = __builtin_amdgcn_s_memrealtime();
   }
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (ABLATE & 32768) {   // timeline: chip-wide 100 MHz stamps at entry / first MFMA / start of the last epilogue / exit
+  if (ABLATE & PROBE_TIMELINE) {   // timeline: chip-wide 100 MHz stamps at entry / first MFMA / start of the last epilogue / exit
     if (threadIdx.x == 0) {
-      sk.dbg[(size_t)blockIdx.x * 8 + 0] = __builtin_amdgcn_s_memrealtime();
-      sk.dbg[(size_t)blockIdx.x * 8 + 5] = __builtin_amdgcn_s_memtime();
+      sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL_ENTRY] = __builtin_amdgcn_s_memrealtime();
+      sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL1_ENTRY_CYC] = __builtin_amdgcn_s_memtime();
       // which CU: HW_REG_HW_ID (cu bits 8-11, se bits 13-15) and HW_REG_XCC_ID
-      sk.dbg[(size_t)blockIdx.x * 8 + 4] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11));
+      sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL1_HW_ID] = ((unsigned long long)__builtin_amdgcn_s_getreg(20 | (31 << 11)) << 32) | __builtin_amdgcn_s_getreg(4 | (31 << 11));
     }
   }
-  if (c_padded && !proj_sc && !(ABLATE & 512)) {   // (A_TAPS_PROJ: t1's ring; the shortcut's is never read)
+  if (c_padded && !proj_sc && !(ABLATE & PROBE_NO_STORE)) {   // (A_TAPS_PROJ: t1's ring; the shortcut's is never read)
     // ring pass: the padded output's zero ring (the 3x3 layer's padding) as a flat list of
     // 16-byte units -- images x ring pixels x Kout/4 units -- split over the grid
     const unsigned upp = (unsigned)Kout >> 2;
@@ -402,10 +400,10 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   auto issue_piece = [&](int stage, unsigned a_soff, unsigned b_soff, int p) {  // p = 0 .. A_PER_WAVE + B_PER_WAVE - 1
     char* sb = smem + stage * G::STAGE;
     if (p < G::A_PER_WAVE) {
-      if (!(ABLATE & 1)) dma16_buf(rsrc_a, a_voff[p], a_soff, sb + a_q[p] * 1024);
+      if (!(ABLATE & PROBE_NO_DMA_A)) dma16_buf(rsrc_a, a_voff[p], a_soff, sb + a_q[p] * 1024);
     } else {
       const int j = p - G::A_PER_WAVE, q = w + NW * j;
-      if (!(ABLATE & 2)) dma16_buf(rsrc_b, b_voff[j], b_soff, sb + G::A_BYTES + q * 1024);
+      if (!(ABLATE & PROBE_NO_DMA_B)) dma16_buf(rsrc_b, b_voff[j], b_soff, sb + G::A_BYTES + q * 1024);
     }
   };
   constexpr int PIECES = G::A_PER_WAVE + G::B_PER_WAVE;
@@ -441,7 +439,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   auto body = [&](auto par, auto more_c, int it) {
     constexpr int PAR = decltype(par)::value;
     constexpr bool more = decltype(more_c)::value;
-    if (!(ABLATE & 8)) {
+    if (!(ABLATE & PROBE_NO_SYNC)) {
       wait_vmem_all();
       __syncthreads();
     }
@@ -469,16 +467,16 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
 #pragma unroll
         for (int j = 0; j < 4; j++) b[s + 1][j] = *(const float*)(st + b_off + (16 * (s + 1) + j) * BN * 4);
       }
-      // this wave's LDS-DMA pieces for the next stage, one per step from step WINO_1X1_DMA0 on
-      if (t >= WINO_1X1_DMA0 && t - WINO_1X1_DMA0 < PIECES) {
-        if (more) issue_piece(PAR ^ 1, a_soff, b_soff, t - WINO_1X1_DMA0);
+      // this wave's LDS-DMA pieces for the next stage, one per step from step DMA0 on
+      if (t >= DMA0 && t - DMA0 < PIECES) {
+        if (more) issue_piece(PAR ^ 1, a_soff, b_soff, t - DMA0);
       }
       __builtin_amdgcn_sched_barrier(0);
       wait_lds1(G::wait_count(t));
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        if (ABLATE & 4) asm volatile("" ::"v"(a[t][j]), "v"(b[s][j]));
+        if (ABLATE & PROBE_NO_MFMA) asm volatile("" ::"v"(a[t][j]), "v"(b[s][j]));
         // The filter fragment is the MFMA's A operand and the pixel fragment its B operand (both are
         // "one value per lane, index lane & 15, k = lane >> 4", so the swap is free): D = C^T, a lane then holds
         // four CONSECUTIVE out-channels 16 w + 4 h + 0..3 of pixel rb*16 + r16 -- one 16-byte store, no staging.
@@ -487,7 +485,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  if ((ABLATE & 32768) && stamp_first == 0) stamp_first = __builtin_amdgcn_s_memrealtime();   // the first stage is about to be waited for
+  if ((ABLATE & PROBE_TIMELINE) && stamp_first == 0) stamp_first = __builtin_amdgcn_s_memrealtime();   // the first stage is about to be waited for
   {
     using P0 = std::integral_constant<int, 0>;
     using P1 = std::integral_constant<int, 1>;
@@ -509,10 +507,10 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     if (cut) continue;   // the tile goes on past the phase boundary in the same accumulators
   }
 
-  if (ABLATE & 32768) {
+  if (ABLATE & PROBE_TIMELINE) {
     if (threadIdx.x == 0) {
-      sk.dbg[(size_t)blockIdx.x * 8 + 2] = __builtin_amdgcn_s_memrealtime();                 // overwritten by every segment: the last one stays
-      if (first_seg_stamp) sk.dbg[(size_t)blockIdx.x * 8 + 1] = stamp_first;
+      sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL_LAST_EPI] = __builtin_amdgcn_s_memrealtime();                 // overwritten by every segment: the last one stays
+      if (first_seg_stamp) sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL_FIRST] = stamp_first;
     }
   }
   // ---- epilogue: BN (+residual) (+ReLU).
@@ -613,7 +611,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     __syncthreads();   // everyone has read the ticket word before the image overwrites it
   }
   if (direct_epi) {
-    if (ABLATE & 512) {   // price the stores: keep the accumulators (and with them the MFMAs) alive
+    if (ABLATE & PROBE_NO_STORE) {   // price the stores: keep the accumulators (and with them the MFMAs) alive
 #pragma unroll
       for (int rb = 0; rb < RB; rb++) asm volatile("" ::"v"(acc[rb]));
       continue;
@@ -665,7 +663,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     }
   }
   __syncthreads();
-  if (ABLATE & 512) continue;
+  if (ABLATE & PROBE_NO_STORE) continue;
   {
     constexpr int LPR = BN / 4;          // lanes per output row
     constexpr int RPI = 64 / LPR;        // rows per store instruction
@@ -702,14 +700,14 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     else store_rows(std::false_type{});
   }
   }   // segments
-  if (ABLATE == 0 && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
+  if (ABLATE == PROBE_OFF && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) {
     wino_clk_slot_1x1[2] = __builtin_amdgcn_s_memtime();
     wino_clk_slot_1x1[3] = __builtin_amdgcn_s_memrealtime();
   }
-  if (ABLATE & 32768) {
+  if (ABLATE & PROBE_TIMELINE) {
     if (threadIdx.x == 0) {
-      sk.dbg[(size_t)blockIdx.x * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-      sk.dbg[(size_t)blockIdx.x * 8 + 6] = __builtin_amdgcn_s_memtime();
+      sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL_EXIT] = __builtin_amdgcn_s_memrealtime();
+      sk.dbg[(size_t)blockIdx.x * TL_WORDS + TL1_EXIT_CYC] = __builtin_amdgcn_s_memtime();
     }
   }
 }

@@ -12,6 +12,7 @@
 #include <utility>
 
 #include "winograd_mi355x.h"
+#include "wino_probe.h"
 
 namespace wino {
 
@@ -54,7 +55,7 @@ inline int check_workspace(const void* workspace, size_t workspace_bytes, size_t
   if (!workspace || workspace_bytes < need) { set_error("workspace too small: need %zu bytes", need); return WINO_E_ARG; }
   return WINO_OK;
 }
-// The Winograd 3x3's shape limits at any batch (WINO_E_SHAPE otherwise; wino_f2_fused.hip): channels, feature map,
+// The Winograd 3x3's shape limits at any batch (WINO_E_SHAPE otherwise; wino_f2_plan.hip): channels, feature map,
 // the filter matrix below 4 GiB and one image per launch.  Blocks call it for their 3x3 before anything is launched.
 int check_conv3x3_dims(int H, int W, int C, int K);
 

@@ -1,14 +1,8 @@
 // The fused Winograd F(2x2,3x3) kernel, as a header so that the library
 // (wino_f2_fused.hip) and the ablation tool (tools/ablate_fused.hip) compile the same source.
 //
-// ABLATE is a debug knob (0 = the product kernel); non-zero values produce wrong results and
-// exist only to price the parts of the kernel:
-//   1 skip the raw-patch LDS-DMA      2 skip the filter LDS-DMA      4 skip the MFMAs
-//   8 skip the per-chunk wait+barrier 16 stamp the main loop (in-kernel clock)
-//   32 skip the A-path reads+transform 64 skip the B-fragment reads  512 skip the output stores
-//   1024 skip the stream-K slab hand-off (partial segments are dropped)
-//   32768 timeline (tools/ablate_fused ... t): s_memrealtime (100 MHz, chip-wide) at kernel entry, first MFMA,
-//         start of the last epilogue and exit of every workgroup, 8 uint64 per workgroup in prm.dbg
+// ABLATE is a developer knob (PROBE_OFF = the product kernel): its bits (PROBE_*) and the stamp buffers the
+// diagnostic builds write (prm.dbg) are listed in wino_probe.h.
 //
 // Work decomposition: the launch's work is a set of "chunk iterations"
 //   (item, chunk),  item = (tile block, k block),  chunk = 8 input channels,
@@ -51,16 +45,8 @@ constexpr int LDS_BYTES = N_RSTAGE * RAW_BYTES + N_USTAGE * U_BYTES;  // 163840 
 constexpr int U_CHUNK_FLOATS = 16 * KB * BC; // 8192 floats per (c-chunk, k-block)
 constexpr int PF = 2;                        // filter-fragment prefetch distance (points); 2..6 measured equal
 constexpr int SLAB_BYTES = TB * 4 * KB * 4;  // 65536: pre-BN output of one item (64 tiles x 2x2 px x 64 k)
-#ifndef WINO_UNROLL2
-#define WINO_UNROLL2 1   // two copies of the loop body, one per raw-stage parity: the stage is an immediate of the patch reads
-#endif
-#ifndef WINO_SCALAR_BTDB
-#define WINO_SCALAR_BTDB 0
-#endif
-#ifndef WINO_DMA0
-#define WINO_DMA0 4   // tools/ablate_fused, current loop: 0 / 2 / 4 / 6 / 8 give 42.7 / 42.5 / 42.45 / 42.5 / 42.7 cycles per MFMA
-#endif
-constexpr int DMA0 = WINO_DMA0;              // first point-step that issues an LDS-DMA piece
+constexpr int DMA0 = 4;                      // first point-step that issues an LDS-DMA piece; tools/ablate_fused, current loop:
+                                             // 0 / 2 / 4 / 6 / 8 give 42.7 / 42.5 / 42.45 / 42.5 / 42.7 cycles per MFMA
 
 // s_waitcnt lgkmcnt(n) alone (vmcnt/expcnt fields at "no wait"); n folds to a literal once the
 // point loop is unrolled.
@@ -185,7 +171,7 @@ struct FusedParams {
   float* slabs;
   unsigned* tickets;
   unsigned* err;               // host-visible word, set when a ticket is drawn on a counter that was not zero at launch
-  unsigned long long* dbg;     // diagnostic builds only (ABLATE & (16 | 2048)): where the stamps go
+  unsigned long long* dbg;     // diagnostic builds only (PROBE_CLOCK, PROBE_PHASES, PROBE_TIMELINE): where the stamps go
 };
 // The arguments of the RES = true kernels: the plain ones, then the residual (padded like `out`; its ring is not read).
 // The residual goes behind every existing field in a struct of its own rather than into FusedParams, so that the plain
@@ -279,18 +265,18 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   const int G = gridDim.x;
   const int lg = (int)(blockIdx.x & 7) * (G >> 3) + ((int)(blockIdx.x & 7) < (G & 7) ? (int)(blockIdx.x & 7) : (G & 7)) +
                  (int)(blockIdx.x >> 3);
-  if (ABLATE & 32768) {
+  if (ABLATE & PROBE_TIMELINE) {
     if (threadIdx.x == 0) {
-      prm.dbg[(size_t)lg * 8 + 0] = __builtin_amdgcn_s_memrealtime();
-      prm.dbg[(size_t)lg * 8 + 4] = __builtin_amdgcn_s_memtime();
+      prm.dbg[(size_t)lg * TL_WORDS + TL_ENTRY] = __builtin_amdgcn_s_memrealtime();
+      prm.dbg[(size_t)lg * TL_WORDS + TL3_ENTRY_CYC] = __builtin_amdgcn_s_memtime();
     }
   }
-  if (ABLATE == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+  if (ABLATE == PROBE_OFF && blockIdx.x == 0 && threadIdx.x == 0) {
     wino_clk_slot_3x3[0] = __builtin_amdgcn_s_memtime();
     wino_clk_slot_3x3[1] = __builtin_amdgcn_s_memrealtime();
   }
   auto clk_exit = [&]() {
-    if (ABLATE == 0 && blockIdx.x == 0 && threadIdx.x == 0) {
+    if (ABLATE == PROBE_OFF && blockIdx.x == 0 && threadIdx.x == 0) {
       wino_clk_slot_3x3[2] = __builtin_amdgcn_s_memtime();
       wino_clk_slot_3x3[3] = __builtin_amdgcn_s_memrealtime();
     }
@@ -317,7 +303,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   // and drain while the first LDS-DMA pieces are in flight.  (Per tile in the epilogue, the ring
   // cost more than the tiles' own stores: sparse predicated stores and their address arithmetic.)
   auto ring_pass = [&]() {
-    if (ABLATE & 512) return;
+    if (ABLATE & PROBE_NO_STORE) return;
     // (POOL: the ring of the pooled output, (H/2 + 2) x (W/2 + 2))
     const unsigned Hi = GEN ? (unsigned)prm.geo.Hp : (unsigned)WINO_HW, Wi = GEN ? (unsigned)prm.geo.Wp : (unsigned)WINO_HW;
     const unsigned Hp = POOL ? (Hi - 2u) / 2u + 2u : Hi, Wp = POOL ? (Wi - 2u) / 2u + 2u : Wi;
@@ -375,8 +361,8 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   // and px+8 share a base register but are never read in the same pinned step.
   // The three patch rows R0, R1, R2 this wave reads are (d0, d2, d1) for ph = 0 and (d2, d1, d3) for
   // ph = 1: then B^T d, rows 2 ph and 2 ph + 1, is  R0 - R1  and  R1 + s2 * R2  with s2 = +1 / -1 for
-  // both halves (one code path).  One address register per pixel (12; the raw stage is selected by
-  // bit 15 of each, flipped after every iteration).
+  // both halves (one code path).  One address register per pixel (12; they point into R0, and the raw stage is a
+  // compile-time offset of each read: see body()).
   int a_adr[3][4];
 #pragma unroll
   for (int k = 0; k < 3; k++) {
@@ -387,7 +373,6 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       a_adr[k][j] = a_base + (((px & 7) ^ a_sw) << 5) + ((px >> 3) << 8);
     }
   }
-#define A_OFF(k, j) (a_adr[k][j])
   // B: logical column block cb' of this wave is out-channel block cb' ^ 2 ph of the item (k_local =
   // (cb' ^ 2 ph) * 16 + t16): cb' = 0, 1 are the two blocks the wave keeps after the epilogue exchange,
   // cb' = 2, 3 the two it hands to its partner -- compile-time indices either way.  The byte offset of
@@ -403,25 +388,8 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   // B^T d B pieces (d, tmp, v are [row i][col j] = index 4i + j; Winograd point e = 4i + j), on
   // channel pairs (v_pk_add_f32)
   typedef f32x2 P2;
-#if WINO_SCALAR_BTDB
-  // experiment: plain v_sub_f32 / v_add_f32 pairs instead of v_pk_add_f32 (asm: the SLP vectoriser
-  // would fuse plain C++ back into packed ops)
-  auto sub2 = [](const P2& a, const P2& b) {
-    P2 r;
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r.x) : "v"(a.x), "v"(b.x));
-    asm("v_sub_f32 %0, %1, %2" : "=v"(r.y) : "v"(a.y), "v"(b.y));
-    return r;
-  };
-  auto add2 = [](const P2& a, const P2& b) {
-    P2 r;
-    asm("v_add_f32 %0, %1, %2" : "=v"(r.x) : "v"(a.x), "v"(b.x));
-    asm("v_add_f32 %0, %1, %2" : "=v"(r.y) : "v"(a.y), "v"(b.y));
-    return r;
-  };
-#else
   auto sub2 = [](const P2& a, const P2& b) { return a - b; };
   auto add2 = [](const P2& a, const P2& b) { return a + b; };
-#endif
   const float s2f = ph ? -1.f : 1.f;
   const P2 s2 = {s2f, s2f};
   // d[k*4 + j] = patch row R_k, column j;  tmp[i'*4 + j] = (B^T d) row 2 ph + i', column j;
@@ -438,7 +406,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     if (j == 3) v[e] = sub2(tmp[i * 4 + 1], tmp[i * 4 + 3]);
   };
 
-  unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0;   // ABLATE & 2048: phase stamps
+  unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0;   // ABLATE & PROBE_PHASES: phase stamps
   unsigned long long st_ph[4] = {0, 0, 0, 0};   // epilogue phases: barrier, A^T m A, slab+ticket, gather+finalize
   auto stamp = [&]() -> unsigned long long {
     unsigned long long t;
@@ -535,11 +503,11 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   //    fragments of iteration i+1 are requested BEFORE the iteration barrier and the MFMAs
   //    resume right after it instead of eating an LDS round trip.
   auto issue_raw1 = [&](int rstage, int j) {  // one 1-KiB piece
-    if (ABLATE & 1) return;
+    if (ABLATE & PROBE_NO_DMA_A) return;
     dma16_buf(rsrc_in, raw_off[j], d_soff_raw, smem + rstage * RAW_BYTES + (8 * j + w) * 1024);
   };
   auto issue_u1 = [&](int ustage, int j) {
-    if (ABLATE & 2) return;
+    if (ABLATE & PROBE_NO_DMA_B) return;
     dma16_buf(rsrc_u, u_off, d_soff_u + j * 8192,
               smem + N_RSTAGE * RAW_BYTES + ustage * U_BYTES + (8 * j + w) * 1024);
   };
@@ -580,14 +548,14 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   for (int j = 0; j < 4; j++) issue_u1(0, j);
   // The DMA walker never leaves this workgroup's range: it stops on the last chunk, and the
   // last two iterations of the range fetch that chunk again into stages nobody reads (see body()).
-  if ((ABLATE & 32768) && tid == 0) prm.dbg[(size_t)lg * 8 + 6] = __builtin_amdgcn_s_memrealtime();   // first stage requested
+  if ((ABLATE & PROBE_TIMELINE) && tid == 0) prm.dbg[(size_t)lg * TL_WORDS + TL3_STAGE_REQ] = __builtin_amdgcn_s_memrealtime();   // first stage requested
   if (L > 1) dma_advance();
   ring_pass();   // in the shadow of the first pieces' flight
-  if (!(ABLATE & 8)) {
+  if (!(ABLATE & PROBE_NO_SYNC)) {
     wait_vmem_all();
     __syncthreads();
   }
-  if ((ABLATE & 32768) && tid == 0) prm.dbg[(size_t)lg * 8 + 7] = __builtin_amdgcn_s_memrealtime();   // ... and landed
+  if ((ABLATE & PROBE_TIMELINE) && tid == 0) prm.dbg[(size_t)lg * TL_WORDS + TL3_STAGE_IN] = __builtin_amdgcn_s_memrealtime();   // ... and landed
   if (L > 1) {
 #pragma unroll
     for (int j = 0; j < 4; j++) issue_raw1(1, j);
@@ -600,7 +568,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
 #pragma unroll
     for (int k = 0; k < 3; k++)
 #pragma unroll
-      for (int j = 0; j < 4; j++) d[k * 4 + j] = lds_read2(A_OFF(k, j));
+      for (int j = 0; j < 4; j++) d[k * 4 + j] = lds_read2(a_adr[k][j]);
     P2 tmp[8];
 #pragma unroll
     for (int j = 0; j < 4; j++) tmp_col(tmp, d, j);
@@ -612,29 +580,24 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       bfn[e][1] = lds_read2(b_base[2 * (e & 1) + 1] + (e >> 1) * 2048);
     }
   }
-#if !WINO_UNROLL2
-#pragma unroll
-  for (int k = 0; k < 3; k++)
-#pragma unroll
-    for (int j = 0; j < 4; j++) a_adr[k][j] ^= RAW_BYTES;   // iteration 0 reads raw_1 from R1
-#endif
-  if (ABLATE & 32768) {
-    if (tid == 0) prm.dbg[(size_t)lg * 8 + 1] = __builtin_amdgcn_s_memrealtime();
+  if (ABLATE & PROBE_TIMELINE) {
+    if (tid == 0) prm.dbg[(size_t)lg * TL_WORDS + TL_FIRST] = __builtin_amdgcn_s_memrealtime();
   }
-  if (ABLATE & 16) {  // diagnostic build only: in-kernel clock = d(s_memtime) / d(s_memrealtime)
+  if (ABLATE & PROBE_CLOCK) {  // diagnostic build only: in-kernel clock = d(s_memtime) / d(s_memrealtime)
     // The start stamps go to memory at once: kept in SGPRs across the main loop (which has none to
     // spare) they pushed loop-carried scalars into VGPRs and the build ran 15 % slower than the
     // product kernel -- not a faithful probe of its clock.
     if (tid == 0) {
-      prm.dbg[(size_t)lg * 4 + 0] = __builtin_amdgcn_s_memtime();
-      prm.dbg[(size_t)lg * 4 + 1] = __builtin_amdgcn_s_memrealtime();
+      prm.dbg[(size_t)lg * CLK_WORDS + CLK_BEGIN_CYC] = __builtin_amdgcn_s_memtime();
+      prm.dbg[(size_t)lg * CLK_WORDS + CLK_BEGIN_RT] = __builtin_amdgcn_s_memrealtime();
     }
   }
 
-  // One pipeline step = iteration `it`.  ONE instantiation: the raw stage that holds raw_{it+1}
-  // is selected by bit 15 of the twelve patch address registers a_adr[][] (R0 at 0, R1 at 32768; they
-  // are flipped after every iteration), the filter stage (it % 3) is a run-time offset added to
-  // the two fragment base registers, the DMA destinations are scalar.
+  // One pipeline step = iteration `it`.  The body exists twice, once per parity of `it` (par_c): iteration `it`
+  // reads raw_{it+1} from R[(it + 1) & 1], which is then a compile-time offset (ROFF) of the patch reads -- the
+  // twelve address registers a_adr[][] stay on R0 (flipping bit 15 of each after every iteration instead cost
+  // twelve v_xor per iteration).  The filter stage (it % 3) is a run-time offset added to the fragment base
+  // registers, the DMA destinations are scalar.
   // The schedule inside is pinned with sched_barrier(0): left alone, hipcc sinks every
   // ds_read to just before its first use and the wave eats one LDS latency per point.
   int ub_cur[4], ub_nxt[4];   // b_base[] + the byte offset of filter stage it % 3 / (it + 1) % 3
@@ -643,17 +606,14 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     ub_cur[cb] = b_base[cb];
     ub_nxt[cb] = b_base[cb] + U_BYTES;
   }
-  // (WINO_UNROLL2: the body exists twice, once per parity of `it`; iteration `it` reads raw_{it+1} from
-  //  R[(it + 1) & 1], which is then a compile-time offset of the patch reads -- a_adr[][] stay on R0 and the
-  //  twelve v_xor toggles per iteration go away.)
-  auto body = [&](auto par_c, int it, int rs_dma, int us_cur, int us_nxt, int us_dma) {
-    constexpr int ROFF = WINO_UNROLL2 ? (decltype(par_c)::value ? 0 : RAW_BYTES) : 0;
-    if (ABLATE & 2048) { const unsigned long long t = stamp(); if (it) st_comp += t - st_prev; st_prev = t; }
-    if (!(ABLATE & 8)) {
+  auto body = [&](auto par_c, int it, int rs_dma, int us_dma) {
+    constexpr int ROFF = decltype(par_c)::value ? 0 : RAW_BYTES;
+    if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (it) st_comp += t - st_prev; st_prev = t; }
+    if (!(ABLATE & PROBE_NO_SYNC)) {
       wait_vmem_all();   // my DMA pieces of raw_{it+1} and U_{it+1} have landed
       __syncthreads();   // everyone's have; everyone is done with the stages refilled below
     }
-    if (ABLATE & 2048) { const unsigned long long t = stamp(); st_wait += t - st_prev; st_prev = t; }
+    if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_wait += t - st_prev; st_prev = t; }
     // The 8 LDS-DMA pieces this wave contributes per iteration (4 of raw_{it+2} into R[it&1], 4 of
     // U_{it+2} into U[(it+2)%3]) are issued one per step in steps DMA0..DMA0+7 instead of in a
     // burst here: an LDS-DMA instruction holds the wave's issue port for >100 cycles, and
@@ -665,16 +625,15 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     // fetch, the walker stands on the range's last chunk (valid addresses) and the pieces land in
     // R[it&1] / U[(it+2)%3] like any others: free stages, disjoint from the ones an epilogue
     // stages its stores in, and drained by the next iteration's vmcnt(0) or by the one before exit.
-    // raw_{it+1}: the stage is in a_adr[][]
+    // raw_{it+1}: the stage is ROFF
     // fragment base addresses of U_it and U_{it+1}: ub_cur[] / ub_nxt[], loop-carried registers that are
     // rotated in the iteration's tail (where the wave would wait at the barrier anyway) -- formed here, at
     // the top, their eight adds sit in front of the iteration's first MFMAs; left inside the reads,
-    // hipcc re-adds the stage offset before every one.  (us_cur / us_nxt: kept for the interface.)
-    (void)us_cur; (void)us_nxt;
-    // (WINO_UNROLL2: the two copies of the body use the two register sets in swapped roles, so the rotation
+    // hipcc re-adds the stage offset before every one.
+    // (the two copies of the body use the two register sets in swapped roles, so the rotation
     //  is four adds into the set that has just gone dead instead of four moves and four adds)
-    const int (&ucur)[4] = (WINO_UNROLL2 && decltype(par_c)::value) ? ub_nxt : ub_cur;
-    const int (&unxt)[4] = (WINO_UNROLL2 && decltype(par_c)::value) ? ub_cur : ub_nxt;
+    const int (&ucur)[4] = decltype(par_c)::value ? ub_nxt : ub_cur;
+    const int (&unxt)[4] = decltype(par_c)::value ? ub_cur : ub_nxt;
     // filter fragment of step s (point s >> 1, column blocks 2 (s & 1) + c)
     auto bread = [&](const int (&base)[4], int s2_, int c) {
       return lds_read2(base[2 * (s2_ & 1) + c] + (s2_ >> 1) * 2048);
@@ -690,7 +649,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       const int pt = e >> 1, cbp = e & 1;
       // -- top of the step: every LDS request of this step, before any MFMA.  Consumers sit
       //    at least one step later, so their waits are counted (lgkmcnt(N)), not drains.
-      if (ABLATE & 64) {
+      if (ABLATE & PROBE_NO_B_READS) {
         const f32x2 fake = {v[(e + 3) & 7].x, v[(e + 5) & 7].y};
         if (e + PF < 16) { bf[e + PF][0] = fake; bf[e + PF][1] = fake; }
         else { bfn[e + PF - 16][0] = fake; bfn[e + PF - 16][1] = fake; }
@@ -717,22 +676,22 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       // (+8 %); the two waves of a SIMD phase-shifted (+6 %).
       // (After the last iteration this works on stale LDS; the result is never used -- cheaper
       // than a branch.)
-      if (e < 6 && !(ABLATE & 32)) {
+      if (e < 6 && !(ABLATE & PROBE_NO_A_PATH)) {
         const int q0 = 2 * e, q1 = 2 * e + 1;   // read index q -> (row k = q % 3, column j = q / 3)
-        d[(q0 % 3) * 4 + q0 / 3] = lds_read2(A_OFF(q0 % 3, q0 / 3) + ROFF);
-        d[(q1 % 3) * 4 + q1 / 3] = lds_read2(A_OFF(q1 % 3, q1 / 3) + ROFF);
+        d[(q0 % 3) * 4 + q0 / 3] = lds_read2(a_adr[q0 % 3][q0 / 3] + ROFF);
+        d[(q1 % 3) * 4 + q1 / 3] = lds_read2(a_adr[q1 % 3][q1 / 3] + ROFF);
       }
       __builtin_amdgcn_sched_barrier(0);
-      if (!(ABLATE & 96)) wait_lds(lds_wait_count(e));
+      if (!(ABLATE & (PROBE_NO_A_PATH | PROBE_NO_B_READS))) wait_lds(lds_wait_count(e));
       __builtin_amdgcn_sched_barrier(0);
-      if (e >= 3 && e <= 7 && e != 5 && !(ABLATE & 32) && !(ABLATE & 8192)) tmp_col(tmp, d, e == 3 ? 0 : e == 4 ? 1 : e == 6 ? 2 : 3);
-      if ((ABLATE & 8192) && e == 7) {
+      if (e >= 3 && e <= 7 && e != 5 && !(ABLATE & PROBE_NO_A_PATH) && !(ABLATE & PROBE_NO_BTDB)) tmp_col(tmp, d, e == 3 ? 0 : e == 4 ? 1 : e == 6 ? 2 : 3);
+      if ((ABLATE & PROBE_NO_BTDB) && e == 7) {
 #pragma unroll
         for (int i = 0; i < 12; i++) asm volatile("" :: "v"(d[i]));
       }
       const P2 a = v[pt];
       const f32x2 b0 = bf[e][0], b1 = bf[e][1];
-      if (ABLATE & 4) {  // keep the operands live, skip the matrix pipe
+      if (ABLATE & PROBE_NO_MFMA) {  // keep the operands live, skip the matrix pipe
         asm volatile("" ::"v"(a.x), "v"(a.y), "v"(b0.x), "v"(b0.y), "v"(b1.x), "v"(b1.y));
       } else {
         // Tied destination: the accumulate chain stays in place (same vDst as SrcC is the
@@ -746,11 +705,11 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 0]) : "v"(a.y), "v"(b0.y));
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 1]) : "v"(a.y), "v"(b1.y));
       }
-      if ((ABLATE & 4096) && !(ABLATE & 8192) && e == 9) {
+      if ((ABLATE & PROBE_NO_VPOINT) && !(ABLATE & PROBE_NO_BTDB) && e == 9) {
 #pragma unroll
         for (int i = 0; i < 8; i++) asm volatile("" :: "v"(tmp[i]));
       }
-      if (!(ABLATE & 32) && !(ABLATE & (4096 | 8192))) {
+      if (!(ABLATE & PROBE_NO_A_PATH) && !(ABLATE & (PROBE_NO_VPOINT | PROBE_NO_BTDB))) {
         // point p retires with step 2 p + 1; all patch reads are in by step 7
         if (e >= 9 && e < 15) v_point(v, tmp, e - 9);   // points 0..5
         if (e == 15) {
@@ -780,7 +739,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   // (raw_{it+1} is already in registers, U_it is spent); each wave takes 8 KiB of them.
   auto epilogue = [&](bool last_of_range, int rfree, int ufree) {
     unsigned long long ph_t = 0;
-    auto phase = [&](int k) { if (ABLATE & 2048) { const unsigned long long t = stamp(); if (k >= 0) st_ph[k] += t - ph_t; ph_t = t; } };
+    auto phase = [&](int k) { if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (k >= 0) st_ph[k] += t - ph_t; ph_t = t; } };
     phase(-1);
     // every wave is done reading those two stages (a bare barrier: no memory counter needs to
     // drain here, and __syncthreads() would wait for the LDS-DMA pieces in flight)
@@ -921,7 +880,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     unsigned old0 = 0;
     if (whole) {
       job0 = c_item;
-    } else if (!(ABLATE & 1024)) {
+    } else if (!(ABLATE & PROBE_NO_HANDOFF)) {
       // slab slot: 2l for the segment that continues an item (head of l's range), 2l+1 for the
       // one that starts an item
       const TailPos tp = tail_pos();
@@ -999,7 +958,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       }
       float sc2[2] = {bn_sc[0], bn_sc[1]}, bi2[2] = {bn_bi[0], bn_bi[1]};
       if (item != c_item) load_bn(item, sc2, bi2);   // the deferred head item
-      if (ABLATE & 512) continue;  // price the store tail
+      if (ABLATE & PROBE_NO_STORE) continue;  // price the store tail
 
       // ---- finalize: BN + ReLU, then the wave's 16 tiles x 2x2 px x 32 out-channels go through
       // its private 8 KiB of LDS so that they leave as whole 128-byte runs of the padded NHWC
@@ -1143,12 +1102,6 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       c_chunk = 0;   // every later segment starts its item
       int us_last = us;
       auto tail = [&](auto par_c) {   // everything between two bodies
-#if !WINO_UNROLL2
-#pragma unroll
-        for (int k = 0; k < 3; k++)
-#pragma unroll
-          for (int j = 0; j < 4; j++) a_adr[k][j] ^= RAW_BYTES;
-#endif
         if (it + 3 < L) dma_advance();
         us_last = us;
         us = next(us);
@@ -1157,48 +1110,35 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
           const int off = next(us) * U_BYTES;
 #pragma unroll
           for (int cb = 0; cb < 4; cb++) {
-#if WINO_UNROLL2
             // the set the body just used as "current" is dead: it becomes the next body's "next"
             if (decltype(par_c)::value) ub_nxt[cb] = b_base[cb] + off;
             else ub_cur[cb] = b_base[cb] + off;
-#else
-            ub_cur[cb] = ub_nxt[cb];
-            ub_nxt[cb] = b_base[cb] + off;
-#endif
           }
         }
       };
-#if WINO_UNROLL2
       {
         int k = n;
 #pragma unroll 1
         for (;;) {
           if (!(it & 1)) {
-            body(std::integral_constant<int, 0>{}, it, 0, us, next(us), next(next(us)));
+            body(std::integral_constant<int, 0>{}, it, 0, next(next(us)));
             tail(std::integral_constant<int, 0>{});
             if (--k == 0) break;
           }
-          body(std::integral_constant<int, 1>{}, it, 1, us, next(us), next(next(us)));
+          body(std::integral_constant<int, 1>{}, it, 1, next(next(us)));
           tail(std::integral_constant<int, 1>{});
           if (--k == 0) break;
         }
       }
-#else
-#pragma unroll 1
-      for (int k = n; k > 0; k--) {
-        body(std::integral_constant<int, 0>{}, it, it & 1, us, next(us), next(next(us)));
-        tail(std::integral_constant<int, 0>{});
-      }
-#endif
       // the segment's last iteration was it-1: raw stage R[it & 1] and filter stage U[us_last] are free
       const bool last_of_range = it == L;
-      if (ABLATE & 2048) { const unsigned long long t = stamp(); st_comp += t - st_prev; st_prev = t; }
-      if ((ABLATE & 32768) && last_of_range && tid == 0) {
+      if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_comp += t - st_prev; st_prev = t; }
+      if ((ABLATE & PROBE_TIMELINE) && last_of_range && tid == 0) {
         KernargPtr kp = kernarg();
-        kp->dbg[(size_t)lg * 8 + 2] = __builtin_amdgcn_s_memrealtime();
+        kp->dbg[(size_t)lg * TL_WORDS + TL_LAST_EPI] = __builtin_amdgcn_s_memrealtime();
       }
       epilogue(last_of_range, (it & 1) * RAW_BYTES, N_RSTAGE * RAW_BYTES + us_last * U_BYTES);
-      if (ABLATE & 2048) { const unsigned long long t = stamp(); st_epi += t - st_prev; st_prev = t; }
+      if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_epi += t - st_prev; st_prev = t; }
       if (last_of_range) break;
       c_tail = __builtin_amdgcn_readfirstlane(c_tail_vg);
       if (c_tail < 0) {   // tail done: first whole item
@@ -1210,36 +1150,35 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       asm volatile("" : "+v"(c_item_vg), "+v"(c_tail_vg));
     }
   }
-#undef A_OFF
   wait_vmem_all();   // no LDS-DMA of this wave may land after the workgroup's LDS has been given away
   clk_exit();
 
   // diagnostic builds: the stamps go to a buffer of their own (prm.dbg), never into an output
-  if (ABLATE & 2048) {
+  if (ABLATE & PROBE_PHASES) {
     if (lane == 0) {
-      unsigned long long* dbg = prm.dbg + ((size_t)lg * 8 + w) * 8;
-      dbg[0] = st_wait;
-      dbg[1] = st_comp;
-      dbg[2] = st_epi;
-      dbg[3] = st_ph[0];
-      dbg[4] = st_ph[1];
-      dbg[5] = st_ph[2];
-      dbg[6] = st_ph[3];
+      unsigned long long* dbg = prm.dbg + ((size_t)lg * PH_WAVES + w) * PH_WORDS;
+      dbg[PH_WAIT] = st_wait;
+      dbg[PH_COMPUTE] = st_comp;
+      dbg[PH_EPILOGUE] = st_epi;
+      dbg[PH_EPI0 + 0] = st_ph[0];
+      dbg[PH_EPI0 + 1] = st_ph[1];
+      dbg[PH_EPI0 + 2] = st_ph[2];
+      dbg[PH_EPI0 + 3] = st_ph[3];
     }
   }
-  if (ABLATE & 32768) {
+  if (ABLATE & PROBE_TIMELINE) {
     if (tid == 0) {
       KernargPtr kp = kernarg();
-      kp->dbg[(size_t)lg * 8 + 3] = __builtin_amdgcn_s_memrealtime();
-      kp->dbg[(size_t)lg * 8 + 5] = __builtin_amdgcn_s_memtime();
+      kp->dbg[(size_t)lg * TL_WORDS + TL_EXIT] = __builtin_amdgcn_s_memrealtime();
+      kp->dbg[(size_t)lg * TL_WORDS + TL3_EXIT_CYC] = __builtin_amdgcn_s_memtime();
     }
   }
-  if (ABLATE & 16) {
+  if (ABLATE & PROBE_CLOCK) {
     if (tid == 0) {
       KernargPtr kp = kernarg();
-      unsigned long long* dbg = kp->dbg + (size_t)lg * 4;
-      dbg[2] = __builtin_amdgcn_s_memtime();
-      dbg[3] = __builtin_amdgcn_s_memrealtime();
+      unsigned long long* dbg = kp->dbg + (size_t)lg * CLK_WORDS;
+      dbg[CLK_END_CYC] = __builtin_amdgcn_s_memtime();
+      dbg[CLK_END_RT] = __builtin_amdgcn_s_memrealtime();
     }
   }
 }

@@ -2,7 +2,7 @@
 // wino_f2_fused.hip (the plain epilogue, EPI = EPI_PLAIN), conv3x3_res.hip (the residual epilogue, EPI = EPI_RES: the
 // second 3x3 of a ResNet basic block) and conv3x3_pool.hip (the pooled epilogue, EPI = EPI_POOL: a VGG layer followed
 // by MaxPool2d(2, 2)).  A template is instantiated where it is used, so each file compiles the kernels of its
-// own epilogue and no others.  The planner (plan_3x3, plan_3x3_here) is defined once, in wino_f2_fused.hip: a residual
+// own epilogue and no others.  The planner (plan_3x3, plan_3x3_here) is defined once, in wino_f2_plan.hip: a residual
 // launch and a pooled launch take exactly the plan of the plain layer of the same shape.
 #pragma once
 #include "wino_f2_small_kernel.h"
@@ -53,19 +53,8 @@ inline int check_conv3x3(int N, int H, int W, int C, int K) {
   return WINO_OK;
 }
 
-// Two kernels, same arithmetic: the throughput kernel (64-tile x 64-out-channel items, 8-wave
-// workgroups, whole-item rounds + stream-K tail) and the one-wave-per-SIMD latency kernel (blocks of 16 tiles
-// x 16 CT out-channels, CT = 1, 2 or 4; any feature map; wino_f2_small_kernel.h), which wins while its blocks fit
-// ONE round of the CUs (a second round of blocks doubles the latency kernel's time at once).
-// While the blocks leave CUs idle the latency kernel also splits a block's contraction over S workgroups
-// (C-split): S as large as the idle CUs allow (at most 8, and every wave of the S workgroups gets a task in the
-// first round: 4 S <= 2 C / 16).
-// Among the block widths that fit, the one with the shortest modelled time (small_form below; least squares over the
-// forms measured by tools/latency_cases.py explore3, profiles/r3/), and only while that beats the throughput kernel's
-// fitted time in this regime, 18.8 us + 0.0174 us x C + 1.94 us x (chunk iterations per CU) (54 points at 64 ... 512
-// channels, within 3 us): the latency kernel's price per task grows with C, and from 384 channels on a full round of
-// its blocks is the slower launch.
-// WINO_3X3_ALGO=big|small, WINO_SMALL_SPLIT, WINO_SMALL_CT override.
+// The latency kernel's form for one launch (wino_f2_small_kernel.h), or use = false: the throughput kernel runs.  The
+// policy is small_plan's (wino_f2_plan.hip).
 struct SmallPlan {
   bool use;
   int split, nT16;       // nT16: blocks of 16 tiles

@@ -74,7 +74,7 @@ struct SmallParams {
   float* slabs;              // [block][S] x CT x 4 KB (S > 1 only)
   unsigned* tickets;         // [block]
   unsigned* err;             // host-visible word: set when a ticket counter was found dirty (S > 1 only)
-  unsigned long long* dbg;   // timeline build only (DIAG, tools/small_timeline): 8 stamps per workgroup
+  unsigned long long* dbg;   // timeline build only (DIAG, tools/small_timeline): SM_WORDS stamps per workgroup
   Geo geo;                   // GEN = true only: the feature map (other than the reference's 14 x 14)
 };
 // RES = true: the plain arguments, then the residual, padded like `out` (its ring is not read); a struct of its own, as
@@ -87,7 +87,7 @@ using SmallArgs = std::conditional_t<RES, SmallResParams, SmallParams>;
 
 // DIAG = true is the timeline build (tools/small_timeline.hip): wave 0 of every workgroup stores s_memrealtime
 // (100 MHz, chip-wide) at entry, first stage in LDS, MFMAs done, LDS level done, slab drained, ticket drawn, gather
-// landed, exit.  The product kernel is DIAG = false.
+// landed, exit (the SM_* slots of wino_probe.h).  The product kernel is DIAG = false.
 // RES = the residual epilogue: out = act(scale*conv + bias + res), res padded like out, read by the finishing lane at
 // its store's own offset just before the store (so out may be res); the ReLU follows the add.
 // POOL = the pooled epilogue: out = maxpool2x2_s2(act(scale*conv + bias)), [N][H/2+2][W/2+2][K] with its zero ring.  The
@@ -115,11 +115,11 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
   auto mark = [&](int i) {
     if (DIAG && threadIdx.x == 0) {
       __builtin_amdgcn_sched_barrier(0);
-      prm.dbg[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * 8 + i] = __builtin_amdgcn_s_memrealtime();   // (any order: the tool sorts)
+      prm.dbg[((size_t)(blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x) * SM_WORDS + i] = __builtin_amdgcn_s_memrealtime();   // (any order: the tool sorts)
       __builtin_amdgcn_sched_barrier(0);
     }
   };
-  mark(0);
+  mark(SM_ENTRY);
   const bool clk = blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && threadIdx.x == 0;
   if (clk) {
     wino_clk_slot_3x3[0] = __builtin_amdgcn_s_memtime();
@@ -254,7 +254,7 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
   __builtin_amdgcn_sched_barrier(0);
   store_a(0);
   __syncthreads();
-  mark(1);
+  mark(SM_STAGED);
 #pragma unroll 1
   for (int r = 0; r < nrounds; r++, t += stride) {
     const bool more_a = r + 1 < nrounds;
@@ -333,7 +333,7 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
       }
     }
   if (DIAG) asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-  mark(2);
+  mark(SM_MFMA_DONE);
   // ---- level 1: the workgroup's four partial blocks meet in wave 0 (in wave order); the image reuses the stages
   // (the loop's last barrier is behind every wave's last fragment read)
   f32x4 (*red)[CT * 4][64] = (f32x4(*)[CT * 4][64])smem;
@@ -348,7 +348,7 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
 #pragma unroll
     for (int i = 0; i < CT * 4; i++) y[i >> 2][i & 3] += red[ww][i][lane];
 
-  mark(3);
+  mark(SM_LDS_LEVEL);
   // ---- level 2: the S workgroups of a block meet through write-through slabs + one ticket per workgroup
   if (S > 1) {
     constexpr unsigned SLAB = CT * SMALL_SLAB_BYTES;
@@ -359,12 +359,12 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
     for (int i = 0; i < CT * 4; i++)
       slab_store16(y[i >> 2][i & 3], rsrc_slab, (unsigned)((i * 64 + lane) * 16), base + (unsigned)split * SLAB);
     wait_vmem_all();   // the write-through stores have left ...
-    mark(4);
+    mark(SM_SLAB_OUT);
     unsigned old = 0;
     if (lane == 0)     // ... before the ticket
       old = __hip_atomic_fetch_add(prm.tickets + block, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     old = __builtin_amdgcn_readfirstlane(old);
-    mark(5);
+    mark(SM_TICKET);
     if (old != (unsigned)(S - 1)) {
       if (old >= (unsigned)S && lane == 0) __hip_atomic_store(prm.err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       clk_exit();
@@ -395,7 +395,7 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
     }
   }
 
-  if (DIAG && S > 1) { wait_vmem_all(); mark(6); }
+  if (DIAG && S > 1) { wait_vmem_all(); mark(SM_GATHERED); }
   // ---- finalize: BN + ReLU + 16-byte stores (and the tile's share of the zero ring)
   const int gt = tb16 * 16 + t16;
   if (gt >= totalTiles) { clk_exit(); return; }
@@ -464,7 +464,7 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
       *(f32x4*)(o + (size_t)((oy + 1) * WINO_HW + 15) * K) = zero4;
     }
   }
-  if (DIAG) { wait_vmem_all(); mark(7); }
+  if (DIAG) { wait_vmem_all(); mark(SM_EXIT); }
   clk_exit();
 }
 

@@ -1,5 +1,5 @@
 // Developer tool: prices the parts of the fused Winograd kernel by timing ablated variants
-// (see ABLATE in csrc/wino_f2_fused_kernel.h).  Not part of the library.
+// (ABLATE; the probe bits and stamp layouts are csrc/wino_probe.h).  Not part of the library.
 //   hipcc --offload-arch=gfx950 -O3 -Iinclude -Icuda-winograd_amd/csrc tools/ablate_fused.hip -o tools/ablate_fused
 #include "wino_f2_fused_kernel.h"
 
@@ -8,6 +8,7 @@
 #include <vector>
 
 namespace wino { void set_error(const char*, ...) {} int hip_fail(hipError_t, const char*) { return -1; } }
+using namespace wino;
 using namespace wino::fused;
 
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
@@ -16,6 +17,8 @@ static float* g_slabs;
 static unsigned* g_tickets;
 static unsigned long long* g_dbg;   // stamps of the diagnostic builds
 static unsigned* g_err;              // the library's dirty-counter word (device memory here)
+// the table's combinations
+constexpr int NO_DMA = PROBE_NO_DMA_A | PROBE_NO_DMA_B, NO_AB = PROBE_NO_A_PATH | PROBE_NO_B_READS, NO_OUT = PROBE_NO_STORE | PROBE_NO_HANDOFF;
 static int g_grid = 256;   // logical workgroups (argv[2]); 0 = one whole item per workgroup
 
 static int grid_for(int N, int K) {
@@ -69,35 +72,36 @@ int main(int argc, char** argv) {
   CK(hipMemcpy(b, h.data(), K * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(s, h.data() + K, K * 4, hipMemcpyHostToDevice));
   if (argc > 3 && argv[3][0] == 'w') {  // per-workgroup pass times of the stamped build, with each range's shape
     const int N = 128;
-    run<0>(in, U, b, s, out, N, C, K, 3000);
+    run<PROBE_OFF>(in, U, b, s, out, N, C, K, 3000);
     const int nTB = (N * 49 + TB - 1) / TB, wgs = grid_for(N, K), nch = C / 8;
     const unsigned items = (unsigned)nTB * (K / KB), ndp = items / wgs, Tt = (items % wgs) * nch, q = Tt / wgs, rem = Tt % wgs;
-    run<16>(in, U, b, s, out, N, C, K, 20);
-    std::vector<unsigned long long> st((size_t)wgs * 4);
+    run<PROBE_CLOCK>(in, U, b, s, out, N, C, K, 20);
+    std::vector<unsigned long long> st((size_t)wgs * CLK_WORDS);
     CK(hipMemcpy(st.data(), g_dbg, st.size() * 8, hipMemcpyDeviceToHost));
     printf("lg cycles tail_begin tail_len segments(tail) straddles\n");
     for (int l = 0; l < wgs; l++) {
       const unsigned t0 = sk_start(l, q, rem, wgs), t1 = sk_start(l + 1, q, rem, wgs);
       const int segs = t1 > t0 ? (int)((t1 - 1) / nch - t0 / nch + 1) : 0;
-      printf("%d %llu %u %u %d %d ndp=%u\n", l, st[4 * l + 2] - st[4 * l], t0, t1 - t0, segs, (int)(t0 % nch != 0) + (int)(t1 % nch != 0), ndp);
+      printf("%d %llu %u %u %d %d ndp=%u\n", l, st[CLK_WORDS * l + CLK_END_CYC] - st[CLK_WORDS * l + CLK_BEGIN_CYC], t0, t1 - t0, segs, (int)(t0 % nch != 0) + (int)(t1 % nch != 0), ndp);
     }
     return 0;
   }
   if (argc > 3 && argv[3][0] == 't') {   // timeline: where a launch's wall time goes (chip-wide 100 MHz stamps)
     const int N = argc > 4 ? atoi(argv[4]) : 128;
-    run<0>(in, U, b, s, out, N, C, K, 3000);
-    const float us_prod = run<0>(in, U, b, s, out, N, C, K, 200);
-    const float us_tl = run<32768>(in, U, b, s, out, N, C, K, 200);   // the stamps of the LAST of 200 back-to-back launches stay
+    run<PROBE_OFF>(in, U, b, s, out, N, C, K, 3000);
+    const float us_prod = run<PROBE_OFF>(in, U, b, s, out, N, C, K, 200);
+    const float us_tl = run<PROBE_TIMELINE>(in, U, b, s, out, N, C, K, 200);   // the stamps of the LAST of 200 back-to-back launches stay
     const int wgs = grid_for(N, K);
-    std::vector<unsigned long long> st((size_t)wgs * 8);
+    std::vector<unsigned long long> st((size_t)wgs * TL_WORDS);
+    auto tl = [&](int l, int slot) { return st[(size_t)TL_WORDS * l + slot]; };
     CK(hipMemcpy(st.data(), g_dbg, st.size() * 8, hipMemcpyDeviceToHost));
     unsigned long long t0 = ~0ull, tend = 0;
     std::vector<double> entry, first, lastep, exitt, pro, epi;
-    for (int l = 0; l < wgs; l++) { t0 = std::min(t0, st[8 * l]); tend = std::max(tend, st[8 * l + 3]); }
+    for (int l = 0; l < wgs; l++) { t0 = std::min(t0, tl(l, TL_ENTRY)); tend = std::max(tend, tl(l, TL_EXIT)); }
     for (int l = 0; l < wgs; l++) {
-      entry.push_back((st[8 * l] - t0) * 0.01); first.push_back((st[8 * l + 1] - t0) * 0.01);
-      lastep.push_back((st[8 * l + 2] - t0) * 0.01); exitt.push_back((st[8 * l + 3] - t0) * 0.01);
-      pro.push_back((st[8 * l + 1] - st[8 * l]) * 0.01); epi.push_back((st[8 * l + 3] - st[8 * l + 2]) * 0.01);
+      entry.push_back((tl(l, TL_ENTRY) - t0) * 0.01); first.push_back((tl(l, TL_FIRST) - t0) * 0.01);
+      lastep.push_back((tl(l, TL_LAST_EPI) - t0) * 0.01); exitt.push_back((tl(l, TL_EXIT) - t0) * 0.01);
+      pro.push_back((tl(l, TL_FIRST) - tl(l, TL_ENTRY)) * 0.01); epi.push_back((tl(l, TL_EXIT) - tl(l, TL_LAST_EPI)) * 0.01);
     }
     auto pr = [&](const char* name, std::vector<double> v) {
       std::sort(v.begin(), v.end());
@@ -108,7 +112,7 @@ int main(int argc, char** argv) {
     pr("entry -> first MFMA", pro); pr("last epilogue -> exit", epi);
     {
       std::vector<double> req, land;
-      for (int l = 0; l < wgs; l++) { req.push_back((st[8 * l + 6] - st[8 * l]) * 0.01); land.push_back((st[8 * l + 7] - st[8 * l]) * 0.01); }
+      for (int l = 0; l < wgs; l++) { req.push_back((tl(l, TL3_STAGE_REQ) - tl(l, TL_ENTRY)) * 0.01); land.push_back((tl(l, TL3_STAGE_IN) - tl(l, TL_ENTRY)) * 0.01); }
       pr("entry -> first stage requested", req); pr("entry -> first stage landed", land);
     }
     if (argc > 5) {   // per workgroup, with the shape of its tail range
@@ -124,24 +128,25 @@ int main(int argc, char** argv) {
     return 0;
   }
   if (argc > 3 && argv[3][0] == 'h') {   // timing only: what the parts of the A path cost
-    run<0>(in, U, b, s, out, 128, C, K, 3000);
+    run<PROBE_OFF>(in, U, b, s, out, 128, C, K, 3000);
     for (int i = 0; i < 3; i++)
-      printf("full %.1f   no v_point %.1f   no tmp_col + v_point (reads only) %.1f   no A path %.1f us\n", run<0>(in, U, b, s, out, 128, C, K, 200),
-             run<4096>(in, U, b, s, out, 128, C, K, 200), run<8192>(in, U, b, s, out, 128, C, K, 200), run<32>(in, U, b, s, out, 128, C, K, 200));
+      printf("full %.1f   no v_point %.1f   no tmp_col + v_point (reads only) %.1f   no A path %.1f us\n", run<PROBE_OFF>(in, U, b, s, out, 128, C, K, 200),
+             run<PROBE_NO_VPOINT>(in, U, b, s, out, 128, C, K, 200), run<PROBE_NO_BTDB>(in, U, b, s, out, 128, C, K, 200), run<PROBE_NO_A_PATH>(in, U, b, s, out, 128, C, K, 200));
     return 0;
   }
   if (argc > 3 && argv[3][0] == 'q') {  // quick mode: just the product kernel at N = 128, three trials of 50 launches
-    run<0>(in, U, b, s, out, 128, C, K, 3000);   // clock ramp: ~0.4 s of the same kernel (see bench.py, preheat)
+    run<PROBE_OFF>(in, U, b, s, out, 128, C, K, 3000);   // clock ramp: ~0.4 s of the same kernel (see bench.py, preheat)
     float t[3];
-    for (int i = 0; i < 3; i++) t[i] = run<0>(in, U, b, s, out, 128, C, K, 200);
+    for (int i = 0; i < 3; i++) t[i] = run<PROBE_OFF>(in, U, b, s, out, 128, C, K, 200);
     std::sort(t, t + 3);
     const int nTB = (128 * 49 + TB - 1) / TB, wgs = grid_for(128, K);
     const double iters = (double)nTB * (K / KB) * (C / 8) / wgs;
-    run<16>(in, U, b, s, out, 128, C, K, 3);
-    std::vector<unsigned long long> st((size_t)wgs * 4);
+    run<PROBE_CLOCK>(in, U, b, s, out, 128, C, K, 3);
+    std::vector<unsigned long long> st((size_t)wgs * CLK_WORDS);
     CK(hipMemcpy(st.data(), g_dbg, st.size() * 8, hipMemcpyDeviceToHost));
     double cyc = 0, rt = 0, cmax = 0;
-    for (int i = 0; i < wgs; i++) { const double c = (double)(st[4 * i + 2] - st[4 * i]); cyc += c; rt += (double)(st[4 * i + 3] - st[4 * i + 1]); cmax = std::max(cmax, c); }
+    auto ck = [&](int i, int slot) { return st[(size_t)CLK_WORDS * i + slot]; };
+    for (int i = 0; i < wgs; i++) { const double c = (double)(ck(i, CLK_END_CYC) - ck(i, CLK_BEGIN_CYC)); cyc += c; rt += (double)(ck(i, CLK_END_RT) - ck(i, CLK_BEGIN_RT)); cmax = std::max(cmax, c); }
     printf("%s C=%d grid=%d: %.1f / %.1f / %.1f us   loop+epilogues: %.1f cycles per MFMA per SIMD (slowest workgroup %.1f) at %.3f GHz\n",
            argv[0], C, wgs, t[0], t[1], t[2], cyc / wgs / iters / 128.0, cmax / iters / 128.0, cyc / rt * 0.1);
     return 0;
@@ -152,49 +157,50 @@ int main(int argc, char** argv) {
   for (int N : Ns) {
     const int items = (K / 64) * ((N * 49 + 63) / 64);
     printf("%6d %6d %6d | %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f %8.1f\n", N, items, grid_for(N, K),
-           run<0>(in, U, b, s, out, N, C, K, 20), run<1>(in, U, b, s, out, N, C, K, 20),
-           run<2>(in, U, b, s, out, N, C, K, 20), run<3>(in, U, b, s, out, N, C, K, 20),
-           run<4>(in, U, b, s, out, N, C, K, 20), run<8>(in, U, b, s, out, N, C, K, 20),
-           run<512>(in, U, b, s, out, N, C, K, 20), run<1024>(in, U, b, s, out, N, C, K, 20),
-           run<32>(in, U, b, s, out, N, C, K, 20), run<64>(in, U, b, s, out, N, C, K, 20));
+           run<PROBE_OFF>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_DMA_A>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_DMA_B>(in, U, b, s, out, N, C, K, 20), run<NO_DMA>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_MFMA>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_SYNC>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_STORE>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_HANDOFF>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_A_PATH>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_B_READS>(in, U, b, s, out, N, C, K, 20));
   }
   {  // what the non-MFMA side costs on its own (N = 128): everything below skips the MFMAs
     const int N = 128;
     printf("noMFMA and ... : alone %.1f  noDMA %.1f  noBarr %.1f  noA %.1f  noB %.1f  noA+noB %.1f  noDMA+noA+noB %.1f  noDMA+noBarr+noA+noB %.1f  +noStore+noSlab %.1f\n",
-           run<4>(in, U, b, s, out, N, C, K, 20), run<4 | 3>(in, U, b, s, out, N, C, K, 20), run<4 | 8>(in, U, b, s, out, N, C, K, 20),
-           run<4 | 32>(in, U, b, s, out, N, C, K, 20), run<4 | 64>(in, U, b, s, out, N, C, K, 20), run<4 | 96>(in, U, b, s, out, N, C, K, 20),
-           run<4 | 96 | 3>(in, U, b, s, out, N, C, K, 20), run<4 | 96 | 3 | 8>(in, U, b, s, out, N, C, K, 20),
-           run<4 | 96 | 3 | 8 | 512 | 1024>(in, U, b, s, out, N, C, K, 20));
+           run<PROBE_NO_MFMA>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_MFMA | NO_DMA>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_MFMA | PROBE_NO_SYNC>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_MFMA | PROBE_NO_A_PATH>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_MFMA | PROBE_NO_B_READS>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_MFMA | NO_AB>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_MFMA | NO_AB | NO_DMA>(in, U, b, s, out, N, C, K, 20), run<PROBE_NO_MFMA | NO_AB | NO_DMA | PROBE_NO_SYNC>(in, U, b, s, out, N, C, K, 20),
+           run<PROBE_NO_MFMA | NO_AB | NO_DMA | PROBE_NO_SYNC | NO_OUT>(in, U, b, s, out, N, C, K, 20));
     printf("MFMA and ...   : noDMA+noBarr %.1f  noDMA+noBarr+noA+noB %.1f  +noStore+noSlab %.1f\n",
-           run<3 | 8>(in, U, b, s, out, N, C, K, 20), run<3 | 8 | 96>(in, U, b, s, out, N, C, K, 20),
-           run<3 | 8 | 96 | 512 | 1024>(in, U, b, s, out, N, C, K, 20));
+           run<NO_DMA | PROBE_NO_SYNC>(in, U, b, s, out, N, C, K, 20), run<NO_DMA | PROBE_NO_SYNC | NO_AB>(in, U, b, s, out, N, C, K, 20),
+           run<NO_DMA | PROBE_NO_SYNC | NO_AB | NO_OUT>(in, U, b, s, out, N, C, K, 20));
   }
-  {  // in-kernel clock of the main loop (diagnostic build, ABLATE bit 16)
+  {  // in-kernel clock of the main loop (diagnostic build, PROBE_CLOCK)
     const int N = 128;
     const int nTB = (N * 49 + TB - 1) / TB, wgs = grid_for(N, K);
     const double iters = (double)nTB * (K / KB) * (C / 8) / wgs;   // chunk iterations per workgroup
-    run<16>(in, U, b, s, out, N, C, K, 3);
-    std::vector<unsigned long long> st((size_t)wgs * 4);
+    run<PROBE_CLOCK>(in, U, b, s, out, N, C, K, 3);
+    std::vector<unsigned long long> st((size_t)wgs * CLK_WORDS);
     CK(hipMemcpy(st.data(), g_dbg, st.size() * 8, hipMemcpyDeviceToHost));
     double cyc = 0, rt = 0, cmin = 1e30, cmax = 0;
-    for (int i = 0; i < wgs; i++) { const double c = (double)(st[4 * i + 2] - st[4 * i]); cyc += c; rt += (double)(st[4 * i + 3] - st[4 * i + 1]); cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
+    auto ck = [&](int i, int slot) { return st[(size_t)CLK_WORDS * i + slot]; };
+    for (int i = 0; i < wgs; i++) { const double c = (double)(ck(i, CLK_END_CYC) - ck(i, CLK_BEGIN_CYC)); cyc += c; rt += (double)(ck(i, CLK_END_RT) - ck(i, CLK_BEGIN_RT)); cmin = std::min(cmin, c); cmax = std::max(cmax, c); }
     printf("main loop, N=128: in-kernel clock %.3f GHz; cycles per WG pass mean %.0f min %.0f max %.0f (= %.1f cycles per MFMA per SIMD)\n",
            cyc / rt * 0.1, cyc / wgs, cmin, cmax, cyc / wgs / iters / 128.0);
   }
-  {  // per-wave phase stamps (ABLATE bit 2048): barrier+DMA wait vs compute, in shader cycles
+  {  // per-wave phase stamps (PROBE_PHASES): barrier+DMA wait vs compute, in shader cycles
     const int N = 128;
     const int nTB = (N * 49 + TB - 1) / TB, wgs = grid_for(N, K);
     const double iters = (double)nTB * (K / KB) * (C / 8) / wgs;
-    run<2048>(in, U, b, s, out, N, C, K, 2);
-    std::vector<unsigned long long> st((size_t)wgs * 64);
+    run<PROBE_PHASES>(in, U, b, s, out, N, C, K, 2);
+    std::vector<unsigned long long> st((size_t)wgs * PH_WAVES * PH_WORDS);
     CK(hipMemcpy(st.data(), g_dbg, st.size() * 8, hipMemcpyDeviceToHost));
-    double sum[8][7] = {{0}};
-    for (int i = 0; i < wgs; i++) for (int w = 0; w < 8; w++) for (int k = 0; k < 7; k++) sum[w][k] += st[(i * 8 + w) * 8 + k];
+    double sum[PH_WAVES][PH_USED] = {{0}};
+    for (int i = 0; i < wgs; i++) for (int w = 0; w < PH_WAVES; w++) for (int k = 0; k < PH_USED; k++) sum[w][k] += st[((size_t)i * PH_WAVES + w) * PH_WORDS + k];
     printf("per chunk iteration (%.2f per workgroup), mean over %d workgroups; stamps add overhead, read the SHARES:\n", iters, wgs);
-    for (int w = 0; w < 8; w++)
+    for (int w = 0; w < PH_WAVES; w++)
       printf("  wave %d: wait(vmcnt+barrier) %6.0f  compute %6.0f cycles per iteration (wait share %4.1f%%) | epilogues per workgroup %7.0f cycles = barrier %6.0f + AtmA %6.0f + slab/ticket %6.0f + gather/finalize %6.0f\n", w,
-             sum[w][0] / wgs / iters, sum[w][1] / wgs / iters, 100.0 * sum[w][0] / (sum[w][0] + sum[w][1]), sum[w][2] / wgs,
-             sum[w][3] / wgs, sum[w][4] / wgs, sum[w][5] / wgs, sum[w][6] / wgs);
+             sum[w][PH_WAIT] / wgs / iters, sum[w][PH_COMPUTE] / wgs / iters, 100.0 * sum[w][PH_WAIT] / (sum[w][PH_WAIT] + sum[w][PH_COMPUTE]), sum[w][PH_EPILOGUE] / wgs,
+             sum[w][PH_EPI0 + 0] / wgs, sum[w][PH_EPI0 + 1] / wgs, sum[w][PH_EPI0 + 2] / wgs, sum[w][PH_EPI0 + 3] / wgs);
   }
   return 0;
 }

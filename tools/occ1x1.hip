@@ -5,16 +5,17 @@
 #include <cstdlib>
 #include <vector>
 namespace wino { void set_error(const char*, ...) {} int hip_fail(hipError_t, const char*) { return -1; } }
+using namespace wino;
 using namespace wino::gemm1x1;
 #define CK(x) do { hipError_t e = (x); if (e != hipSuccess) { printf("%s: %s\n", #x, hipGetErrorString(e)); exit(1); } } while (0)
 template <int NW>
 float run(const float* A, const float* B, const float* b, const float* s, float* C, long M, int Cin, int Kout, int lds) {
   using G = Cfg<32, NW>;
-  CK(hipFuncSetAttribute((const void*)(conv1x1_bn_kernel<32, NW, 0>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
+  CK(hipFuncSetAttribute((const void*)(conv1x1_bn_kernel<32, NW, PROBE_OFF>), hipFuncAttributeMaxDynamicSharedMemorySize, 163840));
   const int nMB = (int)((M + BM - 1) / BM);
   const int grid = 8 * (Kout / G::BN) * ((nMB + 7) / 8);
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
-  auto launch = [&] { hipLaunchKernelGGL((conv1x1_bn_kernel<32, NW, 0>), dim3(grid), dim3(G::NT), lds, 0, A, B, b, s, (const float*)nullptr, C, M, Cin, Kout, 1, nMB, 0L, 0L, 0L, SkArgs{nullptr, nullptr, nullptr}, make_padgeo(14, 14), ProjGeo{}); };
+  auto launch = [&] { hipLaunchKernelGGL((conv1x1_bn_kernel<32, NW, PROBE_OFF>), dim3(grid), dim3(G::NT), lds, 0, A, B, b, s, (const float*)nullptr, C, M, Cin, Kout, 1, nMB, 0L, 0L, 0L, SkArgs{nullptr, nullptr, nullptr}, make_padgeo(14, 14), ProjGeo{}); };
   for (int i = 0; i < 10; i++) launch();
   CK(hipDeviceSynchronize());
   float best = 1e9f;
