@@ -271,6 +271,12 @@ def conv1x1_bn(A: torch.Tensor, B: torch.Tensor, bn_bias: torch.Tensor, bn_scale
 
 
 RELU, A_PADDED, C_PADDED, ADD_RESIDUAL = 1, 2, 4, 8  # WINO_* flag bits of wino_conv1x1_bn_ex
+RESIDUAL_UP2 = 16  # WINO_RESIDUAL_UP2: with ADD_RESIDUAL, the residual is the padded coarser map (conv1x1_bn_ex)
+
+
+def _up_hw(h: int, w: int):
+    """The coarser map under an H x W one in a pyramid of stride-2 stages: ((H+1)//2, (W+1)//2)."""
+    return (h + 1) // 2, (w + 1) // 2
 
 
 def residual_block_prepare(N: int, C4: int, Cm: int, H: int = 14, W: int = 14) -> None:
@@ -309,7 +315,10 @@ def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, 
     3x3 layer (flags A_PADDED / C_PADDED), a residual [M][Kout] may be added before the ReLU.
     The feature-map size comes from the padded A, else from a 4-D unpadded A [N][H][W][Cin], else
     from `hw`, else it is the reference's 14 x 14 (wino_conv1x1_bn_ex); anything but 14 x 14 goes
-    through wino_conv1x1_bn_ex_hw."""
+    through wino_conv1x1_bn_ex_hw.
+    With RESIDUAL_UP2 (beside ADD_RESIDUAL) the residual is the padded coarser map [N][Hc+2][Wc+2][Kout],
+    Hc = (H+1)//2, Wc = (W+1)//2, and output pixel (y, x) adds its pixel (y >> 1, x >> 1): the sum with
+    F.interpolate(residual, size=(H, W), mode="nearest") without the upsampled tensor (an FPN's top-down step)."""
     a, bm = _dev(A, "A"), _dev(B, "B")
     b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
     Cin, Kout = int(bm.shape[0]), int(bm.shape[1])
@@ -335,7 +344,17 @@ def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, 
     if padded and M % (H * W):
         raise WinoError(f"padded layouts need M = N*{H}*{W}, got M={M}")
     r = _dev(residual, "residual") if residual is not None else None
-    if r is not None and r.numel() != M * Kout:
+    up2 = bool(flags & RESIDUAL_UP2)
+    if up2:
+        if not flags & ADD_RESIDUAL or r is None:
+            raise WinoError("RESIDUAL_UP2 needs ADD_RESIDUAL and a residual")
+        if M % (H * W):
+            raise WinoError(f"RESIDUAL_UP2 needs M = N*{H}*{W}, got M={M}")
+        Hc, Wc = _up_hw(H, W)
+        if tuple(r.shape) != (M // (H * W), Hc + 2, Wc + 2, Kout):
+            raise WinoError(f"RESIDUAL_UP2: residual must be the padded coarser map "
+                            f"{(M // (H * W), Hc + 2, Wc + 2, Kout)}, got {tuple(r.shape)}")
+    elif r is not None and r.numel() != M * Kout:
         raise WinoError(f"residual must hold M*Kout = {M * Kout} values, got {r.numel()}")
     shape = (M // (H * W), H + 2, W + 2, Kout) if flags & C_PADDED else (M, Kout)
     if out is None:
@@ -347,7 +366,7 @@ def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, 
     _on_current_device(a, bm, b, s, r, out)
     args = (a.data_ptr(), bm.data_ptr(), b.data_ptr(), s.data_ptr(), r.data_ptr() if r is not None else None,
             out.data_ptr())
-    if padded and (H, W) != (14, 14):
+    if up2 or (padded and (H, W) != (14, 14)):
         _check(lib().wino_conv1x1_bn_ex_hw(*args, M // (H * W), H, W, Cin, Kout, int(flags), _stream()),
                "wino_conv1x1_bn_ex_hw")
     else:
@@ -876,6 +895,47 @@ def avgpool7_flatten(feat, in_padded: bool = False, out=None) -> torch.Tensor:
     return out
 
 
+def fpn_level_prepare(N: int, H: int, W: int, Cin: int, Cf: int) -> None:
+    """Allocate the scratch of fpn_level's two launches for the current stream (before graph capture)."""
+    _prepare("wino_fpn_level_prepare_hw", N, H, W, Cin, Cf)
+
+
+def fpn_level(c, w_lat, b_lat, U_out, b_out, top=None, c_padded: bool = False, ones=None, inner=None, out=None):
+    """One level of a Feature Pyramid Network, two HIP launches: inner = conv1x1(c, w_lat) + b_lat
+    [+ nearest_upsample(top)], P = conv3x3(inner, U_out) + b_out.  c [N][H][W][Cin], or [N][H+2][W+2][Cin] with
+    c_padded (ResNet-18 / -34's stage outputs); w_lat [Cin][Cf]; U_out from filter_transform_f2 (Cf -> Cf); top: the
+    coarser level's inner, padded [N][(H+1)//2+2][(W+1)//2+2][Cf], or None on the coarsest level; ones: a vector of Cf
+    ones (made here when left out: keep one when capturing).  Returns (inner, P), both padded [N][H+2][W+2][Cf] with
+    zero rings."""
+    c, w_lat, U_out = _dev(c, "c"), _dev(w_lat, "w_lat"), _dev(U_out, "U_out")
+    b_lat, b_out = _dev(b_lat, "b_lat"), _dev(b_out, "b_out")
+    p = 2 if c_padded else 0
+    if c.dim() != 4 or c.shape[1] <= p or c.shape[2] <= p:
+        raise WinoError("c must be [N][H+2][W+2][Cin]" if c_padded else "c must be [N][H][W][Cin]")
+    N, H, W, Cin = int(c.shape[0]), int(c.shape[1]) - p, int(c.shape[2]) - p, int(c.shape[3])
+    if w_lat.dim() != 2 or int(w_lat.shape[0]) != Cin:
+        raise WinoError("w_lat must be [Cin][Cf]")
+    Cf = int(w_lat.shape[1])
+    if U_out.numel() != 16 * Cf * Cf:
+        raise WinoError(f"U_out must be a {Cf} -> {Cf} filter from filter_transform_f2 (16*Cf*Cf values)")
+    if b_lat.numel() != Cf or b_out.numel() != Cf:
+        raise WinoError("b_lat / b_out must have Cf values")
+    ones = torch.ones(Cf, dtype=torch.float32, device=c.device) if ones is None else _dev(ones, "ones")
+    if ones.numel() != Cf:
+        raise WinoError("ones must have Cf values")
+    if top is not None:
+        Hc, Wc = _up_hw(H, W)
+        top = _out(top, (N, Hc + 2, Wc + 2, Cf), "top")
+    inner = _output(inner, (N, H + 2, W + 2, Cf), c.device, "inner")
+    out = _output(out, (N, H + 2, W + 2, Cf), c.device)
+    _on_current_device(c, w_lat, b_lat, U_out, b_out, ones, top, inner, out)
+    _check(lib().wino_fpn_level_hw(c.data_ptr(), w_lat.data_ptr(), b_lat.data_ptr(), ones.data_ptr(),
+                                   top.data_ptr() if top is not None else None, inner.data_ptr(), U_out.data_ptr(),
+                                   b_out.data_ptr(), ones.data_ptr(), out.data_ptr(), N, H, W, Cin, Cf,
+                                   int(bool(c_padded)), _stream()), "wino_fpn_level_hw")
+    return inner, out
+
+
 def conv1x1_direct(A, B, bn_bias, bn_scale, relu: bool, out=None) -> torch.Tensor:
     a, bm = _dev(A, "A"), _dev(B, "B")
     b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
@@ -899,3 +959,4 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
 
 from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)
 from .vgg import VGG  # noqa: E402
+from .fpn import ResNetFPN  # noqa: E402

@@ -150,6 +150,9 @@ SIGNATURES = {
     "wino_grouped_residual_block_prepare_hw": (i, [i] * 6 + [vp]),
     "wino_grouped_proj_block_hw": (i, [vp] * 9 + [i] * 8 + [vp, sz, vp]),
     "wino_grouped_proj_block_prepare_hw": (i, [i] * 8 + [vp]),
+    # ---- Feature Pyramid Network
+    "wino_fpn_level_hw": (i, [vp] * 10 + [i] * 6 + [vp]),
+    "wino_fpn_level_prepare_hw": (i, [i] * 5 + [vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

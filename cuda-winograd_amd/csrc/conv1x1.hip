@@ -290,23 +290,30 @@ int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int 
 }
 }  // namespace wino
 
-// Shared body of wino_conv1x1_bn_ex (H = W = 14) and wino_conv1x1_bn_ex_hw.
+// Shared body of wino_conv1x1_bn_ex (H = W = 14; hw_form = false) and wino_conv1x1_bn_ex_hw.
+// WINO_RESIDUAL_UP2 is the _hw form's alone: the coarser map's size follows from H x W, and only for that size pair is
+// (y >> 1, x >> 1) torch's nearest upsampling.  It changes the epilogue, not the GEMM: the launch plan is the same.
 static int conv1x1_ex(const float* A, const float* B, const float* bnBias, const float* bnScale,
                       const float* residual, float* C, long M, int H, int W, int Cin, int Kout, int flags,
-                      wino_stream_t s) {
+                      wino_stream_t s, bool hw_form) {
   if (int rc = check_nonnull(A, B, bnBias, bnScale, C)) return rc;
   if ((flags & WINO_ADD_RESIDUAL) && !residual) { set_error("WINO_ADD_RESIDUAL without residual"); return WINO_E_ARG; }
   if (int rc = check_aligned16(A, B, C, residual)) return rc;
-  if (flags & ~(WINO_RELU | WINO_A_PADDED | WINO_C_PADDED | WINO_ADD_RESIDUAL)) { set_error("unknown flag bits 0x%x", flags); return WINO_E_ARG; }
+  if (flags & ~(WINO_RELU | WINO_A_PADDED | WINO_C_PADDED | WINO_ADD_RESIDUAL | WINO_RESIDUAL_UP2)) { set_error("unknown flag bits 0x%x", flags); return WINO_E_ARG; }
+  const bool up2 = flags & WINO_RESIDUAL_UP2;
+  if (up2 && !hw_form) { set_error("WINO_RESIDUAL_UP2 needs the feature map's size: wino_conv1x1_bn_ex_hw"); return WINO_E_ARG; }
+  if (up2 && !(flags & WINO_ADD_RESIDUAL)) { set_error("WINO_RESIDUAL_UP2 without WINO_ADD_RESIDUAL"); return WINO_E_ARG; }
   if (int rc = check_1x1(M, Cin, Kout)) return rc;
   PadGeo pg = make_padgeo(WINO_PQ, WINO_PQ);
-  if (flags & (WINO_A_PADDED | WINO_C_PADDED)) {
+  if (flags & (WINO_A_PADDED | WINO_C_PADDED | WINO_RESIDUAL_UP2)) {
     if (int rc = check_1x1_padded(M, H, W, Kout)) return rc;
     pg = make_padgeo(H, W);
   }
   int dev = 0;
   Plan1x1 p;
   if (int rc = plan_1x1_here(M, Cin, Kout, 1, &dev, &p)) return rc;
+  if (up2)
+    return launch_1x1_up2(p, dev, {A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg, make_up2geo(H, W)}, (hipStream_t)s);
   return launch_1x1<A_PLAIN>(p, dev, {A, B, bnBias, bnScale, residual, C, M, Cin, Kout, flags, pg}, (hipStream_t)s);
 }
 
@@ -321,6 +328,12 @@ int check_bottleneck_1x1s(int N, int H, int W, int C4, int Cm) {
   if (int rc = check_1x1(M, Cm, C4)) return rc;
   return check_1x1_padded(M, H, W, C4);
 }
+int check_1x1_hw(int N, int H, int W, int Cin, int Kout) {
+  if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
+  const long M = (long)N * H * W;
+  if (int rc = check_1x1(M, Cin, Kout)) return rc;
+  return check_1x1_padded(M, H, W, Kout);
+}
 }  // namespace wino
 
 extern "C" {
@@ -328,14 +341,14 @@ extern "C" {
 int wino_conv1x1_bn_ex(const float* A, const float* B, const float* bnBias, const float* bnScale,
                        const float* residual, float* C, long M, int Cin, int Kout, int flags,
                        wino_stream_t s) {
-  return conv1x1_ex(A, B, bnBias, bnScale, residual, C, M, WINO_PQ, WINO_PQ, Cin, Kout, flags, s);
+  return conv1x1_ex(A, B, bnBias, bnScale, residual, C, M, WINO_PQ, WINO_PQ, Cin, Kout, flags, s, false);
 }
 
 int wino_conv1x1_bn_ex_hw(const float* A, const float* B, const float* bnBias, const float* bnScale,
                           const float* residual, float* C, int N, int H, int W, int Cin, int Kout,
                           int flags, wino_stream_t s) {
   if (N < 1 || H < 1 || W < 1) { set_error("bad N=%d H=%d W=%d", N, H, W); return WINO_E_SHAPE; }
-  return conv1x1_ex(A, B, bnBias, bnScale, residual, C, (long)N * H * W, H, W, Cin, Kout, flags, s);
+  return conv1x1_ex(A, B, bnBias, bnScale, residual, C, (long)N * H * W, H, W, Cin, Kout, flags, s, true);
 }
 
 // Host-side only: the launch form this shape takes on a device with `cus` compute units.

@@ -119,6 +119,30 @@ __device__ __forceinline__ long strided_row(long m, const PadGeo& g, const ProjG
   return (long)n * x.img + (long)(y * x.row + xx * x.s);   // y*row + xx*s < Hin*Win < 2^31 (host)
 }
 
+// The residual forms of the plain operand form (WINO_ADD_RESIDUAL; the template parameter RES of the tiled kernel):
+//   RES_SAME  R is [M][Kout], unpadded, on the output grid: output row m adds row m
+//   RES_UP2   (WINO_RESIDUAL_UP2, the FPN's top-down sum: fpn.hip) R is the PADDED coarser map [N][Hc+2][Wc+2][Kout],
+//             Hc = (H+1)/2, Wc = (W+1)/2, and output pixel (n, y, x) of the H x W grid (pg) adds its pixel
+//             (n, y >> 1, x >> 1) -- torch's nearest upsampling for exactly this size pair; the upsampled tensor never
+//             exists and R's ring is never read.  The coarse geometry travels in the ProjGeo slots the plain form
+//             leaves free: img = (Hc+2)(Wc+2) rows per image, row = Wc+2 rows per line.
+enum { RES_NONE = 0, RES_SAME = 1, RES_UP2 = 2 };
+__host__ inline ProjGeo make_up2geo(int H, int W) {
+  ProjGeo x = {};
+  x.img = (unsigned)((H + 1) / 2 + 2) * (unsigned)((W + 1) / 2 + 2);
+  x.row = (unsigned)((W + 1) / 2 + 2);
+  return x;
+}
+// logical pixel row m of the H x W grid -> row of the padded coarser map (same FastDiv work as padded_row)
+__device__ __forceinline__ long up2_row(long m, const PadGeo& g, const ProjGeo& x) {
+  const unsigned mu = (unsigned)m;   // M < 2^31 (checked on the host)
+  const unsigned n = fastdiv(mu, g.d_hw);
+  const unsigned rem = mu - n * g.hw;
+  const unsigned y = fastdiv(rem, g.d_w);
+  const unsigned xx = rem - y * g.w;
+  return (long)n * x.img + (long)(((y >> 1) + 1) * x.row + (xx >> 1) + 1);
+}
+
 template <int BK, int NW>
 struct Cfg {
   static constexpr int NT = 64 * NW;                // threads per workgroup
@@ -172,7 +196,8 @@ __device__ unsigned long long wino_clk_slot_1x1[4];
 // Resident waves per SIMD the LDS footprint allows -- two 8-wave workgroups (60 KB each) or three
 // 4-wave ones (44 KB) per CU -- stated to the register allocator, which otherwise takes the
 // freedom of 256 VGPRs and halves the residency (tests/test_build_budget.py).
-// RES = the launch adds a residual (WINO_ADD_RESIDUAL): a compile-time property, because the two epilogues in one
+// RES = the launch adds a residual (WINO_ADD_RESIDUAL), and in which form (RES_SAME / RES_UP2 above): a compile-time
+// property, because the two epilogues in one
 // kernel cost the one without residual 2-5 % (256->1024 99.6 -> 101.3 us, 64->256 14.1 -> 14.9) through nothing but
 // their presence -- register allocation and code layout of the rest.
 // AF = the A operand form.  The projection block's forms (proj_block.hip) run with BK = 32, no residual and no batch:
@@ -182,13 +207,13 @@ __device__ unsigned long long wino_clk_slot_1x1[4];
 // the tap forms, is the 3x3's own grid -- the stream-K ranges and the ring pass are cut over that, never over the
 // appended tiles.
 // xg is last, so that the plain form's other arguments keep their offsets.
-template <int BK, int NW, int ABLATE = 0, bool SK = false, bool RES = false, int AF = A_PLAIN>
+template <int BK, int NW, int ABLATE = 0, bool SK = false, int RES = RES_NONE, int AF = A_PLAIN>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3)
 conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
                   const float* __restrict__ bnBias, const float* __restrict__ bnScale,
                   const float* __restrict__ R, float* __restrict__ Cout, long M, int Cin, int Kout,
                   int flags, int nMB, long batchA, long batchB, long batchC, SkArgs sk, PadGeo pg, ProjGeo xg) {
-  static_assert(AF == A_PLAIN || !RES, "the residual epilogue is the plain form's");
+  static_assert(AF == A_PLAIN || RES == RES_NONE, "the residual epilogue is the plain form's");
   constexpr bool TAPS = AF == A_TAPS || AF == A_TAPS_PROJ;
   using G = Cfg<BK, NW>;
   // batched GEMMs (the 36 Winograd points of the F(4x4) compatibility path): blockIdx.y selects
@@ -214,7 +239,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   }
   const bool relu = flags & WINO_RELU, a_padded = flags & WINO_A_PADDED;
   const bool c_padded = flags & WINO_C_PADDED;
-  constexpr bool add_res = RES;   // (the host picks the instantiation from flags & WINO_ADD_RESIDUAL)
+  constexpr bool add_res = RES != RES_NONE;   // (the host picks the instantiation from flags & WINO_ADD_RESIDUAL)
   // Output stores: non-temporal when the output is written once and the layer is MFMA-bound (a K
   // loop of at least 4 steps) -- the L2 then stays with the A / B lines other workgroups re-read.
   // Old and new libraries interleaved: 512->128 31.95 -> 31.1 us, 128->512 36.25 -> 35.6, 1024->256
@@ -681,7 +706,9 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
         const long grow = m0_e + row;
         if (grow < M) {
           if (add_res) {
-            const f32x4 r = *(const f32x4*)(R + grow * Kout + n0 + c4);
+            // RES_UP2: the coarser padded map's pixel (y >> 1, x >> 1), still one aligned 16 bytes per lane
+            const long rrow = RES == RES_UP2 ? up2_row(grow, pg, xg) : grow;
+            const f32x4 r = *(const f32x4*)(R + rrow * Kout + n0 + c4);
             val += r;
             if (relu) {
 #pragma unroll
@@ -696,7 +723,9 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
         }
       }
     };
-    if (stream_out) store_rows(std::true_type{});
+    // (RES_UP2: cached stores only -- the FPN's inner map is read again at once by its 3x3 -- which also spares the
+    //  stream-K form the scalars of a second copy)
+    if (RES != RES_UP2 && stream_out) store_rows(std::true_type{});
     else store_rows(std::false_type{});
   }
   }   // segments

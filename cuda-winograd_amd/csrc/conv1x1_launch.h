@@ -1,6 +1,7 @@
 // The 1x1 kernels' launch plan and launcher, shared by the translation units that launch them: conv1x1.hip (the plain
 // operand form, A_PLAIN), proj_block.hip (the projection block's A_STRIDED / A_TWO forms), conv3x3_s2.hip (the
-// stride-2 3x3's A_TAPS form) and basic_block_s2.hip (A_TAPS_PROJ, the stride-2 3x3 with its 1x1 shortcut); the forms:
+// stride-2 3x3's A_TAPS form), basic_block_s2.hip (A_TAPS_PROJ, the stride-2 3x3 with its 1x1 shortcut) and fpn.hip
+// (A_PLAIN with the upsampled residual); the forms:
 // conv1x1_kernel.h.
 // A template is instantiated where it is used, so each file compiles the kernels of its own forms and no others.
 #pragma once
@@ -43,22 +44,22 @@ struct Operands1x1 {
 };
 
 // the latency kernel's instantiations by [KS / 2][RT - 1][CT / 2]
-template <int AF>
-constexpr decltype(&gemm1x1::conv1x1_small_kernel<1, 1, 1, AF>) SMALL_1X1_KERNELS[3][2][3] = {
-    {{gemm1x1::conv1x1_small_kernel<1, 1, 1, AF>, gemm1x1::conv1x1_small_kernel<1, 1, 2, AF>,
-      gemm1x1::conv1x1_small_kernel<1, 1, 4, AF>},
-     {gemm1x1::conv1x1_small_kernel<1, 2, 1, AF>, gemm1x1::conv1x1_small_kernel<1, 2, 2, AF>,
-      gemm1x1::conv1x1_small_kernel<1, 2, 4, AF>}},
-    {{gemm1x1::conv1x1_small_kernel<2, 1, 1, AF>, gemm1x1::conv1x1_small_kernel<2, 1, 2, AF>,
-      gemm1x1::conv1x1_small_kernel<2, 1, 4, AF>},
-     {gemm1x1::conv1x1_small_kernel<2, 2, 1, AF>, gemm1x1::conv1x1_small_kernel<2, 2, 2, AF>,
-      gemm1x1::conv1x1_small_kernel<2, 2, 4, AF>}},
-    {{gemm1x1::conv1x1_small_kernel<4, 1, 1, AF>, gemm1x1::conv1x1_small_kernel<4, 1, 2, AF>,
-      gemm1x1::conv1x1_small_kernel<4, 1, 4, AF>},
-     {gemm1x1::conv1x1_small_kernel<4, 2, 1, AF>, gemm1x1::conv1x1_small_kernel<4, 2, 2, AF>,
-      gemm1x1::conv1x1_small_kernel<4, 2, 4, AF>}}};
+template <int AF, bool UP2 = false>
+constexpr decltype(&gemm1x1::conv1x1_small_kernel<1, 1, 1, UP2, AF>) SMALL_1X1_KERNELS[3][2][3] = {
+    {{gemm1x1::conv1x1_small_kernel<1, 1, 1, UP2, AF>, gemm1x1::conv1x1_small_kernel<1, 1, 2, UP2, AF>,
+      gemm1x1::conv1x1_small_kernel<1, 1, 4, UP2, AF>},
+     {gemm1x1::conv1x1_small_kernel<1, 2, 1, UP2, AF>, gemm1x1::conv1x1_small_kernel<1, 2, 2, UP2, AF>,
+      gemm1x1::conv1x1_small_kernel<1, 2, 4, UP2, AF>}},
+    {{gemm1x1::conv1x1_small_kernel<2, 1, 1, UP2, AF>, gemm1x1::conv1x1_small_kernel<2, 1, 2, UP2, AF>,
+      gemm1x1::conv1x1_small_kernel<2, 1, 4, UP2, AF>},
+     {gemm1x1::conv1x1_small_kernel<2, 2, 1, UP2, AF>, gemm1x1::conv1x1_small_kernel<2, 2, 2, UP2, AF>,
+      gemm1x1::conv1x1_small_kernel<2, 2, 4, UP2, AF>}},
+    {{gemm1x1::conv1x1_small_kernel<4, 1, 1, UP2, AF>, gemm1x1::conv1x1_small_kernel<4, 1, 2, UP2, AF>,
+      gemm1x1::conv1x1_small_kernel<4, 1, 4, UP2, AF>},
+     {gemm1x1::conv1x1_small_kernel<4, 2, 1, UP2, AF>, gemm1x1::conv1x1_small_kernel<4, 2, 2, UP2, AF>,
+      gemm1x1::conv1x1_small_kernel<4, 2, 4, UP2, AF>}}};
 
-template <int NW, bool SK, int AF, bool RES>
+template <int NW, bool SK, int AF, int RES>
 int launch_tiled_1x1_kernel(dim3 grid, int nMB, const Operands1x1& o, gemm1x1::SkArgs sk, hipStream_t s) {
   using G = gemm1x1::Cfg<32, NW>;
   hipLaunchKernelGGL((gemm1x1::conv1x1_bn_kernel<32, NW, 0, SK, RES, AF>), grid, dim3(G::NT), G::LDS_BYTES, s, o.A,
@@ -70,7 +71,7 @@ int launch_tiled_1x1_kernel(dim3 grid, int nMB, const Operands1x1& o, gemm1x1::S
 // BK = 32 keeps a workgroup at 60 KB of LDS, so two workgroups share a CU (4 waves per SIMD)
 // and one's prologue / barrier bubbles / store tail hide under the other's MFMAs; measured
 // 3-14 % faster than BK = 64 (120 KB, one workgroup per CU) on the four reference shapes.
-template <int NW, int AF, bool RES>
+template <int NW, int AF, int RES>
 int launch_tiled_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
   constexpr int LDS_BYTES = gemm1x1::Cfg<32, NW>::LDS_BYTES;
   if (int rc = lds_cap_once<gemm1x1::conv1x1_bn_kernel<32, NW, 0, false, RES, AF>,
@@ -95,12 +96,13 @@ int launch_tiled_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_
 }
 
 // One launch of the 1x1 GEMM in operand form AF as planned: the latency form, or the tiled kernel with 4 or 8 waves,
-// plain or stream-K.
-template <int AF>
+// plain or stream-K.  UP2: the launch adds the upsampled residual (WINO_RESIDUAL_UP2: o.R the padded coarser map, o.xg
+// from make_up2geo) -- the same plan, the kernels of that epilogue and no others.
+template <int AF, bool UP2 = false>
 int launch_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
   if (p.small.use) {
     const Small1Plan& pl = p.small;
-    const auto kernel = SMALL_1X1_KERNELS<AF>[pl.ks >> 1][pl.rt - 1][pl.ct >> 1];
+    const auto kernel = SMALL_1X1_KERNELS<AF, UP2>[pl.ks >> 1][pl.rt - 1][pl.ct >> 1];
     // x = column group, y = row block: see the kernel.  A_TAPS_PROJ: the shortcut's row blocks behind the 3x3's
     const long long rows = (o.M + 16 * pl.rt - 1) / (16 * pl.rt) * (AF == gemm1x1::A_TAPS_PROJ ? 2 : 1);
     if (rows > 65535) { set_error("latency form: %lld row blocks (gridDim.y)", rows); return WINO_E_SHAPE; }
@@ -109,10 +111,21 @@ int launch_1x1(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s) {
                        o.flags, o.pg, o.xg);
     return launch_status("conv1x1_small_kernel");
   }
-  auto* launch = p.four ? launch_tiled_1x1<4, AF, false> : launch_tiled_1x1<8, AF, false>;
-  if constexpr (AF == gemm1x1::A_PLAIN)   // the residual epilogue is a compile-time property (conv1x1_kernel.h)
-    if (o.flags & WINO_ADD_RESIDUAL) launch = p.four ? launch_tiled_1x1<4, AF, true> : launch_tiled_1x1<8, AF, true>;
-  return launch(p, dev, o, s);
+  if constexpr (UP2) {
+    return (p.four ? launch_tiled_1x1<4, AF, gemm1x1::RES_UP2> : launch_tiled_1x1<8, AF, gemm1x1::RES_UP2>)(p, dev, o, s);
+  } else {
+    auto* launch = p.four ? launch_tiled_1x1<4, AF, gemm1x1::RES_NONE> : launch_tiled_1x1<8, AF, gemm1x1::RES_NONE>;
+    if constexpr (AF == gemm1x1::A_PLAIN)   // the residual epilogue is a compile-time property (conv1x1_kernel.h)
+      if (o.flags & WINO_ADD_RESIDUAL)
+        launch = p.four ? launch_tiled_1x1<4, AF, gemm1x1::RES_SAME> : launch_tiled_1x1<8, AF, gemm1x1::RES_SAME>;
+    return launch(p, dev, o, s);
+  }
 }
+// The plain operand form with the upsampled residual, defined in fpn.hip: that file instantiates the WINO_RESIDUAL_UP2
+// kernels, so that conv1x1.hip keeps exactly the kernels it had.
+int launch_1x1_up2(const Plan1x1& p, int dev, const Operands1x1& o, hipStream_t s);
+// The shape limits of one 1x1 layer on an H x W feature map with padded operands (conv1x1.hip), for the blocks that
+// check every layer before their first launch.
+int check_1x1_hw(int N, int H, int W, int Cin, int Kout);
 
 }  // namespace wino

@@ -45,7 +45,10 @@ namespace gemm1x1 {
 // another 3x3 workgroup because shortcut ones took CUs first (interleaved along x, conv4 at 8 images took 2.5x the
 // plain layer's time).  C / KS is a multiple of 16 whenever 9 C / KS is (gcd(9, 16) = 1).  xg is last, so that
 // the plain form's other arguments keep their offsets.
-template <int KS, int RT = 1, int CT = 1, int AF = A_PLAIN>
+// UP2 = the residual is the padded coarser map read at (y >> 1, x >> 1) (WINO_RESIDUAL_UP2, RES_UP2 in
+// conv1x1_kernel.h; instantiated in fpn.hip): a compile-time property, so that the other kernels keep their code; the
+// residual branch itself stays wave-uniform.
+template <int KS, int RT = 1, int CT = 1, bool UP2 = false, int AF = A_PLAIN>
 __global__ void __launch_bounds__(256)
 conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
                      const float* __restrict__ bnBias, const float* __restrict__ bnScale,
@@ -53,6 +56,7 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
                      const PadGeo pg, const ProjGeo xg) {
   static_assert(KS == 1 || KS == 2 || KS == 4, "waves per block");
   static_assert((RT == 1 || RT == 2) && (CT == 1 || CT == 2 || CT == 4), "MFMA tiles per wave");
+  static_assert(AF == A_PLAIN || !UP2, "the residual epilogue is the plain form's");
   constexpr bool WIDE = CT == 4;           // strided column tiles, 16-byte filter loads
   constexpr int CB = 4 / KS;               // blocks per workgroup, side by side
   constexpr int GS = RT * CT == 1 ? 8 : RT * CT >= 8 ? 2 : 4;   // super-chunks per register buffer; two buffers in flight
@@ -253,6 +257,7 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
   for (int r = 0; r < RT; r++) {
     const long row = m0 + 16 * r + r16;
     const long orow = c_padded && row < M ? padded_row(row, pg) : row;
+    const long rrow = UP2 && add_res && row < M ? up2_row(row, pg, xg) : row;   // (UP2: the coarser padded map's row)
 #pragma unroll
     for (int c = 0; c < CT; c++) {
       // WIDE: c is the register index here: the four tiles' components c are columns n0 + 16 h + 4 c .. + 3
@@ -261,7 +266,7 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
       else val = acc[r][c];
       val = sc[c] * val + bi[c];
       const int col = n0 + (WIDE ? 16 * h + 4 * c : 16 * c + 4 * h);
-      if (add_res && row < M) val += *(const f32x4*)((AF == A_PLAIN ? Res : nullptr) + row * Kout + col);   // the residual is never padded
+      if (add_res && row < M) val += *(const f32x4*)((AF == A_PLAIN ? Res : nullptr) + rrow * Kout + col);   // the same-size residual is never padded
       if (relu) {
 #pragma unroll
         for (int j = 0; j < 4; j++) val[j] = fmaxf(val[j], 0.f);

@@ -1,0 +1,107 @@
+"""torchvision's ResNet-FPN backbones (``BackboneWithFPN`` / ``resnet_fpn_backbone``: the backbones of Faster / Mask /
+Keypoint R-CNN and RetinaNet) on the library's kernels: a headless ResNet body and a Feature Pyramid Network on its
+four stage outputs.
+
+``ResNetFPN.from_state_dict(sd, arch)`` takes the backbone's state dict under torchvision's key names --
+``body.<resnet keys>`` without ``fc``, ``fpn.inner_blocks.{i}.0.weight|bias`` (the 1x1 laterals) and
+``fpn.layer_blocks.{i}.0.weight|bias`` (the 3x3 output convolutions), i = 0..3 -- for every arch of ``resnet.ARCHS``.
+``model(x_nchw)`` returns {"0", "1", "2", "3", "pool"}.
+
+The pyramid runs from the coarsest level down, one ``fpn_level`` (two launches) per level: the lateral 1x1 adds the
+coarser level's ``inner`` in its epilogue, read at (y >> 1, x >> 1) -- ``F.interpolate(mode="nearest")`` for the size
+pairs a stride-2 stage makes -- so no upsampled tensor is ever written; the 3x3 is the Winograd layer.  ``"pool"`` is
+torchvision's ``LastLevelMaxPool``, ``max_pool2d(kernel 1, stride 2)``: the view ``P3[:, ::2, ::2, :]``, no kernel.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import WinoError, filter_transform_f2, fpn_level, fpn_level_prepare
+from ._net import Net, check_state_dict
+from .resnet import ARCHS, ResNet, expected_keys, stage_shapes
+
+LEVELS = 4
+
+
+def expected_fpn_keys(arch: str, out_channels: int):
+    """{key: shape} of a torchvision BackboneWithFPN state dict of `arch` (num_batches_tracked aside)."""
+    exp = {f"body.{k}": v for k, v in expected_keys(arch, None).items()}
+    stage_c = [c for _, c, _, _ in stage_shapes(arch, 64, 64)[1:]]
+    for i, c in enumerate(stage_c):
+        exp[f"fpn.inner_blocks.{i}.0.weight"] = (out_channels, c, 1, 1)
+        exp[f"fpn.inner_blocks.{i}.0.bias"] = (out_channels,)
+        exp[f"fpn.layer_blocks.{i}.0.weight"] = (out_channels, out_channels, 3, 3)
+        exp[f"fpn.layer_blocks.{i}.0.bias"] = (out_channels,)
+    return exp
+
+
+def validate_fpn_state_dict(sd, arch: str, out_channels: int = 256) -> None:
+    """Checks every key and shape of `sd` against `arch` with an FPN of `out_channels` on the host.  Raises WinoError
+    naming the first missing, unexpected or wrongly shaped key."""
+    if arch not in ARCHS:
+        raise WinoError(f"unknown arch {arch!r}: one of {sorted(ARCHS)}")
+    out_channels = int(out_channels)
+    if out_channels < 64 or out_channels % 64:
+        raise WinoError(f"out_channels={out_channels}: the FPN's layers need a multiple of 64")
+    check_state_dict(sd, expected_fpn_keys(arch, out_channels), f"{arch} + FPN", "weight")
+
+
+class ResNetFPN(Net):
+    """A torchvision ResNet-FPN backbone on the library's kernels, inference only (BN folded at load)."""
+
+    def __init__(self, arch: str, out_channels: int, device):
+        super().__init__(device)
+        self.arch, self.out_channels = arch, int(out_channels)
+        self.body = ResNet(arch, 0, device)   # headless: only its _pack_body / _prepare_body / _run_body are used
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, out_channels: int = 256, eps: float = 1e-5, device=None) -> "ResNetFPN":
+        """Validate `sd` (torchvision's BackboneWithFPN key names) for `arch`, fold every BN and pack every filter on
+        `device` (default: the current CUDA device)."""
+        validate_fpn_state_dict(sd, arch, out_channels)
+        return cls._load(sd, eps, device, arch, out_channels)
+
+    def _pack(self, sd, eps):
+        self.body._pack_body(sd, eps, "body.")
+        self.levels = []   # per level, finest first: (lateral [Cin][Cf], its bias, U of the 3x3, its bias)
+        for i in range(LEVELS):
+            wl = sd[f"fpn.inner_blocks.{i}.0.weight"]
+            self.levels.append((self._t(wl.reshape(wl.shape[0], wl.shape[1]).t()),
+                                self._t(sd[f"fpn.inner_blocks.{i}.0.bias"]),
+                                filter_transform_f2(self._t(sd[f"fpn.layer_blocks.{i}.0.weight"])),
+                                self._t(sd[f"fpn.layer_blocks.{i}.0.bias"])))
+        self._ones = torch.ones(self.out_channels, dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+
+    def prepare(self, N: int, H: int, W: int) -> None:
+        """Allocate the body's activations, the four `inner` and four `P` tensors for [N][3][H][W] inputs and reserve
+        the stream scratch of every launch on the current stream.  Call it before capturing a forward into a graph."""
+        N, H, W = int(N), int(H), int(W)
+        dev, f32, body = self.device, torch.float32, self.body
+        with torch.cuda.device(dev):
+            ws = body._prepare_body(N, H, W)
+            body._ws = torch.empty((ws + 3) // 4, dtype=f32, device=dev)
+            self._inner, self._p = [], []
+            for _, c, h, w in stage_shapes(self.arch, H, W)[1:]:
+                self._inner.append(torch.zeros((N, h + 2, w + 2, self.out_channels), dtype=f32, device=dev))
+                self._p.append(torch.zeros((N, h + 2, w + 2, self.out_channels), dtype=f32, device=dev))
+                fpn_level_prepare(N, h, w, c, self.out_channels)
+        self._shape = (N, H, W)
+
+    def forward(self, x: torch.Tensor):
+        """x [N][3][H][W] float32 on the model's device -> {"0", "1", "2", "3", "pool"}: the pyramid levels P2..P5 at
+        strides 4..32 and the pooled P5, each an NHWC view [N][h][w][out_channels] of the model's own tensors, valid
+        until the next forward.  A new input shape re-runs prepare()."""
+        self._begin(x)
+        with torch.cuda.device(self.device):
+            stages = self.body._run_body(x.contiguous())
+            for i in reversed(range(LEVELS)):   # top-down: the coarsest level has no `top`
+                wl, bl, U, bo = self.levels[i]
+                fpn_level(stages[i], wl, bl, U, bo, top=self._inner[i + 1] if i + 1 < LEVELS else None,
+                          c_padded=not self.body.bottleneck, ones=self._ones, inner=self._inner[i], out=self._p[i])
+        out = {str(i): p[:, 1:-1, 1:-1, :] for i, p in enumerate(self._p)}
+        out["pool"] = out[str(LEVELS - 1)][:, ::2, ::2, :]
+        return out
+
+
+__all__ = ["ResNetFPN", "expected_fpn_keys", "validate_fpn_state_dict"]

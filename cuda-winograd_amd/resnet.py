@@ -170,8 +170,9 @@ def stage_shapes(arch: str, H: int, W: int):
     return shapes
 
 
-def expected_keys(arch: str, classes: int):
-    """{key: shape} of a torchvision state dict of `arch` (num_batches_tracked aside)."""
+def expected_keys(arch: str, classes):
+    """{key: shape} of a torchvision state dict of `arch` (num_batches_tracked aside); classes None: the headless
+    body (no fc), as a detection backbone keeps it."""
     if arch not in ARCHS:
         raise WinoError(f"unknown arch {arch!r}: one of {sorted(ARCHS)}")
     bottleneck, blocks = ARCHS[arch]
@@ -204,8 +205,9 @@ def expected_keys(arch: str, classes: int):
                 exp[f"{p}.downsample.0.weight"] = (cout, cin, 1, 1)
                 bn(f"{p}.downsample.1", cout)
             cin = cout
-    exp["fc.weight"] = (classes, cin)
-    exp["fc.bias"] = (classes,)
+    if classes is not None:
+        exp["fc.weight"] = (classes, cin)
+        exp["fc.bias"] = (classes,)
     return exp
 
 
@@ -236,12 +238,19 @@ class ResNet(Net):
         return cls._load(sd, eps, device, arch, validate_state_dict(sd, arch))
 
     def _pack(self, sd, eps):
+        ld = self._pack_body(sd, eps)
+        self.head_packed = head_pack(ld.w("fc.weight"), ld.w("fc.bias"))
+        torch.cuda.current_stream().synchronize()
+
+    def _pack_body(self, sd, eps, prefix: str = ""):
+        """The stem and the four stages from sd[prefix + <torchvision's key>] (a detection backbone keeps the body
+        under "body."); returns the loader."""
         def w1x1(key):   # torch's [K][C][1][1] -> the library's [C][K]
-            w = sd[key]
+            w = sd[prefix + key]
             return self._t(w.reshape(w.shape[0], w.shape[1]).t())
 
-        ld = SimpleNamespace(w=lambda key: self._t(sd[key]), w1x1=w1x1,
-                             bn=lambda prefix: self._fold_bn(sd, prefix, eps))
+        ld = SimpleNamespace(w=lambda key: self._t(sd[prefix + key]), w1x1=w1x1,
+                             bn=lambda p: self._fold_bn(sd, prefix + p, eps))
         self.stem_packed = stem_filter_pack(ld.w("conv1.weight"), ld.bn("bn1"))
         self.layers = []   # per stage: (kind, cin, cm, cout, packed parameters) of its blocks, kind a KINDS row
         cin = 64
@@ -255,41 +264,53 @@ class ResNet(Net):
                 cin = cout
             self.layers.append(blocks)
         self.feat_c = cin
-        self.head_packed = head_pack(ld.w("fc.weight"), ld.w("fc.bias"))
-        torch.cuda.current_stream().synchronize()
+        return ld
 
     # ------------------------------------------------------------------ per input shape
     def prepare(self, N: int, H: int, W: int) -> None:
         """Allocate the activations and the shared workspace for [N][3][H][W] inputs and reserve the stream scratch of
         every launch on the current stream.  Call it before capturing a forward into a graph."""
         N, H, W = int(N), int(H), int(W)
-        if N < 1 or H < 1 or W < 1:
-            raise WinoError(f"bad input shape N={N} H={H} W={W}")
         dev, f32 = self.device, torch.float32
-        shapes = stage_shapes(self.arch, H, W)
-        pad = 0 if self.bottleneck else 2
         with torch.cuda.device(dev):
-            _, c0, h0, w0 = shapes[0]
-            self._stem_out = torch.zeros((N, h0 + pad, w0 + pad, c0), dtype=f32, device=dev)
-            self._stages = []   # per stage: the tensors its blocks write (two for the bottleneck ping-pong)
-            ws = 0
-            h, w = h0, w0
-            for (name, c, ho, wo), blocks in zip(shapes[1:], self.layers):
-                bufs = [torch.zeros((N, ho + pad, wo + pad, c), dtype=f32, device=dev)
-                        for _ in range(2 if self.bottleneck else 1)]
-                self._stages.append(bufs)
-                for kind, cin, cm, cout, _ in blocks:
-                    shape = _Shape(N, h, w, ho, wo, cin, cm, cout, self.groups)
-                    ws = max(ws, KINDS[kind].workspace(shape))
-                    KINDS[kind].prepare(shape)
-                    h, w = ho, wo
-            ws = max(ws, lib().wino_head_workspace_bytes(N, self.feat_c, self.classes))
+            ws = max(self._prepare_body(N, H, W), lib().wino_head_workspace_bytes(N, self.feat_c, self.classes))
             head_prepare(N, self.feat_c, self.classes)
             self._ws = torch.empty((ws + 3) // 4, dtype=f32, device=dev)
             self._logits = torch.empty((N, self.classes), dtype=f32, device=dev)
         self._shape = (N, H, W)
 
+    def _prepare_body(self, N: int, H: int, W: int) -> int:
+        """The stem's and the stages' activations for [N][3][H][W] inputs, and their launches' stream scratch; returns
+        the bytes of workspace the blocks need (the caller allocates self._ws).  On the model's device."""
+        if N < 1 or H < 1 or W < 1:
+            raise WinoError(f"bad input shape N={N} H={H} W={W}")
+        dev, f32 = self.device, torch.float32
+        shapes = stage_shapes(self.arch, H, W)
+        pad = 0 if self.bottleneck else 2
+        _, c0, h0, w0 = shapes[0]
+        self._stem_out = torch.zeros((N, h0 + pad, w0 + pad, c0), dtype=f32, device=dev)
+        self._stages = []   # per stage: the tensors its blocks write (two for the bottleneck ping-pong)
+        ws = 0
+        h, w = h0, w0
+        for (name, c, ho, wo), blocks in zip(shapes[1:], self.layers):
+            bufs = [torch.zeros((N, ho + pad, wo + pad, c), dtype=f32, device=dev)
+                    for _ in range(2 if self.bottleneck else 1)]
+            self._stages.append(bufs)
+            for kind, cin, cm, cout, _ in blocks:
+                shape = _Shape(N, h, w, ho, wo, cin, cm, cout, self.groups)
+                ws = max(ws, KINDS[kind].workspace(shape))
+                KINDS[kind].prepare(shape)
+                h, w = ho, wo
+        return ws
+
     def _run_stages(self, x):
+        outs = self._run_body(x)
+        avgpool_fc(outs[-1], self.head_packed, self.classes, in_padded=not self.bottleneck, out=self._logits,
+                   workspace=self._ws)
+        return outs
+
+    def _run_body(self, x):
+        """The stem and the four stages; returns the stages' output tensors (padded for the basic-block nets)."""
         ws = self._ws
         stem(x, self.stem_packed, out_padded=not self.bottleneck, out=self._stem_out)
         cur = self._stem_out
@@ -298,7 +319,6 @@ class ResNet(Net):
             for i, (kind, _, _, _, p) in enumerate(blocks):   # (bottlenecks ping-pong between the stage's two tensors)
                 cur = KINDS[kind].run(cur, p, self.groups, bufs[i % len(bufs)], ws)
             outs.append(cur)
-        avgpool_fc(cur, self.head_packed, self.classes, in_padded=not self.bottleneck, out=self._logits, workspace=ws)
         return outs
 
     def _interior(self, t):

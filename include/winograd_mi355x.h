@@ -60,7 +60,8 @@ extern "C" {
  * wino_head_elems, wino_head_pack, wino_head_workspace_bytes, wino_head_prepare, wino_avgpool_fc_hw,
  * wino_conv3x3_bn_relu_pool_hw, wino_image_pack_hw, wino_avgpool7_flatten_hw, wino_conv3x3_grouped_filter_elems,
  * wino_conv3x3_grouped_filter_pack, wino_conv3x3_grouped_bn_relu_hw, wino_grouped_residual_block_hw,
- * wino_grouped_residual_block_prepare_hw, wino_grouped_proj_block_hw, wino_grouped_proj_block_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_grouped_residual_block_prepare_hw, wino_grouped_proj_block_hw, wino_grouped_proj_block_prepare_hw,
+ * WINO_RESIDUAL_UP2, wino_fpn_level_hw, wino_fpn_level_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -247,6 +248,12 @@ int wino_conv1x1_bn(const float* A, const float* B, const float* bnBias, const f
 #define WINO_A_PADDED 2
 #define WINO_C_PADDED 4
 #define WINO_ADD_RESIDUAL 8
+/* wino_conv1x1_bn_ex_hw only, and only together with WINO_ADD_RESIDUAL (WINO_E_ARG otherwise): `residual` is the PADDED
+ * coarser map [N][Hc+2][Wc+2][Kout], Hc = (H+1)/2, Wc = (W+1)/2, and output pixel (n, y, x) adds its pixel
+ * (n, y>>1, x>>1) before the ReLU -- for this size pair exactly torch's F.interpolate(size=(H, W), mode="nearest"), the
+ * top-down sum of a Feature Pyramid Network, without the upsampled tensor ever existing.  The residual's ring is never
+ * read.  Combines freely with WINO_RELU, WINO_A_PADDED and WINO_C_PADDED; the launch plan is the plain layer's. */
+#define WINO_RESIDUAL_UP2 16
 int wino_conv1x1_bn_ex(const float* A, const float* B, const float* bnBias, const float* bnScale,
                        const float* residual, float* C, long M, int Cin, int Kout, int flags,
                        wino_stream_t s);
@@ -604,6 +611,24 @@ int wino_grouped_proj_block_hw(const float* x, const float* w1, const float* bn1
                                void* workspace, size_t workspace_bytes, wino_stream_t s);
 int wino_grouped_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int groups, int stride,
                                        wino_stream_t s);
+
+/* ---- Feature Pyramid Network (torchvision's FeaturePyramidNetwork on a ResNet's four stage outputs) ----------------
+ * One pyramid level, two launches on `s`:
+ *   inner = conv1x1(c, wl) + lBias [+ nearest_upsample(top)]     Cin -> Cf, no ReLU   (the lateral and the top-down sum)
+ *   P     = conv3x3(inner, U) + oBias                            Cf -> Cf, no ReLU   (Winograd: wino_conv3x3_bn_relu_hw)
+ *   c      the stage output, [N][H][W][Cin] or, c_padded != 0, [N][H+2][W+2][Cin] (ResNet-18 / -34's layout)
+ *   wl     [Cin][Cf]; U from wino_filter_transform_f2 (Cf -> Cf)
+ *   lBias, oBias   the convolutions' biases; lScale, oScale: the layers' bnScale vectors, which an FPN fills with ones
+ *   top    the coarser level's `inner`, padded [N][Hc+2][Wc+2][Cf] with Hc = (H+1)/2, Wc = (W+1)/2 (its ring is not
+ *          read), added through WINO_RESIDUAL_UP2; NULL on the coarsest level
+ *   inner, P   padded [N][H+2][W+2][Cf], their rings written 0
+ * Every argument is checked before the first launch: Cin % 32 == 0, Cf % 64 == 0, the constraints of
+ * wino_conv1x1_bn_ex_hw and wino_conv3x3_bn_relu_hw (C * K < 2^26 among them); c, top, inner and P must not overlap
+ * (WINO_E_ARG).  wino_fpn_level_prepare_hw reserves the stream scratch of both launches (before a graph capture). */
+int wino_fpn_level_hw(const float* c, const float* wl, const float* lBias, const float* lScale, const float* top,
+                      float* inner, const float* U, const float* oBias, const float* oScale, float* P, int N, int H,
+                      int W, int Cin, int Cf, int c_padded, wino_stream_t s);
+int wino_fpn_level_prepare_hw(int N, int H, int W, int Cin, int Cf, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
