@@ -44,7 +44,7 @@ __global__ void conv1x1_direct_kernel(const float* __restrict__ A, const float* 
   float s = 0.f;
   for (int c = 0; c < Cin; c++) s = fmaf(a[c], B[(size_t)c * Kout + k], s);
   float y = bnScale[k] * s + bnBias[k];
-  if (relu) y = fmaxf(y, 0.f);
+  if (relu) y = relu_nan(y);
   Cout[idx] = y;
 }
 

@@ -655,7 +655,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
         f32x4 val = sc * acc[rb] + bi;
         if (relu) {
 #pragma unroll
-          for (int j = 0; j < 4; j++) val[j] = fmaxf(val[j], 0.f);
+          for (int j = 0; j < 4; j++) val[j] = relu_nan(val[j]);
         }
         if (grow < M) {
           // c_padded: row = pixel (n, y, x) of the H x W map -> interior of [N][H+2][W+2][Kout]
@@ -712,7 +712,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
             val += r;
             if (relu) {
 #pragma unroll
-              for (int j = 0; j < 4; j++) val[j] = fmaxf(val[j], 0.f);
+              for (int j = 0; j < 4; j++) val[j] = relu_nan(val[j]);
             }
           }
           // c_padded: row = pixel (n, y, x) of the H x W map -> interior of [N][H+2][W+2][Kout]

@@ -269,7 +269,7 @@ conv1x1_small_kernel(const float* __restrict__ A, const float* __restrict__ B,
       if (add_res && row < M) val += *(const f32x4*)((AF == A_PLAIN ? Res : nullptr) + rrow * Kout + col);   // the same-size residual is never padded
       if (relu) {
 #pragma unroll
-        for (int j = 0; j < 4; j++) val[j] = fmaxf(val[j], 0.f);
+        for (int j = 0; j < 4; j++) val[j] = relu_nan(val[j]);
       }
       if (row < M) *(f32x4*)(Cout + orow * Kout + col) = val;
     }

@@ -9,11 +9,15 @@
 //      loads, all issued before the first LDS write; pixels outside the padded input are written 0), at 68 floats a
 //      pixel so that the 16 pixels of an MFMA tile start on different banks;
 //   2. wave w owns the 16 output channels 16 w .. 16 w + 15 of the block and every 16-pixel row tile of the
-//      workgroup's tile.  A column tile covers 16 / Cg whole groups when Cg <= 16 and contracts over its own 16 input
-//      channels (four MFMAs a tap; the pack kernel wrote the zeros of the block diagonal), and over the KC = 32 / 64
-//      channels of its group at Cg = 32 / 64.  One ds_read_b128 feeds four MFMAs: a lane's four values are the
-//      channels 4 h + 0..3 (h = lane >> 4) of its pixel, MFMA j takes element j, and the packed filter holds the same
-//      k order.  The filters come as fragments in that order straight from L2: 16 bytes a lane per (tap, 16 channels);
+//      workgroup's tile.  At Cg = 32 / 64 a column tile contracts over the KC = 32 / 64 channels of its group: one
+//      ds_read_b128 feeds four MFMAs, a lane's four values are the channels 4 h + 0..3 (h = lane >> 4) of its pixel,
+//      MFMA j takes element j, and the packed filter holds the same k order.  At Cg <= 16 a column tile covers 16 / Cg
+//      whole groups and contracts over its own 16 input channels, four MFMAs a tap, MFMA j over the channels
+//      4 j .. 4 j + 3 (one group's, or part of one), each into an accumulator of its own; a lane's four output
+//      channels 4 h .. 4 h + 3 then take the sum of the accumulators of their own group, by a select.  A group's
+//      output never meets another group's activation, not even times 0: 0 * NaN is NaN (DESIGN.md section 1,
+//      "Non-finite values").  The filters come as fragments in that order straight from L2: 16 bytes a lane per
+//      (tap, 16 channels);
 //   3. the filter is the MFMA's A operand and the pixels its B operand (conv1x1_kernel.h), so a lane ends up with four
 //      consecutive output channels of one pixel: BN, ReLU and one 16-byte store.  Pixels past H or W are not stored;
 //   4. the workgroups along an image's edge write the ring cells next to their tile as 0.
@@ -32,6 +36,7 @@ struct GroupedArgs {
   int Hin, Win, H, W, C;
   int tiles_y, tiles_x, cblocks;
   int relu;
+  int Cg;
 };
 
 template <int S, int TW, int KC>
@@ -45,8 +50,9 @@ struct GroupedShape {
   static constexpr int PPT = (PIECES + 255) / 256;
   static constexpr int KG = KC / 16;            // 16-channel chunks of a column tile's contraction
   // resident waves per SIMD the registers are held to (= workgroups per CU): what the patch leaves room for at
-  // S = 2 (45 KB), and at S = 1 with KC = 64 what the unrolled tap loop fits without a spill (MFMA-bound there)
-  static constexpr int WAVES = S == 2 ? 3 : KC == 64 ? 2 : 4;
+  // S = 2 (45 KB), and at S = 1 what the unrolled tap loop fits without a spill: KC = 64 (MFMA-bound there), and
+  // KC = 16 with its four accumulators a row tile
+  static constexpr int WAVES = S == 2 ? 3 : KC == 64 ? 2 : KC == 16 ? 3 : 4;
   static_assert(TW == 8 || TW == 16, "a row tile is 16 pixels: one row of 16 or two of 8");
   static_assert(KC == 16 || KC == 32 || KC == 64, "a column tile contracts over 16, 32 or 64 channels");
   static_assert(PH * PW * PS * 4 <= 64 * 1024, "static LDS");
@@ -54,7 +60,8 @@ struct GroupedShape {
 
 // packed filter: [C/16 column tiles][9 taps][KC/16][64 lanes][4] -- element (ct, tap, kg, lane, j) is the tap's weight
 // from input channel ci = 64 (ct / 4) + kbase + 16 kg + 4 (lane >> 4) + j, kbase = (16 (ct % 4) / KC) KC, to output
-// channel ko = 16 ct + (lane & 15); 0 when ci is not in ko's group (Cg < 16: the block diagonal inside the tile)
+// channel ko = 16 ct + (lane & 15); KC = 16: MFMA j contracts over 4 j .. 4 j + 3, ci = 64 (ct / 4) + kbase + 4 j +
+// (lane >> 4); 0 when ci is not in ko's group (Cg < 16: rows of an accumulator that the kernel never selects)
 __global__ void grouped_pack_kernel(const float* __restrict__ w, float* __restrict__ packed, int C, int Cg, int KC) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= 9l * C * KC) return;
@@ -65,7 +72,7 @@ __global__ void grouped_pack_kernel(const float* __restrict__ w, float* __restri
   r /= KG;
   const int tap = (int)(r % 9), ct = (int)(r / 9);
   const int ko = 16 * ct + (lane & 15);
-  const int ci = 64 * (ct / 4) + (16 * (ct % 4) / KC) * KC + 16 * kg + 4 * (lane >> 4) + j;
+  const int ci = 64 * (ct / 4) + (16 * (ct % 4) / KC) * KC + 16 * kg + (KC == 16 ? 4 * j + (lane >> 4) : 4 * (lane >> 4) + j);
   const int g0 = (ko / Cg) * Cg;
   packed[i] = (ci >= g0 && ci < g0 + Cg) ? w[((size_t)ko * Cg + (ci - g0)) * 9 + tap] : 0.f;
 }
@@ -115,11 +122,14 @@ __global__ __launch_bounds__(256, (GroupedShape<S, TW, KC>::WAVES)) void conv3x3
   const int kbase = (16 * wave / KC) * KC;
   int pb[G::RT];
 #pragma unroll
-  for (int t = 0; t < G::RT; ++t) pb[t] = (S * (t * G::RPT + ly) * G::PW + S * lx) * G::PS + kbase + 4 * h;
+  for (int t = 0; t < G::RT; ++t) pb[t] = (S * (t * G::RPT + ly) * G::PW + S * lx) * G::PS + kbase + (KC == 16 ? h : 4 * h);
   const float* fp = packed + (size_t)(cb * 4 + wave) * (9 * G::KG * 256) + lane * 4;
-  f32x4 acc[G::RT];
+  constexpr int NA = KC == 16 ? 4 : 1;   // accumulators per row tile: one per MFMA of a tap at KC = 16
+  f32x4 acc[NA][G::RT];
 #pragma unroll
-  for (int t = 0; t < G::RT; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int q = 0; q < NA; ++q)
+#pragma unroll
+    for (int t = 0; t < G::RT; ++t) acc[q][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
     const int toff = ((tap / 3) * G::PW + tap % 3) * G::PS;
@@ -128,11 +138,19 @@ __global__ __launch_bounds__(256, (GroupedShape<S, TW, KC>::WAVES)) void conv3x3
       const f32x4 f = *reinterpret_cast<const f32x4*>(fp + (tap * G::KG + kg) * 256);
       f32x4 a[G::RT];
 #pragma unroll
-      for (int t = 0; t < G::RT; ++t) a[t] = *reinterpret_cast<const f32x4*>(&lds[pb[t] + toff + 16 * kg]);
+      for (int t = 0; t < G::RT; ++t) {
+        if constexpr (KC == 16) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) a[t][j] = lds[pb[t] + toff + 4 * j];
+        } else {
+          a[t] = *reinterpret_cast<const f32x4*>(&lds[pb[t] + toff + 16 * kg]);
+        }
+      }
 #pragma unroll
       for (int j = 0; j < 4; ++j)
 #pragma unroll
-        for (int t = 0; t < G::RT; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[j], a[t][j], acc[t], 0, 0, 0);
+        for (int t = 0; t < G::RT; ++t)
+          acc[KC == 16 ? j : 0][t] = __builtin_amdgcn_mfma_f32_16x16x4f32(f[j], a[t][j], acc[KC == 16 ? j : 0][t], 0, 0, 0);
     }
   }
 
@@ -147,11 +165,18 @@ __global__ __launch_bounds__(256, (GroupedShape<S, TW, KC>::WAVES)) void conv3x3
 #pragma unroll
     for (int t = 0; t < G::RT; ++t) {
       const int oy = oy0 + t * G::RPT + ly, ox = ox0 + lx;
+      f32x4 sum = acc[0][t];
+      if constexpr (KC == 16) {   // the accumulators of the lane's own group (channels 4 h ..: group 4 h / Cg)
+        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+        sum = 0 == (4 * h) / g.Cg ? sum : zero;
+#pragma unroll
+        for (int j = 1; j < 4; ++j) sum += (4 * j) / g.Cg == (4 * h) / g.Cg ? acc[j][t] : zero;
+      }
       f32x4 r;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float y = acc[t][i] * sc[i] + bs[i];
-        r[i] = g.relu ? fmaxf(y, 0.f) : y;
+        const float y = sum[i] * sc[i] + bs[i];
+        r[i] = g.relu ? relu_nan(y) : y;
       }
       if (oy < g.H && ox < g.W) *reinterpret_cast<f32x4*>(out_n + (((oy + 1) * OWp + ox + 1) * g.C + ch)) = r;
     }
@@ -251,7 +276,7 @@ int wino_conv3x3_grouped_bn_relu_hw(const float* in, const float* packed, const 
   const int kc = g.KC == 16 ? 0 : g.KC == 32 ? 1 : 2;
   const GroupedKernel kernel = stride == 1 ? (g.TW == 16 ? GROUPED_BY_KC<1, 16>[kc] : GROUPED_BY_KC<1, 8>[kc])
                                            : (g.TW == 16 ? GROUPED_BY_KC<2, 16>[kc] : GROUPED_BY_KC<2, 8>[kc]);
-  const GroupedArgs a{Hin, Win, g.H, g.W, C, g.tiles_y, g.tiles_x, C / 64, relu != 0};
+  const GroupedArgs a{Hin, Win, g.H, g.W, C, g.tiles_y, g.tiles_x, C / 64, relu != 0, g.Cg};
   const unsigned wgs = (unsigned)((unsigned long long)N * g.tiles_y * g.tiles_x * (C / 64));
   hipLaunchKernelGGL(kernel, dim3(wgs), dim3(256), 0, (hipStream_t)s, in, packed, bnBias, bnScale, out, a);
   return launch_status("conv3x3_grouped_kernel");

@@ -37,7 +37,7 @@ __global__ void conv3x3_direct_kernel(const float* __restrict__ in, const float*
         s = fmaf(ip[(size_t)(r * Wp + q) * C + c], wp[c * 9 + r * 3 + q], s);
   }
   float y = bnScale[k] * s + bnBias[k];
-  if (relu) y = fmaxf(y, 0.f);
+  if (relu) y = relu_nan(y);
   out[idx] = y;
 }
 

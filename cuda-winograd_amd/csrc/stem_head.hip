@@ -172,7 +172,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
         if (p >= S::NPIX) continue;
         const int ci = p / S::CR, cj = p - ci * S::CR;
         const int cy = cy0 + ci, cx = cx0 + cj;
-        float v = fmaxf(acc[j][i] * sc + bs, 0.f);
+        float v = relu_nan(acc[j][i] * sc + bs);
         if (cy < 0 || cy >= g.Hc || cx < 0 || cx >= g.Wc) v = 0.f;
         lds[p * S::CS + ch] = v;
       }
@@ -203,7 +203,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ x, 
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) {
           const f32x4 v = *reinterpret_cast<const f32x4*>(&lds[((li + dy) * S::CR + lj + dx) * S::CS + 4 * q]);
-          m = f32x4{fmaxf(m.x, v.x), fmaxf(m.y, v.y), fmaxf(m.z, v.z), fmaxf(m.w, v.w)};
+          m = f32x4{max_nan(m.x, v.x), max_nan(m.y, v.y), max_nan(m.z, v.z), max_nan(m.w, v.w)};
         }
     }
     *reinterpret_cast<f32x4*>(on + ((size_t)r * OW + col) * g.K + 4 * q) = m;

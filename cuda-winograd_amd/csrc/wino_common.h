@@ -203,6 +203,12 @@ __device__ __forceinline__ unsigned fastdiv(unsigned n, FastDiv f) {
   return (t + ((n - t) >> 1)) >> (f.l - 1);
 }
 
+// ReLU and max as torch computes them: a NaN operand gives NaN (fmaxf is maxNum and returns the other operand, which
+// turns a NaN activation into a clean-looking 0).  Every epilogue uses these two; DESIGN.md section 1, "Non-finite
+// values".  relu: a NaN fails the compare and passes through, -Inf -> 0, +Inf stays.
+__host__ __device__ __forceinline__ float relu_nan(float y) { return y < 0.f ? 0.f : y; }
+__host__ __device__ __forceinline__ float max_nan(float m, float v) { return (v > m || v != v) ? v : m; }
+
 __device__ __forceinline__ void wait_vmem_all() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 }  // namespace wino

@@ -1001,8 +1001,8 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
 #pragma unroll
             for (int pp = 0; pp < 4; pp++) {
               float v1 = sc2[cb] * y[r][cb][pp] + bi2[cb];
-              if (relu) v1 = fmaxf(v1, 0.f);
-              m = pp == 0 ? v1 : fmaxf(m, v1);
+              if (relu) v1 = relu_nan(v1);
+              m = pp == 0 ? v1 : max_nan(m, v1);
             }
             *(float*)(wreg + (4 * r + e_h) * 128 + ((cb ^ (e_h >> 1)) << 6) + e_t16 * 4) = m;
           }
@@ -1039,7 +1039,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
 #pragma unroll
           for (int pp = 0; pp < 4; pp++) {
             float v1 = sc2[cb] * y[r][cb][pp] + bi2[cb];
-            if (!RES && relu) v1 = fmaxf(v1, 0.f);   // (RES: after the residual's add, below)
+            if (!RES && relu) v1 = relu_nan(v1);   // (RES: after the residual's add, below)
             const int g = pp * 2 + cb;
             *(float*)(wreg + ep_wbase[g & 3] + r * 512 + (g >> 2) * 256) = v1;
           }
@@ -1056,7 +1056,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
           val += rv[i];
           if (relu) {
 #pragma unroll
-            for (int q = 0; q < 4; q++) val[q] = fmaxf(val[q], 0.f);
+            for (int q = 0; q < 4; q++) val[q] = relu_nan(val[q]);
           }
         }
         const int g = tb * TB + e_wt * 16 + 2 * i + (ln >> 5);

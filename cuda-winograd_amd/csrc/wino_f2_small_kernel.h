@@ -416,8 +416,8 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
         val = sc4[c] * val + bi4[c];
 #pragma unroll
         for (int r = 0; r < 4; r++) {
-          if (relu) val[r] = fmaxf(val[r], 0.f);
-          m[r] = pp == 0 ? val[r] : fmaxf(m[r], val[r]);
+          if (relu) val[r] = relu_nan(val[r]);
+          m[r] = pp == 0 ? val[r] : max_nan(m[r], val[r]);
         }
       }
       *(f32x4*)(out + ((size_t)(tc.n * Hq + 1 + tc.ty) * Wq + 1 + tc.tx) * K + (kqq * CT + c) * 16 + 4 * h) = m;
@@ -435,7 +435,7 @@ wino_f2_small_kernel(const SmallArgs<EPI == EPI_RES> prm) {
       }
       if (relu) {
 #pragma unroll
-        for (int r = 0; r < 4; r++) val[r] = fmaxf(val[r], 0.f);
+        for (int r = 0; r < 4; r++) val[r] = relu_nan(val[r]);
       }
       // (odd H or W: the last tile row / column computes one output row / column too many; it must not reach the ring)
       if (!GEN || (oy + (pp >> 1) <= Hp - 2 && ox + (pp & 1) <= Wp - 2))

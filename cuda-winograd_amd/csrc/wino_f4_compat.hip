@@ -99,7 +99,7 @@ __global__ void f4_output_transform_kernel(const float* __restrict__ M, const fl
       const int row = 4 * tx + 1 + a, col = 4 * ty + 1 + b;
       if (row <= WINO_PQ && col <= WINO_PQ) {   // the reference's clip (Kernel128_winograd.cu:155,171,177)
         float y = sc * o[b] + bi;
-        if (relu) y = fmaxf(y, 0.f);
+        if (relu) y = relu_nan(y);
         out[((size_t)(n * WINO_HW + row) * WINO_HW + col) * K + k] = y;
       }
     }

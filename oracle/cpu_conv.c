@@ -223,7 +223,7 @@ int oracle_winograd_f4(const float* in, const float* U36, const float* scale, co
         if (y > PQ || x > PQ) continue;
         for (q = 0; q < 6; q++) s += atm[i][q] * AT4[j][q];
         o = scale[k] * s + bias[k];
-        out[(((size_t)n * HW + y) * HW + x) * K + k] = o > 0.f ? o : 0.f;
+        out[(((size_t)n * HW + y) * HW + x) * K + k] = o < 0.f ? 0.f : o;
       }
     }
   }

@@ -25,10 +25,12 @@ def V(pkg):
 
 
 def rel(torch, got, want):
-    """max |got - want| / max |want| against an fp64 CPU tensor; the shapes agree and `got` holds no NaN."""
+    """max |got - want| / max |want| against an fp64 CPU tensor; the shapes agree and both sides are finite (no NaN,
+    and no Inf either: inf - inf must never pass a tolerance comparison)."""
     got = got.detach().cpu().double()
     assert got.shape == want.shape, (got.shape, want.shape)
-    assert not torch.isnan(got).any()
+    assert bool(torch.isfinite(got).all()), "got holds non-finite values"
+    assert bool(torch.isfinite(want).all()), "the reference holds non-finite values"
     return float((got - want).abs().max() / want.abs().max())
 
 

@@ -2,13 +2,12 @@
 the smallest shapes that exercise each index path, against fp64 with F.interpolate(nearest) at 2e-5, the coarse map's
 ring NaN; the same layer between guards; the stream-K form's hand-off state; one pyramid level; and whole ResNet-FPN
 backbones against an fp64 CPU forward of torchvision's BackboneWithFPN."""
-import contextlib
-
 import pytest
 
 import guarded as G
 import shape_sweeps as S
 from cases import TIGHT
+from forms_1x1 import FORMS, knobs_set as _knobs, sk_plan as _sk_plan, takes as _takes
 from fpn_reference import (LAYER_TOL, Up2Layer, fpn_random_state_dict, fpn_reference_forward, level_reference,
                            padded_nan, up_hw)
 from gpu_support import (R, dirty_ticket_scenario, graph_replay_scenario, network_graph_scenario, rel,  # noqa: F401
@@ -21,57 +20,6 @@ pytestmark = pytest.mark.gpu
 # alone; H != W; a single pixel; 2x3 over 1x2
 SHAPES = [(3, 14, 14), (2, 7, 7), (2, 5, 9), (1, 1, 1), (2, 2, 3)]
 CHANNELS = [(32, 64), (64, 128), (160, 256)]   # the last gives the 8-wave workgroups
-
-TILED = {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 0}
-FORMS = {"auto": {}, "tiled": TILED}
-FORMS.update({f"sk{g}": {"WINO_1X1_ALGO": "big", "WINO_1X1_SK": 1, "WINO_1X1_SK_GRID": g} for g in (8, 24)})
-FORMS.update({f"latency_ks{ks}_rt{rt}_ct{ct}": {"WINO_1X1_ALGO": "small", "WINO_1X1_SMALL_KS": ks,
-                                                 "WINO_1X1_SMALL_RT": rt, "WINO_1X1_SMALL_CT": ct}
-              for ks in (1, 2, 4) for rt in (1, 2) for ct in (1, 2, 4)})
-
-
-@contextlib.contextmanager
-def _knobs(knobs, kv):
-    for k, v in kv.items():
-        knobs.set(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            knobs.unset(k)
-
-
-def _sk_plan(M, Cin, Kout, grid):
-    """(legal, cuts a tile) of the stream-K form with WINO_1X1_SK_GRID = grid, as sk1_grid in conv1x1.hip decides."""
-    four = Kout <= 128 or Cin <= 128 or Kout % 128 != 0
-    nblk, nk, nmb = Kout // (64 if four else 128), Cin // 32, (M + 111) // 112
-    step = 8
-    while step % nblk:
-        step += 8
-    g = min(grid, nmb * nblk * nk)
-    g -= g % step
-    if g < step:
-        return False, False
-    ranges, units = g // nblk, nmb * nk
-    return True, any((units * r // ranges) % nk for r in range(1, ranges))
-
-
-def _takes(pkg, form, M, Cin, Kout):
-    """Does the plan, under the knobs of `form` (set by the caller), take that form for this GEMM?  The forms a shape
-    cannot take -- a K split its Cin does not divide, a grid with more ranges than k-steps -- are skipped by the
-    caller; that each form runs somewhere is test_every_form_runs_somewhere's."""
-    kv = FORMS[form]
-    if form.startswith("latency"):
-        use, ks, rt, ct, _ = pkg.small_plan_1x1_full(M, Cin, Kout, S.CUS)
-        return bool(use) and (ks, rt, ct) == (kv["WINO_1X1_SMALL_KS"], kv["WINO_1X1_SMALL_RT"], kv["WINO_1X1_SMALL_CT"])
-    planned = S.form_1x1(pkg, M, Cin, Kout)
-    if form.startswith("sk"):
-        legal, _ = _sk_plan(M, Cin, Kout, kv["WINO_1X1_SK_GRID"])
-        assert (planned == "stream_k") == legal, (form, M, Cin, Kout, planned)
-        return legal
-    if form == "tiled":
-        assert planned == "tiled"
-    return True
 
 
 def _pad_forms(pkg):

@@ -28,6 +28,11 @@ for ci, spec in enumerate(sys.argv[1:]):
     L.wino_residual_block.argtypes = [P] * 11 + [c_int, c_int, c_int, P, ctypes.c_size_t, P]
     L.wino_residual_block_workspace_bytes.restype = ctypes.c_size_t
     L.wino_residual_block_workspace_bytes.argtypes = [c_int, c_int]
+    L.wino_conv3x3_bn_relu_pool_hw.argtypes = [P, P, P, P, P] + [c_int] * 6 + [P]
+    L.wino_conv3x3_grouped_filter_elems.restype = ctypes.c_size_t
+    L.wino_conv3x3_grouped_filter_elems.argtypes = [c_int, c_int]
+    L.wino_conv3x3_grouped_filter_pack.argtypes = [P, P, c_int, c_int, P]
+    L.wino_conv3x3_grouped_bn_relu_hw.argtypes = [P, P, P, P, P] + [c_int] * 7 + [P]
     libs.append((path, L))
 st = lambda: P(torch.cuda.current_stream().cuda_stream)
 def bench(name, fns, reps=200, rounds=5):
@@ -51,8 +56,8 @@ print(f"{'us per launch':34s}" + "  ".join(f"{os.path.basename(os.path.dirname(o
 N = int(os.environ.get("AB_N", "128"))
 M = N * 196
 rnd = lambda *s: (torch.rand(*s, device=dev) - 0.5)
-only = os.environ.get("AB_ONLY", "")   # "3x3" / "1x1": just those layers
-for (Cin, Kout, relu) in ((512, 128, 1), (128, 512, 0), (1024, 256, 1), (256, 1024, 0), (64, 256, 0), (2048, 512, 1)) if only not in ("3x3", "block") else ():
+only = os.environ.get("AB_ONLY", "")   # "3x3" / "1x1" / "block" / "pool" / "grouped": just those layers
+for (Cin, Kout, relu) in ((512, 128, 1), (128, 512, 0), (1024, 256, 1), (256, 1024, 0), (64, 256, 0), (2048, 512, 1)) if only not in ("3x3", "block", "pool", "grouped") else ():
     A, B, b, s, C = rnd(M, Cin), rnd(Cin, Kout), rnd(Kout), rnd(Kout), torch.empty(M, Kout, device=dev)
     fns = [(lambda L=L: L.wino_conv1x1_bn(A.data_ptr(), B.data_ptr(), b.data_ptr(), s.data_ptr(), C.data_ptr(), M, Cin, Kout, relu, st())) for _, L in libs]
     outs = []
@@ -85,9 +90,35 @@ if only in ("", "block"):
         outb.fill_(float("nan")); assert f() == 0; outs.append(outb.clone())
     same = all(torch.equal(o, outs[0]) for o in outs)
     bench(f"bottleneck block 1024/256 N={N}{'' if same else '  (DIFFER)'}", fns, reps=100)
-for Cc in (128, 256) if only not in ("1x1", "block") else ():
+for Cc in (128, 256) if only not in ("1x1", "block", "pool", "grouped") else ():
     x, w, b, s = rnd(N, 16, 16, Cc), rnd(Cc, Cc, 3, 3), rnd(Cc), rnd(Cc)
     U, out = torch.empty(16 * Cc * Cc, device=dev), torch.empty(N, 16, 16, Cc, device=dev)
     libs[0][1].wino_filter_transform_f2(w.data_ptr(), U.data_ptr(), Cc, Cc, st())
     fns = [(lambda L=L: L.wino_conv3x3_bn_relu(x.data_ptr(), U.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(), N, Cc, Cc, 1, st())) for _, L in libs]
     bench(f"3x3 {Cc}->{Cc} N={N}", fns)
+for Cc in (256,) if only in ("", "pool") else ():   # the pooled epilogue (VGG): 14x14 -> 7x7
+    x, w, b, s = rnd(N, 16, 16, Cc), rnd(Cc, Cc, 3, 3), rnd(Cc), rnd(Cc)
+    U, out = torch.empty(16 * Cc * Cc, device=dev), torch.empty(N, 9, 9, Cc, device=dev)
+    libs[0][1].wino_filter_transform_f2(w.data_ptr(), U.data_ptr(), Cc, Cc, st())
+    fns = [(lambda L=L: L.wino_conv3x3_bn_relu_pool_hw(x.data_ptr(), U.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(), N, 14, 14, Cc, Cc, 1, st())) for _, L in libs]
+    for f in fns:
+        assert f() == 0
+    bench(f"3x3+pool {Cc}->{Cc} N={N}", fns)
+
+# the grouped 3x3 of ResNeXt-50 32x4d's stages (Cg = 4, 8, 16, 32); the packed layout belongs to each library
+for (Cc, Cg, hw, Ng) in ((128, 4, 56, 32), (256, 8, 28, 32), (512, 16, 14, 32), (1024, 32, 7, 32)) if only in ("", "grouped") else ():
+    x, w, b, s = rnd(Ng, hw + 2, hw + 2, Cc), rnd(Cc, Cg, 3, 3), rnd(Cc), rnd(Cc)
+    x[:, 0] = 0; x[:, -1] = 0; x[:, :, 0] = 0; x[:, :, -1] = 0
+    out = torch.empty(Ng, hw + 2, hw + 2, Cc, device=dev)
+    packs = []
+    for _, L in libs:
+        pk = torch.empty(L.wino_conv3x3_grouped_filter_elems(Cc, Cc // Cg), device=dev)
+        assert L.wino_conv3x3_grouped_filter_pack(w.data_ptr(), pk.data_ptr(), Cc, Cc // Cg, st()) == 0
+        packs.append(pk)
+    fns = [(lambda L=L, pk=pk: L.wino_conv3x3_grouped_bn_relu_hw(x.data_ptr(), pk.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(), Ng, hw, hw, Cc, Cc // Cg, 1, 1, st())) for (_, L), pk in zip(libs, packs)]
+    outs = []
+    for f in fns:
+        out.fill_(float("nan")); assert f() == 0; outs.append(out.clone())
+    err = max(float((o - outs[0]).abs().max()) for o in outs)
+    bench(f"grouped 3x3 C={Cc} Cg={Cg} {hw}x{hw} N={Ng}", fns)
+    print(f"    (max |difference| between the libraries' outputs: {err:.2e})", flush=True)
