@@ -374,12 +374,13 @@ def conv1x1_bn_ex(A, B, bn_bias, bn_scale, flags: int, residual=None, out=None, 
     return out
 
 
-def _bottleneck(entry, x, w1, bn1, mid, w2, bn2, last, bn3, out, workspace, stride=1, groups=None):
-    """The one body of the five bottleneck wrappers: operands checked against each other, workspace and output made or
+def _bottleneck(entry, x, w1, bn1, mid, w2, bn2, last, bn3, out, workspace, stride=1, groups=None, dilation=None):
+    """The one body of the seven bottleneck wrappers: operands checked against each other, workspace and output made or
     checked, then `entry(x, w1, bn1, w2, bn2, last[, bn3], out, N, Hin, Win, Cin, Cm[, C4][, groups][, stride],
     workspace, stream)`.  `mid` names what w2 is packed for: "U2" (filter_transform_f2: Winograd, a stride sits on the
-    first 1x1), "w2_taps" (filter_pack_s2: the 3x3 at stride 2, which its entry point does not take as an argument) or
-    "wg" (filter_pack_grouped: `stride` on the 3x3).  `last` is w3 with its bn3 (identity shortcut: C4 = Cin) or, bn3
+    first 1x1), "w2_taps" (filter_pack_s2: the 3x3 as an implicit GEMM -- at stride 2, or, with `dilation`, at stride 1
+    with that dilation; neither entry point takes a stride argument) or "wg" (filter_pack_grouped: `stride` on the
+    3x3).  `dilation` is passed last among the dimensions.  `last` is w3 with its bn3 (identity shortcut: C4 = Cin) or, bn3
     None, the packed tail of a projection block."""
     identity = bn3 is not None
     x = _dev(x, "x")
@@ -424,8 +425,10 @@ def _bottleneck(entry, x, w1, bn1, mid, w2, bn2, last, bn3, out, workspace, stri
     dims = (N, Hin, Win, Cin, Cm) if identity else (N, Hin, Win, Cin, Cm, C4)
     if mid == "wg":
         dims += (groups,)
-    if not identity and mid != "w2_taps":
+    if not identity and mid != "w2_taps":   # (the v1.5 and the dilated projection blocks take no stride argument)
         dims += (int(stride),)
+    if dilation is not None:
+        dims += (int(dilation),)
     if entry == "wino_residual_block_hw" and (H, W) == (14, 14):   # the reference's stage has an entry point of its own
         entry, dims = "wino_residual_block", (N, C4, Cm)
     _check(getattr(lib(), entry)(x.data_ptr(), w1.data_ptr(), vecs[0].data_ptr(), vecs[1].data_ptr(), w2.data_ptr(),
@@ -535,6 +538,64 @@ def proj_block_v15(x, w1, bn1, w2_taps, bn2, tail, out=None, workspace=None) -> 
     [N][H][W][C4], H = (Hin-1)//2 + 1.  bnX = (bias, scale) folded BN vectors; w1 [Cin][Cm]; w2_taps [3][3][Cm][Cm]
     from filter_pack_s2; tail from proj_tail_pack (w3, bn3, wp, bnp)."""
     return _bottleneck("wino_proj_block_v15_hw", x, w1, bn1, "w2_taps", w2_taps, bn2, tail, None, out, workspace, 2)
+
+
+def conv3x3_dilated_bn_relu(inp: torch.Tensor, w_taps: torch.Tensor, bn_bias: torch.Tensor, bn_scale: torch.Tensor,
+                            dilation: int, relu: bool = True, out: torch.Tensor | None = None) -> torch.Tensor:
+    """Stride-1 3x3 conv with dilation = padding = `dilation` + folded BN (+ReLU): inp [N][H+2][W+2][C] with a zero ring
+    of width one (whatever the dilation) -> out [N][H+2][W+2][K], zero ring.  w_taps [3][3][C][K] from filter_pack_s2.
+    One launch of the tiled 1x1 GEMM kernel in its dilated-tap operand form."""
+    x, w = _dev(inp, "inp"), _dev(w_taps, "w_taps")
+    b, s = _dev(bn_bias, "bn_bias"), _dev(bn_scale, "bn_scale")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("inp must be [N][H+2][W+2][C]")
+    N, H, W, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    if w.dim() != 4 or tuple(w.shape[:3]) != (3, 3, C):
+        raise WinoError(f"w_taps must be [3][3][{C}][K]: pack it with filter_pack_s2")
+    K = int(w.shape[3])
+    if b.numel() != K or s.numel() != K:
+        raise WinoError("bn vectors do not match K")
+    out = _output(out, (N, H + 2, W + 2, K), x.device)
+    _on_current_device(x, w, b, s, out)
+    _check(lib().wino_conv3x3_dilated_bn_relu_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(),
+                                                 out.data_ptr(), N, H, W, C, K, int(dilation), int(relu), _stream()),
+           "wino_conv3x3_dilated_bn_relu_hw")
+    return out
+
+
+def conv3x3_dilated_prepare(N: int, H: int, W: int, C: int, K: int, dilation: int) -> None:
+    """Allocate the dilated 3x3 layer's stream-K scratch for the current stream (before graph capture)."""
+    _prepare("wino_conv3x3_dilated_prepare_hw", N, H, W, C, K, dilation)
+
+
+def conv3x3_dilated_plan(N: int, H: int, W: int, C: int, K: int, dilation: int, cus: int = 256) -> int:
+    """The FORM_* the dilated 3x3 layer takes on a device with `cus` CUs (host-side): FORM_TILED or FORM_STREAM_K."""
+    return _plan_query("wino_conv3x3_dilated_plan", 1, int(N), int(H), int(W), int(C), int(K), int(dilation),
+                       int(cus))[0]
+
+
+def dilated_residual_block_prepare(N: int, H: int, W: int, C4: int, Cm: int, dilation: int) -> None:
+    """Allocate the scratch of dilated_residual_block's three launches for the current stream (before graph capture)."""
+    _prepare("wino_dilated_residual_block_prepare_hw", N, H, W, C4, Cm, dilation)
+
+
+def dilated_residual_block(x, w1, bn1, w2_taps, bn2, w3, bn3, dilation: int, out=None, workspace=None) -> torch.Tensor:
+    """Identity bottleneck of a dilated stage: residual_block with the dilated 3x3 in the middle.  x [N][H][W][C4] ->
+    same shape; w1 [C4][Cm], w3 [Cm][C4]; w2_taps [3][3][Cm][Cm] from filter_pack_s2; bnX = (bias, scale)."""
+    return _bottleneck("wino_dilated_residual_block_hw", x, w1, bn1, "w2_taps", w2_taps, bn2, w3, bn3, out, workspace,
+                       dilation=dilation)
+
+
+def dilated_proj_block_prepare(N: int, H: int, W: int, Cin: int, Cm: int, C4: int, dilation: int) -> None:
+    """Allocate the scratch of dilated_proj_block's three launches for the current stream (before graph capture)."""
+    _prepare("wino_dilated_proj_block_prepare_hw", N, H, W, Cin, Cm, C4, dilation)
+
+
+def dilated_proj_block(x, w1, bn1, w2_taps, bn2, tail, dilation: int, out=None, workspace=None) -> torch.Tensor:
+    """Projection bottleneck of a dilated stage (stride 1, the dilated 3x3 in the middle): x [N][H][W][Cin] ->
+    [N][H][W][C4].  w1 [Cin][Cm]; w2_taps [3][3][Cm][Cm] from filter_pack_s2; tail from proj_tail_pack (stride 1)."""
+    return _bottleneck("wino_dilated_proj_block_hw", x, w1, bn1, "w2_taps", w2_taps, bn2, tail, None, out, workspace, 1,
+                       dilation=dilation)
 
 
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
@@ -960,3 +1021,4 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
 from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)
 from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
+from .segmentation import FCN  # noqa: E402

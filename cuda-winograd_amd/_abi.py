@@ -153,6 +153,14 @@ SIGNATURES = {
     # ---- Feature Pyramid Network
     "wino_fpn_level_hw": (i, [vp] * 10 + [i] * 6 + [vp]),
     "wino_fpn_level_prepare_hw": (i, [i] * 5 + [vp]),
+    # ---- dilated 3x3 and the dilated bottleneck blocks
+    "wino_conv3x3_dilated_bn_relu_hw": (i, [vp] * 5 + [i] * 7 + [vp]),
+    "wino_conv3x3_dilated_prepare_hw": (i, [i] * 6 + [vp]),
+    "wino_conv3x3_dilated_plan": (i, [i] * 7 + [ip]),
+    "wino_dilated_residual_block_hw": (i, [vp] * 11 + [i] * 6 + [vp, sz, vp]),
+    "wino_dilated_residual_block_prepare_hw": (i, [i] * 6 + [vp]),
+    "wino_dilated_proj_block_hw": (i, [vp] * 9 + [i] * 7 + [vp, sz, vp]),
+    "wino_dilated_proj_block_prepare_hw": (i, [i] * 7 + [vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -34,12 +34,12 @@ class Net:
         self._shape = None
 
     @classmethod
-    def _load(cls, sd, eps, device, *args):
-        """cls(*args, device) with `sd` packed on `device` (default: the current CUDA device)."""
+    def _load(cls, sd, eps, device, *args, **kwargs):
+        """cls(*args, device, **kwargs) with `sd` packed on `device` (default: the current CUDA device)."""
         dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if dev.type != "cuda":
             raise WinoError(f"{cls.__name__} runs on a CUDA(HIP) device only -- there is no CPU path")
-        m = cls(*args, dev)
+        m = cls(*args, dev, **kwargs)
         with torch.cuda.device(dev):
             m._pack(sd, eps)
         return m

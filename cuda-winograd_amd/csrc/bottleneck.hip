@@ -1,4 +1,4 @@
-// The bottleneck blocks: one composition behind five block entry points (and the 14x14 form of the first).
+// The bottleneck blocks: one composition behind seven block entry points (and the 14x14 form of the first).
 //   first 1x1 (+BN+ReLU)           ->  t1, padded [N][H1+2][W1+2][Cm]   (workspace)
 //   middle 3x3 (+BN+ReLU)          ->  t2, padded [N][H+2][W+2][Cm]     (workspace)
 //   last 1x1 + shortcut (+ReLU)    ->  out [N][H][W][C4]
@@ -10,11 +10,14 @@
 //   proj_block_v15_hw             3x3, 2        stride-2 implicit GEMM (conv3x3_s2)    fused tail
 //   grouped_residual_block_hw     none          grouped (conv3x3_grouped.hip)          1x1 + residual x
 //   grouped_proj_block_hw         3x3, 1 or 2   grouped                                fused tail
+//   dilated_residual_block_hw     none          dilated implicit GEMM (conv3x3_dilated) 1x1 + residual x
+//   dilated_proj_block_hw         none (1)      dilated implicit GEMM                  fused tail
 // From the row follow, once each: the shape check (the layers' own checks, so that a shape any of them refuses launches
 // nothing), the workspace size and its t1 / t2 split, the overlap test, and ONE listing of the three layers
 // (run_bottleneck) that the block's launch and its *_prepare both walk -- a prepare reserves the stream scratch of
 // exactly the launches the block makes.  Every refusal comes in one order: NULL, alignment, shape, workspace size,
 // overlap, then the launches' device queries.  Host code over the layers' launches: this file instantiates no kernel.
+#include "conv3x3_dilated.h"
 #include "conv3x3_grouped.h"
 #include "proj_block.h"
 
@@ -22,7 +25,7 @@ namespace wino {
 namespace {
 
 enum StrideAt { STRIDE_NONE, STRIDE_FIRST, STRIDE_MIDDLE };   // which layer carries the stride (and the shortcut with it)
-enum Middle { MID_WINOGRAD, MID_S2_GEMM, MID_GROUPED };
+enum Middle { MID_WINOGRAD, MID_S2_GEMM, MID_GROUPED, MID_DILATED };
 enum Last { LAST_RESIDUAL, LAST_TAIL };   // 1x1 + the identity shortcut (Cin = C4), or the fused projection tail
 struct Bottleneck {
   int N, Hin, Win, Cin, Cm, C4;
@@ -31,6 +34,7 @@ struct Bottleneck {
   Middle mid;
   int groups;   // MID_GROUPED
   Last last;
+  int dilation = 1;   // MID_DILATED
 };
 // A launch's tensors; w3: the last 1x1's matrix, or the packed tail (then without b3 / s3)
 struct Tensors {
@@ -59,6 +63,10 @@ int check_shape(const Bottleneck& b, ProjGeom* g) {
     case MID_S2_GEMM: {
       S2Geom g2;
       return check_s2(b.N, b.Hin, b.Win, b.Cm, b.Cm, &g2);
+    }
+    case MID_DILATED: {
+      DilGeom gd;
+      return check_dilated(b.N, b.Hin, b.Win, b.Cm, b.Cm, b.dilation, &gd);
     }
     default: {
       GroupedGeom gg;
@@ -110,6 +118,10 @@ int run_bottleneck(const Bottleneck& b, const Tensors* t, void* workspace, size_
       rc = t ? wino_conv3x3_s2_bn_relu_hw(t1, t->w2, t->b2, t->s2, t2, N, H1, W1, Cm, Cm, 1, s)
              : wino_conv3x3_s2_prepare_hw(N, H1, W1, Cm, Cm, s);
       break;
+    case MID_DILATED:
+      rc = t ? wino_conv3x3_dilated_bn_relu_hw(t1, t->w2, t->b2, t->s2, t2, N, H1, W1, Cm, Cm, b.dilation, 1, s)
+             : wino_conv3x3_dilated_prepare_hw(N, H1, W1, Cm, Cm, b.dilation, s);
+      break;
     default:   // (the grouped layer uses no stream scratch)
       rc = t ? wino_conv3x3_grouped_bn_relu_hw(t1, t->w2, t->b2, t->s2, t2, N, H1, W1, Cm, b.groups, g.s, 1, s) : WINO_OK;
   }
@@ -121,7 +133,7 @@ int run_bottleneck(const Bottleneck& b, const Tensors* t, void* workspace, size_
                                WINO_RELU | WINO_A_PADDED | WINO_ADD_RESIDUAL, s);
 }
 
-// the five rows of the table
+// the seven rows of the table
 Bottleneck residual(int N, int H, int W, int C4, int Cm) {
   return {N, H, W, C4, Cm, C4, STRIDE_NONE, 1, MID_WINOGRAD, 1, LAST_RESIDUAL};
 }
@@ -136,6 +148,12 @@ Bottleneck grouped_residual(int N, int H, int W, int C4, int Cm, int groups) {
 }
 Bottleneck grouped_proj(int N, int Hin, int Win, int Cin, int Cm, int C4, int groups, int stride) {
   return {N, Hin, Win, Cin, Cm, C4, STRIDE_MIDDLE, stride, MID_GROUPED, groups, LAST_TAIL};
+}
+Bottleneck dilated_residual(int N, int H, int W, int C4, int Cm, int dilation) {
+  return {N, H, W, C4, Cm, C4, STRIDE_NONE, 1, MID_DILATED, 1, LAST_RESIDUAL, dilation};
+}
+Bottleneck dilated_proj(int N, int H, int W, int Cin, int Cm, int C4, int dilation) {
+  return {N, H, W, Cin, Cm, C4, STRIDE_MIDDLE, 1, MID_DILATED, 1, LAST_TAIL, dilation};
 }
 
 }  // namespace
@@ -239,6 +257,32 @@ int wino_grouped_proj_block_hw(const float* x, const float* w1, const float* bn1
 int wino_grouped_proj_block_prepare_hw(int N, int Hin, int Win, int Cin, int Cm, int C4, int groups, int stride,
                                        wino_stream_t s) {
   return run_bottleneck(grouped_proj(N, Hin, Win, Cin, Cm, C4, groups, stride), nullptr, nullptr, 0, s);
+}
+
+// ---- the dilated blocks (the segmentation backbones' layer3 / layer4): the dilated 3x3 in the middle, stride 1.
+// Their intermediates are the dense blocks', so their workspaces are sized by the dense blocks' queries above.
+int wino_dilated_residual_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                                   const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* w3,
+                                   const float* bn3Bias, const float* bn3Scale, float* out, int N, int H, int W, int C4,
+                                   int Cm, int dilation, void* workspace, size_t workspace_bytes, wino_stream_t s) {
+  const Tensors t{x, w1, bn1Bias, bn1Scale, w2_taps, bn2Bias, bn2Scale, w3, bn3Bias, bn3Scale, out};
+  return run_bottleneck(dilated_residual(N, H, W, C4, Cm, dilation), &t, workspace, workspace_bytes, s);
+}
+
+int wino_dilated_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, int dilation, wino_stream_t s) {
+  return run_bottleneck(dilated_residual(N, H, W, C4, Cm, dilation), nullptr, nullptr, 0, s);
+}
+
+int wino_dilated_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                               const float* w2_taps, const float* bn2Bias, const float* bn2Scale,
+                               const float* tail_packed, float* out, int N, int H, int W, int Cin, int Cm, int C4,
+                               int dilation, void* workspace, size_t workspace_bytes, wino_stream_t s) {
+  const Tensors t{x, w1, bn1Bias, bn1Scale, w2_taps, bn2Bias, bn2Scale, tail_packed, nullptr, nullptr, out};
+  return run_bottleneck(dilated_proj(N, H, W, Cin, Cm, C4, dilation), &t, workspace, workspace_bytes, s);
+}
+
+int wino_dilated_proj_block_prepare_hw(int N, int H, int W, int Cin, int Cm, int C4, int dilation, wino_stream_t s) {
+  return run_bottleneck(dilated_proj(N, H, W, Cin, Cm, C4, dilation), nullptr, nullptr, 0, s);
 }
 
 }  // extern "C"

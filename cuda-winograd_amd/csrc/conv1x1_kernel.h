@@ -97,7 +97,17 @@ __device__ __forceinline__ long padded_row(long m, const PadGeo& g) {
 //              tiles over k-steps [4C / BK, 5C / BK): B is advanced by 5 C rows (GEMM row 4C + j is packed row
 //              9C + j), the second BN, no ReLU, the stores go to R (the latency kernel appends row blocks instead:
 //              conv1x1_small_kernel.h).  The 3x3's workgroups run exactly as A_TAPS.
-enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3, A_TAPS_PROJ = 4 };
+//   A_DIL      a stride-1 3x3 convolution with dilation d and padding d as one GEMM of K = 9 C (conv3x3_dilated.hip),
+//              tiled forms only.  A is the padded [N][H+2][W+2][C] input with a zero ring of width ONE (cx = C,
+//              cm = W+2, s = d; pg is the H x W grid of both input and output).  Tap (dy, dx) of output pixel (y, x)
+//              lies d ((dy-1)(W+2) + (dx-1)) pixels from the row's centre pixel (y+1, x+1) when (y + d(dy-1),
+//              x + d(dx-1)) is inside the image, and is a zero otherwise: the lane then reads the left ring pixel of
+//              its own padded line.  So the A offset is per lane and per tap: each lane keeps its centre offset and
+//              a 9-bit validity mask per A piece and rebuilds the piece's offset when the (wave-uniform) tap changes,
+//              every C / BK k-steps; inside a tap the k-step advance is the usual scalar.  The descriptor window is
+//              the tile's centre pixels plus the taps' reach d (W+2) + d to either side, clipped to the tensor: no
+//              valid tap and no ring pixel lies outside it, and nothing outside `in` is ever addressed.  B as A_TAPS.
+enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3, A_TAPS_PROJ = 4, A_DIL = 5 };
 struct ProjGeo {
   const float* X;         // A_TWO: the block input x
   unsigned img, row, s;   // x's pixels per image (Hin*Win), pixels per strided row step (s*Win), the stride
@@ -205,7 +215,8 @@ __device__ unsigned long long wino_clk_slot_1x1[4];
 // tail matrix.  The stride-2 3x3 layer (conv3x3_s2.hip) runs A_TAPS the same way: A = the padded input, Cin = 9 C.
 // A_TAPS_PROJ (basic_block_s2.hip) is A_TAPS with the shortcut's whole tiles appended to the grid: batchA, unused by
 // the tap forms, is the 3x3's own grid -- the stream-K ranges and the ring pass are cut over that, never over the
-// appended tiles.
+// appended tiles.  The dilated 3x3 layer (conv3x3_dilated.hip) runs A_DIL: A = the padded input, Cin = 9 C, per-lane
+// tap offsets rebuilt at every tap change.
 // xg is last, so that the plain form's other arguments keep their offsets.
 template <int BK, int NW, int ABLATE = 0, bool SK = false, int RES = RES_NONE, int AF = A_PLAIN>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3)
@@ -376,19 +387,35 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   //   A_STRIDED / A_TWO past kb: rows map into the strided x, a window about s^2 times as long (host-checked < 4 GiB).
   //   A_TAPS: rows map into the padded input the same way, and the window grows by the taps' reach, 2 (Win+2) + 2
   //      pixels past the last row (host-checked < 4 GiB); the k offset of a k-step is tap_offset(k BK) * 4 bytes.
+  //   A_DIL: rows map to their centre pixels in the padded input; the window grows by the taps' reach d (W+2) + d pixels
+  //      to BOTH sides and is clipped to the tensor (host-checked < 4 GiB unclipped); the per-piece offsets change with
+  //      the tap (dil_set below), the k offset inside a tap is (k-step inside the tap) * BK * 4 bytes.
   const bool a_str = AF == A_STRIDED || TAPS || (AF == A_TWO && k0 >= kb);
   const float* const Aseg = AF == A_TWO && a_str ? xg.X : A;
-  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : TAPS ? xg.cx : Cin;   // A row length of this segment
+  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : (TAPS || AF == A_DIL) ? xg.cx : Cin;   // A row length of this segment
   const int ka = AF == A_TWO && a_str ? k0 - kb : k0;        // its first k-step inside that source
-  const long a_row0 = a_str ? strided_row(m0 < M ? m0 : M - 1, pg, xg)
-                            : a_padded ? padded_row(m0 < M ? m0 : M - 1, pg) : (m0 < M ? m0 : M - 1);
+  long a_row0 = a_str ? strided_row(m0 < M ? m0 : M - 1, pg, xg)
+                      : (a_padded || AF == A_DIL) ? padded_row(m0 < M ? m0 : M - 1, pg) : (m0 < M ? m0 : M - 1);
   const long m_last = m0 + BM - 1 < M ? m0 + BM - 1 : M - 1;
-  long a_rows = (a_str ? strided_row(m_last, pg, xg) : a_padded ? padded_row(m_last, pg) : m_last) - a_row0 + 1;
+  long a_rows = (a_str ? strided_row(m_last, pg, xg) : (a_padded || AF == A_DIL) ? padded_row(m_last, pg) : m_last) - a_row0 + 1;
   if constexpr (TAPS) a_rows += 2 * (long)xg.cm + 2;
+  if constexpr (AF == A_DIL) {
+    // the centre pixels [a_row0, a_row0 + a_rows) grown by the taps' reach and clipped to the tensor's pixels
+    const unsigned reach = xg.s * (unsigned)(xg.cm + 1);   // (its bytes are below 2^32: checked on the host)
+    const long total = (long)fastdiv((unsigned)M, pg.d_hw) * (long)(pg.Hp * pg.Wp);
+    const long end = a_row0 + a_rows + reach < total ? a_row0 + a_rows + reach : total;
+    a_row0 = a_row0 > (long)reach ? a_row0 - reach : 0;
+    a_rows = end - a_row0;
+  }
   const auto rsrc_a = make_rsrc(Aseg + a_row0 * ca, (unsigned)(a_rows * ca * (long)sizeof(float)));
   const auto rsrc_b = make_rsrc(B, (unsigned)((size_t)Cin * Kout * sizeof(float)));
   unsigned a_voff[G::A_PER_WAVE];
   int a_q[G::A_PER_WAVE];
+  // A_DIL, per A piece: the byte offset of the lane's 16 bytes at its row's centre pixel, and (bits 0-8) which taps
+  // 3 dy + dx lie inside the image, (bits 9-) x + 1, the pixels back to the left ring pixel of the row's padded line
+  // (the state of A_DIL outlives its `if constexpr` blocks, so it is declared for every form: one element and no code there)
+  constexpr int DIL_N = AF == A_DIL ? G::A_PER_WAVE : 1;
+  unsigned dil_c[DIL_N], dil_m[DIL_N];
 #pragma unroll
   for (int j = 0; j < G::A_PER_WAVE; j++) {
     int q = w + NW * j;
@@ -398,6 +425,18 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     const int unit = (lane % G::UNITS) ^ G::fa(row);
     long gr = m0 + row;
     gr = gr < M ? gr : M - 1;  // clamp: rows past the end read a valid row
+    if constexpr (AF == A_DIL) {
+      const unsigned mu = (unsigned)gr;   // M < 2^31 (checked on the host)
+      const unsigned n = fastdiv(mu, pg.d_hw);
+      const unsigned rem = mu - n * pg.hw;
+      const unsigned y = fastdiv(rem, pg.d_w);
+      const unsigned x = rem - y * pg.w;
+      const unsigned d = xg.s;
+      const unsigned cols = (x >= d ? 1u : 0u) | 2u | (d < pg.w - x ? 4u : 0u);
+      dil_m[j] = (y >= d ? cols : 0u) | (cols << 3) | (d < pg.Hp - 2 - y ? cols << 6 : 0u) | ((x + 1) << 9);
+      gr = (long)n * (pg.Hp * pg.Wp) + (long)((y + 1) * pg.Wp + x + 1);
+      dil_c[j] = (unsigned)((gr - a_row0) * ca + unit * 4) * (unsigned)sizeof(float);
+    } else
     if (a_str) gr = strided_row(gr, pg, xg);
     else if (a_padded) gr = padded_row(gr, pg);
     a_voff[j] = (unsigned)((gr - a_row0) * ca + unit * 4) * (unsigned)sizeof(float);
@@ -422,6 +461,29 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   auto taps_soff = [&](int k) {
     return (unsigned)k * a_kstep + (k >= taps_k3 ? taps_row : 0u) + (k >= 2 * taps_k3 ? taps_row : 0u);
   };
+  // A_DIL: the pieces' offsets at tap 3 dy + dx -- the centre plus d ((dy-1)(W+2) + (dx-1)) pixels where the tap is
+  // inside the image, the row's left ring pixel (a zero of the contract) where it is not.  The tap and the k-step
+  // inside it (dil_tap, dil_kin) are wave-uniform and advance with the k-steps; a stream-K segment that starts mid-tap
+  // starts them at k0 / (C / BK) and the remainder, the same addresses.  Offsets wrap modulo 2^32 on their way to a
+  // value inside the window.
+  const int dil_kc = AF == A_DIL ? __builtin_amdgcn_readfirstlane(xg.cx / BK) : 1;
+  const unsigned dil_px = AF == A_DIL ? xg.s * (unsigned)xg.cx * (unsigned)sizeof(float) : 0u;
+  const int dil_wp = AF == A_DIL ? xg.cm : 0;
+  int dil_tap = 0, dil_kin = 0;
+  auto dil_set = [&](int tap) {
+    if constexpr (AF == A_DIL) {
+      const int dy = (tap * 11) >> 5, dx = tap - 3 * dy;
+      const unsigned toff = (unsigned)((dy - 1) * dil_wp + (dx - 1)) * dil_px;
+#pragma unroll
+      for (int j = 0; j < DIL_N; j++)
+        a_voff[j] = (dil_m[j] >> tap) & 1u ? dil_c[j] + toff : dil_c[j] - (dil_m[j] >> 9) * ((unsigned)dil_kc * a_kstep);
+    }
+  };
+  if constexpr (AF == A_DIL) {
+    dil_tap = __builtin_amdgcn_readfirstlane(k0 / dil_kc);
+    dil_kin = k0 - dil_tap * dil_kc;
+    dil_set(dil_tap);
+  }
   auto issue_piece = [&](int stage, unsigned a_soff, unsigned b_soff, int p) {  // p = 0 .. A_PER_WAVE + B_PER_WAVE - 1
     char* sb = smem + stage * G::STAGE;
     if (p < G::A_PER_WAVE) {
@@ -456,7 +518,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
 
 #pragma unroll
   for (int p = 0; p < PIECES; p++)
-    issue_piece(0, TAPS ? taps_soff(k0) : (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
+    issue_piece(0, TAPS ? taps_soff(k0) : AF == A_DIL ? (unsigned)dil_kin * a_kstep : (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
   __builtin_amdgcn_s_setprio(0);
 
   // `more` (is there a k-step after this one to fetch) is a compile-time property of the body: the
@@ -471,6 +533,15 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     unsigned a_soff;   // `it` counts from the segment's first k-step k0 (A_TWO: from ka inside its source)
     if constexpr (AF == A_TWO) a_soff = (unsigned)(ka + it + 1) * a_kstep;
     else if constexpr (TAPS) a_soff = taps_soff(k0 + it + 1);
+    else if constexpr (AF == A_DIL) {
+      if (more) {   // the next k-step's tap; all pieces of this stage were issued in the previous body
+        if (++dil_kin == dil_kc) {
+          dil_kin = 0;
+          dil_set(++dil_tap);
+        }
+      }
+      a_soff = (unsigned)dil_kin * a_kstep;
+    }
     else a_soff = (unsigned)(k0 + it + 1) * a_kstep;
     const unsigned b_soff = (unsigned)(k0 + it + 1) * b_kstep;
     const char* st = smem + PAR * G::STAGE;

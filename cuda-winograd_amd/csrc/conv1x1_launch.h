@@ -1,7 +1,7 @@
 // The 1x1 kernels' launch plan and launcher, shared by the translation units that launch them: conv1x1.hip (the plain
 // operand form, A_PLAIN), proj_block.hip (the projection block's A_STRIDED / A_TWO forms), conv3x3_s2.hip (the
-// stride-2 3x3's A_TAPS form), basic_block_s2.hip (A_TAPS_PROJ, the stride-2 3x3 with its 1x1 shortcut) and fpn.hip
-// (A_PLAIN with the upsampled residual); the forms:
+// stride-2 3x3's A_TAPS form), basic_block_s2.hip (A_TAPS_PROJ, the stride-2 3x3 with its 1x1 shortcut), fpn.hip
+// (A_PLAIN with the upsampled residual) and conv3x3_dilated.hip (A_DIL, tiled forms only: launch_tiled_1x1); the forms:
 // conv1x1_kernel.h.
 // A template is instantiated where it is used, so each file compiles the kernels of its own forms and no others.
 #pragma once

@@ -61,7 +61,9 @@ extern "C" {
  * wino_conv3x3_bn_relu_pool_hw, wino_image_pack_hw, wino_avgpool7_flatten_hw, wino_conv3x3_grouped_filter_elems,
  * wino_conv3x3_grouped_filter_pack, wino_conv3x3_grouped_bn_relu_hw, wino_grouped_residual_block_hw,
  * wino_grouped_residual_block_prepare_hw, wino_grouped_proj_block_hw, wino_grouped_proj_block_prepare_hw,
- * WINO_RESIDUAL_UP2, wino_fpn_level_hw, wino_fpn_level_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * WINO_RESIDUAL_UP2, wino_fpn_level_hw, wino_fpn_level_prepare_hw, wino_conv3x3_dilated_bn_relu_hw,
+ * wino_conv3x3_dilated_prepare_hw, wino_conv3x3_dilated_plan, wino_dilated_residual_block_hw,
+ * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -629,6 +631,41 @@ int wino_fpn_level_hw(const float* c, const float* wl, const float* lBias, const
                       float* inner, const float* U, const float* oBias, const float* oScale, float* P, int N, int H,
                       int W, int Cin, int Cf, int c_padded, wino_stream_t s);
 int wino_fpn_level_prepare_hw(int N, int H, int W, int Cin, int Cf, wino_stream_t s);
+
+/* ---- dilated 3x3 and the dilated bottleneck blocks (the segmentation backbones: torchvision's fcn_resnet* and
+ * deeplabv3_resnet* build layer3 / layer4 with replace_stride_with_dilation) ------------------------------------------
+ *   out = act(bnScale[k] * conv3x3(in, w, stride 1, padding d, dilation d) + bnBias[k])
+ *   in      [N][H+2][W+2][C] with a zero ring of width ONE -- the library's padded layout, what WINO_C_PADDED layers
+ *           write -- whatever the dilation: a tap outside the image is a zero, not a read d pixels out
+ *   w_taps  [3][3][C][K], the stride-2 layer's format (wino_conv3x3_s2_bn_relu_hw)
+ *   out     [N][H+2][W+2][K]: the result in the interior, the ring written 0
+ * C % 32 == 0, K % 64 == 0, dilation >= 1 (one that exceeds the map is legal: only the centre tap then sees data);
+ * N*H*W < 2^31, H, W <= 4094, one padded image < 2^31 pixels, and a row tile's window with the taps' reach of
+ * dilation * (W+2) + dilation pixels to either side, the filter matrix and the ring pass below 2^32 (WINO_E_SHAPE);
+ * in and out must not overlap (WINO_E_ARG).  The layer is the GEMM (N*H*W, 9C, K) on the tiled 1x1 kernel (operand
+ * form A_DIL), whole tiles or stream-K; it has no latency form.  wino_conv3x3_dilated_plan (host only) answers
+ * WINO_1X1_FORM_TILED or WINO_1X1_FORM_STREAM_K. */
+int wino_conv3x3_dilated_bn_relu_hw(const float* in, const float* w_taps, const float* bnBias, const float* bnScale,
+                                    float* out, int N, int H, int W, int C, int K, int dilation, int relu,
+                                    wino_stream_t s);
+int wino_conv3x3_dilated_prepare_hw(int N, int H, int W, int C, int K, int dilation, wino_stream_t s);
+int wino_conv3x3_dilated_plan(int N, int H, int W, int C, int K, int dilation, int cus, int* form);
+/* The bottleneck blocks with the dilated 3x3 in the middle, stride 1, input and output on one H x W grid:
+ *   wino_dilated_residual_block_hw   out = relu(bn3(conv1x1(relu(bn2(conv3x3_dil(relu(bn1(conv1x1(x, w1))), w2_taps))), w3)) + x)
+ *   wino_dilated_proj_block_hw       the same with the projection shortcut, in the fused tail (wino_proj_tail_pack, stride 1)
+ * x [N][H][W][C4 or Cin], out [N][H][W][C4]; w2_taps [3][3][Cm][Cm].  Their intermediates are the dense blocks':
+ * workspaces of wino_residual_block_workspace_bytes_hw(N, H, W, Cm) and wino_proj_block_workspace_bytes_hw(N, H, W, Cm)
+ * bytes.  Checks, their order and *_prepare_hw as for the other bottleneck blocks. */
+int wino_dilated_residual_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                                   const float* w2_taps, const float* bn2Bias, const float* bn2Scale, const float* w3,
+                                   const float* bn3Bias, const float* bn3Scale, float* out, int N, int H, int W, int C4,
+                                   int Cm, int dilation, void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_dilated_residual_block_prepare_hw(int N, int H, int W, int C4, int Cm, int dilation, wino_stream_t s);
+int wino_dilated_proj_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
+                               const float* w2_taps, const float* bn2Bias, const float* bn2Scale,
+                               const float* tail_packed, float* out, int N, int H, int W, int Cin, int Cm, int C4,
+                               int dilation, void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_dilated_proj_block_prepare_hw(int N, int H, int W, int Cin, int Cm, int C4, int dilation, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
