@@ -598,6 +598,113 @@ def dilated_proj_block(x, w1, bn1, w2_taps, bn2, tail, dilation: int, out=None, 
                        dilation=dilation)
 
 
+def _cat_sources(srcs):
+    """The concat layer's sources: one [S][N][h][w][Cs] tensor, or S tensors [N][h][w][Cs] of one shape at equally spaced,
+    ascending addresses of one allocation (views of a buffer: what lies between them is never read).  Returns (first,
+    spacing in floats, S, (N, h, w, Cs), the tensors kept alive)."""
+    if isinstance(srcs, torch.Tensor):
+        t = _dev(srcs, "srcs")
+        if t.dim() != 5:
+            raise WinoError("srcs must be [S][N][H][W][Cs] or a sequence of [N][H][W][Cs] tensors")
+        S = int(t.shape[0])
+        return t, t.numel() // max(S, 1), S, tuple(int(v) for v in t.shape[1:]), (t,)
+    views = [_out(v, None, "srcs[i]") for v in srcs]
+    if len(views) < 2 or any(v.dim() != 4 or v.shape != views[0].shape for v in views):
+        raise WinoError("srcs must be at least two [N][H][W][Cs] tensors of one shape")
+    step = views[1].data_ptr() - views[0].data_ptr()
+    if step <= 0 or step % 4 or any(b.data_ptr() - a.data_ptr() != step for a, b in zip(views, views[1:])):
+        raise WinoError("srcs must lie at equally spaced, ascending addresses")
+    return views[0], step // 4, len(views), tuple(int(v) for v in views[0].shape), tuple(views)
+
+
+def conv1x1_cat_bn(srcs, w: torch.Tensor, bias_per_image: torch.Tensor, bn_scale: torch.Tensor, flags: int = 0,
+                   out: torch.Tensor | None = None) -> torch.Tensor:
+    """The 1x1 layer behind a channel concatenation that is never made: out = act(bn_scale * (cat(srcs, channels) . w) +
+    bias_per_image[n]).  srcs: see _cat_sources ([N][H+2][W+2][Cs] each with A_PADDED); w [S*Cs][Kout]; bias_per_image
+    [N][Kout], one bias row per image; flags: RELU | A_PADDED | C_PADDED.  Returns [N][H][W][Kout], or the padded
+    [N][H+2][W+2][Kout] with a zero ring (C_PADDED).  One launch of the tiled 1x1 GEMM kernel in its concat operand form."""
+    first, stride, S, (N, h, wd, Cs), keep = _cat_sources(srcs)
+    p = 2 if flags & A_PADDED else 0
+    if h <= p or wd <= p:
+        raise WinoError("A_PADDED: the sources must be [N][H+2][W+2][Cs]")
+    H, W = h - p, wd - p
+    bm, b, sc = _dev(w, "w"), _dev(bias_per_image, "bias_per_image"), _dev(bn_scale, "bn_scale")
+    if bm.dim() != 2 or int(bm.shape[0]) != S * Cs:
+        raise WinoError(f"w must be [S*Cs][Kout] = [{S * Cs}][Kout]")
+    Kout = int(bm.shape[1])
+    if tuple(b.shape) != (N, Kout) or sc.numel() != Kout:
+        raise WinoError(f"bias_per_image must be [{N}][{Kout}], bn_scale [{Kout}]")
+    out = _output(out, (N, H + 2, W + 2, Kout) if flags & C_PADDED else (N, H, W, Kout), first.device)
+    _on_current_device(*keep, bm, b, sc, out)
+    _check(lib().wino_conv1x1_cat_bn_hw(first.data_ptr(), stride, bm.data_ptr(), b.data_ptr(), sc.data_ptr(),
+                                        out.data_ptr(), N, H, W, S, Cs, Kout, int(flags), _stream()),
+           "wino_conv1x1_cat_bn_hw")
+    return out
+
+
+def conv1x1_cat_prepare(N: int, H: int, W: int, sources: int, Cs: int, Kout: int) -> None:
+    """Allocate the concat layer's stream-K scratch for the current stream (before graph capture)."""
+    _prepare("wino_conv1x1_cat_prepare_hw", N, H, W, sources, Cs, Kout)
+
+
+def conv1x1_cat_plan(N: int, H: int, W: int, sources: int, Cs: int, Kout: int, cus: int = 256) -> int:
+    """The FORM_* the concat layer takes on a device with `cus` CUs (host-side): FORM_TILED or FORM_STREAM_K."""
+    return _plan_query("wino_conv1x1_cat_plan", 1, int(N), int(H), int(W), int(sources), int(Cs), int(Kout), int(cus))[0]
+
+
+def aspp_workspace_bytes(N: int, H: int, W: int, Cin: int, Cb: int, Kout: int) -> int:
+    """Bytes of aspp's workspace, the formula of winograd_mi355x.h (wino_aspp_hw refuses less): the pooled vector
+    [N][Cin], its branch [N][Cb] and the per-image bias [N][Kout], each rounded up to 256 bytes, and the four spatial
+    branches' unpadded [N][H][W][Cb] slots."""
+    N, H, W, Cin, Cb, Kout = int(N), int(H), int(W), int(Cin), int(Cb), int(Kout)
+    if min(N, H, W, Cin, Cb, Kout) < 1:
+        return 0
+    r256 = lambda b: (b + 255) // 256 * 256
+    return r256(4 * N * Cin) + r256(4 * N * Cb) + r256(4 * N * Kout) + 4 * (4 * N * H * W * Cb)
+
+
+def aspp_prepare(N: int, H: int, W: int, Cin: int, Cb: int, Kout: int, rates) -> None:
+    """Allocate the scratch of aspp's eight launches for the current stream (before graph capture)."""
+    d1, d2, d3 = (int(r) for r in rates)
+    _prepare("wino_aspp_prepare_hw", N, H, W, Cin, Cb, Kout, d1, d2, d3)
+
+
+def aspp(inp, w0, bn0, w_taps, bn_taps, rates, w_pool, bn_pool, w_proj, bn_proj, out=None, workspace=None) -> torch.Tensor:
+    """Atrous spatial pyramid pooling (torchvision's DeepLabV3 ASPP, dropout aside): inp [N][H+2][W+2][Cin] with a zero
+    ring -> relu(bn(cat(five branches) . w_proj)) as the padded [N][H+2][W+2][Kout].  w0, w_pool [Cin][Cb]; w_taps: three
+    [3][3][Cin][Cb] from filter_pack_s2 with their `rates`; w_proj [5*Cb][Kout], the pooled branch's rows last; bnX =
+    (bias, scale), bn_taps three such pairs.  The concatenated tensor and the broadcast pooled branch never exist: see
+    conv1x1_cat_bn."""
+    x = _dev(inp, "inp")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("inp must be [N][H+2][W+2][Cin]")
+    N, H, W, Cin = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    w0, w_pool, w_proj = _dev(w0, "w0"), _dev(w_pool, "w_pool"), _dev(w_proj, "w_proj")
+    if w0.dim() != 2 or int(w0.shape[0]) != Cin or w_pool.shape != w0.shape:
+        raise WinoError("w0 and w_pool must be [Cin][Cb]")
+    Cb = int(w0.shape[1])
+    taps = [_dev(t, "w_taps[i]") for t in w_taps]
+    if len(taps) != 3 or len(bn_taps) != 3 or len(rates) != 3:
+        raise WinoError("aspp takes three dilated branches: three w_taps, bn_taps and rates")
+    if any(tuple(t.shape) != (3, 3, Cin, Cb) for t in taps):
+        raise WinoError(f"every w_taps must be [3][3][{Cin}][{Cb}]: pack it with filter_pack_s2")
+    if w_proj.dim() != 2 or int(w_proj.shape[0]) != 5 * Cb:
+        raise WinoError(f"w_proj must be [5*Cb][Kout] = [{5 * Cb}][Kout]")
+    Kout = int(w_proj.shape[1])
+    vecs = _bn_vecs(bn0, *bn_taps, bn_pool, bn_proj)
+    if any(v.numel() != c for v, c in zip(vecs, [Cb] * 10 + [Kout] * 2)):
+        raise WinoError("the branches' bn vectors must have Cb values, bn_proj's Kout")
+    workspace = _workspace(workspace, aspp_workspace_bytes(N, H, W, Cin, Cb, Kout), x.device)
+    out = _output(out, (N, H + 2, W + 2, Kout), x.device)
+    _on_current_device(x, w0, w_pool, w_proj, out, workspace, *taps, *vecs)
+    v = [t.data_ptr() for t in vecs]
+    _check(lib().wino_aspp_hw(x.data_ptr(), w0.data_ptr(), v[0], v[1], taps[0].data_ptr(), v[2], v[3], taps[1].data_ptr(),
+                              v[4], v[5], taps[2].data_ptr(), v[6], v[7], w_pool.data_ptr(), v[8], v[9],
+                              w_proj.data_ptr(), v[10], v[11], out.data_ptr(), N, H, W, Cin, Cb, Kout,
+                              *(int(r) for r in rates), *_ws_args(workspace), _stream()), "wino_aspp_hw")
+    return out
+
+
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
     """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
     bounds by the kernel)."""
@@ -1021,4 +1128,4 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
 from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)
 from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
-from .segmentation import FCN  # noqa: E402
+from .segmentation import FCN, DeepLabV3  # noqa: E402

@@ -161,6 +161,12 @@ SIGNATURES = {
     "wino_dilated_residual_block_prepare_hw": (i, [i] * 6 + [vp]),
     "wino_dilated_proj_block_hw": (i, [vp] * 9 + [i] * 7 + [vp, sz, vp]),
     "wino_dilated_proj_block_prepare_hw": (i, [i] * 7 + [vp]),
+    # ---- the concat projection and the ASPP module
+    "wino_conv1x1_cat_bn_hw": (i, [vp, c_long] + [vp] * 4 + [i] * 7 + [vp]),
+    "wino_conv1x1_cat_prepare_hw": (i, [i] * 6 + [vp]),
+    "wino_conv1x1_cat_plan": (i, [i] * 7 + [ip]),
+    "wino_aspp_hw": (i, [vp] * 20 + [i] * 9 + [vp, sz, vp]),
+    "wino_aspp_prepare_hw": (i, [i] * 9 + [vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -107,11 +107,20 @@ __device__ __forceinline__ long padded_row(long m, const PadGeo& g) {
 //              every C / BK k-steps; inside a tap the k-step advance is the usual scalar.  The descriptor window is
 //              the tile's centre pixels plus the taps' reach d (W+2) + d to either side, clipped to the tensor: no
 //              valid tap and no ring pixel lies outside it, and nothing outside `in` is ever addressed.  B as A_TAPS.
-enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3, A_TAPS_PROJ = 4, A_DIL = 5 };
+//   A_CAT      the projection behind a channel concatenation that never exists (aspp.hip), tiled forms only: K runs through
+//              S = xg.s sources of Cs = xg.cx channels in turn, each a [N][H][W][Cs] tensor (WINO_A_PADDED: [N][H+2][W+2][Cs],
+//              its ring never read), source j at A + j * batchA floats (batchA: the plain form's batch stride, free here;
+//              it may exceed a source's size, and the gap is never read).  B is the plain [S Cs][Kout] matrix, Cin = S Cs.
+//              Cs % 32 == 0: no k-step crosses a source.  One descriptor per tile: the plain form's window over source 0
+//              grown by (S-1) batchA floats (host-checked < 4 GiB), and the source's offset j * batchA rides in the scalar
+//              k-step offset -- no segment stops at a source boundary, stream-K ranges start, end and cross anywhere.
+//              The epilogue's bias is per IMAGE: bnBias is [N][Kout] and output row m adds row m / (H W) of it (the share
+//              of a branch that is constant over an image, folded by the caller); a tile may span several images.
+enum { A_PLAIN = 0, A_STRIDED = 1, A_TWO = 2, A_TAPS = 3, A_TAPS_PROJ = 4, A_DIL = 5, A_CAT = 6 };
 struct ProjGeo {
   const float* X;         // A_TWO: the block input x
-  unsigned img, row, s;   // x's pixels per image (Hin*Win), pixels per strided row step (s*Win), the stride
-  int cx, cm;             // A_TWO: channels of x, of the first source (the phase boundary is k = cm); A_TAPS: C, Win+2
+  unsigned img, row, s;   // x's pixels per image (Hin*Win), pixels per strided row step (s*Win), the stride; A_CAT: s = sources
+  int cx, cm;             // A_TWO: channels of x, of the first source (the phase boundary is k = cm); A_TAPS: C, Win+2; A_CAT: cx = Cs
 };
 // A_TAPS: the element offset of GEMM column k (any k inside the tap row dy = k / 3C) from its row's window start.
 // k = (3 dy + dx) C + c lies at (dy (Win+2) + dx) C + c = k + dy (Win+2-3) C: a scalar select and multiply-add.
@@ -216,7 +225,8 @@ __device__ unsigned long long wino_clk_slot_1x1[4];
 // A_TAPS_PROJ (basic_block_s2.hip) is A_TAPS with the shortcut's whole tiles appended to the grid: batchA, unused by
 // the tap forms, is the 3x3's own grid -- the stream-K ranges and the ring pass are cut over that, never over the
 // appended tiles.  The dilated 3x3 layer (conv3x3_dilated.hip) runs A_DIL: A = the padded input, Cin = 9 C, per-lane
-// tap offsets rebuilt at every tap change.
+// tap offsets rebuilt at every tap change.  The concat projection (aspp.hip) runs A_CAT: A = the first source, batchA the
+// sources' spacing, Cin = S Cs, bnBias per image.
 // xg is last, so that the plain form's other arguments keep their offsets.
 template <int BK, int NW, int ABLATE = 0, bool SK = false, int RES = RES_NONE, int AF = A_PLAIN>
 __global__ void __launch_bounds__(64 * NW, NW == 8 ? 4 : 3)
@@ -392,7 +402,7 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
   //      the tap (dil_set below), the k offset inside a tap is (k-step inside the tap) * BK * 4 bytes.
   const bool a_str = AF == A_STRIDED || TAPS || (AF == A_TWO && k0 >= kb);
   const float* const Aseg = AF == A_TWO && a_str ? xg.X : A;
-  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : (TAPS || AF == A_DIL) ? xg.cx : Cin;   // A row length of this segment
+  const int ca = AF == A_TWO ? (a_str ? xg.cx : xg.cm) : (TAPS || AF == A_DIL || AF == A_CAT) ? xg.cx : Cin;   // A row length of this segment
   const int ka = AF == A_TWO && a_str ? k0 - kb : k0;        // its first k-step inside that source
   long a_row0 = a_str ? strided_row(m0 < M ? m0 : M - 1, pg, xg)
                       : (a_padded || AF == A_DIL) ? padded_row(m0 < M ? m0 : M - 1, pg) : (m0 < M ? m0 : M - 1);
@@ -407,7 +417,10 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     a_row0 = a_row0 > (long)reach ? a_row0 - reach : 0;
     a_rows = end - a_row0;
   }
-  const auto rsrc_a = make_rsrc(Aseg + a_row0 * ca, (unsigned)(a_rows * ca * (long)sizeof(float)));
+  //   A_CAT: the plain (or padded) window over source 0 plus the way to the last source, (S-1) batchA floats; source
+  //      j's k-steps add j * batchA * 4 bytes to the scalar offset (cat_soff below).
+  const unsigned cat_stride = AF == A_CAT ? (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)batchA * (unsigned)sizeof(float))) : 0u;
+  const auto rsrc_a = make_rsrc(Aseg + a_row0 * ca, (unsigned)(a_rows * ca * (long)sizeof(float)) + (AF == A_CAT ? (xg.s - 1u) * cat_stride : 0u));
   const auto rsrc_b = make_rsrc(B, (unsigned)((size_t)Cin * Kout * sizeof(float)));
   unsigned a_voff[G::A_PER_WAVE];
   int a_q[G::A_PER_WAVE];
@@ -484,6 +497,18 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     dil_kin = k0 - dil_tap * dil_kc;
     dil_set(dil_tap);
   }
+  // A_CAT: the scalar A offset of the current k-step -- (its source) * spacing + (k-step inside the source) * BK * 4 -- kept
+  // as a running value: a k-step adds a_kstep, the last one of a source also the gap from that source's row end to the
+  // next source.  A stream-K segment that starts inside any source starts it at the same value.
+  const int cat_kc = AF == A_CAT ? __builtin_amdgcn_readfirstlane(xg.cx / BK) : 1;
+  const unsigned cat_gap = AF == A_CAT ? cat_stride - (unsigned)cat_kc * a_kstep : 0u;
+  int cat_kin = 0;
+  unsigned cat_soff = 0;
+  if constexpr (AF == A_CAT) {
+    const int src = __builtin_amdgcn_readfirstlane(k0 / cat_kc);
+    cat_kin = k0 - src * cat_kc;
+    cat_soff = (unsigned)src * cat_stride + (unsigned)cat_kin * a_kstep;
+  }
   auto issue_piece = [&](int stage, unsigned a_soff, unsigned b_soff, int p) {  // p = 0 .. A_PER_WAVE + B_PER_WAVE - 1
     char* sb = smem + stage * G::STAGE;
     if (p < G::A_PER_WAVE) {
@@ -518,7 +543,8 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
 
 #pragma unroll
   for (int p = 0; p < PIECES; p++)
-    issue_piece(0, TAPS ? taps_soff(k0) : AF == A_DIL ? (unsigned)dil_kin * a_kstep : (unsigned)ka * a_kstep, (unsigned)k0 * b_kstep, p);
+    issue_piece(0, TAPS ? taps_soff(k0) : AF == A_DIL ? (unsigned)dil_kin * a_kstep : AF == A_CAT ? cat_soff : (unsigned)ka * a_kstep,
+                (unsigned)k0 * b_kstep, p);
   __builtin_amdgcn_s_setprio(0);
 
   // `more` (is there a k-step after this one to fetch) is a compile-time property of the body: the
@@ -541,6 +567,16 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
         }
       }
       a_soff = (unsigned)dil_kin * a_kstep;
+    }
+    else if constexpr (AF == A_CAT) {
+      if (more) {   // the next k-step's offset; all pieces of this stage were issued in the previous body
+        cat_soff += a_kstep;
+        if (++cat_kin == cat_kc) {
+          cat_kin = 0;
+          cat_soff += cat_gap;
+        }
+      }
+      a_soff = cat_soff;
     }
     else a_soff = (unsigned)(k0 + it + 1) * a_kstep;
     const unsigned b_soff = (unsigned)(k0 + it + 1) * b_kstep;
@@ -717,12 +753,19 @@ conv1x1_bn_kernel(const float* __restrict__ A, const float* __restrict__ B,
     f32x4 sc = {1.f, 1.f, 1.f, 1.f}, bi = {0.f, 0.f, 0.f, 0.f};
     if (!raw) {
 #pragma unroll
-      for (int j = 0; j < 4; j++) { sc[j] = bnScale[ch + j]; bi[j] = bnBias[ch + j]; }
+      for (int j = 0; j < 4; j++) {
+        sc[j] = bnScale[ch + j];
+        if constexpr (AF != A_CAT) bi[j] = bnBias[ch + j];
+      }
     }
     auto store_rows = [&](auto stream_c) {
 #pragma unroll
       for (int rb = 0; rb < RB; rb++) {
         const long grow = m0 + rb * 16 + r16;
+        // A_CAT: the bias row of this output row's image (rows past M, never stored, read the last image's); a tile spans
+        // several images whenever H W < 112, so it is one 16-byte load per row block and lane, not one per tile
+        if constexpr (AF == A_CAT)
+          bi = *(const f32x4*)(bnBias + (size_t)fastdiv((unsigned)(grow < M ? grow : M - 1), pg.d_hw) * Kout + ch);
         f32x4 val = sc * acc[rb] + bi;
         if (relu) {
 #pragma unroll

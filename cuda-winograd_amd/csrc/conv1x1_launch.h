@@ -1,8 +1,8 @@
 // The 1x1 kernels' launch plan and launcher, shared by the translation units that launch them: conv1x1.hip (the plain
 // operand form, A_PLAIN), proj_block.hip (the projection block's A_STRIDED / A_TWO forms), conv3x3_s2.hip (the
 // stride-2 3x3's A_TAPS form), basic_block_s2.hip (A_TAPS_PROJ, the stride-2 3x3 with its 1x1 shortcut), fpn.hip
-// (A_PLAIN with the upsampled residual) and conv3x3_dilated.hip (A_DIL, tiled forms only: launch_tiled_1x1); the forms:
-// conv1x1_kernel.h.
+// (A_PLAIN with the upsampled residual), conv3x3_dilated.hip (A_DIL, tiled forms only: launch_tiled_1x1) and aspp.hip
+// (A_CAT, tiled forms only); the forms: conv1x1_kernel.h.
 // A template is instantiated where it is used, so each file compiles the kernels of its own forms and no others.
 #pragma once
 #include "conv1x1_kernel.h"
@@ -32,6 +32,7 @@ int tiled_scratch(int dev, hipStream_t s, const Plan1x1& p, SkBufs* bufs);
 
 // One launch's operands.  R: the residual (A_PLAIN, WINO_ADD_RESIDUAL) or the shortcut's output (A_TAPS_PROJ); xg: the strided / second source (A_STRIDED,
 // A_TWO) or the padded input's tap geometry (A_TAPS); batch and the per-batch strides: the batched plain GEMM (gemm_batched; its plans have no stream-K form).
+// A_CAT: batchA is the spacing of the sources in floats (batch stays 1), bnBias the per-image bias [N][Kout].
 struct Operands1x1 {
   const float *A, *B, *bnBias, *bnScale, *R;
   float* C;

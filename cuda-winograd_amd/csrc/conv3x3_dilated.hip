@@ -54,6 +54,18 @@ Plan1x1 plan_dilated(const DilGeom& g, int cus, const Knobs& kn) {
 }
 
 }  // namespace
+
+int launch_dilated(const DilGeom& g, const float* in, const float* w_taps, const float* bnBias, const float* bnScale,
+                   float* out, bool relu, bool out_padded, hipStream_t s) {
+  int dev = 0, cus = 0;
+  if (int rc = current_device(&dev, &cus)) return rc;
+  const ProjGeo xg{nullptr, 0u, 0u, (unsigned)g.d, g.C, g.W + 2};
+  const int flags = (relu ? WINO_RELU : 0) | WINO_A_PADDED | (out_padded ? WINO_C_PADDED : 0);
+  const Plan1x1 p = plan_dilated(g, cus, knobs());
+  const Operands1x1 o{in, w_taps, bnBias, bnScale, nullptr, out, g.M, 9 * g.C, g.K, flags, make_padgeo(g.H, g.W), xg};
+  return (p.four ? launch_tiled_1x1<4, A_DIL, RES_NONE> : launch_tiled_1x1<8, A_DIL, RES_NONE>)(p, dev, o, s);
+}
+
 }  // namespace wino
 
 using namespace wino;
@@ -71,13 +83,7 @@ int wino_conv3x3_dilated_bn_relu_hw(const float* in, const float* w_taps, const 
     set_error("dilated 3x3: in and out overlap");
     return WINO_E_ARG;
   }
-  int dev = 0, cus = 0;
-  if (int rc = current_device(&dev, &cus)) return rc;
-  const ProjGeo xg{nullptr, 0u, 0u, (unsigned)dilation, C, W + 2};
-  const int flags = (relu ? WINO_RELU : 0) | WINO_A_PADDED | WINO_C_PADDED;
-  const Plan1x1 p = plan_dilated(g, cus, knobs());
-  const Operands1x1 o{in, w_taps, bnBias, bnScale, nullptr, out, g.M, 9 * C, K, flags, make_padgeo(H, W), xg};
-  return (p.four ? launch_tiled_1x1<4, A_DIL, RES_NONE> : launch_tiled_1x1<8, A_DIL, RES_NONE>)(p, dev, o, (hipStream_t)s);
+  return launch_dilated(g, in, w_taps, bnBias, bnScale, out, relu != 0, true, (hipStream_t)s);
 }
 
 int wino_conv3x3_dilated_prepare_hw(int N, int H, int W, int C, int K, int dilation, wino_stream_t s) {

@@ -311,6 +311,13 @@ int check_head(int N, int H, int W, int C, int classes, int padded) {
 }
 
 }  // namespace
+
+int launch_avgpool(const float* feat, float* pooled, int N, int H, int W, int C, int pad, hipStream_t s) {
+  hipLaunchKernelGGL(avgpool_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(N < 65535 ? N : 65535)), dim3(256), 0,
+                     s, feat, pooled, N, H, W, C, pad);
+  return launch_status("avgpool_kernel");
+}
+
 }  // namespace wino
 
 using namespace wino;
@@ -405,9 +412,7 @@ int wino_avgpool_fc_hw(const float* feat, const float* packed, float* out, int N
   float* pooled = (float*)workspace;
   float* logits = Kp == classes ? out : (float*)((char*)workspace + pooled_bytes(N, C));
   const hipStream_t st = (hipStream_t)s;
-  hipLaunchKernelGGL(avgpool_kernel, dim3((unsigned)((C + 255) / 256), (unsigned)(N < 65535 ? N : 65535)), dim3(256), 0,
-                     st, feat, pooled, N, H, W, C, in_padded);
-  if (int rc = launch_status("avgpool_kernel")) return rc;
+  if (int rc = launch_avgpool(feat, pooled, N, H, W, C, in_padded, st)) return rc;
   const float* bias = packed + (size_t)C * Kp;
   if (int rc = wino_conv1x1_bn(pooled, packed, bias, bias + Kp, logits, N, C, Kp, 0, s)) return rc;
   if (logits == out) return WINO_OK;

@@ -130,6 +130,10 @@ int last_clock_1x1(unsigned long long* stamps);
 int gemm_batched(const float* A, const float* B, float* C, long M, int Cin, int Kout, int batch,
                  long batchA, long batchB, long batchC, hipStream_t s);
 
+// Defined in stem_head.hip: the head's average pool as a launch of its own, pooled[n][c] = mean over the H x W interior
+// of feat [N][H+2 pad][W+2 pad][C] (the ASPP module's pooled branch starts with it).  No checks: the caller's.
+int launch_avgpool(const float* feat, float* pooled, int N, int H, int W, int C, int pad, hipStream_t s);
+
 // 16-byte global -> LDS DMA (global_load_lds_dwordx4): each lane fetches 16 B from its
 // own `src`; the wave's 64 pieces land at `lds_wave_base + lane*16` (wave-uniform base).
 __device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {

@@ -63,7 +63,9 @@ extern "C" {
  * wino_grouped_residual_block_prepare_hw, wino_grouped_proj_block_hw, wino_grouped_proj_block_prepare_hw,
  * WINO_RESIDUAL_UP2, wino_fpn_level_hw, wino_fpn_level_prepare_hw, wino_conv3x3_dilated_bn_relu_hw,
  * wino_conv3x3_dilated_prepare_hw, wino_conv3x3_dilated_plan, wino_dilated_residual_block_hw,
- * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
+ * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
+ * wino_aspp_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -666,6 +668,52 @@ int wino_dilated_proj_block_hw(const float* x, const float* w1, const float* bn1
                                const float* tail_packed, float* out, int N, int H, int W, int Cin, int Cm, int C4,
                                int dilation, void* workspace, size_t workspace_bytes, wino_stream_t s);
 int wino_dilated_proj_block_prepare_hw(int N, int H, int W, int Cin, int Cm, int C4, int dilation, wino_stream_t s);
+
+/* ---- the concat projection and the ASPP module (torchvision's deeplabv3_resnet* head) --------------------------------
+ * The 1x1 layer behind a channel concatenation that is never made:
+ *   out[m][k] = act(bnScale[k] * sum_{j < sources} sum_{c < Cs} src_j[row(m)][c] * w[j*Cs + c][k] + bias_per_image[n(m)][k])
+ *   src             source j is the [N][H][W][Cs] tensor at src + j * src_stride floats ([N][H+2][W+2][Cs] with
+ *                   WINO_A_PADDED; its ring is never read).  src_stride % 4 == 0 and at least a source's size; what lies
+ *                   between two sources is never read
+ *   w               [sources * Cs][Kout], the matrix the concatenated tensor would meet
+ *   bias_per_image  [N][Kout], 16-byte aligned: output row m adds the row of its image n(m) = m / (H*W) -- the place of
+ *                   a branch that is constant over an image (ASPP's pooled one), folded by the caller
+ *   out             [N*H*W][Kout], or [N][H+2][W+2][Kout] with its ring written 0 (WINO_C_PADDED)
+ * flags: a subset of WINO_RELU | WINO_A_PADDED | WINO_C_PADDED (anything else: WINO_E_ARG).  2 <= sources <= 8,
+ * Cs % 32 == 0, Kout % 64 == 0 and the limits of wino_conv1x1_bn_ex_hw at Cin = sources * Cs (H, W <= 4094 with or
+ * without padded operands).  One buffer descriptor per 112-row tile spans all sources:
+ *   (rows * Cs + (sources - 1) * src_stride) * 4 bytes < 2^32, rows = 112, or 111 * (2 (W+2) + 3) + 1 with WINO_A_PADDED
+ * (WINO_E_SHAPE otherwise, like every other shape refusal here).  The sources, bias_per_image and out must not overlap
+ * (WINO_E_ARG).  One launch of the tiled 1x1 kernel (operand form A_CAT), whole tiles or stream-K; there is no latency
+ * form.  wino_conv1x1_cat_plan (host only) answers WINO_1X1_FORM_TILED or WINO_1X1_FORM_STREAM_K: the plan of the GEMM
+ * (N*H*W, sources * Cs, Kout), as wino_conv1x1_plan reports it. */
+int wino_conv1x1_cat_bn_hw(const float* src, long src_stride, const float* w, const float* bias_per_image,
+                           const float* bnScale, float* out, int N, int H, int W, int sources, int Cs, int Kout,
+                           int flags, wino_stream_t s);
+int wino_conv1x1_cat_prepare_hw(int N, int H, int W, int sources, int Cs, int Kout, wino_stream_t s);
+int wino_conv1x1_cat_plan(int N, int H, int W, int sources, int Cs, int Kout, int cus, int* form);
+/* Atrous spatial pyramid pooling:
+ *   out = relu(bn(conv1x1(cat(b0, b1, b2, b3, broadcast(bp)), w_proj)))
+ *   b0 = relu(bn0(conv1x1(in, w0)));  b_i = relu(bn_i(conv3x3(in, w_i, dilation d_i)));  bp = relu(bnp(conv1x1(mean_hw(in), w_pool)))
+ *   in       [N][H+2][W+2][Cin], zero ring;  out [N][H+2][W+2][Kout], ring written 0
+ *   w0, w_pool  [Cin][Cb];  w1_taps .. w3_taps  [3][3][Cin][Cb] (the stride-2 layer's format)
+ *   w_proj   [5 * Cb][Kout]: the rows of b0 .. b3, then the pooled branch's Cb rows
+ * Eight launches on `s`: the average pool, two 1x1 layers of N rows that fold the pooled branch into a per-image bias
+ * bnScale * (bp . w_proj[4 Cb ..]) + bnBias, the four spatial branches into unpadded slots of the workspace, and
+ * wino_conv1x1_cat_bn_hw over the slots with that bias.  Cin % 32 == 0, Cb % 64 == 0, Kout % 64 == 0, every d_i >= 1,
+ * H*W < 2^24, and each layer's own limits, all checked before the first launch (WINO_E_SHAPE).  The workspace, 16-byte
+ * aligned, holds at least
+ *   r256(4 N Cin) + r256(4 N Cb) + r256(4 N Kout) + 4 * (4 N H W Cb)   bytes (r256: rounded up to a multiple of 256)
+ * -- the pooled vector, its branch, the per-image bias and the four slots; the Python wrapper's aspp_workspace_bytes
+ * is this formula.  A smaller one, or an overlap among in, out and the workspace, is WINO_E_ARG.  wino_aspp_prepare_hw reserves the stream
+ * scratch of every launch (before a graph capture). */
+int wino_aspp_hw(const float* in, const float* w0, const float* bn0Bias, const float* bn0Scale, const float* w1_taps,
+                 const float* bn1Bias, const float* bn1Scale, const float* w2_taps, const float* bn2Bias,
+                 const float* bn2Scale, const float* w3_taps, const float* bn3Bias, const float* bn3Scale,
+                 const float* w_pool, const float* bnpBias, const float* bnpScale, const float* w_proj,
+                 const float* bnBias, const float* bnScale, float* out, int N, int H, int W, int Cin, int Cb, int Kout,
+                 int d1, int d2, int d3, void* workspace, size_t workspace_bytes, wino_stream_t s);
+int wino_aspp_prepare_hw(int N, int H, int W, int Cin, int Cb, int Kout, int d1, int d2, int d3, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
