@@ -705,6 +705,52 @@ def aspp(inp, w0, bn0, w_taps, bn_taps, rates, w_pool, bn_pool, w_proj, bn_proj,
     return out
 
 
+RESIZE_FORM_STAGED, RESIZE_FORM_DIRECT = 1, 2   # WINO_RESIZE_FORM_*
+
+
+def resize_bilinear_plan(h: int, w: int, C: int, ld: int, Ho: int, Wo: int, want_out: bool = True,
+                         want_labels: bool = False) -> int:
+    """The RESIZE_FORM_* resize_bilinear takes for this shape (host-side, a function of the shape alone)."""
+    return _plan_query("wino_resize_bilinear_plan", 1, int(h), int(w), int(C), int(ld), int(Ho), int(Wo),
+                       int(bool(want_out)), int(bool(want_labels)))[0]
+
+
+def resize_bilinear(src, Ho: int, Wo: int, C=None, in_padded: bool = False, out=None, labels=None,
+                    want_out: bool = True, want_labels: bool = False):
+    """torch's F.interpolate(mode="bilinear", align_corners=False) of class scores, and / or their argmax over the
+    classes, in one HIP launch with exact integer source coordinates.  src [N][h][w][ld] or, in_padded, [N][h+2][w+2][ld]
+    (the ring is not read); the first C of the ld columns are the classes (default: all).  Returns (out, labels): out
+    [N][C][Ho][Wo] float32 (NCHW) or None, labels [N][Ho][Wo] int32 or None.  A given `out` / `labels` tensor is written
+    and implies want_out / want_labels."""
+    x = _dev(src, "src")
+    if x.dim() != 4:
+        raise WinoError("src must be [N][h][w][ld]")
+    p = 2 if in_padded else 0
+    N, h, w, ld = int(x.shape[0]), int(x.shape[1]) - p, int(x.shape[2]) - p, int(x.shape[3])
+    if h < 1 or w < 1:
+        raise WinoError("src has no interior")
+    C = ld if C is None else int(C)
+    Ho, Wo = int(Ho), int(Wo)
+    want_out, want_labels = bool(want_out) or out is not None, bool(want_labels) or labels is not None
+    if not want_out and not want_labels:
+        raise WinoError("resize_bilinear: neither out nor labels is wanted")
+    if min(N, Ho, Wo, C) < 1:
+        raise WinoError(f"resize_bilinear: bad shape N={N} C={C} Ho={Ho} Wo={Wo}")
+    if want_out:
+        out = _output(out, (N, C, Ho, Wo), x.device)
+    if want_labels:
+        if labels is None:
+            labels = torch.empty((N, Ho, Wo), dtype=torch.int32, device=x.device)
+        elif (not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dtype != torch.int32
+              or not labels.is_contiguous() or tuple(labels.shape) != (N, Ho, Wo)):
+            raise WinoError(f"labels must be a contiguous int32 CUDA(HIP) tensor of shape {(N, Ho, Wo)}")
+    _on_current_device(x, out, labels)
+    _check(lib().wino_resize_bilinear_hw(x.data_ptr(), out.data_ptr() if want_out else None,
+                                         labels.data_ptr() if want_labels else None, N, h, w, C, ld,
+                                         int(bool(in_padded)), Ho, Wo, _stream()), "wino_resize_bilinear_hw")
+    return (out if want_out else None), (labels if want_labels else None)
+
+
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
     """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
     bounds by the kernel)."""

@@ -167,6 +167,9 @@ SIGNATURES = {
     "wino_conv1x1_cat_plan": (i, [i] * 7 + [ip]),
     "wino_aspp_hw": (i, [vp] * 20 + [i] * 9 + [vp, sz, vp]),
     "wino_aspp_prepare_hw": (i, [i] * 9 + [vp]),
+    # ---- bilinear resize and label map
+    "wino_resize_bilinear_hw": (i, [vp] * 3 + [i] * 8 + [vp]),
+    "wino_resize_bilinear_plan": (i, [i] * 8 + [ip]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -715,6 +715,32 @@ int wino_aspp_hw(const float* in, const float* w0, const float* bn0Bias, const f
                  int d1, int d2, int d3, void* workspace, size_t workspace_bytes, wino_stream_t s);
 int wino_aspp_prepare_hw(int N, int H, int W, int Cin, int Cb, int Kout, int d1, int d2, int d3, wino_stream_t s);
 
+/* ---- bilinear resize and label map: the output stage of a segmentation network -----------------
+ * torch's F.interpolate(mode="bilinear", align_corners=False) of the class scores, and / or the argmax over the classes
+ * of the resized scores, in one launch:
+ *   src     [N][h][w][ld], or with in_padded = 1 the padded [N][h+2][w+2][ld] (the ring is never read); the first C of
+ *           the ld columns are the classes
+ *   out     [N][C][Ho][Wo] fp32, NCHW (torch's layout), or NULL
+ *   labels  [N][Ho][Wo] int32: the index of the largest of the C resized values of a pixel; a tie goes to the lowest
+ *           index, a NaN counts as larger than every number and the first NaN wins (torch.argmax); or NULL
+ * Source coordinates are exact integers: per axis, num = max((2 d + 1) in - out, 0), i0 = num / (2 out), i1 =
+ * min(i0 + 1, in - 1), lambda = float(num - i0 * 2 out) / float(2 out); value = (1-ly)((1-lx) a + lx b) + ly((1-lx) c +
+ * lx d) in fp32, all four taps always multiplied (a NaN or Inf under a zero weight still reaches the output, also when
+ * Ho == h and Wo == w, where torch copies instead).  With both outputs the labels are taken from the stored values.
+ * No workspace and no stream scratch: the call can be captured into a graph as it is.
+ * N, h, w, Ho, Wo >= 1, 1 <= C <= ld, ld % 4 == 0, in_padded 0 or 1, one image of src, out and labels below 2^31
+ * elements, 2 Ho h and 2 Wo w below 2^31 (WINO_E_SHAPE otherwise); src NULL, out and labels both NULL, a pointer that
+ * is not 16-byte aligned, or any overlap among src, out and labels is WINO_E_ARG.  Any N.
+ * wino_resize_bilinear_plan (host only) answers the form the launch takes, a function of the shape alone: STAGED (a
+ * workgroup stages the source rows of a block of output rows x an x-segment in LDS and writes class planes with 16-byte
+ * stores) or DIRECT (every lane gathers its taps from global memory: when no block of one output row x 64 pixels fits
+ * in 64 KB of LDS, or an axis shrinks by more than 4x). */
+#define WINO_RESIZE_FORM_STAGED 1
+#define WINO_RESIZE_FORM_DIRECT 2
+int wino_resize_bilinear_hw(const float* src, float* out, int* labels, int N, int h, int w, int C, int ld,
+                            int in_padded, int Ho, int Wo, wino_stream_t s);
+int wino_resize_bilinear_plan(int h, int w, int C, int ld, int Ho, int Wo, int want_out, int want_labels, int* form);
+
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
 int wino_debug_reload_knobs(void);
