@@ -1,4 +1,5 @@
-"""Seeded random-shape generators for the ResNet entry points, shared by tests/test_shape_sweeps_host.py (every case is
+"""Seeded random-shape generators for the ResNet entry points and the segmentation path (the dilated 3x3 layer and its
+bottleneck blocks, the concat projection, ASPP, the bilinear resize), shared by tests/test_shape_sweeps_host.py (every case is
 legal and the draws reach the corners they claim, no GPU) and tests/test_gpu_shape_sweeps.py (every case against an
 fp64 reference on an MI355X).
 
@@ -15,8 +16,11 @@ import numpy as np
 
 # the latency forms the plan queries accept are those of the existing forced-form tests (one table per family)
 from cases import PROJ_FORMS, S2_FORMS, s2_legal
+from dilated_cases import FORMS as DIL_FORMS
+from resize_cases import DIRECT, STAGED, smallest_direct_channels
 
 MAX_MACS = 2e9
+MAX_SUM_MACS = 1e10   # the segmentation entries: all of a generator's references together
 CUS = 256
 
 
@@ -74,6 +78,18 @@ def macs(case: Case) -> float:
         return 147.0 * s["N"] * _s2(s["H"]) * _s2(s["W"]) * s["K"]
     if e == "avgpool_fc":
         return float(s["N"]) * s["C"] * (s["H"] * s["W"] + s["classes"])
+    if e == "conv3x3_dilated_bn_relu":
+        return 9.0 * s["N"] * s["H"] * s["W"] * s["C"] * s["K"]
+    if e == "dilated_block":
+        px = float(s["N"]) * s["H"] * s["W"]
+        return px * (s["Cin"] * s["Cm"] + 9.0 * s["Cm"] * s["Cm"] + (s["Cm"] + (s["Cin"] if s["proj"] else 0)) * s["C4"])
+    if e == "conv1x1_cat_bn":
+        return float(s["N"]) * s["H"] * s["W"] * s["S"] * s["Cs"] * s["Kout"]
+    if e == "aspp":
+        px = float(s["N"]) * s["H"] * s["W"]
+        return px * (28.0 * s["Cin"] * s["Cb"] + 5.0 * s["Cb"] * s["Kout"]) + s["N"] * s["Cb"] * (s["Cin"] + s["Kout"])
+    if e == "resize_bilinear":
+        return 4.0 * s["N"] * s["C"] * s["Ho"] * s["Wo"]
     raise KeyError(e)
 
 
@@ -350,7 +366,247 @@ def head_cases():
     return cases
 
 
+# ---- the segmentation path: the dilated 3x3, its bottleneck blocks, the concat projection, ASPP, the resize ---------
+SEG_MACS = 3e8   # per case, so that a generator's references together stay below MAX_SUM_MACS
+
+
+def _pkg():
+    """The library, for the two corners that only a host-side plan query can place (nothing here touches a GPU)."""
+    import __graft_entry__ as ge
+    return ge.load_package()
+
+
+def dil_class(H, W, d):
+    """The reach class of a dilation against the map: 0 d < min(H, W); 1 W <= d < H (only the vertical taps are live);
+    2 H <= d < W; 3 d >= max(H, W) (only the centre tap)."""
+    if d < min(H, W):
+        return 0
+    if d >= max(H, W):
+        return 3
+    return 1 if W <= d < H else 2
+
+
+def _dil_d(r, H, W, cls):
+    """A dilation of reach class `cls` for the map, or None when the map has none."""
+    lo, hi = min(H, W), max(H, W)
+    if cls == 0 and lo == 1:      # a one-line map has no d below both sides: the class of its long side
+        cls = 3 if hi == 1 else (2 if H == 1 else 1)
+    if cls == 0:
+        return int(r.randint(1, lo))
+    if cls == 3:
+        return hi + int(r.randint(0, 12))
+    if (cls == 1) != (W < H) or H == W:
+        return None
+    return int(r.randint(lo, hi))
+
+
+def largest_dilation(pkg, N, H, W, C, K):
+    """The largest dilation check_dilated accepts for the shape: bisected on the plan query's own refusal."""
+    def ok(d):
+        try:
+            pkg.conv3x3_dilated_plan(N, H, W, C, K, d)
+            return True
+        except pkg.WinoError:
+            return False
+    lo, hi = 1, 1 << 30
+    assert ok(lo) and not ok(hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if ok(mid) else (lo, mid)
+    return lo
+
+
+WIDE_MAP = {"N": 1, "H": 3, "W": 2001, "C": 32, "K": 64}   # the map of the largest-dilation corner
+
+# forced forms on shapes that take them (8- and 4-wave tiles; 64-, 128- and 320-wide outputs; 1, 2, 3, 4, 5 k-steps per
+# tap): grids with a range boundary inside a tap, on a tap boundary, and (C = 32) on nothing else
+DIL_FORCED = [
+    ((2, 28, 28, 64, 256, 2), "split_24"), ((3, 15, 13, 96, 128, 4), "split_40"), ((3, 11, 9, 128, 192, 2), "split_104"),
+    ((5, 6, 6, 160, 128, 7), "stream_k"), ((2, 10, 10, 64, 320, 2), "split_40"), ((1, 20, 20, 32, 64, 2), "split_24"),
+    ((2, 9, 11, 64, 64, 3), "tiled"), ((2, 8, 8, 96, 64, 9), "tiled"), ((1, 12, 12, 64, 64, 2), "stream_k"),
+]
+# corners pinned on the automatic draws: d = 1; one-line maps longer than d; odd x odd; a tile over >= 3 images; one
+# k-step per tap; an odd number > 1; C >= 512; K % 128 != 0
+DIL_PINS = [{"d": 1}, {"H": 1, "cls": 2}, {"W": 1, "cls": 1}, {"odd": True}, {"N": 4, "H": 5, "W": 7}, {"C": 32}, {"C": 96},
+            {"C": 512, "K": 64}, {"K": 320}, {"K": 192}, {"C": 32, "N": 6}, {"C": 160}]
+
+
+def dilated_cases():
+    rng = np.random.RandomState(6161)
+    entry = "conv3x3_dilated_bn_relu"
+    cases = []
+    for i in range(20):
+        pin = dict(DIL_PINS[i]) if i < len(DIL_PINS) else {}
+        cls = pin.pop("cls", i % 4)
+        for _ in range(4000):
+            sh = {"N": int(rng.randint(1, 7)), "H": int(rng.randint(1, 23)), "W": int(rng.randint(1, 23)),
+                  "C": 32 * int(rng.randint(1, 9)), "K": int(rng.choice([64, 128, 192, 256, 320]))}
+            sh = _pinned(sh, {k: v for k, v in pin.items() if k != "d"})
+            if sh["H"] == 1 or sh["W"] == 1:     # a one-line map: the line is longer than d
+                sh["H" if sh["W"] == 1 else "W"] += 6
+            sh["d"] = pin.get("d") or _dil_d(rng, sh["H"], sh["W"], cls)
+            if sh["d"] and macs(Case(entry, sh)) <= SEG_MACS:
+                break
+        else:
+            raise RuntimeError(f"{entry}: no shape drawn")
+        cases.append(Case(entry, sh, None, None, _flags(rng, i)))
+    # the whole tensor inside one tile's window; the largest dilation the wide map takes; automatic whole tiles
+    extra = [{"N": 3, "H": 3, "W": 3, "C": 64, "K": 128, "d": 5},
+             {**WIDE_MAP, "d": largest_dilation(_pkg(), *WIDE_MAP.values())},
+             {"N": 12, "H": 20, "W": 20, "C": 32, "K": 64, "d": 2}]
+    for sh in extra:
+        cases.append(Case(entry, sh, None, None, _flags(rng, len(cases))))
+    for (N, H, W, C, K, d), form in DIL_FORCED:
+        sh = {"N": N, "H": H, "W": W, "C": C, "K": K, "d": d}
+        cases.append(Case(entry, sh, dict(DIL_FORMS[form]), form, _flags(rng, len(cases))))
+    return cases
+
+
+BLOCK_FORMS = V15_FORMS
+# (N, H, W, Cin, Cm, C4, d, proj, form): every launch of the block in the forced form
+BLOCK_FORCED = [
+    ((2, 12, 12, 256, 128, 256, 2, False), "stream_k"), ((3, 10, 12, 128, 128, 256, 4, True), "stream_k"),
+    ((2, 9, 9, 256, 64, 256, 2, False), "tiled"), ((1, 7, 11, 128, 64, 192, 4, True), "tiled"),
+]
+BLOCK_PINS = [{"H": 1}, {"W": 1}, {"Cm": 64}, {"Cm": 192}, {"C4": 192}, {"Cm": 320, "C4": 320}, {"odd": True}, {"Cm": 64, "C4": 320}]
+
+
+def dilated_block_cases():
+    rng = np.random.RandomState(6262)
+    entry = "dilated_block"
+    cases = []
+    for i in range(16):
+        proj = bool(i % 2)
+        pin = BLOCK_PINS[(i // 2) % len(BLOCK_PINS)] if i < 2 * len(BLOCK_PINS) else {}
+        cls = (0, 3, 1, 2)[(i // 2 + i % 2) % 4]
+        for _ in range(4000):
+            sh = {"N": int(rng.randint(1, 7)), "H": int(rng.randint(1, 19)), "W": int(rng.randint(1, 19)),
+                  "Cin": 32 * int(rng.randint(1, 13)), "Cm": 64 * int(rng.randint(1, 6)), "C4": 64 * int(rng.randint(1, 7))}
+            sh = _pinned(sh, pin)
+            if not proj:
+                sh["Cin"] = sh["C4"]
+            sh["d"] = _dil_d(rng, sh["H"], sh["W"], cls)
+            sh["proj"] = proj
+            if sh["d"] and macs(Case(entry, sh)) <= SEG_MACS / 2:
+                break
+        else:
+            raise RuntimeError(f"{entry}: no shape drawn")
+        cases.append(Case(entry, sh, None, None, {"nonneg": bool(i % 3 == 1)}))
+    # the automatic whole-tile form of the last 1x1 launch: a batch past its latency form
+    cases.append(Case(entry, {"N": 8, "H": 20, "W": 21, "Cin": 64, "Cm": 64, "C4": 320, "d": 3, "proj": True}, None, None,
+                      {"nonneg": True}))
+    for (N, H, W, Cin, Cm, C4, d, proj), form in BLOCK_FORCED:
+        sh = {"N": N, "H": H, "W": W, "Cin": Cin, "Cm": Cm, "C4": C4, "d": d, "proj": proj}
+        cases.append(Case(entry, sh, dict(BLOCK_FORMS[form]), form, {"nonneg": bool(len(cases) % 3 == 1)}))
+    return cases
+
+
+# forced forms of the concat layer: 1 .. 8 k-steps per source; grids with a range boundary inside a source and on one
+CAT_FORCED = [
+    ((2, 28, 28, 4, 64, 256), "split_24"), ((3, 15, 13, 5, 96, 128), "split_40"), ((1, 16, 16, 8, 256, 64), "split_104"),
+    ((3, 7, 11, 5, 96, 192), "stream_k"), ((2, 12, 12, 3, 160, 320), "split_40"), ((8, 1, 1, 4, 64, 128), "stream_k"),
+    ((2, 9, 9, 4, 64, 64), "tiled"), ((3, 7, 11, 5, 96, 192), "tiled"), ((30, 14, 14, 2, 32, 64), "split_24"),
+]
+# M % 112 == 0; every row its own image; a tile over >= 3 images; one k-step per source, an odd number, DeepLab's width;
+# Kout % 128 != 0
+CAT_PINS = [{"N": 2, "H": 7, "W": 8}, {"N": 9, "H": 1, "W": 1}, {"N": 5, "H": 3, "W": 4}, {"Cs": 32}, {"Cs": 96}, {"Cs": 256},
+            {"Kout": 192}, {"Cs": 32, "S": 8}, {"N": 4, "H": 14, "W": 14, "S": 2}, {"odd": True}]
+
+
+def _cat_flags(i):
+    return {"relu": bool(i % 3 != 2), "a_padded": bool(i % 2), "c_padded": bool((i // 2) % 2), "nonneg": bool(i % 5 == 1)}
+
+
+def cat_cases():
+    rng = np.random.RandomState(6363)
+    entry = "conv1x1_cat_bn"
+    cases = []
+
+    def add(sh, form):
+        i = len(cases)
+        p = 2 if _cat_flags(i)["a_padded"] else 0
+        n = sh["N"] * (sh["H"] + p) * (sh["W"] + p) * sh["Cs"]
+        # between two sources: nothing, the smallest legal gap, more than a source
+        sh["gap"] = (0, 4, n + 4 * int(rng.randint(1, 64)))[i % 3]
+        cases.append(Case(entry, sh, dict(DIL_FORMS[form]) if form else None, form, _cat_flags(i)))
+
+    for i in range(16):
+        def make(r):
+            return {"N": int(r.randint(1, 9)), "H": int(r.randint(1, 15)), "W": int(r.randint(1, 15)),
+                    "S": int(r.choice([2, 3, 5, 8])), "Cs": 32 * int(r.randint(1, 9)),
+                    "Kout": int(r.choice([64, 128, 192, 256, 320]))}
+        add(_draw(rng, make, lambda sh: macs(Case(entry, sh)) <= SEG_MACS, entry, CAT_PINS[i] if i < len(CAT_PINS) else None),
+            None)
+    for (N, H, W, S, Cs, Kout), form in CAT_FORCED:
+        add({"N": N, "H": H, "W": W, "S": S, "Cs": Cs, "Kout": Kout}, form)
+    return cases
+
+
+# (H, W, rates): ascending, non-ascending, two equal; one rate past the map, all three; a 1x1 map
+ASPP_RATES = [((9, 9), (1, 2, 3)), ((7, 11), (4, 2, 12)), ((6, 8), (3, 3, 5)), ((5, 5), (12, 24, 36)), ((1, 1), (1, 2, 3)),
+              ((8, 6), (2, 9, 2)), ((1, 9), (2, 4, 6)), ((10, 3), (1, 3, 2))]
+ASPP_PINS = [{"Cb": 64}, {"Cb": 192}, {"Cb": 320, "Kout": 64}, {"N": 3}, {"Cin": 32, "Cb": 64, "Kout": 128}, {"N": 4, "Cb": 128}]
+
+
+def aspp_cases():
+    rng = np.random.RandomState(6464)
+    entry = "aspp"
+    cases = []
+    for i in range(14):
+        (H, W), rates = ASPP_RATES[i % len(ASPP_RATES)]
+        if i >= len(ASPP_RATES):
+            H, W = int(rng.randint(1, 13)), int(rng.randint(1, 13))
+            rates = tuple(int(v) for v in rng.randint(1, 16, size=3))
+
+        def make(r):
+            return {"N": int(r.randint(1, 5)), "H": H, "W": W, "Cin": 32 * int(r.randint(1, 7)),
+                    "Cb": int(r.choice([64, 128, 192, 320])), "Kout": int(r.choice([64, 128, 192, 256]))}
+        sh = _draw(rng, make, lambda sh: macs(Case(entry, sh)) <= SEG_MACS / 2, entry, ASPP_PINS[i % len(ASPP_PINS)])
+        sh["rates"] = rates
+        cases.append(Case(entry, sh, None, None, {"nonneg": bool(i % 3 == 1)}))
+    # the join's automatic stream-K form: more k-steps than the small draws reach
+    cases.append(Case(entry, {"N": 3, "H": 12, "W": 12, "Cin": 32, "Cb": 192, "Kout": 64, "rates": (2, 13, 5)}, None, None,
+                      {"nonneg": False}))
+    return cases
+
+
+# (N, h, w, Ho, Wo, C, ld): up by a fraction on both axes (Wo % 4 = 3, Ho % 8 != 0); up on one axis and down on the other;
+# the identity; a mild down-scale; more than 4x down on one axis only; one-line and one-pixel inputs and outputs; two
+# x-segments of an odd width; the direct form past 256 columns; N >= 3
+RESIZE_SHAPES = [
+    (2, 9, 7, 23, 19, 21, 24), (1, 8, 12, 20, 5, 5, 8), (1, 9, 9, 9, 9, 4, 4), (2, 12, 10, 5, 7, 64, 64),
+    (2, 40, 6, 8, 9, 8, 16), (3, 1, 7, 5, 13, 3, 4), (1, 6, 1, 11, 2, 2, 4), (2, 5, 9, 1, 17, 6, 8), (2, 7, 4, 9, 1, 1, 4),
+    (1, 3, 40, 9, 301, 2, 4), (1, 30, 70, 5, 259, 3, 4), (3, 5, 3, 33, 49, 5, 8), (1, 4, 90, 12, 19, 12, 20),
+    (2, 6, 5, 14, 518, 3, 12),
+]
+LDS_MAP = (6, 40, 9, 64)   # (h, w, Ho, Wo) of the case that is direct because no block fits in LDS
+
+
+def resize_cases():
+    rng = np.random.RandomState(6565)
+    entry = "resize_bilinear"
+    shapes = [dict(zip(("N", "h", "w", "Ho", "Wo", "C", "ld"), s)) for s in RESIZE_SHAPES]
+    h, w, Ho, Wo = LDS_MAP
+    C = smallest_direct_channels(_pkg(), h, w, Ho, Wo)
+    shapes.append({"N": 1, "h": h, "w": w, "Ho": Ho, "Wo": Wo, "C": C, "ld": C})
+    for _ in range(7):
+        C = int(rng.randint(1, 25))
+        shapes.append({"N": int(rng.randint(1, 4)), "h": int(rng.randint(1, 13)), "w": int(rng.randint(1, 13)),
+                       "Ho": int(rng.randint(1, 41)), "Wo": int(rng.randint(1, 41)), "C": C,
+                       "ld": (C + 3) // 4 * 4 + int(rng.choice([0, 4, 8]))})
+    cases = []
+    for i, sh in enumerate(shapes):
+        sh["outputs"] = ("both", "out", "labels")[i % 3]
+        cases.append(Case(entry, sh, None, None, {"in_padded": bool((i // 3) % 2)}))
+    return cases
+
+
 GENERATORS = {
+    "conv3x3_dilated_bn_relu": dilated_cases,
+    "dilated_block": dilated_block_cases,
+    "conv1x1_cat_bn": cat_cases,
+    "aspp": aspp_cases,
+    "resize_bilinear": resize_cases,
     "conv3x3_bn_add_relu": residual_3x3_cases,
     "basic_block": basic_block_cases,
     "conv3x3_s2_bn_relu": conv3x3_s2_cases,
@@ -421,6 +677,30 @@ def plan_form(pkg, case, cus=CUS):
         return {"form": {1: "big", 2: "small"}[pkg.stem_plan(s["N"], s["H"], s["W"], s["K"], cus)]}
     if e == "avgpool_fc":
         return {"form": form_1x1(pkg, s["N"], s["C"], head_cols(s["classes"]), cus)}
+    if e == "conv3x3_dilated_bn_relu":
+        form = FORM_NAMES[pkg.conv3x3_dilated_plan(s["N"], s["H"], s["W"], s["C"], s["K"], s["d"], cus)]
+        return {"form": form, **sk_ranges(pkg, s["N"] * s["H"] * s["W"], 9 * s["C"], s["K"], s["C"] // 32, cus)}
+    if e == "dilated_block":
+        M = s["N"] * s["H"] * s["W"]
+        first = form_1x1(pkg, M, s["Cin"], s["Cm"], cus)
+        mid = FORM_NAMES[pkg.conv3x3_dilated_plan(s["N"], s["H"], s["W"], s["Cm"], s["Cm"], s["d"], cus)]
+        if s["proj"]:
+            tail = FORM_NAMES[pkg.proj_tail_plan(s["N"], s["H"], s["W"], s["Cin"], s["Cm"], s["C4"], 1, cus)[1]]
+        else:
+            tail = form_1x1(pkg, M, s["Cm"], s["C4"], cus)
+        return {"form": f"{first}/{mid}/{tail}", "first": first, "mid": mid, "tail": tail}
+    if e == "conv1x1_cat_bn":
+        form = FORM_NAMES[pkg.conv1x1_cat_plan(s["N"], s["H"], s["W"], s["S"], s["Cs"], s["Kout"], cus)]
+        return {"form": form, **sk_ranges(pkg, s["N"] * s["H"] * s["W"], s["S"] * s["Cs"], s["Kout"], s["Cs"] // 32, cus)}
+    if e == "aspp":   # the join names the form; every other launch must be one the library plans
+        for d in s["rates"]:
+            pkg.conv3x3_dilated_plan(s["N"], s["H"], s["W"], s["Cin"], s["Cb"], d, cus)
+        form_1x1(pkg, s["N"] * s["H"] * s["W"], s["Cin"], s["Cb"], cus)
+        return {"form": FORM_NAMES[pkg.conv1x1_cat_plan(s["N"], s["H"], s["W"], 4, s["Cb"], s["Kout"], cus)]}
+    if e == "resize_bilinear":
+        form = pkg.resize_bilinear_plan(s["h"], s["w"], s["C"], s["ld"], s["Ho"], s["Wo"], s["outputs"] != "labels",
+                                        s["outputs"] != "out")
+        return {"form": {STAGED: "staged", DIRECT: "direct"}[form]}
     raise KeyError(e)
 
 
@@ -459,6 +739,16 @@ def check_forced(case, plan) -> str | None:
         return None if plan["form"] == f else f"want {f}, plan {plan}"
     if e == "avgpool_fc":
         return None if plan["form"] == f else f"want {f}, plan {plan}"
+    if e in ("conv3x3_dilated_bn_relu", "conv1x1_cat_bn"):
+        want = "tiled" if f == "tiled" else "stream_k"
+        if plan["form"] != want:
+            return f"want {want}, plan {plan}"
+        if "WINO_1X1_SK_GRID" in kn and not 0 < plan["grid"] <= kn["WINO_1X1_SK_GRID"]:
+            return f"want a stream-K grid of at most {kn['WINO_1X1_SK_GRID']}, plan {plan}"
+        return None
+    if e == "dilated_block":
+        ok = (plan["first"], plan["mid"], plan["tail"]) == (f, f, f)
+        return None if ok else f"want {f} for all three launches, plan {plan}"
     raise KeyError(e)
 
 
@@ -491,7 +781,34 @@ def sizes(pkg, case) -> dict:
     if e == "avgpool_fc":
         return {"packed": L.wino_head_elems(s["C"], s["classes"]),
                 "workspace": L.wino_head_workspace_bytes(s["N"], s["C"], s["classes"])}
+    if e == "dilated_block":
+        q = L.wino_proj_block_workspace_bytes_hw if s["proj"] else L.wino_residual_block_workspace_bytes_hw
+        d = {"workspace": q(s["N"], s["H"], s["W"], s["Cm"])}
+        if s["proj"]:
+            d["tail"] = L.wino_proj_tail_elems(s["Cm"], s["Cin"], s["C4"])
+        return d
+    if e == "aspp":
+        return {"workspace": pkg.aspp_workspace_bytes(s["N"], s["H"], s["W"], s["Cin"], s["Cb"], s["Kout"])}
+    if e in ("conv3x3_dilated_bn_relu", "conv1x1_cat_bn", "resize_bilinear"):
+        return {}   # (no pack or workspace query of their own)
     raise KeyError(e)
+
+
+def sk_ranges(pkg, M, Cin, Kout, unit, cus=CUS) -> dict:
+    """The stream-K ranges of the GEMM (M, Cin, Kout) under the knobs currently set, as centre_tap_split reads them off
+    wino_conv1x1_plan: the grid, and how many range boundaries fall strictly inside a unit of `unit` k-steps (a tap of
+    the dilated layer, a source of the concat layer) and how many exactly between two units of one tile.  Zeros for
+    whole tiles."""
+    v = [ctypes.c_int() for _ in range(5)]
+    rc = pkg.lib().wino_conv1x1_plan(M, Cin, Kout, cus, *[ctypes.byref(x) for x in v])
+    if rc:
+        raise pkg.WinoError(f"wino_conv1x1_plan rc={rc}")
+    grid, row_tiles, col_blocks, k_steps, sk = (x.value for x in v)
+    if not sk:
+        return {"grid": 0, "inside": 0, "between": 0}
+    R, T = grid // col_blocks, row_tiles * k_steps
+    pos = [(r * T // R) % k_steps for r in range(1, R)]
+    return {"grid": grid, "inside": sum(1 for p in pos if p % unit), "between": sum(1 for p in pos if p and p % unit == 0)}
 
 
 def centre_tap_split(pkg, case, cus=CUS) -> bool:

@@ -5,15 +5,24 @@ the checks; each runner launches twice per placement, compares with the fp64 ref
 in arena.check, which CHECKS counts by entry point."""
 import collections
 import contextlib
+import types
 
 import numpy as np
 
+import aspp_cases as AC
 import guarded as G
+import resize_cases as RC
 import shape_sweeps as S
 from cases import TIGHT
+from dilated_cases import dilated_reference
 
 SENTINEL = 1234.5
 CHECKS = collections.Counter()   # arena.check calls that passed, by entry point
+WORST = {}                       # the largest relative error close() saw, by entry point
+# the first seed of the segmentation entries' sweeps (case i takes seed + i): tests/test_shape_sweeps_host.py rebuilds
+# the same tensors for the conditions it proves on the references
+SEEDS = {"conv3x3_dilated_bn_relu": 1000, "dilated_block": 1100, "conv1x1_cat_bn": 1200, "aspp": 1300,
+         "resize_bilinear": 1400}
 
 
 @contextlib.contextmanager
@@ -128,6 +137,7 @@ class Sweep:
         assert tuple(g.shape) == tuple(w.shape), f"{self.tag} {what}: shape {tuple(g.shape)} != {tuple(w.shape)}"
         assert bool(self.torch.isfinite(g).all()), f"{self.tag} {what}: non-finite values (not all written)"
         err = float((g - w).abs().max() / w.abs().max())
+        WORST[self.case.entry] = max(WORST.get(self.case.entry, 0.0), err)
         assert err < TIGHT, f"{self.tag} {what}: rel err {err:.3e}"
 
     def ring_is(self, got, value, what="out"):
@@ -165,11 +175,14 @@ def run_sweep(entry, run, pkg, knobs, torch_dev, seed0):
     """Every case of the entry point's generator, and the count that none was left out at either placement."""
     cases = S.GENERATORS[entry]()
     before = CHECKS[entry]
+    WORST.pop(entry, None)
     for i, case in enumerate(cases):
         assert case.entry == entry
         with forced(knobs, case):
             run(pkg, knobs, torch_dev, case, seed0 + i)
     done = CHECKS[entry] - before
+    if entry in WORST:
+        print(f"{entry}: {len(cases)} cases, worst rel err {WORST[entry]:.2e}")
     assert done == 2 * len(cases), f"{entry}: {done} guard checks for {len(cases)} cases at two placements"
 
 
@@ -424,3 +437,174 @@ def head_case(pkg, knobs, torch_dev, case, seed):
                                workspace=sw.ws(need, "wino_head_workspace_bytes")) for _ in range(2)]
         sw.close(outs[0], want, "logits")
         sw.same(outs[0], outs[1], "logits")
+
+
+# ---- the dilated 3x3 and the dilated bottleneck blocks ----------------------------------------------------------------
+def dilated_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    N, H, W, C, K, d, relu = case.N, case.H, case.W, case.C, case.K, case.d, case.flags["relu"]
+    x = sw.padded(sw.act(N, H, W, C))          # the ring is read: zero, as the contract says
+    w, bn = sw.conv_w(K, C), sw.bn(K)
+    pre = sw.torch.from_numpy(dilated_reference(x.numpy(), w.numpy(), bn[1].numpy(), bn[0].numpy(), d, relu=False))
+    if relu:
+        sw.both_sides(pre)
+    want = sw.torch.relu(pre) if relu else pre
+    for _ in sw.passes():
+        xd = sw.d(x, "x")
+        taps = sw.packed(pkg.filter_pack_s2, (3, 3, C, K), "taps", sw.d(w, "w"))
+        bd, sd = sw.bnd(bn)
+        outs = [pkg.conv3x3_dilated_bn_relu(xd, taps, bd, sd, d, relu=relu, out=sw.nan(N, H + 2, W + 2, K))
+                for _ in range(2)]
+        sw.ring_is(outs[0], 0.0)
+        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
+        sw.same(outs[0], outs[1])
+
+
+def dilated_block_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    N, H, W, Cin, Cm, C4, d, proj = case.N, case.H, case.W, case.Cin, case.Cm, case.C4, case.d, case.proj
+    B = ProjCase(sw, types.SimpleNamespace(N=N, Hin=H, Win=W, Cin=Cin, Cm=Cm, C4=C4))
+    f = lambda a: a.numpy().astype(np.float64)
+    bn = [(f(b), f(s)) for b, s in B.bn]
+    x2 = f(B.x).reshape(-1, Cin)
+    t1p = np.zeros((N, H + 2, W + 2, Cm))
+    t1p[:, 1:-1, 1:-1, :] = np.maximum(x2 @ f(B.w1) * bn[0][1] + bn[0][0], 0).reshape(N, H, W, Cm)
+    t2 = dilated_reference(t1p, f(B.w2), bn[1][1], bn[1][0], d, True).reshape(-1, Cm)
+    sc = (x2 @ f(B.wp) * bn[3][1] + bn[3][0]) if proj else x2
+    pre = sw.torch.from_numpy((t2 @ f(B.w3) * bn[2][1] + bn[2][0] + sc).reshape(N, H, W, C4))
+    sw.both_sides(pre)
+    L = pkg.lib()
+    query = "wino_proj_block_workspace_bytes_hw" if proj else "wino_residual_block_workspace_bytes_hw"
+    need = getattr(L, query)(N, H, W, Cm)
+    for _ in sw.passes():
+        xd, w1d = sw.d(B.x, "x"), sw.d(B.w1, "w1")
+        bnd = [sw.bnd(b, f"bn{i}") for i, b in enumerate(B.bn[:3 + proj])]
+        taps = sw.packed(pkg.filter_pack_s2, (3, 3, Cm, Cm), "taps", sw.d(B.w2, "w2"))
+        if proj:
+            last = sw.packed(pkg.proj_tail_pack, L.wino_proj_tail_elems(Cm, Cin, C4), "tail", sw.d(B.w3, "w3"), bnd[2],
+                             sw.d(B.wp, "wp"), bnd[3])
+            run = lambda: pkg.dilated_proj_block(xd, w1d, bnd[0], taps, bnd[1], last, d, out=sw.nan(N, H, W, C4),
+                                                 workspace=sw.ws(need, query))
+        else:
+            last = sw.d(B.w3, "w3")
+            run = lambda: pkg.dilated_residual_block(xd, w1d, bnd[0], taps, bnd[1], last, bnd[2], d,
+                                                     out=sw.nan(N, H, W, C4), workspace=sw.ws(need, query))
+        outs = [run(), run()]
+        sw.close(outs[0], sw.torch.relu(pre))
+        sw.same(outs[0], outs[1])
+
+
+# ---- the concat projection and ASPP ------------------------------------------------------------------------------------
+def cat_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    torch = sw.torch
+    N, H, W, S, Cs, Kout, gap = case.N, case.H, case.W, case.S, case.Cs, case.Kout, case.gap
+    relu, a_pad, c_pad = case.flags["relu"], case.flags["a_padded"], case.flags["c_padded"]
+    srcs = [sw.act(N, H, W, Cs) for _ in range(S)]
+    w = (sw.rand(S * Cs, Kout) - 0.5) / np.sqrt(S * Cs) * 4
+    bias = sw.rand(N, Kout) * 8 - 4            # a neighbouring image's row is far outside TIGHT
+    scale = sw.bn(Kout)[1]
+    pre = torch.from_numpy(AC.cat_reference([s.numpy() for s in srcs], w.numpy(), bias.numpy(), scale.numpy(), False))
+    if relu:
+        sw.both_sides(pre)
+    want = torch.relu(pre) if relu else pre
+    # the sources in one buffer, `stride` floats apart: NaN between them and in the rings of padded sources
+    shape = (N, H + 2, W + 2, Cs) if a_pad else (N, H, W, Cs)
+    n = int(np.prod(shape))
+    stride = n + gap
+    master = torch.full(((S - 1) * stride + n,), float("nan"))
+    for j, src in enumerate(srcs):
+        v = master[j * stride: j * stride + n].view(shape)
+        (v[:, 1:-1, 1:-1, :] if a_pad else v).copy_(src)
+    flags = (AC.RELU if relu else 0) | (AC.A_PADDED if a_pad else 0) | (AC.C_PADDED if c_pad else 0)
+    out_shape = (N, H + 2, W + 2, Kout) if c_pad else (N, H, W, Kout)
+    for _ in sw.passes():
+        buf = sw.d(master, "sources")
+        views = [buf[j * stride: j * stride + n].view(shape) for j in range(S)]
+        wd, bd, sd = sw.d(w, "w"), sw.d(bias, "bias_per_image"), sw.d(scale, "scale")
+        outs = [pkg.conv1x1_cat_bn(views, wd, bd, sd, flags, out=sw.nan(*out_shape)) for _ in range(2)]
+        got = outs[0]
+        if c_pad:
+            sw.ring_is(got, 0.0)
+            got = got[:, 1:-1, 1:-1, :]
+        sw.close(got, want)
+        sw.same(outs[0], outs[1])
+
+
+class AsppProblem:
+    """An ASPP case's tensors (image n's input is shifted by 0.2 n: the pooled branch differs from image to image) and
+    its fp64 reference, with and without the pooled branch."""
+
+    def __init__(self, sw, case):
+        N, H, W, Cin, Cb, Kout = case.N, case.H, case.W, case.Cin, case.Cb, case.Kout
+        shift = 0.2 * sw.torch.arange(N, dtype=sw.torch.float32)[:, None, None, None]
+        self.x = sw.padded(sw.act(N, H, W, Cin) + shift)
+        w11 = lambda i, o: (sw.rand(i, o) - 0.5) / np.sqrt(i) * 4
+        self.w0, self.ws = w11(Cin, Cb), [sw.conv_w(Cb, Cin) for _ in range(3)]
+        self.w_pool, self.w_proj = w11(Cin, Cb), w11(5 * Cb, Kout)
+        self.bn = [sw.bn(c) for c in (Cb, Cb, Cb, Cb, Cb, Kout)]   # b0, three dilated, pool, proj
+        self.rates = tuple(case.rates)
+
+    def reference(self, pooled=True):
+        n = lambda a: a.numpy()
+        bn = [(n(b), n(s)) for b, s in self.bn]
+        return AC.aspp_reference(n(self.x), n(self.w0), bn[0], [n(w) for w in self.ws], bn[1:4], self.rates,
+                                 n(self.w_pool), bn[4], n(self.w_proj), bn[5], pooled)
+
+
+def aspp_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    N, H, W, Cin, Cb, Kout = case.N, case.H, case.W, case.Cin, case.Cb, case.Kout
+    P = AsppProblem(sw, case)
+    want = sw.torch.from_numpy(P.reference())
+    assert float((want > 0).double().mean()) > 0.05 and bool((want == 0).any()), f"{sw.tag}: the ReLU sees one side only"
+    need = pkg.aspp_workspace_bytes(N, H, W, Cin, Cb, Kout)
+    for _ in sw.passes():
+        xd, w0, w_pool, w_proj = sw.d(P.x, "x"), sw.d(P.w0, "w0"), sw.d(P.w_pool, "w_pool"), sw.d(P.w_proj, "w_proj")
+        taps = [sw.packed(pkg.filter_pack_s2, (3, 3, Cin, Cb), f"taps{i}", sw.d(w, f"w{i + 1}")) for i, w in enumerate(P.ws)]
+        bnd = [sw.bnd(b, f"bn{i}") for i, b in enumerate(P.bn)]
+        outs = [pkg.aspp(xd, w0, bnd[0], taps, bnd[1:4], P.rates, w_pool, bnd[4], w_proj, bnd[5],
+                         out=sw.nan(N, H + 2, W + 2, Kout), workspace=sw.ws(need, "aspp_workspace_bytes"))
+                for _ in range(2)]
+        sw.ring_is(outs[0], 0.0)
+        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
+        sw.same(outs[0], outs[1])
+
+
+# ---- the bilinear resize and label map ---------------------------------------------------------------------------------
+def resize_src(sw, case):
+    """src [N][h(+2)][w(+2)][ld]: the classes uniform in [-0.5, 0.5), NaN in the columns past C and in the ring."""
+    N, h, w, C, ld = case.N, case.h, case.w, case.C, case.ld
+    x = sw.torch.full((N, h, w, ld), float("nan"))
+    x[..., :C] = sw.rand(N, h, w, C) - 0.5
+    return sw.padded(x, ring=float("nan")) if case.flags["in_padded"] else x
+
+
+def resize_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    torch = sw.torch
+    N, Ho, Wo, C, padded, use = case.N, case.Ho, case.Wo, case.C, case.flags["in_padded"], case.outputs
+    src = resize_src(sw, case)
+    want = RC.resize_reference(src.numpy(), Ho, Wo, C, padded)
+    for _ in sw.passes():
+        xd = sw.d(src, "src")
+        runs = []
+        for _ in range(2):
+            out = sw.nan(N, C, Ho, Wo, name="out") if use != "labels" else None
+            # (the arena holds float32: an unwritten label keeps the NaN bit pattern, which is no class)
+            lab = sw.nan(N, Ho, Wo, name="labels").view(torch.int32) if use != "out" else None
+            o, l = pkg.resize_bilinear(xd, Ho, Wo, C=C, in_padded=padded, out=out, labels=lab,
+                                       want_out=out is not None, want_labels=lab is not None)
+            assert (o is None) == (out is None) and (l is None) == (lab is None), sw.tag
+            runs.append((o, l))
+        (o, l), (o2, l2) = runs
+        if o is not None:
+            sw.close(o, torch.from_numpy(want))
+            sw.same(o.view(torch.int32), o2.view(torch.int32))
+        if l is not None:
+            lab = l.cpu().numpy()
+            assert lab.min() >= 0 and lab.max() < C, f"{sw.tag}: labels outside [0, {C}) (not all written)"
+            RC.check_labels(lab, want, TIGHT, sw.tag)
+            sw.same(l, l2, "labels")
+        if use == "both":   # the label is the argmax of the values that were stored
+            assert np.array_equal(l.cpu().numpy(), RC.labels_of(o.cpu().numpy())), f"{sw.tag}: labels != argmax(out)"

@@ -13,12 +13,15 @@ batch whose tensors cross 2^31 and 2^32 bytes, into NaN-filled outputs and works
 
 Inputs are built on the device from a seeded generator; a case skips when the card has less free memory than it needs
 (at most about 20 GiB)."""
+import ctypes
 import types
 
 import numpy as np
 import pytest
 
+from aspp_cases import cat_reference
 from cases import TIGHT, BasicBlock, ResLayer, S2Block, S2Layer, V15Block, proj_oracle, proj_weights, ring_zero
+from dilated_cases import dilated_reference
 from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -474,6 +477,152 @@ def test_residual_block_beyond_4gib(pkg, O, torch_dev, free_after):
         assert torch.equal(g_idx, first)
     assert (want > 0).mean() > 0.2
     del x, out, ws
+
+
+# ------------------------------------------------------------------ the dilated 3x3 (A_DIL) and the concat projection (A_CAT)
+@pytest.mark.parametrize("form", sorted(FORMS_1X1))
+def test_dilated_3x3_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
+    """conv3x3_dilated_bn_relu at 62x62, 64 -> 64, dilation 3, 4100 images: one padded image is exactly 1 MiB, so in and
+    out are 4.3 GB each and images 2048 and 4096 start on 2^31 and 2^32 bytes -- the per-lane centre offsets, the tap
+    offset that wraps modulo 2^32 and the window's clipping at both ends of the tensor, in the planner's form, whole
+    tiles and stream-K."""
+    torch, dev = torch_dev
+    N, H, C, K, d = 4100, 62, 64, 64, 3
+    P = (H + 2) * (H + 2) * C * 4
+    assert P == 1 << 20 and N * P > 1 << 32
+    _need(torch, 2 * N * P)
+    _set(knobs, FORMS_1X1[form])
+    if form != "default":
+        assert pkg.conv3x3_dilated_plan(N, H, H, C, K, d) == (pkg.FORM_TILED if form == "tiled" else pkg.FORM_STREAM_K)
+    idx = _images(N, [P])
+    assert {2047, 2048, 4095, 4096} <= set(idx)
+    g = torch.Generator(device="cpu").manual_seed(161)
+    w = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
+    bias, scale = torch.rand(K, generator=g) - 0.5, torch.rand(K, generator=g) + 0.5
+    taps, bt, st = pkg.filter_pack_s2(w.to(dev)), bias.to(dev), scale.to(dev)
+    x = _padded_rand(torch, dev, N, H, H, C, 162)
+    want = dilated_reference(_pick(torch, x, idx).numpy(), w.numpy(), scale.numpy(), bias.numpy(), d, True)
+    out = torch.empty(N, H + 2, H + 2, K, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        pkg.conv3x3_dilated_bn_relu(x, taps, bt, st, d, relu=True, out=out)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert 0.2 < (want > 0).mean() < 0.8
+    del x, out
+
+
+@pytest.mark.parametrize("form", ["default", "stream_k"])
+def test_conv1x1_cat_output_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
+    """conv1x1_cat_bn at 32x32, 2 sources x 32 -> 256, C_PADDED, 4200 images: the sources (0.55 GB each) stay inside
+    one descriptor while the padded output is 5.0 GB, past 2^31 at image 1814 and 2^32 at image 3628.  Every image has a
+    bias row of its own in [-4, 4): the images on both sides of each boundary must have read theirs."""
+    torch, dev = torch_dev
+    N, H, S, Cs, Kout = 4200, 32, 2, 32, 256
+    Psrc, Pout = H * H * Cs * 4, (H + 2) * (H + 2) * Kout * 4
+    assert N * Pout > 1 << 32 and S * N * Psrc < 1 << 32
+    _need(torch, S * N * Psrc + N * Pout)
+    _set(knobs, FORMS_1X1[form])
+    if form != "default":
+        assert pkg.conv1x1_cat_plan(N, H, H, S, Cs, Kout) == pkg.FORM_STREAM_K
+    idx = _images(N, [Pout])
+    g = torch.Generator(device="cpu").manual_seed(171)
+    w = (torch.rand(S * Cs, Kout, generator=g) - 0.5) / np.sqrt(S * Cs) * 4
+    bias = torch.rand(N, Kout, generator=g) * 8 - 4
+    scale = torch.rand(Kout, generator=g) + 0.5
+    wt, bt, st = w.to(dev), bias.to(dev), scale.to(dev)
+    srcs = _rand(torch, dev, (S, N, H, H, Cs), 172)
+    want = cat_reference([_pick(torch, srcs[j], idx).numpy() for j in range(S)], w.numpy(), bias[idx].numpy(),
+                         scale.numpy(), True)
+    out = torch.empty(N, H + 2, H + 2, Kout, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        got = pkg.conv1x1_cat_bn(srcs, wt, bt, st, pkg.RELU | pkg.C_PADDED, out=out)
+        assert got.data_ptr() == out.data_ptr()
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert 0.2 < (want > 0).mean() < 0.8
+    del srcs, out, got
+
+
+E_SHAPE, E_ARG = -2, -3   # WINO_E_SHAPE, WINO_E_ARG
+
+
+@pytest.mark.parametrize("S", [2, 8])
+def test_conv1x1_cat_at_the_descriptor_edge(S, pkg, O, torch_dev, free_after):
+    """conv1x1_cat_bn (2, 9, 9, S x 64 -> 64) at the largest src_stride the entry point accepts: the tile's one
+    descriptor then ends just under 2^32 bytes, and the last source's rows sit at its far end.  The sources lie in one
+    4.3 GB allocation that is NaN between them; the whole output is checked.  The next stride is refused as a shape
+    error and nothing is launched."""
+    torch, dev = torch_dev
+    N, H, W, Cs, Kout = 2, 9, 9, 64, 64
+    n = N * H * W * Cs
+    L = pkg.lib()
+    ptr = lambda v: ctypes.c_void_p(v)
+
+    def accepted(stride):
+        # host addresses with out placed on the sources: a shape that passes is refused as an overlap, the next check,
+        # so no call here launches anything
+        rc = L.wino_conv1x1_cat_bn_hw(ptr(1 << 32), stride, ptr(2 << 32), ptr(3 << 32), ptr(4 << 32), ptr(1 << 32),
+                                      N, H, W, S, Cs, Kout, pkg.RELU, None)
+        assert rc in (E_SHAPE, E_ARG), rc
+        return rc == E_ARG
+
+    lo, hi = n // 4, 1 << 30   # in steps of 4 floats
+    assert accepted(4 * lo) and not accepted(4 * hi)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (mid, hi) if accepted(4 * mid) else (lo, mid)
+    stride = 4 * lo
+    # the header's inequality, rows = 112 (unpadded sources)
+    assert (112 * Cs + (S - 1) * stride) * 4 < 1 << 32 <= (112 * Cs + (S - 1) * (stride + 4)) * 4
+    total = (S - 1) * stride + n
+    _need(torch, 4 * total)
+    buf = torch.full((total,), NAN, device=dev)
+    views = [buf[j * stride: j * stride + n].view(N, H, W, Cs) for j in range(S)]
+    g = torch.Generator(device="cpu").manual_seed(181 + S)
+    srcs = [torch.rand(N, H, W, Cs, generator=g) - 0.5 for _ in range(S)]
+    for v, src in zip(views, srcs):
+        v.copy_(src)
+    w = (torch.rand(S * Cs, Kout, generator=g) - 0.5) / np.sqrt(S * Cs) * 4
+    bias = torch.rand(N, Kout, generator=g) * 8 - 4
+    scale = torch.rand(Kout, generator=g) + 0.5
+    wt, bt, st = w.to(dev), bias.to(dev), scale.to(dev)
+    want = cat_reference([a.numpy() for a in srcs], w.numpy(), bias.numpy(), scale.numpy(), True)
+    out = torch.empty(N, H, W, Kout, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        pkg.conv1x1_cat_bn(views, wt, bt, st, pkg.RELU, out=out)
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        got = out.cpu()
+        assert bool(torch.isfinite(got).all()), rep
+        assert O.rel_error(got.numpy(), want) < TIGHT, rep
+        if first is None:
+            first = got
+        assert torch.equal(got, first)
+    assert 0.2 < (want > 0).mean() < 0.8
+    # one float more of stride, and the next multiple of 4: shape errors before anything is launched
+    out.fill_(NAN)
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    for more in (1, 4):
+        rc = L.wino_conv1x1_cat_bn_hw(ptr(buf.data_ptr()), stride + more, ptr(wt.data_ptr()), ptr(bt.data_ptr()),
+                                      ptr(st.data_ptr()), ptr(out.data_ptr()), N, H, W, S, Cs, Kout, pkg.RELU, stream)
+        assert rc == E_SHAPE, (more, rc)
+    torch.cuda.synchronize()
+    assert bool(torch.isnan(out).all()) and pkg.tickets_in_use() == 0
+    del buf, views, out
 
 
 # ------------------------------------------------------------------ the largest filter matrix the 3x3 accepts

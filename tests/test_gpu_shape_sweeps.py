@@ -1,4 +1,5 @@
-"""Seeded random-shape sweeps of the ResNet entry points (tests/shape_sweeps.py: shapes from the whole legal envelope
+"""Seeded random-shape sweeps of the ResNet entry points and of the segmentation path -- the dilated 3x3 layer, the
+dilated bottleneck blocks, the concat projection, ASPP and the bilinear resize -- (tests/shape_sweeps.py: shapes from the whole legal envelope
 of winograd_mi355x.h, every forced form the planner takes, the automatic ones): each case against an fp64 reference
 computed on the CPU (tests/sweep_cases.py: the case runners) from the raw torch-layout weights and unfolded BN vectors, into NaN-filled outputs and
 workspaces, with NaN in every ring the contract says is not read, negative BN scales on a third of the channels, and
@@ -54,3 +55,23 @@ def test_stem_sweep(pkg, knobs, torch_dev):
 
 def test_head_sweep(pkg, knobs, torch_dev):
     SC.run_sweep("avgpool_fc", SC.head_case, pkg, knobs, torch_dev, 900)
+
+
+def test_dilated_3x3_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("conv3x3_dilated_bn_relu", SC.dilated_case, pkg, knobs, torch_dev, SC.SEEDS["conv3x3_dilated_bn_relu"])
+
+
+def test_dilated_block_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("dilated_block", SC.dilated_block_case, pkg, knobs, torch_dev, SC.SEEDS["dilated_block"])
+
+
+def test_conv1x1_cat_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("conv1x1_cat_bn", SC.cat_case, pkg, knobs, torch_dev, SC.SEEDS["conv1x1_cat_bn"])
+
+
+def test_aspp_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("aspp", SC.aspp_case, pkg, knobs, torch_dev, SC.SEEDS["aspp"])
+
+
+def test_resize_bilinear_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("resize_bilinear", SC.resize_case, pkg, knobs, torch_dev, SC.SEEDS["resize_bilinear"])

@@ -1,10 +1,16 @@
 """Host-side checks (no GPU) of the seeded shape sweeps in tests/shape_sweeps.py that tests/test_gpu_shape_sweeps.py
 runs: every drawn case is one the library accepts, in the form it was drawn for (so a GPU sweep never skips a shape or
 turns it into a WinoError), and the draws of each entry point reach the corners they exist for.  A generator edit that
-loses a corner fails here and names it."""
+loses a corner fails here and names it.  For the segmentation entries the conditions their GPU sweeps lean on are proven
+here on the fp64 references of the very tensors the sweeps draw: ASPP's pooled branch carries weight in every image of
+every case, and the label gap rule leaves out at most 1 % of any resize case's pixels."""
+import numpy as np
 import pytest
 
+import resize_cases as RC
 import shape_sweeps as S
+import sweep_cases as SC
+from cases import TIGHT
 
 ENTRIES = sorted(S.GENERATORS)
 
@@ -33,6 +39,9 @@ def test_every_drawn_case_is_legal(entry, pkg, knobs):
         assert bad is None, f"{c.tag()}: the planner does not take the forced form: {bad}"
         for name, n in S.sizes(pkg, c).items():
             assert n > 0, f"{c.tag()}: size query {name} is 0 (a shape the library refuses)"
+    if entry in SC.SEEDS:   # the segmentation entries: all references of a sweep together stay in seconds
+        total = sum(S.macs(c) for c in cases)
+        assert total < S.MAX_SUM_MACS, f"{entry}: {total:.2e} multiply-adds in all"
 
 
 def _map_hw(c):
@@ -45,6 +54,8 @@ def _map_hw(c):
         return ((s["Hin"] - 1) // st + 1, (s["Win"] - 1) // st + 1), (s["Hin"], s["Win"])
     if c.entry == "stem":
         return S.stem_out(s["H"], s["W"]), (s["H"], s["W"])
+    if c.entry == "resize_bilinear":
+        return (s["Ho"], s["Wo"]), (s["h"], s["w"])
     return (s["H"], s["W"]), (s["H"], s["W"])
 
 
@@ -58,6 +69,10 @@ def _channels(c):
         "proj_block_v15": ([s.get("Cin")], [s.get("Cm"), s.get("C4")]),
         "stem": ([], [s.get("K")]),
         "avgpool_fc": ([s.get("C")], []),
+        "dilated_block": ([s.get("Cin")], [s.get("Cm"), s.get("C4")]),
+        "conv1x1_cat_bn": ([s.get("Cs")], [s.get("Kout")]),
+        "aspp": ([s.get("Cin")], [s.get("Cb"), s.get("Kout")]),
+        "resize_bilinear": ([], []),
     }.get(c.entry, ([s.get("C")], [s.get("K")]))
 
 
@@ -72,6 +87,11 @@ AUTO_FORMS = {
     "proj_block_v15": [{"latency", "tiled", "stream_k"}] * 3,
     "stem": [{"big", "small"}],
     "avgpool_fc": [{"latency", "stream_k"}],
+    "conv3x3_dilated_bn_relu": [{"tiled", "stream_k"}],
+    "dilated_block": [{"latency"}, {"tiled", "stream_k"}, {"latency", "tiled"}],
+    "conv1x1_cat_bn": [{"tiled", "stream_k"}],
+    "aspp": [{"tiled", "stream_k"}],          # (the join's form)
+    "resize_bilinear": [{"staged", "direct"}],
 }
 FORCED_FORMS = {
     "conv3x3_bn_add_relu": {"big_tail", "big_whole", "small"},
@@ -83,6 +103,11 @@ FORCED_FORMS = {
     "proj_block_v15": set(S.V15_FORMS),
     "stem": {"big", "small"},
     "avgpool_fc": set(S.HEAD_FORMS),
+    "conv3x3_dilated_bn_relu": set(S.DIL_FORMS),
+    "dilated_block": set(S.BLOCK_FORMS),
+    "conv1x1_cat_bn": set(S.DIL_FORMS),
+    "aspp": set(),
+    "resize_bilinear": set(),
 }
 FLAGS = {
     "conv3x3_bn_add_relu": ("relu", "in_place", "nonneg"),
@@ -94,7 +119,149 @@ FLAGS = {
     "proj_block_v15": ("nonneg",),
     "stem": ("padded",),
     "avgpool_fc": ("padded",),
+    "conv3x3_dilated_bn_relu": ("relu", "nonneg"),
+    "dilated_block": ("nonneg",),
+    "conv1x1_cat_bn": ("relu", "a_padded", "c_padded", "nonneg"),
+    "aspp": ("nonneg",),
+    "resize_bilinear": ("in_padded",),
 }
+
+
+def _dil_windows(c):
+    """(some tile's window is clipped at neither end, the whole tensor lies inside one tile's window) of a dilated case:
+    a tile's window reaches d (W + 3) padded pixels before its first row's centre pixel and behind its last row's."""
+    N, H, W, d = c.N, c.H, c.W, c.d
+    Wp, M = W + 2, N * H * W
+    img = (H + 2) * Wp
+    total, reach = N * img, d * (W + 3)
+
+    def ppix(m):
+        n, r = divmod(m, H * W)
+        y, x = divmod(r, W)
+        return n * img + (1 + y) * Wp + 1 + x
+
+    tiles = [(ppix(t), ppix(min(t + 111, M - 1))) for t in range(0, M, 112)]
+    neither = any(a > reach and total - 1 - b > reach for a, b in tiles)
+    whole = len(tiles) == 1 and tiles[0][0] <= reach and total - 1 - tiles[0][1] <= reach
+    return neither, whole
+
+
+def _sk(pkg, knobs, c, key):
+    """A count of plan_form's stream-K ranges of a forced-grid case (0 for every other case)."""
+    if not (c.knobs and "WINO_1X1_SK_GRID" in c.knobs):
+        return 0
+    return _with_knobs(knobs, c, lambda: S.plan_form(pkg, c))[key]
+
+
+CLASS_NAMES = ["d < min(H, W)", "W <= d < H", "H <= d < W", "d >= max(H, W)"]
+
+
+def _dilated_corners(cases, pkg, knobs):
+    got = {f"a dilation with {CLASS_NAMES[k]}": any(S.dil_class(c.H, c.W, c.d) == k for c in cases) for k in range(4)}
+    got["d = 1"] = any(c.d == 1 for c in cases)
+    got["the largest dilation a wide map (W >= 2000, H <= 3, C = 32) takes"] = any(
+        c.W >= 2000 and c.H <= 3 and c.C == 32 and c.d == S.largest_dilation(pkg, c.N, c.H, c.W, c.C, c.K) for c in cases)
+    got["H = 1 with W > d"] = any(c.H == 1 and c.W > c.d for c in cases)
+    got["W = 1 with H > d"] = any(c.W == 1 and c.H > c.d for c in cases)
+    got["a tile over three images (H*W < 38, N >= 3)"] = any(c.H * c.W < 38 and c.N >= 3 for c in cases)
+    got["C = 32"] = any(c.C == 32 for c in cases)
+    got["C / 32 odd and > 1"] = any(c.C // 32 > 1 and (c.C // 32) % 2 for c in cases)
+    got["C >= 512"] = any(c.C >= 512 for c in cases)
+    got["K = 320"] = any(c.K == 320 for c in cases)
+    got["a forced stream-K range boundary strictly inside a tap"] = any(_sk(pkg, knobs, c, "inside") for c in cases)
+    got["a forced stream-K range boundary exactly on a tap boundary"] = any(_sk(pkg, knobs, c, "between") for c in cases)
+    windows = [_dil_windows(c) for c in cases]
+    got["a tile's window clipped at neither end"] = any(w[0] for w in windows)
+    got["the whole tensor inside one window"] = any(w[1] for w in windows)
+    return got
+
+
+def _block_corners(cases):
+    got = {}
+    for proj in (False, True):
+        kind = "proj" if proj else "residual"
+        mine = [c for c in cases if c.proj == proj]
+        got[f"the {kind} block"] = bool(mine)
+        got[f"three reach classes of d for the {kind} block"] = len({S.dil_class(c.H, c.W, c.d) for c in mine}) >= 3
+        assert all(c.proj or c.Cin == c.C4 for c in mine)
+    got["Cm = 64"] = any(c.Cm == 64 for c in cases)
+    got["Cm % 128 != 0 and > 64"] = any(c.Cm % 128 and c.Cm > 64 for c in cases)
+    got["C4 % 128 != 0"] = any(c.C4 % 128 for c in cases)
+    return got
+
+
+def _cat_corners(cases, pkg, knobs):
+    got = {f"S = {n}": any(c.S == n for c in cases) for n in (2, 3, 5, 8)}
+
+    def source(c):
+        p = 2 if c.flags["a_padded"] else 0
+        return c.N * (c.H + p) * (c.W + p) * c.Cs
+
+    assert all(c.gap % 4 == 0 for c in cases)
+    got["a gap of 0"] = any(c.gap == 0 for c in cases)
+    got["a gap of 4 floats"] = any(c.gap == 4 for c in cases)
+    got["a gap larger than a source"] = any(c.gap > source(c) for c in cases)
+    got["Cs = 32"] = any(c.Cs == 32 for c in cases)
+    got["Cs / 32 odd and > 1"] = any(c.Cs // 32 > 1 and (c.Cs // 32) % 2 for c in cases)
+    got["Cs = 256"] = any(c.Cs == 256 for c in cases)
+    got["M % 112 == 0"] = any((c.N * c.H * c.W) % 112 == 0 for c in cases)
+    got["M % 112 != 0"] = any((c.N * c.H * c.W) % 112 for c in cases)
+    got["H*W = 1 with N >= 8"] = any(c.H * c.W == 1 and c.N >= 8 for c in cases)
+    got["1 < H*W < 112 with N >= 3"] = any(1 < c.H * c.W < 112 and c.N >= 3 for c in cases)
+    got["a forced stream-K range boundary strictly inside a source"] = any(_sk(pkg, knobs, c, "inside") for c in cases)
+    got["a forced stream-K range boundary exactly at a source boundary"] = any(_sk(pkg, knobs, c, "between") for c in cases)
+    return got
+
+
+def _aspp_corners(cases):
+    past = lambda c: [d >= max(c.H, c.W) for d in c.rates]
+    return {
+        "ascending rates": any(c.rates[0] < c.rates[1] < c.rates[2] for c in cases),
+        "non-ascending rates": any(c.rates[0] > c.rates[1] or c.rates[1] > c.rates[2] for c in cases),
+        "two equal rates": any(len(set(c.rates)) == 2 for c in cases),
+        "a rate >= the map on one branch only": any(sum(past(c)) == 1 for c in cases),
+        "all three rates >= the map": any(all(past(c)) for c in cases),
+        "H*W = 1": any(c.H * c.W == 1 for c in cases),
+        "N >= 3": any(c.N >= 3 for c in cases),
+        "Cin, Cb and Kout pairwise different": any(len({c.Cin, c.Cb, c.Kout}) == 3 for c in cases),
+        "Cb = 64": any(c.Cb == 64 for c in cases),
+        "Cb % 128 != 0 and > 64": any(c.Cb % 128 and c.Cb > 64 for c in cases),
+    }
+
+
+def _resize_corners(cases, pkg):
+    form = {id(c): S.plan_form(pkg, c)["form"] for c in cases}
+    down = lambda a, b: a > b          # an axis shrinks
+    far = lambda a, b: a > 4 * b       # ... by more than 4x
+    lds = any(c.C == c.ld == RC.smallest_direct_channels(pkg, c.h, c.w, c.Ho, c.Wo) and not far(c.h, c.Ho)
+              and not far(c.w, c.Wo) and form[id(c)] == "direct" for c in cases if c.C >= 64)
+    got = {
+        "a non-integer up-scale on both axes": any(c.Ho > c.h and c.Wo > c.w and c.Ho % c.h and c.Wo % c.w for c in cases),
+        "up on one axis and down on the other": any((c.Ho > c.h and down(c.w, c.Wo)) or (c.Wo > c.w and down(c.h, c.Ho))
+                                                    for c in cases),
+        "the identity": any((c.h, c.w) == (c.Ho, c.Wo) for c in cases),
+        "a down-scale in (1, 4] (staged)": any(form[id(c)] == "staged" and (down(c.h, c.Ho) or down(c.w, c.Wo)) for c in cases),
+        "a down-scale > 4 on exactly one axis (direct)": any(form[id(c)] == "direct" and far(c.h, c.Ho) != far(c.w, c.Wo)
+                                                             for c in cases),
+        "h = 1 or w = 1": any(1 in (c.h, c.w) for c in cases),
+        "Ho = 1 or Wo = 1": any(1 in (c.Ho, c.Wo) for c in cases),
+        "Wo < 4": any(c.Wo < 4 for c in cases),
+        "two x-segments of an odd Wo in (256, 520]": any(256 < c.Wo <= 520 and c.Wo % 2 and form[id(c)] == "staged"
+                                                         for c in cases),
+        "Ho % 8 != 0 with Ho > 8": any(c.Ho % 8 and c.Ho > 8 for c in cases),
+        "Wo > 256 in the direct form": any(c.Wo > 256 and form[id(c)] == "direct" for c in cases),
+        "C = 1": any(c.C == 1 for c in cases),
+        "C % 4 != 0": any(c.C % 4 for c in cases),
+        "C == ld": any(c.C == c.ld for c in cases),
+        "ld >= C + 8": any(c.ld >= c.C + 8 for c in cases),
+        "direct because no block fits in LDS": lds,
+        "N >= 3": any(c.N >= 3 for c in cases),
+    }
+    for r in (1, 2, 3):
+        got[f"Wo % 4 = {r}"] = any(c.Wo % 4 == r for c in cases)
+    for use in ("out", "labels", "both"):
+        got[f"outputs: {use}"] = any(c.outputs == use for c in cases)
+    return got
 
 
 def _corners(entry, cases, pkg, knobs):
@@ -128,6 +295,16 @@ def _corners(entry, cases, pkg, knobs):
     if entry == "proj_block":
         got["stride 1"] = any(c.stride == 1 for c in cases)
         got["stride 2"] = any(c.stride == 2 for c in cases)
+    if entry == "conv3x3_dilated_bn_relu":
+        got.update(_dilated_corners(cases, pkg, knobs))
+    if entry == "dilated_block":
+        got.update(_block_corners(cases))
+    if entry == "conv1x1_cat_bn":
+        got.update(_cat_corners(cases, pkg, knobs))
+    if entry == "aspp":
+        got.update(_aspp_corners(cases))
+    if entry == "resize_bilinear":
+        got.update(_resize_corners(cases, pkg))
     if entry == "conv3x3_s2_proj":
         got["a stream-K range boundary inside the centre tap"] = any(
             c.knobs and _with_knobs(knobs, c, lambda: S.centre_tap_split(pkg, c)) for c in cases)
@@ -149,3 +326,34 @@ def test_draws_cover_the_corners(entry, pkg, knobs):
     got = _corners(entry, S.GENERATORS[entry](), pkg, knobs)
     missing = sorted(k for k, v in got.items() if not v)
     assert not missing, f"{entry}: the draws miss {missing}"
+
+
+def _host_sweep(pkg, case, seed):
+    """The tensors the GPU sweep draws for the case, on the host."""
+    import torch
+    return SC.Sweep(torch, "cpu", case, pkg, seed)
+
+
+def test_aspp_pooled_branch_matters_in_every_case(pkg):
+    """A dropped or misplaced per-image bias cannot pass the sweep: in every image of every drawn case the reference
+    without the pooled branch is more than 100 x TIGHT (relative to max|full|) away from the full one."""
+    for i, c in enumerate(S.GENERATORS["aspp"]()):
+        P = SC.AsppProblem(_host_sweep(pkg, c, SC.SEEDS["aspp"] + i), c)
+        full, without = P.reference(True), P.reference(False)
+        share = [float(np.abs(full[n] - without[n]).max() / np.abs(full).max()) for n in range(c.N)]
+        assert min(share) > 100 * TIGHT, f"{c.tag()}: pooled share per image {share}"
+        assert (full > 0).mean() > 0.05 and (full == 0).any(), f"{c.tag()}: the final ReLU sees one side only"
+
+
+def test_resize_label_rule_leaves_out_at_most_one_percent(pkg):
+    """The gap rule of resize_cases.check_labels on the reference of every drawn case: the GPU sweep's label check
+    covers at least 99 % of each case's pixels."""
+    worst = 0.0
+    for i, c in enumerate(S.GENERATORS["resize_bilinear"]()):
+        src = SC.resize_src(_host_sweep(pkg, c, SC.SEEDS["resize_bilinear"] + i), c)
+        want = RC.resize_reference(src.numpy(), c.Ho, c.Wo, c.C, c.flags["in_padded"])
+        assert want.shape == (c.N, c.C, c.Ho, c.Wo) and np.isfinite(want).all(), c.tag()   # no NaN column or ring is read
+        left = 1.0 - RC.decided(want, TIGHT * np.abs(want).max()).mean()
+        worst = max(worst, left)
+        assert left <= 0.01, f"{c.tag()}: the gap rule leaves out {left:.3%} of the pixels"
+    print(f"resize sweep: the gap rule leaves out at most {worst:.4%} of a case's pixels")
