@@ -808,6 +808,12 @@ def conv3x3_grouped_bn_relu(inp: torch.Tensor, packed: torch.Tensor, bn_bias: to
     return out
 
 
+def conv3x3_grouped_plan(N: int, Hin: int, Win: int, C: int, groups: int, stride: int = 1):
+    """(tile_w, kc, tiles_y, tiles_x) of conv3x3_grouped_bn_relu's launch for this shape (host-side): the tile width
+    and contraction width of the kernel instantiation, and the tiles of one image."""
+    return _plan_query("wino_conv3x3_grouped_plan", 4, int(N), int(Hin), int(Win), int(C), int(groups), int(stride))
+
+
 def grouped_residual_block_prepare(N: int, H: int, W: int, C4: int, Cm: int, groups: int) -> None:
     """Allocate the scratch of grouped_residual_block's two 1x1 launches for the current stream (before graph capture)."""
     _prepare("wino_grouped_residual_block_prepare_hw", N, H, W, C4, Cm, groups)

@@ -146,6 +146,7 @@ SIGNATURES = {
     "wino_conv3x3_grouped_filter_elems": (sz, [i] * 2),
     "wino_conv3x3_grouped_filter_pack": (i, [vp] * 2 + [i] * 2 + [vp]),
     "wino_conv3x3_grouped_bn_relu_hw": (i, [vp] * 5 + [i] * 7 + [vp]),
+    "wino_conv3x3_grouped_plan": (i, [i] * 6 + [ip] * 4),
     "wino_grouped_residual_block_hw": (i, [vp] * 11 + [i] * 6 + [vp, sz, vp]),
     "wino_grouped_residual_block_prepare_hw": (i, [i] * 6 + [vp]),
     "wino_grouped_proj_block_hw": (i, [vp] * 9 + [i] * 8 + [vp, sz, vp]),

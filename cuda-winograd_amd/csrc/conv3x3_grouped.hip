@@ -262,6 +262,18 @@ int wino_conv3x3_grouped_filter_pack(const float* w, float* packed, int C, int g
   return launch_status("grouped_pack_kernel");
 }
 
+int wino_conv3x3_grouped_plan(int N, int Hin, int Win, int C, int groups, int stride, int* tile_w, int* kc,
+                              int* tiles_y, int* tiles_x) {
+  if (!tile_w || !kc || !tiles_y || !tiles_x) {
+    set_error("NULL pointer");
+    return WINO_E_ARG;
+  }
+  GroupedGeom g;
+  if (int rc = check_grouped(N, Hin, Win, C, groups, stride, &g)) return rc;
+  *tile_w = g.TW, *kc = g.KC, *tiles_y = g.tiles_y, *tiles_x = g.tiles_x;
+  return WINO_OK;
+}
+
 int wino_conv3x3_grouped_bn_relu_hw(const float* in, const float* packed, const float* bnBias, const float* bnScale,
                                     float* out, int N, int Hin, int Win, int C, int groups, int stride, int relu,
                                     wino_stream_t s) {

@@ -65,7 +65,7 @@ extern "C" {
  * wino_conv3x3_dilated_prepare_hw, wino_conv3x3_dilated_plan, wino_dilated_residual_block_hw,
  * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
- * wino_aspp_prepare_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -586,6 +586,12 @@ int wino_avgpool7_flatten_hw(const float* feat, float* out, int N, int H, int W,
  * WINO_E_ARG.  Any N: every image is addressed from its own 64-bit base, and one padded input image must stay below
  * 2^31 elements (WINO_E_SHAPE).  in and out must not overlap (WINO_E_ARG).  One launch, an implicit GEMM on the f32 MFMA
  * (exact f32; there is no bf16 path); no stream scratch, so there is no prepare.  BN stays in its two vectors.
+ * wino_conv3x3_grouped_plan (host only) answers the launch the layer takes, a function of the shape alone, from the
+ * geometry the launcher itself reads: the kernel is one body compiled for stride x tile width x contraction width, with
+ *   tile_w   8 or 16 output columns per workgroup tile, whichever pads the output row by less
+ *   kc       16, 32 or 64 input channels per 16-channel column tile: max(Cg, 16)
+ *   tiles_y, tiles_x   the tiles of one image; a tile is (stride 1: 4, stride 2: 2) * 16 / tile_w rows high
+ * and returns what the layer would for the shape (WINO_E_SHAPE / WINO_E_ARG, WINO_E_ARG for a NULL pointer).
  *
  * wino_grouped_residual_block_hw: wino_residual_block_hw with this layer in the middle (wg from
  * wino_conv3x3_grouped_filter_pack(Cm, groups)); x, out [N][H][W][C4].
@@ -604,6 +610,8 @@ int wino_conv3x3_grouped_filter_pack(const float* w, float* packed, int C, int g
 int wino_conv3x3_grouped_bn_relu_hw(const float* in, const float* packed, const float* bnBias, const float* bnScale,
                                     float* out, int N, int Hin, int Win, int C, int groups, int stride, int relu,
                                     wino_stream_t s);
+int wino_conv3x3_grouped_plan(int N, int Hin, int Win, int C, int groups, int stride, int* tile_w, int* kc,
+                              int* tiles_y, int* tiles_x);
 int wino_grouped_residual_block_hw(const float* x, const float* w1, const float* bn1Bias, const float* bn1Scale,
                                    const float* wg, const float* bn2Bias, const float* bn2Scale, const float* w3,
                                    const float* bn3Bias, const float* bn3Scale, float* out, int N, int H, int W, int C4,

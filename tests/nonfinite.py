@@ -905,7 +905,8 @@ def layers_s2(torch):
     yield ConvS2(torch, True, True, *S2_SHAPE, seed=3003)
 
 
-SHAPES_GROUPED = [(3, 7, 5), (3, 9, 8)]
+# 7x5 and 9x8 take 8-wide tiles at both strides; 6x12 takes 16-wide tiles at stride 1 and 5x20 (10 wide out) at stride 2
+SHAPES_GROUPED = [(3, 7, 5), (3, 9, 8), (3, 6, 12), (3, 5, 20)]
 
 
 def layers_grouped(torch, N, H, W):

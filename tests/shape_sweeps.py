@@ -1,5 +1,6 @@
-"""Seeded random-shape generators for the ResNet entry points and the segmentation path (the dilated 3x3 layer and its
-bottleneck blocks, the concat projection, ASPP, the bilinear resize), shared by tests/test_shape_sweeps_host.py (every case is
+"""Seeded random-shape generators for the ResNet entry points, the grouped 3x3 layer and the two ResNeXt blocks, and the
+segmentation path (the dilated 3x3 layer and its bottleneck blocks, the concat projection, ASPP, the bilinear resize),
+shared by tests/test_shape_sweeps_host.py (every case is
 legal and the draws reach the corners they claim, no GPU) and tests/test_gpu_shape_sweeps.py (every case against an
 fp64 reference on an MI355X).
 
@@ -90,6 +91,14 @@ def macs(case: Case) -> float:
         return px * (28.0 * s["Cin"] * s["Cb"] + 5.0 * s["Cb"] * s["Kout"]) + s["N"] * s["Cb"] * (s["Cin"] + s["Kout"])
     if e == "resize_bilinear":
         return 4.0 * s["N"] * s["C"] * s["Ho"] * s["Wo"]
+    if e == "conv3x3_grouped_bn_relu":
+        H, W = grouped_out(s["Hin"], s["Win"], s["stride"])
+        return 9.0 * s["N"] * H * W * s["C"] * (s["C"] // s["groups"])
+    if e == "grouped_block":
+        H, W = grouped_out(s["Hin"], s["Win"], s["stride"])
+        px = float(s["N"]) * H * W
+        return (float(s["N"]) * s["Hin"] * s["Win"] * s["Cin"] * s["Cm"] + px * 9.0 * s["Cm"] * (s["Cm"] // s["groups"])
+                + px * (s["Cm"] + (s["Cin"] if s["proj"] else 0)) * s["C4"])
     raise KeyError(e)
 
 
@@ -601,7 +610,119 @@ def resize_cases():
     return cases
 
 
+# ---- the grouped 3x3 and the two ResNeXt blocks ------------------------------------------------------------------------
+GROUPED_CGS = (4, 8, 16, 32, 64)
+# rows of a workgroup's output tile, by (stride, tile width): wino_conv3x3_grouped_plan names the width, the kernel's
+# header comment (conv3x3_grouped.hip) the rows: four 16-pixel row tiles at stride 1, two at stride 2
+GROUPED_TILE_H = {(1, 16): 4, (1, 8): 8, (2, 16): 2, (2, 8): 4}
+
+
+def grouped_out(Hin, Win, stride):
+    return (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+
+
+def grouped_form(pkg, N, Hin, Win, C, groups, stride):
+    """The kernel instantiation of the grouped layer, by name, and the plan query's four answers."""
+    tw, kc, ty, tx = pkg.conv3x3_grouped_plan(N, Hin, Win, C, groups, stride)
+    return {"form": f"s{stride}_tw{tw}_kc{kc}", "tw": tw, "kc": kc, "tiles_y": ty, "tiles_x": tx}
+
+
+def _grouped_map(r, stride, tw, pin, k):
+    """(Hin, Win) whose output takes `tw`-wide tiles.  pin["many"]: at least two tiles down and across, the last ones
+    exactly full (pin["full"]) or clipped; pin["H"] / pin["W"] / pin["Hin"] / pin["Win"]: that size; k: two bits, the
+    parities of a stride-2 input."""
+    oh = GROUPED_TILE_H[(stride, tw)]
+    if pin.get("many"):
+        lo, hi = (17, 24) if tw == 8 else (25, 32)     # (9 .. 16 wide takes one 16-wide tile, not two 8-wide ones)
+        rows = int(r.randint(2, 4))
+        W = hi if pin.get("full") else int(r.randint(lo, hi))
+        H = rows * oh if pin.get("full") else (rows - 1) * oh + int(r.randint(1, oh))
+    else:
+        lo, hi = (1, 8) if tw == 8 else (9, 16)
+        W, H = int(r.randint(lo, hi + 1)), int(r.randint(1, 2 * oh + 2))
+    H, W = pin.get("H", H), pin.get("W", W)
+    if pin.get("odd"):
+        H, W = H | 1, W - 1 + W % 2
+    if stride == 1:
+        return H, W
+    return pin.get("Hin", 2 * H - 1 + (k & 1)), pin.get("Win", 2 * W - 1 + (k >> 1 & 1))
+
+
+# (stride, tile width, Cg, pins): every instantiation at least once, Cg = 4, 8, 16 (one select each) at both widths, and
+# per (stride, width) one map of full tiles and one of clipped ones, two or more down and across; one-line outputs,
+# a 1x1 output of a 2x2 input, the dense C = 64 layer, three channel blocks, three images
+GROUPED_ROWS = [
+    (1, 16, 4, {"many": True, "full": True}), (1, 16, 8, {"many": True}), (1, 16, 16, {"H": 1}),
+    (1, 16, 32, {"many": True, "N": 3, "C": 192}), (1, 16, 64, {"C": 64}),
+    (1, 8, 4, {"many": True, "full": True}), (1, 8, 8, {"many": True}), (1, 8, 16, {"W": 1}), (1, 8, 32, {"odd": True}),
+    (1, 8, 64, {"many": True, "C": 192}),
+    (2, 16, 4, {"many": True, "full": True}), (2, 16, 8, {"many": True}), (2, 16, 16, {"Hin": 2}),
+    (2, 16, 32, {"many": True, "N": 3}), (2, 16, 64, {"C": 256}),
+    (2, 8, 4, {"many": True, "full": True}), (2, 8, 8, {"many": True}), (2, 8, 16, {"Win": 1, "N": 4}), (2, 8, 32, {"C": 64}),
+    (2, 8, 64, {"C": 64, "Hin": 2, "Win": 2}),
+]
+
+
+def grouped_cases():
+    rng = np.random.RandomState(7171)
+    entry = "conv3x3_grouped_bn_relu"
+    cases = []
+    for i, (stride, tw, Cg, pin) in enumerate(GROUPED_ROWS):
+        Hin, Win = _grouped_map(rng, stride, tw, pin, i)
+        C = pin.get("C") or int(rng.choice([c for c in (64, 128, 192, 256) if c % Cg == 0]))
+        sh = {"N": pin.get("N") or int(rng.randint(1, 4)), "Hin": Hin, "Win": Win, "C": C, "groups": C // Cg, "stride": stride}
+        cases.append(Case(entry, sh, None, None, _flags(rng, i)))
+    for i in range(len(cases), len(cases) + 10):   # the whole envelope: whatever instantiation the shape takes
+        Cg = int(rng.choice(GROUPED_CGS))
+        C = 64 * int(rng.randint(1, 5))
+        sh = {"N": int(rng.randint(1, 5)), "Hin": int(rng.randint(1, 41)), "Win": int(rng.randint(1, 67)), "C": C,
+              "groups": C // Cg, "stride": int(rng.randint(1, 3))}
+        cases.append(Case(entry, sh, None, None, _flags(rng, i)))
+    return cases
+
+
+GBLOCK_FORMS = V15_FORMS
+# one pin per (Cg, block) draw, in the order the generator walks them
+GBLOCK_PINS = [{"H": 1}, {"W": 1}, {"odd": True}, {"Cm": 64}, {"Cm": 192}, {"C4": 192}, {"odd": True}, {"Cin": 96},
+               {"Cm": 64, "H": 1}, {"Cm": 192, "C4": 320}, {"Cin": 160, "Cm": 128, "C4": 320}, {"W": 1}, {"Cm": 64}, {"N": 3},
+               {"Cm": 192}]
+# (N, Hin, Win, Cin, Cm, C4, groups, stride, proj): both 1x1 launches in the forced form
+GBLOCK_FORCED = [
+    ((2, 12, 12, 256, 128, 256, 32, 1, False), "stream_k"), ((3, 10, 12, 128, 128, 256, 16, 1, True), "stream_k"),
+    ((2, 19, 24, 128, 64, 256, 4, 2, True), "stream_k"), ((2, 9, 9, 256, 64, 256, 2, 1, False), "tiled"),
+    ((1, 7, 11, 128, 64, 192, 1, 2, True), "tiled"),
+]
+GBLOCK_KEYS = ("N", "Hin", "Win", "Cin", "Cm", "C4", "groups", "stride", "proj")
+
+
+def grouped_block_cases():
+    rng = np.random.RandomState(7272)
+    entry = "grouped_block"
+    cases = []
+    for i, (Cg, (proj, stride)) in enumerate((Cg, kind) for Cg in GROUPED_CGS for kind in ((False, 1), (True, 1), (True, 2))):
+        pin = GBLOCK_PINS[i]
+        tw = 8 if pin.get("W") == 1 else (8, 16)[i % 2]
+        for _ in range(4000):
+            Hin, Win = _grouped_map(rng, stride, tw, pin, i)
+            Cm = pin.get("Cm") or int(rng.choice([c for c in (64, 128, 192, 256) if c % Cg == 0]))
+            C4 = pin.get("C4") or 64 * int(rng.randint(1, 6))
+            Cin = (pin.get("Cin") or 32 * int(rng.randint(1, 9))) if proj else C4
+            if not proj or len({Cin, Cm, C4}) == 3:
+                break
+        sh = {"N": pin.get("N") or int(rng.randint(1, 4)), "Hin": Hin, "Win": Win, "Cin": Cin, "Cm": Cm, "C4": C4,
+              "groups": Cm // Cg, "stride": stride, "proj": proj}
+        cases.append(Case(entry, sh, None, None, {"nonneg": bool(i % 3 == 1)}))
+    # the automatic whole-tile form of the last 1x1 launch: a batch past its latency form
+    cases.append(Case(entry, dict(zip(GBLOCK_KEYS, (8, 20, 21, 64, 64, 320, 16, 1, True))), None, None, {"nonneg": True}))
+    for shape, form in GBLOCK_FORCED:
+        cases.append(Case(entry, dict(zip(GBLOCK_KEYS, shape)), dict(GBLOCK_FORMS[form]), form,
+                          {"nonneg": bool(len(cases) % 3 == 1)}))
+    return cases
+
+
 GENERATORS = {
+    "conv3x3_grouped_bn_relu": grouped_cases,
+    "grouped_block": grouped_block_cases,
     "conv3x3_dilated_bn_relu": dilated_cases,
     "dilated_block": dilated_block_cases,
     "conv1x1_cat_bn": cat_cases,
@@ -697,6 +818,17 @@ def plan_form(pkg, case, cus=CUS):
             pkg.conv3x3_dilated_plan(s["N"], s["H"], s["W"], s["Cin"], s["Cb"], d, cus)
         form_1x1(pkg, s["N"] * s["H"] * s["W"], s["Cin"], s["Cb"], cus)
         return {"form": FORM_NAMES[pkg.conv1x1_cat_plan(s["N"], s["H"], s["W"], 4, s["Cb"], s["Kout"], cus)]}
+    if e == "conv3x3_grouped_bn_relu":
+        return grouped_form(pkg, s["N"], s["Hin"], s["Win"], s["C"], s["groups"], s["stride"])
+    if e == "grouped_block":   # the first 1x1 at the full input, the grouped 3x3 at the stride, the last 1x1 / the tail
+        H, W = grouped_out(s["Hin"], s["Win"], s["stride"])
+        first = form_1x1(pkg, s["N"] * s["Hin"] * s["Win"], s["Cin"], s["Cm"], cus)
+        mid = grouped_form(pkg, s["N"], s["Hin"], s["Win"], s["Cm"], s["groups"], s["stride"])
+        if s["proj"]:
+            tail = FORM_NAMES[pkg.proj_tail_plan(s["N"], s["Hin"], s["Win"], s["Cin"], s["Cm"], s["C4"], s["stride"], cus)[1]]
+        else:
+            tail = form_1x1(pkg, s["N"] * H * W, s["Cm"], s["C4"], cus)
+        return {"form": f"{first}/{mid['form']}/{tail}", "first": first, "mid": mid, "tail": tail}
     if e == "resize_bilinear":
         form = pkg.resize_bilinear_plan(s["h"], s["w"], s["C"], s["ld"], s["Ho"], s["Wo"], s["outputs"] != "labels",
                                         s["outputs"] != "out")
@@ -749,6 +881,8 @@ def check_forced(case, plan) -> str | None:
     if e == "dilated_block":
         ok = (plan["first"], plan["mid"], plan["tail"]) == (f, f, f)
         return None if ok else f"want {f} for all three launches, plan {plan}"
+    if e == "grouped_block":   # (the grouped 3x3 has one form per shape: nothing to force)
+        return None if (plan["first"], plan["tail"]) == (f, f) else f"want {f} for both 1x1 launches, plan {plan}"
     raise KeyError(e)
 
 
@@ -787,11 +921,31 @@ def sizes(pkg, case) -> dict:
         if s["proj"]:
             d["tail"] = L.wino_proj_tail_elems(s["Cm"], s["Cin"], s["C4"])
         return d
+    if e == "conv3x3_grouped_bn_relu":
+        return {"packed": L.wino_conv3x3_grouped_filter_elems(s["C"], s["groups"])}
+    if e == "grouped_block":
+        d = {"wg": L.wino_conv3x3_grouped_filter_elems(s["Cm"], s["groups"]), "workspace": grouped_block_workspace(pkg, case)[1]}
+        if s["proj"]:
+            d["tail"] = L.wino_proj_tail_elems(s["Cm"], s["Cin"], s["C4"])
+        return d
     if e == "aspp":
         return {"workspace": pkg.aspp_workspace_bytes(s["N"], s["H"], s["W"], s["Cin"], s["Cb"], s["Kout"])}
     if e in ("conv3x3_dilated_bn_relu", "conv1x1_cat_bn", "resize_bilinear"):
         return {}   # (no pack or workspace query of their own)
     raise KeyError(e)
+
+
+def grouped_block_workspace(pkg, case):
+    """(the dense block's size query that sizes the grouped block's workspace, its answer)."""
+    s, L = case.shape, pkg.lib()
+    H, W = grouped_out(s["Hin"], s["Win"], s["stride"])
+    if not s["proj"]:
+        query, args = "wino_residual_block_workspace_bytes_hw", (s["N"], s["Hin"], s["Win"], s["Cm"])
+    elif s["stride"] == 1:
+        query, args = "wino_proj_block_workspace_bytes_hw", (s["N"], H, W, s["Cm"])
+    else:
+        query, args = "wino_proj_block_v15_workspace_bytes_hw", (s["N"], s["Hin"], s["Win"], s["Cm"])
+    return query, getattr(L, query)(*args)
 
 
 def sk_ranges(pkg, M, Cin, Kout, unit, cus=CUS) -> dict:

@@ -22,7 +22,7 @@ WORST = {}                       # the largest relative error close() saw, by en
 # the first seed of the segmentation entries' sweeps (case i takes seed + i): tests/test_shape_sweeps_host.py rebuilds
 # the same tensors for the conditions it proves on the references
 SEEDS = {"conv3x3_dilated_bn_relu": 1000, "dilated_block": 1100, "conv1x1_cat_bn": 1200, "aspp": 1300,
-         "resize_bilinear": 1400}
+         "resize_bilinear": 1400, "conv3x3_grouped_bn_relu": 1500, "grouped_block": 1600}
 
 
 @contextlib.contextmanager
@@ -392,6 +392,66 @@ def v15_case(pkg, knobs, torch_dev, case, seed):
         outs = [pkg.proj_block_v15(B.xd, B.w1d, B.bnd[0], taps, B.bnd[1], B.tail, out=sw.nan(case.N, H, W, case.C4),
                                    workspace=sw.ws(need, "wino_proj_block_v15_workspace_bytes_hw")) for _ in range(2)]
         sw.close(outs[0], want.permute(0, 2, 3, 1))
+        sw.same(outs[0], outs[1])
+
+
+# ---- the grouped 3x3 and the ResNeXt blocks ----------------------------------------------------------------------------
+def grouped_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    N, Hin, Win, C, groups, stride, relu = case.N, case.Hin, case.Win, case.C, case.groups, case.stride, case.flags["relu"]
+    H, W = S.grouped_out(Hin, Win, stride)
+    x = sw.padded(sw.act(N, Hin, Win, C))          # the ring is read: zero, as the contract says
+    w, bn = sw.conv_w(C, C // groups), sw.bn(C)
+    pre = sw.affine(sw.F.conv2d(sw.nchw(x[:, 1:-1, 1:-1, :]), w.double(), stride=stride, padding=1, groups=groups), bn)
+    if relu:
+        sw.both_sides(pre)
+    want = (sw.torch.relu(pre) if relu else pre).permute(0, 2, 3, 1)
+    elems = pkg.lib().wino_conv3x3_grouped_filter_elems(C, groups)
+    for _ in sw.passes():
+        xd = sw.d(x, "x")
+        packed = sw.packed(pkg.filter_pack_grouped, elems, "packed", sw.d(w, "w"), groups)
+        assert packed.numel() == elems, sw.tag
+        bd, sd = sw.bnd(bn)
+        outs = [pkg.conv3x3_grouped_bn_relu(xd, packed, bd, sd, groups, stride=stride, relu=relu,
+                                            out=sw.nan(N, H + 2, W + 2, C)) for _ in range(2)]
+        sw.ring_is(outs[0], 0.0)
+        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
+        sw.same(outs[0], outs[1])
+
+
+def grouped_block_case(pkg, knobs, torch_dev, case, seed):
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    N, Hin, Win, Cin, Cm, C4 = case.N, case.Hin, case.Win, case.Cin, case.Cm, case.C4
+    groups, stride, proj = case.groups, case.stride, case.proj
+    H, W = S.grouped_out(Hin, Win, stride)
+    x = sw.act(N, Hin, Win, Cin)
+    w11 = lambda i, o, gain: (sw.rand(i, o) - 0.5) / np.sqrt(i) * gain
+    w1, wg, w3, wp = w11(Cin, Cm, 4), sw.conv_w(Cm, Cm // groups), w11(Cm, C4, 4), w11(Cin, C4, 2)
+    bn = [sw.bn(c) for c in (Cm, Cm, C4, C4)]
+    xi = sw.nchw(x)
+    t1 = sw.torch.relu(sw.affine(sw.conv1x1(xi, w1), bn[0]))
+    t2 = sw.torch.relu(sw.affine(sw.F.conv2d(t1, wg.double(), stride=stride, padding=1, groups=groups), bn[1]))
+    pre = sw.affine(sw.conv1x1(t2, w3), bn[2]) + (sw.affine(sw.conv1x1(xi, wp, stride=stride), bn[3]) if proj else xi)
+    sw.both_sides(pre)
+    want = sw.torch.relu(pre).permute(0, 2, 3, 1)
+    L = pkg.lib()
+    query, need = S.grouped_block_workspace(pkg, case)
+    for _ in sw.passes():
+        xd, w1d = sw.d(x, "x"), sw.d(w1, "w1")
+        bnd = [sw.bnd(b, f"bn{i}") for i, b in enumerate(bn[:3 + proj])]
+        wgd = sw.packed(pkg.filter_pack_grouped, L.wino_conv3x3_grouped_filter_elems(Cm, groups), "wg", sw.d(wg, "wg.w"),
+                        groups)
+        if proj:
+            tail = sw.packed(pkg.proj_tail_pack, L.wino_proj_tail_elems(Cm, Cin, C4), "tail", sw.d(w3, "w3"), bnd[2],
+                             sw.d(wp, "wp"), bnd[3])
+            run = lambda: pkg.grouped_proj_block(xd, w1d, bnd[0], wgd, bnd[1], tail, groups, stride,
+                                                 out=sw.nan(N, H, W, C4), workspace=sw.ws(need, query))
+        else:
+            w3d = sw.d(w3, "w3")
+            run = lambda: pkg.grouped_residual_block(xd, w1d, bnd[0], wgd, bnd[1], w3d, bnd[2], groups,
+                                                     out=sw.nan(N, H, W, C4), workspace=sw.ws(need, query))
+        outs = [run(), run()]
+        sw.close(outs[0], want)
         sw.same(outs[0], outs[1])
 
 

@@ -91,20 +91,54 @@ def test_layer_past_one_tile_in_every_direction(Cg, stride, pkg, torch_dev):
         _layer_case(pkg, torch_dev, 3, 29, 23, 192, Cg, stride, True, align)
 
 
+# the smallest maps with two tiles down and across and clipped last tiles, by (stride, tile width): (Hin, Win)
+TWO_TILE_MAPS = {(1, 16): (5, 25), (1, 8): (9, 17), (2, 16): (5, 49), (2, 8): (9, 33)}
+
+
+@pytest.mark.parametrize("KC", [16, 32, 64])
+@pytest.mark.parametrize("TW", [8, 16])
+@pytest.mark.parametrize("stride", [1, 2])
+def test_every_instantiation_past_one_tile(stride, TW, KC, pkg, torch_dev):
+    """Each conv3x3_grouped_kernel<stride, TW, KC> by name, N = 2, C = 128 (two channel blocks): the plan query says that
+    the shape takes it, with at least two tiles down and across and both last tiles clipped.  KC = 16 serves Cg = 4, 8
+    and 16, each with a select of its own."""
+    Hin, Win = TWO_TILE_MAPS[(stride, TW)]
+    H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    tile_h = (4 if stride == 1 else 2) * 16 // TW
+    for i, Cg in enumerate((4, 8, 16) if KC == 16 else (KC,)):
+        tw, kc, tiles_y, tiles_x = pkg.conv3x3_grouped_plan(2, Hin, Win, 128, 128 // Cg, stride)
+        assert (tw, kc) == (TW, KC) and tiles_y >= 2 and tiles_x >= 2, (tw, kc, tiles_y, tiles_x)
+        assert tiles_y == -(-H // tile_h) and H % tile_h and W % TW
+        for j, align in enumerate(guarded.ALIGNS):
+            _layer_case(pkg, torch_dev, 2, Hin, Win, 128, Cg, stride, bool((i + j) % 2), align)
+
+
+# (Hin, Win) by stride: 8-wide tiles at both strides, 16-wide tiles at both
+ONE_HOT_MAPS = {8: {1: (7, 5), 2: (7, 5)}, 16: {1: (6, 12), 2: (5, 20)}}
+
+
 @pytest.mark.parametrize("Cg", CGS)
 def test_one_hot_weights_do_not_leak_across_groups(Cg, pkg, torch_dev):
     """One non-zero tap from one input channel of one group: every output channel outside that group is exactly
     act(bias) -- a filter value packed off the block diagonal, or a column tile contracting over a neighbour's
-    channels, shows here, where random weights would hide it below the tolerance."""
+    channels, shows here, where random weights would hide it below the tolerance.  In the 8-wide and in the 16-wide
+    instantiations of both strides."""
+    for tw, maps in ONE_HOT_MAPS.items():
+        _one_hot(pkg, torch_dev, Cg, tw, maps)
+
+
+def _one_hot(pkg, torch_dev, Cg, tw, maps):
     torch, _ = torch_dev
-    C, N, Hin, Win = 128, 2, 7, 5
+    C, N = 128, 2
     groups = C // Cg
-    x, _, bias, scale = _layer_inputs(torch, N, Hin, Win, C, Cg, seed=77 + Cg)
+    inputs = {stride: _layer_inputs(torch, N, *maps[stride], C, Cg, seed=77 + Cg) for stride in (1, 2)}
     for i, (grp, cl, tap) in enumerate(((0, 0, 4), (groups - 1, Cg - 1, 0), (groups // 2, Cg // 2, 8), (1 % groups, 1, 5))):
         for stride, relu in ((1, False), (2, True)):
+            x, _, bias, scale = inputs[stride]
+            assert pkg.conv3x3_grouped_plan(N, *maps[stride], C, groups, stride)[0] == tw
             w = torch.zeros(C, Cg, 3, 3)
             w[grp * Cg:(grp + 1) * Cg, cl, tap // 3, tap % 3] = torch.arange(1, Cg + 1, dtype=torch.float32) / Cg
-            tag = f"one-hot Cg={Cg} group={grp} channel={cl} tap={tap} s={stride}"
+            tag = f"one-hot Cg={Cg} TW={tw} group={grp} channel={cl} tap={tap} s={stride}"
             got = _run_layer(pkg, torch_dev, x, w, bias, scale, groups, stride, relu, guarded.ALIGNS[i % 2], tag)
             want = _layer_reference(torch, x, w, bias, scale, groups, stride, relu)
             inside = torch.zeros(C, dtype=torch.bool)

@@ -625,6 +625,114 @@ def test_conv1x1_cat_at_the_descriptor_edge(S, pkg, O, torch_dev, free_after):
     del buf, views, out
 
 
+# ------------------------------------------------------------------ the grouped 3x3 (64-bit image bases, 32-bit offsets inside)
+def _grouped_weights(torch, dev, pkg, C, groups, seed):
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    Cg = C // groups
+    w = (torch.rand(C, Cg, 3, 3, generator=g) - 0.5) / np.sqrt(9 * Cg) * 4
+    bias, scale = torch.rand(C, generator=g) - 0.5, torch.rand(C, generator=g) + 0.5
+    return w, bias, scale, pkg.filter_pack_grouped(w.to(dev), groups), bias.to(dev), scale.to(dev)
+
+
+def _grouped_reference(torch, x_padded, w, bias, scale, groups, stride):
+    """fp64 on the CPU of padded NHWC rows (their zero ring is the padding): [n][H][W][C], after the ReLU."""
+    y = torch.nn.functional.conv2d(x_padded.permute(0, 3, 1, 2).double(), w.double(), stride=stride, groups=groups)
+    y = y * scale.double()[None, :, None, None] + bias.double()[None, :, None, None]
+    return torch.relu(y).permute(0, 2, 3, 1).numpy()
+
+
+# (stride, Hin, Win, C, groups, N, tile width): 8-wide tiles at stride 1, 16-wide at stride 2
+GROUPED_BATCHES = [(1, 6, 7, 128, 4, 116600, 8), (2, 3, 19, 64, 16, 349600, 16)]
+
+
+@pytest.mark.parametrize("stride,Hin,Win,C,groups,N,tw", GROUPED_BATCHES, ids=["s1_tw8", "s2_tw16"])
+def test_grouped_3x3_batch_beyond_4gib(stride, Hin, Win, C, groups, N, tw, pkg, O, torch_dev, free_after):
+    """conv3x3_grouped_bn_relu over a batch of small images: 116600 of 6x7x128 at stride 1 (in and out 4.3 GB each),
+    349600 of 3x19x64 at stride 2 (in 9.4 GB, out 4.3 GB) -- input and output both cross 2^31 and 2^32 bytes, at images
+    of their own, so every workgroup's 64-bit re-basing of its image is exercised on both tensors."""
+    torch, dev = torch_dev
+    H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
+    Pin, Pout = (Hin + 2) * (Win + 2) * C * 4, (H + 2) * (W + 2) * C * 4
+    assert N * Pout > 1 << 32 and N * Pin > 1 << 32
+    assert pkg.conv3x3_grouped_plan(N, Hin, Win, C, groups, stride)[0] == tw
+    _need(torch, N * (Pin + Pout))
+    idx = _images(N, [Pin, Pout])
+    assert len(idx) >= 8
+    w, bias, scale, packed, bt, st = _grouped_weights(torch, dev, pkg, C, groups, 191 + stride)
+    x = _padded_rand(torch, dev, N, Hin, Win, C, 192 + stride)
+    want = _grouped_reference(torch, _pick(torch, x, idx), w, bias, scale, groups, stride)
+    out = torch.empty(N, H + 2, W + 2, C, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        got = pkg.conv3x3_grouped_bn_relu(x, packed, bt, st, groups, stride=stride, relu=True, out=out)
+        assert got.data_ptr() == out.data_ptr()
+        torch.cuda.synchronize()
+        g_idx = _check_padded(O, torch, out, idx, want, f"rep {rep}")
+        if first is None:
+            first = g_idx
+        assert torch.equal(g_idx, first)
+    assert 0.2 < (want > 0).mean() < 0.8
+    del x, out, got
+
+
+def _bands(rows, width=2):
+    """Sorted, merged [lo, hi] ranges of `width` rows on either side of each row of `rows`."""
+    out = []
+    for lo, hi in sorted((r - width, r + width) for r in rows):
+        if out and lo <= out[-1][1] + 1:
+            out[-1][1] = max(out[-1][1], hi)
+        else:
+            out.append([lo, hi])
+    return out
+
+
+def test_grouped_3x3_largest_accepted_image(pkg, O, torch_dev, free_after):
+    """conv3x3_grouped_bn_relu on the largest image the layer accepts: 5790 x 5790 x 64 at stride 2, one padded image of
+    5792^2 * 64 = 2^31 - 458752 elements (8.6 GB; 5791 is refused, tests/test_grouped_host.py), out 2895 x 2895 (2.1 GB),
+    16-wide tiles.  The kernel's 32-bit offsets inside the image run to their limit.  Whole output rows against fp64, each
+    band a convolution of a few input rows: the first and the last rows, the rows that read the padded input rows in
+    which byte 2^31 and byte 2^32 of the input fall, and the output's own row at byte 2^31 -- the last columns of every
+    band (a clipped 16-wide tile) on their own as well."""
+    torch, dev = torch_dev
+    N, Hin, C, groups, stride = 1, 5790, 64, 16, 2
+    H = (Hin - 1) // stride + 1
+    in_row, out_row = (Hin + 2) * C * 4, (H + 2) * C * 4
+    assert (Hin + 2) ** 2 * C < 1 << 31 <= (Hin + 3) ** 2 * C
+    assert (Hin + 2) * in_row > 1 << 32 and (H + 2) * out_row > 1 << 31
+    tw, kc, tiles_y, tiles_x = pkg.conv3x3_grouped_plan(N, Hin, Hin, C, groups, stride)
+    assert (tw, kc) == (16, 16) and tiles_x >= 2 and H % tw
+    _need(torch, (Hin + 2) * in_row + (H + 2) * out_row)
+    # output rows: the ends; those whose three padded input rows 2 oy .. 2 oy + 2 hold a byte boundary of the input; the
+    # one at the output's byte 2^31 (padded output row r is output row r - 1)
+    rows = {0, H - 1}
+    for b in (1 << 31, 1 << 32):
+        rows.add(min(H - 1, (b // in_row) // 2))
+    rows.add(min(H - 1, max(0, (1 << 31) // out_row - 1)))
+    bands = [(max(0, lo), min(H - 1, hi)) for lo, hi in _bands(rows)]
+    assert 3 <= len(bands) <= 5 and sum(hi - lo + 1 for lo, hi in bands) <= 25
+    w, bias, scale, packed, bt, st = _grouped_weights(torch, dev, pkg, C, groups, 201)
+    x = _padded_rand(torch, dev, N, Hin, Hin, C, 202)
+    want = [_grouped_reference(torch, x[:, 2 * lo:2 * hi + 3].cpu(), w, bias, scale, groups, stride) for lo, hi in bands]
+    out = torch.empty(N, H + 2, H + 2, C, device=dev)
+    first = None
+    for rep in range(2):
+        out.fill_(NAN)
+        pkg.conv3x3_grouped_bn_relu(x, packed, bt, st, groups, stride=stride, relu=True, out=out)
+        torch.cuda.synchronize()
+        assert _finite(torch, out) and ring_zero(out), rep
+        got = [out[:, lo + 1:hi + 2, 1:-1, :].cpu() for lo, hi in bands]
+        for (lo, hi), g_, w_ in zip(bands, got, want):
+            assert g_.shape == w_.shape, (lo, hi)
+            assert O.rel_error(g_.numpy(), w_) < TIGHT, (rep, lo, hi)
+            assert O.rel_error(g_.numpy()[:, :, -tw:], w_[:, :, -tw:]) < TIGHT, (rep, lo, hi, "last columns")
+        if first is None:
+            first = got
+        assert all(torch.equal(a, b) for a, b in zip(got, first))
+    assert all(0.2 < (w_ > 0).mean() < 0.8 for w_ in want)
+    del x, out
+
+
 # ------------------------------------------------------------------ the largest filter matrix the 3x3 accepts
 def test_3x3_largest_accepted_filter(pkg, O, torch_dev, knobs, free_after):
     """C = 8192, K = 8128: U is 3.97 GiB (the throughput kernel reads it through one descriptor, so its high offsets

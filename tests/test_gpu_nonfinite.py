@@ -100,7 +100,7 @@ def test_stride2_3x3_and_fused_shortcut(pkg, knobs, torch_dev):
 
 
 # ---- the grouped 3x3 ----------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N,H,W", NF.SHAPES_GROUPED, ids=["3x7x5", "3x9x8"])
+@pytest.mark.parametrize("N,H,W", NF.SHAPES_GROUPED, ids=["3x7x5", "3x9x8", "3x6x12", "3x5x20"])
 def test_grouped_3x3(N, H, W, pkg, knobs, torch_dev):
     """(A poisoned activation channel's footprint is its own group: every other group stays bitwise clean.)"""
     torch, _ = torch_dev

@@ -1,4 +1,5 @@
-"""Seeded random-shape sweeps of the ResNet entry points and of the segmentation path -- the dilated 3x3 layer, the
+"""Seeded random-shape sweeps of the ResNet entry points, of the grouped 3x3 layer and the two ResNeXt blocks (every one
+of the kernel's twelve instantiations, named by wino_conv3x3_grouped_plan) and of the segmentation path -- the dilated 3x3 layer, the
 dilated bottleneck blocks, the concat projection, ASPP and the bilinear resize -- (tests/shape_sweeps.py: shapes from the whole legal envelope
 of winograd_mi355x.h, every forced form the planner takes, the automatic ones): each case against an fp64 reference
 computed on the CPU (tests/sweep_cases.py: the case runners) from the raw torch-layout weights and unfolded BN vectors, into NaN-filled outputs and
@@ -75,3 +76,11 @@ def test_aspp_sweep(pkg, knobs, torch_dev):
 
 def test_resize_bilinear_sweep(pkg, knobs, torch_dev):
     SC.run_sweep("resize_bilinear", SC.resize_case, pkg, knobs, torch_dev, SC.SEEDS["resize_bilinear"])
+
+
+def test_grouped_3x3_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("conv3x3_grouped_bn_relu", SC.grouped_case, pkg, knobs, torch_dev, SC.SEEDS["conv3x3_grouped_bn_relu"])
+
+
+def test_grouped_block_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("grouped_block", SC.grouped_block_case, pkg, knobs, torch_dev, SC.SEEDS["grouped_block"])

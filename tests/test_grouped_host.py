@@ -13,7 +13,7 @@ from conftest import ROOT
 
 E_SHAPE, E_ARG = -2, -3
 NEW = ["wino_conv3x3_grouped_filter_elems", "wino_conv3x3_grouped_filter_pack", "wino_conv3x3_grouped_bn_relu_hw",
-       "wino_grouped_residual_block_hw", "wino_grouped_residual_block_prepare_hw", "wino_grouped_proj_block_hw",
+       "wino_conv3x3_grouped_plan", "wino_grouped_residual_block_hw", "wino_grouped_residual_block_prepare_hw", "wino_grouped_proj_block_hw",
        "wino_grouped_proj_block_prepare_hw"]
 NEW_ARCHS = ["resnext50_32x4d", "resnext101_32x8d", "resnext101_64x4d", "wide_resnet50_2", "wide_resnet101_2"]
 LEGAL_CG = (4, 8, 16, 32, 64)
@@ -96,6 +96,41 @@ def test_layer_rejections(pkg):
     assert "overlap" in L.wino_last_error_string().decode()
     inside = ctypes.c_void_p((1 << 20) + 16 * 16 * 128 * 4 - 16)
     assert run([a, b, b, b, inside]) == E_ARG
+
+
+def test_plan_query(pkg):
+    """wino_conv3x3_grouped_plan answers from the launcher's own geometry: the 8- or 16-wide tile that pads the output
+    row by less, KC = max(Cg, 16), the tiles of one image; and it refuses what the layer refuses, with the same code."""
+    L = pkg.lib()
+    v = [ctypes.c_int(-1) for _ in range(4)]
+    refs = [ctypes.byref(x) for x in v]
+    for stride in (1, 2):
+        for W in list(range(1, 70)) + [2895]:
+            Win = 2 * W - 1 if stride == 2 else W
+            for Cg in LEGAL_CG:
+                tw, kc, ty, tx = pkg.conv3x3_grouped_plan(2, 11, Win, 128 if Cg < 64 else 64, (128 if Cg < 64 else 64) // Cg, stride)
+                pad8, pad16 = -W % 8, -W % 16
+                assert tw == (8 if pad8 < pad16 else 16), (stride, W, tw)
+                assert kc == max(Cg, 16) and tx == -(-W // tw)
+                H = 11 if stride == 1 else 6
+                assert ty == -(-H // ((4 if stride == 1 else 2) * 16 // tw))
+    assert [pkg.conv3x3_grouped_plan(1, 5, W, 64, 16)[0] for W in (8, 9, 16, 17, 24, 25, 32, 33)] == [8, 16, 16, 8, 8, 16, 16, 8]
+    # ResNeXt at 224 x 224: 56 -> 8-wide, 28 and 14 -> 16-wide, 7 -> 8-wide
+    assert [pkg.conv3x3_grouped_plan(1, h, h, 256, 32)[0] for h in (56, 28, 14, 7)] == [8, 16, 16, 8]
+    for C, groups in BAD_CHANNELS:
+        assert L.wino_conv3x3_grouped_plan(1, 14, 14, C, groups, 1, *refs) == E_SHAPE, (C, groups)
+    assert L.wino_conv3x3_grouped_plan(1, 14, 14, 128, 32, 3, *refs) == E_ARG
+    assert L.wino_conv3x3_grouped_plan(0, 14, 14, 128, 32, 1, *refs) == E_SHAPE
+    Hin, Win, C, groups = HUGE
+    assert L.wino_conv3x3_grouped_plan(1, Hin, Win, C, groups, 2, *refs) == E_SHAPE
+    assert L.wino_conv3x3_grouped_plan(1, Hin - 1, Win - 1, C, groups, 2, *refs) == 0
+    assert [x.value for x in v] == [16, 16, 1448, 181]
+    for i in range(4):   # a NULL out-parameter
+        p = list(refs)
+        p[i] = None
+        assert L.wino_conv3x3_grouped_plan(1, 14, 14, 128, 32, 1, *p) == E_ARG, i
+    with pytest.raises(pkg.WinoError):
+        pkg.conv3x3_grouped_plan(1, 14, 14, 96, 3)
 
 
 def test_block_rejections(pkg):

@@ -49,7 +49,7 @@ def _map_hw(c):
     s = c.shape
     if c.entry in ("conv3x3_s2_bn_relu", "conv3x3_s2_proj", "basic_block_s2", "proj_block_v15"):
         return (S._s2(s["Hin"]), S._s2(s["Win"])), (s["Hin"], s["Win"])
-    if c.entry == "proj_block":
+    if c.entry in ("proj_block", "conv3x3_grouped_bn_relu", "grouped_block"):
         st = s["stride"]
         return ((s["Hin"] - 1) // st + 1, (s["Win"] - 1) // st + 1), (s["Hin"], s["Win"])
     if c.entry == "stem":
@@ -73,6 +73,8 @@ def _channels(c):
         "conv1x1_cat_bn": ([s.get("Cs")], [s.get("Kout")]),
         "aspp": ([s.get("Cin")], [s.get("Cb"), s.get("Kout")]),
         "resize_bilinear": ([], []),
+        "conv3x3_grouped_bn_relu": ([s.get("C")], [s.get("C")]),
+        "grouped_block": ([s.get("Cin")], [s.get("Cm"), s.get("C4")]),
     }.get(c.entry, ([s.get("C")], [s.get("K")]))
 
 
@@ -92,6 +94,9 @@ AUTO_FORMS = {
     "conv1x1_cat_bn": [{"tiled", "stream_k"}],
     "aspp": [{"tiled", "stream_k"}],          # (the join's form)
     "resize_bilinear": [{"staged", "direct"}],
+    # all twelve instantiations of the one kernel body
+    "conv3x3_grouped_bn_relu": [{f"s{st}_tw{tw}_kc{kc}" for st in (1, 2) for tw in (8, 16) for kc in (16, 32, 64)}],
+    "grouped_block": [{"latency"}, set(), {"latency", "tiled"}],   # (the middle launch: _grouped_block_corners)
 }
 FORCED_FORMS = {
     "conv3x3_bn_add_relu": {"big_tail", "big_whole", "small"},
@@ -108,6 +113,8 @@ FORCED_FORMS = {
     "conv1x1_cat_bn": set(S.DIL_FORMS),
     "aspp": set(),
     "resize_bilinear": set(),
+    "conv3x3_grouped_bn_relu": set(),
+    "grouped_block": set(S.GBLOCK_FORMS),
 }
 FLAGS = {
     "conv3x3_bn_add_relu": ("relu", "in_place", "nonneg"),
@@ -124,6 +131,8 @@ FLAGS = {
     "conv1x1_cat_bn": ("relu", "a_padded", "c_padded", "nonneg"),
     "aspp": ("nonneg",),
     "resize_bilinear": ("in_padded",),
+    "conv3x3_grouped_bn_relu": ("relu", "nonneg"),
+    "grouped_block": ("nonneg",),
 }
 
 
@@ -264,6 +273,62 @@ def _resize_corners(cases, pkg):
     return got
 
 
+def _grouped_corners(cases, pkg):
+    """The corners of the grouped layer's draws, every one read off wino_conv3x3_grouped_plan's answers."""
+    rows = []
+    for c in cases:
+        p = S.plan_form(pkg, c)
+        H, W = S.grouped_out(c.Hin, c.Win, c.stride)
+        rows.append((c, p, H, W, S.GROUPED_TILE_H[(c.stride, p["tw"])], c.C // c.groups))
+        assert p["tiles_x"] == -(-W // p["tw"]) and p["tiles_y"] == -(-H // rows[-1][4]), c.tag()
+        assert p["kc"] == max(16, c.C // c.groups), c.tag()
+    got = {}
+    for tw in (8, 16):
+        mine = [r for r in rows if r[1]["tw"] == tw]
+        for Cg in (4, 8, 16):
+            got[f"Cg = {Cg} at TW = {tw}"] = any(cg == Cg for *_, cg in mine)
+        got[f"TW = {tw}: a clipped last x-tile"] = any(W % tw for _, _, _, W, _, _ in mine)
+        got[f"TW = {tw}: a full last x-tile behind another"] = any(W % tw == 0 and p["tiles_x"] >= 2 for _, p, _, W, _, _ in mine)
+        for st in (1, 2):
+            pair = [r for r in mine if r[0].stride == st]
+            got[f"stride {st}, TW = {tw}: two tiles down and across"] = any(p["tiles_x"] >= 2 and p["tiles_y"] >= 2
+                                                                            for _, p, *_ in pair)
+            got[f"stride {st}, TW = {tw}: a clipped last y-tile"] = any(H % oh for _, _, H, _, oh, _ in pair)
+            got[f"stride {st}, TW = {tw}: a full last y-tile behind another"] = any(H % oh == 0 and p["tiles_y"] >= 2
+                                                                                    for _, p, H, _, oh, _ in pair)
+    s2 = [c for c in cases if c.stride == 2]
+    for axis in ("Hin", "Win"):
+        got[f"stride 2 with {axis} even"] = any(c.shape[axis] % 2 == 0 for c in s2)
+        got[f"stride 2 with {axis} odd"] = any(c.shape[axis] % 2 for c in s2)
+    got["an output with H = 1"] = any(H == 1 for _, _, H, _, _, _ in rows)
+    got["an output with W = 1"] = any(W == 1 for _, _, _, W, _, _ in rows)
+    got["Hin = 2 at stride 2"] = any(c.Hin == 2 for c in s2)
+    got["C = 64 with groups = 1"] = any(c.C == 64 and c.groups == 1 for c in cases)
+    got["C = 64"] = any(c.C == 64 for c in cases)
+    got["C >= 192"] = any(c.C >= 192 for c in cases)
+    got["N >= 3"] = any(c.N >= 3 for c in cases)
+    return got
+
+
+def _grouped_block_corners(cases, pkg):
+    mids = [S.plan_form(pkg, c)["mid"] for c in cases]
+    got = {"the residual block": any(not c.proj for c in cases)}
+    assert all(c.proj or (c.Cin == c.C4 and c.stride == 1) for c in cases)
+    for st in (1, 2):
+        got[f"the projection block at stride {st}"] = any(c.proj and c.stride == st for c in cases)
+    for Cg in S.GROUPED_CGS:
+        got[f"Cg = {Cg}"] = any(c.Cm // c.groups == Cg for c in cases)
+    for tw in (8, 16):
+        got[f"the middle launch at TW = {tw}"] = any(m["tw"] == tw for m in mids)
+    for kc in (16, 32, 64):
+        got[f"the middle launch at KC = {kc}"] = any(m["kc"] == kc for m in mids)
+    got["Cm = 64"] = any(c.Cm == 64 for c in cases)
+    got["Cm % 128 != 0 and > 64"] = any(c.Cm % 128 and c.Cm > 64 for c in cases)
+    got["C4 % 128 != 0"] = any(c.C4 % 128 for c in cases)
+    got["Cin, Cm and C4 pairwise different"] = any(len({c.Cin, c.Cm, c.C4}) == 3 for c in cases)
+    return got
+
+
 def _corners(entry, cases, pkg, knobs):
     """{corner: reached} for the entry point's draws."""
     maps = [_map_hw(c) for c in cases]
@@ -273,7 +338,7 @@ def _corners(entry, cases, pkg, knobs):
         "a map with H or W = 1": any(1 in out or 1 in inp for out, inp in maps),
         "an odd x odd map": any(out[0] % 2 and out[1] % 2 for out, _ in maps),
     }
-    if entry != "basic_block":    # (its C is a multiple of 64 by contract)
+    if entry not in ("basic_block", "conv3x3_grouped_bn_relu"):    # (their C is a multiple of 64 by contract)
         if cin:
             got["C % 64 != 0"] = any(x % 64 for x in cin)
     if cout:
@@ -305,6 +370,10 @@ def _corners(entry, cases, pkg, knobs):
         got.update(_aspp_corners(cases))
     if entry == "resize_bilinear":
         got.update(_resize_corners(cases, pkg))
+    if entry == "conv3x3_grouped_bn_relu":
+        got.update(_grouped_corners(cases, pkg))
+    if entry == "grouped_block":
+        got.update(_grouped_block_corners(cases, pkg))
     if entry == "conv3x3_s2_proj":
         got["a stream-K range boundary inside the centre tap"] = any(
             c.knobs and _with_knobs(knobs, c, lambda: S.centre_tap_split(pkg, c)) for c in cases)
