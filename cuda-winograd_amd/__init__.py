@@ -751,6 +751,83 @@ def resize_bilinear(src, Ho: int, Wo: int, C=None, in_padded: bool = False, out=
     return (out if want_out else None), (labels if want_labels else None)
 
 
+def roi_align(levels, rois, P: int, scales, sampling: int = 2, in_padded: bool = False, out_padded: bool = False,
+              canonical_scale: float = 224.0, canonical_level: int = 4, out=None) -> torch.Tensor:
+    """torchvision's roi_align(aligned=False) over 1 to 4 pyramid levels with MultiScaleRoIAlign's level assignment, one
+    HIP launch for all boxes.  levels: a tensor or a list of 1..4 tensors, finest first, each [N][h][w][C] or, in_padded,
+    [N][h+2][w+2][C] (the ring is not read); rois [R][5] = (batch index, x1, y1, x2, y2) in image pixels; scales: one
+    spatial_scale per level (several levels: 2^-(k0+l)).  Returns [R][P][P][C], or out_padded [R][P+2][P+2][C] with a zero
+    ring (the Winograd layer's input at N = R).  No scratch: capturable into a graph without a prepare."""
+    maps = [levels] if isinstance(levels, torch.Tensor) else list(levels)
+    if not 1 <= len(maps) <= 4:
+        raise WinoError(f"roi_align takes 1 to 4 level maps, got {len(maps)}")
+    maps = [_dev(m, f"levels[{i}]") for i, m in enumerate(maps)]
+    p = 2 if in_padded else 0
+    if any(m.dim() != 4 or m.shape[1] <= p or m.shape[2] <= p for m in maps):
+        raise WinoError("every level map must be [N][h][w][C]" + (" with a ring (in_padded)" if in_padded else ""))
+    N, C = int(maps[0].shape[0]), int(maps[0].shape[3])
+    if any(int(m.shape[0]) != N or int(m.shape[3]) != C for m in maps):
+        raise WinoError("the level maps must agree in N and C")
+    scales = [float(scales)] if isinstance(scales, (int, float)) else [float(v) for v in scales]
+    if len(scales) != len(maps):
+        raise WinoError(f"{len(maps)} level maps but {len(scales)} scales")
+    r = _dev(rois, "rois")
+    if r.dim() != 2 or int(r.shape[1]) != 5:
+        raise WinoError("rois must be [R][5]: (batch index, x1, y1, x2, y2)")
+    R, P, q = int(r.shape[0]), int(P), 2 if out_padded else 0
+    if P < 1:
+        raise WinoError(f"roi_align: bad P={P}")
+    out = _output(out, (R, P + q, P + q, C), r.device)
+    _on_current_device(*maps, r, out)
+    hw = (c_int * (2 * len(maps)))(*[int(m.shape[d]) - p for m in maps for d in (1, 2)])
+    sc = (ctypes.c_float * len(maps))(*scales)
+    ptrs = [m.data_ptr() for m in maps] + [None] * (4 - len(maps))
+    _check(lib().wino_roi_align_hw(*ptrs, hw, sc, len(maps), N, C, int(bool(in_padded)), r.data_ptr() or None, R, P,
+                                   int(sampling), float(canonical_scale), int(canonical_level), out.data_ptr() or None,
+                                   int(bool(out_padded)), _stream()), "wino_roi_align_hw")
+    return out
+
+
+def boxes_to_rois(boxes) -> torch.Tensor:
+    """torchvision's convert_to_roi_format: a list of per-image [L_i][4] box tensors -> [K][5] with the image index in
+    front, by torch ops on the device (no host synchronisation); a [K][5] tensor passes through."""
+    if isinstance(boxes, torch.Tensor):
+        return boxes
+    ids = torch.cat([torch.full((int(b.shape[0]), 1), float(i), dtype=b.dtype, device=b.device)
+                     for i, b in enumerate(boxes)])
+    return torch.cat([ids, torch.cat(list(boxes))], dim=1)
+
+
+def infer_roi_scales(maps, image_size, in_padded: bool = False):
+    """torchvision's MultiScaleRoIAlign.infer_scale: per level 2^round(log2(h_l / H_img)), the same along both axes."""
+    import math
+    p = 2 if in_padded else 0
+    scales = []
+    for m in maps:
+        per_axis = [2.0 ** round(math.log2((int(m.shape[d]) - p) / float(size))) for d, size in zip((1, 2), image_size)]
+        if per_axis[0] != per_axis[1]:
+            raise WinoError(f"level map {tuple(m.shape)}: the two axes give different scales {per_axis} for image "
+                            f"{tuple(image_size)}")
+        scales.append(per_axis[0])
+    return scales
+
+
+def multiscale_roi_align(features, boxes, image_size, P: int, sampling: int = 2, in_padded: bool = False,
+                         out_padded: bool = False, canonical_scale: float = 224.0, canonical_level: int = 4,
+                         out=None) -> torch.Tensor:
+    """torchvision's MultiScaleRoIAlign (aligned=False) on NHWC level maps.  features: a dict as ResNetFPN returns it (its
+    "pool" entry is left out, as torchvision's detectors do), or a list / one tensor, finest first; with in_padded the
+    padded tensors of ResNetFPN(..., padded=True).  boxes: Tensor[K, 5], or a list of per-image Tensor[L_i, 4].
+    image_size: (H, W) of the network's input, from which the scales are inferred.  See roi_align for the result."""
+    if isinstance(features, dict):
+        maps = [v for k, v in features.items() if k != "pool"]
+    else:
+        maps = [features] if isinstance(features, torch.Tensor) else list(features)
+    scales = infer_roi_scales(maps, image_size, in_padded)
+    return roi_align(maps, boxes_to_rois(boxes), P, scales, sampling, in_padded, out_padded, canonical_scale,
+                     canonical_level, out)
+
+
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
     """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
     bounds by the kernel)."""
@@ -1181,3 +1258,4 @@ from .resnet import ResNet  # noqa: E402  (whole networks on the operators above
 from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
+from .detection import BoxHead, MaskHead  # noqa: E402

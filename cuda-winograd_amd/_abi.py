@@ -171,6 +171,8 @@ SIGNATURES = {
     # ---- bilinear resize and label map
     "wino_resize_bilinear_hw": (i, [vp] * 3 + [i] * 8 + [vp]),
     "wino_resize_bilinear_plan": (i, [i] * 8 + [ip]),
+    # ---- multi-scale RoIAlign
+    "wino_roi_align_hw": (i, [vp] * 4 + [ip, fptr] + [i] * 4 + [vp] + [i] * 3 + [c_float, i, vp, i, vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

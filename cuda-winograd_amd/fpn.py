@@ -88,10 +88,12 @@ class ResNetFPN(Net):
                 fpn_level_prepare(N, h, w, c, self.out_channels)
         self._shape = (N, H, W)
 
-    def forward(self, x: torch.Tensor):
+    def forward(self, x: torch.Tensor, padded: bool = False):
         """x [N][3][H][W] float32 on the model's device -> {"0", "1", "2", "3", "pool"}: the pyramid levels P2..P5 at
         strides 4..32 and the pooled P5, each an NHWC view [N][h][w][out_channels] of the model's own tensors, valid
-        until the next forward.  A new input shape re-runs prepare()."""
+        until the next forward.  A new input shape re-runs prepare().  padded=True returns "0".."3" as the padded
+        tensors [N][h+2][w+2][out_channels] themselves (zero ring), what multiscale_roi_align(in_padded=True) reads
+        without a copy; "pool" stays the strided view of P5's interior."""
         self._begin(x)
         with torch.cuda.device(self.device):
             stages = self.body._run_body(x.contiguous())
@@ -99,8 +101,8 @@ class ResNetFPN(Net):
                 wl, bl, U, bo = self.levels[i]
                 fpn_level(stages[i], wl, bl, U, bo, top=self._inner[i + 1] if i + 1 < LEVELS else None,
                           c_padded=not self.body.bottleneck, ones=self._ones, inner=self._inner[i], out=self._p[i])
-        out = {str(i): p[:, 1:-1, 1:-1, :] for i, p in enumerate(self._p)}
-        out["pool"] = out[str(LEVELS - 1)][:, ::2, ::2, :]
+        out = {str(i): p if padded else p[:, 1:-1, 1:-1, :] for i, p in enumerate(self._p)}
+        out["pool"] = self._p[LEVELS - 1][:, 1:-1:2, 1:-1:2, :]
         return out
 
 

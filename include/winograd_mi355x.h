@@ -65,7 +65,7 @@ extern "C" {
  * wino_conv3x3_dilated_prepare_hw, wino_conv3x3_dilated_plan, wino_dilated_residual_block_hw,
  * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
- * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -748,6 +748,42 @@ int wino_aspp_prepare_hw(int N, int H, int W, int Cin, int Cb, int Kout, int d1,
 int wino_resize_bilinear_hw(const float* src, float* out, int* labels, int N, int h, int w, int C, int ld,
                             int in_padded, int Ho, int Wo, wino_stream_t s);
 int wino_resize_bilinear_plan(int h, int w, int C, int ld, int Ho, int Wo, int want_out, int want_labels, int* form);
+
+/* ---- multi-scale RoIAlign: the pooling stage of a two-stage detector ----------------------------
+ * torchvision's roi_align(..., aligned=False) over 1 to 4 pyramid levels with MultiScaleRoIAlign's level assignment, all
+ * boxes of all images and levels in one launch:
+ *   f0..f3      the level maps, finest first, [N][h_l][w_l][C], or with in_padded = 1 the padded [N][h_l+2][w_l+2][C] that
+ *               wino_fpn_level_hw writes (the ring is never read: RoIAlign clamps to the border pixel); pointers beyond
+ *               `levels` are ignored
+ *   hw_host     HOST array [levels][2] of (h_l, w_l);  scale_host: HOST array [levels] of spatial_scale.  With levels > 1,
+ *               scale_host[l] must be exactly 2^-(k0+l) for an integer k0 (torchvision's LevelMapper assumes it); one
+ *               level takes any finite positive scale
+ *   rois        DEVICE [R][5] fp32 (batch index, x1, y1, x2, y2) in image pixels, torchvision's Tensor[K, 5]
+ *   out         [R][P][P][C], or with out_padded = 1 [R][P+2][P+2][C] with the ring written as exact 0: the layout
+ *               wino_conv3x3_bn_relu_hw reads at N = R.  The unpadded form at P = 7 is the A matrix [R][49 C] of a
+ *               detector's first FC layer
+ * Arithmetic (fp32, torchvision's CPU kernel operation by operation): s = the level's scale; sx = x1 s, ... ; roi_w =
+ * max(ex - sx, 1); bin = roi / P; sampling x sampling samples per bin at start + p bin + (i + .5) bin / sampling.  A
+ * sample with y < -1 || y > h || x < -1 || x > w contributes 0; otherwise clamp at 0, low = (int)v, at low >= size - 1
+ * both taps are size - 1 and the fraction 0; value = hy hx a + hy lx b + ly hx c + ly lx d with all four taps always
+ * multiplied (a NaN under a zero weight reaches the output); the bin is the sum of its samples / sampling^2.
+ * Level (levels > 1): clamp(floor(canonical_level + log2(sqrt(area) / canonical_scale) + 1e-6), k0, k0 + levels - 1) - k0
+ * with area = (x2 - x1)(y2 - y1) in fp32, evaluated as the number of area thresholds (canonical_scale 2^(k0 + j -
+ * canonical_level - 1e-6))^2 the area reaches (computed on the host in double, compared as floats: it can differ from
+ * torch's fp32 log2 only within about 1e-6 relative of a threshold); an area <= 0 or NaN takes level 0 (undefined in torch).
+ * A box whose batch index is not an integer in [0, N) reads nothing and gets zeros; otherwise a box with a non-finite
+ * coordinate reads nothing and gets NaN in its P x P x C outputs (ring 0).  Every tap address is clamped into the box's
+ * own image, and no box changes a bit of another box's output.
+ * 1 <= levels <= 4, N, C >= 1, C % 4 == 0, 1 <= P <= 64, 1 <= sampling <= 4 (torchvision's adaptive sampling_ratio <= 0
+ * is not supported), R >= 0, in_padded and out_padded 0 or 1, h_l, w_l >= 1, one image of a level map and one box's
+ * output below 2^31 elements (WINO_E_SHAPE otherwise); any R (the output may pass 4 GiB).  R == 0 is WINO_OK and launches
+ * nothing.  A NULL or not 16-byte-aligned pointer, an overlap of out with a level map or with rois, a bad scale_host
+ * sequence, or a canonical_scale that is not finite and positive is WINO_E_ARG.  No workspace and no stream scratch: the
+ * call can be captured into a graph as it is. */
+int wino_roi_align_hw(const float* f0, const float* f1, const float* f2, const float* f3, const int* hw_host,
+                      const float* scale_host, int levels, int N, int C, int in_padded, const float* rois, int R, int P,
+                      int sampling, float canonical_scale, int canonical_level, float* out, int out_padded,
+                      wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
