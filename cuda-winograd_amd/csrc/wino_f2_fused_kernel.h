@@ -406,7 +406,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     if (j == 3) v[e] = sub2(tmp[i * 4 + 1], tmp[i * 4 + 3]);
   };
 
-  unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0;   // ABLATE & PROBE_PHASES: phase stamps
+  unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0, st_span = 0;   // ABLATE & PROBE_PHASES: phase stamps
   unsigned long long st_ph[4] = {0, 0, 0, 0};   // epilogue phases: barrier, A^T m A, slab+ticket, gather+finalize
   auto stamp = [&]() -> unsigned long long {
     unsigned long long t;
@@ -442,12 +442,30 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   unsigned raw_off[4];        // per-lane source offsets of the DMA stream's tile block
   unsigned d_soff_raw = 0;    // + chunk * 32 B
   unsigned d_soff_u = 0;      // filter chunk of (k block, chunk), this wave's 1-KiB column
-  int d_item, d_chunk, d_tail, d_tb = -1;   // d_tail: tail iterations the stream still has to issue
-  auto dma_set_item = [&](int item) {   // wave-uniform; the per-lane part only when the tile block changes
+  // The stream is EVENT DRIVEN.  An advance is normally two scalar adds (the next chunk of the same item); every
+  // d_run-th one is an event instead: the stream changes item (dma_set_item: new offsets, and new per-lane offsets when
+  // the tile block changes) or it has issued the whole range and stands on its last chunk from there on -- the two
+  // steps become 0, so the advance stays unconditional.  The main loop runs to the next event without asking; what an
+  // event needs (item, tail iterations, advances left, tile block) waits in the lanes of ONE VGPR (ws_vg: a scalar per
+  // lane, v_writelane / v_readlane in the event code), as it will be AT the event: none of it costs the loop a scalar
+  // register or an instruction, and the epilogues, which are at the register budget, one VGPR.
+  unsigned d_step_raw = (unsigned)(BC * sizeof(float)), d_step_u = u_chunk_stride;   // what an advance adds
+  int d_run = 0;              // advances up to and including the next event
+  int ws_vg = 0;
+  // lanes of ws_vg
+  typedef std::integral_constant<int, 0> WS_D_ITEM; typedef std::integral_constant<int, 1> WS_D_TAIL;
+  typedef std::integral_constant<int, 2> WS_D_LEFT; typedef std::integral_constant<int, 3> WS_D_TB;
+  typedef std::integral_constant<int, 4> WS_D_RUN;  typedef std::integral_constant<int, 5> WS_C_RUN;
+  typedef std::integral_constant<int, 6> WS_C_LEFT;
+  // (v_writelane_b32 has no builtin; volatile asm also keeps the scalars in their lanes: the compiler cannot look through it)
+  auto ws_put = [&ws_vg](auto slot, int val) { asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(ws_vg) : "s"(val), "n"(decltype(slot)::value)); };
+  auto ws_get = [&ws_vg](auto slot) { return __builtin_amdgcn_readlane(ws_vg, decltype(slot)::value); };
+  ws_put(WS_D_TB{}, -1);
+  constexpr int D_NEVER = 0x7fffffff;
+  auto dma_set_item = [&](int item, int chunk) {   // wave-uniform; the per-lane part only when the tile block changes
     const int tb = item / KBLK, kb = item - tb * KBLK;
-    d_item = item;
-    if (tb != d_tb) {
-      d_tb = tb;
+    if (tb != ws_get(WS_D_TB{})) {
+      ws_put(WS_D_TB{}, tb);
       KernargPtr kp = kernarg();
       const Geo geo = load_geo(kp);
       const int Wp = GEN ? geo.Wp : WINO_HW, Hp = GEN ? geo.Hp : WINO_HW;
@@ -466,31 +484,56 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         raw_off[j] = (unsigned)((((size_t)(tc.n * Hp + y) * Wp + x) * C + half * 4) * sizeof(float));
       }
     }
-    d_soff_raw = __builtin_amdgcn_readfirstlane((unsigned)(d_chunk * (BC * sizeof(float))));
-    d_soff_u = __builtin_amdgcn_readfirstlane((unsigned)((kb * U_CHUNK_FLOATS + w * 256) * sizeof(float)) + d_chunk * u_chunk_stride);
-    // ("+s": pins the loop-carried scalars to SGPRs.  Short of SGPRs, the compiler otherwise keeps
-    //  one of them in a VGPR and wraps every LDS-DMA that uses it in a waterfall loop.)
-    asm volatile("" : "+s"(d_soff_raw), "+s"(d_soff_u));
+    // (opaque: the loop carries these four registers as they are, no copy of them goes round it)
+    asm volatile("" : "+v"(raw_off[0]), "+v"(raw_off[1]), "+v"(raw_off[2]), "+v"(raw_off[3]));
+    d_soff_raw = __builtin_amdgcn_readfirstlane((unsigned)(chunk * (BC * sizeof(float))));
+    d_soff_u = __builtin_amdgcn_readfirstlane((unsigned)((kb * U_CHUNK_FLOATS + w * 256) * sizeof(float)) + chunk * u_chunk_stride);
   };
-  auto pin_dma_state = [&]() {   // "+s": keep the loop-carried scalars in SGPRs (see dma_set_item)
-    d_item = __builtin_amdgcn_readfirstlane(d_item);
-    d_chunk = __builtin_amdgcn_readfirstlane(d_chunk);
-    d_tail = __builtin_amdgcn_readfirstlane(d_tail);
-    d_tb = __builtin_amdgcn_readfirstlane(d_tb);
-    asm volatile("" : "+s"(d_item), "+s"(d_chunk), "+s"(d_tail), "+s"(d_tb));
+  // ("+s": pins the loop-carried scalars to SGPRs.  Short of SGPRs, the compiler otherwise keeps
+  //  one of them in a VGPR and wraps every LDS-DMA that uses it in a waterfall loop.)
+  auto pin_dma_state = [&]() {
+    d_run = __builtin_amdgcn_readfirstlane(d_run);
+    asm volatile("" : "+s"(d_soff_raw), "+s"(d_soff_u), "+s"(d_step_raw), "+s"(d_step_u), "+s"(d_run));
   };
-  auto dma_advance = [&]() {
-    if (d_tail > 0 && --d_tail == 0) {          // the tail range is issued: on to the whole items
-      d_chunk = 0;
-      dma_set_item(lg);
-    } else if (++d_chunk == nchunks) {
-      d_chunk = 0;
-      dma_set_item(d_tail > 0 ? d_item + kernarg()->kp : d_item + G);   // the next tail item of this k-group / round
-    } else {
-      d_soff_raw += (unsigned)(BC * sizeof(float));
-      d_soff_u += u_chunk_stride;
-      asm volatile("" : "+s"(d_soff_raw), "+s"(d_soff_u));
+  auto dma_stand = [&]() {   // the range is issued: every later advance adds nothing
+    d_step_raw = 0;
+    d_step_u = 0;
+    d_run = D_NEVER;
+  };
+  // The stream stands on (item, chunk) with `tail` tail iterations (this one included) and `left` advances still to
+  // make: how far it runs on plain advances, and its state at the event that ends the run.
+  auto dma_plan = [&](int item, int chunk, int tail, int left) {
+    const int nch = kernarg()->C / BC;
+    const int in_item = nch - 1 - chunk;
+    const int plain = tail > 0 && tail - 1 < in_item ? tail - 1 : in_item;   // ... before the item or the tail ends
+    if (left <= plain) {   // the range ends first
+      if (left == 0) dma_stand();
+      else d_run = left;
+      left = -1;
+    } else {               // the advance after them changes item
+      d_run = plain + 1;
+      left -= plain + 1;
+      if (tail > 0) tail -= plain;
     }
+    ws_put(WS_D_ITEM{}, item), ws_put(WS_D_TAIL{}, tail), ws_put(WS_D_LEFT{}, left);
+  };
+  auto dma_event = [&]() {   // d_run has run out
+    int item = ws_get(WS_D_ITEM{}), tail = ws_get(WS_D_TAIL{});
+    const int left = ws_get(WS_D_LEFT{});
+    if (left < 0) {
+      dma_stand();
+    } else {
+      if (tail > 0 && --tail == 0) item = lg;            // the tail range is issued: on to the whole items
+      else item += tail > 0 ? kernarg()->kp : G;         // the next tail item of this k-group / round
+      dma_set_item(item, 0);                             // (it overwrites the two offsets the plain advance has just stepped)
+      dma_plan(item, 0, tail, left);
+    }
+    pin_dma_state();
+  };
+  auto dma_advance = [&]() {   // one advance outside the main loop (prologue)
+    d_soff_raw += d_step_raw;
+    d_soff_u += d_step_u;
+    if (--d_run == 0) dma_event();
     pin_dma_state();
   };
   // LDS map: [R0 32K][R1 32K][U0 32K][U1 32K][U2 32K]; R = raw 4x4 patches, U = filter chunk.
@@ -538,18 +581,18 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   f32x2 bfn[PF][2];  // filter fragments of steps 0..PF-1 of the next iteration (requested pre-barrier)
 
   // ---- prologue: iterations 0 and 1 in flight; V_0 and the first fragments un-pipelined -----
-  d_chunk = c_chunk;
-  d_tail = Lt;
-  dma_set_item(c_item_vg);
+  dma_set_item(c_item_vg, c_chunk);
+  dma_plan(c_item_vg, c_chunk, Lt, L - 1);   // L - 1 advances take the stream to the range's last chunk
+  pin_dma_state();
   asm volatile("" : "+v"(c_item_vg));
 #pragma unroll
   for (int j = 0; j < 4; j++) issue_raw1(0, j);
 #pragma unroll
   for (int j = 0; j < 4; j++) issue_u1(0, j);
-  // The DMA walker never leaves this workgroup's range: it stops on the last chunk, and the
-  // last two iterations of the range fetch that chunk again into stages nobody reads (see body()).
+  // The DMA walker never leaves this workgroup's range: it stops on the last chunk (an advance past it adds
+  // nothing), and the last two iterations of the range fetch that chunk again into stages nobody reads (see body()).
   if ((ABLATE & PROBE_TIMELINE) && tid == 0) prm.dbg[(size_t)lg * TL_WORDS + TL3_STAGE_REQ] = __builtin_amdgcn_s_memrealtime();   // first stage requested
-  if (L > 1) dma_advance();
+  dma_advance();
   ring_pass();   // in the shadow of the first pieces' flight
   if (!(ABLATE & PROBE_NO_SYNC)) {
     wait_vmem_all();
@@ -561,7 +604,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     for (int j = 0; j < 4; j++) issue_raw1(1, j);
 #pragma unroll
     for (int j = 0; j < 4; j++) issue_u1(1, j);
-    if (L > 2) dma_advance();
+    dma_advance();
   }
   {
     P2 d[12];
@@ -606,9 +649,9 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     ub_cur[cb] = b_base[cb];
     ub_nxt[cb] = b_base[cb] + U_BYTES;
   }
-  auto body = [&](auto par_c, int it, int rs_dma, int us_dma) {
+  auto body = [&](auto par_c, int rs_dma, int us_dma) {
     constexpr int ROFF = decltype(par_c)::value ? 0 : RAW_BYTES;
-    if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (it) st_comp += t - st_prev; st_prev = t; }
+    if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (st_prev) st_comp += t - st_prev; st_prev = t; }
     if (!(ABLATE & PROBE_NO_SYNC)) {
       wait_vmem_all();   // my DMA pieces of raw_{it+1} and U_{it+1} have landed
       __syncthreads();   // everyone's have; everyone is done with the stages refilled below
@@ -666,10 +709,12 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         issue_u1(us_dma, e - DMA0 - 4);
       }
       // next iteration's A operand rides along: steps 0-5 read its 12 patch pixels (two per step, in
-      // the order R0[j], R1[j], R2[j] column by column); B^T d B itself is written below, after the
-      // step's MFMAs, and is deliberately NOT pinned to its step: the optimizer sinks it behind the
-      // last MFMA of the iteration, where it runs as one burst of packed adds while the SIMD's other
-      // wave still has MFMAs to issue.  Measured alternatives (with 16 points per wave), all slower:
+      // the order R0[j], R1[j], R2[j] column by column); B^T d B itself is written behind the last
+      // step, after the iteration's last MFMA, where it runs as one burst of packed adds while the
+      // SIMD's other wave still has MFMAs to issue.  (It used to be written inside the steps and left
+      // unpinned: the optimizer sank it out of the body's block into the walker's blocks behind it.
+      // The loop is one block per body now, nothing sinks, and written in the steps the adds stay
+      // between the MFMAs.)  Measured alternatives (with 16 points per wave), all slower:
       // pinned to steps 2-15 (scalar or packed, +3..+8 %: arithmetic between a wave's MFMAs delays its
       // own next MFMA, and when it waits on a patch read the whole wave stalls behind it, in-order
       // issue); B^T d as the loop-carried state with every point formed one step ahead of its use
@@ -684,11 +729,6 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       __builtin_amdgcn_sched_barrier(0);
       if (!(ABLATE & (PROBE_NO_A_PATH | PROBE_NO_B_READS))) wait_lds(lds_wait_count(e));
       __builtin_amdgcn_sched_barrier(0);
-      if (e >= 3 && e <= 7 && e != 5 && !(ABLATE & PROBE_NO_A_PATH) && !(ABLATE & PROBE_NO_BTDB)) tmp_col(tmp, d, e == 3 ? 0 : e == 4 ? 1 : e == 6 ? 2 : 3);
-      if ((ABLATE & PROBE_NO_BTDB) && e == 7) {
-#pragma unroll
-        for (int i = 0; i < 12; i++) asm volatile("" :: "v"(d[i]));
-      }
       const P2 a = v[pt];
       const f32x2 b0 = bf[e][0], b1 = bf[e][1];
       if (ABLATE & PROBE_NO_MFMA) {  // keep the operands live, skip the matrix pipe
@@ -705,19 +745,25 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 0]) : "v"(a.y), "v"(b0.y));
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 1]) : "v"(a.y), "v"(b1.y));
       }
-      if ((ABLATE & PROBE_NO_VPOINT) && !(ABLATE & PROBE_NO_BTDB) && e == 9) {
+      if ((ABLATE & PROBE_PHASES) && e == 15) st_span += stamp() - st_prev;   // the iteration's last MFMA is issued
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // B^T d B of the next iteration, in place over V: every point has retired, all patch reads are in (step 7)
+    if (!(ABLATE & PROBE_NO_A_PATH)) {
+      if (ABLATE & PROBE_NO_BTDB) {
 #pragma unroll
-        for (int i = 0; i < 8; i++) asm volatile("" :: "v"(tmp[i]));
-      }
-      if (!(ABLATE & PROBE_NO_A_PATH) && !(ABLATE & (PROBE_NO_VPOINT | PROBE_NO_BTDB))) {
-        // point p retires with step 2 p + 1; all patch reads are in by step 7
-        if (e >= 9 && e < 15) v_point(v, tmp, e - 9);   // points 0..5
-        if (e == 15) {
-          v_point(v, tmp, 6);
-          v_point(v, tmp, 7);
+        for (int i = 0; i < 12; i++) asm volatile("" :: "v"(d[i]));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; j++) tmp_col(tmp, d, j);
+        if (ABLATE & PROBE_NO_VPOINT) {
+#pragma unroll
+          for (int i = 0; i < 8; i++) asm volatile("" :: "v"(tmp[i]));
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; e++) v_point(v, tmp, e);
         }
       }
-      __builtin_amdgcn_sched_barrier(0);
     }
   };
 
@@ -1082,14 +1128,19 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   };
 
   // ================================ main loop =====================================
-  // Per segment: the tight loop over its iterations, then the one epilogue site.
+  // The tight loop runs to the next EVENT: the end of the compute segment (then the one epilogue site) or the DMA
+  // stream's next item switch / end, two iterations ahead of it (dma_event), whichever is due first, or both.  Between
+  // events an iteration's tail is the common path alone: the stream's two scalar adds, the four fragment-base
+  // rotations, the filter-stage counter, the count-down and its branch.  The two copies of the body alternate
+  // statically; which one an entry starts with, and the parity it leaves, are settled once per entry.
   {
-    int us = 0;  // filter stage of iteration `it` (= it % 3)
+    int us = 0;    // filter stage of iteration `it` (= it % 3)
+    int par = 0;   // it & 1
     auto next = [](int s) { return s == 2 ? 0 : s + 1; };
-    int it = 0;
-#pragma unroll 1
-    for (;;) {
-      // iterations of this segment: to the end of the item, or of the tail range
+    int c_run = 0;       // iterations this segment still has to run
+    ws_put(WS_C_LEFT{}, L);   // ... and the range after this segment
+    // iterations of the next segment: to the end of the item, or of the tail range
+    auto segment = [&]() {
       int c_tail = __builtin_amdgcn_readfirstlane(c_tail_vg);
       const int n = c_tail > 0 && c_tail < nchunks - c_chunk ? c_tail : nchunks - c_chunk;
       seg_kind_vg = c_chunk == 0 ? (n == nchunks ? 3 : 2) : 0;
@@ -1098,49 +1149,73 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       // c_tail < 0 = "the tail ends with this segment"
       if (c_tail > 0 && (c_tail -= n) == 0) c_tail = -1;
       c_tail_vg = c_tail;
+      ws_put(WS_C_LEFT{}, ws_get(WS_C_LEFT{}) - n);
       asm volatile("" : "+v"(c_tail_vg));
       c_chunk = 0;   // every later segment starts its item
-      int us_last = us;
-      auto tail = [&](auto par_c) {   // everything between two bodies
-        if (it + 3 < L) dma_advance();
-        us_last = us;
-        us = next(us);
-        it++;
-        {   // rotate the filter-fragment bases: U_{it} was U_{it+1}; the new U_{it+1} is stage next(us)
-          const int off = next(us) * U_BYTES;
+      c_run = n;
+    };
+    auto tail = [&](auto par_c) {   // everything between two bodies
+      d_soff_raw += d_step_raw;
+      d_soff_u += d_step_u;
+      asm volatile("" : "+s"(d_soff_raw), "+s"(d_soff_u));
+      us = next(us);
+      {   // rotate the filter-fragment bases: U_{it} was U_{it+1}; the new U_{it+1} is stage next(us)
+        const int off = next(us) * U_BYTES;
 #pragma unroll
-          for (int cb = 0; cb < 4; cb++) {
-            // the set the body just used as "current" is dead: it becomes the next body's "next"
-            if (decltype(par_c)::value) ub_nxt[cb] = b_base[cb] + off;
-            else ub_cur[cb] = b_base[cb] + off;
-          }
-        }
-      };
-      {
-        int k = n;
-#pragma unroll 1
-        for (;;) {
-          if (!(it & 1)) {
-            body(std::integral_constant<int, 0>{}, it, 0, next(next(us)));
-            tail(std::integral_constant<int, 0>{});
-            if (--k == 0) break;
-          }
-          body(std::integral_constant<int, 1>{}, it, 1, next(next(us)));
-          tail(std::integral_constant<int, 1>{});
-          if (--k == 0) break;
+        for (int cb = 0; cb < 4; cb++) {
+          // the set the body just used as "current" is dead: it becomes the next body's "next"
+          if (decltype(par_c)::value) ub_nxt[cb] = b_base[cb] + off;
+          else ub_cur[cb] = b_base[cb] + off;
         }
       }
-      // the segment's last iteration was it-1: raw stage R[it & 1] and filter stage U[us_last] are free
-      const bool last_of_range = it == L;
+    };
+    segment();
+#pragma unroll 1
+    for (;;) {
+      {
+        int k = d_run < c_run ? d_run : c_run;
+        // both counts as they will be after the k iterations, parked: the loop keeps k alone
+        ws_put(WS_D_RUN{}, d_run - k), ws_put(WS_C_RUN{}, c_run - k);
+        // One trip = (body 0, tail 0, body 1, tail 1): an if for an entry on odd `it`, which skips body 0 once, an
+        // if for a count that runs out after body 0, and the back edge -- three branches, one of them taken.  The
+        // empty asm statements keep the compiler from threading those tests into a loop that is entered in its
+        // middle, which it then repairs with a dispatch block and a flag test after every body.
+        int skip0 = par;
+        par ^= k & 1;   // the parity the k iterations leave
+#pragma unroll 1
+        do {
+          asm volatile("" : "+s"(skip0));
+          if (!skip0) {
+            body(std::integral_constant<int, 0>{}, 0, next(next(us)));
+            tail(std::integral_constant<int, 0>{});
+            --k;
+          }
+          skip0 = 0;
+          asm volatile("" : "+s"(k));
+          if (k != 0) {
+            body(std::integral_constant<int, 1>{}, 1, next(next(us)));
+            tail(std::integral_constant<int, 1>{});
+            --k;
+          }
+          asm volatile("" : "+s"(k));
+        } while (k != 0);
+        d_run = ws_get(WS_D_RUN{});
+        c_run = ws_get(WS_C_RUN{});
+      }
+      if (d_run == 0) dma_event();
+      if (c_run != 0) continue;
+      // the segment's last iteration was it-1: raw stage R[it & 1] and the filter stage before U[us] are free
+      const int us_last = us == 0 ? 2 : us - 1;
+      const bool last_of_range = ws_get(WS_C_LEFT{}) == 0;
       if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_comp += t - st_prev; st_prev = t; }
       if ((ABLATE & PROBE_TIMELINE) && last_of_range && tid == 0) {
         KernargPtr kp = kernarg();
         kp->dbg[(size_t)lg * TL_WORDS + TL_LAST_EPI] = __builtin_amdgcn_s_memrealtime();
       }
-      epilogue(last_of_range, (it & 1) * RAW_BYTES, N_RSTAGE * RAW_BYTES + us_last * U_BYTES);
+      epilogue(last_of_range, par * RAW_BYTES, N_RSTAGE * RAW_BYTES + us_last * U_BYTES);
       if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_epi += t - st_prev; st_prev = t; }
       if (last_of_range) break;
-      c_tail = __builtin_amdgcn_readfirstlane(c_tail_vg);
+      const int c_tail = __builtin_amdgcn_readfirstlane(c_tail_vg);
       if (c_tail < 0) {   // tail done: first whole item
         c_item_vg = lg;
         c_tail_vg = 0;
@@ -1148,6 +1223,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         c_item_vg += c_tail > 0 ? kernarg()->kp : G;
       }
       asm volatile("" : "+v"(c_item_vg), "+v"(c_tail_vg));
+      segment();
     }
   }
   wait_vmem_all();   // no LDS-DMA of this wave may land after the workgroup's LDS has been given away
@@ -1164,6 +1240,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       dbg[PH_EPI0 + 1] = st_ph[1];
       dbg[PH_EPI0 + 2] = st_ph[2];
       dbg[PH_EPI0 + 3] = st_ph[3];
+      dbg[PH_SPAN] = st_span;
     }
   }
   if (ABLATE & PROBE_TIMELINE) {

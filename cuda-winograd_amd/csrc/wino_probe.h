@@ -43,8 +43,9 @@ constexpr int TL1_HW_ID = 4, TL1_ENTRY_CYC = 5, TL1_EXIT_CYC = 6;   // 1x1: HW_R
 constexpr int CLK_WORDS = 4, CLK_BEGIN_CYC = 0, CLK_BEGIN_RT = 1, CLK_END_CYC = 2, CLK_END_RT = 3;
 // PROBE_PHASES: PH_WORDS per wave (PH_USED of them written), PH_WAVES waves per logical workgroup; sums of s_memtime
 // differences: vmcnt wait + barrier, the rest of the iterations, the epilogues, and of those (PH_EPI0 + 0..3) the
-// barrier, A^T m A, slab + ticket, gather + finalize.
-constexpr int PH_WORDS = 8, PH_WAVES = 8, PH_USED = 7, PH_WAIT = 0, PH_COMPUTE = 1, PH_EPILOGUE = 2, PH_EPI0 = 3;
+// barrier, A^T m A, slab + ticket, gather + finalize.  PH_SPAN is the part of PH_COMPUTE from the barrier's release to
+// the iteration's last MFMA: PH_COMPUTE - PH_SPAN is what a wave runs between its last MFMA and the next barrier.
+constexpr int PH_WORDS = 8, PH_WAVES = 8, PH_USED = 8, PH_WAIT = 0, PH_COMPUTE = 1, PH_EPILOGUE = 2, PH_EPI0 = 3, PH_SPAN = 7;
 // DIAG build of the 3x3 latency kernel: SM_WORDS per workgroup, s_memrealtime, in time order (phase i of
 // tools/small_timeline is slot i + 1 minus slot i).  A workgroup that does not finish its block stops at SM_TICKET;
 // without a C-split (S = 1) SM_SLAB_OUT .. SM_GATHERED are not stamped.

@@ -201,6 +201,15 @@ int main(int argc, char** argv) {
       printf("  wave %d: wait(vmcnt+barrier) %6.0f  compute %6.0f cycles per iteration (wait share %4.1f%%) | epilogues per workgroup %7.0f cycles = barrier %6.0f + AtmA %6.0f + slab/ticket %6.0f + gather/finalize %6.0f\n", w,
              sum[w][PH_WAIT] / wgs / iters, sum[w][PH_COMPUTE] / wgs / iters, 100.0 * sum[w][PH_WAIT] / (sum[w][PH_WAIT] + sum[w][PH_COMPUTE]), sum[w][PH_EPILOGUE] / wgs,
              sum[w][PH_EPI0 + 0] / wgs, sum[w][PH_EPI0 + 1] / wgs, sum[w][PH_EPI0 + 2] / wgs, sum[w][PH_EPI0 + 3] / wgs);
+    // where an iteration's compute part ends: barrier release -> last MFMA (the MFMA span), last MFMA -> arrival at the
+    // next barrier (transform burst, DMA walker, loop control), arrival -> release; per wave class (waves 0-3 / 4-7)
+    for (int c = 0; c < 2; c++) {
+      double span = 0, comp = 0, wait = 0;
+      for (int w = 4 * c; w < 4 * c + 4; w++) { span += sum[w][PH_SPAN]; comp += sum[w][PH_COMPUTE]; wait += sum[w][PH_WAIT]; }
+      const double d = 4.0 * wgs * iters;
+      printf("  waves %d-%d: MFMA span %6.0f  last MFMA -> barrier arrival %6.0f  arrival -> release %6.0f  last MFMA -> release %6.0f cycles per iteration\n",
+             4 * c, 4 * c + 3, span / d, (comp - span) / d, wait / d, (comp - span + wait) / d);
+    }
   }
   return 0;
 }
