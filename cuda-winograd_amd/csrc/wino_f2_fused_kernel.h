@@ -408,6 +408,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
 
   unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0, st_span = 0;   // ABLATE & PROBE_PHASES: phase stamps
   unsigned long long st_ph[4] = {0, 0, 0, 0};   // epilogue phases: barrier, A^T m A, slab+ticket, gather+finalize
+  unsigned long long st_sub[PH_NSUB] = {0, 0, 0, 0, 0, 0};   // ... and the parts of A^T m A and of gather+finalize (PH_SUB0 + PHS_*)
   auto stamp = [&]() -> unsigned long long {
     unsigned long long t;
     __builtin_amdgcn_sched_barrier(0);
@@ -768,8 +769,8 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   };
 
   // ---- per-wave epilogue (the DMA pipeline keeps running underneath) -------------------------
-  // Slab image of one partial segment: [wave 0..7][q = 2r+cb][lane] of 16 B (the 2x2 output
-  // pixels of tile row 4h+r, out-channel cb*16+t16, pre-BN).  Waves hand their 8 KiB parts over
+  // Slab image of one partial segment: [wave 0..7][q = 4cb+p][lane] of 16 B (output pixel p of the
+  // tile rows 4h .. 4h+3, out-channel cb*16+t16, pre-BN).  Waves hand their 8 KiB parts over
   // independently: wave w of every segment of an item draws on tickets[8*item + w].
   //
   // A segment ends with the item's last chunk or with the range.  Whole segments are finalized
@@ -786,6 +787,9 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   auto epilogue = [&](bool last_of_range, int rfree, int ufree) {
     unsigned long long ph_t = 0;
     auto phase = [&](int k) { if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (k >= 0) st_ph[k] += t - ph_t; ph_t = t; } };
+    // the finer stamps (PHS_*): sub(-1) starts a stretch, sub(k) books the time since the last stamp on part k
+    unsigned long long sub_t = 0;
+    auto sub = [&](int k) { if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (k >= 0) st_sub[k] += t - sub_t; sub_t = t; } };
     phase(-1);
     // every wave is done reading those two stages (a bare barrier: no memory counter needs to
     // drain here, and __syncthreads() would wait for the LDS-DMA pieces in flight)
@@ -859,60 +863,90 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     //   row transform:  Y[0][b] = c_b(0) + c_b(1) + c_b(2),  Y[1][b] = c_b(1) - c_b(2) - c_b(3)
     // of which this wave can form the part of its two rows:
     //   ph = 0:  P[0][b] = c_b(0) + c_b(1),  P[1][b] = c_b(1)      ph = 1:  P[0][b] = c_b(2),  P[1][b] = -(c_b(2) + c_b(3))
-    // (selects on the wave-uniform ph, no multiplies by 0 / +-1: exact, and an Inf in one part cannot
-    // turn the other into NaN).  Pixel index p = 2a + b.
+    // (no multiplies by 0 / +-1: exact, and an Inf in one part cannot turn the other into NaN).  Pixel index p = 2a + b.
     // The parts of logical column blocks 2, 3 go to the partner wave (w ^ 1, the same tiles) through
     // this wave's 8 KB of the free LDS stages; the partner's parts of MY blocks 0, 1 come back the same
-    // way.  y[r][cb] = the 2x2 output pixels of tile row 4h+r, out-channel (32 ph) + cb*16 + t16 --
+    // way.  y[cb][p][r] = output pixel p of tile row 4h+r, out-channel (32 ph) + cb*16 + t16 --
     // from here on exactly what the wave held when it owned 16 points of 32 out-channels.
-    const bool ph1 = (wv & 1) != 0;
-    auto part = [&](int r, int cb) {
-      float c[2][2];
+    // The two halves differ only in which of {c(0), c(0) + c(1), c(1)} they form, so the code exists once per ph behind
+    // ONE wave-uniform branch (outside the MFMA loop it is free) and each side computes only what it stores -- as
+    // selects on ph this was four v_cndmask per part() on top of both candidates.  The minus of P[1][b], ph = 1, is
+    // folded into the add that consumes the part: that wave keeps and sends the plain sum S = c_b(2) + c_b(3), and
+    //   ph = 0 (receives S from its partner):  Y[1][b] = P[1][b] - S      ph = 1 (holds S itself):  Y[1][b] = X - S
+    // -- x + (-s) and x - s are the same IEEE operation, so every output keeps its bits.
+    // Everything below is written on PAIRS of tile rows (r, r + 1): they sit in adjacent registers of every
+    // accumulator, so each add of the transform is one v_pk_add_f32 on register pairs as they lie -- per (r, cb) and
+    // scalar, the compiler packed across the points instead and paid a v_mov_b32 per operand to line them up.  The
+    // price is the layout of the result: y[cb][p] holds pixel p of the four tile rows r (not the four pixels of one
+    // row); the exchange, the slab and BN + ReLU are elementwise and do not care, the transpose below picks its scalars
+    // by index.
+    f32x4 y[2][4];
+    auto atma = [&](auto ph_c) {
+      constexpr bool PH1 = decltype(ph_c)::value;
+      auto parts = [&](int cb, f32x4 (&o)[4]) {   // of column block cb: o[p = 2a + b], over the four tile rows
 #pragma unroll
-      for (int i = 0; i < 2; i++) {
-        const float m0 = acc[i * 4 + 0][cb][r], m1 = acc[i * 4 + 1][cb][r];
-        const float m2 = acc[i * 4 + 2][cb][r], m3 = acc[i * 4 + 3][cb][r];
-        c[i][0] = m0 + m1 + m2;
-        c[i][1] = m1 - m2 - m3;
-      }
-      f32x4 o;
+        for (int rp = 0; rp < 2; rp++) {
+          P2 c[2][2];
 #pragma unroll
-      for (int bb = 0; bb < 2; bb++) {
-        const float sum = c[0][bb] + c[1][bb];
-        o[bb] = ph1 ? c[0][bb] : sum;          // a = 0
-        o[2 + bb] = ph1 ? -sum : c[1][bb];     // a = 1
-      }
-      return o;
-    };
-    f32x4 y[4][2];
-    {
+          for (int i = 0; i < 2; i++) {
+            const f32x4 &q0 = acc[i * 4 + 0][cb], &q1 = acc[i * 4 + 1][cb], &q2 = acc[i * 4 + 2][cb], &q3 = acc[i * 4 + 3][cb];
+            const P2 m0 = rp ? q0.zw : q0.xy, m1 = rp ? q1.zw : q1.xy, m2 = rp ? q2.zw : q2.xy, m3 = rp ? q3.zw : q3.xy;
+            c[i][0] = m0 + m1 + m2;
+            c[i][1] = m1 - m2 - m3;
+          }
+#pragma unroll
+          for (int bb = 0; bb < 2; bb++) {
+            const P2 a0 = PH1 ? c[0][bb] : c[0][bb] + c[1][bb];   // a = 0
+            const P2 a1 = PH1 ? c[0][bb] + c[1][bb] : c[1][bb];   // a = 1 (ph = 1: S, its minus is in the consumer)
+            if (rp) o[bb].zw = a0, o[2 + bb].zw = a1;
+            else o[bb].xy = a0, o[2 + bb].xy = a1;
+          }
+        }
+      };
       char* const xmine = wreg + ln * 16;
       const char* const xpart = smem + ((wv ^ 1) < 4 ? rfree + (wv ^ 1) * 8192 : ufree + ((wv ^ 1) - 4) * 8192) + ln * 16;
 #pragma unroll
-      for (int r = 0; r < 4; r++)
+      for (int cb = 0; cb < 2; cb++) {
+        f32x4 o[4];
+        parts(2 + cb, o);
 #pragma unroll
-        for (int cb = 0; cb < 2; cb++) *(f32x4*)(xmine + (2 * r + cb) * 1024) = part(r, 2 + cb);
+        for (int pp = 0; pp < 4; pp++) *(f32x4*)(xmine + (4 * cb + pp) * 1024) = o[pp];
+      }
 #pragma unroll
-      for (int r = 0; r < 4; r++)
-#pragma unroll
-        for (int cb = 0; cb < 2; cb++) y[r][cb] = part(r, cb);
+      for (int cb = 0; cb < 2; cb++) parts(cb, y[cb]);
+      sub(PHS_PARTS);
       // every wave's outgoing parts are in LDS (its own ds_writes drained) before anyone reads them
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
 #pragma unroll
-      for (int r = 0; r < 4; r++)
+      for (int cb = 0; cb < 2; cb++)
 #pragma unroll
-        for (int cb = 0; cb < 2; cb++) y[r][cb] += *(const f32x4*)(xpart + (2 * r + cb) * 1024);
+        for (int pp = 0; pp < 4; pp++) {
+          const f32x4 x = *(const f32x4*)(xpart + (4 * cb + pp) * 1024);
+          if (pp < 2) y[cb][pp] += x;
+          else y[cb][pp] = PH1 ? x - y[cb][pp] : y[cb][pp] - x;
+        }
       // ... and read, before the finalize below stages output rows through the same LDS
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();
       asm volatile("" ::: "memory");
-    }
+    };
+    sub(-1);
+    if (wv & 1) atma(std::true_type{});
+    else atma(std::false_type{});
+    sub(PHS_EXCHANGE);
 #pragma unroll
     for (int e = 0; e < 8; e++)
 #pragma unroll
       for (int cb = 0; cb < 4; cb++) acc[e][cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
+    if (ABLATE & PROBE_PHASES) {   // (the stamp must not be overtaken by the moves: they have no other reader before the next body)
+#pragma unroll
+      for (int e = 0; e < 8; e++)
+#pragma unroll
+        for (int cb = 0; cb < 4; cb++) asm volatile("" : "+v"(acc[e][cb]));
+    }
+    sub(PHS_ZERO);
     phase(1);
     const bool whole = !TAIL || (seg_kind & 1) != 0;
     // up to two items to look at: [0] this segment's, [1] the deferred head segment's
@@ -933,7 +967,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       const unsigned my_slot = 2u * (unsigned)(tp.lp * tp.kpg + tp.grp) + ((seg_kind & 2) ? 1u : 0u);
 #pragma unroll
       for (int q = 0; q < 8; q++)
-        slab_store16(y[q >> 1][q & 1], rsrc_slab, slab_voff + q * 1024, my_slot * SLAB_BYTES);
+        slab_store16(y[q >> 2][q & 3], rsrc_slab, slab_voff + q * 1024, my_slot * SLAB_BYTES);
       // When is this segment's ticket drawn?  Whoever draws an item's last ticket gathers it, and a gather is
       // 3-5 us of work that only an epilogue can do:
       //  * the range's last segment: now (there is no later epilogue);
@@ -989,6 +1023,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
                        // drawer is certain to see a value >= nseg -- the report above cannot be missed.)
           __hip_atomic_fetch_sub(tickets + (size_t)item * 8 + wv, (unsigned)nseg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // gather: all segments' parts, summed in segment order
+        sub(-1);
         bool first = true;
 #pragma unroll 1
         for (int g = gA; g <= gB; g++) {
@@ -998,11 +1033,16 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
 #pragma unroll
           for (int q = 0; q < 8; q++) t[q] = slab_load16(rsrc_slab, slab_voff + q * 1024, slot * SLAB_BYTES);
 #pragma unroll
-          for (int q = 0; q < 8; q++) y[q >> 1][q & 1] = first ? t[q] : y[q >> 1][q & 1] + t[q];
+          for (int q = 0; q < 8; q++) y[q >> 2][q & 3] = first ? t[q] : y[q >> 2][q & 3] + t[q];
           first = false;
         }
+        sub(PHS_GATHER);
       }
       float sc2[2] = {bn_sc[0], bn_sc[1]}, bi2[2] = {bn_bi[0], bn_bi[1]};
+      // relu_nan() with the run-time `relu` folded into its threshold (nothing is below -Inf, and a NaN compares false
+      // either way): one compare and one select per element, where testing `relu` per element cost a second select
+      const float relu_thr = relu ? 0.f : -__builtin_inff();
+      auto relu_if = [&](float v) { return v < relu_thr ? 0.f : v; };
       if (item != c_item) load_bn(item, sc2, bi2);   // the deferred head item
       if (ABLATE & PROBE_NO_STORE) continue;  // price the store tail
 
@@ -1014,6 +1054,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       // XORed with (tile>>2)&3 = the MFMA row group h, which makes the ds_write_b32 of the 4 row
       // groups and the ds_read_b128 of every 16 lanes hit 64 distinct banks.
       const int tb = item / KBLK, kb = item - tb * KBLK;
+      sub(-1);
       // RES: the eight residual runs this lane stores are requested before the transpose, so that their latency hides
       // under it; each only where its store is kept (the residual's ring is never read)
       f32x4 rv[RES ? 8 : 1];
@@ -1040,19 +1081,21 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         // hit the four 16-bank quarters, and the two rows a 16-lane ds_read_b128 group reads are consecutive (the
         // two 32-bank halves).
 #pragma unroll
-        for (int r = 0; r < 4; r++) {
+        for (int cb = 0; cb < 2; cb++) {
+          f32x4 m = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int cb = 0; cb < 2; cb++) {
-            float m = 0.f;
+          for (int pp = 0; pp < 4; pp++) {
+            f32x4 v1 = __builtin_elementwise_fma((f32x4){sc2[cb], sc2[cb], sc2[cb], sc2[cb]}, y[cb][pp], (f32x4){bi2[cb], bi2[cb], bi2[cb], bi2[cb]});   // (two v_pk_fma_f32)
 #pragma unroll
-            for (int pp = 0; pp < 4; pp++) {
-              float v1 = sc2[cb] * y[r][cb][pp] + bi2[cb];
-              if (relu) v1 = relu_nan(v1);
-              m = pp == 0 ? v1 : max_nan(m, v1);
+            for (int r = 0; r < 4; r++) {
+              v1[r] = relu_if(v1[r]);
+              m[r] = pp == 0 ? v1[r] : max_nan(m[r], v1[r]);
             }
-            *(float*)(wreg + (4 * r + e_h) * 128 + ((cb ^ (e_h >> 1)) << 6) + e_t16 * 4) = m;
           }
+#pragma unroll
+          for (int r = 0; r < 4; r++) *(float*)(wreg + (4 * r + e_h) * 128 + ((cb ^ (e_h >> 1)) << 6) + e_t16 * 4) = m[r];
         }
+        sub(PHS_BN);
         // lane -> row P = 8 i + (lane >> 3) = tile 4 (P & 3) + (P >> 2), 16-byte chunk lane & 7: two rounds of eight
         // whole 128-byte runs
         const unsigned kbyte = (unsigned)((kb * KB + e_wk * 32 + (ln & 7) * 4) * sizeof(float));
@@ -1069,6 +1112,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
           const bool keep = live && (!GEN || (py <= Hq - 2 && pxx <= Wq - 2));
           if (keep) buf_store16_nt(val, rsrc_out, (unsigned)((img + py * Wq + pxx) * K * sizeof(float)) + kbyte, 0);
         }
+        sub(PHS_STORE);
         continue;
       }
       int ep_wbase[4], ep_rbase[4];
@@ -1079,18 +1123,19 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         ep_rbase[jj] = (ln >> 5) * 512 + (((px * 2 + (c >> 2)) ^ jj) << 6) + (c & 3) * 16;   // + 2i*512
       }
 #pragma unroll
-      for (int r = 0; r < 4; r++) {
+      for (int cb = 0; cb < 2; cb++) {
 #pragma unroll
-        for (int cb = 0; cb < 2; cb++) {
+        for (int pp = 0; pp < 4; pp++) {
+          f32x4 v1 = __builtin_elementwise_fma((f32x4){sc2[cb], sc2[cb], sc2[cb], sc2[cb]}, y[cb][pp], (f32x4){bi2[cb], bi2[cb], bi2[cb], bi2[cb]});   // (two v_pk_fma_f32)
+          const int g = pp * 2 + cb;
 #pragma unroll
-          for (int pp = 0; pp < 4; pp++) {
-            float v1 = sc2[cb] * y[r][cb][pp] + bi2[cb];
-            if (!RES && relu) v1 = relu_nan(v1);   // (RES: after the residual's add, below)
-            const int g = pp * 2 + cb;
-            *(float*)(wreg + ep_wbase[g & 3] + r * 512 + (g >> 2) * 256) = v1;
+          for (int r = 0; r < 4; r++) {
+            if (!RES) v1[r] = relu_if(v1[r]);   // (RES: after the residual's add, below)
+            *(float*)(wreg + ep_wbase[g & 3] + r * 512 + (g >> 2) * 256) = v1[r];
           }
         }
       }
+      sub(PHS_BN);
       // lane -> run (lane>>3) = (tile 2i + (lane>>5), px (lane>>3)&3), 16-byte chunk lane&7
       // (tried: the tile arithmetic on the scalar unit, one tile per half-wave -- 40 % slower)
       const int px = (ln >> 3) & 3, pa = px >> 1, pb = px & 1;
@@ -1123,6 +1168,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         // scalar pushed SGPR spill code into the MFMA loop.)
         if (keep) buf_store16_nt(val, rsrc_out, (unsigned)((img + py * Wp + pxx) * K * sizeof(float)) + kbyte, 0);
       }
+      sub(PHS_STORE);
     }
     phase(3);
   };
@@ -1241,6 +1287,8 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       dbg[PH_EPI0 + 2] = st_ph[2];
       dbg[PH_EPI0 + 3] = st_ph[3];
       dbg[PH_SPAN] = st_span;
+#pragma unroll
+      for (int k = 0; k < PH_NSUB; k++) dbg[PH_SUB0 + k] = st_sub[k];
     }
   }
   if (ABLATE & PROBE_TIMELINE) {

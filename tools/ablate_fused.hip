@@ -201,6 +201,18 @@ int main(int argc, char** argv) {
       printf("  wave %d: wait(vmcnt+barrier) %6.0f  compute %6.0f cycles per iteration (wait share %4.1f%%) | epilogues per workgroup %7.0f cycles = barrier %6.0f + AtmA %6.0f + slab/ticket %6.0f + gather/finalize %6.0f\n", w,
              sum[w][PH_WAIT] / wgs / iters, sum[w][PH_COMPUTE] / wgs / iters, 100.0 * sum[w][PH_WAIT] / (sum[w][PH_WAIT] + sum[w][PH_COMPUTE]), sum[w][PH_EPILOGUE] / wgs,
              sum[w][PH_EPI0 + 0] / wgs, sum[w][PH_EPI0 + 1] / wgs, sum[w][PH_EPI0 + 2] / wgs, sum[w][PH_EPI0 + 3] / wgs);
+    // the finer epilogue stamps (PHS_*), per wave class: the parts of A^T m A and of gather + finalize, cycles per workgroup
+    for (int c = 0; c < 2; c++) {
+      double sub[PH_NSUB] = {0}, atma = 0, fin = 0;
+      for (int w = 4 * c; w < 4 * c + 4; w++) {
+        for (int k = 0; k < PH_NSUB; k++) sub[k] += sum[w][PH_SUB0 + k] / (4.0 * wgs);
+        atma += sum[w][PH_EPI0 + 1] / (4.0 * wgs); fin += sum[w][PH_EPI0 + 3] / (4.0 * wgs);
+      }
+      printf("  waves %d-%d: AtmA %6.0f = parts %6.0f + exchange (2 barriers) %6.0f + re-zeroing %6.0f | gather/finalize %6.0f = slab loads+adds %6.0f + BN/ReLU/LDS writes %6.0f"
+             " + LDS read/decode/store %6.0f + bookkeeping, ticket wait %6.0f cycles per workgroup\n",
+             4 * c, 4 * c + 3, atma, sub[PHS_PARTS], sub[PHS_EXCHANGE], sub[PHS_ZERO], fin, sub[PHS_GATHER], sub[PHS_BN], sub[PHS_STORE],
+             fin - sub[PHS_GATHER] - sub[PHS_BN] - sub[PHS_STORE]);
+    }
     // where an iteration's compute part ends: barrier release -> last MFMA (the MFMA span), last MFMA -> arrival at the
     // next barrier (transform burst, DMA walker, loop control), arrival -> release; per wave class (waves 0-3 / 4-7)
     for (int c = 0; c < 2; c++) {
