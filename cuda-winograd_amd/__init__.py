@@ -788,6 +788,14 @@ def roi_align(levels, rois, P: int, scales, sampling: int = 2, in_padded: bool =
     return out
 
 
+def roi_align_launches(R: int, P: int, out_padded: bool = False) -> int:
+    """How many kernel launches roi_align splits R boxes into (host-side): one until R (P + 2 out_padded)^2 passes 2^31, or
+    the developer knob WINO_ROI_LAUNCH_TASKS."""
+    n = c_long(0)
+    _check(lib().wino_roi_align_launches(int(R), int(P), int(bool(out_padded)), ctypes.byref(n)), "wino_roi_align_launches")
+    return int(n.value)
+
+
 def boxes_to_rois(boxes) -> torch.Tensor:
     """torchvision's convert_to_roi_format: a list of per-image [L_i][4] box tensors -> [K][5] with the image index in
     front, by torch ops on the device (no host synchronisation); a [K][5] tensor passes through."""

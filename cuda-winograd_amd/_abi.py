@@ -173,6 +173,7 @@ SIGNATURES = {
     "wino_resize_bilinear_plan": (i, [i] * 8 + [ip]),
     # ---- multi-scale RoIAlign
     "wino_roi_align_hw": (i, [vp] * 4 + [ip, fptr] + [i] * 4 + [vp] + [i] * 3 + [c_float, i, vp, i, vp]),
+    "wino_roi_align_launches": (i, [i] * 3 + [POINTER(c_long)]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

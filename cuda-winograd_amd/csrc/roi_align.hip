@@ -167,6 +167,15 @@ __global__ __launch_bounds__(64 * ROI_WAVES, 4) void roi_align_kernel(const RoiA
   }
 }
 
+// Boxes per launch: a launch's tasks (boxes x Q x Q) stay within 2^31 -- at least 493 k boxes, 2^31 at Q = 1 -- or within
+// the developer knob WINO_ROI_LAUNCH_TASKS when that is positive (tests run the split loop with it); one box at least.
+long roi_boxes_per_launch(unsigned QQ) {
+  const int cap = knobs().roi_launch_tasks;
+  const unsigned long long tasks = cap > 0 ? (unsigned long long)cap : 1ull << 31;
+  const long n = (long)(tasks / QQ);
+  return n > 0 ? n : 1;
+}
+
 template <int S>
 void launch_roi(const RoiArgs& a, hipStream_t s) {
   const unsigned blocks = (a.tasks + ROI_WAVES - 1) / ROI_WAVES;
@@ -271,7 +280,7 @@ extern "C" int wino_roi_align_hw(const float* f0, const float* f1, const float* 
   a.divQQ = make_fastdiv((unsigned)(Q * Q));
   a.divQ = make_fastdiv((unsigned)Q);
   const unsigned QQ = (unsigned)(Q * Q);
-  const long per_launch = (long)((1ull << 31) / QQ);   // boxes per launch: tasks <= 2^31 (at least 493 k boxes; 2^31 at Q = 1)
+  const long per_launch = roi_boxes_per_launch(QQ);
   for (long r0 = 0; r0 < R; r0 += per_launch) {
     const long n = R - r0 < per_launch ? R - r0 : per_launch;
     a.tasks = (unsigned)(n * QQ);
@@ -285,5 +294,17 @@ extern "C" int wino_roi_align_hw(const float* f0, const float* f1, const float* 
     }
     if (int rc = launch_status("roi_align_kernel")) return rc;
   }
+  return WINO_OK;
+}
+
+extern "C" int wino_roi_align_launches(int R, int P, int out_padded, long* launches) {
+  if (R < 0 || P < 1 || P > ROI_MAX_P || (out_padded != 0 && out_padded != 1)) {
+    set_error("roi_align_launches: unsupported shape R=%d P=%d out_padded=%d", R, P, out_padded);
+    return WINO_E_SHAPE;
+  }
+  if (int rc = check_nonnull(launches)) return rc;
+  const int Q = P + 2 * out_padded;
+  const long per_launch = roi_boxes_per_launch((unsigned)(Q * Q));
+  *launches = (R + per_launch - 1) / per_launch;
   return WINO_OK;
 }

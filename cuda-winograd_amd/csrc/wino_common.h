@@ -97,6 +97,7 @@ struct Knobs {
   int small_ks;       // WINO_1X1_SMALL_KS: K-split of the 1x1 latency kernel, 1 / 2 / 4 (0 = policy)
   int small_rt, small_ct;   // WINO_1X1_SMALL_RT / _CT: MFMA row / column tiles per wave, 1 / 2 (0 = policy)
   int stem_form;      // WINO_STEM_FORM: 0 automatic, 1 8x8-pool tiles x 64 channels, 2 4x4-pool tiles x 16 channels
+  int roi_launch_tasks;   // WINO_ROI_LAUNCH_TASKS: most output positions (boxes x Q x Q) of one RoIAlign launch (<= 0: 2^31)
 };
 Knobs knobs();
 #define WINO_HIP(call)                                          \

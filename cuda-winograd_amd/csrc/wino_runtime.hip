@@ -151,6 +151,7 @@ void read_knobs() {
   k.small_rt = env_num("WINO_1X1_SMALL_RT", 0);
   k.small_ct = env_num("WINO_1X1_SMALL_CT", 0);
   k.stem_form = env_num("WINO_STEM_FORM", 0);
+  k.roi_launch_tasks = env_num("WINO_ROI_LAUNCH_TASKS", 0);
   g_knobs = k;
 }
 }  // namespace

@@ -65,7 +65,7 @@ extern "C" {
  * wino_conv3x3_dilated_prepare_hw, wino_conv3x3_dilated_plan, wino_dilated_residual_block_hw,
  * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
- * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_roi_align_launches, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -779,11 +779,15 @@ int wino_resize_bilinear_plan(int h, int w, int C, int ld, int Ho, int Wo, int w
  * output below 2^31 elements (WINO_E_SHAPE otherwise); any R (the output may pass 4 GiB).  R == 0 is WINO_OK and launches
  * nothing.  A NULL or not 16-byte-aligned pointer, an overlap of out with a level map or with rois, a bad scale_host
  * sequence, or a canonical_scale that is not finite and positive is WINO_E_ARG.  No workspace and no stream scratch: the
- * call can be captured into a graph as it is. */
+ * call can be captured into a graph as it is.
+ * A call whose R (P + 2 out_padded)^2 output positions pass 2^31 runs as several launches of whole boxes, each from its
+ * own rois and out base.  wino_roi_align_launches (host only) answers how many launches R boxes take; the developer knob
+ * WINO_ROI_LAUNCH_TASKS = t > 0 lowers the 2^31 to t (one box per launch at the least), a value <= 0 is ignored. */
 int wino_roi_align_hw(const float* f0, const float* f1, const float* f2, const float* f3, const int* hw_host,
                       const float* scale_host, int levels, int N, int C, int in_padded, const float* rois, int R, int P,
                       int sampling, float canonical_scale, int canonical_level, float* out, int out_padded,
                       wino_stream_t s);
+int wino_roi_align_launches(int R, int P, int out_padded, long* launches);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */

@@ -91,6 +91,8 @@ def macs(case: Case) -> float:
         return px * (28.0 * s["Cin"] * s["Cb"] + 5.0 * s["Cb"] * s["Kout"]) + s["N"] * s["Cb"] * (s["Cin"] + s["Kout"])
     if e == "resize_bilinear":
         return 4.0 * s["N"] * s["C"] * s["Ho"] * s["Wo"]
+    if e == "fpn_level":
+        return float(s["N"]) * s["H"] * s["W"] * (s["Cin"] * s["Cf"] + 9.0 * s["Cf"] * s["Cf"])
     if e == "conv3x3_grouped_bn_relu":
         H, W = grouped_out(s["Hin"], s["Win"], s["stride"])
         return 9.0 * s["N"] * H * W * s["C"] * (s["C"] // s["groups"])
@@ -720,7 +722,80 @@ def grouped_block_cases():
     return cases
 
 
+# ---- one level of the Feature Pyramid Network ---------------------------------------------------------------------------
+# the forced forms of the level's second launch, the Winograd 3x3 Cf -> Cf: the throughput kernel with and without a
+# stream-K tail, the latency kernel without and with a C split (the knob sets of nonfinite.forms_3x3, spelt out by
+# fpn_out_knobs); the first launch, the lateral 1x1 with the top-down read, takes the forms of forms_1x1.FORMS
+FPN_OUT_FORMS = ("auto", "big_tail", "big_whole", "small_split1", "small_split2")
+FPN_CIN, FPN_CF = (32, 96, 160, 256), (64, 128, 192, 256)
+# H = 1, W = 1, odd x odd (the last row and column read a coarse pixel alone), every Cin and three Cf
+FPN_PINS = [{"H": 1, "Cin": 32}, {"W": 1, "Cf": 64}, {"odd": True, "Cin": 96, "Cf": 192}, {"Cin": 160, "Cf": 128},
+            {"Cin": 256, "Cf": 192}, {"odd": True, "Cf": 64}, {"Cin": 32, "Cf": 128}, {"N": 6, "Cin": 96}]
+FPN_MACS = MAX_MACS / 4
+# the automatic forms no draw of the envelope takes: the stream-K lateral needs more k-steps (Cin = 512), the throughput
+# 3x3 more tiles than six images have
+FPN_AUTO = [{"N": 6, "H": 40, "W": 40, "Cin": 512, "Cf": 64}, {"N": 72, "H": 16, "W": 15, "Cin": 32, "Cf": 64}]
+
+
+def fpn_lateral_forms():
+    import forms_1x1   # (forms_1x1 imports this module)
+    return forms_1x1.FORMS
+
+
+def fpn_lateral_legal(form, sh):
+    """Whether the lateral GEMM of the shape can take the forced form: the latency kernel's divisibility rules
+    (conv1x1.hip small1_legal), a stream-K grid with a range for every column block."""
+    import forms_1x1
+    kn = forms_1x1.FORMS[form]
+    M, Cin, Cf = sh["N"] * sh["H"] * sh["W"], sh["Cin"], sh["Cf"]
+    if form.startswith("latency"):
+        ks, ct = kn["WINO_1X1_SMALL_KS"], kn["WINO_1X1_SMALL_CT"]
+        return Cin % (16 * ks) == 0 and Cf % ((4 // ks) * ct * 16) == 0 and not (ks > 1 and Cin // ks < 64)
+    if form.startswith("sk"):
+        return forms_1x1.sk_plan(M, Cin, Cf, kn["WINO_1X1_SK_GRID"])[0]
+    return True
+
+
+def fpn_out_knobs(form, sh):
+    items = _items_3x3(sh["N"], sh["H"], sh["W"], sh["Cf"])
+    return {"auto": {},
+            "big_tail": {"WINO_3X3_ALGO": "big", "WINO_SK_GRID": items + 1 + (items == 1)},
+            "big_whole": {"WINO_3X3_ALGO": "big", "WINO_SK_GRID": items},
+            "small_split1": {"WINO_3X3_ALGO": "small", "WINO_SMALL_CT": 1, "WINO_SMALL_SPLIT": 1},
+            "small_split2": {"WINO_3X3_ALGO": "small", "WINO_SMALL_CT": 2, "WINO_SMALL_SPLIT": 2}}[form]
+
+
+def fpn_forms():
+    """(lateral form, 3x3 form) of every forced case: each lateral form once, the 3x3 forms in turn beside them."""
+    laterals = [f for f in fpn_lateral_forms() if f != "auto"]
+    return [(lat, FPN_OUT_FORMS[i % len(FPN_OUT_FORMS)]) for i, lat in enumerate(laterals)]
+
+
+def fpn_level_cases():
+    rng = np.random.RandomState(7373)
+    entry = "fpn_level"
+    cases = []
+
+    def make(r):
+        return {"N": int(r.randint(1, 7)), "H": int(r.randint(1, 41)), "W": int(r.randint(1, 41)),
+                "Cin": int(r.choice(FPN_CIN)), "Cf": int(r.choice(FPN_CF))}
+
+    def flags(i):
+        return {"top": bool(i % 4 != 3), "c_padded": bool(i % 3 == 0), "nonneg": bool(i % 5 == 1)}
+
+    pairs = [("auto", "auto")] * len(FPN_PINS) + fpn_forms()
+    for i, (lat, out) in enumerate(pairs):
+        ok = lambda sh: macs(Case(entry, sh)) <= FPN_MACS and fpn_lateral_legal(lat, sh)
+        sh = _draw(rng, make, ok, entry, FPN_PINS[i % len(FPN_PINS)])
+        knobs = {**fpn_lateral_forms()[lat], **fpn_out_knobs(out, sh)}
+        cases.append(Case(entry, sh, knobs or None, f"{lat}+{out}" if knobs else None, flags(i)))
+    for sh in FPN_AUTO:
+        cases.append(Case(entry, dict(sh), None, None, flags(len(cases))))
+    return cases
+
+
 GENERATORS = {
+    "fpn_level": fpn_level_cases,
     "conv3x3_grouped_bn_relu": grouped_cases,
     "grouped_block": grouped_block_cases,
     "conv3x3_dilated_bn_relu": dilated_cases,
@@ -829,6 +904,12 @@ def plan_form(pkg, case, cus=CUS):
         else:
             tail = form_1x1(pkg, s["N"] * H * W, s["Cm"], s["C4"], cus)
         return {"form": f"{first}/{mid['form']}/{tail}", "first": first, "mid": mid, "tail": tail}
+    if e == "fpn_level":   # the lateral 1x1 (the top-down read does not alter its plan), then the Winograd 3x3 Cf -> Cf
+        M = s["N"] * s["H"] * s["W"]
+        lat = form_1x1(pkg, M, s["Cin"], s["Cf"], cus)
+        out, d = plan_3x3(pkg, s["N"], s["H"], s["W"], s["Cf"], s["Cf"], cus)
+        return {"form": f"{lat}/{out}", "lateral": lat, "small": pkg.small_plan_1x1_full(M, s["Cin"], s["Cf"], cus)[1:4],
+                "grid_1x1": sk_ranges(pkg, M, s["Cin"], s["Cf"], 1, cus)["grid"], "out": {"form": out, **d}}
     if e == "resize_bilinear":
         form = pkg.resize_bilinear_plan(s["h"], s["w"], s["C"], s["ld"], s["Ho"], s["Wo"], s["outputs"] != "labels",
                                         s["outputs"] != "out")
@@ -883,6 +964,25 @@ def check_forced(case, plan) -> str | None:
         return None if ok else f"want {f} for all three launches, plan {plan}"
     if e == "grouped_block":   # (the grouped 3x3 has one form per shape: nothing to force)
         return None if (plan["first"], plan["tail"]) == (f, f) else f"want {f} for both 1x1 launches, plan {plan}"
+    if e == "fpn_level":
+        lat, out = f.split("+")
+        if lat == "tiled" and plan["lateral"] != "tiled":
+            return f"want a tiled lateral, plan {plan}"
+        if lat.startswith("sk") and not (plan["lateral"] == "stream_k" and 0 < plan["grid_1x1"] <= kn["WINO_1X1_SK_GRID"]):
+            return f"want a stream-K lateral of at most {kn['WINO_1X1_SK_GRID']} workgroups, plan {plan}"
+        if lat.startswith("latency"):
+            ksrc = (kn["WINO_1X1_SMALL_KS"], kn["WINO_1X1_SMALL_RT"], kn["WINO_1X1_SMALL_CT"])
+            if plan["lateral"] != "latency" or tuple(plan["small"]) != ksrc:
+                return f"want a latency lateral with (ks, rt, ct) = {ksrc}, plan {plan}"
+        o = plan["out"]
+        if out.startswith("big"):
+            if o["form"] != "throughput" or o["grid"] != kn["WINO_SK_GRID"] or (o["tail"] > 0) != (out == "big_tail"):
+                return f"want the 3x3 throughput kernel at grid {kn['WINO_SK_GRID']} ({out}), plan {plan}"
+        if out.startswith("small"):
+            want = {"form": "latency", "split": kn["WINO_SMALL_SPLIT"], "ct": kn["WINO_SMALL_CT"]}
+            if o != want:
+                return f"want the 3x3 as {want}, plan {plan}"
+        return None
     raise KeyError(e)
 
 
@@ -930,6 +1030,8 @@ def sizes(pkg, case) -> dict:
         return d
     if e == "aspp":
         return {"workspace": pkg.aspp_workspace_bytes(s["N"], s["H"], s["W"], s["Cin"], s["Cb"], s["Kout"])}
+    if e == "fpn_level":
+        return {"U": L.wino_filter_f2_elems(s["Cf"], s["Cf"])}
     if e in ("conv3x3_dilated_bn_relu", "conv1x1_cat_bn", "resize_bilinear"):
         return {}   # (no pack or workspace query of their own)
     raise KeyError(e)

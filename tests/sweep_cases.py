@@ -15,6 +15,7 @@ import resize_cases as RC
 import shape_sweeps as S
 from cases import TIGHT
 from dilated_cases import dilated_reference
+from fpn_reference import level_reference
 
 SENTINEL = 1234.5
 CHECKS = collections.Counter()   # arena.check calls that passed, by entry point
@@ -22,7 +23,7 @@ WORST = {}                       # the largest relative error close() saw, by en
 # the first seed of the segmentation entries' sweeps (case i takes seed + i): tests/test_shape_sweeps_host.py rebuilds
 # the same tensors for the conditions it proves on the references
 SEEDS = {"conv3x3_dilated_bn_relu": 1000, "dilated_block": 1100, "conv1x1_cat_bn": 1200, "aspp": 1300,
-         "resize_bilinear": 1400, "conv3x3_grouped_bn_relu": 1500, "grouped_block": 1600}
+         "resize_bilinear": 1400, "conv3x3_grouped_bn_relu": 1500, "grouped_block": 1600, "fpn_level": 1700}
 
 
 @contextlib.contextmanager
@@ -184,6 +185,33 @@ def run_sweep(entry, run, pkg, knobs, torch_dev, seed0):
     if entry in WORST:
         print(f"{entry}: {len(cases)} cases, worst rel err {WORST[entry]:.2e}")
     assert done == 2 * len(cases), f"{entry}: {done} guard checks for {len(cases)} cases at two placements"
+
+
+# ---- one FPN level -------------------------------------------------------------------------------------------------------
+def fpn_level_case(pkg, knobs, torch_dev, case, seed):
+    """inner = conv1x1(c) + bias [+ nearest-upsampled top], P = conv3x3(inner) + bias: c and top carry NaN rings (not
+    read), inner and P rings of exact 0, both held against fpn_reference.level_reference."""
+    sw = start(pkg, knobs, torch_dev, case, seed)
+    torch, nan = sw.torch, float("nan")
+    N, H, W, Cin, Cf = case.N, case.H, case.W, case.Cin, case.Cf
+    c = sw.act(N, H, W, Cin)
+    wl, wo = sw.conv_w(Cf, Cin, k=1), sw.conv_w(Cf, Cf)
+    bl, bo = sw.rand(Cf) - 0.5, sw.rand(Cf) - 0.5
+    top = sw.act(N, (H + 1) // 2, (W + 1) // 2, Cf) if case.flags["top"] else None
+    want_inner, want_P = level_reference(torch, c, wl, bl, wo, bo, top)
+    for _ in sw.passes():
+        cd = sw.d(sw.padded(c, ring=nan) if case.flags["c_padded"] else c, "c")
+        wld, U = sw.d(wl.reshape(Cf, Cin).t().contiguous(), "w_lat"), sw.U(wo)
+        bld, bod, ones = sw.d(bl, "b_lat"), sw.d(bo, "b_out"), sw.d(torch.ones(Cf), "ones")
+        topd = sw.d(sw.padded(top, ring=nan), "top") if top is not None else None
+        outs = []
+        for _ in range(2):
+            outs.append(pkg.fpn_level(cd, wld, bld, U, bod, top=topd, c_padded=case.flags["c_padded"], ones=ones,
+                                      inner=sw.nan(N, H + 2, W + 2, Cf, name="inner"), out=sw.nan(N, H + 2, W + 2, Cf, name="P")))
+        for k, (name, want) in enumerate((("inner", want_inner), ("P", want_P))):
+            sw.ring_is(outs[0][k], 0.0, name)
+            sw.close(outs[0][k][:, 1:-1, 1:-1, :], want, name)
+            sw.same(outs[0][k], outs[1][k], name)
 
 
 # ---- the residual 3x3 ------------------------------------------------------------------------------------------------

@@ -22,6 +22,7 @@ import pytest
 from aspp_cases import cat_reference
 from cases import TIGHT, BasicBlock, ResLayer, S2Block, S2Layer, V15Block, proj_oracle, proj_weights, ring_zero
 from dilated_cases import dilated_reference
+from fpn_reference import level_reference
 from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -776,3 +777,51 @@ def test_3x3_largest_accepted_filter(pkg, O, torch_dev, knobs, free_after):
             assert torch.equal(got, first), algo
     assert 0.2 < (want[:, 1:-1, 1:-1, :] > 0).mean() < 0.8
     del x, U, out
+
+
+# ------------------------------------------------------------------ one FPN level
+def test_fpn_level_beyond_4gib(pkg, O, torch_dev, free_after):
+    """fpn_level, 1025 images of 126 x 126, Cin = 32 -> Cf = 64, with the top-down read: inner and P are 4 MiB per image,
+    4.3 GB each, so image 1024 starts at byte 2^32 of both; the lateral writes inner past it and reads top at
+    (y >> 1, x >> 1) of the same image, the 3x3 reads inner and writes P past it.  c (2.1 GB, unpadded) crosses 2^31
+    bytes.  top, [1025][65 + 2][65 + 2][64], stays below 2^31 bytes: pushing it past would take an inner and a P of
+    17 GB each, and the kernel forms the coarse row's address (up2_row) in long.  On the device: both rings exactly 0,
+    every value finite; images 0, 512 and 1024 and those around 2^31 bytes of inner against the fp64 chain at TIGHT."""
+    torch, dev = torch_dev
+    N, H, W, Cin, Cf = 1025, 126, 126, 32, 64
+    P = (H + 2) * (W + 2) * Cf * 4
+    Hc, Wc = (H + 1) // 2, (W + 1) // 2
+    top_bytes = N * (Hc + 2) * (Wc + 2) * Cf * 4
+    assert P == 4 << 20 and 1024 * P == 1 << 32 and top_bytes < 1 << 31
+    _need(torch, 2 * N * P + N * H * W * Cin * 4 + top_bytes)
+    idx = sorted({0, 512, 1024} | set(_images(N, [P])))
+    g = torch.Generator(device="cpu").manual_seed(91)
+    wl = (torch.rand(Cf, Cin, 1, 1, generator=g) - 0.5) / np.sqrt(Cin) * 4
+    wo = (torch.rand(Cf, Cf, 3, 3, generator=g) - 0.5) / np.sqrt(9 * Cf) * 4
+    bl, bo = torch.rand(Cf, generator=g) - 0.5, torch.rand(Cf, generator=g) - 0.5
+    c = _rand(torch, dev, (N, H, W, Cin), 92)
+    top = _rand(torch, dev, (N, Hc + 2, Wc + 2, Cf), 93)
+    for ring in (top[:, 0], top[:, -1], top[:, :, 0], top[:, :, -1]):       # the coarse map's ring is not read
+        ring.fill_(NAN)
+    want_inner, want_P = level_reference(torch, _pick(torch, c, idx), wl, bl, wo, bo,
+                                         _pick(torch, top, idx)[:, 1:-1, 1:-1, :])
+    wld, U = wl.reshape(Cf, Cin).t().contiguous().to(dev), pkg.filter_transform_f2(wo.to(dev))
+    bld, bod, ones = bl.to(dev), bo.to(dev), torch.ones(Cf, device=dev)
+    inner = torch.empty((N, H + 2, W + 2, Cf), device=dev)
+    out = torch.empty_like(inner)
+    first = None
+    for rep in range(2):
+        inner.fill_(NAN)
+        out.fill_(NAN)
+        got = pkg.fpn_level(c, wld, bld, U, bod, top=top, ones=ones, inner=inner, out=out)
+        assert got[0].data_ptr() == inner.data_ptr() and got[1].data_ptr() == out.data_ptr()
+        torch.cuda.synchronize()
+        assert pkg.tickets_in_use() == 0
+        picked = (_check_padded(O, torch, inner, idx, want_inner.numpy(), f"inner, rep {rep}"),
+                  _check_padded(O, torch, out, idx, want_P.numpy(), f"P, rep {rep}"))
+        if first is None:
+            first = picked
+        assert torch.equal(picked[0], first[0]) and torch.equal(picked[1], first[1])
+    errs = [O.rel_error(first[k][:, 1:-1, 1:-1, :].numpy(), w.numpy()) for k, w in enumerate((want_inner, want_P))]
+    print(f"fpn_level past 4 GiB, images {idx}: inner {errs[0]:.2e} P {errs[1]:.2e}")
+    del c, top, inner, out, got

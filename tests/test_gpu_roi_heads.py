@@ -1,10 +1,16 @@
 """GPU tests of the R-CNN box and mask heads (cuda_winograd_amd.detection) and of the second stage end to end:
 ResNetFPN(padded=True) -> multiscale_roi_align -> BoxHead / MaskHead against the fp64 chain of tests/roi_cases.py and
-tests/fpn_reference.py at the project's network bar, reference_nets.NET_TOL."""
+tests/fpn_reference.py at the project's network bar, reference_nets.NET_TOL.  The two sweeps run the heads over
+roi_cases.box_head_cases() / mask_head_cases() in the automatic form and with their GEMMs forced into the tiled, the
+stream-K and the latency form, and count which form each GEMM took."""
+import collections
+
 import pytest
 import torch
 
 import roi_cases as rc
+import shape_sweeps as S
+from cases import PROJ_FORMS
 from fpn_reference import fpn_random_state_dict, fpn_reference_forward
 from gpu_support import R, rel, torch_dev  # noqa: F401
 from reference_nets import NET_TOL
@@ -132,6 +138,103 @@ def test_both_heads_in_one_graph(pkg, torch_dev):
     want_cls, _ = rc.box_head_reference(rc.box_head_state_dict(C, 7, 128, classes), rc.reference(C, 7, 2)[:boxes])
     assert rel(torch, eager[0], want_cls) < NET_TOL
     del graph
+
+
+# ---- the sweeps ------------------------------------------------------------------------------------------------------------
+FORCED = ("tiled", "stream_k", "latency")
+KNOB_NAMES = sorted({k for f in FORCED for k in PROJ_FORMS[f]} | {"WINO_3X3_ALGO"})
+
+
+def force(knobs, form, with_3x3=False):
+    for k in KNOB_NAMES:
+        knobs.unset(k)
+    if form != "auto":
+        for k, v in PROJ_FORMS[form].items():
+            knobs.set(k, v)
+        if with_3x3:
+            knobs.set("WINO_3X3_ALGO", rc.HEAD_3X3_ALGO[form])
+
+
+def test_box_head_sweep(pkg, knobs, torch_dev):
+    """Every case of box_head_cases() on random pooled input, in the automatic form and under the tiled, stream-K and
+    latency knob sets.  The plan queries say which form fc6, fc7 and the predictor take under each (a knob set the plan
+    does not follow for a GEMM is recorded as what it took); over the sweep each of them runs in all three forms
+    (tests/test_roi_host.py shows from the plan queries alone that the list allows it)."""
+    _, dev = torch_dev
+    ran, worst = collections.defaultdict(set), 0.0
+    for c in rc.box_head_cases():
+        sd = rc.box_head_state_dict(c.C, c.P, c.rep, c.classes, seed=c.seed)
+        head = pkg.BoxHead.from_state_dict(sd, in_channels=c.C, P=c.P)
+        pooled = torch.rand(c.R, c.P, c.P, c.C, generator=torch.Generator().manual_seed(c.seed)) - 0.5
+        want_cls, want_box = rc.box_head_reference(sd, pooled)
+        x, kp = pooled.to(dev), (5 * c.classes + 63) // 64 * 64
+        for form in rc.HEAD_FORMS:
+            force(knobs, form)
+            took = {name: S.form_1x1(pkg, *g) for name, g in rc.box_head_gemms(c).items()}
+            first = None
+            for _ in range(2):
+                head.prepare(c.R)
+                for t in (head._h6, head._h7, head._scores):
+                    t.fill_(float("nan"))
+                logits, regression = head(x)
+                torch.cuda.synchronize()
+                assert tuple(head._scores.shape) == (c.R, kp) and bool((head._scores[:, 5 * c.classes:] == 0).all())
+                first = head._scores.clone() if first is None else first
+                assert torch.equal(bits(head._scores), bits(first)), (c, form)
+            errs = rel(torch, logits, want_cls), rel(torch, regression, want_box)
+            worst = max(worst, *errs)
+            print(f"box head {tuple(c)[:5]} {form} {took}: logits {errs[0]:.2e} regression {errs[1]:.2e}")
+            assert max(errs) < NET_TOL, (c, form)
+            assert pkg.tickets_in_use() == 0
+            for name, f in took.items():
+                ran[name].add(f)
+    force(knobs, "auto")
+    print(f"box head sweep: worst rel err {worst:.2e}; forms {dict(ran)}")
+    for name in ("fc6", "fc7", "predictor"):
+        assert ran[name] >= set(FORCED), (name, ran[name])
+
+
+def test_mask_head_sweep(pkg, knobs, torch_dev):
+    """Every case of mask_head_cases() on a random pooled input with an exact-zero ring, which is not written: the
+    automatic form and the three knob sets, WINO_3X3_ALGO beside them (big with tiled and stream-K, small with latency).
+    Over the sweep the transposed convolution and the logits GEMM each run tiled, stream-K and latency, and the 3x3
+    runs on the throughput and on the latency kernel."""
+    _, dev = torch_dev
+    ran, worst = collections.defaultdict(set), 0.0
+    for c in rc.mask_head_cases():
+        sd = rc.mask_head_state_dict(c.C, c.classes, seed=c.seed)
+        head = pkg.MaskHead.from_state_dict(sd, in_channels=c.C)
+        pooled = torch.zeros(c.R, c.P + 2, c.P + 2, c.C)
+        pooled[:, 1:-1, 1:-1, :] = torch.rand(c.R, c.P, c.P, c.C, generator=torch.Generator().manual_seed(c.seed)) - 0.5
+        want = rc.mask_head_reference(sd, pooled[:, 1:-1, 1:-1, :])
+        x = pooled.to(dev)
+        for form in rc.HEAD_FORMS:
+            force(knobs, form, with_3x3=True)
+            took = {name: S.form_1x1(pkg, *g) for name, g in rc.mask_head_gemms(c).items()}
+            took["conv3x3"] = S.plan_3x3(pkg, c.R, c.P, c.P, c.C, c.C)[0]
+            first = None
+            for _ in range(2):
+                head.prepare(c.R, c.P)
+                for t in (head._a, head._b, head._up, head._scores, head._masks):
+                    t.fill_(float("nan"))
+                masks = head(x)
+                torch.cuda.synchronize()
+                assert tuple(masks.shape) == (c.R, c.classes, 2 * c.P, 2 * c.P)
+                first = masks.clone() if first is None else first
+                assert torch.equal(bits(masks), bits(first)), (c, form)
+            assert torch.equal(bits(x.cpu()), bits(pooled)), "the input was written"
+            err = rel(torch, masks, want)
+            worst = max(worst, err)
+            print(f"mask head {tuple(c)[:4]} {form} {took}: {err:.2e}")
+            assert err < NET_TOL, (c, form)
+            assert pkg.tickets_in_use() == 0
+            for name, f in took.items():
+                ran[name].add(f)
+    force(knobs, "auto")
+    print(f"mask head sweep: worst rel err {worst:.2e}; forms {dict(ran)}")
+    for name in ("deconv", "logits"):
+        assert ran[name] >= set(FORCED), (name, ran[name])
+    assert ran["conv3x3"] == {"throughput", "latency"}
 
 
 # ---- end to end ------------------------------------------------------------------------------------------------------------

@@ -1,4 +1,5 @@
-"""Seeded random-shape sweeps of the ResNet entry points, of the grouped 3x3 layer and the two ResNeXt blocks (every one
+"""Seeded random-shape sweeps of the ResNet entry points, of one FPN level (wino_fpn_level_hw: every form of its
+lateral 1x1 and of its 3x3), of the grouped 3x3 layer and the two ResNeXt blocks (every one
 of the kernel's twelve instantiations, named by wino_conv3x3_grouped_plan) and of the segmentation path -- the dilated 3x3 layer, the
 dilated bottleneck blocks, the concat projection, ASPP and the bilinear resize -- (tests/shape_sweeps.py: shapes from the whole legal envelope
 of winograd_mi355x.h, every forced form the planner takes, the automatic ones): each case against an fp64 reference
@@ -84,3 +85,7 @@ def test_grouped_3x3_sweep(pkg, knobs, torch_dev):
 
 def test_grouped_block_sweep(pkg, knobs, torch_dev):
     SC.run_sweep("grouped_block", SC.grouped_block_case, pkg, knobs, torch_dev, SC.SEEDS["grouped_block"])
+
+
+def test_fpn_level_sweep(pkg, knobs, torch_dev):
+    SC.run_sweep("fpn_level", SC.fpn_level_case, pkg, knobs, torch_dev, SC.SEEDS["fpn_level"])

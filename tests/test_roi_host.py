@@ -4,13 +4,15 @@ against torchvision's formula, the fp32 restatement of the arithmetic against th
 tests to cases.TIGHT), the heads' state-dict validation and their pure packing functions against torch in fp64."""
 import ctypes
 import importlib
+import math
 import os
 
 import pytest
 import torch
 
 import roi_cases as rc
-from cases import TIGHT
+import shape_sweeps as S
+from cases import PROJ_FORMS, TIGHT
 from conftest import ROOT
 
 E_SHAPE, E_ARG = -2, -3
@@ -127,7 +129,8 @@ def test_generator_properties():
 def test_exact_subset_is_exact_in_fp32():
     bx = rc.boxes(0)
     ex = bx.index("exact")
-    for P, S in rc.EXACT_COMBOS:
+    assert float(rc.min_sample_margin(bx.rois[ex], bx.levels[ex], rc.EXACT_COMBOS_S4).min()) >= rc.SAMPLE_MARGIN
+    for P, S in rc.EXACT_COMBOS + rc.EXACT_COMBOS_S4:
         for l in range(4):
             sel = [r for r in ex if int(bx.levels[r]) == l]
             y64, x64 = rc.sample_coords(bx.rois[sel], rc.SCALES[l], P, S)
@@ -178,6 +181,156 @@ def test_reference_rules_for_bad_boxes():
         assert bool((out[r] == 0).all()) and touched[r] is None
     for r in (5, 6):
         assert bool(torch.isnan(out[r]).all()) and touched[r] is None
+
+
+def test_launch_split_knob(pkg, knobs):
+    """WINO_ROI_LAUNCH_TASKS caps the output positions of one launch; unset, 0, negative or not a number it changes
+    nothing (the other WINO_* numbers read the same way: 0 is "not given"), and below one box it means one box."""
+    n = pkg.roi_align_launches
+    big = (1 << 31) // (66 * 66)                                # the boxes of one launch at P = 64 padded: 493 k
+    knobs.unset("WINO_ROI_LAUNCH_TASKS")
+    assert big == 492994 and n(big, 64, True) == 1 and n(big + 1, 64, True) == 2 and n(2 * big + 1, 64, True) == 3
+    assert n(0, 7) == 0 and n(89, 7) == 1 and n((1 << 31) - 1, 1) == 1
+    for v in ("0", "-1", "-2147483648", "junk", ""):
+        knobs.set("WINO_ROI_LAUNCH_TASKS", v)
+        assert n(89, 7, True) == 1 and n(big + 1, 64, True) == 2, v
+    knobs.set("WINO_ROI_LAUNCH_TASKS", 12 * 81 + 40)
+    assert n(89, 7, True) == 8 and n(96, 7, True) == 8 and n(97, 7, True) == 9 and n(89, 7, False) == 5
+    knobs.set("WINO_ROI_LAUNCH_TASKS", 5)                       # less than one box of 49 positions: a box per launch
+    assert n(89, 7) == 89 and n(89, 1) == 18
+    knobs.unset("WINO_ROI_LAUNCH_TASKS")
+    assert n(89, 7, True) == 1
+    L, out = pkg.lib(), ctypes.c_long(0)
+    for R, P, padded in ((-1, 7, 0), (1, 0, 0), (1, 65, 0), (1, 7, 2)):
+        assert L.wino_roi_align_launches(R, P, padded, ctypes.byref(out)) == E_SHAPE
+    assert L.wino_roi_align_launches(1, 7, 0, None) == E_ARG
+    assert "wino_roi_align_launches(" in open(os.path.join(ROOT, "include", "winograd_mi355x.h")).read()
+
+
+# ---- the sweep: any geometry ---------------------------------------------------------------------------------------------
+SWEEP = rc.roi_sweep_cases()
+
+
+def test_sweep_cases_pass_the_argument_checks(pkg):
+    """Every sweep case reaches the entry point's last check (out laid over rois), so every earlier one accepts it; the
+    cases that go through multiscale_roi_align get their scales back from infer_roi_scales."""
+    err = lambda: pkg.lib().wino_last_error_string().decode()
+    assert 20 <= len(SWEEP) <= 28 and len({c.name for c in SWEEP}) == len(SWEEP)
+    for c in SWEEP:
+        geo, R = c.geo, len(rc.case_boxes(c).names)
+        hw = [v for s in geo.hw for v in s]
+        assert _call(pkg, hw=hw, scales=list(geo.scales), levels=geo.levels, N=geo.N, C=c.C, in_padded=int(c.in_padded), R=R,
+                     P=c.P, sampling=c.S, out_padded=int(c.out_padded), out=ROIS, **geo.canon) == E_ARG, (c.name, err())
+        assert "overlap" in err(), (c.name, err())
+        if c.defaults:
+            p = 2 if c.in_padded else 0
+            maps = [torch.empty(1, h + p, w + p, 4) for h, w in geo.hw]
+            assert tuple(pkg.infer_roi_scales(maps, geo.image, c.in_padded)) == geo.scales, c.name
+            assert (geo.canonical_scale, geo.canonical_level) == rc.DEFAULT_CANON
+
+
+def test_sweep_reaches_its_corners():
+    got = lambda f: {f(c) for c in SWEEP}
+    for S in (1, 2, 3, 4):
+        Ps = {c.P for c in SWEEP if c.S == S}
+        assert 1 in Ps and any(P % 2 and P > 1 for P in Ps) and any(P % 2 == 0 for P in Ps), (S, Ps)
+    p64 = [c for c in SWEEP if c.P == 64]
+    assert len(p64) == 1 and p64[0].C == 4
+    assert got(lambda c: c.geo.levels) == {1, 2, 3, 4}
+    assert got(lambda c: c.geo.k0) >= {0, 1, 2, 3, 4, 5}
+    one = [c.geo.scales[0] for c in SWEEP if c.geo.levels == 1]
+    assert any(math.log2(s) == round(math.log2(s)) for s in one) and any(math.log2(s) != round(math.log2(s)) for s in one)
+    assert got(lambda c: c.geo.N) == {1, 2, 3, 4, 5}
+    for c in SWEEP:   # boxes in the first and in the last image
+        assert {0.0, float(c.geo.N - 1)} <= set(rc.case_boxes(c).rois[:, 0].tolist()), c.name
+    coarse = lambda g: round(1 / g.scales[-1])
+    odd = [c for c in SWEEP if c.geo.image[0] % coarse(c.geo) and c.geo.image[1] % coarse(c.geo)]
+    assert len(odd) >= len(SWEEP) // 2
+    for c in SWEEP:
+        assert c.geo.hw == tuple((math.ceil(c.geo.image[0] * s), math.ceil(c.geo.image[1] * s)) for s in c.geo.scales)
+    assert any(math.ceil(c.geo.image[0] * s) != c.geo.image[0] * s for c in odd for s in c.geo.scales)
+    all_hw = [s for c in SWEEP for s in c.geo.hw]
+    assert any(h == 1 for h, w in all_hw) and any(w == 1 for h, w in all_hw) and any(w >= 3 * h for h, w in all_hw)
+    assert got(lambda c: c.C) == {4, 8, 252, 256, 260, 320, 516}
+    assert got(lambda c: (c.in_padded, c.out_padded)) == {(False, False), (False, True), (True, False), (True, True)}
+    multi = [c for c in SWEEP if c.geo.levels > 1]
+    assert {c.geo.canonical_scale for c in multi} == {16.0, 24.0, 56.0, 224.0}
+    assert {c.geo.canonical_level for c in multi} == {3, 4, 5}
+    assert len([c for c in multi if c.defaults]) >= 2
+    assert any(c.geo.k0 != 2 for c in multi)
+
+
+def test_sweep_levels_agree_and_spread():
+    """torchvision's formula in fp64 and the thresholds rule give every box of every case the same level, under the
+    case's own canonical values; every case with several levels hits two at least, the list hits all four."""
+    hit = set()
+    for c in SWEEP:
+        gb, geo = rc.case_boxes(c), c.geo
+        want = rc.torchvision_levels(gb.rois, geo.scales, **geo.canon)
+        assert torch.equal(gb.levels, want)
+        assert torch.equal(rc.threshold_levels(gb.rois, geo.scales, **geo.canon), want), c.name
+        good = [r for r, n in enumerate(gb.names) if n != "huge"]        # (a huge box's level is the top one, and unread)
+        levels = set(want[good].tolist())
+        assert len(levels) >= min(geo.levels, 2), (c.name, levels)
+        assert levels <= set(range(geo.levels))
+        hit |= levels
+        for j in range(1, geo.levels):                                    # a box on a threshold takes the upper level
+            assert want[gb.index(f"threshold_{j}")].tolist() == [j, j], (c.name, j)
+    assert hit == {0, 1, 2, 3}
+
+
+def test_sweep_redraw_cap_and_margins():
+    """At most one third of the random draws are redrawn (a condition: a generator that throws most of its draws away
+    would be one that shapes its inputs), and every kept box but those on a threshold keeps both margins."""
+    for c in SWEEP:
+        gb, geo = rc.case_boxes(c), c.geo
+        assert len(gb.index("random")) == c.n == gb.drawn - gb.redrawn
+        assert 3 * gb.redrawn <= gb.drawn, (c.name, gb.redrawn, gb.drawn)
+        m = rc.min_sample_margin(gb.rois, gb.levels, [(c.P, c.S)], hw=geo.hw, scales=geo.scales)
+        assert float(m.min()) >= rc.SAMPLE_MARGIN, c.name
+        lm = rc.level_margin(gb.rois, geo.scales, **geo.canon)
+        for v, n in zip(lm.tolist(), gb.names):
+            assert v == 0 if n.startswith("threshold_") else v >= rc.LEVEL_MARGIN, (c.name, n, v)
+        again = rc.GeoBoxes(geo, ((c.P, c.S),), c.seed, c.n)                  # seeded
+        assert torch.equal(again.rois, gb.rois) and rc.case_boxes(c) is gb
+
+
+def test_sweep_class_properties():
+    """Every named class has its property in every geometry.  A class may be missing from a geometry only where there is
+    no room for it: an interior box of level l needs sqrt(area) above that level's threshold inside the image."""
+    assert all(all(v) for v in rc.geo_class_properties(rc.geometry_boxes(rc.BASE_GEOMETRY, rc.PS_COMBOS, 0, 4)).values())
+    for c in SWEEP:
+        gb, geo = rc.case_boxes(c), c.geo
+        props = rc.geo_class_properties(gb)
+        assert all(all(v) for v in props.values()), (c.name, {k: v for k, v in props.items() if not all(v)})
+        edges = [0.0] + geo.edges()
+        for name in rc.named_classes(geo):
+            room = True
+            if name.startswith("interior_l"):
+                room = (1.02 * edges[int(name[-1])]) ** 2 < 0.98 * 0.98 * geo.image[0] * geo.image[1]
+            assert len(props.get(name, [])) == ((4 if name == "flipped" else 2) if room else 0), (c.name, name)
+        huge = gb.index("huge")
+        assert len(huge) == 2 * len(rc.HUGE) and len(props["huge"]) == len(huge)
+        assert bool((gb.rois[huge, 1:].abs().max(dim=1).values >= 1e30).all()) and bool(torch.isfinite(gb.rois).all())
+        assert {1e30, 3e38} <= {float(f"{abs(v):.0e}") for v in gb.rois[huge, 1:].flatten().tolist()}
+
+
+def test_sweep_fp32_restatement_holds_a_quarter_of_tight():
+    """What entitles the GPU sweep to TIGHT: on every case the straight fp32 restatement is within TIGHT / 4 of the fp64
+    reference, in which the good boxes are finite and the huge ones exact zeros.  Measured worst over the list: 3.9e-6
+    (the defaults case with a 34 x 30 finest level; 2.9e-6 where the finest level's sides are at most 24).  Nothing
+    is claimed for larger maps: the restatement's error grows with the coordinates (README, the RoIAlign paragraph)."""
+    worst = 0.0
+    for c in SWEEP:
+        gb, want = rc.case_boxes(c), rc.case_reference(c)
+        assert bool(torch.isfinite(want).all()) and bool((want[gb.index("huge")] == 0).all()), c.name
+        assert float(want.abs().max()) > 0.05, c.name
+        got = rc.roi_align_reference(rc.case_pyramid(c), gb.rois, c.P, c.geo.scales, c.S, gb.levels, dtype=torch.float32)
+        err = rc.rel_err(got, want)
+        print(f"{c.name} finest {c.geo.hw[0]} P={c.P} S={c.S} C={c.C}: fp32 restatement {err:.2e}")
+        worst = max(worst, err)
+        assert err < TIGHT / 4, c.name
+    print(f"worst {worst:.2e}")
 
 
 # ---- the heads ---------------------------------------------------------------------------------------------------------------
@@ -270,3 +423,42 @@ def test_transposed_convolution_as_a_gemm(D):
     assert bool((scores[:, classes:] == 0).all())
     got = scores.view(R, P, P, 2, 2, 64)[..., :classes].permute(0, 5, 1, 3, 2, 4).reshape(R, classes, 2 * P, 2 * P)
     assert float((got - want).abs().max()) < 1e-13
+
+
+def test_head_sweeps_reach_every_form(pkg, knobs, D):
+    """The case lists have the shapes the issue names, every case passes the heads' own validation, and -- from the plan
+    queries alone -- every GEMM of either head takes the tiled, the stream-K and the latency form under some knob set of
+    some case, and the mask head's 3x3 both of its kernels."""
+    box, mask = rc.box_head_cases(), rc.mask_head_cases()
+    assert 8 <= len(box) <= 12 and 6 <= len(mask) <= 10
+    assert {c.C for c in box} == {32, 64, 96, 160} and {c.P for c in box} == {2, 4, 7, 8}
+    assert {c.rep for c in box} == {64, 192, 320} and {c.classes for c in box} == {1, 2, 12, 13, 91}
+    assert {c.R for c in box} == {1, 2, 111, 112, 113, 300}
+    assert any((c.C * c.P * c.P) % 64 for c in box) and all((c.C * c.P * c.P) % 32 == 0 for c in box)
+    assert {5 * c.classes for c in box} >= {60, 65}
+    assert {c.C for c in mask} == {64, 128} and {c.P for c in mask} == {2, 6, 14}
+    assert {c.classes for c in mask} == {1, 3, 64, 65, 91} and {c.R for c in mask} == {1, 3, 9, 40}
+    for c in box:
+        sd = {k: torch.empty(v) for k, v in D.expected_box_head_keys(c.C, c.P, c.rep, c.classes).items()}
+        assert D.validate_box_head_state_dict(sd, c.C, c.P) == (c.rep, c.classes)
+    for c in mask:
+        sd = {k: torch.empty(v) for k, v in D.expected_mask_head_keys(c.C, c.classes).items()}
+        assert D.validate_mask_head_state_dict(sd, c.C) == c.classes
+    ran = {}
+    for form in rc.HEAD_FORMS:
+        for k in ("WINO_1X1_ALGO", "WINO_1X1_SK", "WINO_3X3_ALGO"):
+            knobs.unset(k)
+        if form != "auto":
+            for k, v in PROJ_FORMS[form].items():
+                knobs.set(k, v)
+            knobs.set("WINO_3X3_ALGO", rc.HEAD_3X3_ALGO[form])
+        for c in box:
+            for name, g in rc.box_head_gemms(c).items():
+                ran.setdefault(name, set()).add(S.form_1x1(pkg, *g))
+        for c in mask:
+            for name, g in rc.mask_head_gemms(c).items():
+                ran.setdefault(name, set()).add(S.form_1x1(pkg, *g))
+            ran.setdefault("conv3x3", set()).add(S.plan_3x3(pkg, c.R, c.P, c.P, c.C, c.C)[0])
+    for name in ("fc6", "fc7", "predictor", "deconv", "logits"):
+        assert ran[name] == {"tiled", "stream_k", "latency"}, (name, ran[name])
+    assert ran["conv3x3"] == {"throughput", "latency"}

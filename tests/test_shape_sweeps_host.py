@@ -75,6 +75,7 @@ def _channels(c):
         "resize_bilinear": ([], []),
         "conv3x3_grouped_bn_relu": ([s.get("C")], [s.get("C")]),
         "grouped_block": ([s.get("Cin")], [s.get("Cm"), s.get("C4")]),
+        "fpn_level": ([s.get("Cin")], [s.get("Cf")]),
     }.get(c.entry, ([s.get("C")], [s.get("K")]))
 
 
@@ -97,6 +98,7 @@ AUTO_FORMS = {
     # all twelve instantiations of the one kernel body
     "conv3x3_grouped_bn_relu": [{f"s{st}_tw{tw}_kc{kc}" for st in (1, 2) for tw in (8, 16) for kc in (16, 32, 64)}],
     "grouped_block": [{"latency"}, set(), {"latency", "tiled"}],   # (the middle launch: _grouped_block_corners)
+    "fpn_level": [{"latency", "tiled", "stream_k"}, {"latency", "throughput"}],
 }
 FORCED_FORMS = {
     "conv3x3_bn_add_relu": {"big_tail", "big_whole", "small"},
@@ -115,6 +117,7 @@ FORCED_FORMS = {
     "resize_bilinear": set(),
     "conv3x3_grouped_bn_relu": set(),
     "grouped_block": set(S.GBLOCK_FORMS),
+    "fpn_level": {f"{lat}+{out}" for lat, out in S.fpn_forms()},
 }
 FLAGS = {
     "conv3x3_bn_add_relu": ("relu", "in_place", "nonneg"),
@@ -133,6 +136,7 @@ FLAGS = {
     "resize_bilinear": ("in_padded",),
     "conv3x3_grouped_bn_relu": ("relu", "nonneg"),
     "grouped_block": ("nonneg",),
+    "fpn_level": ("top", "c_padded", "nonneg"),
 }
 
 
@@ -329,6 +333,30 @@ def _grouped_block_corners(cases, pkg):
     return got
 
 
+def _fpn_corners(cases):
+    """Every lateral form of forms_1x1.FORMS and every 3x3 form beside one, every channel count, the coarse map's last
+    row and column read by one fine row / column alone, under each flag pair."""
+    got = {f"Cin = {v}": any(c.Cin == v for c in cases) for v in S.FPN_CIN}
+    got.update({f"Cf = {v}": any(c.Cf == v for c in cases) for v in S.FPN_CF})
+    forced = [c.form.split("+") for c in cases if c.form]
+    for lat in S.fpn_lateral_forms():
+        got[f"lateral form {lat}"] = any(f[0] == lat for f in forced) or (lat == "auto" and any(not c.form for c in cases))
+    for out in S.FPN_OUT_FORMS:
+        got[f"3x3 form {out}"] = any(f[1] == out for f in forced) or (out == "auto" and any(not c.form for c in cases))
+    got["an odd H and an odd W with a top"] = any(c.H % 2 and c.W % 2 and c.flags["top"] for c in cases)
+    got["an even H or W with a top"] = any((c.H % 2 == 0 or c.W % 2 == 0) and c.flags["top"] for c in cases)
+    for top in (False, True):
+        for pad in (False, True):
+            got[f"top={top} c_padded={pad}"] = any(c.flags["top"] == top and c.flags["c_padded"] == pad for c in cases)
+    got["N = 1"] = any(c.N == 1 for c in cases)
+    got["N = 6"] = any(c.N == 6 for c in cases)
+    got["H or W above 32"] = any(max(c.H, c.W) > 32 for c in cases)
+    drawn = [c for c in cases if c.shape not in S.FPN_AUTO]
+    assert len(drawn) == len(cases) - len(S.FPN_AUTO)
+    assert all(1 <= c.N <= 6 and 1 <= c.H <= 40 and 1 <= c.W <= 40 and S.macs(c) <= S.FPN_MACS for c in drawn)
+    return got
+
+
 def _corners(entry, cases, pkg, knobs):
     """{corner: reached} for the entry point's draws."""
     maps = [_map_hw(c) for c in cases]
@@ -374,6 +402,8 @@ def _corners(entry, cases, pkg, knobs):
         got.update(_grouped_corners(cases, pkg))
     if entry == "grouped_block":
         got.update(_grouped_block_corners(cases, pkg))
+    if entry == "fpn_level":
+        got.update(_fpn_corners(cases))
     if entry == "conv3x3_s2_proj":
         got["a stream-K range boundary inside the centre tap"] = any(
             c.knobs and _with_knobs(knobs, c, lambda: S.centre_tap_split(pkg, c)) for c in cases)
