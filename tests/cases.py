@@ -5,6 +5,10 @@ borrows the reference methods for the few images it checks) all read them from h
 import."""
 import numpy as np
 
+import layer_refs as LR
+from layer_refs import interior, ring_mask  # noqa: F401  (ring_mask: read from here by the layers' tests)
+from layer_refs import ring_is as ring_zero  # noqa: F401  (the ring of a padded tensor is exactly zero)
+
 REL = 1e-3       # BASELINE.json's north_star bar: max|got - want| / max|want|
 TIGHT = 2e-5     # what fp32 F(2x2,3x3) is held to, so that an indexing slip cannot hide under REL
 
@@ -12,18 +16,6 @@ TIGHT = 2e-5     # what fp32 F(2x2,3x3) is held to, so that an indexing slip can
 def to_dev(torch_dev, a):
     torch, dev = torch_dev
     return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def ring_mask(H=14, W=14):
-    """The ring pixels of a padded [H+2][W+2] map, as a bool mask."""
-    r = np.ones((H + 2, W + 2), bool)
-    r[1:-1, 1:-1] = False
-    return r
-
-
-def ring_zero(t):
-    """The ring of a padded [N][H+2][W+2][C] torch tensor is exactly zero."""
-    return all(bool((r == 0).all()) for r in (t[:, 0], t[:, -1], t[:, :, 0], t[:, :, -1]))
 
 
 def rand_layer(rng, N, C, K):
@@ -35,9 +27,7 @@ def rand_layer(rng, N, C, K):
 
 def padded(torch, N, H, W, C, g, ring=0.0):
     """[N][H+2][W+2][C], interior uniform in [-0.5, 0.5), the ring set to `ring`."""
-    x = torch.full((N, H + 2, W + 2, C), ring)
-    x[:, 1:-1, 1:-1, :] = torch.rand(N, H, W, C, generator=g) - 0.5
-    return x
+    return LR.ring(torch.rand(N, H, W, C, generator=g) - 0.5, ring)
 
 # ---- the residual 3x3 layer and the identity basic block ------------------------------------------------------------
 class ResLayer:
@@ -67,16 +57,9 @@ class ResLayer:
                                             relu=relu, out=out)
 
     def reference(self, relu=True, idx=None):
-        torch = self.torch
-        F = torch.nn.functional
         pick = (lambda a: a) if idx is None else (lambda a: a[idx])
-        x = pick(self.x)[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        r = pick(self.res)[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        y = F.conv2d(x, self.w.double(), padding=1)
-        y = y * self.scale.double()[None, :, None, None] + self.bias.double()[None, :, None, None] + r
-        if relu:
-            y = torch.relu(y)
-        return y.permute(0, 2, 3, 1).numpy()
+        return LR.conv3x3(interior(pick(self.x)), self.w, (self.bias, self.scale), relu,
+                          residual=interior(pick(self.res))).numpy()
 
     def check(self, O, got, relu=True, idx=None):
         g = got.cpu().numpy()
@@ -121,14 +104,7 @@ class BasicBlock:
 
     def reference(self, xpadded, blocks=1):
         """fp64 on the CPU, `blocks` times in a row."""
-        torch = self.torch
-        F = torch.nn.functional
-        x = xpadded[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        bn = lambda y, i: y * self.bn[i][1].double()[None, :, None, None] + self.bn[i][0].double()[None, :, None, None]
-        for _ in range(blocks):
-            t1 = torch.relu(bn(F.conv2d(x, self.w[0].double(), padding=1), 0))
-            x = torch.relu(bn(F.conv2d(t1, self.w[1].double(), padding=1), 1) + x)
-        return x.permute(0, 2, 3, 1).numpy()
+        return LR.basic_block(interior(xpadded), self.w[0], self.bn[0], self.w[1], self.bn[1], blocks).numpy()
 
     def check(self, O, got, blocks=1):
         g = got.cpu().numpy()
@@ -148,9 +124,7 @@ class S2Layer:
         self.pkg = pkg
         torch = self.torch
         g = torch.Generator(device="cpu").manual_seed(seed)
-        x = torch.zeros(N, Hin + 2, Win + 2, C)
-        x[:, 1:-1, 1:-1, :] = torch.rand(N, Hin, Win, C, generator=g) - 0.5
-        self.x = x
+        self.x = x = padded(torch, N, Hin, Win, C, g)
         self.w = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
         self.bias = torch.rand(K, generator=g) - 0.5
         self.scale = torch.rand(K, generator=g) + 0.5
@@ -165,15 +139,9 @@ class S2Layer:
         return self.pkg.conv3x3_s2_bn_relu(self.xt, self.taps, self.bt, self.st, relu=relu, out=out)
 
     def reference(self, idx=None, relu=True):
-        """fp64 on the CPU: interior of the padded input -> conv2d(stride 2, padding 1) -> BN -> ReLU, [n][H][W][K]."""
-        torch = self.torch
+        """fp64 on the CPU: interior of the padded input -> 3x3 (stride 2, padding 1) -> BN -> ReLU, [n][H][W][K]."""
         x = self.x if idx is None else self.x[idx]
-        xin = x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        y = torch.nn.functional.conv2d(xin, self.w.double(), stride=2, padding=1)
-        y = y * self.scale.double()[None, :, None, None] + self.bias.double()[None, :, None, None]
-        if relu:
-            y = torch.relu(y)
-        return y.permute(0, 2, 3, 1).numpy()
+        return LR.conv3x3(interior(x), self.w, (self.bias, self.scale), relu, stride=2).numpy()
 
     def check(self, O, got, idx=None, relu=True):
         g = got.cpu().numpy()
@@ -219,9 +187,7 @@ class S2Block:
         torch = self.torch
         self.pkg = pkg
         g = torch.Generator(device="cpu").manual_seed(seed)
-        x = torch.zeros(N, Hin + 2, Win + 2, C)
-        x[:, 1:-1, 1:-1, :] = torch.rand(N, Hin, Win, C, generator=g) - 0.5
-        self.x = x
+        self.x = x = padded(torch, N, Hin, Win, C, g)
         self.w1 = (torch.rand(K, C, 3, 3, generator=g) - 0.5) / np.sqrt(9 * C) * 4
         self.wd = (torch.rand(K, C, 1, 1, generator=g) - 0.5) / np.sqrt(C) * 4
         self.w2 = (torch.rand(K, K, 3, 3, generator=g) - 0.5) / np.sqrt(9 * K) * 4
@@ -255,18 +221,10 @@ class S2Block:
 
     def reference(self, idx=None, block=True):
         """fp64 on the CPU: (t1, sc, out), each [n][H][W][K] (out None unless `block`)."""
-        torch = self.torch
-        F = torch.nn.functional
-        x = self.x if idx is None else self.x[idx]
-        xin = x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()
-        bn = lambda y, s, b: y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-        t1 = torch.relu(bn(F.conv2d(xin, self.w1.double(), stride=2, padding=1), self.s1, self.b1))
-        sc = bn(F.conv2d(xin, self.wd.double(), stride=2), self.sd, self.bd)
-        nhwc = lambda y: y.permute(0, 2, 3, 1).numpy()
-        if not block:
-            return nhwc(t1), nhwc(sc), None
-        out = torch.relu(bn(F.conv2d(t1, self.w2.double(), padding=1), self.s2, self.b2) + sc)
-        return nhwc(t1), nhwc(sc), nhwc(out)
+        tail = (self.w2, (self.b2, self.s2)) if block else ()
+        out = LR.basic_block_s2(interior(self.x if idx is None else self.x[idx]), self.w1, (self.b1, self.s1), self.wd,
+                                (self.bd, self.sd), *tail)
+        return tuple(None if t is None else t.numpy() for t in out)
 
     def check_layer(self, O, t1, sc, idx=None):
         a, b = t1.cpu().numpy(), sc.cpu().numpy()
@@ -300,20 +258,6 @@ def proj_weights(rng, Cin, Cm, C4):
     wp = ((rng.rand(Cin, C4) - 0.5) / np.sqrt(Cin) * 2).astype(np.float32)
     bn = [((rng.rand(c) - 0.5).astype(np.float32), (rng.rand(c) + 0.5).astype(np.float32)) for c in (Cm, Cm, C4, C4)]
     return w1, w2, w3, wp, bn
-
-def proj_oracle(O, x, s, w1, w2, w3, wp, bn):
-    """fp64 composition of the layer oracles: xs = x[:, ::s, ::s], 1x1 + BN + ReLU, 3x3 (pad 1) + BN + ReLU,
-    1x1 + BN, + BN(xs . wp), ReLU."""
-    xs = np.asarray(x, np.float64)[:, ::s, ::s, :]
-    N, H, W, Cin = xs.shape
-    Cm = w1.shape[1]
-    t1 = O.conv1x1_bn(xs.reshape(-1, Cin), w1, bn[0][0], bn[0][1], True).reshape(N, H, W, Cm)
-    t1p = np.zeros((N, H + 2, W + 2, Cm))
-    t1p[:, 1:-1, 1:-1, :] = t1
-    t2 = O.conv3x3_bn_relu_direct(t1p, w2, bn[1][1], bn[1][0], True)[:, 1:-1, 1:-1, :]
-    t3 = O.conv1x1_bn(t2.reshape(-1, Cm), w3, bn[2][0], bn[2][1], False)
-    sc = O.conv1x1_bn(xs.reshape(-1, Cin), wp, bn[3][0], bn[3][1], False)
-    return np.maximum(t3 + sc, 0).reshape(N, H, W, -1)
 
 # (knob settings) -> the forms both 1x1 launches are forced into
 PROJ_FORMS = {
@@ -364,16 +308,9 @@ class V15Block:
 
     def reference(self, idx=None):
         """fp64 on the CPU: 1x1 at stride 1, 3x3 at stride 2 with pad 1, 1x1, plus the stride-2 projection, ReLU."""
-        torch = self.torch
-        F = torch.nn.functional
-        x = (self.x if idx is None else self.x[idx]).permute(0, 3, 1, 2).double()
-        bn = lambda y, i: y * self.bn[i][1].double()[None, :, None, None] + self.bn[i][0].double()[None, :, None, None]
-        one = lambda w: w.double().t()[:, :, None, None]   # [Cin][Cout] -> [Cout][Cin][1][1]
-        t1 = torch.relu(bn(F.conv2d(x, one(self.w1)), 0))
-        t2 = torch.relu(bn(F.conv2d(t1, self.w2.double(), stride=2, padding=1), 1))
-        t3 = bn(F.conv2d(t2, one(self.w3)), 2)
-        sc = bn(F.conv2d(x, one(self.wp), stride=2), 3)
-        return torch.relu(t3 + sc).permute(0, 2, 3, 1).numpy()
+        x, bn = self.x if idx is None else self.x[idx], self.bn
+        return LR.bottleneck(x, self.w1, bn[0], self.w2, bn[1], self.w3, bn[2], self.wp, bn[3], stride=2,
+                             stride_on="3x3").numpy()
 
     def check(self, O, got, idx=None):
         g = got.cpu().numpy()

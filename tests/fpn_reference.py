@@ -2,8 +2,7 @@
 (WINO_RESIDUAL_UP2), one pyramid level, and torchvision's BackboneWithFPN read off a state dict -- each with
 F.interpolate(mode="nearest") and F.max_pool2d(1, 2) written literally -- plus random weights in torchvision's key
 names (the recipe of reference_nets.random_state_dict, extended by the FPN's convolutions)."""
-import numpy as np
-
+import layer_refs as LR
 from reference_nets import random_state_dict, reference_forward
 
 LAYER_TOL = 2e-5   # what the project holds a single fp32 layer to (cases.TIGHT)
@@ -15,16 +14,7 @@ def up_hw(H, W):
 
 def padded_nan(torch, t):
     """[N][H][W][C] -> [N][H+2][W+2][C] with a NaN ring: one ring read by a kernel shows in its result."""
-    N, H, W, C = t.shape
-    p = torch.full((N, H + 2, W + 2, C), float("nan"), dtype=t.dtype)
-    p[:, 1:-1, 1:-1, :] = t
-    return p
-
-
-def upsample_nearest(torch, coarse_nhwc, H, W):
-    """F.interpolate(size=(H, W), mode="nearest") of an NHWC tensor, NHWC again."""
-    F = torch.nn.functional
-    return F.interpolate(coarse_nhwc.permute(0, 3, 1, 2), size=(H, W), mode="nearest").permute(0, 2, 3, 1)
+    return LR.ring(t, float("nan"))
 
 
 class Up2Layer:
@@ -37,14 +27,12 @@ class Up2Layer:
         r = lambda *sh: torch.rand(*sh, generator=g)
         Hc, Wc = up_hw(H, W)
         A = r(N, H, W, Cin) - 0.5
-        B = (r(Cin, Kout) - 0.5) / np.sqrt(Cin) * 4
-        b, s = r(Kout) - 0.5, r(Kout) + 0.5
-        s[::3] *= -1
+        B = LR.w11(r, Cin, Kout)
+        b, s = LR.bn_pair(r, Kout)
         top = r(N, Hc, Wc, Kout) - 0.5
         self.cpu = {"A": A, "Ap": padded_nan(torch, A), "B": B, "b": b, "s": s, "top": padded_nan(torch, top)}
         self.dev = {k: v.to(dev) for k, v in self.cpu.items()}
-        lin = (A.double().reshape(-1, Cin) @ B.double()) * s.double() + b.double()
-        self.pre = lin.reshape(N, H, W, Kout) + upsample_nearest(torch, top.double(), H, W)
+        self.pre = LR.conv1x1(A, B, (b, s), False, top=top)
 
     def out_shape(self, pkg, flags):
         N, H, W, _, Kout = self.shape
@@ -63,14 +51,12 @@ class Up2Layer:
         torch = self.torch
         got = got.detach().cpu().double()
         if flags & pkg.C_PADDED:
-            ring = torch.ones(got.shape[1], got.shape[2], dtype=torch.bool)
-            ring[1:-1, 1:-1] = False
-            assert bool((got[:, ring, :] == 0).all()), f"{tag}: ring is not exactly 0"
-            got = got[:, 1:-1, 1:-1, :]
+            assert LR.ring_is(got, 0.0), f"{tag}: ring is not exactly 0"
+            got = LR.interior(got)
         want = torch.relu(self.pre) if flags & pkg.RELU else self.pre
         assert got.shape == want.shape, f"{tag}: {tuple(got.shape)} != {tuple(want.shape)}"
         assert bool(torch.isfinite(got).all()), f"{tag}: non-finite values (not all written, or a ring was read)"
-        err = float((got - want).abs().max() / want.abs().max())
+        err = LR.rel(got, want)
         print(f"{tag}: rel err {err:.3e}")
         assert err < LAYER_TOL, f"{tag}: rel err {err:.3e}"
 

@@ -6,6 +6,8 @@ import importlib
 
 import pytest
 
+import layer_refs
+
 
 @pytest.fixture(scope="module")
 def torch_dev():
@@ -25,13 +27,8 @@ def V(pkg):
 
 
 def rel(torch, got, want):
-    """max |got - want| / max |want| against an fp64 CPU tensor; the shapes agree and both sides are finite (no NaN,
-    and no Inf either: inf - inf must never pass a tolerance comparison)."""
-    got = got.detach().cpu().double()
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert bool(torch.isfinite(got).all()), "got holds non-finite values"
-    assert bool(torch.isfinite(want).all()), "the reference holds non-finite values"
-    return float((got - want).abs().max() / want.abs().max())
+    """layer_refs.rel: max |got - want| / max |want| against an fp64 CPU tensor, shapes equal, both sides finite."""
+    return layer_refs.rel(got, want)
 
 
 def _clone(r):

@@ -27,7 +27,10 @@ from dataclasses import dataclass
 
 import numpy as np
 
+import layer_refs as LR
 from cases import TIGHT
+from fpn_reference import level_reference
+from layer_refs import ring as _ring
 
 NAN, INF = float("nan"), float("inf")
 VALUES = (NAN, INF, -INF)
@@ -249,18 +252,6 @@ def check_poisoned(torch, got_clean, got_poisoned, want_poisoned, footprint_mask
 
 
 # ---- the layers: masters, fp64 references, footprints ---------------------------------------------------------------
-def _ring(torch, t_nhwc, value=0.0):
-    return torch.nn.functional.pad(t_nhwc, (0, 0, 1, 1, 1, 1), value=value)
-
-
-def _nchw(t):
-    return t.permute(0, 3, 1, 2).double()
-
-
-def _affine(y, b, s):
-    return y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-
-
 def s2_out(h):
     return (h - 1) // 2 + 1
 
@@ -290,13 +281,9 @@ class Layer:
         self.t[name] = self.rand(N, H, W, C) - 0.5
         self.acts[name] = (N, H, W, C)
 
-    def conv_w(self, K, C, k=3):
-        return (self.rand(K, C, k, k) - 0.5) / np.sqrt(k * k * C) * 4
-
     def bn(self, K, b="b", s="s"):
         """bias and scale, a negative scale on every third channel; both poisonable at channels 0 and K - 1."""
-        self.t[b], self.t[s] = self.rand(K) - 0.5, self.rand(K) + 0.5
-        self.t[s][::3] *= -1
+        self.t[b], self.t[s] = LR.bn_pair(self.rand, K)
         for name in (b, s):
             self.params[name] = [(k, (k,)) for k in sorted({0, K - 1})]
 
@@ -331,7 +318,7 @@ class Conv3x3(Layer):
         super().__init__(torch, f"3x3 {mode} relu={int(relu)} {N}x{H}x{W} {C}->{K}", seed)
         self.mode, self.relu, self.shape = mode, relu, (N, H, W, C, K)
         self.act("x", N, H, W, C)
-        self.t["w"] = self.conv_w(K, C)
+        self.t["w"] = LR.conv_w(self.rand, K, C)
         self.params["w"] = [(0, (0, C - 1, 0, 2)), (K - 1, (K - 1, 0, 1, 1))]
         self.bn(K)
         if mode == "res":
@@ -341,24 +328,17 @@ class Conv3x3(Layer):
 
     def run(self, pkg, d):
         torch = self.torch
-        x, U = _ring(torch, d["x"]), pkg.filter_transform_f2(d["w"])
+        x, U = _ring(d["x"]), pkg.filter_transform_f2(d["w"])
         out = torch.full(self.out_shape, NAN, device=x.device)
         if self.mode == "plain":
             return pkg.conv3x3_bn_relu(x, U, d["b"], d["s"], relu=self.relu, out=out)
         if self.mode == "pool":
             return pkg.conv3x3_bn_relu_pool(x, U, d["b"], d["s"], relu=self.relu, out=out)
-        return pkg.conv3x3_bn_add_relu(x, U, d["b"], d["s"], _ring(torch, d["res"], NAN), relu=self.relu, out=out)
+        return pkg.conv3x3_bn_add_relu(x, U, d["b"], d["s"], _ring(d["res"], NAN), relu=self.relu, out=out)
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        y = _affine(F.conv2d(_nchw(t["x"]), t["w"].double(), padding=1), t["b"], t["s"])
-        if self.mode == "res":
-            y = y + _nchw(t["res"])
-        if self.relu:
-            y = torch.relu(y)
-        if self.mode == "pool":
-            y = F.max_pool2d(y, 2, 2)
-        return _ring(torch, y.permute(0, 2, 3, 1).contiguous())
+        return _ring(LR.conv3x3(t["x"], t["w"], (t["b"], t["s"]), self.relu, residual=t.get("res"),
+                                pool=self.mode == "pool"))
 
     def footprint(self, p):
         N, H, W, C, K = self.shape
@@ -393,7 +373,7 @@ class Conv1x1(Layer):
         super().__init__(torch, f"1x1 flags={flags} {N}x{H}x{W} {Cin}->{Kout}", seed)
         self.flags, self.relu, self.shape = flags, bool(flags & self.RELU), (N, H, W, Cin, Kout)
         self.act("A", N, H, W, Cin)
-        self.t["B"] = (self.rand(Cin, Kout) - 0.5) / np.sqrt(Cin) * 4
+        self.t["B"] = LR.w11(self.rand, Cin, Kout)
         self.params["B"] = [(0, (Cin - 1, 0)), (Kout - 1, (0, Kout - 1))]
         self.bn(Kout)
         self.up2 = bool(flags & self.RESIDUAL_UP2)
@@ -408,23 +388,14 @@ class Conv1x1(Layer):
     def run(self, pkg, d):
         torch = self.torch
         N, H, W, Cin, Kout = self.shape
-        A = _ring(torch, d["A"], NAN) if self.flags & self.A_PADDED else d["A"]
-        res = _ring(torch, d["top"], NAN) if self.up2 else d.get("res")
+        A = _ring(d["A"], NAN) if self.flags & self.A_PADDED else d["A"]
+        res = _ring(d["top"], NAN) if self.up2 else d.get("res")
         out = torch.full(self.out_shape, NAN, device=A.device)
         return pkg.conv1x1_bn_ex(A, d["B"], d["b"], d["s"], self.flags, residual=res, out=out, hw=(H, W))
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        N, H, W, Cin, Kout = self.shape
-        y = (t["A"].double().reshape(-1, Cin) @ t["B"].double()) * t["s"].double() + t["b"].double()
-        y = y.reshape(N, H, W, Kout)
-        if self.up2:
-            y = y + F.interpolate(_nchw(t["top"]), size=(H, W), mode="nearest").permute(0, 2, 3, 1)
-        elif "res" in t:
-            y = y + t["res"].double()
-        if self.relu:
-            y = torch.relu(y)
-        return _ring(torch, y) if self.ring else y
+        y = LR.conv1x1(t["A"], t["B"], (t["b"], t["s"]), self.relu, residual=t.get("res"), top=t.get("top"))
+        return _ring(y) if self.ring else y
 
     def footprint(self, p):
         N, H, W, Cin, Kout = self.shape
@@ -450,20 +421,20 @@ class ConvS2(Layer):
         super().__init__(torch, f"3x3/s2 {'proj' if proj else 'plain'} relu={int(relu)} {N}x{Hin}x{Win} {C}->{K}", seed)
         self.proj, self.relu, self.shape = proj, relu or proj, (N, Hin, Win, C, K)
         self.act("x", N, Hin, Win, C)
-        self.t["w"] = self.conv_w(K, C)
+        self.t["w"] = LR.conv_w(self.rand, K, C)
         self.params["w"] = [(0, (0, C - 1, 0, 2)), (K - 1, (K - 1, 0, 1, 1))]
         self.bn(K)
         self.H, self.W = s2_out(Hin), s2_out(Win)
         self.one = (N, self.H + 2, self.W + 2, K)
         if proj:
-            self.t["wd"] = self.conv_w(K, C, k=1)
+            self.t["wd"] = LR.conv_w(self.rand, K, C, k=1)
             self.params["wd"] = [(0, (0, C - 1, 0, 0)), (K - 1, (K - 1, 0, 0, 0))]
             self.bn(K, "bd", "sd")
         self.out_shape = (2,) + self.one if proj else self.one
 
     def run(self, pkg, d):
         torch = self.torch
-        x, taps = _ring(torch, d["x"]), pkg.filter_pack_s2(d["w"])
+        x, taps = _ring(d["x"]), pkg.filter_pack_s2(d["w"])
         if not self.proj:
             return pkg.conv3x3_s2_bn_relu(x, taps, d["b"], d["s"], relu=self.relu,
                                           out=torch.full(self.one, NAN, device=x.device))
@@ -474,14 +445,10 @@ class ConvS2(Layer):
         return torch.stack((t1, sc))
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        xi = _nchw(t["x"])
-        y = _affine(F.conv2d(xi, t["w"].double(), stride=2, padding=1), t["b"], t["s"])
-        y = _ring(torch, (torch.relu(y) if self.relu else y).permute(0, 2, 3, 1).contiguous())
         if not self.proj:
-            return y
-        sc = _affine(F.conv2d(xi, t["wd"].double(), stride=2), t["bd"], t["sd"])
-        return torch.stack((y, _ring(torch, sc.permute(0, 2, 3, 1).contiguous())))
+            return _ring(LR.conv3x3(t["x"], t["w"], (t["b"], t["s"]), self.relu, stride=2))
+        t1, sc, _ = LR.basic_block_s2(t["x"], t["w"], (t["b"], t["s"]), t["wd"], (t["bd"], t["sd"]))
+        return self.torch.stack((_ring(t1), _ring(sc)))
 
     def footprint(self, p):
         N, Hin, Win, C, K = self.shape
@@ -507,7 +474,7 @@ class Grouped(Layer):
         super().__init__(torch, f"grouped relu={int(relu)} s{stride} {N}x{Hin}x{Win} C={C} Cg={Cg}", seed)
         self.relu, self.stride, self.shape, self.groups = relu, stride, (N, Hin, Win, C, Cg), C // Cg
         self.act("x", N, Hin, Win, C)
-        self.t["w"] = self.conv_w(C, Cg)
+        self.t["w"] = LR.conv_w(self.rand, C, Cg)
         self.params["w"] = [(0, (0, Cg - 1, 0, 2)), (C - 1, (C - 1, 0, 1, 1))]
         self.bn(C)
         self.H, self.W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
@@ -515,16 +482,13 @@ class Grouped(Layer):
 
     def run(self, pkg, d):
         torch = self.torch
-        x = _ring(torch, d["x"])
+        x = _ring(d["x"])
         return pkg.conv3x3_grouped_bn_relu(x, pkg.filter_pack_grouped(d["w"], self.groups), d["b"], d["s"], self.groups,
                                            stride=self.stride, relu=self.relu,
                                            out=torch.full(self.out_shape, NAN, device=x.device))
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        y = F.conv2d(_nchw(t["x"]), t["w"].double(), stride=self.stride, padding=1, groups=self.groups)
-        y = _affine(y, t["b"], t["s"])
-        return _ring(torch, (torch.relu(y) if self.relu else y).permute(0, 2, 3, 1).contiguous())
+        return _ring(LR.conv3x3(t["x"], t["w"], (t["b"], t["s"]), self.relu, stride=self.stride, groups=self.groups))
 
     def footprint(self, p):
         N, Hin, Win, C, Cg = self.shape
@@ -568,10 +532,8 @@ class Stem(Layer):
                         out=self.torch.full(self.out_shape, NAN, device=d["x"].device))
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        y = torch.relu(_affine(F.conv2d(t["x"].double(), t["w"].double(), stride=2, padding=3), t["b"], t["s"]))
-        y = F.max_pool2d(y, 3, 2, 1).permute(0, 2, 3, 1).contiguous()
-        return _ring(torch, y) if self.ring else y
+        y = LR.stem(t["x"], t["w"], (t["b"], t["s"]))
+        return _ring(y) if self.ring else y
 
     def footprint(self, p):
         N, H, W, K = self.shape
@@ -602,14 +564,13 @@ class Head(Layer):
 
     def run(self, pkg, d):
         N, H, W, C, classes = self.shape
-        f = _ring(self.torch, d["feat"], NAN) if self.padded else d["feat"]
+        f = _ring(d["feat"], NAN) if self.padded else d["feat"]
         out = self.torch.full((N, classes), NAN, device=f.device)
         return pkg.avgpool_fc(f, pkg.head_pack(d["wfc"], d["bfc"]), classes, in_padded=self.padded,
                               out=out).view(self.out_shape)
 
     def ref(self, t):
-        y = t["feat"].double().mean(dim=(1, 2)) @ t["wfc"].double().t() + t["bfc"].double()
-        return y.view(self.out_shape)
+        return LR.avgpool_fc(t["feat"], t["wfc"], t["bfc"]).view(self.out_shape)
 
     def footprint(self, p):
         if p.where == "param":
@@ -660,13 +621,12 @@ class AvgPool7(Layer):
         self.out_shape = (N, 7, 7, C)
 
     def run(self, pkg, d):
-        f = _ring(self.torch, d["feat"], NAN) if self.padded else d["feat"]
+        f = _ring(d["feat"], NAN) if self.padded else d["feat"]
         out = self.torch.full((self.shape[0], 49 * self.shape[3]), NAN, device=f.device)
         return pkg.avgpool7_flatten(f, in_padded=self.padded, out=out).view(self.out_shape)
 
     def ref(self, t):
-        y = self.torch.nn.functional.adaptive_avg_pool2d(_nchw(t["feat"]), (7, 7))
-        return y.permute(0, 2, 3, 1).contiguous()
+        return LR.avgpool7(t["feat"])
 
     def footprint(self, p):
         N, H, W, C = self.shape
@@ -713,16 +673,6 @@ class Block(Layer):
     def footprint(self, p):
         return box(self.torch, self.out_shape[-4:], p.index[0], ring=self.ring).expand(self.out_shape).clone()
 
-    def w11(self, i, o, gain=4):
-        return (self.rand(i, o) - 0.5) / np.sqrt(i) * gain
-
-    def conv1x1(self, x, w_io, stride=1):
-        return self.torch.nn.functional.conv2d(x, w_io.double().t()[:, :, None, None], stride=stride)
-
-    def nhwc(self, y):
-        y = y.permute(0, 2, 3, 1).contiguous()
-        return _ring(self.torch, y) if self.ring else y
-
     def nan_out(self, dev):
         return self.torch.full(self.out_shape, NAN, device=dev)
 
@@ -736,11 +686,11 @@ class Bottleneck(Block):
         self.kind, self.stride, self.groups = kind, stride, groups
         self.identity = kind in ("residual_block", "grouped_residual_block")
         self.act("x", self.N, H, W, Cin)
-        self.t["w1"], self.t["w3"] = self.w11(Cin, Cm), self.w11(Cm, C4)
-        self.t["w2"] = self.conv_w(Cm, Cm // groups)
+        self.t["w1"], self.t["w3"] = LR.w11(self.rand, Cin, Cm), LR.w11(self.rand, Cm, C4)
+        self.t["w2"] = LR.conv_w(self.rand, Cm, Cm // groups)
         self.bn(Cm, "b1", "s1"), self.bn(Cm, "b2", "s2"), self.bn(C4, "b3", "s3")
         if not self.identity:
-            self.t["wp"] = self.w11(Cin, C4, 2)
+            self.t["wp"] = LR.w11(self.rand, Cin, C4, 2)
             self.bn(C4, "bp", "sp")
         self.params = {}
         self.case_shape = {"N": self.N, "Hin": H, "Win": W, "Cin": Cin, "Cm": Cm, "C4": C4}   # (shape_sweeps.Case)
@@ -765,16 +715,10 @@ class Bottleneck(Block):
         return pkg.grouped_proj_block(d["x"], d["w1"], bn(1), wg, bn(2), *last, self.groups, self.stride, out=out)
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        x, st = _nchw(t["x"]), self.stride
-        xs = x[:, :, ::st, ::st]
-        first_strided = self.kind == "proj_block"          # v1: the stride on the first 1x1
-        t1 = torch.relu(_affine(self.conv1x1(xs if first_strided else x, t["w1"]), t["b1"], t["s1"]))
-        t2 = F.conv2d(t1, t["w2"].double(), stride=1 if first_strided else st, padding=1, groups=self.groups)
-        t2 = torch.relu(_affine(t2, t["b2"], t["s2"]))
-        y = _affine(self.conv1x1(t2, t["w3"]), t["b3"], t["s3"])
-        y = y + (x if self.identity else _affine(self.conv1x1(xs, t["wp"]), t["bp"], t["sp"]))
-        return self.nhwc(torch.relu(y))
+        bn = lambda i: (t[f"b{i}"], t[f"s{i}"])
+        proj = () if self.identity else (t["wp"], bn("p"))
+        return LR.bottleneck(t["x"], t["w1"], bn(1), t["w2"], bn(2), t["w3"], bn(3), *proj, stride=self.stride,
+                             stride_on="first" if self.kind == "proj_block" else "3x3", groups=self.groups)   # v1: on the first 1x1
 
 
 class Basic(Block):
@@ -785,17 +729,17 @@ class Basic(Block):
         super().__init__(torch, f"basic_block{'_s2' if s2 else ''} 2x{H}x{W} {C}->{K}", seed)
         self.s2 = s2
         self.act("x", self.N, H, W, C)
-        self.t["w1"], self.t["w2"] = self.conv_w(K, C), self.conv_w(K, K)
+        self.t["w1"], self.t["w2"] = LR.conv_w(self.rand, K, C), LR.conv_w(self.rand, K, K)
         self.bn(K, "b1", "s1"), self.bn(K, "b2", "s2")
         if s2:
-            self.t["wd"] = self.conv_w(K, C, k=1)
+            self.t["wd"] = LR.conv_w(self.rand, K, C, k=1)
             self.bn(K, "bd", "sd")
         self.params = {}
         Ho, Wo = (s2_out(H), s2_out(W)) if s2 else (H, W)
         self.out_shape = (self.N, Ho + 2, Wo + 2, K)
 
     def run(self, pkg, d):
-        x, out = _ring(self.torch, d["x"]), self.nan_out(d["x"].device)
+        x, out = _ring(d["x"]), self.nan_out(d["x"].device)
         U2, bn2 = pkg.filter_transform_f2(d["w2"]), (d["b2"], d["s2"])
         if not self.s2:
             return pkg.basic_block(x, pkg.filter_transform_f2(d["w1"]), (d["b1"], d["s1"]), U2, bn2, out=out)
@@ -805,11 +749,10 @@ class Basic(Block):
         return pkg.basic_block_s2(x, packed, U2, bn2, out=out)
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        x = _nchw(t["x"])
-        t1 = torch.relu(_affine(F.conv2d(x, t["w1"].double(), stride=2 if self.s2 else 1, padding=1), t["b1"], t["s1"]))
-        sc = _affine(F.conv2d(x, t["wd"].double(), stride=2), t["bd"], t["sd"]) if self.s2 else x
-        return self.nhwc(torch.relu(_affine(F.conv2d(t1, t["w2"].double(), padding=1), t["b2"], t["s2"]) + sc))
+        bn1, bn2 = (t["b1"], t["s1"]), (t["b2"], t["s2"])
+        if self.s2:
+            return _ring(LR.basic_block_s2(t["x"], t["w1"], bn1, t["wd"], (t["bd"], t["sd"]), t["w2"], bn2)[2])
+        return _ring(LR.basic_block(t["x"], t["w1"], bn1, t["w2"], bn2))
 
 
 class FpnLevel(Block):
@@ -821,25 +764,21 @@ class FpnLevel(Block):
         super().__init__(torch, f"fpn_level 2x{H}x{W} {Cin}->{Cf}", seed)
         self.act("c", self.N, H, W, Cin)
         self.act("top", self.N, (H + 1) // 2, (W + 1) // 2, Cf)
-        self.t["wl"], self.t["wo"] = self.w11(Cin, Cf), self.conv_w(Cf, Cf)
+        self.t["wl"], self.t["wo"] = LR.w11(self.rand, Cin, Cf), LR.conv_w(self.rand, Cf, Cf)
         self.t["bl"], self.t["bo"] = self.rand(Cf) - 0.5, self.rand(Cf) - 0.5
-        self.hw = (H, W)
         self.out_shape = (2, self.N, H + 2, W + 2, Cf)
 
     def run(self, pkg, d):
         torch = self.torch
         one = self.out_shape[1:]
         inner, P = pkg.fpn_level(d["c"], d["wl"], d["bl"], pkg.filter_transform_f2(d["wo"]), d["bo"],
-                                 top=_ring(torch, d["top"], NAN), inner=torch.full(one, NAN, device=d["c"].device),
+                                 top=_ring(d["top"], NAN), inner=torch.full(one, NAN, device=d["c"].device),
                                  out=torch.full(one, NAN, device=d["c"].device))
         return torch.stack((inner, P))
 
     def ref(self, t):
-        torch, F = self.torch, self.torch.nn.functional
-        inner = self.conv1x1(_nchw(t["c"]), t["wl"]) + t["bl"].double()[None, :, None, None]
-        inner = inner + F.interpolate(_nchw(t["top"]), size=self.hw, mode="nearest")
-        P = F.conv2d(inner, t["wo"].double(), t["bo"].double(), padding=1)
-        return torch.stack((self.nhwc(inner), self.nhwc(P)))
+        inner, P = level_reference(self.torch, t["c"], LR.w1x1(t["wl"]), t["bl"], t["wo"], t["bo"], t["top"])
+        return self.torch.stack((_ring(inner.contiguous()), _ring(P.contiguous())))
 
 
 def blocks(torch):

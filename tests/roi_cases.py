@@ -13,6 +13,8 @@ import math
 import numpy as np
 import torch
 
+from layer_refs import rel as rel_err, ring  # noqa: F401  (rel_err: the tests' metric, read from here)
+
 # ---- the base pyramid ------------------------------------------------------------------------------------------------------
 IMAGE = (64, 48)                                   # H, W of the image the boxes live in
 LEVEL_HW = ((16, 12), (8, 6), (4, 3), (2, 2))      # (h, w) of the four levels, strides 4 .. 32
@@ -36,10 +38,7 @@ def pyramid(C, seed=0, hw=LEVEL_HW, N=N_IMAGES):
 
 def padded_nan(t):
     """[N][h][w][C] -> [N][h+2][w+2][C] with a NaN ring: one ring read by the kernel shows in its result."""
-    N, h, w, C = t.shape
-    p = torch.full((N, h + 2, w + 2, C), float("nan"), dtype=t.dtype)
-    p[:, 1:-1, 1:-1, :] = t
-    return p
+    return ring(t, float("nan"))
 
 
 # ---- levels ------------------------------------------------------------------------------------------------------------------
@@ -144,15 +143,6 @@ def roi_align_reference(maps, rois, P, scales, sampling, levels, dtype=torch.flo
             for j, r in enumerate(sel.tolist()):
                 touched[r] = (l, int(img[j]), Ty[j], Tx[j])
     return (out, touched) if taps else out
-
-
-def rel_err(got, want):
-    """max |got - want| / max |want| of two tensors; both finite."""
-    got, want = got.detach().cpu().double(), want.double()
-    assert got.shape == want.shape, (tuple(got.shape), tuple(want.shape))
-    assert bool(torch.isfinite(got).all()), "got holds non-finite values"
-    assert bool(torch.isfinite(want).all()), "the reference holds non-finite values"
-    return float((got - want).abs().max() / want.abs().max())
 
 
 # ---- the box generator ---------------------------------------------------------------------------------------------------------

@@ -4,18 +4,20 @@ case's fp32 tensors (CPU masters; device copies on a guarded arena of tests/guar
 the checks; each runner launches twice per placement, compares with the fp64 reference at TIGHT and ends each placement
 in arena.check, which CHECKS counts by entry point."""
 import collections
-import contextlib
 import types
 
 import numpy as np
 
 import aspp_cases as AC
 import guarded as G
+import layer_refs as LR
 import resize_cases as RC
 import shape_sweeps as S
 from cases import TIGHT
 from dilated_cases import dilated_reference
+from forms_1x1 import knobs_set
 from fpn_reference import level_reference
+from layer_refs import bn_pair, conv_w, interior, ring, w11
 
 SENTINEL = 1234.5
 CHECKS = collections.Counter()   # arena.check calls that passed, by entry point
@@ -26,24 +28,11 @@ SEEDS = {"conv3x3_dilated_bn_relu": 1000, "dilated_block": 1100, "conv1x1_cat_bn
          "resize_bilinear": 1400, "conv3x3_grouped_bn_relu": 1500, "grouped_block": 1600, "fpn_level": 1700}
 
 
-@contextlib.contextmanager
-def forced(knobs, case):
-    for k, v in (case.knobs or {}).items():
-        knobs.set(k, v)
-    try:
-        yield
-    finally:
-        for k in case.knobs or {}:
-            knobs.unset(k)
-
-
-
 class Sweep:
     """fp32 tensors drawn for one case (CPU masters; `dev` copies), fp64 reference helpers, and the checks."""
 
     def __init__(self, torch, dev, case, pkg, seed):
         self.torch, self.dev, self.case, self.pkg = torch, dev, case, pkg
-        self.F = torch.nn.functional
         self.g = torch.Generator().manual_seed(seed)
         self.tag = self.base_tag = case.tag()
         self.arena = None
@@ -64,21 +53,6 @@ class Sweep:
         """Activations: uniform in [-0.5, 0.5), or in [0, 1) (non-zero mean, as after a ReLU) for nonneg cases."""
         r = self.rand(*shape)
         return r if self.case.flags.get("nonneg") else r - 0.5
-
-    def conv_w(self, K, C, k=3):
-        return (self.rand(K, C, k, k) - 0.5) / np.sqrt(k * k * C) * 4
-
-    def bn(self, K):
-        """(bias, scale) with a negative scale on every third channel."""
-        bias, scale = self.rand(K) - 0.5, self.rand(K) + 0.5
-        scale[::3] *= -1
-        return bias, scale
-
-    def padded(self, inner, ring=0.0):
-        N, H, W, C = inner.shape
-        x = self.torch.full((N, H + 2, W + 2, C), ring)
-        x[:, 1:-1, 1:-1, :] = inner
-        return x
 
     def nan(self, *shape, name=None):
         """A NaN-filled output between sentinel guards."""
@@ -114,38 +88,16 @@ class Sweep:
         """A fresh guarded copy of `t` that the launch writes in place."""
         return self.arena.input(t, name=name, in_place=True)
 
-    # fp64 reference pieces, NCHW
-    @staticmethod
-    def nchw(x_nhwc):
-        return x_nhwc.permute(0, 3, 1, 2).double()
-
-    def conv(self, x, w, stride=1, pad=1):
-        return self.F.conv2d(x, w.double(), stride=stride, padding=pad)
-
-    def conv1x1(self, x, w_io, stride=1):
-        """w [Cin][Cout] (the library's 1x1 layout)."""
-        return self.F.conv2d(x, w_io.double().t()[:, :, None, None], stride=stride)
-
-    @staticmethod
-    def affine(y, bn):
-        b, s = bn
-        return y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-
     # checks
     def close(self, got, want, what="out"):
-        g = got.detach().cpu().double() if hasattr(got, "detach") else got
-        w = want.detach().cpu().double() if hasattr(want, "detach") else want
-        assert tuple(g.shape) == tuple(w.shape), f"{self.tag} {what}: shape {tuple(g.shape)} != {tuple(w.shape)}"
-        assert bool(self.torch.isfinite(g).all()), f"{self.tag} {what}: non-finite values (not all written)"
-        err = float((g - w).abs().max() / w.abs().max())
+        assert tuple(got.shape) == tuple(want.shape), f"{self.tag} {what}: shape {tuple(got.shape)} != {tuple(want.shape)}"
+        assert bool(self.torch.isfinite(got).all()), f"{self.tag} {what}: non-finite values (not all written)"
+        err = LR.rel(got, want)
         WORST[self.case.entry] = max(WORST.get(self.case.entry, 0.0), err)
         assert err < TIGHT, f"{self.tag} {what}: rel err {err:.3e}"
 
     def ring_is(self, got, value, what="out"):
-        g = got.detach().cpu()
-        ring = self.torch.ones(g.shape[1:3], dtype=self.torch.bool)
-        ring[1:-1, 1:-1] = False
-        assert bool((g[:, ring, :] == value).all()), f"{self.tag} {what}: ring is not exactly {value}"
+        assert LR.ring_is(got.detach().cpu(), value), f"{self.tag} {what}: ring is not exactly {value}"
 
     def both_sides(self, pre):
         pos, neg = int((pre > 0).sum()), int((pre < 0).sum())
@@ -153,6 +105,14 @@ class Sweep:
 
     def same(self, a, b, what="out"):
         assert self.torch.equal(a, b), f"{self.tag} {what}: two launches differ"
+
+    def agree(self, outs, want, what="out", padded=False):
+        """Two launches' outputs: the first against the reference (of a padded one the ring is exactly 0 and the interior
+        is compared), the second bitwise the first."""
+        if padded:
+            self.ring_is(outs[0], 0.0, what)
+        self.close(interior(outs[0]) if padded else outs[0], want, what)
+        self.same(outs[0], outs[1], what)
 
     def done(self):
         assert self.pkg.tickets_in_use() == 0, f"{self.tag}: a stream-K ticket is still held"
@@ -179,7 +139,7 @@ def run_sweep(entry, run, pkg, knobs, torch_dev, seed0):
     WORST.pop(entry, None)
     for i, case in enumerate(cases):
         assert case.entry == entry
-        with forced(knobs, case):
+        with knobs_set(knobs, case.knobs):
             run(pkg, knobs, torch_dev, case, seed0 + i)
     done = CHECKS[entry] - before
     if entry in WORST:
@@ -195,23 +155,21 @@ def fpn_level_case(pkg, knobs, torch_dev, case, seed):
     torch, nan = sw.torch, float("nan")
     N, H, W, Cin, Cf = case.N, case.H, case.W, case.Cin, case.Cf
     c = sw.act(N, H, W, Cin)
-    wl, wo = sw.conv_w(Cf, Cin, k=1), sw.conv_w(Cf, Cf)
+    wl, wo = conv_w(sw.rand, Cf, Cin, k=1), conv_w(sw.rand, Cf, Cf)
     bl, bo = sw.rand(Cf) - 0.5, sw.rand(Cf) - 0.5
     top = sw.act(N, (H + 1) // 2, (W + 1) // 2, Cf) if case.flags["top"] else None
     want_inner, want_P = level_reference(torch, c, wl, bl, wo, bo, top)
     for _ in sw.passes():
-        cd = sw.d(sw.padded(c, ring=nan) if case.flags["c_padded"] else c, "c")
+        cd = sw.d(ring(c, nan) if case.flags["c_padded"] else c, "c")
         wld, U = sw.d(wl.reshape(Cf, Cin).t().contiguous(), "w_lat"), sw.U(wo)
         bld, bod, ones = sw.d(bl, "b_lat"), sw.d(bo, "b_out"), sw.d(torch.ones(Cf), "ones")
-        topd = sw.d(sw.padded(top, ring=nan), "top") if top is not None else None
+        topd = sw.d(ring(top, nan), "top") if top is not None else None
         outs = []
         for _ in range(2):
             outs.append(pkg.fpn_level(cd, wld, bld, U, bod, top=topd, c_padded=case.flags["c_padded"], ones=ones,
                                       inner=sw.nan(N, H + 2, W + 2, Cf, name="inner"), out=sw.nan(N, H + 2, W + 2, Cf, name="P")))
         for k, (name, want) in enumerate((("inner", want_inner), ("P", want_P))):
-            sw.ring_is(outs[0][k], 0.0, name)
-            sw.close(outs[0][k][:, 1:-1, 1:-1, :], want, name)
-            sw.same(outs[0][k], outs[1][k], name)
+            sw.agree((outs[0][k], outs[1][k]), want, name, padded=True)
 
 
 # ---- the residual 3x3 ------------------------------------------------------------------------------------------------
@@ -219,11 +177,11 @@ def residual_case(pkg, knobs, torch_dev, case, seed):
     sw = start(pkg, knobs, torch_dev, case, seed)
     N, H, W, C, K = case.N, case.H, case.W, case.C, case.K
     relu, in_place = case.flags["relu"], case.flags["in_place"]
-    x = sw.padded(sw.act(N, H, W, C))
-    res = sw.padded(sw.act(N, H, W, K), ring=float("nan"))   # the residual's ring is not read
-    w, bn = sw.conv_w(K, C), sw.bn(K)
-    pre = sw.affine(sw.conv(sw.nchw(x[:, 1:-1, 1:-1, :]), w), bn) + sw.nchw(res[:, 1:-1, 1:-1, :])
-    want = (sw.torch.relu(pre) if relu else pre).permute(0, 2, 3, 1)
+    x = ring(sw.act(N, H, W, C))
+    res = ring(sw.act(N, H, W, K), float("nan"))   # the residual's ring is not read
+    w, bn = conv_w(sw.rand, K, C), bn_pair(sw.rand, K)
+    pre = LR.conv3x3(interior(x), w, bn, False, residual=interior(res))
+    want = sw.torch.relu(pre) if relu else pre
     if relu:
         sw.both_sides(pre)
     for _ in sw.passes():
@@ -239,22 +197,18 @@ def residual_case(pkg, knobs, torch_dev, case, seed):
             else:
                 got = pkg.conv3x3_bn_add_relu(xd, U, bd, sd, resd, relu=relu, out=sw.nan(N, H + 2, W + 2, K))
             outs.append(got)
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 # ---- the identity basic block ----------------------------------------------------------------------------------------
 def basic_block_case(pkg, knobs, torch_dev, case, seed):
     sw = start(pkg, knobs, torch_dev, case, seed)
     N, H, W, C = case.N, case.H, case.W, case.C
-    x = sw.padded(sw.act(N, H, W, C))
-    w1, w2, bn1, bn2 = sw.conv_w(C, C), sw.conv_w(C, C), sw.bn(C), sw.bn(C)
-    xi = sw.nchw(x[:, 1:-1, 1:-1, :])
-    t1 = sw.torch.relu(sw.affine(sw.conv(xi, w1), bn1))
-    pre = sw.affine(sw.conv(t1, w2), bn2) + xi
+    x = ring(sw.act(N, H, W, C))
+    w1, w2, bn1, bn2 = conv_w(sw.rand, C, C), conv_w(sw.rand, C, C), bn_pair(sw.rand, C), bn_pair(sw.rand, C)
+    pre = LR.basic_block(interior(x), w1, bn1, w2, bn2, pre=True)
     sw.both_sides(pre)
-    want = sw.torch.relu(pre).permute(0, 2, 3, 1)
+    want = sw.torch.relu(pre)
     need = pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, W, C)
     for _ in sw.passes():
         U1, U2 = sw.U(w1, "U1"), sw.U(w2, "U2")
@@ -270,27 +224,25 @@ def basic_block_case(pkg, knobs, torch_dev, case, seed):
             else:
                 got = pkg.basic_block(xd, U1, bnd1, U2, bnd2, out=sw.nan(N, H + 2, W + 2, C), workspace=ws)
             outs.append(got)
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 # ---- the stride-2 3x3, the fused stride-2 3x3 + shortcut, the downsampling basic block ---------------------------
 class S2Case:
-    """A stride-2 case's tensors: padded x, the 3x3 and 1x1 shortcut weights, their BNs, and the fp64 t1, sc."""
+    """A stride-2 case's tensors: padded x, the 3x3 and 1x1 shortcut weights, their BNs, and the fp64 pre1 (t1 before
+    its ReLU) and sc, NHWC."""
 
     def __init__(self, sw, case, with_block=False):
         N, Hin, Win, C, K = case.N, case.Hin, case.Win, case.C, case.K
         self.H, self.W = S._s2(Hin), S._s2(Win)
-        self.x = sw.padded(sw.act(N, Hin, Win, C))
-        self.w1, self.wd = sw.conv_w(K, C), sw.conv_w(K, C, k=1)
-        self.bn1, self.bnd = sw.bn(K), sw.bn(K)
-        xi = sw.nchw(self.x[:, 1:-1, 1:-1, :])
-        self.pre1 = sw.affine(sw.conv(xi, self.w1, stride=2), self.bn1)
-        self.sc = sw.affine(sw.F.conv2d(xi, self.wd.double(), stride=2), self.bnd)
+        self.x = ring(sw.act(N, Hin, Win, C))
+        self.w1, self.wd = conv_w(sw.rand, K, C), conv_w(sw.rand, K, C, k=1)
+        self.bn1, self.bnd = bn_pair(sw.rand, K), bn_pair(sw.rand, K)
+        self.pre1 = LR.conv3x3(interior(self.x), self.w1, self.bn1, False, stride=2)
+        self.sc = LR.conv1x1(interior(self.x), self.wd[:, :, 0, 0].t(), self.bnd, False, stride=2)
         self.shape = (N, self.H + 2, self.W + 2, K)
         if with_block:
-            self.w2, self.bn2 = sw.conv_w(K, K), sw.bn(K)
+            self.w2, self.bn2 = conv_w(sw.rand, K, K), bn_pair(sw.rand, K)
 
     def place(self, sw):
         """The device operands of one pass, on sw's arena."""
@@ -311,13 +263,11 @@ def s2_case(pkg, knobs, torch_dev, case, seed):
     relu = case.flags["relu"]
     if relu:
         sw.both_sides(L.pre1)
-    want = (sw.torch.relu(L.pre1) if relu else L.pre1).permute(0, 2, 3, 1)
+    want = sw.torch.relu(L.pre1) if relu else L.pre1
     for _ in sw.passes():
         L.place(sw)
         outs = [pkg.conv3x3_s2_bn_relu(L.xd, L.taps, *L.bn1d, relu=relu, out=sw.nan(*L.shape)) for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 def s2_proj_case(pkg, knobs, torch_dev, case, seed):
@@ -336,8 +286,8 @@ def s2_proj_case(pkg, knobs, torch_dev, case, seed):
         (t1, sc), (t1b, scb) = runs
         sw.ring_is(t1, 0.0, "t1")
         sw.ring_is(sc, SENTINEL, "sc")
-        sw.close(t1[:, 1:-1, 1:-1, :], sw.torch.relu(L.pre1).permute(0, 2, 3, 1), "t1")
-        sw.close(sc[:, 1:-1, 1:-1, :], L.sc.permute(0, 2, 3, 1), "sc")
+        sw.close(t1[:, 1:-1, 1:-1, :], sw.torch.relu(L.pre1), "t1")
+        sw.close(sc[:, 1:-1, 1:-1, :], L.sc, "sc")
         plain = pkg.conv3x3_s2_bn_relu(L.xd, L.taps, *L.bn1d, relu=True, out=sw.nan(*L.shape))
         sw.same(t1, plain, "t1 against the plain stride-2 layer:")
         sw.same(t1, t1b, "t1")
@@ -347,10 +297,9 @@ def s2_proj_case(pkg, knobs, torch_dev, case, seed):
 def basic_block_s2_case(pkg, knobs, torch_dev, case, seed):
     sw = start(pkg, knobs, torch_dev, case, seed)
     L = S2Case(sw, case, with_block=True)
-    t1 = sw.torch.relu(L.pre1)
-    pre = sw.affine(sw.conv(t1, L.w2), L.bn2) + L.sc
+    pre = LR.basic_block_s2(interior(L.x), L.w1, L.bn1, L.wd, L.bnd, L.w2, L.bn2, pre=True)[2]
     sw.both_sides(pre)
-    want = sw.torch.relu(pre).permute(0, 2, 3, 1)
+    want = sw.torch.relu(pre)
     need = pkg.lib().wino_basic_block_s2_workspace_bytes_hw(case.N, case.Hin, case.Win, case.K)
     for _ in sw.passes():
         L.place(sw)
@@ -359,9 +308,7 @@ def basic_block_s2_case(pkg, knobs, torch_dev, case, seed):
         outs = [pkg.basic_block_s2(L.xd, packed, U2, bn2, out=sw.nan(*L.shape),
                                    workspace=sw.ws(need, "wino_basic_block_s2_workspace_bytes_hw"))
                 for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 # ---- the projection bottleneck blocks ------------------------------------------------------------------------------
@@ -369,9 +316,9 @@ class ProjCase:
     def __init__(self, sw, case):
         N, Hin, Win, Cin, Cm, C4 = case.N, case.Hin, case.Win, case.Cin, case.Cm, case.C4
         self.x = sw.act(N, Hin, Win, Cin)
-        w11 = lambda i, o, gain: (sw.rand(i, o) - 0.5) / np.sqrt(i) * gain
-        self.w1, self.w2, self.w3, self.wp = w11(Cin, Cm, 4), sw.conv_w(Cm, Cm), w11(Cm, C4, 4), w11(Cin, C4, 2)
-        self.bn = [sw.bn(c) for c in (Cm, Cm, C4, C4)]
+        r = sw.rand
+        self.w1, self.w2, self.w3, self.wp = w11(r, Cin, Cm), conv_w(r, Cm, Cm), w11(r, Cm, C4), w11(r, Cin, C4, 2)
+        self.bn = [bn_pair(sw.rand, c) for c in (Cm, Cm, C4, C4)]
 
     def place(self, sw):
         """The device operands of one pass, on sw's arena."""
@@ -382,12 +329,10 @@ class ProjCase:
                               sw.d(self.w3, "w3"), self.bnd[2], sw.d(self.wp, "wp"), self.bnd[3])
 
     def reference(self, sw, stride, v15):
-        """(pre-ReLU sum, output) in fp64, NCHW."""
-        x = sw.nchw(self.x)
-        xs = x[:, :, ::stride, ::stride]
-        t1 = sw.torch.relu(sw.affine(sw.conv1x1(x if v15 else xs, self.w1), self.bn[0]))
-        t2 = sw.torch.relu(sw.affine(sw.conv(t1, self.w2, stride=2 if v15 else 1), self.bn[1]))
-        pre = sw.affine(sw.conv1x1(t2, self.w3), self.bn[2]) + sw.affine(sw.conv1x1(xs, self.wp), self.bn[3])
+        """(pre-ReLU sum, output) in fp64, NHWC."""
+        bn = self.bn
+        pre = LR.bottleneck(self.x, self.w1, bn[0], self.w2, bn[1], self.w3, bn[2], self.wp, bn[3], stride=stride,
+                            stride_on="3x3" if v15 else "first", pre=True)
         return pre, sw.torch.relu(pre)
 
 
@@ -403,8 +348,7 @@ def proj_case(pkg, knobs, torch_dev, case, seed):
         U2 = sw.U(B.w2, "U2")
         outs = [pkg.proj_block(B.xd, B.w1d, B.bnd[0], U2, B.bnd[1], B.tail, st, out=sw.nan(case.N, H, W, case.C4),
                                workspace=sw.ws(need, "wino_proj_block_workspace_bytes_hw")) for _ in range(2)]
-        sw.close(outs[0], want.permute(0, 2, 3, 1))
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want)
 
 
 def v15_case(pkg, knobs, torch_dev, case, seed):
@@ -419,8 +363,7 @@ def v15_case(pkg, knobs, torch_dev, case, seed):
         taps = sw.packed(pkg.filter_pack_s2, (3, 3, case.Cm, case.Cm), "taps", sw.d(B.w2, "w2"))
         outs = [pkg.proj_block_v15(B.xd, B.w1d, B.bnd[0], taps, B.bnd[1], B.tail, out=sw.nan(case.N, H, W, case.C4),
                                    workspace=sw.ws(need, "wino_proj_block_v15_workspace_bytes_hw")) for _ in range(2)]
-        sw.close(outs[0], want.permute(0, 2, 3, 1))
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want)
 
 
 # ---- the grouped 3x3 and the ResNeXt blocks ----------------------------------------------------------------------------
@@ -428,12 +371,12 @@ def grouped_case(pkg, knobs, torch_dev, case, seed):
     sw = start(pkg, knobs, torch_dev, case, seed)
     N, Hin, Win, C, groups, stride, relu = case.N, case.Hin, case.Win, case.C, case.groups, case.stride, case.flags["relu"]
     H, W = S.grouped_out(Hin, Win, stride)
-    x = sw.padded(sw.act(N, Hin, Win, C))          # the ring is read: zero, as the contract says
-    w, bn = sw.conv_w(C, C // groups), sw.bn(C)
-    pre = sw.affine(sw.F.conv2d(sw.nchw(x[:, 1:-1, 1:-1, :]), w.double(), stride=stride, padding=1, groups=groups), bn)
+    x = ring(sw.act(N, Hin, Win, C))          # the ring is read: zero, as the contract says
+    w, bn = conv_w(sw.rand, C, C // groups), bn_pair(sw.rand, C)
+    pre = LR.conv3x3(interior(x), w, bn, False, stride=stride, groups=groups)
     if relu:
         sw.both_sides(pre)
-    want = (sw.torch.relu(pre) if relu else pre).permute(0, 2, 3, 1)
+    want = sw.torch.relu(pre) if relu else pre
     elems = pkg.lib().wino_conv3x3_grouped_filter_elems(C, groups)
     for _ in sw.passes():
         xd = sw.d(x, "x")
@@ -442,9 +385,7 @@ def grouped_case(pkg, knobs, torch_dev, case, seed):
         bd, sd = sw.bnd(bn)
         outs = [pkg.conv3x3_grouped_bn_relu(xd, packed, bd, sd, groups, stride=stride, relu=relu,
                                             out=sw.nan(N, H + 2, W + 2, C)) for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 def grouped_block_case(pkg, knobs, torch_dev, case, seed):
@@ -453,15 +394,13 @@ def grouped_block_case(pkg, knobs, torch_dev, case, seed):
     groups, stride, proj = case.groups, case.stride, case.proj
     H, W = S.grouped_out(Hin, Win, stride)
     x = sw.act(N, Hin, Win, Cin)
-    w11 = lambda i, o, gain: (sw.rand(i, o) - 0.5) / np.sqrt(i) * gain
-    w1, wg, w3, wp = w11(Cin, Cm, 4), sw.conv_w(Cm, Cm // groups), w11(Cm, C4, 4), w11(Cin, C4, 2)
-    bn = [sw.bn(c) for c in (Cm, Cm, C4, C4)]
-    xi = sw.nchw(x)
-    t1 = sw.torch.relu(sw.affine(sw.conv1x1(xi, w1), bn[0]))
-    t2 = sw.torch.relu(sw.affine(sw.F.conv2d(t1, wg.double(), stride=stride, padding=1, groups=groups), bn[1]))
-    pre = sw.affine(sw.conv1x1(t2, w3), bn[2]) + (sw.affine(sw.conv1x1(xi, wp, stride=stride), bn[3]) if proj else xi)
+    r = sw.rand
+    w1, wg, w3, wp = w11(r, Cin, Cm), conv_w(r, Cm, Cm // groups), w11(r, Cm, C4), w11(r, Cin, C4, 2)
+    bn = [bn_pair(r, c) for c in (Cm, Cm, C4, C4)]
+    pre = LR.bottleneck(x, w1, bn[0], wg, bn[1], w3, bn[2], *((wp, bn[3]) if proj else ()), stride=stride,
+                        stride_on="3x3", groups=groups, pre=True)
     sw.both_sides(pre)
-    want = sw.torch.relu(pre).permute(0, 2, 3, 1)
+    want = sw.torch.relu(pre)
     L = pkg.lib()
     query, need = S.grouped_block_workspace(pkg, case)
     for _ in sw.passes():
@@ -479,8 +418,7 @@ def grouped_block_case(pkg, knobs, torch_dev, case, seed):
             run = lambda: pkg.grouped_residual_block(xd, w1d, bnd[0], wgd, bnd[1], w3d, bnd[2], groups,
                                                      out=sw.nan(N, H, W, C4), workspace=sw.ws(need, query))
         outs = [run(), run()]
-        sw.close(outs[0], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want)
 
 
 # ---- the stem and the head -----------------------------------------------------------------------------------------
@@ -489,10 +427,10 @@ def stem_case(pkg, knobs, torch_dev, case, seed):
     N, H, W, K, padded = case.N, case.H, case.W, case.K, case.flags["padded"]
     x = sw.rand(N, 3, H, W) * 2 - 1
     w = (sw.rand(K, 3, 7, 7) - 0.5) * 0.3
-    bn = sw.bn(K)
-    pre = sw.affine(sw.conv(x.double(), w, stride=2, pad=3), bn)
+    bn = bn_pair(sw.rand, K)
+    pre = LR.stem(x, w, bn, pre=True)
     sw.both_sides(pre)
-    want = sw.F.max_pool2d(sw.torch.relu(pre), 3, 2, 1).permute(0, 2, 3, 1)
+    want = LR.stem(x, w, bn)
     Hp, Wp = pkg.stem_out_hw(H, W)
     p = 2 if padded else 0
     for _ in sw.passes():
@@ -500,12 +438,7 @@ def stem_case(pkg, knobs, torch_dev, case, seed):
                            sw.bnd(bn))
         xd = sw.d(x, "x")
         outs = [pkg.stem(xd, packed, out_padded=padded, out=sw.nan(N, Hp + p, Wp + p, K)) for _ in range(2)]
-        got = outs[0]
-        if padded:
-            sw.ring_is(got, 0.0)
-            got = got[:, 1:-1, 1:-1, :]
-        sw.close(got, want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=padded)
 
 
 def head_case(pkg, knobs, torch_dev, case, seed):
@@ -514,8 +447,8 @@ def head_case(pkg, knobs, torch_dev, case, seed):
     feat = sw.rand(N, H, W, C) * 2            # post-ReLU features
     wfc = (sw.rand(classes, C) - 0.5) / np.sqrt(C) * 2
     bfc = sw.rand(classes) - 0.5
-    want = feat.double().mean(dim=(1, 2)) @ wfc.double().t() + bfc.double()
-    f = sw.padded(feat, ring=float("nan")) if padded else feat   # the padded input's ring is not read
+    want = LR.avgpool_fc(feat, wfc, bfc)
+    f = ring(feat, float("nan")) if padded else feat   # the padded input's ring is not read
     need = pkg.lib().wino_head_workspace_bytes(N, C, classes)
     for _ in sw.passes():
         packed = sw.packed(pkg.head_pack, pkg.lib().wino_head_elems(C, classes), "packed",
@@ -523,16 +456,15 @@ def head_case(pkg, knobs, torch_dev, case, seed):
         fd = sw.d(f, "feat")
         outs = [pkg.avgpool_fc(fd, packed, classes, in_padded=padded, out=sw.nan(N, classes),
                                workspace=sw.ws(need, "wino_head_workspace_bytes")) for _ in range(2)]
-        sw.close(outs[0], want, "logits")
-        sw.same(outs[0], outs[1], "logits")
+        sw.agree(outs, want, "logits")
 
 
 # ---- the dilated 3x3 and the dilated bottleneck blocks ----------------------------------------------------------------
 def dilated_case(pkg, knobs, torch_dev, case, seed):
     sw = start(pkg, knobs, torch_dev, case, seed)
     N, H, W, C, K, d, relu = case.N, case.H, case.W, case.C, case.K, case.d, case.flags["relu"]
-    x = sw.padded(sw.act(N, H, W, C))          # the ring is read: zero, as the contract says
-    w, bn = sw.conv_w(K, C), sw.bn(K)
+    x = ring(sw.act(N, H, W, C))          # the ring is read: zero, as the contract says
+    w, bn = conv_w(sw.rand, K, C), bn_pair(sw.rand, K)
     pre = sw.torch.from_numpy(dilated_reference(x.numpy(), w.numpy(), bn[1].numpy(), bn[0].numpy(), d, relu=False))
     if relu:
         sw.both_sides(pre)
@@ -543,9 +475,7 @@ def dilated_case(pkg, knobs, torch_dev, case, seed):
         bd, sd = sw.bnd(bn)
         outs = [pkg.conv3x3_dilated_bn_relu(xd, taps, bd, sd, d, relu=relu, out=sw.nan(N, H + 2, W + 2, K))
                 for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 def dilated_block_case(pkg, knobs, torch_dev, case, seed):
@@ -578,8 +508,7 @@ def dilated_block_case(pkg, knobs, torch_dev, case, seed):
             run = lambda: pkg.dilated_residual_block(xd, w1d, bnd[0], taps, bnd[1], last, bnd[2], d,
                                                      out=sw.nan(N, H, W, C4), workspace=sw.ws(need, query))
         outs = [run(), run()]
-        sw.close(outs[0], sw.torch.relu(pre))
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, sw.torch.relu(pre))
 
 
 # ---- the concat projection and ASPP ------------------------------------------------------------------------------------
@@ -591,7 +520,7 @@ def cat_case(pkg, knobs, torch_dev, case, seed):
     srcs = [sw.act(N, H, W, Cs) for _ in range(S)]
     w = (sw.rand(S * Cs, Kout) - 0.5) / np.sqrt(S * Cs) * 4
     bias = sw.rand(N, Kout) * 8 - 4            # a neighbouring image's row is far outside TIGHT
-    scale = sw.bn(Kout)[1]
+    scale = bn_pair(sw.rand, Kout)[1]
     pre = torch.from_numpy(AC.cat_reference([s.numpy() for s in srcs], w.numpy(), bias.numpy(), scale.numpy(), False))
     if relu:
         sw.both_sides(pre)
@@ -611,12 +540,7 @@ def cat_case(pkg, knobs, torch_dev, case, seed):
         views = [buf[j * stride: j * stride + n].view(shape) for j in range(S)]
         wd, bd, sd = sw.d(w, "w"), sw.d(bias, "bias_per_image"), sw.d(scale, "scale")
         outs = [pkg.conv1x1_cat_bn(views, wd, bd, sd, flags, out=sw.nan(*out_shape)) for _ in range(2)]
-        got = outs[0]
-        if c_pad:
-            sw.ring_is(got, 0.0)
-            got = got[:, 1:-1, 1:-1, :]
-        sw.close(got, want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=c_pad)
 
 
 class AsppProblem:
@@ -626,11 +550,11 @@ class AsppProblem:
     def __init__(self, sw, case):
         N, H, W, Cin, Cb, Kout = case.N, case.H, case.W, case.Cin, case.Cb, case.Kout
         shift = 0.2 * sw.torch.arange(N, dtype=sw.torch.float32)[:, None, None, None]
-        self.x = sw.padded(sw.act(N, H, W, Cin) + shift)
-        w11 = lambda i, o: (sw.rand(i, o) - 0.5) / np.sqrt(i) * 4
-        self.w0, self.ws = w11(Cin, Cb), [sw.conv_w(Cb, Cin) for _ in range(3)]
-        self.w_pool, self.w_proj = w11(Cin, Cb), w11(5 * Cb, Kout)
-        self.bn = [sw.bn(c) for c in (Cb, Cb, Cb, Cb, Cb, Kout)]   # b0, three dilated, pool, proj
+        self.x = ring(sw.act(N, H, W, Cin) + shift)
+        r = sw.rand
+        self.w0, self.ws = w11(r, Cin, Cb), [conv_w(r, Cb, Cin) for _ in range(3)]
+        self.w_pool, self.w_proj = w11(r, Cin, Cb), w11(r, 5 * Cb, Kout)
+        self.bn = [bn_pair(sw.rand, c) for c in (Cb, Cb, Cb, Cb, Cb, Kout)]   # b0, three dilated, pool, proj
         self.rates = tuple(case.rates)
 
     def reference(self, pooled=True):
@@ -654,9 +578,7 @@ def aspp_case(pkg, knobs, torch_dev, case, seed):
         outs = [pkg.aspp(xd, w0, bnd[0], taps, bnd[1:4], P.rates, w_pool, bnd[4], w_proj, bnd[5],
                          out=sw.nan(N, H + 2, W + 2, Kout), workspace=sw.ws(need, "aspp_workspace_bytes"))
                 for _ in range(2)]
-        sw.ring_is(outs[0], 0.0)
-        sw.close(outs[0][:, 1:-1, 1:-1, :], want)
-        sw.same(outs[0], outs[1])
+        sw.agree(outs, want, padded=True)
 
 
 # ---- the bilinear resize and label map ---------------------------------------------------------------------------------
@@ -665,7 +587,7 @@ def resize_src(sw, case):
     N, h, w, C, ld = case.N, case.h, case.w, case.C, case.ld
     x = sw.torch.full((N, h, w, ld), float("nan"))
     x[..., :C] = sw.rand(N, h, w, C) - 0.5
-    return sw.padded(x, ring=float("nan")) if case.flags["in_padded"] else x
+    return ring(x, float("nan")) if case.flags["in_padded"] else x
 
 
 def resize_case(pkg, knobs, torch_dev, case, seed):

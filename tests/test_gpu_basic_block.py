@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import layer_refs as LR
 from cases import TIGHT, BasicBlock, ResLayer
 from gpu_support import dirty_ticket_scenario, graph_replay_scenario, torch_dev  # noqa: F401
 
@@ -264,10 +265,7 @@ def test_batch_split_across_two_launches(pkg, O, torch_dev):
     g_idx = got[idx].cpu().numpy()
     del x, res, got
     torch.cuda.empty_cache()
-    F = torch.nn.functional
-    y = F.conv2d(xs[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double(), w.cpu().double(), padding=1)
-    y = y * s.cpu().double()[None, :, None, None] + b.cpu().double()[None, :, None, None]
-    want = torch.relu(y + rs[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double()).permute(0, 2, 3, 1).numpy()
+    want = LR.conv3x3(LR.interior(xs), w, (b, s), True, residual=LR.interior(rs)).numpy()
     assert O.rel_error(g_idx[:, 1:-1, 1:-1, :], want) < TIGHT
     assert (g_idx[:, 0, :, :] == 0).all() and (g_idx[:, -1, :, :] == 0).all()
     assert pkg.tickets_in_use() == 0

@@ -7,6 +7,7 @@ contract; Python argument errors."""
 import numpy as np
 import pytest
 
+import layer_refs as LR
 from cases import S2_FORM_SHAPES, S2_FORMS, TIGHT, S2Block, ring_mask, s2_legal
 from gpu_support import dirty_ticket_scenario, graph_replay_scenario, torch_dev  # noqa: F401
 
@@ -139,11 +140,7 @@ def test_resnet18_stage_opening(N, pkg, O, torch_dev):
     out = pkg.basic_block(y, pkg.filter_transform_f2(t(w3)), (t(b3), t(s3)), pkg.filter_transform_f2(t(w4)),
                           (t(b4), t(s4)), out=y)
     assert out.data_ptr() == y.data_ptr()
-    F = torch.nn.functional
-    bn = lambda v, s, b: v * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-    y0 = torch.from_numpy(blk.reference()[2]).permute(0, 3, 1, 2)
-    u = torch.relu(bn(F.conv2d(y0, w3.double(), padding=1), s3, b3))
-    want = torch.relu(bn(F.conv2d(u, w4.double(), padding=1), s4, b4) + y0).permute(0, 2, 3, 1).numpy()
+    want = LR.basic_block(blk.reference()[2], w3, (b3, s3), w4, (b4, s4)).numpy()
     g_ = out.cpu().numpy()
     assert (g_[:, ring_mask(blk.H, blk.W), :] == 0).all()
     assert O.rel_error(g_[:, 1:-1, 1:-1, :], want) < TIGHT

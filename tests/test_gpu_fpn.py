@@ -12,6 +12,7 @@ from fpn_reference import (LAYER_TOL, Up2Layer, fpn_random_state_dict, fpn_refer
                            padded_nan, up_hw)
 from gpu_support import (R, dirty_ticket_scenario, graph_replay_scenario, network_graph_scenario, rel,  # noqa: F401
                          torch_dev)
+from layer_refs import ring_is
 from reference_nets import NET_TOL
 
 pytestmark = pytest.mark.gpu
@@ -178,11 +179,9 @@ class Level:
 
     def check(self, inner, P):
         torch = self.torch
-        ring = torch.ones(inner.shape[1], inner.shape[2], dtype=torch.bool)
-        ring[1:-1, 1:-1] = False
         for name, got, want in (("inner", inner, self.want[0]), ("P", P, self.want[1])):
             got = got.cpu()
-            assert bool((got[:, ring, :] == 0).all()), f"{name}: ring is not exactly 0"
+            assert ring_is(got, 0.0), f"{name}: ring is not exactly 0"
             err = rel(torch, got[:, 1:-1, 1:-1, :], want)
             print(f"fpn_level {name}: rel err {err:.3e}")
             assert err < TIGHT, (name, err)

@@ -1,13 +1,14 @@
 """GPU tests of the grouped 3x3 layer (wino_conv3x3_grouped_bn_relu_hw), the two ResNeXt blocks built on it and the
 ResNeXt / Wide-ResNet networks.
 
-The oracle is F.conv2d(..., groups=G) in fp64 on the CPU with BN and the ReLU applied in fp64; an fp32 CPU grouped
+The oracle is layer_refs.conv3x3(..., groups=G), fp64 on the CPU with BN and the ReLU applied in fp64; an fp32 CPU grouped
 conv sits at 2-4e-7 from it at these shapes, and the bar is the project's layer bar, max |diff| / max |want| < 2e-5.
 Every layer and block tensor lives on a guarded arena (tests/guarded.py) at both placements of guarded.ALIGNS, and
 arena.check runs after every case: no guard word written, every input equal to its master bit for bit."""
 import pytest
 
 import guarded
+import layer_refs as LR
 from gpu_support import R, network_graph_scenario, rel, torch_dev  # noqa: F401
 from reference_nets import NET_TOL, check_net, random_state_dict, reference_forward
 
@@ -28,14 +29,6 @@ def _layer_inputs(torch, N, Hin, Win, C, Cg, seed):
     sign = (torch.rand(C, generator=g) < 0.5).float() * 2 - 1          # BN scales of both signs
     scale = (torch.rand(C, generator=g) + 0.5) * sign
     return x, w, bias, scale
-
-
-def _layer_reference(torch, x, w, bias, scale, groups, stride, relu):
-    """fp64 on the CPU, NHWC interior [N][H][W][C]."""
-    F = torch.nn.functional
-    y = F.conv2d(x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double(), w.double(), stride=stride, padding=1, groups=groups)
-    y = y * scale.double()[None, :, None, None] + bias.double()[None, :, None, None]
-    return (torch.relu(y) if relu else y).permute(0, 2, 3, 1)
 
 
 def _run_layer(pkg, torch_dev, x, w, bias, scale, groups, stride, relu, align, tag):
@@ -64,7 +57,7 @@ def _layer_case(pkg, torch_dev, N, Hin, Win, C, Cg, stride, relu, align):
     tag = f"grouped N={N} {Hin}x{Win} C={C} Cg={Cg} s={stride} relu={relu} align={align}"
     x, w, bias, scale = _layer_inputs(torch, N, Hin, Win, C, Cg, seed=1000 * Hin + 10 * Win + Cg + stride)
     got = _run_layer(pkg, torch_dev, x, w, bias, scale, C // Cg, stride, relu, align, tag)
-    want = _layer_reference(torch, x, w, bias, scale, C // Cg, stride, relu)
+    want = LR.conv3x3(LR.interior(x), w, (bias, scale), relu, stride=stride, groups=C // Cg)
     err = rel(torch, got, want)
     assert err < TIGHT, (tag, err)
     return want
@@ -140,7 +133,7 @@ def _one_hot(pkg, torch_dev, Cg, tw, maps):
             w[grp * Cg:(grp + 1) * Cg, cl, tap // 3, tap % 3] = torch.arange(1, Cg + 1, dtype=torch.float32) / Cg
             tag = f"one-hot Cg={Cg} TW={tw} group={grp} channel={cl} tap={tap} s={stride}"
             got = _run_layer(pkg, torch_dev, x, w, bias, scale, groups, stride, relu, guarded.ALIGNS[i % 2], tag)
-            want = _layer_reference(torch, x, w, bias, scale, groups, stride, relu)
+            want = LR.conv3x3(LR.interior(x), w, (bias, scale), relu, stride=stride, groups=groups)
             inside = torch.zeros(C, dtype=torch.bool)
             inside[grp * Cg:(grp + 1) * Cg] = True
             act = torch.relu(bias) if relu else bias
@@ -182,12 +175,11 @@ CIN, CM, C4, GROUPS = 64, 128, 256, 32
 
 class _Blocks:
     """The tensors of one identity and one projection block (folded BN vectors, NHWC activations) and their fp64
-    compositions."""
+    references."""
 
     def __init__(self, torch, N, Hin, Win, seed):
         g = torch.Generator().manual_seed(seed)
         r = lambda *s: torch.rand(*s, generator=g) - 0.5
-        self.torch = torch
         self.N, self.Hin, self.Win = N, Hin, Win
         self.x_res = r(N, Hin, Win, C4)
         self.x_proj = r(N, Hin, Win, CIN)
@@ -198,27 +190,14 @@ class _Blocks:
         self.wp = r(CIN, C4) / CIN ** 0.5 * 2
         self.bn = [(r(c), r(c) + 1.0) for c in (CM, CM, C4, C4)]     # (bias, scale): bn1, bn2, bn3, bnp
 
-    def _bn(self, y, i):
-        b, s = self.bn[i]
-        return y * s.double()[None, :, None, None] + b.double()[None, :, None, None]
-
-    def _middle(self, x, w1, stride):
-        torch = self.torch
-        F = torch.nn.functional
-        one = lambda w: w.double().t()[:, :, None, None]              # [Cin][Cout] -> [Cout][Cin][1][1]
-        t1 = torch.relu(self._bn(F.conv2d(x, one(w1)), 0))
-        t2 = torch.relu(self._bn(F.conv2d(t1, self.wg.double(), stride=stride, padding=1, groups=GROUPS), 1))
-        return self._bn(F.conv2d(t2, one(self.w3)), 2)
-
     def reference_residual(self):
-        x = self.x_res.permute(0, 3, 1, 2).double()
-        return self.torch.relu(self._middle(x, self.w1_res, 1) + x).permute(0, 2, 3, 1)
+        bn = self.bn
+        return LR.bottleneck(self.x_res, self.w1_res, bn[0], self.wg, bn[1], self.w3, bn[2], groups=GROUPS)
 
     def reference_proj(self, stride):
-        F = self.torch.nn.functional
-        x = self.x_proj.permute(0, 3, 1, 2).double()
-        sc = self._bn(F.conv2d(x, self.wp.double().t()[:, :, None, None], stride=stride), 3)
-        return self.torch.relu(self._middle(x, self.w1_proj, stride) + sc).permute(0, 2, 3, 1)
+        bn = self.bn
+        return LR.bottleneck(self.x_proj, self.w1_proj, bn[0], self.wg, bn[1], self.w3, bn[2], self.wp, bn[3],
+                             stride=stride, stride_on="3x3", groups=GROUPS)
 
 
 def _run_blocks(pkg, torch_dev, blk, stride, align, tag):

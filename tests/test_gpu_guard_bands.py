@@ -13,42 +13,27 @@ in place on the device, have no CPU masters and exist for 64-bit offsets, which 
 follow.  Whole-network runs are left out because resnet.py allocates its own activations.  The library-owned stream-K
 scratch (slabs, tickets, error word) cannot be guarded from outside.  What a guard proves: no store outside the tensor,
 and no load outside it whose value reaches the result; a load that is out of range and discarded is not seen."""
-import contextlib
 import ctypes
 
 import numpy as np
 import pytest
 
 import guarded as G
+import layer_refs as LR
 import shape_sweeps as S
 import sweep_cases as SC
 from cases import TIGHT
+from forms_1x1 import knobs_set as _knobs
 from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@contextlib.contextmanager
-def _knobs(knobs, kv):
-    for k, v in kv.items():
-        knobs.set(k, v)
-    try:
-        yield
-    finally:
-        for k in kv:
-            knobs.unset(k)
-
-
-def _rel(got, want):
-    g, w = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    return float(np.abs(g - w).max() / max(np.abs(w).max(), 1e-30))
 
 
 def _close(got, want, tag):
     got = got.detach().cpu().numpy() if hasattr(got, "detach") else got
     assert got.shape == want.shape, f"{tag}: shape {got.shape} != {want.shape}"
     assert np.isfinite(got).all(), f"{tag}: non-finite values (not all written, or a guard was read)"
-    err = _rel(got, want)
+    err = LR.rel(got, want, floor=1e-30)
     print(f"{tag}: rel err {err:.3e}")
     assert err < TIGHT, f"{tag}: rel err {err:.3e}"
 
@@ -252,9 +237,7 @@ def test_conv1x1_operand_forms(shape, form, pkg, knobs, torch_dev):
                 tag = f"[conv1x1_bn_ex {shape} form={form} plan={planned} flags={flags} align={align}]"
                 got = out.cpu().numpy()
                 if flags & pkg.C_PADDED:
-                    ring = np.ones((H + 2, W + 2), bool)
-                    ring[1:-1, 1:-1] = False
-                    assert (got[:, ring, :] == 0).all(), f"{tag}: ring is not exactly 0"
+                    assert LR.ring_is(got, 0.0), f"{tag}: ring is not exactly 0"
                     got = got[:, 1:-1, 1:-1, :].reshape(M, Kout)
                 _close(got, want, tag)
                 assert pkg.tickets_in_use() == 0, tag
@@ -282,7 +265,6 @@ def test_residual_block_between_guards(N, H, W, forced, pkg, knobs, torch_dev):
     the planner takes (the latency kernels: asserted), ragged batches with the throughput kernels forced.  A third pass
     puts the workspace at 16 mod 256 too, the checked minimum: the block carves t1 and t2 from it."""
     torch, dev = torch_dev
-    F = torch.nn.functional
     C4, Cm = 256, 64
     g = torch.Generator().manual_seed(N * 100 + H)
     r = lambda *sh: torch.rand(*sh, generator=g)
@@ -290,13 +272,9 @@ def test_residual_block_between_guards(N, H, W, forced, pkg, knobs, torch_dev):
     w1, w3 = (r(C4, Cm) - 0.5) / np.sqrt(C4) * 4, (r(Cm, C4) - 0.5) / np.sqrt(Cm) * 4
     w2 = (r(Cm, Cm, 3, 3) - 0.5) / np.sqrt(9 * Cm) * 4
     bn = [(r(c) - 0.5, r(c) + 0.5) for c in (Cm, Cm, C4)]
-    aff = lambda y, p: y * p[1].double()[None, :, None, None] + p[0].double()[None, :, None, None]
-    xi = x.permute(0, 3, 1, 2).double()
-    t1 = torch.relu(aff(F.conv2d(xi, w1.double().t()[:, :, None, None]), bn[0]))
-    t2 = torch.relu(aff(F.conv2d(t1, w2.double(), padding=1), bn[1]))
-    pre = aff(F.conv2d(t2, w3.double().t()[:, :, None, None]), bn[2]) + xi
+    pre = LR.bottleneck(x, w1, bn[0], w2, bn[1], w3, bn[2], pre=True)
     assert bool((pre > 0).any()) and bool((pre < 0).any())
-    want = torch.relu(pre).permute(0, 2, 3, 1).numpy()
+    want = torch.relu(pre).numpy()
     L = pkg.lib()
     need = L.wino_residual_block_workspace_bytes_hw(N, H, W, Cm)
     if (H, W) == (14, 14):
@@ -337,8 +315,6 @@ def test_f4_compat_path_between_guards(N, pkg, O, torch_dev):
     s, b = (rng.rand(K) - 0.5).astype(np.float32), (rng.rand(K) - 0.5).astype(np.float32)
     u36 = np.einsum('xr,kcrs,ys->xyck', O.G_F4, w.astype(np.float64), O.G_F4).reshape(36, C, K).astype(np.float32)
     need = pkg.lib().wino_conv3x3_f4_workspace_bytes(N, C, K)
-    ring = np.ones((16, 16), bool)
-    ring[1:15, 1:15] = False
     for relu in (True, False):
         want = O.conv3x3_bn_relu_direct(x, w, s, b, relu=relu)
         for align in G.ALIGNS:
@@ -350,7 +326,7 @@ def test_f4_compat_path_between_guards(N, pkg, O, torch_dev):
                                          out=arena.output(N, 16, 16, K, name="out"), workspace=ws)
             tag = f"[conv3x3_f4_bn_relu N={N} C={C} K={K} relu={relu} align={align}]"
             got = out.cpu().numpy()
-            assert (got[:, ring, :] == 0).all(), f"{tag}: ring is not exactly 0"
+            assert LR.ring_is(got, 0.0), f"{tag}: ring is not exactly 0"
             _close(got, want, tag)
             arena.check(tag)
 

@@ -19,8 +19,9 @@ import types
 import numpy as np
 import pytest
 
+import layer_refs as LR
 from aspp_cases import cat_reference
-from cases import TIGHT, BasicBlock, ResLayer, S2Block, S2Layer, V15Block, proj_oracle, proj_weights, ring_zero
+from cases import TIGHT, S2Block, V15Block, proj_weights, ring_zero
 from dilated_cases import dilated_reference
 from fpn_reference import level_reference
 from gpu_support import torch_dev  # noqa: F401
@@ -78,17 +79,9 @@ def _rand(torch, dev, shape, seed, out=None):
     return torch.rand(*shape, device=dev, generator=g).sub_(0.5)
 
 
-def _zero_ring(x):
-    x[:, 0].zero_()
-    x[:, -1].zero_()
-    x[:, :, 0].zero_()
-    x[:, :, -1].zero_()
-    return x
-
-
 def _padded_rand(torch, dev, N, H, W, C, seed, out=None):
     """[N][H+2][W+2][C], interior uniform in [-0.5, 0.5), zero ring; built in place (no interior-sized temporary)."""
-    return _zero_ring(_rand(torch, dev, (N, H + 2, W + 2, C), seed, out=out))
+    return LR.fill_ring(_rand(torch, dev, (N, H + 2, W + 2, C), seed, out=out))
 
 
 def _finite(torch, t):
@@ -135,9 +128,8 @@ def test_residual_3x3_beyond_4gib(form, in_place, pkg, O, torch_dev, knobs, free
     U, bt, st = pkg.filter_transform_f2(w.to(dev)), bias.to(dev), scale.to(dev)
     x = _padded_rand(torch, dev, N, H, H, C, 72)
     res = _padded_rand(torch, dev, N, H, H, C, 73)
-    ref = types.SimpleNamespace(torch=torch, x=_pick(torch, x, idx), res=_pick(torch, res, idx), w=w, bias=bias,
-                                scale=scale)
-    want = ResLayer.reference(ref, relu=True)
+    want = LR.conv3x3(LR.interior(_pick(torch, x, idx)), w, (bias, scale), True,
+                      residual=LR.interior(_pick(torch, res, idx))).numpy()
     out = res if in_place else torch.empty_like(x)
     first = None
     for rep in range(2):
@@ -172,7 +164,7 @@ def test_basic_block_beyond_4gib(pkg, O, torch_dev, free_after):
     bnt = [(b.to(dev), s.to(dev)) for b, s in bn]
     x = _padded_rand(torch, dev, N, H, H, C, 82)
     x_idx = _pick(torch, x, idx)
-    want = BasicBlock.reference(types.SimpleNamespace(torch=torch, w=ws_, bn=bn), x_idx)
+    want = LR.basic_block(LR.interior(x_idx), ws_[0], bn[0], ws_[1], bn[1]).numpy()
     need = pkg.lib().wino_basic_block_workspace_bytes_hw(N, H, H, C)
     assert need == N * P
     out = torch.empty_like(x)
@@ -266,8 +258,7 @@ def test_conv3x3_s2_beyond_4gib(form, pkg, O, torch_dev, knobs, free_after):
     bias, scale = torch.rand(K, generator=g) - 0.5, torch.rand(K, generator=g) + 0.5
     taps, bt, st = pkg.filter_pack_s2(w.to(dev)), bias.to(dev), scale.to(dev)
     x = _padded_rand(torch, dev, N, Hin, Hin, C, 102)
-    ref = types.SimpleNamespace(torch=torch, x=_pick(torch, x, idx), w=w, bias=bias, scale=scale)
-    want = S2Layer.reference(ref)
+    want = LR.conv3x3(LR.interior(_pick(torch, x, idx)), w, (bias, scale), True, stride=2).numpy()
     out = torch.empty(N, H + 2, H + 2, K, device=dev)
     first = None
     for rep in range(2):
@@ -373,7 +364,7 @@ def test_proj_block_beyond_4gib(stride, form, pkg, O, torch_dev, knobs, free_aft
     U2 = pkg.filter_transform_f2(t(w2))
     tail = pkg.proj_tail_pack(t(w3), bnt[2], t(wp), bnt[3])
     x = _rand(torch, dev, (N, Hin, Hin, Cin), 122)
-    want = proj_oracle(O, _pick(torch, x, idx).numpy(), stride, w1, w2, w3, wp, bn)
+    want = LR.bottleneck(_pick(torch, x, idx), w1, bn[0], w2, bn[1], w3, bn[2], wp, bn[3], stride=stride).numpy()
     out = torch.empty(N, H, H, C4, device=dev)
     ws = torch.empty(need // 4, device=dev)
     first = None
@@ -635,13 +626,6 @@ def _grouped_weights(torch, dev, pkg, C, groups, seed):
     return w, bias, scale, pkg.filter_pack_grouped(w.to(dev), groups), bias.to(dev), scale.to(dev)
 
 
-def _grouped_reference(torch, x_padded, w, bias, scale, groups, stride):
-    """fp64 on the CPU of padded NHWC rows (their zero ring is the padding): [n][H][W][C], after the ReLU."""
-    y = torch.nn.functional.conv2d(x_padded.permute(0, 3, 1, 2).double(), w.double(), stride=stride, groups=groups)
-    y = y * scale.double()[None, :, None, None] + bias.double()[None, :, None, None]
-    return torch.relu(y).permute(0, 2, 3, 1).numpy()
-
-
 # (stride, Hin, Win, C, groups, N, tile width): 8-wide tiles at stride 1, 16-wide at stride 2
 GROUPED_BATCHES = [(1, 6, 7, 128, 4, 116600, 8), (2, 3, 19, 64, 16, 349600, 16)]
 
@@ -661,7 +645,7 @@ def test_grouped_3x3_batch_beyond_4gib(stride, Hin, Win, C, groups, N, tw, pkg, 
     assert len(idx) >= 8
     w, bias, scale, packed, bt, st = _grouped_weights(torch, dev, pkg, C, groups, 191 + stride)
     x = _padded_rand(torch, dev, N, Hin, Win, C, 192 + stride)
-    want = _grouped_reference(torch, _pick(torch, x, idx), w, bias, scale, groups, stride)
+    want = LR.conv3x3(_pick(torch, x, idx), w, (bias, scale), True, stride=stride, groups=groups, padding=0).numpy()
     out = torch.empty(N, H + 2, W + 2, C, device=dev)
     first = None
     for rep in range(2):
@@ -714,7 +698,9 @@ def test_grouped_3x3_largest_accepted_image(pkg, O, torch_dev, free_after):
     assert 3 <= len(bands) <= 5 and sum(hi - lo + 1 for lo, hi in bands) <= 25
     w, bias, scale, packed, bt, st = _grouped_weights(torch, dev, pkg, C, groups, 201)
     x = _padded_rand(torch, dev, N, Hin, Hin, C, 202)
-    want = [_grouped_reference(torch, x[:, 2 * lo:2 * hi + 3].cpu(), w, bias, scale, groups, stride) for lo, hi in bands]
+    # (padding=0: the zero ring is the padding left and right, and a band brings the rows above and below it along)
+    want = [LR.conv3x3(x[:, 2 * lo:2 * hi + 3].cpu(), w, (bias, scale), True, stride=stride, groups=groups, padding=0).numpy()
+            for lo, hi in bands]
     out = torch.empty(N, H + 2, H + 2, C, device=dev)
     first = None
     for rep in range(2):

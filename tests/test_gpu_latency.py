@@ -8,6 +8,7 @@ import pytest
 import guarded as G
 from cases import TIGHT, ring_mask
 from gpu_support import dirty_ticket_scenario, torch_dev  # noqa: F401
+from layer_refs import ring_is
 
 pytestmark = pytest.mark.gpu
 
@@ -85,8 +86,6 @@ def test_conv3x3_latency_other_feature_maps(N, H, W, C, K, pkg, O, torch_dev, kn
     U = pkg.filter_transform_f2(wt)
     want = O.conv3x3_bn_relu_direct(x, w, s, b)
     scale = float(np.abs(want).max())
-    ring = np.ones((H + 2, W + 2), bool)
-    ring[1:H + 1, 1:W + 1] = False
     tiles = ((H + 1) // 2) * ((W + 1) // 2)
     knobs.set("WINO_3X3_ALGO", "small")
     ref = None
@@ -106,7 +105,7 @@ def test_conv3x3_latency_other_feature_maps(N, H, W, C, K, pkg, O, torch_dev, kn
             got = out.cpu().numpy()
             assert not np.isnan(got).any(), (ct, sp)
             assert O.rel_error(got, want) < TIGHT, (ct, sp, O.rel_error(got, want))
-            assert (got[:, ring, :] == 0).all(), (ct, sp)
+            assert ring_is(got, 0.0), (ct, sp)
             assert torch.equal(pkg.conv3x3_bn_relu(xt, U, bt, st), out), (ct, sp)
             if ref is None:
                 ref = out
@@ -226,13 +225,11 @@ def test_one_by_one_latency_chained_forms(N, H, W, Cin, Kout, pkg, torch_dev, kn
     lin = (A.reshape(-1, Cin).double() @ Bm.double()) * s.double() + b.double()
     want, want_res = torch.relu(lin), torch.relu(lin + R.double())
     scale = float(want_res.abs().max())
-    ring = torch.ones(H + 2, W + 2, dtype=torch.bool, device=dev)
-    ring[1:-1, 1:-1] = False
 
     def run(tag):
         out = torch.full((N, H + 2, W + 2, Kout), float("nan"), device=dev)
         pkg.conv1x1_bn_ex(A, Bm, b, s, pkg.RELU | pkg.C_PADDED, out=out, hw=(H, W))
-        assert bool((out[:, ring, :] == 0).all()), tag
+        assert ring_is(out, 0.0), tag
         assert float((out[:, 1:-1, 1:-1, :].reshape(-1, Kout).double() - want).abs().max()) < TIGHT * scale, tag
         got2 = pkg.conv1x1_bn_ex(Ap, Bm, b, s, pkg.RELU | pkg.A_PADDED, hw=(H, W))
         assert float((got2.reshape(-1, Kout).double() - want).abs().max()) < TIGHT * scale, tag
@@ -282,15 +279,13 @@ def test_latency_kernels_random_shapes(pkg, torch_dev, knobs):
         assert pkg.small_plan_3x3_full(N, C, K, H=H, W=W)[:4] == (1, 2, sp, ct), (N, H, W, C, K, ct, sp)
         want = pkg.conv3x3_direct(x, w, b, s, relu=bool(i & 1))
         inner = (slice(None), slice(1, H + 1), slice(1, W + 1), slice(None))
-        ring = torch.ones(H + 2, W + 2, dtype=torch.bool, device=dev)
-        ring[1:-1, 1:-1] = False
         for align in G.ALIGNS:
             arena = G.Arena(torch, dev, align=align)
             out = arena.output(N, H + 2, W + 2, K)
             pkg.conv3x3_bn_relu(*(arena.input(v) for v in (x, U, b, s)), relu=bool(i & 1), out=out)
             assert not bool(torch.isnan(out).any()), (N, H, W, C, K, ct, sp, align)
             assert float((out[inner] - want[inner]).abs().max()) < TIGHT * float(want[inner].abs().max() + 1e-6), (N, H, W, C, K, ct, sp, align)
-            assert bool((out[:, ring, :] == 0).all()), (N, H, W, C, K, ct, sp, align)
+            assert ring_is(out, 0.0), (N, H, W, C, K, ct, sp, align)
             assert pkg.tickets_in_use() == 0
             arena.check(f"conv3x3_bn_relu latency N={N} H={H} W={W} C={C} K={K} ct={ct} split={sp} align={align}")
     for k in ("WINO_3X3_ALGO", "WINO_SMALL_CT", "WINO_SMALL_SPLIT"):
@@ -324,9 +319,7 @@ def test_latency_kernels_random_shapes(pkg, torch_dev, knobs):
                               out=out, hw=(H, W))
             tag = (M, Cin, Kout, ks, rt, ct, flags, align)
             if flags & pkg.C_PADDED:
-                ring = torch.ones(H + 2, W + 2, dtype=torch.bool, device=dev)
-                ring[1:-1, 1:-1] = False
-                assert bool((out[:, ring, :] == 0).all()), tag
+                assert ring_is(out, 0.0), tag
                 got = out[:, 1:-1, 1:-1, :].reshape(M, Kout)
             else:
                 got = out

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import guarded as G
+import layer_refs as LR
 import shape_sweeps as S
 from cases import ring_zero
 from gpu_support import torch_dev  # noqa: F401
@@ -108,20 +109,6 @@ def _operands(torch, sh, seed, nonneg=False):
     return x, w, bias, scale
 
 
-def _reference(torch, x, w, bias, scale, relu):
-    """fp64: max_pool2d(act(scale * conv3x3(x) + bias), 2, 2), NHWC."""
-    import torch.nn.functional as F
-    y = F.conv2d(x[:, 1:-1, 1:-1, :].permute(0, 3, 1, 2).double(), w.double(), padding=1)
-    y = y * scale.double().view(1, -1, 1, 1) + bias.double().view(1, -1, 1, 1)
-    if relu:
-        y = torch.relu(y)
-    return F.max_pool2d(y, 2, 2).permute(0, 2, 3, 1)
-
-
-def _rel(got, want):
-    return float((got.double() - want).abs().max() / want.abs().max().clamp_min(1e-30))
-
-
 def run_case(pkg, knobs, torch_dev, form, sh, kn, flags, seed, exact):
     torch, dev = torch_dev
     import torch.nn.functional as F
@@ -131,7 +118,7 @@ def run_case(pkg, knobs, torch_dev, form, sh, kn, flags, seed, exact):
     N, H, W, C, K = (sh[k] for k in "NHWCK")
     x, w, bias, scale = _operands(torch, sh, seed, flags.get("nonneg", False))
     relu = flags["relu"]
-    want = _reference(torch, x, w, bias, scale, relu)
+    want = LR.conv3x3(LR.interior(x), w, (bias, scale), relu, pool=True)
     U = pkg.filter_transform_f2(w.to(dev))
     worst = 0.0
     for align in G.ALIGNS:
@@ -149,7 +136,7 @@ def run_case(pkg, knobs, torch_dev, form, sh, kn, flags, seed, exact):
         o = out.cpu()
         assert not torch.isnan(o).any(), tag
         assert ring_zero(o), tag
-        err = _rel(o[:, 1:-1, 1:-1, :], want)
+        err = LR.rel(o[:, 1:-1, 1:-1, :], want, floor=1e-30)
         print(f"{tag} rel {err:.2e}")
         worst = max(worst, err)
         assert err < TIGHT, (tag, err)
@@ -181,14 +168,14 @@ def test_pooled_layer_automatic_plan(pkg, knobs, torch_dev):
                      ({"N": 96, "H": 14, "W": 14, "C": 64, "K": 64}, "throughput")):
         assert S.plan_3x3(pkg, *(sh[k] for k in "NHWCK"))[0] == kind, sh
         x, w, bias, scale = _operands(torch, sh, 9)
-        want = _reference(torch, x, w, bias, scale, True)
+        want = LR.conv3x3(LR.interior(x), w, (bias, scale), True, pool=True)
         arena = G.Arena(torch, dev, 16)
         out = arena.output(sh["N"], sh["H"] // 2 + 2, sh["W"] // 2 + 2, sh["K"])
         pkg.conv3x3_bn_relu_pool(arena.input(x), arena.input(pkg.filter_transform_f2(w.to(dev))), arena.input(bias),
                                  arena.input(scale), True, out=out)
         arena.check(str(sh))
         assert pkg.tickets_in_use() == 0
-        assert ring_zero(out) and _rel(out.cpu()[:, 1:-1, 1:-1, :], want) < TIGHT
+        assert ring_zero(out) and LR.rel(LR.interior(out), want, floor=1e-30) < TIGHT
 
 
 @pytest.mark.parametrize("form", FORMS)
@@ -222,17 +209,15 @@ def test_pooled_layer_beyond_4gib(pkg, torch_dev):
     w = torch.randn(C, C, 3, 3, generator=g) * (2.0 / (9 * C)) ** 0.5
     bias, scale = torch.rand(C, generator=g) - 0.5, torch.rand(C, generator=g) + 0.5
     gd = torch.Generator(device=dev).manual_seed(72)
-    x = torch.rand(N, H + 2, H + 2, C, device=dev, generator=gd).sub_(0.5)
-    for r in (x[:, 0], x[:, -1], x[:, :, 0], x[:, :, -1]):
-        r.zero_()
+    x = LR.fill_ring(torch.rand(N, H + 2, H + 2, C, device=dev, generator=gd).sub_(0.5))
     out = torch.full((N, H // 2 + 2, H // 2 + 2, C), float("nan"), device=dev)
     pkg.conv3x3_bn_relu_pool(x, pkg.filter_transform_f2(w.to(dev)), bias.to(dev), scale.to(dev), True, out=out)
     torch.cuda.synchronize()
     assert pkg.tickets_in_use() == 0
     assert bool(torch.isfinite(out).all()) and ring_zero(out)
     sel = torch.as_tensor(idx, device=dev)
-    want = _reference(torch, x[sel].cpu(), w, bias, scale, True)
-    assert _rel(out[sel].cpu()[:, 1:-1, 1:-1, :], want) < TIGHT
+    want = LR.conv3x3(LR.interior(x[sel]), w, (bias, scale), True, pool=True)
+    assert LR.rel(LR.interior(out[sel]), want, floor=1e-30) < TIGHT
     del x, out
     torch.cuda.empty_cache()
 
@@ -256,14 +241,13 @@ def test_image_pack_is_a_copy(N, Cin, H, W, Cpad, pkg, torch_dev):
                                              (3, 13, 7, 4, True), (1, 3, 4, 128, False), (2, 31, 17, 8, True)])
 def test_avgpool7_flatten(N, H, W, C, padded, pkg, torch_dev):
     torch, dev = torch_dev
-    import torch.nn.functional as F
     p = 1 if padded else 0
     x = torch.randn(N, H, W, C, generator=torch.Generator().manual_seed(H * W + C))
     feat = torch.full((N, H + 2 * p, W + 2 * p, C), 1e30)     # a ring that is read shows
     feat[:, p:p + H, p:p + W, :] = x
-    want = F.adaptive_avg_pool2d(x.permute(0, 3, 1, 2).double(), (7, 7)).permute(0, 2, 3, 1).reshape(N, 49 * C)
+    want = LR.avgpool7(x).reshape(N, 49 * C)
     for align in G.ALIGNS:
         arena = G.Arena(torch, dev, align)
         out = pkg.avgpool7_flatten(arena.input(feat, name="feat"), in_padded=padded, out=arena.output(N, 49 * C, name="out"))
         arena.check(f"[avgpool7 {N} {H} {W} {C} align={align}]")
-        assert _rel(out.cpu(), want) < TIGHT
+        assert LR.rel(out, want, floor=1e-30) < TIGHT

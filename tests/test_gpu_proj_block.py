@@ -5,7 +5,8 @@ the layer oracles, the comparator kernels, and the four-launch composition the l
 import numpy as np
 import pytest
 
-from cases import PROJ_FORMS, TIGHT, proj_oracle, proj_weights
+import layer_refs as LR
+from cases import PROJ_FORMS, TIGHT, proj_weights
 from gpu_support import graph_replay_scenario, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -59,15 +60,15 @@ class _Block:
                                 pkg.RELU | pkg.A_PADDED | pkg.ADD_RESIDUAL, residual=short)
         return out.reshape(self.N, self.H, self.W, self.C4)
 
-    def oracle(self, O, idx=None):
-        x = self.x if idx is None else self.x[idx]
-        return proj_oracle(O, x, self.s, self.w1, self.w2, self.w3, self.wp, self.bn)
+    def oracle(self, idx=None):
+        x, bn = self.x if idx is None else self.x[idx], self.bn
+        return LR.bottleneck(x, self.w1, bn[0], self.w2, bn[1], self.w3, bn[2], self.wp, bn[3], stride=self.s).numpy()
 
 
 def _check_block(blk, O, got, idx=None):
     got = got.cpu().numpy()
     assert np.isfinite(got).all()
-    want = blk.oracle(O, idx)
+    want = blk.oracle(idx)
     g = got if idx is None else got[idx]
     assert g.shape == want.shape
     assert O.rel_error(g, want) < TIGHT

@@ -8,16 +8,11 @@ import pytest
 import guarded
 from cases import TIGHT
 from gpu_support import graph_replay_scenario, torch_dev  # noqa: F401
+from layer_refs import rel as rel_err
 from resize_cases import (DIRECT, DIRECT_SMALL, EXACT_WIDTHS, STAGED, STAGED_SHAPES, ResizeCase, axis_coords,
                           check_labels, labels_of, resize_reference, smallest_direct_channels)
 
 pytestmark = pytest.mark.gpu
-
-
-def rel_err(got, want):
-    assert got.shape == want.shape, (got.shape, want.shape)
-    assert np.isfinite(got).all(), "got holds non-finite values"
-    return float(np.abs(got - want).max() / np.abs(want).max())
 
 
 def bits(a):

@@ -15,6 +15,7 @@ import guarded
 import roi_cases as rc
 from cases import TIGHT
 from gpu_support import torch_dev  # noqa: F401
+from layer_refs import ring_is
 
 pytestmark = pytest.mark.gpu
 CANON = dict(canonical_scale=rc.CANONICAL_SCALE, canonical_level=rc.CANONICAL_LEVEL)
@@ -60,9 +61,7 @@ def interior(got, out_padded):
     """The P x P interior of an output; a padded output's ring is exactly 0."""
     if not out_padded:
         return got
-    ring = torch.ones(got.shape[1], got.shape[2], dtype=torch.bool)
-    ring[1:-1, 1:-1] = False
-    assert bool((got[:, ring, :] == 0).all()), "the ring is not exactly 0"
+    assert ring_is(got, 0.0), "the ring is not exactly 0"
     return got[:, 1:-1, 1:-1, :]
 
 

@@ -2,9 +2,9 @@
 classifier head (wino_avgpool_fc_hw).  Outputs go into NaN-filled buffers and are compared with fp64 references built
 here (torch on the CPU): every shape class, both output layouts, negative BN scales, both forced forms, and a batch
 whose input and output cross 2^32 bytes."""
-import numpy as np
 import pytest
 
+import layer_refs as LR
 from gpu_support import torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -22,14 +22,6 @@ def _stem_params(torch, K, seed, neg=True):
     return w, bias, scale
 
 
-def _stem_ref(torch, x, w, bias, scale):
-    """fp64 CPU: maxpool3x3_s2_p1(relu(bn(conv7x7_s2_p3(x)))) -> NHWC"""
-    import torch.nn.functional as F
-    y = F.conv2d(x.double(), w, stride=2, padding=3)
-    y = torch.relu(y * scale[None, :, None, None] + bias[None, :, None, None])
-    return F.max_pool2d(y, 3, 2, 1).permute(0, 2, 3, 1).contiguous()
-
-
 def _run_stem(pkg, torch, dev, x, w, bias, scale, padded):
     packed = pkg.stem_filter_pack(w.float().to(dev), (bias.float().to(dev), scale.float().to(dev)))
     N, _, H, W = x.shape
@@ -44,13 +36,11 @@ def _run_stem(pkg, torch, dev, x, w, bias, scale, padded):
 def _check_stem(torch, got, want, padded):
     got = got.cpu().double()
     if padded:
-        ring = torch.ones(got.shape[1:3], dtype=torch.bool)
-        ring[1:-1, 1:-1] = False
-        assert (got[:, ring, :] == 0).all(), "padded ring is not exactly 0"
-        got = got[:, 1:-1, 1:-1, :]
+        assert LR.ring_is(got, 0.0), "padded ring is not exactly 0"
+        got = LR.interior(got)
     assert got.shape == want.shape, (got.shape, want.shape)
     assert not torch.isnan(got).any(), "output not fully written"
-    rel = float((got - want).abs().max() / max(float(want.abs().max()), 1e-30))
+    rel = LR.rel(got, want, floor=1e-30)
     assert rel < TIGHT, rel
 
 
@@ -66,7 +56,7 @@ def test_stem_matches_fp64(N, H, W, K, padded, pkg, torch_dev):
     x = torch.rand(N, 3, H, W, generator=g) * 2 - 1
     w, bias, scale = _stem_params(torch, K, seed=H * W + K)
     got = _run_stem(pkg, torch, dev, x.to(dev), w, bias, scale, padded)
-    _check_stem(torch, got, _stem_ref(torch, x, w, bias, scale), padded)
+    _check_stem(torch, got, LR.stem(x, w, (bias, scale)), padded)
 
 
 @pytest.mark.parametrize("form", [1, 2])
@@ -80,7 +70,7 @@ def test_stem_forced_forms(form, N, H, W, K, padded, pkg, torch_dev, knobs):
     x = torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(7 + form)) * 2 - 1
     w, bias, scale = _stem_params(torch, K, seed=11 * form + H)
     got = _run_stem(pkg, torch, dev, x.to(dev), w, bias, scale, padded)
-    _check_stem(torch, got, _stem_ref(torch, x, w, bias, scale), padded)
+    _check_stem(torch, got, LR.stem(x, w, (bias, scale)), padded)
 
 
 def test_stem_forms_agree_and_auto_picks_per_shape(pkg, torch_dev, knobs):
@@ -114,7 +104,7 @@ def test_stem_past_4gib(pkg, torch_dev):
     img_b = 56 * 56 * K * 4
     b = (1 << 32) // img_b
     for n in sorted({0, b - 1, b, b + 1, N - 1}):
-        _check_stem(torch, out[n:n + 1], _stem_ref(torch, x[n:n + 1].cpu(), w, bias, scale), False)
+        _check_stem(torch, out[n:n + 1], LR.stem(x[n:n + 1], w, (bias, scale)), False)
     del x, out
     torch.cuda.empty_cache()
 
@@ -129,7 +119,7 @@ def test_head_matches_fp64(N, H, W, C, classes, padded, pkg, torch_dev):
     feat = torch.rand(N, H, W, C, generator=g, dtype=torch.float64) * 2
     wfc = (torch.rand(classes, C, generator=g, dtype=torch.float64) - 0.5) * 0.1
     bfc = torch.rand(classes, generator=g, dtype=torch.float64) - 0.5
-    want = feat.mean(dim=(1, 2)) @ wfc.t() + bfc
+    want = LR.avgpool_fc(feat, wfc, bfc)
     if padded:
         f = torch.full((N, H + 2, W + 2, C), float("nan"), dtype=torch.float64)   # the ring is not read
         f[:, 1:-1, 1:-1, :] = feat
@@ -142,6 +132,6 @@ def test_head_matches_fp64(N, H, W, C, classes, padded, pkg, torch_dev):
     torch.cuda.synchronize()
     got = out.cpu().double()
     assert not torch.isnan(got).any()
-    rel = float((got - want).abs().max() / want.abs().max())
+    rel = LR.rel(got, want)
     assert rel < TIGHT, rel
     assert pkg.tickets_in_use() == 0
