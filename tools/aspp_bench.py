@@ -18,31 +18,21 @@ usage: python tools/aspp_bench.py cat [out.json] [--ns 1,8] [--trials 7] [--reps
          rows behind it (avgpool_fc: the module runs the same pool and two such 1x1 layers)
        python tools/aspp_bench.py all profiles/aspp/bench.json
          cat, module and net, into one file"""
-import argparse
-import importlib
-import json
-import os
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
-from dilated_bench import DILATE, FORM_NAMES, TorchFCN, fcn_state_dict  # noqa: E402
-from resnet_bench import _interleaved  # noqa: E402
+import benchlib
+import torch
+import torch.nn.functional as F
+import torch_nets
+from benchlib import FORM_NAMES
 
 H = 65                  # layer4's map at a 520x520 input
-CIN, CB = 2048, 256
-RATES = (12, 24, 36)
+CIN, CB, RATES = torch_nets.ASPP_CIN, torch_nets.ASPP_CB, torch_nets.ASPP_RATES   # 2048 -> 256, rates 12, 24, 36
 RELU, A_PADDED, C_PADDED = 1, 2, 4
 
 
 def cat(a, pkg, dev):
     rows = []
     S, K = 4, CB
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         g = torch.Generator().manual_seed(N)
         srcs = (torch.rand(S, N, H, H, CB, generator=g) - 0.5).to(dev)
         w = ((torch.rand(S * CB, K, generator=g) - 0.5) * (4.0 / (S * CB) ** 0.5)).to(dev)
@@ -57,7 +47,7 @@ def cat(a, pkg, dev):
             "cat_plain": lambda: plain(torch.cat(list(srcs), dim=-1)),
             "plain": lambda: plain(copy),
         }
-        med, times = _interleaved(variants, a.trials, a.reps)
+        med, times = benchlib.interleaved(variants, a.trials, a.reps)
         form = FORM_NAMES[pkg.conv1x1_cat_plan(N, H, H, S, CB, K)]
         rows.append({"N": N, "H": H, "sources": S, "Cs": CB, "Kout": K, "form": form, "median_us": med, "trials_us": times,
                      "cat_form_over_cat_plain": med["cat_form"] / med["cat_plain"],
@@ -73,7 +63,7 @@ def cat(a, pkg, dev):
 
 def module(a, pkg, dev):
     rows = []
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         g = torch.Generator().manual_seed(N + 7)
         r = lambda *s: torch.rand(*s, generator=g) - 0.5
         x = torch.zeros(N, H + 2, H + 2, CIN)
@@ -104,7 +94,7 @@ def module(a, pkg, dev):
         mine = lambda: pkg.aspp(x, w0, bn[0], taps, bn[1:4], RATES, w_pool, bn[4], w_proj, bn[5], out=out, workspace=wsp)
         ref = torch_aspp().permute(0, 2, 3, 1)
         diff = float((mine()[:, 1:-1, 1:-1, :] - ref).abs().max() / ref.abs().max())
-        med, times = _interleaved({"aspp": mine, "torch": torch_aspp}, a.trials, a.reps)
+        med, times = benchlib.interleaved({"aspp": mine, "torch": torch_aspp}, a.trials, a.reps)
         flop = 2.0 * N * H * H * CB * (CIN * 28 + 4 * CB)
         rows.append({"N": N, "H": H, "Cin": CIN, "Cb": CB, "rates": RATES, "median_us": med, "trials_us": times,
                      "rel_diff_to_torch_fp32": diff, "aspp_over_torch": med["aspp"] / med["torch"],
@@ -119,7 +109,7 @@ def module(a, pkg, dev):
 
 def parts(a, pkg, dev):
     rows = []
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         g = torch.Generator().manual_seed(N + 11)
         r = lambda *s: torch.rand(*s, generator=g) - 0.5
         x = torch.zeros(N, H + 2, H + 2, CIN)
@@ -141,7 +131,7 @@ def parts(a, pkg, dev):
             variants[f"dilated_{d}"] = lambda d=d: pkg.conv3x3_dilated_bn_relu(x, taps, b, s, d, out=o_p)
         variants["join"] = lambda: pkg.conv1x1_cat_bn(srcs, w_proj, bias, s, RELU | C_PADDED, out=o_p)
         variants["avgpool_fc"] = lambda: pkg.avgpool_fc(x, head, CB, in_padded=True, out=logits)
-        med, times = _interleaved(variants, a.trials, a.reps)
+        med, times = benchlib.interleaved(variants, a.trials, a.reps)
         rows.append({"N": N, "H": H, "Cin": CIN, "Cb": CB, "median_us": med, "trials_us": times, "sum_us": sum(med.values())})
         print(f"parts N={N:2d}  " + "  ".join(f"{k} {v:.1f}" for k, v in med.items()) + f"  sum {sum(med.values()):.1f} us",
               flush=True)
@@ -150,117 +140,42 @@ def parts(a, pkg, dev):
     return rows
 
 
-class TorchDeepLab(TorchFCN):
-    """torch eager on channels-last fp32 with the same weights: the body as TorchFCN, then ASPP, the 3x3 head, the
-    classes and the bilinear resize."""
-
-    def __call__(self, x):
-        q = "backbone."
-        t = F.max_pool2d(self._cb(x, q + "conv1.weight", q + "bn1", 2, 3), 3, 2, 1)
-        plan = importlib.import_module("cuda_winograd_amd.resnet").dilated_block_plan(DILATE, self.blocks)
-        for L, stage in enumerate(plan, 1):
-            for b, (kind, d) in enumerate(stage):
-                p = f"{q}layer{L}.{b}"
-                st = 2 if kind == "proj_v15" else 1
-                y = self._cb(t, p + ".conv1.weight", p + ".bn1")
-                y = self._cb(y, p + ".conv2.weight", p + ".bn2", st, d, d)
-                y = self._cb(y, p + ".conv3.weight", p + ".bn3", relu=False)
-                sc = self._cb(t, p + ".downsample.0.weight", p + ".downsample.1", st, relu=False) if b == 0 else t
-                t = torch.relu(y + sc)
-        a = "classifier.0."
-        br = [self._cb(t, a + "convs.0.0.weight", a + "convs.0.1")]
-        for i, d in zip((1, 2, 3), RATES):
-            br.append(self._cb(t, a + f"convs.{i}.0.weight", a + f"convs.{i}.1", 1, d, d))
-        pooled = self._cb(F.adaptive_avg_pool2d(t, 1), a + "convs.4.1.weight", a + "convs.4.2")
-        br.append(pooled.expand(-1, -1, t.shape[2], t.shape[3]))
-        t = self._cb(torch.cat(br, dim=1), a + "project.0.weight", a + "project.1")
-        t = self._cb(t, "classifier.1.weight", "classifier.2", 1, 1)
-        t = F.conv2d(t, self.w["classifier.4.weight"], self.w["classifier.4.bias"])
-        return F.interpolate(t, size=x.shape[-2:], mode="bilinear", align_corners=False)
-
-
-def deeplab_state_dict(R, arch, classes=21, seed=1):
-    g = torch.Generator().manual_seed(seed + 200)
-    sd = {k: v for k, v in fcn_state_dict(R, arch, classes, seed).items() if not k.startswith("classifier.")}
-
-    def conv_bn(conv, bn, shape):
-        sd[conv + ".weight"] = torch.randn(shape, generator=g) * (2.0 / (shape[1] * shape[2] * shape[3])) ** 0.5
-        sd[bn + ".weight"] = torch.rand(shape[0], generator=g) + 0.5
-        sd[bn + ".bias"] = (torch.rand(shape[0], generator=g) - 0.5) * 0.2
-        sd[bn + ".running_mean"] = (torch.rand(shape[0], generator=g) - 0.5) * 0.2
-        sd[bn + ".running_var"] = torch.rand(shape[0], generator=g) + 0.5
-
-    a = "classifier.0."
-    conv_bn(a + "convs.0.0", a + "convs.0.1", (CB, CIN, 1, 1))
-    for i in (1, 2, 3):
-        conv_bn(a + f"convs.{i}.0", a + f"convs.{i}.1", (CB, CIN, 3, 3))
-    conv_bn(a + "convs.4.1", a + "convs.4.2", (CB, CIN, 1, 1))
-    conv_bn(a + "project.0", a + "project.1", (CB, 5 * CB, 1, 1))
-    conv_bn("classifier.1", "classifier.2", (CB, CB, 3, 3))
-    sd["classifier.4.weight"] = torch.randn(classes, CB, 1, 1, generator=g) * (1.0 / CB) ** 0.5
-    sd["classifier.4.bias"] = torch.rand(classes, generator=g) - 0.5
-    return sd
-
-
 def net(a, pkg, dev):
-    R = importlib.import_module("cuda_winograd_amd.resnet")
-    sd = deeplab_state_dict(R, "resnet50")
+    R = benchlib.package_module("resnet")
+    sd = torch_nets.deeplab_state_dict(R, "resnet50")
     model = pkg.DeepLabV3.from_state_dict(sd, "resnet50")
-    tnet = TorchDeepLab(R, sd, "resnet50", dev)
+    body = torch_nets.TorchResNetBody(R, sd, "resnet50", dev, prefix="backbone.", dilate=torch_nets.SEGMENTATION_DILATE)
     rows = []
     S = a.size
-    for N in (int(v) for v in a.ns.split(",")):
-        x = (torch.rand(N, 3, S, S, generator=torch.Generator().manual_seed(N)) * 2 - 1).to(dev)
-        x_cl = x.contiguous(memory_format=torch.channels_last)
-        sg = torch.cuda.Stream()
-        sg.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(sg):
-            model.prepare(N, S, S)
-            mine = model(x)["out"]
-        sg.synchronize()
-        ref = tnet(x_cl)
+    for N in benchlib.ints(a.ns):
+        x, x_cl = torch_nets.image_batch(N, S, S, dev)
+        tnet = lambda: torch_nets.deeplab_head(body, body(x_cl), (S, S))
+        graph, first = benchlib.captured(lambda: model(x), lambda: model.prepare(N, S, S))
+        mine, ref = first["out"], tnet()
         diff = float((mine - ref).abs().max() / ref.abs().max())
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=sg):
-            model(x)
-        torch.cuda.synchronize()
-        variants = {"eager": lambda: model(x), "graph": graph.replay, "torch": lambda: tnet(x_cl)}
-        med, times = _interleaved(variants, a.trials, a.reps)
+        med, times = benchlib.interleaved(benchlib.net_variants(lambda: model(x), graph, tnet), a.trials, a.reps)
         rows.append({"arch": "deeplabv3_resnet50", "N": N, "size": S, "median_us": med, "trials_us": times,
-                     "rel_diff_to_torch_fp32": diff, "graph_over_eager": med["graph"] / med["eager"],
-                     "graph_over_torch": med["graph"] / med["torch"], "eager_over_torch": med["eager"] / med["torch"]})
+                     "rel_diff_to_torch_fp32": diff, **benchlib.net_ratios(med)})
         print(f"deeplabv3_resnet50 N={N:2d} {S}x{S}  eager {med['eager']:9.1f} us  graph {med['graph']:9.1f} us  torch "
               f"{med['torch']:9.1f} us  graph/torch {rows[-1]['graph_over_torch']:.3f}  eager/torch "
               f"{rows[-1]['eager_over_torch']:.3f}  (max rel diff to torch fp32 {diff:.1e})", flush=True)
-        del graph, x, x_cl, mine, ref
+        del graph, x, x_cl, first, mine, ref
         torch.cuda.empty_cache()
     return rows
 
 
+MODES = {"cat": dict(fn=cat, ns="1,8", trials=7, reps=20),
+         "module": dict(fn=module, ns="1,8", trials=5, reps=5),
+         "net": dict(fn=net, ns="1,8", size=520, trials=5, reps=3),
+         "parts": dict(fn=parts, ns="1,8", trials=5, reps=10),
+         "all": ["cat", "module", "net"]}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["cat", "module", "net", "parts", "all"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default="1,8")
-    ap.add_argument("--size", type=int, default=520)
-    ap.add_argument("--trials", type=int, default=None)
-    ap.add_argument("--reps", type=int, default=None)
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    result = {"tool": f"tools/aspp_bench.py {a.mode}", "device": torch.cuda.get_device_name(0)}
-    trials, reps = a.trials, a.reps
-    defaults = {"cat": (cat, 7, 20), "module": (module, 5, 5), "net": (net, 5, 3)}
-    if a.mode == "parts":
-        defaults = {"parts": (parts, 5, 10)}
-    for mode, (fn, t, r) in defaults.items():
-        if a.mode in (mode, "all"):
-            a.trials, a.reps = trials or t, reps or r
-            result[mode] = {"trials": a.trials, "reps": a.reps, "rows": fn(a, pkg, dev)}
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(result, f, indent=1)
+    a = benchlib.parse(MODES)
+    result = benchlib.header(f"tools/aspp_bench.py {a.mode}")
+    result.update(benchlib.sections(a, MODES, benchlib.load_package(), torch.device("cuda:0")))
+    benchlib.write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -8,17 +8,9 @@ usage: python tools/basic_block_bench.py bench [out.json] [--ns 1,8,32,128] [--t
        python tools/basic_block_bench.py trace [--ns 128] [--reps 20]
          the residual and the plain layer back to back, then the block -- run it under
          `rocprofv3 --kernel-trace --stats -- python ...` to compare the kernels' own times in one trace"""
-import argparse
-import json
-import os
-import statistics
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
+import benchlib
+import torch
+import torch.nn.functional as F
 
 STAGES = {"conv2": (56, 64), "conv3": (28, 128), "conv4": (14, 256), "conv5": (7, 512)}   # (H, C)
 
@@ -70,33 +62,15 @@ class _Case:
         return torch.relu(y * s2[None, :, None, None] + b2[None, :, None, None] + self.x_cl)
 
 
-def _time(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
 def bench(a, pkg, dev):
     rows = []
     for stage, (H, C) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             c = _Case(pkg, N, H, C, dev)
             pkg.basic_block_prepare(N, H, H, C)
             variants = {"plain_layer": c.plain_layer, "res_layer": c.res_layer, "block": c.block,
                         "composed": c.composed, "torch": c.torch_block}
-            for fn in variants.values():   # warm-up: plans, scratch, torch's algorithm choice
-                for _ in range(3):
-                    fn()
-            torch.cuda.synchronize()
-            times = {k: [] for k in variants}
-            for _ in range(a.trials):
-                for k, fn in variants.items():
-                    times[k].append(_time(fn, a.reps))
-            med = {k: statistics.median(v) for k, v in times.items()}
+            med, times = benchlib.interleaved(variants, a.trials, a.reps)
             row = {"stage": stage, "H": H, "C": C, "N": N, "median_us": med, "trials_us": times,
                    "res_over_plain": med["res_layer"] / med["plain_layer"],
                    "block_over_composed": med["block"] / med["composed"],
@@ -108,15 +82,12 @@ def bench(a, pkg, dev):
                   flush=True)
             del c
             torch.cuda.empty_cache()
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump({"tool": "tools/basic_block_bench.py bench", "device": torch.cuda.get_device_name(0),
-                       "trials": a.trials, "reps": a.reps, "rows": rows}, f, indent=1)
+    return rows
 
 
 def trace(a, pkg, dev):
     for stage, (H, C) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             c = _Case(pkg, N, H, C, dev)
             for fn in (c.res_layer, c.plain_layer, c.block):
                 for _ in range(a.reps):
@@ -125,22 +96,12 @@ def trace(a, pkg, dev):
             print(f"{stage} N={N}: {a.reps} x (residual layer, plain layer, block)", flush=True)
 
 
+MODES = {"bench": dict(fn=bench, ns="1,8,32,128", trials=7, reps=20),
+         "trace": dict(fn=trace, ns="128", reps=20)}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["bench", "trace"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default=None)
-    ap.add_argument("--trials", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=20)
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    if a.mode == "bench":
-        a.ns = a.ns or "1,8,32,128"
-        bench(a, pkg, dev)
-    else:
-        a.ns = a.ns or "128"
-        trace(a, pkg, dev)
+    benchlib.main_rows("tools/basic_block_bench.py", MODES)
 
 
 if __name__ == "__main__":

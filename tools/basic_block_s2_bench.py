@@ -11,17 +11,9 @@ usage: python tools/basic_block_s2_bench.py bench [out.json] [--ns 1,8,32,128] [
        python tools/basic_block_s2_bench.py trace [--ns 128] [--reps 20]
          the fused layer, the plain stride-2 3x3 and the block back to back -- run it under
          `rocprofv3 --kernel-trace --stats -- python ...` to compare the kernels' own times in one trace"""
-import argparse
-import json
-import os
-import statistics
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
+import benchlib
+import torch
+import torch.nn.functional as F
 
 STAGES = {"conv3": (56, 64, 128), "conv4": (28, 128, 256), "conv5": (14, 256, 512)}   # (Hin, C, K)
 
@@ -84,34 +76,16 @@ class _Case:
         return torch.relu(y + sc)
 
 
-def _time(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
 def bench(a, pkg, dev):
     rows = []
     for stage, (Hin, C, K) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             c = _Case(pkg, N, Hin, C, K, dev)
             pkg.basic_block_s2_prepare(N, Hin, Hin, C, K)
             variants = {"fused_layer": c.fused_layer, "plain_layer": c.plain_layer,
                         "plain_and_shortcut": c.plain_and_shortcut, "block": c.block, "composed": c.composed,
                         "torch": c.torch_block}
-            for fn in variants.values():   # warm-up: plans, scratch, torch's algorithm choice
-                for _ in range(3):
-                    fn()
-            torch.cuda.synchronize()
-            times = {k: [] for k in variants}
-            for _ in range(a.trials):
-                for k, fn in variants.items():
-                    times[k].append(_time(fn, a.reps))
-            med = {k: statistics.median(v) for k, v in times.items()}
+            med, times = benchlib.interleaved(variants, a.trials, a.reps)
             row = {"stage": stage, "Hin": Hin, "C": C, "K": K, "N": N, "median_us": med, "trials_us": times,
                    "fused_over_plain": med["fused_layer"] / med["plain_layer"],
                    "fused_over_plain_and_shortcut": med["fused_layer"] / med["plain_and_shortcut"],
@@ -123,15 +97,12 @@ def bench(a, pkg, dev):
                   f"/composed {row['block_over_composed']:.3f} /torch {row['block_over_torch']:.3f}", flush=True)
             del c
             torch.cuda.empty_cache()
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump({"tool": "tools/basic_block_s2_bench.py bench", "device": torch.cuda.get_device_name(0),
-                       "trials": a.trials, "reps": a.reps, "rows": rows}, f, indent=1)
+    return rows
 
 
 def trace(a, pkg, dev):
     for stage, (Hin, C, K) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             c = _Case(pkg, N, Hin, C, K, dev)
             for fn in (c.fused_layer, c.plain_layer, c.shortcut, c.block):
                 for _ in range(a.reps):
@@ -140,22 +111,12 @@ def trace(a, pkg, dev):
             print(f"{stage} N={N}: {a.reps} x (fused layer, plain stride-2 layer, shortcut 1x1, block)", flush=True)
 
 
+MODES = {"bench": dict(fn=bench, ns="1,8,32,128", trials=7, reps=20),
+         "trace": dict(fn=trace, ns="128", reps=20)}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["bench", "trace"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default=None)
-    ap.add_argument("--trials", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=20)
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    if a.mode == "bench":
-        a.ns = a.ns or "1,8,32,128"
-        bench(a, pkg, dev)
-    else:
-        a.ns = a.ns or "128"
-        trace(a, pkg, dev)
+    benchlib.main_rows("tools/basic_block_s2_bench.py", MODES)
 
 
 if __name__ == "__main__":

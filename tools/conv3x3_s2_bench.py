@@ -6,17 +6,10 @@ usage: python tools/conv3x3_s2_bench.py trace [--ns 128] [--reps 20]
        python tools/conv3x3_s2_bench.py policy [out.json] [--ns 1,2,8,16,32,128] [--trials 5] [--reps 30]
          the automatic plan against every forced form (latency KS x RT x CT, tiled, stream-K) at the conv3/4/5 shapes,
          interleaved rounds between events; reports each form's median and automatic / best forced"""
-import argparse
-import json
 import os
-import statistics
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
+import benchlib
+import torch
 
 STAGES = {"conv3": (56, 128), "conv4": (28, 256), "conv5": (14, 512)}   # (Hin, C = K)
 KNOBS = ("WINO_1X1_ALGO", "WINO_1X1_SMALL_KS", "WINO_1X1_SMALL_RT", "WINO_1X1_SMALL_CT", "WINO_1X1_SK", "WINO_1X1_SK_GRID")
@@ -41,7 +34,7 @@ def _layer(N, Hin, C, K, dev):
 
 def trace(a, pkg, dev):
     for stage, (Hin, C) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             H = (Hin - 1) // 2 + 1
             x, w, b, s = _layer(N, Hin, C, C, dev)
             taps = pkg.filter_pack_s2(w)
@@ -77,7 +70,7 @@ def _forms(C, K):
 def policy(a, pkg, dev):
     rows = []
     for stage, (Hin, C) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             H = (Hin - 1) // 2 + 1
             x, w, b, s = _layer(N, Hin, C, C, dev)
             taps = pkg.filter_pack_s2(w)
@@ -88,23 +81,9 @@ def policy(a, pkg, dev):
                 _set(pkg, **kv)
                 plans[name] = pkg.conv3x3_s2_plan(N, Hin, Hin, C, C)
                 pkg.conv3x3_s2_prepare(N, Hin, Hin, C, C)
-            t0 = time.time()
-            while time.time() - t0 < 0.3:
-                for _ in range(10):
-                    pkg.conv3x3_s2_bn_relu(x, taps, b, s, out=out)
-                torch.cuda.synchronize()
-            times = {k: [] for k in forms}
-            for _ in range(a.trials):
-                for name, kv in forms.items():
-                    _set(pkg, **kv)
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(a.reps):
-                        pkg.conv3x3_s2_bn_relu(x, taps, b, s, out=out)
-                    e1.record()
-                    e1.synchronize()
-                    times[name].append(e0.elapsed_time(e1) * 1e3 / a.reps)
-            med = {k: statistics.median(v) for k, v in times.items()}
+            run = lambda: pkg.conv3x3_s2_bn_relu(x, taps, b, s, out=out)
+            med, times = benchlib.interleaved({k: run for k in forms}, a.trials, a.reps, preheat_s=0.3,
+                                              setups={k: (lambda kv=kv: _set(pkg, **kv)) for k, kv in forms.items()})
             best = min((v, k) for k, v in med.items() if k != "auto")
             row = {"stage": stage, "N": N, "auto_form": plans["auto"], "auto_us": med["auto"], "best_forced": best[1],
                    "best_forced_us": best[0], "auto_over_best": med["auto"] / best[0], "median_us": med,
@@ -113,28 +92,15 @@ def policy(a, pkg, dev):
             print(f"{stage} N={N:4d} auto {med['auto']:8.1f} us (form {plans['auto']})  best forced {best[1]} "
                   f"{best[0]:8.1f} us  ratio {row['auto_over_best']:.3f}", flush=True)
             _set(pkg)
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump({"tool": "tools/conv3x3_s2_bench.py policy", "device": torch.cuda.get_device_name(0),
-                       "trials": a.trials, "reps": a.reps, "rows": rows}, f, indent=1)
+    return rows
+
+
+MODES = {"trace": dict(fn=trace, ns="128", reps=20),
+         "policy": dict(fn=policy, ns="1,2,8,16,32,128", trials=5, reps=30)}
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["trace", "policy"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default=None)
-    ap.add_argument("--trials", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=None)
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    if a.mode == "trace":
-        a.ns, a.reps = a.ns or "128", a.reps or 20
-        trace(a, pkg, dev)
-    else:
-        a.ns, a.reps = a.ns or "1,2,8,16,32,128", a.reps or 30
-        policy(a, pkg, dev)
+    benchlib.main_rows("tools/conv3x3_s2_bench.py", MODES)
 
 
 if __name__ == "__main__":

@@ -14,24 +14,16 @@ usage: python tools/fpn_bench.py lateral [out.json] [--n 2] [--hw 800,1344] [--t
          replayed, and a torch fp32 channels-last composition with the same weights (conv, BN as scale and bias,
          F.interpolate, F.max_pool2d(1, 2))
 Results under profiles/fpn/ (bench.json holds both modes' rows)."""
-import argparse
-import importlib
-import json
-import os
-import sys
+import benchlib
+import torch
+import torch.nn.functional as F
+import torch_nets
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
-from resnet_bench import TorchNet, _interleaved, random_state_dict  # noqa: E402
-
-CF = 256
+CF = torch_nets.FPN_CHANNELS
 
 
 def lateral(a, pkg, dev):
-    R = importlib.import_module("cuda_winograd_amd.resnet")
+    R = benchlib.package_module("resnet")
     N, (H0, W0) = a.n, a.hw
     stages = R.stage_shapes("resnet50", H0, W0)[1:]            # (name, C, h, w) of conv2..conv5
     rows = []
@@ -71,7 +63,7 @@ def lateral(a, pkg, dev):
         composed()
         torch.cuda.synchronize()
         assert float((inner - want).abs().max()) < 1e-5, "the fused launch and the composition disagree"
-        med, times = _interleaved({"fused": fused, "plain": plain, "composed": composed, "same_size": same_size},
+        med, times = benchlib.interleaved({"fused": fused, "plain": plain, "composed": composed, "same_size": same_size},
                                   a.trials, a.reps)
         row = {"level": lvl, "N": N, "H": H, "W": W, "Cin": Cin, "Cf": CF, "median_us": med, "trials_us": times,
                "fused_over_plain": med["fused"] / med["plain"], "fused_over_composed": med["fused"] / med["composed"],
@@ -85,122 +77,42 @@ def lateral(a, pkg, dev):
     return rows
 
 
-def fpn_state_dict(R, arch, seed=1):
-    body = random_state_dict(R, arch, seed=seed)
-    sd = {"body." + k: v for k, v in body.items() if not k.startswith("fc.")}
-    g = torch.Generator().manual_seed(seed + 1)
-    for i, (_, c, _, _) in enumerate(R.stage_shapes(arch, 64, 64)[1:]):
-        sd[f"fpn.inner_blocks.{i}.0.weight"] = torch.randn(CF, c, 1, 1, generator=g) * (1.0 / c) ** 0.5
-        sd[f"fpn.inner_blocks.{i}.0.bias"] = (torch.rand(CF, generator=g) - 0.5) * 0.2
-        sd[f"fpn.layer_blocks.{i}.0.weight"] = torch.randn(CF, CF, 3, 3, generator=g) * (1.0 / (9 * CF)) ** 0.5
-        sd[f"fpn.layer_blocks.{i}.0.bias"] = (torch.rand(CF, generator=g) - 0.5) * 0.2
-    return sd, body
-
-
-class TorchFPN(TorchNet):
-    """torch eager on channels-last fp32 with the same weights: the body of resnet_bench.TorchNet, then
-    torchvision's FeaturePyramidNetwork and LastLevelMaxPool written out."""
-
-    def __init__(self, R, sd, body, arch, dev):
-        super().__init__(R, body, arch, dev)
-        self.f = {k: v.to(dev).contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.to(dev)
-                  for k, v in sd.items() if k.startswith("fpn.")}
-
-    def __call__(self, x):
-        t = F.max_pool2d(self._cb(x, "conv1.weight", "bn1", 2, 3), 3, 2, 1)
-        c = []
-        for L, nb in enumerate(self.blocks, 1):
-            for b in range(nb):
-                p = f"layer{L}.{b}"
-                st = 2 if (b == 0 and L > 1) else 1
-                if self.bottleneck:
-                    y = self._cb(t, p + ".conv1.weight", p + ".bn1")
-                    y = self._cb(y, p + ".conv2.weight", p + ".bn2", st, 1)
-                    y = self._cb(y, p + ".conv3.weight", p + ".bn3", relu=False)
-                else:
-                    y = self._cb(t, p + ".conv1.weight", p + ".bn1", st, 1)
-                    y = self._cb(y, p + ".conv2.weight", p + ".bn2", 1, 1, relu=False)
-                sc = t
-                if p + ".downsample.0.weight" in self.w:
-                    sc = self._cb(t, p + ".downsample.0.weight", p + ".downsample.1", st, relu=False)
-                t = torch.relu(y + sc)
-            c.append(t)
-        f = self.f
-        last = F.conv2d(c[3], f["fpn.inner_blocks.3.0.weight"], f["fpn.inner_blocks.3.0.bias"])
-        out = [None, None, None, F.conv2d(last, f["fpn.layer_blocks.3.0.weight"], f["fpn.layer_blocks.3.0.bias"], padding=1)]
-        for i in (2, 1, 0):
-            lat = F.conv2d(c[i], f[f"fpn.inner_blocks.{i}.0.weight"], f[f"fpn.inner_blocks.{i}.0.bias"])
-            last = lat + F.interpolate(last, size=lat.shape[-2:], mode="nearest")
-            out[i] = F.conv2d(last, f[f"fpn.layer_blocks.{i}.0.weight"], f[f"fpn.layer_blocks.{i}.0.bias"], padding=1)
-        return out + [F.max_pool2d(out[3], 1, 2, 0)]
-
-
 def net(a, pkg, dev):
-    R = importlib.import_module("cuda_winograd_amd.resnet")
+    R = benchlib.package_module("resnet")
     N, (H, W) = a.n, a.hw
     rows = []
     for arch in a.archs.split(","):
-        sd, body = fpn_state_dict(R, arch)
+        sd, _ = torch_nets.fpn_state_dict(R, arch)
         model = pkg.ResNetFPN.from_state_dict(sd, arch, out_channels=CF)
-        tnet = TorchFPN(R, sd, body, arch, dev)
-        x = (torch.rand(N, 3, H, W, generator=torch.Generator().manual_seed(N)) * 2 - 1).to(dev)
-        x_cl = x.contiguous(memory_format=torch.channels_last)
-        sg = torch.cuda.Stream()
-        sg.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(sg):
-            model.prepare(N, H, W)
-            got = model(x)
-        sg.synchronize()
-        want = tnet(x_cl)
+        body = torch_nets.TorchResNetBody(R, sd, arch, dev, prefix="body.")
+        x, x_cl = torch_nets.image_batch(N, H, W, dev)
+        tnet = lambda: torch_nets.fpn_head(body, body(x_cl))
+        graph, got = benchlib.captured(lambda: model(x), lambda: model.prepare(N, H, W))
+        want = tnet()
         errs = {k: float((got[k].permute(0, 3, 1, 2) - w).abs().max() / w.abs().max())
                 for k, w in zip(("0", "1", "2", "3", "pool"), want)}
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=sg):
-            model(x)
-        torch.cuda.synchronize()
-        med, times = _interleaved({"eager": lambda: model(x), "graph": graph.replay, "torch": lambda: tnet(x_cl)},
-                                  a.trials, a.reps)
+        med, times = benchlib.interleaved(benchlib.net_variants(lambda: model(x), graph, tnet), a.trials, a.reps)
         row = {"arch": arch, "N": N, "H": H, "W": W, "median_us": med, "trials_us": times,
-               "max_rel_diff_vs_torch_fp32": errs, "graph_over_eager": med["graph"] / med["eager"],
-               "graph_over_torch": med["graph"] / med["torch"], "eager_over_torch": med["eager"] / med["torch"]}
+               "max_rel_diff_vs_torch_fp32": errs, **benchlib.net_ratios(med)}
         rows.append(row)
         print(f"{arch:9s}-fpn N={N} {H}x{W}  eager {med['eager']:9.1f} us  graph {med['graph']:9.1f} us  torch "
               f"{med['torch']:9.1f} us  graph/torch {row['graph_over_torch']:.3f}  max rel diff vs torch "
               f"{max(errs.values()):.1e}", flush=True)
-        del graph, model, tnet, x, x_cl, got, want
+        del graph, model, body, x, x_cl, got, want
         torch.cuda.empty_cache()
     return rows
 
 
+MODES = {"lateral": dict(fn=lateral, n=2, hw="800,1344", trials=7, reps=20),
+         "net": dict(fn=net, archs="resnet50,resnet18", n=2, hw="800,1344", trials=5, reps=5)}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["lateral", "net"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--n", type=int, default=2)
-    ap.add_argument("--hw", default="800,1344")
-    ap.add_argument("--archs", default="resnet50,resnet18")
-    ap.add_argument("--trials", type=int, default=None)
-    ap.add_argument("--reps", type=int, default=None)
-    a = ap.parse_args()
-    a.hw = tuple(int(v) for v in a.hw.split(","))
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    if a.mode == "lateral":
-        a.trials, a.reps = a.trials or 7, a.reps or 20
-        rows = lateral(a, pkg, dev)
-    else:
-        a.trials, a.reps = a.trials or 5, a.reps or 5
-        rows = net(a, pkg, dev)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        doc = {}
-        if os.path.exists(a.out):   # one file for both modes: the other mode's rows stay
-            with open(a.out) as f:
-                doc = json.load(f)
-        doc.update({"tool": "tools/fpn_bench.py", "device": torch.cuda.get_device_name(0),
-                    a.mode: {"trials": a.trials, "reps": a.reps, "rows": rows}})
-        with open(a.out, "w") as f:
-            json.dump(doc, f, indent=1)
+    a = benchlib.parse(MODES)
+    a.hw = tuple(benchlib.ints(a.hw))
+    rows = a.fn(a, benchlib.load_package(), torch.device("cuda:0"))
+    # one file for both modes: the other mode's rows stay
+    benchlib.write_json(a.out, benchlib.header("tools/fpn_bench.py", **{a.mode: benchlib.section(a, rows)}), merge=True)
 
 
 if __name__ == "__main__":

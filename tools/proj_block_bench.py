@@ -9,17 +9,10 @@ of each variant ran at (wino_diag_last_clock).
 the stride-2 3x3 done by torch -- F.conv2d(stride=2, padding=1) on channels-last tensors, BN and ReLU in torch -- and
 the tail as the library's shortcut 1x1 + last 1x1 with WINO_ADD_RESIDUAL (the fused tail has no entry point of its
 own); in the same rounds the stride-2 3x3 alone, library against torch."""
-import argparse
-import json
-import os
 import statistics
-import sys
-import time
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
+import benchlib
+import torch
 
 STAGES = {   # ResNet-50's stage-entry blocks: (Hin, Cin, Cm, C4, stride)
     "conv2": (56, 64, 64, 256, 1),
@@ -27,23 +20,13 @@ STAGES = {   # ResNet-50's stage-entry blocks: (Hin, Cin, Cm, C4, stride)
     "conv4": (28, 512, 256, 1024, 2),
     "conv5": (14, 1024, 512, 2048, 2),
 }
+PREHEAT_S = 0.4
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default="1,16,128")
-    ap.add_argument("--trials", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=50)
-    ap.add_argument("--v15", action="store_true")
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    if a.v15:
-        return main_v15(a, pkg)
-    dev = torch.device("cuda:0")
+def main_v1(a, pkg, dev):
     rows = []
     for stage, (Hin, Cin, Cm, C4, s) in STAGES.items():
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             g = torch.Generator(device="cpu").manual_seed(N)
             r = lambda *shape, sc=1.0: ((torch.rand(*shape, generator=g) - 0.5) * sc).to(dev)
             x = r(N, Hin, Hin, Cin)
@@ -74,28 +57,13 @@ def main():
             fns = {"fused": fused, "composed": composed}
             fused(); composed(); torch.cuda.synchronize()
             rel = float((out.reshape(-1, C4) - out2).abs().max() / out2.abs().max().clamp_min(1e-30))
-            t0 = time.time()
-            while time.time() - t0 < 0.4:
-                for f in fns.values():
-                    for _ in range(5):
-                        f()
-                torch.cuda.synchronize()
-            times = {k: [] for k in fns}
-            clocks = {k: [] for k in fns}
-            for _ in range(a.trials):
-                for k, f in fns.items():
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    for _ in range(a.reps):
-                        f()
-                    e1.record()
-                    e1.synchronize()
-                    times[k].append(e0.elapsed_time(e1) * 1e3 / a.reps)
-                    c = pkg.last_clock_ghz(0)
-                    clocks[k].append(c[0] if c else None)
+            clocks = {k: [] for k in fns}   # the chip clock of each round's last 3x3 launch, read after its window
+            stamp = lambda k: clocks[k].append((pkg.last_clock_ghz(0) or [None])[0])
+            med, times = benchlib.interleaved(fns, a.trials, a.reps, preheat_s=PREHEAT_S,
+                                              after={k: (lambda k=k: stamp(k)) for k in fns})
             row = {"stage": stage, "N": N, "Hin": Hin, "Cin": Cin, "Cm": Cm, "C4": C4, "stride": s,
                    "forms_first_tail": pkg.proj_tail_plan(N, Hin, Hin, Cin, Cm, C4, s),
-                   "fused_us": statistics.median(times["fused"]), "composed_us": statistics.median(times["composed"]),
+                   "fused_us": med["fused"], "composed_us": med["composed"],
                    "fused_trials_us": times["fused"], "composed_trials_us": times["composed"],
                    "clock_ghz_fused": statistics.median([c for c in clocks["fused"] if c] or [0.0]),
                    "clock_ghz_composed": statistics.median([c for c in clocks["composed"] if c] or [0.0]),
@@ -107,42 +75,16 @@ def main():
                   f"forms {row['forms_first_tail']}  rel {rel:.1e}", flush=True)
             del x, out, ws, short, t1p, t2p, out2
             torch.cuda.empty_cache()
-    res = {"tool": "tools/proj_block_bench.py", "device": torch.cuda.get_device_name(0), "trials": a.trials,
-           "reps": a.reps, "rows": rows}
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    return rows
 
 
-def _interleaved(fns, trials, reps):
-    """0.4 s of preheat, then `trials` rounds of every variant: the median us per call of each."""
-    t0 = time.time()
-    while time.time() - t0 < 0.4:
-        for f in fns.values():
-            for _ in range(5):
-                f()
-        torch.cuda.synchronize()
-    times = {k: [] for k in fns}
-    for _ in range(trials):
-        for k, f in fns.items():
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for _ in range(reps):
-                f()
-            e1.record()
-            e1.synchronize()
-            times[k].append(e0.elapsed_time(e1) * 1e3 / reps)
-    return {k: statistics.median(v) for k, v in times.items()}, times
-
-
-def main_v15(a, pkg):
+def main_v15(a, pkg, dev):
     F = torch.nn.functional
-    dev = torch.device("cuda:0")
     rows = []
     for stage in ("conv3", "conv4", "conv5"):
         Hin, Cin, Cm, C4, _ = STAGES[stage]
         H = (Hin - 1) // 2 + 1
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             g = torch.Generator(device="cpu").manual_seed(N)
             r = lambda *shape, sc=1.0: ((torch.rand(*shape, generator=g) - 0.5) * sc).to(dev)
             x = r(N, Hin, Hin, Cin)
@@ -182,7 +124,7 @@ def main_v15(a, pkg):
             fused(); composed(); layer(); torch.cuda.synchronize()
             rel = float((out.reshape(-1, C4) - out2).abs().max() / out2.abs().max().clamp_min(1e-30))
             rel_layer = float((t2l - t2p).abs().max() / t2p.abs().max().clamp_min(1e-30))
-            med, trials = _interleaved(fns, a.trials, a.reps)
+            med, trials = benchlib.interleaved(fns, a.trials, a.reps, preheat_s=PREHEAT_S)
             row = {"stage": stage, "N": N, "Hin": Hin, "Cin": Cin, "Cm": Cm, "C4": C4,
                    "form_3x3": pkg.conv3x3_s2_plan(N, Hin, Hin, Cm, Cm),
                    "fused_us": med["fused"], "composed_torch_3x3_us": med["composed"],
@@ -196,11 +138,18 @@ def main_v15(a, pkg):
                   f"x{row['speedup_layer']:.3f}  form {row['form_3x3']}  rel {rel:.1e} / {rel_layer:.1e}", flush=True)
             del x, out, ws, t1p, t2p, t2l, short, out2
             torch.cuda.empty_cache()
-    res = {"tool": "tools/proj_block_bench.py --v15", "device": torch.cuda.get_device_name(0), "trials": a.trials,
-           "reps": a.reps, "rows": rows}
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump(res, f, indent=1)
+    return rows
+
+
+MODES = {None: dict(ns="1,16,128", trials=5, reps=50)}
+EXTRA = [("--v15", dict(action="store_true"))]
+
+
+def main():
+    a = benchlib.parse(MODES, EXTRA)
+    rows = (main_v15 if a.v15 else main_v1)(a, benchlib.load_package(), torch.device("cuda:0"))
+    tool = "tools/proj_block_bench.py" + (" --v15" if a.v15 else "")
+    benchlib.write_json(a.out, benchlib.header(tool, **benchlib.section(a, rows)))
 
 
 if __name__ == "__main__":

@@ -14,23 +14,16 @@ usage: python tools/resize_bench.py layer [out.json] [--ns 1,8] [--trials 7] [--
        python tools/resize_bench.py all profiles/resize/bench.json
          both, each in a child process of its own under its own time limit, into one file
 (median of the trials, events around `reps` calls)"""
-import argparse
-import importlib
 import json
 import os
 import subprocess
 import sys
 import tempfile
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
-from aspp_bench import deeplab_state_dict  # noqa: E402
-from dilated_bench import fcn_state_dict  # noqa: E402
-from resnet_bench import _interleaved  # noqa: E402
+import benchlib
+import torch
+import torch.nn.functional as F
+import torch_nets
 
 COPY_TBS = 6.29          # the measured device copy rate the floors are taken at
 POINTS = [(65, 520), (33, 260)]
@@ -42,7 +35,7 @@ STEP_LIMIT_S = {"layer": 240, "net": 420}
 def layer(a, pkg, dev):
     rows = []
     for h, Ho in POINTS:
-        for N in (int(v) for v in a.ns.split(",")):
+        for N in benchlib.ints(a.ns):
             g = torch.Generator().manual_seed(N + h)
             scores = (torch.rand(N, h, h, LD, generator=g) - 0.5).to(dev)
             out = torch.empty(N, C, Ho, Ho, device=dev)
@@ -59,16 +52,9 @@ def layer(a, pkg, dev):
             ref = t_out()
             diff = float((variants["out"]()[0] - ref).abs().max() / ref.abs().max())
             agree = float((variants["labels"]()[1] == ref.argmax(1)).float().mean())
-            med, times = _interleaved(variants, a.trials, a.reps)
-            sg = torch.cuda.Stream()
-            sg.wait_stream(torch.cuda.current_stream())
-            graphs = {}
-            for k, fn in variants.items():   # `reps` calls per graph
-                graphs[k] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graphs[k], stream=sg):
-                    for _ in range(a.reps):
-                        fn()
-            gmed, gtimes = _interleaved({k: gph.replay for k, gph in graphs.items()}, a.trials, 3)
+            med, times = benchlib.interleaved(variants, a.trials, a.reps)
+            graphs = {k: benchlib.captured(benchlib.repeated(fn, a.reps))[0] for k, fn in variants.items()}
+            gmed, gtimes = benchlib.interleaved({k: gph.replay for k, gph in graphs.items()}, a.trials, 3)
             gmed = {k: v / a.reps for k, v in gmed.items()}
             gtimes = {k: [t / a.reps for t in v] for k, v in gtimes.items()}
             del graphs
@@ -96,32 +82,21 @@ def layer(a, pkg, dev):
 
 
 def net(a, pkg, dev):
-    R = importlib.import_module("cuda_winograd_amd.resnet")
+    R = benchlib.package_module("resnet")
     rows = []
     S = a.size
-    for name, cls, make in (("fcn_resnet50", pkg.FCN, fcn_state_dict), ("deeplabv3_resnet50", pkg.DeepLabV3, deeplab_state_dict)):
+    for name, cls, make in (("fcn_resnet50", pkg.FCN, torch_nets.fcn_state_dict),
+                            ("deeplabv3_resnet50", pkg.DeepLabV3, torch_nets.deeplab_state_dict)):
         model = cls.from_state_dict(make(R, "resnet50"), "resnet50")
-        for N in (int(v) for v in a.ns.split(",")):
-            x = (torch.rand(N, 3, S, S, generator=torch.Generator().manual_seed(N)) * 2 - 1).to(dev)
-            sg = torch.cuda.Stream()
-            sg.wait_stream(torch.cuda.current_stream())
+        for N in benchlib.ints(a.ns):
+            x, _ = torch_nets.image_batch(N, S, S, dev)
             runs = {"torch": lambda: model(x, resize="torch")["out"].argmax(1),
                     "kernel": lambda: model(x, labels=True, out=False)["labels"]}
             graphs, results = {}, {}
-            with torch.cuda.stream(sg):
-                model.prepare(N, S, S)
-                for k, fn in runs.items():
-                    fn()
-            sg.synchronize()
-            for k, fn in runs.items():
-                graphs[k] = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graphs[k], stream=sg):
-                    results[k] = fn()
-            for gph in graphs.values():
-                gph.replay()
-            torch.cuda.synchronize()
+            for k, fn in runs.items():   # prepare allocates the activations: once, before the first capture
+                graphs[k], results[k] = benchlib.captured(fn, None if graphs else lambda: model.prepare(N, S, S))
             agree = float((results["torch"] == results["kernel"]).float().mean())
-            med, times = _interleaved({k: gph.replay for k, gph in graphs.items()}, a.trials, a.reps)
+            med, times = benchlib.interleaved({k: gph.replay for k, gph in graphs.items()}, a.trials, a.reps)
             rows.append({"arch": name, "N": N, "size": S, "median_us": med, "trials_us": times,
                          "labels_equal_torch": agree, "kernel_over_torch": med["kernel"] / med["torch"],
                          "saved_us": med["torch"] - med["kernel"]})
@@ -135,13 +110,19 @@ def net(a, pkg, dev):
     return rows
 
 
+MODES = {"layer": dict(fn=layer, ns="1,8", trials=7, reps=20),
+         "net": dict(fn=net, ns="1,8", size=520, trials=5, reps=3),
+         "all": ["layer", "net"]}
+
+
 def run_all(a):
     """Each step in a fresh child process under its own time limit; the first that fails ends the run."""
     result = {"tool": "tools/resize_bench.py all"}
     with tempfile.TemporaryDirectory() as tmp:
-        for mode in ("layer", "net"):
+        for mode in MODES["all"]:
             part = os.path.join(tmp, mode + ".json")
-            cmd = [sys.executable, os.path.abspath(__file__), mode, part, "--ns", a.ns, "--size", str(a.size)]
+            cmd = [sys.executable, os.path.abspath(__file__), mode, part]
+            cmd += (["--ns", a.ns] if a.ns else []) + (["--size", str(a.size)] if a.size else [])
             subprocess.run(cmd, check=True, timeout=STEP_LIMIT_S[mode])
             with open(part) as f:
                 got = json.load(f)
@@ -151,27 +132,13 @@ def run_all(a):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["layer", "net", "all"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default="1,8")
-    ap.add_argument("--size", type=int, default=520)
-    ap.add_argument("--trials", type=int, default=None)
-    ap.add_argument("--reps", type=int, default=None)
-    a = ap.parse_args()
+    a = benchlib.parse(MODES)
     if a.mode == "all":
         result = run_all(a)
     else:
-        pkg = ge.load_package()
-        dev = torch.device("cuda:0")
-        result = {"tool": f"tools/resize_bench.py {a.mode}", "device": torch.cuda.get_device_name(0)}
-        fn, t, r = {"layer": (layer, 7, 20), "net": (net, 5, 3)}[a.mode]
-        a.trials, a.reps = a.trials or t, a.reps or r
-        result[a.mode] = {"trials": a.trials, "reps": a.reps, "rows": fn(a, pkg, dev)}
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(result, f, indent=1)
+        result = benchlib.header(f"tools/resize_bench.py {a.mode}")
+        result.update(benchlib.sections(a, MODES, benchlib.load_package(), torch.device("cuda:0")))
+    benchlib.write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -11,44 +11,13 @@ usage: python tools/resnet_bench.py stem [out.json] [--ns 1,32,128] [--trials 7]
        python tools/resnet_bench.py trace [--archs resnet18] [--ns 1] [--reps 20]
          eager forwards back to back -- run it under `rocprofv3 --kernel-trace --stats -- python ...` to see every
          launch of a forward, the stem's among them"""
-import argparse
-import json
 import os
-import statistics
-import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
-
-FLOP_PER_CLK = 256 * 4 * 64   # CUs x SIMDs x f32 MFMA FLOP per clock per SIMD
-
-
-def _time(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def _interleaved(variants, trials, reps, setups=None):
-    setups = setups or {}
-    for k, fn in variants.items():   # warm-up: plans, scratch, torch's algorithm choice
-        setups.get(k, lambda: None)()
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in variants}
-    for _ in range(trials):
-        for k, fn in variants.items():
-            setups.get(k, lambda: None)()   # outside the timed repetitions
-            times[k].append(_time(fn, reps))
-    return {k: statistics.median(v) for k, v in times.items()}, times
+import benchlib
+import torch
+import torch.nn.functional as F
+import torch_nets
+from benchlib import FLOP_PER_CLK
 
 
 def _stem_executed_flop(N, H, W, K, form):
@@ -62,7 +31,7 @@ def _stem_executed_flop(N, H, W, K, form):
 def stem(a, pkg, dev):
     rows = []
     L = pkg.lib()
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         H = W = 224
         K = 64
         g = torch.Generator().manual_seed(N)
@@ -98,7 +67,7 @@ def stem(a, pkg, dev):
         variants = {"stem_auto": run_stem, "stem_big": run_stem, "stem_small": run_stem, "torch": torch_stem}
         setups = {"stem_auto": form_knob(0), "stem_big": form_knob(1), "stem_small": form_knob(2),
                   "torch": form_knob(0)}
-        med, times = _interleaved(variants, a.trials, a.reps, setups)
+        med, times = benchlib.interleaved(variants, a.trials, a.reps, setups)
         form_knob(0)()
         run_stem()
         pkg.conv1x1_bn(A, B, ob, os_, False)
@@ -124,108 +93,36 @@ def stem(a, pkg, dev):
     return rows
 
 
-def random_state_dict(R, arch, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    sd = {}
-    for k, shape in R.expected_keys(arch, 1000).items():
-        if k.endswith(".weight") and len(shape) == 4:
-            sd[k] = torch.randn(shape, generator=g) * (2.0 / (shape[1] * shape[2] * shape[3])) ** 0.5
-        elif k.endswith("running_var"):
-            sd[k] = torch.rand(shape, generator=g) + 0.5
-        elif k == "fc.weight":
-            sd[k] = torch.randn(shape, generator=g) * (1.0 / shape[1]) ** 0.5
-        elif k.endswith(".weight"):
-            sd[k] = (torch.rand(shape, generator=g) + 0.5) * (0.2 if k.endswith(("bn3.weight",)) or
-                                                               (k.endswith("bn2.weight") and "layer" in k and
-                                                                not R.ARCHS[arch][0]) else 1.0)
-        else:
-            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
-    return sd
-
-
-class TorchNet:
-    """torch eager on channels-last fp32 with the same weights: conv, BN as scale and bias, ReLU, add."""
-
-    def __init__(self, R, sd, arch, dev, eps=1e-5):
-        self.bottleneck, self.blocks = R.ARCHS[arch]
-        self.w = {k: v.to(dev).contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.to(dev)
-                  for k, v in sd.items()}
-        self.bn = {}
-        for k in sd:
-            if k.endswith("running_var"):
-                p = k[: -len(".running_var")]
-                s = sd[p + ".weight"] / torch.sqrt(sd[k] + eps)
-                self.bn[p] = (s.to(dev)[None, :, None, None], (sd[p + ".bias"] - sd[p + ".running_mean"] * s)
-                              .to(dev)[None, :, None, None])
-
-    def _cb(self, t, conv, bn, stride=1, pad=0, relu=True):
-        s, b = self.bn[bn]
-        y = F.conv2d(t, self.w[conv], stride=stride, padding=pad) * s + b
-        return torch.relu(y) if relu else y
-
-    def __call__(self, x):
-        t = F.max_pool2d(self._cb(x, "conv1.weight", "bn1", 2, 3), 3, 2, 1)
-        for L, nb in enumerate(self.blocks, 1):
-            for b in range(nb):
-                p = f"layer{L}.{b}"
-                st = 2 if (b == 0 and L > 1) else 1
-                if self.bottleneck:
-                    y = self._cb(t, p + ".conv1.weight", p + ".bn1")
-                    y = self._cb(y, p + ".conv2.weight", p + ".bn2", st, 1)
-                    y = self._cb(y, p + ".conv3.weight", p + ".bn3", relu=False)
-                else:
-                    y = self._cb(t, p + ".conv1.weight", p + ".bn1", st, 1)
-                    y = self._cb(y, p + ".conv2.weight", p + ".bn2", 1, 1, relu=False)
-                sc = t
-                if p + ".downsample.0.weight" in self.w:
-                    sc = self._cb(t, p + ".downsample.0.weight", p + ".downsample.1", st, relu=False)
-                t = torch.relu(y + sc)
-        return F.linear(t.mean(dim=(2, 3)), self.w["fc.weight"], self.w["fc.bias"])
-
-
 def net(a, pkg, dev):
-    import importlib
-    R = importlib.import_module("cuda_winograd_amd.resnet")
+    R = benchlib.package_module("resnet")
     rows = []
     for arch in a.archs.split(","):
-        sd = random_state_dict(R, arch, seed=1)
+        sd = torch_nets.random_state_dict(R, arch, seed=1)
         model = pkg.ResNet.from_state_dict(sd, arch)
-        tnet = TorchNet(R, sd, arch, dev)
-        for N in (int(v) for v in a.ns.split(",")):
-            x = (torch.rand(N, 3, 224, 224, generator=torch.Generator().manual_seed(N)) * 2 - 1).to(dev)
-            x_cl = x.contiguous(memory_format=torch.channels_last)
-            sg = torch.cuda.Stream()
-            sg.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(sg):
-                model.prepare(N, 224, 224)
-                model(x)
-            sg.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=sg):
-                model(x)
-            torch.cuda.synchronize()
-            variants = {"eager": lambda: model(x), "graph": graph.replay, "torch": lambda: tnet(x_cl)}
-            med, times = _interleaved(variants, a.trials, a.reps)
+        body = torch_nets.TorchResNetBody(R, sd, arch, dev)
+        for N in benchlib.ints(a.ns):
+            x, x_cl = torch_nets.image_batch(N, 224, 224, dev)
+            graph, _ = benchlib.captured(lambda: model(x), lambda: model.prepare(N, 224, 224))
+            variants = benchlib.net_variants(lambda: model(x), graph,
+                                             lambda: torch_nets.classifier_head(body, body(x_cl)))
+            med, times = benchlib.interleaved(variants, a.trials, a.reps)
             gflop = model.flops() * N / 1e9
-            row = {"arch": arch, "N": N, "median_us": med, "trials_us": times, "gflop": gflop,
-                   "graph_over_eager": med["graph"] / med["eager"], "graph_over_torch": med["graph"] / med["torch"],
-                   "eager_over_torch": med["eager"] / med["torch"]}
+            row = {"arch": arch, "N": N, "median_us": med, "trials_us": times, "gflop": gflop, **benchlib.net_ratios(med)}
             rows.append(row)
             print(f"{arch:9s} N={N:4d}  eager {med['eager']:9.1f} us  graph {med['graph']:9.1f} us  torch "
                   f"{med['torch']:9.1f} us  graph/eager {row['graph_over_eager']:.3f}  graph/torch "
                   f"{row['graph_over_torch']:.3f}  ({gflop / med['graph'] * 1e3:.1f} TF/s algorithmic, replayed)", flush=True)
             del graph, x, x_cl
             torch.cuda.empty_cache()
-        del model, tnet
+        del model, body
     return rows
 
 
 def trace(a, pkg, dev):
-    import importlib
-    R = importlib.import_module("cuda_winograd_amd.resnet")
+    R = benchlib.package_module("resnet")
     for arch in a.archs.split(","):
-        model = pkg.ResNet.from_state_dict(random_state_dict(R, arch, seed=1), arch)
-        for N in (int(v) for v in a.ns.split(",")):
+        model = pkg.ResNet.from_state_dict(torch_nets.random_state_dict(R, arch, seed=1), arch)
+        for N in benchlib.ints(a.ns):
             x = (torch.rand(N, 3, 224, 224) * 2 - 1).to(dev)
             for _ in range(a.reps):
                 model(x)
@@ -233,33 +130,15 @@ def trace(a, pkg, dev):
             print(f"{arch} N={N}: {a.reps} eager forwards", flush=True)
 
 
+MODES = {"stem": dict(fn=stem, ns="1,32,128", trials=7, reps=20),
+         "net": dict(fn=net, archs="resnet18,resnet50", ns="1,32,128", trials=5, reps=5),
+         "trace": dict(fn=trace, archs="resnet18", ns="1", reps=20)}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["stem", "net", "trace"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default=None)
-    ap.add_argument("--archs", default=None)
-    ap.add_argument("--trials", type=int, default=None)
-    ap.add_argument("--reps", type=int, default=None)
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    if a.mode == "stem":
-        a.ns, a.trials, a.reps = a.ns or "1,32,128", a.trials or 7, a.reps or 20
-        rows = stem(a, pkg, dev)
-    elif a.mode == "net":
-        a.ns, a.archs = a.ns or "1,32,128", a.archs or "resnet18,resnet50"
-        a.trials, a.reps = a.trials or 5, a.reps or 5
-        rows = net(a, pkg, dev)
-    else:
-        a.ns, a.archs, a.reps = a.ns or "1", a.archs or "resnet18", a.reps or 20
-        trace(a, pkg, dev)
-        return
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump({"tool": f"tools/resnet_bench.py {a.mode}", "device": torch.cuda.get_device_name(0),
-                       "trials": a.trials, "reps": a.reps, "rows": rows}, f, indent=1)
+    benchlib.main_rows("tools/resnet_bench.py", MODES)
 
 
 if __name__ == "__main__":
     main()
+

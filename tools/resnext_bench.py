@@ -11,19 +11,11 @@ usage: python tools/resnext_bench.py layer [out.json] [--ns 128,1] [--trials 7] 
          channels-last fp32 with the same weights
        python tools/resnext_bench.py trace [--ns 128] [--reps 10]
          the seven layer points back to back -- run it under `rocprofv3 --kernel-trace --stats -- python ...`"""
-import argparse
-import importlib
-import json
-import os
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
-from resnet_bench import FLOP_PER_CLK, TorchNet, _interleaved, random_state_dict  # noqa: E402
+import benchlib
+import torch
+import torch.nn.functional as F
+import torch_nets
+from benchlib import FLOP_PER_CLK
 
 HBM_BYTES_PER_S = 6.3e12
 PEAK_CLOCK_HZ = 2.4e9
@@ -59,7 +51,7 @@ def _layer_tensors(pkg, dev, N, Hin, C, stride):
 
 def layer(a, pkg, dev):
     rows = []
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         for name, Hin, C, stride in POINTS:
             x, w, bias, scale, packed, out = _layer_tensors(pkg, dev, N, Hin, C, stride)
             # torch: the unpadded map as a channels-last NCHW view, pad = 1 inside the conv
@@ -73,7 +65,7 @@ def layer(a, pkg, dev):
             def torch_layer():
                 return torch.relu(F.conv2d(x_cl, w_cl, stride=stride, padding=1, groups=GROUPS) * sc + bs)
 
-            med, times = _interleaved({"grouped": mine, "torch": torch_layer}, a.trials, a.reps)
+            med, times = benchlib.interleaved({"grouped": mine, "torch": torch_layer}, a.trials, a.reps)
             hbm, mfma, alg = _floors(N, Hin, C, stride)
             t = med["grouped"] * 1e-6
             rows.append({"point": name, "N": N, "Hin": Hin, "C": C, "Cg": C // GROUPS, "stride": stride,
@@ -88,53 +80,33 @@ def layer(a, pkg, dev):
     return rows
 
 
-class TorchNetGrouped(TorchNet):
-    """resnet_bench's torch eager network with the groups of every conv read off its weight."""
-
-    def _cb(self, t, conv, bn, stride=1, pad=0, relu=True):
-        s, b = self.bn[bn]
-        w = self.w[conv]
-        y = F.conv2d(t, w, stride=stride, padding=pad, groups=t.shape[1] // w.shape[1]) * s + b
-        return torch.relu(y) if relu else y
-
-
 def net(a, pkg, dev):
-    R = importlib.import_module("cuda_winograd_amd.resnet")
+    R = benchlib.package_module("resnet")
     rows = []
     for arch in a.archs.split(","):
-        sd = random_state_dict(R, arch, seed=1)
+        sd = torch_nets.random_state_dict(R, arch, seed=1)
         model = pkg.ResNet.from_state_dict(sd, arch)
-        tnet = TorchNetGrouped(R, sd, arch, dev)
-        for N in (int(v) for v in a.ns.split(",")):
-            x = (torch.rand(N, 3, 224, 224, generator=torch.Generator().manual_seed(N)) * 2 - 1).to(dev)
-            x_cl = x.contiguous(memory_format=torch.channels_last)
-            sg = torch.cuda.Stream()
-            sg.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(sg):
-                model.prepare(N, 224, 224)
-                model(x)
-            sg.synchronize()
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=sg):
-                model(x)
-            torch.cuda.synchronize()
-            variants = {"eager": lambda: model(x), "graph": graph.replay, "torch": lambda: tnet(x_cl)}
-            med, times = _interleaved(variants, a.trials, a.reps)
+        body = torch_nets.TorchResNetBody(R, sd, arch, dev)
+        for N in benchlib.ints(a.ns):
+            x, x_cl = torch_nets.image_batch(N, 224, 224, dev)
+            graph, _ = benchlib.captured(lambda: model(x), lambda: model.prepare(N, 224, 224))
+            variants = benchlib.net_variants(lambda: model(x), graph,
+                                             lambda: torch_nets.classifier_head(body, body(x_cl)))
+            med, times = benchlib.interleaved(variants, a.trials, a.reps)
             gflop = model.flops() * N / 1e9
             rows.append({"arch": arch, "N": N, "median_us": med, "trials_us": times, "gflop": gflop,
-                         "graph_over_eager": med["graph"] / med["eager"], "graph_over_torch": med["graph"] / med["torch"],
-                         "eager_over_torch": med["eager"] / med["torch"]})
+                         **benchlib.net_ratios(med)})
             print(f"{arch:16s} N={N:4d}  eager {med['eager']:9.1f} us  graph {med['graph']:9.1f} us  torch "
                   f"{med['torch']:9.1f} us  graph/torch {rows[-1]['graph_over_torch']:.3f}  eager/torch "
                   f"{rows[-1]['eager_over_torch']:.3f}  ({gflop / med['graph'] * 1e3:.1f} TF/s algorithmic, replayed)", flush=True)
             del graph, x, x_cl
             torch.cuda.empty_cache()
-        del model, tnet
+        del model, body
     return rows
 
 
 def trace(a, pkg, dev):
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         for name, Hin, C, stride in POINTS:
             x, w, bias, scale, packed, out = _layer_tensors(pkg, dev, N, Hin, C, stride)
             for _ in range(a.reps):
@@ -143,31 +115,13 @@ def trace(a, pkg, dev):
             print(f"{name} N={N}: {a.reps} launches", flush=True)
 
 
+MODES = {"layer": dict(fn=layer, ns="128,1", trials=7, reps=20),
+         "net": dict(fn=net, archs="resnext50_32x4d,wide_resnet50_2", ns="128,1", trials=5, reps=3),
+         "trace": dict(fn=trace, ns="128", reps=10)}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["layer", "net", "trace"])
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--ns", default=None)
-    ap.add_argument("--archs", default="resnext50_32x4d,wide_resnet50_2")
-    ap.add_argument("--trials", type=int, default=None)
-    ap.add_argument("--reps", type=int, default=None)
-    a = ap.parse_args()
-    pkg = ge.load_package()
-    dev = torch.device("cuda:0")
-    if a.mode == "layer":
-        a.ns, a.trials, a.reps = a.ns or "128,1", a.trials or 7, a.reps or 20
-        rows = layer(a, pkg, dev)
-    elif a.mode == "net":
-        a.ns, a.trials, a.reps = a.ns or "128,1", a.trials or 5, a.reps or 3
-        rows = net(a, pkg, dev)
-    else:
-        a.ns, a.reps = a.ns or "128", a.reps or 10
-        trace(a, pkg, dev)
-        return
-    if a.out:
-        with open(a.out, "w") as f:
-            json.dump({"tool": f"tools/resnext_bench.py {a.mode}", "device": torch.cuda.get_device_name(0),
-                       "trials": a.trials, "reps": a.reps, "rows": rows}, f, indent=1)
+    benchlib.main_rows("tools/resnext_bench.py", MODES)
 
 
 if __name__ == "__main__":

@@ -9,18 +9,8 @@ usage: python tools/roi_bench.py [profiles/roi/bench.json] [--trials 7] [--reps 
              whole forward eager against one-graph replay
     error    the torch-fp32 restatement against fp64 at the 200 x 336 level (why no tight claim is made for full-size maps)
 (median of the trials, events around `reps` calls)"""
-import argparse
-import json
-import os
-import sys
-
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
-import torch  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
-from resnet_bench import _interleaved  # noqa: E402
+import benchlib
+import torch
 
 HBM_GBS = 8000.0                        # bench.py's HBM_PEAK_GBS
 IMAGE, N, C = (800, 1344), 2, 256
@@ -81,21 +71,8 @@ def torch_roi_align(maps, rois, P, S, sels):
     return out
 
 
-def graph_of(fn, reps):
-    sg = torch.cuda.Stream()
-    sg.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(sg):   # one eager call on the capture stream: the library's scratch is per stream
-        fn()
-    sg.synchronize()
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g, stream=sg):
-        for _ in range(reps):
-            fn()
-    return g
-
-
 def kernel_rows(a, pkg, dev):
-    import roi_cases as rc
+    rc = benchlib.tests_module("roi_cases")
     rows = []
     g = torch.Generator().manual_seed(1)
     padded = [torch.zeros(N, h + 2, w + 2, C) for h, w in LEVEL_HW]
@@ -116,9 +93,9 @@ def kernel_rows(a, pkg, dev):
         ref = comp()
         diff = float((got - ref).abs().max() / ref.abs().max())
         variants = {"kernel": kern, "torch": comp}
-        med, times = _interleaved(variants, a.trials, a.reps)
-        graphs = {k: graph_of(fn, a.reps) for k, fn in variants.items()}
-        gmed, gtimes = _interleaved({k: gr.replay for k, gr in graphs.items()}, a.trials, 3)
+        med, times = benchlib.interleaved(variants, a.trials, a.reps)
+        graphs = {k: benchlib.captured(benchlib.repeated(fn, a.reps))[0] for k, fn in variants.items()}
+        gmed, gtimes = benchlib.interleaved({k: gr.replay for k, gr in graphs.items()}, a.trials, 3)
         gmed = {k: v / a.reps for k, v in gmed.items()}
         del graphs
         floor = out.numel() * 4.0 / HBM_GBS / 1e3     # us
@@ -136,7 +113,7 @@ def kernel_rows(a, pkg, dev):
 
 
 def head_rows(a, pkg, dev):
-    import roi_cases as rc
+    rc = benchlib.tests_module("roi_cases")
     rows = []
     classes, rep = 91, 1024
     box = pkg.BoxHead.from_state_dict(rc.box_head_state_dict(C, 7, rep, classes), in_channels=C, P=7)
@@ -161,9 +138,9 @@ def head_rows(a, pkg, dev):
         "box head": lambda: box(p7),
         "mask head": lambda: mask(p14),
     }
-    med, times = _interleaved(launches, a.trials, a.reps)
-    graphs = {k: graph_of(fn, a.reps) for k, fn in launches.items()}
-    gmed, _ = _interleaved({k: gr.replay for k, gr in graphs.items()}, a.trials, 3)
+    med, times = benchlib.interleaved(launches, a.trials, a.reps)
+    graphs = {k: benchlib.captured(benchlib.repeated(fn, a.reps))[0] for k, fn in launches.items()}
+    gmed, _ = benchlib.interleaved({k: gr.replay for k, gr in graphs.items()}, a.trials, 3)
     gmed = {k: v / a.reps for k, v in gmed.items()}
     del graphs
     for k in launches:
@@ -175,7 +152,7 @@ def head_rows(a, pkg, dev):
 def restatement_error():
     """torch fp32 against fp64 at the workload's finest level, 200 x 336, on the CPU (C = 8 is enough: the error is
     in the coordinates and weights)."""
-    import roi_cases as rc
+    rc = benchlib.tests_module("roi_cases")
     g = torch.Generator().manual_seed(3)
     fmap = torch.rand(N, 200, 336, 8, generator=g) - 0.5
     rois = make_boxes(300, 3, "cpu")
@@ -190,23 +167,19 @@ def restatement_error():
     return res
 
 
+MODES = {None: dict(trials=7, reps=10)}
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("out", nargs="?", default=None)
-    ap.add_argument("--trials", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=10)
-    a = ap.parse_args()
-    pkg = ge.load_package()
+    a = benchlib.parse(MODES)
+    pkg = benchlib.load_package()
     dev = torch.device("cuda:0")
-    result = {"tool": "tools/roi_bench.py", "device": torch.cuda.get_device_name(0), "trials": a.trials, "reps": a.reps,
-              "workload": {"N": N, "image": IMAGE, "C": C, "levels": LEVEL_HW}, "hbm_gbs": HBM_GBS}
+    result = benchlib.header("tools/roi_bench.py", trials=a.trials, reps=a.reps,
+                             workload={"N": N, "image": IMAGE, "C": C, "levels": LEVEL_HW}, hbm_gbs=HBM_GBS)
     result["kernel"] = kernel_rows(a, pkg, dev)
     result["heads"] = head_rows(a, pkg, dev)
     result["fp32_restatement_rel_err_200x336"] = restatement_error()
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            json.dump(result, f, indent=1)
+    benchlib.write_json(a.out, result)
 
 
 if __name__ == "__main__":

@@ -6,49 +6,21 @@ usage: python tools/vgg_bench.py [out.json] [--ns 128,1] [--trials 7] [--reps 20
          (b) VGG-16 (random weights) eager and replayed from one graph, against torch eager on channels-last tensors
              (F.conv2d + bias + relu + max_pool2d + linear).
        The default output is profiles/vgg/bench.json."""
-import argparse
-import importlib
-import json
 import os
-import statistics
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-import torch  # noqa: E402
-import torch.nn.functional as F  # noqa: E402
-
-import __graft_entry__ as ge  # noqa: E402
+import benchlib
+import torch
+import torch.nn.functional as F
+import torch_nets
 
 MARGIN = 1.02   # the pooled launch may not be slower than the plain launch alone beyond the box-to-box scatter
 SHAPES = [(224, 64, 64), (112, 128, 128), (56, 256, 256), (28, 512, 512), (14, 512, 512)]   # (H, C, K)
 
 
-def _time(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) * 1e3 / reps
-
-
-def _interleaved(variants, trials, reps):
-    for fn in variants.values():   # warm-up: plans, scratch, torch's algorithm choice
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
-    times = {k: [] for k in variants}
-    for _ in range(trials):
-        for k, fn in variants.items():
-            times[k].append(_time(fn, reps))
-    return {k: statistics.median(v) for k, v in times.items()}, times
-
-
 def layers(a, pkg, dev):
     rows = []
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         for H, C, K in SHAPES:
             g = torch.Generator(device=dev).manual_seed(N + H)
             x = torch.rand(N, H + 2, H + 2, C, device=dev, generator=g).sub_(0.5)
@@ -71,7 +43,7 @@ def layers(a, pkg, dev):
             def pooled():
                 pkg.conv3x3_bn_relu_pool(x, U, b, s, out=small)
 
-            med, times = _interleaved({"plain": plain, "plain_then_pool": plain_then_pool, "pooled": pooled},
+            med, times = benchlib.interleaved({"plain": plain, "plain_then_pool": plain_then_pool, "pooled": pooled},
                                       a.trials, a.reps)
             row = {"N": N, "H": H, "C": C, "K": K, "median_us": med, "trials_us": times,
                    "pooled_over_plain": med["pooled"] / med["plain"],
@@ -89,44 +61,18 @@ def layers(a, pkg, dev):
 
 
 def network(a, pkg, dev):
-    V = importlib.import_module("cuda_winograd_amd.vgg")
+    V = benchlib.package_module("vgg")
     g = torch.Generator().manual_seed(16)
-    sd = {}
-    for k, shape in V.expected_keys("vgg16", 1000, 4096).items():
-        fan = shape[1] * (9 if len(shape) == 4 else 1) if len(shape) > 1 else 1
-        sd[k] = torch.randn(shape, generator=g) * (2.0 / fan) ** 0.5 if len(shape) > 1 else torch.zeros(shape)
+    sd = torch_nets.vgg_state_dict(V, "vgg16", g)
     model = pkg.VGG.from_state_dict(sd, "vgg16")
-    convs = [(sd[f"features.{i}.weight"].to(dev).contiguous(memory_format=torch.channels_last),
-              sd[f"features.{i}.bias"].to(dev), pool) for i, _, _, pool in V.conv_layers("vgg16")]
-    fcs = [(sd[f"classifier.{i}.weight"].to(dev), sd[f"classifier.{i}.bias"].to(dev)) for i in (0, 3, 6)]
+    torch_eager = torch_nets.torch_vgg(sd, V, "vgg16", dev)
     rows = []
-    for N in (int(v) for v in a.ns.split(",")):
+    for N in benchlib.ints(a.ns):
         x = (torch.rand(N, 3, 224, 224, generator=g) * 2 - 1).to(dev)
         x_cl = x.contiguous(memory_format=torch.channels_last)
-        sg = torch.cuda.Stream()
-        with torch.cuda.stream(sg):
-            model.prepare(N, 224, 224)
-            model(x)
-        sg.synchronize()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, stream=sg):
-            model(x)
-
-        def torch_eager():
-            t = x_cl
-            for w, b, pool in convs:
-                t = torch.relu(F.conv2d(t, w, b, padding=1))
-                if pool:
-                    t = F.max_pool2d(t, 2, 2)
-            t = F.adaptive_avg_pool2d(t, (7, 7)).flatten(1)
-            for i, (w, b) in enumerate(fcs):
-                t = F.linear(t, w, b)
-                if i < 2:
-                    t = torch.relu(t)
-            return t
-
-        med, times = _interleaved({"eager": lambda: model(x), "graph": graph.replay, "torch": torch_eager},
-                                  a.trials, max(1, a.reps // 4))
+        graph, _ = benchlib.captured(lambda: model(x), lambda: model.prepare(N, 224, 224))
+        med, times = benchlib.interleaved(benchlib.net_variants(lambda: model(x), graph, lambda: torch_eager(x_cl)),
+                                          a.trials, max(1, a.reps // 4))
         rows.append({"arch": "vgg16", "N": N, "median_us": med, "trials_us": times,
                      "tflops_eager": model.flops() * N / med["eager"] / 1e6})
         print(f"vgg16 N={N:4d}: eager {med['eager']:10.1f} us  graph {med['graph']:10.1f} us  "
@@ -136,23 +82,18 @@ def network(a, pkg, dev):
     return rows
 
 
+MODES = {None: dict(ns="128,1", trials=7, reps=20)}
+EXTRA = [("--skip-net", dict(action="store_true"))]
+
+
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("out", nargs="?", default=os.path.join(ROOT, "profiles", "vgg", "bench.json"))
-    ap.add_argument("--ns", default="128,1")
-    ap.add_argument("--trials", type=int, default=7)
-    ap.add_argument("--reps", type=int, default=20)
-    ap.add_argument("--skip-net", action="store_true")
-    a = ap.parse_args()
-    pkg = ge.load_package()
+    a = benchlib.parse(MODES, EXTRA)
+    pkg = benchlib.load_package()
     dev = torch.device("cuda:0")
-    res = {"tool": "tools/vgg_bench.py", "device": torch.cuda.get_device_name(0), "trials": a.trials, "reps": a.reps,
-           "layers": layers(a, pkg, dev)}
+    res = benchlib.header("tools/vgg_bench.py", trials=a.trials, reps=a.reps, layers=layers(a, pkg, dev))
     if not a.skip_net:
         res["network"] = network(a, pkg, dev)
-    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-    with open(a.out, "w") as f:
-        json.dump(res, f, indent=1)
+    benchlib.write_json(a.out or os.path.join(benchlib.ROOT, "profiles", "vgg", "bench.json"), res)
     slow = [r for r in res["layers"] if not r["within_margin"]]
     if slow:
         print(f"{len(slow)} pooled shape(s) slower than the plain launch beyond the margin", flush=True)
