@@ -836,6 +836,122 @@ def multiscale_roi_align(features, boxes, image_size, P: int, sampling: int = 2,
                      canonical_level, out)
 
 
+BBOX_XFORM_CLIP = 4.135166556742356   # log(1000 / 16): torchvision's BoxCoder.bbox_xform_clip
+
+
+def _int32(t, shape, device, name: str) -> torch.Tensor:
+    """The caller's int32 output checked like _out, or a new one of `shape` on `device`."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.int32, device=device)
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous()
+            or tuple(t.shape) != tuple(shape)):
+        raise WinoError(f"{name} must be a contiguous int32 CUDA(HIP) tensor of shape {tuple(shape)}")
+    return t
+
+
+def box_decode(head, anchors, image_hw, A: int, weights=(1.0, 1.0, 1.0, 1.0), grid=None, delta_col: int = 0,
+               score_col=None, out_boxes=None, out_scores=None, out_offset: int = 0, clamp: float = BBOX_XFORM_CLIP):
+    """torchvision's BoxCoder.decode_single + clip_boxes_to_image in one HIP launch, on a GEMM output read in place.
+    head [...][ld] float32 with N * rows_per_image rows: anchor a of a row has its deltas at columns delta_col + 4a .. + 3
+    and, with score_col given, its raw score at column score_col + a.  image_hw [N][2] float32 (H, W) per image.
+    grid=(h, w, stride_y, stride_x): anchors is [A][4] base anchors and row (n, y, x) of the h x w level takes base[a]
+    shifted by (x stride_x, y stride_y), torchvision's AnchorGenerator; grid=None: anchors is [rows][4], one box per row
+    for every a (the second stage, a = class).  Returns (boxes [N][total][4], scores [N][total] or None); this call
+    writes [:, out_offset : out_offset + rows_per_image * A] of them, in the order (row, a).  Given out_boxes /
+    out_scores may be wider than that (a level's slice of all levels' proposals); new ones are exactly that wide.
+    No scratch: capturable into a graph without a prepare."""
+    h = _dev(head, "head")
+    hw = _dev(image_hw, "image_hw")
+    anc = _dev(anchors, "anchors")
+    A, off = int(A), int(out_offset)
+    if h.dim() < 2 or hw.dim() != 2 or int(hw.shape[1]) != 2:
+        raise WinoError("head must be [...][ld] and image_hw [N][2]")
+    ld, N = int(h.shape[-1]), int(hw.shape[0])
+    rows = h.numel() // ld if ld else 0
+    if N < 1 or A < 1 or rows % N or off < 0:
+        raise WinoError(f"box_decode: {rows} rows for N={N} images, A={A}, out_offset={off}")
+    rpi = rows // N
+    if grid is None:
+        gh = gw = sy = sx = 0
+        want = (rows, 4)
+    else:
+        gh, gw, sy, sx = (int(v) for v in grid)
+        want = (A, 4)
+        if gh * gw != rpi:
+            raise WinoError(f"box_decode: grid {gh}x{gw} but {rpi} rows per image")
+    if tuple(anc.shape) != want:
+        raise WinoError(f"anchors must have shape {want}, got {tuple(anc.shape)}")
+    wx, wy, ww, wh = (float(v) for v in weights)
+    per_image = rpi * A
+
+    def slot(t, tail, name):
+        if t is None:
+            if off:
+                raise WinoError(f"out_offset={off} needs {name}")
+            return torch.empty((N, per_image) + tail, dtype=torch.float32, device=h.device)
+        _out(t, None, name)
+        if t.dim() != 2 + len(tail) or int(t.shape[0]) != N or tuple(t.shape[2:]) != tail or int(t.shape[1]) < off + per_image:
+            raise WinoError(f"{name} must be [{N}][total >= {off + per_image}]{list(tail)}, got {tuple(t.shape)}")
+        return t
+
+    boxes = slot(out_boxes, (4,), "out_boxes")
+    scores = None if score_col is None else slot(out_scores, (), "out_scores")
+    _on_current_device(h, hw, anc, boxes, scores)
+    _check(lib().wino_box_decode_hw(h.data_ptr() or None, N, rpi, ld, A, int(delta_col),
+                                    -1 if score_col is None else int(score_col), anc.data_ptr() or None, gh, gw, sy, sx,
+                                    hw.data_ptr(), wx, wy, ww, wh, float(clamp), boxes.data_ptr() or None,
+                                    int(boxes.shape[1]), off, None if scores is None else (scores.data_ptr() or None),
+                                    0 if scores is None else int(scores.shape[1]), off, _stream()), "wino_box_decode_hw")
+    return boxes, scores
+
+
+def nms_workspace_bytes(S: int, R: int) -> int:
+    """Bytes of batched_nms's workspace, the formula of winograd_mi355x.h (wino_batched_nms_hw refuses less): the
+    suppression bit matrix, R rows of ceil(R / 64) 64-bit words per segment."""
+    S, R = int(S), int(R)
+    if S < 1 or R < 1:
+        return 0
+    return S * R * ((R + 63) // 64) * 8
+
+
+def batched_nms(boxes, scores=None, groups=None, iou_thresh: float = 0.5, min_size: float = 0.0,
+                score_thresh: float = float("-inf"), max_out=None, rois_out=False, workspace=None, keep=None, count=None):
+    """Greedy NMS over S independent segments of R boxes in two HIP launches, never leaving the device, with fixed-size
+    outputs.  boxes [S][R][4] float32, already in priority order (the caller sorts; ties are the caller's too); scores
+    [S][R] float32 or None; groups [S][R] int32 or None (boxes of different groups never suppress each other).  A box is
+    a candidate when both sides are >= min_size and its score >= score_thresh; the first max_out (default R) candidates
+    that no kept box of their group overlaps by IoU > iou_thresh are kept.  Returns (keep [S][max_out] int32: the kept
+    indices ascending, then -1; count [S] int32[; rois [S][max_out][5] = (segment, box), padding rows (-1, 0, 0, 0, 0):
+    roi_align's input]).  rois_out: True, or the tensor to write.  workspace: nms_workspace_bytes(S, R) bytes.  No
+    scratch of the library's: capturable into a graph without a prepare."""
+    b = _dev(boxes, "boxes")
+    if b.dim() != 3 or int(b.shape[2]) != 4:
+        raise WinoError("boxes must be [S][R][4]")
+    S, R = int(b.shape[0]), int(b.shape[1])
+    sc = None if scores is None else _dev(scores, "scores")
+    if sc is not None and tuple(sc.shape) != (S, R):
+        raise WinoError(f"scores must be [{S}][{R}]")
+    g = None if groups is None else _int32(groups, (S, R), b.device, "groups")
+    max_out = max(R, 1) if max_out is None else int(max_out)
+    if max_out < 1:
+        raise WinoError(f"batched_nms: max_out={max_out}")
+    keep = _int32(keep, (S, max_out), b.device, "keep")
+    count = _int32(count, (S,), b.device, "count")
+    rois = None
+    if rois_out is not False and rois_out is not None:
+        rois = _output(None if rois_out is True else rois_out, (S, max_out, 5), b.device, "rois_out")
+    ws = _workspace(workspace, nms_workspace_bytes(S, R), b.device)
+    _on_current_device(b, sc, g, keep, count, rois, ws)
+    if R == 0 and rois is not None and S > 0:   # the library launches nothing: every row is a padding row
+        rois.zero_()
+        rois[:, :, 0] = -1.0
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    _check(lib().wino_batched_nms_hw(ptr(b), ptr(sc), ptr(g), S, R, float(iou_thresh), float(min_size),
+                                     float(score_thresh), max_out, ptr(keep), ptr(count), ptr(rois), ptr(ws),
+                                     ws.numel() * 4, _stream()), "wino_batched_nms_hw")
+    return (keep, count) if rois is None else (keep, count, rois)
+
+
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
     """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
     bounds by the kernel)."""
@@ -1266,4 +1382,4 @@ from .resnet import ResNet  # noqa: E402  (whole networks on the operators above
 from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
-from .detection import BoxHead, MaskHead  # noqa: E402
+from .detection import BoxHead, MaskHead, RPN, FasterRCNN  # noqa: E402

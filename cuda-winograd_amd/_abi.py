@@ -174,6 +174,9 @@ SIGNATURES = {
     # ---- multi-scale RoIAlign
     "wino_roi_align_hw": (i, [vp] * 4 + [ip, fptr] + [i] * 4 + [vp] + [i] * 3 + [c_float, i, vp, i, vp]),
     "wino_roi_align_launches": (i, [i] * 3 + [POINTER(c_long)]),
+    # ---- box decoding and batched NMS
+    "wino_box_decode_hw": (i, [vp] + [i] * 6 + [vp] + [i] * 4 + [vp] + [c_float] * 5 + [vp, c_long, c_long] * 2 + [vp]),
+    "wino_batched_nms_hw": (i, [vp] * 3 + [i] * 2 + [c_float] * 3 + [i] + [vp] * 4 + [sz, vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

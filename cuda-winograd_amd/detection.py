@@ -1,4 +1,4 @@
-"""The second stage of torchvision's Faster / Mask R-CNN on the library's kernels: what follows ``MultiScaleRoIAlign``
+"""torchvision's Faster / Mask R-CNN on the library's kernels.  The second stage: what follows ``MultiScaleRoIAlign``
 (``multiscale_roi_align``, the one new kernel) runs on layers the library already has.
 
 ``BoxHead.from_state_dict(sd)`` is ``TwoMLPHead`` + ``FastRCNNPredictor`` under the key names they have below
@@ -23,8 +23,25 @@ tiled four times.  Its output ``[R*P*P][4C]`` is the same memory as ``[R*P*P*4][
 in which order the pixels come, so that view is its A matrix as it stands; the order is undone once, on the small
 ``classes``-channel result, by a view + permute + copy in torch: ``[R][P][P][2][2][classes] -> [R][classes][P][2][P][2]``.
 
-Not built: the RPN, box decoding, NMS, the post-processing (softmax / sigmoid, the selection of the predicted class's
-mask, the paste into the image) and the BN variants of the v2 heads.  Boxes come from the caller.
+The first stage and the detector.  ``RPN.from_state_dict(sd)`` takes the keys below torchvision's ``rpn.``
+(``head.conv.0.0.weight|bias``, or the legacy ``head.conv.weight|bias``; ``head.cls_logits`` [A][C][1][1]; ``head.bbox_pred``
+[4A][C][1][1]), packs the two 1x1s like ``pack_predictor`` into one GEMM of 5A columns padded to 64 (objectness 0..A, deltas
+A..5A) and runs per level ``conv3x3_bn_relu`` -> ``conv1x1_bn_ex(A_PADDED)`` -> ``box_decode`` in grid mode (base anchors
+computed on the host in float32 as AnchorGenerator does; strides image // grid; "pool" copied once into a zero-ring
+tensor), then ``filter_proposals`` with torch as plumbing: per-level ``topk`` on the logits, ``gather``, one stable
+descending ``sort`` per image on the logit (the order of the probabilities wherever they differ, ties to the lower
+index), ``sigmoid``, and ``batched_nms`` with groups = level.  ``postprocess_detections`` is softmax, ``box_decode`` in
+boxes mode straight on the box head's GEMM output, class 0 dropped, padding rows' scores 0, per image the ``topk`` of at
+most ``max_candidates`` (default min(all, 8192)), ``batched_nms`` with groups = label and score_thresh =
+nextafter(0.05) (torchvision's strict >).  Named deviation: the result is torchvision's whenever at most
+``max_candidates`` scores of an image pass the threshold; ``overflow`` [N] says when more did.
+``FasterRCNN.from_state_dict(sd, arch)`` (``backbone.body.*``, ``backbone.fpn.*``, ``rpn.*``, ``roi_heads.box_head.*``,
+``roi_heads.box_predictor.*``) composes ResNetFPN(padded) -> RPN -> multiscale_roi_align -> BoxHead -> postprocess; after
+``prepare(N, H, W)`` a forward reads no device data on the host and is captured into one graph.
+
+Not built: ``GeneralizedRCNNTransform`` (resize / normalise / batching) and the mapping of boxes back to original image
+sizes, Mask R-CNN's mask selection and paste, a select / sort kernel (torch's ``topk`` / ``sort`` stay), Keypoint R-CNN,
+RetinaNet and the BN variants of the v2 heads.
 
 The key names above are written from memory of torchvision's source and have not been checked against an installed
 torchvision; the tests build their own state dicts under these names.
@@ -262,5 +279,282 @@ class MaskHead(Net):
         return self._masks
 
 
-__all__ = ["BoxHead", "MaskHead", "expected_box_head_keys", "expected_mask_head_keys", "validate_box_head_state_dict",
+# ---- the first stage ---------------------------------------------------------------------------------------------------
+ANCHOR_SIZES = ((32,), (64,), (128,), (256,), (512,))
+ANCHOR_RATIOS = (0.5, 1.0, 2.0)
+RPN_LEVELS = ("0", "1", "2", "3", "pool")
+BOX_WEIGHTS = (10.0, 10.0, 5.0, 5.0)
+SCORE_THRESH_STRICT = 0.05000000447034836   # nextafter(float32(0.05), inf): torchvision keeps score > 0.05
+
+
+def base_anchors(sizes, ratios) -> torch.Tensor:
+    """torchvision's AnchorGenerator.generate_anchors on the host in float32: h_r = sqrt(ratio), w_r = 1 / h_r,
+    round([-w, -h, w, h] / 2), ratio-major: [len(ratios) * len(sizes)][4]."""
+    scales = torch.as_tensor(sizes, dtype=torch.float32)
+    ar = torch.as_tensor(ratios, dtype=torch.float32)
+    h_r = torch.sqrt(ar)
+    w_r = 1 / h_r
+    ws = (w_r[:, None] * scales[None, :]).view(-1)
+    hs = (h_r[:, None] * scales[None, :]).view(-1)
+    return (torch.stack([-ws, -hs, ws, hs], dim=1) / 2).round()
+
+
+def pack_rpn_head(cls_w, cls_b, box_w, box_b):
+    """cls_logits [A][C][1][1] and bbox_pred [4A][C][1][1] -> (B [C][kp], bias [kp]) of one GEMM, like pack_predictor:
+    objectness at columns 0..A, deltas at A..5A, the rest (kp = 5A up to a multiple of 64) zero."""
+    A, C = int(cls_w.shape[0]), int(cls_w.shape[1])
+    return pack_predictor(cls_w.reshape(A, C), cls_b, box_w.reshape(4 * A, C), box_b)
+
+
+def expected_rpn_keys(sd, in_channels: int, A: int):
+    """{key: shape} of torchvision's RPNHead below `rpn.`; the legacy spelling head.conv.weight|bias is accepted."""
+    conv = "head.conv" if "head.conv.weight" in sd else "head.conv.0.0"
+    C = in_channels
+    return {f"{conv}.weight": (C, C, 3, 3), f"{conv}.bias": (C,), "head.cls_logits.weight": (A, C, 1, 1),
+            "head.cls_logits.bias": (A,), "head.bbox_pred.weight": (4 * A, C, 1, 1), "head.bbox_pred.bias": (4 * A,)}
+
+
+class RPN(Net):
+    """torchvision's RegionProposalNetwork at test time: RPNHead (one Winograd 3x3 and one 1x1 GEMM per level),
+    box_decode in grid mode per level, and filter_proposals with torch as plumbing (topk, gather, sigmoid, sort) around
+    batched_nms.  No host read of device data after prepare()."""
+
+    def __init__(self, in_channels, sizes, ratios, pre_nms_top_n, post_nms_top_n, nms_thresh, score_thresh, min_size, device):
+        super().__init__(device)
+        self.in_channels, self.sizes, self.ratios = int(in_channels), tuple(tuple(s) for s in sizes), tuple(ratios)
+        self.A = len(self.sizes[0]) * len(self.ratios)
+        self.pre, self.post = int(pre_nms_top_n), int(post_nms_top_n)
+        self.nms_thresh, self.score_thresh, self.min_size = float(nms_thresh), float(score_thresh), float(min_size)
+
+    @classmethod
+    def from_state_dict(cls, sd, in_channels: int = 256, sizes=ANCHOR_SIZES, ratios=ANCHOR_RATIOS, pre_nms_top_n: int = 1000,
+                        post_nms_top_n: int = 1000, nms_thresh: float = 0.7, score_thresh: float = 0.0,
+                        min_size: float = 1e-3, device=None) -> "RPN":
+        """sd: the keys below torchvision's `rpn.` (head.conv.0.0, head.cls_logits, head.bbox_pred)."""
+        if len(sizes) != len(RPN_LEVELS) or len({len(s) for s in sizes}) != 1:
+            raise WinoError(f"rpn: {len(RPN_LEVELS)} levels need {len(RPN_LEVELS)} size tuples of one length")
+        A = len(sizes[0]) * len(ratios)
+        check_state_dict(sd, expected_rpn_keys(sd, int(in_channels), A), "the RPN head", "weight")
+        if in_channels < 64 or in_channels % 64:
+            raise WinoError(f"rpn: in_channels={in_channels} must be a multiple of 64")
+        if min(int(pre_nms_top_n), int(post_nms_top_n)) < 1:
+            raise WinoError("rpn: pre_nms_top_n and post_nms_top_n must be at least 1")
+        return cls._load(sd, None, device, in_channels, sizes, ratios, pre_nms_top_n, post_nms_top_n, nms_thresh,
+                         score_thresh, min_size)
+
+    def _pack(self, sd, eps):
+        conv = "head.conv" if "head.conv.weight" in sd else "head.conv.0.0"
+        self.U = filter_transform_f2(self._t(sd[f"{conv}.weight"]))
+        self.bc = self._t(sd[f"{conv}.bias"])
+        wp, bp = pack_rpn_head(sd["head.cls_logits.weight"], sd["head.cls_logits.bias"], sd["head.bbox_pred.weight"],
+                               sd["head.bbox_pred.bias"])
+        self.wp, self.bp = self._t(wp), self._t(bp)
+        self.base = [self._t(base_anchors(s, self.ratios)) for s in self.sizes]
+        self._ones = torch.ones(max(self.in_channels, int(self.wp.shape[1])), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+
+    def prepare(self, N: int, level_hw, image_size) -> None:
+        """Allocate every tensor of the first stage for N images whose five levels are `level_hw` [(h, w)] and reserve
+        the launches' stream scratch on the current stream.  Call it before capturing a forward into a graph."""
+        from . import nms_workspace_bytes
+        N, C, kp, dev, f32 = int(N), self.in_channels, int(self.wp.shape[1]), self.device, torch.float32
+        level_hw = [(int(h), int(w)) for h, w in level_hw]
+        H, W = int(image_size[0]), int(image_size[1])
+        if len(level_hw) != len(RPN_LEVELS):
+            raise WinoError(f"rpn: {len(RPN_LEVELS)} levels, got {len(level_hw)}")
+        with torch.cuda.device(dev):
+            self._t3 = [torch.zeros((N, h + 2, w + 2, C), dtype=f32, device=dev) for h, w in level_hw]
+            self._head = [torch.empty((N * h * w, kp), dtype=f32, device=dev) for h, w in level_hw]
+            ph, pw = level_hw[-1]
+            self._pool = torch.zeros((N, ph + 2, pw + 2, C), dtype=f32, device=dev)
+            self._n = [h * w * self.A for h, w in level_hw]
+            self._k = [min(self.pre, n) for n in self._n]
+            total, K = sum(self._n), sum(self._k)
+            self._boxes = torch.empty((N, total, 4), dtype=f32, device=dev)
+            self._logits = torch.empty((N, total), dtype=f32, device=dev)
+            self._level_of = torch.cat([torch.full((k,), l, dtype=torch.int32) for l, k in enumerate(self._k)]).to(dev)
+            self._keep = torch.empty((N, self.post), dtype=torch.int32, device=dev)
+            self._count = torch.empty((N,), dtype=torch.int32, device=dev)
+            self._rois = torch.empty((N, self.post, 5), dtype=f32, device=dev)
+            self._ws = torch.empty((nms_workspace_bytes(N, K) + 3) // 4, dtype=f32, device=dev)
+            for h, w in level_hw:
+                conv3x3_prepare(N, C, C, h, w)
+                conv1x1_prepare(N * h * w, C, kp)
+        self._grid = [(h, w, H // h, W // w) for h, w in level_hw]
+        self._shape = (N, tuple(level_hw), (H, W))
+
+    def forward(self, features, image_hw: torch.Tensor, image_size, stages=None):
+        """features: ResNetFPN(...)(x, padded=True); image_hw [N][2] float32 on the device (the clip sizes); image_size
+        (H, W) of the batch.  Returns (rois [N * post][5] with padding rows of index -1, scores [N][post], count [N]):
+        tensors of the module's, valid until the next forward.  `stages`: a dict that receives every intermediate."""
+        from . import batched_nms, box_decode
+        maps = [features[k] for k in RPN_LEVELS]
+        N, C, kp, A = int(maps[0].shape[0]), self.in_channels, int(self.wp.shape[1]), self.A
+        level_hw = tuple((int(m.shape[1]) - 2, int(m.shape[2]) - 2) for m in maps[:-1]) + \
+            ((int(maps[-1].shape[1]), int(maps[-1].shape[2])),)
+        shape = (N, level_hw, (int(image_size[0]), int(image_size[1])))
+        if shape != self._shape:
+            self.prepare(N, level_hw, image_size)
+        with torch.cuda.device(self.device):
+            self._pool[:, 1:-1, 1:-1, :].copy_(maps[-1])   # "pool" is a strided view: once into a zero-ring tensor
+            maps[-1] = self._pool
+            off = 0
+            for l, x in enumerate(maps):
+                conv3x3_bn_relu(x, self.U, self.bc, self._ones[:C], relu=True, out=self._t3[l])
+                conv1x1_bn_ex(self._t3[l], self.wp, self.bp, self._ones[:kp], A_PADDED, out=self._head[l])
+                box_decode(self._head[l], self.base[l], image_hw, A, grid=self._grid[l], delta_col=A, score_col=0,
+                           out_boxes=self._boxes, out_scores=self._logits, out_offset=off)
+                off += self._n[l]
+            # filter_proposals: torch as plumbing
+            idx, off = [], 0
+            for n, k in zip(self._n, self._k):
+                idx.append(self._logits[:, off:off + n].topk(k, dim=1, sorted=True).indices + off)
+                off += n
+            idx = torch.cat(idx, dim=1)
+            logit = self._logits.gather(1, idx)
+            slogit, order = torch.sort(logit, dim=1, descending=True, stable=True)   # (by logit: the order of the probabilities)
+            sidx = idx.gather(1, order)
+            sboxes = self._boxes.gather(1, sidx[:, :, None].expand(-1, -1, 4)).contiguous()
+            slevel = self._level_of[order].contiguous()
+            prob = torch.sigmoid(slogit)
+            batched_nms(sboxes, prob, slevel, self.nms_thresh, self.min_size, self.score_thresh, self.post, self._rois,
+                        self._ws, self._keep, self._count)
+            kept = self._keep >= 0
+            scores = torch.where(kept, prob.gather(1, self._keep.clamp(min=0).long()), torch.zeros_like(prob[:, :1]))
+        if stages is not None:
+            stages.update(rpn_head=list(self._head), rpn_boxes=self._boxes, rpn_logits=self._logits, topk_idx=idx,
+                          sorted_boxes=sboxes, sorted_logits=slogit, sorted_scores=prob, sorted_levels=slevel,
+                          rpn_keep=self._keep, rpn_count=self._count, rois=self._rois, proposal_scores=scores)
+        return self._rois.view(N * self.post, 5), scores, self._count
+
+
+def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw: torch.Tensor, classes: int,
+                           score_thresh: float = SCORE_THRESH_STRICT, nms_thresh: float = 0.5, detections: int = 100,
+                           min_size: float = 1e-2, max_candidates=None, stages=None):
+    """torchvision's RoIHeads.postprocess_detections with fixed-size outputs and no host read.  head_out [R][kp]: BoxHead's
+    one GEMM output (class logits at 0..classes, deltas at classes..5*classes), R = N * per rows; rois [R][5] with padding
+    rows of index -1; image_hw [N][2].  softmax (torch), box_decode in boxes mode on head_out in place with weights
+    (10, 10, 5, 5), class 0 dropped, padding rows' scores 0, per image the top max_candidates (default min(all, 8192))
+    by score, batched_nms with groups = label.  score_thresh is >=: the default is nextafter(0.05), torchvision's strict >.
+    Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D] int64 (-1 past count), "count" [N], "overflow" [N]}.
+    Named deviation: the result equals torchvision's whenever at most max_candidates scores of an image pass the
+    threshold; overflow[n] (computed on the device) says when more did."""
+    from . import batched_nms, box_decode
+    N, R, classes = int(image_hw.shape[0]), int(rois.shape[0]), int(classes)
+    if classes < 2 or R % N or head_out.dim() != 2 or int(head_out.shape[0]) != R or int(head_out.shape[1]) < 5 * classes:
+        raise WinoError(f"postprocess_detections: head_out {tuple(head_out.shape)}, rois {tuple(rois.shape)}, N={N}, "
+                        f"classes={classes}")
+    per, fg = R // N, classes - 1
+    M = per * fg
+    kc = M if max_candidates is None else int(max_candidates)
+    kc = max(1, min(kc, M, 8192 if max_candidates is None else M))
+    prob = torch.softmax(head_out[:, :classes], dim=-1)
+    boxes, _ = box_decode(head_out, rois[:, 1:5].contiguous(), image_hw, classes, BOX_WEIGHTS, None, classes)
+    boxes = boxes.view(N, per, classes, 4)[:, :, 1:].reshape(N, M, 4)
+    valid = (rois[:, 0] >= 0).view(N, per, 1)
+    scores = (prob.view(N, per, classes)[:, :, 1:] * valid).reshape(N, M)
+    top = scores.topk(kc, dim=1, sorted=True)
+    cboxes = boxes.gather(1, top.indices[:, :, None].expand(-1, -1, 4)).contiguous()
+    clabels = (top.indices % fg + 1).to(torch.int32).contiguous()
+    cscores = top.values.contiguous()
+    overflow = (scores >= score_thresh).sum(dim=1) > kc
+    keep, count = batched_nms(cboxes, cscores, clabels, nms_thresh, min_size, score_thresh, int(detections))
+    kept = keep >= 0
+    at = keep.clamp(min=0).long()
+    out = {"boxes": cboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
+           "scores": cscores.gather(1, at) * kept,
+           "labels": torch.where(kept, clabels.gather(1, at).long(), torch.full_like(at, -1)),
+           "count": count, "overflow": overflow}
+    if stages is not None:
+        stages.update(class_prob=prob, class_boxes=boxes, class_scores=scores, cand_idx=top.indices, cand_boxes=cboxes,
+                      cand_scores=cscores, cand_labels=clabels, det_keep=keep)
+    return out
+
+
+class FasterRCNN(Net):
+    """torchvision's fasterrcnn_*_fpn at test time on the library's kernels: ResNetFPN(padded) -> RPN ->
+    multiscale_roi_align -> BoxHead -> postprocess_detections, on the already normalised batch.  Out of scope:
+    GeneralizedRCNNTransform (resize / normalise / batching) and the mapping of boxes back to original image sizes."""
+
+    def __init__(self, backbone, rpn, box_head, detections, score_thresh, nms_thresh, max_candidates, device):
+        super().__init__(device)
+        self.backbone, self.rpn, self.box_head = backbone, rpn, box_head
+        self.detections, self.score_thresh, self.nms_thresh = int(detections), float(score_thresh), float(nms_thresh)
+        self.max_candidates = max_candidates
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, P: int = 7, eps: float = 1e-5,
+                        rpn_pre_nms_top_n: int = 1000, rpn_post_nms_top_n: int = 1000, rpn_nms_thresh: float = 0.7,
+                        rpn_score_thresh: float = 0.0, box_score_thresh: float = SCORE_THRESH_STRICT,
+                        box_nms_thresh: float = 0.5, box_detections_per_img: int = 100, max_candidates=None, sizes=ANCHOR_SIZES,
+                        ratios=ANCHOR_RATIOS, device=None) -> "FasterRCNN":
+        """sd under torchvision's key names: backbone.body.*, backbone.fpn.*, rpn.*, roi_heads.box_head.*,
+        roi_heads.box_predictor.*; each part is validated with check_state_dict."""
+        from .fpn import ResNetFPN
+        parts = {"backbone.": {}, "rpn.": {}, "roi_heads.": {}}
+        for k, v in sd.items():
+            for prefix, part in parts.items():
+                if k.startswith(prefix):
+                    part[k[len(prefix):]] = v
+                    break
+            else:
+                raise WinoError(f"state dict: unexpected key {k!r} for Faster R-CNN")
+        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device)
+        rpn = RPN.from_state_dict(parts["rpn."], out_channels, sizes, ratios, rpn_pre_nms_top_n, rpn_post_nms_top_n,
+                                  rpn_nms_thresh, rpn_score_thresh, 1e-3, backbone.device)
+        box_head = BoxHead.from_state_dict(parts["roi_heads."], out_channels, P, backbone.device)
+        if num_classes is not None and int(num_classes) != box_head.classes:
+            raise WinoError(f"state dict has {box_head.classes} classes, num_classes={num_classes}")
+        return cls(backbone, rpn, box_head, box_detections_per_img, box_score_thresh, box_nms_thresh, max_candidates,
+                   backbone.device)
+
+    def prepare(self, N: int, H: int, W: int) -> None:
+        """Allocate everything for [N][3][H][W] inputs and reserve every launch's stream scratch on the current stream.
+        After it a forward performs no host read of device data, so it can be captured into one graph."""
+        N, H, W, dev = int(N), int(H), int(W), self.device
+        with torch.cuda.device(dev):
+            self.backbone.prepare(N, H, W)
+            p = self.backbone._p
+            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in p]
+            level_hw.append(((level_hw[-1][0] + 1) // 2, (level_hw[-1][1] + 1) // 2))
+            self.rpn.prepare(N, level_hw, (H, W))
+            R, bh = N * self.rpn.post, self.box_head
+            bh.prepare(R)
+            self._pooled = torch.empty((R, bh.P, bh.P, bh.in_channels), dtype=torch.float32, device=dev)
+            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=torch.float32, device=dev)
+        self._shape = (N, H, W)
+
+    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
+        """x [N][3][H][W] float32, already normalised; image_sizes: None (every image fills the batch) or a float32
+        device tensor [N][2] of (H_img, W_img).  Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D], "count" [N],
+        "overflow" [N]}, rows past count zero with label -1; with stages=True also every intermediate."""
+        from . import multiscale_roi_align
+        self._begin(x)
+        N, H, W = self._shape
+        st = {} if stages else None
+        hw = self._full_hw if image_sizes is None else image_sizes
+        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
+            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
+        with torch.cuda.device(self.device):
+            feats = self.backbone(x, padded=True)
+            rois, _, _ = self.rpn(feats, hw, (H, W), stages=st)
+            pooled = multiscale_roi_align(feats, rois, (H, W), self.box_head.P, 2, in_padded=True, out=self._pooled)
+            self.box_head(pooled)
+            out = postprocess_detections(self.box_head._scores, rois, hw, self.box_head.classes, self.score_thresh,
+                                         self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st)
+        if stages:
+            st.update(features=feats, pooled=pooled, head_out=self.box_head._scores)
+            out.update(st)
+        return out
+
+    @staticmethod
+    def to_lists(out):
+        """torchvision's list of {"boxes", "scores", "labels"} per image.  Synchronises (it reads count)."""
+        counts = out["count"].tolist()
+        return [{"boxes": out["boxes"][n, :c].clone(), "scores": out["scores"][n, :c].clone(),
+                 "labels": out["labels"][n, :c].clone()} for n, c in enumerate(counts)]
+
+
+__all__ = ["BoxHead", "MaskHead", "RPN", "FasterRCNN", "postprocess_detections", "base_anchors", "pack_rpn_head",
+           "expected_rpn_keys", "expected_box_head_keys", "expected_mask_head_keys", "validate_box_head_state_dict",
            "validate_mask_head_state_dict", "pack_fc6", "pack_predictor", "pack_deconv", "pack_logits"]

@@ -65,7 +65,8 @@ extern "C" {
  * wino_conv3x3_dilated_prepare_hw, wino_conv3x3_dilated_plan, wino_dilated_residual_block_hw,
  * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
- * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_roi_align_launches, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
+ * wino_roi_align_launches, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -788,6 +789,60 @@ int wino_roi_align_hw(const float* f0, const float* f1, const float* f2, const f
                       int sampling, float canonical_scale, int canonical_level, float* out, int out_padded,
                       wino_stream_t s);
 int wino_roi_align_launches(int R, int P, int out_padded, long* launches);
+
+/* ---- box decoding and batched non-maximum suppression (boxes.hip) --------------------------------
+ * wino_box_decode_hw: torchvision's BoxCoder.decode_single followed by clip_boxes_to_image, in fp32 operation by
+ * operation, on rows of a GEMM output read in place: one HIP launch, one thread and one 16-byte store per box.
+ *   head        DEVICE [N * rows_per_image][ld]; anchor a of a row has its four deltas at columns delta_col + 4 a .. + 3
+ *               and, when score_col >= 0, its score at column score_col + a
+ *   anchors     grid mode (grid_h, grid_w >= 1, grid_h * grid_w == rows_per_image): DEVICE [A][4] base anchors; row
+ *               (n, y, x) takes base[a] + (x stride_x, y stride_y, x stride_x, y stride_y), torchvision's AnchorGenerator
+ *               in the order (y, x, a), the row order of an NHWC head output.  boxes mode (grid_h == grid_w == 0):
+ *               DEVICE [N * rows_per_image][4], the same box for every a (the second stage, a = class)
+ *   image_hw    DEVICE [N][2] floats (H_img, W_img): the clip window of the row's own image
+ *   wx..wh      BoxCoder's weights; clamp: its bbox_xform_clip, log(1000 / 16) in torchvision
+ *   boxes       box (n, j, a), j the row within its image, is stored at boxes + 4 (n boxes_image_stride + boxes_offset +
+ *               j A + a): strides and offsets count boxes, so that a level writes its slice of an [N][total][4] tensor
+ *   scores      with score_col >= 0 the raw score column, no activation, at scores + n scores_image_stride +
+ *               scores_offset + j A + a; ignored (may be NULL) otherwise
+ * w = ax2 - ax1, h = ay2 - ay1, cx = ax1 + .5 w, cy = ay1 + .5 h;  dx = d0 / wx, dy = d1 / wy, dw = min(d2 / ww, clamp),
+ * dh = min(d3 / wh, clamp);  pcx = dx w + cx, pcy = dy h + cy, pw = exp(dw) w, ph = exp(dh) h;  box = (pcx - .5 pw,
+ * pcy - .5 ph, pcx + .5 pw, pcy + .5 ph) with x clamped to [0, W_img] and y to [0, H_img].  A NaN delta reaches the
+ * coordinates it feeds, as under torch.clamp, and no other box changes a bit.
+ * N, rows_per_image >= 0 (either 0: WINO_OK, nothing launched), ld, A >= 1, delta_col >= 0, delta_col + 4 A <= ld,
+ * score_col + A <= ld, strides >= 1 in grid mode, N rows_per_image A < 2^31, an image's rows_per_image A boxes between
+ * its offset and its image stride (WINO_E_SHAPE otherwise).  A NULL or not 16-byte-aligned pointer, a weight that is zero
+ * or not finite, a NaN clamp, or an output that overlaps an input or the other output is WINO_E_ARG.  No workspace and no
+ * stream scratch: the call can be captured into a graph as it is. */
+int wino_box_decode_hw(const float* head, int N, int rows_per_image, int ld, int A, int delta_col, int score_col,
+                       const float* anchors, int grid_h, int grid_w, int stride_y, int stride_x, const float* image_hw,
+                       float wx, float wy, float ww, float wh, float clamp, float* boxes, long boxes_image_stride,
+                       long boxes_offset, float* scores, long scores_image_stride, long scores_offset, wino_stream_t s);
+/* wino_batched_nms_hw: greedy non-maximum suppression over S independent segments of R boxes each, entirely on the
+ * device and with fixed-size outputs: two launches (the suppression bit matrix, then one workgroup per segment that
+ * walks it), no host read.  Priority is index order within a segment: the caller sorts, and that is part of the contract.
+ *   boxes       DEVICE [S][R][4] (x1, y1, x2, y2);  scores: DEVICE [S][R] or NULL;  groups: DEVICE [S][R] int32 or NULL
+ *   candidate(i) = x2 - x1 >= min_size && y2 - y1 >= min_size && (scores == NULL || score >= score_thresh); a NaN fails
+ *               every compare, so a box with a NaN coordinate or score is never kept and never suppresses
+ *   Walking i = 0 .. R - 1: a candidate that is not suppressed is kept; a kept box suppresses every later candidate j of
+ *   the same group with inter / (area_i + area_j - inter) > iou_thresh, inter = max(min(x2) - max(x1), 0) *
+ *   max(min(y2) - max(y1), 0), torchvision's form in fp32; the walk stops at max_out kept.
+ *   keep        DEVICE [S][max_out] int32: the kept indices, ascending, then -1
+ *   count       DEVICE [S] int32
+ *   rois_out    NULL, or DEVICE [S][max_out][5]: (float(segment), box) for kept rows, (-1, 0, 0, 0, 0) after them:
+ *               wino_roi_align_hw's rois as they stand (a row of index -1 pools zeros)
+ *   workspace   S * R * ceil(R / 64) * 8 bytes (the bit matrix: R rows of ceil(R / 64) 64-bit words per segment); its
+ *               contents before the call do not matter
+ * A segment never reads or writes another segment's data.  S >= 0, 0 <= R <= 32768, max_out >= 1, S ceil(R / 64) < 2^24
+ * (the mask kernel's workgroups; WINO_E_SHAPE otherwise).  S == 0 or R == 0 is WINO_OK and launches nothing; with R == 0
+ * and S > 0 count is zeroed and keep, when given, filled with -1 by memsets, and rois_out is NOT written (the Python
+ * wrapper fills it with padding rows).
+ * A NULL boxes / keep / count, a pointer that is not 16-byte aligned, a NaN threshold, a workspace that is too small, or
+ * an output (keep, count, rois_out, workspace) that overlaps an input or another output is WINO_E_ARG.  Every check
+ * comes before the first launch.  No stream scratch: the call can be captured into a graph as it is. */
+int wino_batched_nms_hw(const float* boxes, const float* scores, const int* groups, int S, int R, float iou_thresh,
+                        float min_size, float score_thresh, int max_out, int* keep, int* count, float* rois_out,
+                        void* workspace, size_t workspace_bytes, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
