@@ -30,7 +30,8 @@
 //   diagonal are not written, and what the scan reads of them it drops.  A workgroup of four waves takes one block of
 //   64 rows and four blocks of 64 columns; a lane owns a row, the wave's 64 column boxes are broadcast from LDS.
 //
-//   nms_scan_kernel, one workgroup of 1024 threads per segment, walks the 64-row blocks.  `removed` (one bit per box,
+//   nms_scan_kernel, one workgroup of 1024 threads per segment (at most 2^22 - 1 segments per launch, each launch told
+//   its first segment), walks the 64-row blocks.  `removed` (one bit per box,
 //   in LDS) starts as the complement of the candidate bits.  Per block b: every wave holds the block's diagonal word of
 //   row b 64 + lane in its lane and resolves the block in scalar registers (count trailing zeros of the live bits, read
 //   lane i's word, clear what it suppresses); wave 0 writes the kept rows' outputs from the boxes it holds by lane; then
@@ -53,6 +54,9 @@ typedef unsigned long long u64;
 constexpr int NMS_MAX_R = 32768;
 constexpr int NMS_MAX_WORDS = NMS_MAX_R / 64;
 constexpr int SCAN_THREADS = 1024;
+// HIP takes fewer than 2^32 threads along x, and the scan has one workgroup of SCAN_THREADS per segment: a launch of
+// 2^22 segments is refused, and a larger count wraps (S = 2^24 - 1 ran as 2^22 - 1 workgroups and reported no error)
+constexpr int SCAN_MAX_SEGMENTS = (1 << 22) - 1;
 constexpr int MASK_WAVES = 4;
 
 // ---- decode ----------------------------------------------------------------------------------------------------------------
@@ -115,6 +119,7 @@ struct NmsArgs {
   int* count;
   float* rois;
   int S, R, nb, max_out;
+  int s0;   // the scan launch's first segment (the mask kernel takes all S at once)
   float iou, min_size, score_thresh;
 };
 
@@ -168,7 +173,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void nms_scan_kernel(const NmsArgs a)
   constexpr bool TWO_SETS = RPT <= 16;   // (two sets of 32 64-bit words would not fit a thread's 128 registers)
   __shared__ u64 removed[NMS_MAX_WORDS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int s = blockIdx.x, R = a.R, nb = a.nb;
+  const int s = a.s0 + (int)blockIdx.x, R = a.R, nb = a.nb;
   const size_t seg = (size_t)s * (size_t)R;
   const u64* mask = a.mask + seg * (size_t)nb;
   const f32x4* boxes = a.boxes + seg;
@@ -268,8 +273,13 @@ __global__ __launch_bounds__(SCAN_THREADS) void nms_scan_kernel(const NmsArgs a)
 }
 
 template <int W>
-void launch_scan(const NmsArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL(nms_scan_kernel<W>, dim3((unsigned)a.S), dim3(SCAN_THREADS), 0, s, a);
+int launch_scan(NmsArgs a, hipStream_t s) {   // launches of at most SCAN_MAX_SEGMENTS segments, each from its own s0
+  for (a.s0 = 0; a.s0 < a.S; a.s0 += SCAN_MAX_SEGMENTS) {
+    const int n = a.S - a.s0 < SCAN_MAX_SEGMENTS ? a.S - a.s0 : SCAN_MAX_SEGMENTS;
+    hipLaunchKernelGGL(nms_scan_kernel<W>, dim3((unsigned)n), dim3(SCAN_THREADS), 0, s, a);
+    if (int rc = launch_status("nms_scan_kernel")) return rc;
+  }
+  return WINO_OK;
 }
 
 bool finite_nonzero(float v) { return std::isfinite(v) && v != 0.f; }
@@ -354,7 +364,8 @@ extern "C" int wino_batched_nms_hw(const float* boxes, const float* scores, cons
                                    float iou_thresh, float min_size, float score_thresh, int max_out, int* keep, int* count,
                                    float* rois_out, void* workspace, size_t workspace_bytes, wino_stream_t s) {
   const int nb = R > 0 ? (R + 63) / 64 : 0;
-  // S ceil(R / 64) workgroups of 256 threads: HIP refuses a launch of 2^32 threads or more along x
+  // S ceil(R / 64) workgroups of 256 threads: HIP takes fewer than 2^32 threads along x (the scan, one workgroup of 1024
+  // threads per segment, is cut into launches of at most SCAN_MAX_SEGMENTS)
   if (S < 0 || R < 0 || R > NMS_MAX_R || max_out < 1 || (long long)S * (nb > 0 ? nb : 1) >= (1ll << 24)) {
     set_error("batched_nms: unsupported shape S=%d R=%d max_out=%d (need S >= 0, 0 <= R <= %d, max_out >= 1, "
               "S ceil(R / 64) < 2^24)", S, R, max_out, NMS_MAX_R);
@@ -400,14 +411,13 @@ extern "C" int wino_batched_nms_hw(const float* boxes, const float* scores, cons
   NmsArgs a;
   a.boxes = (const f32x4*)boxes, a.scores = scores, a.groups = groups, a.mask = (u64*)workspace;
   a.keep = keep, a.count = count, a.rois = rois_out;
-  a.S = S, a.R = R, a.nb = nb, a.max_out = max_out;
+  a.S = S, a.R = R, a.nb = nb, a.max_out = max_out, a.s0 = 0;
   a.iou = iou_thresh, a.min_size = min_size, a.score_thresh = score_thresh;
   hipLaunchKernelGGL(nms_mask_kernel, dim3((unsigned)(S * nb), (unsigned)((nb + MASK_WAVES - 1) / MASK_WAVES)),
                      dim3(64 * MASK_WAVES), 0, (hipStream_t)s, a);
   if (int rc = launch_status("nms_mask_kernel")) return rc;
-  if (nb <= 64) launch_scan<64>(a, (hipStream_t)s);
-  else if (nb <= 128) launch_scan<128>(a, (hipStream_t)s);
-  else if (nb <= 256) launch_scan<256>(a, (hipStream_t)s);
-  else launch_scan<512>(a, (hipStream_t)s);
-  return launch_status("nms_scan_kernel");
+  if (nb <= 64) return launch_scan<64>(a, (hipStream_t)s);
+  if (nb <= 128) return launch_scan<128>(a, (hipStream_t)s);
+  if (nb <= 256) return launch_scan<256>(a, (hipStream_t)s);
+  return launch_scan<512>(a, (hipStream_t)s);
 }

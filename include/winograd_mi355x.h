@@ -820,7 +820,7 @@ int wino_box_decode_hw(const float* head, int N, int rows_per_image, int ld, int
                        long boxes_offset, float* scores, long scores_image_stride, long scores_offset, wino_stream_t s);
 /* wino_batched_nms_hw: greedy non-maximum suppression over S independent segments of R boxes each, entirely on the
  * device and with fixed-size outputs: two launches (the suppression bit matrix, then one workgroup per segment that
- * walks it), no host read.  Priority is index order within a segment: the caller sorts, and that is part of the contract.
+ * walks it; from S = 2^22 on the walk is cut into launches of at most 2^22 - 1 segments), no host read.  Priority is index order within a segment: the caller sorts, and that is part of the contract.
  *   boxes       DEVICE [S][R][4] (x1, y1, x2, y2);  scores: DEVICE [S][R] or NULL;  groups: DEVICE [S][R] int32 or NULL
  *   candidate(i) = x2 - x1 >= min_size && y2 - y1 >= min_size && (scores == NULL || score >= score_thresh); a NaN fails
  *               every compare, so a box with a NaN coordinate or score is never kept and never suppresses

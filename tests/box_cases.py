@@ -14,7 +14,12 @@ smallest margin of every decision it made, and the generator redraws a box whose
     the IoU decisions greedy NMS makes: a row that is not kept suppresses nothing;
   * size_margin(min_size): no side within 1e-4 + 1e-3 min_size of min_size;
   * SCORE_MARGIN: no score within 1e-6 of the threshold.
-At most REDRAW_CAP of a case's boxes may be redrawn (a generator that throws most draws away shapes its inputs)."""
+At most REDRAW_CAP of a case's boxes may be redrawn (a generator that throws most draws away shapes its inputs).
+A decision that is exact in both precisions needs no margin: an IoU that is NaN, infinite or exactly 0 or 1, and the
+sides of lattice boxes against an fp32 min_size.  EqualityCase is built of such decisions alone, with every compare at
+equality; SweepNmsCase mixes degenerate and infinite boxes into the clusters and keeps the margins under every
+combination of extreme thresholds; OffLatticeCase leaves the lattice; decode_sweep_cases() are 40 legal decode launches
+over the column layouts, grids, weights, clamps and image sizes the library accepts."""
 from __future__ import annotations
 
 import functools
@@ -43,7 +48,10 @@ def rel_err(got, want) -> float:
     assert np.array_equal(np.isnan(got), nan), "NaNs differ"
     if nan.all():
         return 0.0
-    return float(np.abs(got - want)[~nan].max() / np.abs(want[~nan]).max())
+    err, scale = float(np.abs(got - want)[~nan].max()), float(np.abs(want[~nan]).max())
+    if scale == 0.0:                      # an all-zero reference: only an all-zero result matches it
+        return 0.0 if err == 0.0 else INF
+    return err / scale
 
 
 # ---- anchors and decode ----------------------------------------------------------------------------------------------------
@@ -108,7 +116,7 @@ class DecodeCase:
         self.N, self.A, self.ld, self.grid, self.weights = N, A, ld, grid, tuple(float(v) for v in weights)
         self.rpi = grid[0] * grid[1] if grid else rows_per_image
         rows = N * self.rpi
-        self.delta_col, self.score_col = A, 0
+        self.delta_col, self.score_col, self.clamp = A, 0, CLIP
         assert 5 * A <= ld
         head = rng.uniform(-1, 1, (rows, ld))
         d = head[:, A:5 * A].reshape(rows, A, 4)
@@ -137,10 +145,13 @@ class DecodeCase:
 
     def reference(self, head=None, dtype=np.float64):
         return decode_reference(self.head if head is None else head, self.anchors, self.image_hw, self.A, self.weights,
-                                self.grid, self.delta_col, CLIP, dtype)
+                                self.grid, self.delta_col, self.clamp, dtype)
 
     def scores(self):
-        return self.head[:, :self.A].reshape(self.N, self.rpi * self.A)
+        """The score column as the kernel copies it, [N][rows_per_image * A]; None without one."""
+        if self.score_col is None:
+            return None
+        return self.head[:, self.score_col:self.score_col + self.A].reshape(self.N, self.rpi * self.A)
 
 
 GRID_SHAPES = ((1, 1), (3, 5), (13, 21))
@@ -158,6 +169,99 @@ def decode_case(index: int, boxes_mode: bool = False) -> DecodeCase:
     return DecodeCase(seed=100 * boxes_mode + index, **(BOX_MODE_CASES if boxes_mode else GRID_CASES)[index])
 
 
+# ---- decode: a sweep over the legal launches -----------------------------------------------------------------------------
+SWEEP_A = (1, 2, 3, 5, 12, 15, 91)
+SWEEP_WEIGHTS = ((1.0, 1.0, 1.0, 1.0), (10.0, 10.0, 5.0, 5.0), (-10.0, 10.0, -5.0, 5.0), (0.5, 0.25, 3.0, 7.0))
+SWEEP_CLAMPS = (CLIP, 0.0, -1.0, INF)
+SWEEP_HW = ("usual", "zero", "fractional", "nothing_clips")
+SWEEP_GRIDS = ((1, 1), (1, 40), (40, 1), (3, 5), (13, 21), (40, 40), (7, 1), (1, 9), (24, 17), (2, 2))
+SWEEP_STRIDES = ((8, 8), (16, 12), (1, 1), (1, 5), (4, 32))               # (stride_y, stride_x)
+SWEEP_SLICES = ((0, 0), (37, 11), (5, 0), (0, 3))                         # (out_offset, room behind)
+SWEEP_BOX_ROWS = (1, 255, 256, 257, 300)                                  # with A = 1, N = 1: total at the 256-thread block edge
+LAYOUTS = ("scores_deltas", "deltas_scores", "deltas_only", "gap_deltas", "scores_gap_deltas", "deltas_pad_scores",
+           "odd_everything")
+
+
+def decode_layout(kind: str, A: int):
+    """(ld, delta_col, score_col or None) of a named column layout: every legal relation of the three appears."""
+    pad64 = lambda n: -(-n // 64) * 64
+    return {"scores_deltas": (5 * A, A, 0),                       # the RPN's order, ld = 5A: delta_col + 4A == ld
+            "deltas_scores": (5 * A, 0, 4 * A),                   # deltas before the scores, score_col + A == ld
+            "deltas_only": (4 * A, 0, None),                      # ld = 4A, no score column
+            "gap_deltas": (4 * A + 1, 1, None),                   # ld = 4A + 1, delta_col no multiple of 4
+            "scores_gap_deltas": (5 * A + 3, A + 3, 0),           # ld = 5A + 3
+            "deltas_pad_scores": (pad64(5 * A + 2), 2, pad64(5 * A + 2) - A),
+            "odd_everything": (5 * A + 11, 7, 4 * A + 8)}[kind]    # scores after the deltas, room behind both
+
+
+def decode_sweep_specs():
+    """40 seeded legal launches, 30 in grid mode and 10 in boxes mode; tests/test_boxes_host.py asserts the pins."""
+    rng = np.random.RandomState(77)
+    pick = lambda seq: seq[rng.randint(len(seq))]
+    specs = []
+    for i in range(30):
+        A, (gh, gw) = SWEEP_A[i % 7], SWEEP_GRIDS[i % 10]
+        ld, delta_col, score_col = decode_layout(LAYOUTS[(i + i // 7) % 7], A)
+        specs.append(dict(N=1 + i % 4, A=A, ld=ld, delta_col=delta_col, score_col=score_col,
+                          grid=(gh, gw) + SWEEP_STRIDES[(i + i // 5) % 5], rows_per_image=None,
+                          weights=SWEEP_WEIGHTS[(i + i // 4) % 4], clamp=pick(SWEEP_CLAMPS), hw=SWEEP_HW[(i + i // 8) % 4],
+                          slice=pick(SWEEP_SLICES)))
+    for i in range(10):
+        edge = i < 5
+        A = 1 if edge else SWEEP_A[(2 * i) % 7]
+        ld, delta_col, score_col = decode_layout(LAYOUTS[(3 * i + 1) % 7], A)
+        specs.append(dict(N=1 if edge else 2 + i % 3, A=A, ld=ld, delta_col=delta_col, score_col=score_col, grid=None,
+                          rows_per_image=SWEEP_BOX_ROWS[i % 5] if edge else (1, 63, 65, 300, 17)[i % 5],
+                          weights=SWEEP_WEIGHTS[(i + 1) % 4], clamp=SWEEP_CLAMPS[(i + i // 4) % 4], hw=SWEEP_HW[(i + i // 3) % 4],
+                          slice=pick(SWEEP_SLICES)))
+    return specs
+
+
+class DecodeSweepCase(DecodeCase):
+    """One launch of decode_sweep_specs().  dx, dy in +-0.5 and dw, dh in +-1 of a side, 6 % of dw / dh between the
+    default clamp and twice it (exp stays below e^8.3 = 3900 whatever the clamp; none where nothing is to clip, so that
+    one huge box does not set the scale of the error), all times the weights; every other column is noise.  Base anchors
+    are lattice boxes around the origin.  image_hw: "usual" cuts through the boxes, "zero" clips every box to 0,
+    "fractional" is the usual plus (0.5, 0.25), "nothing_clips" is larger than every box."""
+
+    def __init__(self, spec, seed):
+        rng = np.random.RandomState(seed)
+        N, A, ld, grid = spec["N"], spec["A"], spec["ld"], spec["grid"]
+        self.spec, self.N, self.A, self.ld, self.grid = spec, N, A, ld, grid
+        self.weights, self.clamp = tuple(float(v) for v in spec["weights"]), float(spec["clamp"])
+        self.delta_col, self.score_col = spec["delta_col"], spec["score_col"]
+        self.offset, self.extra = spec["slice"]
+        self.rpi = grid[0] * grid[1] if grid else spec["rows_per_image"]
+        rows, dc, hw = N * self.rpi, self.delta_col, spec["hw"]
+        assert ld >= 1 and 0 <= dc and dc + 4 * A <= ld and (self.score_col is None or 0 <= self.score_col <= ld - A)
+        head = rng.uniform(-1, 1, (rows, ld))
+        d = np.concatenate([rng.uniform(-0.5, 0.5, (rows, A, 2)), rng.uniform(-1.0, 1.0, (rows, A, 2))], axis=2)
+        above = (rng.rand(rows, A, 2) < 0.06) & (hw != "nothing_clips")
+        d[..., 2:][above] = rng.uniform(CLIP, 2 * CLIP, int(above.sum()))
+        head[:, dc:dc + 4 * A] = (d * np.asarray(self.weights)).reshape(rows, 4 * A)
+        self.above = int(above.sum())
+        self.head = head.astype(np.float32)
+        if grid:
+            gh, gw, sy, sx = grid
+            c = rng.randint(-16, 17, (A, 2)) * LATTICE
+            half = rng.randint(4, 4 * 40, (A, 2)) * LATTICE
+            self.anchors = np.concatenate([c - half, c + half], axis=1).astype(np.float32)
+            span = np.array([gh * sy + 30.0, gw * sx + 30.0])
+        else:
+            x1, y1 = rng.randint(0, 4 * 150, rows) * LATTICE, rng.randint(0, 4 * 100, rows) * LATTICE
+            self.anchors = np.stack([x1, y1, x1 + rng.randint(4, 4 * 60, rows) * LATTICE,
+                                     y1 + rng.randint(4, 4 * 60, rows) * LATTICE], axis=1).astype(np.float32)
+            span = np.array([160.0, 210.0])
+        usual = np.array([np.floor(0.7 * span) + (1 + n % 3, 2 + n) for n in range(N)])
+        self.image_hw = {"usual": usual, "zero": 0 * usual, "fractional": usual + (0.5, 0.25),
+                         "nothing_clips": 0 * usual + 4096.0}[hw].astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def decode_sweep_cases():
+    return tuple(DecodeSweepCase(spec, 500 + i) for i, spec in enumerate(decode_sweep_specs()))
+
+
 # ---- NMS -----------------------------------------------------------------------------------------------------------------
 class NmsResult:
     """One segment's greedy walk: keep (ascending indices), and the smallest margins of the decisions it made."""
@@ -168,8 +272,11 @@ class NmsResult:
 
 
 def nms_reference(boxes, scores=None, groups=None, iou_thresh=0.5, min_size=0.0, score_thresh=-INF, max_out=None,
-                  dtype=np.float64) -> NmsResult:
-    """Greedy NMS of one segment, boxes [R][4] in priority order, every operation in `dtype`."""
+                  dtype=np.float64, exact_sides=False) -> NmsResult:
+    """Greedy NMS of one segment, boxes [R][4] in priority order, every operation in `dtype`.  Decisions that are exact in
+    fp32 and fp64 alike need no margin and are not reported as fragile: an IoU that is NaN, infinite or exactly 0 or 1 (an
+    empty intersection, or an intersection equal to the union, is the same in both); and, with `exact_sides` (the caller's
+    word that the boxes are on the lattice and min_size is an fp32 number), the sides, whose differences are then exact."""
     f = dtype
     b = np.asarray(boxes, dtype=f)
     R = b.shape[0]
@@ -179,7 +286,7 @@ def nms_reference(boxes, scores=None, groups=None, iou_thresh=0.5, min_size=0.0,
         w, h = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
         cand = (w >= ms) & (h >= ms)
         side = np.minimum(np.abs(w.astype(np.float64) - min_size), np.abs(h.astype(np.float64) - min_size))
-        near = np.nan_to_num(side, nan=INF) < size_margin(min_size)
+        near = np.nan_to_num(side, nan=INF) < (-INF if exact_sides else size_margin(min_size))
         res.size_margin = float(np.nan_to_num(side, nan=INF).min()) if R else INF
         if scores is not None:
             sc = np.asarray(scores, dtype=f)
@@ -207,7 +314,8 @@ def nms_reference(boxes, scores=None, groups=None, iou_thresh=0.5, min_size=0.0,
             iou = inter / (area[i] + area[j] - inter)
             live = cand[j] if g is None else cand[j] & (g[j] == g[i])
             dead[j] |= live & (iou > thr)
-            gap = np.where(live & np.isfinite(iou), np.abs(iou.astype(np.float64) - iou_thresh), INF)
+            exact = ~np.isfinite(iou) | (iou == zero) | (iou == f(1))
+            gap = np.where(live & ~exact, np.abs(iou.astype(np.float64) - iou_thresh), INF)
             if gap.size:
                 res.iou_margin = min(res.iou_margin, float(gap.min()))
                 res.fragile |= set((np.nonzero(gap < IOU_MARGIN)[0] + i + 1).tolist())
@@ -215,7 +323,7 @@ def nms_reference(boxes, scores=None, groups=None, iou_thresh=0.5, min_size=0.0,
 
 
 def batched_nms_reference(boxes, scores=None, groups=None, iou_thresh=0.5, min_size=0.0, score_thresh=-INF, max_out=None,
-                          dtype=np.float64):
+                          dtype=np.float64, exact_sides=False):
     """boxes [S][R][4] -> (keep [S][max_out] int32 padded with -1, count [S] int32, rois [S][max_out][5] float32,
     [NmsResult per segment])."""
     S, R = boxes.shape[:2]
@@ -227,7 +335,7 @@ def batched_nms_reference(boxes, scores=None, groups=None, iou_thresh=0.5, min_s
     results = []
     for s in range(S):
         r = nms_reference(boxes[s], None if scores is None else scores[s], None if groups is None else groups[s],
-                          iou_thresh, min_size, score_thresh, max_out, dtype)
+                          iou_thresh, min_size, score_thresh, max_out, dtype, exact_sides)
         k = len(r.keep)
         keep[s, :k], count[s] = r.keep, k
         rois[s, :k, 0] = s
@@ -263,31 +371,46 @@ class NmsCase:
         self.groups = rng.randint(0, n_groups, (S, R)).astype(np.int32)
         self.drawn, self.redrawn = S * R, 0
         for s in range(S):
-            n_seeds = max(1, R // 6) if spread is None else spread
-            seeds = np.stack([rng.randint(0, 4 * 1600, n_seeds), rng.randint(0, 4 * 1200, n_seeds),
-                              rng.randint(4, 4 * 96, n_seeds), rng.randint(4, 4 * 96, n_seeds)], axis=1)
-            seeds[rng.rand(n_seeds) < 0.08, 2] = rng.randint(0, 12)          # some thin boxes, around min_size
-            self.boxes[s] = _cluster_boxes(rng, R, seeds)
+            seeds = self._seeds(rng, max(1, R // 6) if spread is None else spread)
+            self.boxes[s] = self._draw(rng, R, seeds)
             self.scores[s] = np.sort(rng.uniform(0.05, 1.0, R).astype(np.float32))[::-1]
+            self._plant(rng, s)
             for _ in range(50):
                 bad = set()
-                for use_groups, use_scores in self.variants:
-                    p = dict(self.PARAMS)
-                    if not use_scores:
-                        p.pop("score_thresh")
+                for use_groups, use_scores, p in self._walks():
                     bad |= nms_reference(self.boxes[s], self.scores[s] if use_scores else None,
                                          self.groups[s] if use_groups else None, **p).fragile
                 bad = sorted(bad)
                 if not bad:
                     break
                 self.redrawn += len(bad)
-                self.boxes[s, bad] = _cluster_boxes(rng, len(bad), seeds)
+                self.boxes[s, bad] = self._draw(rng, len(bad), seeds)
                 fresh = rng.uniform(0.05, 1.0, len(bad)).astype(np.float32)
                 self.scores[s, bad] = fresh
                 order = np.argsort(-self.scores[s], kind="stable")
                 self.boxes[s], self.scores[s], self.groups[s] = self.boxes[s][order], self.scores[s][order], self.groups[s][order]
             else:
                 raise AssertionError("the generator does not converge")
+
+    @staticmethod
+    def _seeds(rng, n_seeds):
+        seeds = np.stack([rng.randint(0, 4 * 1600, n_seeds), rng.randint(0, 4 * 1200, n_seeds),
+                          rng.randint(4, 4 * 96, n_seeds), rng.randint(4, 4 * 96, n_seeds)], axis=1)
+        seeds[rng.rand(n_seeds) < 0.08, 2] = rng.randint(0, 12)              # some thin boxes, around min_size
+        return seeds
+
+    _draw = staticmethod(_cluster_boxes)
+
+    def _plant(self, rng, s):
+        """Boxes of a subclass's own put into segment s after the first draw (a fragile one is redrawn like any other)."""
+
+    def _walks(self):
+        """(groups in use, scores in use, the reference's parameters) of every walk the case must keep its margins in."""
+        for use_groups, use_scores in self.variants:
+            p = dict(self.PARAMS)
+            if not use_scores:
+                p.pop("score_thresh")
+            yield use_groups, use_scores, p
 
     def expected(self, use_groups=True, use_scores=True, max_out=None):
         return _expected(self, use_groups, use_scores, max_out)
@@ -310,9 +433,19 @@ NMS_WIDE_R = (4100, 8200, 16400)
 WIDE_VARIANTS = (VARIANTS[0], VARIANTS[3])
 
 
+# nb == W of three scan instantiations (R = 64 W) and the largest R the library takes, one segment each.  The 32768 case
+# has 410 clusters (80 boxes each, so the walk is shorter) and the (groups, scores) variant only.  Host cost measured on
+# a CPU: building the three cases takes 0.3 s, 2.6 s and 5.5 s, one fp64 reference walk 0.1 s, 0.8 s and 2.5 s
+# (R = 32768: 7380 kept, 16 of 32768 boxes redrawn); the GPU test of R = 32768 took 4.1 s in all, the walks included
+NMS_LIMIT_R = (4096, 16384, 32768)
+NMS_MAX_R = 32768
+
+
 @functools.lru_cache(maxsize=None)
 def nms_case(R: int, S: int) -> NmsCase:
-    if R in NMS_WIDE_R:
+    if R == NMS_MAX_R:
+        return NmsCase(R, S, seed=7 * R + S, spread=410, variants=VARIANTS[:1])
+    if R in NMS_WIDE_R or R in NMS_LIMIT_R:
         return NmsCase(R, S, seed=7 * R + S, spread=R // 40, variants=WIDE_VARIANTS)
     return NmsCase(R, S, seed=7 * R + S)
 
@@ -345,6 +478,231 @@ class ClassCase:
 @functools.lru_cache(maxsize=None)
 def class_case() -> ClassCase:
     return ClassCase()
+
+
+# ---- NMS: every compare at equality -------------------------------------------------------------------------------------
+def f32_below(v: float) -> float:
+    return float(np.nextafter(np.float32(v), np.float32(-INF)))
+
+
+def f32_above(v: float) -> float:
+    return float(np.nextafter(np.float32(v), np.float32(INF)))
+
+
+class EqualityCase:
+    """16 segments of R = 130 lattice boxes whose every decisive quantity is exact in fp32 and fp64 alike, so a compare may
+    sit at equality: the expected result is the fp64 reference's, and the fp32 restatement must give the same.
+      * a pair (first, second) of PAIRS, IoU exactly PAIRS[k][2], at the rows PLACES[p] of segment 4 k + p: lanes 0 and 63
+        of one block (the tie is in the diagonal word), rows 63 / 64 and 0 / 129 (an off-diagonal word), lanes 0 and 63
+        of block 1.  Pairs 2 and 3 have sides of exactly 2.0 and 0.25, the two min_size values; the first of a pair has
+        the score threshold as its score in every other segment, so what it suppresses hangs on `>=`;
+      * every other row is a box that overlaps nothing, with a side of min_size - 0.25, min_size, min_size + 0.25 for both
+        min_size values in turn, as its width or as its height, and a score of the threshold, its fp32 neighbour below,
+        its neighbour above or 0.9; the rotation moves with the segment, so each of rows 0, 63, 64 and 129 has, in some
+        segment, a side equal to either min_size and a score equal to the threshold."""
+
+    R, S = 130, 16
+    PLACES = ((0, 63), (63, 64), (0, 129), (64, 127))
+    PAIRS = (((0, 0, 8, 4), (0, 0, 4, 4), 0.5), ((0, 0, 4, 4), (0, 0, 3, 4), 0.75), ((0, 0, 4, 2), (0, 0, 2, 2), 0.5),
+             ((0, 0, 0.5, 0.25), (0, 0, 0.25, 0.25), 0.5))
+    MIN_SIZES = (2.0, 0.25)
+    SCORE_THRESH = 0.25
+    SIDES = (1.75, 2.0, 2.25, 0.0, 0.25, 0.5, 8.0, 8.0)
+
+    def __init__(self):
+        R, S, thr = self.R, self.S, self.SCORE_THRESH
+        score_of = np.array([f32_below(thr), thr, f32_above(thr), 0.9], dtype=np.float32)
+        self.boxes = np.zeros((S, R, 4), dtype=np.float32)
+        self.scores = np.zeros((S, R), dtype=np.float32)
+        self.groups = np.tile((np.arange(R) % 3).astype(np.int32), (S, 1))
+        self.pair_rows = []
+        for s in range(S):
+            r = np.arange(R)
+            q = r + s + s // 4
+            side = np.asarray(self.SIDES)[q % 8]
+            tall = (q // 8) % 2 == 1
+            w, h = np.where(tall, 8.0, side), np.where(tall, side, 8.0)
+            self.boxes[s] = np.stack([32.0 * r, 0 * r, 32.0 * r + w, h], axis=1)
+            self.scores[s] = score_of[q % 4]
+            (i, j), (first, second, _) = self.PLACES[s % 4], self.PAIRS[s // 4]
+            at = np.array([32.0 * i, 64.0, 32.0 * i, 64.0])
+            self.boxes[s, i], self.boxes[s, j] = np.asarray(first) + at, np.asarray(second) + at
+            self.scores[s, i] = thr if s % 2 == 0 else 0.9
+            self.scores[s, j] = thr if s % 3 == 0 else f32_above(thr)
+            self.groups[s, [i, j]] = 1
+            self.pair_rows.append((i, j))
+        assert np.array_equal(self.boxes, np.round(self.boxes * 4) / 4)
+
+    @staticmethod
+    def runs():
+        """(iou_thresh, min_size) of every run: each pair's IoU and its fp32 neighbours, at both min_size values."""
+        return [(t, ms) for v in (0.5, 0.75) for t in (f32_below(v), v, f32_above(v)) for ms in EqualityCase.MIN_SIZES]
+
+    def expected(self, iou_thresh, min_size, use_groups=True, max_out=None, dtype=np.float64):
+        return _equality_expected(self, iou_thresh, min_size, use_groups, max_out, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _equality_expected(c, iou_thresh, min_size, use_groups, max_out, dtype):
+    return batched_nms_reference(c.boxes, c.scores, c.groups if use_groups else None, iou_thresh, min_size, c.SCORE_THRESH,
+                                 max_out, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def equality_case() -> EqualityCase:
+    return EqualityCase()
+
+
+# ---- NMS: the parameter and geometry sweep -----------------------------------------------------------------------------
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+SWEEP_R = (65, 257)
+SWEEP_IOU = (-1.0, 0.0, 0.25, 0.75, 1.0, 2.0)
+SWEEP_MIN_SIZE = (-INF, -1.0, 0.0, 2.1)
+SWEEP_SCORE_THRESH = (None, -INF, 0.2, INF)          # None: no scores operand
+SWEEP_GROUPS = (INT32_MIN, -1, 0, 7, INT32_MAX)
+SPECIALS = ("zero_width", "zero_height", "zero_area_pair", "inverted_x", "inverted_y", "inverted_both", "touching",
+            "x1_neg_inf", "x2_pos_inf", "all_inf", "x2_neg_inf", "y1_pos_inf")
+
+
+def sweep_combos(iou_thresh=None):
+    """(iou_thresh, min_size, score_thresh or None, groups in use) of every run of the sweep (of one iou_thresh when
+    given); one run in three goes without groups."""
+    out = []
+    for a, iou in enumerate(SWEEP_IOU):
+        for b, ms in enumerate(SWEEP_MIN_SIZE):
+            for c, st in enumerate(SWEEP_SCORE_THRESH):
+                if iou_thresh is None or iou == iou_thresh:
+                    out.append((iou, ms, st, (a + b + c) % 3 != 0))
+    return out
+
+
+class SweepNmsCase(NmsCase):
+    """The lattice cluster case with a fifth of each segment replaced by the boxes of SPECIALS (each kind in every
+    segment, at seeded rows) and group ids from SWEEP_GROUPS, keeping its margins in every run of sweep_combos().  The
+    sides need none: lattice sides are exact and every min_size but 2.1 is an fp32 number (2.1 is 0.1 from the lattice)."""
+
+    def __init__(self, R, S=3, seed=0):
+        super().__init__(R, S, seed=seed, n_groups=len(SWEEP_GROUPS))
+        self.groups = np.asarray(SWEEP_GROUPS, dtype=np.int64)[self.groups].astype(np.int32)
+
+    def _plant(self, rng, s):
+        R, b = self.R, self.boxes[s]
+        n = max(R // 5, len(SPECIALS) + 1)
+        rows = rng.choice(R, n, replace=False)
+        kinds = [SPECIALS[k % len(SPECIALS)] for k in range(n)]
+        for k, (r, kind) in enumerate(zip(rows.tolist(), kinds)):
+            x1, y1, x2, y2 = b[r].tolist()
+            if kind == "zero_width":
+                b[r] = (x1, y1, x1, y2)
+            elif kind == "zero_height":
+                b[r] = (x1, y1, x2, y1)
+            elif kind == "zero_area_pair":                        # this row and the next planted one: the same zero-area box
+                b[r] = b[rows[(k + 1) % n]] = (x1, y1, x1, y1)
+            elif kind == "inverted_x":
+                b[r] = (x2, y1, x1, y2)
+            elif kind == "inverted_y":
+                b[r] = (x1, y2, x2, y1)
+            elif kind == "inverted_both":
+                b[r] = (x2, y2, x1, y1)
+            elif kind == "touching":                               # shares an edge with another row's box: intersection 0
+                o = b[(r + 1) % R].tolist()
+                b[r] = (o[2], o[1], o[2] + (x2 - x1), o[3])
+            elif kind == "x1_neg_inf":
+                b[r] = (-INF, y1, x2, y2)
+            elif kind == "x2_pos_inf":
+                b[r] = (x1, y1, INF, y2)
+            elif kind == "all_inf":
+                b[r] = (-INF, -INF, INF, INF)
+            elif kind == "x2_neg_inf":
+                b[r] = (x1, y1, -INF, y2)
+            elif kind == "y1_pos_inf":
+                b[r] = (x1, INF, x2, y2)
+
+    def _walks(self):
+        for iou, ms, st, use_groups in sweep_combos():
+            p = dict(iou_thresh=iou, min_size=ms, exact_sides=ms != 2.1)
+            if st is not None:
+                p["score_thresh"] = st
+            yield use_groups, st is not None, p
+
+    def expected(self, combo, max_out=None, dtype=np.float64):
+        return _sweep_expected(self, combo, max_out, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def _sweep_expected(c, combo, max_out, dtype):
+    iou, ms, st, use_groups = combo
+    return batched_nms_reference(c.boxes, None if st is None else c.scores, c.groups if use_groups else None, iou, ms,
+                                 -INF if st is None else st, max_out, dtype)
+
+
+@functools.lru_cache(maxsize=None)
+def sweep_nms_case(R: int) -> SweepNmsCase:
+    return SweepNmsCase(R, 3, seed=31 * R)
+
+
+# ---- NMS: boxes off the lattice ---------------------------------------------------------------------------------------
+OFF_LATTICE_R = (300, 3000)
+
+
+class OffLatticeCase(NmsCase):
+    """Clustered boxes with arbitrary fp32 coordinates in a 1333 x 800 frame, sides log-uniform in 4 .. 300 pixels around
+    R / 50 seeds with a jitter of up to a third of a side: what a decode hands NMS.  Products and sums round in fp32
+    here; the margins of the lattice cases (IOU_MARGIN is thirty times an fp32 IoU's error) are kept by redrawing."""
+
+    PARAMS = dict(iou_thresh=0.5, min_size=4.5, score_thresh=0.2)
+
+    def __init__(self, R, S=2, seed=0):
+        super().__init__(R, S, seed=seed, spread=max(R // 50, 1), variants=WIDE_VARIANTS)
+
+    @staticmethod
+    def _seeds(rng, n_seeds):
+        side = np.exp(rng.uniform(math.log(4.0), math.log(300.0), (n_seeds, 2)))
+        return np.concatenate([rng.uniform(0, 1333, (n_seeds, 1)), rng.uniform(0, 800, (n_seeds, 1)), side], axis=1)
+
+    @staticmethod
+    def _draw(rng, n, seeds):
+        k = rng.randint(0, len(seeds), n)
+        x1, y1, w, h = (seeds[k, c] for c in range(4))
+        jit = lambda side: rng.uniform(-1, 1, n) * side / 3
+        x1, y1, w, h = x1 + jit(w), y1 + jit(h), w + jit(w), h + jit(h)
+        return np.stack([x1, y1, x1 + w, y1 + h], axis=1).astype(np.float32)
+
+
+@functools.lru_cache(maxsize=None)
+def off_lattice_case(R: int) -> OffLatticeCase:
+    return OffLatticeCase(R, 2, seed=R)
+
+
+# ---- NMS: many segments -------------------------------------------------------------------------------------------------
+ONE_BOX_PARAMS = dict(iou_thresh=0.5, min_size=2.0, score_thresh=0.25)
+
+
+@functools.lru_cache(maxsize=None)
+def one_box_sources(K: int = 300):
+    """K segments of one lattice box each, a candidate or not by a side (1.75, 2.0, 2.25 and larger, against min_size 2.0)
+    and by its score (the threshold 0.25, its fp32 neighbours, and others): (boxes [K][1][4], scores [K][1], and the
+    reference's keep / count / rois at max_out = 1)."""
+    rng = np.random.RandomState(5)
+    x1, y1 = rng.randint(0, 4000, K) * LATTICE, rng.randint(0, 4000, K) * LATTICE
+    w = np.asarray([1.75, 2.0, 2.25, 40.0, 7.5])[rng.randint(0, 5, K)]
+    h = np.asarray([1.75, 2.0, 2.25, 13.25, 90.0])[rng.randint(0, 5, K)]
+    boxes = np.stack([x1, y1, x1 + w, y1 + h], axis=1).astype(np.float32).reshape(K, 1, 4)
+    scores = np.asarray([f32_below(0.25), 0.25, f32_above(0.25), 0.05, 0.9], dtype=np.float32)[rng.randint(0, 5, K)]
+    scores = scores.reshape(K, 1)
+    keep, count, rois, _ = batched_nms_reference(boxes, scores, None, max_out=1, **ONE_BOX_PARAMS)
+    return boxes, scores, keep, count, rois
+
+
+def tile_segments(src_keep, src_count, src_rois, S: int):
+    """The expected outputs of S segments that repeat K source segments cyclically (segment s is source s % K): the
+    sources' keep and count, and their rois with column 0 set to s wherever a box was kept (float32 holds s < 2^24)."""
+    assert S <= 1 << 24
+    idx = np.arange(S) % src_keep.shape[0]
+    keep, count, rois = src_keep[idx], src_count[idx], src_rois[idx]
+    own = np.broadcast_to(np.arange(S, dtype=np.float32)[:, None], rois.shape[:2])
+    rois[:, :, 0] = np.where(rois[:, :, 0] >= 0, own, np.float32(-1))
+    return keep, count, rois
 
 
 # ---- the detector: per-stage fp64 references, each usable on the GPU's own input to that stage --------------------------------

@@ -178,7 +178,7 @@ def torch_decode_fp32(c: bc.DecodeCase) -> np.ndarray:
     widths, heights = anc[..., 2] - anc[..., 0], anc[..., 3] - anc[..., 1]
     ctr_x, ctr_y = anc[..., 0] + 0.5 * widths, anc[..., 1] + 0.5 * heights
     dx, dy = d[..., 0] / wx, d[..., 1] / wy
-    dw, dh = torch.clamp(d[..., 2] / ww, max=bc.CLIP), torch.clamp(d[..., 3] / wh, max=bc.CLIP)
+    dw, dh = torch.clamp(d[..., 2] / ww, max=c.clamp), torch.clamp(d[..., 3] / wh, max=c.clamp)
     pcx, pcy = dx * widths + ctr_x, dy * heights + ctr_y
     pw, ph = torch.exp(dw) * widths, torch.exp(dh) * heights
     H = hw[:, 0].repeat_interleave(c.rpi)[:, None]
@@ -221,6 +221,17 @@ def test_decode_fp32_restatement_holds_a_quarter_of_tight():
                 worst = max(worst, e)
                 assert e < TIGHT / 4, (mode, i, e)
     print(f"worst fp32 restatement of the decode: {worst:.2e}")
+    # the sweep over the legal launches: measured worst 4.3e-7
+    worst = 0.0
+    for i, c in enumerate(bc.decode_sweep_cases()):
+        want = c.reference()
+        for got in (torch_decode_fp32(c), c.reference(dtype=np.float32)):
+            e = bc.rel_err(got, want)
+            worst = max(worst, e)
+            assert e < TIGHT / 4, (i, c.spec, e)
+            if c.spec["hw"] == "zero":
+                assert not got.any()
+    print(f"worst fp32 restatement of the decode over the sweep: {worst:.2e}")
 
 
 def test_decode_reference_propagates_nan_and_clamps_inf():
@@ -354,6 +365,190 @@ def test_reference_never_keeps_a_nan_box():
     assert np.array_equal(keep[1], c.expected()[0][1])
     boxes[0] = np.nan
     assert bc.batched_nms_reference(boxes, c.scores, c.groups, **c.PARAMS)[1].tolist() == [0, int(c.expected()[1][1])]
+
+
+# ---- the sweeps: decode layouts, NMS at equality, parameters, off-lattice boxes, many segments ---------------------------
+def test_decode_sweep_has_every_pin():
+    specs = bc.decode_sweep_specs()
+    cases = bc.decode_sweep_cases()
+    assert len(specs) == 40 and [c.spec for c in cases] == specs
+    grid = [s for s in specs if s["grid"]]
+    box = [s for s in specs if not s["grid"]]
+    assert {s["N"] for s in specs} == {1, 2, 3, 4} and {s["A"] for s in specs} == set(bc.SWEEP_A)
+    for mode in (grid, box):
+        assert {s["score_col"] is None for s in mode} == {True, False}
+    # the leading dimension: 4A, 4A + 1, 5A, 5A + 3, odd ones and ones that are no multiple of 4
+    for form in (lambda A: 4 * A, lambda A: 4 * A + 1, lambda A: 5 * A, lambda A: 5 * A + 3):
+        assert any(s["ld"] == form(s["A"]) for s in specs)
+    assert any(s["ld"] % 2 for s in specs) and any(s["ld"] % 4 for s in specs) and any(s["ld"] % 64 == 0 for s in specs)
+    # the columns: deltas off a multiple of 4, deltas before the scores, the scores against the row's end, none
+    assert any(s["delta_col"] % 4 for s in specs) and any(s["delta_col"] == 0 for s in specs)
+    assert any(s["score_col"] is not None and s["delta_col"] < s["score_col"] for s in specs)
+    assert any(s["score_col"] is not None and s["score_col"] + s["A"] == s["ld"] for s in specs)
+    assert any(s["score_col"] == 0 for s in specs) and any(s["delta_col"] + 4 * s["A"] == s["ld"] for s in specs)
+    # grid mode: single rows, columns and cells, unequal strides and a stride of 1
+    shapes = {s["grid"][:2] for s in grid}
+    assert (1, 1) in shapes and any(h == 1 and w > 1 for h, w in shapes) and any(w == 1 and h > 1 for h, w in shapes)
+    assert max(h for h, _ in shapes) == 40 and max(w for _, w in shapes) == 40
+    assert any(s["grid"][2] != s["grid"][3] for s in grid) and any(s["grid"][2:] == (1, 1) for s in grid)
+    assert {s["grid"][2:] for s in grid} == set(bc.SWEEP_STRIDES)
+    # boxes mode: total at the edge of a 256-thread block
+    assert {s["rows_per_image"] for s in box if s["A"] == 1 and s["N"] == 1} == set(bc.SWEEP_BOX_ROWS)
+    for key, values in (("weights", bc.SWEEP_WEIGHTS), ("clamp", bc.SWEEP_CLAMPS), ("hw", bc.SWEEP_HW),
+                        ("slice", bc.SWEEP_SLICES)):
+        assert {s[key] for s in specs} == set(values), key
+    assert any(s["slice"][0] > 0 and s["slice"][1] > 0 for s in specs)
+    for c in cases:
+        want = c.reference()
+        assert np.isfinite(want).all() and np.isfinite(c.head).all()
+        d = c.head[:, c.delta_col:c.delta_col + 4 * c.A].reshape(-1, c.A, 4) / np.asarray(c.weights, dtype=np.float32)
+        assert float(np.exp(d[..., 2:].max())) < 1e4                       # whatever the clamp
+        if c.spec["hw"] == "zero":
+            assert not want.any() and bc.rel_err(want, want) == 0.0 and bc.rel_err(want + 1e-30, want) == bc.INF
+        if c.spec["hw"] == "nothing_clips":
+            assert float(want.max()) < float(c.image_hw.min())
+        if c.spec["hw"] == "fractional":
+            assert (c.image_hw % 1 != 0).all()
+    assert sum(c.above for c in cases) >= 50
+    clipped = [c for c in cases if c.spec["hw"] in ("usual", "fractional")]
+    at_edge = [bool((c.reference() == c.image_hw[:, None, [1, 0, 1, 0]]).any()) for c in clipped]
+    assert sum(at_edge) >= 0.75 * len(clipped), at_edge                   # (a launch of one or two boxes may miss the edge)
+
+
+def test_equality_family_is_exact_in_both_precisions():
+    """Every run of the equality family: the fp32 restatement keeps what the fp64 reference keeps, with and without
+    groups; the pair at equality is kept at its IoU and above, suppressed a neighbour below; a side or a score equal
+    to its threshold makes a candidate, its neighbour below does not."""
+    four = np.array([[0, 0, 8, 4], [0, 0, 4, 4], [100, 0, 104, 4], [100, 0, 103, 4]], dtype=np.float32)
+    for dtype in (np.float64, np.float32):
+        assert bc.nms_reference(four, iou_thresh=0.5, dtype=dtype).keep == [0, 1, 2]
+        assert bc.nms_reference(four, iou_thresh=0.75, dtype=dtype).keep == [0, 1, 2, 3]
+        assert bc.nms_reference(four, iou_thresh=bc.f32_below(0.5), dtype=dtype).keep == [0, 2]
+    c = bc.equality_case()
+    assert bc.equality_case() is c and c.boxes.shape == (c.S, c.R, 4) and c.R == 130
+    assert {rows for rows in c.pair_rows} == {(0, 63), (63, 64), (0, 129), (64, 127)}
+    thr = c.SCORE_THRESH
+    for iou, ms in c.runs():
+        for use_groups in (True, False):
+            keep, count, rois, _ = c.expected(iou, ms, use_groups)
+            got = c.expected(iou, ms, use_groups, dtype=np.float32)
+            assert np.array_equal(got[0], keep) and np.array_equal(got[1], count) and np.array_equal(got[2], rois)
+            for s in range(c.S):
+                k = set(keep[s, :count[s]].tolist())
+                w, h = c.boxes[s, :, 2] - c.boxes[s, :, 0], c.boxes[s, :, 3] - c.boxes[s, :, 1]
+                cand = (w >= ms) & (h >= ms) & (c.scores[s] >= np.float32(thr))
+                (i, j), (_, _, v) = c.pair_rows[s], c.PAIRS[s // 4]
+                lone = np.ones(c.R, dtype=bool)
+                lone[[i, j]] = False
+                assert k - {i, j} == set(np.nonzero(cand & lone)[0].tolist())      # a box that overlaps nothing: kept iff candidate
+                if cand[i] and cand[j]:
+                    assert i in k and (j in k) == (not v > iou), (s, iou, ms)
+        # the thresholds themselves are met: sides and scores equal to them, and the neighbours on both sides
+        w, h = c.boxes[..., 2] - c.boxes[..., 0], c.boxes[..., 3] - c.boxes[..., 1]
+        for side in (ms - 0.25, ms, ms + 0.25):
+            assert (w == side).any() and (h == side).any()
+    for r in (0, 63, 64, 129):                                            # lanes 0 and 63 of a block, and the next block's
+        w, h = c.boxes[:, r, 2] - c.boxes[:, r, 0], c.boxes[:, r, 3] - c.boxes[:, r, 1]
+        for v in (bc.f32_below(thr), thr, bc.f32_above(thr)):
+            assert (c.scores[:, r] == np.float32(v)).any(), (v, r)
+        for side in (2.0, 0.25):
+            assert ((w == side) | (h == side)).any(), (side, r)
+    # pairs that are both candidates exist at equality with a threshold score on the suppressor
+    assert sum(c.scores[s, c.pair_rows[s][0]] == np.float32(thr) for s in range(c.S)) == c.S // 2
+
+
+@pytest.mark.parametrize("R", bc.SWEEP_R)
+def test_nms_sweep_keeps_its_margins_in_every_combination(R):
+    """The parameter and geometry sweep: the redraw cap holds, every special kind is in every segment, every group id is
+    used, and the fp32 walk equals the fp64 walk under each of the 96 combinations."""
+    c = bc.sweep_nms_case(R)
+    combos = bc.sweep_combos()
+    assert len(combos) == 96 and len(set(combos)) == 96
+    assert {x[0] for x in combos} == set(bc.SWEEP_IOU) and {x[1] for x in combos} == set(bc.SWEEP_MIN_SIZE)
+    assert {x[2] for x in combos} == set(bc.SWEEP_SCORE_THRESH) and {x[3] for x in combos} == {True, False}
+    assert c.S == 3 and c.redrawn <= bc.REDRAW_CAP * c.drawn, (c.redrawn, c.drawn)
+    assert set(np.unique(c.groups).tolist()) == set(bc.SWEEP_GROUPS)
+    finite = np.where(np.isfinite(c.boxes), c.boxes, 0)
+    assert np.array_equal(finite, np.round(finite * 4) / 4) and float(np.abs(finite).max()) < 4096 and not np.isnan(c.boxes).any()
+    for s in range(c.S):
+        b = c.boxes[s]
+        with np.errstate(invalid="ignore"):
+            w, h = b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]
+        assert ((w == 0) & (h > 0)).any() and ((h == 0) & (w > 0)).any() and (w < 0).any() and (h < 0).any()
+        assert ((w < 0) & (h < 0)).any()
+        point = np.nonzero((w == 0) & (h == 0))[0]
+        assert any(np.array_equal(b[i], b[j]) for i in point for j in point if i < j)          # an identical zero-area pair
+        assert np.isinf(b).any(axis=1).sum() >= 5 and (np.isinf(b).sum(axis=1) == 4).any()
+        assert (b == -bc.INF).any() and (b == bc.INF).any()
+        touch = (b[:, None, 0] == b[None, :, 2]) & (b[:, None, 1] < b[None, :, 3]) & (b[None, :, 1] < b[:, None, 3])
+        assert touch.any()                                                                      # shares an edge: intersection 0
+    kept = set()
+    for combo in combos:
+        keep, count, rois, results = c.expected(combo)
+        for r in results:
+            assert r.iou_margin >= bc.IOU_MARGIN and r.score_margin >= bc.SCORE_MARGIN, combo
+        got = c.expected(combo, dtype=np.float32)
+        assert np.array_equal(got[0], keep) and np.array_equal(got[1], count), combo
+        assert np.array_equal(got[2].view(np.int32), rois.view(np.int32)), combo
+        kept.add(tuple(count.tolist()))
+    assert len(kept) >= 20                                                  # the parameters bite
+    print(f"R={R}: drawn {c.drawn}, redrawn {c.redrawn}, {len(kept)} distinct count vectors")
+
+
+@pytest.mark.parametrize("R", bc.OFF_LATTICE_R)
+def test_off_lattice_case_keeps_its_margins(R):
+    c = bc.off_lattice_case(R)
+    assert c.S == 2 and c.boxes.dtype == np.float32 and c.redrawn <= bc.REDRAW_CAP * c.drawn, (c.redrawn, c.drawn)
+    assert (c.boxes != np.round(c.boxes * 4) / 4).mean() > 0.99             # off the lattice
+    w, h = c.boxes[..., 2] - c.boxes[..., 0], c.boxes[..., 3] - c.boxes[..., 1]
+    assert 2.5 < float(min(w.min(), h.min())) < 4.5 and 300 < float(max(w.max(), h.max())) < 400
+    assert (np.diff(c.scores, axis=1) <= 0).all()
+    for use_groups, use_scores in c.variants:
+        p = dict(c.PARAMS)
+        if not use_scores:
+            p.pop("score_thresh")
+        keep, count, rois, results = c.expected(use_groups, use_scores)
+        for r in results:
+            assert not r.fragile and r.iou_margin >= bc.IOU_MARGIN and r.score_margin >= bc.SCORE_MARGIN
+            assert r.size_margin >= bc.size_margin(c.PARAMS["min_size"])
+        got = bc.batched_nms_reference(c.boxes, c.scores if use_scores else None, c.groups if use_groups else None,
+                                       dtype=np.float32, **p)
+        assert np.array_equal(got[0], keep) and np.array_equal(got[1], count)
+        assert (count > 0.15 * R).all() and (count < 0.6 * R).all(), count
+    print(f"R={R}: kept {c.expected()[1].tolist()}, redrawn {c.redrawn}")
+
+
+def test_limit_cases_keep_their_margins():
+    """nb == W at three scan widths; the largest R is left to the GPU test (its walk takes seconds)."""
+    for R in bc.NMS_LIMIT_R[:2]:
+        c = bc.nms_case(R, 1)
+        assert -(-R // 64) in (64, 256) and c.redrawn <= bc.REDRAW_CAP * c.drawn
+        for use_groups, use_scores in c.variants:
+            keep, count, _, results = c.expected(use_groups, use_scores)
+            assert not results[0].fragile and 0 < count[0] < 0.9 * R
+    assert bc.NMS_LIMIT_R[-1] == bc.NMS_MAX_R == 32768
+
+
+def test_one_box_sources_and_tiling():
+    boxes, scores, keep, count, rois = bc.one_box_sources()
+    K = boxes.shape[0]
+    assert K == 300 and boxes.shape == (K, 1, 4) and keep.shape == (K, 1) and rois.shape == (K, 1, 5)
+    w, h = boxes[:, 0, 2] - boxes[:, 0, 0], boxes[:, 0, 3] - boxes[:, 0, 1]
+    cand = (w >= 2.0) & (h >= 2.0) & (scores[:, 0] >= np.float32(0.25))
+    assert np.array_equal(count, cand.astype(np.int32)) and np.array_equal(keep[:, 0], np.where(cand, 0, -1))
+    for side in (1.75, 2.0, 2.25):
+        assert (w == side).any() and (h == side).any()
+    for v in (bc.f32_below(0.25), 0.25, bc.f32_above(0.25)):
+        assert ((scores[:, 0] == np.float32(v)) & (w >= 2.0) & (h >= 2.0)).any()
+    assert 0.2 < cand.mean() < 0.8
+    got = bc.batched_nms_reference(boxes, scores, None, max_out=1, dtype=np.float32, **bc.ONE_BOX_PARAMS)
+    assert np.array_equal(got[0], keep) and np.array_equal(got[2], rois)
+    S = 2 * K + 7
+    tk, tc, tr = bc.tile_segments(keep, count, rois, S)
+    want = bc.batched_nms_reference(np.tile(boxes, (3, 1, 1))[:S], np.tile(scores, (3, 1))[:S], None, max_out=1,
+                                    **bc.ONE_BOX_PARAMS)
+    assert np.array_equal(tk, want[0]) and np.array_equal(tc, want[1]) and np.array_equal(tr.view(np.int32), want[2].view(np.int32))
+    assert np.float32((1 << 24) - 1) == (1 << 24) - 1                       # float(s) is exact for every s the library takes
 
 
 # ---- the detector's seed ---------------------------------------------------------------------------------------------------

@@ -10,50 +10,13 @@ import torch
 import box_cases as bc
 import guarded
 from cases import TIGHT
-from gpu_support import torch_dev  # noqa: F401
+from gpu_support import bits, run_decode, run_nms, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 NAN = float("nan")
 
 
-def as_f32(a: np.ndarray) -> torch.Tensor:
-    """An int32 array as the float32 master the arena holds (same bits)."""
-    return torch.from_numpy(np.ascontiguousarray(a)).view(torch.float32)
-
-
-def bits(t: torch.Tensor) -> torch.Tensor:
-    return t.contiguous().view(torch.int32)
-
-
 # ---- decode ---------------------------------------------------------------------------------------------------------------
-def run_decode(pkg, dev, c, head=None, offset=0, extra=0, aligns=guarded.ALIGNS, tag=""):
-    """The kernel on case `c` (or on another `head`), into [N][offset + boxes + extra] outputs; returns this launch's
-    slice of (boxes, scores) on the CPU.  What lies outside the slice keeps its NaN fill."""
-    per, first = c.rpi * c.A, None
-    total = offset + per + extra
-    for align in aligns:
-        arena = guarded.Arena(torch, dev, align)
-        h = arena.input(torch.from_numpy(c.head if head is None else head), name="head")
-        anc = arena.input(torch.from_numpy(c.anchors), name="anchors")
-        hw = arena.input(torch.from_numpy(c.image_hw), name="image_hw")
-        ob, os_ = arena.output(c.N, total, 4, name="boxes"), arena.output(c.N, total, name="scores")
-        for _ in range(2):
-            ob.fill_(NAN), os_.fill_(NAN)
-            got = pkg.box_decode(h, anc, hw, c.A, c.weights, c.grid, c.delta_col, c.score_col, ob, os_, offset)
-            assert got[0] is ob and got[1] is os_
-            arena.check(f"box_decode {tag} align={align}")
-            b, s = ob.cpu(), os_.cpu()
-            outside = torch.ones(total, dtype=torch.bool)
-            outside[offset:offset + per] = False
-            assert bool(torch.isnan(b[:, outside]).all()) and bool(torch.isnan(s[:, outside]).all()), "wrote outside its slice"
-            cur = (b[:, offset:offset + per].contiguous(), s[:, offset:offset + per].contiguous())
-            if first is None:
-                first = cur
-            assert torch.equal(bits(cur[0]), bits(first[0])) and torch.equal(bits(cur[1]), bits(first[1])), \
-                f"{tag}: not bitwise reproducible (align {align})"
-    return first[0].numpy(), first[1].numpy()
-
-
 def check_decode(pkg, dev, c, tag, **kw):
     boxes, scores = run_decode(pkg, dev, c, tag=tag, **kw)
     err = bc.rel_err(boxes, c.reference())
@@ -104,35 +67,6 @@ def test_decode_nonfinite_delta_stays_in_its_coordinates(index, mode, pkg, torch
 
 
 # ---- NMS ------------------------------------------------------------------------------------------------------------------
-def run_nms(pkg, dev, boxes, scores, groups, max_out, params, rois=True, aligns=guarded.ALIGNS, tag=""):
-    """The two kernels on numpy operands, on the guarded arena at each of `aligns`: a first call, then a second one into
-    NaN-filled outputs and a NaN-filled workspace, bitwise the first.  Returns (keep, count, rois) as numpy arrays."""
-    S, R = boxes.shape[:2]
-    first = None
-    for align in aligns:
-        arena = guarded.Arena(torch, dev, align)
-        b = arena.input(torch.from_numpy(boxes), name="boxes")
-        sc = None if scores is None else arena.input(torch.from_numpy(scores), name="scores")
-        g = None if groups is None else arena.input(as_f32(groups), name="groups").view(torch.int32)
-        keep = arena.output(S, max_out, name="keep").view(torch.int32)
-        count = arena.output(S, name="count").view(torch.int32)
-        ro = arena.output(S, max_out, 5, name="rois") if rois else False
-        ws = arena.workspace(pkg.nms_workspace_bytes(S, R), name="workspace")
-        for _ in range(2):
-            keep.view(torch.float32).fill_(NAN), count.view(torch.float32).fill_(NAN), ws.fill_(NAN)
-            if rois:
-                ro.fill_(NAN)
-            got = pkg.batched_nms(b, sc, g, max_out=max_out, rois_out=ro, workspace=ws, keep=keep, count=count, **params)
-            assert got[0] is keep and got[1] is count and (not rois or got[2] is ro)
-            arena.check(f"batched_nms {tag} S={S} R={R} max_out={max_out} align={align}")
-            cur = (keep.cpu().numpy(), count.cpu().numpy(), ro.cpu().numpy() if rois else None)
-            if first is None:
-                first = cur
-            for x, y in zip(cur, first):
-                assert x is None or np.array_equal(x.view(np.int32), y.view(np.int32)), f"{tag}: not bitwise reproducible"
-    return first
-
-
 def check_nms(pkg, dev, c, use_groups, use_scores, max_out, aligns=guarded.ALIGNS):
     p = dict(c.PARAMS)
     if not use_scores:

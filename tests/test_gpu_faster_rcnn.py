@@ -169,3 +169,36 @@ def test_a_padding_roi_never_reaches_the_output(pkg, R, torch_dev):
         k = int(out["count"][n])
         src = cpu(out["cand_idx"])[n].gather(0, cpu(out["det_keep"])[n, :k].long()) // fg      # the proposal of each detection
         assert k > 0 and bool((src < c).all())
+
+
+def test_more_candidates_than_max_candidates_raise_overflow(pkg, R, torch_dev):
+    """postprocess_detections with max_candidates below the number of scores that pass the threshold: overflow is True
+    for those images, and every output is candidates_reference's at that max_candidates, fed the GPU's own class boxes
+    and scores."""
+    det = importlib.import_module("cuda_winograd_amd.detection")
+    m = pkg.FasterRCNN.from_state_dict(bc.detector_state_dict(R)[0], D["arch"], num_classes=D["classes"],
+                                       out_channels=D["out_channels"], P=D["P"], rpn_pre_nms_top_n=D["pre"],
+                                       rpn_post_nms_top_n=D["post"], box_detections_per_img=D["detections"],
+                                       device=torch_dev[1])
+    full = m(bc.detector_input().to(torch_dev[1]), stages=True)
+    torch.cuda.synchronize()
+    passing = (cpu(full["class_scores"]) >= bc.SCORE_THRESH).sum(dim=1)
+    kc = int(passing.min()) // 2
+    assert kc >= 4 and not bool(cpu(full["overflow"]).any()), passing
+    hw = torch.tensor([[float(D["H"]), float(D["W"])]] * D["N"], device=torch_dev[1])
+    stages = {}
+    out = det.postprocess_detections(full["head_out"], full["rois"].view(-1, 5), hw, D["classes"],
+                                     detections=D["detections"], max_candidates=kc, stages=stages)
+    torch.cuda.synchronize()
+    assert same_bits(stages["class_boxes"], full["class_boxes"]) and same_bits(stages["class_scores"], full["class_scores"])
+    cand = bc.candidates_reference(cpu(stages["class_boxes"]), cpu(stages["class_scores"]), D["classes"] - 1,
+                                   D["detections"], max_candidates=kc)
+    assert cand["overflow"].tolist() == [True] * D["N"] and cpu(out["overflow"]).tolist() == [True] * D["N"]
+    assert tuple(stages["cand_idx"].shape) == (D["N"], kc)
+    assert torch.equal(cpu(stages["cand_idx"]), cand["idx"]) and torch.equal(cpu(stages["cand_labels"]), cand["cand_labels"])
+    assert same_bits(stages["cand_boxes"], cand["cand_boxes"]) and same_bits(stages["cand_scores"], cand["cand_scores"])
+    assert np.array_equal(cpu(stages["det_keep"]).numpy(), cand["keep"]) and np.array_equal(cpu(out["count"]).numpy(), cand["count"])
+    assert same_bits(out["boxes"], cand["det_boxes"]) and same_bits(out["scores"], cand["det_scores"])
+    assert torch.equal(cpu(out["labels"]), cand["det_labels"])
+    print("passing", passing.tolist(), "max_candidates", kc, "margins", {k: cand[k] for k in ("iou_margin", "size_margin", "score_margin")})
+    assert cand["iou_margin"] >= bc.IOU_MARGIN and cand["score_margin"] >= bc.SCORE_MARGIN and cand["tie_gap"] > 0

@@ -11,6 +11,9 @@ batch whose tensors cross 2^31 and 2^32 bytes, into NaN-filled outputs and works
   CPU (the suite's own: the oracle module and the reference methods of the other GPU test files) at TIGHT;
 * a second launch gives the same bits on those images, and no stream-K ticket is left held.
 
+The box kernels (at the end) are plain HIP with 64-bit addresses: batched NMS runs at its widest segments, with a
+workspace past 4 GiB and at its largest segment counts, box decode with a head and with an output past 4 GiB.
+
 Inputs are built on the device from a seeded generator; a case skips when the card has less free memory than it needs
 (at most about 20 GiB)."""
 import ctypes
@@ -19,12 +22,13 @@ import types
 import numpy as np
 import pytest
 
+import box_cases as bc
 import layer_refs as LR
 from aspp_cases import cat_reference
 from cases import TIGHT, S2Block, V15Block, proj_weights, ring_zero
 from dilated_cases import dilated_reference
 from fpn_reference import level_reference
-from gpu_support import torch_dev  # noqa: F401
+from gpu_support import run_nms, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -811,3 +815,182 @@ def test_fpn_level_beyond_4gib(pkg, O, torch_dev, free_after):
     errs = [O.rel_error(first[k][:, 1:-1, 1:-1, :].numpy(), w.numpy()) for k, w in enumerate((want_inner, want_P))]
     print(f"fpn_level past 4 GiB, images {idx}: inner {errs[0]:.2e} P {errs[1]:.2e}")
     del c, top, inner, out, got
+
+
+# ------------------------------------------------------------------ batched NMS at its limits, box decode past 4 GiB
+def _assert_nms(got, want, tag):
+    for name, g, w in zip(("count", "keep", "rois"), (got[1], got[0], got[2]), (want[1], want[0], want[2])):
+        if g is not None:
+            assert np.array_equal(g.view(np.int32), w.view(np.int32)), (tag, name)
+
+
+@pytest.mark.parametrize("R", bc.NMS_LIMIT_R)
+def test_nms_full_width_segments(R, pkg, torch_dev, free_after):
+    """ceil(R / 64) equal to the scan kernel's thread count along the words (R = 4096 and 16384: W = 64 and 256), and
+    the largest segment the library takes (R = 32768, W = 512, a 128 MiB bit matrix): exactly the fp64 reference, all of
+    it and cut at half the kept count."""
+    torch, dev = torch_dev
+    _need(torch, 2 * (pkg.nms_workspace_bytes(1, R) + (256 << 20)))
+    c = bc.nms_case(R, 1)
+    for use_groups, use_scores in c.variants:
+        p = dict(c.PARAMS)
+        if not use_scores:
+            p.pop("score_thresh")
+        got = run_nms(pkg, dev, c.boxes, c.scores if use_scores else None, c.groups if use_groups else None, R, p,
+                      aligns=(256,), tag=f"full width groups={use_groups}")
+        _assert_nms(got, c.expected(use_groups, use_scores), (R, use_groups, use_scores))
+    count = int(c.expected()[1][0])
+    got = run_nms(pkg, dev, c.boxes, c.scores, c.groups, count // 2, c.PARAMS, aligns=(16,), tag="full width, cut")
+    _assert_nms(got, c.expected(True, True, count // 2), (R, "cut"))
+    print(f"R={R}: kept {count}, redrawn {c.redrawn} of {c.drawn}")
+
+
+def test_nms_workspace_beyond_4gib(pkg, torch_dev, free_after):
+    """2100 segments of 4100 boxes: the bit matrix is 2100 x 4100 x 65 words, 4.48 GB, NaN-filled.  The segments repeat
+    the three of nms_case(4100, 3) cyclically, so a segment that read a wrapped address would see another case's bits.
+    Every segment's keep, count and rois equal its source's reference, rois column 0 its own index; the segments on
+    both sides of byte 2^31 and byte 2^32 of the workspace are checked by name."""
+    torch, dev = torch_dev
+    S, R = 2100, 4100
+    per = R * 65 * 8
+    assert pkg.nms_workspace_bytes(S, R) == S * per > (1 << 32) + (1 << 27)
+    _need(torch, S * per + S * R * (16 + 4 + 4 + 4 + 20) * 2 + GIB)
+    c = bc.nms_case(R, 3)
+    assert len({c.boxes[k].tobytes() for k in range(3)}) == 3
+    idx = np.arange(S) % 3
+    src = c.expected()
+    assert len({tuple(src[0][k].tolist()) for k in range(3)}) == 3
+    want = bc.tile_segments(*src[:3], S)
+    got = run_nms(pkg, dev, c.boxes[idx], c.scores[idx], c.groups[idx], R, c.PARAMS, aligns=(256,), tag="workspace > 4 GiB")
+    named = sorted({0, S - 1} | {b // per + d for b in (1 << 31, 1 << 32) for d in (-1, 0, 1)})
+    assert named == [0, 1006, 1007, 1008, 2013, 2014, 2015, 2099]
+    for s in named:
+        k = int(want[1][s])
+        assert got[1][s] == k == src[1][s % 3] and np.array_equal(got[0][s], src[0][s % 3]), s
+        assert (got[2][s, :k, 0] == s).all() and np.array_equal(got[2][s, :, 1:], src[2][s % 3][:, 1:]), s
+    _assert_nms(got, want, "every segment")
+
+
+def test_nms_many_segments(pkg, torch_dev, free_after):
+    """S = 70001 segments of 65 boxes (two words per row), the seven of nms_case(65, 7) repeated."""
+    torch, dev = torch_dev
+    S, R = 70001, 65
+    _need(torch, GIB)
+    c = bc.nms_case(R, 7)
+    idx = np.arange(S) % 7
+    want = bc.tile_segments(*c.expected()[:3], S)
+    got = run_nms(pkg, dev, c.boxes[idx], c.scores[idx], c.groups[idx], R, c.PARAMS, aligns=(256,), tag="70001 segments")
+    _assert_nms(got, want, S)
+    assert got[2][S - 1, 0, 0] == S - 1
+
+
+@pytest.mark.parametrize("S,rois", [((1 << 22) - 1, True), (1 << 22, True), ((1 << 24) - 1, False)])
+def test_nms_one_box_segments_up_to_the_limit(S, rois, pkg, torch_dev, free_after):
+    """R = 1, max_out = 1 on both sides of S = 2^22 (the scan kernel has one workgroup of 1024 threads per segment, and
+    a launch takes fewer than 2^32 threads along x, so the library cuts the scan into launches of at most 2^22 - 1
+    segments) and at the largest S the library takes, 2^24 - 1.  One launch each, into NaN-filled outputs."""
+    torch, dev = torch_dev
+    _need(torch, 2 * S * (16 + 4 + 8 + 4 + 4 + 20) + GIB)
+    boxes, scores, keep, count, src_rois = bc.one_box_sources()
+    idx = np.arange(S) % boxes.shape[0]
+    want = bc.tile_segments(keep, count, src_rois, S)
+    got = run_nms(pkg, dev, boxes[idx], scores[idx], None, 1, bc.ONE_BOX_PARAMS, rois=rois, aligns=(256,), repeats=1,
+                  tag=f"S={S}")
+    _assert_nms(got, want, S)
+    last = max(s for s in range(S - 300, S) if want[1][s])
+    assert got[0][last, 0] == 0 and (not rois or got[2][last, 0, 0] == np.float32(last))
+
+
+DECODE_HEAD = dict(N=3, rpi=699051, A=3, ld=520, delta_col=520 - 12, score_col=5, weights=(10.0, 10.0, 5.0, 5.0))
+
+
+def _decode_rows(torch, head, anchors, image_hw, rows, d):
+    """fp64 boxes [len(rows)][A][4] of the picked rows of a boxes-mode head, image by image."""
+    out = np.zeros((len(rows), d["A"], 4))
+    h, a = _pick(torch, head, rows).numpy(), _pick(torch, anchors, rows).numpy()
+    for n in range(d["N"]):
+        m = np.array([r // d["rpi"] == n for r in rows])
+        if m.any():
+            out[m] = bc.decode_reference(h[m], a[m], image_hw[n:n + 1], d["A"], d["weights"], None,
+                                         d["delta_col"]).reshape(-1, d["A"], 4)
+    return out, h
+
+
+def test_box_decode_head_beyond_4gib(pkg, torch_dev, free_after):
+    """Boxes mode on a head of 3 x 699051 rows of 520 floats, 4.36 GB, deltas in the row's last 12 columns and scores at
+    column 5: the rows on both sides of byte 2^31 and byte 2^32 of the head, the first and last row of every image and
+    1000 seeded rows against fp64 at TIGHT; the whole output finite; a second launch gives the same bits."""
+    torch, dev = torch_dev
+    d = DECODE_HEAD
+    N, rpi, A, ld = d["N"], d["rpi"], d["A"], d["ld"]
+    rows = N * rpi
+    assert rows * ld * 4 > (1 << 32) + (1 << 25)
+    _need(torch, rows * ld * 4 + 2 * rows * A * 20 + rows * 16)
+    head = _rand(torch, dev, (rows, ld), 301).mul_(4.0)                   # deltas / weights: +-0.2 and +-0.4
+    g = torch.Generator(device=dev).manual_seed(302)
+    anchors = torch.rand(rows, 4, device=dev, generator=g)
+    anchors[:, 0].mul_(600.0), anchors[:, 1].mul_(400.0)
+    anchors[:, 2] = anchors[:, 0] + 1.0 + 120.0 * anchors[:, 2]
+    anchors[:, 3] = anchors[:, 1] + 1.0 + 120.0 * anchors[:, 3]
+    image_hw = np.array([[420.0, 610.5], [333.25, 700.0], [512.0, 512.0]], dtype=np.float32)
+    hw = torch.from_numpy(image_hw).to(dev)
+    pick = {0, rows - 1} | {n * rpi + e for n in range(N) for e in (0, rpi - 1)}
+    pick |= {b // (4 * ld) + e for b in (1 << 31, 1 << 32) for e in (-1, 0, 1)}
+    pick |= set(np.random.RandomState(303).randint(0, rows, 1000).tolist())
+    pick = sorted(pick)
+    want, picked_head = _decode_rows(torch, head, anchors, image_hw, pick, d)
+    out_b = torch.empty(N, rpi * A, 4, device=dev)
+    out_s = torch.empty(N, rpi * A, device=dev)
+    first = None
+    for rep in range(2):
+        out_b.fill_(NAN), out_s.fill_(NAN)
+        pkg.box_decode(head, anchors, hw, A, d["weights"], None, d["delta_col"], d["score_col"], out_b, out_s)
+        torch.cuda.synchronize()
+        assert _finite(torch, out_b) and _finite(torch, out_s)
+        got_b = _pick(torch, out_b.view(rows, A, 4), pick).numpy()
+        got_s = _pick(torch, out_s.view(rows, A), pick).numpy()
+        err = bc.rel_err(got_b, want)
+        assert err < TIGHT, (rep, err)
+        assert np.array_equal(got_s.view(np.int32), picked_head[:, d["score_col"]:d["score_col"] + A].view(np.int32))
+        if first is None:
+            first = (out_b.clone(), out_s.clone())
+        assert torch.equal(out_b.view(torch.int32), first[0].view(torch.int32))
+        assert torch.equal(out_s.view(torch.int32), first[1].view(torch.int32))
+    print(f"box_decode, head past 4 GiB, {len(pick)} rows: {err:.2e}")
+    del head, anchors, out_b, out_s, first
+
+
+def _count_not_nan(torch, t):
+    flat, total = t.reshape(-1), 0
+    for i in range(0, flat.numel(), 1 << 28):
+        total += int((~torch.isnan(flat[i:i + (1 << 28)])).sum())
+    return total
+
+
+def test_box_decode_output_beyond_4gib(pkg, torch_dev, free_after):
+    """out_boxes [2][2^28 + 4096][4], 8.6 GB, and out_scores to match, NaN-filled; a small grid-mode head written at
+    out_offset = 2^28 - 100: image 0's slice of the boxes straddles byte 2^32, image 1's slice lies beyond it (and, for
+    the scores, beyond byte 2^31).  Both slices at TIGHT and the scores bit for bit; counted on the device, the elements
+    that are not NaN are exactly the two slices'."""
+    torch, dev = torch_dev
+    total, off = (1 << 28) + 4096, (1 << 28) - 100
+    _need(torch, 2 * total * 20 + GIB)
+    c = bc.decode_case(7)                                                  # 13 x 21, A = 3, N = 3 -> the first two images
+    N, per = 2, c.rpi * c.A
+    assert off * 16 < (1 << 32) < (off + per) * 16 and off + per <= total
+    head_np, hw_np = c.head[:N * c.rpi], c.image_hw[:N]
+    want = bc.decode_reference(head_np, c.anchors, hw_np, c.A, c.weights, c.grid, c.delta_col)
+    head, anc, hw = (torch.from_numpy(a).to(dev) for a in (head_np, c.anchors, hw_np))
+    out_b = torch.empty(N, total, 4, device=dev)
+    out_s = torch.empty(N, total, device=dev)
+    for rep in range(2):
+        out_b.fill_(NAN), out_s.fill_(NAN)
+        pkg.box_decode(head, anc, hw, c.A, c.weights, c.grid, c.delta_col, c.score_col, out_b, out_s, off)
+        torch.cuda.synchronize()
+        got_b, got_s = out_b[:, off:off + per].cpu().numpy(), out_s[:, off:off + per].cpu().numpy()
+        err = bc.rel_err(got_b, want)
+        assert err < TIGHT, (rep, err)
+        assert np.array_equal(got_s.view(np.int32), head_np[:, :c.A].reshape(N, per).view(np.int32))
+        assert _count_not_nan(torch, out_b) == N * per * 4 and _count_not_nan(torch, out_s) == N * per
+    print(f"box_decode, output past 4 GiB: {err:.2e}")
+    del out_b, out_s
