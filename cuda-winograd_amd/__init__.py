@@ -952,6 +952,88 @@ def batched_nms(boxes, scores=None, groups=None, iou_thresh: float = 0.5, min_si
     return (keep, count) if rois is None else (keep, count, rois)
 
 
+MASK_LAYOUTS = {"planes": 0, "gemm_rows": 1}   # WINO_MASK_LAYOUT_*
+MASK_MAX_M = 62
+
+
+def _uint8(t, shape, device, name: str) -> torch.Tensor:
+    """The caller's uint8 output checked like _out, or a new one of `shape` on `device`."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.uint8, device=device)
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous()
+            or tuple(t.shape) != tuple(shape)):
+        raise WinoError(f"{name} must be a contiguous uint8 CUDA(HIP) tensor of shape {tuple(shape)}")
+    return t
+
+
+def paste_masks(logits, labels, boxes, image_hw, H: int, W: int, M=None, classes=None, layout: str = "planes",
+                out=None, binary=None, want_out: bool = True, want_binary: bool = False, threshold: float = 0.5):
+    """torchvision's maskrcnn_inference + paste_masks_in_image (padding 1) for all detections in one HIP launch: detection
+    r = n D + d takes the mask of class labels[r] out of `logits`, applies the sigmoid and pastes it, resized to its box
+    grown by (M + 2) / M, into plane (n, d).  logits, read in place: layout "planes" [R][classes][M][M] (M and classes
+    from the shape), or "gemm_rows" [R (M/2)^2 4][ld], the mask head's logits GEMM output (MaskHead's raw form; M must be
+    given, classes defaults to ld).  labels [N][D] (or [R]) int32: a label outside [0, classes), such as a padding row's
+    -1, gives a zero plane.  boxes [N][D][4] (or [R][4]) float32; image_hw [N][2] float32 (H, W) per image, beyond which
+    the plane is zero.  Returns (out, binary): out [N][D][H][W] float32 or None, binary [N][D][H][W] uint8 = out >
+    threshold or None.  A given `out` / `binary` tensor is written and implies want_out / want_binary.  No scratch:
+    capturable into a graph without a prepare."""
+    if layout not in MASK_LAYOUTS:
+        raise WinoError(f"paste_masks: layout must be one of {sorted(MASK_LAYOUTS)}, got {layout!r}")
+    H, W, threshold = int(H), int(W), float(threshold)
+    if H < 1 or W < 1 or H * W >= 1 << 31:
+        raise WinoError(f"paste_masks: bad plane H={H} W={W} (need H, W >= 1, H W < 2^31)")
+    if threshold != threshold:
+        raise WinoError("paste_masks: threshold is NaN")
+    want_out, want_binary = bool(want_out) or out is not None, bool(want_binary) or binary is not None
+    if not want_out and not want_binary:
+        raise WinoError("paste_masks: neither out nor binary is wanted")
+    lg = _dev(logits, "logits")
+    hw = _dev(image_hw, "image_hw")
+    bx = _dev(boxes, "boxes")
+    if hw.dim() != 2 or int(hw.shape[1]) != 2:
+        raise WinoError("image_hw must be [N][2]")
+    N = int(hw.shape[0])
+    if bx.dim() not in (2, 3) or int(bx.shape[-1]) != 4:
+        raise WinoError("boxes must be [N][D][4] or [N D][4]")
+    R = bx.numel() // 4
+    if N < 1 or R % N:
+        raise WinoError(f"paste_masks: {R} boxes for N={N} images")
+    D = R // N
+    if not isinstance(labels, torch.Tensor):
+        raise WinoError("labels must be an int32 CUDA(HIP) tensor")
+    lb = _int32(labels, tuple(labels.shape), bx.device, "labels")
+    if lb.numel() != R:
+        raise WinoError(f"labels must hold {R} int32, one per box, got {tuple(lb.shape)}")
+    if layout == "planes":
+        if lg.dim() != 4 or int(lg.shape[0]) != R or int(lg.shape[2]) != int(lg.shape[3]):
+            raise WinoError(f"logits must be [{R}][classes][M][M] in the planes layout, got {tuple(lg.shape)}")
+        ld = cls = int(lg.shape[1])
+        m = int(lg.shape[2])
+        if (M is not None and int(M) != m) or (classes is not None and int(classes) != cls):
+            raise WinoError(f"paste_masks: M={M} classes={classes} but logits is {tuple(lg.shape)}")
+    else:
+        if M is None:
+            raise WinoError("paste_masks: the gemm_rows layout needs M")
+        m = int(M)
+        if lg.dim() != 2 or m < 2 or m % 2 or int(lg.shape[0]) != R * m * m:
+            raise WinoError(f"logits must be [{R} * M * M][ld] with M even in the gemm_rows layout, got {tuple(lg.shape)} "
+                            f"for M={m}")
+        ld = int(lg.shape[1])
+        cls = ld if classes is None else int(classes)
+    if not 1 <= m <= MASK_MAX_M or not 1 <= cls <= ld:
+        raise WinoError(f"paste_masks: need 1 <= M <= {MASK_MAX_M} and 1 <= classes <= ld, got M={m} classes={cls} ld={ld}")
+    if want_out:
+        out = _output(out, (N, D, H, W), bx.device)
+    if want_binary:
+        binary = _uint8(binary, (N, D, H, W), bx.device, "binary")
+    _on_current_device(lg, lb, bx, hw, out, binary)
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    _check(lib().wino_mask_paste_hw(ptr(lg), MASK_LAYOUTS[layout], ptr(lb), ptr(bx), ptr(hw), N, D, cls, m, ld, H, W,
+                                    threshold, ptr(out) if want_out else None, ptr(binary) if want_binary else None,
+                                    _stream()), "wino_mask_paste_hw")
+    return (out if want_out else None), (binary if want_binary else None)
+
+
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
     """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
     bounds by the kernel)."""
@@ -1382,4 +1464,4 @@ from .resnet import ResNet  # noqa: E402  (whole networks on the operators above
 from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
-from .detection import BoxHead, MaskHead, RPN, FasterRCNN  # noqa: E402
+from .detection import BoxHead, MaskHead, RPN, FasterRCNN, MaskRCNN  # noqa: E402

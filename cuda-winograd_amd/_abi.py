@@ -177,6 +177,8 @@ SIGNATURES = {
     # ---- box decoding and batched NMS
     "wino_box_decode_hw": (i, [vp] + [i] * 6 + [vp] + [i] * 4 + [vp] + [c_float] * 5 + [vp, c_long, c_long] * 2 + [vp]),
     "wino_batched_nms_hw": (i, [vp] * 3 + [i] * 2 + [c_float] * 3 + [i] + [vp] * 4 + [sz, vp]),
+    # ---- mask selection and paste
+    "wino_mask_paste_hw": (i, [vp, i] + [vp] * 3 + [i] * 7 + [c_float] + [vp] * 3),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

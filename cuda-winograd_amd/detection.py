@@ -39,9 +39,17 @@ nextafter(0.05) (torchvision's strict >).  Named deviation: the result is torchv
 ``roi_heads.box_predictor.*``) composes ResNetFPN(padded) -> RPN -> multiscale_roi_align -> BoxHead -> postprocess; after
 ``prepare(N, H, W)`` a forward reads no device data on the host and is captured into one graph.
 
-Not built: ``GeneralizedRCNNTransform`` (resize / normalise / batching) and the mapping of boxes back to original image
-sizes, Mask R-CNN's mask selection and paste, a select / sort kernel (torch's ``topk`` / ``sort`` stay), Keypoint R-CNN,
-RetinaNet and the BN variants of the v2 heads.
+``MaskRCNN.from_state_dict(sd, arch)`` adds ``roi_heads.mask_head.*`` / ``roi_heads.mask_predictor.*`` (split off before
+``BoxHead``'s validator, which rejects keys it does not know).  ``postprocess_detections(rois_out=...)`` lets
+``batched_nms`` write the detections as RoIAlign rows, ``(n, box)`` then ``(-1, 0, 0, 0, 0)``; on them run
+``multiscale_roi_align(P = mask_P, in_padded, out_padded)`` -> ``MaskHead(raw=True)`` (the logits GEMM's output, no
+permute copy) -> ``paste_masks(layout="gemm_rows")``: torchvision's ``maskrcnn_inference`` + ``paste_masks_in_image`` in
+one launch, ``"masks"`` [N][D][H][W] float32 and / or ``"masks_binary"`` uint8, planes past ``count`` zero (label -1).
+Like the rest, a forward after ``prepare`` reads no device data on the host and is captured into one graph.
+
+Not built: ``GeneralizedRCNNTransform`` (resize / normalise / batching) and the mapping of boxes and masks back to
+original image sizes, a select / sort kernel (torch's ``topk`` / ``sort`` stay), Keypoint R-CNN, RetinaNet and the BN
+variants of the v2 heads.
 
 The key names above are written from memory of torchvision's source and have not been checked against an installed
 torchvision; the tests build their own state dicts under these names.
@@ -253,10 +261,11 @@ class MaskHead(Net):
             conv1x1_prepare(R * P * P * 4, C, kp)
         self._shape = (R, P)
 
-    def forward(self, pooled_padded: torch.Tensor) -> torch.Tensor:
+    def forward(self, pooled_padded: torch.Tensor, raw: bool = False):
         """pooled_padded [R][P+2][P+2][C] float32 with a zero ring (roi_align's out_padded output; it is not written) ->
         mask logits [R][classes][2P][2P], a tensor of the head's, valid until the next forward.  A new (R, P) re-runs
-        prepare()."""
+        prepare().  raw=True: returns (the logits GEMM's output [R*P*P*4][ld] with rows ordered (r, y, x, dy, dx) and the
+        classes in its first columns, ld) and skips the permute copy: paste_masks' "gemm_rows" layout."""
         x, C = pooled_padded, self.in_channels
         if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or x.shape[1] != x.shape[2]:
             raise WinoError(f"pooled_padded must be [R][P+2][P+2][{C}]")
@@ -274,6 +283,8 @@ class MaskHead(Net):
             conv1x1_bn_ex(src, self.wd, self.bd, ones[: 4 * C], A_PADDED | RELU, out=self._up, hw=(P, P))
             # rows (r, y, x) x columns (dy, dx, c) are rows (r, y, x, dy, dx) x columns c: the logits GEMM's A as it stands
             conv1x1_bn(self._up.view(R * P * P * 4, C), self.wl, self.bl, ones[:kp], False, out=self._scores)
+            if raw:
+                return self._scores, kp
             scores = self._scores.view(R, P, P, 2, 2, kp)[..., : self.classes]
             self._masks.view(R, self.classes, P, 2, P, 2).copy_(scores.permute(0, 5, 1, 3, 2, 4))
         return self._masks
@@ -430,7 +441,7 @@ class RPN(Net):
 
 def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw: torch.Tensor, classes: int,
                            score_thresh: float = SCORE_THRESH_STRICT, nms_thresh: float = 0.5, detections: int = 100,
-                           min_size: float = 1e-2, max_candidates=None, stages=None):
+                           min_size: float = 1e-2, max_candidates=None, stages=None, rois_out=None):
     """torchvision's RoIHeads.postprocess_detections with fixed-size outputs and no host read.  head_out [R][kp]: BoxHead's
     one GEMM output (class logits at 0..classes, deltas at classes..5*classes), R = N * per rows; rois [R][5] with padding
     rows of index -1; image_hw [N][2].  softmax (torch), box_decode in boxes mode on head_out in place with weights
@@ -438,7 +449,8 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
     by score, batched_nms with groups = label.  score_thresh is >=: the default is nextafter(0.05), torchvision's strict >.
     Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D] int64 (-1 past count), "count" [N], "overflow" [N]}.
     Named deviation: the result equals torchvision's whenever at most max_candidates scores of an image pass the
-    threshold; overflow[n] (computed on the device) says when more did."""
+    threshold; overflow[n] (computed on the device) says when more did.  rois_out: a tensor [N][D][5] that batched_nms
+    fills with the detections as RoIAlign rows, (n, box) then (-1, 0, 0, 0, 0): the mask branch's input."""
     from . import batched_nms, box_decode
     N, R, classes = int(image_hw.shape[0]), int(rois.shape[0]), int(classes)
     if classes < 2 or R % N or head_out.dim() != 2 or int(head_out.shape[0]) != R or int(head_out.shape[1]) < 5 * classes:
@@ -458,7 +470,8 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
     clabels = (top.indices % fg + 1).to(torch.int32).contiguous()
     cscores = top.values.contiguous()
     overflow = (scores >= score_thresh).sum(dim=1) > kc
-    keep, count = batched_nms(cboxes, cscores, clabels, nms_thresh, min_size, score_thresh, int(detections))
+    keep, count = batched_nms(cboxes, cscores, clabels, nms_thresh, min_size, score_thresh, int(detections),
+                              rois_out=rois_out)[:2]
     kept = keep >= 0
     at = keep.clamp(min=0).long()
     out = {"boxes": cboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
@@ -524,14 +537,11 @@ class FasterRCNN(Net):
             self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=torch.float32, device=dev)
         self._shape = (N, H, W)
 
-    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
-        """x [N][3][H][W] float32, already normalised; image_sizes: None (every image fills the batch) or a float32
-        device tensor [N][2] of (H_img, W_img).  Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D], "count" [N],
-        "overflow" [N]}, rows past count zero with label -1; with stages=True also every intermediate."""
+    def _detect(self, x, image_sizes, st, rois_out=None):
+        """The stages of forward; returns (the result dict, the pyramid, the box head's pooled input, image_hw)."""
         from . import multiscale_roi_align
         self._begin(x)
         N, H, W = self._shape
-        st = {} if stages else None
         hw = self._full_hw if image_sizes is None else image_sizes
         if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
             raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
@@ -541,9 +551,19 @@ class FasterRCNN(Net):
             pooled = multiscale_roi_align(feats, rois, (H, W), self.box_head.P, 2, in_padded=True, out=self._pooled)
             self.box_head(pooled)
             out = postprocess_detections(self.box_head._scores, rois, hw, self.box_head.classes, self.score_thresh,
-                                         self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st)
-        if stages:
+                                         self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st,
+                                         rois_out=rois_out)
+        if st is not None:
             st.update(features=feats, pooled=pooled, head_out=self.box_head._scores)
+        return out, feats, pooled, hw
+
+    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
+        """x [N][3][H][W] float32, already normalised; image_sizes: None (every image fills the batch) or a float32
+        device tensor [N][2] of (H_img, W_img).  Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D], "count" [N],
+        "overflow" [N]}, rows past count zero with label -1; with stages=True also every intermediate."""
+        st = {} if stages else None
+        out = self._detect(x, image_sizes, st)[0]
+        if stages:
             out.update(st)
         return out
 
@@ -555,6 +575,106 @@ class FasterRCNN(Net):
                  "labels": out["labels"][n, :c].clone()} for n, c in enumerate(counts)]
 
 
-__all__ = ["BoxHead", "MaskHead", "RPN", "FasterRCNN", "postprocess_detections", "base_anchors", "pack_rpn_head",
+MASK_PREFIXES = ("roi_heads.mask_head.", "roi_heads.mask_predictor.")
+MASK_OUTPUTS = ("prob", "binary", "both")
+
+
+def split_mask_state_dict(sd):
+    """(the Faster R-CNN keys as they are, the mask branch's keys below `roi_heads.`): BoxHead's validator rejects keys
+    it does not know, so the mask branch leaves before it sees the rest."""
+    rest, mask = {}, {}
+    for k, v in sd.items():
+        if k.startswith(MASK_PREFIXES):
+            mask[k[len("roi_heads."):]] = v
+        else:
+            rest[k] = v
+    return rest, mask
+
+
+class MaskRCNN(FasterRCNN):
+    """torchvision's maskrcnn_resnet50_fpn at test time: FasterRCNN, then on its detections multiscale_roi_align
+    (padded, P = mask_P) -> MaskHead (raw logits) -> paste_masks in the gemm_rows layout.  The masks are image-size planes
+    [N][D][H][W] of the normalised batch.  Out of scope, as for FasterRCNN: GeneralizedRCNNTransform and the mapping back
+    to original image sizes."""
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, mask_P: int = 14,
+                        masks: str = "prob", mask_threshold: float = 0.5, **faster_rcnn) -> "MaskRCNN":
+        """sd: FasterRCNN's keys plus roi_heads.mask_head.* and roi_heads.mask_predictor.*.  masks: which tensors a
+        forward returns, "prob" ("masks", float32), "binary" ("masks_binary", uint8 = prob > mask_threshold) or "both".
+        Every other argument is FasterRCNN.from_state_dict's."""
+        mask_P, mask_threshold = int(mask_P), float(mask_threshold)
+        if masks not in MASK_OUTPUTS:
+            raise WinoError(f"masks must be one of {MASK_OUTPUTS}, got {masks!r}")
+        if mask_P < 2 or mask_P % 2 or 2 * mask_P > 62:
+            raise WinoError(f"mask_P={mask_P}: need an even mask_P with 2 <= mask_P <= 31")
+        if mask_threshold != mask_threshold:
+            raise WinoError("mask_threshold is NaN")
+        rest, mask_sd = split_mask_state_dict(sd)
+        mask_classes = validate_mask_head_state_dict(mask_sd, out_channels)
+        m = super().from_state_dict(rest, arch, num_classes, out_channels, device=faster_rcnn.pop("device", None),
+                                    **faster_rcnn)
+        if mask_classes != m.box_head.classes:
+            raise WinoError(f"state dict: the mask head has {mask_classes} classes, the box head {m.box_head.classes}")
+        m.mask_head = MaskHead.from_state_dict(mask_sd, out_channels, m.device)
+        m.mask_P, m.masks, m.mask_threshold = mask_P, masks, mask_threshold
+        return m
+
+    def prepare(self, N: int, H: int, W: int) -> None:
+        """FasterRCNN.prepare, then the mask branch's tensors: the mask RoIAlign output [N*D][P+2][P+2][C], the detection
+        rois [N][D][5], int32 labels [N][D] and the masks [N][D][H][W]."""
+        super().prepare(N, H, W)
+        self._shape = None   # (until the rest is in place)
+        N, H, W, D, P, dev = int(N), int(H), int(W), self.detections, self.mask_P, self.device
+        with torch.cuda.device(dev):
+            self.mask_head.prepare(N * D, P)
+            self._mask_pooled = torch.empty((N * D, P + 2, P + 2, self.mask_head.in_channels), dtype=torch.float32, device=dev)
+            self._det_rois = torch.empty((N, D, 5), dtype=torch.float32, device=dev)
+            self._labels32 = torch.empty((N, D), dtype=torch.int32, device=dev)
+            self._masks = torch.empty((N, D, H, W), dtype=torch.float32, device=dev) if self.masks != "binary" else None
+            self._masks_bin = torch.empty((N, D, H, W), dtype=torch.uint8, device=dev) if self.masks != "prob" else None
+        self._shape = (N, H, W)
+
+    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
+        """FasterRCNN.forward's dict plus "masks" [N][D][H][W] float32 and / or "masks_binary" [N][D][H][W] uint8 (planes
+        past count are zero): tensors of the model's, valid until the next forward.  stages=True adds mask_rois,
+        mask_pooled and mask_logits (the raw [N*D*P*P*4][ld] GEMM output)."""
+        from . import multiscale_roi_align, paste_masks
+        st = {} if stages else None
+        self._begin(x)   # (prepare before _det_rois is named)
+        out, feats, _, hw = self._detect(x, image_sizes, st, rois_out=self._det_rois)
+        N, H, W = self._shape
+        D, P = self.detections, self.mask_P
+        with torch.cuda.device(self.device):
+            pooled = multiscale_roi_align(feats, self._det_rois.view(N * D, 5), (H, W), P, 2, in_padded=True,
+                                          out_padded=True, out=self._mask_pooled)
+            logits, _ = self.mask_head(pooled, raw=True)
+            self._labels32.copy_(out["labels"])
+            prob, binary = paste_masks(logits, self._labels32, out["boxes"], hw, H, W, M=2 * P,
+                                       classes=self.mask_head.classes, layout="gemm_rows", out=self._masks,
+                                       binary=self._masks_bin, want_out=False, threshold=self.mask_threshold)
+        if prob is not None:
+            out["masks"] = prob
+        if binary is not None:
+            out["masks_binary"] = binary
+        if stages:
+            st.update(mask_rois=self._det_rois, mask_pooled=pooled, mask_logits=logits)
+            out.update(st)
+        return out
+
+    @staticmethod
+    def to_lists(out):
+        """torchvision's list of {"boxes", "scores", "labels", "masks" [c][1][H][W]} per image ("masks_binary" likewise
+        when the model returns it).  Synchronises (it reads count)."""
+        counts = out["count"].tolist()
+        res = FasterRCNN.to_lists(out)
+        for n, c in enumerate(counts):
+            for key in ("masks", "masks_binary"):
+                if key in out:
+                    res[n][key] = out[key][n, :c].unsqueeze(1).clone()
+        return res
+
+
+__all__ = ["BoxHead", "MaskHead", "RPN", "FasterRCNN", "MaskRCNN", "split_mask_state_dict", "postprocess_detections", "base_anchors", "pack_rpn_head",
            "expected_rpn_keys", "expected_box_head_keys", "expected_mask_head_keys", "validate_box_head_state_dict",
            "validate_mask_head_state_dict", "pack_fc6", "pack_predictor", "pack_deconv", "pack_logits"]

@@ -66,7 +66,7 @@ extern "C" {
  * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
  * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
- * wino_roi_align_launches, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_roi_align_launches, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -843,6 +843,47 @@ int wino_box_decode_hw(const float* head, int N, int rows_per_image, int ld, int
 int wino_batched_nms_hw(const float* boxes, const float* scores, const int* groups, int S, int R, float iou_thresh,
                         float min_size, float score_thresh, int max_out, int* keep, int* count, float* rois_out,
                         void* workspace, size_t workspace_bytes, wino_stream_t s);
+
+/* ---- mask selection and paste: the output stage of Mask R-CNN (mask_paste.hip) -------------------
+ * torchvision's maskrcnn_inference followed by paste_masks_in_image(padding = 1) (CPU path: expand_masks, expand_boxes,
+ * .to(int64), paste_mask_in_image), operation by operation, for all detections in one HIP launch: detection r = n D + d
+ * takes the mask of class labels[r] out of the mask head's logits, applies the sigmoid and pastes it into plane (n, d).
+ *   logits    DEVICE, read in place, in one of two layouts:
+ *             WINO_MASK_LAYOUT_PLANES     [R][classes][M][M], torchvision's
+ *             WINO_MASK_LAYOUT_GEMM_ROWS  [R P P 4][ld], rows ordered (r, y, x, dy, dx), M = 2 P: the output of the mask
+ *                                         head's logits GEMM.  Pixel (Y, X) of class c is
+ *                                         logits[(((r P + (Y >> 1)) P + (X >> 1)) 4 + (Y & 1) 2 + (X & 1)) ld + c]
+ *             R = N D.  `ld` is ignored for PLANES
+ *   labels    DEVICE [R] int32.  A label outside [0, classes) (a padding row's -1) makes the plane all zeros and reads no
+ *             logit and no box
+ *   boxes     DEVICE [R][4] fp32 (x1, y1, x2, y2)
+ *   image_hw  DEVICE [N][2] floats (H_img, W_img) as in wino_box_decode_hw, truncated to int and clamped to [0, H] x
+ *             [0, W]: torchvision's im_h, im_w.  The plane beyond it is zero
+ *   out       [N][D][H][W] fp32 (torchvision's [D][1][H][W] per image), or NULL
+ *   binary    [N][D][H][W] uint8 = value > threshold, or NULL.  With both outputs the bytes are those of the stored fp32
+ *             values
+ * Box (fp32, in this order, no product folded into a sum): scale = float(M + 2) / M; w_half = (x2 - x1) 0.5 scale, x_c =
+ * (x2 + x1) 0.5; ex1 = x_c - w_half, ex2 = x_c + w_half, likewise y; bx1 = (int) ex1 ... truncate toward zero (-0.5 -> 0).
+ * Named deviation: the expanded coordinates are clamped to +-2^30 before the conversion, and everything below is 64-bit
+ * integer arithmetic (torch would have to allocate w x h for such a box).
+ * w = max(bx2 - bx1 + 1, 1), h likewise.  Window: x0 = max(bx1, 0), x1e = min(bx2 + 1, im_w), likewise y; an empty window
+ * gives a zero plane.  Inside the window the value at (y, x) is the bilinear align_corners=False resize to h x w, at
+ * (y - by1, x - bx1), of the (M + 2)^2 map that holds 1 / (1 + exp(-logit)) (computed once per mask element) inside a ring
+ * of zeros, with wino_resize_bilinear_hw's exact integer source coordinates per axis (in = M + 2, out = w or h) and its
+ * value formula, all four taps always multiplied: a NaN logit reaches exactly the output pixels whose taps include it.
+ * Outside the window the value is 0.  A box with a coordinate that is not finite gives NaN in the whole image window
+ * [0, im_h) x [0, im_w) of its plane, reads no logit and changes no other plane.
+ * 1 <= M <= 62; GEMM_ROWS: M even and classes <= ld; classes >= 1; N, D >= 0 (either 0: WINO_OK, nothing launched);
+ * H, W >= 1 of any parity; one plane below 2^31 elements (WINO_E_SHAPE otherwise).  Any N D: planes are addressed from
+ * 64-bit bases, the outputs may pass 4 GiB.  A NULL input, out and binary both NULL, a pointer that is not 16-byte
+ * aligned, a layout that is neither of the two, a NaN threshold, or an output that overlaps an input or the other output
+ * is WINO_E_ARG.  Every check comes before the launch.  No workspace and no stream scratch: the call can be captured
+ * into a graph as it is. */
+#define WINO_MASK_LAYOUT_PLANES 0
+#define WINO_MASK_LAYOUT_GEMM_ROWS 1
+int wino_mask_paste_hw(const float* logits, int layout, const int* labels, const float* boxes, const float* image_hw,
+                       int N, int D, int classes, int M, int ld, int H, int W, float threshold, float* out, void* binary,
+                       wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
