@@ -952,6 +952,97 @@ def batched_nms(boxes, scores=None, groups=None, iou_thresh: float = 0.5, min_si
     return (keep, count) if rois is None else (keep, count, rois)
 
 
+SELECT_MAX_K = 8192   # the keys one workgroup of select.hip sorts in LDS: the most a part can keep
+
+
+def _select_parts(k, n, off, stride=None):
+    """(k, n, off) as equally long lists of ints: each an int (one part) or a sequence; n defaults to the rest of the
+    row behind off, off to 0."""
+    ks = [int(v) for v in k] if isinstance(k, (list, tuple)) else [int(k)]
+    parts = len(ks)
+
+    def seq(v, name, default):
+        if v is None:
+            return default
+        v = [int(x) for x in v] if isinstance(v, (list, tuple)) else [int(v)]
+        if len(v) != parts:
+            raise WinoError(f"select: {name} has {len(v)} entries for {parts} parts")
+        return v
+
+    offs = seq(off, "off", [0] * parts)
+    if n is None and stride is None:
+        raise WinoError("select: n is needed")
+    ns = seq(n, "n", None if stride is None else [int(stride) - o for o in offs])
+    return ks, ns, offs
+
+
+def select_workspace_bytes(N: int, n, k) -> int:
+    """Bytes of select_topk's workspace for N images whose parts have n[p] scores and keep k[p] (ints or sequences), the
+    formula of winograd_mi355x.h (wino_select_topk_hw refuses less): per part longer than 8192 scores three histograms
+    and a list length, one word per chunk of 2048 scores and k[p] 64-bit keys, each region rounded up to 16 bytes.  0 when
+    every n[p] <= 8192.  Host only; raises WinoError outside the entry point's limits."""
+    ks, ns, _ = _select_parts(k, n, None)
+    N = int(N)
+    if N < 0 or not 1 <= len(ks) <= 8 or min(ns) < 0 or min(ks) < 1 or max(ks) > SELECT_MAX_K:
+        raise WinoError(f"select: unsupported shape N={N} n={ns} k={ks} (need N >= 0, 1 <= parts <= 8, n[p] >= 0, "
+                        f"1 <= k[p] <= {SELECT_MAX_K})")
+    long_parts = [(n_p, k_p) for n_p, k_p in zip(ns, ks) if n_p > SELECT_MAX_K]
+    round16 = lambda b: (b + 15) // 16 * 16
+    header, chunk = 3 * 2048 + 4, 2048   # select.hip's SEL_HDR words per long segment and SEL_CHUNK scores per workgroup
+    return (round16(N * len(long_parts) * header * 4) + round16(N * sum((n_p + chunk - 1) // chunk for n_p, _ in long_parts) * 4)
+            + round16(N * sum(k_p for _, k_p in long_parts) * 8))
+
+
+def select_topk(scores, k, n=None, off=None, score_thresh=None, boxes=None, out_idx=None, out_vals=None, out_count=None,
+                out_boxes=None, workspace=None):
+    """Segmented top-k and sort on the device (select.hip), with fixed-size outputs and an order that is a function of the
+    inputs: torch.sort(descending=True, stable=True) truncated to k (NaN first, -0.0 == +0.0, ties to the lower index).
+    scores [N][stride] float32.  k, n, off: ints, or sequences for several parts; part p of every image reads n[p] scores
+    from column off[p] (default: one part over the whole row) and keeps the best min(k[p], candidates), where with
+    score_thresh given only scores >= score_thresh are candidates.  Part p writes k[p] rows behind those of the parts
+    before it.  Returns (idx [N][sum k] int32: column indices within the row, -1 past the kept count; vals [N][sum k]: the
+    scores' own bits, 0.0 past it; count [N][parts] int32[; boxes [N][sum k][4]: with boxes [N][stride][4] given, the kept
+    scores' rows, zeros past the count]).  Given outputs may be wider than sum k; what lies behind is not written.
+    workspace: select_workspace_bytes(N, n, k) bytes.  No scratch of the library's: capturable into a graph without a
+    prepare."""
+    sc = _dev(scores, "scores")
+    if sc.dim() != 2:
+        raise WinoError("scores must be [N][stride]")
+    N, stride = int(sc.shape[0]), int(sc.shape[1])
+    ks, ns, offs = _select_parts(k, n, off, stride)
+    parts, ksum = len(ks), sum(ks)
+    bx = None
+    if boxes is not None:
+        bx = _dev(boxes, "boxes")
+        if bx.dim() != 3 or int(bx.shape[0]) != N or int(bx.shape[2]) != 4:
+            raise WinoError(f"boxes must be [{N}][stride][4]")
+
+    def slot(t, tail, dtype, name):
+        if t is None:
+            return torch.empty((N, ksum) + tail, dtype=dtype, device=sc.device)
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous()
+                or t.dim() != 2 + len(tail) or int(t.shape[0]) != N or tuple(t.shape[2:]) != tail or int(t.shape[1]) < ksum):
+            raise WinoError(f"{name} must be a contiguous {dtype} CUDA(HIP) tensor [{N}][>= {ksum}]{list(tail)}")
+        return t
+
+    idx = slot(out_idx, (), torch.int32, "out_idx")
+    vals = slot(out_vals, (), torch.float32, "out_vals")
+    count = _int32(out_count, (N, parts), sc.device, "out_count")
+    ob = None if bx is None else slot(out_boxes, (4,), torch.float32, "out_boxes")
+    out_stride = int(idx.shape[1])
+    if int(vals.shape[1]) != out_stride or (ob is not None and int(ob.shape[1]) != out_stride):
+        raise WinoError("select_topk: out_idx, out_vals and out_boxes must have the same row length")
+    ws = _workspace(workspace, select_workspace_bytes(N, ns, ks), sc.device)
+    _on_current_device(sc, bx, idx, vals, count, ob, ws)
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    _check(lib().wino_select_topk_hw(ptr(sc), N, stride, parts, (c_long * parts)(*offs), (c_int * parts)(*ns),
+                                     (c_int * parts)(*ks), 0 if score_thresh is None else 1,
+                                     0.0 if score_thresh is None else float(score_thresh), ptr(idx), ptr(vals), ptr(count),
+                                     out_stride, ptr(bx), 0 if bx is None else int(bx.shape[1]), ptr(ob), ptr(ws),
+                                     ws.numel() * 4, _stream()), "wino_select_topk_hw")
+    return (idx, vals, count) if ob is None else (idx, vals, count, ob)
+
+
 MASK_LAYOUTS = {"planes": 0, "gemm_rows": 1}   # WINO_MASK_LAYOUT_*
 MASK_MAX_M = 62
 

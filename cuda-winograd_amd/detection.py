@@ -30,7 +30,12 @@ A..5A) and runs per level ``conv3x3_bn_relu`` -> ``conv1x1_bn_ex(A_PADDED)`` -> 
 computed on the host in float32 as AnchorGenerator does; strides image // grid; "pool" copied once into a zero-ring
 tensor), then ``filter_proposals`` with torch as plumbing: per-level ``topk`` on the logits, ``gather``, one stable
 descending ``sort`` per image on the logit (the order of the probabilities wherever they differ, ties to the lower
-index), ``sigmoid``, and ``batched_nms`` with groups = level.  ``postprocess_detections`` is softmax, ``box_decode`` in
+index), ``sigmoid``, and ``batched_nms`` with groups = level.  ``select="kernel"`` (``RPN``, ``postprocess_detections``,
+``FasterRCNN`` / ``MaskRCNN.from_state_dict``; the default ``"torch"`` is the code above, bit for bit) hands the
+selecting and ordering to ``select_topk``: one call over the five levels (top k per level, logits and boxes gathered
+into ``filter_proposals``' slots), one over the gathered logits (the stable sort, boxes written in order), and one in
+``postprocess_detections`` (the candidates and their boxes).  Equal scores then go to the lower index everywhere, which
+torch's ``topk`` does not promise; at most 8192 rows per call.  ``postprocess_detections`` is softmax, ``box_decode`` in
 boxes mode straight on the box head's GEMM output, class 0 dropped, padding rows' scores 0, per image the ``topk`` of at
 most ``max_candidates`` (default min(all, 8192)), ``batched_nms`` with groups = label and score_thresh =
 nextafter(0.05) (torchvision's strict >).  Named deviation: the result is torchvision's whenever at most
@@ -48,8 +53,7 @@ one launch, ``"masks"`` [N][D][H][W] float32 and / or ``"masks_binary"`` uint8, 
 Like the rest, a forward after ``prepare`` reads no device data on the host and is captured into one graph.
 
 Not built: ``GeneralizedRCNNTransform`` (resize / normalise / batching) and the mapping of boxes and masks back to
-original image sizes, a select / sort kernel (torch's ``topk`` / ``sort`` stay), Keypoint R-CNN, RetinaNet and the BN
-variants of the v2 heads.
+original image sizes, Keypoint R-CNN, RetinaNet and the BN variants of the v2 heads.
 
 The key names above are written from memory of torchvision's source and have not been checked against an installed
 torchvision; the tests build their own state dicts under these names.
@@ -296,6 +300,14 @@ ANCHOR_RATIOS = (0.5, 1.0, 2.0)
 RPN_LEVELS = ("0", "1", "2", "3", "pool")
 BOX_WEIGHTS = (10.0, 10.0, 5.0, 5.0)
 SCORE_THRESH_STRICT = 0.05000000447034836   # nextafter(float32(0.05), inf): torchvision keeps score > 0.05
+SELECTS = ("torch", "kernel")
+SELECT_MAX_ROWS = 8192   # what one select_topk part can keep
+
+
+def _check_select(select) -> str:
+    if select not in SELECTS:
+        raise WinoError(f"select must be one of {SELECTS}, got {select!r}")
+    return select
 
 
 def base_anchors(sizes, ratios) -> torch.Tensor:
@@ -330,8 +342,10 @@ class RPN(Net):
     box_decode in grid mode per level, and filter_proposals with torch as plumbing (topk, gather, sigmoid, sort) around
     batched_nms.  No host read of device data after prepare()."""
 
-    def __init__(self, in_channels, sizes, ratios, pre_nms_top_n, post_nms_top_n, nms_thresh, score_thresh, min_size, device):
+    def __init__(self, in_channels, sizes, ratios, pre_nms_top_n, post_nms_top_n, nms_thresh, score_thresh, min_size, device,
+                 select="torch"):
         super().__init__(device)
+        self.select = _check_select(select)
         self.in_channels, self.sizes, self.ratios = int(in_channels), tuple(tuple(s) for s in sizes), tuple(ratios)
         self.A = len(self.sizes[0]) * len(self.ratios)
         self.pre, self.post = int(pre_nms_top_n), int(post_nms_top_n)
@@ -340,8 +354,10 @@ class RPN(Net):
     @classmethod
     def from_state_dict(cls, sd, in_channels: int = 256, sizes=ANCHOR_SIZES, ratios=ANCHOR_RATIOS, pre_nms_top_n: int = 1000,
                         post_nms_top_n: int = 1000, nms_thresh: float = 0.7, score_thresh: float = 0.0,
-                        min_size: float = 1e-3, device=None) -> "RPN":
-        """sd: the keys below torchvision's `rpn.` (head.conv.0.0, head.cls_logits, head.bbox_pred)."""
+                        min_size: float = 1e-3, device=None, select: str = "torch") -> "RPN":
+        """sd: the keys below torchvision's `rpn.` (head.conv.0.0, head.cls_logits, head.bbox_pred).  select: "torch"
+        (topk / sort / gather) or "kernel" (select_topk), see the module docstring."""
+        _check_select(select)
         if len(sizes) != len(RPN_LEVELS) or len({len(s) for s in sizes}) != 1:
             raise WinoError(f"rpn: {len(RPN_LEVELS)} levels need {len(RPN_LEVELS)} size tuples of one length")
         A = len(sizes[0]) * len(ratios)
@@ -351,7 +367,7 @@ class RPN(Net):
         if min(int(pre_nms_top_n), int(post_nms_top_n)) < 1:
             raise WinoError("rpn: pre_nms_top_n and post_nms_top_n must be at least 1")
         return cls._load(sd, None, device, in_channels, sizes, ratios, pre_nms_top_n, post_nms_top_n, nms_thresh,
-                         score_thresh, min_size)
+                         score_thresh, min_size, select=select)
 
     def _pack(self, sd, eps):
         conv = "head.conv" if "head.conv.weight" in sd else "head.conv.0.0"
@@ -367,7 +383,7 @@ class RPN(Net):
     def prepare(self, N: int, level_hw, image_size) -> None:
         """Allocate every tensor of the first stage for N images whose five levels are `level_hw` [(h, w)] and reserve
         the launches' stream scratch on the current stream.  Call it before capturing a forward into a graph."""
-        from . import nms_workspace_bytes
+        from . import nms_workspace_bytes, select_workspace_bytes
         N, C, kp, dev, f32 = int(N), self.in_channels, int(self.wp.shape[1]), self.device, torch.float32
         level_hw = [(int(h), int(w)) for h, w in level_hw]
         H, W = int(image_size[0]), int(image_size[1])
@@ -381,6 +397,9 @@ class RPN(Net):
             self._n = [h * w * self.A for h, w in level_hw]
             self._k = [min(self.pre, n) for n in self._n]
             total, K = sum(self._n), sum(self._k)
+            if self.select == "kernel" and K > SELECT_MAX_ROWS:
+                raise WinoError(f"rpn: select=\"kernel\" sorts at most {SELECT_MAX_ROWS} proposals per image, the levels "
+                                f"keep {K}")
             self._boxes = torch.empty((N, total, 4), dtype=f32, device=dev)
             self._logits = torch.empty((N, total), dtype=f32, device=dev)
             self._level_of = torch.cat([torch.full((k,), l, dtype=torch.int32) for l, k in enumerate(self._k)]).to(dev)
@@ -388,6 +407,16 @@ class RPN(Net):
             self._count = torch.empty((N,), dtype=torch.int32, device=dev)
             self._rois = torch.empty((N, self.post, 5), dtype=f32, device=dev)
             self._ws = torch.empty((nms_workspace_bytes(N, K) + 3) // 4, dtype=f32, device=dev)
+            if self.select == "kernel":
+                i32 = torch.int32
+                self._sel = dict(
+                    idx=torch.empty((N, K), dtype=i32, device=dev), logit=torch.empty((N, K), dtype=f32, device=dev),
+                    count=torch.empty((N, len(self._k)), dtype=i32, device=dev),
+                    boxes=torch.empty((N, K, 4), dtype=f32, device=dev),
+                    ws=torch.empty((select_workspace_bytes(N, self._n, self._k) + 3) // 4, dtype=f32, device=dev),
+                    order=torch.empty((N, K), dtype=i32, device=dev), slogit=torch.empty((N, K), dtype=f32, device=dev),
+                    count2=torch.empty((N, 1), dtype=i32, device=dev), sboxes=torch.empty((N, K, 4), dtype=f32, device=dev),
+                    ws2=torch.empty((select_workspace_bytes(N, K, K) + 3) // 4, dtype=f32, device=dev))
             for h, w in level_hw:
                 conv3x3_prepare(N, C, C, h, w)
                 conv1x1_prepare(N * h * w, C, kp)
@@ -398,7 +427,7 @@ class RPN(Net):
         """features: ResNetFPN(...)(x, padded=True); image_hw [N][2] float32 on the device (the clip sizes); image_size
         (H, W) of the batch.  Returns (rois [N * post][5] with padding rows of index -1, scores [N][post], count [N]):
         tensors of the module's, valid until the next forward.  `stages`: a dict that receives every intermediate."""
-        from . import batched_nms, box_decode
+        from . import batched_nms, box_decode, select_topk
         maps = [features[k] for k in RPN_LEVELS]
         N, C, kp, A = int(maps[0].shape[0]), self.in_channels, int(self.wp.shape[1]), self.A
         level_hw = tuple((int(m.shape[1]) - 2, int(m.shape[2]) - 2) for m in maps[:-1]) + \
@@ -416,16 +445,27 @@ class RPN(Net):
                 box_decode(self._head[l], self.base[l], image_hw, A, grid=self._grid[l], delta_col=A, score_col=0,
                            out_boxes=self._boxes, out_scores=self._logits, out_offset=off)
                 off += self._n[l]
-            # filter_proposals: torch as plumbing
-            idx, off = [], 0
-            for n, k in zip(self._n, self._k):
-                idx.append(self._logits[:, off:off + n].topk(k, dim=1, sorted=True).indices + off)
-                off += n
-            idx = torch.cat(idx, dim=1)
-            logit = self._logits.gather(1, idx)
-            slogit, order = torch.sort(logit, dim=1, descending=True, stable=True)   # (by logit: the order of the probabilities)
-            sidx = idx.gather(1, order)
-            sboxes = self._boxes.gather(1, sidx[:, :, None].expand(-1, -1, 4)).contiguous()
+            if self.select == "kernel":
+                # filter_proposals on select_topk: the levels' top k into the cat's slots, then the stable sort
+                b, offs = self._sel, [sum(self._n[:l]) for l in range(len(self._n))]
+                idx32, logit, _, lboxes = select_topk(self._logits, self._k, self._n, offs, boxes=self._boxes,
+                                                      out_idx=b["idx"], out_vals=b["logit"], out_count=b["count"],
+                                                      out_boxes=b["boxes"], workspace=b["ws"])
+                order32, slogit, _, sboxes = select_topk(logit, sum(self._k), boxes=lboxes, out_idx=b["order"],
+                                                         out_vals=b["slogit"], out_count=b["count2"],
+                                                         out_boxes=b["sboxes"], workspace=b["ws2"])
+                idx, order = idx32.long(), order32.long()
+            else:
+                # filter_proposals: torch as plumbing
+                idx, off = [], 0
+                for n, k in zip(self._n, self._k):
+                    idx.append(self._logits[:, off:off + n].topk(k, dim=1, sorted=True).indices + off)
+                    off += n
+                idx = torch.cat(idx, dim=1)
+                logit = self._logits.gather(1, idx)
+                slogit, order = torch.sort(logit, dim=1, descending=True, stable=True)   # (by logit: the order of the probabilities)
+                sidx = idx.gather(1, order)
+                sboxes = self._boxes.gather(1, sidx[:, :, None].expand(-1, -1, 4)).contiguous()
             slevel = self._level_of[order].contiguous()
             prob = torch.sigmoid(slogit)
             batched_nms(sboxes, prob, slevel, self.nms_thresh, self.min_size, self.score_thresh, self.post, self._rois,
@@ -441,7 +481,7 @@ class RPN(Net):
 
 def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw: torch.Tensor, classes: int,
                            score_thresh: float = SCORE_THRESH_STRICT, nms_thresh: float = 0.5, detections: int = 100,
-                           min_size: float = 1e-2, max_candidates=None, stages=None, rois_out=None):
+                           min_size: float = 1e-2, max_candidates=None, stages=None, rois_out=None, select: str = "torch"):
     """torchvision's RoIHeads.postprocess_detections with fixed-size outputs and no host read.  head_out [R][kp]: BoxHead's
     one GEMM output (class logits at 0..classes, deltas at classes..5*classes), R = N * per rows; rois [R][5] with padding
     rows of index -1; image_hw [N][2].  softmax (torch), box_decode in boxes mode on head_out in place with weights
@@ -450,8 +490,11 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
     Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D] int64 (-1 past count), "count" [N], "overflow" [N]}.
     Named deviation: the result equals torchvision's whenever at most max_candidates scores of an image pass the
     threshold; overflow[n] (computed on the device) says when more did.  rois_out: a tensor [N][D][5] that batched_nms
-    fills with the detections as RoIAlign rows, (n, box) then (-1, 0, 0, 0, 0): the mask branch's input."""
-    from . import batched_nms, box_decode
+    fills with the detections as RoIAlign rows, (n, box) then (-1, 0, 0, 0, 0): the mask branch's input.
+    select: "torch" (topk and gather) or "kernel" (one select_topk call; equal scores, the padding rows' zeros among
+    them, then go to the lower index; max_candidates <= 8192)."""
+    from . import batched_nms, box_decode, select_topk
+    _check_select(select)
     N, R, classes = int(image_hw.shape[0]), int(rois.shape[0]), int(classes)
     if classes < 2 or R % N or head_out.dim() != 2 or int(head_out.shape[0]) != R or int(head_out.shape[1]) < 5 * classes:
         raise WinoError(f"postprocess_detections: head_out {tuple(head_out.shape)}, rois {tuple(rois.shape)}, N={N}, "
@@ -460,15 +503,23 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
     M = per * fg
     kc = M if max_candidates is None else int(max_candidates)
     kc = max(1, min(kc, M, 8192 if max_candidates is None else M))
+    if select == "kernel" and kc > SELECT_MAX_ROWS:
+        raise WinoError(f"postprocess_detections: select=\"kernel\" keeps at most {SELECT_MAX_ROWS} candidates, "
+                        f"max_candidates={kc}")
     prob = torch.softmax(head_out[:, :classes], dim=-1)
     boxes, _ = box_decode(head_out, rois[:, 1:5].contiguous(), image_hw, classes, BOX_WEIGHTS, None, classes)
     boxes = boxes.view(N, per, classes, 4)[:, :, 1:].reshape(N, M, 4)
     valid = (rois[:, 0] >= 0).view(N, per, 1)
     scores = (prob.view(N, per, classes)[:, :, 1:] * valid).reshape(N, M)
-    top = scores.topk(kc, dim=1, sorted=True)
-    cboxes = boxes.gather(1, top.indices[:, :, None].expand(-1, -1, 4)).contiguous()
-    clabels = (top.indices % fg + 1).to(torch.int32).contiguous()
-    cscores = top.values.contiguous()
+    if select == "kernel":
+        cidx32, cscores, _, cboxes = select_topk(scores, kc, boxes=boxes)
+        cidx = cidx32.long()
+    else:
+        top = scores.topk(kc, dim=1, sorted=True)
+        cidx = top.indices
+        cboxes = boxes.gather(1, cidx[:, :, None].expand(-1, -1, 4)).contiguous()
+        cscores = top.values.contiguous()
+    clabels = (cidx % fg + 1).to(torch.int32).contiguous()
     overflow = (scores >= score_thresh).sum(dim=1) > kc
     keep, count = batched_nms(cboxes, cscores, clabels, nms_thresh, min_size, score_thresh, int(detections),
                               rois_out=rois_out)[:2]
@@ -479,7 +530,7 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
            "labels": torch.where(kept, clabels.gather(1, at).long(), torch.full_like(at, -1)),
            "count": count, "overflow": overflow}
     if stages is not None:
-        stages.update(class_prob=prob, class_boxes=boxes, class_scores=scores, cand_idx=top.indices, cand_boxes=cboxes,
+        stages.update(class_prob=prob, class_boxes=boxes, class_scores=scores, cand_idx=cidx, cand_boxes=cboxes,
                       cand_scores=cscores, cand_labels=clabels, det_keep=keep)
     return out
 
@@ -489,8 +540,10 @@ class FasterRCNN(Net):
     multiscale_roi_align -> BoxHead -> postprocess_detections, on the already normalised batch.  Out of scope:
     GeneralizedRCNNTransform (resize / normalise / batching) and the mapping of boxes back to original image sizes."""
 
-    def __init__(self, backbone, rpn, box_head, detections, score_thresh, nms_thresh, max_candidates, device):
+    def __init__(self, backbone, rpn, box_head, detections, score_thresh, nms_thresh, max_candidates, device,
+                 select="torch"):
         super().__init__(device)
+        self.select = _check_select(select)
         self.backbone, self.rpn, self.box_head = backbone, rpn, box_head
         self.detections, self.score_thresh, self.nms_thresh = int(detections), float(score_thresh), float(nms_thresh)
         self.max_candidates = max_candidates
@@ -500,10 +553,12 @@ class FasterRCNN(Net):
                         rpn_pre_nms_top_n: int = 1000, rpn_post_nms_top_n: int = 1000, rpn_nms_thresh: float = 0.7,
                         rpn_score_thresh: float = 0.0, box_score_thresh: float = SCORE_THRESH_STRICT,
                         box_nms_thresh: float = 0.5, box_detections_per_img: int = 100, max_candidates=None, sizes=ANCHOR_SIZES,
-                        ratios=ANCHOR_RATIOS, device=None) -> "FasterRCNN":
+                        ratios=ANCHOR_RATIOS, device=None, select: str = "torch") -> "FasterRCNN":
         """sd under torchvision's key names: backbone.body.*, backbone.fpn.*, rpn.*, roi_heads.box_head.*,
-        roi_heads.box_predictor.*; each part is validated with check_state_dict."""
+        roi_heads.box_predictor.*; each part is validated with check_state_dict.  select: "torch" or "kernel", for the
+        RPN's filter_proposals and postprocess_detections alike (see the module docstring)."""
         from .fpn import ResNetFPN
+        _check_select(select)
         parts = {"backbone.": {}, "rpn.": {}, "roi_heads.": {}}
         for k, v in sd.items():
             for prefix, part in parts.items():
@@ -514,17 +569,20 @@ class FasterRCNN(Net):
                 raise WinoError(f"state dict: unexpected key {k!r} for Faster R-CNN")
         backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device)
         rpn = RPN.from_state_dict(parts["rpn."], out_channels, sizes, ratios, rpn_pre_nms_top_n, rpn_post_nms_top_n,
-                                  rpn_nms_thresh, rpn_score_thresh, 1e-3, backbone.device)
+                                  rpn_nms_thresh, rpn_score_thresh, 1e-3, backbone.device, select=select)
         box_head = BoxHead.from_state_dict(parts["roi_heads."], out_channels, P, backbone.device)
         if num_classes is not None and int(num_classes) != box_head.classes:
             raise WinoError(f"state dict has {box_head.classes} classes, num_classes={num_classes}")
         return cls(backbone, rpn, box_head, box_detections_per_img, box_score_thresh, box_nms_thresh, max_candidates,
-                   backbone.device)
+                   backbone.device, select=select)
 
     def prepare(self, N: int, H: int, W: int) -> None:
         """Allocate everything for [N][3][H][W] inputs and reserve every launch's stream scratch on the current stream.
         After it a forward performs no host read of device data, so it can be captured into one graph."""
         N, H, W, dev = int(N), int(H), int(W), self.device
+        if self.select == "kernel" and self.max_candidates is not None and int(self.max_candidates) > SELECT_MAX_ROWS:
+            raise WinoError(f"select=\"kernel\" keeps at most {SELECT_MAX_ROWS} candidates, "
+                            f"max_candidates={self.max_candidates}")
         with torch.cuda.device(dev):
             self.backbone.prepare(N, H, W)
             p = self.backbone._p
@@ -552,7 +610,7 @@ class FasterRCNN(Net):
             self.box_head(pooled)
             out = postprocess_detections(self.box_head._scores, rois, hw, self.box_head.classes, self.score_thresh,
                                          self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st,
-                                         rois_out=rois_out)
+                                         rois_out=rois_out, select=self.select)
         if st is not None:
             st.update(features=feats, pooled=pooled, head_out=self.box_head._scores)
         return out, feats, pooled, hw
@@ -604,6 +662,7 @@ class MaskRCNN(FasterRCNN):
         forward returns, "prob" ("masks", float32), "binary" ("masks_binary", uint8 = prob > mask_threshold) or "both".
         Every other argument is FasterRCNN.from_state_dict's."""
         mask_P, mask_threshold = int(mask_P), float(mask_threshold)
+        _check_select(faster_rcnn.get("select", "torch"))
         if masks not in MASK_OUTPUTS:
             raise WinoError(f"masks must be one of {MASK_OUTPUTS}, got {masks!r}")
         if mask_P < 2 or mask_P % 2 or 2 * mask_P > 62:

@@ -66,7 +66,8 @@ extern "C" {
  * wino_dilated_residual_block_prepare_hw, wino_dilated_proj_block_hw, wino_dilated_proj_block_prepare_hw,
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
  * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
- * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_roi_align_launches, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_select_topk_hw, wino_roi_align_launches,
+ * wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -884,6 +885,50 @@ int wino_batched_nms_hw(const float* boxes, const float* scores, const int* grou
 int wino_mask_paste_hw(const float* logits, int layout, const int* labels, const float* boxes, const float* image_hw,
                        int N, int D, int classes, int M, int ld, int H, int W, float threshold, float* out, void* binary,
                        wino_stream_t s);
+
+/* ---- segmented top-k and sort (select.hip) ---------------------------------------------------------
+ * wino_select_topk_hw: S = N * parts independent segments, entirely on the device and with fixed-size outputs, no host
+ * read.  Image i, part p reads n[p] fp32 scores at scores + i * image_stride + off[p].  Its candidates are all n[p]
+ * elements, or with use_thresh != 0 only those with score >= score_thresh (a NaN score fails the compare, as in
+ * wino_batched_nms_hw).  The segment keeps the best min(k[p], candidates) of them, best first, in this total order:
+ *   1. NaN ranks above +Inf (torch's rule for a descending sort / topk);
+ *   2. then the larger value; -0.0 and +0.0 are equal; denormals are ordered, not flushed;
+ *   3. equal scores, and all NaNs among themselves, go to the lower index.
+ * That is torch.sort(descending=True, stable=True) truncated to k[p]: the order of the 64-bit key (orderable(score) << 32)
+ * | (0xffffffff - index), orderable(x) = ~bits when the sign bit is set, else bits | 0x80000000, with -0 mapped to +0 and
+ * every NaN to 0xffffffff first.  The result is a function of the inputs alone.
+ *   off_host, n_host, k_host   HOST arrays of `parts` entries (read during the call, like wino_roi_align_hw's hw_host)
+ *   idx        DEVICE int32; image i, part p writes k[p] rows at i * out_stride + sum_{q<p} k[q] (the slots of a
+ *              concatenation of the parts): off[p] + the index within the part, i.e. the index within the image's row;
+ *              rows past the kept count hold -1
+ *   vals       NULL, or DEVICE fp32 in the same slots: the input's own bits (-0.0 and NaN payloads survive); rows past
+ *              the kept count hold 0.0
+ *   count      DEVICE [N][parts] int32: the kept count
+ *   boxes_in   NULL, or DEVICE [N][boxes_image_stride] rows of 4 floats indexed like the scores; boxes_out (same slots as
+ *              idx, 16-byte rows) then gets the kept rows, zeros past the kept count.  boxes_out is ignored without it
+ *   workspace  the bytes of the formula below (0 when every n[p] <= 8192: the workspace
+ *              may then be NULL); its contents before the call do not matter
+ * A segment of n[p] <= 8192 is one launch: one workgroup loads it into LDS, sorts the keys with a bitonic network and
+ * writes whole rows.  A longer one first runs a radix select over many workgroups (three histogram passes of 11, 11 and
+ * 10 bits, a count of the elements that tie with the k-th, an index-ordered gather of the winners into the workspace),
+ * then the same sort: seven launches, the five in the middle each reading every score once whatever the values are.
+ * A segment never reads or writes another segment's data.
+ * 1 <= parts <= 8, N >= 0, N * parts <= 65535 (the launches carry the segment in the grid's y), n[p] >= 0,
+ * 1 <= k[p] <= 8192, 0 <= off[p], off[p] + n[p] <= image_stride < 2^31 (and <= boxes_image_stride with boxes_in),
+ * sum k[p] <= out_stride (WINO_E_SHAPE otherwise).  N == 0 is WINO_OK and launches nothing; n[p] == 0 gives count 0 and
+ * idx -1.  A NULL or not 16-byte-aligned base pointer (off[p] may be any value: a segment need not start 16-byte
+ * aligned), a NULL host array, a NaN score_thresh with use_thresh, a workspace that is too small, or an output or the
+ * workspace that overlaps an input or another output is WINO_E_ARG.  Every check comes before the first launch.  No
+ * stream scratch: the call can be captured into a graph as it is.
+ * Workspace bytes, over the long parts L = {p : n[p] > 8192}, each term rounded up to a multiple of 16:
+ *   N * |L| * 6148 * 4  (three histograms of 2048 words and four words of list length per long segment)
+ *   + N * sum_L ceil(n[p] / 2048) * 4  (the ties per chunk)  + N * sum_L k[p] * 8  (the candidate keys).
+ * It grows with every n[p] and k[p]; a smaller workspace is refused.  The Python wrapper's select_workspace_bytes
+ * computes it, as nms_workspace_bytes does for wino_batched_nms_hw. */
+int wino_select_topk_hw(const float* scores, int N, long image_stride, int parts, const long* off_host,
+                        const int* n_host, const int* k_host, int use_thresh, float score_thresh, int* idx, float* vals,
+                        int* count, long out_stride, const float* boxes_in, long boxes_image_stride, float* boxes_out,
+                        void* workspace, size_t workspace_bytes, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
