@@ -24,8 +24,18 @@
 // order, whoever is last: the result is bitwise reproducible), applies BN + ReLU and stores.
 // Nobody ever waits on another workgroup, so there is no residency assumption and no deadlock; the
 // hand-off follows the write-through recipe (sc1 stores, the storing wave drains vmcnt, one relaxed
-// agent-scope ticket add, sc1 loads by the reducer).  The tail runs FIRST: its hand-offs then
-// complete in the middle of the launch and every workgroup ends with a whole item.
+// agent-scope ticket add, sc1 loads by the reducer).
+// Order of a range: a range that crosses an item boundary (a "straddler", two partial segments) runs its tail
+// FIRST: its hand-offs complete in the middle of the launch and it ends with a whole item.  A range that lies
+// inside ONE item (one partial segment) runs its whole items first and that segment LAST: by then the item's other
+// segments were published a whole item ago, so this workgroup is the item's natural last arriver.
+// The peek: a partial segment that would draw its ticket at once first LOOKS at the counter (one relaxed load per
+// wave, in flight under A^T m A).  At nseg - 1 every other segment has drained and drawn and nobody else will look
+// at the item again: the wave finishes it from its registers -- it never publishes its own part, draws no ticket
+// and reads only the OTHER segments' slabs, its own part taking its place in the segment order (same operands,
+// same order, same bits).  At anything less it takes the ticket path above, unchanged.  A shortcut, never a wait.
+// And a ticket that comes back 0 was the item's first of at least two: its drawer skips the walk over the item's
+// segments, which had nothing to tell it.
 #pragma once
 #include "wino_common.h"
 
@@ -458,6 +468,9 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   typedef std::integral_constant<int, 2> WS_D_LEFT; typedef std::integral_constant<int, 3> WS_D_TB;
   typedef std::integral_constant<int, 4> WS_D_RUN;  typedef std::integral_constant<int, 5> WS_C_RUN;
   typedef std::integral_constant<int, 6> WS_C_LEFT;
+  // a whole-first range (below): its tail segment's item, first chunk and length (WS_WF_LT = -1: not such a range)
+  typedef std::integral_constant<int, 7> WS_T_ITEM; typedef std::integral_constant<int, 8> WS_T_CHUNK;
+  typedef std::integral_constant<int, 9> WS_WF_LT;
   // (v_writelane_b32 has no builtin; volatile asm also keeps the scalars in their lanes: the compiler cannot look through it)
   auto ws_put = [&ws_vg](auto slot, int val) { asm volatile("v_writelane_b32 %0, %1, %2" : "+v"(ws_vg) : "s"(val), "n"(decltype(slot)::value)); };
   auto ws_get = [&ws_vg](auto slot) { return __builtin_amdgcn_readlane(ws_vg, decltype(slot)::value); };
@@ -524,10 +537,13 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     if (left < 0) {
       dma_stand();
     } else {
-      if (tail > 0 && --tail == 0) item = lg;            // the tail range is issued: on to the whole items
+      int chunk = 0;
+      if (TAIL && left + 1 == ws_get(WS_WF_LT{})) {      // whole-first range, rounds issued: its tail segment is what is left
+        item = ws_get(WS_T_ITEM{}), chunk = ws_get(WS_T_CHUNK{}), tail = left + 1;
+      } else if (tail > 0 && --tail == 0) item = lg;     // the tail range is issued: on to the whole items
       else item += tail > 0 ? kernarg()->kp : G;         // the next tail item of this k-group / round
-      dma_set_item(item, 0);                             // (it overwrites the two offsets the plain advance has just stepped)
-      dma_plan(item, 0, tail, left);
+      dma_set_item(item, chunk);                         // (it overwrites the two offsets the plain advance has just stepped)
+      dma_plan(item, chunk, tail, left);
     }
     pin_dma_state();
   };
@@ -559,12 +575,30 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   // ---- the compute stream's position --------------------------------------------
   // (readfirstlane: the divisions run on the vector unit; without it the walkers' scalar state --
   //  and with it the LDS-DMA scalar offsets -- would be treated as divergent)
-  int c_tail_vg = Lt;              // tail iterations still to compute
+  // Order of the range.  A tail range that lies inside ONE item (one tail segment) runs its whole-item rounds first and
+  // that segment last ("whole-first"); every other range runs its tail first.  The one-segment workgroup is then its tail
+  // item's natural last arriver -- the other segments' slabs and tickets are a whole item old when it gets there -- and
+  // finishes the item from its registers (epilogue(), "the peek").  Wave-uniform, settled here once; both walkers find
+  // the tail segment's start in three lanes of ws_vg when the rounds run out.
+  // (TAIL = false spells the start of the range as it always did: those builds keep their code byte for byte)
+  int t_item = 0, t_chunk = 0;
+  bool whole_first = false;
+  if (TAIL) {
+    t_item = __builtin_amdgcn_readfirstlane(tail_item0 + (int)(t_begin / (unsigned)nchunks) * kpg + grp);
+    t_chunk = __builtin_amdgcn_readfirstlane((int)(t_begin % (unsigned)nchunks));
+    whole_first = ndp > 0 && Lt > 0 && t_chunk + Lt <= nchunks;
+    ws_put(WS_T_ITEM{}, t_item), ws_put(WS_T_CHUNK{}, t_chunk), ws_put(WS_WF_LT{}, whole_first ? Lt : -1);
+  }
+  const bool tail_first = Lt > 0 && !whole_first;
+  const int tail0 = TAIL ? (tail_first ? Lt : 0) : Lt;
+  int c_tail_vg = tail0;           // tail iterations still to compute (whole-first: none until the rounds are done)
   // (The current item and the kind of the current segment are looked at by the epilogue and the segment switch
   //  only: they ride through the main loop in VGPRs, like pend_vg below, and are read back with readfirstlane
   //  where they are needed.  The loop has no SGPR to spare.)
-  int c_item_vg = __builtin_amdgcn_readfirstlane(Lt > 0 ? tail_item0 + (int)(t_begin / (unsigned)nchunks) * kpg + grp : lg);
-  int c_chunk = __builtin_amdgcn_readfirstlane(Lt > 0 ? (int)(t_begin % (unsigned)nchunks) : 0);
+  int c_item_vg = TAIL ? __builtin_amdgcn_readfirstlane(tail_first ? t_item : lg)
+                       : __builtin_amdgcn_readfirstlane(Lt > 0 ? tail_item0 + (int)(t_begin / (unsigned)nchunks) * kpg + grp : lg);
+  int c_chunk = TAIL ? __builtin_amdgcn_readfirstlane(tail_first ? t_chunk : 0)
+                     : __builtin_amdgcn_readfirstlane(Lt > 0 ? (int)(t_begin % (unsigned)nchunks) : 0);
   int seg_kind_vg = 0;             // bit 1: the current segment starts its item, bit 0: it is the whole item
   // a partial segment whose ticket is drawn in the next epilogue (-1: none).  Parked in a VGPR across the
   // main loop ("+v"; read back with readfirstlane in the epilogue): the loop has no SGPR to spare -- as a
@@ -583,7 +617,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
 
   // ---- prologue: iterations 0 and 1 in flight; V_0 and the first fragments un-pipelined -----
   dma_set_item(c_item_vg, c_chunk);
-  dma_plan(c_item_vg, c_chunk, Lt, L - 1);   // L - 1 advances take the stream to the range's last chunk
+  dma_plan(c_item_vg, c_chunk, tail0, L - 1);   // L - 1 advances take the stream to the range's last chunk
   pin_dma_state();
   asm volatile("" : "+v"(c_item_vg));
 #pragma unroll
@@ -857,6 +891,18 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     int pend_item = __builtin_amdgcn_readfirstlane(pend_vg);
     unsigned pend_old = 0;
     if (TAIL && pend_item >= 0) pend_old = draw_ticket(pend_item);   // in flight while A^T m A runs
+    // The peek.  A partial segment that ends its range looks at its item's counter before it publishes anything: one
+    // relaxed agent-scope load per wave, in flight while A^T m A runs.  If every other segment has already drawn, this
+    // wave finishes the item from its registers (below); if not, nothing is lost -- it takes the ticket path.
+    // (sk_q = 0, ranges of at most one iteration on a grid beyond the tail's iterations, keeps the ticket path: some
+    //  ranges own nothing there, and the gather from registers does not look for them.)
+    // Every partial segment that would draw at once peeks (`now`, below: the range's last segment, and a straddler's
+    // second one -- where the item lies between two straddlers, nseg = 2, the later of them finishes it this way).
+    const bool draws_now = last_of_range || ((seg_kind & 2) && pend_item >= 0);
+    const bool peeking = TAIL && draws_now && !(seg_kind & 1) && sk_q > 0 && !(ABLATE & PROBE_NO_HANDOFF);
+    unsigned peek = 0;
+    if (peeking && ln == 0)
+      peek = __hip_atomic_load(tickets + (size_t)c_item * 8 + wv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     // A^T m A (C/D layout: col = lane&15, row = 4*(lane>>4)+r).  The wave holds point rows i = 2 ph and
     // 2 ph + 1 (local rows 0, 1) for all four column blocks.  Per (tile row r, column block cb):
     //   column transform inside each point row:  c0(i) = m_i0 + m_i1 + m_i2,  c1(i) = m_i1 - m_i2 - m_i3
@@ -963,11 +1009,15 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     } else if (!(ABLATE & PROBE_NO_HANDOFF)) {
       // slab slot: 2l for the segment that continues an item (head of l's range), 2l+1 for the
       // one that starts an item
-      const TailPos tp = tail_pos();
-      const unsigned my_slot = 2u * (unsigned)(tp.lp * tp.kpg + tp.grp) + ((seg_kind & 2) ? 1u : 0u);
+      // (a peeking segment publishes only if its peek fails: in the gather loop below, once the item's segment count
+      //  is known)
+      if (!peeking) {
+        const TailPos tp = tail_pos();
+        const unsigned my_slot = 2u * (unsigned)(tp.lp * tp.kpg + tp.grp) + ((seg_kind & 2) ? 1u : 0u);
 #pragma unroll
-      for (int q = 0; q < 8; q++)
-        slab_store16(y[q >> 2][q & 3], rsrc_slab, slab_voff + q * 1024, my_slot * SLAB_BYTES);
+        for (int q = 0; q < 8; q++)
+          slab_store16(y[q >> 2][q & 3], rsrc_slab, slab_voff + q * 1024, my_slot * SLAB_BYTES);
+      }
       // When is this segment's ticket drawn?  Whoever draws an item's last ticket gathers it, and a gather is
       // 3-5 us of work that only an epilogue can do:
       //  * the range's last segment: now (there is no later epilogue);
@@ -977,14 +1027,24 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       //    gathered at the very end of the launch (round 1: exits spread over 106 .. 117.6 us at 256 channels,
       //    N = 128; tools/ablate_fused 256 256 t).  The wait costs little: the next iteration's vmcnt(0)
       //    would have waited for the same stores;
-      //  * any other partial segment: at the next epilogue, when its stores have long drained.  The only tail
-      //    segment of a range that lies inside one item thus draws at the final epilogue: these workgroups have
-      //    the slack (no second partial epilogue), and they become the gatherers of the 3-segment items.
+      //  * any other partial segment (the head of a straddling range): at the next epilogue, when its stores have
+      //    long drained.
       // 256 channels: N = 128 118.7 -> 117.7 us, N = 96 98.5 -> 94.8; elsewhere within +-0.7 %.  (On top of this, the
       // gather's slabs requested all at once, the deferred item's before this segment's own finalize, with the
       // accumulators re-zeroed at the end of the epilogue to make room: 0.1-0.6 % slower everywhere.)
-      const bool now = last_of_range || ((seg_kind & 2) && job1 >= 0);
-      if (!now) {
+      // Both kinds of "now" peek first (above) and publish and draw, in the gather loop below, only when the peek finds
+      // a segment still out.  The only tail segment of a range that lies inside one item is such a last segment: it
+      // runs after the range's whole items, finds the others long done and finishes the (usual) 3-segment item from
+      // its registers -- these workgroups have the slack (no second partial epilogue).  The straddler's second segment
+      // must keep its "now": deferred, its ticket would be drawn in the straddler's final epilogue, AFTER the
+      // one-segment workgroup has peeked, whose peek would then always fail (measured: +3.5 us at 256 channels,
+      // N = 128).  Its peek pays where the item has no later finisher -- a 2-segment item between two straddlers, or
+      // a grid without whole-item rounds: the later of the two finishes it with one slab read instead of a round trip
+      // of its own part.
+      const bool now = draws_now;
+      if (peeking) {
+        job0 = c_item;
+      } else if (!now) {
         pend_item = c_item;        // ticket deferred to the next segment's epilogue
       } else {
         wait_vmem_all();           // this wave's write-through stores have left ...
@@ -1000,10 +1060,27 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       const int item = j == 0 ? job0 : job1;
       if (item < 0) continue;
       if (!(j == 0 && whole)) {
-        // which logical workgroups share `item`: walk outwards from lg.  With more workgroups
-        // than iterations some own nothing; they are not segments.
         const TailPos tp = tail_pos();
         const int kpg = tp.kpg, Gp = tp.Gp, grp_e = tp.grp;
+        unsigned old = __builtin_amdgcn_readfirstlane(j == 0 ? old0 : pend_old);
+        bool cand = j == 0 && peeking;   // this wave may still finish the item from its registers
+        const unsigned pk = __builtin_amdgcn_readfirstlane(peek);
+        auto publish_and_draw = [&]() {   // a peek that failed: the ticket path
+          const unsigned my_slot = 2u * (unsigned)(tp.lp * kpg + grp_e) + ((seg_kind & 2) ? 1u : 0u);
+#pragma unroll
+          for (int q = 0; q < 8; q++)
+            slab_store16(y[q >> 2][q & 3], rsrc_slab, slab_voff + q * 1024, my_slot * SLAB_BYTES);
+          wait_vmem_all();
+          old = __builtin_amdgcn_readfirstlane(draw_ticket(item));
+          cand = false;
+        };
+        // (a partial segment's item has at least two segments: a counter at 0 cannot be at nseg - 1)
+        if (cand && pk == 0u) publish_and_draw();
+        // A drawn ticket that came back 0 was the item's first: somebody else will finish the item, and the walk below
+        // (a dozen range starts per wave) has nothing to find out.
+        if (!cand && old == 0u) continue;
+        // which logical workgroups share `item`: walk outwards from lg.  With more workgroups
+        // than iterations some own nothing; they are not segments.
         const unsigned x0 = fastdiv((unsigned)(item - tail_item0), tp.d_kp) * (unsigned)nchunks, x1 = x0 + nchunks - 1;   // the group's tail space
         int gA = tp.lp, gB = tp.lp;
         while (sk_start(gA, sk_q, sk_rem, Gp) > x0) gA--;
@@ -1011,8 +1088,16 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         int nseg = 0;
         for (int g = gA; g <= gB; g++)
           nseg += sk_start(g + 1, sk_q, sk_rem, Gp) != sk_start(g, sk_q, sk_rem, Gp);
-        const unsigned old = __builtin_amdgcn_readfirstlane(j == 0 ? old0 : pend_old);
-        if (old != (unsigned)(nseg - 1)) {   // another workgroup's wave w will finish the item
+        // A peeking segment: a counter at nseg - 1 means that every other segment has drained its slab and drawn its
+        // ticket and that nobody else will look at the item again -- this wave is its last arriver without drawing, and
+        // its own part never leaves its registers.  Anything less: the ticket path -- publish, drain, draw.  Nobody waits.
+        const bool mine = cand && pk == (unsigned)(nseg - 1);
+        if (cand && !mine) {
+          if (pk >= (unsigned)nseg && ln == 0)   // (as below: the counter was not zero at launch)
+            __hip_atomic_store(kp->err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          publish_and_draw();
+        }
+        if (!mine && old != (unsigned)(nseg - 1)) {   // another workgroup's wave w will finish the item
           // ... unless the counter was not zero when the launch began (a launch that died mid-way before this
           // one): say so on the host-visible word; the library then refuses the stream until it is reset
           if (old >= (unsigned)nseg && ln == 0) __hip_atomic_store(kp->err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -1021,12 +1106,34 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         if (ln == 0)   // self-cleaning counter: the next launch finds 0 again.  (Subtracted, not stored: a counter
                        // that was NOT zero at launch then stays off by the same amount, and the item's last
                        // drawer is certain to see a value >= nseg -- the report above cannot be missed.)
-          __hip_atomic_fetch_sub(tickets + (size_t)item * 8 + wv, (unsigned)nseg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          __hip_atomic_fetch_sub(tickets + (size_t)item * 8 + wv, (unsigned)(mine ? nseg - 1 : nseg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         // gather: all segments' parts, summed in segment order
         sub(-1);
         bool first = true;
+        int g0 = gA;
+        if (mine) {
+          // This wave's own part takes its place in that order from y: the segments before it are summed in t and y
+          // joins them as t + y (the same IEEE operation as y + t); the ones behind it are added to y as ever.  Same
+          // operands, same order, same bits.  (sk_q > 0: every range in gA .. gB owns something.)
+          if (gA < tp.lp) {
+            f32x4 t[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++)
+              t[q] = slab_load16(rsrc_slab, slab_voff + q * 1024, (2u * (unsigned)(gA * kpg + grp_e) + 1u) * SLAB_BYTES);
 #pragma unroll 1
-        for (int g = gA; g <= gB; g++) {
+            for (int g = gA + 1; g < tp.lp; g++) {   // (piecewise: y and t are all the registers the gather may hold)
+#pragma unroll
+              for (int q = 0; q < 8; q++)
+                t[q] = t[q] + slab_load16(rsrc_slab, slab_voff + q * 1024, 2u * (unsigned)(g * kpg + grp_e) * SLAB_BYTES);
+            }
+#pragma unroll
+            for (int q = 0; q < 8; q++) y[q >> 2][q & 3] = t[q] + y[q >> 2][q & 3];
+          }
+          first = false;
+          g0 = tp.lp + 1;
+        }
+#pragma unroll 1
+        for (int g = g0; g <= gB; g++) {
           if (sk_start(g + 1, sk_q, sk_rem, Gp) == sk_start(g, sk_q, sk_rem, Gp)) continue;   // owns nothing
           const unsigned slot = 2u * (unsigned)(g * kpg + grp_e) + (first ? 1u : 0u);   // (tail range g, this group)
           f32x4 t[8];
@@ -1262,7 +1369,11 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_epi += t - st_prev; st_prev = t; }
       if (last_of_range) break;
       const int c_tail = __builtin_amdgcn_readfirstlane(c_tail_vg);
-      if (c_tail < 0) {   // tail done: first whole item
+      if (TAIL && ws_get(WS_C_LEFT{}) == ws_get(WS_WF_LT{})) {   // whole-first range, rounds done: its tail segment
+        c_item_vg = ws_get(WS_T_ITEM{});
+        c_chunk = ws_get(WS_T_CHUNK{});
+        c_tail_vg = ws_get(WS_WF_LT{});
+      } else if (c_tail < 0) {   // tail done: first whole item
         c_item_vg = lg;
         c_tail_vg = 0;
       } else {

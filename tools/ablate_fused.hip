@@ -115,14 +115,24 @@ int main(int argc, char** argv) {
       for (int l = 0; l < wgs; l++) { req.push_back((tl(l, TL3_STAGE_REQ) - tl(l, TL_ENTRY)) * 0.01); land.push_back((tl(l, TL3_STAGE_IN) - tl(l, TL_ENTRY)) * 0.01); }
       pr("entry -> first stage requested", req); pr("entry -> first stage landed", land);
     }
-    if (argc > 5) {   // per workgroup, with the shape of its tail range
+    if (argc > 5) {   // per workgroup, with the shape of its tail range: the launch's real cut (k-groups, phase order)
       const int nTB = (N * 49 + TB - 1) / TB, nch = C / 8;
-      const unsigned items = (unsigned)nTB * (K / KB), Tt = (items % wgs) * nch, q = Tt / wgs, rem = Tt % wgs;
-      printf("lg first_chunk len segs | first_mfma last_epi_start exit epi_len\n");
+      FusedParams lay{};
+      lay.C = C, lay.K = K;
+      fused_work_layout(lay, (long long)nTB * (K / KB), wgs);
+      std::vector<double> cls[2][3];   // [one-segment range / straddler][last epilogue start, its length, exit]
+      printf("lg range first_chunk len segs | first_mfma last_epi_start exit epi_len\n");
       for (int l = 0; l < wgs; l++) {
-        const unsigned a = sk_start(l, q, rem, wgs), b2 = sk_start(l + 1, q, rem, wgs);
+        const int lp = tail_range_of(l / lay.kp, lay.ph_P, lay.ph_inv, lay.ph_copies);
+        const unsigned a = sk_start(lp, lay.sk_q, lay.sk_rem, lay.Gp), b2 = sk_start(lp + 1, lay.sk_q, lay.sk_rem, lay.Gp);
         const int segs = b2 > a ? (int)((b2 - 1) / nch - a / nch + 1) : 0;
-        printf("%3d %2u %2u %d | %6.2f %7.2f %7.2f %5.2f\n", l, a % nch, b2 - a, segs, first[l], lastep[l], exitt[l], epi[l]);
+        printf("%3d %3d %2u %2u %d | %6.2f %7.2f %7.2f %5.2f\n", l, lp, a % nch, b2 - a, segs, first[l], lastep[l], exitt[l], epi[l]);
+        if (segs == 1 || segs == 2) { cls[segs - 1][0].push_back(lastep[l]); cls[segs - 1][1].push_back(epi[l]); cls[segs - 1][2].push_back(exitt[l]); }
+      }
+      for (int c = 0; c < 2; c++) {
+        if (cls[c][0].empty()) continue;
+        printf("%s (%zu workgroups):\n", c ? "straddlers (two tail segments)" : "one-segment ranges", cls[c][0].size());
+        pr("start of the last epilogue", cls[c][0]); pr("last epilogue -> exit", cls[c][1]); pr("exit", cls[c][2]);
       }
     }
     return 0;
