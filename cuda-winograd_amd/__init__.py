@@ -751,6 +751,63 @@ def resize_bilinear(src, Ho: int, Wo: int, C=None, in_padded: bool = False, out=
     return (out if want_out else None), (labels if want_labels else None)
 
 
+IMAGENET_MEAN, IMAGENET_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)   # torchvision's detectors' defaults
+TRANSFORM_MAX_IMAGES = 32                                                     # WINO_TRANSFORM_MAX_IMAGES
+IMAGE_DTYPES = {torch.float32: 0, torch.uint8: 1}                             # WINO_IMAGE_F32, WINO_IMAGE_U8
+
+
+def transform_size(h: int, w: int, min_size: int = 800, max_size: int = 1333):
+    """(ho, wo): the size torchvision's GeneralizedRCNNTransform resizes an h x w image to (host-side, torch's fp32
+    scale factor and floor bit for bit)."""
+    return _plan_query("wino_transform_size", 2, int(h), int(w), int(min_size), int(max_size))
+
+
+def batch_hw(sizes, size_divisible: int = 32):
+    """(Hb, Wb) of the batch that holds images of `sizes` [(h, w)]: the per-axis maximum, rounded up to a multiple of
+    size_divisible (torchvision's batch_images)."""
+    sizes, d = [(int(h), int(w)) for h, w in sizes], int(size_divisible)
+    if not sizes or d < 1:
+        raise WinoError(f"batch_hw: {len(sizes)} sizes, size_divisible={d} (need at least one size and size_divisible >= 1)")
+    return tuple((max(s[k] for s in sizes) + d - 1) // d * d for k in (0, 1))
+
+
+def image_transform(images, out_sizes, Hb: int, Wb: int, mean=IMAGENET_MEAN, std=IMAGENET_STD, out=None) -> torch.Tensor:
+    """torchvision's GeneralizedRCNNTransform at test time in one HIP launch per 32 images: every image [C][h][w] of the
+    list (all float32 in [0, 1], or all uint8, taken as byte / 255) is normalised with mean / std [C], resized to its
+    (ho, wo) of `out_sizes` (bilinear, align_corners=False, exact integer source coordinates) and written into the top-left
+    corner of its planes of out [N][C][Hb][Wb] float32; the rest of every plane is written 0.  No scratch: capturable
+    into a graph without a prepare."""
+    images = list(images)
+    if not images:
+        raise WinoError("image_transform: no images")
+    for k, t in enumerate(images):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise WinoError(f"images[{k}] must be a CUDA(HIP) tensor -- this framework has no CPU path")
+        if t.dtype not in IMAGE_DTYPES or t.dtype != images[0].dtype:
+            raise WinoError(f"images[{k}] is {t.dtype}: the images must be all float32 or all uint8")
+        if t.dim() != 3 or t.shape[0] != images[0].shape[0] or min(t.shape) < 1:
+            raise WinoError(f"images[{k}] must be [C][h][w] with the C of images[0], got {tuple(t.shape)}")
+    imgs = [t.contiguous() for t in images]
+    N, C = len(imgs), int(imgs[0].shape[0])
+    out_sizes = [(int(h), int(w)) for h, w in out_sizes]
+    mean, std = [float(v) for v in mean], [float(v) for v in std]
+    if len(out_sizes) != N or len(mean) != C or len(std) != C:
+        raise WinoError(f"image_transform: {N} images of {C} channels, {len(out_sizes)} out_sizes, {len(mean)} means, "
+                        f"{len(std)} stds")
+    Hb, Wb = int(Hb), int(Wb)
+    if Hb < 1 or Wb < 1:
+        raise WinoError(f"image_transform: bad batch Hb={Hb} Wb={Wb}")
+    out = _output(out, (N, C, Hb, Wb), imgs[0].device)
+    _on_current_device(*imgs, out)
+    ptrs = (c_void_p * N)(*[t.data_ptr() for t in imgs])
+    hw = (c_int * (2 * N))(*[int(t.shape[d]) for t in imgs for d in (1, 2)])
+    ohw = (c_int * (2 * N))(*[v for s in out_sizes for v in s])
+    _check(lib().wino_image_transform_hw(ptrs, hw, ohw, N, C, IMAGE_DTYPES[imgs[0].dtype], (ctypes.c_float * C)(*mean),
+                                         (ctypes.c_float * C)(*std), out.data_ptr(), Hb, Wb, _stream()),
+           "wino_image_transform_hw")
+    return out
+
+
 def roi_align(levels, rois, P: int, scales, sampling: int = 2, in_padded: bool = False, out_padded: bool = False,
               canonical_scale: float = 224.0, canonical_level: int = 4, out=None) -> torch.Tensor:
     """torchvision's roi_align(aligned=False) over 1 to 4 pyramid levels with MultiScaleRoIAlign's level assignment, one

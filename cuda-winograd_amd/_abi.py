@@ -179,6 +179,9 @@ SIGNATURES = {
     "wino_batched_nms_hw": (i, [vp] * 3 + [i] * 2 + [c_float] * 3 + [i] + [vp] * 4 + [sz, vp]),
     # ---- mask selection and paste
     "wino_mask_paste_hw": (i, [vp, i] + [vp] * 3 + [i] * 7 + [c_float] + [vp] * 3),
+    # ---- image transform
+    "wino_image_transform_hw": (i, [POINTER(vp), ip, ip, i, i, i, fptr, fptr, vp, i, i, vp]),
+    "wino_transform_size": (i, [i] * 4 + [ip] * 2),
     # ---- segmented top-k and sort
     "wino_select_topk_hw": (i, [vp, i, c_long, i, POINTER(c_long), ip, ip, i, c_float] + [vp] * 3 + [c_long, vp, c_long]
                             + [vp] * 2 + [sz, vp]),

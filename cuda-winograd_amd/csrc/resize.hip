@@ -25,6 +25,7 @@
 //   DIRECT  Each lane owns one output column, walks output rows and gathers its four taps from global memory per
 //           class.  Correct for every legal shape; taken when no block of one output row x 64 pixels fits in 64 KB of
 //           LDS, or when an axis shrinks by more than 4x (most of a staged span would never be read).
+#include "resize_coord.h"
 #include "wino_common.h"
 
 namespace wino {
@@ -34,28 +35,6 @@ constexpr int LDS_LIMIT = 64 << 10;   // bytes per workgroup: two workgroups per
 constexpr int STAGED_WAVES = 8;       // waves of a staged workgroup: one per output row of a full block
 constexpr int STAGED_THREADS = 64 * STAGED_WAVES;
 constexpr int MAX_DOWN = 4;           // staged up to this down-scale factor per axis
-
-struct Coord {
-  int i0, i1;
-  float lam;
-};
-// (2d+1) in < 2 out in < 2^31 (checked by the entry points)
-__host__ __device__ __forceinline__ Coord coord(int d, int in, int out) {
-  int num = (2 * d + 1) * in - out;
-  if (num < 0) num = 0;
-  const int two = 2 * out;
-  Coord c;
-  c.i0 = num / two;
-  c.i1 = c.i0 + 1 < in ? c.i0 + 1 : in - 1;
-  c.lam = (float)(num - c.i0 * two) / (float)two;
-  return c;
-}
-
-__device__ __forceinline__ float lerp2(float a, float b, float c, float d, float lx, float ly) {
-  const float top = (1.f - lx) * a + lx * b;
-  const float bot = (1.f - lx) * c + lx * d;
-  return (1.f - ly) * top + ly * bot;
-}
 
 // torch.argmax's order: larger wins, a tie keeps the lower index, a NaN beats every number and the first NaN stays.
 // Branch-free (selects); the running maximum starts at -Inf with index 0, so class 0 needs no case of its own: a

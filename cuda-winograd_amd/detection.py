@@ -52,8 +52,18 @@ permute copy) -> ``paste_masks(layout="gemm_rows")``: torchvision's ``maskrcnn_i
 one launch, ``"masks"`` [N][D][H][W] float32 and / or ``"masks_binary"`` uint8, planes past ``count`` zero (label -1).
 Like the rest, a forward after ``prepare`` reads no device data on the host and is captured into one graph.
 
-Not built: ``GeneralizedRCNNTransform`` (resize / normalise / batching) and the mapping of boxes and masks back to
-original image sizes, Keypoint R-CNN, RetinaNet and the BN variants of the v2 heads.
+``predict(images)`` is torchvision's whole call: a list of ``[3][h][w]`` images of different sizes (all float32 in
+[0, 1] or all uint8) in, detections in each image's own pixels out.  ``prepare_images(shapes, ...)`` computes the resized
+sizes (``transform_size``: torchvision's rule bit for bit) and the batch size, runs ``prepare`` and allocates the batch,
+the resized sizes and the box ratios; ``predict`` then runs ``image_transform`` (one launch: normalise, resize, batch) ->
+the detector -> ``torch.mul(boxes, ratio)`` (torchvision's ``resize_boxes``, ratio = fp32(original) / fp32(resized)), and
+Mask R-CNN pastes its masks once, at original size: ``paste_masks`` with the rescaled boxes and ``image_hw`` = the original
+sizes into ``[N][D][Hmax][Wmax]`` planes, zero beyond each image's own size (``to_image_lists`` crops them).  The mask
+RoIAlign reads the un-rescaled detections, as in torchvision.  After ``prepare_images`` a ``predict`` reads no device data
+on the host and is captured into one graph.  ``forward`` on a ready batch is unchanged.
+
+Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets, Keypoint R-CNN, RetinaNet and the
+BN variants of the v2 heads.
 
 The key names above are written from memory of torchvision's source and have not been checked against an installed
 torchvision; the tests build their own state dicts under these names.
@@ -62,7 +72,8 @@ from __future__ import annotations
 
 import torch
 
-from . import A_PADDED, RELU, WinoError, conv1x1_bn, conv1x1_bn_ex, conv1x1_prepare, conv3x3_bn_relu, conv3x3_prepare
+from . import A_PADDED, IMAGENET_MEAN, IMAGENET_STD, IMAGE_DTYPES, RELU, WinoError, conv1x1_bn, conv1x1_bn_ex
+from . import conv1x1_prepare, conv3x3_bn_relu, conv3x3_prepare
 from . import filter_transform_f2
 from ._net import Net, check_state_dict
 
@@ -537,8 +548,9 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
 
 class FasterRCNN(Net):
     """torchvision's fasterrcnn_*_fpn at test time on the library's kernels: ResNetFPN(padded) -> RPN ->
-    multiscale_roi_align -> BoxHead -> postprocess_detections, on the already normalised batch.  Out of scope:
-    GeneralizedRCNNTransform (resize / normalise / batching) and the mapping of boxes back to original image sizes."""
+    multiscale_roi_align -> BoxHead -> postprocess_detections.  forward takes the already normalised batch; predict
+    takes a list of images of different sizes (GeneralizedRCNNTransform in one launch) and returns boxes in each image's
+    own pixels."""
 
     def __init__(self, backbone, rpn, box_head, detections, score_thresh, nms_thresh, max_candidates, device,
                  select="torch"):
@@ -547,6 +559,7 @@ class FasterRCNN(Net):
         self.backbone, self.rpn, self.box_head = backbone, rpn, box_head
         self.detections, self.score_thresh, self.nms_thresh = int(detections), float(score_thresh), float(nms_thresh)
         self.max_candidates = max_candidates
+        self._tf, self._tf_params = None, None   # prepare_images' state, and the parameters of its last call
 
     @classmethod
     def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, P: int = 7, eps: float = 1e-5,
@@ -625,12 +638,87 @@ class FasterRCNN(Net):
             out.update(st)
         return out
 
+    def prepare_images(self, shapes, dtype=torch.float32, min_size: int = 800, max_size: int = 1333, mean=IMAGENET_MEAN,
+                       std=IMAGENET_STD, size_divisible: int = 32) -> None:
+        """Everything predict needs for a list of images of `shapes` [(h, w)] (or (3, h, w)) and `dtype` (float32 or
+        uint8): the resized sizes (transform_size) and the batch size (batch_hw), prepare(N, Hb, Wb), the batch
+        [N][3][Hb][Wb], the device image_hw [N][2] (the resized sizes: forward's image_sizes), the ratio tensor [N][1][4] =
+        fp32(original) / fp32(resized) as (rw, rh, rw, rh) (torchvision's resize_boxes) and the rescaled boxes.  After it
+        a predict on such a list performs no host read of device data, so it can be captured into one graph."""
+        from . import batch_hw, transform_size
+        if dtype not in IMAGE_DTYPES:
+            raise WinoError(f"prepare_images: dtype must be torch.float32 or torch.uint8, got {dtype}")
+        shapes = [tuple(s) for s in shapes]
+        if not shapes or any(len(s) not in (2, 3) or (len(s) == 3 and int(s[0]) != 3) for s in shapes):
+            raise WinoError("prepare_images: shapes must be a non-empty list of (h, w) or (3, h, w)")
+        orig = [(int(s[-2]), int(s[-1])) for s in shapes]
+        params = dict(min_size=int(min_size), max_size=int(max_size), mean=tuple(float(v) for v in mean),
+                      std=tuple(float(v) for v in std), size_divisible=int(size_divisible))
+        self._tf, self._tf_params = None, params   # (remembered for predict even if what follows raises)
+        sizes = [transform_size(h, w, params["min_size"], params["max_size"]) for h, w in orig]
+        Hb, Wb = batch_hw(sizes, params["size_divisible"])
+        N, dev, f32 = len(orig), self.device, torch.float32
+        self._prepare_for_predict(N, Hb, Wb)
+        new, old = torch.tensor(orig, dtype=f32), torch.tensor(sizes, dtype=f32)
+        ratio = (new / old)[:, [1, 0, 1, 0]].reshape(N, 1, 4)   # (a torch fp32 division of the two size tensors)
+        with torch.cuda.device(dev):
+            tf = dict(key=(tuple(orig), dtype), params=params, orig=orig, sizes=sizes, shape=(N, Hb, Wb),
+                      batch=torch.empty((N, 3, Hb, Wb), dtype=f32, device=dev), image_hw=old.to(dev),
+                      orig_hw=new.to(dev), ratio=ratio.contiguous().to(dev),
+                      boxes=torch.empty((N, self.detections, 4), dtype=f32, device=dev))
+            self._prepare_outputs(tf, max(h for h, _ in orig), max(w for _, w in orig))
+        torch.cuda.current_stream().synchronize()
+        self._tf = tf
+
+    def _prepare_for_predict(self, N: int, Hb: int, Wb: int) -> None:
+        """prepare(), as predict needs it."""
+        self.prepare(N, Hb, Wb)
+
+    def _prepare_outputs(self, tf, Hmax: int, Wmax: int) -> None:
+        """What a subclass's predict writes besides the boxes."""
+
+    def _ready(self, images):
+        """predict's opening: the list checked, prepare_images re-run when its shapes or dtype are new (with the
+        parameters of the last prepare_images, or the defaults)."""
+        images = list(images)
+        if not images or any(not isinstance(t, torch.Tensor) or t.dim() != 3 or int(t.shape[0]) != 3 for t in images):
+            raise WinoError("images must be a non-empty list of [3][h][w] tensors")
+        if any(t.device != self.device or t.dtype != images[0].dtype for t in images):
+            raise WinoError(f"the images must be on {self.device} and of one dtype")
+        key = (tuple((int(t.shape[1]), int(t.shape[2])) for t in images), images[0].dtype)
+        if self._tf is None or self._tf["key"] != key or self._tf["shape"] != self._shape:
+            self.prepare_images(key[0], key[1], **(self._tf_params or {}))
+        return images, self._tf
+
+    def _transform(self, images, tf):
+        from . import image_transform
+        p = tf["params"]
+        with torch.cuda.device(self.device):
+            return image_transform(images, tf["sizes"], tf["shape"][1], tf["shape"][2], p["mean"], p["std"], out=tf["batch"])
+
+    def predict(self, images):
+        """torchvision's detector call: images, a list of [3][h][w] tensors of different sizes (all float32 in [0, 1] or
+        all uint8), through image_transform -> the detector -> the mapping back.  Returns forward's dict with "boxes"
+        [N][D][4] in each image's own pixels (a tensor of the model's, valid until the next predict) plus
+        "original_sizes", the host list of (h, w).  A list of new shapes or dtype re-runs prepare_images."""
+        images, tf = self._ready(images)
+        out = self._detect(self._transform(images, tf), tf["image_hw"], None)[0]
+        with torch.cuda.device(self.device):
+            out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
+        out["original_sizes"] = list(tf["orig"])
+        return out
+
     @staticmethod
     def to_lists(out):
         """torchvision's list of {"boxes", "scores", "labels"} per image.  Synchronises (it reads count)."""
         counts = out["count"].tolist()
         return [{"boxes": out["boxes"][n, :c].clone(), "scores": out["scores"][n, :c].clone(),
                  "labels": out["labels"][n, :c].clone()} for n, c in enumerate(counts)]
+
+    @staticmethod
+    def to_image_lists(out):
+        """to_lists of a predict's result: the boxes are already in each image's own pixels."""
+        return FasterRCNN.to_lists(out)
 
 
 MASK_PREFIXES = ("roi_heads.mask_head.", "roi_heads.mask_predictor.")
@@ -651,9 +739,8 @@ def split_mask_state_dict(sd):
 
 class MaskRCNN(FasterRCNN):
     """torchvision's maskrcnn_resnet50_fpn at test time: FasterRCNN, then on its detections multiscale_roi_align
-    (padded, P = mask_P) -> MaskHead (raw logits) -> paste_masks in the gemm_rows layout.  The masks are image-size planes
-    [N][D][H][W] of the normalised batch.  Out of scope, as for FasterRCNN: GeneralizedRCNNTransform and the mapping back
-    to original image sizes."""
+    (padded, P = mask_P) -> MaskHead (raw logits) -> paste_masks in the gemm_rows layout.  forward's masks are image-size
+    planes [N][D][H][W] of the normalised batch; predict's are pasted once, at original size, into [N][D][Hmax][Wmax]."""
 
     @classmethod
     def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, mask_P: int = 14,
@@ -679,9 +766,10 @@ class MaskRCNN(FasterRCNN):
         m.mask_P, m.masks, m.mask_threshold = mask_P, masks, mask_threshold
         return m
 
-    def prepare(self, N: int, H: int, W: int) -> None:
+    def prepare(self, N: int, H: int, W: int, planes: bool = True) -> None:
         """FasterRCNN.prepare, then the mask branch's tensors: the mask RoIAlign output [N*D][P+2][P+2][C], the detection
-        rois [N][D][5], int32 labels [N][D] and the masks [N][D][H][W]."""
+        rois [N][D][5], int32 labels [N][D] and the masks [N][D][H][W] (planes=False leaves the masks to the first
+        forward)."""
         super().prepare(N, H, W)
         self._shape = None   # (until the rest is in place)
         N, H, W, D, P, dev = int(N), int(H), int(W), self.detections, self.mask_P, self.device
@@ -690,35 +778,84 @@ class MaskRCNN(FasterRCNN):
             self._mask_pooled = torch.empty((N * D, P + 2, P + 2, self.mask_head.in_channels), dtype=torch.float32, device=dev)
             self._det_rois = torch.empty((N, D, 5), dtype=torch.float32, device=dev)
             self._labels32 = torch.empty((N, D), dtype=torch.int32, device=dev)
-            self._masks = torch.empty((N, D, H, W), dtype=torch.float32, device=dev) if self.masks != "binary" else None
-            self._masks_bin = torch.empty((N, D, H, W), dtype=torch.uint8, device=dev) if self.masks != "prob" else None
+            self._masks = self._masks_bin = None
+            if planes:
+                self._forward_planes(N, H, W)
         self._shape = (N, H, W)
+
+    def _forward_planes(self, N: int, H: int, W: int) -> None:
+        """forward's mask planes [N][D][H][W], unless they are there."""
+        D, dev = self.detections, self.device
+        with torch.cuda.device(dev):
+            if self.masks != "binary" and self._masks is None:
+                self._masks = torch.empty((N, D, H, W), dtype=torch.float32, device=dev)
+            if self.masks != "prob" and self._masks_bin is None:
+                self._masks_bin = torch.empty((N, D, H, W), dtype=torch.uint8, device=dev)
+
+    def _prepare_for_predict(self, N: int, Hb: int, Wb: int) -> None:
+        """prepare() without forward's batch-size mask planes (0.8 GB of fp32 at N = 2, D = 100, 800 x 1216): predict
+        pastes into planes of its own, at original size.  A forward on the prepared batch allocates them when it runs."""
+        self.prepare(N, Hb, Wb, planes=False)
 
     def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
         """FasterRCNN.forward's dict plus "masks" [N][D][H][W] float32 and / or "masks_binary" [N][D][H][W] uint8 (planes
         past count are zero): tensors of the model's, valid until the next forward.  stages=True adds mask_rois,
         mask_pooled and mask_logits (the raw [N*D*P*P*4][ld] GEMM output)."""
-        from . import multiscale_roi_align, paste_masks
         st = {} if stages else None
         self._begin(x)   # (prepare before _det_rois is named)
         out, feats, _, hw = self._detect(x, image_sizes, st, rois_out=self._det_rois)
+        N, H, W = self._shape
+        logits, pooled = self._mask_logits(feats)
+        self._forward_planes(N, H, W)
+        self._paste(out, logits, out["boxes"], hw, H, W, self._masks, self._masks_bin)
+        if stages:
+            st.update(mask_rois=self._det_rois, mask_pooled=pooled, mask_logits=logits)
+            out.update(st)
+        return out
+
+    def _mask_logits(self, feats):
+        """The mask branch up to the logits, on the detections _detect left in _det_rois: (the raw logits GEMM output, the
+        mask RoIAlign's output)."""
+        from . import multiscale_roi_align
         N, H, W = self._shape
         D, P = self.detections, self.mask_P
         with torch.cuda.device(self.device):
             pooled = multiscale_roi_align(feats, self._det_rois.view(N * D, 5), (H, W), P, 2, in_padded=True,
                                           out_padded=True, out=self._mask_pooled)
             logits, _ = self.mask_head(pooled, raw=True)
+        return logits, pooled
+
+    def _paste(self, out, logits, boxes, hw, H, W, masks, masks_bin) -> None:
+        """The paste: the detections' masks into `masks` / `masks_bin` [N][D][H][W] at `boxes`, zero beyond `hw`; adds
+        "masks" / "masks_binary" to out."""
+        from . import paste_masks
+        with torch.cuda.device(self.device):
             self._labels32.copy_(out["labels"])
-            prob, binary = paste_masks(logits, self._labels32, out["boxes"], hw, H, W, M=2 * P,
-                                       classes=self.mask_head.classes, layout="gemm_rows", out=self._masks,
-                                       binary=self._masks_bin, want_out=False, threshold=self.mask_threshold)
+            prob, binary = paste_masks(logits, self._labels32, boxes, hw, H, W, M=2 * self.mask_P,
+                                       classes=self.mask_head.classes, layout="gemm_rows", out=masks,
+                                       binary=masks_bin, want_out=False, threshold=self.mask_threshold)
         if prob is not None:
             out["masks"] = prob
         if binary is not None:
             out["masks_binary"] = binary
-        if stages:
-            st.update(mask_rois=self._det_rois, mask_pooled=pooled, mask_logits=logits)
-            out.update(st)
+
+    def _prepare_outputs(self, tf, Hmax: int, Wmax: int) -> None:
+        N, D, dev = tf["shape"][0], self.detections, self.device
+        tf["mask_hw"] = (Hmax, Wmax)
+        tf["masks"] = torch.empty((N, D, Hmax, Wmax), dtype=torch.float32, device=dev) if self.masks != "binary" else None
+        tf["masks_bin"] = torch.empty((N, D, Hmax, Wmax), dtype=torch.uint8, device=dev) if self.masks != "prob" else None
+
+    def predict(self, images):
+        """FasterRCNN.predict's dict plus "masks" [N][D][Hmax][Wmax] float32 and / or "masks_binary" uint8, Hmax x Wmax the
+        largest original height and width: pasted once, at original size, with the rescaled boxes, zero beyond each
+        image's own size and in the planes past count.  The mask RoIAlign reads the un-rescaled detections."""
+        images, tf = self._ready(images)
+        out, feats, _, _ = self._detect(self._transform(images, tf), tf["image_hw"], None, rois_out=self._det_rois)
+        logits, _ = self._mask_logits(feats)
+        with torch.cuda.device(self.device):
+            out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
+        self._paste(out, logits, out["boxes"], tf["orig_hw"], *tf["mask_hw"], tf["masks"], tf["masks_bin"])
+        out["original_sizes"] = list(tf["orig"])
         return out
 
     @staticmethod
@@ -731,6 +868,16 @@ class MaskRCNN(FasterRCNN):
             for key in ("masks", "masks_binary"):
                 if key in out:
                     res[n][key] = out[key][n, :c].unsqueeze(1).clone()
+        return res
+
+    @staticmethod
+    def to_image_lists(out):
+        """to_lists of a predict's result, each image's masks cropped to its own [h][w]: torchvision's list of dicts."""
+        res = MaskRCNN.to_lists(out)
+        for d, (h, w) in zip(res, out["original_sizes"]):
+            for key in ("masks", "masks_binary"):
+                if key in d:
+                    d[key] = d[key][:, :, :h, :w].contiguous()
         return res
 
 

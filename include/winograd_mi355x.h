@@ -67,6 +67,7 @@ extern "C" {
  * wino_conv1x1_cat_bn_hw, wino_conv1x1_cat_prepare_hw, wino_conv1x1_cat_plan, wino_aspp_hw,
  * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
  * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_select_topk_hw, wino_roi_align_launches,
+ * wino_image_transform_hw, WINO_IMAGE_*, WINO_TRANSFORM_MAX_IMAGES, wino_transform_size,
  * wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
@@ -885,6 +886,53 @@ int wino_batched_nms_hw(const float* boxes, const float* scores, const int* grou
 int wino_mask_paste_hw(const float* logits, int layout, const int* labels, const float* boxes, const float* image_hw,
                        int N, int D, int classes, int M, int ld, int H, int W, float threshold, float* out, void* binary,
                        wino_stream_t s);
+
+/* ---- image transform: the input stage of an R-CNN (image_transform.hip) ---------------------------
+ * torchvision's GeneralizedRCNNTransform at test time -- normalise, resize, batch -- for N images of different sizes, in
+ * one launch per WINO_TRANSFORM_MAX_IMAGES images (a larger N goes out as several launches of whole images):
+ *   images_host  HOST array of N DEVICE pointers (read during the call, like wino_roi_align_hw's hw_host); image i is
+ *                [C][h_i][w_i] contiguous, fp32 (dtype WINO_IMAGE_F32) or uint8 (WINO_IMAGE_U8), one dtype per call
+ *   hw_host      HOST [N][2] ints (h_i, w_i)
+ *   out_hw_host  HOST [N][2] ints (ho_i, wo_i): the size image i is resized to (wino_transform_size gives torchvision's)
+ *   mean_host, std_host  HOST [C] floats
+ *   out          DEVICE [N][C][Hb][Wb] fp32, NCHW (wino_stem_hw's input).  Plane (i, c) holds the resized image in its
+ *                top-left ho_i x wo_i corner and 0 in the rest.  Every element of out is written: no memset is needed
+ * Arithmetic, the contract.  A pixel is v = the float (fp32) or float(byte) / 255.0f (uint8).  The normalised tap is
+ * t = (v - mean_c) * inv_c in fp32, inv_c = 1.0f / std_c computed once on the host in fp32 (the reciprocal form, not a
+ * division per pixel: within 1.5 ulp of torchvision's (v - mean) / std).  The output is the bilinear
+ * align_corners=False, no-antialias resize of the taps with wino_resize_bilinear_hw's coordinates and value formula:
+ * per axis num = max((2 d + 1) in - out, 0), i0 = num / (2 out), i1 = min(i0 + 1, in - 1), lambda = float(num - i0 * 2
+ * out) / float(2 out); value = (1-ly)((1-lx) a + lx b) + ly((1-lx) c + lx d) in fp32, all four taps always multiplied.
+ * A NaN pixel therefore reaches exactly the outputs whose taps include it, also when ho == h and wo == w; the 0 of the
+ * pad region is stored, never computed from a tap.  Normalising the taps and then interpolating is torchvision's order.
+ * Named deviation from torchvision: the source coordinates are exact integers where torch computes an fp32 source
+ * coordinate (scale * (d + 0.5) - 0.5, off by 1e-4 relative beyond a few thousand pixels, 7.6e-5 of the value range at
+ * 480x640 -> 800x1066) -- the same deviation as wino_resize_bilinear_hw.  None other: the size rule below is torch's
+ * bit for bit.
+ * One form: a direct gather (a lane owns four consecutive output x of a row, 16-byte stores where the address allows,
+ * 4-byte stores on the tails of an odd Wb; tiles wholly in the pad region only store zeros; uint8 taps go through a
+ * per-workgroup table of the 256 normalised values per channel).  No workspace and no stream scratch: the descriptors
+ * travel in the kernel's arguments and the call can be captured into a graph as it is.
+ * N >= 0 (0: WINO_OK, nothing launched), 1 <= C <= 4, Hb, Wb >= 1, h, w, ho, wo >= 1, ho <= Hb, wo <= Wb, 2 ho h and 2 wo w
+ * below 2^31, one image of out (C Hb Wb) and each source image (C h w) below 2^31 elements, ceil(Hb / 8) ceil(Wb / 256)
+ * below 2^24 (the tiles of a plane are one launch's grid; WINO_E_SHAPE otherwise).  A
+ * NULL pointer (a host array, out, or an image), a dtype that is neither of the two, out not 16-byte aligned, an fp32
+ * image not 4-byte aligned (uint8 images need no alignment), a mean that is not finite, a std that is zero or not
+ * finite or whose fp32 reciprocal is not finite (a denormal), or out overlapping any image is WINO_E_ARG.  Every check comes before the first launch.  Any N.
+ *
+ * wino_transform_size (host only): torchvision's _resize_image_and_masks followed by F.interpolate(scale_factor = s,
+ * recompute_scale_factor = True), bit for bit.  `self_min_size / min_size` there is a Python float over an fp32 tensor,
+ * which torch evaluates as reciprocal(tensor) * float, so s_min = fp32(fp32(1 / fp32(min(h, w))) * fp32(min_size)), s_max
+ * the same over max(h, w) and max_size, s = min(s_min, s_max), ho = floor(double(h) * double(s)), wo likewise (a true
+ * fp32 division gives 799 x 1066 for 480 x 640 at 800 / 1333 where torch gives 800 x 1066).  h, w, min_size, max_size
+ * >= 1 and 1 <= ho, wo < 2^31 (WINO_E_SHAPE otherwise); a NULL out-parameter is WINO_E_ARG. */
+#define WINO_TRANSFORM_MAX_IMAGES 32
+#define WINO_IMAGE_F32 0
+#define WINO_IMAGE_U8 1
+int wino_image_transform_hw(const void* const* images_host, const int* hw_host, const int* out_hw_host, int N, int C,
+                            int dtype, const float* mean_host, const float* std_host, float* out, int Hb, int Wb,
+                            wino_stream_t s);
+int wino_transform_size(int h, int w, int min_size, int max_size, int* ho, int* wo);
 
 /* ---- segmented top-k and sort (select.hip) ---------------------------------------------------------
  * wino_select_topk_hw: S = N * parts independent segments, entirely on the device and with fixed-size outputs, no host
