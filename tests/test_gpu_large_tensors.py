@@ -11,11 +11,14 @@ batch whose tensors cross 2^31 and 2^32 bytes, into NaN-filled outputs and works
   CPU (the suite's own: the oracle module and the reference methods of the other GPU test files) at TIGHT;
 * a second launch gives the same bits on those images, and no stream-K ticket is left held.
 
-The box kernels (at the end) are plain HIP with 64-bit addresses: batched NMS runs at its widest segments, with a
-workspace past 4 GiB and at its largest segment counts, box decode with a head and with an output past 4 GiB.
+The box kernels are plain HIP with 64-bit addresses: batched NMS runs at its widest segments, with a
+workspace past 4 GiB and at its largest segment counts, box decode with a head and with an output past 4 GiB.  The image
+transform and the segmented select (at the end) run at the limits their entry points accept: coord()'s 2 out in < 2^31, an
+out past 4 GiB, the largest source image, scores addressed past 2^31 elements, the longest segment and the most segments.
 
 Inputs are built on the device from a seeded generator; a case skips when the card has less free memory than it needs
-(at most about 20 GiB)."""
+(at most about 20 GiB for the layers; about 60 GiB for the select past 2^31 elements, whose boxes have a stride of 2^30
+rows of 16 bytes)."""
 import ctypes
 import types
 
@@ -24,6 +27,8 @@ import pytest
 
 import box_cases as bc
 import layer_refs as LR
+import select_cases as sc
+import transform_cases as tc
 from aspp_cases import cat_reference
 from cases import TIGHT, S2Block, V15Block, proj_weights, ring_zero
 from dilated_cases import dilated_reference
@@ -994,3 +999,195 @@ def test_box_decode_output_beyond_4gib(pkg, torch_dev, free_after):
         assert _count_not_nan(torch, out_b) == N * per * 4 and _count_not_nan(torch, out_s) == N * per
     print(f"box_decode, output past 4 GiB: {err:.2e}")
     del out_b, out_s
+
+
+# ------------------------------------------------------------------ the image transform at its accepted limits
+@pytest.mark.parametrize("axis", ["rows", "columns"])
+def test_transform_at_the_coordinate_bound(axis, pkg, torch_dev, free_after):
+    """C = 1, a source of 32767 x 1 resized to 32768 x 1 (and the transposed one): 2 ho h = 2^31 - 65536, the last pair the
+    entry point accepts (tests/test_transform_host.py shows 32768 refused), and coord()'s (2 d + 1) in - out reaches
+    2147352577 in int.  The whole output against the fp64 reference, whose coordinates are int64."""
+    torch, dev = torch_dev
+    h, ho = 32767, 32768
+    assert 2 * ho * h == (1 << 31) - 65536 and (2 * (ho - 1) + 1) * h - ho == 2147352577
+    shape, size = ((h, 1), (ho, 1)) if axis == "rows" else ((1, h), (1, ho))
+    imgs = tc.images([shape], 1, seed=41)
+    mean, std = tc.mean_std(1)
+    want = tc.transform_reference(imgs, [size], *size, mean, std)
+    out = torch.full((1, 1, *size), NAN, device=dev)
+    pkg.image_transform([imgs[0].to(dev)], [size], *size, mean, std, out=out)
+    torch.cuda.synchronize()
+    tc.check(out.cpu().numpy(), want, [size], f"coordinate bound, {axis}")
+
+
+def _count(torch, flat, pred):
+    return sum(int(pred(flat[i:i + (1 << 28)]).sum()) for i in range(0, flat.numel(), 1 << 28))
+
+
+def test_transform_output_beyond_4gib(pkg, torch_dev, free_after):
+    """out [5][4][8192][8192], 5.4 GB prefilled with NaN, five small sources resized to a 16 x 16 corner: counted on the
+    device no NaN is left and every element outside the corners is bitwise +0; each image's corner is bitwise what a call
+    with that image alone writes, and the fp64 reference's at the transform's own bar."""
+    torch, dev = torch_dev
+    N, C, Hb, Wb, size = 5, 4, 8192, 8192, (16, 16)
+    assert N * C * Hb * Wb * 4 == 5 << 30 and 4 * C * Hb * Wb * 4 == 1 << 32      # image 4 starts at byte 2^32
+    _need(torch, (N + 1) * C * Hb * Wb * 4)
+    shapes = [(5, 7), (9, 4), (16, 16), (3, 3), (1, 20)]
+    imgs = tc.images(shapes, C, seed=42)
+    mean, std = tc.mean_std(C)
+    d = [t.to(dev) for t in imgs]
+    out = torch.full((N, C, Hb, Wb), NAN, device=dev)
+    pkg.image_transform(d, [size] * N, Hb, Wb, mean, std, out=out)
+    torch.cuda.synchronize()
+    flat = out.view(-1)
+    assert _count(torch, flat, torch.isnan) == 0
+    corners = out[:, :, :16, :16].contiguous()
+    nonzero = lambda t: t.view(torch.int32) != 0
+    assert _count(torch, flat, nonzero) == int(nonzero(corners).sum()), "an element outside the corners is not +0"
+    assert int(nonzero(corners).sum()) > N * C * 250
+    tc.check(corners.cpu().numpy(), tc.transform_reference(imgs, [size] * N, *size, mean, std), [size] * N, "corners")
+    one = torch.empty((1, C, Hb, Wb), device=dev)
+    for i in range(N):
+        one.fill_(NAN)
+        pkg.image_transform(d[i:i + 1], [size], Hb, Wb, mean, std, out=one)
+        assert torch.equal(one[0, :, :16, :16].contiguous().view(torch.int32), corners[i].view(torch.int32)), i
+    del out, one, flat
+
+
+def test_transform_largest_source_image(pkg, torch_dev, free_after):
+    """One float32 source of 4 x 32768 x 16383, 8 GiB and the largest the entry point accepts (one column more is refused,
+    tests/test_transform_host.py), resized to 8 x 8: the taps lie up to 2^31 - 2^15 elements into the image.  The
+    reference gathers the 4 * 64 * 4 taps with torch indexing on the device and interpolates them in fp64."""
+    torch, dev = torch_dev
+    C, h, w, size = 4, 32768, 16383, (8, 8)
+    assert C * h * w < 1 << 31 <= C * h * (w + 1)
+    _need(torch, C * h * w * 4 + GIB)
+    src = _rand(torch, dev, (C, h, w), 43).add_(0.5)
+    mean, std = tc.mean_std(C)
+    out = torch.full((1, C, *size), NAN, device=dev)
+    pkg.image_transform([src], [size], *size, mean, std, out=out)
+    torch.cuda.synchronize()
+    y0, y1, ly = tc.axis_coords(h, size[0])
+    x0, x1, lx = tc.axis_coords(w, size[1])
+    assert (C - 1) * h * w + int(y1.max()) * w + int(x1.max()) > (1 << 31) - (1 << 29)      # the farthest tap
+    t = lambda a: torch.as_tensor(a, device=dev)
+    m = torch.tensor(mean, dtype=torch.float64, device=dev)[:, None, None]
+    s = torch.tensor(std, dtype=torch.float64, device=dev)[:, None, None]
+    tap = lambda ys, xs: (src[:, t(ys)][:, :, t(xs)].double() - m) / s
+    ly_t, lx_t = t(ly)[:, None], t(lx)[None, :]
+    top = (1 - lx_t) * tap(y0, x0) + lx_t * tap(y0, x1)
+    bot = (1 - lx_t) * tap(y1, x0) + lx_t * tap(y1, x1)
+    want = ((1 - ly_t) * top + ly_t * bot).cpu().numpy()[None]
+    tc.check(out.cpu().numpy(), want, [size], "largest source")
+    del src
+
+
+# ------------------------------------------------------------------ the segmented select at its accepted limits
+def test_select_scores_beyond_2gi_elements(pkg, torch_dev, free_after):
+    """N = 3 at image_stride = 2^30: image 2 starts at element 2^31 of the scores (12 GiB, torch.empty) and byte 2^35 of
+    the boxes, which have a longer stride of their own.  A long part and a short one sit at the end of every row; only
+    those ranges are initialised.  The reference is numpy over them; the box payload names its image and its place."""
+    torch, dev = torch_dev
+    N, stride, bstride = 3, 1 << 30, (1 << 30) + 64
+    n, off, k = [19000, 500], [stride - 20000, stride - 500], [1000, 600]
+    _need(torch, N * stride * 4 + N * bstride * 16 + GIB)
+    scores = torch.empty((N, stride), device=dev)
+    boxes = torch.empty((N, bstride, 4), device=dev)
+    x = [[sc.case(name, N, n_p, seed=44 + p)[i] for p, (name, n_p) in enumerate(zip(("ties", "distinct"), n))] for i in range(N)]
+    b = [[np.stack([np.full(n_p, i), np.arange(n_p), -np.arange(n_p), np.full(n_p, 0.5 + p)], axis=1).astype(np.float32)
+          for p, n_p in enumerate(n)] for i in range(N)]
+    for i in range(N):
+        for p in range(2):
+            scores[i, off[p]:off[p] + n[p]] = torch.from_numpy(x[i][p].copy()).to(dev)
+            boxes[i, off[p]:off[p] + n[p]] = torch.from_numpy(b[i][p]).to(dev)
+    ksum = sum(k)
+    idx = torch.full((N, ksum), -7, dtype=torch.int32, device=dev)
+    vals, ob = torch.full((N, ksum), NAN, device=dev), torch.full((N, ksum, 4), NAN, device=dev)
+    count = torch.full((N, 2), -7, dtype=torch.int32, device=dev)
+    ws = torch.full((pkg.select_workspace_bytes(N, n, k) // 4,), NAN, device=dev)
+    for thresh in (None, 0.25):
+        pkg.select_topk(scores, k, n, off, thresh, boxes, idx, vals, count, ob, ws)
+        torch.cuda.synchronize()
+        got = [t.cpu().numpy() for t in (idx, vals, count, ob)]
+        for i in range(N):
+            base = 0
+            for p in range(2):
+                order = sc.topk_order(x[i][p], k[p], thresh)
+                c = len(order)
+                assert got[2][i, p] == c and (p == 0 or c < k[p])
+                assert np.array_equal(got[0][i, base:base + c], order + off[p]) and (got[0][i, base + c:base + k[p]] == -1).all()
+                assert np.array_equal(got[1][i, base:base + c].view(np.int32), x[i][p][order].view(np.int32))
+                assert np.array_equal(got[3][i, base:base + c].view(np.int32), b[i][p][order].view(np.int32)), (i, p)
+                assert not got[1][i, base + c:base + k[p]].any() and not got[3][i, base + c:base + k[p]].any()
+                base += k[p]
+    del scores, boxes
+
+
+LONGEST_SEGMENT = (1 << 31) - 1      # the longest the entry point accepts
+
+
+def longest_segment(pkg, torch, dev, n):
+    """One segment of n scores, k = 8192: zeros written on the device and 300 planted distinct positive values, among
+    them index 0, index n - 1 and both sides of several chunk boundaries.  The result is known by construction: the
+    planted ones by value, then the lowest indices that were not planted (equal scores go to the lower index).
+    Returns the seconds the call took."""
+    import time
+    k, chunk = 8192, 2048
+    rng = np.random.RandomState(45)
+    chunks = (n + chunk - 1) // chunk
+    at = {0, n - 1, n - 2}
+    for c in (1, 2, 3, 255, 256, chunks // 2, chunks - 1):
+        at |= {c * chunk - 1, c * chunk}
+    at |= {int(v) for v in rng.randint(0, 3000, 40)} | {int(v) for v in rng.randint(0, n, 250)}
+    at = np.array(sorted(at), dtype=np.int64)
+    assert 250 < len(at) < 320 and at[0] == 0 and at[-1] == n - 1
+    values = (1.0 + rng.permutation(len(at))).astype(np.float32)
+    scores = torch.zeros((1, n), device=dev)
+    scores[0, torch.from_numpy(at).to(dev)] = torch.from_numpy(values).to(dev)
+    idx = torch.full((1, k), -7, dtype=torch.int32, device=dev)
+    vals = torch.full((1, k), NAN, device=dev)
+    count = torch.full((1, 1), -7, dtype=torch.int32, device=dev)
+    ws = torch.full((pkg.select_workspace_bytes(1, n, k) // 4,), NAN, device=dev)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    pkg.select_topk(scores, k, out_idx=idx, out_vals=vals, out_count=count, workspace=ws)
+    torch.cuda.synchronize()
+    seconds = time.perf_counter() - t0
+    by_value = at[np.argsort(-values, kind="stable")]
+    rest = np.setdiff1d(np.arange(k + len(at)), at)[:k - len(at)]
+    assert count.cpu().tolist() == [[k]]
+    assert np.array_equal(idx.cpu().numpy()[0], np.concatenate([by_value, rest]))
+    want_vals = np.concatenate([np.sort(values)[::-1], np.zeros(k - len(at), np.float32)])
+    assert np.array_equal(vals.cpu().numpy()[0].view(np.int32), want_vals.view(np.int32))
+    del scores
+    return seconds
+
+
+@pytest.mark.parametrize("n", [1 << 30, LONGEST_SEGMENT], ids=["2^30", "2^31-1"])
+def test_select_longest_segment(n, pkg, torch_dev, free_after):
+    """The longest segment the entry point accepts, and half of it: the gather's scan over the earlier chunks' tie counts
+    is quadratic in the chunks, so the second run does four times the first one's scan (DESIGN.md section 3.2p has the
+    measured times)."""
+    torch, dev = torch_dev
+    _need(torch, n * 4 + GIB)
+    seconds = longest_segment(pkg, torch, dev, n)
+    print(f"select_topk, one segment of {n} scores, k = 8192: {seconds:.3f} s")
+
+
+@pytest.mark.parametrize("N,parts", [(65535, 1), (13107, 5)])
+def test_select_most_segments(N, parts, pkg, torch_dev, free_after):
+    """N parts = 65535, the most the entry point takes (the grid's y carries the segment): four distinct scores per
+    segment, k = 2.  The rows are a rotation by the segment's number, so a segment that read another's scores shows."""
+    torch, dev = torch_dev
+    S = N * parts
+    assert S == 65535
+    base = np.array([0.5, -2.0, 3.0, 1.0], dtype=np.float32)
+    x = np.stack([np.roll(base, s % 4) + np.float32(s % 7) for s in range(S)]).reshape(N, parts * 4)
+    off = [4 * p for p in range(parts)]
+    idx, vals, count = pkg.select_topk(torch.from_numpy(x).to(dev), [2] * parts, [4] * parts, off)
+    torch.cuda.synchronize()
+    seg = x.reshape(N, parts, 4)
+    order = np.argsort(-seg, axis=2, kind="stable")[:, :, :2]
+    assert (count.cpu().numpy() == 2).all()
+    assert np.array_equal(idx.cpu().numpy().reshape(N, parts, 2), order + np.array(off)[None, :, None])
+    assert np.array_equal(vals.cpu().numpy().reshape(N, parts, 2), np.take_along_axis(seg, order, axis=2))

@@ -3,7 +3,8 @@ reference of tests/transform_cases.py at 2e-5 of max |want| -- wino_resize_bilin
 -- with the pad region compared bitwise with +0.  Outputs are prefilled with NaN, so an element the launch does not write
 fails either check.  Shapes are the smallest at which the kernel can go wrong: three images of different sizes in one
 batch, an odd Wb (4-byte store tails, rows off 16 bytes), an identity size, an upscale, a down-scale beyond 4x, a batch of
-two x-chunks and three row tiles, uint8 images at odd addresses, 33 images (two launches)."""
+two x-chunks and three row tiles, pad tiles to the right of an image, sizes on and one off every tile edge, axes of length
+1, extreme ratios, C = 1 to 4, uint8 images at odd addresses, 33 images (two launches), and a seeded sweep of legal calls."""
 import functools
 
 import numpy as np
@@ -54,7 +55,7 @@ def run(pkg, dev, imgs, sizes, batch, mean, std):
     return out.cpu().numpy()
 
 
-@pytest.mark.parametrize("C", [3, 1])
+@pytest.mark.parametrize("C", [3, 1, 2, 4])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.uint8], ids=["f32", "u8"])
 @pytest.mark.parametrize("name", sorted(tc.CASES))
 def test_cases_against_fp64(pkg, torch_dev, name, dtype, C):
@@ -68,7 +69,8 @@ def test_cases_against_fp64(pkg, torch_dev, name, dtype, C):
 
 
 @pytest.mark.parametrize("name,image,at", [("rule", 1, (11, 4)), ("explicit", 0, (6, 8)), ("explicit", 2, (50, 20)),
-                                           ("odd_wb", 1, (29, 8))])
+                                           ("odd_wb", 1, (29, 8)), ("pad_right", 1, (5, 22)), ("pad_right", 0, (8, 149)),
+                                           ("tile_edges", 2, (3, 63)), ("tile_edges", 0, (0, 99))])
 def test_a_nan_pixel_reaches_exactly_its_footprint(pkg, torch_dev, name, image, at):
     """One NaN pixel in one channel of one image: NaN at exactly the outputs whose four taps include it (also under a
     zero weight, also at the identity size of "explicit" image 0), and no other bit of the batch changes."""
@@ -103,7 +105,7 @@ def test_33_images_split_into_launches_equal_single_calls(pkg, torch_dev):
 
 
 @pytest.mark.parametrize("align", guarded.ALIGNS)
-@pytest.mark.parametrize("name", ["rule", "odd_wb"])
+@pytest.mark.parametrize("name", ["rule", "odd_wb", "pad_right"] + tc.THIN)
 def test_guarded_arena(pkg, torch_dev, name, align):
     """Every image and the output between guards: no byte next to out changes, and the NaN that fills the guards behind
     and in front of every image never reaches a result."""
@@ -152,3 +154,16 @@ def test_captured_into_a_graph_replays_on_new_contents(pkg, torch_dev, dtype):
         assert torch.equal(out.view(torch.int32), eager.view(torch.int32))
     tc.check(out.cpu().numpy(), tc.transform_reference(other, c["sizes"], *c["batch"], mean, std), c["sizes"], "replay")
     del graph
+
+
+@pytest.mark.parametrize("index", range(tc.SWEEP_COUNT))
+def test_transform_sweep(index, pkg, torch_dev):
+    """Seeded legal calls: 1 to 5 images of 1 to 4 channels, either dtype (uint8 at odd addresses), sources up to 60 px,
+    outputs up to 300 px in a batch that is a multiple of nothing, into a NaN-filled out."""
+    s = tc.sweep_specs()[index]
+    dtype = torch.uint8 if s["dtype"] == "u8" else torch.float32
+    imgs = tc.images(s["shapes"], s["C"], dtype, seed=500 + index)
+    mean, std = tc.mean_std(s["C"])
+    want = tc.transform_reference(imgs, s["sizes"], *s["batch"], mean, std)
+    got = run(pkg, torch_dev[1], imgs, s["sizes"], s["batch"], mean, std)
+    tc.check(got, want, s["sizes"], f"sweep {index} {s}")

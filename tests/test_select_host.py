@@ -1,6 +1,8 @@
 """Host tests of the segmented top-k / sort (no GPU): the numpy reference of tests/select_cases.py is torch's stable
-descending sort truncated to k, for every case class; the entry point and the workspace query refuse every bad argument
-before any launch; the query is monotone and is what the entry point asks for; select= rejects an unknown value."""
+descending sort truncated to k, for every case class; the constructed radix cases reach every corner of find_digit in
+every pass and the layout sweep holds the layouts it is for (conditions on the GPU tests' inputs); the entry point and
+the workspace query refuse every bad argument before any launch; the query is monotone and is what the entry point asks
+for; select= rejects an unknown value."""
 from ctypes import c_int, c_long
 
 import numpy as np
@@ -13,7 +15,7 @@ SIZES = [1, 2, 7, 64, 65, 1000, 5000]
 KS = [1, 2, 64, 1000, 8192]
 
 
-@pytest.mark.parametrize("name", sorted(sc.CLASSES))
+@pytest.mark.parametrize("name", sorted(sc.ALL_CLASSES))
 def test_reference_is_torchs_stable_descending_sort(name):
     for n in SIZES:
         x = sc.case(name, 2, n, seed=3)
@@ -24,7 +26,7 @@ def test_reference_is_torchs_stable_descending_sort(name):
                 assert np.array_equal(got, want[:k]), (name, n, k)
 
 
-@pytest.mark.parametrize("name", sorted(sc.CLASSES))
+@pytest.mark.parametrize("name", sorted(sc.ALL_CLASSES))
 def test_reference_is_torchs_topk_set_where_the_cut_is_clean(name):
     checked = 0
     for n in SIZES:
@@ -61,6 +63,96 @@ def test_reference_layout_and_padding():
     assert (idx[:, 23:33] == -1).all() and (vals[:, 23:33] == 0).all() and (boxes[:, 23:33] == 0).all()
     assert (idx[:, 33:] == -1).all()
     assert (idx[:, 3:23] >= 13).all() and (idx[:, 3:23] < 33).all()
+
+
+# ---- the constructed radix cases and the sweep: conditions on the inputs --------------------------------------------------
+def test_from_orderable_inverts_orderable():
+    rng = np.random.RandomState(11)
+    key = rng.randint(0x00800000, 0xff800000, size=20000, dtype=np.uint64).astype(np.uint32)
+    key = key[key != np.uint32(0x7fffffff)]                       # (-0, which orderable maps to +0's key)
+    assert np.array_equal(sc.orderable(sc.from_orderable(key)), key)
+    for name, low_bits in (("narrow10", 10), ("narrow10_neg", 10), ("narrow21", 21), ("narrow21_neg", 21)):
+        key = sc.orderable(sc.case(name, 1, 5000, seed=2)[0])
+        assert len(set((key >> np.uint32(low_bits)).tolist())) == 1 and len(set(key.tolist())) > 900, name
+        assert (sc.case(name, 1, 5000, seed=2)[0] < 0).all() == name.endswith("_neg")
+    x = sc.case("bits", 1, 70001, seed=2)[0]
+    b = x.view(np.uint32)
+    assert np.isnan(x[b >> 31 == 0]).any() and np.isnan(x[b >> 31 == 1]).any()          # NaNs of both signs
+    assert ((b & 0x7f800000) == 0).any()                                                # denormals (or zeros)
+
+
+def test_radix_corner_cases_hit_every_corner_of_every_pass():
+    """Every constructed case is what it says (its own pass, place and kind occur when the k-th key is looked for), and
+    together the cases of every (n, k) the GPU test runs reach, in each of the three passes: the first and the last bin
+    of a find_digit thread, the highest occupied bin, the histogram's last bin, bin 0 in passes 1 and 2, a rank of 1 and
+    a rank equal to the bin's count."""
+    want = {(p, c) for p in range(3) for c in ("first", "last", "highest", "top", "kr1", "krfull")} | {(1, "zero"), (2, "zero")}
+    for n in (8193, 20481, 70001):
+        for k in sc.SIZES_K:
+            seen = set()
+            specs = sc.radix_corner_specs(k)
+            assert len(specs) >= 14
+            for p, place, kind in specs:
+                x = sc.radix_corner(n, k, p, place, kind, seed=1)
+                assert x.shape == (n,) and x.dtype == np.float32
+                hits = sc.radix_hits(x, k)
+                need = {(p, place), (p, "kr1" if kind == "kr1" else "krfull")}
+                if kind == "full_highest":
+                    need.add((p, "highest"))
+                assert need <= hits, (n, k, p, place, kind, sorted(hits))
+                seen |= hits
+                if n == 8193 and k in (2, 1000):                       # the reference on them is torch's sort as well
+                    order = torch.sort(torch.from_numpy(x.copy()), descending=True, stable=True).indices.numpy()
+                    assert np.array_equal(sc.topk_order(x, k), order[:k])
+            assert want <= seen, (n, k, sorted(want - seen))
+
+
+def test_sweep_specs_hold_the_layouts_they_are_for():
+    specs = sc.sweep_specs()
+    assert len(specs) == sc.SWEEP_COUNT == 40 and [s["index"] for s in specs] == list(range(40))
+    longs = lambda s: [n > 8192 for n in s["n"]]
+    assert sum(sum(longs(s)) >= 2 for s in specs) >= 5
+    assert any(a and not b for s in specs for b, a in zip(longs(s), longs(s)[1:]))        # long after short
+    assert any(b and not a for s in specs for b, a in zip(longs(s), longs(s)[1:]))        # short after long
+    assert any(0 in s["n"] for s in specs) and any(k > n for s in specs for k, n in zip(s["k"], s["n"]))
+    assert max(s["N"] * len(s["n"]) for s in specs) >= 24
+    assert {s["N"] for s in specs} == {1, 2, 3, 4} and {len(s["n"]) for s in specs} >= {1, 2, 4, 8}
+    assert {n for s in specs for n in s["n"]} >= {0, 1, 8192, 8193} and max(n for s in specs for n in s["n"]) > 20000
+    starved = overlap = 0
+    for s in specs:
+        assert 1 <= len(s["n"]) <= 8 and all(1 <= k <= 8192 for k in s["k"]) and sum(s["k"]) <= 12000
+        assert all(o >= 0 and o + n <= s["stride"] for o, n in zip(s["off"], s["n"]))
+        assert s["out_stride"] >= sum(s["k"]) and s["boxes_stride"] >= s["stride"]
+        ends = np.maximum.accumulate([o + n for o, n in zip(s["off"], s["n"])])
+        overlap += any(o < e for o, e, n in zip(s["off"][1:], ends, s["n"][1:]) if n)
+        x, t = sc.sweep_case(s["index"])
+        assert x.shape == (s["N"], s["stride"]) and (t is None) == (s["thresh"] is None)
+        if t is not None:
+            with np.errstate(invalid="ignore"):
+                starved += any(n > 8192 and ((x[:, o:o + n] >= np.float32(t)).sum(axis=1) < k).any()
+                               for n, o, k in zip(s["n"], s["off"], s["k"]))
+    assert starved >= 1 and overlap >= 2
+    for key in ("boxes", "with_vals"):
+        assert {s[key] for s in specs} == {True, False}
+    assert any(s["thresh"] is None for s in specs) and {s["thresh"][0] for s in specs if s["thresh"]} == {"point", "value"}
+    assert any(s["out_stride"] > sum(s["k"]) for s in specs) and any(s["boxes"] and s["boxes_stride"] > s["stride"] for s in specs)
+    assert {c for s in specs for c in s["classes"]} == set(sc.ALL_CLASSES)
+
+
+def test_sweep_workspaces_are_what_the_entry_point_asks_for(pkg):
+    """For every spec of the sweep: one byte less than select_workspace_bytes is refused, the figure itself gets as far
+    as the overlap check.  No launch."""
+    for s in sc.sweep_specs():
+        need = pkg.select_workspace_bytes(s["N"], s["n"], s["k"])
+        assert (need > 0) == any(n > 8192 for n in s["n"])
+        kw = dict(scores=0x40000000, N=s["N"], stride=s["stride"], off=tuple(s["off"]), n=tuple(s["n"]), k=tuple(s["k"]),
+                  out_stride=s["out_stride"], idx=0x40000000)
+        if need:
+            assert _topk(pkg, ws=0x10000000, ws_bytes=need - 1, **kw) == ARG, s
+            assert f"workspace too small: need {need} bytes" in pkg.lib().wino_last_error_string().decode()
+        if max(s["n"]):                                  # (idx lies on the scores: with no score to read nothing would clash)
+            assert _topk(pkg, ws=0x10000000 if need else None, ws_bytes=need, **kw) == ARG, s
+            assert "must not overlap" in pkg.lib().wino_last_error_string().decode()
 
 
 # ---- the C entry points' refusals ---------------------------------------------------------------------------------------
