@@ -1182,6 +1182,70 @@ def paste_masks(logits, labels, boxes, image_hw, H: int, W: int, M=None, classes
     return (out if want_out else None), (binary if want_binary else None)
 
 
+KP_LAYOUTS = {"planes": 0, "deconv_rows": 1}   # WINO_KP_LAYOUT_*
+KP_MAX_M = 64
+KP_MAX_SIDE = 16384
+
+
+def heatmaps_to_keypoints(maps, rois, K=None, M=None, layout: str = "planes", bias=None, ld=None, max_side: int = 16384,
+                          out=None, scores_out=None):
+    """torchvision's heatmaps_to_keypoints for all detections in one HIP launch: heatmap plane (r, k) is resized to the box
+    of detection r with torch's bicubic (exact integer source coordinates), and the argmax becomes keypoint k of that
+    detection.  maps, read in place: layout "planes" [R][K][M][M] (K and M from the shape), or "deconv_rows" [R (M/4)^2][ld],
+    the partial products of ConvTranspose2d(C, K, 4, 2, 1) as KeypointHead's raw form leaves them (K and M must be given,
+    ld is read off the shape, bias [K] is required; the kernel gathers them, adds the bias and upsamples x2).  rois
+    [R][5] (or [N][D][5]) float32 (n, x1, y1, x2, y2): a padding row, !(n >= 0), gives zeros; a box that is not finite or
+    larger than max_side gives NaN and reads no map.  Returns (keypoints [R][K][3] (or [N][D][K][3]) = (x, y, 1) in image
+    coordinates, scores [R][K] = the heatmap value there); `out` / `scores_out` are written when given.  No scratch:
+    capturable into a graph without a prepare."""
+    if layout not in KP_LAYOUTS:
+        raise WinoError(f"heatmaps_to_keypoints: layout must be one of {sorted(KP_LAYOUTS)}, got {layout!r}")
+    max_side = int(max_side)
+    if not 1 <= max_side <= KP_MAX_SIDE:
+        raise WinoError(f"heatmaps_to_keypoints: need 1 <= max_side <= {KP_MAX_SIDE}, got {max_side}")
+    mp = _dev(maps, "maps")
+    ro = _dev(rois, "rois")
+    if ro.dim() not in (2, 3) or int(ro.shape[-1]) != 5:
+        raise WinoError("rois must be [R][5] or [N][D][5]")
+    R = ro.numel() // 5
+    if layout == "planes":
+        if mp.dim() != 4 or int(mp.shape[0]) != R or int(mp.shape[2]) != int(mp.shape[3]):
+            raise WinoError(f"maps must be [{R}][K][M][M] in the planes layout, got {tuple(mp.shape)}")
+        k, m = int(mp.shape[1]), int(mp.shape[2])
+        if (K is not None and int(K) != k) or (M is not None and int(M) != m):
+            raise WinoError(f"heatmaps_to_keypoints: K={K} M={M} but maps is {tuple(mp.shape)}")
+        if bias is not None:
+            raise WinoError("heatmaps_to_keypoints: the planes layout takes no bias")
+        if not 1 <= m <= KP_MAX_M or k < 1:
+            raise WinoError(f"heatmaps_to_keypoints: need 1 <= M <= {KP_MAX_M} and K >= 1, got M={m} K={k}")
+        lead, b = 0, None
+    else:
+        if K is None or M is None:
+            raise WinoError("heatmaps_to_keypoints: the deconv_rows layout needs K and M")
+        k, m = int(K), int(M)
+        if k < 1 or m < 4 or m % 4 or m > KP_MAX_M:
+            raise WinoError(f"heatmaps_to_keypoints: the deconv_rows layout needs K >= 1 and M = 4 P <= {KP_MAX_M}, got "
+                            f"K={k} M={m}")
+        if mp.dim() != 2 or int(mp.shape[0]) != R * (m // 4) ** 2:
+            raise WinoError(f"maps must be [{R} * (M/4)^2][ld] in the deconv_rows layout, got {tuple(mp.shape)} for M={m}")
+        lead = int(mp.shape[1])
+        if (ld is not None and int(ld) != lead) or lead < 16 * k:
+            raise WinoError(f"heatmaps_to_keypoints: ld={ld} K={k} but maps is {tuple(mp.shape)} (need 16 K <= ld)")
+        if bias is None:
+            raise WinoError("heatmaps_to_keypoints: the deconv_rows layout needs bias")
+        b = _dev(bias, "bias")
+        if tuple(b.shape) != (k,):
+            raise WinoError(f"bias must be [{k}], got {tuple(b.shape)}")
+    front = tuple(ro.shape[:-1])
+    out = _output(out, front + (k, 3), ro.device)
+    scores_out = _output(scores_out, front + (k,), ro.device, "scores_out")
+    _on_current_device(mp, ro, b, out, scores_out)
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    _check(lib().wino_keypoints_hw(ptr(mp), KP_LAYOUTS[layout], ptr(b), ptr(ro), R, k, m, lead, max_side, ptr(out),
+                                   ptr(scores_out), _stream()), "wino_keypoints_hw")
+    return out, scores_out
+
+
 def _groups_of(packed: torch.Tensor, C: int, groups: int, name: str) -> int:
     """`groups` checked against C and against a buffer from filter_pack_grouped (a wrong-sized one would be read out of
     bounds by the kernel)."""
@@ -1612,4 +1676,4 @@ from .resnet import ResNet  # noqa: E402  (whole networks on the operators above
 from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
-from .detection import BoxHead, MaskHead, RPN, FasterRCNN, MaskRCNN  # noqa: E402
+from .detection import BoxHead, MaskHead, KeypointHead, RPN, FasterRCNN, MaskRCNN, KeypointRCNN  # noqa: E402

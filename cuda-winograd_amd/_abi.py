@@ -179,6 +179,8 @@ SIGNATURES = {
     "wino_batched_nms_hw": (i, [vp] * 3 + [i] * 2 + [c_float] * 3 + [i] + [vp] * 4 + [sz, vp]),
     # ---- mask selection and paste
     "wino_mask_paste_hw": (i, [vp, i] + [vp] * 3 + [i] * 7 + [c_float] + [vp] * 3),
+    # ---- heatmaps to keypoints
+    "wino_keypoints_hw": (i, [vp, i, vp, vp] + [i] * 5 + [vp] * 3),
     # ---- image transform
     "wino_image_transform_hw": (i, [POINTER(vp), ip, ip, i, i, i, fptr, fptr, vp, i, i, vp]),
     "wino_transform_size": (i, [i] * 4 + [ip] * 2),

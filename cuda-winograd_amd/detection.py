@@ -1,4 +1,4 @@
-"""torchvision's Faster / Mask R-CNN on the library's kernels.  The second stage: what follows ``MultiScaleRoIAlign``
+"""torchvision's Faster / Mask / Keypoint R-CNN on the library's kernels.  The second stage: what follows ``MultiScaleRoIAlign``
 (``multiscale_roi_align``, the one new kernel) runs on layers the library already has.
 
 ``BoxHead.from_state_dict(sd)`` is ``TwoMLPHead`` + ``FastRCNNPredictor`` under the key names they have below
@@ -62,8 +62,21 @@ sizes into ``[N][D][Hmax][Wmax]`` planes, zero beyond each image's own size (``t
 RoIAlign reads the un-rescaled detections, as in torchvision.  After ``prepare_images`` a ``predict`` reads no device data
 on the host and is captured into one graph.  ``forward`` on a ready batch is unchanged.
 
-Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets, Keypoint R-CNN, RetinaNet and the
-BN variants of the v2 heads.
+``KeypointRCNN.from_state_dict(sd, arch)`` adds ``roi_heads.keypoint_head.{0,2,..,14}.weight|bias`` (eight 3x3
+convolutions, the widths read off the state dict) and ``roi_heads.keypoint_predictor.kps_score_lowres.weight|bias`` (the
+``ConvTranspose2d(C, K, 4, 2, 1)``), split off like the mask branch's keys.  On the detections' RoIAlign rows run
+``multiscale_roi_align(P = keypoint_P, in_padded, out_padded)`` -> ``KeypointHead(raw=True)``: eight ``conv3x3_bn_relu``
+launches at N = R and one GEMM with ``pack_kps_deconv``'s ``B [C][16K -> 64]`` (columns ``(ky, kx, k)``), which leaves
+the transposed convolution's partial products, one row per input pixel.  With stride 2 and kernel 4 up to four of them
+meet in an output pixel, so there is no view that undoes it; ``heatmaps_to_keypoints(layout="deconv_rows")`` gathers them
+in LDS, adds the bias, upsamples x2 and then does torchvision's ``heatmaps_to_keypoints`` -- there a Python loop with a
+host read and a ``[K][h][w]`` bicubic resize per detection -- in one launch: ``"keypoints"`` [N][D][K][3] = (x, y, 1) and
+``"keypoints_scores"`` [N][D][K], rows past ``count`` zero.  ``predict`` computes them on the un-rescaled detections and
+multiplies by ``(rw, rh, 1)`` (``resize_keypoints``).  ``KeypointHead(raw=False)`` composes torchvision's logits
+[R][K][4P][4P] in torch (``fold``, bias, ``interpolate``) for callers who want them.
+
+Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets, RetinaNet and the BN variants of
+the v2 heads.
 
 The key names above are written from memory of torchvision's source and have not been checked against an installed
 torchvision; the tests build their own state dicts under these names.
@@ -881,6 +894,255 @@ class MaskRCNN(FasterRCNN):
         return res
 
 
-__all__ = ["BoxHead", "MaskHead", "RPN", "FasterRCNN", "MaskRCNN", "split_mask_state_dict", "postprocess_detections", "base_anchors", "pack_rpn_head",
-           "expected_rpn_keys", "expected_box_head_keys", "expected_mask_head_keys", "validate_box_head_state_dict",
-           "validate_mask_head_state_dict", "pack_fc6", "pack_predictor", "pack_deconv", "pack_logits"]
+# ---- Keypoint R-CNN ------------------------------------------------------------------------------------------------------
+KEYPOINT_CONVS = 8
+KEYPOINT_PREFIXES = ("roi_heads.keypoint_head.", "roi_heads.keypoint_predictor.")
+KEYPOINT_MAX_P = 16      # heatmaps_to_keypoints takes M = 4 P <= 64
+KEYPOINT_MAX_SIDE = 16384
+
+
+def pack_kps_deconv(w: torch.Tensor, b: torch.Tensor):
+    """kps_score_lowres, ConvTranspose2d(C, K, 4, stride 2, padding 1): weight [C][K][4][4] and bias [K] -> (B [C][ld] with
+    columns (ky, kx, k), ld = 16 K up to a multiple of 64 and the rest zero, the bias [K] as it is).  The GEMM of the pixels
+    [R*P*P][C] with B leaves the transposed convolution's partial products, one row per INPUT pixel; unlike MaskHead's
+    stride = kernel = 2 deconvolution up to four of them meet in an output pixel, so the bias cannot ride in the GEMM:
+    heatmaps_to_keypoints' "deconv_rows" layout gathers them and adds it."""
+    C, K = int(w.shape[0]), int(w.shape[1])
+    B = w.new_zeros((C, _pad64(16 * K)))
+    B[:, : 16 * K] = w.permute(0, 2, 3, 1).reshape(C, 16 * K)
+    return B, b.clone()
+
+
+def _keypoint_widths(sd):
+    return [_dim0(sd, f"keypoint_head.{2 * i}.weight") for i in range(KEYPOINT_CONVS)]
+
+
+def expected_keypoint_head_keys(in_channels: int, widths, K: int):
+    """{key: shape} of KeypointRCNNHeads(in_channels, widths) + KeypointRCNNPredictor(widths[-1], K): the convolutions sit
+    at the even indices of a Sequential whose odd entries are ReLUs."""
+    exp, c = {}, int(in_channels)
+    for i, wd in enumerate(widths):
+        exp[f"keypoint_head.{2 * i}.weight"] = (int(wd), c, 3, 3)
+        exp[f"keypoint_head.{2 * i}.bias"] = (int(wd),)
+        c = int(wd)
+    exp["keypoint_predictor.kps_score_lowres.weight"] = (c, int(K), 4, 4)
+    exp["keypoint_predictor.kps_score_lowres.bias"] = (int(K),)
+    return exp
+
+
+def validate_keypoint_head_state_dict(sd, in_channels: int = 256) -> int:
+    """Checks every key and shape on the host; the eight widths are read off the convolutions and K off
+    kps_score_lowres.  Returns K."""
+    in_channels = int(in_channels)
+    widths = _keypoint_widths(sd)
+    w = sd.get("keypoint_predictor.kps_score_lowres.weight")
+    if w is None:
+        raise WinoError("state dict: missing key 'keypoint_predictor.kps_score_lowres.weight'")
+    if w.dim() != 4:
+        raise WinoError(f"state dict: key 'keypoint_predictor.kps_score_lowres.weight' has shape {tuple(w.shape)}, the "
+                        "keypoint head needs [C][K][4][4]")
+    K = int(w.shape[1])
+    check_state_dict(sd, expected_keypoint_head_keys(in_channels, widths, K), "the keypoint head", "weight")
+    for c in [in_channels] + widths:
+        if c < 64 or c % 64:
+            raise WinoError(f"keypoint head: every width must be a multiple of 64, got in_channels={in_channels}, "
+                            f"widths={widths}")
+    if K < 1:
+        raise WinoError("keypoint head: K=0 keypoints")
+    return K
+
+
+class KeypointHead(Net):
+    """KeypointRCNNHeads + KeypointRCNNPredictor on the Winograd 3x3 and the 1x1 GEMM kernels, inference only: eight
+    conv3x3_bn_relu launches at N = R, then the transposed convolution's partial products as one GEMM."""
+
+    def __init__(self, in_channels: int, widths, K: int, device):
+        super().__init__(device)
+        self.in_channels, self.widths, self.K = int(in_channels), [int(w) for w in widths], int(K)
+
+    @classmethod
+    def from_state_dict(cls, sd, in_channels: int = 256, device=None) -> "KeypointHead":
+        K = validate_keypoint_head_state_dict(sd, in_channels)
+        return cls._load(sd, None, device, in_channels, _keypoint_widths(sd), K)
+
+    def _pack(self, sd, eps):
+        self.convs = [(filter_transform_f2(self._t(sd[f"keypoint_head.{2 * i}.weight"])),
+                       self._t(sd[f"keypoint_head.{2 * i}.bias"])) for i in range(KEYPOINT_CONVS)]
+        wd, bd = pack_kps_deconv(sd["keypoint_predictor.kps_score_lowres.weight"],
+                                 sd["keypoint_predictor.kps_score_lowres.bias"])
+        self.wd, self.bias = self._t(wd), self._t(bd)
+        self.ld = int(self.wd.shape[1])
+        n = max(self.widths + [self.ld])
+        self._ones = torch.ones(n, dtype=torch.float32, device=self.device)
+        self._zeros = torch.zeros(self.ld, dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+
+    def prepare(self, R: int, P: int = 14) -> None:
+        """Allocate the ping-pong tensors [R][P+2][P+2][width] (two when the widths agree, as torchvision's 512s do) and
+        the rows tensor [R*P*P][ld], and reserve the stream scratch of the nine launches on the current stream.  Call it
+        before capturing a forward into a graph."""
+        R, P, f32, dev = int(R), int(P), torch.float32, self.device
+        if R < 1 or not 1 <= P <= KEYPOINT_MAX_P:
+            raise WinoError(f"keypoint head: R={R} boxes of P={P}: need R >= 1 and 1 <= P <= {KEYPOINT_MAX_P}")
+        with torch.cuda.device(dev):
+            bufs, self._acts = {}, []
+            for i, w in enumerate(self.widths):   # layer i writes buffer (its width, i mod 2)
+                if (w, i % 2) not in bufs:
+                    bufs[(w, i % 2)] = torch.zeros((R, P + 2, P + 2, w), dtype=f32, device=dev)
+                self._acts.append(bufs[(w, i % 2)])
+            self._rows = torch.empty((R * P * P, self.ld), dtype=f32, device=dev)
+            self._maps = torch.empty((R, self.K, 4 * P, 4 * P), dtype=f32, device=dev)
+            c = self.in_channels
+            for w in self.widths:
+                conv3x3_prepare(R, c, w, P, P)
+                c = w
+            conv1x1_prepare(R * P * P, c, self.ld)
+        self._shape = (R, P)
+
+    def forward(self, pooled_padded: torch.Tensor, raw: bool = False):
+        """pooled_padded [R][P+2][P+2][in_channels] float32 with a zero ring (roi_align's out_padded output; it is not
+        written) -> torchvision's keypoint logits [R][K][4P][4P], a tensor of the head's, valid until the next forward.
+        A new (R, P) re-runs prepare().  raw=True: returns (the GEMM's output [R*P*P][ld], rows (r, iy, ix) and columns
+        (ky, kx, k), ld): heatmaps_to_keypoints' "deconv_rows" layout, to be passed with the head's `bias`.  raw=False
+        composes the logits in torch (fold, bias, x2 bilinear upsample): plumbing for callers who want them, not on
+        KeypointRCNN's path."""
+        x, C = pooled_padded, self.in_channels
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or x.shape[1] != x.shape[2]:
+            raise WinoError(f"pooled_padded must be [R][P+2][P+2][{C}]")
+        if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+            raise WinoError(f"pooled_padded must be contiguous float32 on {self.device}")
+        R, P = int(x.shape[0]), int(x.shape[1]) - 2
+        if (R, P) != self._shape:
+            self.prepare(R, P)
+        K, ld = self.K, self.ld
+        with torch.cuda.device(self.device):
+            src = x
+            for (U, bias), dst, w in zip(self.convs, self._acts, self.widths):
+                conv3x3_bn_relu(src, U, bias, self._ones[:w], relu=True, out=dst)
+                src = dst
+            conv1x1_bn_ex(src, self.wd, self._zeros, self._ones[:ld], A_PADDED, out=self._rows)
+            if raw:
+                return self._rows, ld
+            F = torch.nn.functional
+            cols = self._rows[:, : 16 * K].view(R, P, P, 4, 4, K).permute(0, 5, 3, 4, 1, 2).reshape(R, 16 * K, P * P)
+            low = F.fold(cols, (2 * P, 2 * P), kernel_size=4, stride=2, padding=1) + self.bias.view(1, K, 1, 1)
+            self._maps.copy_(F.interpolate(low, scale_factor=2, mode="bilinear", align_corners=False))
+        return self._maps
+
+
+def split_keypoint_state_dict(sd):
+    """(the Faster R-CNN keys as they are, the keypoint branch's keys below `roi_heads.`), like split_mask_state_dict."""
+    rest, kp = {}, {}
+    for k, v in sd.items():
+        if k.startswith(KEYPOINT_PREFIXES):
+            kp[k[len("roi_heads."):]] = v
+        else:
+            rest[k] = v
+    return rest, kp
+
+
+class KeypointRCNN(FasterRCNN):
+    """torchvision's keypointrcnn_resnet50_fpn at test time: FasterRCNN, then on its detections multiscale_roi_align
+    (padded, P = keypoint_P) -> KeypointHead (raw rows) -> heatmaps_to_keypoints in the deconv_rows layout.  Adds
+    "keypoints" [N][D][K][3] = (x, y, 1) and "keypoints_scores" [N][D][K], rows past count zero."""
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, keypoint_P: int = 14,
+                        **faster_rcnn) -> "KeypointRCNN":
+        """sd: FasterRCNN's keys plus roi_heads.keypoint_head.* and roi_heads.keypoint_predictor.*.  Every other argument
+        is FasterRCNN.from_state_dict's."""
+        keypoint_P = int(keypoint_P)
+        _check_select(faster_rcnn.get("select", "torch"))
+        if not 1 <= keypoint_P <= KEYPOINT_MAX_P:
+            raise WinoError(f"keypoint_P={keypoint_P}: need 1 <= keypoint_P <= {KEYPOINT_MAX_P}")
+        rest, kp_sd = split_keypoint_state_dict(sd)
+        validate_keypoint_head_state_dict(kp_sd, out_channels)
+        m = super().from_state_dict(rest, arch, num_classes, out_channels, device=faster_rcnn.pop("device", None),
+                                    **faster_rcnn)
+        m.keypoint_head = KeypointHead.from_state_dict(kp_sd, out_channels, m.device)
+        m.keypoint_P = keypoint_P
+        return m
+
+    def prepare(self, N: int, H: int, W: int) -> None:
+        """FasterRCNN.prepare, then the keypoint branch's tensors: the keypoint RoIAlign output [N*D][P+2][P+2][C], the
+        detection rois [N][D][5] and the outputs [N][D][K][3] and [N][D][K]."""
+        if max(int(H), int(W)) > KEYPOINT_MAX_SIDE:
+            raise WinoError(f"Keypoint R-CNN: a batch of {H} x {W} exceeds {KEYPOINT_MAX_SIDE} pixels a side")
+        super().prepare(N, H, W)
+        self._shape = None   # (until the rest is in place)
+        N, D, P, K, dev, f32 = int(N), self.detections, self.keypoint_P, self.keypoint_head.K, self.device, torch.float32
+        with torch.cuda.device(dev):
+            self.keypoint_head.prepare(N * D, P)
+            self._kp_pooled = torch.empty((N * D, P + 2, P + 2, self.keypoint_head.in_channels), dtype=f32, device=dev)
+            self._det_rois = torch.empty((N, D, 5), dtype=f32, device=dev)
+            self._keypoints = torch.empty((N, D, K, 3), dtype=f32, device=dev)
+            self._kp_scores = torch.empty((N, D, K), dtype=f32, device=dev)
+        self._shape = (int(N), int(H), int(W))
+
+    def _keypoint_branch(self, out, feats, st=None) -> None:
+        """The keypoint branch on the detections _detect left in _det_rois; adds "keypoints" and "keypoints_scores"."""
+        from . import heatmaps_to_keypoints, multiscale_roi_align
+        N, H, W = self._shape
+        D, P, head = self.detections, self.keypoint_P, self.keypoint_head
+        with torch.cuda.device(self.device):
+            pooled = multiscale_roi_align(feats, self._det_rois.view(N * D, 5), (H, W), P, 2, in_padded=True,
+                                          out_padded=True, out=self._kp_pooled)
+            rows, ld = head(pooled, raw=True)
+            heatmaps_to_keypoints(rows, self._det_rois, K=head.K, M=4 * P, layout="deconv_rows", bias=head.bias, ld=ld,
+                                  max_side=max(H, W), out=self._keypoints, scores_out=self._kp_scores)
+        out["keypoints"], out["keypoints_scores"] = self._keypoints, self._kp_scores
+        if st is not None:
+            st.update(keypoint_rois=self._det_rois, keypoint_pooled=pooled, keypoint_rows=rows)
+
+    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
+        """FasterRCNN.forward's dict plus "keypoints" [N][D][K][3] and "keypoints_scores" [N][D][K] (rows past count are
+        zero): tensors of the model's, valid until the next forward.  stages=True adds keypoint_rois, keypoint_pooled and
+        keypoint_rows (the raw [N*D*P*P][ld] GEMM output)."""
+        st = {} if stages else None
+        self._begin(x)   # (prepare before _det_rois is named)
+        out, feats, _, _ = self._detect(x, image_sizes, st, rois_out=self._det_rois)
+        self._keypoint_branch(out, feats, st)
+        if stages:
+            out.update(st)
+        return out
+
+    def _prepare_outputs(self, tf, Hmax: int, Wmax: int) -> None:
+        N, D, K, dev = tf["shape"][0], self.detections, self.keypoint_head.K, self.device
+        ones = torch.ones((N, 1, 1), dtype=torch.float32, device=dev)
+        tf["kp_ratio"] = torch.cat([tf["ratio"][:, :, :2], ones], dim=2).reshape(N, 1, 1, 3).contiguous()   # (rw, rh, 1)
+        tf["keypoints"] = torch.empty((N, D, K, 3), dtype=torch.float32, device=dev)
+
+    def predict(self, images):
+        """FasterRCNN.predict's dict plus "keypoints" in each image's own pixels and "keypoints_scores": the keypoints are
+        computed on the un-rescaled detections, then multiplied by (rw, rh, 1) (torchvision's resize_keypoints)."""
+        images, tf = self._ready(images)
+        out, feats, _, _ = self._detect(self._transform(images, tf), tf["image_hw"], None, rois_out=self._det_rois)
+        self._keypoint_branch(out, feats)
+        with torch.cuda.device(self.device):
+            out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
+            out["keypoints"] = torch.mul(out["keypoints"], tf["kp_ratio"], out=tf["keypoints"])
+        out["original_sizes"] = list(tf["orig"])
+        return out
+
+    @staticmethod
+    def to_lists(out):
+        """torchvision's list of {"boxes", "scores", "labels", "keypoints" [c][K][3], "keypoints_scores" [c][K]} per image.
+        Synchronises (it reads count)."""
+        counts = out["count"].tolist()
+        res = FasterRCNN.to_lists(out)
+        for n, c in enumerate(counts):
+            for key in ("keypoints", "keypoints_scores"):
+                res[n][key] = out[key][n, :c].clone()
+        return res
+
+    @staticmethod
+    def to_image_lists(out):
+        """to_lists of a predict's result: boxes and keypoints are already in each image's own pixels."""
+        return KeypointRCNN.to_lists(out)
+
+
+__all__ = ["BoxHead", "MaskHead", "KeypointHead", "RPN", "FasterRCNN", "MaskRCNN", "KeypointRCNN", "split_mask_state_dict",
+           "split_keypoint_state_dict", "postprocess_detections", "base_anchors", "pack_rpn_head",
+           "expected_rpn_keys", "expected_box_head_keys", "expected_mask_head_keys", "expected_keypoint_head_keys",
+           "validate_box_head_state_dict", "validate_mask_head_state_dict", "validate_keypoint_head_state_dict", "pack_fc6",
+           "pack_predictor", "pack_deconv", "pack_logits", "pack_kps_deconv"]

@@ -68,7 +68,7 @@ extern "C" {
  * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
  * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_select_topk_hw, wino_roi_align_launches,
  * wino_image_transform_hw, WINO_IMAGE_*, WINO_TRANSFORM_MAX_IMAGES, wino_transform_size,
- * wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_keypoints_hw, WINO_KP_LAYOUT_*, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -886,6 +886,48 @@ int wino_batched_nms_hw(const float* boxes, const float* scores, const int* grou
 int wino_mask_paste_hw(const float* logits, int layout, const int* labels, const float* boxes, const float* image_hw,
                        int N, int D, int classes, int M, int ld, int H, int W, float threshold, float* out, void* binary,
                        wino_stream_t s);
+
+/* ---- heatmaps to keypoints: the output stage of Keypoint R-CNN (keypoints.hip) ---------------------
+ * torchvision's heatmaps_to_keypoints -- there a Python loop over detections that reads each box size on the host,
+ * allocates a [K][hc][wc] bicubic resize of the detection's heatmaps and takes an argmax over it -- for all R detections
+ * and all K keypoints in one HIP launch, one workgroup per (r, k); the resized map is never stored.
+ *   maps       DEVICE, read in place, in one of two layouts:
+ *              WINO_KP_LAYOUT_PLANES       [R][K][M][M], torchvision's keypoint logits.  `ld` is ignored, bias is NULL
+ *              WINO_KP_LAYOUT_DECONV_ROWS  [R P P][ld], M = 4 P: the partial products of ConvTranspose2d(C, K, 4, stride
+ *                                          2, padding 1) as a GEMM writes them, row (r, iy, ix), column (ky 4 + kx) K + k,
+ *                                          16 K <= ld.  The kernel forms low[k][oy][ox], 2P x 2P: the at most four
+ *                                          elements with ky = (oy + 1) mod 2 or that + 2, iy = (oy + 1 - ky) / 2 in
+ *                                          [0, P), likewise in x, summed in ascending (ky, kx), then + bias[k].  It
+ *                                          upsamples low x2 with wino_resize_bilinear_hw's coordinates (in = 2P, out =
+ *                                          4P: lambdas exactly 0, 0.25, 0.75) and value formula -- torch's
+ *                                          interpolate(scale_factor=2, bilinear, align_corners=False) -- which gives
+ *                                          the M x M plane PLANES would have held
+ *   bias       DEVICE [K], required for DECONV_ROWS; NULL for PLANES
+ *   rois       DEVICE [R][5] fp32 (n, x1, y1, x2, y2): the RoIAlign rows wino_batched_nms_hw writes into rois_out,
+ *              padding rows (-1, 0, 0, 0, 0)
+ *   keypoints  DEVICE [R][K][3] fp32 (x, y, 1);  scores  DEVICE [R][K] fp32
+ * Box (fp32, in this order, no product folded into a sum): w = max(x2 - x1, 1), wc = (int) ceil(w), cw = w / wc; h, hc,
+ * ch likewise.  Plane (r, k) is resized to hc x wc with torch's bicubic, align_corners=False: A = -0.75, taps at
+ * i - 1 .. i + 2 with each index clamped into [0, M), all 16 taps always multiplied.  Named deviation: the source
+ * coordinate is exact integer arithmetic like wino_resize_bilinear_hw's, but not clamped at 0: per axis num =
+ * (2 d + 1) M - out, i = floor_div(num, 2 out), t = float(num - i 2 out) / float(2 out).  pos is the argmax over the
+ * hc x wc values under torch.argmax's rules: a NaN is the greatest value, and among equal values the lowest flat index
+ * y wc + x wins.  With x_i = pos mod wc, y_i = pos / wc: keypoints[r][k] = ((x_i + 0.5) cw + x1, (y_i + 0.5) ch + y1, 1),
+ * scores[r][k] = the value at pos.  The order in which the 16 products are summed is the kernel's own.
+ * Special rows.  !(n >= 0) (a padding row): all 3K + K outputs of the row are 0 and nothing else of the row is read.  A
+ * box coordinate that is not finite, or wc or hc above max_side: NaN in all of the row's outputs and no map read (named
+ * deviation: torch would have to allocate such a map; it cannot occur for boxes clipped to an image no larger than
+ * max_side).  A NaN in a map reaches exactly the outputs whose taps include it and changes no other (r, k).
+ * 1 <= M <= 64 (DECONV_ROWS: M = 4 P, 1 <= P <= 16, 16 K <= ld), K >= 1, 1 <= max_side <= 16384, R >= 0 (0: WINO_OK,
+ * nothing launched); WINO_E_SHAPE otherwise.  maps may pass 2^31 elements: it is addressed from 64-bit bases.  A NULL
+ * maps / rois / keypoints / scores, a bias that is NULL for DECONV_ROWS or given for PLANES, a pointer that is not 16-byte
+ * aligned, a layout that is neither of the two, or an output that overlaps an input or the other output is WINO_E_ARG.
+ * Every check comes before the launch.  No workspace and no stream scratch: the call can be captured into a graph as
+ * it is. */
+#define WINO_KP_LAYOUT_PLANES 0
+#define WINO_KP_LAYOUT_DECONV_ROWS 1
+int wino_keypoints_hw(const float* maps, int layout, const float* bias, const float* rois, int R, int K, int M, int ld,
+                      int max_side, float* keypoints, float* scores, wino_stream_t s);
 
 /* ---- image transform: the input stage of an R-CNN (image_transform.hip) ---------------------------
  * torchvision's GeneralizedRCNNTransform at test time -- normalise, resize, batch -- for N images of different sizes, in
