@@ -55,8 +55,12 @@ constexpr int LDS_BYTES = N_RSTAGE * RAW_BYTES + N_USTAGE * U_BYTES;  // 163840 
 constexpr int U_CHUNK_FLOATS = 16 * KB * BC; // 8192 floats per (c-chunk, k-block)
 constexpr int PF = 2;                        // filter-fragment prefetch distance (points); 2..6 measured equal
 constexpr int SLAB_BYTES = TB * 4 * KB * 4;  // 65536: pre-BN output of one item (64 tiles x 2x2 px x 64 k)
-constexpr int DMA0 = 4;                      // first point-step that issues an LDS-DMA piece; tools/ablate_fused, current loop:
-                                             // 0 / 2 / 4 / 6 / 8 give 42.7 / 42.5 / 42.45 / 42.5 / 42.7 cycles per MFMA
+// First point-step that issues an LDS-DMA piece.  tools/ablate_fused 256 256 q with the iteration's barrier behind step 1
+// (SYNC_STEP): 2 / 4 / 6 / 7 / 8 give 39.5 / 39.2 / 38.8 / 38.8 / 38.9-39.1 cycles per MFMA (the barrier at the top of the
+// body: 4 / 6 gave 39.2 / 39.3) -- the pieces' barrier moved two steps back, and so did the best start.  The
+// any-feature-map build keeps 4: at 7x7x512 (whole 64-iteration items, all 256 workgroups asking for the same filter
+// chunk in the same step) 6 measured +0.4 % and 4 equal to the barrier at the top (profiles/loop_barrier/).
+constexpr int dma0_for(bool gen) { return gen ? 4 : 6; }
 
 // s_waitcnt lgkmcnt(n) alone (vmcnt/expcnt fields at "no wait"); n folds to a literal once the
 // point loop is unrolled.
@@ -78,23 +82,34 @@ __device__ __forceinline__ void wait_lds(int n) {
     default: __builtin_amdgcn_s_waitcnt(0xCF7F); break;
   }
 }
+// The iteration's vmcnt(0) + barrier sits BEHIND the MFMAs of step SYNC_STEP - 1, not at the top of the body: steps
+// 0 .. SYNC_STEP - 1 (point 0: 8 MFMAs) consume only what the wave already holds -- V_it, the fragments requested at
+// steps 14, 15 of the iteration before -- and read only U_it, visible since the barrier before.  A wave goes from its
+// transform burst and loop tail straight into those MFMAs and arrives at the barrier while the last of them executes
+// (it cannot arrive before it has issued all eight; measured, DESIGN.md section 3.1 "Where the time goes").  Everything
+// that needs the barrier comes behind it: the patch reads of raw_{it+1}, the reads of U_{it+1} (steps 14, 15) and the
+// LDS-DMA refills.
+constexpr int SYNC_STEP = 2;
+static_assert(SYNC_STEP >= 1 && SYNC_STEP + 6 <= 16, "the twelve patch reads lie between the barrier and the burst");
+static_assert(dma0_for(false) >= SYNC_STEP && dma0_for(false) + 8 <= 16 && dma0_for(true) >= SYNC_STEP && dma0_for(true) + 8 <= 16,
+              "no LDS-DMA piece in front of the iteration's barrier");
+static_assert(16 - PF >= SYNC_STEP, "the reads of U_{it+1} lie behind the iteration's barrier");
 // LDS requests issued at the top of pinned step q of the point loop (see the kernel): always 2
 // filter-fragment reads (step q+2 of this chunk, or step q-14 of the NEXT chunk on steps
-// 14, 15), then 2 patch reads while q < 6 (a wave reads 12 of its tiles' 16 patch pixels).
-constexpr int lds_nr(int q) { return q < 6 ? 2 : 0; }
+// 14, 15), then 2 patch reads on the six steps from SYNC_STEP on (a wave reads 12 of its tiles' 16 patch pixels).
+constexpr int lds_nr(int q) { return q >= SYNC_STEP && q < SYNC_STEP + 6 ? 2 : 0; }
 constexpr int lds_n(int q) { return 2 + lds_nr(q); }
-// How many LDS requests are younger than the last one step e's consumers need: the filter
-// fragments of point e (requested two steps earlier; for e < 2 before the barrier, which
-// drains lgkmcnt) and, on steps 2,4,6,8, the patch pixels requested at steps e-2, e-1.
+// How many LDS requests are younger than the last one step e's MFMAs need: the filter fragments of step e, requested
+// PF steps earlier (for e < PF at steps 14, 15 of the iteration before: the count runs round the loop, and nothing
+// between two bodies issues an LDS request that is still in flight at the next body's top; an extra one would only
+// make the wait stricter).  The patch pixels are consumed by the burst behind step 15, which drains.
 constexpr int lds_wait_count(int e) {
-  // the fragments of point e were requested at step e-PF, before that step's patch reads
-  int after = 15;
-  if (e >= PF) {
-    after = lds_nr(e - PF);
-    for (int q = e - PF + 1; q <= e; q++) after += lds_n(q);
-  }
+  // the fragments of step e were requested at step e-PF, before that step's patch reads
+  int after = lds_nr((e - PF + 16) % 16);
+  for (int q = e - PF + 1; q <= e; q++) after += lds_n((q + 16) % 16);
   return after > 15 ? 15 : after;
 }
+static_assert(lds_wait_count(0) == 4 && lds_wait_count(1) == 4, "steps 0, 1: two steps' fragment reads are younger");
 
 // 8-byte LDS read at an absolute LDS byte address held in a register.  (`smem + offset` leaves a
 // `v_add_u32 v, 0, v` per read in the loop -- the dynamic-LDS base is a symbol the optimizer does not
@@ -258,6 +273,7 @@ __global__ void __launch_bounds__(NTHREADS, 2)
 wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   static_assert(EPI == EPI_PLAIN || EPI == EPI_RES || EPI == EPI_POOL, "epilogue form");
   constexpr bool RES = EPI == EPI_RES, POOL = EPI == EPI_POOL;
+  constexpr int DMA0 = dma0_for(GEN);
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const float* in = prm.in;
   const float* Uq = prm.Uq;
@@ -416,7 +432,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     if (j == 3) v[e] = sub2(tmp[i * 4 + 1], tmp[i * 4 + 3]);
   };
 
-  unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0, st_span = 0;   // ABLATE & PROBE_PHASES: phase stamps
+  unsigned long long st_wait = 0, st_comp = 0, st_epi = 0, st_prev = 0, st_span = 0, st_restart = 0;   // ABLATE & PROBE_PHASES: phase stamps
   unsigned long long st_ph[4] = {0, 0, 0, 0};   // epilogue phases: barrier, A^T m A, slab+ticket, gather+finalize
   unsigned long long st_sub[PH_NSUB] = {0, 0, 0, 0, 0, 0};   // ... and the parts of A^T m A and of gather+finalize (PH_SUB0 + PHS_*)
   auto stamp = [&]() -> unsigned long long {
@@ -560,8 +576,9 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   //    V_{i+1}, in place over the V registers of points that have already retired, so the
   //    matrix pipe never waits for the input transform (2 raw stages suffice);
   //  * U_{i+1} is already visible during iteration i (3 filter stages), so the first filter
-  //    fragments of iteration i+1 are requested BEFORE the iteration barrier and the MFMAs
-  //    resume right after it instead of eating an LDS round trip.
+  //    fragments of iteration i+1 are requested at steps 14, 15 of iteration i, and iteration i+1 runs
+  //    point 0 (steps 0, 1: 8 MFMAs) straight from them and from V_{i+1}, IN FRONT of its vmcnt(0) + barrier
+  //    (SYNC_STEP): only what follows needs raw_{i+2} / U_{i+2} landed and the refilled stages free.
   auto issue_raw1 = [&](int rstage, int j) {  // one 1-KiB piece
     if (ABLATE & PROBE_NO_DMA_A) return;
     dma16_buf(rsrc_in, raw_off[j], d_soff_raw, smem + rstage * RAW_BYTES + (8 * j + w) * 1024);
@@ -613,7 +630,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     for (int cb = 0; cb < 4; cb++) acc[e][cb] = (f32x4){0.f, 0.f, 0.f, 0.f};
   P2 v[8];           // V_it (the wave's 8 points) at the top of iteration `it`; rewritten in place with V_{it+1}
   // A pinned step s = 0..15 of an iteration is (point p = s >> 1, column-block pair s & 1): 4 MFMAs.
-  f32x2 bfn[PF][2];  // filter fragments of steps 0..PF-1 of the next iteration (requested pre-barrier)
+  f32x2 bfn[PF][2];  // filter fragments of steps 0..PF-1 of the next iteration (requested at steps 14, 15; consumed in front of its barrier)
 
   // ---- prologue: iterations 0 and 1 in flight; V_0 and the first fragments un-pipelined -----
   dma_set_item(c_item_vg, c_chunk);
@@ -686,17 +703,27 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
   }
   auto body = [&](auto par_c, int rs_dma, int us_dma) {
     constexpr int ROFF = decltype(par_c)::value ? 0 : RAW_BYTES;
-    if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (st_prev) st_comp += t - st_prev; st_prev = t; }
-    if (!(ABLATE & PROBE_NO_SYNC)) {
-      wait_vmem_all();   // my DMA pieces of raw_{it+1} and U_{it+1} have landed
-      __syncthreads();   // everyone's have; everyone is done with the stages refilled below
-    }
-    if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_wait += t - st_prev; st_prev = t; }
+    // The iteration's synchronisation point, behind the MFMAs of step SYNC_STEP - 1 (see SYNC_STEP).  A bare barrier
+    // behind the wave's own vmcnt(0): __syncthreads() would also drain lgkmcnt, and with it the fragment requests
+    // steps 0 and 1 have just made.  What it orders: the LDS-DMA writes of raw_{it+1} / U_{it+1} (every wave's have
+    // landed) before the reads below it, and every wave's reads of raw_it (iteration it - 1) and U_{it-1} before the
+    // refills of R[it & 1] and U[(it + 2) % 3] from step DMA0 on.
+    auto sync_point = [&]() {
+      if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); if (st_prev) st_comp += t - st_prev; st_prev = t; }
+      if (!(ABLATE & PROBE_NO_SYNC)) {
+        wait_vmem_all();   // my DMA pieces of raw_{it+1} and U_{it+1} have landed
+        __builtin_amdgcn_s_barrier();   // everyone's have; everyone is done with the stages refilled below
+        asm volatile("" ::: "memory");
+      }
+      if (ABLATE & PROBE_PHASES) { const unsigned long long t = stamp(); st_wait += t - st_prev; st_prev = t; }
+    };
     // The 8 LDS-DMA pieces this wave contributes per iteration (4 of raw_{it+2} into R[it&1], 4 of
     // U_{it+2} into U[(it+2)%3]) are issued one per step in steps DMA0..DMA0+7 instead of in a
-    // burst here: an LDS-DMA instruction holds the wave's issue port for >100 cycles, and
-    // spread out the SIMD's other wave covers that with its MFMAs; starting at step 4 leaves the
-    // last pieces a third of an iteration of flight time before the next vmcnt(0).
+    // burst behind the barrier: an LDS-DMA instruction holds the wave's issue port for >100 cycles, and
+    // spread out the SIMD's other wave covers that with its MFMAs; starting at step DMA0 = 6 (the 14x14 builds) leaves the
+    // last pieces steps 14, 15 and the burst of flight time before the wave's next vmcnt(0) -- the compiler, which cannot
+    // tell the LDS stages apart, puts one of its own in front of the next body's first ds_read -- and point 0 more
+    // before the barrier.
     // They are issued unconditionally: a branch per piece (the compiler routes half of the
     // conditions through a VALU compare) cost ~30 of the ~210 instructions between an iteration's
     // first and last MFMA.  In the last two iterations of the range, where nothing is left to
@@ -705,7 +732,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
     // stages its stores in, and drained by the next iteration's vmcnt(0) or by the one before exit.
     // raw_{it+1}: the stage is ROFF
     // fragment base addresses of U_it and U_{it+1}: ub_cur[] / ub_nxt[], loop-carried registers that are
-    // rotated in the iteration's tail (where the wave would wait at the barrier anyway) -- formed here, at
+    // rotated in the iteration's tail -- formed here, at
     // the top, their eight adds sit in front of the iteration's first MFMAs; left inside the reads,
     // hipcc re-adds the stage offset before every one.
     // (the two copies of the body use the two register sets in swapped roles, so the rotation
@@ -743,7 +770,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       } else if (e >= DMA0 + 4 && e < DMA0 + 8) {
         issue_u1(us_dma, e - DMA0 - 4);
       }
-      // next iteration's A operand rides along: steps 0-5 read its 12 patch pixels (two per step, in
+      // next iteration's A operand rides along: the six steps behind the barrier (2-7) read its 12 patch pixels (two per step, in
       // the order R0[j], R1[j], R2[j] column by column); B^T d B itself is written behind the last
       // step, after the iteration's last MFMA, where it runs as one burst of packed adds while the
       // SIMD's other wave still has MFMAs to issue.  (It used to be written inside the steps and left
@@ -756,8 +783,8 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       // (+8 %); the two waves of a SIMD phase-shifted (+6 %).
       // (After the last iteration this works on stale LDS; the result is never used -- cheaper
       // than a branch.)
-      if (e < 6 && !(ABLATE & PROBE_NO_A_PATH)) {
-        const int q0 = 2 * e, q1 = 2 * e + 1;   // read index q -> (row k = q % 3, column j = q / 3)
+      if (e >= SYNC_STEP && e < SYNC_STEP + 6 && !(ABLATE & PROBE_NO_A_PATH)) {
+        const int q0 = 2 * (e - SYNC_STEP), q1 = q0 + 1;   // read index q -> (row k = q % 3, column j = q / 3)
         d[(q0 % 3) * 4 + q0 / 3] = lds_read2(a_adr[q0 % 3][q0 / 3] + ROFF);
         d[(q1 % 3) * 4 + q1 / 3] = lds_read2(a_adr[q1 % 3][q1 / 3] + ROFF);
       }
@@ -776,14 +803,21 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
         // see MFMA hazards of inline asm: the only VALU access to acc[] is in the epilogue, behind
         // explicit s_nops.
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 0]) : "v"(a.x), "v"(b0.x));
+        if ((ABLATE & PROBE_PHASES) && e == SYNC_STEP) st_restart += stamp() - st_prev;   // the first MFMA behind the barrier is issued (since its release)
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 1]) : "v"(a.x), "v"(b1.x));
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 0]) : "v"(a.y), "v"(b0.y));
         asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc[pt][2 * cbp + 1]) : "v"(a.y), "v"(b1.y));
       }
-      if ((ABLATE & PROBE_PHASES) && e == 15) st_span += stamp() - st_prev;   // the iteration's last MFMA is issued
+      if (ABLATE & PROBE_PHASES) {
+        if (e == 15) st_span += stamp() - st_prev;   // the iteration's last MFMA is issued (since the barrier's release)
+      }
       __builtin_amdgcn_sched_barrier(0);
+      if (e == SYNC_STEP - 1) {
+        sync_point();
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
-    // B^T d B of the next iteration, in place over V: every point has retired, all patch reads are in (step 7)
+    // B^T d B of the next iteration, in place over V: every point has retired, all patch reads are in (step 9)
     if (!(ABLATE & PROBE_NO_A_PATH)) {
       if (ABLATE & PROBE_NO_BTDB) {
 #pragma unroll
@@ -1398,6 +1432,7 @@ wino_f2_fused_kernel(const FusedArgs<EPI == EPI_RES> prm) {
       dbg[PH_EPI0 + 2] = st_ph[2];
       dbg[PH_EPI0 + 3] = st_ph[3];
       dbg[PH_SPAN] = st_span;
+      dbg[PH_RESTART] = st_restart;
 #pragma unroll
       for (int k = 0; k < PH_NSUB; k++) dbg[PH_SUB0 + k] = st_sub[k];
     }

@@ -43,16 +43,18 @@ constexpr int TL1_HW_ID = 4, TL1_ENTRY_CYC = 5, TL1_EXIT_CYC = 6;   // 1x1: HW_R
 constexpr int CLK_WORDS = 4, CLK_BEGIN_CYC = 0, CLK_BEGIN_RT = 1, CLK_END_CYC = 2, CLK_END_RT = 3;
 // PROBE_PHASES: PH_WORDS per wave (PH_USED of them written), PH_WAVES waves per logical workgroup; sums of s_memtime
 // differences: vmcnt wait + barrier, the rest of the iterations, the epilogues, and of those (PH_EPI0 + 0..3) the
-// barrier, A^T m A, slab + ticket, gather + finalize.  PH_SPAN is the part of PH_COMPUTE from the barrier's release to
-// the iteration's last MFMA: PH_COMPUTE - PH_SPAN is what a wave runs between its last MFMA and the next barrier.
+// barrier, A^T m A, slab + ticket, gather + finalize.  The iteration's barrier sits behind the MFMAs of point 0 (steps 0, 1):
+// PH_SPAN is the part of PH_COMPUTE from the barrier's release to the last MFMA of step 15, PH_COMPUTE - PH_SPAN what a
+// wave runs from there to its arrival at the next barrier (the burst, the loop tail and point 0's 8 MFMAs), PH_RESTART
+// the time from a release to the issue of the first MFMA behind it.
 // PH_SUB0 + PHS_*: finer stamps inside two of the epilogue phases.  A^T m A = the 16 part() evaluations with their LDS
 // writes (PARTS), the pair exchange with its two barriers (EXCHANGE), the accumulators' re-zeroing (ZERO).  Of gather +
 // finalize: a gather's slab loads and adds (GATHER), BN + ReLU + the LDS writes of the transpose (BN), the LDS read /
 // tile decode / store loop (STORE); what is left of that phase is the hand-off bookkeeping and the ticket's round
 // trip.  Each stamp costs an s_memtime and an lgkmcnt(0) wait, so the three parts of A^T m A add up to a little less
 // than the (now longer) phase around them: read shares.
-constexpr int PH_WORDS = 16, PH_WAVES = 8, PH_USED = 14, PH_WAIT = 0, PH_COMPUTE = 1, PH_EPILOGUE = 2, PH_EPI0 = 3, PH_SPAN = 7,
-              PH_SUB0 = 8, PH_NSUB = 6;
+constexpr int PH_WORDS = 16, PH_WAVES = 8, PH_USED = 15, PH_WAIT = 0, PH_COMPUTE = 1, PH_EPILOGUE = 2, PH_EPI0 = 3, PH_SPAN = 7,
+              PH_SUB0 = 8, PH_NSUB = 6, PH_RESTART = 14;
 constexpr int PHS_PARTS = 0, PHS_EXCHANGE = 1, PHS_ZERO = 2, PHS_GATHER = 3, PHS_BN = 4, PHS_STORE = 5;
 // DIAG build of the 3x3 latency kernel: SM_WORDS per workgroup, s_memrealtime, in time order (phase i of
 // tools/small_timeline is slot i + 1 minus slot i).  A workgroup that does not finish its block stops at SM_TICKET;

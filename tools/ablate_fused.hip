@@ -223,14 +223,15 @@ int main(int argc, char** argv) {
              4 * c, 4 * c + 3, atma, sub[PHS_PARTS], sub[PHS_EXCHANGE], sub[PHS_ZERO], fin, sub[PHS_GATHER], sub[PHS_BN], sub[PHS_STORE],
              fin - sub[PHS_GATHER] - sub[PHS_BN] - sub[PHS_STORE]);
     }
-    // where an iteration's compute part ends: barrier release -> last MFMA (the MFMA span), last MFMA -> arrival at the
-    // next barrier (transform burst, DMA walker, loop control), arrival -> release; per wave class (waves 0-3 / 4-7)
+    // where an iteration's compute part ends: barrier release -> last MFMA of step 15 (the MFMA span), from there to the
+    // arrival at the next barrier (transform burst, DMA walker, loop control and the 8 MFMAs of point 0, which run in
+    // front of the barrier), arrival -> release, release -> first MFMA behind it; per wave class (waves 0-3 / 4-7)
     for (int c = 0; c < 2; c++) {
-      double span = 0, comp = 0, wait = 0;
-      for (int w = 4 * c; w < 4 * c + 4; w++) { span += sum[w][PH_SPAN]; comp += sum[w][PH_COMPUTE]; wait += sum[w][PH_WAIT]; }
+      double span = 0, comp = 0, wait = 0, restart = 0;
+      for (int w = 4 * c; w < 4 * c + 4; w++) { span += sum[w][PH_SPAN]; comp += sum[w][PH_COMPUTE]; wait += sum[w][PH_WAIT]; restart += sum[w][PH_RESTART]; }
       const double d = 4.0 * wgs * iters;
-      printf("  waves %d-%d: MFMA span %6.0f  last MFMA -> barrier arrival %6.0f  arrival -> release %6.0f  last MFMA -> release %6.0f cycles per iteration\n",
-             4 * c, 4 * c + 3, span / d, (comp - span) / d, wait / d, (comp - span + wait) / d);
+      printf("  waves %d-%d: MFMA span %6.0f  step 15's last MFMA -> barrier arrival %6.0f  arrival -> release %6.0f  release -> first MFMA %6.0f cycles per iteration\n",
+             4 * c, 4 * c + 3, span / d, (comp - span) / d, wait / d, restart / d);
     }
   }
   return 0;
