@@ -75,6 +75,18 @@ host read and a ``[K][h][w]`` bicubic resize per detection -- in one launch: ``"
 multiplies by ``(rw, rh, 1)`` (``resize_keypoints``).  ``KeypointHead(raw=False)`` composes torchvision's logits
 [R][K][4P][4P] in torch (``fold``, bias, ``interpolate``) for callers who want them.
 
+How a branch plugs in.  ``FasterRCNN`` holds the only ``prepare`` / ``forward`` / ``predict`` / ``to_lists``; a detector
+differs by ``self.branches`` (``MaskBranch``, ``KeypointBranch``; none for Faster R-CNN), and all a detector keeps for
+them is ``_det_rois`` [N][D][5], the detections as RoIAlign rows, allocated and handed to ``postprocess_detections`` only
+when there is a branch.  A branch owns its head, P, RoIAlign output and output tensors and has five hooks:
+``check(H, W)`` raises before anything is allocated; ``prepare(N, D, H, W, for_predict)`` allocates and prepares the head
+at R = N * D; ``run(out, feats, det_rois, (H, W), stages)`` is everything that reads the un-rescaled detections;
+``finish(out, image_hw, (H, W), tf)`` runs once the boxes are final (``tf`` is ``prepare_images``' dict in ``predict``,
+None in ``forward``); ``predict_outputs(tf, Hmax, Wmax)`` adds the branch's entries to that dict.  One pass is
+``_detect`` -> every ``run`` in list order -> ``predict``'s boxes x ratio -> every ``finish`` in list order, and ``_shape``
+is set when the last branch has prepared.  ``to_lists`` slices whichever output keys the dict holds.  Both heads' 3x3
+chains are ``_ConvTower``: the filter packing, the ``pooled_padded`` checks, the zero-ring buffers and the launch loop.
+
 Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets, RetinaNet and the BN variants of
 the v2 heads.
 
@@ -249,12 +261,58 @@ class BoxHead(Net):
         return self._scores[:, : self.classes], self._scores[:, self.classes: 5 * self.classes]
 
 
-class MaskHead(Net):
+class _ConvTower(Net):
+    """What MaskHead and KeypointHead share: a chain of conv3x3_bn_relu layers at N = R on the padded RoIAlign output.  A
+    subclass gives `in_channels`, `widths` (one per layer) and `_ones` (at least max(widths) long)."""
+
+    def _pack_tower(self, sd, stems) -> None:
+        """convs = [(the F(2x2) filter transform, the bias)] of the layers at sd[stem.weight|bias]."""
+        self.convs = [(filter_transform_f2(self._t(sd[f"{s}.weight"])), self._t(sd[f"{s}.bias"])) for s in stems]
+
+    def _alloc_tower(self, R: int, P: int) -> None:
+        """The layers' outputs [R][P+2][P+2][width] with zero rings.  Layer i writes buffer (its width, i mod 2): equal
+        widths ping-pong on two tensors."""
+        bufs, self._acts = {}, []
+        for i, w in enumerate(self.widths):
+            if (w, i % 2) not in bufs:
+                bufs[(w, i % 2)] = torch.zeros((R, P + 2, P + 2, w), dtype=torch.float32, device=self.device)
+            self._acts.append(bufs[(w, i % 2)])
+
+    def _reserve_tower(self, R: int, P: int) -> None:
+        """The stream scratch of the launches; a head calls it after all its allocations, as it always has."""
+        for c, w in zip([self.in_channels] + self.widths, self.widths):
+            conv3x3_prepare(R, c, w, P, P)
+
+    def _begin_tower(self, x):
+        """forward's opening: x is [R][P+2][P+2][in_channels] float32 on the head's device; a new (R, P) re-runs
+        prepare().  Returns (R, P)."""
+        C = self.in_channels
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or x.shape[1] != x.shape[2]:
+            raise WinoError(f"pooled_padded must be [R][P+2][P+2][{C}]")
+        if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+            raise WinoError(f"pooled_padded must be contiguous float32 on {self.device}")
+        R, P = int(x.shape[0]), int(x.shape[1]) - 2
+        if (R, P) != self._shape:
+            self.prepare(R, P)
+        return R, P
+
+    def _run_tower(self, x):
+        """The launches; returns the last layer's output (it is not x's memory: x is not written)."""
+        for (U, bias), dst, w in zip(self.convs, self._acts, self.widths):
+            conv3x3_bn_relu(x, U, bias, self._ones[:w], relu=True, out=dst)
+            x = dst
+        return x
+
+
+class MaskHead(_ConvTower):
     """MaskRCNNHeads + MaskRCNNPredictor on the Winograd 3x3 and the 1x1 GEMM kernels, inference only."""
+    _a = property(lambda self: self._acts[0])   # the two ping-pong tensors under the names they had
+    _b = property(lambda self: self._acts[1])
 
     def __init__(self, in_channels: int, classes: int, device):
         super().__init__(device)
         self.in_channels, self.classes = int(in_channels), int(classes)
+        self.widths = [self.in_channels] * MASK_CONVS
 
     @classmethod
     def from_state_dict(cls, sd, in_channels: int = 256, device=None) -> "MaskHead":
@@ -262,8 +320,7 @@ class MaskHead(Net):
         return cls._load(sd, None, device, in_channels, classes)
 
     def _pack(self, sd, eps):
-        self.convs = [(filter_transform_f2(self._t(sd[f"mask_head.{i}.0.weight"])), self._t(sd[f"mask_head.{i}.0.bias"]))
-                      for i in range(MASK_CONVS)]
+        self._pack_tower(sd, [f"mask_head.{i}.0" for i in range(MASK_CONVS)])
         wd, bd = pack_deconv(sd["mask_predictor.conv5_mask.weight"], sd["mask_predictor.conv5_mask.bias"])
         self.wd, self.bd = self._t(wd), self._t(bd)
         wl, bl = pack_logits(sd["mask_predictor.mask_fcn_logits.weight"], sd["mask_predictor.mask_fcn_logits.bias"])
@@ -279,12 +336,11 @@ class MaskHead(Net):
         if R < 1 or P < 2 or P % 2:
             raise WinoError(f"mask head: R={R} boxes of P={P}: need R >= 1 and an even P >= 2")
         with torch.cuda.device(self.device):
-            self._a = torch.zeros((R, P + 2, P + 2, C), dtype=f32, device=self.device)
-            self._b = torch.zeros((R, P + 2, P + 2, C), dtype=f32, device=self.device)
+            self._alloc_tower(R, P)
             self._up = torch.empty((R * P * P, 4 * C), dtype=f32, device=self.device)
             self._scores = torch.empty((R * P * P * 4, kp), dtype=f32, device=self.device)
             self._masks = torch.empty((R, self.classes, 2 * P, 2 * P), dtype=f32, device=self.device)
-            conv3x3_prepare(R, C, C, P, P)
+            self._reserve_tower(R, P)
             conv1x1_prepare(R * P * P, C, 4 * C)
             conv1x1_prepare(R * P * P * 4, C, kp)
         self._shape = (R, P)
@@ -294,21 +350,11 @@ class MaskHead(Net):
         mask logits [R][classes][2P][2P], a tensor of the head's, valid until the next forward.  A new (R, P) re-runs
         prepare().  raw=True: returns (the logits GEMM's output [R*P*P*4][ld] with rows ordered (r, y, x, dy, dx) and the
         classes in its first columns, ld) and skips the permute copy: paste_masks' "gemm_rows" layout."""
-        x, C = pooled_padded, self.in_channels
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or x.shape[1] != x.shape[2]:
-            raise WinoError(f"pooled_padded must be [R][P+2][P+2][{C}]")
-        if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
-            raise WinoError(f"pooled_padded must be contiguous float32 on {self.device}")
-        R, P = int(x.shape[0]), int(x.shape[1]) - 2
-        if (R, P) != self._shape:
-            self.prepare(R, P)
-        kp, ones = int(self.wl.shape[1]), self._ones
+        R, P = self._begin_tower(pooled_padded)
+        C, kp, ones = self.in_channels, int(self.wl.shape[1]), self._ones
         with torch.cuda.device(self.device):
-            src, dst = x, self._a
-            for U, bias in self.convs:   # pooled -> a -> b -> a -> b
-                conv3x3_bn_relu(src, U, bias, ones[:C], relu=True, out=dst)
-                src, dst = dst, (self._b if dst is self._a else self._a)
-            conv1x1_bn_ex(src, self.wd, self.bd, ones[: 4 * C], A_PADDED | RELU, out=self._up, hw=(P, P))
+            top = self._run_tower(pooled_padded)
+            conv1x1_bn_ex(top, self.wd, self.bd, ones[: 4 * C], A_PADDED | RELU, out=self._up, hw=(P, P))
             # rows (r, y, x) x columns (dy, dx, c) are rows (r, y, x, dy, dx) x columns c: the logits GEMM's A as it stands
             conv1x1_bn(self._up.view(R * P * P * 4, C), self.wl, self.bl, ones[:kp], False, out=self._scores)
             if raw:
@@ -559,6 +605,10 @@ def postprocess_detections(head_out: torch.Tensor, rois: torch.Tensor, image_hw:
     return out
 
 
+MASK_KEYS = ("masks", "masks_binary")
+LIST_KEYS = ("boxes", "scores", "labels") + MASK_KEYS + ("keypoints", "keypoints_scores")   # what to_lists slices per image
+
+
 class FasterRCNN(Net):
     """torchvision's fasterrcnn_*_fpn at test time on the library's kernels: ResNetFPN(padded) -> RPN ->
     multiscale_roi_align -> BoxHead -> postprocess_detections.  forward takes the already normalised batch; predict
@@ -572,6 +622,7 @@ class FasterRCNN(Net):
         self.backbone, self.rpn, self.box_head = backbone, rpn, box_head
         self.detections, self.score_thresh, self.nms_thresh = int(detections), float(score_thresh), float(nms_thresh)
         self.max_candidates = max_candidates
+        self.branches = []   # the RoI branches that run on the detections, in order: none for Faster R-CNN
         self._tf, self._tf_params = None, None   # prepare_images' state, and the parameters of its last call
 
     @classmethod
@@ -605,10 +656,18 @@ class FasterRCNN(Net):
     def prepare(self, N: int, H: int, W: int) -> None:
         """Allocate everything for [N][3][H][W] inputs and reserve every launch's stream scratch on the current stream.
         After it a forward performs no host read of device data, so it can be captured into one graph."""
-        N, H, W, dev = int(N), int(H), int(W), self.device
+        self._prepare(N, H, W, for_predict=False)
+
+    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
+        """prepare(); for_predict: on behalf of prepare_images, so a branch may leave what only forward needs to the
+        first forward.  The model counts as prepared (_shape) once the last branch is."""
+        N, H, W, D, dev = int(N), int(H), int(W), self.detections, self.device
         if self.select == "kernel" and self.max_candidates is not None and int(self.max_candidates) > SELECT_MAX_ROWS:
             raise WinoError(f"select=\"kernel\" keeps at most {SELECT_MAX_ROWS} candidates, "
                             f"max_candidates={self.max_candidates}")
+        for b in self.branches:
+            b.check(H, W)
+        self._shape = None   # (a prepare that raises from here on leaves the model unprepared, whatever it was before)
         with torch.cuda.device(dev):
             self.backbone.prepare(N, H, W)
             p = self.backbone._p
@@ -619,10 +678,14 @@ class FasterRCNN(Net):
             bh.prepare(R)
             self._pooled = torch.empty((R, bh.P, bh.P, bh.in_channels), dtype=torch.float32, device=dev)
             self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=torch.float32, device=dev)
+            # the detections as RoIAlign rows [N][D][5]: what every branch reads, so only written when there is one
+            self._det_rois = torch.empty((N, D, 5), dtype=torch.float32, device=dev) if self.branches else None
+            for b in self.branches:
+                b.prepare(N, D, H, W, for_predict)
         self._shape = (N, H, W)
 
-    def _detect(self, x, image_sizes, st, rois_out=None):
-        """The stages of forward; returns (the result dict, the pyramid, the box head's pooled input, image_hw)."""
+    def _detect(self, x, image_sizes, st):
+        """Faster R-CNN's stages; returns (the result dict, the pyramid, image_hw)."""
         from . import multiscale_roi_align
         self._begin(x)
         N, H, W = self._shape
@@ -636,20 +699,36 @@ class FasterRCNN(Net):
             self.box_head(pooled)
             out = postprocess_detections(self.box_head._scores, rois, hw, self.box_head.classes, self.score_thresh,
                                          self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st,
-                                         rois_out=rois_out, select=self.select)
+                                         rois_out=self._det_rois, select=self.select)
         if st is not None:
             st.update(features=feats, pooled=pooled, head_out=self.box_head._scores)
-        return out, feats, pooled, hw
+        return out, feats, hw
+
+    def _run(self, x, image_sizes, st, tf=None):
+        """forward's and predict's one path: _detect, every branch on the un-rescaled detections, predict's boxes into
+        each image's own pixels (`tf`: prepare_images' state, None in forward), then what the branches do once the boxes
+        are final."""
+        out, feats, hw = self._detect(x, image_sizes, st)
+        size = self._shape[1:]
+        with torch.cuda.device(self.device):
+            for b in self.branches:
+                b.run(out, feats, self._det_rois, size, st)
+            if tf is not None:
+                out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
+            for b in self.branches:
+                b.finish(out, hw, size, tf)
+        if tf is not None:
+            out["original_sizes"] = list(tf["orig"])
+        if st is not None:
+            out.update(st)
+        return out
 
     def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
         """x [N][3][H][W] float32, already normalised; image_sizes: None (every image fills the batch) or a float32
         device tensor [N][2] of (H_img, W_img).  Returns {"boxes" [N][D][4], "scores" [N][D], "labels" [N][D], "count" [N],
-        "overflow" [N]}, rows past count zero with label -1; with stages=True also every intermediate."""
-        st = {} if stages else None
-        out = self._detect(x, image_sizes, st)[0]
-        if stages:
-            out.update(st)
-        return out
+        "overflow" [N]}, rows past count zero with label -1, plus what each branch adds (tensors of the model's, valid
+        until the next forward); with stages=True also every intermediate."""
+        return self._run(x, image_sizes, {} if stages else None)
 
     def prepare_images(self, shapes, dtype=torch.float32, min_size: int = 800, max_size: int = 1333, mean=IMAGENET_MEAN,
                        std=IMAGENET_STD, size_divisible: int = 32) -> None:
@@ -671,7 +750,7 @@ class FasterRCNN(Net):
         sizes = [transform_size(h, w, params["min_size"], params["max_size"]) for h, w in orig]
         Hb, Wb = batch_hw(sizes, params["size_divisible"])
         N, dev, f32 = len(orig), self.device, torch.float32
-        self._prepare_for_predict(N, Hb, Wb)
+        self._prepare(N, Hb, Wb, for_predict=True)
         new, old = torch.tensor(orig, dtype=f32), torch.tensor(sizes, dtype=f32)
         ratio = (new / old)[:, [1, 0, 1, 0]].reshape(N, 1, 4)   # (a torch fp32 division of the two size tensors)
         with torch.cuda.device(dev):
@@ -679,16 +758,10 @@ class FasterRCNN(Net):
                       batch=torch.empty((N, 3, Hb, Wb), dtype=f32, device=dev), image_hw=old.to(dev),
                       orig_hw=new.to(dev), ratio=ratio.contiguous().to(dev),
                       boxes=torch.empty((N, self.detections, 4), dtype=f32, device=dev))
-            self._prepare_outputs(tf, max(h for h, _ in orig), max(w for _, w in orig))
+            for b in self.branches:
+                b.predict_outputs(tf, max(h for h, _ in orig), max(w for _, w in orig))
         torch.cuda.current_stream().synchronize()
         self._tf = tf
-
-    def _prepare_for_predict(self, N: int, Hb: int, Wb: int) -> None:
-        """prepare(), as predict needs it."""
-        self.prepare(N, Hb, Wb)
-
-    def _prepare_outputs(self, tf, Hmax: int, Wmax: int) -> None:
-        """What a subclass's predict writes besides the boxes."""
 
     def _ready(self, images):
         """predict's opening: the list checked, prepare_images re-run when its shapes or dtype are new (with the
@@ -712,26 +785,66 @@ class FasterRCNN(Net):
     def predict(self, images):
         """torchvision's detector call: images, a list of [3][h][w] tensors of different sizes (all float32 in [0, 1] or
         all uint8), through image_transform -> the detector -> the mapping back.  Returns forward's dict with "boxes"
-        [N][D][4] in each image's own pixels (a tensor of the model's, valid until the next predict) plus
-        "original_sizes", the host list of (h, w).  A list of new shapes or dtype re-runs prepare_images."""
+        [N][D][4] in each image's own pixels (a tensor of the model's, valid until the next predict), what each branch
+        adds, mapped back likewise, plus "original_sizes", the host list of (h, w).  A list of new shapes or dtype re-runs
+        prepare_images."""
         images, tf = self._ready(images)
-        out = self._detect(self._transform(images, tf), tf["image_hw"], None)[0]
-        with torch.cuda.device(self.device):
-            out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
-        out["original_sizes"] = list(tf["orig"])
-        return out
+        return self._run(self._transform(images, tf), tf["image_hw"], None, tf)
 
     @staticmethod
     def to_lists(out):
-        """torchvision's list of {"boxes", "scores", "labels"} per image.  Synchronises (it reads count)."""
-        counts = out["count"].tolist()
-        return [{"boxes": out["boxes"][n, :c].clone(), "scores": out["scores"][n, :c].clone(),
-                 "labels": out["labels"][n, :c].clone()} for n, c in enumerate(counts)]
+        """torchvision's list of dicts per image: "boxes", "scores", "labels" and whichever of the branches' outputs `out`
+        holds, "masks" / "masks_binary" [c][1][H][W], "keypoints" [c][K][3], "keypoints_scores" [c][K].  Synchronises (it
+        reads count)."""
+        keys = [k for k in LIST_KEYS if k in out]
+        return [{k: (out[k][n, :c].unsqueeze(1) if k in MASK_KEYS else out[k][n, :c]).clone() for k in keys}
+                for n, c in enumerate(out["count"].tolist())]
 
     @staticmethod
     def to_image_lists(out):
-        """to_lists of a predict's result: the boxes are already in each image's own pixels."""
-        return FasterRCNN.to_lists(out)
+        """to_lists of a predict's result: boxes and keypoints are already in each image's own pixels, each image's
+        masks are cropped to its own [h][w]."""
+        res = FasterRCNN.to_lists(out)
+        for key in MASK_KEYS:
+            if key in out:
+                for d, (h, w) in zip(res, out["original_sizes"]):
+                    d[key] = d[key][:, :, :h, :w].contiguous()
+        return res
+
+
+def _split_state_dict(sd, prefixes):
+    """(the keys that start with none of `prefixes`, as they are; those that do, below `roi_heads.`)."""
+    rest, part = {}, {}
+    for k, v in sd.items():
+        if k.startswith(prefixes):
+            part[k[len("roi_heads."):]] = v
+        else:
+            rest[k] = v
+    return rest, part
+
+
+class _RoIBranch:
+    """What runs on a detector's detections beside the box head.  A branch owns its head, its P, its RoIAlign output and
+    its outputs; FasterRCNN calls check, prepare, run, finish and predict_outputs (see the module docstring) and knows
+    nothing else about it."""
+
+    def __init__(self, head, P: int):
+        self.head, self.P = head, int(P)
+
+    def check(self, H: int, W: int) -> None:
+        """Raises for a batch size the branch cannot take, before anything is allocated."""
+
+    def _prepare_head(self, R: int) -> None:
+        self.head.prepare(R, self.P)
+        self.pooled = torch.empty((R, self.P + 2, self.P + 2, self.head.in_channels), dtype=torch.float32,
+                                  device=self.head.device)
+
+    def _head_on(self, feats, det_rois, size):
+        """RoIAlign on the detections and the head: (the head's raw GEMM output, its leading dimension)."""
+        from . import multiscale_roi_align
+        pooled = multiscale_roi_align(feats, det_rois.view(-1, 5), size, self.P, 2, in_padded=True, out_padded=True,
+                                      out=self.pooled)
+        return self.head(pooled, raw=True)
 
 
 MASK_PREFIXES = ("roi_heads.mask_head.", "roi_heads.mask_predictor.")
@@ -741,19 +854,72 @@ MASK_OUTPUTS = ("prob", "binary", "both")
 def split_mask_state_dict(sd):
     """(the Faster R-CNN keys as they are, the mask branch's keys below `roi_heads.`): BoxHead's validator rejects keys
     it does not know, so the mask branch leaves before it sees the rest."""
-    rest, mask = {}, {}
-    for k, v in sd.items():
-        if k.startswith(MASK_PREFIXES):
-            mask[k[len("roi_heads."):]] = v
+    return _split_state_dict(sd, MASK_PREFIXES)
+
+
+class MaskBranch(_RoIBranch):
+    """multiscale_roi_align (padded, P) -> MaskHead (raw logits) -> paste_masks in the gemm_rows layout: adds "masks"
+    float32 and / or "masks_binary" uint8 (`masks`: "prob", "binary" or "both"), planes past count zero.  forward's are
+    [N][D][H][W] planes of the batch; predict's are pasted once, at original size, with the rescaled boxes into
+    [N][D][Hmax][Wmax], zero beyond each image's own size.  stages: mask_rois, mask_pooled and mask_logits (the raw
+    [N*D*P*P*4][ld] GEMM output)."""
+
+    def __init__(self, head, P: int, masks: str, threshold: float):
+        super().__init__(head, P)
+        self.masks, self.threshold = masks, threshold
+
+    def prepare(self, N: int, D: int, H: int, W: int, for_predict: bool) -> None:
+        self._prepare_head(N * D)
+        self._labels32 = torch.empty((N, D), dtype=torch.int32, device=self.head.device)
+        self._masks = self._masks_bin = None
+        if not for_predict:
+            self._planes(N, D, H, W)
+
+    def _planes(self, N: int, D: int, H: int, W: int) -> None:
+        """forward's mask planes [N][D][H][W] (0.8 GB of fp32 at N = 2, D = 100, 800 x 1216), unless they are there:
+        predict pastes into planes of its own, so after prepare_images the first forward allocates them."""
+        dev = self.head.device
+        if self.masks != "binary" and self._masks is None:
+            self._masks = torch.empty((N, D, H, W), dtype=torch.float32, device=dev)
+        if self.masks != "prob" and self._masks_bin is None:
+            self._masks_bin = torch.empty((N, D, H, W), dtype=torch.uint8, device=dev)
+
+    def predict_outputs(self, tf, Hmax: int, Wmax: int) -> None:
+        shape, dev = (*tf["boxes"].shape[:2], Hmax, Wmax), self.head.device
+        tf["mask_hw"] = (Hmax, Wmax)
+        tf["masks"] = torch.empty(shape, dtype=torch.float32, device=dev) if self.masks != "binary" else None
+        tf["masks_bin"] = torch.empty(shape, dtype=torch.uint8, device=dev) if self.masks != "prob" else None
+
+    def run(self, out, feats, det_rois, size, st) -> None:
+        self._logits = self._head_on(feats, det_rois, size)[0]
+        if st is not None:
+            st.update(mask_rois=det_rois, mask_pooled=self.pooled, mask_logits=self._logits)
+
+    def finish(self, out, image_hw, size, tf) -> None:
+        from . import paste_masks
+        if tf is None:
+            self._planes(*out["labels"].shape, *size)
+            masks, masks_bin = self._masks, self._masks_bin
         else:
-            rest[k] = v
-    return rest, mask
+            image_hw, size, masks, masks_bin = tf["orig_hw"], tf["mask_hw"], tf["masks"], tf["masks_bin"]
+        self._labels32.copy_(out["labels"])
+        prob, binary = paste_masks(self._logits, self._labels32, out["boxes"], image_hw, *size, M=2 * self.P,
+                                   classes=self.head.classes, layout="gemm_rows", out=masks, binary=masks_bin,
+                                   want_out=False, threshold=self.threshold)
+        if prob is not None:
+            out["masks"] = prob
+        if binary is not None:
+            out["masks_binary"] = binary
 
 
 class MaskRCNN(FasterRCNN):
     """torchvision's maskrcnn_resnet50_fpn at test time: FasterRCNN, then on its detections multiscale_roi_align
     (padded, P = mask_P) -> MaskHead (raw logits) -> paste_masks in the gemm_rows layout.  forward's masks are image-size
     planes [N][D][H][W] of the normalised batch; predict's are pasted once, at original size, into [N][D][Hmax][Wmax]."""
+    # the mask branch's buffers under the names they had on the model: read-only, the branch owns them
+    _mask_pooled = property(lambda self: self.branches[0].pooled)
+    _masks = property(lambda self: self.branches[0]._masks)
+    _masks_bin = property(lambda self: self.branches[0]._masks_bin)
 
     @classmethod
     def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, mask_P: int = 14,
@@ -777,121 +943,8 @@ class MaskRCNN(FasterRCNN):
             raise WinoError(f"state dict: the mask head has {mask_classes} classes, the box head {m.box_head.classes}")
         m.mask_head = MaskHead.from_state_dict(mask_sd, out_channels, m.device)
         m.mask_P, m.masks, m.mask_threshold = mask_P, masks, mask_threshold
+        m.branches = [MaskBranch(m.mask_head, mask_P, masks, mask_threshold)]
         return m
-
-    def prepare(self, N: int, H: int, W: int, planes: bool = True) -> None:
-        """FasterRCNN.prepare, then the mask branch's tensors: the mask RoIAlign output [N*D][P+2][P+2][C], the detection
-        rois [N][D][5], int32 labels [N][D] and the masks [N][D][H][W] (planes=False leaves the masks to the first
-        forward)."""
-        super().prepare(N, H, W)
-        self._shape = None   # (until the rest is in place)
-        N, H, W, D, P, dev = int(N), int(H), int(W), self.detections, self.mask_P, self.device
-        with torch.cuda.device(dev):
-            self.mask_head.prepare(N * D, P)
-            self._mask_pooled = torch.empty((N * D, P + 2, P + 2, self.mask_head.in_channels), dtype=torch.float32, device=dev)
-            self._det_rois = torch.empty((N, D, 5), dtype=torch.float32, device=dev)
-            self._labels32 = torch.empty((N, D), dtype=torch.int32, device=dev)
-            self._masks = self._masks_bin = None
-            if planes:
-                self._forward_planes(N, H, W)
-        self._shape = (N, H, W)
-
-    def _forward_planes(self, N: int, H: int, W: int) -> None:
-        """forward's mask planes [N][D][H][W], unless they are there."""
-        D, dev = self.detections, self.device
-        with torch.cuda.device(dev):
-            if self.masks != "binary" and self._masks is None:
-                self._masks = torch.empty((N, D, H, W), dtype=torch.float32, device=dev)
-            if self.masks != "prob" and self._masks_bin is None:
-                self._masks_bin = torch.empty((N, D, H, W), dtype=torch.uint8, device=dev)
-
-    def _prepare_for_predict(self, N: int, Hb: int, Wb: int) -> None:
-        """prepare() without forward's batch-size mask planes (0.8 GB of fp32 at N = 2, D = 100, 800 x 1216): predict
-        pastes into planes of its own, at original size.  A forward on the prepared batch allocates them when it runs."""
-        self.prepare(N, Hb, Wb, planes=False)
-
-    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
-        """FasterRCNN.forward's dict plus "masks" [N][D][H][W] float32 and / or "masks_binary" [N][D][H][W] uint8 (planes
-        past count are zero): tensors of the model's, valid until the next forward.  stages=True adds mask_rois,
-        mask_pooled and mask_logits (the raw [N*D*P*P*4][ld] GEMM output)."""
-        st = {} if stages else None
-        self._begin(x)   # (prepare before _det_rois is named)
-        out, feats, _, hw = self._detect(x, image_sizes, st, rois_out=self._det_rois)
-        N, H, W = self._shape
-        logits, pooled = self._mask_logits(feats)
-        self._forward_planes(N, H, W)
-        self._paste(out, logits, out["boxes"], hw, H, W, self._masks, self._masks_bin)
-        if stages:
-            st.update(mask_rois=self._det_rois, mask_pooled=pooled, mask_logits=logits)
-            out.update(st)
-        return out
-
-    def _mask_logits(self, feats):
-        """The mask branch up to the logits, on the detections _detect left in _det_rois: (the raw logits GEMM output, the
-        mask RoIAlign's output)."""
-        from . import multiscale_roi_align
-        N, H, W = self._shape
-        D, P = self.detections, self.mask_P
-        with torch.cuda.device(self.device):
-            pooled = multiscale_roi_align(feats, self._det_rois.view(N * D, 5), (H, W), P, 2, in_padded=True,
-                                          out_padded=True, out=self._mask_pooled)
-            logits, _ = self.mask_head(pooled, raw=True)
-        return logits, pooled
-
-    def _paste(self, out, logits, boxes, hw, H, W, masks, masks_bin) -> None:
-        """The paste: the detections' masks into `masks` / `masks_bin` [N][D][H][W] at `boxes`, zero beyond `hw`; adds
-        "masks" / "masks_binary" to out."""
-        from . import paste_masks
-        with torch.cuda.device(self.device):
-            self._labels32.copy_(out["labels"])
-            prob, binary = paste_masks(logits, self._labels32, boxes, hw, H, W, M=2 * self.mask_P,
-                                       classes=self.mask_head.classes, layout="gemm_rows", out=masks,
-                                       binary=masks_bin, want_out=False, threshold=self.mask_threshold)
-        if prob is not None:
-            out["masks"] = prob
-        if binary is not None:
-            out["masks_binary"] = binary
-
-    def _prepare_outputs(self, tf, Hmax: int, Wmax: int) -> None:
-        N, D, dev = tf["shape"][0], self.detections, self.device
-        tf["mask_hw"] = (Hmax, Wmax)
-        tf["masks"] = torch.empty((N, D, Hmax, Wmax), dtype=torch.float32, device=dev) if self.masks != "binary" else None
-        tf["masks_bin"] = torch.empty((N, D, Hmax, Wmax), dtype=torch.uint8, device=dev) if self.masks != "prob" else None
-
-    def predict(self, images):
-        """FasterRCNN.predict's dict plus "masks" [N][D][Hmax][Wmax] float32 and / or "masks_binary" uint8, Hmax x Wmax the
-        largest original height and width: pasted once, at original size, with the rescaled boxes, zero beyond each
-        image's own size and in the planes past count.  The mask RoIAlign reads the un-rescaled detections."""
-        images, tf = self._ready(images)
-        out, feats, _, _ = self._detect(self._transform(images, tf), tf["image_hw"], None, rois_out=self._det_rois)
-        logits, _ = self._mask_logits(feats)
-        with torch.cuda.device(self.device):
-            out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
-        self._paste(out, logits, out["boxes"], tf["orig_hw"], *tf["mask_hw"], tf["masks"], tf["masks_bin"])
-        out["original_sizes"] = list(tf["orig"])
-        return out
-
-    @staticmethod
-    def to_lists(out):
-        """torchvision's list of {"boxes", "scores", "labels", "masks" [c][1][H][W]} per image ("masks_binary" likewise
-        when the model returns it).  Synchronises (it reads count)."""
-        counts = out["count"].tolist()
-        res = FasterRCNN.to_lists(out)
-        for n, c in enumerate(counts):
-            for key in ("masks", "masks_binary"):
-                if key in out:
-                    res[n][key] = out[key][n, :c].unsqueeze(1).clone()
-        return res
-
-    @staticmethod
-    def to_image_lists(out):
-        """to_lists of a predict's result, each image's masks cropped to its own [h][w]: torchvision's list of dicts."""
-        res = MaskRCNN.to_lists(out)
-        for d, (h, w) in zip(res, out["original_sizes"]):
-            for key in ("masks", "masks_binary"):
-                if key in d:
-                    d[key] = d[key][:, :, :h, :w].contiguous()
-        return res
 
 
 # ---- Keypoint R-CNN ------------------------------------------------------------------------------------------------------
@@ -952,7 +1005,7 @@ def validate_keypoint_head_state_dict(sd, in_channels: int = 256) -> int:
     return K
 
 
-class KeypointHead(Net):
+class KeypointHead(_ConvTower):
     """KeypointRCNNHeads + KeypointRCNNPredictor on the Winograd 3x3 and the 1x1 GEMM kernels, inference only: eight
     conv3x3_bn_relu launches at N = R, then the transposed convolution's partial products as one GEMM."""
 
@@ -966,8 +1019,7 @@ class KeypointHead(Net):
         return cls._load(sd, None, device, in_channels, _keypoint_widths(sd), K)
 
     def _pack(self, sd, eps):
-        self.convs = [(filter_transform_f2(self._t(sd[f"keypoint_head.{2 * i}.weight"])),
-                       self._t(sd[f"keypoint_head.{2 * i}.bias"])) for i in range(KEYPOINT_CONVS)]
+        self._pack_tower(sd, [f"keypoint_head.{2 * i}" for i in range(KEYPOINT_CONVS)])
         wd, bd = pack_kps_deconv(sd["keypoint_predictor.kps_score_lowres.weight"],
                                  sd["keypoint_predictor.kps_score_lowres.bias"])
         self.wd, self.bias = self._t(wd), self._t(bd)
@@ -985,18 +1037,11 @@ class KeypointHead(Net):
         if R < 1 or not 1 <= P <= KEYPOINT_MAX_P:
             raise WinoError(f"keypoint head: R={R} boxes of P={P}: need R >= 1 and 1 <= P <= {KEYPOINT_MAX_P}")
         with torch.cuda.device(dev):
-            bufs, self._acts = {}, []
-            for i, w in enumerate(self.widths):   # layer i writes buffer (its width, i mod 2)
-                if (w, i % 2) not in bufs:
-                    bufs[(w, i % 2)] = torch.zeros((R, P + 2, P + 2, w), dtype=f32, device=dev)
-                self._acts.append(bufs[(w, i % 2)])
+            self._alloc_tower(R, P)
             self._rows = torch.empty((R * P * P, self.ld), dtype=f32, device=dev)
             self._maps = torch.empty((R, self.K, 4 * P, 4 * P), dtype=f32, device=dev)
-            c = self.in_channels
-            for w in self.widths:
-                conv3x3_prepare(R, c, w, P, P)
-                c = w
-            conv1x1_prepare(R * P * P, c, self.ld)
+            self._reserve_tower(R, P)
+            conv1x1_prepare(R * P * P, self.widths[-1], self.ld)
         self._shape = (R, P)
 
     def forward(self, pooled_padded: torch.Tensor, raw: bool = False):
@@ -1006,21 +1051,11 @@ class KeypointHead(Net):
         (ky, kx, k), ld): heatmaps_to_keypoints' "deconv_rows" layout, to be passed with the head's `bias`.  raw=False
         composes the logits in torch (fold, bias, x2 bilinear upsample): plumbing for callers who want them, not on
         KeypointRCNN's path."""
-        x, C = pooled_padded, self.in_channels
-        if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or x.shape[1] != x.shape[2]:
-            raise WinoError(f"pooled_padded must be [R][P+2][P+2][{C}]")
-        if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
-            raise WinoError(f"pooled_padded must be contiguous float32 on {self.device}")
-        R, P = int(x.shape[0]), int(x.shape[1]) - 2
-        if (R, P) != self._shape:
-            self.prepare(R, P)
+        R, P = self._begin_tower(pooled_padded)
         K, ld = self.K, self.ld
         with torch.cuda.device(self.device):
-            src = x
-            for (U, bias), dst, w in zip(self.convs, self._acts, self.widths):
-                conv3x3_bn_relu(src, U, bias, self._ones[:w], relu=True, out=dst)
-                src = dst
-            conv1x1_bn_ex(src, self.wd, self._zeros, self._ones[:ld], A_PADDED, out=self._rows)
+            top = self._run_tower(pooled_padded)
+            conv1x1_bn_ex(top, self.wd, self._zeros, self._ones[:ld], A_PADDED, out=self._rows)
             if raw:
                 return self._rows, ld
             F = torch.nn.functional
@@ -1032,19 +1067,50 @@ class KeypointHead(Net):
 
 def split_keypoint_state_dict(sd):
     """(the Faster R-CNN keys as they are, the keypoint branch's keys below `roi_heads.`), like split_mask_state_dict."""
-    rest, kp = {}, {}
-    for k, v in sd.items():
-        if k.startswith(KEYPOINT_PREFIXES):
-            kp[k[len("roi_heads."):]] = v
-        else:
-            rest[k] = v
-    return rest, kp
+    return _split_state_dict(sd, KEYPOINT_PREFIXES)
+
+
+class KeypointBranch(_RoIBranch):
+    """multiscale_roi_align (padded, P) -> KeypointHead (raw rows) -> heatmaps_to_keypoints in the deconv_rows layout: adds
+    "keypoints" [N][D][K][3] = (x, y, 1) and "keypoints_scores" [N][D][K], rows past count zero.  They are computed on the
+    un-rescaled detections; predict multiplies the keypoints by (rw, rh, 1) (torchvision's resize_keypoints).  stages:
+    keypoint_rois, keypoint_pooled and keypoint_rows (the raw [N*D*P*P][ld] GEMM output)."""
+
+    def check(self, H: int, W: int) -> None:
+        if max(int(H), int(W)) > KEYPOINT_MAX_SIDE:
+            raise WinoError(f"Keypoint R-CNN: a batch of {H} x {W} exceeds {KEYPOINT_MAX_SIDE} pixels a side")
+
+    def prepare(self, N: int, D: int, H: int, W: int, for_predict: bool) -> None:
+        K, dev = self.head.K, self.head.device
+        self._prepare_head(N * D)
+        self._keypoints = torch.empty((N, D, K, 3), dtype=torch.float32, device=dev)
+        self._kp_scores = torch.empty((N, D, K), dtype=torch.float32, device=dev)
+
+    def predict_outputs(self, tf, Hmax: int, Wmax: int) -> None:
+        (N, D), K, dev = tf["boxes"].shape[:2], self.head.K, self.head.device
+        ones = torch.ones((N, 1, 1), dtype=torch.float32, device=dev)
+        tf["kp_ratio"] = torch.cat([tf["ratio"][:, :, :2], ones], dim=2).reshape(N, 1, 1, 3).contiguous()   # (rw, rh, 1)
+        tf["keypoints"] = torch.empty((N, D, K, 3), dtype=torch.float32, device=dev)
+
+    def run(self, out, feats, det_rois, size, st) -> None:
+        from . import heatmaps_to_keypoints
+        rows, ld = self._head_on(feats, det_rois, size)
+        heatmaps_to_keypoints(rows, det_rois, K=self.head.K, M=4 * self.P, layout="deconv_rows", bias=self.head.bias, ld=ld,
+                              max_side=max(size), out=self._keypoints, scores_out=self._kp_scores)
+        out["keypoints"], out["keypoints_scores"] = self._keypoints, self._kp_scores
+        if st is not None:
+            st.update(keypoint_rois=det_rois, keypoint_pooled=self.pooled, keypoint_rows=rows)
+
+    def finish(self, out, image_hw, size, tf) -> None:
+        if tf is not None:
+            out["keypoints"] = torch.mul(out["keypoints"], tf["kp_ratio"], out=tf["keypoints"])
 
 
 class KeypointRCNN(FasterRCNN):
     """torchvision's keypointrcnn_resnet50_fpn at test time: FasterRCNN, then on its detections multiscale_roi_align
     (padded, P = keypoint_P) -> KeypointHead (raw rows) -> heatmaps_to_keypoints in the deconv_rows layout.  Adds
     "keypoints" [N][D][K][3] = (x, y, 1) and "keypoints_scores" [N][D][K], rows past count zero."""
+    _kp_pooled = property(lambda self: self.branches[0].pooled)   # (the name it had on the model; the branch owns it)
 
     @classmethod
     def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, keypoint_P: int = 14,
@@ -1061,84 +1127,8 @@ class KeypointRCNN(FasterRCNN):
                                     **faster_rcnn)
         m.keypoint_head = KeypointHead.from_state_dict(kp_sd, out_channels, m.device)
         m.keypoint_P = keypoint_P
+        m.branches = [KeypointBranch(m.keypoint_head, keypoint_P)]
         return m
-
-    def prepare(self, N: int, H: int, W: int) -> None:
-        """FasterRCNN.prepare, then the keypoint branch's tensors: the keypoint RoIAlign output [N*D][P+2][P+2][C], the
-        detection rois [N][D][5] and the outputs [N][D][K][3] and [N][D][K]."""
-        if max(int(H), int(W)) > KEYPOINT_MAX_SIDE:
-            raise WinoError(f"Keypoint R-CNN: a batch of {H} x {W} exceeds {KEYPOINT_MAX_SIDE} pixels a side")
-        super().prepare(N, H, W)
-        self._shape = None   # (until the rest is in place)
-        N, D, P, K, dev, f32 = int(N), self.detections, self.keypoint_P, self.keypoint_head.K, self.device, torch.float32
-        with torch.cuda.device(dev):
-            self.keypoint_head.prepare(N * D, P)
-            self._kp_pooled = torch.empty((N * D, P + 2, P + 2, self.keypoint_head.in_channels), dtype=f32, device=dev)
-            self._det_rois = torch.empty((N, D, 5), dtype=f32, device=dev)
-            self._keypoints = torch.empty((N, D, K, 3), dtype=f32, device=dev)
-            self._kp_scores = torch.empty((N, D, K), dtype=f32, device=dev)
-        self._shape = (int(N), int(H), int(W))
-
-    def _keypoint_branch(self, out, feats, st=None) -> None:
-        """The keypoint branch on the detections _detect left in _det_rois; adds "keypoints" and "keypoints_scores"."""
-        from . import heatmaps_to_keypoints, multiscale_roi_align
-        N, H, W = self._shape
-        D, P, head = self.detections, self.keypoint_P, self.keypoint_head
-        with torch.cuda.device(self.device):
-            pooled = multiscale_roi_align(feats, self._det_rois.view(N * D, 5), (H, W), P, 2, in_padded=True,
-                                          out_padded=True, out=self._kp_pooled)
-            rows, ld = head(pooled, raw=True)
-            heatmaps_to_keypoints(rows, self._det_rois, K=head.K, M=4 * P, layout="deconv_rows", bias=head.bias, ld=ld,
-                                  max_side=max(H, W), out=self._keypoints, scores_out=self._kp_scores)
-        out["keypoints"], out["keypoints_scores"] = self._keypoints, self._kp_scores
-        if st is not None:
-            st.update(keypoint_rois=self._det_rois, keypoint_pooled=pooled, keypoint_rows=rows)
-
-    def forward(self, x: torch.Tensor, image_sizes=None, stages: bool = False):
-        """FasterRCNN.forward's dict plus "keypoints" [N][D][K][3] and "keypoints_scores" [N][D][K] (rows past count are
-        zero): tensors of the model's, valid until the next forward.  stages=True adds keypoint_rois, keypoint_pooled and
-        keypoint_rows (the raw [N*D*P*P][ld] GEMM output)."""
-        st = {} if stages else None
-        self._begin(x)   # (prepare before _det_rois is named)
-        out, feats, _, _ = self._detect(x, image_sizes, st, rois_out=self._det_rois)
-        self._keypoint_branch(out, feats, st)
-        if stages:
-            out.update(st)
-        return out
-
-    def _prepare_outputs(self, tf, Hmax: int, Wmax: int) -> None:
-        N, D, K, dev = tf["shape"][0], self.detections, self.keypoint_head.K, self.device
-        ones = torch.ones((N, 1, 1), dtype=torch.float32, device=dev)
-        tf["kp_ratio"] = torch.cat([tf["ratio"][:, :, :2], ones], dim=2).reshape(N, 1, 1, 3).contiguous()   # (rw, rh, 1)
-        tf["keypoints"] = torch.empty((N, D, K, 3), dtype=torch.float32, device=dev)
-
-    def predict(self, images):
-        """FasterRCNN.predict's dict plus "keypoints" in each image's own pixels and "keypoints_scores": the keypoints are
-        computed on the un-rescaled detections, then multiplied by (rw, rh, 1) (torchvision's resize_keypoints)."""
-        images, tf = self._ready(images)
-        out, feats, _, _ = self._detect(self._transform(images, tf), tf["image_hw"], None, rois_out=self._det_rois)
-        self._keypoint_branch(out, feats)
-        with torch.cuda.device(self.device):
-            out["boxes"] = torch.mul(out["boxes"], tf["ratio"], out=tf["boxes"])
-            out["keypoints"] = torch.mul(out["keypoints"], tf["kp_ratio"], out=tf["keypoints"])
-        out["original_sizes"] = list(tf["orig"])
-        return out
-
-    @staticmethod
-    def to_lists(out):
-        """torchvision's list of {"boxes", "scores", "labels", "keypoints" [c][K][3], "keypoints_scores" [c][K]} per image.
-        Synchronises (it reads count)."""
-        counts = out["count"].tolist()
-        res = FasterRCNN.to_lists(out)
-        for n, c in enumerate(counts):
-            for key in ("keypoints", "keypoints_scores"):
-                res[n][key] = out[key][n, :c].clone()
-        return res
-
-    @staticmethod
-    def to_image_lists(out):
-        """to_lists of a predict's result: boxes and keypoints are already in each image's own pixels."""
-        return KeypointRCNN.to_lists(out)
 
 
 __all__ = ["BoxHead", "MaskHead", "KeypointHead", "RPN", "FasterRCNN", "MaskRCNN", "KeypointRCNN", "split_mask_state_dict",

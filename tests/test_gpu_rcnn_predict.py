@@ -3,12 +3,14 @@ roi_cases.mask_head_state_dict under roi_heads., for both `select` values: two i
 max_size 96 resize to 64 x 96 and 71 x 64 in a 96 x 96 batch.  The detector's accuracy against fp64 is pinned by the
 existing suites and the transform's by tests/test_gpu_transform.py, so these are exact comparisons: predict against the
 composition from public pieces (image_transform, forward, the fp32 multiply by the ratios restated in numpy, paste_masks),
-bit for bit."""
+bit for bit.  Last, on the mask model and on a keypoint model (keypoint_P = 4, K = 3): a first forward prepares the model and
+the branch's head exactly once each, and a branch head that refuses to prepare leaves the model unprepared."""
 import numpy as np
 import pytest
 import torch
 
 import box_cases as bc
+import keypoint_cases as kc
 import roi_cases as rc
 import transform_cases as tc
 from gpu_support import R, torch_dev  # noqa: F401
@@ -217,3 +219,72 @@ def test_forward_is_what_it_was_before_any_predict(pkg, R, torch_dev):
         assert int(before["count"].min()) > 0
         if cls == "mask":
             assert tuple(after["masks"].shape) == (D["N"], D["detections"], D["H"], D["W"])
+
+
+# ---- prepare, with a branch --------------------------------------------------------------------------------------------
+def branch_model(pkg, R, dev, cls):
+    """(a model that has never been prepared, its branch's head)."""
+    if cls == "mask":
+        m = build(pkg, R, dev, "mask", "torch")
+        return m, m.mask_head
+    full = dict(bc.detector_state_dict(R)[0])
+    full.update({"roi_heads." + k: v for k, v in kc.keypoint_head_state_dict(D["out_channels"], [64] * 8, 3,
+                                                                             seed=D["seed"] + 3).items()})
+    m = pkg.KeypointRCNN.from_state_dict(full, D["arch"], keypoint_P=4, **kwargs(dev))
+    return m, m.keypoint_head
+
+
+def tensors(out):
+    torch.cuda.synchronize()
+    return {k: v.clone() for k, v in out.items() if isinstance(v, torch.Tensor)}
+
+
+def count_calls(obj, tag, calls):
+    """Wraps the bound obj.prepare on the object itself, so that calls through `self` are counted too."""
+    bound = obj.prepare
+
+    def prepare(*args, **kwargs):
+        calls.append(tag)
+        return bound(*args, **kwargs)
+    obj.prepare = prepare
+
+
+@pytest.mark.parametrize("cls", ("mask", "keypoint"))
+def test_a_first_forward_prepares_once(pkg, R, torch_dev, cls):
+    m, head = branch_model(pkg, R, torch_dev[1], cls)
+    x = bc.detector_input().to(torch_dev[1])
+    calls = []
+    count_calls(m, "model", calls)
+    count_calls(head, "head", calls)
+    assert m._shape is None and head._shape is None
+    first = tensors(m(x))
+    assert sorted(calls) == ["head", "model"], calls
+    assert m._shape == (D["N"], D["H"], D["W"])
+    again = tensors(m(x))                         # the same shape: neither prepares again
+    assert sorted(calls) == ["head", "model"], calls
+    assert set(again) == set(first) and int(first["count"].min()) > 0
+    for k in first:
+        assert same_bits(again[k], first[k]), k
+
+
+@pytest.mark.parametrize("cls", ("mask", "keypoint"))
+def test_a_failed_branch_prepare_leaves_the_model_unprepared(pkg, R, torch_dev, cls):
+    """The head's prepare is replaced on the Python object by one that raises before it launches anything."""
+    dev = torch_dev[1]
+    x = bc.detector_input().to(dev)
+    want = tensors(branch_model(pkg, R, dev, cls)[0](x))
+    m, head = branch_model(pkg, R, dev, cls)
+
+    def refuse(*args, **kwargs):
+        raise pkg.WinoError("stub: the head does not prepare")
+    for was_prepared in (False, True):            # on a new model, and on one that has run
+        head.prepare = refuse
+        with pytest.raises(pkg.WinoError, match="stub"):
+            m.prepare(D["N"], D["H"], D["W"])
+        assert m._shape is None
+        del head.prepare
+        got = tensors(m(x))                        # prepares, and is what a fresh model returns
+        assert m._shape == (D["N"], D["H"], D["W"])
+        assert set(got) == set(want)
+        for k in want:
+            assert same_bits(got[k], want[k]), (was_prepared, k)
