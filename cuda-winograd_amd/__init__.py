@@ -1100,6 +1100,98 @@ def select_topk(scores, k, n=None, off=None, score_thresh=None, boxes=None, out_
     return (idx, vals, count) if ob is None else (idx, vals, count, ob)
 
 
+SELECT_MAX_N = (1 << 31) - 1   # the longest segment: an index must fit idx's int32
+
+
+def select_map_workspace_bytes(N: int, h: int, w: int, cols: int, k: int) -> int:
+    """Bytes of select_topk_map's workspace for N maps of h x w pixels with `cols` scores each: select_workspace_bytes
+    for the one part n = h * w * cols, the formula of winograd_mi355x.h.  Host only; raises WinoError outside the
+    entry point's limits, a segment longer than 2^31 - 1 scores among them."""
+    N, h, w, cols, k = int(N), int(h), int(w), int(cols), int(k)
+    if h < 1 or w < 1 or cols < 1:
+        raise WinoError(f"select_topk_map: unsupported shape h={h} w={w} cols={cols} (need h, w, cols >= 1)")
+    n = h * w * cols
+    if n > SELECT_MAX_N:
+        raise WinoError(f"select_topk_map: a segment of h w cols = {h} x {w} x {cols} scores is longer than 2^31 - 1")
+    return select_workspace_bytes(N, n, k)
+
+
+def select_topk_map(scores_map, cols: int, k: int, score_thresh=None, out_idx=None, out_vals=None, out_count=None,
+                    out_offset: int = 0, workspace=None):
+    """select_topk on a padded NHWC map, in place (select.hip).  scores_map [N][h+2][w+2][ld] float32, what a 3x3 layer
+    writes; image i's segment is its h * w * cols scores map[i][1 + y][1 + x][c], c < cols <= ld, and the index of one is
+    (y * w + x) * cols + c: with cols = A * K and channel a * K + k, torchvision's (N, HWA, K) flattening.  The ring and
+    the pad columns have no index and are never read as candidates.  Order, NaN and +-0 rules, score_thresh (>=) and
+    k <= 8192 are select_topk's.  Returns (idx [N][total] int32, vals [N][total], count [N] int32); this call writes
+    [:, out_offset : out_offset + k] of idx and vals (a level's slice of one buffer for all levels; new ones are exactly k
+    wide).  workspace: select_map_workspace_bytes(N, h, w, cols, k) bytes.  No scratch of the library's: capturable into
+    a graph without a prepare."""
+    m = _dev(scores_map, "scores_map")
+    if m.dim() != 4 or int(m.shape[1]) < 3 or int(m.shape[2]) < 3:
+        raise WinoError("scores_map must be [N][h+2][w+2][ld]")
+    N, h, w, ld = int(m.shape[0]), int(m.shape[1]) - 2, int(m.shape[2]) - 2, int(m.shape[3])
+    cols, k, off = int(cols), int(k), int(out_offset)
+    if not 1 <= cols <= ld or off < 0:
+        raise WinoError(f"select_topk_map: cols={cols} of ld={ld}, out_offset={off}")
+    need = select_map_workspace_bytes(N, h, w, cols, k)
+
+    def slot(t, dtype, name):
+        if t is None:
+            if off:
+                raise WinoError(f"out_offset={off} needs {name}")
+            return torch.empty((N, k), dtype=dtype, device=m.device)
+        if (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.dim() != 2
+                or int(t.shape[0]) != N or int(t.shape[1]) < off + k):
+            raise WinoError(f"{name} must be a contiguous {dtype} CUDA(HIP) tensor [{N}][>= {off + k}]")
+        return t
+
+    idx = slot(out_idx, torch.int32, "out_idx")
+    vals = slot(out_vals, torch.float32, "out_vals")
+    count = _int32(out_count, (N,), m.device, "out_count")
+    if int(vals.shape[1]) != int(idx.shape[1]):
+        raise WinoError("select_topk_map: out_idx and out_vals must have the same row length")
+    ws = _workspace(workspace, need, m.device)
+    _on_current_device(m, idx, vals, count, ws)
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    _check(lib().wino_select_topk_map_hw(ptr(m), N, h, w, cols, ld, k, 0 if score_thresh is None else 1,
+                                         0.0 if score_thresh is None else float(score_thresh), ptr(idx), ptr(vals),
+                                         ptr(count), int(idx.shape[1]), off, ptr(ws), ws.numel() * 4, _stream()),
+           "wino_select_topk_map_hw")
+    return idx, vals, count
+
+
+def retina_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=None, out_labels=None, out_offset: int = 0,
+                  clamp: float = BBOX_XFORM_CLIP):
+    """RetinaNet's decode of the selected anchors only, in one HIP launch (retina.hip).  idx [N][total] int32 as
+    select_topk_map writes it with cols = A * K; this call reads rows [:, out_offset : out_offset + k] (k defaults to the
+    rest of the row): anchor = idx // K, label = idx % K.  reg_map [N][h+2][w+2][ld_r] float32, the regression head's
+    padded output with the deltas of anchor a at columns 4a .. 4a + 3; base [A][4]; image_hw [N][2];
+    grid = (h, w, stride_y, stride_x).  The box is box_decode's in grid mode at the same anchor, bit for bit (weights
+    (1, 1, 1, 1), clamp, clipped to the image).  Returns (boxes [N][total][4], labels [N][total] int32), of which the
+    same rows are written; rows with idx < 0 get a zero box and label -1.  No scratch: capturable without a prepare."""
+    ix = idx
+    if not isinstance(ix, torch.Tensor) or not ix.is_cuda or ix.dtype != torch.int32 or not ix.is_contiguous() or ix.dim() != 2:
+        raise WinoError("idx must be a contiguous int32 CUDA(HIP) tensor [N][total]")
+    reg, anc, hw = _dev(reg_map, "reg_map"), _dev(base, "base"), _dev(image_hw, "image_hw")
+    N, total, off = int(ix.shape[0]), int(ix.shape[1]), int(out_offset)
+    gh, gw, sy, sx = (int(v) for v in grid)
+    if reg.dim() != 4 or tuple(reg.shape[:3]) != (N, gh + 2, gw + 2) or tuple(hw.shape) != (N, 2):
+        raise WinoError(f"reg_map must be [{N}][{gh + 2}][{gw + 2}][ld_r] and image_hw [{N}][2]")
+    if anc.dim() != 2 or int(anc.shape[1]) != 4:
+        raise WinoError("base must be [A][4]")
+    k = total - off if k is None else int(k)
+    if off < 0 or k < 0 or off + k > total:
+        raise WinoError(f"retina_decode: rows {off} .. {off + k} of {total}")
+    boxes = _output(out_boxes, (N, total, 4), ix.device, "out_boxes")
+    labels = _int32(out_labels, (N, total), ix.device, "out_labels")
+    _on_current_device(ix, reg, anc, hw, boxes, labels)
+    ptr = lambda t: t.data_ptr() or None
+    _check(lib().wino_retina_decode_hw(ptr(ix), N, k, total, off, ptr(reg), gh, gw, int(reg.shape[3]), int(anc.shape[0]),
+                                       int(K), ptr(anc), sy, sx, ptr(hw), float(clamp), ptr(boxes), ptr(labels), _stream()),
+           "wino_retina_decode_hw")
+    return boxes, labels
+
+
 MASK_LAYOUTS = {"planes": 0, "gemm_rows": 1}   # WINO_MASK_LAYOUT_*
 MASK_MAX_M = 62
 
@@ -1677,3 +1769,4 @@ from .vgg import VGG  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
 from .detection import BoxHead, MaskHead, KeypointHead, RPN, FasterRCNN, MaskRCNN, KeypointRCNN  # noqa: E402
+from .detection import RetinaNetHead, RetinaNet  # noqa: E402

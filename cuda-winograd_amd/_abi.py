@@ -187,6 +187,9 @@ SIGNATURES = {
     # ---- segmented top-k and sort
     "wino_select_topk_hw": (i, [vp, i, c_long, i, POINTER(c_long), ip, ip, i, c_float] + [vp] * 3 + [c_long, vp, c_long]
                             + [vp] * 2 + [sz, vp]),
+    "wino_select_topk_map_hw": (i, [vp] + [i] * 7 + [c_float] + [vp] * 3 + [c_long] * 2 + [vp, sz, vp]),
+    # ---- RetinaNet: decode only the selected anchors
+    "wino_retina_decode_hw": (i, [vp, i, i, c_long, c_long, vp] + [i] * 5 + [vp, i, i, vp, c_float, vp, vp, vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -43,6 +43,7 @@
 //   the other 1024 / W split the block's rows.
 #include <cmath>
 
+#include "box_decode_math.h"   // decode_box and grid_anchor: the decode arithmetic, shared with retina.hip
 #include "wino_common.h"
 
 #pragma clang fp contract(off)   // torch's arithmetic operation by operation: no product folded into a sum
@@ -69,14 +70,11 @@ struct DecodeArgs {
   unsigned total;            // N x rows_per_image x A
   unsigned rpi, A, grid_w;   // grid_w == 0: boxes mode
   int ld, delta_col, score_col;
-  float stride_x, stride_y, wx, wy, ww, wh, clamp;
+  float stride_x, stride_y;
+  DecodeWeights k;
   long long bstride, boff, sstride, soff;
   FastDiv divA, divRpi, divW;
 };
-
-// torch.clamp's two halves: a NaN fails the compare and passes through
-__device__ __forceinline__ float min_nan(float v, float hi) { return v > hi ? hi : v; }
-__device__ __forceinline__ float clip_nan(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
 
 __global__ __launch_bounds__(256) void box_decode_kernel(const DecodeArgs a) {
   const unsigned t = blockIdx.x * 256u + threadIdx.x;
@@ -86,8 +84,7 @@ __global__ __launch_bounds__(256) void box_decode_kernel(const DecodeArgs a) {
   f32x4 anc;
   if (a.grid_w) {
     const unsigned y = fastdiv(j, a.divW), x = j - y * a.grid_w;
-    const float ox = (float)x * a.stride_x, oy = (float)y * a.stride_y;
-    anc = ((const f32x4*)a.anchors)[an] + f32x4{ox, oy, ox, oy};
+    anc = grid_anchor(((const f32x4*)a.anchors)[an], x, y, a.stride_x, a.stride_y);
   } else {
     anc = ((const f32x4*)a.anchors)[(size_t)r];
   }
@@ -95,15 +92,7 @@ __global__ __launch_bounds__(256) void box_decode_kernel(const DecodeArgs a) {
   const float* d = row + a.delta_col + 4 * an;
   const float d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
   const float Himg = a.image_hw[2 * (size_t)n], Wimg = a.image_hw[2 * (size_t)n + 1];
-  const float w = anc.z - anc.x, h = anc.w - anc.y;
-  const float cx = anc.x + 0.5f * w, cy = anc.y + 0.5f * h;
-  const float dx = d0 / a.wx, dy = d1 / a.wy;
-  const float dw = min_nan(d2 / a.ww, a.clamp), dh = min_nan(d3 / a.wh, a.clamp);
-  const float pcx = dx * w + cx, pcy = dy * h + cy;
-  const float pw = expf(dw) * w, ph = expf(dh) * h;
-  const float hw_ = 0.5f * pw, hh_ = 0.5f * ph;
-  const f32x4 box = {clip_nan(pcx - hw_, Wimg), clip_nan(pcy - hh_, Himg), clip_nan(pcx + hw_, Wimg),
-                     clip_nan(pcy + hh_, Himg)};
+  const f32x4 box = decode_box(anc, d0, d1, d2, d3, a.k, Himg, Wimg);
   const size_t in_image = (size_t)j * a.A + an;
   ((f32x4*)a.boxes)[(size_t)((long long)n * a.bstride + a.boff) + in_image] = box;
   if (a.score_col >= 0) a.scores[(size_t)((long long)n * a.sstride + a.soff) + in_image] = row[a.score_col + an];
@@ -353,7 +342,7 @@ extern "C" int wino_box_decode_hw(const float* head, int N, int rows_per_image, 
   a.rpi = (unsigned)rows_per_image, a.A = (unsigned)A, a.grid_w = grid ? (unsigned)grid_w : 0u;
   a.ld = ld, a.delta_col = delta_col, a.score_col = want_scores ? score_col : -1;
   a.stride_x = (float)stride_x, a.stride_y = (float)stride_y;
-  a.wx = wx, a.wy = wy, a.ww = ww, a.wh = wh, a.clamp = clamp;
+  a.k = DecodeWeights{wx, wy, ww, wh, clamp};
   a.bstride = boxes_image_stride, a.boff = boxes_offset, a.sstride = scores_image_stride, a.soff = scores_offset;
   a.divA = make_fastdiv(a.A), a.divRpi = make_fastdiv(a.rpi), a.divW = make_fastdiv(grid ? a.grid_w : 1u);
   hipLaunchKernelGGL(box_decode_kernel, dim3((a.total + 255u) / 256u), dim3(256), 0, (hipStream_t)s, a);

@@ -87,8 +87,14 @@ None in ``forward``); ``predict_outputs(tf, Hmax, Wmax)`` adds the branch's entr
 is set when the last branch has prepared.  ``to_lists`` slices whichever output keys the dict holds.  Both heads' 3x3
 chains are ``_ConvTower``: the filter packing, the ``pooled_padded`` checks, the zero-ring buffers and the launch loop.
 
-Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets, RetinaNet and the BN variants of
-the v2 heads.
+``RetinaNet.from_state_dict(sd, arch)`` (``backbone.*`` with ``fpn.extra_blocks.p6|p7``, ``head.*``) is the one-stage
+detector on the same plumbing (``_Detector``: ``prepare`` / ``forward`` / ``predict`` / ``prepare_images`` /
+``to_lists`` are shared with ``FasterRCNN``, a detector gives ``_prepare`` and ``_detect``): ResNetFPN(returned_layers =
+(2, 3, 4), "p6p7") -> ``RetinaNetHead`` -> per level ``select_topk_map`` on the class logit map in place and
+``retina_decode`` of the selected anchors -> one ``select_topk`` by score -> ``batched_nms`` by label; see its docstring
+for the two named deviations.
+
+Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets and the v2 heads.
 
 The key names above are written from memory of torchvision's source and have not been checked against an installed
 torchvision; the tests build their own state dicts under these names.
@@ -609,100 +615,22 @@ MASK_KEYS = ("masks", "masks_binary")
 LIST_KEYS = ("boxes", "scores", "labels") + MASK_KEYS + ("keypoints", "keypoints_scores")   # what to_lists slices per image
 
 
-class FasterRCNN(Net):
-    """torchvision's fasterrcnn_*_fpn at test time on the library's kernels: ResNetFPN(padded) -> RPN ->
-    multiscale_roi_align -> BoxHead -> postprocess_detections.  forward takes the already normalised batch; predict
-    takes a list of images of different sizes (GeneralizedRCNNTransform in one launch) and returns boxes in each image's
-    own pixels."""
+class _Detector(Net):
+    """What the detectors share: prepare, the one forward / predict path, prepare_images and the list views.  A subclass
+    gives `_prepare(N, H, W, for_predict)` (which sets `_shape = (N, H, W)` last) and `_detect(x, image_sizes, st)` ->
+    (the result dict, the pyramid, image_hw), and may fill `branches` (and then `_det_rois`)."""
 
-    def __init__(self, backbone, rpn, box_head, detections, score_thresh, nms_thresh, max_candidates, device,
-                 select="torch"):
+    def __init__(self, device, detections: int):
         super().__init__(device)
-        self.select = _check_select(select)
-        self.backbone, self.rpn, self.box_head = backbone, rpn, box_head
-        self.detections, self.score_thresh, self.nms_thresh = int(detections), float(score_thresh), float(nms_thresh)
-        self.max_candidates = max_candidates
-        self.branches = []   # the RoI branches that run on the detections, in order: none for Faster R-CNN
+        self.detections = int(detections)
+        self.branches = []   # the RoI branches that run on the detections, in order: none for Faster R-CNN and RetinaNet
+        self._det_rois = None
         self._tf, self._tf_params = None, None   # prepare_images' state, and the parameters of its last call
-
-    @classmethod
-    def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, P: int = 7, eps: float = 1e-5,
-                        rpn_pre_nms_top_n: int = 1000, rpn_post_nms_top_n: int = 1000, rpn_nms_thresh: float = 0.7,
-                        rpn_score_thresh: float = 0.0, box_score_thresh: float = SCORE_THRESH_STRICT,
-                        box_nms_thresh: float = 0.5, box_detections_per_img: int = 100, max_candidates=None, sizes=ANCHOR_SIZES,
-                        ratios=ANCHOR_RATIOS, device=None, select: str = "torch") -> "FasterRCNN":
-        """sd under torchvision's key names: backbone.body.*, backbone.fpn.*, rpn.*, roi_heads.box_head.*,
-        roi_heads.box_predictor.*; each part is validated with check_state_dict.  select: "torch" or "kernel", for the
-        RPN's filter_proposals and postprocess_detections alike (see the module docstring)."""
-        from .fpn import ResNetFPN
-        _check_select(select)
-        parts = {"backbone.": {}, "rpn.": {}, "roi_heads.": {}}
-        for k, v in sd.items():
-            for prefix, part in parts.items():
-                if k.startswith(prefix):
-                    part[k[len(prefix):]] = v
-                    break
-            else:
-                raise WinoError(f"state dict: unexpected key {k!r} for Faster R-CNN")
-        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device)
-        rpn = RPN.from_state_dict(parts["rpn."], out_channels, sizes, ratios, rpn_pre_nms_top_n, rpn_post_nms_top_n,
-                                  rpn_nms_thresh, rpn_score_thresh, 1e-3, backbone.device, select=select)
-        box_head = BoxHead.from_state_dict(parts["roi_heads."], out_channels, P, backbone.device)
-        if num_classes is not None and int(num_classes) != box_head.classes:
-            raise WinoError(f"state dict has {box_head.classes} classes, num_classes={num_classes}")
-        return cls(backbone, rpn, box_head, box_detections_per_img, box_score_thresh, box_nms_thresh, max_candidates,
-                   backbone.device, select=select)
 
     def prepare(self, N: int, H: int, W: int) -> None:
         """Allocate everything for [N][3][H][W] inputs and reserve every launch's stream scratch on the current stream.
         After it a forward performs no host read of device data, so it can be captured into one graph."""
         self._prepare(N, H, W, for_predict=False)
-
-    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
-        """prepare(); for_predict: on behalf of prepare_images, so a branch may leave what only forward needs to the
-        first forward.  The model counts as prepared (_shape) once the last branch is."""
-        N, H, W, D, dev = int(N), int(H), int(W), self.detections, self.device
-        if self.select == "kernel" and self.max_candidates is not None and int(self.max_candidates) > SELECT_MAX_ROWS:
-            raise WinoError(f"select=\"kernel\" keeps at most {SELECT_MAX_ROWS} candidates, "
-                            f"max_candidates={self.max_candidates}")
-        for b in self.branches:
-            b.check(H, W)
-        self._shape = None   # (a prepare that raises from here on leaves the model unprepared, whatever it was before)
-        with torch.cuda.device(dev):
-            self.backbone.prepare(N, H, W)
-            p = self.backbone._p
-            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in p]
-            level_hw.append(((level_hw[-1][0] + 1) // 2, (level_hw[-1][1] + 1) // 2))
-            self.rpn.prepare(N, level_hw, (H, W))
-            R, bh = N * self.rpn.post, self.box_head
-            bh.prepare(R)
-            self._pooled = torch.empty((R, bh.P, bh.P, bh.in_channels), dtype=torch.float32, device=dev)
-            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=torch.float32, device=dev)
-            # the detections as RoIAlign rows [N][D][5]: what every branch reads, so only written when there is one
-            self._det_rois = torch.empty((N, D, 5), dtype=torch.float32, device=dev) if self.branches else None
-            for b in self.branches:
-                b.prepare(N, D, H, W, for_predict)
-        self._shape = (N, H, W)
-
-    def _detect(self, x, image_sizes, st):
-        """Faster R-CNN's stages; returns (the result dict, the pyramid, image_hw)."""
-        from . import multiscale_roi_align
-        self._begin(x)
-        N, H, W = self._shape
-        hw = self._full_hw if image_sizes is None else image_sizes
-        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
-            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
-        with torch.cuda.device(self.device):
-            feats = self.backbone(x, padded=True)
-            rois, _, _ = self.rpn(feats, hw, (H, W), stages=st)
-            pooled = multiscale_roi_align(feats, rois, (H, W), self.box_head.P, 2, in_padded=True, out=self._pooled)
-            self.box_head(pooled)
-            out = postprocess_detections(self.box_head._scores, rois, hw, self.box_head.classes, self.score_thresh,
-                                         self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st,
-                                         rois_out=self._det_rois, select=self.select)
-        if st is not None:
-            st.update(features=feats, pooled=pooled, head_out=self.box_head._scores)
-        return out, feats, hw
 
     def _run(self, x, image_sizes, st, tf=None):
         """forward's and predict's one path: _detect, every branch on the un-rescaled detections, predict's boxes into
@@ -804,12 +732,101 @@ class FasterRCNN(Net):
     def to_image_lists(out):
         """to_lists of a predict's result: boxes and keypoints are already in each image's own pixels, each image's
         masks are cropped to its own [h][w]."""
-        res = FasterRCNN.to_lists(out)
+        res = _Detector.to_lists(out)
         for key in MASK_KEYS:
             if key in out:
                 for d, (h, w) in zip(res, out["original_sizes"]):
                     d[key] = d[key][:, :, :h, :w].contiguous()
         return res
+
+
+class FasterRCNN(_Detector):
+    """torchvision's fasterrcnn_*_fpn at test time on the library's kernels: ResNetFPN(padded) -> RPN ->
+    multiscale_roi_align -> BoxHead -> postprocess_detections.  forward takes the already normalised batch; predict
+    takes a list of images of different sizes (GeneralizedRCNNTransform in one launch) and returns boxes in each image's
+    own pixels."""
+
+    def __init__(self, backbone, rpn, box_head, detections, score_thresh, nms_thresh, max_candidates, device,
+                 select="torch"):
+        super().__init__(device, detections)
+        self.select = _check_select(select)
+        self.backbone, self.rpn, self.box_head = backbone, rpn, box_head
+        self.score_thresh, self.nms_thresh = float(score_thresh), float(nms_thresh)
+        self.max_candidates = max_candidates
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, num_classes=None, out_channels: int = 256, P: int = 7, eps: float = 1e-5,
+                        rpn_pre_nms_top_n: int = 1000, rpn_post_nms_top_n: int = 1000, rpn_nms_thresh: float = 0.7,
+                        rpn_score_thresh: float = 0.0, box_score_thresh: float = SCORE_THRESH_STRICT,
+                        box_nms_thresh: float = 0.5, box_detections_per_img: int = 100, max_candidates=None, sizes=ANCHOR_SIZES,
+                        ratios=ANCHOR_RATIOS, device=None, select: str = "torch") -> "FasterRCNN":
+        """sd under torchvision's key names: backbone.body.*, backbone.fpn.*, rpn.*, roi_heads.box_head.*,
+        roi_heads.box_predictor.*; each part is validated with check_state_dict.  select: "torch" or "kernel", for the
+        RPN's filter_proposals and postprocess_detections alike (see the module docstring)."""
+        from .fpn import ResNetFPN
+        _check_select(select)
+        parts = {"backbone.": {}, "rpn.": {}, "roi_heads.": {}}
+        for k, v in sd.items():
+            for prefix, part in parts.items():
+                if k.startswith(prefix):
+                    part[k[len(prefix):]] = v
+                    break
+            else:
+                raise WinoError(f"state dict: unexpected key {k!r} for Faster R-CNN")
+        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device)
+        rpn = RPN.from_state_dict(parts["rpn."], out_channels, sizes, ratios, rpn_pre_nms_top_n, rpn_post_nms_top_n,
+                                  rpn_nms_thresh, rpn_score_thresh, 1e-3, backbone.device, select=select)
+        box_head = BoxHead.from_state_dict(parts["roi_heads."], out_channels, P, backbone.device)
+        if num_classes is not None and int(num_classes) != box_head.classes:
+            raise WinoError(f"state dict has {box_head.classes} classes, num_classes={num_classes}")
+        return cls(backbone, rpn, box_head, box_detections_per_img, box_score_thresh, box_nms_thresh, max_candidates,
+                   backbone.device, select=select)
+
+    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
+        """prepare(); for_predict: on behalf of prepare_images, so a branch may leave what only forward needs to the
+        first forward.  The model counts as prepared (_shape) once the last branch is."""
+        N, H, W, D, dev = int(N), int(H), int(W), self.detections, self.device
+        if self.select == "kernel" and self.max_candidates is not None and int(self.max_candidates) > SELECT_MAX_ROWS:
+            raise WinoError(f"select=\"kernel\" keeps at most {SELECT_MAX_ROWS} candidates, "
+                            f"max_candidates={self.max_candidates}")
+        for b in self.branches:
+            b.check(H, W)
+        self._shape = None   # (a prepare that raises from here on leaves the model unprepared, whatever it was before)
+        with torch.cuda.device(dev):
+            self.backbone.prepare(N, H, W)
+            p = self.backbone._p
+            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in p]
+            level_hw.append(((level_hw[-1][0] + 1) // 2, (level_hw[-1][1] + 1) // 2))
+            self.rpn.prepare(N, level_hw, (H, W))
+            R, bh = N * self.rpn.post, self.box_head
+            bh.prepare(R)
+            self._pooled = torch.empty((R, bh.P, bh.P, bh.in_channels), dtype=torch.float32, device=dev)
+            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=torch.float32, device=dev)
+            # the detections as RoIAlign rows [N][D][5]: what every branch reads, so only written when there is one
+            self._det_rois = torch.empty((N, D, 5), dtype=torch.float32, device=dev) if self.branches else None
+            for b in self.branches:
+                b.prepare(N, D, H, W, for_predict)
+        self._shape = (N, H, W)
+
+    def _detect(self, x, image_sizes, st):
+        """Faster R-CNN's stages; returns (the result dict, the pyramid, image_hw)."""
+        from . import multiscale_roi_align
+        self._begin(x)
+        N, H, W = self._shape
+        hw = self._full_hw if image_sizes is None else image_sizes
+        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
+            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
+        with torch.cuda.device(self.device):
+            feats = self.backbone(x, padded=True)
+            rois, _, _ = self.rpn(feats, hw, (H, W), stages=st)
+            pooled = multiscale_roi_align(feats, rois, (H, W), self.box_head.P, 2, in_padded=True, out=self._pooled)
+            self.box_head(pooled)
+            out = postprocess_detections(self.box_head._scores, rois, hw, self.box_head.classes, self.score_thresh,
+                                         self.nms_thresh, self.detections, 1e-2, self.max_candidates, stages=st,
+                                         rois_out=self._det_rois, select=self.select)
+        if st is not None:
+            st.update(features=feats, pooled=pooled, head_out=self.box_head._scores)
+        return out, feats, hw
 
 
 def _split_state_dict(sd, prefixes):
@@ -1131,7 +1148,268 @@ class KeypointRCNN(FasterRCNN):
         return m
 
 
-__all__ = ["BoxHead", "MaskHead", "KeypointHead", "RPN", "FasterRCNN", "MaskRCNN", "KeypointRCNN", "split_mask_state_dict",
+# ---- RetinaNet --------------------------------------------------------------------------------------------------------------
+RETINA_SIZES = tuple((x, int(x * 2 ** (1.0 / 3)), int(x * 2 ** (2.0 / 3))) for x in (32, 64, 128, 256, 512))
+RETINA_LEVELS = ("0", "1", "2", "p6", "p7")
+RETINA_CONVS = 4
+RETINA_NMS_SCORE_MIN = 1.1754943508222875e-38   # FLT_MIN: what a padding row's score 0.0 fails in batched_nms
+
+
+def logit_threshold(score_thresh: float) -> float:
+    """The fp32 logit t with sigmoid(t) > score_thresh >= sigmoid(pred(t)), sigmoid evaluated in fp64: the fp32 successor
+    of log(s / (1 - s)).  `logit >= t` is then `sigmoid(logit) > s` on exact arithmetic: torchvision's strict compare,
+    moved in front of the sigmoid."""
+    import math
+    s = float(score_thresh)
+    if not 0.0 < s < 1.0:
+        raise WinoError(f"score_thresh={score_thresh}: RetinaNet thresholds the logit and needs 0 < score_thresh < 1")
+    # sigmoid in fp64 is monotone over the fp32 numbers: bisect their order (the bit patterns, negatives mirrored) for the
+    # first one whose sigmoid exceeds s.  No stepping from log(s / (1 - s)): at s = 0.5 the first fp32 number whose fp64
+    # sigmoid exceeds 0.5 lies 2^29 numbers above 0.
+    import struct
+    sig = lambda v: 0.0 if v < -700.0 else 1.0 / (1.0 + math.exp(-v))
+    value = lambda key: struct.unpack("<f", struct.pack("<I", key if key >= 0 else 0x80000000 - key - 1))[0]   # -1 is -0.0
+    lo, hi = -0x7f800001, 0x7f800000   # -Inf (sigmoid 0 <= s) and +Inf (sigmoid 1 > s)
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if sig(value(mid)) > s:
+            hi = mid
+        else:
+            lo = mid
+    return value(hi)
+
+
+def _retina_conv(sd, head: str, i: int) -> str:
+    """The stem of tower convolution i of `head`: conv.{i}.0 (Conv2dNormActivation), or the legacy Sequential's
+    conv.{2i} (its odd entries are ReLUs)."""
+    return f"{head}.conv.{2 * i}" if f"{head}.conv.0.weight" in sd else f"{head}.conv.{i}.0"
+
+
+def expected_retinanet_head_keys(sd, in_channels: int, A: int, classes: int):
+    """{key: shape} of torchvision's RetinaNetHead below `head.`; the legacy spelling conv.{2i} is accepted per tower."""
+    C, exp = int(in_channels), {}
+    for head, last, width in (("classification_head", "cls_logits", A * classes), ("regression_head", "bbox_reg", 4 * A)):
+        for i in range(RETINA_CONVS):
+            exp[f"{_retina_conv(sd, head, i)}.weight"] = (C, C, 3, 3)
+            exp[f"{_retina_conv(sd, head, i)}.bias"] = (C,)
+        exp[f"{head}.{last}.weight"] = (width, C, 3, 3)
+        exp[f"{head}.{last}.bias"] = (width,)
+    return exp
+
+
+def validate_retinanet_head_state_dict(sd, in_channels: int = 256, A: int = 9) -> int:
+    """Checks every key and shape on the host; the class count is read off cls_logits.  Returns it."""
+    in_channels, A = int(in_channels), int(A)
+    width = _dim0(sd, "classification_head.cls_logits.weight")
+    if A < 1 or width < A or width % A:
+        raise WinoError(f"state dict: key 'classification_head.cls_logits.weight' has {width} channels for A={A} anchors")
+    check_state_dict(sd, expected_retinanet_head_keys(sd, in_channels, A, width // A), "the RetinaNet head", "weight")
+    if in_channels < 64 or in_channels % 64:
+        raise WinoError(f"RetinaNet head: in_channels={in_channels} must be a multiple of 64")
+    return width // A
+
+
+def pack_retina_last(w: torch.Tensor, b: torch.Tensor):
+    """A tower's last 3x3, weight [K][C][3][3] and bias [K] -> the same with K zero-padded to a multiple of 64 (819 -> 832,
+    36 -> 64): the pad columns of the map are then exactly 0."""
+    K, kp = int(w.shape[0]), _pad64(int(w.shape[0]))
+    wp, bp = w.new_zeros((kp,) + tuple(w.shape[1:])), b.new_zeros(kp)
+    wp[:K], bp[:K] = w, b
+    return wp, bp
+
+
+class RetinaNetHead(_ConvTower):
+    """torchvision's RetinaNetHead (classification and regression towers, no norm layer) on the Winograd 3x3, inference
+    only: per level four conv3x3 + ReLU and one conv3x3 without, per tower, with the same packed weights on every level.
+    The outputs stay the padded maps the kernels write: class logits [N][h+2][w+2][pad64(A classes)] with channel
+    a * classes + k, box regression [N][h+2][w+2][pad64(4 A)] with anchor a's deltas at 4a .. 4a + 3 -- what
+    select_topk_map and retina_decode read in place."""
+
+    def __init__(self, in_channels: int, A: int, classes: int, device):
+        super().__init__(device)
+        self.in_channels, self.A, self.classes = int(in_channels), int(A), int(classes)
+        self.widths = [self.in_channels] * RETINA_CONVS
+        self.cols, self.ld_cls, self.ld_reg = self.A * self.classes, _pad64(self.A * self.classes), _pad64(4 * self.A)
+
+    @classmethod
+    def from_state_dict(cls, sd, in_channels: int = 256, A: int = 9, device=None) -> "RetinaNetHead":
+        """sd: the keys below torchvision's `head.`."""
+        classes = validate_retinanet_head_state_dict(sd, in_channels, A)
+        return cls._load(sd, None, device, in_channels, A, classes)
+
+    def _pack(self, sd, eps):
+        self.towers = []   # (the four (U, bias) of the tower, U and bias of its last convolution, its padded width)
+        for head, last in (("classification_head", "cls_logits"), ("regression_head", "bbox_reg")):
+            self._pack_tower(sd, [_retina_conv(sd, head, i) for i in range(RETINA_CONVS)])
+            wl, bl = pack_retina_last(sd[f"{head}.{last}.weight"], sd[f"{head}.{last}.bias"])
+            self.towers.append((self.convs, filter_transform_f2(self._t(wl)), self._t(bl), int(wl.shape[0])))
+        del self.convs
+        self._ones = torch.ones(max(self.in_channels, self.ld_cls, self.ld_reg), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+
+    def prepare(self, N: int, level_hw) -> None:
+        """Allocate, per level of `level_hw` [(h, w)], the two ping-pong tensors both towers share and the two output
+        maps, and reserve the stream scratch of every launch on the current stream.  Call it before capturing a forward
+        into a graph."""
+        N, C, dev, f32 = int(N), self.in_channels, self.device, torch.float32
+        level_hw = tuple((int(h), int(w)) for h, w in level_hw)
+        if N < 1 or not level_hw or min(min(hw) for hw in level_hw) < 1:
+            raise WinoError(f"RetinaNet head: N={N} images, levels {level_hw}")
+        with torch.cuda.device(dev):
+            zeros = lambda h, w, c: torch.zeros((N, h + 2, w + 2, c), dtype=f32, device=dev)
+            self._pp = [(zeros(h, w, C), zeros(h, w, C)) for h, w in level_hw]
+            self._cls = [zeros(h, w, self.ld_cls) for h, w in level_hw]
+            self._reg = [zeros(h, w, self.ld_reg) for h, w in level_hw]
+            for h, w in level_hw:
+                for k in (C, self.ld_cls, self.ld_reg):
+                    conv3x3_prepare(N, C, k, h, w)
+        self._shape = (N, level_hw)
+
+    def forward(self, maps):
+        """maps: the levels' padded features [N][h+2][w+2][in_channels] (zero rings; they are not written).  Returns
+        (class logit maps, box regression maps), one per level: tensors of the head's, valid until the next forward.
+        New shapes re-run prepare()."""
+        maps, C = list(maps), self.in_channels
+        for x in maps:
+            if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or min(x.shape[1:3]) < 3:
+                raise WinoError(f"RetinaNet head: every level must be [N][h+2][w+2][{C}]")
+            if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+                raise WinoError(f"RetinaNet head: every level must be contiguous float32 on {self.device}")
+        shape = (int(maps[0].shape[0]), tuple((int(x.shape[1]) - 2, int(x.shape[2]) - 2) for x in maps))
+        if any(int(x.shape[0]) != shape[0] for x in maps):
+            raise WinoError("RetinaNet head: the levels differ in N")
+        if shape != self._shape:
+            self.prepare(*shape)
+        with torch.cuda.device(self.device):
+            for l, x0 in enumerate(maps):
+                for (convs, U, bias, kp), outs in zip(self.towers, (self._cls, self._reg)):
+                    x = x0
+                    for i, (Ui, bi) in enumerate(convs):
+                        x = conv3x3_bn_relu(x, Ui, bi, self._ones[:C], relu=True, out=self._pp[l][i % 2])
+                    conv3x3_bn_relu(x, U, bias, self._ones[:kp], relu=False, out=outs[l])
+        return self._cls, self._reg
+
+
+class RetinaNet(_Detector):
+    """torchvision's retinanet_resnet50_fpn at test time on the library's kernels: ResNetFPN(returned_layers = (2, 3, 4),
+    extra_blocks = "p6p7", padded) -> RetinaNetHead -> per level select_topk_map on the class logit map in place and
+    retina_decode of the selected anchors -> one select_topk over the levels' candidates by score with the boxes as
+    payload -> batched_nms with groups = label.  Scores are torch plumbing, as in RPN: sigmoid(logit) where a row is
+    kept, else 0; the labels follow the sort by a torch gather.  forward takes the normalised batch, predict a list of
+    images (the shared detector path).  After prepare a forward reads no device data on the host and is captured into
+    one graph, bit-identical to the eager run.
+
+    Named deviations from torchvision's postprocess_detections:
+      * the threshold is applied to the logit, `logit >= t` with t = logit_threshold(score_thresh), the fp32 successor of
+        log(s / (1 - s)) evaluated in fp64, not to the fp32 sigmoid (`sigmoid(logit) > s`): the two differ only where
+        the fp32 sigmoid rounds across s;
+      * the per-level top-k orders by logit with ties to the lower index (torchvision's order among equal scores is
+        unspecified), and so does the order in which equal scores enter the NMS.
+    Not built: the v2 heads (GroupNorm, P6 from C5), FCOS, SSD."""
+
+    def __init__(self, backbone, head, sizes, ratios, detections, score_thresh, nms_thresh, topk_candidates, device):
+        super().__init__(device, detections)
+        self.backbone, self.head = backbone, head
+        self.sizes, self.ratios = tuple(tuple(s) for s in sizes), tuple(ratios)
+        self.score_thresh, self.nms_thresh, self.topk = float(score_thresh), float(nms_thresh), int(topk_candidates)
+        self.logit_thresh = logit_threshold(self.score_thresh)
+        with torch.cuda.device(self.device):
+            self.base = [self._t(base_anchors(s, self.ratios)) for s in self.sizes]
+            torch.cuda.current_stream().synchronize()
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, num_classes=None, score_thresh: float = 0.05, nms_thresh: float = 0.5,
+                        detections_per_img: int = 300, topk_candidates: int = 1000, sizes=RETINA_SIZES, ratios=ANCHOR_RATIOS,
+                        device=None, out_channels: int = 256, eps: float = 1e-5) -> "RetinaNet":
+        """sd under torchvision's key names: backbone.body.*, backbone.fpn.* (inner_blocks / layer_blocks 0..2 and
+        extra_blocks.p6|p7) and head.*; each part is validated with check_state_dict."""
+        from .fpn import ResNetFPN
+        if len(sizes) != len(RETINA_LEVELS) or len({len(s) for s in sizes}) != 1:
+            raise WinoError(f"RetinaNet: {len(RETINA_LEVELS)} levels need {len(RETINA_LEVELS)} size tuples of one length")
+        logit_threshold(score_thresh)
+        if not 1 <= int(topk_candidates) <= SELECT_MAX_ROWS // len(RETINA_LEVELS) or int(detections_per_img) < 1:
+            raise WinoError(f"RetinaNet: topk_candidates={topk_candidates} (the levels' candidates are sorted by one "
+                            f"select_topk of at most {SELECT_MAX_ROWS} rows), detections_per_img={detections_per_img}")
+        parts = {"backbone.": {}, "head.": {}}
+        for k, v in sd.items():
+            for prefix, part in parts.items():
+                if k.startswith(prefix):
+                    part[k[len(prefix):]] = v
+                    break
+            else:
+                raise WinoError(f"state dict: unexpected key {k!r} for RetinaNet")
+        A = len(sizes[0]) * len(ratios)
+        classes = validate_retinanet_head_state_dict(parts["head."], out_channels, A)
+        if num_classes is not None and int(num_classes) != classes:
+            raise WinoError(f"state dict has {classes} classes, num_classes={num_classes}")
+        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device, returned_layers=(2, 3, 4),
+                                             extra_blocks="p6p7")
+        head = RetinaNetHead.from_state_dict(parts["head."], out_channels, A, backbone.device)
+        return cls(backbone, head, sizes, ratios, detections_per_img, score_thresh, nms_thresh, topk_candidates,
+                   backbone.device)
+
+    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
+        from . import nms_workspace_bytes, select_map_workspace_bytes, select_workspace_bytes
+        N, H, W, D, dev, f32, i32 = int(N), int(H), int(W), self.detections, self.device, torch.float32, torch.int32
+        self._shape = None
+        with torch.cuda.device(dev):
+            self.backbone.prepare(N, H, W)
+            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in (*self.backbone._p, *self.backbone._extra[::2])]
+            self.head.prepare(N, level_hw)
+            cols = self.head.cols
+            self._grid = [(h, w, H // h, W // w) for h, w in level_hw]
+            if min(min(g[2:]) for g in self._grid) < 1:
+                raise WinoError(f"RetinaNet: a batch of {H} x {W} is smaller than its pyramid levels {level_hw}")
+            self._k = [min(self.topk, h * w * cols) for h, w in level_hw]
+            self._off = [sum(self._k[:l]) for l in range(len(self._k))]
+            K = sum(self._k)
+            empty = lambda shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
+            self._b = dict(
+                idx=empty((N, K), i32), logit=empty((N, K)), count=[empty((N,), i32) for _ in level_hw], boxes=empty((N, K, 4)),
+                labels=empty((N, K), i32), order=empty((N, K), i32), sscores=empty((N, K)), count2=empty((N, 1), i32),
+                sboxes=empty((N, K, 4)), keep=empty((N, D), i32), det_count=empty((N,), i32),
+                ws=[empty(((select_map_workspace_bytes(N, h, w, cols, k) + 3) // 4,)) for (h, w), k in zip(level_hw, self._k)],
+                ws2=empty(((select_workspace_bytes(N, K, K) + 3) // 4,)), nms=empty(((nms_workspace_bytes(N, K) + 3) // 4,)))
+            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=f32, device=dev)
+        self._shape = (N, H, W)
+
+    def _detect(self, x, image_sizes, st):
+        """RetinaNet's stages; returns (the result dict, the pyramid, image_hw)."""
+        from . import batched_nms, retina_decode, select_topk, select_topk_map
+        self._begin(x)
+        N, H, W = self._shape
+        hw = self._full_hw if image_sizes is None else image_sizes
+        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
+            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
+        b, K, cols = self._b, self.head.classes, self.head.cols
+        with torch.cuda.device(self.device):
+            feats = self.backbone(x, padded=True)
+            cls, reg = self.head([feats[name] for name in RETINA_LEVELS])
+            for l, (k, off) in enumerate(zip(self._k, self._off)):
+                select_topk_map(cls[l], cols, k, self.logit_thresh, b["idx"], b["logit"], b["count"][l], off, b["ws"][l])
+                retina_decode(b["idx"], reg[l], self.base[l], hw, self._grid[l], K, k, b["boxes"], b["labels"], off)
+            scores = torch.where(b["idx"] >= 0, torch.sigmoid(b["logit"]), torch.zeros_like(b["logit"]))
+            order, sscores, _, sboxes = select_topk(scores, sum(self._k), boxes=b["boxes"], out_idx=b["order"],
+                                                    out_vals=b["sscores"], out_count=b["count2"], out_boxes=b["sboxes"],
+                                                    workspace=b["ws2"])
+            slabels = b["labels"].gather(1, order.long())
+            keep, count = batched_nms(sboxes, sscores, slabels, self.nms_thresh, 0.0, RETINA_NMS_SCORE_MIN, self.detections,
+                                      workspace=b["nms"], keep=b["keep"], count=b["det_count"])
+            kept = keep >= 0
+            at = keep.clamp(min=0).long()
+            out = {"boxes": sboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
+                   "scores": sscores.gather(1, at) * kept,
+                   "labels": torch.where(kept, slabels.gather(1, at).long(), torch.full_like(at, -1)), "count": count}
+        if st is not None:
+            st.update(features=feats, cls_maps=list(cls), reg_maps=list(reg), level_idx=b["idx"], level_logits=b["logit"],
+                      level_count=torch.stack(b["count"]), cand_boxes=b["boxes"], cand_labels=b["labels"], cand_scores=scores,
+                      order=order, sorted_boxes=sboxes, sorted_scores=sscores, sorted_labels=slabels, det_keep=keep)
+        return out, feats, hw
+
+
+__all__ = ["BoxHead", "MaskHead", "KeypointHead", "RPN", "FasterRCNN", "MaskRCNN", "KeypointRCNN", "RetinaNetHead",
+           "RetinaNet", "logit_threshold", "expected_retinanet_head_keys", "validate_retinanet_head_state_dict",
+           "pack_retina_last", "split_mask_state_dict",
            "split_keypoint_state_dict", "postprocess_detections", "base_anchors", "pack_rpn_head",
            "expected_rpn_keys", "expected_box_head_keys", "expected_mask_head_keys", "expected_keypoint_head_keys",
            "validate_box_head_state_dict", "validate_mask_head_state_dict", "validate_keypoint_head_state_dict", "pack_fc6",

@@ -68,6 +68,7 @@ extern "C" {
  * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
  * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_select_topk_hw, wino_roi_align_launches,
  * wino_image_transform_hw, WINO_IMAGE_*, WINO_TRANSFORM_MAX_IMAGES, wino_transform_size,
+ * wino_select_topk_map_hw, wino_retina_decode_hw,
  * wino_keypoints_hw, WINO_KP_LAYOUT_*, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
@@ -1019,6 +1020,47 @@ int wino_select_topk_hw(const float* scores, int N, long image_stride, int parts
                         const int* n_host, const int* k_host, int use_thresh, float score_thresh, int* idx, float* vals,
                         int* count, long out_stride, const float* boxes_in, long boxes_image_stride, float* boxes_out,
                         void* workspace, size_t workspace_bytes, wino_stream_t s);
+
+/* wino_select_topk_map_hw: the same select on a padded NHWC map, in place.  map is DEVICE [N][h+2][w+2][ld] fp32 (what
+ * a 3x3 layer writes: interior at (1 + y, 1 + x), a ring of one pixel around it, ld - cols pad columns per pixel).
+ * Segment i is image i's n = h * w * cols scores map[i][1 + y][1 + x][c], c < cols <= ld, and the index of one is
+ *   (y * w + x) * cols + c
+ * -- with cols = A * K and the head's channel a * K + k, torchvision's (N, HWA, K) flattening.  Order, NaN and +-0 rules,
+ * the score_thresh candidates (>=), k <= 8192 and the fixed-size outputs are wino_select_topk_hw's with parts = 1:
+ *   idx    DEVICE int32; image i writes k rows at i * out_stride + out_offset: the index above, -1 past the kept count
+ *   vals   NULL, or DEVICE fp32 in the same slots: the score's own bits, 0.0 past the kept count
+ *   count  DEVICE [N] int32
+ * out_offset (like wino_box_decode_hw's boxes_offset) lets every level of a pyramid write its slice of one [N][sum k]
+ * buffer; what lies outside the slice is not written.  The ring and the pad columns have no index: no launch reads them
+ * as candidates, whatever they hold.  Offsets into the map are 64-bit (N * (h+2) * (w+2) * ld * 4 passes 4 GiB long
+ * before n passes 2^31).  The launches are wino_select_topk_hw's: one for n <= 8192, seven beyond, each of the middle
+ * five reading every score once; an element's address costs two multiply-highs, no division.
+ * 0 <= N <= 65535, h, w >= 1, 1 <= cols <= ld, 1 <= k <= 8192, (w+2) * ld < 2^32, (h+2) * (w+2) * ld < 2^40,
+ * 0 <= out_offset, out_offset + k <= out_stride < 2^31 (WINO_E_SHAPE otherwise); n = h * w * cols > 2^31 - 1 is refused
+ * with a message of its own (an index would not fit idx).  Pointer, threshold, workspace and overlap rules as for
+ * wino_select_topk_hw.  No stream scratch: capturable as it is.
+ * The workspace is the formula above for the one part n = h * w * cols (0 when n <= 8192); the Python wrapper's
+ * select_map_workspace_bytes computes it. */
+int wino_select_topk_map_hw(const float* map, int N, int h, int w, int cols, int ld, int k, int use_thresh,
+                            float score_thresh, int* idx, float* vals, int* count, long out_stride, long out_offset,
+                            void* workspace, size_t workspace_bytes, wino_stream_t s);
+
+/* ---- RetinaNet: decode only the selected anchors (retina.hip) -------------------------------------
+ * wino_retina_decode_hw: rows offset .. offset + k of image i's idx [N][stride] (DEVICE int32, as
+ * wino_select_topk_map_hw writes them with cols = A * K) name class k' = idx % K of anchor idx / K of an h x w level with
+ * A anchors per pixel: pixel (idx / K) / A = y * w + x, anchor a = (idx / K) % A.  The deltas of anchor a are columns
+ * 4a .. 4a + 3 of pixel (1 + y, 1 + x) of reg, DEVICE [N][h+2][w+2][ld_r] fp32; the anchor is base[a] (DEVICE [A][4])
+ * shifted by (x * stride_x, y * stride_y); the box is wino_box_decode_hw's arithmetic with weights (1, 1, 1, 1) and
+ * `clamp`, clipped to image_hw[i] (DEVICE [N][2]): bit for bit what wino_box_decode_hw writes in grid mode for that
+ * anchor.  Writes the same rows of boxes (DEVICE [N][stride][4] fp32) and labels (DEVICE [N][stride] int32).  A row whose
+ * idx is negative (past the kept count) or not below h * w * A * K gets a zero box and label -1 and reads no map.
+ * N, k >= 0 (either 0: WINO_OK, nothing launched), N * k < 2^31, h, w, A, K >= 1, h * w * A * K <= 2^31 - 1,
+ * 4 * A <= ld_r, (w+2) * ld_r < 2^32, (h+2) * (w+2) * ld_r < 2^40, strides >= 1, 0 <= offset, offset + k <= stride
+ * (WINO_E_SHAPE otherwise).  A NULL or not 16-byte-aligned pointer, a NaN clamp, or an output that overlaps an input or
+ * the other output is WINO_E_ARG.  No scratch: capturable as it is. */
+int wino_retina_decode_hw(const int* idx, int N, int k, long stride, long offset, const float* reg, int h, int w,
+                          int ld_r, int A, int K, const float* base, int stride_y, int stride_x, const float* image_hw,
+                          float clamp, float* boxes, int* labels, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
