@@ -1192,6 +1192,94 @@ def retina_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=
     return boxes, labels
 
 
+GN_FORMS = {1: "whole", 2: "split"}   # WINO_GN_FORM_*
+
+
+def groupnorm_plan(N: int, h: int, w: int, C: int, groups: int, cus: int = 256):
+    """(form, chunks) of groupnorm_relu for N maps of h x w pixels and C channels in `groups` groups on a device of `cus`
+    CUs: form "whole" (one launch, chunks = 1) or "split" (statistics per chunk of pixels, then apply).  Host only;
+    WINO_GN_FORM = whole | split (read at the library's first use, or by wino_debug_reload_knobs) forces a form.  Raises WinoError outside the layer's limits."""
+    form, chunks = _plan_query("wino_groupnorm_plan", 2, int(N), int(h), int(w), int(C), int(groups), int(cus))
+    return GN_FORMS[form], chunks
+
+
+def groupnorm_workspace_bytes(N: int, h: int, w: int, C: int, groups: int) -> int:
+    """Bytes of groupnorm_relu's workspace: 0 for the whole form, N * min(h w, 128) * 4 * groups * 4 for the split form
+    (enough on any device): the formula of winograd_mi355x.h.  Host only; raises WinoError outside the layer's limits."""
+    form, _ = groupnorm_plan(N, h, w, C, groups)
+    return 0 if form == "whole" else int(N) * min(int(h) * int(w), 128) * 4 * int(groups) * 4
+
+
+def groupnorm_relu(x, gamma, beta, groups: int, eps: float = 1e-5, relu: bool = True, out=None, workspace=None):
+    """torch's F.group_norm(x, groups, gamma, beta, eps), then ReLU when `relu`, on a padded NHWC map (groupnorm.hip).
+    x [N][h+2][w+2][C] float32, what a 3x3 layer writes; gamma, beta [C].  Statistics per (image, group) over the h * w *
+    (C / groups) interior values, biased variance; only the interior of `out` is written (a new `out` starts as zeros, so
+    its ring is the padding the next 3x3 reads).  out=x normalises in place.  C a multiple of 64, C / groups a power of
+    two.  workspace: groupnorm_workspace_bytes(...) bytes.  One launch or two (groupnorm_plan); deterministic; no scratch
+    of the library's: capturable into a graph without a prepare."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4 \
+            or int(x.shape[1]) < 3 or int(x.shape[2]) < 3:
+        raise WinoError("x must be a contiguous float32 CUDA(HIP) tensor [N][h+2][w+2][C]")
+    N, h, w, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    g, b = _dev(gamma, "gamma"), _dev(beta, "beta")
+    if tuple(g.shape) != (C,) or tuple(b.shape) != (C,):
+        raise WinoError(f"gamma and beta must be [{C}]")
+    need = groupnorm_workspace_bytes(N, h, w, C, groups)
+    o = torch.zeros_like(x) if out is None else _out(out, x.shape, "out")
+    ws = _workspace(workspace, need, x.device) if need or workspace is not None else None
+    _on_current_device(x, g, b, o, ws)
+    ptr = lambda t: None if t is None else (t.data_ptr() or None)
+    _check(lib().wino_groupnorm_relu_hw(ptr(x), ptr(g), ptr(b), ptr(o), N, h, w, C, int(groups), float(eps), 1 if relu else 0,
+                                        ptr(ws), 0 if ws is None else ws.numel() * 4, _stream()), "wino_groupnorm_relu_hw")
+    return o
+
+
+def fcos_score_map(cls_map, reg_map, K: int, ctr_col: int = 4):
+    """FCOS's score of every location, in place on the class-logit map, in one HIP launch (fcos.hip).  cls_map
+    [N][h+2][w+2][ld_c] float32: interior columns < K become sqrt(sigmoid(logit) * sigmoid(ctr)) with ctr = column ctr_col
+    of the same pixel of reg_map [N][h+2][w+2][ld_r].  Rings and pad columns are neither read nor written.  Returns
+    cls_map.  No scratch: capturable without a prepare."""
+    for t, name in ((cls_map, "cls_map"), (reg_map, "reg_map")):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous() or t.dim() != 4:
+            raise WinoError(f"{name} must be a contiguous float32 CUDA(HIP) tensor [N][h+2][w+2][ld]")
+    if tuple(cls_map.shape[:3]) != tuple(reg_map.shape[:3]) or int(cls_map.shape[1]) < 3 or int(cls_map.shape[2]) < 3:
+        raise WinoError("cls_map and reg_map must be [N][h+2][w+2][ld] maps of one level")
+    N, h, w = int(cls_map.shape[0]), int(cls_map.shape[1]) - 2, int(cls_map.shape[2]) - 2
+    _on_current_device(cls_map, reg_map)
+    _check(lib().wino_fcos_score_map_hw(cls_map.data_ptr() or None, reg_map.data_ptr() or None, N, h, w, int(K),
+                                        int(cls_map.shape[3]), int(reg_map.shape[3]), int(ctr_col), _stream()),
+           "wino_fcos_score_map_hw")
+    return cls_map
+
+
+def fcos_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=None, out_labels=None, out_offset: int = 0):
+    """FCOS's decode of the selected locations only, in one HIP launch (fcos.hip): retina_decode's operands, rows and
+    outputs, with the anchor-free box of torchvision's BoxLinearCoder(normalize_by_size=True): (l, t, r, b) = relu of
+    columns 4a .. 4a + 3 of reg_map, box = (cx - l w, cy - t h, cx + r w, cy + b h) of the shifted base anchor, clipped to
+    the image.  Rows with idx < 0 get a zero box and label -1.  No scratch: capturable without a prepare."""
+    ix = idx
+    if not isinstance(ix, torch.Tensor) or not ix.is_cuda or ix.dtype != torch.int32 or not ix.is_contiguous() or ix.dim() != 2:
+        raise WinoError("idx must be a contiguous int32 CUDA(HIP) tensor [N][total]")
+    reg, anc, hw = _dev(reg_map, "reg_map"), _dev(base, "base"), _dev(image_hw, "image_hw")
+    N, total, off = int(ix.shape[0]), int(ix.shape[1]), int(out_offset)
+    gh, gw, sy, sx = (int(v) for v in grid)
+    if reg.dim() != 4 or tuple(reg.shape[:3]) != (N, gh + 2, gw + 2) or tuple(hw.shape) != (N, 2):
+        raise WinoError(f"reg_map must be [{N}][{gh + 2}][{gw + 2}][ld_r] and image_hw [{N}][2]")
+    if anc.dim() != 2 or int(anc.shape[1]) != 4:
+        raise WinoError("base must be [A][4]")
+    k = total - off if k is None else int(k)
+    if off < 0 or k < 0 or off + k > total:
+        raise WinoError(f"fcos_decode: rows {off} .. {off + k} of {total}")
+    boxes = _output(out_boxes, (N, total, 4), ix.device, "out_boxes")
+    labels = _int32(out_labels, (N, total), ix.device, "out_labels")
+    _on_current_device(ix, reg, anc, hw, boxes, labels)
+    ptr = lambda t: t.data_ptr() or None
+    _check(lib().wino_fcos_decode_hw(ptr(ix), N, k, total, off, ptr(reg), gh, gw, int(reg.shape[3]), int(anc.shape[0]),
+                                     int(K), ptr(anc), sy, sx, ptr(hw), ptr(boxes), ptr(labels), _stream()),
+           "wino_fcos_decode_hw")
+    return boxes, labels
+
+
 MASK_LAYOUTS = {"planes": 0, "gemm_rows": 1}   # WINO_MASK_LAYOUT_*
 MASK_MAX_M = 62
 
@@ -1770,3 +1858,4 @@ from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
 from .detection import BoxHead, MaskHead, KeypointHead, RPN, FasterRCNN, MaskRCNN, KeypointRCNN  # noqa: E402
 from .detection import RetinaNetHead, RetinaNet  # noqa: E402
+from .detection import FCOSHead, FCOS  # noqa: E402

@@ -190,6 +190,12 @@ SIGNATURES = {
     "wino_select_topk_map_hw": (i, [vp] + [i] * 7 + [c_float] + [vp] * 3 + [c_long] * 2 + [vp, sz, vp]),
     # ---- RetinaNet: decode only the selected anchors
     "wino_retina_decode_hw": (i, [vp, i, i, c_long, c_long, vp] + [i] * 5 + [vp, i, i, vp, c_float, vp, vp, vp]),
+    # ---- GroupNorm (+ ReLU) on a padded map
+    "wino_groupnorm_plan": (i, [i] * 6 + [ip] * 2),
+    "wino_groupnorm_relu_hw": (i, [vp] * 4 + [i] * 5 + [c_float, i, vp, sz, vp]),
+    # ---- FCOS: score map and decode of the selected locations
+    "wino_fcos_score_map_hw": (i, [vp] * 2 + [i] * 7 + [vp]),
+    "wino_fcos_decode_hw": (i, [vp, i, i, c_long, c_long, vp] + [i] * 5 + [vp, i, i, vp, vp, vp, vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

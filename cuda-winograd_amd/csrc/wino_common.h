@@ -98,6 +98,7 @@ struct Knobs {
   int small_rt, small_ct;   // WINO_1X1_SMALL_RT / _CT: MFMA row / column tiles per wave, 1 / 2 (0 = policy)
   int stem_form;      // WINO_STEM_FORM: 0 automatic, 1 8x8-pool tiles x 64 channels, 2 4x4-pool tiles x 16 channels
   int roi_launch_tasks;   // WINO_ROI_LAUNCH_TASKS: most output positions (boxes x Q x Q) of one RoIAlign launch (<= 0: 2^31)
+  int gn_form;        // WINO_GN_FORM: 0 automatic, 1 "whole" (one launch), 2 "split" (statistics, then apply)
 };
 Knobs knobs();
 #define WINO_HIP(call)                                          \

@@ -152,6 +152,8 @@ void read_knobs() {
   k.small_ct = env_num("WINO_1X1_SMALL_CT", 0);
   k.stem_form = env_num("WINO_STEM_FORM", 0);
   k.roi_launch_tasks = env_num("WINO_ROI_LAUNCH_TASKS", 0);
+  const char* gn = getenv("WINO_GN_FORM");
+  k.gn_form = gn && !strcmp(gn, "whole") ? 1 : gn && !strcmp(gn, "split") ? 2 : 0;
   g_knobs = k;
 }
 }  // namespace

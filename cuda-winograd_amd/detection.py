@@ -1305,7 +1305,7 @@ class RetinaNet(_Detector):
         the fp32 sigmoid rounds across s;
       * the per-level top-k orders by logit with ties to the lower index (torchvision's order among equal scores is
         unspecified), and so does the order in which equal scores enter the NMS.
-    Not built: the v2 heads (GroupNorm, P6 from C5), FCOS, SSD."""
+    Not built: the v2 heads (they need P6 from C5 beside the GroupNorm kernel FCOSHead runs), SSD."""
 
     def __init__(self, backbone, head, sizes, ratios, detections, score_thresh, nms_thresh, topk_candidates, device):
         super().__init__(device, detections)
@@ -1407,7 +1407,244 @@ class RetinaNet(_Detector):
         return out, feats, hw
 
 
+# ---- FCOS ------------------------------------------------------------------------------------------------------------------
+FCOS_SIZES = ((8,), (16,), (32,), (64,), (128,))
+FCOS_GROUPS = 32     # torchvision's GroupNorm(32, in_channels) between the tower convolutions
+FCOS_CTR_COL = 4     # bbox_ctrness rides in column 4 of the regression map, beside bbox_reg's 0 .. 3
+
+
+def score_threshold(score_thresh: float) -> float:
+    """The fp32 successor of score_thresh: `score >= t` on fp32 scores is torchvision's strict `score > score_thresh`."""
+    import numpy as np
+    s = np.float32(score_thresh)
+    if not 0.0 <= float(s) < 1.0:
+        raise WinoError(f"score_thresh={score_thresh}: FCOS needs 0 <= score_thresh < 1")
+    return float(np.nextafter(s, np.float32(np.inf)))
+
+
+def expected_fcos_head_keys(in_channels: int, classes: int):
+    """{key: shape} of torchvision's FCOSHead below `head.`: per tower conv.{0,3,6,9} (3x3 with bias) and their
+    GroupNorms conv.{1,4,7,10}, then cls_logits, bbox_reg and bbox_ctrness."""
+    C, exp = int(in_channels), {}
+    for head in ("classification_head", "regression_head"):
+        for i in range(RETINA_CONVS):
+            exp[f"{head}.conv.{3 * i}.weight"], exp[f"{head}.conv.{3 * i}.bias"] = (C, C, 3, 3), (C,)
+            exp[f"{head}.conv.{3 * i + 1}.weight"], exp[f"{head}.conv.{3 * i + 1}.bias"] = (C,), (C,)
+    for key, width in (("classification_head.cls_logits", int(classes)), ("regression_head.bbox_reg", 4),
+                       ("regression_head.bbox_ctrness", 1)):
+        exp[f"{key}.weight"], exp[f"{key}.bias"] = (width, C, 3, 3), (width,)
+    return exp
+
+
+def validate_fcos_head_state_dict(sd, in_channels: int = 256) -> int:
+    """Checks every key and shape on the host (the GroupNorm keys included); the class count is read off cls_logits.
+    Returns it."""
+    in_channels = int(in_channels)
+    classes = _dim0(sd, "classification_head.cls_logits.weight")
+    check_state_dict(sd, expected_fcos_head_keys(in_channels, classes), "the FCOS head", "weight")
+    if in_channels < 64 or in_channels % 64 or (in_channels // FCOS_GROUPS) & (in_channels // FCOS_GROUPS - 1):
+        raise WinoError(f"FCOS head: in_channels={in_channels} must be a multiple of 64 with in_channels / {FCOS_GROUPS} a "
+                        "power of two")
+    return classes
+
+
+class FCOSHead(_ConvTower):
+    """torchvision's FCOSHead (classification and regression towers with GroupNorm(32, C) + ReLU) on the Winograd 3x3 and
+    the GroupNorm kernel, inference only: per level and tower four times conv3x3 (bias, no ReLU) -> groupnorm_relu in
+    place, then the last 3x3 without ReLU, with the same packed weights on every level.  The outputs stay the padded maps
+    the kernels write: class logits [N][h+2][w+2][pad64(classes)], and one regression map [N][h+2][w+2][64] with bbox_reg
+    in columns 0 .. 3 (before its ReLU: fcos_decode applies it) and bbox_ctrness in column 4 -- what fcos_score_map,
+    select_topk_map and fcos_decode read in place."""
+
+    def __init__(self, in_channels: int, classes: int, device):
+        super().__init__(device)
+        self.in_channels, self.classes = int(in_channels), int(classes)
+        self.widths = [self.in_channels] * RETINA_CONVS
+        self.cols, self.ld_cls, self.ld_reg = self.classes, _pad64(self.classes), 64
+
+    @classmethod
+    def from_state_dict(cls, sd, in_channels: int = 256, device=None) -> "FCOSHead":
+        """sd: the keys below torchvision's `head.`."""
+        classes = validate_fcos_head_state_dict(sd, in_channels)
+        return cls._load(sd, None, device, in_channels, classes)
+
+    def _pack(self, sd, eps):
+        self.towers = []   # (the four (U, bias) of the tower, its four (gamma, beta), U and bias of its last convolution, its width)
+        for head, last in (("classification_head", ("cls_logits",)), ("regression_head", ("bbox_reg", "bbox_ctrness"))):
+            self._pack_tower(sd, [f"{head}.conv.{3 * i}" for i in range(RETINA_CONVS)])
+            norms = [(self._t(sd[f"{head}.conv.{3 * i + 1}.weight"]), self._t(sd[f"{head}.conv.{3 * i + 1}.bias"]))
+                     for i in range(RETINA_CONVS)]
+            wl, bl = pack_retina_last(torch.cat([sd[f"{head}.{k}.weight"] for k in last]),
+                                      torch.cat([sd[f"{head}.{k}.bias"] for k in last]))
+            self.towers.append((self.convs, norms, filter_transform_f2(self._t(wl)), self._t(bl), int(wl.shape[0])))
+        del self.convs
+        self._ones = torch.ones(max(self.in_channels, self.ld_cls, self.ld_reg), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+
+    def prepare(self, N: int, level_hw) -> None:
+        """Allocate, per level of `level_hw` [(h, w)], the two ping-pong tensors both towers share, the two output maps
+        and the GroupNorm workspace, and reserve the stream scratch of every convolution on the current stream.  Call it
+        before capturing a forward into a graph."""
+        N, C, dev, f32 = int(N), self.in_channels, self.device, torch.float32
+        level_hw = tuple((int(h), int(w)) for h, w in level_hw)
+        if N < 1 or not level_hw or min(min(hw) for hw in level_hw) < 1:
+            raise WinoError(f"FCOS head: N={N} images, levels {level_hw}")
+        with torch.cuda.device(dev):
+            zeros = lambda h, w, c: torch.zeros((N, h + 2, w + 2, c), dtype=f32, device=dev)
+            self._pp = [(zeros(h, w, C), zeros(h, w, C)) for h, w in level_hw]
+            self._cls = [zeros(h, w, self.ld_cls) for h, w in level_hw]
+            self._reg = [zeros(h, w, self.ld_reg) for h, w in level_hw]
+            # the split form's size whatever the plan says now: a WINO_GN_FORM set after prepare finds room
+            self._gn_ws = [torch.empty((N * min(h * w, 128) * 4 * FCOS_GROUPS,), dtype=f32, device=dev) for h, w in level_hw]
+            for h, w in level_hw:
+                for k in (C, self.ld_cls, self.ld_reg):
+                    conv3x3_prepare(N, C, k, h, w)
+        self._shape = (N, level_hw)
+
+    def forward(self, maps):
+        """maps: the levels' padded features [N][h+2][w+2][in_channels] (zero rings; they are not written).  Returns
+        (class logit maps, regression maps), one per level: tensors of the head's, valid until the next forward.  New
+        shapes re-run prepare()."""
+        from . import groupnorm_relu
+        maps, C = list(maps), self.in_channels
+        for x in maps:
+            if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or min(x.shape[1:3]) < 3:
+                raise WinoError(f"FCOS head: every level must be [N][h+2][w+2][{C}]")
+            if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+                raise WinoError(f"FCOS head: every level must be contiguous float32 on {self.device}")
+        shape = (int(maps[0].shape[0]), tuple((int(x.shape[1]) - 2, int(x.shape[2]) - 2) for x in maps))
+        if any(int(x.shape[0]) != shape[0] for x in maps):
+            raise WinoError("FCOS head: the levels differ in N")
+        if shape != self._shape:
+            self.prepare(*shape)
+        with torch.cuda.device(self.device):
+            for l, x0 in enumerate(maps):
+                for (convs, norms, U, bias, kp), outs in zip(self.towers, (self._cls, self._reg)):
+                    x = x0
+                    for i, ((Ui, bi), (gamma, beta)) in enumerate(zip(convs, norms)):
+                        x = conv3x3_bn_relu(x, Ui, bi, self._ones[:C], relu=False, out=self._pp[l][i % 2])
+                        groupnorm_relu(x, gamma, beta, FCOS_GROUPS, out=x, workspace=self._gn_ws[l])
+                    conv3x3_bn_relu(x, U, bias, self._ones[:kp], relu=False, out=outs[l])
+        return self._cls, self._reg
+
+
+class FCOS(_Detector):
+    """torchvision's fcos_resnet50_fpn at test time on the library's kernels: ResNetFPN(returned_layers = (2, 3, 4),
+    extra_blocks = "p6p7", padded) -> FCOSHead -> per level fcos_score_map in place on the class logit map,
+    select_topk_map on the score map and fcos_decode of the selected locations -> one select_topk over the levels'
+    candidates by score with the boxes as payload -> batched_nms with groups = label.  forward takes the normalised
+    batch, predict a list of images (the shared detector path).  After prepare a forward reads no device data on the
+    host and is captured into one graph, bit-identical to the eager run.
+
+    Named deviations from torchvision's postprocess_detections:
+      * equal scores go to the lower index, in the per-level top-k and in the order in which they enter the NMS
+        (torchvision's order among equal scores is unspecified);
+      * the score is the kernel's fp32 value of sqrt(sigmoid(logit) * sigmoid(centerness)); the threshold `score >
+        score_thresh` is applied to it as `score >= score_threshold(score_thresh)`, its fp32 successor;
+      * stages=True exposes the score maps ("cls_maps") where RetinaNet exposes logit maps: the logits are overwritten
+        in place."""
+
+    def __init__(self, backbone, head, sizes, detections, score_thresh, nms_thresh, topk_candidates, device):
+        super().__init__(device, detections)
+        self.backbone, self.head = backbone, head
+        self.sizes = tuple(tuple(s) for s in sizes)
+        self.score_thresh, self.nms_thresh, self.topk = float(score_thresh), float(nms_thresh), int(topk_candidates)
+        self.thresh = score_threshold(self.score_thresh)
+        with torch.cuda.device(self.device):
+            self.base = [self._t(base_anchors(s, (1.0,))) for s in self.sizes]
+            torch.cuda.current_stream().synchronize()
+
+    @classmethod
+    def from_state_dict(cls, sd, arch: str, num_classes=None, score_thresh: float = 0.2, nms_thresh: float = 0.6,
+                        detections_per_img: int = 100, topk_candidates: int = 1000, sizes=FCOS_SIZES, device=None,
+                        out_channels: int = 256, eps: float = 1e-5) -> "FCOS":
+        """sd under torchvision's key names: backbone.body.*, backbone.fpn.* (inner_blocks / layer_blocks 0..2 and
+        extra_blocks.p6|p7) and head.*; each part is validated with check_state_dict."""
+        from .fpn import ResNetFPN
+        if len(sizes) != len(RETINA_LEVELS) or any(len(s) != 1 for s in sizes):
+            raise WinoError(f"FCOS: {len(RETINA_LEVELS)} levels need {len(RETINA_LEVELS)} tuples of one anchor size")
+        score_threshold(score_thresh)
+        if not 1 <= int(topk_candidates) <= SELECT_MAX_ROWS // len(RETINA_LEVELS) or int(detections_per_img) < 1:
+            raise WinoError(f"FCOS: topk_candidates={topk_candidates} (the levels' candidates are sorted by one "
+                            f"select_topk of at most {SELECT_MAX_ROWS} rows), detections_per_img={detections_per_img}")
+        parts = {"backbone.": {}, "head.": {}}
+        for k, v in sd.items():
+            for prefix, part in parts.items():
+                if k.startswith(prefix):
+                    part[k[len(prefix):]] = v
+                    break
+            else:
+                raise WinoError(f"state dict: unexpected key {k!r} for FCOS")
+        classes = validate_fcos_head_state_dict(parts["head."], out_channels)
+        if num_classes is not None and int(num_classes) != classes:
+            raise WinoError(f"state dict has {classes} classes, num_classes={num_classes}")
+        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device, returned_layers=(2, 3, 4),
+                                             extra_blocks="p6p7")
+        head = FCOSHead.from_state_dict(parts["head."], out_channels, backbone.device)
+        return cls(backbone, head, sizes, detections_per_img, score_thresh, nms_thresh, topk_candidates, backbone.device)
+
+    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
+        from . import nms_workspace_bytes, select_map_workspace_bytes, select_workspace_bytes
+        N, H, W, D, dev, f32, i32 = int(N), int(H), int(W), self.detections, self.device, torch.float32, torch.int32
+        self._shape = None
+        with torch.cuda.device(dev):
+            self.backbone.prepare(N, H, W)
+            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in (*self.backbone._p, *self.backbone._extra[::2])]
+            self.head.prepare(N, level_hw)
+            cols = self.head.cols
+            self._grid = [(h, w, H // h, W // w) for h, w in level_hw]
+            if min(min(g[2:]) for g in self._grid) < 1:
+                raise WinoError(f"FCOS: a batch of {H} x {W} is smaller than its pyramid levels {level_hw}")
+            self._k = [min(self.topk, h * w * cols) for h, w in level_hw]
+            self._off = [sum(self._k[:l]) for l in range(len(self._k))]
+            K = sum(self._k)
+            empty = lambda shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
+            self._b = dict(
+                idx=empty((N, K), i32), score=empty((N, K)), count=[empty((N,), i32) for _ in level_hw], boxes=empty((N, K, 4)),
+                labels=empty((N, K), i32), order=empty((N, K), i32), sscores=empty((N, K)), count2=empty((N, 1), i32),
+                sboxes=empty((N, K, 4)), keep=empty((N, D), i32), det_count=empty((N,), i32),
+                ws=[empty(((select_map_workspace_bytes(N, h, w, cols, k) + 3) // 4,)) for (h, w), k in zip(level_hw, self._k)],
+                ws2=empty(((select_workspace_bytes(N, K, K) + 3) // 4,)), nms=empty(((nms_workspace_bytes(N, K) + 3) // 4,)))
+            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=f32, device=dev)
+        self._shape = (N, H, W)
+
+    def _detect(self, x, image_sizes, st):
+        """FCOS's stages; returns (the result dict, the pyramid, image_hw)."""
+        from . import batched_nms, fcos_decode, fcos_score_map, select_topk, select_topk_map
+        self._begin(x)
+        N, H, W = self._shape
+        hw = self._full_hw if image_sizes is None else image_sizes
+        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
+            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
+        b, K = self._b, self.head.classes
+        with torch.cuda.device(self.device):
+            feats = self.backbone(x, padded=True)
+            cls, reg = self.head([feats[name] for name in RETINA_LEVELS])
+            for l, (k, off) in enumerate(zip(self._k, self._off)):
+                fcos_score_map(cls[l], reg[l], K, FCOS_CTR_COL)
+                select_topk_map(cls[l], K, k, self.thresh, b["idx"], b["score"], b["count"][l], off, b["ws"][l])
+                fcos_decode(b["idx"], reg[l], self.base[l], hw, self._grid[l], K, k, b["boxes"], b["labels"], off)
+            scores = b["score"]                          # (the select writes 0.0 past a level's kept count)
+            order, sscores, _, sboxes = select_topk(scores, sum(self._k), boxes=b["boxes"], out_idx=b["order"],
+                                                    out_vals=b["sscores"], out_count=b["count2"], out_boxes=b["sboxes"],
+                                                    workspace=b["ws2"])
+            slabels = b["labels"].gather(1, order.long())
+            keep, count = batched_nms(sboxes, sscores, slabels, self.nms_thresh, 0.0, RETINA_NMS_SCORE_MIN, self.detections,
+                                      workspace=b["nms"], keep=b["keep"], count=b["det_count"])
+            kept = keep >= 0
+            at = keep.clamp(min=0).long()
+            out = {"boxes": sboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
+                   "scores": sscores.gather(1, at) * kept,
+                   "labels": torch.where(kept, slabels.gather(1, at).long(), torch.full_like(at, -1)), "count": count}
+        if st is not None:
+            st.update(features=feats, cls_maps=list(cls), reg_maps=list(reg), level_idx=b["idx"], level_scores=b["score"],
+                      level_count=torch.stack(b["count"]), cand_boxes=b["boxes"], cand_labels=b["labels"], cand_scores=scores,
+                      order=order, sorted_boxes=sboxes, sorted_scores=sscores, sorted_labels=slabels, det_keep=keep)
+        return out, feats, hw
+
+
 __all__ = ["BoxHead", "MaskHead", "KeypointHead", "RPN", "FasterRCNN", "MaskRCNN", "KeypointRCNN", "RetinaNetHead",
+           "FCOSHead", "FCOS", "score_threshold", "expected_fcos_head_keys", "validate_fcos_head_state_dict",
            "RetinaNet", "logit_threshold", "expected_retinanet_head_keys", "validate_retinanet_head_state_dict",
            "pack_retina_last", "split_mask_state_dict",
            "split_keypoint_state_dict", "postprocess_detections", "base_anchors", "pack_rpn_head",

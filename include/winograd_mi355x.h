@@ -68,7 +68,8 @@ extern "C" {
  * wino_aspp_prepare_hw, wino_conv3x3_grouped_plan, wino_box_decode_hw, wino_batched_nms_hw,
  * wino_mask_paste_hw, WINO_MASK_LAYOUT_*, wino_select_topk_hw, wino_roi_align_launches,
  * wino_image_transform_hw, WINO_IMAGE_*, WINO_TRANSFORM_MAX_IMAGES, wino_transform_size,
- * wino_select_topk_map_hw, wino_retina_decode_hw,
+ * wino_select_topk_map_hw, wino_retina_decode_hw, wino_groupnorm_relu_hw,
+ * wino_groupnorm_plan, WINO_GN_FORM_*, wino_fcos_score_map_hw, wino_fcos_decode_hw,
  * wino_keypoints_hw, WINO_KP_LAYOUT_*, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
@@ -1061,6 +1062,51 @@ int wino_select_topk_map_hw(const float* map, int N, int h, int w, int cols, int
 int wino_retina_decode_hw(const int* idx, int N, int k, long stride, long offset, const float* reg, int h, int w,
                           int ld_r, int A, int K, const float* base, int stride_y, int stride_x, const float* image_hw,
                           float clamp, float* boxes, int* labels, wino_stream_t s);
+
+/* ---- GroupNorm (+ ReLU) on a padded NHWC map (groupnorm.hip) ---------------------------------------
+ * wino_groupnorm_relu_hw: torch's F.group_norm(x, G, gamma, beta, eps), then ReLU when relu != 0, on in, DEVICE
+ * [N][h+2][w+2][C] fp32 (what a 3x3 layer writes), into out of the same shape.  Statistics per (image, group) over the
+ * h * w * (C / G) interior values of the group's channels, biased variance;
+ *   out = (in - mean) * (gamma / sqrt(var + eps)) + beta
+ * gamma, beta DEVICE [C].  Interior only: no byte of either ring is read or written.  out == in (in place) is allowed;
+ * any other overlap of in and out is WINO_E_ARG.  The statistics are Welford updates merged by Chan's formula in an
+ * order that is a function of the shape and the form alone (no atomics): two launches give equal bits.  A NaN or Inf
+ * element makes its own (image, group) NaN throughout and changes no bit elsewhere; the ReLU propagates NaN.
+ * Two forms: WINO_GN_FORM_WHOLE, one launch, a workgroup owns an image's pixels for a block of groups and reads them
+ * twice; WINO_GN_FORM_SPLIT, two launches, per-chunk (count, mean, M2, shift) partials in the caller's workspace, merged in
+ * chunk order by every workgroup of the second.  wino_groupnorm_plan (host only) names the form and the chunks per image
+ * for a device of `cus` CUs (chunks = 1 for the whole form); WINO_GN_FORM = whole | split forces one.
+ * The workspace is a formula, like wino_select_topk_hw's: 0 bytes for the whole form, else N * min(h * w, 128) * 4 * G * 4,
+ * enough on any device (the Python wrapper's groupnorm_workspace_bytes computes it from the plan).  workspace: 16-byte
+ * aligned, at least that; it must not overlap an operand.
+ * N >= 0 (0: WINO_OK, nothing launched), h, w >= 1, h * w < 2^31, C a multiple of 64, G a divisor of C with C / G a
+ * power of two (1 .. C), (w+2) * C < 2^32, (h+2) * (w+2) * C < 2^40 (WINO_E_SHAPE otherwise; offsets are 64-bit, a map may
+ * pass 4 GiB).  A NULL or not 16-byte-aligned pointer, an eps that is not finite and > 0, a workspace that is too small
+ * or an overlap is WINO_E_ARG.  Every check comes before the first launch.  No stream scratch: capturable as it is. */
+enum { WINO_GN_FORM_WHOLE = 1, WINO_GN_FORM_SPLIT = 2 };
+int wino_groupnorm_plan(int N, int h, int w, int C, int G, int cus, int* form, int* chunks);
+int wino_groupnorm_relu_hw(const float* in, const float* gamma, const float* beta, float* out, int N, int h, int w, int C,
+                           int G, float eps, int relu, void* workspace, size_t workspace_bytes, wino_stream_t s);
+
+/* ---- FCOS: score map and decode of the selected locations (fcos.hip) -----------------------------
+ * wino_fcos_score_map_hw: in place on the class-logit map cls, DEVICE [N][h+2][w+2][ld_c] fp32: every interior element
+ * in columns < K becomes sqrt(sigmoid(logit) * sigmoid(ctr)), ctr = column ctr_col of the same pixel of reg, DEVICE
+ * [N][h+2][w+2][ld_r].  Pad columns and both rings are neither read nor written.  A NaN logit or centerness gives a NaN
+ * score; a product that underflows in fp32 gives 0.  h, w, K >= 1, K <= ld_c, 0 <= ctr_col < ld_r, ld_c and ld_r
+ * multiples of 4, both maps within (w+2) * ld < 2^32 and (h+2) * (w+2) * ld < 2^40, N * h * w * ceil(K / 4) < 2^31 (WINO_E_SHAPE
+ * otherwise); N == 0 is WINO_OK.  NULL, misaligned or overlapping maps are WINO_E_ARG.  No scratch: capturable.
+ *
+ * wino_fcos_decode_hw: wino_retina_decode_hw's rows, outputs, limits, refusals and padding-row rule, with the
+ * anchor-free decode: (l, t, r, b) = max(columns 4a .. 4a + 3, 0) (NaN-propagating), the shifted base anchor's
+ * cx = 0.5 * (x1 + x2), cy = 0.5 * (y1 + y2), aw = x2 - x1, ah = y2 - y1, and
+ *   box = (cx - l * aw, cy - t * ah, cx + r * aw, cy + b * ah)
+ * in fp32 in this order without contraction (torchvision's BoxLinearCoder(normalize_by_size=True).decode), clipped to
+ * image_hw[i]. */
+int wino_fcos_score_map_hw(float* cls, const float* reg, int N, int h, int w, int K, int ld_c, int ld_r, int ctr_col,
+                           wino_stream_t s);
+int wino_fcos_decode_hw(const int* idx, int N, int k, long stride, long offset, const float* reg, int h, int w, int ld_r,
+                        int A, int K, const float* base, int stride_y, int stride_x, const float* image_hw, float* boxes,
+                        int* labels, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
