@@ -1160,15 +1160,9 @@ def select_topk_map(scores_map, cols: int, k: int, score_thresh=None, out_idx=No
     return idx, vals, count
 
 
-def retina_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=None, out_labels=None, out_offset: int = 0,
-                  clamp: float = BBOX_XFORM_CLIP):
-    """RetinaNet's decode of the selected anchors only, in one HIP launch (retina.hip).  idx [N][total] int32 as
-    select_topk_map writes it with cols = A * K; this call reads rows [:, out_offset : out_offset + k] (k defaults to the
-    rest of the row): anchor = idx // K, label = idx % K.  reg_map [N][h+2][w+2][ld_r] float32, the regression head's
-    padded output with the deltas of anchor a at columns 4a .. 4a + 3; base [A][4]; image_hw [N][2];
-    grid = (h, w, stride_y, stride_x).  The box is box_decode's in grid mode at the same anchor, bit for bit (weights
-    (1, 1, 1, 1), clamp, clipped to the image).  Returns (boxes [N][total][4], labels [N][total] int32), of which the
-    same rows are written; rows with idx < 0 get a zero box and label -1.  No scratch: capturable without a prepare."""
+def _decode_rows(entry: str, idx, reg_map, base, image_hw, grid, K, k, out_boxes, out_labels, out_offset, clamp=None):
+    """retina_decode's and fcos_decode's checks and launch: entry point wino_`entry`_hw, messages under `entry`; `clamp` is
+    passed on only where it is given (the FCOS entry point takes none)."""
     ix = idx
     if not isinstance(ix, torch.Tensor) or not ix.is_cuda or ix.dtype != torch.int32 or not ix.is_contiguous() or ix.dim() != 2:
         raise WinoError("idx must be a contiguous int32 CUDA(HIP) tensor [N][total]")
@@ -1181,15 +1175,27 @@ def retina_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=
         raise WinoError("base must be [A][4]")
     k = total - off if k is None else int(k)
     if off < 0 or k < 0 or off + k > total:
-        raise WinoError(f"retina_decode: rows {off} .. {off + k} of {total}")
+        raise WinoError(f"{entry}: rows {off} .. {off + k} of {total}")
     boxes = _output(out_boxes, (N, total, 4), ix.device, "out_boxes")
     labels = _int32(out_labels, (N, total), ix.device, "out_labels")
     _on_current_device(ix, reg, anc, hw, boxes, labels)
     ptr = lambda t: t.data_ptr() or None
-    _check(lib().wino_retina_decode_hw(ptr(ix), N, k, total, off, ptr(reg), gh, gw, int(reg.shape[3]), int(anc.shape[0]),
-                                       int(K), ptr(anc), sy, sx, ptr(hw), float(clamp), ptr(boxes), ptr(labels), _stream()),
-           "wino_retina_decode_hw")
+    _check(getattr(lib(), f"wino_{entry}_hw")(ptr(ix), N, k, total, off, ptr(reg), gh, gw, int(reg.shape[3]), int(anc.shape[0]),
+                                              int(K), ptr(anc), sy, sx, ptr(hw), *(() if clamp is None else (float(clamp),)),
+                                              ptr(boxes), ptr(labels), _stream()), f"wino_{entry}_hw")
     return boxes, labels
+
+
+def retina_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=None, out_labels=None, out_offset: int = 0,
+                  clamp: float = BBOX_XFORM_CLIP):
+    """RetinaNet's decode of the selected anchors only, in one HIP launch (retina.hip).  idx [N][total] int32 as
+    select_topk_map writes it with cols = A * K; this call reads rows [:, out_offset : out_offset + k] (k defaults to the
+    rest of the row): anchor = idx // K, label = idx % K.  reg_map [N][h+2][w+2][ld_r] float32, the regression head's
+    padded output with the deltas of anchor a at columns 4a .. 4a + 3; base [A][4]; image_hw [N][2];
+    grid = (h, w, stride_y, stride_x).  The box is box_decode's in grid mode at the same anchor, bit for bit (weights
+    (1, 1, 1, 1), clamp, clipped to the image).  Returns (boxes [N][total][4], labels [N][total] int32), of which the
+    same rows are written; rows with idx < 0 get a zero box and label -1.  No scratch: capturable without a prepare."""
+    return _decode_rows("retina_decode", idx, reg_map, base, image_hw, grid, K, k, out_boxes, out_labels, out_offset, clamp)
 
 
 GN_FORMS = {1: "whole", 2: "split"}   # WINO_GN_FORM_*
@@ -1257,27 +1263,7 @@ def fcos_decode(idx, reg_map, base, image_hw, grid, K: int, k=None, out_boxes=No
     outputs, with the anchor-free box of torchvision's BoxLinearCoder(normalize_by_size=True): (l, t, r, b) = relu of
     columns 4a .. 4a + 3 of reg_map, box = (cx - l w, cy - t h, cx + r w, cy + b h) of the shifted base anchor, clipped to
     the image.  Rows with idx < 0 get a zero box and label -1.  No scratch: capturable without a prepare."""
-    ix = idx
-    if not isinstance(ix, torch.Tensor) or not ix.is_cuda or ix.dtype != torch.int32 or not ix.is_contiguous() or ix.dim() != 2:
-        raise WinoError("idx must be a contiguous int32 CUDA(HIP) tensor [N][total]")
-    reg, anc, hw = _dev(reg_map, "reg_map"), _dev(base, "base"), _dev(image_hw, "image_hw")
-    N, total, off = int(ix.shape[0]), int(ix.shape[1]), int(out_offset)
-    gh, gw, sy, sx = (int(v) for v in grid)
-    if reg.dim() != 4 or tuple(reg.shape[:3]) != (N, gh + 2, gw + 2) or tuple(hw.shape) != (N, 2):
-        raise WinoError(f"reg_map must be [{N}][{gh + 2}][{gw + 2}][ld_r] and image_hw [{N}][2]")
-    if anc.dim() != 2 or int(anc.shape[1]) != 4:
-        raise WinoError("base must be [A][4]")
-    k = total - off if k is None else int(k)
-    if off < 0 or k < 0 or off + k > total:
-        raise WinoError(f"fcos_decode: rows {off} .. {off + k} of {total}")
-    boxes = _output(out_boxes, (N, total, 4), ix.device, "out_boxes")
-    labels = _int32(out_labels, (N, total), ix.device, "out_labels")
-    _on_current_device(ix, reg, anc, hw, boxes, labels)
-    ptr = lambda t: t.data_ptr() or None
-    _check(lib().wino_fcos_decode_hw(ptr(ix), N, k, total, off, ptr(reg), gh, gw, int(reg.shape[3]), int(anc.shape[0]),
-                                     int(K), ptr(anc), sy, sx, ptr(hw), ptr(boxes), ptr(labels), _stream()),
-           "wino_fcos_decode_hw")
-    return boxes, labels
+    return _decode_rows("fcos_decode", idx, reg_map, base, image_hw, grid, K, k, out_boxes, out_labels, out_offset)
 
 
 MASK_LAYOUTS = {"planes": 0, "gemm_rows": 1}   # WINO_MASK_LAYOUT_*

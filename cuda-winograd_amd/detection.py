@@ -87,12 +87,21 @@ None in ``forward``); ``predict_outputs(tf, Hmax, Wmax)`` adds the branch's entr
 is set when the last branch has prepared.  ``to_lists`` slices whichever output keys the dict holds.  Both heads' 3x3
 chains are ``_ConvTower``: the filter packing, the ``pooled_padded`` checks, the zero-ring buffers and the launch loop.
 
-``RetinaNet.from_state_dict(sd, arch)`` (``backbone.*`` with ``fpn.extra_blocks.p6|p7``, ``head.*``) is the one-stage
-detector on the same plumbing (``_Detector``: ``prepare`` / ``forward`` / ``predict`` / ``prepare_images`` /
-``to_lists`` are shared with ``FasterRCNN``, a detector gives ``_prepare`` and ``_detect``): ResNetFPN(returned_layers =
-(2, 3, 4), "p6p7") -> ``RetinaNetHead`` -> per level ``select_topk_map`` on the class logit map in place and
-``retina_decode`` of the selected anchors -> one ``select_topk`` by score -> ``batched_nms`` by label; see its docstring
-for the two named deviations.
+How a dense detector plugs in.  ``RetinaNet`` and ``FCOS`` (``from_state_dict(sd, arch)``: ``backbone.*`` with
+``fpn.extra_blocks.p6|p7``, ``head.*``) are the one-stage detectors on the same plumbing (``_Detector``: ``prepare`` /
+``forward`` / ``predict`` / ``prepare_images`` / ``to_lists`` are shared with ``FasterRCNN``).  ``_DenseDetector`` holds
+their only ``_prepare`` and ``_detect``: ResNetFPN(returned_layers = (2, 3, 4), "p6p7") -> the head -> per level
+``select_topk_map`` on the class map in place and the decode of the selected rows -> one ``select_topk`` by score with
+the boxes as payload -> the label gather -> ``batched_nms`` by label -> the padded result and the ``stages`` dict; and
+``_load_parts``, what the two ``from_state_dict`` share: the argument checks, the state-dict split, the class-count check
+and the backbone and head.  ``_DenseHead`` holds the heads' only ``prepare`` and ``forward``: per level the ping-pong
+pair, the two output maps and the level x tower loop, with ``groupnorm_relu`` in place after each tower convolution where
+the tower has norms.  A head gives its name for messages, ``cols`` / ``ld_cls`` / ``ld_reg`` and a ``_pack`` that lists each
+tower's keys.  A model gives its name, head class and validator, its threshold function (``logit_threshold`` /
+``score_threshold``), its base anchors, the stage key of the selected values (``level_logits`` / ``level_scores``),
+``ctr_col`` (FCOS: ``fcos_score_map`` runs on the class map before the select), ``_decode`` (``retina_decode`` /
+``fcos_decode``) and ``_scores`` (the selected values to candidate scores: the sigmoid where a row is kept, or the values
+themselves).  See the two classes' docstrings for the named deviations.
 
 Not built: torchvision's ``fixed_size`` / ``_skip_resize`` options, training targets and the v2 heads.
 
@@ -765,14 +774,7 @@ class FasterRCNN(_Detector):
         RPN's filter_proposals and postprocess_detections alike (see the module docstring)."""
         from .fpn import ResNetFPN
         _check_select(select)
-        parts = {"backbone.": {}, "rpn.": {}, "roi_heads.": {}}
-        for k, v in sd.items():
-            for prefix, part in parts.items():
-                if k.startswith(prefix):
-                    part[k[len(prefix):]] = v
-                    break
-            else:
-                raise WinoError(f"state dict: unexpected key {k!r} for Faster R-CNN")
+        parts = _split_by_prefix(sd, ("backbone.", "rpn.", "roi_heads."), "Faster R-CNN")
         backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device)
         rpn = RPN.from_state_dict(parts["rpn."], out_channels, sizes, ratios, rpn_pre_nms_top_n, rpn_post_nms_top_n,
                                   rpn_nms_thresh, rpn_score_thresh, 1e-3, backbone.device, select=select)
@@ -838,6 +840,19 @@ def _split_state_dict(sd, prefixes):
         else:
             rest[k] = v
     return rest, part
+
+
+def _split_by_prefix(sd, prefixes, name: str):
+    """{prefix: the keys of `sd` below it} for each of `prefixes`; a key below none of them raises, naming the model."""
+    parts = {prefix: {} for prefix in prefixes}
+    for k, v in sd.items():
+        for prefix, part in parts.items():
+            if k.startswith(prefix):
+                part[k[len(prefix):]] = v
+                break
+        else:
+            raise WinoError(f"state dict: unexpected key {k!r} for {name}")
+    return parts
 
 
 class _RoIBranch:
@@ -1148,11 +1163,191 @@ class KeypointRCNN(FasterRCNN):
         return m
 
 
-# ---- RetinaNet --------------------------------------------------------------------------------------------------------------
-RETINA_SIZES = tuple((x, int(x * 2 ** (1.0 / 3)), int(x * 2 ** (2.0 / 3))) for x in (32, 64, 128, 256, 512))
+# ---- the dense detectors: what RetinaNet and FCOS share -------------------------------------------------------------------------
 RETINA_LEVELS = ("0", "1", "2", "p6", "p7")
 RETINA_CONVS = 4
 RETINA_NMS_SCORE_MIN = 1.1754943508222875e-38   # FLT_MIN: what a padding row's score 0.0 fails in batched_nms
+FCOS_GROUPS = 32     # torchvision's GroupNorm(32, in_channels) between FCOS's tower convolutions
+
+
+class _DenseHead(_ConvTower):
+    """What RetinaNetHead and FCOSHead share: a classification and a regression tower of RETINA_CONVS 3x3 convolutions and
+    a last 3x3 without ReLU, run per level with the same packed weights on every level, into padded maps of the head's.
+    A tower without norms runs its convolutions with ReLU; one with norms runs them without and follows each with
+    groupnorm_relu in place.  A subclass gives `name` (for messages), `cols`, `ld_cls`, `ld_reg` and a `_pack(sd, eps)`
+    that hands `_pack_towers` the keys of its two towers."""
+
+    def __init__(self, in_channels: int, classes: int, device):
+        super().__init__(device)
+        self.in_channels, self.classes = int(in_channels), int(classes)
+        self.widths = [self.in_channels] * RETINA_CONVS
+
+    def _pack_towers(self, sd, towers) -> None:
+        """towers: per tower (the stems of its convolutions, the stems of their GroupNorms or None, the stems of the last
+        convolutions, concatenated along K).  Sets `towers` = [(convs [(U, bias)], norms [(gamma, beta)] or None, U and
+        bias of the last convolution, its padded width)]."""
+        self.towers = []
+        for stems, norm_stems, last in towers:
+            self._pack_tower(sd, stems)
+            norms = norm_stems and [(self._t(sd[f"{s}.weight"]), self._t(sd[f"{s}.bias"])) for s in norm_stems]
+            wl, bl = pack_retina_last(torch.cat([sd[f"{s}.weight"] for s in last]), torch.cat([sd[f"{s}.bias"] for s in last]))
+            self.towers.append((self.convs, norms, filter_transform_f2(self._t(wl)), self._t(bl), int(wl.shape[0])))
+        del self.convs
+        self._ones = torch.ones(max(self.in_channels, self.ld_cls, self.ld_reg), dtype=torch.float32, device=self.device)
+        torch.cuda.current_stream().synchronize()
+
+    def prepare(self, N: int, level_hw) -> None:
+        """Allocate, per level of `level_hw` [(h, w)], the two ping-pong tensors both towers share, the two output maps
+        and, for a head with norms, the GroupNorm workspace, and reserve the stream scratch of every convolution on the
+        current stream.  Call it before capturing a forward into a graph."""
+        N, C, dev, f32 = int(N), self.in_channels, self.device, torch.float32
+        level_hw = tuple((int(h), int(w)) for h, w in level_hw)
+        if N < 1 or not level_hw or min(min(hw) for hw in level_hw) < 1:
+            raise WinoError(f"{self.name}: N={N} images, levels {level_hw}")
+        with torch.cuda.device(dev):
+            zeros = lambda h, w, c: torch.zeros((N, h + 2, w + 2, c), dtype=f32, device=dev)
+            self._pp = [(zeros(h, w, C), zeros(h, w, C)) for h, w in level_hw]
+            self._cls = [zeros(h, w, self.ld_cls) for h, w in level_hw]
+            self._reg = [zeros(h, w, self.ld_reg) for h, w in level_hw]
+            if self.towers[0][1] is not None:
+                # the split form's size whatever the plan says now: a WINO_GN_FORM set after prepare finds room
+                self._gn_ws = [torch.empty((N * min(h * w, 128) * 4 * FCOS_GROUPS,), dtype=f32, device=dev) for h, w in level_hw]
+            for h, w in level_hw:
+                for k in (C, self.ld_cls, self.ld_reg):
+                    conv3x3_prepare(N, C, k, h, w)
+        self._shape = (N, level_hw)
+
+    def forward(self, maps):
+        """maps: the levels' padded features [N][h+2][w+2][in_channels] (zero rings; they are not written).  Returns
+        (class maps, regression maps), one per level: tensors of the head's, valid until the next forward.  New shapes
+        re-run prepare()."""
+        from . import groupnorm_relu   # looked up per call: a tool that times the convolutions alone replaces it
+        maps, C = list(maps), self.in_channels
+        for x in maps:
+            if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or min(x.shape[1:3]) < 3:
+                raise WinoError(f"{self.name}: every level must be [N][h+2][w+2][{C}]")
+            if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
+                raise WinoError(f"{self.name}: every level must be contiguous float32 on {self.device}")
+        shape = (int(maps[0].shape[0]), tuple((int(x.shape[1]) - 2, int(x.shape[2]) - 2) for x in maps))
+        if any(int(x.shape[0]) != shape[0] for x in maps):
+            raise WinoError(f"{self.name}: the levels differ in N")
+        if shape != self._shape:
+            self.prepare(*shape)
+        with torch.cuda.device(self.device):
+            for l, x0 in enumerate(maps):
+                for (convs, norms, U, bias, kp), outs in zip(self.towers, (self._cls, self._reg)):
+                    x = x0
+                    for i, (Ui, bi) in enumerate(convs):
+                        x = conv3x3_bn_relu(x, Ui, bi, self._ones[:C], relu=norms is None, out=self._pp[l][i % 2])
+                        if norms is not None:
+                            groupnorm_relu(x, *norms[i], FCOS_GROUPS, out=x, workspace=self._gn_ws[l])
+                    conv3x3_bn_relu(x, U, bias, self._ones[:kp], relu=False, out=outs[l])
+        return self._cls, self._reg
+
+
+class _DenseDetector(_Detector):
+    """What RetinaNet and FCOS share: ResNetFPN(returned_layers = (2, 3, 4), extra_blocks = "p6p7", padded) -> the head ->
+    per level select_topk_map on the class map in place and the model's decode of the selected rows -> one select_topk over
+    the levels' candidates by score with the boxes as payload -> batched_nms with groups = label -> the padded result.
+    A model gives `name`, `head_cls` and `validate_head`, `threshold` (score_thresh -> what select_topk_map compares
+    with, kept as `thresh`), `values_key` (the stage key of the selected values), `ctr_col` (the regression map's
+    centerness column where fcos_score_map runs before the select, else None), `_decode` and `_scores`."""
+    ctr_col = None
+
+    def __init__(self, backbone, head, base, detections, score_thresh, nms_thresh, topk_candidates, device):
+        """base: the base anchors [A][4] of each level, host tensors."""
+        super().__init__(device, detections)
+        self.backbone, self.head = backbone, head
+        self.score_thresh, self.nms_thresh, self.topk = float(score_thresh), float(nms_thresh), int(topk_candidates)
+        self.thresh = self.threshold(self.score_thresh)
+        with torch.cuda.device(self.device):
+            self.base = [self._t(b) for b in base]
+            torch.cuda.current_stream().synchronize()
+
+    @classmethod
+    def _load_parts(cls, sd, arch, num_classes, sizes_ok: bool, sizes_need: str, score_thresh, topk_candidates,
+                    detections_per_img, device, out_channels, eps, *head_args):
+        """from_state_dict's shared part: the argument checks, the state dict split into `backbone.` and `head.` and
+        validated, and (the backbone, the head) loaded; `head_args` go between out_channels and the device."""
+        from .fpn import ResNetFPN
+        levels = len(RETINA_LEVELS)
+        if not sizes_ok:
+            raise WinoError(f"{cls.name}: {levels} levels need {levels} {sizes_need}")
+        cls.threshold(score_thresh)
+        if not 1 <= int(topk_candidates) <= SELECT_MAX_ROWS // levels or int(detections_per_img) < 1:
+            raise WinoError(f"{cls.name}: topk_candidates={topk_candidates} (the levels' candidates are sorted by one "
+                            f"select_topk of at most {SELECT_MAX_ROWS} rows), detections_per_img={detections_per_img}")
+        parts = _split_by_prefix(sd, ("backbone.", "head."), cls.name)
+        classes = cls.validate_head(parts["head."], out_channels, *head_args)
+        if num_classes is not None and int(num_classes) != classes:
+            raise WinoError(f"state dict has {classes} classes, num_classes={num_classes}")
+        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device, returned_layers=(2, 3, 4),
+                                             extra_blocks="p6p7")
+        return backbone, cls.head_cls.from_state_dict(parts["head."], out_channels, *head_args, backbone.device)
+
+    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
+        from . import nms_workspace_bytes, select_map_workspace_bytes, select_workspace_bytes
+        N, H, W, D, dev, f32, i32 = int(N), int(H), int(W), self.detections, self.device, torch.float32, torch.int32
+        self._shape = None
+        with torch.cuda.device(dev):
+            self.backbone.prepare(N, H, W)
+            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in (*self.backbone._p, *self.backbone._extra[::2])]
+            self.head.prepare(N, level_hw)
+            cols = self.head.cols
+            self._grid = [(h, w, H // h, W // w) for h, w in level_hw]
+            if min(min(g[2:]) for g in self._grid) < 1:
+                raise WinoError(f"{self.name}: a batch of {H} x {W} is smaller than its pyramid levels {level_hw}")
+            self._k = [min(self.topk, h * w * cols) for h, w in level_hw]
+            self._off = [sum(self._k[:l]) for l in range(len(self._k))]
+            K = sum(self._k)
+            empty = lambda shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
+            self._b = dict(
+                idx=empty((N, K), i32), vals=empty((N, K)), count=[empty((N,), i32) for _ in level_hw], boxes=empty((N, K, 4)),
+                labels=empty((N, K), i32), order=empty((N, K), i32), sscores=empty((N, K)), count2=empty((N, 1), i32),
+                sboxes=empty((N, K, 4)), keep=empty((N, D), i32), det_count=empty((N,), i32),
+                ws=[empty(((select_map_workspace_bytes(N, h, w, cols, k) + 3) // 4,)) for (h, w), k in zip(level_hw, self._k)],
+                ws2=empty(((select_workspace_bytes(N, K, K) + 3) // 4,)), nms=empty(((nms_workspace_bytes(N, K) + 3) // 4,)))
+            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=f32, device=dev)
+        self._shape = (N, H, W)
+
+    def _detect(self, x, image_sizes, st):
+        """The dense detector's stages; returns (the result dict, the pyramid, image_hw)."""
+        from . import batched_nms, fcos_score_map, select_topk, select_topk_map
+        self._begin(x)
+        N, H, W = self._shape
+        hw = self._full_hw if image_sizes is None else image_sizes
+        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
+            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
+        b, K, cols = self._b, self.head.classes, self.head.cols
+        with torch.cuda.device(self.device):
+            feats = self.backbone(x, padded=True)
+            cls, reg = self.head([feats[name] for name in RETINA_LEVELS])
+            for l, (k, off) in enumerate(zip(self._k, self._off)):
+                if self.ctr_col is not None:
+                    fcos_score_map(cls[l], reg[l], K, self.ctr_col)
+                select_topk_map(cls[l], cols, k, self.thresh, b["idx"], b["vals"], b["count"][l], off, b["ws"][l])
+                self._decode(b["idx"], reg[l], self.base[l], hw, self._grid[l], K, k, b["boxes"], b["labels"], off)
+            scores = self._scores(b["idx"], b["vals"])
+            order, sscores, _, sboxes = select_topk(scores, sum(self._k), boxes=b["boxes"], out_idx=b["order"],
+                                                    out_vals=b["sscores"], out_count=b["count2"], out_boxes=b["sboxes"],
+                                                    workspace=b["ws2"])
+            slabels = b["labels"].gather(1, order.long())
+            keep, count = batched_nms(sboxes, sscores, slabels, self.nms_thresh, 0.0, RETINA_NMS_SCORE_MIN, self.detections,
+                                      workspace=b["nms"], keep=b["keep"], count=b["det_count"])
+            kept = keep >= 0
+            at = keep.clamp(min=0).long()
+            out = {"boxes": sboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
+                   "scores": sscores.gather(1, at) * kept,
+                   "labels": torch.where(kept, slabels.gather(1, at).long(), torch.full_like(at, -1)), "count": count}
+        if st is not None:
+            st.update({self.values_key: b["vals"]}, features=feats, cls_maps=list(cls), reg_maps=list(reg), level_idx=b["idx"],
+                      level_count=torch.stack(b["count"]), cand_boxes=b["boxes"], cand_labels=b["labels"], cand_scores=scores,
+                      order=order, sorted_boxes=sboxes, sorted_scores=sscores, sorted_labels=slabels, det_keep=keep)
+        return out, feats, hw
+
+
+# ---- RetinaNet --------------------------------------------------------------------------------------------------------------
+RETINA_SIZES = tuple((x, int(x * 2 ** (1.0 / 3)), int(x * 2 ** (2.0 / 3))) for x in (32, 64, 128, 256, 512))
 
 
 def logit_threshold(score_thresh: float) -> float:
@@ -1218,17 +1413,18 @@ def pack_retina_last(w: torch.Tensor, b: torch.Tensor):
     return wp, bp
 
 
-class RetinaNetHead(_ConvTower):
+class RetinaNetHead(_DenseHead):
     """torchvision's RetinaNetHead (classification and regression towers, no norm layer) on the Winograd 3x3, inference
     only: per level four conv3x3 + ReLU and one conv3x3 without, per tower, with the same packed weights on every level.
     The outputs stay the padded maps the kernels write: class logits [N][h+2][w+2][pad64(A classes)] with channel
     a * classes + k, box regression [N][h+2][w+2][pad64(4 A)] with anchor a's deltas at 4a .. 4a + 3 -- what
     select_topk_map and retina_decode read in place."""
 
+    name = "RetinaNet head"
+
     def __init__(self, in_channels: int, A: int, classes: int, device):
-        super().__init__(device)
-        self.in_channels, self.A, self.classes = int(in_channels), int(A), int(classes)
-        self.widths = [self.in_channels] * RETINA_CONVS
+        super().__init__(in_channels, classes, device)
+        self.A = int(A)
         self.cols, self.ld_cls, self.ld_reg = self.A * self.classes, _pad64(self.A * self.classes), _pad64(4 * self.A)
 
     @classmethod
@@ -1238,59 +1434,11 @@ class RetinaNetHead(_ConvTower):
         return cls._load(sd, None, device, in_channels, A, classes)
 
     def _pack(self, sd, eps):
-        self.towers = []   # (the four (U, bias) of the tower, U and bias of its last convolution, its padded width)
-        for head, last in (("classification_head", "cls_logits"), ("regression_head", "bbox_reg")):
-            self._pack_tower(sd, [_retina_conv(sd, head, i) for i in range(RETINA_CONVS)])
-            wl, bl = pack_retina_last(sd[f"{head}.{last}.weight"], sd[f"{head}.{last}.bias"])
-            self.towers.append((self.convs, filter_transform_f2(self._t(wl)), self._t(bl), int(wl.shape[0])))
-        del self.convs
-        self._ones = torch.ones(max(self.in_channels, self.ld_cls, self.ld_reg), dtype=torch.float32, device=self.device)
-        torch.cuda.current_stream().synchronize()
-
-    def prepare(self, N: int, level_hw) -> None:
-        """Allocate, per level of `level_hw` [(h, w)], the two ping-pong tensors both towers share and the two output
-        maps, and reserve the stream scratch of every launch on the current stream.  Call it before capturing a forward
-        into a graph."""
-        N, C, dev, f32 = int(N), self.in_channels, self.device, torch.float32
-        level_hw = tuple((int(h), int(w)) for h, w in level_hw)
-        if N < 1 or not level_hw or min(min(hw) for hw in level_hw) < 1:
-            raise WinoError(f"RetinaNet head: N={N} images, levels {level_hw}")
-        with torch.cuda.device(dev):
-            zeros = lambda h, w, c: torch.zeros((N, h + 2, w + 2, c), dtype=f32, device=dev)
-            self._pp = [(zeros(h, w, C), zeros(h, w, C)) for h, w in level_hw]
-            self._cls = [zeros(h, w, self.ld_cls) for h, w in level_hw]
-            self._reg = [zeros(h, w, self.ld_reg) for h, w in level_hw]
-            for h, w in level_hw:
-                for k in (C, self.ld_cls, self.ld_reg):
-                    conv3x3_prepare(N, C, k, h, w)
-        self._shape = (N, level_hw)
-
-    def forward(self, maps):
-        """maps: the levels' padded features [N][h+2][w+2][in_channels] (zero rings; they are not written).  Returns
-        (class logit maps, box regression maps), one per level: tensors of the head's, valid until the next forward.
-        New shapes re-run prepare()."""
-        maps, C = list(maps), self.in_channels
-        for x in maps:
-            if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or min(x.shape[1:3]) < 3:
-                raise WinoError(f"RetinaNet head: every level must be [N][h+2][w+2][{C}]")
-            if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
-                raise WinoError(f"RetinaNet head: every level must be contiguous float32 on {self.device}")
-        shape = (int(maps[0].shape[0]), tuple((int(x.shape[1]) - 2, int(x.shape[2]) - 2) for x in maps))
-        if any(int(x.shape[0]) != shape[0] for x in maps):
-            raise WinoError("RetinaNet head: the levels differ in N")
-        if shape != self._shape:
-            self.prepare(*shape)
-        with torch.cuda.device(self.device):
-            for l, x0 in enumerate(maps):
-                for (convs, U, bias, kp), outs in zip(self.towers, (self._cls, self._reg)):
-                    x = x0
-                    for i, (Ui, bi) in enumerate(convs):
-                        x = conv3x3_bn_relu(x, Ui, bi, self._ones[:C], relu=True, out=self._pp[l][i % 2])
-                    conv3x3_bn_relu(x, U, bias, self._ones[:kp], relu=False, out=outs[l])
-        return self._cls, self._reg
+        self._pack_towers(sd, [([_retina_conv(sd, head, i) for i in range(RETINA_CONVS)], None, [f"{head}.{last}"])
+                               for head, last in (("classification_head", "cls_logits"), ("regression_head", "bbox_reg"))])
 
 
-class RetinaNet(_Detector):
+class RetinaNet(_DenseDetector):
     """torchvision's retinanet_resnet50_fpn at test time on the library's kernels: ResNetFPN(returned_layers = (2, 3, 4),
     extra_blocks = "p6p7", padded) -> RetinaNetHead -> per level select_topk_map on the class logit map in place and
     retina_decode of the selected anchors -> one select_topk over the levels' candidates by score with the boxes as
@@ -1307,15 +1455,13 @@ class RetinaNet(_Detector):
         unspecified), and so does the order in which equal scores enter the NMS.
     Not built: the v2 heads (they need P6 from C5 beside the GroupNorm kernel FCOSHead runs), SSD."""
 
+    name, head_cls, values_key = "RetinaNet", RetinaNetHead, "level_logits"
+    validate_head, threshold = staticmethod(validate_retinanet_head_state_dict), staticmethod(logit_threshold)
+
     def __init__(self, backbone, head, sizes, ratios, detections, score_thresh, nms_thresh, topk_candidates, device):
-        super().__init__(device, detections)
-        self.backbone, self.head = backbone, head
         self.sizes, self.ratios = tuple(tuple(s) for s in sizes), tuple(ratios)
-        self.score_thresh, self.nms_thresh, self.topk = float(score_thresh), float(nms_thresh), int(topk_candidates)
-        self.logit_thresh = logit_threshold(self.score_thresh)
-        with torch.cuda.device(self.device):
-            self.base = [self._t(base_anchors(s, self.ratios)) for s in self.sizes]
-            torch.cuda.current_stream().synchronize()
+        super().__init__(backbone, head, [base_anchors(s, self.ratios) for s in self.sizes], detections, score_thresh,
+                         nms_thresh, topk_candidates, device)
 
     @classmethod
     def from_state_dict(cls, sd, arch: str, num_classes=None, score_thresh: float = 0.05, nms_thresh: float = 0.5,
@@ -1323,93 +1469,23 @@ class RetinaNet(_Detector):
                         device=None, out_channels: int = 256, eps: float = 1e-5) -> "RetinaNet":
         """sd under torchvision's key names: backbone.body.*, backbone.fpn.* (inner_blocks / layer_blocks 0..2 and
         extra_blocks.p6|p7) and head.*; each part is validated with check_state_dict."""
-        from .fpn import ResNetFPN
-        if len(sizes) != len(RETINA_LEVELS) or len({len(s) for s in sizes}) != 1:
-            raise WinoError(f"RetinaNet: {len(RETINA_LEVELS)} levels need {len(RETINA_LEVELS)} size tuples of one length")
-        logit_threshold(score_thresh)
-        if not 1 <= int(topk_candidates) <= SELECT_MAX_ROWS // len(RETINA_LEVELS) or int(detections_per_img) < 1:
-            raise WinoError(f"RetinaNet: topk_candidates={topk_candidates} (the levels' candidates are sorted by one "
-                            f"select_topk of at most {SELECT_MAX_ROWS} rows), detections_per_img={detections_per_img}")
-        parts = {"backbone.": {}, "head.": {}}
-        for k, v in sd.items():
-            for prefix, part in parts.items():
-                if k.startswith(prefix):
-                    part[k[len(prefix):]] = v
-                    break
-            else:
-                raise WinoError(f"state dict: unexpected key {k!r} for RetinaNet")
-        A = len(sizes[0]) * len(ratios)
-        classes = validate_retinanet_head_state_dict(parts["head."], out_channels, A)
-        if num_classes is not None and int(num_classes) != classes:
-            raise WinoError(f"state dict has {classes} classes, num_classes={num_classes}")
-        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device, returned_layers=(2, 3, 4),
-                                             extra_blocks="p6p7")
-        head = RetinaNetHead.from_state_dict(parts["head."], out_channels, A, backbone.device)
+        ok = len(sizes) == len(RETINA_LEVELS) and len({len(s) for s in sizes}) == 1
+        backbone, head = cls._load_parts(sd, arch, num_classes, ok, "size tuples of one length", score_thresh,
+                                         topk_candidates, detections_per_img, device, out_channels, eps,
+                                         len(sizes[0]) * len(ratios) if ok else 0)
         return cls(backbone, head, sizes, ratios, detections_per_img, score_thresh, nms_thresh, topk_candidates,
                    backbone.device)
 
-    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
-        from . import nms_workspace_bytes, select_map_workspace_bytes, select_workspace_bytes
-        N, H, W, D, dev, f32, i32 = int(N), int(H), int(W), self.detections, self.device, torch.float32, torch.int32
-        self._shape = None
-        with torch.cuda.device(dev):
-            self.backbone.prepare(N, H, W)
-            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in (*self.backbone._p, *self.backbone._extra[::2])]
-            self.head.prepare(N, level_hw)
-            cols = self.head.cols
-            self._grid = [(h, w, H // h, W // w) for h, w in level_hw]
-            if min(min(g[2:]) for g in self._grid) < 1:
-                raise WinoError(f"RetinaNet: a batch of {H} x {W} is smaller than its pyramid levels {level_hw}")
-            self._k = [min(self.topk, h * w * cols) for h, w in level_hw]
-            self._off = [sum(self._k[:l]) for l in range(len(self._k))]
-            K = sum(self._k)
-            empty = lambda shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
-            self._b = dict(
-                idx=empty((N, K), i32), logit=empty((N, K)), count=[empty((N,), i32) for _ in level_hw], boxes=empty((N, K, 4)),
-                labels=empty((N, K), i32), order=empty((N, K), i32), sscores=empty((N, K)), count2=empty((N, 1), i32),
-                sboxes=empty((N, K, 4)), keep=empty((N, D), i32), det_count=empty((N,), i32),
-                ws=[empty(((select_map_workspace_bytes(N, h, w, cols, k) + 3) // 4,)) for (h, w), k in zip(level_hw, self._k)],
-                ws2=empty(((select_workspace_bytes(N, K, K) + 3) // 4,)), nms=empty(((nms_workspace_bytes(N, K) + 3) // 4,)))
-            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=f32, device=dev)
-        self._shape = (N, H, W)
+    def _decode(self, *operands):
+        from . import retina_decode
+        retina_decode(*operands)
 
-    def _detect(self, x, image_sizes, st):
-        """RetinaNet's stages; returns (the result dict, the pyramid, image_hw)."""
-        from . import batched_nms, retina_decode, select_topk, select_topk_map
-        self._begin(x)
-        N, H, W = self._shape
-        hw = self._full_hw if image_sizes is None else image_sizes
-        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
-            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
-        b, K, cols = self._b, self.head.classes, self.head.cols
-        with torch.cuda.device(self.device):
-            feats = self.backbone(x, padded=True)
-            cls, reg = self.head([feats[name] for name in RETINA_LEVELS])
-            for l, (k, off) in enumerate(zip(self._k, self._off)):
-                select_topk_map(cls[l], cols, k, self.logit_thresh, b["idx"], b["logit"], b["count"][l], off, b["ws"][l])
-                retina_decode(b["idx"], reg[l], self.base[l], hw, self._grid[l], K, k, b["boxes"], b["labels"], off)
-            scores = torch.where(b["idx"] >= 0, torch.sigmoid(b["logit"]), torch.zeros_like(b["logit"]))
-            order, sscores, _, sboxes = select_topk(scores, sum(self._k), boxes=b["boxes"], out_idx=b["order"],
-                                                    out_vals=b["sscores"], out_count=b["count2"], out_boxes=b["sboxes"],
-                                                    workspace=b["ws2"])
-            slabels = b["labels"].gather(1, order.long())
-            keep, count = batched_nms(sboxes, sscores, slabels, self.nms_thresh, 0.0, RETINA_NMS_SCORE_MIN, self.detections,
-                                      workspace=b["nms"], keep=b["keep"], count=b["det_count"])
-            kept = keep >= 0
-            at = keep.clamp(min=0).long()
-            out = {"boxes": sboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
-                   "scores": sscores.gather(1, at) * kept,
-                   "labels": torch.where(kept, slabels.gather(1, at).long(), torch.full_like(at, -1)), "count": count}
-        if st is not None:
-            st.update(features=feats, cls_maps=list(cls), reg_maps=list(reg), level_idx=b["idx"], level_logits=b["logit"],
-                      level_count=torch.stack(b["count"]), cand_boxes=b["boxes"], cand_labels=b["labels"], cand_scores=scores,
-                      order=order, sorted_boxes=sboxes, sorted_scores=sscores, sorted_labels=slabels, det_keep=keep)
-        return out, feats, hw
+    def _scores(self, idx, logit):
+        return torch.where(idx >= 0, torch.sigmoid(logit), torch.zeros_like(logit))
 
 
 # ---- FCOS ------------------------------------------------------------------------------------------------------------------
 FCOS_SIZES = ((8,), (16,), (32,), (64,), (128,))
-FCOS_GROUPS = 32     # torchvision's GroupNorm(32, in_channels) between the tower convolutions
 FCOS_CTR_COL = 4     # bbox_ctrness rides in column 4 of the regression map, beside bbox_reg's 0 .. 3
 
 
@@ -1448,7 +1524,7 @@ def validate_fcos_head_state_dict(sd, in_channels: int = 256) -> int:
     return classes
 
 
-class FCOSHead(_ConvTower):
+class FCOSHead(_DenseHead):
     """torchvision's FCOSHead (classification and regression towers with GroupNorm(32, C) + ReLU) on the Winograd 3x3 and
     the GroupNorm kernel, inference only: per level and tower four times conv3x3 (bias, no ReLU) -> groupnorm_relu in
     place, then the last 3x3 without ReLU, with the same packed weights on every level.  The outputs stay the padded maps
@@ -1456,10 +1532,10 @@ class FCOSHead(_ConvTower):
     in columns 0 .. 3 (before its ReLU: fcos_decode applies it) and bbox_ctrness in column 4 -- what fcos_score_map,
     select_topk_map and fcos_decode read in place."""
 
+    name = "FCOS head"
+
     def __init__(self, in_channels: int, classes: int, device):
-        super().__init__(device)
-        self.in_channels, self.classes = int(in_channels), int(classes)
-        self.widths = [self.in_channels] * RETINA_CONVS
+        super().__init__(in_channels, classes, device)
         self.cols, self.ld_cls, self.ld_reg = self.classes, _pad64(self.classes), 64
 
     @classmethod
@@ -1469,66 +1545,13 @@ class FCOSHead(_ConvTower):
         return cls._load(sd, None, device, in_channels, classes)
 
     def _pack(self, sd, eps):
-        self.towers = []   # (the four (U, bias) of the tower, its four (gamma, beta), U and bias of its last convolution, its width)
-        for head, last in (("classification_head", ("cls_logits",)), ("regression_head", ("bbox_reg", "bbox_ctrness"))):
-            self._pack_tower(sd, [f"{head}.conv.{3 * i}" for i in range(RETINA_CONVS)])
-            norms = [(self._t(sd[f"{head}.conv.{3 * i + 1}.weight"]), self._t(sd[f"{head}.conv.{3 * i + 1}.bias"]))
-                     for i in range(RETINA_CONVS)]
-            wl, bl = pack_retina_last(torch.cat([sd[f"{head}.{k}.weight"] for k in last]),
-                                      torch.cat([sd[f"{head}.{k}.bias"] for k in last]))
-            self.towers.append((self.convs, norms, filter_transform_f2(self._t(wl)), self._t(bl), int(wl.shape[0])))
-        del self.convs
-        self._ones = torch.ones(max(self.in_channels, self.ld_cls, self.ld_reg), dtype=torch.float32, device=self.device)
-        torch.cuda.current_stream().synchronize()
-
-    def prepare(self, N: int, level_hw) -> None:
-        """Allocate, per level of `level_hw` [(h, w)], the two ping-pong tensors both towers share, the two output maps
-        and the GroupNorm workspace, and reserve the stream scratch of every convolution on the current stream.  Call it
-        before capturing a forward into a graph."""
-        N, C, dev, f32 = int(N), self.in_channels, self.device, torch.float32
-        level_hw = tuple((int(h), int(w)) for h, w in level_hw)
-        if N < 1 or not level_hw or min(min(hw) for hw in level_hw) < 1:
-            raise WinoError(f"FCOS head: N={N} images, levels {level_hw}")
-        with torch.cuda.device(dev):
-            zeros = lambda h, w, c: torch.zeros((N, h + 2, w + 2, c), dtype=f32, device=dev)
-            self._pp = [(zeros(h, w, C), zeros(h, w, C)) for h, w in level_hw]
-            self._cls = [zeros(h, w, self.ld_cls) for h, w in level_hw]
-            self._reg = [zeros(h, w, self.ld_reg) for h, w in level_hw]
-            # the split form's size whatever the plan says now: a WINO_GN_FORM set after prepare finds room
-            self._gn_ws = [torch.empty((N * min(h * w, 128) * 4 * FCOS_GROUPS,), dtype=f32, device=dev) for h, w in level_hw]
-            for h, w in level_hw:
-                for k in (C, self.ld_cls, self.ld_reg):
-                    conv3x3_prepare(N, C, k, h, w)
-        self._shape = (N, level_hw)
-
-    def forward(self, maps):
-        """maps: the levels' padded features [N][h+2][w+2][in_channels] (zero rings; they are not written).  Returns
-        (class logit maps, regression maps), one per level: tensors of the head's, valid until the next forward.  New
-        shapes re-run prepare()."""
-        from . import groupnorm_relu
-        maps, C = list(maps), self.in_channels
-        for x in maps:
-            if not isinstance(x, torch.Tensor) or x.dim() != 4 or int(x.shape[3]) != C or min(x.shape[1:3]) < 3:
-                raise WinoError(f"FCOS head: every level must be [N][h+2][w+2][{C}]")
-            if x.device != self.device or x.dtype != torch.float32 or not x.is_contiguous():
-                raise WinoError(f"FCOS head: every level must be contiguous float32 on {self.device}")
-        shape = (int(maps[0].shape[0]), tuple((int(x.shape[1]) - 2, int(x.shape[2]) - 2) for x in maps))
-        if any(int(x.shape[0]) != shape[0] for x in maps):
-            raise WinoError("FCOS head: the levels differ in N")
-        if shape != self._shape:
-            self.prepare(*shape)
-        with torch.cuda.device(self.device):
-            for l, x0 in enumerate(maps):
-                for (convs, norms, U, bias, kp), outs in zip(self.towers, (self._cls, self._reg)):
-                    x = x0
-                    for i, ((Ui, bi), (gamma, beta)) in enumerate(zip(convs, norms)):
-                        x = conv3x3_bn_relu(x, Ui, bi, self._ones[:C], relu=False, out=self._pp[l][i % 2])
-                        groupnorm_relu(x, gamma, beta, FCOS_GROUPS, out=x, workspace=self._gn_ws[l])
-                    conv3x3_bn_relu(x, U, bias, self._ones[:kp], relu=False, out=outs[l])
-        return self._cls, self._reg
+        self._pack_towers(sd, [([f"{head}.conv.{3 * i}" for i in range(RETINA_CONVS)],
+                                [f"{head}.conv.{3 * i + 1}" for i in range(RETINA_CONVS)], [f"{head}.{k}" for k in last])
+                               for head, last in (("classification_head", ("cls_logits",)),
+                                                  ("regression_head", ("bbox_reg", "bbox_ctrness")))])
 
 
-class FCOS(_Detector):
+class FCOS(_DenseDetector):
     """torchvision's fcos_resnet50_fpn at test time on the library's kernels: ResNetFPN(returned_layers = (2, 3, 4),
     extra_blocks = "p6p7", padded) -> FCOSHead -> per level fcos_score_map in place on the class logit map,
     select_topk_map on the score map and fcos_decode of the selected locations -> one select_topk over the levels'
@@ -1544,15 +1567,13 @@ class FCOS(_Detector):
       * stages=True exposes the score maps ("cls_maps") where RetinaNet exposes logit maps: the logits are overwritten
         in place."""
 
+    name, head_cls, values_key, ctr_col = "FCOS", FCOSHead, "level_scores", FCOS_CTR_COL
+    validate_head, threshold = staticmethod(validate_fcos_head_state_dict), staticmethod(score_threshold)
+
     def __init__(self, backbone, head, sizes, detections, score_thresh, nms_thresh, topk_candidates, device):
-        super().__init__(device, detections)
-        self.backbone, self.head = backbone, head
         self.sizes = tuple(tuple(s) for s in sizes)
-        self.score_thresh, self.nms_thresh, self.topk = float(score_thresh), float(nms_thresh), int(topk_candidates)
-        self.thresh = score_threshold(self.score_thresh)
-        with torch.cuda.device(self.device):
-            self.base = [self._t(base_anchors(s, (1.0,))) for s in self.sizes]
-            torch.cuda.current_stream().synchronize()
+        super().__init__(backbone, head, [base_anchors(s, (1.0,)) for s in self.sizes], detections, score_thresh, nms_thresh,
+                         topk_candidates, device)
 
     @classmethod
     def from_state_dict(cls, sd, arch: str, num_classes=None, score_thresh: float = 0.2, nms_thresh: float = 0.6,
@@ -1560,87 +1581,17 @@ class FCOS(_Detector):
                         out_channels: int = 256, eps: float = 1e-5) -> "FCOS":
         """sd under torchvision's key names: backbone.body.*, backbone.fpn.* (inner_blocks / layer_blocks 0..2 and
         extra_blocks.p6|p7) and head.*; each part is validated with check_state_dict."""
-        from .fpn import ResNetFPN
-        if len(sizes) != len(RETINA_LEVELS) or any(len(s) != 1 for s in sizes):
-            raise WinoError(f"FCOS: {len(RETINA_LEVELS)} levels need {len(RETINA_LEVELS)} tuples of one anchor size")
-        score_threshold(score_thresh)
-        if not 1 <= int(topk_candidates) <= SELECT_MAX_ROWS // len(RETINA_LEVELS) or int(detections_per_img) < 1:
-            raise WinoError(f"FCOS: topk_candidates={topk_candidates} (the levels' candidates are sorted by one "
-                            f"select_topk of at most {SELECT_MAX_ROWS} rows), detections_per_img={detections_per_img}")
-        parts = {"backbone.": {}, "head.": {}}
-        for k, v in sd.items():
-            for prefix, part in parts.items():
-                if k.startswith(prefix):
-                    part[k[len(prefix):]] = v
-                    break
-            else:
-                raise WinoError(f"state dict: unexpected key {k!r} for FCOS")
-        classes = validate_fcos_head_state_dict(parts["head."], out_channels)
-        if num_classes is not None and int(num_classes) != classes:
-            raise WinoError(f"state dict has {classes} classes, num_classes={num_classes}")
-        backbone = ResNetFPN.from_state_dict(parts["backbone."], arch, out_channels, eps, device, returned_layers=(2, 3, 4),
-                                             extra_blocks="p6p7")
-        head = FCOSHead.from_state_dict(parts["head."], out_channels, backbone.device)
+        ok = len(sizes) == len(RETINA_LEVELS) and all(len(s) == 1 for s in sizes)
+        backbone, head = cls._load_parts(sd, arch, num_classes, ok, "tuples of one anchor size", score_thresh,
+                                         topk_candidates, detections_per_img, device, out_channels, eps)
         return cls(backbone, head, sizes, detections_per_img, score_thresh, nms_thresh, topk_candidates, backbone.device)
 
-    def _prepare(self, N: int, H: int, W: int, for_predict: bool) -> None:
-        from . import nms_workspace_bytes, select_map_workspace_bytes, select_workspace_bytes
-        N, H, W, D, dev, f32, i32 = int(N), int(H), int(W), self.detections, self.device, torch.float32, torch.int32
-        self._shape = None
-        with torch.cuda.device(dev):
-            self.backbone.prepare(N, H, W)
-            level_hw = [(int(t.shape[1]) - 2, int(t.shape[2]) - 2) for t in (*self.backbone._p, *self.backbone._extra[::2])]
-            self.head.prepare(N, level_hw)
-            cols = self.head.cols
-            self._grid = [(h, w, H // h, W // w) for h, w in level_hw]
-            if min(min(g[2:]) for g in self._grid) < 1:
-                raise WinoError(f"FCOS: a batch of {H} x {W} is smaller than its pyramid levels {level_hw}")
-            self._k = [min(self.topk, h * w * cols) for h, w in level_hw]
-            self._off = [sum(self._k[:l]) for l in range(len(self._k))]
-            K = sum(self._k)
-            empty = lambda shape, dtype=f32: torch.empty(shape, dtype=dtype, device=dev)
-            self._b = dict(
-                idx=empty((N, K), i32), score=empty((N, K)), count=[empty((N,), i32) for _ in level_hw], boxes=empty((N, K, 4)),
-                labels=empty((N, K), i32), order=empty((N, K), i32), sscores=empty((N, K)), count2=empty((N, 1), i32),
-                sboxes=empty((N, K, 4)), keep=empty((N, D), i32), det_count=empty((N,), i32),
-                ws=[empty(((select_map_workspace_bytes(N, h, w, cols, k) + 3) // 4,)) for (h, w), k in zip(level_hw, self._k)],
-                ws2=empty(((select_workspace_bytes(N, K, K) + 3) // 4,)), nms=empty(((nms_workspace_bytes(N, K) + 3) // 4,)))
-            self._full_hw = torch.tensor([[float(H), float(W)]] * N, dtype=f32, device=dev)
-        self._shape = (N, H, W)
+    def _decode(self, *operands):
+        from . import fcos_decode
+        fcos_decode(*operands)
 
-    def _detect(self, x, image_sizes, st):
-        """FCOS's stages; returns (the result dict, the pyramid, image_hw)."""
-        from . import batched_nms, fcos_decode, fcos_score_map, select_topk, select_topk_map
-        self._begin(x)
-        N, H, W = self._shape
-        hw = self._full_hw if image_sizes is None else image_sizes
-        if tuple(hw.shape) != (N, 2) or hw.device != self.device or hw.dtype != torch.float32:
-            raise WinoError(f"image_sizes must be a float32 tensor [{N}][2] on {self.device}")
-        b, K = self._b, self.head.classes
-        with torch.cuda.device(self.device):
-            feats = self.backbone(x, padded=True)
-            cls, reg = self.head([feats[name] for name in RETINA_LEVELS])
-            for l, (k, off) in enumerate(zip(self._k, self._off)):
-                fcos_score_map(cls[l], reg[l], K, FCOS_CTR_COL)
-                select_topk_map(cls[l], K, k, self.thresh, b["idx"], b["score"], b["count"][l], off, b["ws"][l])
-                fcos_decode(b["idx"], reg[l], self.base[l], hw, self._grid[l], K, k, b["boxes"], b["labels"], off)
-            scores = b["score"]                          # (the select writes 0.0 past a level's kept count)
-            order, sscores, _, sboxes = select_topk(scores, sum(self._k), boxes=b["boxes"], out_idx=b["order"],
-                                                    out_vals=b["sscores"], out_count=b["count2"], out_boxes=b["sboxes"],
-                                                    workspace=b["ws2"])
-            slabels = b["labels"].gather(1, order.long())
-            keep, count = batched_nms(sboxes, sscores, slabels, self.nms_thresh, 0.0, RETINA_NMS_SCORE_MIN, self.detections,
-                                      workspace=b["nms"], keep=b["keep"], count=b["det_count"])
-            kept = keep >= 0
-            at = keep.clamp(min=0).long()
-            out = {"boxes": sboxes.gather(1, at[:, :, None].expand(-1, -1, 4)) * kept[:, :, None],
-                   "scores": sscores.gather(1, at) * kept,
-                   "labels": torch.where(kept, slabels.gather(1, at).long(), torch.full_like(at, -1)), "count": count}
-        if st is not None:
-            st.update(features=feats, cls_maps=list(cls), reg_maps=list(reg), level_idx=b["idx"], level_scores=b["score"],
-                      level_count=torch.stack(b["count"]), cand_boxes=b["boxes"], cand_labels=b["labels"], cand_scores=scores,
-                      order=order, sorted_boxes=sboxes, sorted_scores=sscores, sorted_labels=slabels, det_keep=keep)
-        return out, feats, hw
+    def _scores(self, idx, score):
+        return score                                     # (the select writes 0.0 past a level's kept count)
 
 
 __all__ = ["BoxHead", "MaskHead", "KeypointHead", "RPN", "FasterRCNN", "MaskRCNN", "KeypointRCNN", "RetinaNetHead",

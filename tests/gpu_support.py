@@ -36,6 +36,15 @@ def rel(torch, got, want):
     return layer_refs.rel(got, want)
 
 
+def same_bits(a, b):
+    """Two tensors (or arrays), wherever they live, have one shape, one dtype and the same bytes."""
+    import torch
+    a, b = (torch.as_tensor(t).detach().cpu().contiguous() for t in (a, b))
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    return bool((a.reshape(-1).view(torch.uint8) == b.reshape(-1).view(torch.uint8)).all())
+
+
 def _clone(r):
     return tuple(t.clone() for t in r) if isinstance(r, tuple) else r.clone()
 

@@ -12,13 +12,14 @@ import pytest
 import torch
 
 import box_cases as bc
+import dense_detector_checks as dc
 import fcos_reference as fr
 from cases import TIGHT
-from gpu_support import R, torch_dev  # noqa: F401
+from dense_detector_checks import cpu
+from gpu_support import R, same_bits, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 D = fr.FCOS
-OUT_KEYS = ("boxes", "scores", "labels", "count")
 LAYER_TOL = 2e-5
 
 
@@ -31,19 +32,8 @@ def model(pkg, R, torch_dev):
     return m, sd
 
 
-def cpu(t):
-    return t.detach().cpu()
-
-
 def rel(got, want):
     return bc.rel_err(cpu(got).double().numpy(), np.asarray(want, dtype=np.float64))
-
-
-def same_bits(a, b):
-    a, b = cpu(a).contiguous(), torch.as_tensor(b).cpu().contiguous()
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    return bool((a.reshape(-1).view(torch.uint8) == b.reshape(-1).view(torch.uint8)).all())
 
 
 def test_every_stage_against_fp64_on_the_gpus_own_input(pkg, model, torch_dev):
@@ -127,71 +117,17 @@ def test_every_stage_against_fp64_on_the_gpus_own_input(pkg, model, torch_dev):
     # the tail on the GPU's candidates: order, NMS, the padded detections
     det = fr.detections_reference(cpu(out["cand_boxes"]).numpy(), score_all, cpu(out["cand_labels"]).numpy(), valid,
                                   D["nms_thresh"], D["detections"])
-    order = cpu(out["order"]).numpy()
-    for i in range(N):
-        c = len(det["orders"][i])
-        assert np.array_equal(order[i, :c], det["orders"][i]) and not valid[i, order[i, c:]].any()
-    assert np.array_equal(cpu(out["count"]).numpy(), det["count"])
-    assert same_bits(out["boxes"], det["boxes"]) and same_bits(out["scores"], det["scores"])
-    assert torch.equal(cpu(out["labels"]), torch.from_numpy(det["labels"]))
-    print("margins: threshold", thresh_margin, "ties", tie_gaps, det["tie_gap"], "iou", det["iou_margin"], "detections",
-          det["count"].tolist())
-    fr.assert_margins(thresh_margin, tie_gaps + [det["tie_gap"]], det["iou_margin"])
-    assert int(det["count"].min()) > 0
-    for n, d in enumerate(m.to_lists(out)):                           # rows past count: zero, label -1
-        c = int(det["count"][n])
-        assert tuple(d["boxes"].shape) == (c, 4) and bool((d["labels"] >= 0).all()) and bool((d["scores"] > D["score_thresh"]).all())
-        assert bool((cpu(out["boxes"])[n, c:] == 0).all()) and bool((cpu(out["labels"])[n, c:] == -1).all())
-        assert bool((cpu(out["scores"])[n, c:] == 0).all())
+    dc.check_tail(m, out, det, valid, D["score_thresh"], fr.assert_margins, thresh_margin, tie_gaps)
 
 
 def test_one_graph_replays_bitwise(pkg, model, torch_dev):
     """The whole forward captured into one graph -- a host read of device data inside it would fail the capture -- replays
     bitwise equal to eager into NaN-filled buffers, and no ticket stays held."""
-    m, _ = model
-    x = fr.detector_input().to(torch_dev[1])
-    sg = torch.cuda.Stream()
-    with torch.cuda.stream(sg):
-        m.prepare(D["N"], D["H"], D["W"])
-        eager = {k: v.clone() for k, v in m(x).items()}
-    sg.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=sg):
-        out = m(x)
-    for _ in range(2):
-        for k in ("boxes", "scores"):
-            out[k].fill_(float("nan"))
-        for t in (m._b["idx"], m._b["score"], m._b["boxes"], m._b["sboxes"], m._b["keep"], *m.head._gn_ws):
-            t.view(torch.int32).fill_(0x7FC00000)
-        graph.replay()
-        torch.cuda.synchronize()
-        for k in OUT_KEYS:
-            assert same_bits(out[k], eager[k]), k
-    with torch.cuda.stream(sg):
-        assert pkg.tickets_in_use() == 0
-    del graph
+    dc.check_one_graph_replays_bitwise(pkg, model[0], fr.detector_input().to(torch_dev[1]), lambda m: (
+        m._b["idx"], m._b["vals"], m._b["boxes"], m._b["sboxes"], m._b["keep"], *m.head._gn_ws))
 
 
 def test_predict_on_two_images_of_different_sizes(pkg, model, torch_dev):
     """predict is the shared detector path: image_transform -> forward on the batch with the resized sizes -> boxes x
     ratio.  Its boxes are forward's on the transformed batch times the ratio, bit for bit, and lie inside each image."""
-    m, _ = model
-    dev = torch_dev[1]
-    g = torch.Generator().manual_seed(3)
-    images = [torch.rand(3, 50, 70, generator=g).to(dev), torch.rand(3, 64, 48, generator=g).to(dev)]
-    m.prepare_images([t.shape for t in images], min_size=64, max_size=96)
-    out = m.predict(images)
-    torch.cuda.synchronize()
-    got = {k: out[k].clone() for k in OUT_KEYS}
-    tf = m._tf
-    assert out["original_sizes"] == [(50, 70), (64, 48)] and tuple(tf["batch"].shape) == (2, 3, *tf["shape"][1:])
-    ref = m(tf["batch"].clone(), tf["image_hw"])
-    torch.cuda.synchronize()
-    assert same_bits(got["boxes"], cpu(ref["boxes"] * tf["ratio"]))
-    for k in ("scores", "labels", "count"):
-        assert same_bits(got[k], cpu(ref[k])), k
-    assert int(got["count"].min()) > 0
-    for d, (h, w) in zip(m.to_image_lists(out), out["original_sizes"]):
-        b = d["boxes"].cpu()
-        assert bool((b[:, 0::2] <= w + 1e-3).all()) and bool((b[:, 1::2] <= h + 1e-3).all()) and bool((b >= 0).all())
-    m.prepare(D["N"], D["H"], D["W"])
+    dc.check_predict_on_two_images_of_different_sizes(model[0], torch_dev[1], (D["N"], D["H"], D["W"]))

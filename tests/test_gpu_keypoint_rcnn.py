@@ -11,7 +11,7 @@ import torch
 import box_cases as bc
 import keypoint_cases as kc
 import transform_cases as tc
-from gpu_support import R, torch_dev  # noqa: F401
+from gpu_support import R, same_bits, torch_dev  # noqa: F401
 from reference_nets import NET_TOL
 
 pytestmark = pytest.mark.gpu
@@ -47,13 +47,6 @@ def model(pkg, R, torch_dev):
 
 def cpu(t):
     return t.detach().cpu()
-
-
-def same_bits(a, b):
-    a, b = cpu(a).contiguous(), cpu(b).contiguous()
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    return bool((a.reshape(-1).view(torch.uint8) == b.reshape(-1).view(torch.uint8)).all())
 
 
 @pytest.mark.parametrize("P", (2, 4))

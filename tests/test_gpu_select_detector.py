@@ -12,7 +12,7 @@ import torch
 import box_cases as bc
 import roi_cases as rc
 import select_cases as sc
-from gpu_support import R, torch_dev  # noqa: F401
+from gpu_support import R, same_bits, torch_dev  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 D = bc.DETECTOR
@@ -24,13 +24,6 @@ MASK_P = 14
 def kwargs(dev, **more):
     return dict(num_classes=D["classes"], out_channels=D["out_channels"], P=D["P"], rpn_pre_nms_top_n=D["pre"],
                 rpn_post_nms_top_n=D["post"], box_detections_per_img=D["detections"], device=dev, **more)
-
-
-def same_bits(a, b):
-    a, b = a.detach().cpu().contiguous(), b.detach().cpu().contiguous()
-    if a.shape != b.shape or a.dtype != b.dtype:
-        return False
-    return bool((a.reshape(-1).view(torch.uint8) == b.reshape(-1).view(torch.uint8)).all())
 
 
 @pytest.fixture(scope="module")
