@@ -141,8 +141,8 @@ def _res_kernels(kernels, family):
     return {n: template_args(n, family) for n in kernels if template_args(n, family) is not None}
 
 
-def test_res_file_compiles_the_res_kernels_only_within_budget(tmp_path):
-    k = compile_report("conv3x3_res.hip", tmp_path)
+def test_res_file_compiles_the_res_kernels_only_within_budget():
+    k = compile_report("conv3x3_res.hip")
     fused = _res_kernels(k, "wino_f2_fused_kernel")
     small = _res_kernels(k, "wino_f2_small_kernel")
     assert len(k) == len(fused) + len(small), sorted(k)        # nothing else
@@ -160,8 +160,8 @@ def test_res_file_compiles_the_res_kernels_only_within_budget(tmp_path):
         assert v["mfma"] >= 32, (name, v)
 
 
-def test_plain_file_has_no_res_instantiation(tmp_path):
-    k = compile_report("wino_f2_fused.hip", tmp_path)
+def test_plain_file_has_no_res_instantiation():
+    k = compile_report("wino_f2_fused.hip")
     for family in ("wino_f2_fused_kernel", "wino_f2_small_kernel"):
         args = _res_kernels(k, family)
         assert args, family

@@ -5,12 +5,10 @@ are fake), and the build of basic_block_s2.hip, which instantiates the 1x1 kerne
 only, within the budgets of the tap form (test_conv3x3_s2_host.py)."""
 import os
 import re
-import shutil
-import subprocess
 
 import pytest
 
-from build_report import CSRC, compile_report, template_args
+from build_report import compile_report, template_args
 from conftest import ROOT
 
 E_SHAPE, E_ARG = -2, -3
@@ -161,13 +159,13 @@ def test_python_argument_errors(pkg):
         pkg.basic_block_s2(x, packed, U2, bn)
 
 
-def test_proj_file_compiles_the_proj_form_only_within_budget(tmp_path):
+def test_proj_file_compiles_the_proj_form_only_within_budget():
     """basic_block_s2.hip instantiates the 1x1 kernel templates in form A_TAPS_PROJ (4) only -- 4 tiled kernels
     ({4, 8 waves} x {plain, stream-K}) and 18 latency kernels (KS x RT x CT) -- and its pack kernel, within the tap form's
     budgets: the tiled kernel 128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), the latency kernels no spill at all, no
     spill code beside MFMAs.  (The stream-K kernels hold a few more SGPRs than A_TAPS's -- the shortcut's flag and
     pointers -- spilled to VGPR lanes outside the MFMA blocks.)"""
-    k = compile_report("basic_block_s2.hip", tmp_path)
+    k = compile_report("basic_block_s2.hip")
     tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
     small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     pack = {n: v for n, v in k.items() if "s2_proj_pack_kernel" in n}
@@ -187,22 +185,13 @@ def test_proj_file_compiles_the_proj_form_only_within_budget(tmp_path):
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)
 
 
-def test_proj_form_k_loop_has_no_per_lane_offsets(tmp_path):
+def test_proj_form_k_loop_has_no_per_lane_offsets():
     """As in the tap form (test_conv3x3_s2_host.py): no readfirstlane loop and no per-lane multiply in a basic block with
     MFMAs of the A_TAPS_PROJ tiled kernels -- the shortcut tiles reuse the tap form's scalar k offsets."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    asm = tmp_path / "bb_s2.s"
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                          "-I" + CSRC, "--cuda-device-only", "-S", os.path.join(CSRC, "basic_block_s2.hip"), "-o",
-                          str(asm)], capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    text = asm.read_text()
-    names = re.findall(r"^(_ZN4wino7gemm1x117conv1x1_bn_kernel\w+):", text, re.M)
-    assert len(names) == 4, names
-    for name in names:
-        i = text.index("\n" + name + ":") + 1
-        body = text[i:text.index(".Lfunc_end", i)]
-        hot = [b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body) if "v_mfma" in b]
+    tiled = {n: v for n, v in compile_report("basic_block_s2.hip").items() if n.startswith("_ZN4wino7gemm1x117conv1x1_bn_kernel")}
+    assert len(tiled) == 4, sorted(tiled)
+    for name, v in tiled.items():
+        hot = [b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", "\n".join(v["body"])) if "v_mfma" in b]
         assert hot, name
         for op in ("v_readfirstlane", "s_and_saveexec", "v_mul_lo_u32"):
             assert sum(b.count(op) for b in hot) == 0, (name, op)

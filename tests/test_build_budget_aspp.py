@@ -8,8 +8,8 @@ from build_report import CSRC, compile_report, template_args
 A_CAT = 6
 
 
-def test_aspp_kernels_build_budget(tmp_path):
-    k = compile_report("aspp.hip", tmp_path)
+def test_aspp_kernels_build_budget():
+    k = compile_report("aspp.hip")
     assert len(k) == 4, sorted(k)
     args = sorted(template_args(n, "conv1x1_bn_kernel") for n in k)
     # <BK, NW, ABLATE, SK, RES, AF>

@@ -7,8 +7,8 @@ from build_report import compile_report, template_args
 RES_UP2, A_PLAIN = 2, 0
 
 
-def test_fpn_kernels_build_budget(tmp_path):
-    k = compile_report("fpn.hip", tmp_path)
+def test_fpn_kernels_build_budget():
+    k = compile_report("fpn.hip")
     tiled = {n: template_args(n, "conv1x1_bn_kernel") for n in k if "conv1x1_bn_kernel" in n}
     small = {n: template_args(n, "conv1x1_small_kernel") for n in k if "conv1x1_small_kernel" in n}
     assert len(k) == len(tiled) + len(small), sorted(k)          # the file instantiates nothing else
@@ -27,10 +27,10 @@ def test_fpn_kernels_build_budget(tmp_path):
         assert v["mfma"] >= 4, (name, v)
 
 
-def test_the_other_files_instantiate_no_up2_kernel(tmp_path):
+def test_the_other_files_instantiate_no_up2_kernel():
     """conv1x1.hip hands WINO_RESIDUAL_UP2 launches to fpn.hip and keeps exactly its kernels: no instantiation there
     carries the upsampled residual."""
-    k = compile_report("conv1x1.hip", tmp_path)
+    k = compile_report("conv1x1.hip")
     tiled = [template_args(n, "conv1x1_bn_kernel") for n in k if "conv1x1_bn_kernel" in n]
     small = [template_args(n, "conv1x1_small_kernel") for n in k if "conv1x1_small_kernel" in n]
     assert len(tiled) == 8 and len(small) == 18

@@ -5,8 +5,8 @@ block (the grouped ones among them) as host code over existing launches, instant
 from build_report import compile_report, template_args
 
 
-def test_grouped_kernel_spills_nothing(tmp_path):
-    k = compile_report("conv3x3_grouped.hip", tmp_path)
+def test_grouped_kernel_spills_nothing():
+    k = compile_report("conv3x3_grouped.hip")
     conv = {n: tuple(template_args(n, "conv3x3_grouped_kernel")) for n in k if "conv3x3_grouped_kernel" in n}
     assert sorted(conv.values()) == [(s, tw, kc) for s in (1, 2) for tw in (8, 16) for kc in (16, 32, 64)], conv
     assert len(k) == len(conv) + 1 and any("grouped_pack_kernel" in n for n in k), sorted(k)
@@ -20,5 +20,5 @@ def test_grouped_kernel_spills_nothing(tmp_path):
         assert v["occupancy"] >= 2, (name, v)
 
 
-def test_grouped_blocks_instantiate_no_kernel(tmp_path):
-    assert compile_report("bottleneck.hip", tmp_path) == {}
+def test_grouped_blocks_instantiate_no_kernel():
+    assert compile_report("bottleneck.hip") == {}

@@ -12,8 +12,8 @@ def _of(kernels, family):
     return {n: template_args(n, family) for n in kernels if template_args(n, family) is not None}
 
 
-def test_pool_file_compiles_the_pooled_kernels_only_within_budget(tmp_path):
-    k = compile_report("conv3x3_pool.hip", tmp_path)
+def test_pool_file_compiles_the_pooled_kernels_only_within_budget():
+    k = compile_report("conv3x3_pool.hip")
     fused = _of(k, "wino_f2_fused_kernel")
     small = _of(k, "wino_f2_small_kernel")
     assert len(k) == len(fused) + len(small), sorted(k)        # nothing else
@@ -32,8 +32,8 @@ def test_pool_file_compiles_the_pooled_kernels_only_within_budget(tmp_path):
         assert v["mfma"] >= 32, (name, v)
 
 
-def test_vgg_ops_file_spills_nothing(tmp_path):
-    k = compile_report("vgg_ops.hip", tmp_path)
+def test_vgg_ops_file_spills_nothing():
+    k = compile_report("vgg_ops.hip")
     assert sorted(n for n in k) and all("image_pack_kernel" in n or "avgpool7_flatten_kernel" in n for n in k), sorted(k)
     assert len(k) == 2, sorted(k)
     for name, v in k.items():

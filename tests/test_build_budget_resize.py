@@ -2,23 +2,16 @@
 at four waves per SIMD or more, and with no more than 64 KB of static LDS (the staged form's is dynamic: the launch
 asks for what the plan computed, at most 64 KB, so that two workgroups fit on a CU)."""
 import os
-import re
 
 from build_report import compile_report
 
 LDS_LIMIT = 64 << 10
 
 
-def test_resize_kernels_build_budget(tmp_path):
-    k = compile_report("resize.hip", tmp_path)
+def test_resize_kernels_build_budget():
+    k = compile_report("resize.hip")
     assert len(k) == 2 and any("resize_staged_kernel" in n for n in k) and any("resize_direct_kernel" in n for n in k), sorted(k)
-    isa = [f for f in os.listdir(tmp_path) if f.endswith(".s") and "gfx950" in f]
-    assert len(isa) == 1, isa
-    text = (tmp_path / isa[0]).read_text()
     for name, v in k.items():
-        m = re.search(r"\.amdhsa_kernel " + re.escape(name) + r"\b.*?\.amdhsa_group_segment_fixed_size (\d+)", text, flags=re.S)
-        assert m, name
-        v["static_lds"] = int(m.group(1))
         print(name, v)
         assert v["spill"] == 0 and v["sgpr_spill"] == 0, (name, v)
         assert v["occupancy"] >= 4, (name, v)

@@ -8,25 +8,15 @@ the order is settled once, in the prologue, and costs the loop nothing."""
 import pytest
 
 from build_report import compile_report, template_args
-from test_build_budget_loop import innermost_mfma_loop, loop_counts   # the loop finder and its counters, as pinned there
+from isa_analysis import innermost_mfma_loop, loop_counts
 
 SOURCES = ["wino_f2_fused.hip", "conv3x3_res.hip", "conv3x3_pool.hip"]
 
 
 @pytest.fixture(scope="module")
-def reports(tmp_path_factory):
-    out = {}
-    for src in SOURCES:
-        tmp = tmp_path_factory.mktemp(src.replace(".", "_"))
-        kernels = {n: v for n, v in compile_report(src, tmp).items() if "wino_f2_fused_kernel" in n}
-        isa = [f for f in tmp.iterdir() if f.name.endswith(".s") and "gfx950" in f.name]
-        assert len(isa) == 1, isa
-        text = isa[0].read_text()
-        for name, v in kernels.items():
-            i = text.index(name + ":")
-            v["body"] = text[i:text.index(".Lfunc_end", i)].splitlines()
-            out[(src, tuple(template_args(name, "wino_f2_fused_kernel")))] = v
-    return out
+def reports():
+    return {(src, tuple(template_args(name, "wino_f2_fused_kernel"))): v for src in SOURCES
+            for name, v in compile_report(src).items() if "wino_f2_fused_kernel" in name}
 
 
 def test_every_instantiation_is_there(reports):

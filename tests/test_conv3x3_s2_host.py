@@ -5,6 +5,7 @@ the plain 1x1 GEMM of shape (N*H*W, 9C, K), and the build budget of conv3x3_s2.h
 templates in operand form A_TAPS only."""
 import ctypes
 import os
+import re
 
 from build_report import compile_report, template_args
 from conftest import ROOT
@@ -151,12 +152,12 @@ def test_plan_routes_as_measured(pkg, knobs):
     assert pkg.conv3x3_s2_plan(*shape) == pkg.FORM_STREAM_K
 
 
-def test_tap_form_kernels_build_budget(tmp_path):
+def test_tap_form_kernels_build_budget():
     """conv3x3_s2.hip instantiates the 1x1 kernel templates in form A_TAPS (3) only -- 4 tiled kernels ({4, 8 waves} x
     {plain, stream-K}) and 18 latency kernels (KS x RT x CT) -- within the budgets of the other forms
     (test_proj_block_host.py): the tiled kernel 128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), a few spills outside
     the loops at most; the latency kernels no spill at all; no spill code beside MFMAs."""
-    k = compile_report("conv3x3_s2.hip", tmp_path)
+    k = compile_report("conv3x3_s2.hip")
     tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
     small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     assert len(tiled) == 4, sorted(tiled)
@@ -174,28 +175,15 @@ def test_tap_form_kernels_build_budget(tmp_path):
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)
 
 
-def test_tap_offset_is_scalar_in_the_k_loop(tmp_path):
+def test_tap_offset_is_scalar_in_the_k_loop():
     """The tiled kernel's A offset of a k-step is one wave-uniform scalar in every operand form.  Computed on the VALU,
     it has to reach the LDS-DMA's soffset through a readfirstlane loop around every A piece (v_readfirstlane,
     v_cmp_eq, s_and_saveexec, ..., s_cbranch_execnz) inside the MFMA loop.  None of that, and no per-lane multiply,
     may sit in a basic block with MFMAs of the tap-form kernels."""
-    import re
-    import shutil
-    import subprocess
-    from build_report import CSRC
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    asm = tmp_path / "s2.s"
-    out = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                          "-I" + CSRC, "--cuda-device-only", "-S", os.path.join(CSRC, "conv3x3_s2.hip"), "-o", str(asm)],
-                         capture_output=True, text=True, timeout=600)
-    assert out.returncode == 0, out.stderr[-2000:]
-    text = asm.read_text()
-    names = re.findall(r"^(_ZN4wino7gemm1x117conv1x1_bn_kernel\w+):", text, re.M)
-    assert len(names) == 4, names
-    for name in names:
-        i = text.index("\n" + name + ":") + 1
-        body = text[i:text.index(".Lfunc_end", i)]
-        hot = [b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", body) if "v_mfma" in b]
+    tiled = {n: v for n, v in compile_report("conv3x3_s2.hip").items() if n.startswith("_ZN4wino7gemm1x117conv1x1_bn_kernel")}
+    assert len(tiled) == 4, sorted(tiled)
+    for name, v in tiled.items():
+        hot = [b for b in re.split(r"\n(?=\.LBB\d+_\d+:)", "\n".join(v["body"])) if "v_mfma" in b]
         assert hot, name
         for op in ("v_readfirstlane", "s_and_saveexec", "v_mul_lo_u32"):
             assert sum(b.count(op) for b in hot) == 0, (name, op)

@@ -115,12 +115,12 @@ def test_plan_routing_at_the_stage_shapes(pkg, knobs):
     assert _plan(pkg, 2, 28, 28, 256, 128, 512, 2)[1] == (pkg.FORM_TILED,) * 2
 
 
-def test_proj_form_kernels_build_budget(tmp_path):
+def test_proj_form_kernels_build_budget():
     """proj_block.hip instantiates the 1x1 kernel templates in the projection forms only (the form is the templates'
     last argument, AF), and those keep the budgets of the plain forms (tests/test_build_budget.py): the tiled kernel
     128 VGPRs / 4 waves (8-wave) or 168 / 3 (4-wave), a few spills outside the loops at most; the latency kernel no
     spill at all; neither any spill code beside MFMAs."""
-    k = compile_report("proj_block.hip", tmp_path)
+    k = compile_report("proj_block.hip")
     tiled = {n: v for n, v in k.items() if "conv1x1_bn_kernel" in n}
     small = {n: v for n, v in k.items() if "conv1x1_small_kernel" in n}
     assert len(tiled) == 8, sorted(tiled)     # {4, 8 waves} x {plain, stream-K} x {strided, two sources}
@@ -140,10 +140,10 @@ def test_proj_form_kernels_build_budget(tmp_path):
         assert v["spill"] == 0 and v["sgpr_spill"] == 0 and v["spill_code_in_mfma_blocks"] == 0, (name, v)
 
 
-def test_conv1x1_kernel_set_unchanged(tmp_path):
+def test_conv1x1_kernel_set_unchanged():
     """conv1x1.hip instantiates exactly the kernels it did before the projection forms existed: all in the plain
     operand form (AF = A_PLAIN = 0), none in the new ones."""
-    k = compile_report("conv1x1.hip", tmp_path)
+    k = compile_report("conv1x1.hip")
     tiled = [n for n in k if "conv1x1_bn_kernel" in n]
     small = [n for n in k if "conv1x1_small_kernel" in n]
     assert len(tiled) == 8 and len(small) == 18, sorted(k)

@@ -4,12 +4,10 @@ fires before the GPU is touched; the addresses are fake), the Python argument er
 budget (no spill code)."""
 import ctypes
 import os
-import re
-import shutil
-import subprocess
 
 import pytest
 
+from build_report import compile_report
 from conftest import ROOT
 
 E_SHAPE, E_ARG = -2, -3
@@ -130,23 +128,14 @@ def test_python_argument_errors(pkg):
     assert pkg.stem_out_hw(97, 131) == (25, 33)
 
 
-def test_stem_kernels_do_not_spill(tmp_path):
+def test_stem_kernels_do_not_spill():
     """Both stem forms fit their registers: no scratch, no spill code (the MFMA loop keeps 37 filter values and the
     accumulators of up to 19 row tiles per lane)."""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc):
-        pytest.skip("hipcc not available")
-    src = os.path.join(ROOT, "cuda-winograd_amd", "csrc", "stem_head.hip")
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"),
-                        "-I" + os.path.join(ROOT, "cuda-winograd_amd", "csrc"), "-c", src, "-o",
-                        str(tmp_path / "s.o"), "-Rpass-analysis=kernel-resource-usage"],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    blocks = re.split(r"remark: Function Name: ", r.stderr)
-    stem = [b for b in blocks if b.startswith("_ZN4wino") and "stem_kernel" in b.split()[0]]
-    assert len(stem) == 2, [b.split()[0] for b in blocks[1:]]
-    for b in stem:
-        assert re.search(r"VGPRs Spill: 0\b", b) and re.search(r"SGPRs Spill: 0\b", b), b
-        assert re.search(r"ScratchSize \[bytes/lane\]: 0\b", b), b
-        lds = int(re.search(r"LDS Size \[bytes/block\]: (\d+)", b).group(1))
+    k = compile_report("stem_head.hip")
+    stem = [v for n, v in k.items() if n.startswith("_ZN4wino") and "stem_kernel" in n]
+    assert len(stem) == 2, sorted(k)
+    for v in stem:
+        assert v["spill"] == 0 and v["sgpr_spill"] == 0, v
+        assert v["scratch"] == 0, v
+        lds = v["static_lds"]
         assert lds <= 80 * 1024, lds     # two workgroups of the big form share a CU's 160 KiB
