@@ -1475,6 +1475,42 @@ def conv3x3_grouped_plan(N: int, Hin: int, Win: int, C: int, groups: int, stride
     return _plan_query("wino_conv3x3_grouped_plan", 4, int(N), int(Hin), int(Win), int(C), int(groups), int(stride))
 
 
+ACTS = {"none": 0, "relu": 1, "relu6": 2}   # WINO_ACT_*
+
+
+def dwconv3x3_bn_act(x, w_taps, bias, scale, stride: int = 1, act: str = "relu6", in_cap=None, out=None) -> torch.Tensor:
+    """Depthwise 3x3 conv (stride 1 or 2, pad 1) + folded BN + activation, one HIP launch (depthwise.hip):
+    x [N][Hin+2][Win+2][C] (zero ring) -> out [N][H+2][W+2][C] (interior H x W = (Hin-1)//stride + 1 x (Win-1)//stride + 1,
+    zero ring).  w_taps [3][3][C]: torch's w[:, 0].permute(1, 2, 0) of the depthwise weight [C][1][3][3].  act: "none",
+    "relu" or "relu6".  in_cap: an upper bound applied to every input value as it is loaded (None: off); behind a layer
+    that ends in ReLU, in_cap=6 makes that layer's activation ReLU6.  C % 4 == 0.  No scratch: capturable as it is."""
+    x, w = _dev(x, "x"), _dev(w_taps, "w_taps")
+    b, s = _dev(bias, "bias"), _dev(scale, "scale")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("x must be [N][Hin+2][Win+2][C]")
+    N, Hin, Win, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    if tuple(w.shape) != (3, 3, C):
+        raise WinoError(f"w_taps must be [3][3][{C}], got {tuple(w.shape)}")
+    if b.numel() != C or s.numel() != C:
+        raise WinoError("bn vectors do not match C")
+    if act not in ACTS:
+        raise WinoError(f"unknown act {act!r}: one of {sorted(ACTS)}")
+    H, W = _out_hw(Hin, Win, int(stride)) if int(stride) in (1, 2) else (Hin, Win)   # (the library refuses the stride)
+    out = _output(out, (N, H + 2, W + 2, C), x.device)
+    _on_current_device(x, w, b, s, out)
+    cap = float("inf") if in_cap is None else float(in_cap)
+    _check(lib().wino_dwconv3x3_bn_act_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(), N, Hin,
+                                          Win, C, int(stride), ACTS[act], cap, _stream()), "wino_dwconv3x3_bn_act_hw")
+    return out
+
+
+def dwconv3x3_plan(N: int, Hin: int, Win: int, C: int, stride: int = 1, cus: int = 256):
+    """(cb, tile_h, tile_w, tiles_y, tiles_x) of dwconv3x3_bn_act's launch on a device of `cus` CUs (host-side): the
+    channels per workgroup (64, or 16 when 64 would launch fewer workgroups than `cus`; WINO_DW_CB = 64 | 16 forces one),
+    the output tile of a workgroup and the tiles of one image.  Raises WinoError outside the layer's limits."""
+    return _plan_query("wino_dwconv3x3_plan", 5, int(N), int(Hin), int(Win), int(C), int(stride), int(cus))
+
+
 def grouped_residual_block_prepare(N: int, H: int, W: int, C4: int, Cm: int, groups: int) -> None:
     """Allocate the scratch of grouped_residual_block's two 1x1 launches for the current stream (before graph capture)."""
     _prepare("wino_grouped_residual_block_prepare_hw", N, H, W, C4, Cm, groups)
@@ -1840,6 +1876,7 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
 
 from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)
 from .vgg import VGG  # noqa: E402
+from .mobilenet import MobileNetV2  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
 from .detection import BoxHead, MaskHead, KeypointHead, RPN, FasterRCNN, MaskRCNN, KeypointRCNN  # noqa: E402

@@ -196,6 +196,9 @@ SIGNATURES = {
     # ---- FCOS: score map and decode of the selected locations
     "wino_fcos_score_map_hw": (i, [vp] * 2 + [i] * 7 + [vp]),
     "wino_fcos_decode_hw": (i, [vp, i, i, c_long, c_long, vp] + [i] * 5 + [vp, i, i, vp, vp, vp, vp]),
+    # ---- depthwise 3x3 + BN + activation
+    "wino_dwconv3x3_plan": (i, [i] * 6 + [ip] * 5),
+    "wino_dwconv3x3_bn_act_hw": (i, [vp] * 5 + [i] * 6 + [c_float, vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -154,6 +154,7 @@ void read_knobs() {
   k.roi_launch_tasks = env_num("WINO_ROI_LAUNCH_TASKS", 0);
   const char* gn = getenv("WINO_GN_FORM");
   k.gn_form = gn && !strcmp(gn, "whole") ? 1 : gn && !strcmp(gn, "split") ? 2 : 0;
+  k.dw_cb = env_num("WINO_DW_CB", 0);
   g_knobs = k;
 }
 }  // namespace

@@ -70,7 +70,8 @@ extern "C" {
  * wino_image_transform_hw, WINO_IMAGE_*, WINO_TRANSFORM_MAX_IMAGES, wino_transform_size,
  * wino_select_topk_map_hw, wino_retina_decode_hw, wino_groupnorm_relu_hw,
  * wino_groupnorm_plan, WINO_GN_FORM_*, wino_fcos_score_map_hw, wino_fcos_decode_hw,
- * wino_keypoints_hw, WINO_KP_LAYOUT_*, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_keypoints_hw, WINO_KP_LAYOUT_*, wino_dwconv3x3_bn_act_hw, wino_dwconv3x3_plan, WINO_ACT_*,
+ * wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -1107,6 +1108,41 @@ int wino_fcos_score_map_hw(float* cls, const float* reg, int N, int h, int w, in
 int wino_fcos_decode_hw(const int* idx, int N, int k, long stride, long offset, const float* reg, int h, int w, int ld_r,
                         int A, int K, const float* base, int stride_y, int stride_x, const float* image_hw, float* boxes,
                         int* labels, wino_stream_t s);
+
+/* ---- depthwise 3x3 convolution + BN + activation (depthwise.hip) ---------------------------------------
+ *   out[n][y][x][c] = act(bnScale[c] * sum_{dy,dx} w_taps[dy][dx][c] * min(in[n][s y + dy][s x + dx][c], in_cap) + bnBias[c])
+ * stride s = 1 or 2, pad 1, no dilation: the 3x3 of MobileNet's inverted residual (groups = C, one filter per channel).
+ *   in      [N][Hin+2][Win+2][C] with a zero ring (what WINO_C_PADDED layers and the 3x3 layers write)
+ *   w_taps  [3][3][C]: torch's w[:, 0].permute(1, 2, 0) of the depthwise weight [C][1][3][3]; there is no pack kernel
+ *   bnBias, bnScale  [C], the library's order
+ *   out     [N][H+2][W+2][C], the result at [1..H][1..W], the ring written 0 by the same launch;
+ *           H = (Hin-1)/stride + 1, the same for W
+ *   act     WINO_ACT_NONE, WINO_ACT_RELU or WINO_ACT_RELU6 = min(max(y, 0), 6); both propagate NaN, as the library's
+ *           ReLU does
+ *   in_cap  an upper bound applied to every interior input value as it is loaded (NaN stays NaN, the ring is taken as
+ *           it is, so a zero ring stays zero under any cap); +inf switches it off.  A 1x1 layer launched with WINO_RELU
+ *           followed by this layer with in_cap = 6 is exactly relu6 between them: ReLU6 reaches the pointwise layers
+ *           without a flag on the GEMM kernels
+ * The nine products are accumulated by fma in tap order (0,0) .. (2,2) into an accumulator that starts at 0, then
+ * fma(bnScale, acc, bnBias), then the activation: every instantiation of the kernel gives the same bits.
+ * Constraints: C % 4 == 0 (a ragged last channel block is allowed), N >= 0 (0: WINO_OK, nothing launched), Hin, Win >= 1,
+ * one padded input image below 2^31 elements and at most 2^31 - 1 workgroups (WINO_E_SHAPE otherwise); every image is
+ * addressed from its own 64-bit base, so a map may pass 4 GiB.  A stride outside {1, 2}, an unknown act, a NaN in_cap,
+ * a NULL or not 16-byte-aligned pointer (the BN vectors included: they are read as quads), or an out that overlaps an
+ * operand is WINO_E_ARG.  Every check comes before the launch.  One launch, plain HIP off the matrix pipe (a contraction
+ * of length nine, nothing shared between channels); no stream scratch and no prepare: capturable as it is.
+ * wino_dwconv3x3_plan (host only) answers the launch the layer takes on a device of `cus` CUs, from the geometry the
+ * launcher itself reads: the kernel is one body compiled for stride x channel block, with
+ *   cb       64 or 16 channels per workgroup: 16 when the 64-channel grid would be fewer workgroups than `cus`
+ *            (WINO_DW_CB = 64 | 16 forces one)
+ *   tile_h, tile_w   output pixels of a workgroup's tile: 8 x 8, or 4 x 8 at stride 2 with cb = 64
+ *   tiles_y, tiles_x the tiles of one image
+ * and returns what the layer would for the shape. */
+enum { WINO_ACT_NONE = 0, WINO_ACT_RELU = 1, WINO_ACT_RELU6 = 2 };
+int wino_dwconv3x3_plan(int N, int Hin, int Win, int C, int stride, int cus, int* cb, int* tile_h, int* tile_w,
+                        int* tiles_y, int* tiles_x);
+int wino_dwconv3x3_bn_act_hw(const float* in, const float* w_taps, const float* bnBias, const float* bnScale, float* out,
+                             int N, int Hin, int Win, int C, int stride, int act, float in_cap, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */

@@ -210,3 +210,49 @@ def torch_vgg(sd, V, arch, dev):
                 t = torch.relu(t)
         return t
     return forward
+
+
+def mobilenet_state_dict(M, width_mult=1.0, classes=1000, seed=0):
+    """He-scaled convolutions (fan-in of the group), BN near identity, in mobilenet_v2's key names."""
+    g = torch.Generator().manual_seed(seed)
+    sd = {}
+    for k, shape in M.expected_keys(width_mult, classes).items():
+        if len(shape) > 1:
+            fan = shape[1] * (9 if len(shape) == 4 and shape[2] == 3 else 1)
+            sd[k] = torch.randn(shape, generator=g) * (2.0 / fan) ** 0.5
+        elif k.endswith((".running_var", ".weight")):
+            sd[k] = torch.rand(shape, generator=g) + 0.5
+        else:
+            sd[k] = (torch.rand(shape, generator=g) - 0.5) * 0.2
+    return sd
+
+
+def torch_mobilenet(sd, M, width_mult, dev, eps=1e-5):
+    """mobilenet_v2 as a function of the channels-last input: F.conv2d (groups read off the weight), BN as scale and
+    bias, clamp to [0, 6], the residual add, mean and linear."""
+    w = {k: v.to(dev).contiguous(memory_format=torch.channels_last) if v.dim() == 4 else v.to(dev) for k, v in sd.items()}
+    bn = {}
+    for k in sd:
+        if k.endswith("running_var"):
+            p = k[: -len(".running_var")]
+            s = sd[p + ".weight"] / torch.sqrt(sd[k] + eps)
+            bn[p] = (s.to(dev)[None, :, None, None], (sd[p + ".bias"] - sd[p + ".running_mean"] * s).to(dev)[None, :, None, None])
+    blks = M.blocks(width_mult)[1]
+
+    def cb(t, conv, norm, stride=1, pad=0, act=True):
+        s, b = bn[norm]
+        y = F.conv2d(t, w[conv + ".weight"], stride=stride, padding=pad, groups=t.shape[1] // w[conv + ".weight"].shape[1]) * s + b
+        return y.clamp_(0, 6) if act else y
+
+    def forward(x_cl):
+        t = cb(x_cl, "features.0.0", "features.0.1", 2, 1)
+        for i, cin, _, cout, st, e in blks:
+            p, j, y = f"features.{i}.conv", 0, t
+            if e != 1:
+                y, j = cb(y, f"{p}.0.0", f"{p}.0.1"), 1
+            y = cb(y, f"{p}.{j}.0", f"{p}.{j}.1", st, 1)
+            y = cb(y, f"{p}.{j + 1}", f"{p}.{j + 2}", act=False)
+            t = t + y if st == 1 and cin == cout else y
+        t = cb(t, "features.18.0", "features.18.1")
+        return F.linear(t.mean(dim=(2, 3)), w["classifier.1.weight"], w["classifier.1.bias"])
+    return forward
