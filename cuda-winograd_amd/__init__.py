@@ -1475,7 +1475,7 @@ def conv3x3_grouped_plan(N: int, Hin: int, Win: int, C: int, groups: int, stride
     return _plan_query("wino_conv3x3_grouped_plan", 4, int(N), int(Hin), int(Win), int(C), int(groups), int(stride))
 
 
-ACTS = {"none": 0, "relu": 1, "relu6": 2}   # WINO_ACT_*
+ACTS = {"none": 0, "relu": 1, "relu6": 2, "hardswish": 3, "hardsigmoid": 4}   # WINO_ACT_*
 
 
 def dwconv3x3_bn_act(x, w_taps, bias, scale, stride: int = 1, act: str = "relu6", in_cap=None, out=None) -> torch.Tensor:
@@ -1509,6 +1509,116 @@ def dwconv3x3_plan(N: int, Hin: int, Win: int, C: int, stride: int = 1, cus: int
     channels per workgroup (64, or 16 when 64 would launch fewer workgroups than `cus`; WINO_DW_CB = 64 | 16 forces one),
     the output tile of a workgroup and the tiles of one image.  Raises WinoError outside the layer's limits."""
     return _plan_query("wino_dwconv3x3_plan", 5, int(N), int(Hin), int(Win), int(C), int(stride), int(cus))
+
+
+def _act(act, what: str = "act") -> int:
+    act = "none" if act is None else act
+    if act not in ACTS:
+        raise WinoError(f"unknown {what} {act!r}: one of {sorted(ACTS)}")
+    return ACTS[act]
+
+
+def _cus(device) -> int:
+    return int(torch.cuda.get_device_properties(device).multi_processor_count)
+
+
+def dwconv_bn_act(x, w_taps, bias, scale, stride: int = 1, act="none", in_act=None, pool: bool = False, out=None,
+                  partials=None):
+    """Depthwise K x K conv, K = 3 or 5 (stride 1 or 2, pad K // 2) + folded BN + activation, one HIP launch
+    (depthwise_ex.hip): x [N][Hin+2][Win+2][C] (zero ring) -> out [N][H+2][W+2][C] (zero ring).  w_taps [K][K][C]: torch's
+    w[:, 0].permute(1, 2, 0).  act and in_act: "none" (None), "relu", "relu6" or "hardswish"; in_act is applied to every
+    interior input value as it is staged, so behind a 1x1 launched without activation it is that layer's activation.
+    pool=True: returns (out, partials), partials [N][tiles_y * tiles_x][C] the per-tile channel sums of what was stored
+    (dwconv_plan names the tiles on this device; `partials` is the caller's tensor for them); their sum over the tiles
+    over H W is the average pool, which fc_act forms.  C % 4 == 0.  No scratch: capturable as it is."""
+    x, w = _dev(x, "x"), _dev(w_taps, "w_taps")
+    b, s = _dev(bias, "bias"), _dev(scale, "scale")
+    if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+        raise WinoError("x must be [N][Hin+2][Win+2][C]")
+    N, Hin, Win, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    K = int(w.shape[0]) if w.dim() == 3 else 0
+    if w.dim() != 3 or tuple(w.shape) != (K, K, C):
+        raise WinoError(f"w_taps must be [K][K][{C}], got {tuple(w.shape)}")
+    if b.numel() != C or s.numel() != C:
+        raise WinoError("bn vectors do not match C")
+    a, ia = _act(act), _act(in_act, "in_act")
+    stride = int(stride)
+    H, W = _out_hw(Hin, Win, stride) if stride in (1, 2) else (Hin, Win)   # (the library refuses the stride)
+    out = _output(out, (N, H + 2, W + 2, C), x.device)
+    tiles, pp = 0, None
+    if pool or partials is not None:
+        _, _, _, ty, tx = dwconv_plan(N, Hin, Win, C, K, stride, _cus(x.device))
+        tiles = ty * tx
+        pp = _output(partials, (N, tiles, C), x.device, "partials")
+    _on_current_device(x, w, b, s, out, pp)
+    _check(lib().wino_dwconv_bn_act_hw(x.data_ptr(), w.data_ptr(), b.data_ptr(), s.data_ptr(), out.data_ptr(),
+                                       None if pp is None else pp.data_ptr(), N, Hin, Win, C, K, stride, a, ia, tiles,
+                                       _stream()), "wino_dwconv_bn_act_hw")
+    return out if pp is None else (out, pp)
+
+
+def dwconv_plan(N: int, Hin: int, Win: int, C: int, K: int = 3, stride: int = 1, cus: int = 256):
+    """(cb, tile_h, tile_w, tiles_y, tiles_x) of dwconv_bn_act's launch on a device of `cus` CUs (host-side), as
+    dwconv3x3_plan answers it for the 3x3: tiles_y * tiles_x is the number of pool partials per image."""
+    return _plan_query("wino_dwconv_plan", 5, int(N), int(Hin), int(Win), int(C), int(K), int(stride), int(cus))
+
+
+def fc_act(parts, W, b, act="none", x_scale: float = 1.0, out=None) -> torch.Tensor:
+    """out[n][j] = act(sum_c W[j][c] x[n][c] + b[j]) with x[n][c] = x_scale * sum_p parts[n][p][c], one HIP launch (se.hip):
+    parts [N][P][C] (or [N][C]), W [J][C] (torch's Linear layout, or a 1x1 weight [J][C][1][1]), b [J] -> out [N][J].
+    act: any of ACTS.  For a handful of rows (N up to a few dozen), C % 4 == 0, C <= 2048; W is read once per launch and a
+    row's bits do not depend on the batch."""
+    p, w, bb = _dev(parts, "parts"), _dev(W, "W"), _dev(b, "b")
+    if p.dim() == 2:
+        p = p[:, None, :]
+    if w.dim() == 4 and w.shape[2] == w.shape[3] == 1:
+        w = w[:, :, 0, 0]
+    if p.dim() != 3 or w.dim() != 2 or int(w.shape[1]) != int(p.shape[2]) or bb.numel() != int(w.shape[0]):
+        raise WinoError(f"fc_act: parts {tuple(p.shape)}, W {tuple(w.shape)} and b {tuple(bb.shape)} do not match")
+    N, P, C, J = int(p.shape[0]), int(p.shape[1]), int(p.shape[2]), int(w.shape[0])
+    out = _output(out, (N, J), p.device)
+    _on_current_device(p, w, bb, out)
+    _check(lib().wino_fc_act_hw(p.data_ptr(), float(x_scale), w.data_ptr(), bb.data_ptr(), out.data_ptr(), N, P, C, J,
+                                _act(act), _stream()), "wino_fc_act_hw")
+    return out
+
+
+def act_scale_pool_plan(N: int, H: int, W: int, C: int, padded: bool = False):
+    """(pix_chunk, parts) of act_scale_pool on an H x W map (host-side): the pixels of one pooled chunk and the number of
+    pool partials per image."""
+    return _plan_query("wino_act_scale_pool_plan", 2, int(N), int(H), int(W), int(C), int(bool(padded)))
+
+
+def act_scale_pool(x, act="none", gate=None, padded: bool = False, pool: bool = False, partials=None):
+    """In place x = act(x) * gate[n][c], one HIP launch (se.hip): x a flat map [N][H][W][C] (or [N][H W][C]) or, with
+    padded, [N][H+2][W+2][C] whose ring is left alone; gate [N][C] or None.  pool=True: returns (x, partials), partials
+    [N][parts][C] the channel sums of what was stored per chunk of pixels (act_scale_pool_plan)."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous():
+        raise WinoError("x must be a contiguous float32 CUDA(HIP) tensor: it is rewritten in place")
+    if padded:
+        if x.dim() != 4 or x.shape[1] < 3 or x.shape[2] < 3:
+            raise WinoError("padded: x must be [N][H+2][W+2][C]")
+        N, H, W, C = int(x.shape[0]), int(x.shape[1]) - 2, int(x.shape[2]) - 2, int(x.shape[3])
+    elif x.dim() == 4:
+        N, H, W, C = (int(v) for v in x.shape)
+    elif x.dim() == 3:
+        N, H, W, C = int(x.shape[0]), 1, int(x.shape[1]), int(x.shape[2])
+    else:
+        raise WinoError("x must be [N][H][W][C] or [N][H W][C]")
+    g = None
+    if gate is not None:
+        g = _dev(gate, "gate")
+        if tuple(g.shape) != (N, C):
+            raise WinoError(f"gate must be [{N}][{C}], got {tuple(g.shape)}")
+    parts, pp = 0, None
+    if pool or partials is not None:
+        parts = act_scale_pool_plan(N, H, W, C, padded)[1]
+        pp = _output(partials, (N, parts, C), x.device, "partials")
+    _on_current_device(x, g, pp)
+    _check(lib().wino_act_scale_pool_hw(x.data_ptr(), None if g is None else g.data_ptr(),
+                                        None if pp is None else pp.data_ptr(), N, H, W, C, int(bool(padded)), _act(act),
+                                        parts, _stream()), "wino_act_scale_pool_hw")
+    return x if pp is None else (x, pp)
 
 
 def grouped_residual_block_prepare(N: int, H: int, W: int, C4: int, Cm: int, groups: int) -> None:
@@ -1876,7 +1986,7 @@ def shard_range(N: int, rank: int, world: int) -> tuple[int, int]:
 
 from .resnet import ResNet  # noqa: E402  (whole networks on the operators above)
 from .vgg import VGG  # noqa: E402
-from .mobilenet import MobileNetV2  # noqa: E402
+from .mobilenet import MobileNetV2, MobileNetV3  # noqa: E402
 from .fpn import ResNetFPN  # noqa: E402
 from .segmentation import FCN, DeepLabV3  # noqa: E402
 from .detection import BoxHead, MaskHead, KeypointHead, RPN, FasterRCNN, MaskRCNN, KeypointRCNN  # noqa: E402

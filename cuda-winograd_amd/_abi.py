@@ -199,6 +199,12 @@ SIGNATURES = {
     # ---- depthwise 3x3 + BN + activation
     "wino_dwconv3x3_plan": (i, [i] * 6 + [ip] * 5),
     "wino_dwconv3x3_bn_act_hw": (i, [vp] * 5 + [i] * 6 + [c_float, vp]),
+    # ---- depthwise K x K (3 or 5) + BN + activation with pool partials; the squeeze-excite kernels
+    "wino_dwconv_plan": (i, [i] * 7 + [ip] * 5),
+    "wino_dwconv_bn_act_hw": (i, [vp] * 6 + [i] * 9 + [vp]),
+    "wino_fc_act_hw": (i, [vp, c_float] + [vp] * 3 + [i] * 5 + [vp]),
+    "wino_act_scale_pool_plan": (i, [i] * 5 + [ip] * 2),
+    "wino_act_scale_pool_hw": (i, [vp] * 3 + [i] * 7 + [vp]),
     # ---- diagnostics
     "wino_debug_reload_knobs": (i, []),
     "wino_debug_tickets_in_use": (i, [vp, POINTER(c_long)]),

@@ -99,7 +99,7 @@ struct Knobs {
   int stem_form;      // WINO_STEM_FORM: 0 automatic, 1 8x8-pool tiles x 64 channels, 2 4x4-pool tiles x 16 channels
   int roi_launch_tasks;   // WINO_ROI_LAUNCH_TASKS: most output positions (boxes x Q x Q) of one RoIAlign launch (<= 0: 2^31)
   int gn_form;        // WINO_GN_FORM: 0 automatic, 1 "whole" (one launch), 2 "split" (statistics, then apply)
-  int dw_cb;          // WINO_DW_CB: channels per workgroup of the depthwise 3x3, 64 / 16 (anything else = plan)
+  int dw_cb;          // WINO_DW_CB: channels per workgroup of the depthwise layers, 64 / 16 (anything else = plan)
 };
 Knobs knobs();
 #define WINO_HIP(call)                                          \

@@ -235,4 +235,6 @@ class MobileNetV2(Net):
         return self._logits, maps
 
 
-__all__ = ["MobileNetV2", "SETTING", "STAGES", "blocks", "expected_keys", "layer_shapes"]
+from .mobilenet_v3 import MobileNetV3  # noqa: E402  (mobilenet_v3.py: its block tables and expected_keys(arch, classes))
+
+__all__ = ["MobileNetV2", "MobileNetV3", "SETTING", "STAGES", "blocks", "expected_keys", "layer_shapes"]

@@ -71,7 +71,8 @@ extern "C" {
  * wino_select_topk_map_hw, wino_retina_decode_hw, wino_groupnorm_relu_hw,
  * wino_groupnorm_plan, WINO_GN_FORM_*, wino_fcos_score_map_hw, wino_fcos_decode_hw,
  * wino_keypoints_hw, WINO_KP_LAYOUT_*, wino_dwconv3x3_bn_act_hw, wino_dwconv3x3_plan, WINO_ACT_*,
- * wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
+ * wino_dwconv_bn_act_hw, wino_dwconv_plan, WINO_ACT_HARDSWISH, WINO_ACT_HARDSIGMOID, wino_fc_act_hw,
+ * wino_act_scale_pool_hw, wino_act_scale_pool_plan, wino_roi_align_hw.  The library-owned stream-K scratch is never freed or moved while its
  * stream lives (it used to be reallocated when a larger shape arrived).  wino_residual_block(_hw) now also check every
  * pointer and both 1x1 layers' shapes before their first launch, and they and wino_proj_block(_v15)_hw refuse a
  * workspace that overlaps x or out (WINO_E_ARG): such calls used to launch part of the block, or to return WINO_OK
@@ -1138,11 +1139,68 @@ int wino_fcos_decode_hw(const int* idx, int N, int k, long stride, long offset, 
  *   tile_h, tile_w   output pixels of a workgroup's tile: 8 x 8, or 4 x 8 at stride 2 with cb = 64
  *   tiles_y, tiles_x the tiles of one image
  * and returns what the layer would for the shape. */
-enum { WINO_ACT_NONE = 0, WINO_ACT_RELU = 1, WINO_ACT_RELU6 = 2 };
+enum { WINO_ACT_NONE = 0, WINO_ACT_RELU = 1, WINO_ACT_RELU6 = 2, WINO_ACT_HARDSWISH = 3, WINO_ACT_HARDSIGMOID = 4 };
 int wino_dwconv3x3_plan(int N, int Hin, int Win, int C, int stride, int cus, int* cb, int* tile_h, int* tile_w,
                         int* tiles_y, int* tiles_x);
 int wino_dwconv3x3_bn_act_hw(const float* in, const float* w_taps, const float* bnBias, const float* bnScale, float* out,
                              int N, int Hin, int Win, int C, int stride, int act, float in_cap, wino_stream_t s);
+
+/* ---- depthwise K x K convolution + BN + activation, K = 3 or 5 (depthwise_ex.hip) ----------------------
+ *   out[n][y][x][c] = act(bnScale[c] * sum_{dy,dx} w_taps[dy][dx][c] * in_act(in[n][s y + dy - K/2 + 1][s x + dx - K/2 + 1][c]) + bnBias[c])
+ * stride s = 1 or 2, pad K/2, no dilation: the depthwise layer of MobileNetV3's blocks.  The coordinates are those of
+ * the padded input; a position outside it (a 5 x 5 reaches two pixels past the interior, the maps carry a ring of one)
+ * counts as 0.  wino_dwconv3x3_bn_act_hw above is unchanged; this entry adds to it:
+ *   K        3 or 5; w_taps is [K][K][C], torch's w[:, 0].permute(1, 2, 0)
+ *   act, in_act  WINO_ACT_NONE, _RELU, _RELU6 or WINO_ACT_HARDSWISH = y * min(max(y + 3, 0), 6) * (1/6); all propagate NaN.
+ *            in_act is applied to every interior input value as it is staged (the ring is taken as read: all four
+ *            map 0 to 0): a 1x1 layer launched without an activation followed by this layer with in_act = HARDSWISH is
+ *            hardswish between them, without a flag on the GEMM kernels
+ *   pool_partials  NULL, or [N][tiles_y tiles_x][C]: row (n, ty tiles_x + tx) receives the per-channel sums of the outputs
+ *            (after the activation) that tile (ty, tx) of image n stored, added in a fixed order (no atomics: the same
+ *            bits every launch).  Their sum over the tiles divided by H W is the global average pool, which
+ *            wino_fc_act_hw forms.  pool_tiles must then be tiles_y tiles_x of the plan the launch takes (wino_dwconv_plan
+ *            with the device's CU count), WINO_E_ARG otherwise; it is not read when pool_partials is NULL
+ * WINO_ACT_HARDSIGMOID = min(max(y + 3, 0), 6) * (1/6) is for wino_fc_act_hw and wino_act_scale_pool_hw; here it is refused.
+ * Every accumulator starts at 0 and receives its K K products by fma in tap order (0,0) .. (K-1,K-1), then
+ * fma(bnScale, acc, bnBias), then the activation: every instantiation gives the same map bits (the partials of the two
+ * channel blocks may differ, their tiles do), and K = 3 with in_act = WINO_ACT_NONE and no pool gives the bits of
+ * wino_dwconv3x3_bn_act_hw with in_cap = +inf.  Constraints and refusals are that entry's: C % 4 == 0, N >= 0, Hin,
+ * Win >= 1, one padded input image below 2^31 elements, at most 2^31 - 1 workgroups (WINO_E_SHAPE); K, stride, act or
+ * in_act outside their sets, a NULL or not 16-byte-aligned pointer, a wrong pool_tiles, or out or pool_partials
+ * overlapping an operand or each other is WINO_E_ARG.  Every check comes before the launch.  One launch, no stream
+ * scratch, no prepare: capturable as it is.
+ * wino_dwconv_plan (host only) answers the launch on a device of `cus` CUs as wino_dwconv3x3_plan does, with the same
+ * rule between 64 and 16 channels per workgroup (WINO_DW_CB forces one) and the same tiles for both K: 8 x 8, or 4 x 8
+ * at stride 2 with cb = 64. */
+int wino_dwconv_plan(int N, int Hin, int Win, int C, int K, int stride, int cus, int* cb, int* tile_h, int* tile_w,
+                     int* tiles_y, int* tiles_x);
+int wino_dwconv_bn_act_hw(const float* in, const float* w_taps, const float* bnBias, const float* bnScale, float* out,
+                          float* pool_partials, int N, int Hin, int Win, int C, int K, int stride, int act, int in_act,
+                          int pool_tiles, wino_stream_t s);
+
+/* ---- squeeze-excite and classifier kernels (se.hip) ------------------------------------------------------
+ * wino_fc_act_hw: a fully connected layer for a handful of rows,
+ *   out[n][j] = act(sum_c W[j][c] * x[n][c] + b[j]),   x[n][c] = x_scale * (parts[n][0][c] + parts[n][1][c] + ..)
+ *   parts  [N][P][C]: P partial sums per image, added in index order (P = 1, x_scale = 1: a plain FC on [N][C]); with the
+ *          pool partials of wino_dwconv_bn_act_hw or wino_act_scale_pool_hw and x_scale = 1 / (H W), x is the average pool
+ *   W      [J][C], torch's Linear / 1x1 weight; b [J]; out [N][J]
+ *   act    any WINO_ACT_*
+ * W is read once per launch; an image's row has the same bits alone, inside a batch and anywhere in it.
+ * Constraints: N >= 0 (0: nothing launched), P, J >= 1, C % 4 == 0, 4 <= C <= 2048 (WINO_E_SHAPE); parts and W 16-byte
+ * aligned, out overlapping no operand, a known act (WINO_E_ARG).  No scratch: capturable as it is.
+ * wino_act_scale_pool_hw: in place, x[n][p][c] = act(x[n][p][c]) * gate[n][c] on a flat map [N][H W][C] (padded = 0) or
+ * on the interior of a padded one [N][H+2][W+2][C] (padded = 1; its ring is neither read nor written).
+ *   gate   [N][C], or NULL for no factor
+ *   pool_partials  NULL, or [N][parts][C]: the per-channel sums of what was stored over chunks of pix_chunk consecutive
+ *          pixels (row-major over the H x W interior), fixed order, no atomics; pool_parts must be the `parts` that
+ *          wino_act_scale_pool_plan answers for the map (ceil(H W / pix_chunk)), WINO_E_ARG otherwise
+ * Constraints: N >= 0, H, W >= 1, C % 4 == 0, one image below 2^31 elements (WINO_E_SHAPE); 16-byte-aligned pointers, no
+ * overlap between x, gate and pool_partials, a known act (WINO_E_ARG). */
+int wino_fc_act_hw(const float* parts, float x_scale, const float* W, const float* b, float* out, int N, int P, int C, int J,
+                   int act, wino_stream_t s);
+int wino_act_scale_pool_plan(int N, int H, int W, int C, int padded, int* pix_chunk, int* parts);
+int wino_act_scale_pool_hw(float* x, const float* gate, float* pool_partials, int N, int H, int W, int C, int padded, int act,
+                           int pool_parts, wino_stream_t s);
 
 /* ---- diagnostics (measurement infrastructure, not part of the reference interface) -------------
  * Re-reads the WINO_* developer knobs (the library reads them once per process). */
